@@ -1042,6 +1042,36 @@ def test_bench_line_contract():
     assert j["hbm_workspace_bytes"] == 3 * j["hbm_workspace_per_engine_bytes"] and "3 batches in flight" in j["timed_region"]
 
 
+def test_bench_dump_outputs_are_the_rows_of_the_timed_path(tmp_path):
+    """bench.py --dump-outputs DIR: the rows the last timed step returned (rows.npy: template, start, end, score;
+    read_row_offsets.npy) equal what the same stream path hands a caller for the same seeded reads, and a second run
+    with the same arguments writes the same bytes."""
+    args = ["--steps", "2", "--warmup", "1", "--reads", "120", "--no-cpu-baseline", "--timed-only"]
+    files = []
+    for k in range(2):
+        d = str(tmp_path / ("dump%d" % k))
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", d],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dumped_outputs"]["sampled"] is False
+        files.append({f: open(os.path.join(d, f), "rb").read() for f in ("rows.npy", "read_row_offsets.npy")})
+    assert files[0] == files[1]
+    rows, off = np.load(str(tmp_path / "dump0" / "rows.npy")), np.load(str(tmp_path / "dump0" / "read_row_offsets.npy"))
+    assert rows.dtype == np.float64 and off.dtype == np.float64
+    assert rows.shape == (j["rows_out_per_gpu"], 4) and off.shape == (121,) and off[0] == 0 and off[-1] == len(rows)
+    mn, ms = synth.make_monomers(12, seed=1)
+    rn, rs = synth.make_reads(ms, 120, read_len=50000, seed=1)
+    st = lib.Stream(ms, threads=8)
+    st.submit(rs)
+    per_read = st.collect(as_lists=True)
+    st.close()
+    assert np.diff(off).astype(np.int64).tolist() == [len(x) for x in per_read]
+    assert rows.astype(np.int64).tolist() == [list(r) for x in per_read for r in x]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("nm", [12, "12+legacy", 64, 140, "tiled"])
 def test_f16_range_guard_trips_and_the_batch_is_repeated_with_integer_cells(oracle, nm):

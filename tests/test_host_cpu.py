@@ -876,6 +876,45 @@ def test_committed_pmc_profile_belongs_to_these_kernel_sources():
         "kernel sources changed: rerun tools/profile_r02.sh + tools/reduce_pmc.py on the GPU box"
 
 
+def test_bench_dump_outputs_exact_and_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: the rows and per-read offsets a caller of the timed path receives (malloc'ed by the
+    library, freed by the writer) as float64 .npy files, exact and in the caller's order; past 64 MB in all, the same
+    seeded sample every time, with the indices it kept."""
+    import bench
+    libc = ctypes.CDLL(None)
+    libc.malloc.restype = ctypes.c_void_p
+    libc.malloc.argtypes = [ctypes.c_size_t]
+    rows = np.array([[5, 0, 170, 161], [17, 171, 340, -3], [2, 2 ** 31 - 2, 2 ** 31 - 1, 7]], dtype=np.int32)
+    off = np.array([0, 2, 2, 3], dtype=np.int64)
+    pr, po = libc.malloc(rows.nbytes), libc.malloc(off.nbytes)
+    ctypes.memmove(pr, rows.ctypes.data, rows.nbytes)
+    ctypes.memmove(po, off.ctypes.data, off.nbytes)
+    held = (lib.load(), ctypes.cast(pr, ctypes.POINTER(lib.Rec)), ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), 3, 3)
+    d = str(tmp_path / "small")
+    info = bench.write_held_outputs(d, held)
+    assert info["sampled"] is False and sorted(info["files"]) == ["read_row_offsets.npy", "rows.npy"]
+    got_rows, got_off = np.load(os.path.join(d, "rows.npy")), np.load(os.path.join(d, "read_row_offsets.npy"))
+    assert got_rows.dtype == np.float64 and got_rows.shape == (3, 4) and (got_rows == rows).all()
+    assert got_off.dtype == np.float64 and (got_off == off).all()
+
+    big = {"rows": np.arange(4 * 2300000, dtype=np.float64).reshape(-1, 4), "read_row_offsets": np.arange(5001.0)}
+    assert sum(a.nbytes for a in big.values()) > 64 * 2 ** 20
+    sizes, first = [], None
+    for k in range(2):
+        d = str(tmp_path / ("big%d" % k))
+        info = bench.write_outputs(d, big)
+        assert info["sampled"] is True
+        files = {f: open(os.path.join(d, f), "rb").read() for f in info["files"]}
+        sizes.append(sum(len(b) for b in files.values()))
+        if first is None:
+            first = files
+        assert files == first
+    assert max(sizes) <= 64 * 2 ** 20
+    idx = np.load(os.path.join(str(tmp_path / "big0"), "rows_index.npy"))
+    sample = np.load(os.path.join(str(tmp_path / "big0"), "rows.npy"))
+    assert len(idx) > 1600000 and (np.diff(idx) > 0).all() and (sample == big["rows"][idx.astype(np.int64)]).all()
+
+
 def test_packed_traceback_applies_up_to_256_bp_templates():
     """sd_plan_info's public trace_regs: the packed two-block traceback takes templates of up to 64 * 4 = 256 bp
     (ceil(L / 64) registers per lane); one base more and the one-block int32 form runs (trace_regs == 0)."""
