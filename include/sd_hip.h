@@ -86,7 +86,7 @@ void sd_free(void* p);               /* frees anything this library returned    
  * The file and chunk-range entry points (sd_run_files*, sd_decompose_files*, sd_decompose_chunk_range) also keep the
  * device pipeline of a finished job -- engines, streams, pinned staging and their device buffers, i.e. GIGABYTES of
  * HBM that other users of the GPU in this process or on this device do not see as free -- for the next job with the
- * same parameters and monomer set (at most two pipelines, none above SD_PIPE_CACHE_GB [96] GB, none whose engines had
+ * same parameters and monomer set (at most two pipelines per device entry, none above SD_PIPE_CACHE_GB [96] GB, none whose engines had
  * to leave their layout; SD_PIPE_CACHE_OFF=1 disables it).  sd_release_cache() destroys them too; nothing of either
  * cache is torn down at process exit. */
 void sd_release_cache(void);
@@ -191,6 +191,23 @@ int sd_run_files_records(const char* reads_fa, const char* monomers_fa, const sd
                          const char* final_tsv_out, const char* alt_tsv_out, const char* records_out,
                          int32_t min_identity, int32_t second_best, const double* lr_coef, char* errbuf,
                          size_t errlen);
+/* The whole CLI job on several devices of this process: one batch pipeline per entry of devices[0 .. n_devices)
+ * (p->device is ignored), the job's batches dealt to whichever pipeline frees a slot first, their records consumed
+ * strictly in batch order by the one per-read assembler and writer.  The three TSVs (and the record stream when
+ * records_out != NULL) are byte-identical to sd_run_files / sd_run_files_records with the same parameters.
+ * 1 <= n_devices <= 16; every ordinal must exist and be a gfx950 device, checked before any work starts on any of
+ * them (SD_ERR_PARAM / SD_ERR_NO_DEVICE, errbuf names the ordinal).  An ordinal may repeat: {0, 0} runs two
+ * pipelines on device 0 (how the form is tested on a machine with one GPU).  n_devices == 1 is sd_run_files_records
+ * on devices[0].  A HIP failure on one device ends the job with SD_ERR_HIP naming the device; the other pipelines are
+ * drained first. */
+int sd_run_files_devices(const char* reads_fa, const char* monomers_fa, const sd_params* p, const int32_t* devices,
+                         int32_t n_devices, const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
+                         const char* records_out, int32_t min_identity, int32_t second_best, const double* lr_coef,
+                         char* errbuf, size_t errlen);
+/* Per device entry of the last sd_run_files* call of this process (one entry for the single-device calls): batches
+ * dealt to it and its device busy time in ms (HIP-event spans of its batches), up to cap entries; returns the number
+ * of entries. */
+int sd_last_run_device_stats(int64_t* batches, double* busy_ms, int32_t cap);
 
 /* ---- chunk-range form: one job sharded over several GPUs, one process per GPU ---------------
  * The chunks of a read set (main.cpp:70-81, all reads, input order) form one global table; a chunk's
@@ -395,6 +412,12 @@ int sd_write_parts_selftest(const char* path, int32_t n_parts, int64_t part_byte
 /* Host only (CPU test): the pipeline-cache key (which jobs share cached engines) and the batch planner (how a job is cut
  * into device batches) against their contracts, without a device; SD_OK, or SD_ERR_INTERNAL with the broken property. */
 int sd_pipeline_logic_selftest(char* errbuf, size_t errlen);
+/* Self-test of the batch dealing of sd_run_files_devices (no device): the plan of 1..16 device entries cuts a chunk
+ * table into contiguous, covering batches of equal share, at least 2 x entries of them where the chunks allow; batches
+ * that complete on several threads in shuffled order are consumed strictly in batch order, slice by slice; a batch that
+ * fails on one pipeline (pushed, popped, or popped while it drains) ends the job on every driver thread with an in-order
+ * prefix consumed, and an aborted job releases every waiter.  SD_OK, or SD_ERR_INTERNAL with the broken property in errbuf. */
+int sd_multi_device_selftest(char* errbuf, size_t errlen);
 /* Rates of the host stages alone (no device): out[0] = chunk table + 2-bit packing, bp/s; out[1] = per-read
  * assembly (chunk offsets, seam merge) + raw TSV text of one synthetic record per 171 bases, bp/s; out[2] =
  * TSV rows/s; out[3] = bytes of text per pass.  p->threads host threads, `iters` passes over the reads. */

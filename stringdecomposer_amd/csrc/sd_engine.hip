@@ -1094,14 +1094,15 @@ int sd_engine_info(sd_engine* e, int64_t info[8]) {
 // Pipelines of finished jobs (sd_run_files, the chunk-range calls), kept for the next job with the same parameters and monomer set: creating
 // the engines (layout plan, tables, identity masks, streams, events, pinned staging) is 25-40 ms per call, a quarter of
 // a C4 --second-best job.  A process that decomposes many read sets against one monomer set (a service behind the
-// C-ABI, bench.py's steps) pays it once; sd_release_cache() drops them.  At most two are kept, none that holds more
+// C-ABI, bench.py's steps) pays it once; sd_release_cache() drops them.  At most two are kept per device entry (the
+// pipelines of an sd_run_files_devices job are keyed by ordinal and entry), none that holds more
 // than SD_PIPE_CACHE_GB (default 96) GB of device memory, and none whose engines left the layout they were created
 // with (a tripped fp16 guard, an overflowing filter-only batch: the next job should start from the plan again).
 // The entries are never destroyed at process exit (as g_pool / g_pinpool: the HIP runtime may be gone by then);
 // sd_release_cache() is the only place that tears them down.
 extern "C++" {
 namespace {
-struct PipeCacheEntry { std::string key; std::unique_ptr<Pipeline> pipe; };
+struct PipeCacheEntry { std::string key; std::unique_ptr<Pipeline> pipe; int entry; };
 struct PipeCache { std::mutex m; std::vector<PipeCacheEntry> v; };
 PipeCache& pipe_cache() { static PipeCache* c = new PipeCache; return *c; }   // leaked on purpose
 }  // namespace
@@ -1128,15 +1129,20 @@ std::unique_ptr<Pipeline> pipe_cache_take(const std::string& key) {
         }
     return nullptr;
 }
-void pipe_cache_give(const std::string& key, std::unique_ptr<Pipeline> q) {
+void pipe_cache_give(const std::string& key, std::unique_ptr<Pipeline> q, int entry) {
     static const size_t cap = [] { const char* e = getenv("SD_PIPE_CACHE_GB"); return (size_t)(e ? std::max(0, atoi(e)) : 96) << 30; }();
     if (!q || q->degraded() || q->held_bytes() > cap) return;   // (destroyed here, outside the lock)
     std::vector<PipeCacheEntry> drop;   // destroyed outside the lock
     {
         PipeCache& c = pipe_cache();
         std::lock_guard<std::mutex> g(c.m);
-        c.v.push_back(PipeCacheEntry{key, std::move(q)});
-        while (c.v.size() > 2) { drop.push_back(std::move(c.v.front())); c.v.erase(c.v.begin()); }
+        c.v.push_back(PipeCacheEntry{key, std::move(q), entry});
+        // at most two per device entry (sd_run_files_devices keeps one pipeline per entry of its device list)
+        size_t same = 0;
+        for (const PipeCacheEntry& x : c.v) same += x.entry == entry;
+        for (size_t i = 0; same > 2 && i < c.v.size();)
+            if (c.v[i].entry == entry) { drop.push_back(std::move(c.v[i])); c.v.erase(c.v.begin() + (long)i); --same; }
+            else ++i;
     }
 }
 void pipe_cache_clear() {

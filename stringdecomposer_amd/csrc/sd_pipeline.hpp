@@ -784,7 +784,7 @@ inline int64_t fresh_row_budget(int64_t budget, int64_t job_rows) {
 // ---- pipelines kept between jobs (sd_engine.hip) ----------------------------------------------------------------
 std::string pipe_cache_key(const sd_params& pe, char kind, const std::vector<const char*>& mseq, const std::vector<int32_t>& mlen);
 std::unique_ptr<Pipeline> pipe_cache_take(const std::string& key);
-void pipe_cache_give(const std::string& key, std::unique_ptr<Pipeline> q);
+void pipe_cache_give(const std::string& key, std::unique_ptr<Pipeline> q, int entry = 0);   // entry: of a device list
 void pipe_cache_clear();
 void text_pool_clear();      // (sd_run_files.hip: the text buffers sd_run_files keeps between jobs)
 

@@ -48,17 +48,121 @@ static TextPool& g_textpool_ref() { static TextPool* p = new TextPool; return *p
 #define g_textpool g_textpool_ref()
 extern "C++" void text_pool_clear() { g_textpool.clear(); }
 
+// per device entry of the last call (sd_last_run_device_stats): batches dealt to it, device busy ms
+static constexpr int kMaxDevices = 16;
+static int g_last_ndev = 0;
+static int64_t g_last_dev_batches[kMaxDevices] = {0};
+static double g_last_dev_busy[kMaxDevices] = {0};
+
+// Several devices in one process (sd_run_files_devices): every pipeline hands its batches to the assembler from its own
+// host thread, and this makes them take turns in batch order -- batch b's records (every slice of them) reach the
+// assembler only after all of batch b - 1's have.  A pipeline pops its batches in the order it was dealt them, and it is
+// always dealt the lowest batch nobody has, so the thread that holds the batch whose turn it is never waits for another.
+// abort() (a failed pipeline) releases every waiter; their records are dropped.
+struct BatchTurns {
+    std::mutex m;
+    std::condition_variable cv;
+    size_t turn = 0;
+    bool aborted = false;
+    bool wait(size_t b) {   // false: the job was aborted
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return aborted || turn == b; });
+        return !aborted;
+    }
+    void done(size_t b) {   // the last slice of batch b was consumed
+        {
+            std::lock_guard<std::mutex> g(m);
+            if (turn == b) turn = b + 1;
+        }
+        cv.notify_all();
+    }
+    void abort() {
+        {
+            std::lock_guard<std::mutex> g(m);
+            aborted = true;
+        }
+        cv.notify_all();
+    }
+    bool is_aborted() {
+        std::lock_guard<std::mutex> g(m);
+        return aborted;
+    }
+};
+
+// One driver thread of sd_run_files_devices: push(b) deals batch b to the entry's pipeline (whose sinks take their turns
+// in `turns`) until the batches run out, the job has failed somewhere (turns aborted, the writer failed) or this pipeline
+// fails; then the pipeline is drained.  A pop that fails drops its batch before the batch's last slice reaches the
+// assembler, so every batch behind it -- in this pipeline and in the others -- would wait for that turn forever: the
+// turns are aborted at once, and the rest is drained with sinks that return at once.  (Pipe: Pipeline, or the host-only
+// model of sd_multi_device_selftest.)  Returns the first error of this entry; dealt counts the batches it took.
+extern "C++" template <class Pipe, class Push>
+static int drive_entry(Pipe& pq, BatchTurns& turns, std::atomic<size_t>& next_batch, size_t n_batches,
+                       const std::atomic<int>& sink_rc, Push&& push, int64_t& dealt) {
+    int r = SD_OK;
+    while (r == SD_OK && sink_rc.load() == SD_OK && !turns.is_aborted()) {
+        const size_t b = next_batch.fetch_add(1);
+        if (b >= n_batches) break;
+        r = push(b);
+        if (r == SD_OK) ++dealt;
+        else turns.abort();   // (this batch, or the one a full pipeline popped for it, never reaches its sink)
+    }
+    while (pq.inflight() > 0) {
+        const int e = pq.pop();
+        if (e) {
+            if (r == SD_OK) r = e;
+            turns.abort();
+        }
+    }
+    return r;
+}
+
+// The batches of a job on n_dev pipelines: at least min_batches and 2 * n_dev of them (as far as the chunks go), so that
+// every pipeline gets work and the last batch to finish is short, cut where the cumulative rows cross k / nb of the
+// total -- equal shares up to one chunk -- and none of several chunks above the budget.
+static void plan_device_batches(const std::vector<CRef>& table, int64_t budget, int min_batches, int n_dev,
+                                std::vector<std::pair<size_t, size_t>>& out) {
+    out.clear();
+    const size_t n = table.size();
+    if (n == 0) return;
+    std::vector<int64_t> cum(n + 1, 0);
+    int64_t lmax = 1;
+    for (size_t c = 0; c < n; ++c) { cum[c + 1] = cum[c] + table[c].len; lmax = std::max<int64_t>(lmax, table[c].len); }
+    budget = std::max<int64_t>(budget, 1);
+    const int64_t holds = std::max<int64_t>(1, budget - (lmax - 1));
+    size_t nb = std::max<size_t>({(size_t)std::max(min_batches, 1), (size_t)2 * (size_t)std::max(n_dev, 1),
+                                  (size_t)((cum[n] + holds - 1) / holds)});
+    for (nb = std::min(nb, n);; nb = std::min(nb + 1, n)) {
+        out.clear();
+        bool fits = true;
+        size_t c0 = 0;
+        for (size_t k = 1; k <= nb; ++k) {
+            const int64_t want = (int64_t)((__int128)cum[n] * (int64_t)k / (int64_t)nb);
+            size_t c1 = k == nb ? n : (size_t)(std::lower_bound(cum.begin(), cum.end(), want) - cum.begin());
+            c1 = std::min(std::max(c1, c0 + 1), n - (nb - k));
+            if (c1 - c0 > 1 && cum[c1] - cum[c0] > budget) fits = false;
+            out.emplace_back(c0, c1);
+            c0 = c1;
+        }
+        if (fits || nb == n) return;
+    }
+}
+
 static int run_files_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank, int32_t world,
                           const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
                           int32_t min_identity, int32_t second_best, const double* lr_coef, int64_t* info,
-                          char* errbuf, size_t errlen, const char* records_out = nullptr) {
+                          char* errbuf, size_t errlen, const char* records_out = nullptr,
+                          const std::vector<int32_t>* devs = nullptr) {
     std::string err;
+    // devs (sd_run_files_devices, two or more entries): one pipeline per entry, batches dealt and consumed in order below
+    const int nd = devs ? (int)devs->size() : 1;
+    const bool multi = nd > 1;
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     if (!reads_fa || !monomers_fa || !raw_tsv_out || !final_tsv_out || !alt_tsv_out || !lr_coef || world < 1 || rank < 0 ||
         rank >= world)
         return SD_ERR_PARAM;
     if (records_out && world != 1) { set_err(errbuf, errlen, "the record stream is written by a single process"); return SD_ERR_PARAM; }
+    if (multi && world != 1) return SD_ERR_PARAM;
     const bool timing = getenv("SD_TIMING") != nullptr;
     const double t_begin = now_s();
     double t_prev = t_begin;
@@ -129,7 +233,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     if (info) { info[0] = (int64_t)r_lo; info[1] = (int64_t)r_hi; info[2] = (int64_t)all_reads.size(); info[3] = 0; }
     TemplateSet ts(monos);
     sd::PostProcessor pp;
-    rc = pp.init(monos, min_identity, second_best != 0, lr_coef, p->device, p->threads, err);
+    rc = pp.init(monos, min_identity, second_best != 0, lr_coef, multi ? (*devs)[0] : p->device, p->threads, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     // the three outputs as plain descriptors: every batch's text is written by all host threads with pwrite at its
     // offset (sd::write_parts) -- the copy into the page cache is what a 300-MB _alt batch costs
@@ -254,29 +358,71 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     }
     // identities of the final TSV in-stream, behind every batch's compaction (sd_ident.hip); template sets the kernel
     // does not take (and SD_IDENT_STREAM=0, developer A/B) leave them to the post-processing as in round 2
-    bool stream_ident;
-    std::string pkey;
+    std::atomic<bool> stream_ident{false};
+    std::vector<std::string> pkeys((size_t)nd);
     {
         sd_params pe = *p;
         apply_env_overrides(pe);
         stream_ident = !(pe.reserved[1] & SD_FLAG_NO_STREAM_IDENT);
-        pkey = pipe_cache_key(pe, second_best ? '2' : '1', ts.mseq, ts.mlen);   // (host threads do not shape an engine)
+        for (int i = 0; i < nd; ++i) {   // (multi: keyed by the entry's device and, beyond the first, its index)
+            if (multi) pe.device = (*devs)[(size_t)i];
+            pkeys[(size_t)i] = pipe_cache_key(pe, second_best ? '2' : '1', ts.mseq, ts.mlen);   // (host threads do not shape an engine)
+            if (i > 0) pkeys[(size_t)i] += "#entry " + std::to_string(i);
+        }
     }
-    std::unique_ptr<Pipeline> pipe_h = getenv("SD_PIPE_CACHE_OFF") ? nullptr : pipe_cache_take(pkey);
-    const bool reused = pipe_h != nullptr;
-    if (!pipe_h) pipe_h.reset(new Pipeline);
-    Pipeline& pipe = *pipe_h;
-    pipe.restart_idle = true;
-    pipe.on_engine = [&](sd_engine* e) {
+    std::vector<std::unique_ptr<Pipeline>> pipes((size_t)nd);
+    std::vector<char> from_cache((size_t)nd, 0);
+    std::vector<int64_t> entry_budget((size_t)nd, 0);
+    std::vector<std::string> entry_err((size_t)nd);
+    auto on_engine = [&](sd_engine* e) {
         if (stream_ident && !engine_set_identity(e, pp.interleaved_seqs(), pp.own_interleaved(), second_best != 0)) stream_ident = false;
     };
-    if (reused) {
-        pipe.begin_job(p, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-        stream_ident = stream_ident && pipe.ident_ok;
+    // the pipeline of entry i, from the cache or new; in a multi-device job on a thread bound to the entry's device
+    auto open_pipe = [&](int i) -> int {
+        sd_params pi = *p;
+        if (multi) pi.device = (*devs)[(size_t)i];
+        std::unique_ptr<Pipeline>& h = pipes[(size_t)i];
+        h = getenv("SD_PIPE_CACHE_OFF") ? nullptr : pipe_cache_take(pkeys[(size_t)i]);
+        from_cache[(size_t)i] = h != nullptr;
+        if (!h) h.reset(new Pipeline);
+        h->restart_idle = true;
+        h->on_engine = on_engine;
+        if (from_cache[(size_t)i]) {
+            h->begin_job(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
+            if (!h->ident_ok) stream_ident = false;
+            return SD_OK;
+        }
+        const int r = h->create(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
+        if (r) entry_err[(size_t)i] = h->eb;
+        return r;
+    };
+    if (!multi) {
+        rc = open_pipe(0);
+        if (rc) err = entry_err[0];
     } else {
-        rc = pipe.create(p, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-        if (rc) err = pipe.eb;
+        // the pipelines are created side by side, each on a thread bound to its device (hipSetDevice is per host thread)
+        std::vector<int> crc((size_t)nd, SD_OK);
+        std::vector<std::thread> th;
+        for (int i = 0; i < nd; ++i)
+            th.emplace_back([&, i]() {
+                const int dev = (*devs)[(size_t)i];
+                if (hipSetDevice(dev) != hipSuccess) {
+                    (void)hipGetLastError();
+                    pipes[(size_t)i].reset(new Pipeline);
+                    crc[(size_t)i] = SD_ERR_HIP;
+                    entry_err[(size_t)i] = "hipSetDevice failed";
+                    return;
+                }
+                crc[(size_t)i] = open_pipe(i);
+                if (crc[(size_t)i] == SD_OK) entry_budget[(size_t)i] = pipes[(size_t)i]->row_budget();   // (hipMemGetInfo of this device)
+            });
+        for (std::thread& t : th) t.join();
+        for (int i = 0; i < nd && rc == SD_OK; ++i)
+            if (crc[(size_t)i]) { rc = crc[(size_t)i]; err = "device " + std::to_string((*devs)[(size_t)i]) + ": " + entry_err[(size_t)i]; }
     }
+    Pipeline& pipe = *pipes[0];
+    bool reused = true;
+    for (char c : from_cache) reused = reused && c;
     lap(reused ? "pipeline from the cache" : "engine (HIP runtime start, layout plan, tables, identity masks)");
     if (stream_ident) job.per = second_best ? (int)pp.interleaved_seqs().size() : 1;
     std::vector<std::pair<size_t, size_t>> batches;
@@ -300,7 +446,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         min_batches = std::max(min_batches, nc >= 4096 ? 8 : nc >= 1024 ? 4 : 1);
     }
     if (const char* ev = getenv("SD_MIN_BATCHES")) min_batches = std::max(1, atoi(ev));   // developer A/B
-    if (rc == SD_OK) {
+    if (rc == SD_OK && !multi) {
         int64_t budget = pipe.row_budget();
         if (!reused) {
             int64_t rows = 0;
@@ -308,6 +454,23 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
             if (rows > budget) budget = fresh_row_budget(budget, rows);   // many batches: smaller ones, smaller engines
         }
         plan_batches(job.table, 0, job.table.size(), budget, min_batches, batches);
+    } else if (rc == SD_OK) {
+        // every entry's budget, its device's free HBM shared with the other entries on that device (an explicit cap
+        // stays as it is); the job takes the smallest
+        int64_t budget = INT64_MAX;
+        for (int i = 0; i < nd; ++i) {
+            int64_t b = entry_budget[(size_t)i];
+            int same = 0;
+            for (int j = 0; j < nd; ++j) same += (*devs)[(size_t)j] == (*devs)[(size_t)i];
+            if (p->max_batch_rows <= 0 && !getenv("SD_BATCH_ROWS")) b = std::max<int64_t>(b / same, (int64_t)p->part_size + p->overlap);
+            budget = std::min(budget, b);
+        }
+        if (!reused) {
+            int64_t rows = 0;
+            for (const CRef& c : job.table) rows += c.len;
+            if (rows > budget) budget = fresh_row_budget(budget, rows);
+        }
+        plan_device_batches(job.table, budget, min_batches, nd, batches);
     }
     lap("batch plan");
     const double t_setup = now_s() - t_begin;
@@ -447,13 +610,13 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     };
     std::thread sink_thread(sink_loop);
     std::thread io_thread(io_loop);
-    auto sink = [&](size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff) {
+    auto sink = [&](Pipeline& pq, size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff) {
         if (sink_rc.load()) return;
         const size_t r0 = job.next_read;
         job.n_rows = 0;
         job.row_off[r0] = 0;
-        job.bid = pipe.cur_ident.id;
-        job.bidh = pipe.cur_ident.idh;
+        job.bid = pq.cur_ident.id;
+        job.bidh = pq.cur_ident.idh;
         job.add(c0, c1, recs, roff);
         if (job.oom) { sink_fail(SD_ERR_INTERNAL, "out of host memory"); return; }
         const size_t r1 = job.next_read;
@@ -473,7 +636,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         job.xid.clear();
         job.xidh.clear();
         w.ident = Pipeline::IdentOut{};
-        if (w.have_ident && job.bid) w.ident = pipe.take_ident();   // the rows point into the batch's pinned arrays
+        if (w.have_ident && job.bid) w.ident = pq.take_ident();   // the rows point into the batch's pinned arrays
         job.ident_ok = job.carry.empty() || job.bid != nullptr;
         job.rows = nullptr;       // the next batch assembles into a fresh (or recycled) buffer
         job.cap_rows = 0;
@@ -484,9 +647,8 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         lk.unlock();
         wq_cv.notify_all();
     };
-    std::vector<const char*> cptr;
-    std::vector<int32_t> clen;
-    for (size_t b = 0; b < batches.size() && rc == SD_OK && sink_rc.load() == SD_OK; ++b) {
+    // the chunks of batch b and the cut of its identities into slices
+    auto batch_input = [&](size_t b, std::vector<const char*>& cptr, std::vector<int32_t>& clen, std::vector<int>& slice_end) {
         const size_t c0 = batches[b].first, c1 = batches[b].second;
         cptr.clear();
         clen.clear();
@@ -494,7 +656,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
             cptr.push_back(reads[(size_t)job.table[c].read].seq + job.table[c].off);
             clen.push_back(job.table[c].len);
         }
-        std::vector<int> slice_end;
+        slice_end.clear();
         if (slice_ident && stream_ident) {
             // up to eight slices of at least 256 chunks, each ending with a read (a read that ends in a later slice would
             // only be carried; the last slice ends the batch)
@@ -510,12 +672,59 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
             }
             if (slice_end.empty() || slice_end.back() != (int)nb) slice_end.push_back((int)nb);
         }
-        rc = pipe.push(cptr, clen, [&sink, c0](const sd_rec* r, const int64_t* ro, size_t first, size_t n) { sink(c0 + first, c0 + first + n, r, ro); },
-                       slice_end);
-        if (rc) err = pipe.eb;
+    };
+    std::vector<int64_t> dealt((size_t)nd, 0);   // batches per entry
+    if (!multi) {
+        std::vector<const char*> cptr;
+        std::vector<int32_t> clen;
+        std::vector<int> slice_end;
+        for (size_t b = 0; b < batches.size() && rc == SD_OK && sink_rc.load() == SD_OK; ++b) {
+            const size_t c0 = batches[b].first;
+            batch_input(b, cptr, clen, slice_end);
+            rc = pipe.push(cptr, clen, [&sink, &pipe, c0](const sd_rec* r, const int64_t* ro, size_t first, size_t n) { sink(pipe, c0 + first, c0 + first + n, r, ro); },
+                           slice_end);
+            if (rc) err = pipe.eb;
+            else ++dealt[0];
+        }
+        const int rc2 = pipe.drain();
+        if (rc == SD_OK && rc2) { rc = rc2; err = pipe.eb; }
+    } else if (rc == SD_OK) {
+        // One driver thread per entry, bound to its device: it takes the next batch nobody has whenever its pipeline can
+        // take one (a pipeline pushes until all its slots are busy, then waits for its oldest batch), and hands its
+        // batches' records to the assembler in batch order (BatchTurns).  Every HIP call of a pipeline -- engines,
+        // streams, events, copies, identity slices -- is made on its driver thread; the sink and writer threads make none.
+        BatchTurns turns;
+        std::atomic<size_t> next_batch{0};
+        std::vector<int> drc((size_t)nd, SD_OK);
+        std::vector<std::thread> drivers;
+        for (int i = 0; i < nd; ++i)
+            drivers.emplace_back([&, i]() {
+                Pipeline& pq = *pipes[(size_t)i];
+                int r = hipSetDevice((*devs)[(size_t)i]) == hipSuccess ? SD_OK : SD_ERR_HIP;
+                if (r) {
+                    (void)hipGetLastError();
+                    std::snprintf(pq.eb, sizeof pq.eb, "hipSetDevice failed");
+                    turns.abort();
+                    drc[(size_t)i] = r;
+                    return;
+                }
+                std::vector<const char*> cptr;
+                std::vector<int32_t> clen;
+                std::vector<int> slice_end;
+                auto push = [&](size_t b) {
+                    const size_t c0 = batches[b].first, c1 = batches[b].second;
+                    batch_input(b, cptr, clen, slice_end);
+                    return pq.push(cptr, clen, [&sink, &pq, &turns, b, c0, c1](const sd_rec* rr, const int64_t* ro, size_t first, size_t n) {
+                        if (turns.wait(b)) sink(pq, c0 + first, c0 + first + n, rr, ro);
+                        if (c0 + first + n == c1) turns.done(b);
+                    }, slice_end);
+                };
+                drc[(size_t)i] = drive_entry(pq, turns, next_batch, batches.size(), sink_rc, push, dealt[(size_t)i]);
+            });
+        for (std::thread& t : drivers) t.join();
+        for (int i = 0; i < nd && rc == SD_OK; ++i)
+            if (drc[(size_t)i]) { rc = drc[(size_t)i]; err = "device " + std::to_string((*devs)[(size_t)i]) + ": " + pipes[(size_t)i]->eb; }
     }
-    const int rc2 = pipe.drain();
-    if (rc == SD_OK && rc2) { rc = rc2; err = pipe.eb; }
     {
         std::lock_guard<std::mutex> lk(wq_m);
         wq_done = true;
@@ -532,9 +741,12 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     end_prealloc();
     if (!close_all() && rc == SD_OK) { rc = SD_ERR_IO; err = std::string("short write to ") + raw_tsv_out; }
     if (records_out && rc == SD_OK) rc = rec_w.close(err, records_out);
+    // kernel times, batches and host stage times summed over the pipelines (one unless several devices)
+    auto total = [&](double (*f)(const Pipeline&)) { double t = 0; for (const auto& q : pipes) t += f(*q); return t; };
+    const double s_pack = total([](const Pipeline& q) { return q.pack_s; }), s_wait = total([](const Pipeline& q) { return q.wait_s; });
     if (timing)
         std::fprintf(stderr, "[sd timing] %zu batches: pack+enqueue %.1f ms, wait %.1f ms, raw text %.1f ms, post-processing %.1f ms, "
-                     "file writes %.1f ms, total %.1f ms\n", batches.size(), pipe.pack_s * 1e3, pipe.wait_s * 1e3, t_fmt * 1e3,
+                     "file writes %.1f ms, total %.1f ms\n", batches.size(), s_pack * 1e3, s_wait * 1e3, t_fmt * 1e3,
                      t_post * 1e3, t_io * 1e3, (now_s() - t_begin) * 1e3);
     if (timing)
         std::fprintf(stderr, "[sd timing] of which device / pinned allocations (hipMalloc, hipHostMalloc): %.1f ms\n", (double)g_alloc_ns.load() / 1e6);
@@ -543,11 +755,17 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
                      pp.t_prepare * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, pp.t_concat * 1e3);
     {
         std::lock_guard<std::mutex> lk(g_last_m);
-        const double v[24] = {pipe.fill_ms, pipe.trace_ms, pipe.compact_ms, pipe.ident_ms, (double)pipe.ident_pairs,
-                              (double)pipe.batches, (double)pipe.rows, pipe.pack_s * 1e3, pipe.wait_s * 1e3, t_fmt * 1e3,
+        const double v[24] = {total([](const Pipeline& q) { return q.fill_ms; }), total([](const Pipeline& q) { return q.trace_ms; }),
+                              total([](const Pipeline& q) { return q.compact_ms; }), total([](const Pipeline& q) { return q.ident_ms; }),
+                              total([](const Pipeline& q) { return (double)q.ident_pairs; }), total([](const Pipeline& q) { return (double)q.batches; }),
+                              total([](const Pipeline& q) { return (double)q.rows; }), s_pack * 1e3, s_wait * 1e3, t_fmt * 1e3,
                               t_post * 1e3, t_io * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, (now_s() - t_begin) * 1e3,
-                              (double)g_alloc_ns.load() / 1e6, t_setup * 1e3, pipe.sink_s * 1e3, (double)pipe.homo_pairs, (double)pipe.homo_full_pairs, 0, 0, 0, 0};
+                              (double)g_alloc_ns.load() / 1e6, t_setup * 1e3, total([](const Pipeline& q) { return q.sink_s; }) * 1e3,
+                              total([](const Pipeline& q) { return (double)q.homo_pairs; }),
+                              total([](const Pipeline& q) { return (double)q.homo_full_pairs; }), 0, 0, 0, 0};
         std::memcpy(g_last_run, v, sizeof v);
+        g_last_ndev = std::min(nd, kMaxDevices);
+        for (int i = 0; i < g_last_ndev; ++i) { g_last_dev_batches[i] = dealt[(size_t)i]; g_last_dev_busy[i] = pipes[(size_t)i]->run_ms; }
     }
     if (timing) {
         double nw[4];
@@ -555,9 +773,11 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         std::fprintf(stderr, "[sd timing] identities on the device: preparation + staging %.1f ms, uploads %.1f ms, launch %.1f ms, "
                      "kernel + downloads %.1f ms\n", nw[0] * 1e3, nw[1] * 1e3, nw[2] * 1e3, nw[3] * 1e3);
     }
-    pipe.ident_ok = stream_ident;
-    pipe.on_engine = nullptr;   // (it refers to this call's locals)
-    if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkey, std::move(pipe_h));
+    for (int i = 0; i < nd; ++i) {
+        pipes[(size_t)i]->ident_ok = stream_ident;
+        pipes[(size_t)i]->on_engine = nullptr;   // (it refers to this call's locals)
+        if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkeys[(size_t)i], std::move(pipes[(size_t)i]), i);
+    }
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     return SD_OK;
 }
@@ -586,6 +806,212 @@ int sd_run_files_range(const char* reads_fa, const char* monomers_fa, const sd_p
                        int32_t second_best, const double* lr_coef, int64_t* info, char* errbuf, size_t errlen) {
     return run_files_impl(reads_fa, monomers_fa, p, rank, world, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity,
                           second_best, lr_coef, info, errbuf, errlen);
+}
+
+int sd_run_files_devices(const char* reads_fa, const char* monomers_fa, const sd_params* p, const int32_t* devices,
+                         int32_t n_devices, const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
+                         const char* records_out, int32_t min_identity, int32_t second_best, const double* lr_coef,
+                         char* errbuf, size_t errlen) {
+    // the device list is checked completely before anything is started on any of its devices
+    if (!p || !devices || n_devices < 1 || n_devices > kMaxDevices) {
+        set_err(errbuf, errlen, "sd_run_files_devices: 1 to " + std::to_string(kMaxDevices) + " device entries");
+        return SD_ERR_PARAM;
+    }
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }
+    static std::atomic<int> arch_ok[64];   // per ordinal: 0 not looked at, 1 gfx950, 2 another chip
+    for (int32_t i = 0; i < n_devices; ++i) {
+        const int32_t d = devices[i];
+        if (d < 0 || d >= count) {
+            set_err(errbuf, errlen, "device " + std::to_string(d) + " does not exist (" + std::to_string(count) + " HIP devices visible)");
+            return d < 0 ? SD_ERR_PARAM : SD_ERR_NO_DEVICE;
+        }
+        int known = d < 64 ? arch_ok[d].load() : 0;
+        if (known == 0) {
+            hipDeviceProp_t prop;
+            if (hipGetDeviceProperties(&prop, d) != hipSuccess) { (void)hipGetLastError(); known = 2; }
+            else known = std::strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : 2;
+            if (d < 64) arch_ok[d].store(known);
+        }
+        if (known != 1) {
+            set_err(errbuf, errlen, "device " + std::to_string(d) + " is not a gfx950 device");
+            return SD_ERR_NO_DEVICE;
+        }
+    }
+    sd_params q = *p;
+    q.device = devices[0];
+    if (n_devices == 1)   // the single-device path as it is, pipeline cache included
+        return run_files_impl(reads_fa, monomers_fa, &q, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
+                              lr_coef, nullptr, errbuf, errlen, records_out);
+    const std::vector<int32_t> devs(devices, devices + n_devices);
+    return run_files_impl(reads_fa, monomers_fa, &q, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
+                          lr_coef, nullptr, errbuf, errlen, records_out, &devs);
+}
+
+int sd_last_run_device_stats(int64_t* batches, double* busy_ms, int32_t cap) {
+    std::lock_guard<std::mutex> lk(g_last_m);
+    for (int i = 0; i < g_last_ndev && i < cap; ++i) {
+        if (batches) batches[i] = g_last_dev_batches[i];
+        if (busy_ms) busy_ms[i] = g_last_dev_busy[i];
+    }
+    return g_last_ndev;
+}
+
+// Host only (CPU test): the dealing of sd_run_files_devices against its contract -- plan_device_batches and BatchTurns
+// as the job uses them, without a device.
+int sd_multi_device_selftest(char* errbuf, size_t errlen) {
+    auto fail = [&](const std::string& m) { set_err(errbuf, errlen, m); return SD_ERR_INTERNAL; };
+    uint64_t rng = 0x2545F4914F6CDD1Dull;
+    auto rnd = [&](uint64_t n) { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (uint64_t)(rng % n); };
+    // (1) plans: contiguous, covering, non-empty; at least 2N batches (and min_batches) where the chunks allow; no batch of
+    // several chunks above the budget; equal chunks: batch sizes differ by at most one chunk
+    for (int nd = 1; nd <= kMaxDevices; ++nd)
+        for (int trial = 0; trial < 60; ++trial) {
+            const size_t n = 1 + (size_t)rnd(trial < 20 ? 40 : 3000);
+            const bool equal = rnd(2) == 0;
+            std::vector<CRef> table(n);
+            for (size_t c = 0; c < n; ++c) table[c] = CRef{(int32_t)(c / 7), 0, equal ? 5500 : (int32_t)(1 + rnd(5500))};
+            const int64_t budget = rnd(3) == 0 ? (int64_t)1 << 40 : 5500 + (int64_t)rnd(2000000);
+            const int minb = 1 + (int)rnd(9);
+            std::vector<std::pair<size_t, size_t>> out;
+            plan_device_batches(table, budget, minb, nd, out);
+            size_t at = 0, lo = SIZE_MAX, hi = 0;
+            for (const auto& b : out) {
+                if (b.first != at || b.second <= b.first) return fail("device batches are not contiguous and non-empty");
+                int64_t rows = 0;
+                for (size_t c = b.first; c < b.second; ++c) rows += table[c].len;
+                if (rows > budget && b.second - b.first > 1) return fail("a device batch of several chunks exceeds the budget");
+                lo = std::min(lo, b.second - b.first);
+                hi = std::max(hi, b.second - b.first);
+                at = b.second;
+            }
+            if (at != n) return fail("device batches do not cover the table");
+            if (out.size() < std::min(n, (size_t)std::max(2 * nd, minb)))
+                return fail("fewer than 2 x " + std::to_string(nd) + " device batches although the chunks allow them");
+            if (equal && budget >= (int64_t)5500 * (int64_t)n && hi > lo + 1) return fail("device batches of unequal share");
+        }
+    // (2) consumption: N threads deal batches dynamically (as the driver threads), each completes its batches in the order
+    // it took them but after shuffled delays, in one or several slices; the consumer must see every slice in batch order
+    for (int nd = 1; nd <= 6; ++nd)
+        for (int trial = 0; trial < 4; ++trial) {
+            const size_t nb = 2 * (size_t)nd + (size_t)rnd(40);
+            std::vector<int> slices(nb), delay_us(nb);
+            for (size_t b = 0; b < nb; ++b) { slices[b] = 1 + (int)rnd(3); delay_us[b] = (int)rnd(400); }
+            BatchTurns turns;
+            std::atomic<size_t> next{0};
+            std::mutex seen_m;
+            std::vector<std::pair<size_t, int>> seen;
+            std::vector<std::thread> th;
+            for (int i = 0; i < nd; ++i)
+                th.emplace_back([&]() {
+                    for (;;) {
+                        const size_t b = next.fetch_add(1);
+                        if (b >= nb) return;
+                        std::this_thread::sleep_for(std::chrono::microseconds(delay_us[b]));
+                        for (int sl = 0; sl < slices[b]; ++sl) {
+                            if (turns.wait(b)) { std::lock_guard<std::mutex> g(seen_m); seen.emplace_back(b, sl); }
+                            if (sl + 1 == slices[b]) turns.done(b);
+                        }
+                    }
+                });
+            for (std::thread& t : th) t.join();
+            size_t k = 0;
+            for (size_t b = 0; b < nb; ++b)
+                for (int sl = 0; sl < slices[b]; ++sl, ++k)
+                    if (k >= seen.size() || seen[k] != std::make_pair(b, sl)) return fail("batches consumed out of batch order");
+            if (k != seen.size()) return fail("a batch slice was consumed twice");
+        }
+    // (3) a pipeline that fails on a batch that is not its last -- when it pops the batch to make room for the next, or
+    // while it drains, or when it cannot take a batch at all -- ends the job: every driver returns (a driver that waited
+    // for the failed batch's turn would hang the job; a watchdog aborts the turns after 20 s and reports it), the error is
+    // returned, and what was consumed is a prefix of the batches in order that stops before the failed one.
+    {
+        struct ModelPipe {   // Pipeline's order of pops: FIFO, the oldest popped when a push finds all slots busy
+            int slots = 3;
+            size_t fail_pop = SIZE_MAX, fail_push = SIZE_MAX;
+            std::deque<std::pair<size_t, std::function<void()>>> q;
+            int inflight() const { return (int)q.size(); }
+            int pop() {
+                std::pair<size_t, std::function<void()>> x = std::move(q.front());
+                q.pop_front();
+                if (x.first == fail_pop) return SD_ERR_HIP;   // (its sink never runs)
+                x.second();
+                return SD_OK;
+            }
+            int push(size_t b, std::function<void()> sink) {
+                if (b == fail_push) return SD_ERR_HIP;
+                if (inflight() == slots) {
+                    const int e = pop();
+                    if (e) return e;
+                }
+                q.emplace_back(b, std::move(sink));
+                return SD_OK;
+            }
+        };
+        for (int trial = 0; trial < 120; ++trial) {
+            const int nd = 1 + (int)rnd(6);
+            const size_t nb = 2 * (size_t)nd + (size_t)rnd(30);
+            const size_t bad = (size_t)rnd(nb - 1);   // never the last batch
+            const bool on_push = rnd(4) == 0;
+            BatchTurns turns;
+            std::atomic<size_t> next{0};
+            const std::atomic<int> sink_ok{SD_OK};
+            std::mutex seen_m;
+            std::vector<size_t> seen;
+            std::vector<int> rcs((size_t)nd, SD_OK);
+            std::vector<int64_t> dealt((size_t)nd, 0);
+            std::vector<ModelPipe> pipes((size_t)nd);
+            for (ModelPipe& mp : pipes) {
+                mp.slots = 1 + (int)rnd(3);
+                if (on_push) mp.fail_push = bad; else mp.fail_pop = bad;
+            }
+            std::mutex fin_m;
+            std::condition_variable fin_cv;
+            int finished = 0;
+            std::vector<std::thread> th;
+            for (int i = 0; i < nd; ++i)
+                th.emplace_back([&, i]() {
+                    ModelPipe& mp = pipes[(size_t)i];
+                    auto push = [&](size_t b) {
+                        if ((b * 2654435761u + (size_t)trial) & 4) std::this_thread::sleep_for(std::chrono::microseconds(50));
+                        return mp.push(b, [&, b]() {
+                            if (turns.wait(b)) { std::lock_guard<std::mutex> g(seen_m); seen.push_back(b); }
+                            turns.done(b);
+                        });
+                    };
+                    rcs[(size_t)i] = drive_entry(mp, turns, next, nb, sink_ok, push, dealt[(size_t)i]);
+                    std::lock_guard<std::mutex> g(fin_m);
+                    ++finished;
+                    fin_cv.notify_all();
+                });
+            bool hung;
+            {
+                std::unique_lock<std::mutex> lk(fin_m);
+                hung = !fin_cv.wait_for(lk, std::chrono::seconds(20), [&] { return finished == nd; });
+            }
+            if (hung) turns.abort();
+            for (std::thread& t : th) t.join();
+            if (hung) return fail("a driver waited forever for the turn of a batch its pipeline failed on");
+            int failed = 0;
+            for (int r : rcs) failed += r != SD_OK;
+            if (failed != 1) return fail("a failed batch did not end the job with exactly that pipeline's error");
+            for (size_t k = 0; k < seen.size(); ++k)
+                if (seen[k] != k || k >= bad) return fail("after a failure, consumption was not an in-order prefix before the failed batch");
+        }
+    }
+    // (4) an aborted job: every waiter returns, nothing after the abort is consumed
+    {
+        BatchTurns turns;
+        std::atomic<int> consumed{0};
+        std::vector<std::thread> th;
+        for (size_t b = 1; b <= 4; ++b)
+            th.emplace_back([&, b]() { if (turns.wait(b)) ++consumed; });
+        std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        turns.abort();
+        for (std::thread& t : th) t.join();
+        if (consumed.load() != 0) return fail("a batch was consumed after the job was aborted");
+    }
+    return SD_OK;
 }
 
 }  // extern "C"

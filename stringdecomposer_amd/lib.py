@@ -41,6 +41,7 @@ EXPORTS = [
     "sd_range_assemble_begin", "sd_range_assemble_begin_files", "sd_range_assemble_text", "sd_range_assemble_write",
     "sd_range_assemble_copy", "sd_range_assemble_stats", "sd_range_assemble_free", "sd_decompose_files_range_begin",
     "sd_range_assemble_records",
+    "sd_run_files_devices", "sd_last_run_device_stats", "sd_multi_device_selftest",
 ]
 
 
@@ -169,6 +170,10 @@ def load():
     L.sd_decompose_files_records.argtypes = [C.c_char_p, C.c_char_p, P(Params), C.c_char_p, C.c_char_p, C.c_size_t]
     L.sd_run_files_records.argtypes = [C.c_char_p, C.c_char_p, P(Params), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
                                        C.c_int32, C.c_int32, P(C.c_double), C.c_char_p, C.c_size_t]
+    L.sd_run_files_devices.argtypes = [C.c_char_p, C.c_char_p, P(Params), P(C.c_int32), C.c_int32, C.c_char_p, C.c_char_p,
+                                       C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P(C.c_double), C.c_char_p, C.c_size_t]
+    L.sd_last_run_device_stats.argtypes = [P(C.c_int64), P(C.c_double), C.c_int32]
+    L.sd_multi_device_selftest.argtypes = [C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -257,14 +262,23 @@ def decompose_files(reads_fa, monomers_fa, raw_tsv_out, **kw):
 
 
 def run_files(reads_fa, monomers_fa, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity=0, second_best=False,
-              lr_coef=(-31.48494996, 0.41784018, 0.69186882), records_out=None, **kw):
+              lr_coef=(-31.48494996, 0.41784018, 0.69186882), records_out=None, devices=None, **kw):
     """The whole CLI job natively (sd_run_files): raw, final and _alt TSV files from the two FASTA files; with
-    records_out also the binary record stream of the raw rows (sd_run_files_records)."""
+    records_out also the binary record stream of the raw rows (sd_run_files_records).  devices (a list of ordinals,
+    repeats allowed): one pipeline per entry in this process (sd_run_files_devices; `device` is then ignored), the
+    same output bytes."""
     L = load()
     p = make_params(**kw)
     err = C.create_string_buffer(4096)
     coef = (C.c_double * 3)(*[float(x) for x in lr_coef])
-    if records_out is None:
+    if devices is not None:
+        devs = [int(d) for d in devices]
+        arr = (C.c_int32 * max(len(devs), 1))(*devs)
+        rc = L.sd_run_files_devices(os.fsencode(reads_fa), os.fsencode(monomers_fa), C.byref(p), arr, len(devs),
+                                    os.fsencode(raw_tsv_out), os.fsencode(final_tsv_out), os.fsencode(alt_tsv_out),
+                                    None if records_out is None else os.fsencode(records_out), int(min_identity),
+                                    1 if second_best else 0, coef, err, 4096)
+    elif records_out is None:
         rc = L.sd_run_files(os.fsencode(reads_fa), os.fsencode(monomers_fa), C.byref(p), os.fsencode(raw_tsv_out),
                             os.fsencode(final_tsv_out), os.fsencode(alt_tsv_out), int(min_identity), 1 if second_best else 0,
                             coef, err, 4096)
@@ -345,6 +359,26 @@ def last_run_stats():
             "raw_text_ms", "post_ms", "io_ms", "text_identity_ms", "final_text_ms", "total_ms", "alloc_ms", "setup_ms",
             "assemble_ms", "homo_pairs", "homo_full_pairs")
     return dict(zip(keys, [float(x) for x in v]))
+
+
+def last_run_device_stats():
+    """Per device entry of the last run_files call of this process (sd_last_run_device_stats): a list of
+    {"batches": batches dealt to the entry, "busy_ms": its device busy time (HIP-event spans of its batches)}."""
+    L = load()
+    b = (C.c_int64 * 16)()
+    ms = (C.c_double * 16)()
+    n = L.sd_last_run_device_stats(b, ms, 16)
+    return [{"batches": int(b[i]), "busy_ms": float(ms[i])} for i in range(min(n, 16))]
+
+
+def multi_device_selftest():
+    """Host-only check of the batch dealing of run_files(devices=...) (sd_multi_device_selftest); raises on a
+    broken property."""
+    L = load()
+    err = C.create_string_buffer(1024)
+    rc = L.sd_multi_device_selftest(err, 1024)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace"))
 
 
 def run_files_range(reads_fa, monomers_fa, rank, world, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity=0,

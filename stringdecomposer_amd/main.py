@@ -355,11 +355,14 @@ def convert_tsv(decomposition, reads, monomers, outfile, identity_th, light, thr
 
 
 def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr, overlap, logger,
-        ref_compat=False, device=0, kernel=0, final_file=None, min_identity=0, second_best=False, records_file=None):
+        ref_compat=False, device=0, kernel=0, final_file=None, min_identity=0, second_best=False, records_file=None,
+        devices=None):
     """main.py:186-197 with the subprocess replaced by libsd_hip.so.
 
     Single process with final_file given: ONE native call (sd_run_files) streams the job through the
     device and writes the raw, final and _alt TSVs batch by batch -- nothing is re-read, returns True.
+    devices (a list of ordinals, --gpus / --devices): the same call with one pipeline per entry
+    (sd_run_files_devices); `device` is then ignored.
     Otherwise (a multi-GPU launch, or no final_file): writes the raw TSV and returns its text (rank 0)."""
     ins, dels, mm, match = [int(x) for x in scoring.split(",")]
     if ref_compat:
@@ -371,6 +374,8 @@ def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr,
         sys.exit(1)
     logger.info(" ".join(["Run", lib.LIB_PATH, "with parameters", sequences, monomers, str(num_threads),
                           str(batch_size), str(overlap), scoring]))
+    if devices is not None:
+        logger.info("HIP devices of this process: " + ",".join(str(d) for d in devices))
     rank, local_rank, ws = shard.world()
     if ws > 1:
         # launched with `python -m torch.distributed.run --nproc-per-node G bin/stringdecomposer ...`:
@@ -415,14 +420,55 @@ def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr,
                       scoring=(ins, dels, mm, match), part_size=int(batch_size), overlap=int(overlap),
                       ed_thr=int(ed_thr), threads=int(num_threads), device=device, kernel=kernel,
                       flags=lib.FLAG_PROGRESS,   # the dp binary's progress lines on stderr (main.cpp:82,115,393)
-                      records_out=records_file)
+                      records_out=records_file, devices=devices)
         return True
     lib.decompose_files(sequences, monomers, raw_file, scoring=(ins, dels, mm, match),
                         part_size=int(batch_size), overlap=int(overlap), ed_thr=int(ed_thr),
-                        threads=int(num_threads), device=device, kernel=kernel)
+                        threads=int(num_threads), device=devices[0] if devices else device, kernel=kernel)
     with open(raw_file, "r") as f:
         raw_decomposition = "".join(f.readlines())
     return raw_decomposition
+
+
+MAX_DEVICE_ENTRIES = 16   # sd_run_files_devices
+
+
+def _device_list(args):
+    """--gpus / --devices -> None (the single-device path of --device) or the list of ordinals for sd_run_files_devices.
+    A request this process cannot serve ends it here, with one line on stderr, before any work on a GPU."""
+    def refuse(msg):
+        sys.stderr.write("stringdecomposer: %s\n" % msg)
+        sys.exit(2)
+    if args.gpus is None and args.devices is None:
+        return None
+    if args.devices is not None:
+        items = args.devices.split(",")
+        if not all(x.strip().isdigit() for x in items):
+            refuse("--devices %s: expected a comma-separated list of device ordinals, e.g. 0,2,5" % args.devices)
+        devs = [int(x) for x in items]
+        what = "--devices %s" % args.devices
+    else:
+        if args.gpus < 1:
+            refuse("--gpus %d: at least one device" % args.gpus)
+        if args.gpus == 1:
+            return None   # today's single-device path, exactly
+        devs = list(range(args.gpus))
+        what = "--gpus %d" % args.gpus
+    if len(devs) > MAX_DEVICE_ENTRIES:
+        refuse("%s: at most %d device entries in one process" % (what, MAX_DEVICE_ENTRIES))
+    if len(devs) > 1 and shard.world()[2] > 1:
+        refuse("%s: several devices per process cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)"
+               % (what, shard.world()[2]))
+    try:
+        count = lib.device_count()
+    except lib.SdError as e:
+        refuse("%s: the HIP library is not available (%s)" % (what, e.msg))
+    bad = [d for d in devs if d >= count]
+    if bad and args.devices is None:
+        refuse("%s: %d devices asked for, %d HIP device%s visible" % (what, len(devs), count, "" if count == 1 else "s"))
+    if bad:
+        refuse("%s: device %d does not exist (%d HIP device%s visible)" % (what, bad[0], count, "" if count == 1 else "s"))
+    return devs
 
 
 def main(argv=None):
@@ -452,12 +498,19 @@ def main(argv=None):
     parser.add_argument("--ref-compat", action="store_true",
                         help="reproduce the reference CLI exactly: -s/--scoring is ignored (default scores)")
     parser.add_argument("--device", type=int, default=0, help="HIP device ordinal (by default 0)")
+    dg = parser.add_mutually_exclusive_group()
+    dg.add_argument("--gpus", type=int, default=None, metavar="N",
+                    help="use HIP devices 0..N-1 in this process (by default 1: the --device ordinal)")
+    dg.add_argument("--devices", default=None, metavar="LIST",
+                    help="comma-separated HIP device ordinals to use in this process, e.g. 0,2,5 (repeats allowed: 0,0 runs "
+                         "two pipelines on device 0)")
     parser.add_argument("--kernel", choices=["auto", "generic", "fast"], default="auto",
                         help="device kernel family (by default auto)")
     parser.add_argument("--records", action="store_true",
                         help="also write <out-file>_raw.sdr: the rows of the raw tsv as a binary record stream "
                              "(stringdecomposer_amd.formats.read_records)")
     args = parser.parse_args(argv)
+    devices = _device_list(args)
     pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
 
     logfn = os.path.join(args.out_dir, "stringdecomposer.log")
@@ -479,7 +532,7 @@ def main(argv=None):
                                 ref_compat=args.ref_compat, device=args.device, kernel=kernel,
                                 final_file=convert_tsv_fn, min_identity=int(args.min_identity),
                                 second_best=args.second_best,
-                                records_file=records_fn if shard.world()[2] == 1 else None)
+                                records_file=records_fn if shard.world()[2] == 1 else None, devices=devices)
     except lib.SdError as e:
         # the reference dies with CalledProcessError after the binary printed its message on stderr
         sys.stderr.write(e.msg + "\n")
