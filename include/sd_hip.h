@@ -197,9 +197,9 @@ int sd_run_files_records(const char* reads_fa, const char* monomers_fa, const sd
  * records_out != NULL) are byte-identical to sd_run_files / sd_run_files_records with the same parameters.
  * 1 <= n_devices <= 16; every ordinal must exist and be a gfx950 device, checked before any work starts on any of
  * them (SD_ERR_PARAM / SD_ERR_NO_DEVICE, errbuf names the ordinal).  An ordinal may repeat: {0, 0} runs two
- * pipelines on device 0 (how the form is tested on a machine with one GPU).  n_devices == 1 is sd_run_files_records
- * on devices[0].  A HIP failure on one device ends the job with SD_ERR_HIP naming the device; the other pipelines are
- * drained first. */
+ * pipelines on device 0 (how the form is tested on a machine with one GPU).  The single-device calls are this route
+ * with one entry, driven on the calling thread; n_devices == 1 is sd_run_files_records on devices[0].  A HIP failure
+ * on one of several devices ends the job with SD_ERR_HIP naming the device; the other pipelines are drained first. */
 int sd_run_files_devices(const char* reads_fa, const char* monomers_fa, const sd_params* p, const int32_t* devices,
                          int32_t n_devices, const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
                          const char* records_out, int32_t min_identity, int32_t second_best, const double* lr_coef,

@@ -1201,12 +1201,7 @@ static int run_chunk_batches(const std::vector<ReadView>& reads, const std::vect
     std::vector<int32_t> clen;
     for (size_t b = 0; b < batches.size() && rc == SD_OK; ++b) {
         const size_t c0 = batches[b].first, c1 = batches[b].second;
-        cptr.clear();
-        clen.clear();
-        for (size_t c = c0; c < c1; ++c) {
-            cptr.push_back(reads[(size_t)table[c].read].seq + table[c].off);
-            clen.push_back(table[c].len);
-        }
+        batch_chunks(reads, table, c0, c1, cptr, clen);
         rc = pipe.push(cptr, clen, [&sink, c0](const sd_rec* r, const int64_t* ro, size_t first, size_t n) { sink(c0 + first, c0 + first + n, r, ro); });
     }
     std::string busy_err;

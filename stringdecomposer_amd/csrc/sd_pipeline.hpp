@@ -764,6 +764,20 @@ inline void plan_batches(const std::vector<CRef>& table, size_t c_lo, size_t c_h
         c0 = c1;
     }
 }
+// The chunks [c0, c1) of a table as Pipeline::push takes them: where each starts in its read (reads[r]: a ReadView or the
+// read's bases) and its length.
+inline const char* read_bases(const ReadView& r) { return r.seq; }
+inline const char* read_bases(const char* s) { return s; }
+template <class Reads>
+inline void batch_chunks(const Reads& reads, const std::vector<CRef>& table, size_t c0, size_t c1,
+                         std::vector<const char*>& cptr, std::vector<int32_t>& clen) {
+    cptr.clear();
+    clen.clear();
+    for (size_t c = c0; c < c1; ++c) {
+        cptr.push_back(read_bases(reads[(size_t)table[c].read]) + table[c].off);
+        clen.push_back(table[c].len);
+    }
+}
 // Rows per batch for a pipeline whose engines do not exist yet (the first job of a process, or of a parameter set).
 // Such a job pays for every byte it allocates -- the driver scrubs memory before it hands it out, ~29 ms per GB on the
 // GPU box: the three full-size engines of a 500-Mbp job (50 GB) cost 1.45 s for 0.14 s of device work.  Buffers scale

@@ -8,15 +8,6 @@
 
 extern "C" {
 
-// -------------------------------------------------------------------------------------------
-// whole CLI job as one native call: FASTA files -> raw TSV + final TSV + _alt TSV, streamed per
-// device batch (main.py:186-197 run + :168-184 convert_tsv without the round trip through the raw file)
-// -------------------------------------------------------------------------------------------
-// rank / world: this process handles the reads [lo, hi) of a split of the read set into `world` contiguous
-// groups of about equal chunk counts (world == 1: everything).  *info (may be null): [0] first read, [1] one
-// past the last read, [2] reads in the file, [3] chunks of this rank.  A read set that cannot be split by
-// reads (one read holds more than half a rank's share, e.g. a single chromosome) gives SD_ERR_UNSUPPORTED
-// before anything is written; the caller then shards by chunk range instead.
 // stage times of the last sd_run_files / sd_run_files_range call of this process (sd_last_run_stats)
 static std::mutex g_last_m;
 static double g_last_run[24] = {0};
@@ -54,8 +45,8 @@ static int g_last_ndev = 0;
 static int64_t g_last_dev_batches[kMaxDevices] = {0};
 static double g_last_dev_busy[kMaxDevices] = {0};
 
-// Several devices in one process (sd_run_files_devices): every pipeline hands its batches to the assembler from its own
-// host thread, and this makes them take turns in batch order -- batch b's records (every slice of them) reach the
+// The pipelines of a job (one per device entry, several with sd_run_files_devices) hand their batches to the assembler
+// from their own driver threads, and this makes them take turns in batch order -- batch b's records (every slice of them) reach the
 // assembler only after all of batch b - 1's have.  A pipeline pops its batches in the order it was dealt them, and it is
 // always dealt the lowest batch nobody has, so the thread that holds the batch whose turn it is never waits for another.
 // abort() (a failed pipeline) releases every waiter; their records are dropped.
@@ -89,7 +80,7 @@ struct BatchTurns {
     }
 };
 
-// One driver thread of sd_run_files_devices: push(b) deals batch b to the entry's pipeline (whose sinks take their turns
+// The driver of one device entry of a job (every job, one entry or several): push(b) deals batch b to the entry's pipeline (whose sinks take their turns
 // in `turns`) until the batches run out, the job has failed somewhere (turns aborted, the writer failed) or this pipeline
 // fails; then the pipeline is drained.  A pop that fails drops its batch before the batch's last slice reaches the
 // assembler, so every batch behind it -- in this pipeline and in the others -- would wait for that turn forever: the
@@ -147,124 +138,145 @@ static void plan_device_batches(const std::vector<CRef>& table, int64_t budget, 
     }
 }
 
-static int run_files_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank, int32_t world,
-                          const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
-                          int32_t min_identity, int32_t second_best, const double* lr_coef, int64_t* info,
-                          char* errbuf, size_t errlen, const char* records_out = nullptr,
-                          const std::vector<int32_t>* devs = nullptr) {
-    std::string err;
-    // devs (sd_run_files_devices, two or more entries): one pipeline per entry, batches dealt and consumed in order below
-    const int nd = devs ? (int)devs->size() : 1;
-    const bool multi = nd > 1;
-    int rc = validate_params(p, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    if (!reads_fa || !monomers_fa || !raw_tsv_out || !final_tsv_out || !alt_tsv_out || !lr_coef || world < 1 || rank < 0 ||
-        rank >= world)
-        return SD_ERR_PARAM;
-    if (records_out && world != 1) { set_err(errbuf, errlen, "the record stream is written by a single process"); return SD_ERR_PARAM; }
-    if (multi && world != 1) return SD_ERR_PARAM;
-    const bool timing = getenv("SD_TIMING") != nullptr;
-    const double t_begin = now_s();
-    double t_prev = t_begin;
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        const double t = now_s();
-        std::fprintf(stderr, "[sd timing] %-34s %9.2f ms\n", what, (t - t_prev) * 1e3);
-        t_prev = t;
-    };
+// The planner of a job: plan_batches for one device entry (a job that fits one batch stays one batch), plan_device_batches
+// for several (at least two batches per entry, so that every pipeline gets work).
+static void cut_batches(const std::vector<CRef>& table, int64_t budget, int min_batches, int n_dev,
+                        std::vector<std::pair<size_t, size_t>>& out) {
+    if (n_dev == 1) plan_batches(table, 0, table.size(), budget, min_batches, out);
+    else plan_device_batches(table, budget, min_batches, n_dev, out);
+}
+
+// fn(i) for every device entry of a job.  One entry: inline, on the calling thread and its current device (as every
+// single-device call).  Several: side by side, each on a thread bound to devs[i] (hipSetDevice is per host thread); a
+// failed hipSetDevice or a std::bad_alloc there is the entry's result, with its message in msg[i], and calls on_fail().
+// Returns the first failed entry's result; its message (err) names the device when there are several.
+extern "C++" template <class Fn, class OnFail>
+static int on_entries(const std::vector<int32_t>& devs, std::vector<std::string>& msg, std::string& err, Fn&& fn, OnFail&& on_fail) {
+    std::vector<int> rc(devs.size(), SD_OK);
+    if (devs.size() == 1) rc[0] = fn(0);
+    else {
+        struct Joined { std::vector<std::thread> t; ~Joined() { for (std::thread& x : t) x.join(); } } th;
+        for (size_t i = 0; i < devs.size(); ++i)
+            th.t.emplace_back([&, i]() {
+                try {
+                    if (hipSetDevice(devs[i]) == hipSuccess) { rc[i] = fn((int)i); return; }
+                    (void)hipGetLastError();
+                    rc[i] = SD_ERR_HIP;
+                    msg[i] = "hipSetDevice failed";
+                } catch (const std::bad_alloc&) {
+                    rc[i] = SD_ERR_INTERNAL;
+                    msg[i] = "out of host memory";
+                }
+                on_fail();
+            });
+    }
+    for (size_t i = 0; i < rc.size(); ++i)
+        if (rc[i]) {
+            err = devs.size() > 1 ? "device " + std::to_string(devs[i]) + ": " + msg[i] : msg[i];
+            return rc[i];
+        }
+    return SD_OK;
+}
+
+// The FASTA side of a job: both files indexed and checked, the monomers, and this rank's reads -- the reads [lo, hi) of a
+// split of the read set into `world` contiguous groups of about equal chunk counts (world == 1: everything).
+struct JobInput {
     sd::FastaFile rf, mf;
-    const bool progress = (p->reserved[1] & SD_FLAG_PROGRESS) != 0 && rank == 0;
-    if (progress)   // main.cpp:393
-        std::fprintf(stderr, "Scores: insertion=%d deletion=%d mismatch=%d match=%d\n", p->ins, p->del, p->mismatch, p->match);
-    rc = rf.open(reads_fa, p->threads, err);                                  // main.cpp:394
-    if (rc == SD_OK && world == 1) rc = rf.validate(0, rf.recs.size(), p->threads, err);   // reads are checked first, as there
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);              // main.cpp:395
-    if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
     std::vector<sd::Seq> monos;
-    for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
-    if (monos.empty()) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
-    std::vector<ReadView> all_reads;
-    all_reads.reserve(rf.recs.size());
-    for (const auto& r : rf.recs) {
-        if (r.len <= 0) { set_err(errbuf, errlen, "ERROR: Sequence " + std::string(r.name, r.name_len) + " is empty"); return SD_ERR_EMPTY; }
-        all_reads.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
-    }
-    {
-        // SeqIO.to_dict (main.py:65) refuses repeated read ids
-        std::vector<std::pair<std::string, size_t>> nm;
-        nm.reserve(all_reads.size());
-        for (size_t r = 0; r < all_reads.size(); ++r) nm.emplace_back(std::string(all_reads[r].name, all_reads[r].name_len), r);
-        std::sort(nm.begin(), nm.end());
-        for (size_t i = 1; i < nm.size(); ++i)
-            if (nm[i].first == nm[i - 1].first) { set_err(errbuf, errlen, "Duplicate key '" + nm[i].first + "'"); return SD_ERR_FORMAT; }
-    }
-    // this rank's reads: contiguous groups of about equal chunk counts
-    size_t r_lo = 0, r_hi = all_reads.size();
-    if (world > 1) {
-        std::vector<int64_t> cum(all_reads.size() + 1, 0);
-        int64_t biggest = 0;
-        for (size_t r = 0; r < all_reads.size(); ++r) {
-            const int64_t k = sd::chunk_plan(all_reads[r].len, p->part_size, p->overlap, [](int64_t, int32_t) {});
-            cum[r + 1] = cum[r] + k;
-            biggest = std::max(biggest, k);
+    std::vector<ReadView> reads;
+    int load(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank, int32_t world, bool progress,
+             int64_t* info, std::string& err) {
+        if (progress)   // main.cpp:393
+            std::fprintf(stderr, "Scores: insertion=%d deletion=%d mismatch=%d match=%d\n", p->ins, p->del, p->mismatch, p->match);
+        int rc = rf.open(reads_fa, p->threads, err);                              // main.cpp:394
+        if (rc == SD_OK && world == 1) rc = rf.validate(0, rf.recs.size(), p->threads, err);   // reads are checked first, as there
+        if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);              // main.cpp:395
+        if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
+        if (rc) return rc;
+        for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
+        if (monos.empty()) { err = "no monomers"; return SD_ERR_PARAM; }
+        std::vector<ReadView> all_reads;
+        all_reads.reserve(rf.recs.size());
+        for (const auto& r : rf.recs) {
+            if (r.len <= 0) { err = "ERROR: Sequence " + std::string(r.name, r.name_len) + " is empty"; return SD_ERR_EMPTY; }
+            all_reads.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
         }
-        const int64_t total = cum[all_reads.size()];
-        if (biggest * 2 * world > total) {
-            set_err(errbuf, errlen, "read set cannot be split by reads (one read holds more than half a rank's share)");
-            return SD_ERR_UNSUPPORTED;
+        {
+            // SeqIO.to_dict (main.py:65) refuses repeated read ids
+            std::vector<std::pair<std::string, size_t>> nm;
+            nm.reserve(all_reads.size());
+            for (size_t r = 0; r < all_reads.size(); ++r) nm.emplace_back(std::string(all_reads[r].name, all_reads[r].name_len), r);
+            std::sort(nm.begin(), nm.end());
+            for (size_t i = 1; i < nm.size(); ++i)
+                if (nm[i].first == nm[i - 1].first) { err = "Duplicate key '" + nm[i].first + "'"; return SD_ERR_FORMAT; }
         }
-        auto bound = [&](int g) {
-            const int64_t want = total * g / world;
-            return (size_t)(std::lower_bound(cum.begin(), cum.end(), want) - cum.begin());
-        };
-        r_lo = std::min(bound(rank), all_reads.size());
-        r_hi = rank + 1 == world ? all_reads.size() : std::min(bound(rank + 1), all_reads.size());
-        if (r_hi < r_lo) r_hi = r_lo;
+        // this rank's reads: contiguous groups of about equal chunk counts
+        size_t r_lo = 0, r_hi = all_reads.size();
+        if (world > 1) {
+            std::vector<int64_t> cum(all_reads.size() + 1, 0);
+            int64_t biggest = 0;
+            for (size_t r = 0; r < all_reads.size(); ++r) {
+                const int64_t k = sd::chunk_plan(all_reads[r].len, p->part_size, p->overlap, [](int64_t, int32_t) {});
+                cum[r + 1] = cum[r] + k;
+                biggest = std::max(biggest, k);
+            }
+            const int64_t total = cum[all_reads.size()];
+            if (biggest * 2 * world > total) {
+                err = "read set cannot be split by reads (one read holds more than half a rank's share)";
+                return SD_ERR_UNSUPPORTED;
+            }
+            auto bound = [&](int g) {
+                const int64_t want = total * g / world;
+                return (size_t)(std::lower_bound(cum.begin(), cum.end(), want) - cum.begin());
+            };
+            r_lo = std::min(bound(rank), all_reads.size());
+            r_hi = rank + 1 == world ? all_reads.size() : std::min(bound(rank + 1), all_reads.size());
+            if (r_hi < r_lo) r_hi = r_lo;
+            rc = rf.validate(r_lo, r_hi, p->threads, err);   // a rank checks the reads it touches (the launcher exchanges failures)
+            if (rc) return rc;
+        }
+        // main.cpp:343 (load_fasta): the N warning, once per file, on stderr
+        for (const auto& ff : {std::make_pair(&rf, reads_fa), std::make_pair(&mf, monomers_fa)})
+            if (ff.first->has_n && rank == 0)
+                std::fprintf(stderr, "WARNING: sequences in %s contain N symbol. It will be counted as a separate symbol in scoring!\n", ff.second);
+        reads.assign(all_reads.begin() + (long)r_lo, all_reads.begin() + (long)r_hi);
+        if (info) { info[0] = (int64_t)r_lo; info[1] = (int64_t)r_hi; info[2] = (int64_t)all_reads.size(); info[3] = 0; }
+        return SD_OK;
     }
-    if (world > 1) rc = rf.validate(r_lo, r_hi, p->threads, err);   // a rank checks the reads it touches (the launcher exchanges failures)
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    // main.cpp:343 (load_fasta): the N warning, once per file, on stderr
-    for (const auto& ff : {std::make_pair(&rf, reads_fa), std::make_pair(&mf, monomers_fa)})
-        if (ff.first->has_n && rank == 0)
-            std::fprintf(stderr, "WARNING: sequences in %s contain N symbol. It will be counted as a separate symbol in scoring!\n", ff.second);
-    lap("FASTA index + alphabet check");
-    std::vector<ReadView> reads(all_reads.begin() + (long)r_lo, all_reads.begin() + (long)r_hi);
-    if (info) { info[0] = (int64_t)r_lo; info[1] = (int64_t)r_hi; info[2] = (int64_t)all_reads.size(); info[3] = 0; }
-    TemplateSet ts(monos);
-    sd::PostProcessor pp;
-    rc = pp.init(monos, min_identity, second_best != 0, lr_coef, multi ? (*devs)[0] : p->device, p->threads, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    // the three outputs as plain descriptors: every batch's text is written by all host threads with pwrite at its
-    // offset (sd::write_parts) -- the copy into the page cache is what a 300-MB _alt batch costs
-    const int fr = ::open(raw_tsv_out, O_RDWR | O_CREAT | O_TRUNC, 0666);   // O_RDWR: write_parts maps the new range
-    const int ff = fr >= 0 ? ::open(final_tsv_out, O_RDWR | O_CREAT | O_TRUNC, 0666) : -1;
-    const int fa = ff >= 0 ? ::open(alt_tsv_out, O_RDWR | O_CREAT | O_TRUNC, 0666) : -1;
+};
+
+// Bytes of a job's _alt TSV, known closely from the reads alone: every base ends up in a block (main.cpp:217-269), a
+// block prints one row per template.
+static int64_t alt_size_estimate(const std::vector<sd::Seq>& monos, const std::vector<ReadView>& reads) {
+    double lmean = 0, nmean = 0;
+    for (const sd::Seq& m : monos) { lmean += (double)m.seq.size(); nmean += (double)m.name.size() + 0.5; }   // (half of the templates carry the "'")
+    lmean /= std::max<size_t>(1, monos.size());
+    nmean /= std::max<size_t>(1, monos.size());
+    double est = 0;
+    auto digits = [](int64_t v) { int d = 1; while (v >= 10) { v /= 10; ++d; } return d; };
+    for (const ReadView& r : reads)
+        est += ((double)r.len / std::max(1.0, lmean) + 1.0) * (2.0 * (double)monos.size()) *
+               ((double)r.name_len + nmean + 2.0 * digits(r.len) + 5 + 1 + 6);
+    return (int64_t)est;
+}
+
+// The three outputs of a job as plain descriptors: every hand-over's text is written by all host threads with pwrite at
+// its offset (sd::write_parts) -- the copy into the page cache is what a 300-MB _alt batch costs.  close() -- or the
+// destructor, on a path that did not reach it -- ends the _alt reservation, cuts that file to what was written and
+// closes all three.
+struct OutFiles {
+    int fr = -1, ff = -1, fa = -1;
     int64_t off_r = 0, off_f = 0, off_a = 0;
-    auto close_all = [&]() {
-        bool ok = true;
-        for (int f : {fr, ff, fa}) if (f >= 0 && ::close(f) != 0) ok = false;
-        return ok;
-    };
-    if (fr < 0 || ff < 0 || fa < 0) {
-        close_all();
-        set_err(errbuf, errlen, std::string("cannot write ") + raw_tsv_out);
-        return SD_ERR_IO;
-    }
-    sd::RecordsWriter rec_w;   // the rows once more as the binary record stream (sd_records.hpp), written as reads complete
-    if (records_out) {
-        rc = rec_w.open(records_out, *p, ts.tnames, err);
-        if (rc) { close_all(); set_err(errbuf, errlen, err); return rc; }
-    }
+    int threads = 1;
     // Round 6: the pages of the _alt file are reserved WHILE THE DEVICE RUNS THE DP.  A --second-best job writes 2T rows of
     // text per block (280 MB at BASELINE config 4) and the page-cache copy of that text bounded the job: on tmpfs the pages
     // of a new range are zeroed by ONE thread inside fallocate (36-49 ms per 280 MB, sd::write_parts), and that could only
     // begin when the first identities arrived, 20 ms into the job.  The size of the file is known closely from the reads
-    // alone -- every base ends up in a block (main.cpp:217-269), a block prints one row per template -- so a helper thread
-    // reserves that much in steps of 16 MB from the start of the job (short steps: write_parts' own fallocate of a range
-    // that already has its pages, and the page faults of the copying threads, take the inode's lock in between); the file
-    // is cut to its real size at the end.  Only with -i 0 (a higher threshold drops rows, main.py:152), only on tmpfs /
-    // ramfs (where write_parts copies through a mapping), only for texts of at least 32 MB.
+    // alone (alt_size_estimate), so a helper thread reserves that much in steps of 16 MB from the start of the job (short
+    // steps: write_parts' own fallocate of a range that already has its pages, and the page faults of the copying threads,
+    // take the inode's lock in between); the file is cut to its real size at the end.  Only with -i 0 (a higher threshold
+    // drops rows, main.py:152), only on tmpfs / ramfs (where write_parts copies through a mapping), only for texts of at
+    // least 32 MB.
     // The reserved range is mapped ONCE for the job and the helper also fills its page tables (MADV_POPULATE_WRITE on pages
     // that exist is a walk, not an allocation): a hand-over's _alt text is then a plain parallel copy -- the per-hand-over
     // fallocate / mmap / 8 000 minor faults / munmap of write_parts made eight 34-MB writes take 5.5-7 ms each, back to
@@ -275,57 +287,48 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     char* alt_map = nullptr;
     int64_t alt_map_len = 0;
     int64_t alt_unmapped = 0;   // the mapping below this (page-aligned) offset is gone again
-    {
+
+    bool open(const char* raw, const char* fin, const char* alt, int n_threads) {
+        threads = n_threads;
+        fr = ::open(raw, O_RDWR | O_CREAT | O_TRUNC, 0666);   // O_RDWR: write_parts maps the new range
+        ff = fr >= 0 ? ::open(fin, O_RDWR | O_CREAT | O_TRUNC, 0666) : -1;
+        fa = ff >= 0 ? ::open(alt, O_RDWR | O_CREAT | O_TRUNC, 0666) : -1;
+        return fa >= 0;
+    }
+    // the _alt text of a job is expected to take `want` bytes
+    void reserve_alt(int64_t want, double t_begin) {
         struct statfs fs;
         const bool ram = ::fstatfs(fa, &fs) == 0 && ((unsigned long)fs.f_type == 0x01021994ul || (unsigned long)fs.f_type == 0x858458f6ul);
-        double lmean = 0, nmean = 0;
-        for (const sd::Seq& m : monos) { lmean += (double)m.seq.size(); nmean += (double)m.name.size() + 0.5; }   // (half of the templates carry the "'")
-        lmean /= std::max<size_t>(1, monos.size());
-        nmean /= std::max<size_t>(1, monos.size());
-        double est = 0;
-        auto digits = [](int64_t v) { int d = 1; while (v >= 10) { v /= 10; ++d; } return d; };
-        for (const ReadView& r : reads)
-            est += ((double)r.len / std::max(1.0, lmean) + 1.0) * (2.0 * (double)monos.size()) *
-                   ((double)r.name_len + nmean + 2.0 * digits(r.len) + 5 + 1 + 6);
-        const int64_t want = (int64_t)est;
-        if (second_best && min_identity <= 0 && ram && want >= (32 << 20) && sd::write_parts_fallocate_ok() && !getenv("SD_ALT_PREALLOC_OFF"))
-        {
-            void* mp = getenv("SD_ALT_MAP_OFF") ? MAP_FAILED : ::mmap(nullptr, (size_t)want, PROT_READ | PROT_WRITE, MAP_SHARED, fa, 0);
-            if (mp != MAP_FAILED) { alt_map = static_cast<char*>(mp); alt_map_len = want; }
-            prealloc = std::thread([&, want]() {
-                const double tp0 = now_s();
-                const int64_t step = 16 << 20;
-                for (int64_t at = 0; at < want && !pre_stop.load(std::memory_order_relaxed); at += step) {
-                    const int64_t n = std::min(step, want - at);
-                    if (::fallocate(fa, 0, (off_t)at, (off_t)n) != 0) break;   // (no space: write_parts reports it)
-                    // (page tables first, then the range is handed to the writer: write_alt unmaps what it has written, and
-                    // an madvise still walking a range that has left the mapping could meet somebody else's pages there)
+        if (!ram || want < (32 << 20) || !sd::write_parts_fallocate_ok() || getenv("SD_ALT_PREALLOC_OFF")) return;
+        void* mp = getenv("SD_ALT_MAP_OFF") ? MAP_FAILED : ::mmap(nullptr, (size_t)want, PROT_READ | PROT_WRITE, MAP_SHARED, fa, 0);
+        if (mp != MAP_FAILED) { alt_map = static_cast<char*>(mp); alt_map_len = want; }
+        prealloc = std::thread([this, want, t_begin]() {
+            const double tp0 = now_s();
+            const int64_t step = 16 << 20;
+            for (int64_t at = 0; at < want && !pre_stop.load(std::memory_order_relaxed); at += step) {
+                const int64_t n = std::min(step, want - at);
+                if (::fallocate(fa, 0, (off_t)at, (off_t)n) != 0) break;   // (no space: write_parts reports it)
+                // (page tables first, then the range is handed to the writer: write_alt unmaps what it has written, and
+                // an madvise still walking a range that has left the mapping could meet somebody else's pages there)
 #ifdef MADV_POPULATE_WRITE
-                    if (alt_map) (void)::madvise(alt_map + at, (size_t)n, MADV_POPULATE_WRITE);
+                if (alt_map) (void)::madvise(alt_map + at, (size_t)n, MADV_POPULATE_WRITE);
 #endif
-                    pre_done.store(at + n, std::memory_order_release);
-                }
-                if (getenv("SD_TIMING"))
-                    std::fprintf(stderr, "[sd timing] _alt pages reserved ahead: %lld of %lld bytes in %.1f ms (from %.1f ms into the job)\n",
-                                 (long long)pre_done.load(), (long long)want, (now_s() - tp0) * 1e3, (tp0 - t_begin) * 1e3);
-            });
-        }
+                pre_done.store(at + n, std::memory_order_release);
+            }
+            if (getenv("SD_TIMING"))
+                std::fprintf(stderr, "[sd timing] _alt pages reserved ahead: %lld of %lld bytes in %.1f ms (from %.1f ms into the job)\n",
+                             (long long)pre_done.load(), (long long)want, (now_s() - tp0) * 1e3, (tp0 - t_begin) * 1e3);
+        });
     }
-    auto end_prealloc = [&]() {   // before the files are closed, on every path
-        pre_stop.store(true);
-        if (prealloc.joinable()) prealloc.join();
-        if (pre_done.load() > off_a) (void)!::ftruncate(fa, (off_t)off_a);
-        if (alt_map) {   // (what write_alt has not unmapped yet: the page of the file's end and the unused rest of the estimate)
-            if (alt_unmapped < alt_map_len) ::munmap(alt_map + alt_unmapped, (size_t)(alt_map_len - alt_unmapped));
-            alt_map = nullptr;
-        }
-    };
+    bool write(const TextJob& j) {
+        return sd::write_parts(fr, off_r, j.raw, threads) && sd::write_parts(ff, off_f, j.fin, threads) && write_alt(j.alt);
+    }
     // a hand-over's _alt text: into the job's mapping where its pages are reserved, else as every other text
-    auto write_alt = [&](const std::vector<sd::TextBuf>& parts) -> bool {
+    bool write_alt(const std::vector<sd::TextBuf>& parts) {
         std::vector<int64_t> at(parts.size() + 1, off_a);
         for (size_t i = 0; i < parts.size(); ++i) at[i + 1] = at[i] + (int64_t)parts[i].size();
         if (alt_map && at[parts.size()] <= pre_done.load(std::memory_order_acquire)) {
-            sd::parallel_for((int64_t)parts.size(), p->threads, 1, [&](int64_t i) {
+            sd::parallel_for((int64_t)parts.size(), threads, 1, [&](int64_t i) {
                 const sd::TextBuf& q = parts[(size_t)i];
                 if (q.size()) std::memcpy(alt_map + at[(size_t)i], q.data(), q.size());
             });
@@ -341,196 +344,100 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
             }
             return true;
         }
-        return sd::write_parts(fa, off_a, parts, p->threads);
-    };
-    RowJob job;
-    job.n_reads = (int32_t)reads.size();
-    job.threads = p->threads;
-    build_chunk_table(reads, p, job.table, job.nch);
-    if (info) info[3] = (int64_t)job.table.size();
-    lap("chunk table");
-    job.row_off = static_cast<int64_t*>(std::calloc(reads.size() + 1, sizeof(int64_t)));
-    if (!job.row_off) {
-        end_prealloc();
-        close_all();
-        set_err(errbuf, errlen, "out of host memory");
-        return SD_ERR_INTERNAL;
+        return sd::write_parts(fa, off_a, parts, threads);
     }
-    // identities of the final TSV in-stream, behind every batch's compaction (sd_ident.hip); template sets the kernel
-    // does not take (and SD_IDENT_STREAM=0, developer A/B) leave them to the post-processing as in round 2
-    std::atomic<bool> stream_ident{false};
-    std::vector<std::string> pkeys((size_t)nd);
-    {
-        sd_params pe = *p;
-        apply_env_overrides(pe);
-        stream_ident = !(pe.reserved[1] & SD_FLAG_NO_STREAM_IDENT);
-        for (int i = 0; i < nd; ++i) {   // (multi: keyed by the entry's device and, beyond the first, its index)
-            if (multi) pe.device = (*devs)[(size_t)i];
-            pkeys[(size_t)i] = pipe_cache_key(pe, second_best ? '2' : '1', ts.mseq, ts.mlen);   // (host threads do not shape an engine)
-            if (i > 0) pkeys[(size_t)i] += "#entry " + std::to_string(i);
+    bool close() {   // false: a file did not close cleanly
+        pre_stop.store(true);
+        if (prealloc.joinable()) prealloc.join();
+        if (fa >= 0 && pre_done.load() > off_a) (void)!::ftruncate(fa, (off_t)off_a);
+        if (alt_map) {   // (what write_alt has not unmapped yet: the page of the file's end and the unused rest of the estimate)
+            if (alt_unmapped < alt_map_len) ::munmap(alt_map + alt_unmapped, (size_t)(alt_map_len - alt_unmapped));
+            alt_map = nullptr;
         }
-    }
-    std::vector<std::unique_ptr<Pipeline>> pipes((size_t)nd);
-    std::vector<char> from_cache((size_t)nd, 0);
-    std::vector<int64_t> entry_budget((size_t)nd, 0);
-    std::vector<std::string> entry_err((size_t)nd);
-    auto on_engine = [&](sd_engine* e) {
-        if (stream_ident && !engine_set_identity(e, pp.interleaved_seqs(), pp.own_interleaved(), second_best != 0)) stream_ident = false;
-    };
-    // the pipeline of entry i, from the cache or new; in a multi-device job on a thread bound to the entry's device
-    auto open_pipe = [&](int i) -> int {
-        sd_params pi = *p;
-        if (multi) pi.device = (*devs)[(size_t)i];
-        std::unique_ptr<Pipeline>& h = pipes[(size_t)i];
-        h = getenv("SD_PIPE_CACHE_OFF") ? nullptr : pipe_cache_take(pkeys[(size_t)i]);
-        from_cache[(size_t)i] = h != nullptr;
-        if (!h) h.reset(new Pipeline);
-        h->restart_idle = true;
-        h->on_engine = on_engine;
-        if (from_cache[(size_t)i]) {
-            h->begin_job(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-            if (!h->ident_ok) stream_ident = false;
-            return SD_OK;
+        bool ok = true;
+        for (int* f : {&fr, &ff, &fa}) {
+            if (*f >= 0 && ::close(*f) != 0) ok = false;
+            *f = -1;
         }
-        const int r = h->create(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-        if (r) entry_err[(size_t)i] = h->eb;
-        return r;
-    };
-    if (!multi) {
-        rc = open_pipe(0);
-        if (rc) err = entry_err[0];
-    } else {
-        // the pipelines are created side by side, each on a thread bound to its device (hipSetDevice is per host thread)
-        std::vector<int> crc((size_t)nd, SD_OK);
-        std::vector<std::thread> th;
-        for (int i = 0; i < nd; ++i)
-            th.emplace_back([&, i]() {
-                const int dev = (*devs)[(size_t)i];
-                if (hipSetDevice(dev) != hipSuccess) {
-                    (void)hipGetLastError();
-                    pipes[(size_t)i].reset(new Pipeline);
-                    crc[(size_t)i] = SD_ERR_HIP;
-                    entry_err[(size_t)i] = "hipSetDevice failed";
-                    return;
-                }
-                crc[(size_t)i] = open_pipe(i);
-                if (crc[(size_t)i] == SD_OK) entry_budget[(size_t)i] = pipes[(size_t)i]->row_budget();   // (hipMemGetInfo of this device)
-            });
-        for (std::thread& t : th) t.join();
-        for (int i = 0; i < nd && rc == SD_OK; ++i)
-            if (crc[(size_t)i]) { rc = crc[(size_t)i]; err = "device " + std::to_string((*devs)[(size_t)i]) + ": " + entry_err[(size_t)i]; }
+        return ok;
     }
-    Pipeline& pipe = *pipes[0];
-    bool reused = true;
-    for (char c : from_cache) reused = reused && c;
-    lap(reused ? "pipeline from the cache" : "engine (HIP runtime start, layout plan, tables, identity masks)");
-    if (stream_ident) job.per = second_best ? (int)pp.interleaved_seqs().size() : 1;
-    std::vector<std::pair<size_t, size_t>> batches;
-    // --second-best makes the host side of a batch (2T identities' worth of text per row) as long as its kernels.  Round 3
-    // cut a job that fits ONE batch in up to four, so that the text of a part is written while the next is on the
-    // device -- four under-filled fill launches (C4: 47.6 instead of 22.6 ms of fill).  Now the DP of a batch is one
-    // launch and its IDENTITIES run in slices of whole reads (sd_engine::slice_end): the host fetches, assembles and
-    // formats slice s while the device computes slice s + 1.
-    int min_batches = 1;
-    const bool slice_ident = second_best && rc == SD_OK && !getenv("SD_IDENT_SLICES_OFF");
-    if (second_best && rc == SD_OK && !slice_ident) {
-        const size_t nc = job.table.size();
-        min_batches = nc >= 2048 ? 4 : nc >= 1024 ? 2 : 1;   // C4 shape, 2 560 chunks: 170 / 159 / 149 / 140 / 134+ ms for 1 / 2 / 3 / 4 / 5+
-    }
-    // A process's first job pays for every byte it allocates: the driver scrubs memory another process released before
-    // it hands it out -- the 17 GB a 50-Mbp job takes as ONE batch cost 0.2-1.2 s, more than the job (0.3 s).  Such a
-    // job is cut into eight batches (two run side by side, stream mode 2), so that its buffers are an eighth as large;
-    // a pipeline that comes from the cache has its buffers, and a job of many batches allocates full-size ones once.
-    if (!reused && rc == SD_OK && !slice_ident) {
-        const size_t nc = job.table.size();
-        min_batches = std::max(min_batches, nc >= 4096 ? 8 : nc >= 1024 ? 4 : 1);
-    }
-    if (const char* ev = getenv("SD_MIN_BATCHES")) min_batches = std::max(1, atoi(ev));   // developer A/B
-    if (rc == SD_OK && !multi) {
-        int64_t budget = pipe.row_budget();
-        if (!reused) {
-            int64_t rows = 0;
-            for (const CRef& c : job.table) rows += c.len;
-            if (rows > budget) budget = fresh_row_budget(budget, rows);   // many batches: smaller ones, smaller engines
-        }
-        plan_batches(job.table, 0, job.table.size(), budget, min_batches, batches);
-    } else if (rc == SD_OK) {
-        // every entry's budget, its device's free HBM shared with the other entries on that device (an explicit cap
-        // stays as it is); the job takes the smallest
-        int64_t budget = INT64_MAX;
-        for (int i = 0; i < nd; ++i) {
-            int64_t b = entry_budget[(size_t)i];
-            int same = 0;
-            for (int j = 0; j < nd; ++j) same += (*devs)[(size_t)j] == (*devs)[(size_t)i];
-            if (p->max_batch_rows <= 0 && !getenv("SD_BATCH_ROWS")) b = std::max<int64_t>(b / same, (int64_t)p->part_size + p->overlap);
-            budget = std::min(budget, b);
-        }
-        if (!reused) {
-            int64_t rows = 0;
-            for (const CRef& c : job.table) rows += c.len;
-            if (rows > budget) budget = fresh_row_budget(budget, rows);
-        }
-        plan_device_batches(job.table, budget, min_batches, nd, batches);
-    }
-    lap("batch plan");
-    const double t_setup = now_s() - t_begin;
-    if (progress) std::fprintf(stderr, "Prepared reads\n");   // main.cpp:82
-    // The rows of a batch are assembled on the driver thread (they come out of the engine's pinned buffer, which
-    // the next load reuses) and handed to a second host thread that turns them into the three texts and writes
-    // them, while the driver packs and enqueues the next batch.  At most two batches wait in the hand-over.
-    // identities of the rows: the batch's pinned arrays (taken from the pipeline, given back to the pool when the text is
-    // written), where each row's words are (src), and the words of carried rows by value (xid / xidh)
-    struct Work {
-        size_t r0, r1; sd_rec* rows; std::vector<int64_t> off;
-        Pipeline::IdentOut ident; int64_t* src; std::vector<uint32_t> xid, xidh; bool have_ident;
-    };
-    std::mutex wq_m;
-    std::condition_variable wq_cv;
-    std::deque<Work> wq;
-    bool wq_done = false;
-    std::atomic<int> sink_rc{SD_OK};
-    std::string sink_err;     // written under wq_m by whichever thread fails first (driver or sink thread)
-    auto sink_fail = [&](int code, const std::string& msg) {
-        std::lock_guard<std::mutex> lk(wq_m);
-        if (sink_rc.load() == SD_OK) { sink_err = msg; sink_rc.store(code); }
-    };
+    ~OutFiles() { close(); }
+};
+
+// The rows of the reads [r0, r1) as a driver hands them over, with their identities: the batch's pinned arrays (taken from
+// the pipeline, given back to the pool when the text is made), where each row's words are (src), and the words of carried
+// rows by value (xid / xidh).
+struct Work {
+    size_t r0, r1; sd_rec* rows; std::vector<int64_t> off;
+    Pipeline::IdentOut ident; int64_t* src; std::vector<uint32_t> xid, xidh; bool have_ident;
+};
+
+// The host side of a job behind its drivers.  The rows of a batch are assembled on the driver's thread (they come out of
+// the engine's pinned buffer, which the next load reuses) and handed to a sink thread that turns them into the three texts,
+// while the driver packs and enqueues the next batch.  The texts go to a writer thread that copies them into the files
+// (the page-cache copy of a --second-best job's _alt rows -- 280 MB at C4 -- takes twice as long as formatting them):
+// formatting hand-over s + 1 and writing hand-over s run side by side.  At most two hand-overs wait for either thread.
+// Text buffers circulate between the two threads and stay with the process between jobs (g_textpool: a fresh 35-MB vector
+// is page faults, and giving 300 MB back to the kernel at the end of every job was 16 ms).  The first failure -- of
+// either thread, or of a driver's assembly -- is the job's (rc, err); what is handed over after it is dropped.
+struct TextStages {
+    const std::vector<ReadView>& reads;
+    const TemplateSet& ts;
+    sd::PostProcessor& pp;
+    sd::RecordsWriter* rec;   // the rows once more as the binary record stream, or null
+    OutFiles& files;
+    const char* raw_path;
+    bool progress, second_best, timing;
+    double t_begin;
+    std::atomic<int> rc{SD_OK};
+    std::string err;   // written under wq_m by whichever thread fails first
     double t_fmt = 0, t_post = 0, t_io = 0;
-    // The text of a hand-over goes to a third thread that copies it into the files (the page-cache copy of a --second-best
-    // job's _alt rows -- 280 MB at C4 -- takes twice as long as formatting them): formatting hand-over s + 1 and writing
-    // hand-over s run side by side.  Text buffers circulate between the two threads (a fresh 35-MB vector is page faults).
-    // Text buffers circulate between the two threads and stay with the process between jobs (g_textpool: a fresh 35-MB
-    // vector is page faults, and giving 300 MB back to the kernel at the end of every job was 16 ms).
-    using WriteJob = TextJob;
-    std::mutex io_m;
-    std::condition_variable io_cv;
-    std::deque<WriteJob> io_q;
-    bool io_done = false;
-    auto io_loop = [&]() {
-        sd::HostPool::lane() = 2;
-        for (;;) {
-            WriteJob j;
-            {
-                std::unique_lock<std::mutex> lk(io_m);
-                io_cv.wait(lk, [&] { return io_done || !io_q.empty(); });
-                if (io_q.empty()) return;
-                j = std::move(io_q.front());
-                io_q.pop_front();
-            }
-            io_cv.notify_all();
-            const double t0 = now_s();
-            const int64_t a0 = off_a;
-            if (sink_rc.load() == SD_OK &&
-                (!sd::write_parts(fr, off_r, j.raw, p->threads) || !sd::write_parts(ff, off_f, j.fin, p->threads) ||
-                 !write_alt(j.alt)))
-                sink_fail(SD_ERR_IO, std::string("short write to ") + raw_tsv_out);
-            t_io += now_s() - t0;
-            if (timing)
-                std::fprintf(stderr, "[sd timing] write of a hand-over: %.1f MB of _alt rows in %.1f ms, at %.1f ms into the job\n",
-                             (double)(off_a - a0) / 1e6, (now_s() - t0) * 1e3, (now_s() - t_begin) * 1e3);
-            g_textpool.give(std::move(j));
+    std::mutex wq_m, io_m;
+    std::condition_variable wq_cv, io_cv;
+    std::deque<Work> wq;
+    std::deque<TextJob> io_q;
+    bool wq_done = false, io_done = false;
+    std::thread sink_thread, io_thread;
+
+    TextStages(const std::vector<ReadView>& reads_, const TemplateSet& ts_, sd::PostProcessor& pp_, sd::RecordsWriter* rec_,
+               OutFiles& files_, const char* raw_path_, bool progress_, bool second_best_, bool timing_, double t_begin_)
+        : reads(reads_), ts(ts_), pp(pp_), rec(rec_), files(files_), raw_path(raw_path_), progress(progress_),
+          second_best(second_best_), timing(timing_), t_begin(t_begin_) {}
+    ~TextStages() { finish(); }
+    void start() {
+        sink_thread = std::thread([this]() { sink_loop(); });
+        io_thread = std::thread([this]() { io_loop(); });
+    }
+    bool failed() const { return rc.load() != SD_OK; }
+    void fail(int code, const std::string& msg) {
+        std::lock_guard<std::mutex> lk(wq_m);
+        if (rc.load() == SD_OK) { err = msg; rc.store(code); }
+    }
+    void hand_over(Work&& w) {
+        std::unique_lock<std::mutex> lk(wq_m);
+        wq_cv.wait(lk, [&] { return wq.size() < 2; });
+        wq.push_back(std::move(w));
+        lk.unlock();
+        wq_cv.notify_all();
+    }
+    // what was handed over is made and written; both threads end
+    void finish() {
+        {
+            std::lock_guard<std::mutex> lk(wq_m);
+            wq_done = true;
         }
-    };
-    auto sink_loop = [&]() {
+        wq_cv.notify_all();
+        if (sink_thread.joinable()) sink_thread.join();
+        {
+            std::lock_guard<std::mutex> lk(io_m);
+            io_done = true;
+        }
+        io_cv.notify_all();
+        if (io_thread.joinable()) io_thread.join();
+    }
+
+  private:
+    void sink_loop() {
         sd::HostPool::lane() = 1;   // this thread's parallel loops run on the second pool, beside the driver's
         std::vector<sd::PostRead> preads;
         for (;;) {
@@ -543,62 +450,10 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
                 wq.pop_front();
             }
             wq_cv.notify_all();
-            if (sink_rc.load() == SD_OK) {
-                if (progress) {   // main.cpp:115, one line per read, written per hand-over
-                    std::string pl;
-                    const size_t n_all = reads.size();
-                    for (size_t r = w.r0; r < w.r1; ++r) {
-                        sd::put_int(pl, (int64_t)((r + 1) * 100 / n_all));
-                        pl.append("%: Aligned ");
-                        pl.append(reads[r].name, reads[r].name_len);
-                        pl.push_back('\n');
-                    }
-                    (void)std::fwrite(pl.data(), 1, pl.size(), stderr);
-                }
-                double t0 = now_s();
-                // raw TSV (SaveBatch, main.cpp:272-285): slices of <= 32 k rows, so that a chromosome-sized read is
-                // formatted by all threads; a slice needs the end of the row before it
-                struct Slice { size_t r; int64_t a, b; };
-                std::vector<Slice> slices;
-                const int64_t* off = w.off.data();   // off[r - r0] .. : rows of read r
-                for (size_t r = w.r0; r < w.r1; ++r)
-                    for (int64_t a = off[r - w.r0]; a < off[r - w.r0 + 1]; a += 32768)
-                        slices.push_back(Slice{r, a, std::min<int64_t>(off[r - w.r0 + 1], a + 32768)});
-                WriteJob wj = g_textpool.take();
-                std::vector<std::string>& parts = wj.raw;
-                std::vector<std::string>& fin_parts = wj.fin;
-                std::vector<sd::TextBuf>& alt_parts = wj.alt;
-                parts.resize(slices.size());
-                for (std::string& q : parts) q.clear();
-                sd::parallel_for((int64_t)slices.size(), p->threads, 1, [&](int64_t x) {
-                    const Slice& sl = slices[(size_t)x];
-                    sd::format_rows(parts[(size_t)x], reads[sl.r].name, reads[sl.r].name_len, ts.tnames, w.rows + sl.a,
-                                    (size_t)(sl.b - sl.a), sl.a > off[sl.r - w.r0] ? w.rows[sl.a - 1].end : 0);
-                });
-                if (records_out)
-                    for (size_t r = w.r0; r < w.r1; ++r)
-                        rec_w.add_read(reads[r].name, reads[r].name_len, reads[r].len, w.rows + off[r - w.r0], off[r - w.r0 + 1] - off[r - w.r0]);
-                t_fmt += now_s() - t0;
-                t0 = now_s();
-                preads.clear();
-                for (size_t r = w.r0; r < w.r1; ++r)
-                    preads.push_back(sd::PostRead{reads[r].name, reads[r].name_len, reads[r].seq, reads[r].len});
-                std::string e2;
-                sd::IdentRef iref;
-                if (w.have_ident)
-                    iref = sd::IdentRef{w.ident.id, second_best ? w.ident.idh : nullptr, w.src, w.xid.data(), w.xidh.data()};
-                const int r2 = pp.process_parts(preads.data(), preads.size(), w.rows, off, fin_parts, alt_parts, e2,
-                                                w.have_ident ? &iref : nullptr);
-                t_post += now_s() - t0;
-                if (r2) {
-                    sink_fail(r2, e2);
-                } else {
-                    std::unique_lock<std::mutex> lk(io_m);
-                    io_cv.wait(lk, [&] { return io_q.size() < 2; });
-                    io_q.push_back(std::move(wj));
-                    lk.unlock();
-                    io_cv.notify_all();
-                }
+            try {
+                if (!failed()) make_text(w, preads);
+            } catch (const std::bad_alloc&) {
+                fail(SD_ERR_INTERNAL, "out of host memory");
             }
             std::free(w.rows);
             std::free(w.src);
@@ -607,150 +462,185 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
                 g_pinpool.give(w.ident.idh, w.ident.idh_bytes);
             }
         }
-    };
-    std::thread sink_thread(sink_loop);
-    std::thread io_thread(io_loop);
-    auto sink = [&](Pipeline& pq, size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff) {
-        if (sink_rc.load()) return;
-        const size_t r0 = job.next_read;
-        job.n_rows = 0;
-        job.row_off[r0] = 0;
-        job.bid = pq.cur_ident.id;
-        job.bidh = pq.cur_ident.idh;
-        job.add(c0, c1, recs, roff);
-        if (job.oom) { sink_fail(SD_ERR_INTERNAL, "out of host memory"); return; }
-        const size_t r1 = job.next_read;
-        if (r1 == r0) return;
-        Work w;
-        w.r0 = r0;
-        w.r1 = r1;
-        w.rows = job.rows;
-        w.off.assign(job.row_off + r0, job.row_off + r1 + 1);
-        // identities that came with the batches of these rows; a batch without them (more records than the outputs
-        // had room for) sends the whole hand-over through the text-based identities
-        w.have_ident = job.per && job.ident_ok;
-        w.src = job.rsrc;
-        job.rsrc = nullptr;
-        w.xid.swap(job.xid);
-        w.xidh.swap(job.xidh);
-        job.xid.clear();
-        job.xidh.clear();
-        w.ident = Pipeline::IdentOut{};
-        if (w.have_ident && job.bid) w.ident = pq.take_ident();   // the rows point into the batch's pinned arrays
-        job.ident_ok = job.carry.empty() || job.bid != nullptr;
-        job.rows = nullptr;       // the next batch assembles into a fresh (or recycled) buffer
-        job.cap_rows = 0;
-        job.n_rows = 0;
-        std::unique_lock<std::mutex> lk(wq_m);
-        wq_cv.wait(lk, [&] { return wq.size() < 2; });
-        wq.push_back(std::move(w));
-        lk.unlock();
-        wq_cv.notify_all();
-    };
-    // the chunks of batch b and the cut of its identities into slices
-    auto batch_input = [&](size_t b, std::vector<const char*>& cptr, std::vector<int32_t>& clen, std::vector<int>& slice_end) {
-        const size_t c0 = batches[b].first, c1 = batches[b].second;
-        cptr.clear();
-        clen.clear();
-        for (size_t c = c0; c < c1; ++c) {
-            cptr.push_back(reads[(size_t)job.table[c].read].seq + job.table[c].off);
-            clen.push_back(job.table[c].len);
-        }
-        slice_end.clear();
-        if (slice_ident && stream_ident) {
-            // up to eight slices of at least 256 chunks, each ending with a read (a read that ends in a later slice would
-            // only be carried; the last slice ends the batch)
-            const size_t nb = c1 - c0;
-            int n_sl = (int)std::max<size_t>(1, std::min<size_t>(8, nb / 256));
-            if (const char* ev = getenv("SD_IDENT_SLICES")) n_sl = std::max(1, std::min(64, atoi(ev)));   // developer A/B
-            size_t at = 0;
-            for (int sl = 0; sl < n_sl && at < nb; ++sl) {
-                size_t want = sl + 1 == n_sl ? nb : std::max(at + 1, nb * (size_t)(sl + 1) / (size_t)n_sl);
-                while (want < nb && job.table[c0 + want].read == job.table[c0 + want - 1].read) ++want;
-                slice_end.push_back((int)want);
-                at = want;
+    }
+    // a hand-over's three texts (and its records), queued for the writer
+    void make_text(const Work& w, std::vector<sd::PostRead>& preads) {
+        if (progress) {   // main.cpp:115, one line per read, written per hand-over
+            std::string pl;
+            const size_t n_all = reads.size();
+            for (size_t r = w.r0; r < w.r1; ++r) {
+                sd::put_int(pl, (int64_t)((r + 1) * 100 / n_all));
+                pl.append("%: Aligned ");
+                pl.append(reads[r].name, reads[r].name_len);
+                pl.push_back('\n');
             }
-            if (slice_end.empty() || slice_end.back() != (int)nb) slice_end.push_back((int)nb);
+            (void)std::fwrite(pl.data(), 1, pl.size(), stderr);
         }
-    };
-    std::vector<int64_t> dealt((size_t)nd, 0);   // batches per entry
-    if (!multi) {
-        std::vector<const char*> cptr;
-        std::vector<int32_t> clen;
-        std::vector<int> slice_end;
-        for (size_t b = 0; b < batches.size() && rc == SD_OK && sink_rc.load() == SD_OK; ++b) {
-            const size_t c0 = batches[b].first;
-            batch_input(b, cptr, clen, slice_end);
-            rc = pipe.push(cptr, clen, [&sink, &pipe, c0](const sd_rec* r, const int64_t* ro, size_t first, size_t n) { sink(pipe, c0 + first, c0 + first + n, r, ro); },
-                           slice_end);
-            if (rc) err = pipe.eb;
-            else ++dealt[0];
+        double t0 = now_s();
+        // raw TSV (SaveBatch, main.cpp:272-285): slices of <= 32 k rows, so that a chromosome-sized read is
+        // formatted by all threads; a slice needs the end of the row before it
+        struct Slice { size_t r; int64_t a, b; };
+        std::vector<Slice> slices;
+        const int64_t* off = w.off.data();   // off[r - r0] .. : rows of read r
+        for (size_t r = w.r0; r < w.r1; ++r)
+            for (int64_t a = off[r - w.r0]; a < off[r - w.r0 + 1]; a += 32768)
+                slices.push_back(Slice{r, a, std::min<int64_t>(off[r - w.r0 + 1], a + 32768)});
+        TextJob wj = g_textpool.take();
+        wj.raw.resize(slices.size());
+        for (std::string& q : wj.raw) q.clear();
+        sd::parallel_for((int64_t)slices.size(), files.threads, 1, [&](int64_t x) {
+            const Slice& sl = slices[(size_t)x];
+            sd::format_rows(wj.raw[(size_t)x], reads[sl.r].name, reads[sl.r].name_len, ts.tnames, w.rows + sl.a,
+                            (size_t)(sl.b - sl.a), sl.a > off[sl.r - w.r0] ? w.rows[sl.a - 1].end : 0);
+        });
+        if (rec)
+            for (size_t r = w.r0; r < w.r1; ++r)
+                rec->add_read(reads[r].name, reads[r].name_len, reads[r].len, w.rows + off[r - w.r0], off[r - w.r0 + 1] - off[r - w.r0]);
+        t_fmt += now_s() - t0;
+        t0 = now_s();
+        preads.clear();
+        for (size_t r = w.r0; r < w.r1; ++r)
+            preads.push_back(sd::PostRead{reads[r].name, reads[r].name_len, reads[r].seq, reads[r].len});
+        std::string e2;
+        sd::IdentRef iref;
+        if (w.have_ident)
+            iref = sd::IdentRef{w.ident.id, second_best ? w.ident.idh : nullptr, w.src, w.xid.data(), w.xidh.data()};
+        const int r2 = pp.process_parts(preads.data(), preads.size(), w.rows, off, wj.fin, wj.alt, e2,
+                                        w.have_ident ? &iref : nullptr);
+        t_post += now_s() - t0;
+        if (r2) { fail(r2, e2); return; }
+        std::unique_lock<std::mutex> lk(io_m);
+        io_cv.wait(lk, [&] { return io_q.size() < 2; });
+        io_q.push_back(std::move(wj));
+        lk.unlock();
+        io_cv.notify_all();
+    }
+    void io_loop() {
+        sd::HostPool::lane() = 2;
+        for (;;) {
+            TextJob j;
+            {
+                std::unique_lock<std::mutex> lk(io_m);
+                io_cv.wait(lk, [&] { return io_done || !io_q.empty(); });
+                if (io_q.empty()) return;
+                j = std::move(io_q.front());
+                io_q.pop_front();
+            }
+            io_cv.notify_all();
+            try {
+                const double t0 = now_s();
+                const int64_t a0 = files.off_a;
+                if (!failed() && !files.write(j)) fail(SD_ERR_IO, std::string("short write to ") + raw_path);
+                t_io += now_s() - t0;
+                if (timing)
+                    std::fprintf(stderr, "[sd timing] write of a hand-over: %.1f MB of _alt rows in %.1f ms, at %.1f ms into the job\n",
+                                 (double)(files.off_a - a0) / 1e6, (now_s() - t0) * 1e3, (now_s() - t_begin) * 1e3);
+                g_textpool.give(std::move(j));
+            } catch (const std::bad_alloc&) {
+                fail(SD_ERR_INTERNAL, "out of host memory");
+            }
         }
-        const int rc2 = pipe.drain();
-        if (rc == SD_OK && rc2) { rc = rc2; err = pipe.eb; }
-    } else if (rc == SD_OK) {
-        // One driver thread per entry, bound to its device: it takes the next batch nobody has whenever its pipeline can
-        // take one (a pipeline pushes until all its slots are busy, then waits for its oldest batch), and hands its
-        // batches' records to the assembler in batch order (BatchTurns).  Every HIP call of a pipeline -- engines,
-        // streams, events, copies, identity slices -- is made on its driver thread; the sink and writer threads make none.
-        BatchTurns turns;
-        std::atomic<size_t> next_batch{0};
-        std::vector<int> drc((size_t)nd, SD_OK);
-        std::vector<std::thread> drivers;
-        for (int i = 0; i < nd; ++i)
-            drivers.emplace_back([&, i]() {
-                Pipeline& pq = *pipes[(size_t)i];
-                int r = hipSetDevice((*devs)[(size_t)i]) == hipSuccess ? SD_OK : SD_ERR_HIP;
-                if (r) {
-                    (void)hipGetLastError();
-                    std::snprintf(pq.eb, sizeof pq.eb, "hipSetDevice failed");
-                    turns.abort();
-                    drc[(size_t)i] = r;
-                    return;
-                }
-                std::vector<const char*> cptr;
-                std::vector<int32_t> clen;
-                std::vector<int> slice_end;
-                auto push = [&](size_t b) {
-                    const size_t c0 = batches[b].first, c1 = batches[b].second;
-                    batch_input(b, cptr, clen, slice_end);
-                    return pq.push(cptr, clen, [&sink, &pq, &turns, b, c0, c1](const sd_rec* rr, const int64_t* ro, size_t first, size_t n) {
-                        if (turns.wait(b)) sink(pq, c0 + first, c0 + first + n, rr, ro);
-                        if (c0 + first + n == c1) turns.done(b);
-                    }, slice_end);
-                };
-                drc[(size_t)i] = drive_entry(pq, turns, next_batch, batches.size(), sink_rc, push, dealt[(size_t)i]);
-            });
-        for (std::thread& t : drivers) t.join();
-        for (int i = 0; i < nd && rc == SD_OK; ++i)
-            if (drc[(size_t)i]) { rc = drc[(size_t)i]; err = "device " + std::to_string((*devs)[(size_t)i]) + ": " + pipes[(size_t)i]->eb; }
     }
-    {
-        std::lock_guard<std::mutex> lk(wq_m);
-        wq_done = true;
+};
+
+// A driver's side of a hand-over: the records of the chunks [c0, c1) that pipeline pq just fetched are assembled into the
+// rows of the reads they complete, which go to the text stages with their identities.
+static void assemble(RowJob& job, Pipeline& pq, size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff, TextStages& text) {
+    if (text.failed()) return;
+    const size_t r0 = job.next_read;
+    job.n_rows = 0;
+    job.row_off[r0] = 0;
+    job.bid = pq.cur_ident.id;
+    job.bidh = pq.cur_ident.idh;
+    job.add(c0, c1, recs, roff);
+    if (job.oom) { text.fail(SD_ERR_INTERNAL, "out of host memory"); return; }
+    const size_t r1 = job.next_read;
+    if (r1 == r0) return;
+    Work w;
+    w.r0 = r0;
+    w.r1 = r1;
+    w.rows = job.rows;
+    w.off.assign(job.row_off + r0, job.row_off + r1 + 1);
+    // identities that came with the batches of these rows; a batch without them (more records than the outputs
+    // had room for) sends the whole hand-over through the text-based identities
+    w.have_ident = job.per && job.ident_ok;
+    w.src = job.rsrc;
+    job.rsrc = nullptr;
+    w.xid.swap(job.xid);
+    w.xidh.swap(job.xidh);   // (w's are empty)
+    if (w.have_ident && job.bid) w.ident = pq.take_ident();   // the rows point into the batch's pinned arrays
+    job.ident_ok = job.carry.empty() || job.bid != nullptr;
+    job.rows = nullptr;       // the next batch assembles into a fresh (or recycled) buffer
+    job.cap_rows = 0;
+    job.n_rows = 0;
+    text.hand_over(std::move(w));
+}
+
+// The cut of the identities of the chunks [c0, c1) into slices (sd_engine::slice_end): up to eight slices of at least 256
+// chunks, each ending with a read (a read that ends in a later slice would only be carried; the last slice ends the batch).
+static void ident_slices(const std::vector<CRef>& table, size_t c0, size_t c1, std::vector<int>& slice_end) {
+    const size_t nb = c1 - c0;
+    int n_sl = (int)std::max<size_t>(1, std::min<size_t>(8, nb / 256));
+    if (const char* ev = getenv("SD_IDENT_SLICES")) n_sl = std::max(1, std::min(64, atoi(ev)));   // developer A/B
+    size_t at = 0;
+    for (int sl = 0; sl < n_sl && at < nb; ++sl) {
+        size_t want = sl + 1 == n_sl ? nb : std::max(at + 1, nb * (size_t)(sl + 1) / (size_t)n_sl);
+        while (want < nb && table[c0 + want].read == table[c0 + want - 1].read) ++want;
+        slice_end.push_back((int)want);
+        at = want;
     }
-    wq_cv.notify_all();
-    sink_thread.join();
-    {
-        std::lock_guard<std::mutex> lk(io_m);
-        io_done = true;
+    if (slice_end.empty() || slice_end.back() != (int)nb) slice_end.push_back((int)nb);
+}
+
+// The batches of a job whose pipelines hold entry_budget rows per batch.
+static void plan_job(const RowJob& job, const std::vector<int64_t>& entry_budget, const std::vector<int32_t>& devs,
+                     const sd_params* p, bool second_best, bool slice_ident, bool reused,
+                     std::vector<std::pair<size_t, size_t>>& batches) {
+    const size_t nc = job.table.size();
+    // --second-best makes the host side of a batch (2T identities' worth of text per row) as long as its kernels.  Round 3
+    // cut a job that fits ONE batch in up to four, so that the text of a part is written while the next is on the
+    // device -- four under-filled fill launches (C4: 47.6 instead of 22.6 ms of fill).  Now the DP of a batch is one
+    // launch and its IDENTITIES run in slices of whole reads (sd_engine::slice_end): the host fetches, assembles and
+    // formats slice s while the device computes slice s + 1.
+    int min_batches = 1;
+    if (second_best && !slice_ident)
+        min_batches = nc >= 2048 ? 4 : nc >= 1024 ? 2 : 1;   // C4 shape, 2 560 chunks: 170 / 159 / 149 / 140 / 134+ ms for 1 / 2 / 3 / 4 / 5+
+    // A process's first job pays for every byte it allocates: the driver scrubs memory another process released before
+    // it hands it out -- the 17 GB a 50-Mbp job takes as ONE batch cost 0.2-1.2 s, more than the job (0.3 s).  Such a
+    // job is cut into eight batches (two run side by side, stream mode 2), so that its buffers are an eighth as large;
+    // a pipeline that comes from the cache has its buffers, and a job of many batches allocates full-size ones once.
+    if (!reused && !slice_ident) min_batches = std::max(min_batches, nc >= 4096 ? 8 : nc >= 1024 ? 4 : 1);
+    if (const char* ev = getenv("SD_MIN_BATCHES")) min_batches = std::max(1, atoi(ev));   // developer A/B
+    // every entry's budget, its device's free HBM shared with the other entries on that device (an explicit cap stays as
+    // it is); the job takes the smallest
+    int64_t budget = INT64_MAX;
+    for (size_t i = 0; i < devs.size(); ++i) {
+        int64_t b = entry_budget[i];
+        const int same = (int)std::count(devs.begin(), devs.end(), devs[i]);
+        if (same > 1 && p->max_batch_rows <= 0 && !getenv("SD_BATCH_ROWS")) b = std::max<int64_t>(b / same, (int64_t)p->part_size + p->overlap);
+        budget = std::min(budget, b);
     }
-    io_cv.notify_all();
-    io_thread.join();
-    if (rc == SD_OK && sink_rc.load()) { rc = sink_rc.load(); err = sink_err; }
-    end_prealloc();
-    if (!close_all() && rc == SD_OK) { rc = SD_ERR_IO; err = std::string("short write to ") + raw_tsv_out; }
-    if (records_out && rc == SD_OK) rc = rec_w.close(err, records_out);
-    // kernel times, batches and host stage times summed over the pipelines (one unless several devices)
+    if (!reused) {
+        int64_t rows = 0;
+        for (const CRef& c : job.table) rows += c.len;
+        if (rows > budget) budget = fresh_row_budget(budget, rows);   // many batches: smaller ones, smaller engines
+    }
+    cut_batches(job.table, budget, min_batches, (int)devs.size(), batches);
+}
+
+// Kernel times, batches and host stage times of a job, summed over its pipelines: sd_last_run_stats,
+// sd_last_run_device_stats, and with SD_TIMING on stderr.
+static void report_stats(const std::vector<std::unique_ptr<Pipeline>>& pipes, const std::vector<int64_t>& dealt,
+                         const TextStages& text, const sd::PostProcessor& pp, size_t n_batches, double t_setup) {
     auto total = [&](double (*f)(const Pipeline&)) { double t = 0; for (const auto& q : pipes) t += f(*q); return t; };
     const double s_pack = total([](const Pipeline& q) { return q.pack_s; }), s_wait = total([](const Pipeline& q) { return q.wait_s; });
-    if (timing)
+    if (text.timing)
         std::fprintf(stderr, "[sd timing] %zu batches: pack+enqueue %.1f ms, wait %.1f ms, raw text %.1f ms, post-processing %.1f ms, "
-                     "file writes %.1f ms, total %.1f ms\n", batches.size(), s_pack * 1e3, s_wait * 1e3, t_fmt * 1e3,
-                     t_post * 1e3, t_io * 1e3, (now_s() - t_begin) * 1e3);
-    if (timing)
+                     "file writes %.1f ms, total %.1f ms\n", n_batches, s_pack * 1e3, s_wait * 1e3, text.t_fmt * 1e3,
+                     text.t_post * 1e3, text.t_io * 1e3, (now_s() - text.t_begin) * 1e3);
+    if (text.timing)
         std::fprintf(stderr, "[sd timing] of which device / pinned allocations (hipMalloc, hipHostMalloc): %.1f ms\n", (double)g_alloc_ns.load() / 1e6);
-    if (timing)
+    if (text.timing)
         std::fprintf(stderr, "[sd timing] post-processing: segments %.1f ms, identities %.1f ms, text %.1f ms, concatenation %.1f ms\n",
                      pp.t_prepare * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, pp.t_concat * 1e3);
     {
@@ -758,29 +648,184 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         const double v[24] = {total([](const Pipeline& q) { return q.fill_ms; }), total([](const Pipeline& q) { return q.trace_ms; }),
                               total([](const Pipeline& q) { return q.compact_ms; }), total([](const Pipeline& q) { return q.ident_ms; }),
                               total([](const Pipeline& q) { return (double)q.ident_pairs; }), total([](const Pipeline& q) { return (double)q.batches; }),
-                              total([](const Pipeline& q) { return (double)q.rows; }), s_pack * 1e3, s_wait * 1e3, t_fmt * 1e3,
-                              t_post * 1e3, t_io * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, (now_s() - t_begin) * 1e3,
+                              total([](const Pipeline& q) { return (double)q.rows; }), s_pack * 1e3, s_wait * 1e3, text.t_fmt * 1e3,
+                              text.t_post * 1e3, text.t_io * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, (now_s() - text.t_begin) * 1e3,
                               (double)g_alloc_ns.load() / 1e6, t_setup * 1e3, total([](const Pipeline& q) { return q.sink_s; }) * 1e3,
                               total([](const Pipeline& q) { return (double)q.homo_pairs; }),
                               total([](const Pipeline& q) { return (double)q.homo_full_pairs; }), 0, 0, 0, 0};
         std::memcpy(g_last_run, v, sizeof v);
-        g_last_ndev = std::min(nd, kMaxDevices);
+        g_last_ndev = std::min((int)pipes.size(), kMaxDevices);
         for (int i = 0; i < g_last_ndev; ++i) { g_last_dev_batches[i] = dealt[(size_t)i]; g_last_dev_busy[i] = pipes[(size_t)i]->run_ms; }
     }
-    if (timing) {
+    if (text.timing) {
         double nw[4];
         sd::nw_stage_seconds(nw);
         std::fprintf(stderr, "[sd timing] identities on the device: preparation + staging %.1f ms, uploads %.1f ms, launch %.1f ms, "
                      "kernel + downloads %.1f ms\n", nw[0] * 1e3, nw[1] * 1e3, nw[2] * 1e3, nw[3] * 1e3);
     }
-    for (int i = 0; i < nd; ++i) {
-        pipes[(size_t)i]->ident_ok = stream_ident;
-        pipes[(size_t)i]->on_engine = nullptr;   // (it refers to this call's locals)
-        if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkeys[(size_t)i], std::move(pipes[(size_t)i]), i);
+}
+
+// The whole CLI job as one native call: FASTA files -> raw TSV + final TSV + _alt TSV, streamed per device batch
+// (main.py:186-197 run + :168-184 convert_tsv without the round trip through the raw file).  devs: the device entries,
+// one pipeline each ({p->device} for the single-device calls); their batches are dealt and consumed in order below.
+// rank / world and *info (may be null): [0] first read, [1] one past the last read, [2] reads in the file, [3] chunks of
+// this rank.  A read set that cannot be split by reads (one read holds more than half a rank's share, e.g. a single
+// chromosome) gives SD_ERR_UNSUPPORTED before anything is written; the caller then shards by chunk range instead.
+// Every thread the job starts is joined by its owner on every path, so running out of host memory is an error like any other.
+static int run_files_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank, int32_t world,
+                          const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
+                          int32_t min_identity, int32_t second_best, const double* lr_coef, int64_t* info,
+                          char* errbuf, size_t errlen, const char* records_out = nullptr,
+                          const std::vector<int32_t>* dev_list = nullptr) try {
+    std::string err;
+    int rc = validate_params(p, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    const std::vector<int32_t> devs = dev_list ? *dev_list : std::vector<int32_t>{p->device};
+    const size_t nd = devs.size();
+    if (!reads_fa || !monomers_fa || !raw_tsv_out || !final_tsv_out || !alt_tsv_out || !lr_coef || world < 1 || rank < 0 ||
+        rank >= world)
+        return SD_ERR_PARAM;
+    if (records_out && world != 1) { set_err(errbuf, errlen, "the record stream is written by a single process"); return SD_ERR_PARAM; }
+    if (nd > 1 && world != 1) return SD_ERR_PARAM;
+    const bool timing = getenv("SD_TIMING") != nullptr;
+    const double t_begin = now_s();
+    double t_prev = t_begin;
+    auto lap = [&](const char* what) {
+        if (!timing) return;
+        const double t = now_s();
+        std::fprintf(stderr, "[sd timing] %-34s %9.2f ms\n", what, (t - t_prev) * 1e3);
+        t_prev = t;
+    };
+    const bool progress = (p->reserved[1] & SD_FLAG_PROGRESS) != 0 && rank == 0;
+    JobInput in;
+    rc = in.load(reads_fa, monomers_fa, p, rank, world, progress, info, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    lap("FASTA index + alphabet check");
+    const std::vector<ReadView>& reads = in.reads;
+    TemplateSet ts(in.monos);
+    sd::PostProcessor pp;
+    rc = pp.init(in.monos, min_identity, second_best != 0, lr_coef, devs[0], p->threads, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    OutFiles files;
+    if (!files.open(raw_tsv_out, final_tsv_out, alt_tsv_out, p->threads)) {
+        set_err(errbuf, errlen, std::string("cannot write ") + raw_tsv_out);
+        return SD_ERR_IO;
+    }
+    sd::RecordsWriter rec_w;   // the rows once more as the binary record stream (sd_records.hpp), written as reads complete
+    if (records_out) {
+        rc = rec_w.open(records_out, *p, ts.tnames, err);
+        if (rc) { set_err(errbuf, errlen, err); return rc; }
+    }
+    if (second_best && min_identity <= 0) files.reserve_alt(alt_size_estimate(in.monos, reads), t_begin);
+    RowJob job;
+    job.n_reads = (int32_t)reads.size();
+    job.threads = p->threads;
+    build_chunk_table(reads, p, job.table, job.nch);
+    if (info) info[3] = (int64_t)job.table.size();
+    lap("chunk table");
+    job.row_off = static_cast<int64_t*>(std::calloc(reads.size() + 1, sizeof(int64_t)));
+    if (!job.row_off) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
+    // identities of the final TSV in-stream, behind every batch's compaction (sd_ident.hip); template sets the kernel
+    // does not take (and SD_IDENT_STREAM=0, developer A/B) leave them to the post-processing as in round 2
+    std::atomic<bool> stream_ident{false};
+    std::vector<std::string> pkeys(nd), entry_err(nd);
+    {
+        sd_params pe = *p;
+        apply_env_overrides(pe);
+        stream_ident = !(pe.reserved[1] & SD_FLAG_NO_STREAM_IDENT);
+        for (size_t i = 0; i < nd; ++i) {   // keyed by the entry's device and, beyond the first, its index
+            pe.device = devs[i];
+            pkeys[i] = pipe_cache_key(pe, second_best ? '2' : '1', ts.mseq, ts.mlen);   // (host threads do not shape an engine)
+            if (i > 0) pkeys[i] += "#entry " + std::to_string(i);
+        }
+    }
+    std::vector<std::unique_ptr<Pipeline>> pipes(nd);
+    std::vector<int64_t> entry_budget(nd, 0);
+    std::atomic<bool> reused{true};
+    auto on_engine = [&](sd_engine* e) {
+        if (stream_ident && !engine_set_identity(e, pp.interleaved_seqs(), pp.own_interleaved(), second_best != 0)) stream_ident = false;
+    };
+    // the pipeline of entry i, from the cache or new, and its budget (hipMemGetInfo of the entry's device)
+    auto open_pipe = [&](int i) -> int {
+        sd_params pi = *p;
+        pi.device = devs[(size_t)i];
+        std::unique_ptr<Pipeline>& h = pipes[(size_t)i];
+        h = getenv("SD_PIPE_CACHE_OFF") ? nullptr : pipe_cache_take(pkeys[(size_t)i]);
+        const bool cached = h != nullptr;
+        if (!cached) { h.reset(new Pipeline); reused = false; }
+        h->restart_idle = true;
+        h->on_engine = on_engine;
+        if (cached) {
+            h->begin_job(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
+            if (!h->ident_ok) stream_ident = false;
+        } else if (const int r = h->create(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size())) {
+            entry_err[(size_t)i] = h->eb;
+            return r;
+        }
+        entry_budget[(size_t)i] = h->row_budget();
+        return SD_OK;
+    };
+    rc = on_entries(devs, entry_err, err, open_pipe, [] {});
+    for (std::unique_ptr<Pipeline>& h : pipes)
+        if (!h) { h.reset(new Pipeline); reused = false; }   // (an entry whose device could not be selected)
+    lap(reused ? "pipeline from the cache" : "engine (HIP runtime start, layout plan, tables, identity masks)");
+    if (stream_ident) job.per = second_best ? (int)pp.interleaved_seqs().size() : 1;
+    const bool slice_ident = second_best && !getenv("SD_IDENT_SLICES_OFF");
+    std::vector<std::pair<size_t, size_t>> batches;
+    if (rc == SD_OK) plan_job(job, entry_budget, devs, p, second_best != 0, slice_ident, reused, batches);
+    lap("batch plan");
+    const double t_setup = now_s() - t_begin;
+    if (progress) std::fprintf(stderr, "Prepared reads\n");   // main.cpp:82
+    TextStages text(reads, ts, pp, records_out ? &rec_w : nullptr, files, raw_tsv_out, progress, second_best != 0, timing, t_begin);
+    text.start();
+    std::vector<int64_t> dealt(nd, 0);   // batches per entry
+    if (rc == SD_OK) {
+        // One driver per entry takes the lowest batch nobody has whenever its pipeline can take one (a pipeline pushes
+        // until all its slots are busy, then waits for its oldest batch), and hands its batches' records to the assembler
+        // in batch order (BatchTurns).  Every HIP call of a pipeline -- engines, streams, events, copies, identity slices
+        // -- is made on its driver's thread; the text stages make none.
+        BatchTurns turns;
+        std::atomic<size_t> next_batch{0};
+        auto drive = [&](int i) {
+            Pipeline& pq = *pipes[(size_t)i];
+            std::vector<const char*> cptr;
+            std::vector<int32_t> clen;
+            std::vector<int> slice_end;
+            auto push = [&](size_t b) {
+                const size_t c0 = batches[b].first, c1 = batches[b].second;
+                batch_chunks(reads, job.table, c0, c1, cptr, clen);
+                slice_end.clear();
+                if (slice_ident && stream_ident) ident_slices(job.table, c0, c1, slice_end);
+                const int r = pq.push(cptr, clen, [&turns, &job, &pq, &text, b, c0, c1](const sd_rec* rr, const int64_t* ro, size_t first, size_t n) {
+                    if (turns.wait(b)) assemble(job, pq, c0 + first, c0 + first + n, rr, ro, text);
+                    if (c0 + first + n == c1) turns.done(b);
+                }, slice_end);
+                if (r) entry_err[(size_t)i] = pq.eb;   // (what failed first, not a pop while the pipeline drains)
+                return r;
+            };
+            const int r = drive_entry(pq, turns, next_batch, batches.size(), text.rc, push, dealt[(size_t)i]);
+            if (r && entry_err[(size_t)i].empty()) entry_err[(size_t)i] = pq.eb;
+            return r;
+        };
+        rc = on_entries(devs, entry_err, err, drive, [&turns] { turns.abort(); });
+    }
+    text.finish();
+    if (rc == SD_OK && text.failed()) { rc = text.rc.load(); err = text.err; }
+    if (!files.close() && rc == SD_OK) { rc = SD_ERR_IO; err = std::string("short write to ") + raw_tsv_out; }
+    if (records_out && rc == SD_OK) rc = rec_w.close(err, records_out);
+    report_stats(pipes, dealt, text, pp, batches.size(), t_setup);
+    for (size_t i = 0; i < nd; ++i) {
+        pipes[i]->ident_ok = stream_ident;
+        pipes[i]->on_engine = nullptr;   // (it refers to this call's locals)
+        if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkeys[i], std::move(pipes[i]), (int)i);
     }
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     return SD_OK;
+} catch (const std::bad_alloc&) {
+    set_err(errbuf, errlen, "out of host memory");
+    return SD_ERR_INTERNAL;
 }
+
 
 int sd_run_files_records(const char* reads_fa, const char* monomers_fa, const sd_params* p, const char* raw_tsv_out,
                          const char* final_tsv_out, const char* alt_tsv_out, const char* records_out, int32_t min_identity,
@@ -840,9 +885,6 @@ int sd_run_files_devices(const char* reads_fa, const char* monomers_fa, const sd
     }
     sd_params q = *p;
     q.device = devices[0];
-    if (n_devices == 1)   // the single-device path as it is, pipeline cache included
-        return run_files_impl(reads_fa, monomers_fa, &q, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
-                              lr_coef, nullptr, errbuf, errlen, records_out);
     const std::vector<int32_t> devs(devices, devices + n_devices);
     return run_files_impl(reads_fa, monomers_fa, &q, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
                           lr_coef, nullptr, errbuf, errlen, records_out, &devs);

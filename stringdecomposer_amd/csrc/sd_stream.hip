@@ -68,12 +68,7 @@ int sd_stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* 
     int rc = SD_OK;
     for (size_t b = 0; b < batches.size() && rc == SD_OK; ++b) {
         const size_t c0 = batches[b].first, c1 = batches[b].second;
-        cptr.clear();
-        clen.clear();
-        for (size_t c = c0; c < c1; ++c) {
-            cptr.push_back(read_seqs[jp->table[c].read] + jp->table[c].off);
-            clen.push_back(jp->table[c].len);
-        }
+        batch_chunks(read_seqs, jp->table, c0, c1, cptr, clen);
         rc = s->pipe.push(cptr, clen, [jp, c0, c1](const sd_rec* r, const int64_t* ro, size_t first, size_t n) {
             jp->add(c0 + first, c0 + first + n, r, ro);
             if (c0 + first + n == c1) --jp->batches_left;

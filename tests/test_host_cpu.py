@@ -6,6 +6,8 @@ import ctypes
 import hashlib
 import os
 import re
+import shutil
+import tempfile
 
 import numpy as np
 import pytest
@@ -38,6 +40,26 @@ def test_no_cpu_fallback_without_device():
     with pytest.raises(lib.SdError) as e:
         lib.decompose(["r"], [b"ACGT" * 10], mn, ms)
     assert e.value.code == lib.SD_ERR_NO_DEVICE
+    # the whole CLI job with an _alt text large enough that its pages are reserved ahead on a helper thread: the job
+    # fails when it opens its pipeline, the helper is joined and the _alt file is cut back to what was written
+    rn, rs = synth.make_reads(ms, 300, read_len=30000, seed=1)
+    lmean = sum(len(s) for s in ms) / len(ms)
+    nmean = sum(len(n) + 0.5 for n in mn) / len(mn)
+    est = sum((len(s) / max(1.0, lmean) + 1.0) * 2.0 * len(ms) * (len(n) + nmean + 2.0 * len(str(len(s))) + 12)
+              for n, s in zip(rn, rs))   # as the job estimates the size of the _alt TSV
+    assert est > 32 << 20
+    d = tempfile.mkdtemp(dir="/dev/shm")
+    try:
+        rfa, mfa = os.path.join(d, "r.fa"), os.path.join(d, "m.fa")
+        synth.write_fasta(rfa, rn, rs)
+        synth.write_fasta(mfa, mn, ms)
+        out = [os.path.join(d, x + ".tsv") for x in ("raw", "final", "alt")]
+        with pytest.raises(lib.SdError) as e:
+            lib.run_files(rfa, mfa, *out, second_best=True, min_identity=0)
+        assert e.value.code == lib.SD_ERR_NO_DEVICE
+        assert os.path.getsize(out[2]) == 0
+    finally:
+        shutil.rmtree(d)
 
 
 def test_param_validation_is_host_side():
