@@ -59,7 +59,7 @@ typedef struct sd_params {
 #define SD_FLAG_NO_EDTHR_COMPACT 4 /* --ed_thr with > 128 templates: every chunk on the W-wave ranked kernel (a set
                                     * beyond eight waves, whose only fast form is the compacted one: generic family)   */
 #define SD_FLAG_FILTER_GENERAL 8   /* --ed_thr: the general prefilter kernel instead of the uniform one             */
-#define SD_FLAG_NO_STREAM_IDENT 16 /* sd_run_files: identities from the read text in the post-processing (round 2)  */
+#define SD_FLAG_NO_STREAM_IDENT 16 /* sd_run_files, final-mode streams: identities from the read text (round 2)     */
 #define SD_FLAG_TRACE_V1 64        /* the one-block int32 traceback (sd_fast_trace) where the packed two-block form would run */
 #define SD_FLAG_NO_IDENT_PRUNE 256 /* sd_run_files --second-best: every homopolymer-compressed pair aligned in full (rounds 3-5; A/B) */
 #define SD_FLAG_PROGRESS 32        /* sd_run_files: the reference binary's progress lines on stderr ("Scores: ...",
@@ -385,9 +385,51 @@ int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n
 /* Accumulated over all collected batches: [0] fill [1] traceback [2] compaction [3] whole-run HIP-event
  * ms (per-batch spans; batches on the two streams overlap, so these do not add up to wall time),
  * [4] fill launches [5] batches [6] chunk rows, host ms: [7] pack+enqueue [8] wait for the device
- * [9] assembly [10] inside submit [11] inside collect, [12] jobs [13] sub_batches [14] row budget. */
+ * [9] assembly [10] inside submit [11] inside collect, [12] jobs [13] sub_batches [14] row budget, [15] 0
+ * (the identity figures of a final-mode stream: sd_stream_final_stats). */
 int sd_stream_stats(sd_stream* s, double out[16]);
 int sd_stream_info(sd_stream* s, int64_t info[8]);   /* as sd_engine_info, of the stream's engine */
+
+/* ---- final mode of the stream: the rows of final_decomposition.tsv / _alt.tsv in host memory -----------------
+ * The same jobs, but collect returns what the command line writes (main.py:107-165) as typed rows instead of the raw
+ * DP rows.  The identities come from the in-stream kernels (csrc/sd_ident.hip) that run on the 2-bit reads already
+ * on the device behind each batch's compaction; pairs those kernels do not take (a segment over their length limit, a
+ * pair edlib aligns by Hirschberg's split, a batch whose identity outputs had no room) take the fallback of the file
+ * path (sd_identity_segments_dev, then the host).  The selection rules are the ones sd_run_files formats with.
+ *
+ * One kept block (a row of final_decomposition.tsv).  Names are key indices into sd_stream_keys (-1: "None"); the
+ * identities are the doubles the text prints with "%.2f" (-1 where it prints -1.00). */
+typedef struct sd_final_row {
+    int32_t read;                    /* read index within its job                                           */
+    int64_t start, end;              /* read-global, inclusive (as in the raw TSV)                            */
+    int32_t best, second, homo_best, homo_second;
+    double ident, second_ident, homo_ident, homo_second_ident;
+    int8_t reliable;                 /* 1: '+', 0: '?' (classify, main.py:95-104)                             */
+} sd_final_row;
+/* sd_stream_create's arguments plus the monomer names (the first header token: names are the keys, a repeated name
+ * is one key), main.py's -i (min_identity), --second-best and the three logistic-regression coefficients.
+ * SD_ERR_PARAM before any device work for a missing name, n_mono <= 0 or lr_coef NULL.
+ * sd_stream_submit of a final-mode stream COPIES the reads (the buffers are still free on return, as in the raw mode):
+ * the fallback identities of a batch need the read text when its rows come back, which can be at a later submit or
+ * at collect.  (Keeping the caller's buffers alive until collect instead would make a raw-mode rule depend on the
+ * mode; the copy is one memcpy per read, on the stream's host threads.) */
+int sd_stream_create_final(sd_stream** out, const sd_params* p, const char* const* mono_names,
+                           const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
+                           int32_t sub_batches, int32_t min_identity, int32_t second_best,
+                           const double* lr_coef, char* errbuf, size_t errlen);
+/* Kept rows of the oldest submitted job (FIFO), in read order: read r owns rows[row_off[r] .. row_off[r+1]).
+ * alt (may be NULL; NULL is returned without second_best): n_rows x n_keys identities in key order, the _alt rows
+ * of each kept block (main.py:161-165; the block's own key is `best`).  All arrays malloc'ed (sd_free).
+ * SD_ERR_PARAM on a stream made by sd_stream_create (and sd_stream_collect on a final-mode stream). */
+int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off, int64_t* n_rows, double** alt,
+                            char* errbuf, size_t errlen);
+/* The distinct monomer names in key order (m0, m0', m1, m1', ... first occurrences): up to cap pointers, valid
+ * until sd_stream_destroy; *n_keys = the number of keys.  SD_ERR_PARAM on a stream not in final mode. */
+int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys);
+/* Identities of a final-mode stream, accumulated over its collected batches: [0] in-stream identity kernels, ms (HIP
+ * events, as sd_last_run_stats [3]), [1] pairs computed in-stream (as [4]), [2] blocks whose identities came from
+ * the fallback, [3] kept rows.  All 0 on a stream not in final mode. */
+int sd_stream_final_stats(sd_stream* s, double out[4]);
 
 /* ---- host-side pieces of the path, exported for CPU-only tests ----------------------------- */
 

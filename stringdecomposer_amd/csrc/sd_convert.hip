@@ -63,6 +63,8 @@ int PostProcessor::init(const std::vector<Seq>& monos, int min_identity_, bool s
         own_il_of_t[t] = kcol[(size_t)key_of_t[t]];   // light mode keeps the last monomer of that name (main.py:112-116)
     }
     own_il32.assign(own_il_of_t.begin(), own_il_of_t.end());
+    key_of_il.assign(il_name.size(), -1);
+    for (size_t x = 0; x < il_name.size(); ++x) key_of_il[x] = kidx[il_name[x]];
     return SD_OK;
 }
 
@@ -150,26 +152,15 @@ int PostProcessor::process(const PostRead* reads, size_t n_reads, const sd_rec* 
     return SD_OK;
 }
 
-int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off,
-                                 std::vector<std::string>& pf, std::vector<TextBuf>& pa, std::string& err,
-                                 const IdentRef* ident) {
-    // (pf / pa may come back from an earlier call: their elements keep their memory -- a fresh 0.5-MB buffer per slice of
-    // blocks is an mmap and a few hundred page faults, 280 MB of them per C4 --second-best job)
-    const int64_t nB = row_off[n_reads];
-    if (nB == 0) { pf.clear(); pa.clear(); return SD_OK; }
+int PostProcessor::prepare(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off,
+                           const IdentRef* ident, Batch& bt, std::string& err) {
     const double t_0 = now_seconds();
-    const int T = (int)il_seq.size();
-    const int nK = (int)keys.size();
-    const int per = second_best ? T : 1;
+    const int64_t nB = row_off[n_reads];
+    bt.ident = ident;
+    bt.per = second_best ? (int)il_seq.size() : 1;
+    const int per = bt.per;
     bool have = ident && ident->id && (!second_best || ident->idh);
     bool host_only = false;   // the batch holds a pair edlib aligns by Hirschberg's split
-    // words of row b (plain / compressed)
-    auto words = [&](int64_t b, bool homo) -> const uint32_t* {
-        if (!ident->src) return (homo ? ident->idh : ident->id) + (size_t)b * (size_t)per;
-        const int64_t sx = ident->src[b];
-        return sx >= 0 ? (homo ? ident->idh : ident->id) + (size_t)sx * (size_t)per
-                       : (homo ? ident->xidh : ident->xid) + (size_t)(-1 - sx) * (size_t)per;
-    };
     if (have) {
         // every word computed?  (0xffffffff: a pair the kernel left out; dist + matches == 0 cannot be an alignment)
         std::vector<uint8_t> bad((size_t)((nB + 4095) / 4096), 0);
@@ -177,10 +168,10 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
             const int64_t e = std::min<int64_t>(nB, (blk + 1) * 4096);
             uint8_t bb = 0;
             for (int64_t b = blk * 4096; b < e; ++b) {
-                const uint32_t* v = words(b, false);
+                const uint32_t* v = bt.words(b, false);
                 for (int x = 0; x < per; ++x) bb |= (uint8_t)(v[x] == 0xffffffffu || v[x] == 0u);
                 if (second_best) {
-                    const uint32_t* h = words(b, true);
+                    const uint32_t* h = bt.words(b, true);
                     for (int x = 0; x < per; ++x) bb |= (uint8_t)(h[x] == 0xffffffffu || h[x] == 0u);
                 }
             }
@@ -191,7 +182,8 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
     // text = the reads that have blocks, concatenated; blocks never cross a read
     std::vector<std::pair<const char*, int64_t>> spans;
     std::vector<int64_t> seg_start((size_t)nB);
-    std::vector<int32_t> seg_len((size_t)nB), read_of((size_t)nB);
+    std::vector<int32_t> seg_len((size_t)nB);
+    bt.read_of.resize((size_t)nB);
     {
         int64_t pos = 0;
         for (size_t r = 0; r < n_reads; ++r) {
@@ -204,7 +196,7 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
                 const int64_t e1 = std::min<int64_t>(std::max<int64_t>((int64_t)x.end + 1, s0), reads[r].len);
                 seg_start[(size_t)b] = pos + s0;
                 seg_len[(size_t)b] = (int32_t)std::min<int64_t>(e1 - s0, 0x7fffffff);
-                read_of[(size_t)b] = (int32_t)r;
+                bt.read_of[(size_t)b] = (int32_t)r;
             }
             spans.emplace_back(reads[r].seq, reads[r].len);
             pos += reads[r].len;
@@ -224,24 +216,91 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
         host_only = edlib_splits(worst, (int64_t)tmax) && tmax <= 512;
         if (edlib_splits(worst, (int64_t)tmax)) have = false;
     }
-    const bool id = have;   // identities came with the rows
+    bt.id = have;   // identities came with the rows
     const double t_a = now_seconds();
-    RawVec<double> vals, hvals;
     int rc;
-    if (id) {
+    if (bt.id) {
         // identities came with the rows
     } else if (!second_best) {
         std::vector<int32_t> pair((size_t)nB);
         for (int64_t b = 0; b < nB; ++b) pair[(size_t)b] = own_il_of_t[(size_t)rows[b].tmpl];
-        rc = identities(spans, seg_start, seg_len, pair.data(), false, vals, err, host_only);
+        rc = identities(spans, seg_start, seg_len, pair.data(), false, bt.vals, err, host_only);
         if (rc) return rc;
     } else {
-        rc = identities(spans, seg_start, seg_len, nullptr, false, vals, err, host_only);
+        rc = identities(spans, seg_start, seg_len, nullptr, false, bt.vals, err, host_only);
         if (rc) return rc;
-        rc = identities(spans, seg_start, seg_len, nullptr, true, hvals, err, host_only);
+        rc = identities(spans, seg_start, seg_len, nullptr, true, bt.hvals, err, host_only);
         if (rc) return rc;
     }
+    if (!bt.id) fallback_blocks += nB;
+    t_prepare += t_a - t_0;
+    t_identity += now_seconds() - t_a;
+    return SD_OK;
+}
+
+bool PostProcessor::select(const Batch& bt, const sd_rec* rows, int64_t b, double* kbuf, double* hbuf, sd_final_row& f) const {
+    const int T = (int)il_seq.size();
+    const int nK = (int)keys.size();
+    const sd_rec& x = rows[b];
+    const int ko = key_of_t[(size_t)x.tmpl];
+    double score, sbs = -1, h0s = -1, h1s = -1;
+    int sb = -1, h0 = -1, h1 = -1;
+    if (!second_best) {
+        score = bt.id ? ident_percent(bt.words(b, false)[0]) : bt.vals[(size_t)b];
+    } else {
+        if (bt.id) {
+            const uint32_t* v = bt.words(b, false);
+            for (int k = 0; k < nK; ++k) kbuf[k] = ident_percent(v[kcol[(size_t)k]]);
+            const uint32_t* hw = bt.words(b, true);
+            for (int j = 0; j < T; ++j) hbuf[j] = ident_percent(hw[j]);
+        } else {
+            const double* v = &bt.vals[(size_t)b * T];
+            for (int k = 0; k < nK; ++k) kbuf[k] = v[kcol[(size_t)k]];
+        }
+        score = kbuf[ko];
+        for (int k = 0; k < nK; ++k) {   // main.py:124-128: first maximum among the other names
+            if (k == ko) continue;
+            if (sb < 0 || sbs < kbuf[k]) { sb = k; sbs = kbuf[k]; }
+        }
+        if (sb < 0) sbs = -1;
+        // main.py:130-135: all monomers (the own one included), stable sort by -score: ranks 0 and 1
+        const double* h = bt.id ? hbuf : &bt.hvals[(size_t)b * T];
+        int i0 = 0;
+        for (int j = 1; j < T; ++j) if (h[j] > h[i0]) i0 = j;
+        int i1 = -1;
+        for (int j = 0; j < T; ++j) {
+            if (j == i0) continue;
+            if (i1 < 0 || h[j] > h[i1]) i1 = j;
+        }
+        h0 = key_of_il[(size_t)i0]; h0s = h[i0];
+        if (i1 >= 0) { h1 = key_of_il[(size_t)i1]; h1s = h[i1]; }
+    }
+    if (!(score >= (double)min_identity)) return false;     // main.py:156
+    // classify (main.py:95-104): intercept + c1 * identity + c2 * (identity - second best) > 0
+    const double logit = (1.0 * coef[0] + score * coef[1]) + (score - sbs) * coef[2];
+    std::memset(&f, 0, sizeof f);   // (padding too: callers of the C-ABI get the same bytes for the same rows)
+    f.read = bt.read_of[(size_t)b];
+    f.start = x.start;
+    f.end = x.end;
+    f.best = ko; f.second = sb; f.homo_best = h0; f.homo_second = h1;
+    f.ident = score; f.second_ident = sbs; f.homo_ident = h0s; f.homo_second_ident = h1s;
+    f.reliable = logit > 0 ? 1 : 0;
+    return true;
+}
+
+int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off,
+                                 std::vector<std::string>& pf, std::vector<TextBuf>& pa, std::string& err,
+                                 const IdentRef* ident) {
+    // (pf / pa may come back from an earlier call: their elements keep their memory -- a fresh 0.5-MB buffer per slice of
+    // blocks is an mmap and a few hundred page faults, 280 MB of them per C4 --second-best job)
+    const int64_t nB = row_off[n_reads];
+    if (nB == 0) { pf.clear(); pa.clear(); return SD_OK; }
+    Batch bt;
+    const int rc = prepare(reads, n_reads, rows, row_off, ident, bt, err);
+    if (rc) return rc;
     const double t_b = now_seconds();
+    const int T = (int)il_seq.size();
+    const int nK = (int)keys.size();
     // rows -> text, in slices of blocks formatted by all threads
     const int64_t grain = second_best ? 64 : 2048;
     const int64_t n_sl = (nB + grain - 1) / grain;
@@ -264,71 +323,31 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
         if (second_best) oa.resize((size_t)(b1 - sl * grain) * (key_bytes + (size_t)nK * alt_row_max));
         char* wa = oa.data();
         std::vector<double> kbuf((size_t)nK), hbuf((size_t)T);
+        static const std::string none = "None";
+        auto name = [&](int k) -> const std::string& { return k >= 0 ? keys[(size_t)k] : none; };
         for (int64_t b = sl * grain; b < b1; ++b) {
-            const sd_rec& x = rows[b];
-            const PostRead& rd = reads[(size_t)read_of[(size_t)b]];
-            const int ko = key_of_t[(size_t)x.tmpl];
-            double score, sbs = -1, h0s = -1, h1s = -1;
-            const std::string* sbn = nullptr;
-            const std::string* h0n = nullptr;
-            const std::string* h1n = nullptr;
-            const double* kv = nullptr;
-            if (!second_best) {
-                score = id ? ident_percent(words(b, false)[0]) : vals[(size_t)b];
-            } else {
-                if (id) {
-                    const uint32_t* v = words(b, false);
-                    for (int k = 0; k < nK; ++k) kbuf[(size_t)k] = ident_percent(v[kcol[(size_t)k]]);
-                    const uint32_t* hw = words(b, true);
-                    for (int j = 0; j < T; ++j) hbuf[(size_t)j] = ident_percent(hw[j]);
-                } else {
-                    const double* v = &vals[(size_t)b * T];
-                    for (int k = 0; k < nK; ++k) kbuf[(size_t)k] = v[kcol[(size_t)k]];
-                }
-                kv = kbuf.data();
-                score = kv[ko];
-                int sb = -1;   // main.py:124-128: first maximum among the other names
-                for (int k = 0; k < nK; ++k) {
-                    if (k == ko) continue;
-                    if (sb < 0 || sbs < kv[k]) { sb = k; sbs = kv[k]; }
-                }
-                if (sb >= 0) sbn = &keys[(size_t)sb];
-                else sbs = -1;
-                // main.py:130-135: all monomers (the own one included), stable sort by -score: ranks 0 and 1
-                const double* h = id ? hbuf.data() : &hvals[(size_t)b * T];
-                int i0 = 0;
-                for (int j = 1; j < T; ++j) if (h[j] > h[i0]) i0 = j;
-                int i1 = -1;
-                for (int j = 0; j < T; ++j) {
-                    if (j == i0) continue;
-                    if (i1 < 0 || h[j] > h[i1]) i1 = j;
-                }
-                h0n = &il_name[(size_t)i0]; h0s = h[i0];
-                if (i1 >= 0) { h1n = &il_name[(size_t)i1]; h1s = h[i1]; }
-            }
-            if (!(score >= (double)min_identity)) continue;     // main.py:156
-            // classify (main.py:95-104): intercept + c1 * identity + c2 * (identity - second best) > 0
-            const double logit = (1.0 * coef[0] + score * coef[1]) + (score - sbs) * coef[2];
-            static const std::string none = "None";
+            sd_final_row f;
+            if (!select(bt, rows, b, kbuf.data(), hbuf.data(), f)) continue;
+            const PostRead& rd = reads[(size_t)f.read];
             of.append(rd.name, rd.name_len); of.push_back('\t');
-            of.append(tname[(size_t)x.tmpl]); of.push_back('\t');
-            put_int(of, x.start); of.push_back('\t');
-            put_int(of, x.end); of.push_back('\t');
-            put_f2(of, score); of.push_back('\t');
-            of.append(sbn ? *sbn : none); of.push_back('\t');
-            put_f2(of, sbs); of.push_back('\t');
-            of.append(h0n ? *h0n : none); of.push_back('\t');
-            put_f2(of, h0s); of.push_back('\t');
-            of.append(h1n ? *h1n : none); of.push_back('\t');
-            put_f2(of, h1s); of.push_back('\t');
-            of.push_back(logit > 0 ? '+' : '?');
+            of.append(keys[(size_t)f.best]); of.push_back('\t');
+            put_int(of, f.start); of.push_back('\t');
+            put_int(of, f.end); of.push_back('\t');
+            put_f2(of, f.ident); of.push_back('\t');
+            of.append(name(f.second)); of.push_back('\t');
+            put_f2(of, f.second_ident); of.push_back('\t');
+            of.append(name(f.homo_best)); of.push_back('\t');
+            put_f2(of, f.homo_ident); of.push_back('\t');
+            of.append(name(f.homo_second)); of.push_back('\t');
+            put_f2(of, f.homo_second_ident); of.push_back('\t');
+            of.push_back(f.reliable ? '+' : '?');
             of.push_back('\n');
             if (second_best) {   // main.py:161-165: one row per name of the dict
                 char mid[32];    // "\t<start>\t<end>\t": the same for the nK rows of the block
                 size_t ml = 0;
                 {
                     std::string t;
-                    t.push_back('\t'); put_int(t, x.start); t.push_back('\t'); put_int(t, x.end); t.push_back('\t');
+                    t.push_back('\t'); put_int(t, f.start); t.push_back('\t'); put_int(t, f.end); t.push_back('\t');
                     ml = t.size();
                     std::memcpy(mid, t.data(), ml);
                 }
@@ -338,15 +357,64 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
                     const std::string& key = keys[(size_t)k];
                     std::memcpy(wa, key.data(), key.size()); wa += key.size();
                     std::memcpy(wa, mid, ml); wa += ml;
-                    wa = put_fixed2_at(wa, kv[k]);
-                    std::memcpy(wa, k == ko ? "\t*\n" : "\t-\n", 3); wa += 3;
+                    wa = put_fixed2_at(wa, kbuf[(size_t)k]);
+                    std::memcpy(wa, k == f.best ? "\t*\n" : "\t-\n", 3); wa += 3;
                 }
             }
         }
         if (second_best) oa.resize((size_t)(wa - oa.data()));
     });
-    t_prepare += t_a - t_0;
-    t_identity += t_b - t_a;
+    t_format += now_seconds() - t_b;
+    return SD_OK;
+}
+
+int PostProcessor::process_rows(const PostRead* reads, size_t n_reads, int32_t read0, const sd_rec* rows,
+                                const int64_t* row_off, HeapArray<sd_final_row>& out, HeapArray<double>& alt,
+                                std::string& err, const IdentRef* ident) {
+    const int64_t nB = row_off[n_reads];
+    if (nB == 0) return SD_OK;
+    Batch bt;
+    const int rc = prepare(reads, n_reads, rows, row_off, ident, bt, err);
+    if (rc) return rc;
+    const double t_b = now_seconds();
+    const int T = (int)il_seq.size();
+    const size_t nK = keys.size();
+    // room for every block; each slice of blocks writes its kept ones at its own place, and the slices are then closed up
+    // (nothing moves when no block is filtered out)
+    const size_t o0 = out.n;
+    if (!out.resize(o0 + (size_t)nB) || (second_best && !alt.resize((o0 + (size_t)nB) * nK))) {
+        err = "out of host memory";
+        return SD_ERR_INTERNAL;
+    }
+    const int64_t grain = second_best ? 64 : 2048;
+    const int64_t n_sl = (nB + grain - 1) / grain;
+    std::vector<int64_t> kept((size_t)n_sl, 0);
+    parallel_for(n_sl, threads, 1, [&](int64_t sl) {
+        const int64_t b1 = std::min(nB, (sl + 1) * grain);
+        std::vector<double> hbuf((size_t)T);
+        int64_t k = 0;
+        for (int64_t b = sl * grain; b < b1; ++b) {
+            const size_t at = o0 + (size_t)(sl * grain + k);
+            double* kv = second_best ? alt.p + at * nK : nullptr;   // (light mode: no per-key identities)
+            sd_final_row f;
+            if (!select(bt, rows, b, kv, hbuf.data(), f)) continue;
+            f.read += read0;
+            std::memcpy(out.p + at, &f, sizeof f);
+            ++k;
+        }
+        kept[(size_t)sl] = k;
+    });
+    size_t to = o0;
+    for (int64_t sl = 0; sl < n_sl; ++sl) {
+        const size_t from = o0 + (size_t)(sl * grain), k = (size_t)kept[(size_t)sl];
+        if (from != to && k) {
+            std::memmove(out.p + to, out.p + from, k * sizeof(sd_final_row));
+            if (second_best) std::memmove(alt.p + to * nK, alt.p + from * nK, k * nK * sizeof(double));
+        }
+        to += k;
+    }
+    out.n = to;
+    if (second_best) alt.n = to * nK;
     t_format += now_seconds() - t_b;
     return SD_OK;
 }

@@ -2,7 +2,9 @@
 // rows of final_decomposition.tsv / _alt.tsv (stringdecomposer/main.py:107-165).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <utility>
 #include <vector>
@@ -29,6 +31,30 @@ struct IdentRef {
     const uint32_t* xidh = nullptr;
 };
 
+// A malloc'ed array that grows by realloc (a large block moves by remapping its pages, not by a copy) and hands its block
+// to a caller of the C-ABI, who frees it with sd_free.
+template <class T>
+struct HeapArray {
+    T* p = nullptr;
+    size_t n = 0, cap = 0;
+    HeapArray() = default;
+    HeapArray(const HeapArray&) = delete;
+    HeapArray& operator=(const HeapArray&) = delete;
+    ~HeapArray() { std::free(p); }
+    bool resize(size_t m) {   // false: out of memory (the contents are kept)
+        if (m > cap) {
+            const size_t c = std::max(m, cap * 2);
+            T* q = static_cast<T*>(std::realloc(p, std::max<size_t>(c, 1) * sizeof(T)));
+            if (!q) return false;
+            p = q;
+            cap = c;
+        }
+        n = m;
+        return true;
+    }
+    T* release() { T* q = p; p = nullptr; n = cap = 0; return q; }
+};
+
 class PostProcessor {
   public:
     // monomers in file order (names = first header token, sequences upper-case); device < 0: host identities
@@ -46,20 +72,47 @@ class PostProcessor {
     int process_parts(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off,
                       std::vector<std::string>& fin_parts, std::vector<TextBuf>& alt_parts, std::string& err,
                       const IdentRef* ident = nullptr);
+    // the same selection as typed rows (the final mode of sd_stream): the kept blocks are APPENDED to `out` in block
+    // order, their read = read0 + index into reads; with second_best their identities in key order to `alt` (nK each)
+    int process_rows(const PostRead* reads, size_t n_reads, int32_t read0, const sd_rec* rows, const int64_t* row_off,
+                     HeapArray<sd_final_row>& out, HeapArray<double>& alt, std::string& err,
+                     const IdentRef* ident = nullptr);
+    const std::vector<std::string>& key_names() const { return keys; }   // distinct names, first-occurrence order
     const std::vector<std::string>& interleaved_seqs() const { return il_seq; }   // m0, m0', m1, m1', ... (main.py:79-84)
     const std::vector<int32_t>& own_interleaved() const { return own_il32; }      // DP template -> interleaved index
     int tmpl_of_name(const std::string& nm) const;   // first template of that name in the DP's order, -1 if none
     std::vector<std::string> tname;                  // the DP's template names: m, ..., m', ...
     double t_prepare = 0, t_identity = 0, t_format = 0, t_concat = 0;   // seconds spent in process(), by stage
+    int64_t fallback_blocks = 0;     // blocks whose identities were computed here, not taken from the rows' words
 
   private:
+    // a batch's identities as the selection reads them: the words that came with the rows (id) or the values
+    // computed from the read text (vals: own / all interleaved templates, hvals: homopolymer-compressed)
+    struct Batch {
+        const IdentRef* ident = nullptr;
+        bool id = false;
+        int per = 1;
+        RawVec<double> vals, hvals;
+        std::vector<int32_t> read_of;    // block -> index into reads
+        const uint32_t* words(int64_t b, bool homo) const {   // words of block b (plain / compressed)
+            if (!ident->src) return (homo ? ident->idh : ident->id) + (size_t)b * (size_t)per;
+            const int64_t sx = ident->src[b];
+            return sx >= 0 ? (homo ? ident->idh : ident->id) + (size_t)sx * (size_t)per
+                           : (homo ? ident->xidh : ident->xid) + (size_t)(-1 - sx) * (size_t)per;
+        }
+    };
+    int prepare(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off, const IdentRef* ident,
+                Batch& bt, std::string& err);
+    // main.py:107-150 + classify (:95-104) for block b: false if the block is filtered out (main.py:156); f.read = the
+    // block's index into reads.  kbuf (nK) receives the block's identities in key order with second_best; hbuf (T) is scratch
+    bool select(const Batch& bt, const sd_rec* rows, int64_t b, double* kbuf, double* hbuf, sd_final_row& f) const;
     int identities(const std::vector<std::pair<const char*, int64_t>>& spans, const std::vector<int64_t>& seg_start,
                    const std::vector<int32_t>& seg_len, const int32_t* pair, bool homo, RawVec<double>& out,
                    std::string& err, bool host_only = false);
     std::vector<std::string> il_name, il_seq;        // interleaved m0, m0', m1, m1', ... (main.py:79-84)
     std::vector<std::string> keys;                   // distinct names in first-occurrence order
     std::vector<int> kcol;                           // key -> last interleaved index of that name
-    std::vector<int> key_of_t, own_il_of_t;
+    std::vector<int> key_of_t, own_il_of_t, key_of_il;
     std::vector<int32_t> own_il32;
     int min_identity = 0;
     bool second_best = false;

@@ -778,6 +778,21 @@ inline void batch_chunks(const Reads& reads, const std::vector<CRef>& table, siz
         clen.push_back(table[c].len);
     }
 }
+// The cut of the identities of the chunks [c0, c1) into slices (sd_engine::slice_end): up to eight slices of at least 256
+// chunks, each ending with a read (a read that ends in a later slice would only be carried; the last slice ends the batch).
+inline void ident_slices(const std::vector<CRef>& table, size_t c0, size_t c1, std::vector<int>& slice_end) {
+    const size_t nb = c1 - c0;
+    int n_sl = (int)std::max<size_t>(1, std::min<size_t>(8, nb / 256));
+    if (const char* ev = getenv("SD_IDENT_SLICES")) n_sl = std::max(1, std::min(64, atoi(ev)));   // developer A/B
+    size_t at = 0;
+    for (int sl = 0; sl < n_sl && at < nb; ++sl) {
+        size_t want = sl + 1 == n_sl ? nb : std::max(at + 1, nb * (size_t)(sl + 1) / (size_t)n_sl);
+        while (want < nb && table[c0 + want].read == table[c0 + want - 1].read) ++want;
+        slice_end.push_back((int)want);
+        at = want;
+    }
+    if (slice_end.empty() || slice_end.back() != (int)nb) slice_end.push_back((int)nb);
+}
 // Rows per batch for a pipeline whose engines do not exist yet (the first job of a process, or of a parameter set).
 // Such a job pays for every byte it allocates -- the driver scrubs memory before it hands it out, ~29 ms per GB on the
 // GPU box: the three full-size engines of a 500-Mbp job (50 GB) cost 1.45 s for 0.14 s of device work.  Buffers scale

@@ -576,22 +576,6 @@ static void assemble(RowJob& job, Pipeline& pq, size_t c0, size_t c1, const sd_r
     text.hand_over(std::move(w));
 }
 
-// The cut of the identities of the chunks [c0, c1) into slices (sd_engine::slice_end): up to eight slices of at least 256
-// chunks, each ending with a read (a read that ends in a later slice would only be carried; the last slice ends the batch).
-static void ident_slices(const std::vector<CRef>& table, size_t c0, size_t c1, std::vector<int>& slice_end) {
-    const size_t nb = c1 - c0;
-    int n_sl = (int)std::max<size_t>(1, std::min<size_t>(8, nb / 256));
-    if (const char* ev = getenv("SD_IDENT_SLICES")) n_sl = std::max(1, std::min(64, atoi(ev)));   // developer A/B
-    size_t at = 0;
-    for (int sl = 0; sl < n_sl && at < nb; ++sl) {
-        size_t want = sl + 1 == n_sl ? nb : std::max(at + 1, nb * (size_t)(sl + 1) / (size_t)n_sl);
-        while (want < nb && table[c0 + want].read == table[c0 + want - 1].read) ++want;
-        slice_end.push_back((int)want);
-        at = want;
-    }
-    if (slice_end.empty() || slice_end.back() != (int)nb) slice_end.push_back((int)nb);
-}
-
 // The batches of a job whose pipelines hold entry_budget rows per batch.
 static void plan_job(const RowJob& job, const std::vector<int64_t>& entry_budget, const std::vector<int32_t>& devs,
                      const sd_params* p, bool second_best, bool slice_ident, bool reused,

@@ -135,6 +135,24 @@ def format_alt(rows):
                               "*" if r.best else "-"]) + "\n" for r in rows)
 
 
+def final_rows(final, read_names, keys):
+    """The rows of a final-mode stream job (lib.Stream(final=True).collect(): a FinalRows, or its (rows, row_off, alt))
+    as the command line would write them: ([FinalRow], [AltRow]) -- format_final / format_alt of these are the text of
+    <out>.tsv / <out>_alt.tsv.  read_names: the job's reads in submit order; keys: Stream.keys().  The _alt list is
+    empty without second_best (alt None)."""
+    rows, _, alt = final
+    name = lambda k: keys[k] if k >= 0 else "None"   # noqa: E731
+    fin, alts = [], []
+    for i, r in enumerate(rows.tolist()):
+        read, start, end, best, second, hb, hs, ident, sid, hid, hsid, rel = r
+        fin.append(FinalRow(read_names[read], keys[best], start, end, ident, name(second), sid, name(hb), hid, name(hs),
+                            hsid, "+" if rel else "?"))
+        if alt is not None:
+            for k, v in enumerate(alt[i].tolist()):
+                alts.append(AltRow(read_names[read], keys[k], start, end, v, k == best))
+    return fin, alts
+
+
 def by_read(rows):
     """Group consecutive rows by read name, preserving file order: [(read, [rows])]."""
     out = []

@@ -6,6 +6,7 @@ no CPU fallback; a missing library or a missing GPU is a loud error.
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SD_HIP_LIB lets a developer A/B an alternative build of the same library (never a CPU path)
@@ -42,6 +43,7 @@ EXPORTS = [
     "sd_range_assemble_copy", "sd_range_assemble_stats", "sd_range_assemble_free", "sd_decompose_files_range_begin",
     "sd_range_assemble_records",
     "sd_run_files_devices", "sd_last_run_device_stats", "sd_multi_device_selftest",
+    "sd_stream_create_final", "sd_stream_collect_final", "sd_stream_keys", "sd_stream_final_stats",
 ]
 
 
@@ -62,6 +64,14 @@ class Params(C.Structure):
 class Rec(C.Structure):
     _fields_ = [("tmpl", C.c_int32), ("start", C.c_int32), ("end", C.c_int32),
                 ("score", C.c_int32)]
+
+
+class FinalRec(C.Structure):
+    """sd_final_row (include/sd_hip.h): one kept block of a final-mode stream."""
+    _fields_ = [("read", C.c_int32), ("start", C.c_int64), ("end", C.c_int64), ("best", C.c_int32),
+                ("second", C.c_int32), ("homo_best", C.c_int32), ("homo_second", C.c_int32), ("ident", C.c_double),
+                ("second_ident", C.c_double), ("homo_ident", C.c_double), ("homo_second_ident", C.c_double),
+                ("reliable", C.c_int8)]
 
 
 class Records(C.Structure):
@@ -158,6 +168,12 @@ def load():
     L.sd_stream_submit.argtypes = [C.c_void_p, P(C.c_char_p), P(C.c_int64), C.c_int32, C.c_char_p, C.c_size_t]
     L.sd_stream_collect.argtypes = [C.c_void_p, P(P(Rec)), P(P(C.c_int64)), P(C.c_int64), C.c_char_p, C.c_size_t]
     L.sd_stream_stats.argtypes = [C.c_void_p, P(C.c_double)]
+    L.sd_stream_create_final.argtypes = [P(C.c_void_p), P(Params), P(C.c_char_p), P(C.c_char_p), P(C.c_int32), C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, P(C.c_double), C.c_char_p, C.c_size_t]
+    L.sd_stream_collect_final.argtypes = [C.c_void_p, P(P(FinalRec)), P(P(C.c_int64)), P(C.c_int64), P(P(C.c_double)),
+                                          C.c_char_p, C.c_size_t]
+    L.sd_stream_keys.argtypes = [C.c_void_p, P(C.c_char_p), C.c_int32, P(C.c_int32)]
+    L.sd_stream_final_stats.argtypes = [C.c_void_p, P(C.c_double)]
     L.sd_stream_info.argtypes = [C.c_void_p, P(C.c_int64)]
     L.sd_pack_bases.restype = C.c_int32
     L.sd_pack_bases.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -436,7 +452,7 @@ def decompose(read_names, read_seqs, mono_names, mono_seqs, **kw):
     ml = (C.c_int32 * max(len(ms), 1))(*[len(s) for s in ms])
     out = C.c_void_p()
     ln = C.c_size_t()
-    rc = L.sd_decompose(_strs(read_names), _strs(rs), rl, len(rs), _strs(mono_names), _strs(ms), ml,
+    rc = L.sd_decompose(_strs(read_names), _strs(rs), rl, len(rs), None if mono_names is None else _strs(mono_names), _strs(ms), ml,
                         len(ms), C.byref(p), C.byref(out), C.byref(ln), err, 4096)
     if rc != SD_OK:
         raise SdError(rc, err.value.decode(errors="replace"))
@@ -564,19 +580,55 @@ class ReadSet:
         self.bp = sum(len(s) for s in self.seqs)
 
 
+def final_dtype():
+    """numpy dtype of sd_final_row (include/sd_hip.h): read, start, end, best, second, homo_best, homo_second (key
+    indices into Stream.keys(), -1 = None), ident, second_ident, homo_ident, homo_second_ident, reliable."""
+    import numpy as np
+    dt = np.dtype([("read", "<i4"), ("start", "<i8"), ("end", "<i8"), ("best", "<i4"), ("second", "<i4"),
+                   ("homo_best", "<i4"), ("homo_second", "<i4"), ("ident", "<f8"), ("second_ident", "<f8"),
+                   ("homo_ident", "<f8"), ("homo_second_ident", "<f8"), ("reliable", "i1")], align=True)
+    assert dt.itemsize == C.sizeof(FinalRec)
+    return dt
+
+
+FinalRows = namedtuple("FinalRows", "rows row_off alt")
+"""A final-mode job: rows (numpy, final_dtype()), row_off (n_reads + 1: read r owns rows[row_off[r]:row_off[r+1]]) and
+alt (n_rows x n_keys identities in key order, second_best only, else None)."""
+
+
 class Stream:
     """Pipelined sequences-in-host-memory -> rows-in-host-memory path (sd_stream_*): submit() read sets,
-    collect() their rows in FIFO order; two device batches are in flight across job boundaries."""
+    collect() their rows in FIFO order; two device batches are in flight across job boundaries.
 
-    def __init__(self, mono_seqs, sub_batches=1, **kw):
+    final=True (sd_stream_create_final): collect() returns the rows of final_decomposition.tsv (and, with second_best,
+    of _alt.tsv) as a FinalRows instead of the raw DP rows, with identities computed on the device behind each batch.
+    mono_names are required there (names are the keys: a repeated name is one key); min_identity, second_best and
+    lr_coef are the command line's -i, --second-best and model coefficients (None: models/ont_logreg_model.txt, as
+    the command line reads it).  formats.final_rows turns a FinalRows into FinalRow / AltRow lists."""
+
+    def __init__(self, mono_seqs, sub_batches=1, final=False, mono_names=None, second_best=False, min_identity=0,
+                 lr_coef=None, **kw):
         self.L = load()
         self.params = make_params(**kw)
         self._err = C.create_string_buffer(4096)
         ms = [_b(s) for s in mono_seqs]
         ml = (C.c_int32 * max(len(ms), 1))(*[len(s) for s in ms])
         self.h = C.c_void_p()
-        self._check(self.L.sd_stream_create(C.byref(self.h), C.byref(self.params), _strs(ms), ml, len(ms),
-                                            int(sub_batches), self._err, 4096))
+        self.final = bool(final)
+        self.second_best = bool(second_best)
+        if self.final:
+            if mono_names is not None and len(mono_names) != len(ms):
+                raise SdError(SD_ERR_PARAM, "final=True needs one name per monomer (mono_names)")
+            if lr_coef is None:
+                from .main import _lr_coef
+                lr_coef = _lr_coef()
+            coef = (C.c_double * 3)(*[float(x) for x in lr_coef])
+            self._check(self.L.sd_stream_create_final(C.byref(self.h), C.byref(self.params), None if mono_names is None else _strs(mono_names), _strs(ms),
+                                                      ml, len(ms), int(sub_batches), int(min_identity),
+                                                      1 if second_best else 0, coef, self._err, 4096))
+        else:
+            self._check(self.L.sd_stream_create(C.byref(self.h), C.byref(self.params), _strs(ms), ml, len(ms),
+                                                int(sub_batches), self._err, 4096))
         self._n_reads = []
 
     def _check(self, rc):
@@ -595,13 +647,25 @@ class Stream:
             pass
 
     def submit(self, reads):
+        """Enqueues a job.  The library is done with the read buffers when this returns (a final-mode stream keeps
+        its own copy of the reads for the identities it computes later), so `reads` may be dropped at once."""
         rs = reads if isinstance(reads, ReadSet) else ReadSet(reads)
         self._check(self.L.sd_stream_submit(self.h, rs.ptrs, rs.lens, rs.n, self._err, 4096))
         self._n_reads.append(rs.n)
 
+    def keys(self):
+        """Final mode: the distinct monomer names in the library's key order (what FinalRows' indices refer to)."""
+        n = C.c_int32()
+        self._check(self.L.sd_stream_keys(self.h, None, 0, C.byref(n)))
+        arr = (C.c_char_p * max(n.value, 1))()
+        self._check(self.L.sd_stream_keys(self.h, arr, n.value, C.byref(n)))
+        return [arr[i].decode() for i in range(n.value)]
+
     def collect(self, as_lists=False):
         """Rows of the oldest job: (n_rows,) by default -- the arrays are freed at once -- or, with
-        as_lists, a list over reads of [(tmpl, start, end, score), ...]."""
+        as_lists, a list over reads of [(tmpl, start, end, score), ...].  Final mode: a FinalRows (as_lists ignored)."""
+        if self.final:
+            return self._collect_final()
         rows = C.POINTER(Rec)()
         off = C.POINTER(C.c_int64)()
         n = C.c_int64()
@@ -620,6 +684,29 @@ class Stream:
         self.L.sd_free(rows)
         self.L.sd_free(off)
         return out
+
+    def _collect_final(self):
+        import numpy as np
+        rows = C.POINTER(FinalRec)()
+        off = C.POINTER(C.c_int64)()
+        alt = C.POINTER(C.c_double)()
+        n = C.c_int64()
+        rc = self.L.sd_stream_collect_final(self.h, C.byref(rows), C.byref(off), C.byref(n), C.byref(alt), self._err, 4096)
+        nr = self._n_reads.pop(0)
+        try:
+            self._check(rc)
+            dt = final_dtype()
+            r = np.frombuffer(C.string_at(rows, n.value * dt.itemsize), dtype=dt) if n.value else np.zeros(0, dtype=dt)
+            o = np.ctypeslib.as_array(off, shape=(nr + 1,)).copy()
+            a = None
+            if self.second_best:
+                nk = len(self.keys())
+                a = (np.ctypeslib.as_array(alt, shape=(n.value * nk,)).copy() if n.value else np.zeros(0)).reshape(n.value, nk)
+        finally:
+            self.L.sd_free(rows)
+            self.L.sd_free(off)
+            self.L.sd_free(alt)
+        return FinalRows(r, o, a)
 
     DEPTH = 2   # jobs outstanding before the oldest is collected: all three engines of the pipeline have a batch then
 
@@ -645,7 +732,11 @@ class Stream:
         self.L.sd_stream_stats(self.h, v)
         keys = ["fill_ms", "trace_ms", "compact_ms", "run_ms", "fill_launches", "batches", "rows", "host_pack_ms",
                 "host_wait_ms", "host_assemble_ms", "submit_ms", "collect_ms", "jobs", "sub_batches", "row_budget"]
-        return dict(zip(keys, list(v)[:15]))
+        out = dict(zip(keys, list(v)[:15]))
+        f = (C.c_double * 4)()
+        self.L.sd_stream_final_stats(self.h, f)
+        out.update({"ident_ms": f[0], "ident_pairs": int(f[1]), "fallback_blocks": int(f[2]), "final_rows": int(f[3])})
+        return out
 
     def info(self):
         v = (C.c_int64 * 8)()
