@@ -431,6 +431,34 @@ int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys
  * the fallback, [3] kept rows.  All 0 on a stream not in final mode. */
 int sd_stream_final_stats(sd_stream* s, double out[4]);
 
+/* ---- a stream on several devices of this process ----------------------------------------------------------------
+ * sd_stream_create / sd_stream_create_final with a device list: one batch pipeline per entry of devices[0 .. n_devices)
+ * (repeats allowed, as in sd_run_files_devices; p->device is ignored).  1 <= n_devices <= 16; every ordinal must exist
+ * and be a gfx950 device, checked before any work starts on any of them (the checks and messages of
+ * sd_run_files_devices; without a device SD_ERR_NO_DEVICE).  n_devices == 1 is the plain stream on devices[0]: driven
+ * on the calling thread, no thread of its own.
+ * With several entries each pipeline is driven by a thread of its own, bound to its device for the life of the stream.
+ * A job is cut into at least 2 x n_devices batches (and sub_batches); the batches are numbered across jobs, each entry
+ * takes the lowest one no entry has, and their records are assembled strictly in batch order, so the rows are those of
+ * a single-device stream, in both modes.  Entries on the same device share its free HBM.  The other sd_stream_* calls
+ * work unchanged, jobs are collected in FIFO order, and stats sum over the entries.  sd_stream_submit of a raw-mode
+ * stream returns once every batch of the job has been packed by its entry (the read buffers are then free, as with one
+ * device: no copy, but submit waits for the entries to have room for the job); a final-mode stream copies the reads
+ * and returns at once.  The fallback identities run on devices[0].  The first failure of any entry fails the stream as
+ * on one device -- the batches in flight on every entry are drained and the jobs dropped -- with the message prefixed
+ * "device N: ", reported by the next submit or collect.  sd_stream_destroy joins every thread. */
+int sd_stream_create_devices(sd_stream** out, const sd_params* p, const int32_t* devices, int32_t n_devices,
+                             const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono, int32_t sub_batches,
+                             char* errbuf, size_t errlen);
+int sd_stream_create_final_devices(sd_stream** out, const sd_params* p, const int32_t* devices, int32_t n_devices,
+                                   const char* const* mono_names, const char* const* mono_seqs, const int32_t* mono_lens,
+                                   int32_t n_mono, int32_t sub_batches, int32_t min_identity, int32_t second_best,
+                                   const double* lr_coef, char* errbuf, size_t errlen);
+/* Per entry of a stream (one for a stream made without a device list): batches dealt to it and its device busy time
+ * in ms (HIP-event spans of its batches, as sd_last_run_device_stats), up to cap entries; returns the number of
+ * entries (0 for a NULL stream). */
+int sd_stream_device_stats(sd_stream* s, int64_t* batches, double* busy_ms, int32_t cap);
+
 /* ---- host-side pieces of the path, exported for CPU-only tests ----------------------------- */
 
 /* chunk plan of one read (main.cpp:70-81): up to cap (offset,len) pairs; returns the count */

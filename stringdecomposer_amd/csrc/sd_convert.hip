@@ -234,7 +234,7 @@ int PostProcessor::prepare(const PostRead* reads, size_t n_reads, const sd_rec* 
     }
     if (!bt.id) fallback_blocks += nB;
     t_prepare += t_a - t_0;
-    t_identity += now_seconds() - t_a;
+    if (!bt.id) t_identity += now_seconds() - t_a;   // (0 when every identity came with the rows: sd_last_run_stats [12])
     return SD_OK;
 }
 

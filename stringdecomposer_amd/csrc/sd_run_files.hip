@@ -4,7 +4,7 @@
 #include <sys/mman.h>
 #include <sys/vfs.h>
 
-#include "sd_pipeline.hpp"
+#include "sd_devices.hpp"
 
 extern "C" {
 
@@ -40,143 +40,9 @@ static TextPool& g_textpool_ref() { static TextPool* p = new TextPool; return *p
 extern "C++" void text_pool_clear() { g_textpool.clear(); }
 
 // per device entry of the last call (sd_last_run_device_stats): batches dealt to it, device busy ms
-static constexpr int kMaxDevices = 16;
 static int g_last_ndev = 0;
 static int64_t g_last_dev_batches[kMaxDevices] = {0};
 static double g_last_dev_busy[kMaxDevices] = {0};
-
-// The pipelines of a job (one per device entry, several with sd_run_files_devices) hand their batches to the assembler
-// from their own driver threads, and this makes them take turns in batch order -- batch b's records (every slice of them) reach the
-// assembler only after all of batch b - 1's have.  A pipeline pops its batches in the order it was dealt them, and it is
-// always dealt the lowest batch nobody has, so the thread that holds the batch whose turn it is never waits for another.
-// abort() (a failed pipeline) releases every waiter; their records are dropped.
-struct BatchTurns {
-    std::mutex m;
-    std::condition_variable cv;
-    size_t turn = 0;
-    bool aborted = false;
-    bool wait(size_t b) {   // false: the job was aborted
-        std::unique_lock<std::mutex> lk(m);
-        cv.wait(lk, [&] { return aborted || turn == b; });
-        return !aborted;
-    }
-    void done(size_t b) {   // the last slice of batch b was consumed
-        {
-            std::lock_guard<std::mutex> g(m);
-            if (turn == b) turn = b + 1;
-        }
-        cv.notify_all();
-    }
-    void abort() {
-        {
-            std::lock_guard<std::mutex> g(m);
-            aborted = true;
-        }
-        cv.notify_all();
-    }
-    bool is_aborted() {
-        std::lock_guard<std::mutex> g(m);
-        return aborted;
-    }
-};
-
-// The driver of one device entry of a job (every job, one entry or several): push(b) deals batch b to the entry's pipeline (whose sinks take their turns
-// in `turns`) until the batches run out, the job has failed somewhere (turns aborted, the writer failed) or this pipeline
-// fails; then the pipeline is drained.  A pop that fails drops its batch before the batch's last slice reaches the
-// assembler, so every batch behind it -- in this pipeline and in the others -- would wait for that turn forever: the
-// turns are aborted at once, and the rest is drained with sinks that return at once.  (Pipe: Pipeline, or the host-only
-// model of sd_multi_device_selftest.)  Returns the first error of this entry; dealt counts the batches it took.
-extern "C++" template <class Pipe, class Push>
-static int drive_entry(Pipe& pq, BatchTurns& turns, std::atomic<size_t>& next_batch, size_t n_batches,
-                       const std::atomic<int>& sink_rc, Push&& push, int64_t& dealt) {
-    int r = SD_OK;
-    while (r == SD_OK && sink_rc.load() == SD_OK && !turns.is_aborted()) {
-        const size_t b = next_batch.fetch_add(1);
-        if (b >= n_batches) break;
-        r = push(b);
-        if (r == SD_OK) ++dealt;
-        else turns.abort();   // (this batch, or the one a full pipeline popped for it, never reaches its sink)
-    }
-    while (pq.inflight() > 0) {
-        const int e = pq.pop();
-        if (e) {
-            if (r == SD_OK) r = e;
-            turns.abort();
-        }
-    }
-    return r;
-}
-
-// The batches of a job on n_dev pipelines: at least min_batches and 2 * n_dev of them (as far as the chunks go), so that
-// every pipeline gets work and the last batch to finish is short, cut where the cumulative rows cross k / nb of the
-// total -- equal shares up to one chunk -- and none of several chunks above the budget.
-static void plan_device_batches(const std::vector<CRef>& table, int64_t budget, int min_batches, int n_dev,
-                                std::vector<std::pair<size_t, size_t>>& out) {
-    out.clear();
-    const size_t n = table.size();
-    if (n == 0) return;
-    std::vector<int64_t> cum(n + 1, 0);
-    int64_t lmax = 1;
-    for (size_t c = 0; c < n; ++c) { cum[c + 1] = cum[c] + table[c].len; lmax = std::max<int64_t>(lmax, table[c].len); }
-    budget = std::max<int64_t>(budget, 1);
-    const int64_t holds = std::max<int64_t>(1, budget - (lmax - 1));
-    size_t nb = std::max<size_t>({(size_t)std::max(min_batches, 1), (size_t)2 * (size_t)std::max(n_dev, 1),
-                                  (size_t)((cum[n] + holds - 1) / holds)});
-    for (nb = std::min(nb, n);; nb = std::min(nb + 1, n)) {
-        out.clear();
-        bool fits = true;
-        size_t c0 = 0;
-        for (size_t k = 1; k <= nb; ++k) {
-            const int64_t want = (int64_t)((__int128)cum[n] * (int64_t)k / (int64_t)nb);
-            size_t c1 = k == nb ? n : (size_t)(std::lower_bound(cum.begin(), cum.end(), want) - cum.begin());
-            c1 = std::min(std::max(c1, c0 + 1), n - (nb - k));
-            if (c1 - c0 > 1 && cum[c1] - cum[c0] > budget) fits = false;
-            out.emplace_back(c0, c1);
-            c0 = c1;
-        }
-        if (fits || nb == n) return;
-    }
-}
-
-// The planner of a job: plan_batches for one device entry (a job that fits one batch stays one batch), plan_device_batches
-// for several (at least two batches per entry, so that every pipeline gets work).
-static void cut_batches(const std::vector<CRef>& table, int64_t budget, int min_batches, int n_dev,
-                        std::vector<std::pair<size_t, size_t>>& out) {
-    if (n_dev == 1) plan_batches(table, 0, table.size(), budget, min_batches, out);
-    else plan_device_batches(table, budget, min_batches, n_dev, out);
-}
-
-// fn(i) for every device entry of a job.  One entry: inline, on the calling thread and its current device (as every
-// single-device call).  Several: side by side, each on a thread bound to devs[i] (hipSetDevice is per host thread); a
-// failed hipSetDevice or a std::bad_alloc there is the entry's result, with its message in msg[i], and calls on_fail().
-// Returns the first failed entry's result; its message (err) names the device when there are several.
-extern "C++" template <class Fn, class OnFail>
-static int on_entries(const std::vector<int32_t>& devs, std::vector<std::string>& msg, std::string& err, Fn&& fn, OnFail&& on_fail) {
-    std::vector<int> rc(devs.size(), SD_OK);
-    if (devs.size() == 1) rc[0] = fn(0);
-    else {
-        struct Joined { std::vector<std::thread> t; ~Joined() { for (std::thread& x : t) x.join(); } } th;
-        for (size_t i = 0; i < devs.size(); ++i)
-            th.t.emplace_back([&, i]() {
-                try {
-                    if (hipSetDevice(devs[i]) == hipSuccess) { rc[i] = fn((int)i); return; }
-                    (void)hipGetLastError();
-                    rc[i] = SD_ERR_HIP;
-                    msg[i] = "hipSetDevice failed";
-                } catch (const std::bad_alloc&) {
-                    rc[i] = SD_ERR_INTERNAL;
-                    msg[i] = "out of host memory";
-                }
-                on_fail();
-            });
-    }
-    for (size_t i = 0; i < rc.size(); ++i)
-        if (rc[i]) {
-            err = devs.size() > 1 ? "device " + std::to_string(devs[i]) + ": " + msg[i] : msg[i];
-            return rc[i];
-        }
-    return SD_OK;
-}
 
 // The FASTA side of a job: both files indexed and checked, the monomers, and this rank's reads -- the reads [lo, hi) of a
 // split of the read set into `world` contiguous groups of about equal chunk counts (world == 1: everything).
@@ -595,15 +461,7 @@ static void plan_job(const RowJob& job, const std::vector<int64_t>& entry_budget
     // a pipeline that comes from the cache has its buffers, and a job of many batches allocates full-size ones once.
     if (!reused && !slice_ident) min_batches = std::max(min_batches, nc >= 4096 ? 8 : nc >= 1024 ? 4 : 1);
     if (const char* ev = getenv("SD_MIN_BATCHES")) min_batches = std::max(1, atoi(ev));   // developer A/B
-    // every entry's budget, its device's free HBM shared with the other entries on that device (an explicit cap stays as
-    // it is); the job takes the smallest
-    int64_t budget = INT64_MAX;
-    for (size_t i = 0; i < devs.size(); ++i) {
-        int64_t b = entry_budget[i];
-        const int same = (int)std::count(devs.begin(), devs.end(), devs[i]);
-        if (same > 1 && p->max_batch_rows <= 0 && !getenv("SD_BATCH_ROWS")) b = std::max<int64_t>(b / same, (int64_t)p->part_size + p->overlap);
-        budget = std::min(budget, b);
-    }
+    int64_t budget = shared_row_budget(entry_budget, devs, p);
     if (!reused) {
         int64_t rows = 0;
         for (const CRef& c : job.table) rows += c.len;
@@ -842,31 +700,8 @@ int sd_run_files_devices(const char* reads_fa, const char* monomers_fa, const sd
                          const char* records_out, int32_t min_identity, int32_t second_best, const double* lr_coef,
                          char* errbuf, size_t errlen) {
     // the device list is checked completely before anything is started on any of its devices
-    if (!p || !devices || n_devices < 1 || n_devices > kMaxDevices) {
-        set_err(errbuf, errlen, "sd_run_files_devices: 1 to " + std::to_string(kMaxDevices) + " device entries");
-        return SD_ERR_PARAM;
-    }
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }
-    static std::atomic<int> arch_ok[64];   // per ordinal: 0 not looked at, 1 gfx950, 2 another chip
-    for (int32_t i = 0; i < n_devices; ++i) {
-        const int32_t d = devices[i];
-        if (d < 0 || d >= count) {
-            set_err(errbuf, errlen, "device " + std::to_string(d) + " does not exist (" + std::to_string(count) + " HIP devices visible)");
-            return d < 0 ? SD_ERR_PARAM : SD_ERR_NO_DEVICE;
-        }
-        int known = d < 64 ? arch_ok[d].load() : 0;
-        if (known == 0) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, d) != hipSuccess) { (void)hipGetLastError(); known = 2; }
-            else known = std::strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : 2;
-            if (d < 64) arch_ok[d].store(known);
-        }
-        if (known != 1) {
-            set_err(errbuf, errlen, "device " + std::to_string(d) + " is not a gfx950 device");
-            return SD_ERR_NO_DEVICE;
-        }
-    }
+    const int rc = check_device_list("sd_run_files_devices", p ? devices : nullptr, n_devices, errbuf, errlen);
+    if (rc) return rc;
     sd_params q = *p;
     q.device = devices[0];
     const std::vector<int32_t> devs(devices, devices + n_devices);

@@ -44,6 +44,7 @@ EXPORTS = [
     "sd_range_assemble_records",
     "sd_run_files_devices", "sd_last_run_device_stats", "sd_multi_device_selftest",
     "sd_stream_create_final", "sd_stream_collect_final", "sd_stream_keys", "sd_stream_final_stats",
+    "sd_stream_create_devices", "sd_stream_create_final_devices", "sd_stream_device_stats",
 ]
 
 
@@ -190,6 +191,12 @@ def load():
                                        C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, P(C.c_double), C.c_char_p, C.c_size_t]
     L.sd_last_run_device_stats.argtypes = [P(C.c_int64), P(C.c_double), C.c_int32]
     L.sd_multi_device_selftest.argtypes = [C.c_char_p, C.c_size_t]
+    L.sd_stream_create_devices.argtypes = [P(C.c_void_p), P(Params), P(C.c_int32), C.c_int32, P(C.c_char_p), P(C.c_int32),
+                                           C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]
+    L.sd_stream_create_final_devices.argtypes = [P(C.c_void_p), P(Params), P(C.c_int32), C.c_int32, P(C.c_char_p),
+                                                 P(C.c_char_p), P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 P(C.c_double), C.c_char_p, C.c_size_t]
+    L.sd_stream_device_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double), C.c_int32]
     _lib = L
     return L
 
@@ -604,10 +611,14 @@ class Stream:
     of _alt.tsv) as a FinalRows instead of the raw DP rows, with identities computed on the device behind each batch.
     mono_names are required there (names are the keys: a repeated name is one key); min_identity, second_best and
     lr_coef are the command line's -i, --second-best and model coefficients (None: models/ont_logreg_model.txt, as
-    the command line reads it).  formats.final_rows turns a FinalRows into FinalRow / AltRow lists."""
+    the command line reads it).  formats.final_rows turns a FinalRows into FinalRow / AltRow lists.
+
+    devices (a list of ordinals, repeats allowed; `device` is then ignored): one pipeline per entry in this process
+    (sd_stream_create_devices / sd_stream_create_final_devices), each driven by a thread of its own; every job is cut
+    into at least two batches per entry and the rows are those of the plain stream.  [d] is the plain stream on d."""
 
     def __init__(self, mono_seqs, sub_batches=1, final=False, mono_names=None, second_best=False, min_identity=0,
-                 lr_coef=None, **kw):
+                 lr_coef=None, devices=None, **kw):
         self.L = load()
         self.params = make_params(**kw)
         self._err = C.create_string_buffer(4096)
@@ -616,6 +627,8 @@ class Stream:
         self.h = C.c_void_p()
         self.final = bool(final)
         self.second_best = bool(second_best)
+        self.devices = None if devices is None else [int(d) for d in devices]
+        devs = None if devices is None else (C.c_int32 * max(len(self.devices), 1))(*self.devices)
         if self.final:
             if mono_names is not None and len(mono_names) != len(ms):
                 raise SdError(SD_ERR_PARAM, "final=True needs one name per monomer (mono_names)")
@@ -623,9 +636,18 @@ class Stream:
                 from .main import _lr_coef
                 lr_coef = _lr_coef()
             coef = (C.c_double * 3)(*[float(x) for x in lr_coef])
-            self._check(self.L.sd_stream_create_final(C.byref(self.h), C.byref(self.params), None if mono_names is None else _strs(mono_names), _strs(ms),
-                                                      ml, len(ms), int(sub_batches), int(min_identity),
-                                                      1 if second_best else 0, coef, self._err, 4096))
+            names = None if mono_names is None else _strs(mono_names)
+            if devs is not None:
+                self._check(self.L.sd_stream_create_final_devices(C.byref(self.h), C.byref(self.params), devs, len(self.devices),
+                                                                  names, _strs(ms), ml, len(ms), int(sub_batches),
+                                                                  int(min_identity), 1 if second_best else 0, coef, self._err, 4096))
+            else:
+                self._check(self.L.sd_stream_create_final(C.byref(self.h), C.byref(self.params), names, _strs(ms),
+                                                          ml, len(ms), int(sub_batches), int(min_identity),
+                                                          1 if second_best else 0, coef, self._err, 4096))
+        elif devs is not None:
+            self._check(self.L.sd_stream_create_devices(C.byref(self.h), C.byref(self.params), devs, len(self.devices),
+                                                        _strs(ms), ml, len(ms), int(sub_batches), self._err, 4096))
         else:
             self._check(self.L.sd_stream_create(C.byref(self.h), C.byref(self.params), _strs(ms), ml, len(ms),
                                                 int(sub_batches), self._err, 4096))
@@ -714,7 +736,13 @@ class Stream:
         """Rows of every job of the iterable `jobs` (read lists / ReadSets), in order, with `depth` later jobs submitted
         before a job is collected -- the order of calls that keeps the device busy (sd_hip.h at sd_stream_create: the
         traceback of a batch ends with the fill of the next one, so with only ONE job outstanding the job after that is
-        enqueued late; bench.py's timed loop is this generator)."""
+        enqueued late; bench.py's timed loop is this generator).
+
+        The default depth is DEPTH = 2 with a device list too.  There every job is cut into at least two batches per
+        entry, so two jobs outstanding give each entry at least four batches -- more than its pipeline's three slots --
+        and while the oldest job is collected the other still holds two batches per entry, back to back, which is what
+        one pipeline gets from two single-batch jobs.  A deeper queue would only hold more reads and rows in memory
+        (a raw-mode submit already waits until its batches are packed, so it cannot run far ahead of the devices)."""
         depth = self.DEPTH if depth is None else max(0, int(depth))
         out = 0
         for reads in jobs:
@@ -742,6 +770,15 @@ class Stream:
         v = (C.c_int64 * 8)()
         self.L.sd_stream_info(self.h, v)
         return _info_dict(v)
+
+    def device_stats(self):
+        """Per entry of the stream (one without a device list; sd_stream_device_stats): a list of {"device",
+        "batches": batches dealt to the entry, "busy_ms": its device busy time (HIP-event spans of its batches)}."""
+        b = (C.c_int64 * 16)()
+        ms = (C.c_double * 16)()
+        n = self.L.sd_stream_device_stats(self.h, b, ms, 16)
+        devs = self.devices if self.devices is not None else [self.params.device]
+        return [{"device": devs[i], "batches": int(b[i]), "busy_ms": float(ms[i])} for i in range(min(n, 16))]
 
 
 def host_stage_rates(reads, iters=3, **kw):
