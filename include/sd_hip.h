@@ -64,6 +64,8 @@ typedef struct sd_params {
 #define SD_FLAG_NO_IDENT_PRUNE 256 /* sd_run_files --second-best: every homopolymer-compressed pair aligned in full (rounds 3-5; A/B) */
 #define SD_FLAG_PROGRESS 32        /* sd_run_files: the reference binary's progress lines on stderr ("Scores: ...",
                                       "Prepared reads", "<p>%: Aligned <read>", main.cpp:82,115,393); the command line sets it */
+#define SD_FLAG_PROFILE 512        /* sd_run_files*, final-mode streams: per-monomer column profiles of the kept rows
+                                      (sd_last_run_profile / sd_stream_profile); a repeated monomer name is SD_ERR_PARAM */
 
 void sd_params_default(sd_params* p); /* -1,-1,-1,1 / 5000 / 500 / -1 / 1 / 0 / auto */
 
@@ -430,6 +432,11 @@ int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys
  * events, as sd_last_run_stats [3]), [1] pairs computed in-stream (as [4]), [2] blocks whose identities came from
  * the fallback, [3] kept rows.  All 0 on a stream not in final mode. */
 int sd_stream_final_stats(sd_stream* s, double out[4]);
+/* A final-mode stream created with SD_FLAG_PROFILE: the profile summed over the jobs collected so far, in the form of
+ * sd_last_run_profile.  reset != 0 (with counts given) zeroes it after the copy.  SD_ERR_PARAM on a raw-mode stream
+ * or one created without the flag. */
+int sd_stream_profile(sd_stream* s, int32_t reset, int32_t* n_monomers, int64_t* n_counts, int64_t* text_bytes,
+                      char* text, uint64_t* counts);
 
 /* ---- a stream on several devices of this process ----------------------------------------------------------------
  * sd_stream_create / sd_stream_create_final with a device list: one batch pipeline per entry of devices[0 .. n_devices)
@@ -540,6 +547,35 @@ int sd_identity_segments_dev(const char* seq, int64_t seqlen, const int64_t* sta
                              const int32_t* pair_tmpl, int32_t homo, int32_t device, int32_t threads,
                              int32_t* dist, int32_t* matches, int32_t* columns);
 void sd_nw_release_cache(void);
+
+/* ---- monomer column profiles (--profile) -----------------------------------------------------------------------
+ * The alignment behind a row's identity (edlib NW path of the block against its monomer, Hirschberg's split where
+ * edlib takes it), folded into the FORWARD monomer: a pair against rc(m) (length L) counts rc position q at L-1-q,
+ * insertion slot h at L-h, and its bases complemented.  Per monomer, SD_PROFILE_COLS counters for every slot
+ * g = 0..L, in this order:
+ *   [0..4] read bases A C G T N aligned to template position g (g < L)   [5] deletions of position g (g < L)
+ *   [6] instances with at least one read base inserted in slot g (bases before position g, after g - 1)
+ *   [7..11] the inserted bases of slot g, A C G T N
+ * Monomer t's block starts at sum over t' < t of (tlen[t'] + 1) * SD_PROFILE_COLS.  A pair with an empty side is not
+ * an instance.  Read bases other than ACGT count as N. */
+#define SD_PROFILE_COLS 12
+
+/* Segment s = seq[starts[s] .. ends[s]] (inclusive) against monomer pair_tmpl[s] >> 1, its reverse complement when
+ * pair_tmpl[s] & 1 (the interleaved order m0, m0', m1, m1', ...).  tmpl / tlen / T: the FORWARD monomers.  counts
+ * (sum of (tlen + 1) * SD_PROFILE_COLS) is overwritten.  Host threads (sd_profile_segments) or the device
+ * (sd_profile_segments_dev: the profile kernel of csrc/sd_nw.hip, with the host form for the pairs it does not take
+ * -- monomers over 512 bp, segments over 1024 bp, pairs edlib splits). */
+int sd_profile_segments(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                        const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl,
+                        int32_t threads, uint64_t* counts);
+int sd_profile_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends,
+                            int64_t n_seg, const char* const* tmpl, const int32_t* tlen, int32_t T,
+                            const int32_t* pair_tmpl, int32_t device, int32_t threads, uint64_t* counts);
+/* The profile of the last successful sd_run_files* call of this process made with SD_FLAG_PROFILE (summed over its
+ * device entries).  Every output may be NULL: *n_monomers, *n_counts and *text_bytes size the buffers of a second
+ * call.  text: "name\tsequence\n" per monomer in FASTA order, NUL-terminated (text_bytes counts the NUL); counts as
+ * above.  SD_ERR_PARAM when the last call did not profile. */
+int sd_last_run_profile(int32_t* n_monomers, int64_t* n_counts, int64_t* text_bytes, char* text, uint64_t* counts);
 
 /* Text of `_alt.tsv` rows (main.py:161-165): for each of n_rows kept blocks one line per monomer name
  * (key): read, name, start, end, "%.2f" of vals[row * n_keys + key], '*' if key == own_key[row] else

@@ -68,6 +68,57 @@ int PostProcessor::init(const std::vector<Seq>& monos, int min_identity_, bool s
     return SD_OK;
 }
 
+int PostProcessor::enable_profile(std::string& err) {
+    std::unordered_map<std::string, int> seen;
+    for (const std::string& n : il_name)
+        if (++seen[n] == 2) { err = "monomer name " + n + " is not unique: a profile needs one template per name"; return SD_ERR_PARAM; }
+    std::vector<int32_t> fl;
+    for (size_t x = 0; x < il_seq.size(); x += 2) fl.push_back((int32_t)il_seq[x].size());
+    std::vector<int64_t> off;
+    prof.assign((size_t)profile_offsets(fl, off), 0);
+    prof_on = true;
+    return SD_OK;
+}
+
+std::string PostProcessor::profile_text() const {
+    std::string o;
+    for (size_t x = 0; x < il_seq.size(); x += 2) o += il_name[x] + "\t" + il_seq[x] + "\n";
+    return o;
+}
+
+// The alignments behind the identities of the kept blocks (own interleaved template), on the device when there is one
+int PostProcessor::profile_kept(const Batch& bt, const sd_rec* rows, std::string& err) {
+    const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    std::vector<int64_t> st;
+    std::vector<int32_t> ln, pil;
+    for (size_t b = 0; b < bt.kept.size(); ++b)
+        if (bt.kept[b]) {
+            st.push_back(bt.seg_start[b]);
+            ln.push_back(bt.seg_len[b]);
+            pil.push_back(own_il_of_t[(size_t)rows[b].tmpl]);
+        }
+    std::vector<uint64_t> add(prof.size(), 0);
+    int rc;
+    if (device >= 0) {
+        rc = nw_profile_device(bt.spans, st.data(), ln.data(), (int64_t)st.size(), il_seq, pil.data(), device, threads, add.data());
+    } else {
+        std::vector<int64_t> so;   // span offsets in the concatenation
+        int64_t pos = 0;
+        for (const auto& sp : bt.spans) { so.push_back(pos); pos += sp.second; }
+        std::vector<const char*> q(st.size());
+        for (size_t x = 0; x < st.size(); ++x) {
+            const size_t k = (size_t)(std::upper_bound(so.begin(), so.end(), st[x]) - so.begin()) - 1;
+            q[x] = bt.spans[k].first + (st[x] - so[k]);
+        }
+        rc = profile_host(q.data(), ln.data(), pil.data(), (int64_t)q.size(), il_seq, threads, add.data());
+    }
+    if (rc) { err = "profile computation failed (rc " + std::to_string(rc) + ")"; return rc; }
+    std::lock_guard<std::mutex> g(*prof_m);
+    for (size_t i = 0; i < add.size(); ++i) prof[i] += add[i];
+    t_profile += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
+    return SD_OK;
+}
+
 int PostProcessor::tmpl_of_name(const std::string& nm) const {
     for (size_t t = 0; t < tname.size(); ++t)
         if (tname[t] == nm) return (int)t;
@@ -217,6 +268,7 @@ int PostProcessor::prepare(const PostRead* reads, size_t n_reads, const sd_rec* 
         if (edlib_splits(worst, (int64_t)tmax)) have = false;
     }
     bt.id = have;   // identities came with the rows
+    if (prof_on) bt.kept.assign((size_t)nB, 0);
     const double t_a = now_seconds();
     int rc;
     if (bt.id) {
@@ -233,6 +285,11 @@ int PostProcessor::prepare(const PostRead* reads, size_t n_reads, const sd_rec* 
         if (rc) return rc;
     }
     if (!bt.id) fallback_blocks += nB;
+    if (prof_on) {
+        bt.spans = std::move(spans);
+        bt.seg_start = std::move(seg_start);
+        bt.seg_len = std::move(seg_len);
+    }
     t_prepare += t_a - t_0;
     if (!bt.id) t_identity += now_seconds() - t_a;   // (0 when every identity came with the rows: sd_last_run_stats [12])
     return SD_OK;
@@ -328,6 +385,7 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
         for (int64_t b = sl * grain; b < b1; ++b) {
             sd_final_row f;
             if (!select(bt, rows, b, kbuf.data(), hbuf.data(), f)) continue;
+            if (prof_on) bt.kept[(size_t)b] = 1;
             const PostRead& rd = reads[(size_t)f.read];
             of.append(rd.name, rd.name_len); of.push_back('\t');
             of.append(keys[(size_t)f.best]); of.push_back('\t');
@@ -365,6 +423,7 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
         if (second_best) oa.resize((size_t)(wa - oa.data()));
     });
     t_format += now_seconds() - t_b;
+    if (prof_on) return profile_kept(bt, rows, err);
     return SD_OK;
 }
 
@@ -398,6 +457,7 @@ int PostProcessor::process_rows(const PostRead* reads, size_t n_reads, int32_t r
             double* kv = second_best ? alt.p + at * nK : nullptr;   // (light mode: no per-key identities)
             sd_final_row f;
             if (!select(bt, rows, b, kv, hbuf.data(), f)) continue;
+            if (prof_on) bt.kept[(size_t)b] = 1;
             f.read += read0;
             std::memcpy(out.p + at, &f, sizeof f);
             ++k;
@@ -416,6 +476,7 @@ int PostProcessor::process_rows(const PostRead* reads, size_t n_reads, int32_t r
     out.n = to;
     if (second_best) alt.n = to * nK;
     t_format += now_seconds() - t_b;
+    if (prof_on) return profile_kept(bt, rows, err);
     return SD_OK;
 }
 

@@ -5,6 +5,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -82,7 +84,18 @@ class PostProcessor {
     const std::vector<int32_t>& own_interleaved() const { return own_il32; }      // DP template -> interleaved index
     int tmpl_of_name(const std::string& nm) const;   // first template of that name in the DP's order, -1 if none
     std::vector<std::string> tname;                  // the DP's template names: m, ..., m', ...
-    double t_prepare = 0, t_identity = 0, t_format = 0, t_concat = 0;   // seconds spent in process(), by stage
+    // Column profiles of the kept rows (SD_FLAG_PROFILE): SD_ERR_PARAM when a name repeats (a key must name one template).
+    // prof: the forward monomers' counters (include/sd_hip.h), summed over every process* call since enable_profile.
+    int enable_profile(std::string& err);
+    bool profiling() const { return prof_on; }
+    std::vector<uint64_t> profile(bool reset = false) {   // a copy (reset: and zero it, in one step)
+        std::lock_guard<std::mutex> g(*prof_m);
+        std::vector<uint64_t> v = prof;
+        if (reset) std::fill(prof.begin(), prof.end(), 0);
+        return v;
+    }
+    std::string profile_text() const;   // "name\tsequence\n" per monomer, file order
+    double t_prepare = 0, t_identity = 0, t_format = 0, t_concat = 0, t_profile = 0;   // seconds spent in process(), by stage
     int64_t fallback_blocks = 0;     // blocks whose identities were computed here, not taken from the rows' words
 
   private:
@@ -94,6 +107,11 @@ class PostProcessor {
         int per = 1;
         RawVec<double> vals, hvals;
         std::vector<int32_t> read_of;    // block -> index into reads
+        // the blocks as segments of the concatenated reads, and (profiling) which of them select kept
+        std::vector<std::pair<const char*, int64_t>> spans;
+        std::vector<int64_t> seg_start;
+        std::vector<int32_t> seg_len;
+        std::vector<uint8_t> kept;
         const uint32_t* words(int64_t b, bool homo) const {   // words of block b (plain / compressed)
             if (!ident->src) return (homo ? ident->idh : ident->id) + (size_t)b * (size_t)per;
             const int64_t sx = ident->src[b];
@@ -106,6 +124,7 @@ class PostProcessor {
     // main.py:107-150 + classify (:95-104) for block b: false if the block is filtered out (main.py:156); f.read = the
     // block's index into reads.  kbuf (nK) receives the block's identities in key order with second_best; hbuf (T) is scratch
     bool select(const Batch& bt, const sd_rec* rows, int64_t b, double* kbuf, double* hbuf, sd_final_row& f) const;
+    int profile_kept(const Batch& bt, const sd_rec* rows, std::string& err);   // the kept blocks into prof
     int identities(const std::vector<std::pair<const char*, int64_t>>& spans, const std::vector<int64_t>& seg_start,
                    const std::vector<int32_t>& seg_len, const int32_t* pair, bool homo, RawVec<double>& out,
                    std::string& err, bool host_only = false);
@@ -119,6 +138,9 @@ class PostProcessor {
     double coef[3] = {0, 0, 0};
     int device = -1;
     int threads = 1;
+    bool prof_on = false;
+    std::vector<uint64_t> prof;
+    std::shared_ptr<std::mutex> prof_m = std::make_shared<std::mutex>();
 };
 
 }  // namespace sd

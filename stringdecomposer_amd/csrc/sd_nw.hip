@@ -92,6 +92,69 @@ void launch_nw_pairs(int K, hipStream_t st, int grid, const uint8_t* seq, const 
 #undef SD_NW
 }
 
+// Column profiles (--profile): the walk of sd_nw_pairs with every step counted (nw_pair<K, Query, true>).  A work item is
+// up to `per` pairs of ONE forward monomer -- the host groups the pairs by monomer -- and a one-wave workgroup (the kept rows
+// of a batch are only tens of thousands of pairs: waves, not workgroups of 256, spread them over the CUs) keeps that monomer's
+// counters in LDS ((L + 1) x 12 dwords, 8.3 KB at 171 bp) and adds them to the global 64-bit counters once per item:
+// ~290 000 instances of a 12-monomer set per 50 Mbp would otherwise aim every step's atomic at ~2 000 addresses of HBM.
+// items[w] = {monomer, first, end} into order[] (segment indices); peq / tlen: the interleaved templates (2m, 2m + 1 = rc).
+template <int K>
+__global__ __launch_bounds__(64) void sd_nw_profile(const uint8_t* __restrict__ seq, const int64_t* __restrict__ seg_start,
+                                                        const int32_t* __restrict__ seg_len, const int32_t* __restrict__ order,
+                                                        const int32_t* __restrict__ pair_il, const int4* __restrict__ items,
+                                                        int n_items, const unsigned long long* __restrict__ peq,
+                                                        const int32_t* __restrict__ tlen, const int64_t* __restrict__ off, int cap,
+                                                        uint4* __restrict__ ck, int* __restrict__ ckpos,
+                                                        unsigned long long* __restrict__ counts, int* __restrict__ fails) {
+    extern __shared__ unsigned long long smem[];   // [2][5][K] masks of m and rc(m), then (Lmax + 1) x 12 counters
+    uint32_t* cnt = reinterpret_cast<uint32_t*>(smem + 10 * K);
+    uint32_t* ckl = reinterpret_cast<uint32_t*>(ck) + (size_t)blockIdx.x * (size_t)cap * K * 4 * 64 + threadIdx.x;
+    int* ckp = ckpos + threadIdx.x;   // (not written: no homopolymer compression)
+    for (int w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const int4 it = items[w];
+        const int m = it.x;
+        const int L = tlen[2 * m];
+        const int nc = (L + 1) * 12;
+        __syncthreads();   // the previous item's flush has read its counters
+        for (int i = threadIdx.x; i < nc; i += blockDim.x) cnt[i] = 0u;
+        for (int i = threadIdx.x; i < 10 * K; i += blockDim.x) smem[i] = peq[(size_t)2 * m * 5 * K + i];
+        __syncthreads();
+        for (int p = it.y + (int)threadIdx.x; p < it.z; p += blockDim.x) {
+            const int sg = order[p];
+            const int rc = pair_il[sg] & 1;
+            NwQueryAscii q{seq, seg_start[sg]};
+            NwProf pr{cnt, L, rc != 0};
+            int d = 0, mm = 0;
+            if (!nw_pair<K, NwQueryAscii, true>(q, seg_len[sg], reinterpret_cast<const uint2*>(smem + rc * 5 * K), L, false, ckl,
+                                                ckp, (size_t)64, cap, d, mm, &pr))
+                atomicAdd(fails, 1);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < nc; i += blockDim.x) {
+            const uint32_t v = cnt[i];
+            if (v) atomicAdd(counts + off[m] + i, (unsigned long long)v);
+        }
+    }
+}
+
+void launch_nw_profile(int K, hipStream_t st, int grid, size_t lds, const uint8_t* seq, const int64_t* seg_start,
+                       const int32_t* seg_len, const int32_t* order, const int32_t* pair_il, const int4* items, int n_items,
+                       const unsigned long long* peq, const int32_t* tlen, const int64_t* off, int cap, void* ck, int* ckpos,
+                       unsigned long long* counts, int* fails) {
+#define SD_NWP(KK)                                                                                                   \
+    hipLaunchKernelGGL(sd_nw_profile<KK>, dim3(grid), dim3(64), lds, st, seq, seg_start, seg_len, order, pair_il, items, \
+                       n_items, peq, tlen, off, cap, reinterpret_cast<uint4*>(ck), ckpos, counts, fails)
+    switch (K) {
+        case 1: SD_NWP(1); break;
+        case 2: SD_NWP(2); break;
+        case 3: SD_NWP(3); break;
+        case 4: SD_NWP(4); break;
+        case 6: SD_NWP(6); break;
+        default: SD_NWP(8); break;
+    }
+#undef SD_NWP
+}
+
 // match masks of a template set, top-aligned in K words per (template, symbol): symbol k of a template of length
 // L sits at bit 64 K - L + k (sd_nw_kernel.hpp)
 void nw_build_masks(const std::vector<std::string>& ts, int K, std::vector<unsigned long long>& peq,
@@ -146,14 +209,14 @@ struct NwBuf {
 struct NwCtx {
     std::mutex m;
     int dev = -1;
-    NwBuf seq, starts, lens, pair, peq, tlen, ck, ckpos, idx, dist, matches;
+    NwBuf seq, starts, lens, pair, peq, tlen, ck, ckpos, idx, dist, matches, items, poff, pcnt;
     char* stage = nullptr;      // pinned staging of the text
     size_t stage_cap = 0;
     void release() {
         if (stage) (void)hipHostFree(stage);
         stage = nullptr;
         stage_cap = 0;
-        for (NwBuf* b : {&seq, &starts, &lens, &pair, &peq, &tlen, &ck, &ckpos, &idx, &dist, &matches}) {
+        for (NwBuf* b : {&seq, &starts, &lens, &pair, &peq, &tlen, &ck, &ckpos, &idx, &dist, &matches, &items, &poff, &pcnt}) {
             if (b->p) (void)hipFree(b->p);
             b->p = nullptr;
             b->cap = 0;
@@ -446,6 +509,165 @@ int nw_identity_device(const std::vector<std::pair<const char*, int64_t>>& spans
         return SD_ERR_HIP;
     lap.to(3);
     return SD_OK;
+}
+}  // namespace sd
+
+namespace sd {
+// Column profiles of segments of a text (the concatenation of `spans`) on the device: pairs of monomers up to 512 bp
+// and segments up to 1024 bp that edlib aligns by its block traceback go to sd_nw_profile, the others -- and every
+// pair when the text holds a symbol outside ACGTN -- to the host fold (profile_host) under the kernel.
+int nw_profile_device(const std::vector<std::pair<const char*, int64_t>>& spans, const int64_t* seg_start,
+                      const int32_t* seg_len, int64_t n_seg, const std::vector<std::string>& il, const int32_t* pair_il,
+                      int device, int threads, uint64_t* counts) {
+    constexpr int NWP_QMAX = 1024;
+    const int M = (int)il.size() / 2;
+    if (n_seg == 0 || M == 0) return SD_OK;
+    if (n_seg > 0x7fffffff) return SD_ERR_UNSUPPORTED;
+    std::vector<int32_t> fl((size_t)M);
+    for (int m = 0; m < M; ++m) fl[(size_t)m] = (int32_t)il[(size_t)(2 * m)].size();
+    std::vector<int64_t> off;
+    const int64_t total = profile_offsets(fl, off);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SD_ERR_NO_DEVICE; }
+    if (device < 0 || device >= ndev) return SD_ERR_PARAM;
+    int tmax = 1;
+    bool dev_ok = true;
+    for (const std::string& t : il) {
+        tmax = std::max(tmax, (int)t.size());
+        for (char ch : t) dev_ok = dev_ok && nw_code(ch) >= 0;
+    }
+    dev_ok = dev_ok && tmax <= 512;
+    int64_t text = 0;
+    std::vector<int64_t> span_off(spans.size() + 1, 0);
+    for (size_t i = 0; i < spans.size(); ++i) { span_off[i] = text; text += spans[i].second; }
+    span_off[spans.size()] = text;
+    for (int64_t s = 0; s < n_seg; ++s) {
+        if (pair_il[s] < 0 || pair_il[s] >= 2 * M) return SD_ERR_PARAM;
+        if (seg_len[s] < 0 || seg_start[s] < 0 || seg_start[s] + seg_len[s] > text) return SD_ERR_PARAM;
+    }
+
+    std::lock_guard<std::mutex> g(g_nw.m);
+    if (hipSetDevice(device) != hipSuccess) return SD_ERR_HIP;
+    if (g_nw.dev != device) { if (g_nw.dev >= 0) g_nw.release(); g_nw.dev = device; }
+    if ((size_t)text + 8 > g_nw.stage_cap) {
+        if (g_nw.stage) nw_retired().host.push_back(g_nw.stage);   // (not freed here: see NwRetired)
+        const size_t want = std::max((size_t)text + (size_t)text / 4 + 4096, 2 * g_nw.stage_cap);
+        g_nw.stage = nullptr;
+        g_nw.stage_cap = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&g_nw.stage), want, hipHostMallocDefault) != hipSuccess) return SD_ERR_HIP;
+        g_nw.stage_cap = want;
+    }
+    {   // text -> pinned staging, alphabet checked on the way (pieces of <= 1 MB over all threads)
+        struct Piece { size_t span; int64_t off, len; };
+        std::vector<Piece> pieces;
+        for (size_t i = 0; i < spans.size(); ++i)
+            for (int64_t o = 0; o < spans[i].second; o += (1 << 20))
+                pieces.push_back(Piece{i, o, std::min<int64_t>(1 << 20, spans[i].second - o)});
+        std::vector<uint8_t> bad(pieces.size(), 0);
+        sd::parallel_for((int64_t)pieces.size(), threads, 1, [&](int64_t x) {
+            const Piece& pc = pieces[(size_t)x];
+            const char* src = spans[pc.span].first + pc.off;
+            char* dst = g_nw.stage + span_off[pc.span] + pc.off;
+            uint8_t b = 0;
+            for (int64_t i = 0; i < pc.len; ++i) {
+                const char ch = src[i];
+                b |= (uint8_t)!(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' || ch == 'N');
+                dst[i] = ch;
+            }
+            bad[(size_t)x] = b;
+        });
+        for (uint8_t b : bad) dev_ok = dev_ok && !b;
+    }
+    // the kernel's pairs grouped by forward monomer (counting sort), the host's pairs as query pointers
+    std::vector<int32_t> order, per_m((size_t)M + 1, 0);
+    std::vector<const char*> hq;
+    std::vector<int32_t> hl, hp;
+    int qmax = 1;
+    for (int64_t s = 0; s < n_seg; ++s) {
+        const int il_s = pair_il[s];
+        const int64_t L = (int64_t)il[(size_t)il_s].size();
+        if (seg_len[s] <= 0 || L == 0) continue;   // no alignment: not an instance
+        if (dev_ok && seg_len[s] <= NWP_QMAX && !sd::edlib_splits(seg_len[s], L)) {
+            ++per_m[(size_t)(il_s >> 1) + 1];
+            qmax = std::max(qmax, (int)seg_len[s]);
+        } else {
+            hq.push_back(g_nw.stage + seg_start[s]);
+            hl.push_back(seg_len[s]);
+            hp.push_back(il_s);
+        }
+    }
+    for (int m = 0; m < M; ++m) per_m[(size_t)m + 1] += per_m[(size_t)m];
+    const int64_t nd = per_m[(size_t)M];
+    order.resize((size_t)nd);
+    {
+        std::vector<int32_t> at(per_m.begin(), per_m.end() - 1);
+        for (int64_t s = 0; s < n_seg; ++s) {
+            const int il_s = pair_il[s];
+            const int64_t L = (int64_t)il[(size_t)il_s].size();
+            if (seg_len[s] <= 0 || L == 0) continue;
+            if (dev_ok && seg_len[s] <= NWP_QMAX && !sd::edlib_splits(seg_len[s], L)) order[(size_t)at[(size_t)(il_s >> 1)]++] = (int32_t)s;
+        }
+    }
+    if (nd > 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) != hipSuccess) return SD_ERR_HIP;
+        const int n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        int K = (tmax + 63) / 64;
+        if (K == 5) K = 6;
+        if (K == 7) K = 8;
+        const int S = sd::nw_block_cols(K);
+        const int cap = std::max(1, (qmax + S - 1) / S);
+        // items of up to `per` pairs of one monomer: ~12 waves per CU, more pairs per item (fewer flushes) on big sets
+        const int64_t R = std::max<int64_t>(1, std::min<int64_t>(64, nd / ((int64_t)n_cu * 12 * 64)));
+        const int64_t per = 64 * R;
+        std::vector<int32_t> items;
+        for (int m = 0; m < M; ++m)
+            for (int64_t a = per_m[(size_t)m]; a < per_m[(size_t)m + 1]; a += per)
+                items.insert(items.end(), {m, (int32_t)a, (int32_t)std::min<int64_t>(a + per, per_m[(size_t)m + 1]), 0});
+        const int n_items = (int)(items.size() / 4);
+        const size_t lane_bytes = (size_t)cap * K * 16;
+        int grid = (int)std::min<int64_t>(n_items, (int64_t)n_cu * 12);
+        grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (int64_t)(((size_t)1 << 30) / (lane_bytes * 64))));
+        const size_t lds = (size_t)10 * K * 8 + (size_t)(tmax + 1) * 12 * 4;
+        std::vector<unsigned long long> peq;
+        std::vector<int32_t> tl;
+        sd::nw_build_masks(il, K, peq, tl);
+        bool ok = g_nw.seq.need((size_t)text + 8) && g_nw.starts.need(sizeof(int64_t) * (size_t)n_seg) &&
+                  g_nw.lens.need(sizeof(int32_t) * (size_t)n_seg) && g_nw.pair.need(sizeof(int32_t) * (size_t)n_seg) &&
+                  g_nw.idx.need(sizeof(int32_t) * (size_t)nd) && g_nw.items.need(sizeof(int32_t) * items.size()) &&
+                  g_nw.peq.need(sizeof(unsigned long long) * peq.size()) && g_nw.tlen.need(sizeof(int32_t) * tl.size()) &&
+                  g_nw.poff.need(sizeof(int64_t) * off.size()) && g_nw.pcnt.need(sizeof(unsigned long long) * (size_t)total + 64) &&
+                  g_nw.ck.need(lane_bytes * 64 * (size_t)grid) && g_nw.ckpos.need((size_t)64 * 4);
+        if (!ok) return SD_ERR_HIP;
+        auto up = [](void* d, const void* h, size_t n) { return n == 0 || hipMemcpy(d, h, n, hipMemcpyHostToDevice) == hipSuccess; };
+        ok = up(g_nw.seq.p, g_nw.stage, (size_t)text) && up(g_nw.starts.p, seg_start, sizeof(int64_t) * (size_t)n_seg) &&
+             up(g_nw.lens.p, seg_len, sizeof(int32_t) * (size_t)n_seg) && up(g_nw.pair.p, pair_il, sizeof(int32_t) * (size_t)n_seg) &&
+             up(g_nw.idx.p, order.data(), sizeof(int32_t) * (size_t)nd) && up(g_nw.items.p, items.data(), sizeof(int32_t) * items.size()) &&
+             up(g_nw.peq.p, peq.data(), sizeof(unsigned long long) * peq.size()) && up(g_nw.tlen.p, tl.data(), sizeof(int32_t) * tl.size()) &&
+             up(g_nw.poff.p, off.data(), sizeof(int64_t) * off.size()) &&
+             hipMemset(g_nw.pcnt.p, 0, sizeof(unsigned long long) * (size_t)total + 64) == hipSuccess;
+        if (!ok) return SD_ERR_HIP;
+        unsigned long long* dcnt = static_cast<unsigned long long*>(g_nw.pcnt.p);
+        int* dfail = reinterpret_cast<int*>(dcnt + total);   // (the 64 bytes behind the counters)
+        launch_nw_profile(K, nullptr, grid, lds, static_cast<const uint8_t*>(g_nw.seq.p), static_cast<const int64_t*>(g_nw.starts.p),
+                          static_cast<const int32_t*>(g_nw.lens.p), static_cast<const int32_t*>(g_nw.idx.p),
+                          static_cast<const int32_t*>(g_nw.pair.p), static_cast<const int4*>(g_nw.items.p), n_items,
+                          static_cast<const unsigned long long*>(g_nw.peq.p), static_cast<const int32_t*>(g_nw.tlen.p),
+                          static_cast<const int64_t*>(g_nw.poff.p), cap, g_nw.ck.p, static_cast<int*>(g_nw.ckpos.p), dcnt, dfail);
+        if (hipGetLastError() != hipSuccess) return SD_ERR_HIP;
+    }
+    // the host's pairs, under the kernel
+    const int hrc = hq.empty() ? SD_OK : profile_host(hq.data(), hl.data(), hp.data(), (int64_t)hq.size(), il, threads, counts);
+    if (nd > 0) {
+        std::vector<unsigned long long> dc((size_t)total + 8);
+        if (hipMemcpy(dc.data(), g_nw.pcnt.p, sizeof(unsigned long long) * ((size_t)total + 8), hipMemcpyDeviceToHost) != hipSuccess)
+            return SD_ERR_HIP;
+        int fails = 0;
+        std::memcpy(&fails, dc.data() + total, sizeof fails);
+        if (fails) return SD_ERR_INTERNAL;   // cannot happen: the checkpoints are sized by the longest segment
+        for (int64_t i = 0; i < total; ++i) counts[i] += dc[(size_t)i];
+    }
+    return hrc;
 }
 }  // namespace sd
 

@@ -38,6 +38,15 @@ int nw_identity_device(const std::vector<std::pair<const char*, int64_t>>& spans
                        const int32_t* seg_len, int64_t n_seg, const std::vector<std::string>& tmpl,
                        const int32_t* pair_tmpl, bool homo, int device, int threads, int32_t* dist,
                        int32_t* matches);
+// Column profiles (include/sd_hip.h: SD_FLAG_PROFILE).  il: the interleaved templates m0, rc(m0), m1, ...; pair_il[s]:
+// segment s's template; counts: the forward monomers' blocks (profile_offsets), ADDED to.  nw_profile_device takes the
+// pairs of its kernel and gives the rest to profile_host (q[x], qlen[x]: pair x's query).
+int nw_profile_device(const std::vector<std::pair<const char*, int64_t>>& spans, const int64_t* seg_start,
+                      const int32_t* seg_len, int64_t n_seg, const std::vector<std::string>& il, const int32_t* pair_il,
+                      int device, int threads, uint64_t* counts);
+int profile_host(const char* const* q, const int32_t* qlen, const int32_t* pair_il, int64_t n,
+                 const std::vector<std::string>& il, int threads, uint64_t* counts);
+int64_t profile_offsets(const std::vector<int32_t>& fwd_len, std::vector<int64_t>& off);   // -> total counters
 // accumulated over the device identity calls of the process: preparation + staging, uploads, kernel, downloads
 void nw_stage_seconds(double out[4]);
 

@@ -127,17 +127,37 @@ struct NwQueryPacked {
     }
 };
 
+// Sink of the profile variant of nw_pair (PROF = true): the walk's steps of one pair, folded into the counters of its
+// forward monomer (include/sd_hip.h: SD_PROFILE_COLS per slot) -- cnt in LDS, one workgroup's privatised copy.  A pair
+// against rc(m): position p -> L-1-p, insertion slot h -> L-h, bases complemented.  The walk meets the insertions of a
+// slot consecutively (the row only decreases), so `last` is enough to count each instance once per slot.
+struct NwProf {
+    uint32_t* cnt;
+    int L;
+    bool rc;
+    int last = -1;
+    __device__ __forceinline__ int base(int b) const { return rc && b < 4 ? 3 - b : b; }
+    __device__ __forceinline__ void diag(int p, int b) { atomicAdd(cnt + (rc ? L - 1 - p : p) * 12 + base(b), 1u); }
+    __device__ __forceinline__ void del(int p) { atomicAdd(cnt + (rc ? L - 1 - p : p) * 12 + 5, 1u); }
+    __device__ __forceinline__ void ins(int h, int b) {
+        const int g = rc ? L - h : h;
+        if (g != last) { atomicAdd(cnt + g * 12 + 6, 1u); last = g; }
+        atomicAdd(cnt + g * 12 + 7 + base(b), 1u);
+    }
+};
+
 // The pair: ql query symbols (before compression), template masks eqt ([5][K] words, LDS or global), template
 // length tl (1 <= tl <= 64 K), homo = homopolymer-compress the query on the fly (main.py:87-92; the templates are
 // compressed by the host).  ck / ckpos: this lane's checkpoint slots, element stride `ckstride` in dwords: component
 // x (PvL, PvH, MvL, MvH) of word b of slot s at ck[((s * K + b) * 4 + x) * ckstride] -- planar dwords, so that a
 // wave's store is 256 contiguous bytes AND the four components need not sit in consecutive registers (as one 16-byte
 // store per word they cost a dozen register moves per column to keep them there); ckpos[s * ckstride]; `cap` slots.
-// Returns false when the pair needs more than `cap` checkpoints (nothing computed).
-template <int K, class Query>
+// Returns false when the pair needs more than `cap` checkpoints (nothing computed).  PROF: every step of the walk also
+// goes to *prof (homo must be false: a profile counts read bases).
+template <int K, class Query, bool PROF = false>
 __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restrict__ eqt, int tl, bool homo,
                                         uint32_t* __restrict__ ck, int* __restrict__ ckpos, size_t ckstride, int cap,
-                                        int& dist_out, int& matches_out) {
+                                        int& dist_out, int& matches_out, NwProf* prof = nullptr) {
     constexpr int S = nw_block_cols(K);
     const int pad = 64 * K - tl;           // padding rows below the template
     auto init = [&](NwState<K>& s) {
@@ -194,6 +214,7 @@ __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restric
     }
     // ---- pass 2: blocks from the last to the first; walk with edlib's priority up > left > diagonal
     int row = tl, nL = 0;
+    [[maybe_unused]] int qleft = c;   // (PROF) columns the walk has not consumed yet
     for (int blk = (c - 1) / S; blk >= 0 && row > 0; --blk) {
         int i;
         if (blk == 0) {
@@ -213,6 +234,7 @@ __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restric
         // column keeps "Pv after column x" in ONE set of registers that is both the history entry and the input of
         // column x + 1 (a predicated one costs a register copy per vector and column).
         uint32_t hPhL[S][K], hPhH[S][K], hPvL[S][K], hPvH[S][K];
+        [[maybe_unused]] int hsym[S];   // (PROF) the block's query symbols
         int pv = i > 0 ? q.code(i - 1) : -1;
 #pragma unroll
         for (int x = 0; x < S; ++x) {
@@ -225,6 +247,7 @@ __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restric
                     if (!skip) break;
                 } while (true);
             }
+            if constexpr (PROF) hsym[x] = r;
             NwState<K> in;
 #pragma unroll
             for (int b2 = 0; b2 < K; ++b2) {
@@ -249,11 +272,21 @@ __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restric
                 const uint32_t pw = nw_pick<K>(hPvL[x], hPvH[x], bit >> 5);
                 const uint32_t up = (ph >> (bit & 31)) & 1u;
                 const uint32_t lf = (pw >> (bit & 31)) & 1u & ~up;
+                if constexpr (PROF) {
+                    if (up) prof->ins(row, hsym[x]);
+                    else if (lf) prof->del(row - 1);
+                    else prof->diag(row - 1, hsym[x]);
+                    qleft -= (int)(1u - lf);
+                }
                 row -= (int)(1u - up);   // left or diagonal: one template symbol consumed
                 nL += (int)lf;
                 live = lf && row > 0;    // a left move stays in this column
             }
         }
+    }
+    if constexpr (PROF) {   // row 0 reached with query symbols left: insertions before the template; column 0 with rows left: deletions
+        for (int j = 0; j < qleft; ++j) prof->ins(0, q.code(j));
+        for (int r = 0; r < row; ++r) prof->del(r);
     }
     nL += row;   // column 0 reached with template symbols left: all "left" moves
     dist_out = score;

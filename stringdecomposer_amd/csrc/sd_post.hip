@@ -13,6 +13,7 @@
 
 #include "../../include/sd_hip.h"
 #include "sd_host.hpp"
+#include "sd_nw.hpp"
 
 namespace {
 
@@ -34,6 +35,7 @@ struct BitNW {
     std::vector<uint64_t> cp, cm;  // one column (column scores)
     std::vector<int32_t> colL, colR;
     std::string rq, rt;
+    std::vector<uint8_t>* ops = nullptr;   // when set, traceback / path append the path in edlib's codes (0 '=', 1 'I', 2 'D', 3 'X')
     uint16_t cls[256];
     // symbol classes of one pair: every byte of the query its own class, bytes only the target has share class 0
     // (they match nothing) -- edlib's alphabet is the set of bytes that occur
@@ -123,6 +125,7 @@ struct BitNW {
         int i = qlen, j = tlen, m = 0;
         int cur = D(i, j);
         const int dist = cur;
+        const size_t o0 = ops ? ops->size() : 0;
         while (i > 0 || j > 0) {
             int up = -1;
             if (i > 0) {  // D[i-1][j] from the vertical delta of row i in column j
@@ -130,15 +133,17 @@ struct BitNW {
                 const size_t w = (size_t)j * K + ((i - 1) >> 6);
                 up = cur - ((pv[w] & bit) ? 1 : 0) + ((mv[w] & bit) ? 1 : 0);
             }
-            if (i > 0 && up + 1 == cur) { --i; cur = up; continue; }          // 'I'
+            if (i > 0 && up + 1 == cur) { --i; cur = up; if (ops) ops->push_back(1); continue; }   // 'I'
             if (j > 0) {
                 const int left = D(i, j - 1);
-                if (left + 1 == cur) { --j; cur = left; continue; }          // 'D'
+                if (left + 1 == cur) { --j; cur = left; if (ops) ops->push_back(2); continue; }   // 'D'
             }
             const int dg = D(i - 1, j - 1);                                    // '=' or 'X'
             if (dg == cur) ++m;
+            if (ops) ops->push_back(dg == cur ? 0 : 3);
             --i; --j; cur = dg;
         }
+        if (ops) std::reverse(ops->begin() + (std::ptrdiff_t)o0, ops->end());   // walked from the end
         matches += m;
         return dist;
     }
@@ -150,7 +155,10 @@ struct BitNW {
     // (edlib.cpp:1315-1349; its banded columns hold every cell of an optimal path exactly, so the full columns
     // find the same row), and the paths of (q[0..x], left half) and (q[x+1..), right half) are concatenated.
     bool path(const char* q, int qlen, const char* t, int tlen, int best, int32_t& matches) {
-        if (qlen == 0 || tlen == 0) return true;
+        if (qlen == 0 || tlen == 0) {   // one side empty: the other's symbols all as 'D' / 'I'
+            if (ops) ops->insert(ops->end(), (size_t)(qlen + tlen), (uint8_t)(qlen == 0 ? 2 : 1));
+            return true;
+        }
         if (!edlib_splits(qlen, tlen)) return traceback(q, qlen, t, tlen, matches) == best;
         const int lw = tlen / 2, rw = tlen - lw;
         std::vector<int32_t> L, R;
@@ -290,6 +298,149 @@ extern "C" int sd_identity_segments(const char* seq, int64_t seqlen, const int64
         for (auto& x : th) x.join();
     }
     return SD_OK;
+}
+
+
+// ---- monomer column profiles (--profile): the path behind a row's identity, folded into its forward monomer ----------
+namespace sd {
+
+int64_t profile_offsets(const std::vector<int32_t>& fwd_len, std::vector<int64_t>& off) {
+    off.assign(fwd_len.size() + 1, 0);
+    for (size_t m = 0; m < fwd_len.size(); ++m) off[m + 1] = off[m] + ((int64_t)fwd_len[m] + 1) * SD_PROFILE_COLS;
+    return off.back();
+}
+
+namespace {
+inline int prof_code(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
+// edlib path of (q, template) -> counters of the forward monomer (cnt: its (L + 1) x SD_PROFILE_COLS block).  rc: the
+// template is the reverse complement of the monomer: position p -> L-1-p, slot h -> L-h, bases complemented.
+void fold_path(const std::vector<uint8_t>& ops, const char* q, int L, bool rc, uint64_t* cnt) {
+    int i = 0, j = 0, last = -1;
+    for (uint8_t op : ops) {
+        if (op == 2) { cnt[(size_t)(rc ? L - 1 - j : j) * SD_PROFILE_COLS + 5] += 1; ++j; continue; }
+        int b = prof_code(q[i++]);
+        if (rc && b < 4) b = 3 - b;
+        if (op == 1) {
+            const int g = rc ? L - j : j;
+            if (g != last) { cnt[(size_t)g * SD_PROFILE_COLS + 6] += 1; last = g; }
+            cnt[(size_t)g * SD_PROFILE_COLS + 7 + b] += 1;
+        } else {
+            cnt[(size_t)(rc ? L - 1 - j : j) * SD_PROFILE_COLS + b] += 1;
+            ++j;
+        }
+    }
+}
+}  // namespace
+
+int profile_host(const char* const* q, const int32_t* qlen, const int32_t* pair_il, int64_t n,
+                 const std::vector<std::string>& il_seq, int threads, uint64_t* counts) {
+    const size_t M = il_seq.size() / 2;
+    std::vector<int32_t> fl(M);
+    for (size_t m = 0; m < M; ++m) fl[m] = (int32_t)il_seq[2 * m].size();
+    std::vector<int64_t> off;
+    const int64_t total = profile_offsets(fl, off);
+    for (int64_t x = 0; x < n; ++x) {
+        if (pair_il[x] < 0 || (size_t)pair_il[x] >= 2 * M) return SD_ERR_PARAM;
+        if (qlen[x] > SD_NW_HOST_MAX) return SD_ERR_UNSUPPORTED;
+    }
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads, n / 16 + 1));
+    std::vector<std::vector<uint64_t>> part((size_t)nt);
+    std::atomic<int64_t> next{0};
+    std::atomic<int> bad{0};
+    auto work = [&](int k) {
+        std::vector<uint64_t>& acc = part[(size_t)k];
+        acc.assign((size_t)total, 0);
+        BitNW nw;
+        std::vector<uint8_t> ops;
+        nw.ops = &ops;
+        for (;;) {
+            const int64_t x = next.fetch_add(1);
+            if (x >= n) break;
+            const int il = pair_il[x];
+            const std::string& t = il_seq[(size_t)il];
+            const int ql = qlen[x], tl = (int)t.size();
+            if (ql <= 0 || tl <= 0) continue;   // no alignment (main.py:30-33): not an instance
+            ops.clear();
+            int32_t m = 0;
+            if (!edlib_splits(ql, tl)) {
+                nw.traceback(q[x], ql, t.data(), tl, m);
+            } else {
+                std::vector<int32_t> col;
+                nw.column_scores(q[x], ql, t.data(), tl, col);
+                if (!nw.path(q[x], ql, t.data(), tl, col[(size_t)ql], m)) { bad = 1; continue; }
+            }
+            fold_path(ops, q[x], tl, (il & 1) != 0, acc.data() + off[(size_t)(il >> 1)]);
+        }
+    };
+    if (nt == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> th;
+        for (int k = 0; k < nt; ++k) th.emplace_back(work, k);
+        for (auto& x : th) x.join();
+    }
+    if (bad) return SD_ERR_INTERNAL;
+    for (const std::vector<uint64_t>& a : part)
+        for (int64_t i = 0; i < total; ++i) counts[i] += a[(size_t)i];
+    return SD_OK;
+}
+
+}  // namespace sd
+
+// monomers (forward) -> interleaved m0, m0', m1, m1', ... as the profile functions take them
+static int profile_templates(const char* const* tmpl, const int32_t* tlen, int32_t T, std::vector<std::string>& il) {
+    il.clear();
+    for (int t = 0; t < T; ++t) {
+        if (tlen[t] < 0 || tlen[t] > SD_NW_HOST_MAX) return SD_ERR_PARAM;
+        std::string f(tmpl[t], (size_t)tlen[t]), r;
+        if (!sd::reverse_complement(f, r)) return SD_ERR_SYMBOL;
+        il.push_back(f);
+        il.push_back(r);
+    }
+    return SD_OK;
+}
+
+static int profile_segments_impl(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                                 const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl,
+                                 int32_t device, int32_t threads, uint64_t* counts) {
+    if (n_seg < 0 || T < 1 || !seq || !tmpl || !tlen || !counts || (n_seg && (!starts || !ends || !pair_tmpl)))
+        return SD_ERR_PARAM;
+    std::vector<std::string> il;
+    int rc = profile_templates(tmpl, tlen, T, il);
+    if (rc) return rc;
+    std::vector<int32_t> fl((size_t)T);
+    for (int t = 0; t < T; ++t) fl[(size_t)t] = tlen[t];
+    std::vector<int64_t> off;
+    std::memset(counts, 0, sizeof(uint64_t) * (size_t)sd::profile_offsets(fl, off));
+    std::vector<int64_t> st((size_t)n_seg);
+    std::vector<int32_t> ln((size_t)n_seg);
+    for (int64_t s = 0; s < n_seg; ++s) {
+        if (starts[s] < 0 || ends[s] >= seqlen || pair_tmpl[s] < 0 || pair_tmpl[s] >= 2 * T) return SD_ERR_PARAM;
+        const int64_t l = std::max<int64_t>(0, ends[s] - starts[s] + 1);
+        if (l > SD_NW_HOST_MAX) return SD_ERR_UNSUPPORTED;
+        st[(size_t)s] = starts[s];
+        ln[(size_t)s] = (int32_t)l;
+    }
+    if (device >= 0) {
+        std::vector<std::pair<const char*, int64_t>> spans(1, std::make_pair(seq, seqlen));
+        return sd::nw_profile_device(spans, st.data(), ln.data(), n_seg, il, pair_tmpl, device, threads, counts);
+    }
+    std::vector<const char*> qp((size_t)n_seg);
+    for (int64_t s = 0; s < n_seg; ++s) qp[(size_t)s] = seq + st[(size_t)s];
+    return sd::profile_host(qp.data(), ln.data(), pair_tmpl, n_seg, il, threads, counts);
+}
+
+extern "C" int sd_profile_segments(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends,
+                                   int64_t n_seg, const char* const* tmpl, const int32_t* tlen, int32_t T,
+                                   const int32_t* pair_tmpl, int32_t threads, uint64_t* counts) {
+    return profile_segments_impl(seq, seqlen, starts, ends, n_seg, tmpl, tlen, T, pair_tmpl, -1, threads, counts);
+}
+
+extern "C" int sd_profile_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends,
+                                       int64_t n_seg, const char* const* tmpl, const int32_t* tlen, int32_t T,
+                                       const int32_t* pair_tmpl, int32_t device, int32_t threads, uint64_t* counts) {
+    if (device < 0) return SD_ERR_PARAM;
+    return profile_segments_impl(seq, seqlen, starts, ends, n_seg, tmpl, tlen, T, pair_tmpl, device, threads, counts);
 }
 
 

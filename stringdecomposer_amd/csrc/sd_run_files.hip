@@ -40,6 +40,11 @@ static TextPool& g_textpool_ref() { static TextPool* p = new TextPool; return *p
 extern "C++" void text_pool_clear() { g_textpool.clear(); }
 
 // per device entry of the last call (sd_last_run_device_stats): batches dealt to it, device busy ms
+// the profile of the last sd_run_files* call (SD_FLAG_PROFILE; sd_last_run_profile)
+static bool g_last_prof_on = false;
+static std::vector<uint64_t> g_last_prof;
+static std::string g_last_prof_text;
+static int32_t g_last_prof_n = 0;
 static int g_last_ndev = 0;
 static int64_t g_last_dev_batches[kMaxDevices] = {0};
 static double g_last_dev_busy[kMaxDevices] = {0};
@@ -522,6 +527,15 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     std::string err;
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    // SD_FLAG_PROFILE shapes the post-processing only: the pipelines (and their cache keys) never see it
+    sd_params p_job = *p;
+    const bool profile = (p_job.reserved[1] & SD_FLAG_PROFILE) != 0;
+    p_job.reserved[1] &= ~SD_FLAG_PROFILE;
+    p = &p_job;
+    {
+        std::lock_guard<std::mutex> lk(g_last_m);
+        g_last_prof_on = false;
+    }
     const std::vector<int32_t> devs = dev_list ? *dev_list : std::vector<int32_t>{p->device};
     const size_t nd = devs.size();
     if (!reads_fa || !monomers_fa || !raw_tsv_out || !final_tsv_out || !alt_tsv_out || !lr_coef || world < 1 || rank < 0 ||
@@ -547,6 +561,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     TemplateSet ts(in.monos);
     sd::PostProcessor pp;
     rc = pp.init(in.monos, min_identity, second_best != 0, lr_coef, devs[0], p->threads, err);
+    if (rc == SD_OK && profile) rc = pp.enable_profile(err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     OutFiles files;
     if (!files.open(raw_tsv_out, final_tsv_out, alt_tsv_out, p->threads)) {
@@ -662,6 +677,14 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkeys[i], std::move(pipes[i]), (int)i);
     }
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    if (profile) {
+        if (timing) std::fprintf(stderr, "[sd timing] column profiles of the kept rows: %.1f ms\n", pp.t_profile * 1e3);
+        std::lock_guard<std::mutex> lk(g_last_m);
+        g_last_prof = pp.profile();
+        g_last_prof_text = pp.profile_text();
+        g_last_prof_n = (int32_t)in.monos.size();
+        g_last_prof_on = true;
+    }
     return SD_OK;
 } catch (const std::bad_alloc&) {
     set_err(errbuf, errlen, "out of host memory");
@@ -674,6 +697,17 @@ int sd_run_files_records(const char* reads_fa, const char* monomers_fa, const sd
                          int32_t second_best, const double* lr_coef, char* errbuf, size_t errlen) {
     return run_files_impl(reads_fa, monomers_fa, p, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
                           lr_coef, nullptr, errbuf, errlen, records_out);
+}
+
+int sd_last_run_profile(int32_t* n_monomers, int64_t* n_counts, int64_t* text_bytes, char* text, uint64_t* counts) {
+    std::lock_guard<std::mutex> lk(g_last_m);
+    if (!g_last_prof_on) return SD_ERR_PARAM;
+    if (n_monomers) *n_monomers = g_last_prof_n;
+    if (n_counts) *n_counts = (int64_t)g_last_prof.size();
+    if (text_bytes) *text_bytes = (int64_t)g_last_prof_text.size() + 1;
+    if (text) std::memcpy(text, g_last_prof_text.c_str(), g_last_prof_text.size() + 1);
+    if (counts) std::memcpy(counts, g_last_prof.data(), sizeof(uint64_t) * g_last_prof.size());
+    return SD_OK;
 }
 
 void sd_last_run_stats(double out[24]) {

@@ -346,6 +346,7 @@ int sd_stream_create(sd_stream** out, const sd_params* p, const char* const* mon
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     if (n_mono <= 0 || !mono_seqs || !mono_lens) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
+    if (p->reserved[1] & SD_FLAG_PROFILE) { set_err(errbuf, errlen, "SD_FLAG_PROFILE needs a final-mode stream"); return SD_ERR_PARAM; }
     std::unique_ptr<sd_stream> s(new sd_stream);
     rc = stream_open(s.get(), p, mono_seqs, mono_lens, n_mono, sub_batches, errbuf, errlen);
     if (rc) return rc;
@@ -379,7 +380,10 @@ static int stream_create_final(sd_stream** out, const sd_params* p, const char* 
     FinalMode& fm = *s->fin;
     fm.second_best = second_best != 0;
     rc = fm.pp.init(monos, min_identity, fm.second_best, lr_coef, p->device, p->threads, err);
+    if (rc == SD_OK && (p->reserved[1] & SD_FLAG_PROFILE)) rc = fm.pp.enable_profile(err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    sd_params q = *p;   // (the flag shapes the post-processing only)
+    q.reserved[1] &= ~SD_FLAG_PROFILE;
     // every engine of the pipeline (the first now, the others as the pipeline creates them) computes the identities of
     // its batches in-stream; a template set the kernels do not take, or SD_FLAG_NO_STREAM_IDENT, leaves them all to
     // the fallback
@@ -389,7 +393,7 @@ static int stream_create_final(sd_stream** out, const sd_params* p, const char* 
         if (sp->pipe.p.reserved[1] & SD_FLAG_NO_STREAM_IDENT) f.ident = false;
         if (f.ident && !engine_set_identity(e, f.pp.interleaved_seqs(), f.pp.own_interleaved(), f.second_best)) f.ident = false;
     };
-    rc = stream_open(s.get(), p, mono_seqs, mono_lens, n_mono, sub_batches, errbuf, errlen, devs);
+    rc = stream_open(s.get(), &q, mono_seqs, mono_lens, n_mono, sub_batches, errbuf, errlen, devs);
     if (rc) return rc;
     *out = s.release();
     return SD_OK;
@@ -422,6 +426,7 @@ int sd_stream_create_devices(sd_stream** out, const sd_params* p, const int32_t*
     q.device = devices[0];
     if (n_devices == 1) return sd_stream_create(out, &q, mono_seqs, mono_lens, n_mono, sub_batches, errbuf, errlen);
     if (n_mono <= 0 || !mono_seqs || !mono_lens) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
+    if (p->reserved[1] & SD_FLAG_PROFILE) { set_err(errbuf, errlen, "SD_FLAG_PROFILE needs a final-mode stream"); return SD_ERR_PARAM; }
     const std::vector<int32_t> devs(devices, devices + n_devices);
     std::unique_ptr<sd_stream> s(new sd_stream);
     rc = stream_open(s.get(), &q, mono_seqs, mono_lens, n_mono, sub_batches, errbuf, errlen, &devs);
@@ -659,6 +664,20 @@ int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys
     const std::vector<std::string>& k = s->fin->pp.key_names();
     for (int32_t i = 0; i < cap && i < (int32_t)k.size(); ++i) keys[i] = k[(size_t)i].c_str();
     if (n_keys) *n_keys = (int32_t)k.size();
+    return SD_OK;
+}
+
+int sd_stream_profile(sd_stream* s, int32_t reset, int32_t* n_monomers, int64_t* n_counts, int64_t* text_bytes,
+                      char* text, uint64_t* counts) {
+    if (!s || !s->fin || !s->fin->pp.profiling()) return SD_ERR_PARAM;
+    sd::PostProcessor& pp = s->fin->pp;
+    const std::vector<uint64_t> v = pp.profile(reset && counts);
+    const std::string t = pp.profile_text();
+    if (n_monomers) *n_monomers = (int32_t)(pp.interleaved_seqs().size() / 2);
+    if (n_counts) *n_counts = (int64_t)v.size();
+    if (text_bytes) *text_bytes = (int64_t)t.size() + 1;
+    if (text) std::memcpy(text, t.c_str(), t.size() + 1);
+    if (counts) std::memcpy(counts, v.data(), sizeof(uint64_t) * v.size());
     return SD_OK;
 }
 

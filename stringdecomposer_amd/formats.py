@@ -12,6 +12,15 @@ Three tab-separated text files make up the contract with downstream tools (centr
   <out>_alt.tsv   6 columns (main.py:161-165): read, monomer, start, end, identity, '*' for the
                   monomer reported in <out>.tsv else '-'
 
+Two more text files are this package's own (opt-in, `--profile`):
+
+  <out>_profile.tsv   the column profile of every monomer over the rows of <out>.tsv: a header line, then per
+                      monomer (FASTA order) rows g = 0..L of 16 columns -- name, g, ref (the monomer's base at g, '-' at
+                      g = L), n (instances), A C G T N (read bases aligned to position g), del, ins_n (instances with
+                      an insertion in slot g, i.e. before position g), insA insC insG insT insN (the inserted bases).
+                      Instances of m' are folded into m (reverse-complemented).  read_profile / write_profile below.
+  <out>_consensus.fa  one record per monomer, ">name instances=n", the consensus of its profile (consensus below).
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -292,3 +301,118 @@ def raw_to_records(rows, templates, scoring=(-1, -1, -1, 1), part_size=5000, ove
         reads.append((name, -1 if read_lens is None else read_lens.get(name, -1),
                       [(idx[r.monomer], r.start, r.end, int(r.score)) for r in rr]))
     return Records(tuple(scoring), part_size, overlap, ed_thr, list(templates), reads)
+
+
+# ---- column profiles (--profile) -------------------------------------------------------------------------------------
+PROFILE_COLUMNS = ("A", "C", "G", "T", "N", "del", "ins_n", "insA", "insC", "insG", "insT", "insN")
+PROFILE_NCOLS = len(PROFILE_COLUMNS)
+PROFILE_HEADER = "name\tg\tref\tn\t" + "\t".join(PROFILE_COLUMNS) + "\n"
+# names, seqs (forward monomers, FASTA order) and counts: per monomer an int64 array [len(seq) + 1, PROFILE_NCOLS] (or,
+# from lib.last_run_profile(numpy=False), the same rows as lists of ints -- every function below takes either)
+Profile = namedtuple("Profile", "names seqs counts")
+
+
+def split_counts(lens, flat, numpy=True):
+    """The flat counter vector of the C-ABI (monomer after monomer, (L + 1) x 12 each) -> a list of [L + 1, 12] arrays
+    (numpy=False: lists of row lists)."""
+    out, at = [], 0
+    for L in lens:
+        k = (int(L) + 1) * PROFILE_NCOLS
+        if numpy:
+            import numpy as np
+            out.append(np.asarray(flat[at:at + k], dtype=np.int64).reshape(int(L) + 1, PROFILE_NCOLS))
+        else:
+            out.append([[int(v) for v in flat[at + g * PROFILE_NCOLS:at + (g + 1) * PROFILE_NCOLS]] for g in range(int(L) + 1)])
+        at += k
+    return out
+
+
+def profile_from_counts(names, seqs, flat, numpy=True):
+    return Profile(list(names), list(seqs), split_counts([len(x) for x in seqs], flat, numpy=numpy))
+
+
+def profile_instances(c):
+    """n of one monomer's counters: the instances (NW is global, so A..del sum to n at every position)."""
+    return sum(int(v) for v in c[0][:6]) if len(c) > 1 else 0
+
+
+def format_profile(prof):
+    out = [PROFILE_HEADER]
+    for name, seq, c in zip(prof.names, prof.seqs, prof.counts):
+        n = profile_instances(c)
+        for g in range(len(seq) + 1):
+            ref = seq[g] if g < len(seq) else "-"
+            out.append("%s\t%d\t%s\t%d\t%s\n" % (name, g, ref, n, "\t".join(str(int(v)) for v in c[g])))
+    return "".join(out)
+
+
+def write_profile(path, prof):
+    with open(path, "w") as f:
+        f.write(format_profile(prof))
+
+
+def read_profile(path):
+    """<out>_profile.tsv -> Profile (the sequences are rebuilt from the ref column)."""
+    import numpy as np
+    names, seqs, rows = [], [], []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            if lineno == 1 and line == PROFILE_HEADER:
+                continue
+            x = line.rstrip("\n").split("\t")
+            if len(x) != 4 + PROFILE_NCOLS:
+                raise FormatError(path, lineno, "expected %d columns, got %d" % (4 + PROFILE_NCOLS, len(x)))
+            if int(x[1]) == 0:
+                names.append(x[0])
+                seqs.append([])
+                rows.append([])
+            elif not names or x[0] != names[-1] or int(x[1]) != len(rows[-1]):
+                raise FormatError(path, lineno, "rows of a monomer must run g = 0, 1, ..., L")
+            if x[2] != "-":
+                seqs[-1].append(x[2])
+            rows[-1].append([int(v) for v in x[4:]])
+    return Profile(names, ["".join(q) for q in seqs], [np.asarray(r, dtype=np.int64).reshape(-1, PROFILE_NCOLS) for r in rows])
+
+
+def _argmax_first(vals):
+    best = 0
+    for i in range(1, len(vals)):
+        if vals[i] > vals[best]:
+            best = i
+    return best
+
+
+def consensus(prof):
+    """[(name, n, sequence)]: per slot g = 0..L, the most frequent inserted base when more than half of the instances
+    insert there (ties: first of ACGTN), then for g < L the most frequent of A C G T N del (ties: the monomer's own
+    base if it is among them, else the first in that order; del emits nothing).  n = 0 keeps the monomer's sequence."""
+    out = []
+    for name, seq, c in zip(prof.names, prof.seqs, prof.counts):
+        n = profile_instances(c)
+        if n == 0:
+            out.append((name, 0, seq))
+            continue
+        s = []
+        for g in range(len(seq) + 1):
+            row = [int(x) for x in c[g]]
+            if 2 * row[6] > n:
+                s.append("ACGTN"[_argmax_first(row[7:12])])
+            if g == len(seq):
+                break
+            v = row[:6]
+            top = max(v)
+            r = "ACGTN".find(seq[g])
+            k = r if r >= 0 and v[r] == top else v.index(top)
+            if k < 5:
+                s.append("ACGTN"[k])
+        out.append((name, n, "".join(s)))
+    return out
+
+
+def format_consensus(prof):
+    return "".join(">%s instances=%d\n%s\n" % (name, n, sq) for name, n, sq in consensus(prof))
+
+
+def write_consensus(path, prof):
+    with open(path, "w") as f:
+        f.write(format_consensus(prof))

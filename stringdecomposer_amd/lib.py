@@ -45,6 +45,7 @@ EXPORTS = [
     "sd_run_files_devices", "sd_last_run_device_stats", "sd_multi_device_selftest",
     "sd_stream_create_final", "sd_stream_collect_final", "sd_stream_keys", "sd_stream_final_stats",
     "sd_stream_create_devices", "sd_stream_create_final_devices", "sd_stream_device_stats",
+    "sd_profile_segments", "sd_profile_segments_dev", "sd_last_run_profile", "sd_stream_profile",
 ]
 
 
@@ -197,6 +198,13 @@ def load():
                                                  P(C.c_char_p), P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                  P(C.c_double), C.c_char_p, C.c_size_t]
     L.sd_stream_device_stats.argtypes = [C.c_void_p, P(C.c_int64), P(C.c_double), C.c_int32]
+    L.sd_profile_segments.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_char_p),
+                                      P(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    L.sd_profile_segments_dev.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_char_p),
+                                          P(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
+    L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
+                                    C.c_void_p]
     _lib = L
     return L
 
@@ -216,6 +224,7 @@ FLAG_NO_F16, FLAG_FULL_FLOOR, FLAG_NO_EDTHR_COMPACT, FLAG_FILTER_GENERAL, FLAG_N
 FLAG_TRACE_V1 = 64
 FLAG_NO_IDENT_PRUNE = 256   # --second-best: every homopolymer-compressed pair aligned in full (no distance-only pruning)
 FLAG_NO_U16 = 128     # narrow layout: fp16 / int16 cells as in rounds 1-5 instead of the biased-u16 format
+FLAG_PROFILE = 512    # per-monomer column profiles of the kept rows (run_files(profile=True), Stream(profile=True))
 
 
 def make_params(scoring=(-1, -1, -1, 1), part_size=5000, overlap=500, ed_thr=-1, threads=1,
@@ -285,12 +294,15 @@ def decompose_files(reads_fa, monomers_fa, raw_tsv_out, **kw):
 
 
 def run_files(reads_fa, monomers_fa, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity=0, second_best=False,
-              lr_coef=(-31.48494996, 0.41784018, 0.69186882), records_out=None, devices=None, **kw):
+              lr_coef=(-31.48494996, 0.41784018, 0.69186882), records_out=None, devices=None, profile=False, **kw):
     """The whole CLI job natively (sd_run_files): raw, final and _alt TSV files from the two FASTA files; with
     records_out also the binary record stream of the raw rows (sd_run_files_records).  devices (a list of ordinals,
     repeats allowed): one pipeline per entry in this process (sd_run_files_devices; `device` is then ignored), the
-    same output bytes."""
+    same output bytes.  profile=True (SD_FLAG_PROFILE): also the column profiles of the monomers over the rows of the
+    final TSV, returned as a formats.Profile (and by last_run_profile()); the three files are unchanged."""
     L = load()
+    if profile:
+        kw["flags"] = int(kw.get("flags", 0)) | FLAG_PROFILE
     p = make_params(**kw)
     err = C.create_string_buffer(4096)
     coef = (C.c_double * 3)(*[float(x) for x in lr_coef])
@@ -311,6 +323,62 @@ def run_files(reads_fa, monomers_fa, raw_tsv_out, final_tsv_out, alt_tsv_out, mi
                                     int(min_identity), 1 if second_best else 0, coef, err, 4096)
     if rc != SD_OK:
         raise SdError(rc, err.value.decode(errors="replace"))
+    return last_run_profile() if profile else None
+
+
+def _profile_from(fn, *lead, numpy=True):
+    """A formats.Profile from the two-call form of sd_last_run_profile / sd_stream_profile (fn(*lead, outputs...))."""
+    from . import formats
+    n, nc, tb = C.c_int32(), C.c_int64(), C.c_int64()
+    rc = fn(*lead, C.byref(n), C.byref(nc), C.byref(tb), None, None)
+    if rc != SD_OK:
+        raise SdError(rc, "no profile: the call was made without the profile flag")
+    text = C.create_string_buffer(max(int(tb.value), 1))
+    counts = (C.c_uint64 * max(int(nc.value), 1))()
+    rc = fn(*lead, C.byref(n), C.byref(nc), C.byref(tb), text, counts)
+    if rc != SD_OK:
+        raise SdError(rc, "profile")
+    lines = text.value.decode().split("\n")[:n.value]
+    names = [x.split("\t")[0] for x in lines]
+    seqs = [x.split("\t")[1] for x in lines]
+    return formats.profile_from_counts(names, seqs, counts[:int(nc.value)], numpy=numpy)
+
+
+def last_run_profile(numpy=True):
+    """The formats.Profile of the last run_files call of this process made with profile=True (sd_last_run_profile);
+    numpy=False gives the counters as lists of row lists (no numpy import: what the command line writes from)."""
+    L = load()
+    return _profile_from(L.sd_last_run_profile, numpy=numpy)
+
+
+def profile_segments(seq, starts, ends, templates, pair_tmpl, threads=1, device=None):
+    """Column profiles (sd_profile_segments[_dev]) of segments seq[starts[s] .. ends[s]] (inclusive) aligned to
+    monomer pair_tmpl[s] >> 1, against its reverse complement when pair_tmpl[s] & 1; templates = the FORWARD monomers.
+    Returns the counters: a list over monomers of int64 arrays [L + 1, 12] (formats.PROFILE_COLUMNS).  device=None: host
+    threads; device=<ordinal>: the HIP kernel, with the host form for the pairs it does not take."""
+    import numpy as np
+    from . import formats
+    L = load()
+    sb = _b(seq)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
+    n = int(st.shape[0])
+    if en.shape[0] != n or pt.shape[0] != n:
+        raise SdError(SD_ERR_PARAM, "profile_segments: starts, ends and pair_tmpl differ in length")
+    tb = [_b(t) for t in templates]
+    T = len(tb)
+    tl = (C.c_int32 * max(T, 1))(*[len(t) for t in tb])
+    counts = np.zeros(sum(len(t) + 1 for t in tb) * formats.PROFILE_NCOLS, dtype=np.uint64)
+    if device is None:
+        rc = L.sd_profile_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data,
+                                   int(threads), counts.ctypes.data)
+    else:
+        rc = L.sd_profile_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data,
+                                       int(device), int(threads), counts.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_profile_segments" + ("" if device is None else "_dev"))
+    return formats.split_counts([len(t) for t in tb], counts.astype(np.int64))
 
 
 def decompose_files_records(reads_fa, monomers_fa, records_out, **kw):
@@ -611,15 +679,18 @@ class Stream:
     of _alt.tsv) as a FinalRows instead of the raw DP rows, with identities computed on the device behind each batch.
     mono_names are required there (names are the keys: a repeated name is one key); min_identity, second_best and
     lr_coef are the command line's -i, --second-best and model coefficients (None: models/ont_logreg_model.txt, as
-    the command line reads it).  formats.final_rows turns a FinalRows into FinalRow / AltRow lists.
+    the command line reads it).  formats.final_rows turns a FinalRows into FinalRow / AltRow lists.  profile=True
+    (final mode only, names unique) also sums the column profiles of the kept rows: profile().
 
     devices (a list of ordinals, repeats allowed; `device` is then ignored): one pipeline per entry in this process
     (sd_stream_create_devices / sd_stream_create_final_devices), each driven by a thread of its own; every job is cut
     into at least two batches per entry and the rows are those of the plain stream.  [d] is the plain stream on d."""
 
     def __init__(self, mono_seqs, sub_batches=1, final=False, mono_names=None, second_best=False, min_identity=0,
-                 lr_coef=None, devices=None, **kw):
+                 lr_coef=None, devices=None, profile=False, **kw):
         self.L = load()
+        if profile:
+            kw["flags"] = int(kw.get("flags", 0)) | FLAG_PROFILE
         self.params = make_params(**kw)
         self._err = C.create_string_buffer(4096)
         ms = [_b(s) for s in mono_seqs]
@@ -674,6 +745,11 @@ class Stream:
         rs = reads if isinstance(reads, ReadSet) else ReadSet(reads)
         self._check(self.L.sd_stream_submit(self.h, rs.ptrs, rs.lens, rs.n, self._err, 4096))
         self._n_reads.append(rs.n)
+
+    def profile(self, reset=False):
+        """Stream(final=True, profile=True): the formats.Profile of the rows of every job processed so far (summed);
+        reset=True zeroes the sums after the copy."""
+        return _profile_from(self.L.sd_stream_profile, self.h, 1 if reset else 0)
 
     def keys(self):
         """Final mode: the distinct monomer names in the library's key order (what FinalRows' indices refer to)."""

@@ -356,7 +356,7 @@ def convert_tsv(decomposition, reads, monomers, outfile, identity_th, light, thr
 
 def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr, overlap, logger,
         ref_compat=False, device=0, kernel=0, final_file=None, min_identity=0, second_best=False, records_file=None,
-        devices=None):
+        devices=None, profile=False):
     """main.py:186-197 with the subprocess replaced by libsd_hip.so.
 
     Single process with final_file given: ONE native call (sd_run_files) streams the job through the
@@ -419,7 +419,9 @@ def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr,
                       min_identity=min_identity, second_best=second_best, lr_coef=_lr_coef(),
                       scoring=(ins, dels, mm, match), part_size=int(batch_size), overlap=int(overlap),
                       ed_thr=int(ed_thr), threads=int(num_threads), device=device, kernel=kernel,
-                      flags=lib.FLAG_PROGRESS,   # the dp binary's progress lines on stderr (main.cpp:82,115,393)
+                      # the dp binary's progress lines on stderr (main.cpp:82,115,393); --profile: the counters stay in the
+                      # library until main() writes them (lib.last_run_profile(numpy=False): no numpy import on this path)
+                      flags=lib.FLAG_PROGRESS | (lib.FLAG_PROFILE if profile else 0),
                       records_out=records_file, devices=devices)
         return True
     lib.decompose_files(sequences, monomers, raw_file, scoring=(ins, dels, mm, match),
@@ -471,6 +473,25 @@ def _device_list(args):
     return devs
 
 
+def _check_profile(args):
+    """--profile requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
+    if shard.world()[2] > 1:
+        sys.stderr.write("stringdecomposer: --profile cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)\n"
+                         % shard.world()[2])
+        sys.exit(2)
+    try:
+        names = lib.fasta_load(args.monomers)[0]
+    except lib.SdError:
+        return   # the job itself reports an unreadable monomer file
+    seen = set()
+    for n in names + [x + "'" for x in names]:
+        if n in seen:
+            sys.stderr.write("stringdecomposer: --profile: monomer name %s is not unique: a profile needs one template "
+                             "per name\n" % n)
+            sys.exit(lib.SD_ERR_PARAM)
+        seen.add(n)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Decomposes string into blocks alphabet")
     parser.add_argument("sequences", help="fasta-file with long reads or genomic sequences")
@@ -509,7 +530,12 @@ def main(argv=None):
     parser.add_argument("--records", action="store_true",
                         help="also write <out-file>_raw.sdr: the rows of the raw tsv as a binary record stream "
                              "(stringdecomposer_amd.formats.read_records)")
+    parser.add_argument("--profile", action="store_true",
+                        help="also write <out-file>_profile.tsv (per-monomer column profiles of the rows of <out-file>.tsv) "
+                             "and <out-file>_consensus.fa (their consensus sequences)")
     args = parser.parse_args(argv)
+    if args.profile:
+        _check_profile(args)
     devices = _device_list(args)
     pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
 
@@ -532,7 +558,8 @@ def main(argv=None):
                                 ref_compat=args.ref_compat, device=args.device, kernel=kernel,
                                 final_file=convert_tsv_fn, min_identity=int(args.min_identity),
                                 second_best=args.second_best,
-                                records_file=records_fn if shard.world()[2] == 1 else None, devices=devices)
+                                records_file=records_fn if shard.world()[2] == 1 else None, devices=devices,
+                                profile=args.profile)
     except lib.SdError as e:
         # the reference dies with CalledProcessError after the binary printed its message on stderr
         sys.stderr.write(e.msg + "\n")
@@ -565,6 +592,15 @@ def main(argv=None):
             logger.info("Transformation failed (%s); the raw decomposition is in %s" % (e.msg, raw_decomp_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
     logger.info("Transformation finished. Results can be found in " + convert_tsv_fn)
+    if args.profile:
+        from . import formats
+        prof = lib.last_run_profile(numpy=False)
+        prof_fn = os.path.join(args.out_dir, args.out_file + "_profile.tsv")
+        cons_fn = os.path.join(args.out_dir, args.out_file + "_consensus.fa")
+        formats.write_profile(prof_fn, prof)
+        formats.write_consensus(cons_fn, prof)
+        logger.info("Saved the monomer column profiles to " + prof_fn)
+        logger.info("Saved the monomer consensus sequences to " + cons_fn)
 
     logger.info("Thank you for using StringDecomposer!")
 
