@@ -451,9 +451,10 @@ int sd_stream_profile(sd_stream* s, int32_t reset, int32_t* n_monomers, int64_t*
  * work unchanged, jobs are collected in FIFO order, and stats sum over the entries.  sd_stream_submit of a raw-mode
  * stream returns once every batch of the job has been packed by its entry (the read buffers are then free, as with one
  * device: no copy, but submit waits for the entries to have room for the job); a final-mode stream copies the reads
- * and returns at once.  The fallback identities run on devices[0].  The first failure of any entry fails the stream as
- * on one device -- the batches in flight on every entry are drained and the jobs dropped -- with the message prefixed
- * "device N: ", reported by the next submit or collect.  sd_stream_destroy joins every thread. */
+ * and returns at once.  The fallback identities run on devices[0].  The first push or pop failure of any stream, on one
+ * entry or several, fails it: the batches in flight on every entry are drained, every outstanding job is dropped, and
+ * the submit or collect that meets the failure reports it (with several entries the message is prefixed "device N: ").
+ * sd_stream_destroy joins every thread. */
 int sd_stream_create_devices(sd_stream** out, const sd_params* p, const int32_t* devices, int32_t n_devices,
                              const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono, int32_t sub_batches,
                              char* errbuf, size_t errlen);

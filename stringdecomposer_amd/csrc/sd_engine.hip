@@ -1218,8 +1218,8 @@ static int run_chunk_batches(const std::vector<ReadView>& reads, const std::vect
         std::fprintf(stderr, "[sd timing] host work under the device: %.2f ms\n", t_busy * 1e3);
     if (timing)
         std::fprintf(stderr, "[sd timing] %zu batches: pack+enqueue %.1f ms, wait %.1f ms, sink %.1f ms, kernels fill %.1f "
-                     "trace %.1f compact %.2f ms, total %.1f ms\n", batches.size(), pipe.pack_s * 1e3, pipe.wait_s * 1e3,
-                     pipe.sink_s * 1e3, pipe.fill_ms, pipe.trace_ms, pipe.compact_ms, (now_s() - t_begin) * 1e3);
+                     "trace %.1f compact %.2f ms, total %.1f ms\n", batches.size(), pipe.cnt.pack_s * 1e3, pipe.cnt.wait_s * 1e3,
+                     pipe.cnt.sink_s * 1e3, pipe.cnt.fill_ms, pipe.cnt.trace_ms, pipe.cnt.compact_ms, (now_s() - t_begin) * 1e3);
     if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkey, std::move(pipe_h));
     return rc;
 }

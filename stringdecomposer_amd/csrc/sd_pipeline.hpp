@@ -396,6 +396,22 @@ void engine_grow_ident(sd_engine* e, int64_t total);
 using RecSink = std::function<void(const sd_rec*, const int64_t*, size_t, size_t)>;
 namespace sdi {
 
+// What a pipeline accumulates over its batches: HIP-event kernel times (ms), host stage times (s) and counts.  The
+// callers that drive several pipelines sum them with +=.
+struct PipeCounters {
+    double fill_ms = 0, trace_ms = 0, compact_ms = 0, run_ms = 0, ident_ms = 0;
+    double pack_s = 0, wait_s = 0, sink_s = 0;
+    int64_t ident_pairs = 0, launches = 0, batches = 0, rows = 0;
+    int64_t homo_pairs = 0, homo_full_pairs = 0;   // homopolymer-compressed pairs of the job / those aligned in full (pruned pass)
+    PipeCounters& operator+=(const PipeCounters& o) {
+        fill_ms += o.fill_ms; trace_ms += o.trace_ms; compact_ms += o.compact_ms; run_ms += o.run_ms; ident_ms += o.ident_ms;
+        pack_s += o.pack_s; wait_s += o.wait_s; sink_s += o.sink_s;
+        ident_pairs += o.ident_pairs; launches += o.launches; batches += o.batches; rows += o.rows;
+        homo_pairs += o.homo_pairs; homo_full_pairs += o.homo_full_pairs;
+        return *this;
+    }
+};
+
 struct Pipeline {
     static constexpr int NSMAX = 3;
     // Batches in flight.  Three since round 5: with two, the engine of batch b is busy until b's traceback -- which shares
@@ -436,12 +452,7 @@ struct Pipeline {
     }
     uint64_t pushed = 0, popped = 0;
     char eb[1024] = {0};
-    // accumulated over all batches: HIP-event kernel times (ms) and host stage times (s)
-    double fill_ms = 0, trace_ms = 0, compact_ms = 0, run_ms = 0, ident_ms = 0;
-    int64_t ident_pairs = 0;
-    int64_t homo_pairs = 0, homo_full_pairs = 0;   // homopolymer-compressed pairs of the job / those aligned in full (pruned pass)
-    double pack_s = 0, wait_s = 0, sink_s = 0;
-    int64_t launches = 0, batches = 0, rows = 0;
+    PipeCounters cnt;   // accumulated over all batches
 
     const bool timeline = getenv("SD_TIMELINE") != nullptr;   // developer knob, see pop_fetch
     hipEvent_t tl_ref = nullptr;
@@ -454,11 +465,7 @@ struct Pipeline {
         for (sd_engine* e : eng) if (e) e->p.threads = pp->threads;
         mseq.assign(mono_seqs, mono_seqs + n_mono);
         mlen.assign(mono_lens, mono_lens + n_mono);
-        fill_ms = trace_ms = compact_ms = run_ms = ident_ms = 0;
-        ident_pairs = 0;
-        homo_pairs = homo_full_pairs = 0;
-        pack_s = wait_s = sink_s = 0;
-        launches = batches = rows = 0;
+        cnt = PipeCounters{};
         eb[0] = 0;
     }
     int create(const sd_params* pp, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono) {
@@ -570,7 +577,7 @@ struct Pipeline {
         eng[k]->lds_gate = fill_st2 != nullptr;
         eng[k]->slice_end = slice_end;
         if (rc == SD_OK) rc = engine_run2(eng[k], fs, trace_st ? trace_st : fs, eb, sizeof eb);
-        pack_s += now_s() - t0;
+        cnt.pack_s += now_s() - t0;
         tl_push1[k] = now_s();
         if (rc) return rc;
         sinks[k] = std::move(sink);
@@ -609,12 +616,12 @@ struct Pipeline {
             }
             if (rc == SD_OK) rc = fetch_range(e, 0, total, e->h_ident, e->h_identh, eb, sizeof eb);
         }
-        wait_s += now_s() - t0;
+        cnt.wait_s += now_s() - t0;
         ++popped;
         if (rc) { sinks[k] = nullptr; return rc; }
-        launches += e->fill_launches;
-        ++batches;
-        rows += e->rows;
+        cnt.launches += e->fill_launches;
+        ++cnt.batches;
+        cnt.rows += e->rows;
         if (sliced) {
             RecSink fn = std::move(sinks[k]);
             sinks[k] = nullptr;
@@ -646,7 +653,7 @@ struct Pipeline {
                 uint32_t* idhp = own_idh ? static_cast<uint32_t*>(own_idh.get()) + (size_t)r_lo * per : nullptr;
                 if (hipEventSynchronize(e->ev_slice[sl]) != hipSuccess) { std::snprintf(eb, sizeof eb, "device run failed"); rc = SD_ERR_HIP; }
                 if (rc == SD_OK) rc = fetch_range(e, r_lo, r_hi, idp, idhp, eb, sizeof eb);
-                wait_s += now_s() - t0;
+                cnt.wait_s += now_s() - t0;
                 if (rc == SD_OK) {
                     t0 = now_s();
                     ro.resize((size_t)(c_hi - c_lo) + 1);
@@ -659,14 +666,14 @@ struct Pipeline {
                     }
                     if (fn) fn(e->h_recs.p + r_lo, ro.data(), (size_t)c_lo, (size_t)(c_hi - c_lo));
                     cur_ident = IdentOut{};
-                    sink_s += now_s() - t0;
+                    cnt.sink_s += now_s() - t0;
                 }
                 c_lo = c_hi;
             }
             (void)hipEventSynchronize(e->ev_run1);
         }
         float ms[4];
-        if (sd_engine_timings(e, ms) == SD_OK) { fill_ms += ms[0]; trace_ms += ms[1]; compact_ms += ms[2]; run_ms += ms[3]; }
+        if (sd_engine_timings(e, ms) == SD_OK) { cnt.fill_ms += ms[0]; cnt.trace_ms += ms[1]; cnt.compact_ms += ms[2]; cnt.run_ms += ms[3]; }
         if (timeline && tl_ref && e->family == 2 && !e->chunks.empty()) {
             // developer knob SD_TIMELINE=1: where each kernel of the batch began and ended on the DEVICE clock (ms since the
             // pipeline's reference event) next to the host's clock for its enqueue and fetch -- shows whether the device waited
@@ -682,14 +689,14 @@ struct Pipeline {
         }
         if (e->ident_mode && !e->chunks.empty()) {
             float im = 0.f;
-            if (hipEventElapsedTime(&im, e->ev_id0, e->ev_id1) == hipSuccess) ident_ms += im;
-            if (e->ident_valid) ident_pairs += total * (e->ident_mode == 2 ? 2 * (int64_t)e->iT : 1);
+            if (hipEventElapsedTime(&im, e->ev_id0, e->ev_id1) == hipSuccess) cnt.ident_ms += im;
+            if (e->ident_valid) cnt.ident_pairs += total * (e->ident_mode == 2 ? 2 * (int64_t)e->iT : 1);
             // pruned homopolymer pass: the pairs that were aligned in full (one counter per identity slice)
             if (e->ident_valid && e->ident_mode == 2 && e->ia_homo.cand_list && e->d_icandcnt.p) {
-                int cnt[64];
-                if (hipMemcpy(cnt, e->d_icandcnt.p, sizeof cnt, hipMemcpyDeviceToHost) == hipSuccess)
-                    for (size_t sl = 0; sl < std::max<size_t>(1, e->sliced_run ? e->slice_end.size() : 1) && sl < 64; ++sl) homo_full_pairs += cnt[sl];
-                homo_pairs += total * (int64_t)e->iT;
+                int nc[64];
+                if (hipMemcpy(nc, e->d_icandcnt.p, sizeof nc, hipMemcpyDeviceToHost) == hipSuccess)
+                    for (size_t sl = 0; sl < std::max<size_t>(1, e->sliced_run ? e->slice_end.size() : 1) && sl < 64; ++sl) cnt.homo_full_pairs += nc[sl];
+                cnt.homo_pairs += total * (int64_t)e->iT;
             }
         }
         if (sliced) return rc;
@@ -720,7 +727,7 @@ struct Pipeline {
         sink_fn = nullptr;
         cur_ident = IdentOut{};
         cur_engine = nullptr;
-        sink_s += now_s() - t0;
+        cnt.sink_s += now_s() - t0;
     }
     int drain() {
         int rc = SD_OK;

@@ -479,11 +479,11 @@ static void plan_job(const RowJob& job, const std::vector<int64_t>& entry_budget
 // sd_last_run_device_stats, and with SD_TIMING on stderr.
 static void report_stats(const std::vector<std::unique_ptr<Pipeline>>& pipes, const std::vector<int64_t>& dealt,
                          const TextStages& text, const sd::PostProcessor& pp, size_t n_batches, double t_setup) {
-    auto total = [&](double (*f)(const Pipeline&)) { double t = 0; for (const auto& q : pipes) t += f(*q); return t; };
-    const double s_pack = total([](const Pipeline& q) { return q.pack_s; }), s_wait = total([](const Pipeline& q) { return q.wait_s; });
+    PipeCounters t;
+    for (const auto& q : pipes) t += q->cnt;
     if (text.timing)
         std::fprintf(stderr, "[sd timing] %zu batches: pack+enqueue %.1f ms, wait %.1f ms, raw text %.1f ms, post-processing %.1f ms, "
-                     "file writes %.1f ms, total %.1f ms\n", n_batches, s_pack * 1e3, s_wait * 1e3, text.t_fmt * 1e3,
+                     "file writes %.1f ms, total %.1f ms\n", n_batches, t.pack_s * 1e3, t.wait_s * 1e3, text.t_fmt * 1e3,
                      text.t_post * 1e3, text.t_io * 1e3, (now_s() - text.t_begin) * 1e3);
     if (text.timing)
         std::fprintf(stderr, "[sd timing] of which device / pinned allocations (hipMalloc, hipHostMalloc): %.1f ms\n", (double)g_alloc_ns.load() / 1e6);
@@ -492,17 +492,14 @@ static void report_stats(const std::vector<std::unique_ptr<Pipeline>>& pipes, co
                      pp.t_prepare * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, pp.t_concat * 1e3);
     {
         std::lock_guard<std::mutex> lk(g_last_m);
-        const double v[24] = {total([](const Pipeline& q) { return q.fill_ms; }), total([](const Pipeline& q) { return q.trace_ms; }),
-                              total([](const Pipeline& q) { return q.compact_ms; }), total([](const Pipeline& q) { return q.ident_ms; }),
-                              total([](const Pipeline& q) { return (double)q.ident_pairs; }), total([](const Pipeline& q) { return (double)q.batches; }),
-                              total([](const Pipeline& q) { return (double)q.rows; }), s_pack * 1e3, s_wait * 1e3, text.t_fmt * 1e3,
+        const double v[24] = {t.fill_ms, t.trace_ms, t.compact_ms, t.ident_ms, (double)t.ident_pairs, (double)t.batches,
+                              (double)t.rows, t.pack_s * 1e3, t.wait_s * 1e3, text.t_fmt * 1e3,
                               text.t_post * 1e3, text.t_io * 1e3, pp.t_identity * 1e3, pp.t_format * 1e3, (now_s() - text.t_begin) * 1e3,
-                              (double)g_alloc_ns.load() / 1e6, t_setup * 1e3, total([](const Pipeline& q) { return q.sink_s; }) * 1e3,
-                              total([](const Pipeline& q) { return (double)q.homo_pairs; }),
-                              total([](const Pipeline& q) { return (double)q.homo_full_pairs; }), 0, 0, 0, 0};
+                              (double)g_alloc_ns.load() / 1e6, t_setup * 1e3, t.sink_s * 1e3, (double)t.homo_pairs,
+                              (double)t.homo_full_pairs, 0, 0, 0, 0};
         std::memcpy(g_last_run, v, sizeof v);
         g_last_ndev = std::min((int)pipes.size(), kMaxDevices);
-        for (int i = 0; i < g_last_ndev; ++i) { g_last_dev_batches[i] = dealt[(size_t)i]; g_last_dev_busy[i] = pipes[(size_t)i]->run_ms; }
+        for (int i = 0; i < g_last_ndev; ++i) { g_last_dev_batches[i] = dealt[(size_t)i]; g_last_dev_busy[i] = pipes[(size_t)i]->cnt.run_ms; }
     }
     if (text.timing) {
         double nw[4];
