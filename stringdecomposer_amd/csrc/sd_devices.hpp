@@ -1,7 +1,7 @@
-// sd_devices.hpp -- internal to libsd_hip.so: what a job on several devices of one process is made of, shared by
-// sd_run_files.hip (sd_run_files_devices) and sd_stream.hip (sd_stream_create_devices): the device-list check, the
-// batch plan of several pipelines and the budget rule of entries that share a device, the batch-ordered hand-over of
-// their records (BatchTurns), and the per-entry drivers (on_entries, drive_entry).
+// sd_devices.hpp -- internal to libsd_hip.so: what a job on one or several devices of one process is made of, shared by
+// sd_run_files.hip (sd_run_files*), sd_engine.hip (the raw calls) and sd_stream.hip (the streams): the device-list check,
+// the batch plan of several pipelines and the budget rule of entries that share a device, the batch-ordered hand-over of
+// their records (BatchTurns), the per-entry drivers (on_entries, drive_entry) and the owner of a job's pipelines (JobPipes).
 #pragma once
 
 #include "sd_pipeline.hpp"
@@ -91,15 +91,17 @@ struct BatchTurns {
     }
 };
 
-// The driver of one device entry of a job (every job, one entry or several): push(b) deals batch b to the entry's pipeline (whose sinks take their turns
-// in `turns`) until the batches run out, the job has failed somewhere (turns aborted, the writer failed) or this pipeline
-// fails; then the pipeline is drained.  A pop that fails drops its batch before the batch's last slice reaches the
-// assembler, so every batch behind it -- in this pipeline and in the others -- would wait for that turn forever: the
-// turns are aborted at once, and the rest is drained with sinks that return at once.  (Pipe: Pipeline, or the host-only
-// model of sd_multi_device_selftest.)  Returns the first error of this entry; dealt counts the batches it took.
-template <class Pipe, class Push>
+// The driver of one device entry of a job (every job that runs to its end, one entry or several; not the streams):
+// push(b) deals batch b to the entry's pipeline (whose sinks take their turns in `turns`) until the batches run out, the
+// job has failed somewhere (turns aborted, a sink failed: sink_rc) or this pipeline fails; then busy() runs -- once, while
+// the device works on what was dealt, unless a push failed -- and the pipeline is drained.  A pop that fails drops its
+// batch before the batch's last slice reaches the assembler, so every batch behind it -- in this pipeline and in the
+// others -- would wait for that turn forever: the turns are aborted at once, and the rest is drained with sinks that
+// return at once.  (Pipe: Pipeline, or the host-only model of sd_multi_device_selftest.)  Returns the first error of
+// this entry; dealt counts the batches it took.
+template <class Pipe, class Push, class Busy>
 int drive_entry(Pipe& pq, BatchTurns& turns, std::atomic<size_t>& next_batch, size_t n_batches,
-                       const std::atomic<int>& sink_rc, Push&& push, int64_t& dealt) {
+                const std::atomic<int>& sink_rc, Push&& push, int64_t& dealt, Busy&& busy) {
     int r = SD_OK;
     while (r == SD_OK && sink_rc.load() == SD_OK && !turns.is_aborted()) {
         const size_t b = next_batch.fetch_add(1);
@@ -108,6 +110,7 @@ int drive_entry(Pipe& pq, BatchTurns& turns, std::atomic<size_t>& next_batch, si
         if (r == SD_OK) ++dealt;
         else turns.abort();   // (this batch, or the one a full pipeline popped for it, never reaches its sink)
     }
+    if (r == SD_OK) busy();
     while (pq.inflight() > 0) {
         const int e = pq.pop();
         if (e) {
@@ -188,5 +191,90 @@ int on_entries(const std::vector<int32_t>& devs, std::vector<std::string>& msg, 
         }
     return SD_OK;
 }
+
+// The pipelines of a job that runs to its end, one per device entry: sd_run_files* ('1', or '2' with --second-best) and
+// the raw calls of sd_engine.hip ('C', the one entry {p->device}).  This is the only place that takes pipelines from the
+// cache and gives them back.  The cache key of an entry is the job's kind, parameters (with the entry's device) and
+// monomers, and beyond the first entry its index.
+struct JobPipes {
+    const std::vector<int32_t> devs;
+    std::vector<std::unique_ptr<Pipeline>> pipes;   // after open: one per entry (empty if its device could not be opened)
+    std::vector<std::string> keys, msg;             // per entry: cache key, message of its first error
+    std::vector<int64_t> budget, dealt;             // per entry: rows per batch (row_budget), batches it took
+    std::vector<char> cached;                       // per entry: the pipeline came from the cache
+
+    explicit JobPipes(const std::vector<int32_t>& d)
+        : devs(d), pipes(d.size()), keys(d.size()), msg(d.size()), budget(d.size(), 0), dealt(d.size(), 0), cached(d.size(), 0) {}
+    bool reused() const { return std::count(cached.begin(), cached.end(), 1) == (std::ptrdiff_t)cached.size(); }
+
+    // Every entry's pipeline, from the cache or new, on the entry's thread (on_entries); on_engine (may be empty) is
+    // called for every engine the pipelines create.  Returns the first error, its message in err.
+    int open(const sd_params* p, char kind, const TemplateSet& ts, const std::function<void(sd_engine*)>& on_engine, std::string& err) {
+        const int rc = on_entries(devs, msg, err, [&](int i) -> int {
+            sd_params pi = *p, pe = *p;
+            pi.device = pe.device = devs[(size_t)i];
+            apply_env_overrides(pe);   // (host threads do not shape an engine; pipe_cache_key leaves them out)
+            keys[(size_t)i] = pipe_cache_key(pe, kind, ts.mseq, ts.mlen) + (i > 0 ? "#entry " + std::to_string(i) : std::string());
+            std::unique_ptr<Pipeline>& h = pipes[(size_t)i];
+            if (!getenv("SD_PIPE_CACHE_OFF")) h = pipe_cache_take(keys[(size_t)i]);
+            cached[(size_t)i] = h != nullptr;
+            if (!h) h.reset(new Pipeline);
+            h->restart_idle = true;
+            h->on_engine = on_engine;
+            if (cached[(size_t)i]) h->begin_job(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
+            else if (const int r = h->create(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size())) {
+                msg[(size_t)i] = h->eb;
+                return r;
+            }
+            budget[(size_t)i] = h->row_budget();   // (hipMemGetInfo of the entry's device)
+            return SD_OK;
+        }, [] {});
+        for (std::unique_ptr<Pipeline>& h : pipes)
+            if (!h) h.reset(new Pipeline);   // (an entry whose device could not be selected)
+        return rc;
+    }
+
+    // Deals the batches -- the chunks [c0, c1) of `table`, their identities cut into slices by slices(c0, c1, slice_end)
+    // -- to the entries' pipelines and drains them (drive_entry on every entry, through on_entries); every slice of
+    // records goes to sink(pq, c0', c1', recs, rec_off) in batch order (BatchTurns).  busy() runs in entry 0's driver,
+    // i.e. on the calling thread of a one-entry job.  Returns the first error, its message in err.
+    template <class Reads, class Slices, class Sink, class Busy>
+    int drive(const Reads& reads, const std::vector<CRef>& table, const std::vector<std::pair<size_t, size_t>>& batches,
+              const std::atomic<int>& sink_rc, Slices&& slices, Sink&& sink, Busy&& busy, std::string& err) {
+        BatchTurns turns;
+        std::atomic<size_t> next_batch{0};
+        return on_entries(devs, msg, err, [&](int i) {
+            Pipeline& pq = *pipes[(size_t)i];
+            std::string& m = msg[(size_t)i];
+            std::vector<const char*> cptr;
+            std::vector<int32_t> clen;
+            std::vector<int> slice_end;
+            const int r = drive_entry(pq, turns, next_batch, batches.size(), sink_rc, [&](size_t b) {
+                const size_t c0 = batches[b].first, c1 = batches[b].second;
+                batch_chunks(reads, table, c0, c1, cptr, clen);
+                slice_end.clear();
+                slices(c0, c1, slice_end);
+                const int rp = pq.push(cptr, clen, [&turns, &pq, &sink, b, c0, c1](const sd_rec* rr, const int64_t* ro, size_t first, size_t n) {
+                    if (turns.wait(b)) sink(pq, c0 + first, c0 + first + n, rr, ro);
+                    if (c0 + first + n == c1) turns.done(b);
+                }, slice_end);
+                if (rp) m = pq.eb;   // (what failed first, not a pop while the pipeline drains)
+                return rp;
+            }, dealt[(size_t)i], [&] { if (i == 0) busy(); });
+            if (r && m.empty()) m = pq.eb;
+            return r;
+        }, [&turns] { turns.abort(); });
+    }
+
+    // The pipelines of a job that succeeded go back to the cache (unless SD_PIPE_CACHE_OFF); on_engine, which refers to
+    // the caller's locals, is cleared in any case.
+    void give_back(bool ok) {
+        const bool keep = ok && !getenv("SD_PIPE_CACHE_OFF");
+        for (size_t i = 0; i < pipes.size(); ++i) {
+            pipes[i]->on_engine = nullptr;
+            if (keep) pipe_cache_give(keys[i], std::move(pipes[i]), (int)i);
+        }
+    }
+};
 
 }  // namespace sdi

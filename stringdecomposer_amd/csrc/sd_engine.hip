@@ -33,7 +33,7 @@
 #include "sd_records.hpp"
 #include "sd_seam.hpp"
 #include "sd_engine_int.hpp"
-#include "sd_pipeline.hpp"
+#include "sd_devices.hpp"
 
 namespace sdi {
 DevPool g_pool;
@@ -1091,7 +1091,7 @@ int sd_engine_info(sd_engine* e, int64_t info[8]) {
 }
 
 
-// Pipelines of finished jobs (sd_run_files, the chunk-range calls), kept for the next job with the same parameters and monomer set: creating
+// Pipelines of finished jobs (sd_run_files*, the raw calls; taken and given back by JobPipes only), kept for the next job with the same parameters and monomer set: creating
 // the engines (layout plan, tables, identity masks, streams, events, pinned staging) is 25-40 ms per call, a quarter of
 // a C4 --second-best job.  A process that decomposes many read sets against one monomer set (a service behind the
 // C-ABI, bench.py's steps) pays it once; sd_release_cache() drops them.  At most two are kept per device entry (the
@@ -1155,75 +1155,105 @@ void pipe_cache_clear() {
 }
 }  // extern "C++"
 
-// Runs the chunks [c_lo, c_hi) of `table` through the device in batches of consecutive chunks sized to
-// the free HBM, so a single 200-Mb sequence and a million reads take the same path; the records of
-// every batch go to `sink(c0, c1, recs, rec_off)` in table order (chunk-local coordinates, rec_off
-// relative to the batch).
-using BatchSink = std::function<void(size_t, size_t, const sd_rec*, const int64_t*)>;
-// `while_busy` (may be empty) runs on the calling thread once the last batch is enqueued, i.e. while the device
-// works: the chunk-range calls check their share's alphabet there instead of before the first upload (a bad symbol
-// still fails the call -- the records of the run are dropped -- it just no longer delays the device by the 0.2 ms the
-// check of 27 Mb takes; the packer maps any byte to a 2-bit code, so the kernels run on whatever the bytes are).
-static int run_chunk_batches(const std::vector<ReadView>& reads, const std::vector<CRef>& table, size_t c_lo,
-                             size_t c_hi, const TemplateSet& ts, const sd_params* p, std::string& err,
-                             const BatchSink& sink, const std::function<int(std::string&)>& while_busy = nullptr) {
-    const bool timing = getenv("SD_TIMING") != nullptr;  // developer knob: stage times on stderr
-    const double t_begin = now_s();
-    std::string pkey;
-    {
-        sd_params pe = *p;
-        apply_env_overrides(pe);
-        pkey = pipe_cache_key(pe, 'C', ts.mseq, ts.mlen);
+namespace {
+// Records of a chunk range as the C-ABI hands them out (malloc'ed records + offsets), filled batch by batch straight
+// from the pipeline's pinned buffers: one copy per record (a std::vector + a final copy cost 6 ms per 200-Mb job).
+struct RangeCollector {
+    sd_rec* recs = nullptr;
+    int64_t* off = nullptr;
+    size_t cap = 0, n = 0, c_lo, n_chunks;
+    bool failed = false;
+    RangeCollector(size_t chunks, size_t first) : c_lo(first), n_chunks(chunks) {
+        off = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * (chunks + 1)));
+        cap = std::max<size_t>(4096, chunks * 40);   // ~32 records per 5.5-kb chunk of satellite DNA
+        recs = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec) * cap));
+        if (!off || !recs) failed = true; else off[0] = 0;
     }
-    std::unique_ptr<Pipeline> pipe_h = getenv("SD_PIPE_CACHE_OFF") ? nullptr : pipe_cache_take(pkey);
-    int rc = SD_OK;
-    const bool from_cache = pipe_h != nullptr;
-    if (pipe_h) {
-        pipe_h->begin_job(p, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-    } else {
-        pipe_h.reset(new Pipeline);
-        rc = pipe_h->create(p, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-    }
-    Pipeline& pipe = *pipe_h;
-    if (rc) { err = pipe.eb; return rc; }
-    pipe.restart_idle = true;
-    std::vector<std::pair<size_t, size_t>> batches;
-    {
-        int64_t budget = pipe.row_budget();
-        if (!from_cache) {
-            int64_t rows = 0;
-            for (size_t c = c_lo; c < c_hi; ++c) rows += table[c].len;
-            if (rows > budget) budget = fresh_row_budget(budget, rows);   // (a job of one batch stays one batch)
+    void add(size_t c0, size_t c1, const sd_rec* r, const int64_t* ro, int threads) {
+        if (failed) return;
+        const size_t k = (size_t)ro[c1 - c0];
+        if (n + k > cap) {
+            cap = std::max(n + k, cap + cap / 2);
+            sd_rec* q = static_cast<sd_rec*>(std::realloc(recs, sizeof(sd_rec) * cap));
+            if (!q) { failed = true; return; }
+            recs = q;
         }
-        plan_batches(table, c_lo, c_hi, budget, 1, batches);
+        const size_t pieces = (k + 65535) / 65536;
+        sd::parallel_for((int64_t)pieces, threads, 1, [&](int64_t x) {
+            const size_t a = (size_t)x * 65536, b = std::min(k, a + 65536);
+            std::memcpy(recs + n + a, r + a, sizeof(sd_rec) * (b - a));
+        });
+        for (size_t c = 1; c <= c1 - c0; ++c) off[c0 - c_lo + c] = (int64_t)n + ro[c];
+        n += k;
     }
-    std::vector<const char*> cptr;
-    std::vector<int32_t> clen;
-    for (size_t b = 0; b < batches.size() && rc == SD_OK; ++b) {
-        const size_t c0 = batches[b].first, c1 = batches[b].second;
-        batch_chunks(reads, table, c0, c1, cptr, clen);
-        rc = pipe.push(cptr, clen, [&sink, c0](const sd_rec* r, const int64_t* ro, size_t first, size_t n) { sink(c0 + first, c0 + first + n, r, ro); });
-    }
-    std::string busy_err;
-    const double t_busy0 = now_s();
-    const int busy_rc = (rc == SD_OK && while_busy) ? while_busy(busy_err) : SD_OK;
-    const double t_busy = now_s() - t_busy0;
-    const int rc2 = pipe.drain();
-    if (rc == SD_OK) rc = rc2;
-    if (rc) err = pipe.eb;
-    // an undefined symbol in the share is the reference's own diagnostic (main.cpp:335): it is what the caller sees, also
-    // when the device run over those bytes failed as well
-    if (busy_rc) { rc = busy_rc; err = busy_err; }
-    if (timing)
-        std::fprintf(stderr, "[sd timing] host work under the device: %.2f ms\n", t_busy * 1e3);
-    if (timing)
-        std::fprintf(stderr, "[sd timing] %zu batches: pack+enqueue %.1f ms, wait %.1f ms, sink %.1f ms, kernels fill %.1f "
-                     "trace %.1f compact %.2f ms, total %.1f ms\n", batches.size(), pipe.cnt.pack_s * 1e3, pipe.cnt.wait_s * 1e3,
-                     pipe.cnt.sink_s * 1e3, pipe.cnt.fill_ms, pipe.cnt.trace_ms, pipe.cnt.compact_ms, (now_s() - t_begin) * 1e3);
-    if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkey, std::move(pipe_h));
-    return rc;
-}
+    void release(sd_rec** r, int64_t** o) { *r = recs; *o = off; recs = nullptr; off = nullptr; }
+    ~RangeCollector() { std::free(recs); std::free(off); }
+};
 
+// The raw calls' job (sd_decompose*, the chunk-range calls): the reads' chunk table against a template set.  run() takes
+// the chunks [lo, hi) through the device in batches of consecutive chunks sized to the free HBM, so a single 200-Mb
+// sequence and a million reads take the same path, on one pipeline of its own kind ('C': JobPipes with the one entry
+// {p->device}, driven on the calling thread); the records of every batch go to `sink(c0, c1, recs, rec_off)` in table
+// order (chunk-local coordinates, rec_off relative to the batch), and a sink that returns false stops the dealing.
+// `check` (may be empty) runs on the calling thread once the last batch is enqueued, i.e. while the device works
+// (drive_entry's busy): the chunk-range calls check their share's alphabet there instead of before the first upload (a
+// bad symbol still fails the call -- the records of the run are dropped -- it just no longer delays the device by the
+// 0.2 ms the check of 27 Mb takes; the packer maps any byte to a 2-bit code, so the kernels run on whatever the bytes are).
+using BatchSink = std::function<bool(size_t, size_t, const sd_rec*, const int64_t*)>;
+using BusyCheck = std::function<int(std::string&)>;
+struct RawJob {
+    const std::vector<ReadView>& reads;
+    const sd_params* p;
+    TemplateSet ts;
+    std::vector<CRef> table;
+    std::vector<int32_t> nch;
+    RawJob(const std::vector<ReadView>& r, const std::vector<sd::Seq>& monos, const sd_params* pp) : reads(r), p(pp), ts(monos) {
+        build_chunk_table(reads, p, table, nch);
+    }
+    int run(size_t lo, size_t hi, const BatchSink& sink, const BusyCheck& check, std::string& err) {
+        const bool timing = getenv("SD_TIMING") != nullptr;  // developer knob: stage times on stderr
+        const double t_begin = now_s();
+        JobPipes jp({p->device});
+        int rc = jp.open(p, 'C', ts, nullptr, err);
+        if (rc) return rc;
+        int64_t rows = 0;
+        for (size_t c = lo; c < hi; ++c) rows += table[c].len;
+        const int64_t budget = jp.budget[0];   // (a new pipeline: fresh_row_budget; a job of one batch stays one batch)
+        std::vector<std::pair<size_t, size_t>> batches;
+        plan_batches(table, lo, hi, jp.reused() || rows <= budget ? budget : fresh_row_budget(budget, rows), 1, batches);
+        std::atomic<int> sink_rc{SD_OK};
+        int busy_rc = SD_OK;
+        std::string busy_err;
+        double t_busy = 0;
+        rc = jp.drive(reads, table, batches, sink_rc, [](size_t, size_t, std::vector<int>&) {},
+                      [&](Pipeline&, size_t c0, size_t c1, const sd_rec* r, const int64_t* ro) { if (!sink(c0, c1, r, ro)) sink_rc = SD_ERR_IO; },
+                      [&] { t_busy = now_s(); if (check) busy_rc = check(busy_err); t_busy = now_s() - t_busy; }, err);
+        // an undefined symbol in the share is the reference's own diagnostic (main.cpp:335): it is what the caller sees,
+        // also when the device run over those bytes failed as well
+        if (busy_rc) { rc = busy_rc; err = busy_err; }
+        const PipeCounters& t = jp.pipes[0]->cnt;
+        if (timing) {
+            std::fprintf(stderr, "[sd timing] host work under the device: %.2f ms\n", t_busy * 1e3);
+            std::fprintf(stderr, "[sd timing] %zu batches: pack+enqueue %.1f ms, wait %.1f ms, sink %.1f ms, kernels fill %.1f "
+                         "trace %.1f compact %.2f ms, total %.1f ms\n", batches.size(), t.pack_s * 1e3, t.wait_s * 1e3,
+                         t.sink_s * 1e3, t.fill_ms, t.trace_ms, t.compact_ms, (now_s() - t_begin) * 1e3);
+        }
+        jp.give_back(rc == SD_OK);
+        return rc;
+    }
+    // The chunk-range calls: the records of [lo, hi) as the C-ABI hands them out (*recs / *rec_off, set on success only).
+    int collect(size_t lo, size_t hi, const BusyCheck& check, sd_rec** recs, int64_t** rec_off, std::string& err) {
+        RangeCollector col(hi - lo, lo);
+        int rc = run(lo, hi, [&](size_t c0, size_t c1, const sd_rec* r, const int64_t* ro) {
+            col.add(c0, c1, r, ro, p->threads);
+            return !col.failed;
+        }, check, err);
+        if (rc == SD_OK && col.failed) { rc = SD_ERR_INTERNAL; err = "out of host memory"; }
+        if (rc == SD_OK) col.release(recs, rec_off);
+        return rc;
+    }
+};
+}  // namespace
 
 static int decompose_impl(const std::vector<ReadView>& reads, const std::vector<sd::Seq>& monos,
                           const sd_params* p, std::string& tsv, std::string& err, const char* records_out = nullptr,
@@ -1232,24 +1262,21 @@ static int decompose_impl(const std::vector<ReadView>& reads, const std::vector<
     if (monos.empty()) { err = "no monomers"; return SD_ERR_PARAM; }
     for (const ReadView& r : reads)
         if (r.len <= 0) { err = "ERROR: Sequence " + std::string(r.name, r.name_len) + " is empty"; return SD_ERR_EMPTY; }
-    TemplateSet ts(monos);
-    std::vector<CRef> table;
-    std::vector<int32_t> nch;
-    build_chunk_table(reads, p, table, nch);
-    ReadAssembler as(reads, table, nch, ts.tnames, p->threads, tsv);
+    RawJob job(reads, monos, p);
+    ReadAssembler as(reads, job.table, job.nch, job.ts.tnames, p->threads, tsv);
     as.part_sink = parts_out;
     sd::RecordsWriter rw;
     if (records_out) {
-        const int orc = rw.open(records_out, *p, ts.tnames, err);
+        const int orc = rw.open(records_out, *p, job.ts.tnames, err);
         if (orc) return orc;
         as.rec_out = &rw;
     }
-    bool flush_ok = true;
-    int rc = run_chunk_batches(reads, table, 0, table.size(), ts, p, err,
-                               [&](size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff) {
-                                   as.add(c0, c1, recs, roff);
-                                   if (flush_parts && parts_out && flush_ok) flush_ok = flush_parts(*parts_out);
-                               });
+    bool flush_ok = true;   // (a failed write stops the dealing)
+    int rc = job.run(0, job.table.size(), [&](size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff) {
+        as.add(c0, c1, recs, roff);
+        if (flush_parts && parts_out && flush_ok) flush_ok = flush_parts(*parts_out);
+        return flush_ok;
+    }, nullptr, err);
     if (rc == SD_OK && !flush_ok) { rc = SD_ERR_IO; err = "short write"; }
     if (records_out && rc == SD_OK) rc = rw.close(err, records_out);
     return rc;
@@ -1443,41 +1470,6 @@ int sd_pipeline_logic_selftest(char* errbuf, size_t errlen) {
 void sd_release_cache(void) { pipe_cache_clear(); g_pool.release_all(); g_pinpool.release_all(); g_deferred.drain(); text_pool_clear(); }
 
 
-namespace {
-// Records of a chunk range as the C-ABI hands them out (malloc'ed records + offsets), filled batch by batch straight
-// from the pipeline's pinned buffers: one copy per record (a std::vector + a final copy cost 6 ms per 200-Mb job).
-struct RangeCollector {
-    sd_rec* recs = nullptr;
-    int64_t* off = nullptr;
-    size_t cap = 0, n = 0, c_lo, n_chunks;
-    bool failed = false;
-    RangeCollector(size_t chunks, size_t first) : c_lo(first), n_chunks(chunks) {
-        off = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * (chunks + 1)));
-        cap = std::max<size_t>(4096, chunks * 40);   // ~32 records per 5.5-kb chunk of satellite DNA
-        recs = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec) * cap));
-        if (!off || !recs) failed = true; else off[0] = 0;
-    }
-    void add(size_t c0, size_t c1, const sd_rec* r, const int64_t* ro, int threads) {
-        if (failed) return;
-        const size_t k = (size_t)ro[c1 - c0];
-        if (n + k > cap) {
-            cap = std::max(n + k, cap + cap / 2);
-            sd_rec* q = static_cast<sd_rec*>(std::realloc(recs, sizeof(sd_rec) * cap));
-            if (!q) { failed = true; return; }
-            recs = q;
-        }
-        const size_t pieces = (k + 65535) / 65536;
-        sd::parallel_for((int64_t)pieces, threads, 1, [&](int64_t x) {
-            const size_t a = (size_t)x * 65536, b = std::min(k, a + 65536);
-            std::memcpy(recs + n + a, r + a, sizeof(sd_rec) * (b - a));
-        });
-        for (size_t c = 1; c <= c1 - c0; ++c) off[c0 - c_lo + c] = (int64_t)n + ro[c];
-        n += k;
-    }
-    void release(sd_rec** r, int64_t** o) { *r = recs; *o = off; recs = nullptr; off = nullptr; }
-    ~RangeCollector() { std::free(recs); std::free(off); }
-};
-}  // namespace
 
 int sd_decompose_chunk_range(const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads,
                              const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
@@ -1502,10 +1494,8 @@ int sd_decompose_chunk_range(const char* const* read_seqs, const int64_t* read_l
         rc = sd::check_alphabet(monos[(size_t)m].name.c_str(), mono_seqs[m], mono_lens[m], err);
         if (rc) { set_err(errbuf, errlen, err); return rc; }
     }
-    TemplateSet ts(monos);
-    std::vector<CRef> table;
-    std::vector<int32_t> nch;
-    build_chunk_table(reads, p, table, nch);
+    RawJob job(reads, monos, p);
+    const std::vector<CRef>& table = job.table;
     if (chunk_lo < 0 || chunk_hi < chunk_lo || (size_t)chunk_hi > table.size()) {
         set_err(errbuf, errlen, "chunk range outside the chunk table");
         return SD_ERR_PARAM;
@@ -1526,14 +1516,9 @@ int sd_decompose_chunk_range(const char* const* read_seqs, const int64_t* read_l
             }
         return SD_OK;
     };
-    RangeCollector col((size_t)(chunk_hi - chunk_lo), (size_t)chunk_lo);
-    rc = run_chunk_batches(reads, table, (size_t)chunk_lo, (size_t)chunk_hi, ts, p, err,
-                           [&](size_t c0, size_t c1, const sd_rec* r, const int64_t* ro) { col.add(c0, c1, r, ro, p->threads); },
-                           validate);
-    if (rc == SD_OK && col.failed) { rc = SD_ERR_INTERNAL; err = "out of host memory"; }
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    col.release(recs, rec_off);
-    return SD_OK;
+    rc = job.collect((size_t)chunk_lo, (size_t)chunk_hi, validate, recs, rec_off, err);
+    if (rc) set_err(errbuf, errlen, err);
+    return rc;
 }
 
 // File form of the chunk-range call for a job sharded over ranks: every rank maps and indexes the FASTA
@@ -1562,37 +1547,25 @@ static int decompose_files_range_impl(const char* reads_fa, const char* monomers
         if (r.len <= 0) { set_err(errbuf, errlen, "ERROR: Sequence " + std::string(r.name, r.name_len) + " is empty"); return SD_ERR_EMPTY; }
         reads.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
     }
-    TemplateSet ts(monos);
-    std::vector<CRef> table;
-    std::vector<int32_t> nch;
-    build_chunk_table(reads, p, table, nch);
-    const int64_t n = (int64_t)table.size();
+    RawJob job(reads, monos, p);
+    const int64_t n = (int64_t)job.table.size();
     const int64_t base = n / world, extra = n % world;
     const int64_t lo = rank * base + std::min<int64_t>(rank, extra);
     const int64_t hi = lo + base + (rank < extra ? 1 : 0);
     if (chunk_lo) *chunk_lo = lo;
     if (chunk_hi) *chunk_hi = hi;
     if (n_chunks_total) *n_chunks_total = n;
-    // the reads this share touches are checked under the device's work (run_chunk_batches: while_busy)
+    // the reads this share touches are checked under the device's work
     auto validate = [&](std::string& verr) -> int {
-        return hi > lo ? rf.validate((size_t)table[(size_t)lo].read, (size_t)table[(size_t)hi - 1].read + 1, p->threads, verr) : SD_OK;
+        return hi > lo ? rf.validate((size_t)job.table[(size_t)lo].read, (size_t)job.table[(size_t)hi - 1].read + 1, p->threads, verr) : SD_OK;
     };
-    RangeCollector col((size_t)(hi - lo), (size_t)lo);
-    rc = run_chunk_batches(reads, table, (size_t)lo, (size_t)hi, ts, p, err,
-                           [&](size_t c0, size_t c1, const sd_rec* r, const int64_t* ro) { col.add(c0, c1, r, ro, p->threads); },
-                           validate);
-    if (rc == SD_OK && col.failed) { rc = SD_ERR_INTERNAL; err = "out of host memory"; }
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    if (hout) {
-        sd_rec* r = nullptr;
-        int64_t* o = nullptr;
-        col.release(&r, &o);
-        rc = range_asm_from_files(rf, mf, p, lo, hi, r, o, edge, hout, err);   // (takes r / o over, also when it fails)
-        if (rc) { set_err(errbuf, errlen, err); return rc; }
-        return SD_OK;
-    }
-    col.release(recs, rec_off);
-    return SD_OK;
+    sd_rec* r = nullptr;
+    int64_t* o = nullptr;
+    rc = job.collect((size_t)lo, (size_t)hi, validate, &r, &o, err);
+    if (rc == SD_OK && hout) rc = range_asm_from_files(rf, mf, p, lo, hi, r, o, edge, hout, err);   // (takes r / o over, also when it fails)
+    else if (rc == SD_OK) { *recs = r; *rec_off = o; }
+    if (rc) set_err(errbuf, errlen, err);
+    return rc;
 }
 
 int sd_decompose_files_range(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank,

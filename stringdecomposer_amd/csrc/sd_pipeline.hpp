@@ -729,14 +729,6 @@ struct Pipeline {
         cur_engine = nullptr;
         cnt.sink_s += now_s() - t0;
     }
-    int drain() {
-        int rc = SD_OK;
-        while (inflight() > 0) {
-            const int r2 = pop();
-            if (r2 && !rc) rc = r2;
-        }
-        return rc;
-    }
     ~Pipeline() {
         if (inflight() > 0) (void)hipDeviceSynchronize();  // nothing may still run on buffers we free
         for (sd_engine* e : eng)

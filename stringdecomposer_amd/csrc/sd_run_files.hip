@@ -581,98 +581,42 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     if (!job.row_off) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
     // identities of the final TSV in-stream, behind every batch's compaction (sd_ident.hip); template sets the kernel
     // does not take (and SD_IDENT_STREAM=0, developer A/B) leave them to the post-processing as in round 2
-    std::atomic<bool> stream_ident{false};
-    std::vector<std::string> pkeys(nd), entry_err(nd);
-    {
-        sd_params pe = *p;
-        apply_env_overrides(pe);
-        stream_ident = !(pe.reserved[1] & SD_FLAG_NO_STREAM_IDENT);
-        for (size_t i = 0; i < nd; ++i) {   // keyed by the entry's device and, beyond the first, its index
-            pe.device = devs[i];
-            pkeys[i] = pipe_cache_key(pe, second_best ? '2' : '1', ts.mseq, ts.mlen);   // (host threads do not shape an engine)
-            if (i > 0) pkeys[i] += "#entry " + std::to_string(i);
-        }
-    }
-    std::vector<std::unique_ptr<Pipeline>> pipes(nd);
-    std::vector<int64_t> entry_budget(nd, 0);
-    std::atomic<bool> reused{true};
-    auto on_engine = [&](sd_engine* e) {
+    sd_params pe = *p;
+    apply_env_overrides(pe);
+    std::atomic<bool> stream_ident{!(pe.reserved[1] & SD_FLAG_NO_STREAM_IDENT)};
+    JobPipes jp(devs);
+    rc = jp.open(p, second_best ? '2' : '1', ts, [&](sd_engine* e) {
         if (stream_ident && !engine_set_identity(e, pp.interleaved_seqs(), pp.own_interleaved(), second_best != 0)) stream_ident = false;
-    };
-    // the pipeline of entry i, from the cache or new, and its budget (hipMemGetInfo of the entry's device)
-    auto open_pipe = [&](int i) -> int {
-        sd_params pi = *p;
-        pi.device = devs[(size_t)i];
-        std::unique_ptr<Pipeline>& h = pipes[(size_t)i];
-        h = getenv("SD_PIPE_CACHE_OFF") ? nullptr : pipe_cache_take(pkeys[(size_t)i]);
-        const bool cached = h != nullptr;
-        if (!cached) { h.reset(new Pipeline); reused = false; }
-        h->restart_idle = true;
-        h->on_engine = on_engine;
-        if (cached) {
-            h->begin_job(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size());
-            if (!h->ident_ok) stream_ident = false;
-        } else if (const int r = h->create(&pi, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size())) {
-            entry_err[(size_t)i] = h->eb;
-            return r;
-        }
-        entry_budget[(size_t)i] = h->row_budget();
-        return SD_OK;
-    };
-    rc = on_entries(devs, entry_err, err, open_pipe, [] {});
-    for (std::unique_ptr<Pipeline>& h : pipes)
-        if (!h) { h.reset(new Pipeline); reused = false; }   // (an entry whose device could not be selected)
-    lap(reused ? "pipeline from the cache" : "engine (HIP runtime start, layout plan, tables, identity masks)");
+    }, err);
+    for (size_t i = 0; i < nd; ++i)
+        if (jp.cached[i] && !jp.pipes[i]->ident_ok) stream_ident = false;   // (its engines carry no identity tables)
+    lap(jp.reused() ? "pipeline from the cache" : "engine (HIP runtime start, layout plan, tables, identity masks)");
     if (stream_ident) job.per = second_best ? (int)pp.interleaved_seqs().size() : 1;
     const bool slice_ident = second_best && !getenv("SD_IDENT_SLICES_OFF");
     std::vector<std::pair<size_t, size_t>> batches;
-    if (rc == SD_OK) plan_job(job, entry_budget, devs, p, second_best != 0, slice_ident, reused, batches);
+    if (rc == SD_OK) plan_job(job, jp.budget, devs, p, second_best != 0, slice_ident, jp.reused(), batches);
     lap("batch plan");
     const double t_setup = now_s() - t_begin;
     if (progress) std::fprintf(stderr, "Prepared reads\n");   // main.cpp:82
     TextStages text(reads, ts, pp, records_out ? &rec_w : nullptr, files, raw_tsv_out, progress, second_best != 0, timing, t_begin);
     text.start();
-    std::vector<int64_t> dealt(nd, 0);   // batches per entry
-    if (rc == SD_OK) {
-        // One driver per entry takes the lowest batch nobody has whenever its pipeline can take one (a pipeline pushes
-        // until all its slots are busy, then waits for its oldest batch), and hands its batches' records to the assembler
-        // in batch order (BatchTurns).  Every HIP call of a pipeline -- engines, streams, events, copies, identity slices
-        // -- is made on its driver's thread; the text stages make none.
-        BatchTurns turns;
-        std::atomic<size_t> next_batch{0};
-        auto drive = [&](int i) {
-            Pipeline& pq = *pipes[(size_t)i];
-            std::vector<const char*> cptr;
-            std::vector<int32_t> clen;
-            std::vector<int> slice_end;
-            auto push = [&](size_t b) {
-                const size_t c0 = batches[b].first, c1 = batches[b].second;
-                batch_chunks(reads, job.table, c0, c1, cptr, clen);
-                slice_end.clear();
-                if (slice_ident && stream_ident) ident_slices(job.table, c0, c1, slice_end);
-                const int r = pq.push(cptr, clen, [&turns, &job, &pq, &text, b, c0, c1](const sd_rec* rr, const int64_t* ro, size_t first, size_t n) {
-                    if (turns.wait(b)) assemble(job, pq, c0 + first, c0 + first + n, rr, ro, text);
-                    if (c0 + first + n == c1) turns.done(b);
-                }, slice_end);
-                if (r) entry_err[(size_t)i] = pq.eb;   // (what failed first, not a pop while the pipeline drains)
-                return r;
-            };
-            const int r = drive_entry(pq, turns, next_batch, batches.size(), text.rc, push, dealt[(size_t)i]);
-            if (r && entry_err[(size_t)i].empty()) entry_err[(size_t)i] = pq.eb;
-            return r;
-        };
-        rc = on_entries(devs, entry_err, err, drive, [&turns] { turns.abort(); });
-    }
+    // One driver per entry takes the lowest batch nobody has whenever its pipeline can take one (a pipeline pushes until
+    // all its slots are busy, then waits for its oldest batch), and hands its batches' records to the assembler in batch
+    // order (BatchTurns).  Every HIP call of a pipeline -- engines, streams, events, copies, identity slices -- is made on
+    // its driver's thread; the text stages make none.
+    if (rc == SD_OK)
+        rc = jp.drive(reads, job.table, batches, text.rc, [&](size_t c0, size_t c1, std::vector<int>& slice_end) {
+            if (slice_ident && stream_ident) ident_slices(job.table, c0, c1, slice_end);
+        }, [&](Pipeline& pq, size_t c0, size_t c1, const sd_rec* recs, const int64_t* roff) {
+            assemble(job, pq, c0, c1, recs, roff, text);
+        }, [] {}, err);
     text.finish();
     if (rc == SD_OK && text.failed()) { rc = text.rc.load(); err = text.err; }
     if (!files.close() && rc == SD_OK) { rc = SD_ERR_IO; err = std::string("short write to ") + raw_tsv_out; }
     if (records_out && rc == SD_OK) rc = rec_w.close(err, records_out);
-    report_stats(pipes, dealt, text, pp, batches.size(), t_setup);
-    for (size_t i = 0; i < nd; ++i) {
-        pipes[i]->ident_ok = stream_ident;
-        pipes[i]->on_engine = nullptr;   // (it refers to this call's locals)
-        if (rc == SD_OK && !getenv("SD_PIPE_CACHE_OFF")) pipe_cache_give(pkeys[i], std::move(pipes[i]), (int)i);
-    }
+    report_stats(jp.pipes, jp.dealt, text, pp, batches.size(), t_setup);
+    for (std::unique_ptr<Pipeline>& q : jp.pipes) q->ident_ok = stream_ident;
+    jp.give_back(rc == SD_OK);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     if (profile) {
         if (timing) std::fprintf(stderr, "[sd timing] column profiles of the kept rows: %.1f ms\n", pp.t_profile * 1e3);
@@ -816,14 +760,17 @@ int sd_multi_device_selftest(char* errbuf, size_t errlen) {
     // (3) a pipeline that fails on a batch that is not its last -- when it pops the batch to make room for the next, or
     // while it drains, or when it cannot take a batch at all -- ends the job: every driver returns (a driver that waited
     // for the failed batch's turn would hang the job; a watchdog aborts the turns after 20 s and reports it), the error is
-    // returned, and what was consumed is a prefix of the batches in order that stops before the failed one.
+    // returned, and what was consumed is a prefix of the batches in order that stops before the failed one.  A driver's
+    // busy() runs once, after its last push and before its first drain pop, and not at all after a failed push.
     {
         struct ModelPipe {   // Pipeline's order of pops: FIFO, the oldest popped when a push finds all slots busy
             int slots = 3;
             size_t fail_pop = SIZE_MAX, fail_push = SIZE_MAX;
             std::deque<std::pair<size_t, std::function<void()>>> q;
+            std::string log;   // 'p' a batch taken, 'x' a push failed, 'o' a pop of the driver's drain, 'b' busy()
             int inflight() const { return (int)q.size(); }
-            int pop() {
+            int pop(bool drain = true) {
+                if (drain) log += 'o';
                 std::pair<size_t, std::function<void()>> x = std::move(q.front());
                 q.pop_front();
                 if (x.first == fail_pop) return SD_ERR_HIP;   // (its sink never runs)
@@ -831,12 +778,13 @@ int sd_multi_device_selftest(char* errbuf, size_t errlen) {
                 return SD_OK;
             }
             int push(size_t b, std::function<void()> sink) {
-                if (b == fail_push) return SD_ERR_HIP;
+                if (b == fail_push) { log += 'x'; return SD_ERR_HIP; }
                 if (inflight() == slots) {
-                    const int e = pop();
-                    if (e) return e;
+                    const int e = pop(false);
+                    if (e) { log += 'x'; return e; }
                 }
                 q.emplace_back(b, std::move(sink));
+                log += 'p';
                 return SD_OK;
             }
         };
@@ -871,7 +819,7 @@ int sd_multi_device_selftest(char* errbuf, size_t errlen) {
                             turns.done(b);
                         });
                     };
-                    rcs[(size_t)i] = drive_entry(mp, turns, next, nb, sink_ok, push, dealt[(size_t)i]);
+                    rcs[(size_t)i] = drive_entry(mp, turns, next, nb, sink_ok, push, dealt[(size_t)i], [&mp] { mp.log += 'b'; });
                     std::lock_guard<std::mutex> g(fin_m);
                     ++finished;
                     fin_cv.notify_all();
@@ -889,6 +837,13 @@ int sd_multi_device_selftest(char* errbuf, size_t errlen) {
             if (failed != 1) return fail("a failed batch did not end the job with exactly that pipeline's error");
             for (size_t k = 0; k < seen.size(); ++k)
                 if (seen[k] != k || k >= bad) return fail("after a failure, consumption was not an in-order prefix before the failed batch");
+            for (const ModelPipe& mp : pipes) {
+                const size_t at = mp.log.find('b'), npos = std::string::npos;
+                if (mp.log.find('x') != npos ? at != npos : at == npos || mp.log.find('b', at + 1) != npos)
+                    return fail("busy() did not run exactly once, or ran after a failed push");
+                if (at != npos && (mp.log.find('p', at) != npos || mp.log.rfind('o', at) != npos))
+                    return fail("busy() did not run between the last push and the first drain pop");
+            }
         }
     }
     // (4) an aborted job: every waiter returns, nothing after the abort is consumed
