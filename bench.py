@@ -6,19 +6,23 @@
 
 A "step" is one pass of the hot path over one batch of synthetic reads, from sequences in host memory to
 rows in host memory: chunk table, 2-bit packing, H2D, DP fill, traceback, record
-compaction, D2H, per-read assembly (chunk offsets + seam merge).  The same K steps are then repeated
-with the batch packed and resident in HBM (one launch per kernel) for the clean per-kernel times
-(`device_resident`).  At N=1 the workload is BASELINE.json configs[1] (C2): 1000 reads x 50 kb,
-12 monomers (~171 bp), default scoring.  With N GPUs every rank owns its own 1000 reads (weak scaling; reads are independent, no
-data-path collective -- SURVEY.md section 8(e)); torch.distributed is used for the barrier and the
-max-over-ranks time only.
+compaction, D2H, per-read assembly (chunk offsets + seam merge).  At N=1 the workload is BASELINE.json
+configs[1] (C2): 1000 reads x 50 kb, 12 monomers (~171 bp), default scoring.  With N GPUs every rank owns its own 1000
+reads (weak scaling; reads are independent, no data-path collective -- SURVEY.md section 8(e)); torch.distributed is
+used for the barrier and the max-over-ranks time only.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what the headline needs: it
+sets up, warms up, times the K steps, writes --dump-outputs and prints the line, whose other figures are those the
+timed steps recorded themselves (kernel and host-stage times).  With --full (N=1) it then measures the rest, each
+figure on runs of its own after the timed steps:
+  other_pipe_mode, sustained   the same steps in the other kernel-stream mode; the same steps for seconds
+  device_resident              the same K steps with the batch packed and resident in HBM (one launch per kernel): the
+                               clean per-kernel times; roofline.int16_cells / f16_cells the same with the other cell formats
   roofline      the fill kernel against what binds it: VALU wave-instructions per second against the measured
                 issue ceiling (bound "valu"); roofline.hbm_notional = algorithmic bytes of the fill (SURVEY 8(d):
                 sum_chunks n*(sumL/4 + 6.25) + 24*rows) over the fill's average HIP-event duration against 8 TB/s
   cpu_baseline  the real reference binary (oracle/_ref/dp, kind "reference") or the C oracle
-                (kind "port") timed on this box's host cores on a bounded sample of the same reads.
+                (kind "port") timed on the host cores on a bounded sample of the same reads.
 """
 import argparse
 import json
@@ -272,9 +276,9 @@ def bench_c4_second_best(args):
                              "insts_source": "committed profile profiles/ident_traffic.json (rocprofv3 --pmc SQ_INSTS_VALU)"})
         else:
             roofline.update({"bound": "valu", "achieved": None, "peak": VALU_PEAK_GINST, "unit": "G wave-inst/s", "frac": None})
-        # the leg's CPU baseline, timed on THIS box: reference dp + reference edlib on the first two reads; the unmodified
+        # --full: the leg's CPU baseline, timed on THIS box: reference dp + reference edlib on the first two reads; the unmodified
         # reference command line (pandas / Bio driver included) was timed once in the build container, where it can run
-        cpu = None if args.no_cpu_baseline else cpu_baseline_c4_second_best(mn, ms, rn[:2], rs[:2])
+        cpu = None if (args.no_cpu_baseline or not args.full) else cpu_baseline_c4_second_best(mn, ms, rn[:2], rs[:2])
         cj = os.path.join(ROOT, "profiles", "ref_cli_c4_second_best.json")
         if os.path.isfile(cj) and cpu is not None:
             with open(cj) as f:
@@ -372,9 +376,9 @@ def bench_strong(args):
     # (shard._assemble_by_ranks: two exchanges of a few hundred bytes, csrc/sd_seam.hpp) instead of rank 0 for everybody;
     # timed once and reported beside the DP.  One process: the whole-job assembly a single GPU pays, and the same job cut
     # into eight ranges assembled one after the other with the threads a rank of eight gets (what each of eight GPUs' hosts
-    # would pay: the slowest range counts).
+    # would pay: the slowest range counts).  --full only.
     serial = None
-    if st is None:
+    if st is None and args.full:
         import numpy as np
         shard.barrier(dist, bar_dev)
         if dist is not None and ws > 1:
@@ -563,19 +567,26 @@ def main():
     ap.add_argument("--monomers", type=int, default=12)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--kernel", choices=["auto", "generic", "fast"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure as well: the CPU baseline, the other kernel-stream "
+                         "mode, the sustained leg, the device-resident repeat, the other cell formats and the roofline (c2); "
+                         "the CPU baseline (c4-second-best); the assembly after the DP (strong scaling).  Without it a run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--allow-port-baseline", action="store_true",
-                    help="accept the C restatement (kind \"port\") as cpu_baseline even under SD_REQUIRE_REF=1, which otherwise "
-                         "makes a run without oracle/_ref/dp exit 3 after printing its line (without SD_REQUIRE_REF the port "
-                         "stands in, as in the test suite, and the line says so in cpu_baseline.kind)")
+                    help="--full: accept the C restatement (kind \"port\") as cpu_baseline even under SD_REQUIRE_REF=1, which "
+                         "otherwise makes a run without oracle/_ref/dp exit 3 after printing its line (without SD_REQUIRE_REF the "
+                         "port stands in, as in the test suite, and the line says so in cpu_baseline.kind)")
     ap.add_argument("--cpu-sample-reads", type=int, default=200,
-                    help="reads of the benchmark set the reference CPU path is timed on and compared with (200 x 50 kb = 10 Mbp: "
-                         "~25 s of `dp -t 8`)")
+                    help="--full: reads of the benchmark set the reference CPU path is timed on and compared with (200 x 50 kb "
+                         "= 10 Mbp: ~25 s of `dp -t 8`)")
     ap.add_argument("--sustain-seconds", type=float, default=8.0,
-                    help="N = 1: after the timed region, the same steps for about this long (reported as `sustained`; 0 = skip)")
+                    help="--full, N = 1: after the timed region, the same steps for about this long (reported as `sustained`; "
+                         "0 = skip)")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the timed region (no second pipe mode, no device-resident repeat): for profilers, so "
-                         "that per-kernel averages are those of the timed launches")
+                    help="--full without the runs of its own (no second pipe mode, no sustained leg, no device-resident "
+                         "repeat, no other cell formats): the roofline and the CPU baseline of the timed region only.  A "
+                         "plain run has none of them: for profilers, per-kernel averages are those of the timed launches")
     ap.add_argument("--ed-thr", type=int, default=-1, help="--ed_thr prefilter (profiling the filter kernels; not the headline)")
     ap.add_argument("--pipe-mode", type=int, choices=[0, 1, 2], default=2,
                     help="kernel streams of the timed region: 2 = the library default (traceback and the next fill move into "
@@ -710,6 +721,54 @@ def main():
     dt = shard.max_over_ranks(dist, dt, dev)
     bp_total = shard.sum_over_ranks(dist, bp_rank, dev)
     n_chunks = lib.chunk_table_size([len(x) for x in rs])
+
+    # ---- the result line: the headline and what the timed region itself recorded; --full adds the figures below ----------
+    out = {
+        "metric": "decomposed read-bp/sec (whole node) at 12 monomers x 50kb reads",
+        "value": bp_total * K / dt, "unit": "bp/s", "n_gpus": ws, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / K * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": info["cells"].split("/")[0],
+        "data": "synthetic",
+        "timed_region": "sequences in host memory -> chunk -> 2-bit pack -> H2D -> fill -> traceback -> compaction -> "
+                        "D2H -> per-read assembly -> rows in host memory (SURVEY 8(d)); %d device batch(es) per step, %d "
+                        "batches in flight (pinned staging, copies on their own streams), pipelined across steps: a step's "
+                        "rows are collected when %d later step(s) have been submitted; every step's rows are in host memory "
+                        "inside the timed region; kernel streams: %s" % (
+                            args.sub_batches, BENCH_DEPTH + 1, BENCH_DEPTH, "one, in order (pipe_mode 0)" if args.pipe_mode == 0 else
+                                         "overlapped (pipe_mode %d, the library default is 2)" % args.pipe_mode),
+        "config": {"workload": "%s: synthetic %d reads x %d bp per GPU, %d monomers (~171 bp) + reverse complements, "
+                               "default scoring -1,-1,-1,1, part 5000 / overlap 500" % (
+                                   "C2" if (args.monomers, args.reads, args.read_len) == (12, 1000, 50000) else
+                                   "C4 shape (DP only)" if args.monomers == 64 else "custom", args.reads, args.read_len, args.monomers),
+                   "reads_per_gpu": args.reads, "read_len": args.read_len, "n_templates": info["n_templates"],
+                   "sum_template_len": info["sum_template_len"], "chunks_per_gpu": n_chunks,
+                   "kernel_family": info["family"], "cells_per_lane": info["cells_per_lane"],
+                   "cell_arithmetic": info["cells"] + (" (packed pairs holding exact integers)" if info["cells"] == "f16" else
+                                                       " (packed pairs of biased unsigned 16-bit integers, exact over +-15 k)" if info["cells"] == "u16" else ""),
+                   "sub_batches": args.sub_batches, "host_threads": threads, "ed_thr": args.ed_thr,
+                   "seed": args.seed, "sharding": "reads dealt to ranks in contiguous blocks, no collective"},
+        "roofline": None,
+        "kernel_ms_per_step": {"fill": d["fill_ms"] / K, "traceback": d["trace_ms"] / K, "compact": d["compact_ms"] / K,
+                               "note": "HIP-event spans per batch, summed; batches on the two streams overlap"},
+        "host_ms_per_step": {"pack_upload_enqueue": d["host_pack_ms"] / K, "wait_for_device": d["host_wait_ms"] / K,
+                             "d2h_assemble": d["host_assemble_ms"] / K,
+                             "process_cpu_ms": d["host_cpu_ms_per_step"],
+                             "cpu_quota_cores": cpu_quota_cores(),
+                             "note": "wall ms of the host stages of one step; process_cpu_ms = CPU time of all host "
+                                     "threads of this rank per step (user + system)"},
+        "other_pipe_mode": None,
+        "sustained": None,
+        "amd_direct_dispatch": AMD_DIRECT_DISPATCH,
+        "rows_out_per_gpu": rows_out,
+        "device_resident": None,
+        "cpu_baseline": None,
+        "full": args.full,
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if not args.full:
+        return finish_weak(out, [], rank, dist)
+
     other = None
     if ws == 1 and not args.timed_only:   # the other kernel-stream mode, same K steps (secondary figure)
         om = 2 if args.pipe_mode == 0 else 0
@@ -912,70 +971,30 @@ def main():
         f16_leg["same_rows_as_headline"] = bool(f16_leg.pop("rows_out") == res_recs)
         roofline["f16_cells"] = f16_leg
 
-    out = {
-        "metric": "decomposed read-bp/sec (whole node) at 12 monomers x 50kb reads",
-        "value": bp_total * K / dt, "unit": "bp/s", "n_gpus": ws, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / K * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": info["cells"].split("/")[0],
-        "data": "synthetic",
-        "timed_region": "sequences in host memory -> chunk -> 2-bit pack -> H2D -> fill -> traceback -> compaction -> "
-                        "D2H -> per-read assembly -> rows in host memory (SURVEY 8(d)); %d device batch(es) per step, %d "
-                        "batches in flight (pinned staging, copies on their own streams), pipelined across steps: a step's "
-                        "rows are collected when %d later step(s) have been submitted; every step's rows are in host memory "
-                        "inside the timed region; kernel streams: %s" % (
-                            args.sub_batches, BENCH_DEPTH + 1, BENCH_DEPTH, "one, in order (pipe_mode 0)" if args.pipe_mode == 0 else
-                                         "overlapped (pipe_mode %d, the library default is 2)" % args.pipe_mode),
-        "config": {"workload": "%s: synthetic %d reads x %d bp per GPU, %d monomers (~171 bp) + reverse complements, "
-                               "default scoring -1,-1,-1,1, part 5000 / overlap 500" % (
-                                   "C2" if (args.monomers, args.reads, args.read_len) == (12, 1000, 50000) else
-                                   "C4 shape (DP only)" if args.monomers == 64 else "custom", args.reads, args.read_len, args.monomers),
-                   "reads_per_gpu": args.reads, "read_len": args.read_len, "n_templates": info["n_templates"],
-                   "sum_template_len": sumL, "chunks_per_gpu": n_chunks, "rows_per_gpu": rows,
-                   "kernel_family": info["family"], "cells_per_lane": info["cells_per_lane"],
-                   "cell_arithmetic": info["cells"] + (" (packed pairs holding exact integers)" if info["cells"] == "f16" else
-                                                       " (packed pairs of biased unsigned 16-bit integers, exact over +-15 k)" if info["cells"] == "u16" else ""),
-                   "sub_batches": args.sub_batches, "host_threads": threads, "ed_thr": args.ed_thr,
-                   "seed": args.seed, "sharding": "reads dealt to ranks in contiguous blocks, no collective"},
+    out["config"]["rows_per_gpu"] = rows
+    out.update({
         # contract figure: SURVEY 8(d) algorithmic bytes of a fill launch / its HIP-event duration, launches of
         # the timed region (in the default stream mode a fill's span contains the neighbouring batch's traceback
         # and the drain hand-over; isolated_* = the same kernel launched alone, from the device_resident steps)
         "roofline": roofline,
-        "kernel_ms_per_step": {"fill": d["fill_ms"] / K, "traceback": d["trace_ms"] / K, "compact": d["compact_ms"] / K,
-                               "note": "HIP-event spans per batch, summed; batches on the two streams overlap"},
-        "host_ms_per_step": {"pack_upload_enqueue": d["host_pack_ms"] / K, "wait_for_device": d["host_wait_ms"] / K,
-                             "d2h_assemble": d["host_assemble_ms"] / K,
-                             "process_cpu_ms": d["host_cpu_ms_per_step"],
-                             "cpu_quota_cores": cpu_quota_cores(),
-                             "note": "wall ms of the host stages of one step; process_cpu_ms = CPU time of all host "
-                                     "threads of this rank per step (user + system)"},
         "other_pipe_mode": other,
         "sustained": sustained,
-        "amd_direct_dispatch": AMD_DIRECT_DISPATCH,
-        # batches repeated with integer cells because the fp16 range guard tripped: must be 0 (checked below)
-        "f16_guard_trips": lib.guard_trips(),
-        "rows_out_per_gpu": rows_out, "hbm_workspace_bytes": einfo["workspace_bytes"] * (BENCH_DEPTH + 1),
+        "hbm_workspace_bytes": einfo["workspace_bytes"] * (BENCH_DEPTH + 1),
         "hbm_workspace_per_engine_bytes": einfo["workspace_bytes"],   # (one engine per batch in flight)
         # kernels only, batch packed and resident in HBM before the clock starts, one launch per kernel
         "device_resident": None if not res_steps else {
             "bp_per_s": bp_rank * res_steps / dtr, "ms_per_step": dtr / res_steps * 1e3,
             "kernel_ms_per_step": {"fill": r_fill / res_steps, "traceback": r_trace / res_steps, "compact": r_cmp / res_steps},
             "fill_roofline_frac": res_achieved / HBM_PEAK_GBS, "load_reads_s": t_load},
-    }
+    })
     if rank == 0 and ws == 1 and not args.no_cpu_baseline:
         k = max(1, min(args.cpu_sample_reads, len(rs)))
         txt = lib.decompose(rn[:k], rs[:k], mn, ms, device=local_rank, kernel=kernel)
         out["cpu_baseline"] = cpu_baseline(mn, ms, rn[:k], rs[:k], txt)
-    elif rank == 0:
-        out["cpu_baseline"] = None
-    if dumped is not None:
-        out["dumped_outputs"] = dumped
-    # The line is only a result if the fp16 guard never tripped, and -- where a CPU baseline was asked for -- if its
-    # rows equal the HIP path's on the sample; with SD_REQUIRE_REF=1 (as in the test suite) the baseline must also be the
-    # REAL reference binary, which a checkout only has where oracle/_ref/ was built.  Otherwise the line is still printed
-    # (with "invalid") and the process exits non-zero.
+    # where a CPU baseline was asked for, the line is only a result if its rows equal the HIP path's on the sample; with
+    # SD_REQUIRE_REF=1 (as in the test suite) the baseline must also be the REAL reference binary, which a checkout only has
+    # where oracle/_ref/ was built
     problems = []
-    if out["f16_guard_trips"] != 0:
-        problems.append("fp16 range guard tripped %d time(s)" % out["f16_guard_trips"])
     cb = out.get("cpu_baseline")
     if cb is not None:
         if cb["kind"] != "reference" and os.environ.get("SD_REQUIRE_REF") and not args.allow_port_baseline:
@@ -986,10 +1005,20 @@ def main():
         problems.append("integer-cell run produced a different number of rows")
     if f16_leg is not None and not f16_leg["same_rows_as_headline"]:
         problems.append("fp16-cell run produced a different number of rows")
-    if problems:
-        out["invalid"] = problems
     if profile_problems:   # (the measured value stands; only the figures derived from the committed counters are withheld)
         out["profile_problems"] = profile_problems
+    return finish_weak(out, problems, rank, dist)
+
+
+def finish_weak(out, problems, rank, dist):
+    """Prints the line of the weak-scaling leg on rank 0.  The line is only a result if the fp16 range guard never tripped
+    and `problems` (what --full found) is empty; otherwise it is still printed (with "invalid") and the process exits 3."""
+    # batches repeated with integer cells because the fp16 range guard tripped: must be 0
+    out["f16_guard_trips"] = lib.guard_trips()
+    if out["f16_guard_trips"] != 0:
+        problems = ["fp16 range guard tripped %d time(s)" % out["f16_guard_trips"]] + problems
+    if problems:
+        out["invalid"] = problems
     if rank == 0:
         print(json.dumps(out), file=_claimed_stdout(), flush=True)
     if dist is not None:

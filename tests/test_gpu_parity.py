@@ -1011,10 +1011,10 @@ def test_cli_vs_unmodified_reference_cli(name, tmp_path):
 
 
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the fields the driver parses (metric / value / unit / n_gpus / steps /
+    """bench.py --full prints ONE JSON line with the fields the driver parses (metric / value / unit / n_gpus / steps /
     warmup / ms_per_step / scaling / dtype / data / config.workload / roofline / cpu_baseline); small workload."""
     import json
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--reads", "120",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--reads", "120",
                         "--cpu-sample-reads", "2", "--sustain-seconds", "1.5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -1040,6 +1040,26 @@ def test_bench_line_contract():
     assert su["same_rows_as_headline"] is True and su["steps"] >= 3 and 1.0 < su["seconds"] < 60 and 0.3 < su["vs_timed_region"] < 3
     # three batches in flight, one engine each (the timed loop keeps two later steps outstanding)
     assert j["hbm_workspace_bytes"] == 3 * j["hbm_workspace_per_engine_bytes"] and "3 batches in flight" in j["timed_region"]
+    assert j["full"] is True and j["config"]["rows_per_gpu"] > 0 and j["f16_guard_trips"] == 0 and "invalid" not in j
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """bench.py without --full: the same headline fields, from the timed steps alone -- none of the figures that take runs
+    of their own (CPU baseline, other stream mode, sustained leg, device-resident repeat, other cell formats, roofline)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--reads", "120"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["unit"] == "bp/s" and j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["scaling"] == "weak"
+    assert j["higher_is_better"] is True and j["data"] == "synthetic" and j["dtype"] == "u16" and j["full"] is False
+    assert j["value"] > 1e8 and abs(j["value"] - 120 * 50000 / (j["ms_per_step"] / 1e3)) / j["value"] < 1e-6
+    assert "workload" in j["config"] and "3 batches in flight" in j["timed_region"] and j["f16_guard_trips"] == 0
+    assert j["kernel_ms_per_step"]["fill"] > 0 and j["host_ms_per_step"]["process_cpu_ms"] > 0 and j["rows_out_per_gpu"] > 0
+    for k in ("roofline", "cpu_baseline", "other_pipe_mode", "sustained", "device_resident"):
+        assert j[k] is None, k
+    assert "invalid" not in j and "dumped_outputs" not in j
 
 
 def test_bench_dump_outputs_are_the_rows_of_the_timed_path(tmp_path):

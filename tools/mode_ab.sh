@@ -6,7 +6,7 @@ O=gpurun_out/$V
 mkdir -p $O
 for i in $(seq 1 $N); do
   for m in 2 1 0; do
-    timeout 300 python bench.py --steps 20 --no-cpu-baseline --timed-only --pipe-mode $m > $O/m${m}_$i.json 2> $O/m${m}_$i.err
+    timeout 300 python bench.py --full --steps 20 --no-cpu-baseline --timed-only --pipe-mode $m > $O/m${m}_$i.json 2> $O/m${m}_$i.err
     python3 - $O/m${m}_$i.json $m <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

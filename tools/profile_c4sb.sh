@@ -5,7 +5,7 @@ O=$PWD/${1:-gpurun_out/c4sb}
 mkdir -p "$O"
 R=$PWD
 export TMPDIR=/tmp
-timeout 600 python bench.py --config c4-second-best --steps 5 --warmup 2 > $O/bench_c4sb.json 2> $O/bench_c4sb.err
+timeout 600 python bench.py --full --config c4-second-best --steps 5 --warmup 2 > $O/bench_c4sb.json 2> $O/bench_c4sb.err
 tail -c 600 $O/bench_c4sb.json
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --config c4-second-best --steps 3 --warmup 1 > $O/stats.log 2>&1)
 for c in "SQ_INSTS_VALU GRBM_GUI_ACTIVE" FETCH_SIZE WRITE_SIZE; do

@@ -4,10 +4,10 @@
 V=${1:-wide}
 O=gpurun_out/$V
 mkdir -p $O
-timeout 300 python bench.py --no-cpu-baseline --monomers 64 --reads 256 --steps 10 --warmup 2 > $O/bench_c4.json 2> $O/bench_c4.err
-timeout 300 python bench.py --no-cpu-baseline --monomers 128 --reads 64 --steps 5 --warmup 2 > $O/bench_m128.json 2> $O/bench_m128.err
-timeout 300 python bench.py --no-cpu-baseline --monomers 128 --reads 256 --steps 5 --warmup 2 > $O/bench_m128_256reads.json 2> $O/bench_m128_256.err
-timeout 300 python bench.py --no-cpu-baseline --monomers 400 --reads 64 --steps 5 --warmup 2 > $O/bench_m400.json 2> $O/bench_m400.err
+timeout 300 python bench.py --full --no-cpu-baseline --monomers 64 --reads 256 --steps 10 --warmup 2 > $O/bench_c4.json 2> $O/bench_c4.err
+timeout 300 python bench.py --full --no-cpu-baseline --monomers 128 --reads 64 --steps 5 --warmup 2 > $O/bench_m128.json 2> $O/bench_m128.err
+timeout 300 python bench.py --full --no-cpu-baseline --monomers 128 --reads 256 --steps 5 --warmup 2 > $O/bench_m128_256reads.json 2> $O/bench_m128_256.err
+timeout 300 python bench.py --full --no-cpu-baseline --monomers 400 --reads 64 --steps 5 --warmup 2 > $O/bench_m400.json 2> $O/bench_m400.err
 python3 - <<PY
 import json
 for w in ("c4", "m128", "m128_256reads", "m400"):

@@ -8,7 +8,7 @@ n=0
 for cfg in "$@"; do
   n=$((n+1))
   if [ "$cfg" = "-" ]; then cfg=""; fi
-  env $cfg timeout 300 python bench.py --steps 20 --no-cpu-baseline > $O/b$n.json 2> $O/b$n.err
+  env $cfg timeout 300 python bench.py --full --steps 20 --no-cpu-baseline > $O/b$n.json 2> $O/b$n.err
   python3 - "$O/b$n.json" "$cfg" <<'PY'
 import json, sys
 try:
