@@ -726,6 +726,14 @@ extern "C++" int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char*
                                             compact ? e->d_klist.p : nullptr, compact ? e->d_nkept.p : nullptr,
                                             e->filter_uniform, e->d_vlane0.p);
                 SD_HIP(hipEventRecord(e->ev_fill[0], st));
+                sd::FillArgs fa{};
+                fa.chunks = e->dp_chunks; fa.n_chunks = C; fa.bases2 = e->dp_bases2; fa.nmask = e->dp_nmask;
+                fa.table = e->d_ftable.p; fa.lane_consts = e->d_flane.p; fa.sc = e->sc;
+                fa.B = e->d_B.p; fa.argV = e->d_argB.p; fa.ckpt = e->d_fckpt.p; fa.ckbase = e->d_fckbase.p;
+                fa.queue = qfill; fa.order = e->dp_order; fa.n_cu = e->n_cu;
+                if (ranked) { fa.cendoff = e->d_cendoff.p; fa.crank = e->d_crank.p; }
+                if (compact) { fa.klist = e->d_klist.p; fa.lane_t = e->fplan.tiled ? e->d_lanet.p : nullptr; }
+                fa.tcodes = e->d_ftcodes.p; fa.toff = e->d_toff.p; fa.tlen = e->d_tlen.p;
                 if (compact) {
                     // more than 128 templates: a chunk is filled by as many waves as its kept templates need, holding
                     // exactly those (the point of the reference's prefilter, main.cpp:128-149: less DP work); chunks
@@ -737,50 +745,29 @@ extern "C++" int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char*
                         sd::launch_tiled_place(st, C, e->T, e->fplan.P, W, e->d_klist.p, e->d_nkept.p, e->d_tlen.p,
                                                e->d_kpos.p, e->d_lanet.p, e->fplan.filter_only ? e->d_guard.p : nullptr);
                     sd::launch_split_order(st, e->dp_order, C, e->d_nkept.p, ord, e->d_cls.p, W);
-                    for (int w = 1; w < W; ++w)
-                        if (e->fplan.tiled)
-                            sd::launch_fast_fill_wt_compact(e->fplan, st, e->dp_chunks, e->dp_bases2, e->dp_nmask, e->d_flane.p,
-                                                            e->sc, e->d_B.p, e->d_fckpt.p, e->d_fckbase.p,
-                                                            w == 1 ? qfill : qfill + 1 + w, ord + (size_t)(w - 1) * C,
-                                                            e->d_cls.p + (w - 1), e->n_cu, e->d_lanet.p, e->d_ftcodes.p,
-                                                            e->d_toff.p, e->d_tlen.p, w);
-                        else
-                        sd::launch_fast_fill_wn_compact(e->fplan, st, e->dp_chunks, e->dp_bases2, e->dp_nmask, e->d_flane.p,
-                                                        e->sc, e->d_B.p, e->d_fckpt.p, e->d_fckbase.p,
-                                                        w == 1 ? qfill : qfill + 1 + w, ord + (size_t)(w - 1) * C,
-                                                        e->d_cls.p + (w - 1), e->n_cu, e->d_klist.p, e->d_ftcodes.p,
-                                                        e->d_toff.p, e->d_tlen.p, w);
-                    if (e->fplan.filter_only)   // no layout of the whole set: the chunks that need all W waves are compacted too
-                        sd::launch_fast_fill_wt_compact(e->fplan, st, e->dp_chunks, e->dp_bases2, e->dp_nmask, e->d_flane.p,
-                                                        e->sc, e->d_B.p, e->d_fckpt.p, e->d_fckbase.p, qfill + 2,
-                                                        ord + (size_t)(W - 1) * C, e->d_cls.p + (W - 1), e->n_cu,
-                                                        e->d_lanet.p, e->d_ftcodes.p, e->d_toff.p, e->d_tlen.p, W);
-                    else if (e->fplan.tiled)
-                        sd::launch_fast_fill_wt(e->fplan, st, e->dp_chunks, C, e->dp_bases2, e->dp_nmask, e->d_ftable.p,
-                                                e->d_flane.p, e->sc, e->d_B.p, e->d_fckpt.p, e->d_fckbase.p, qfill + 2,
-                                                ord + (size_t)(W - 1) * C, e->n_cu, e->d_cendoff.p, e->d_crank.p,
-                                                e->d_cls.p + (W - 1));
-                    else
-                    sd::launch_fast_fill_wn(e->fplan, st, e->dp_chunks, C, e->dp_bases2, e->dp_nmask, e->d_ftable.p,
-                                            e->d_flane.p, e->sc, e->d_B.p, e->d_fckpt.p, e->d_fckbase.p, qfill + 2,
-                                            ord + (size_t)(W - 1) * C, e->n_cu, e->d_cendoff.p, e->d_crank.p,
-                                            e->d_cls.p + (W - 1));
+                    for (int w = 1; w <= W; ++w) {
+                        sd::FillArgs cw = fa;   // class w; queue heads: class 1 the run's fill head, class W the third
+                        cw.queue = w == 1 ? qfill : w == W ? qfill + 2 : qfill + 1 + w;
+                        cw.order = ord + (size_t)(w - 1) * C;
+                        cw.n_ptr = e->d_cls.p + (w - 1);
+                        // (FastPlan::filter_only: no layout of the whole set, the chunks that need all W waves are compacted too)
+                        if (w < W || e->fplan.filter_only) sd::launch_fast_fill_compact(e->fplan, st, cw, w);
+                        else sd::launch_fast_fill(e->fplan, st, cw);
+                    }
                 } else
-                sd::launch_fast_fill(e->fplan, st, e->dp_chunks, C, e->dp_bases2, e->dp_nmask,
-                                     e->d_ftable.p, e->d_flane.p, e->sc, e->d_B.p, e->d_argB.p,
-                                     e->d_fckpt.p, e->d_fckbase.p, qfill, e->dp_order, e->n_cu,
-                                     ranked ? e->d_cendoff.p : nullptr, ranked ? e->d_crank.p : nullptr,
-                                     e->lds_gate ? 54 * 1024 : 0);
+                    sd::launch_fast_fill(e->fplan, st, fa, e->lds_gate ? 54 * 1024 : 0);
                 SD_HIP(hipEventRecord(e->ev_fill[1], st));
                 if (ts != st) SD_HIP(hipStreamWaitEvent(ts, e->ev_fill[1], 0));
                 SD_HIP(hipEventRecord(e->ev_trace[0], ts));
-                sd::launch_fast_trace(e->fplan, ts, e->dp_chunks, C, e->dp_bases2, e->dp_nmask,
-                                      e->d_fslot.p, e->d_ftcodes.p, e->d_flane.p, e->d_toff.p,
-                                      e->d_tlen.p, e->sc, e->d_B.p, e->d_argB.p, e->d_fckpt.p,
-                                      e->d_fckbase.p, e->d_recs.p, e->d_cnt.p, qtrace, e->dp_order,
-                                      e->n_cu, compact ? e->d_klist.p : nullptr, compact ? e->d_kpos.p : nullptr,
-                                      compact ? e->d_nkept.p : nullptr, e->fplan.tr2_ok ? e->d_ftr2.p : nullptr,
-                                      compact && e->fplan.tiled ? e->d_lanet.p : nullptr);
+                sd::TraceArgs ta{};
+                ta.chunks = e->dp_chunks; ta.n_chunks = C; ta.bases2 = e->dp_bases2; ta.nmask = e->dp_nmask;
+                ta.slot_of = e->d_fslot.p; ta.tcodes = e->d_ftcodes.p; ta.lane_consts = e->d_flane.p;
+                ta.toff = e->d_toff.p; ta.tlen = e->d_tlen.p; ta.sc = e->sc;
+                ta.B = e->d_B.p; ta.argV = e->d_argB.p; ta.ckpt = e->d_fckpt.p; ta.ckbase = e->d_fckbase.p;
+                ta.recs = e->d_recs.p; ta.rec_cnt = e->d_cnt.p; ta.queue = qtrace; ta.order = e->dp_order; ta.n_cu = e->n_cu;
+                ta.tr2_tab = e->fplan.tr2_ok ? e->d_ftr2.p : nullptr;
+                if (compact) { ta.klist = e->d_klist.p; ta.kpos = e->d_kpos.p; ta.nkept = e->d_nkept.p; ta.lane_t = fa.lane_t; }
+                sd::launch_fast_trace(e->fplan, ts, ta);
                 SD_HIP(hipEventRecord(e->ev_trace[1], ts));
                 e->fill_launches = 1;
             }

@@ -28,7 +28,7 @@
 
 #include "sd_fast.hpp"
 #include "sd_fast_dev.hpp"
-#include "sd_fast_fill.hpp"
+#include "sd_fast_launch.hpp"
 
 namespace sd {
 
@@ -384,7 +384,7 @@ bool fast_plan_build(const std::vector<std::string>& tseq, ScoreArgs sc, int max
     // the one with the fewest cell ops per row wins (2P + the FL level its lanes allow, see below)
     int P = 0, split = 0;
     std::vector<std::pair<int, int>> cand;   // (P, split)
-    for (int p : FAST_P_LIST) {
+    for (int p : FastP::v) {
         int used = 0, s = 0;
         while (s < T && used + ((int)tseq[s].size() + p - 1) / p <= 64) {
             used += ((int)tseq[s].size() + p - 1) / p;
@@ -403,7 +403,7 @@ bool fast_plan_build(const std::vector<std::string>& tseq, ScoreArgs sc, int max
     if (P == 0) {
         // wide layout: one template per virtual lane
         if (T <= 1024 && !has1)   // (a 1-bp template ends its lane at slot 0: the narrow and the tiled fills know that form)
-            for (int p : FAST_WIDE_P_LIST)
+            for (int p : FastWideP::v)
                 if (p >= Lmax) { P = p; break; }
         if (P != 0) {
             // (rounds 1-4 also refused (3 Lmax + 2 REBASE + 4) * max|score| > 8000 here, a bound from before the range proof
@@ -423,7 +423,7 @@ bool fast_plan_build(const std::vector<std::string>& tseq, ScoreArgs sc, int max
             int bestW = 0;
             int64_t best_cost = 0;
             const int force_p = getenv("SD_TILED_P") ? atoi(getenv("SD_TILED_P")) : 0;   // developer knob
-            for (int p : FAST_TILED_P_LIST) {
+            for (int p : FastTiledP::v) {
                 if (force_p && p != force_p) continue;
                 std::vector<int> v0((size_t)T, 0);
                 int cur = 0;
@@ -815,126 +815,122 @@ int64_t fast_ckpt_rows_total(const FastPlan& plan, std::vector<ChunkDesc>& chunk
 }
 
 // ---------------------------------------------------------------------------------------------
-// launch wrappers
+// launch: which fill kernel runs for a plan, with which geometry
 // ---------------------------------------------------------------------------------------------
-void launch_fast_fill(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                      const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                      const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV,
-                      uint32_t* ckpt, int32_t* ckbase, int* queue, const int* order, int n_cu,
-                      const uint32_t* cendoff, const uint32_t* crank, size_t min_lds) {
-    // 16 waves per CU either way (4 per SIMD): one workgroup of 16 when the launch fills the machine, else workgroups of 8
-    int nw = n_chunks >= SD_FILL_NW_MAX * n_cu ? SD_FILL_NW_MAX : 8;
-    if (const char* ev = getenv("SD_FILL_NW")) nw = atoi(ev) == 16 ? 16 : 8;   // developer knob
-    const int NW = nw;
-    int grid = std::min((n_chunks + NW - 1) / NW, (16 / NW) * n_cu);  // persistent
-    if (const char* ev = getenv("SD_FILL_GRID")) grid = std::max(1, atoi(ev));   // developer knob
-    // `queue` points at a zeroed work-queue head that no earlier launch has used (sd_engine hands out a fresh
-    // one per run): no memset kernel sits between the launches of a stream
-    if (plan.tiled) {
-        launch_fast_fill_wt(plan, st, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B, ckpt, ckbase, queue,
-                            order, n_cu, cendoff, crank);
-        return;
-    }
-    if (plan.wide && plan.waves > 1) {
-        launch_fast_fill_wn(plan, st, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B, ckpt, ckbase, queue,
-                            order, n_cu, cendoff, crank);
+uint32_t fast_fill_hx(const FastPlan& plan, int fl, int step) {
+    uint32_t hx = plan.Hx;
+    if (step > 0)
+        for (int b = 0; b < 5; ++b) {
+            uint32_t lv = 0;
+            while (lv < 3 && fl - (int)(lv + 1) * step >= std::max(1, plan.floor_sym[b])) ++lv;
+            hx |= lv << (22 + 2 * b);
+        }
+    return hx;
+}
+
+// the first floor level of the list that covers FastPlan::floor_slots and leaves two slots behind it; 0 = none
+template <int... L> static int floor_level(const FastPlan& plan, PList<L...>) {
+    for (int c : {L...})
+        if (plan.floor_slots >= 1 && plan.floor_slots <= c && c + 2 < plan.P) return c;
+    return 0;
+}
+
+// the multi-wave layouts' floor form: the start-term maximum in the first 48 slots (where it suffices) or in every slot
+static int multi_wave_fl(const FastPlan& plan) {
+    return !plan.full_floor && floor_level(plan, PList<48>()) ? 48 : plan.P;
+}
+
+// the narrow fill with the start-term maximum in every slot, fp16 and int16 cells (u16 cells: sd_fast_u16.hip)
+static void launch_fast_fill_full(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, bool one) {
+    with_p(FastP(), plan.P, [&](auto p) {
+        constexpr int P = decltype(p)::value;
+        with_bool(one, [&](auto on) {
+            if (plan.f16) launch_narrow<P, CF_F16, P, decltype(on)::value, 0>(st, a, grid, nw, lds, plan.Hx);
+            else launch_narrow<P, CF_I16, P, decltype(on)::value, 0>(st, a, grid, nw, lds, plan.Hx);
+        });
+    });
+}
+
+void launch_fast_fill(const FastPlan& plan, hipStream_t st, const FillArgs& a, size_t min_lds) {
+    const int P = plan.P, W = plan.waves;
+    if (plan.tiled || W > 1) {
+        // multi-wave layouts (sd_fast_wn_fill.hpp): two waves per SIMD (the register budget of the kernels), and the tiled
+        // one as many workgroups per CU as their LDS allows; int16 cells have the full kernels only
+        const size_t lds = ((size_t)W * (P / 16) * 512 + 64) * sizeof(uint32_t);
+        const int per_cu = std::max(1, plan.tiled ? std::min(8 / W, (int)((size_t)160 * 1024 / lds)) : 8 / W);
+        const int grid = std::min(a.n_chunks, per_cu * a.n_cu);
+        const int fl = multi_wave_fl(plan);
+        if (!plan.f16) (plan.tiled ? launch_fast_fill_wt_i16 : launch_fast_fill_wn_i16)(plan, st, a, grid, lds);
+        else if (plan.tiled) launch_fast_fill_wt(plan, st, a, grid, lds, fl);
+        else if (fl == 48) launch_fast_fill_wn_fl(plan, st, a, grid, lds);
+        else launch_fast_fill_wn(plan, st, a, grid, lds);
         return;
     }
     if (plan.wide) {
-        launch_fast_fill_wide(plan, st, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B, ckpt,
-                              ckbase, queue, order, n_cu, cendoff, crank);
+        // one template per virtual lane: 8 waves per workgroup, one workgroup per CU (LDS)
+        const int grid = std::min((a.n_chunks + 7) / 8, a.n_cu);
+        const size_t lds = (size_t)5 * (P / 16) * 512 * sizeof(uint32_t) + 128;   // + FairShare's words
+        const int fl = plan.f16 && !plan.full_floor ? floor_level(plan, FlWideLevels()) : 0;
+        if (fl) launch_fast_fill_wide_fl(plan, st, a, grid, lds, fl);
+        else launch_fast_fill_wide(plan, st, a, grid, lds);
         return;
     }
-    // min_lds (pipeline mode 2): ask for at least this much, so that a third workgroup never fits a CU
+    // narrow layout: 16 waves per CU either way (4 per SIMD), one workgroup of 16 when the launch fills the machine, else
+    // workgroups of 8
+    int nw = a.n_chunks >= SD_FILL_NW_MAX * a.n_cu ? SD_FILL_NW_MAX : 8;
+    if (const char* ev = getenv("SD_FILL_NW")) nw = atoi(ev) == 16 ? 16 : 8;   // developer knob
+    int grid = std::min((a.n_chunks + nw - 1) / nw, (16 / nw) * a.n_cu);  // persistent
+    if (const char* ev = getenv("SD_FILL_GRID")) grid = std::max(1, atoi(ev));   // developer knob
     const size_t lds = std::max((size_t)5 * plan.P4 * 64 * sizeof(uint32_t) + 128, min_lds);   // + FairShare's words
-    const bool ranked = cendoff != nullptr;
-#define SD_FILL_K(PP, RK, HF)                                                                        \
-    {                                                                                                \
-        if (has1) {                                                                                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sd_fast_fill<PP, RK, HF, PP, true>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
-            hipLaunchKernelGGL((sd_fast_fill<PP, RK, HF, PP, true>), dim3(grid), dim3(nw * 64), lds, st, chunks, \
-                               n_chunks, bases2, nmask, table, lane_consts, sc, plan.Hx, B, argV, ckpt, \
-                               ckbase, queue, order, cendoff, crank);                                \
-        } else {                                                                                     \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sd_fast_fill<PP, RK, HF>),      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
-            hipLaunchKernelGGL((sd_fast_fill<PP, RK, HF>), dim3(grid), dim3(nw * 64), lds, st, chunks, \
-                               n_chunks, bases2, nmask, table, lane_consts, sc, plan.Hx, B, argV, ckpt, \
-                               ckbase, queue, order, cendoff, crank);                                \
-        }                                                                                            \
-    }
-#define SD_FILL(PP)                                                                                  \
-    case PP:                                                                                         \
-        if (plan.f16) {                                                                              \
-            if (ranked) SD_FILL_K(PP, true, true) else SD_FILL_K(PP, false, true)                    \
-        } else {                                                                                     \
-            if (ranked) SD_FILL_K(PP, true, false) else SD_FILL_K(PP, false, false)                  \
-        }                                                                                            \
-        break;
-    // fp16 cells, 150-200 bp monomers: the variants that skip the dominated start-term maxima (sd_fast_fl.hip);
-    // FastPlan::full_floor (SD_FLAG_FULL_FLOOR) keeps the full kernel (developer A/B and the parity test of the two)
-    const bool has1 = ((plan.Hx >> 10) & 1) != 0;   // 1-bp templates: the full-floor kernels carry the FLC_ONE form
-    if (!plan.full_floor && !has1 &&
-        (plan.u16 ? (launch_fast_fill_fl_u16(plan, st, grid, nw, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B,
-                                             argV, ckpt, ckbase, queue, order, cendoff, crank) ||
-                     launch_fast_fill_fl_u16s(plan, st, grid, nw, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B,
-                                              argV, ckpt, ckbase, queue, order, cendoff, crank))
-         : plan.f16 ? launch_fast_fill_fl(plan, st, grid, nw, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B,
-                                          argV, ckpt, ckbase, queue, order, cendoff, crank)
-                    : launch_fast_fill_fl_i16(plan, st, grid, nw, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc,
-                                              B, argV, ckpt, ckbase, queue, order, cendoff, crank)))
-        return;
-    if (plan.u16) {   // the full-floor kernels of the biased-u16 cell format live in their own unit (sd_fast_u16.hip)
-        launch_fast_fill_full_u16(plan, st, grid, nw, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B, argV, ckpt,
-                                  ckbase, queue, order, cendoff, crank);
-        return;
-    }
-    switch (plan.P) {
-        SD_FILL(4) SD_FILL(8) SD_FILL(12) SD_FILL(16) SD_FILL(20) SD_FILL(24) SD_FILL(28) SD_FILL(30)
-        SD_FILL(31) SD_FILL(32) SD_FILL(33) SD_FILL(34) SD_FILL(35) SD_FILL(36) SD_FILL(37) SD_FILL(38)
-        SD_FILL(39) SD_FILL(40) SD_FILL(42) SD_FILL(44) SD_FILL(46) SD_FILL(48) SD_FILL(52) SD_FILL(56)
-        SD_FILL(60) SD_FILL(64)
-        default: break;
-    }
-#undef SD_FILL
-#undef SD_FILL_K
+    // cell format, then floor form: the kernels that skip the dominated start-term maxima behind the first FL slots of a lane
+    // (sd_fast_fl*.hip), else the full ones -- which alone carry the 1-bp form (FLC_ONE), and which FastPlan::full_floor
+    // (SD_FLAG_FULL_FLOOR: developer A/B, parity test) keeps
+    const bool one = fast_has_1bp(plan), lng = P > 40;
+    const int fl = plan.full_floor || one || P < 30 ? 0
+                 : plan.f16 || plan.u16 ? (lng ? floor_level(plan, FlLongLevels()) : floor_level(plan, FlLevels()))
+                                        : (lng ? floor_level(plan, FlLongI16Levels()) : floor_level(plan, FlI16Levels()));
+    if (fl && plan.u16 && plan.table_nonneg && !getenv("SD_FILL_ONE_LEVEL"))   // levels by read symbol (sd_fast_fill.hpp: FLS)
+        (lng ? launch_fast_fill_fl_long_u16 : launch_fast_fill_fl_u16)(plan, st, a, grid, nw, lds, fl);
+    else if (fl && plan.u16)   // one level for every row
+        (lng ? launch_fast_fill_fl_long_u16s : launch_fast_fill_fl_u16s)(plan, st, a, grid, nw, lds, fl);
+    else if (fl && plan.f16)
+        (lng ? launch_fast_fill_fl_long : launch_fast_fill_fl)(plan, st, a, grid, nw, lds, fl);
+    else if (fl)
+        launch_fast_fill_fl_i16(plan, st, a, grid, nw, lds, fl);
+    else if (plan.u16)
+        launch_fast_fill_full_u16(plan, st, a, grid, nw, lds, one);
+    else
+        launch_fast_fill_full(plan, st, a, grid, nw, lds, one);
 }
 
-void launch_fast_trace(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                       const uint32_t* bases2, const uint32_t* nmask, const uint32_t* slot_of,
-                       const uint8_t* tcodes, const uint32_t* lane_consts, const int32_t* toff,
-                       const int32_t* tlen, ScoreArgs sc, const int32_t* B, const int32_t* argV,
-                       const uint32_t* ckpt, const int32_t* ckbase, DevRec* recs,
-                       int32_t* rec_cnt, int* queue, const int* order, int n_cu, const uint16_t* klist,
-                       const uint16_t* kpos, const int32_t* nkept, const uint32_t* tr2_tab, const uint32_t* lane_t) {
+void launch_fast_fill_compact(const FastPlan& plan, hipStream_t st, const FillArgs& a, int wb) {
+    // two waves per SIMD, and as many workgroups per CU as their LDS allows
+    const size_t lds = ((size_t)wb * (plan.P / 16) * 512 + 64) * sizeof(uint32_t);
+    const int per_cu = std::max(1, std::min(8 / wb, (int)((plan.tiled ? (size_t)160 : 150) * 1024 / lds)));
+    if (plan.tiled) launch_fast_fill_wt_compact(plan, st, a, per_cu * a.n_cu, wb, lds, multi_wave_fl(plan));
+    else launch_fast_fill_wn_compact(plan, st, a, per_cu * a.n_cu, wb, lds, multi_wave_fl(plan));
+}
+
+void launch_fast_trace(const FastPlan& plan, hipStream_t st, const TraceArgs& a) {
     // the packed two-block form where the plan has it (one wave per chunk in the fill, templates <= 256 bp, 16-bit tagged range)
-    if (klist == nullptr && launch_fast_trace2(plan, st, chunks, n_chunks, bases2, nmask, lane_consts, tcodes, toff, tlen, sc,
-                                               B, ckpt, ckbase, tr2_tab, recs, rec_cnt, queue, order, n_cu))
+    if (a.klist == nullptr && plan.tr2_ok && a.tr2_tab != nullptr) {
+        launch_fast_trace2(plan, st, a);
         return;
+    }
     int bpc = 8;
     if (const char* ev = getenv("SD_TRACE_BPC")) bpc = std::max(1, atoi(ev));  // developer knob
-    int grid = std::min((n_chunks + 3) / 4, bpc * n_cu);  // persistent: 8 workgroups of 4 waves per CU
+    int grid = std::min((a.n_chunks + 3) / 4, bpc * a.n_cu);  // persistent: 8 workgroups of 4 waves per CU
     // long templates: one wave per workgroup; 16 cells per lane: 239 registers and 18 KB of LDS, two waves per SIMD (5.2 ->
     // 3.4 ms on five 1-kb monomers); 32 cells per lane: 412 registers, one
-    if (plan.Qk > 8) grid = std::min(n_chunks, (plan.Qk == 16 ? 8 : 4) * n_cu);
+    if (plan.Qk > 8) grid = std::min(a.n_chunks, (plan.Qk == 16 ? 8 : 4) * a.n_cu);
     if (const char* ev = getenv("SD_TRACE_GRID")) grid = std::max(1, atoi(ev));   // developer knob
-#define SD_TRACE(QQ)                                                                              \
-    hipLaunchKernelGGL(sd_fast_trace<QQ>, dim3(grid), dim3(64 * trace_waves_per_group(QQ)), 0, st, chunks, n_chunks, bases2, \
-                       nmask, slot_of, tcodes, lane_consts, toff, tlen, sc, plan.P, B, argV, ckpt, \
-                       ckbase, recs, rec_cnt, queue, order, plan.u16 ? 2 : plan.f16 ? 1 : 0, plan.bshift, plan.waves, klist, kpos, \
-                       nkept, plan.filter_only ? -plan.T : plan.T, lane_t)
-    switch (plan.Qk) {
-        case 1: SD_TRACE(1); break;
-        case 2: SD_TRACE(2); break;
-        case 3: SD_TRACE(3); break;
-        case 4: SD_TRACE(4); break;
-        case 6: SD_TRACE(6); break;
-        case 8: SD_TRACE(8); break;
-        case 16: SD_TRACE(16); break;
-        default: SD_TRACE(32); break;
-    }
-#undef SD_TRACE
+    with_p(PList<1, 2, 3, 4, 6, 8, 16, 32>(), plan.Qk, [&](auto q) {
+        constexpr int QK = decltype(q)::value;
+        hipLaunchKernelGGL(sd_fast_trace<QK>, dim3(grid), dim3(64 * trace_waves_per_group(QK)), 0, st, a.chunks, a.n_chunks,
+                           a.bases2, a.nmask, a.slot_of, a.tcodes, a.lane_consts, a.toff, a.tlen, a.sc, plan.P, a.B, a.argV,
+                           a.ckpt, a.ckbase, a.recs, a.rec_cnt, a.queue, a.order, plan.u16 ? 2 : plan.f16 ? 1 : 0, plan.bshift,
+                           plan.waves, a.klist, a.kpos, a.nkept, plan.filter_only ? -plan.T : plan.T, a.lane_t);
+    });
 }
 
 }  // namespace sd

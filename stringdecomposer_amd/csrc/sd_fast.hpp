@@ -13,6 +13,7 @@
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sd_device.hpp"
@@ -45,8 +46,16 @@ struct FastPlan {
     int P = 0;            // slots per virtual lane
     int P4 = 0;           // P rounded up to a multiple of 4 (LDS table row)
     int H = 0;            // carry hops of the cross-lane chain: Vmax-1
-    int Hx = 0;           // what the narrow fills get: H | (carry scan through ds_bpermute) << 8 | (scan form in the last
-                          // round too, developer A/B) << 9 | (the set has 1-bp templates) << 10 | idle lane << 16
+    // what the narrow fills get as their `int Hx` (the same bits):
+    //   bits 0..7    H
+    //   bit 8        the carry scan takes its shifted operands from ds_bpermute (both planes segment alike, bits 16..21)
+    //   bit 9        ... in the last round too (developer A/B: SD_FILL_BPERM_TAIL)
+    //   bit 10       the set has 1-bp templates (FLC_ONE: fast_has_1bp)
+    //   bit 11       rebase every 64 rows instead of 128 (FastPlan::rebase)
+    //   bits 16..21  with bit 8: a virtual lane that is idle in both planes
+    //   bits 22..31  0 in the plan; the u16 fills with floor levels by read symbol get two bits per symbol A C G T N there,
+    //                level l = the start-term maximum in the first FL - l * step slots (fast_fill_hx; sd_fast_fill.hpp: FLS)
+    uint32_t Hx = 0;
     int T = 0;
     int split = 0;        // templates [0,split) in the lo plane
     int Lmax = 0;
@@ -82,16 +91,30 @@ struct FastPlan {
 
 // the tables of sd_fast_trace_pk for a built narrow plan (tr2_ok = false when it does not apply)
 void fast_plan_trace2(const std::vector<std::string>& tseq, ScoreArgs sc, FastPlan& plan);
-bool launch_fast_trace2(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks, const uint32_t* bases2,
-                        const uint32_t* nmask, const uint32_t* lane_consts, const uint8_t* tcodes, const int32_t* toff,
-                        const int32_t* tlen, ScoreArgs sc, const int32_t* B, const uint32_t* ckpt, const int32_t* ckbase,
-                        const uint32_t* tr2_tab, DevRec* recs, int32_t* rec_cnt, int* queue, const int* order, int n_cu);
 
-// slots-per-virtual-lane values the fill kernels are instantiated for
-static const int FAST_P_LIST[] = {4, 8, 12, 16, 20, 24, 28, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39,
-                                  40, 42, 44, 46, 48, 52, 56, 60, 64};
-static const int FAST_WIDE_P_LIST[] = {80, 96, 112, 128, 144, 160, 176, 192, 208, 224};
-static const int FAST_TILED_P_LIST[] = {96, 128, 160, 192, 224};   // slots per lane of the tiled multi-wave layout
+// the set has 1-bp templates (FastPlan::Hx bit 10): only the full narrow fills and the tiled ones know that form
+inline bool fast_has_1bp(const FastPlan& plan) { return (plan.Hx >> 10) & 1; }
+
+// The values a kernel template is instantiated for.  with_p(List(), v, f) calls f(std::integral_constant<int, v>()) when v
+// is in the list, else nothing: a launcher maps a run-time P or floor level onto the template argument with it.
+template <int... Vs> struct PList { static constexpr int v[] = {Vs...}; };
+template <int... Vs, typename F> void with_p(PList<Vs...>, int v, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+template <typename F> void with_bool(bool b, F&& f) { b ? f(std::true_type()) : f(std::false_type()); }
+
+// slots per virtual lane: the narrow layout, the P of its FL kernels (P <= 40, P > 40), the wide and the tiled layouts
+using FastP = PList<4, 8, 12, 16, 20, 24, 28, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 42, 44, 46, 48, 52, 56, 60, 64>;
+using FastFlP = PList<30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40>;
+using FastFlLongP = PList<42, 44, 46, 48, 52, 56, 60, 64>;
+using FastWideP = PList<80, 96, 112, 128, 144, 160, 176, 192, 208, 224>;
+using FastTiledP = PList<96, 128, 160, 192, 224>;
+// floor levels FL of the FL kernels: narrow fp16 / u16 cells (P <= 40, P > 40), narrow int16 cells (the same), wide layout
+using FlLevels = PList<12, 16, 20, 24, 28>;
+using FlLongLevels = PList<16, 24, 32>;
+using FlI16Levels = PList<16, 24>;
+using FlLongI16Levels = PList<24>;
+using FlWideLevels = PList<32, 64>;
 
 // Builds the plan; returns false (with the reason) when the fast family cannot represent the
 // input exactly (then the generic family is used).
@@ -122,120 +145,102 @@ void launch_split_order(hipStream_t st, const int* order, int n, const int32_t* 
 // number of checkpoint rows of the batch; fills ChunkDesc::pad with each chunk's first checkpoint
 int64_t fast_ckpt_rows_total(const FastPlan& plan, std::vector<ChunkDesc>& chunks);
 
-void launch_fast_fill(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                      const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                      const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV,
-                      uint32_t* ckpt, int32_t* ckbase, int* queue, const int* order, int n_cu,
-                      const uint32_t* cendoff, const uint32_t* crank, size_t min_lds = 0);
+// Operands of one batch's fill.  Every fill launcher takes (plan, stream, FillArgs) and, beside them, only what its
+// chooser decides (launch_fast_fill, launch_fast_fill_compact: sd_fast.hip): the launch geometry -- grid, nw (or wb) waves
+// per workgroup, lds bytes -- and the kernel form -- fl = the floor level (P: the full kernel), one = the 1-bp form.
+struct FillArgs {
+    const ChunkDesc* chunks;
+    int n_chunks;                      // (where n_ptr is set: the bound the launch geometry is sized by)
+    const int* n_ptr = nullptr;        // the number of chunks lives on the device (order = a class list of launch_split_order)
+    const uint32_t* bases2;
+    const uint32_t* nmask;
+    const uint32_t* table;             // FastPlan::table on the device
+    const uint32_t* lane_consts;
+    ScoreArgs sc;
+    int32_t* B;
+    int32_t* argV;
+    uint32_t* ckpt;
+    int32_t* ckbase;
+    int* queue;                        // a zeroed work-queue head that no earlier launch has used: no memset between launches
+    const int* order;
+    int n_cu;
+    const uint32_t* cendoff = nullptr; // --ed_thr: per-chunk end offsets and ranks (the RANKED kernels)
+    const uint32_t* crank = nullptr;
+    // the compacted classes of --ed_thr: a chunk's kept templates, one per lane (klist) or over the lanes of the tiled
+    // layout (lane_t: sd_tiled_place), and the templates' codes, offsets and lengths
+    const uint16_t* klist = nullptr;
+    const uint32_t* lane_t = nullptr;
+    const uint8_t* tcodes = nullptr;
+    const int32_t* toff = nullptr;
+    const int32_t* tlen = nullptr;
+};
 
-// variants with the start-term maximum in the first slots of a lane only (sd_fast_fl.hip); false = not covered
-bool launch_fast_fill_fl(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                         int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                         const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                         int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                         const uint32_t* crank);
+// Operands of one batch's traceback (launch_fast_trace)
+struct TraceArgs {
+    const ChunkDesc* chunks;
+    int n_chunks;
+    const uint32_t* bases2;
+    const uint32_t* nmask;
+    const uint32_t* slot_of;
+    const uint8_t* tcodes;
+    const uint32_t* lane_consts;
+    const int32_t* toff;
+    const int32_t* tlen;
+    ScoreArgs sc;
+    const int32_t* B;
+    const int32_t* argV;
+    const uint32_t* ckpt;
+    const int32_t* ckbase;
+    DevRec* recs;
+    int32_t* rec_cnt;
+    int* queue;
+    const int* order;
+    int n_cu;
+    const uint32_t* tr2_tab = nullptr; // device copy of FastPlan::tr2_tab: the packed two-block form where it applies
+    // chunks filled in the compacted form: kept templates, their places and count per chunk; the tiled layout's lane table
+    // (kpos = first lanes then; FastPlan::filter_only: every chunk is one, or skipped)
+    const uint16_t* klist = nullptr;
+    const uint16_t* kpos = nullptr;
+    const int32_t* nkept = nullptr;
+    const uint32_t* lane_t = nullptr;
+};
 
-// the same for the biased-u16 cell format (sd_fast_fl_u16.hip, sd_fast_fl_long_u16.hip) and its full-floor kernels (sd_fast_u16.hip)
-bool launch_fast_fill_fl_u16(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                             int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                             const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                             int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                             const uint32_t* crank);
-bool launch_fast_fill_fl_long_u16(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                                  int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                                  const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                                  int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                                  const uint32_t* crank);
-// the u16 kernels with ONE floor level for every row (scorings with a negative table value: sd_fast_fl_u16s.hip)
-bool launch_fast_fill_fl_u16s(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                              int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                              const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                              int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                              const uint32_t* crank);
-bool launch_fast_fill_fl_long_u16s(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                                   int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                                   const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                                   int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                                   const uint32_t* crank);
-void launch_fast_fill_full_u16(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                               int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                               const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                               int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                               const uint32_t* crank);
+// The fill of one batch: chooses the kernel -- layout, cell format, floor form -- and its launch geometry (min_lds,
+// pipeline mode 2: what the narrow fills ask for at least, so that a third workgroup never fits a CU)
+void launch_fast_fill(const FastPlan& plan, hipStream_t st, const FillArgs& a, size_t min_lds = 0);
+// --ed_thr, multi-wave layouts: one class of chunks (a.order, a.n_ptr) filled by wb waves holding their kept templates
+void launch_fast_fill_compact(const FastPlan& plan, hipStream_t st, const FillArgs& a, int wb);
+// the Hx of a narrow FL launch: FastPlan::Hx and, for step > 0, the floor level of every read symbol in bits 22..31
+uint32_t fast_fill_hx(const FastPlan& plan, int fl, int step);
 
-bool launch_fast_fill_fl_i16(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                             int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                             const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                             int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                             const uint32_t* crank);
-bool launch_fast_fill_fl_long(const FastPlan& plan, hipStream_t st, int grid, int nw, size_t lds, const ChunkDesc* chunks,
-                              int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                              const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, int32_t* argV, uint32_t* ckpt,
-                              int32_t* ckbase, int* queue, const int* order, const uint32_t* cendoff,
-                              const uint32_t* crank);
+// The kernels of one family at plan.P, launched by the two choosers above.
+// Narrow layout, the start-term maximum in the first fl slots of a lane only: fp16 cells (sd_fast_fl.hip: P <= 40,
+// sd_fast_fl_long.hip: P > 40), u16 cells with levels by read symbol (_u16) or one level (_u16s), int16 cells (_i16)
+void launch_fast_fill_fl(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+void launch_fast_fill_fl_long(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+void launch_fast_fill_fl_u16(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+void launch_fast_fill_fl_long_u16(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+void launch_fast_fill_fl_u16s(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+void launch_fast_fill_fl_long_u16s(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+void launch_fast_fill_fl_i16(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl);
+// ... and in every slot, u16 cells (sd_fast_u16.hip; fp16 and int16 cells: sd_fast.hip)
+void launch_fast_fill_full_u16(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, bool one);
+// wide layout: every slot (sd_fast_wide.hip), fp16 cells with fl = 32 / 64 (sd_fast_wide_fl.hip)
+void launch_fast_fill_wide(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds);
+void launch_fast_fill_wide_fl(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds, int fl);
+// multi-wave layouts, plan.waves waves per workgroup: wide (sd_fast_wn.hip, sd_fast_wn_fl.hip: fl = 48) and tiled
+// (sd_fast_wt.hip: fl = 48 or P) with fp16 cells, both with int16 cells (sd_fast_wn_i16.hip)
+void launch_fast_fill_wn(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds);
+void launch_fast_fill_wn_fl(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds);
+void launch_fast_fill_wt(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds, int fl);
+void launch_fast_fill_wn_i16(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds);
+void launch_fast_fill_wt_i16(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds);
+// their compacted forms, wb waves per workgroup (sd_fast_wn_ck.hip, sd_fast_wt.hip): fl = 48 or P
+void launch_fast_fill_wn_compact(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int wb, size_t lds, int fl);
+void launch_fast_fill_wt_compact(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int wb, size_t lds, int fl);
 
-// wide variant (sd_fast_wide.hip), called by launch_fast_fill when plan.wide
-void launch_fast_fill_wide(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                           const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                           const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, uint32_t* ckpt,
-                           int32_t* ckbase, int* queue, const int* order, int n_cu,
-                           const uint32_t* cendoff, const uint32_t* crank);
-
-bool launch_fast_fill_wide_fl(const FastPlan& plan, hipStream_t st, int grid, size_t lds, const ChunkDesc* chunks,
-                              int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                              const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase,
-                              int* queue, const int* order, const uint32_t* cendoff, const uint32_t* crank);
-
-// multi-wave wide variant (sd_fast_wn.hip): more than 128 templates, W = plan.waves waves per chunk
-void launch_fast_fill_wn(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                         const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                         const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase,
-                         int* queue, const int* order, int n_cu, const uint32_t* cendoff, const uint32_t* crank,
-                         const int* n_ptr = nullptr);   // n_ptr: the number of chunks lives on the device (order = a class list)
-// tiled multi-wave variant (sd_fast_wt.hip): templates over consecutive virtual lanes, W = plan.waves >= 1 waves per chunk
-void launch_fast_fill_wt(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                         const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                         const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase,
-                         int* queue, const int* order, int n_cu, const uint32_t* cendoff, const uint32_t* crank,
-                         const int* n_ptr = nullptr);   // n_ptr: the number of chunks lives on the device (order = a class list)
-// --ed_thr on the tiled layout: one class of chunks, filled by wb waves holding their kept templates (lane_t: sd_tiled_place)
-void launch_fast_fill_wt_compact(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, const uint32_t* bases2,
-                                 const uint32_t* nmask, const uint32_t* lane_consts, ScoreArgs sc, int32_t* B,
-                                 uint32_t* ckpt, int32_t* ckbase, int* queue, const int* order_w, const int* n_ptr,
-                                 int n_cu, const uint32_t* lane_t, const uint8_t* tcodes, const int32_t* toff,
-                                 const int32_t* tlen, int wb);
-// --ed_thr, more than 128 templates: one class of chunks, filled by wb waves holding their kept templates (sd_fast_wn_ck.hip)
-void launch_fast_fill_wn_compact(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, const uint32_t* bases2,
-                                 const uint32_t* nmask, const uint32_t* lane_consts, ScoreArgs sc, int32_t* B,
-                                 uint32_t* ckpt, int32_t* ckbase, int* queue, const int* order_w, const int* n_ptr,
-                                 int n_cu, const uint16_t* klist, const uint8_t* tcodes, const int32_t* toff,
-                                 const int32_t* tlen, int wb);   // wb: waves per chunk of this class
-
-// the same two layouts with int16 cells / int8 table bytes (sd_fast_wn_i16.hip): plan.f16 == false
-bool launch_fast_fill_wn_i16(const FastPlan& plan, hipStream_t st, int grid, size_t lds, const ChunkDesc* chunks, int n_chunks,
-                             const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table, const uint32_t* lane_consts,
-                             ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase, int* queue, const int* order,
-                             const uint32_t* cendoff, const uint32_t* crank, const int* n_ptr);
-bool launch_fast_fill_wt_i16(const FastPlan& plan, hipStream_t st, int grid, size_t lds, const ChunkDesc* chunks, int n_chunks,
-                             const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table, const uint32_t* lane_consts,
-                             ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase, int* queue, const int* order,
-                             const uint32_t* cendoff, const uint32_t* crank, const int* n_ptr);
-
-bool launch_fast_fill_wn_fl(const FastPlan& plan, hipStream_t st, int grid, size_t lds, const ChunkDesc* chunks,
-                            int n_chunks, const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                            const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase,
-                            int* queue, const int* order, const uint32_t* cendoff, const uint32_t* crank,
-                            const int* n_ptr = nullptr);
-
-void launch_fast_trace(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                       const uint32_t* bases2, const uint32_t* nmask, const uint32_t* slot_of,
-                       const uint8_t* tcodes, const uint32_t* lane_consts, const int32_t* toff,
-                       const int32_t* tlen, ScoreArgs sc, const int32_t* B, const int32_t* argV,
-                       const uint32_t* ckpt, const int32_t* ckbase, DevRec* recs,
-                       int32_t* rec_cnt, int* queue, const int* order, int n_cu,
-                       const uint16_t* klist = nullptr, const uint16_t* kpos = nullptr, const int32_t* nkept = nullptr,
-                       const uint32_t* tr2_tab = nullptr,   // device copy of FastPlan::tr2_tab: the packed two-block form where it applies
-                       const uint32_t* lane_t = nullptr);   // compacted tiled chunks: the lane table (kpos = first lanes then;
-                                                            // FastPlan::filter_only: every chunk is one, or skipped)
+// The traceback of one batch: the packed two-block form (sd_fast_trace2.hip) where the plan has it, else sd_fast_trace
+void launch_fast_trace(const FastPlan& plan, hipStream_t st, const TraceArgs& a);
+void launch_fast_trace2(const FastPlan& plan, hipStream_t st, const TraceArgs& a);
 
 }  // namespace sd

@@ -4,6 +4,4 @@
 #define SD_FL_CF CF_U16
 #define SD_FL_STEP 0
 #define SD_FL_ENTRY launch_fast_fill_fl_u16s
-#define SD_FL_ENTRY_LONG launch_fast_fill_fl_long_u16s
-#define SD_FL_TAKES(plan) ((plan).u16)
 #include "sd_fast_fl.hip"

@@ -405,29 +405,19 @@ void fast_plan_trace2(const std::vector<std::string>& tseq, ScoreArgs sc, FastPl
     plan.tr2_ok = true;
 }
 
-bool launch_fast_trace2(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks, const uint32_t* bases2,
-                        const uint32_t* nmask, const uint32_t* lane_consts, const uint8_t* tcodes, const int32_t* toff,
-                        const int32_t* tlen, ScoreArgs sc, const int32_t* B, const uint32_t* ckpt, const int32_t* ckbase,
-                        const uint32_t* tr2_tab, DevRec* recs, int32_t* rec_cnt, int* queue, const int* order, int n_cu) {
-    if (!plan.tr2_ok || tr2_tab == nullptr) return false;
+void launch_fast_trace2(const FastPlan& plan, hipStream_t st, const TraceArgs& a) {
     int bpc = 26;
     if (const char* ev = getenv("SD_TRACE_BPC")) bpc = std::max(1, atoi(ev));  // developer knob
-    int grid = std::min((n_chunks + TR2_NWV - 1) / TR2_NWV, bpc * n_cu);     // persistent: as many one-wave workgroups as the LDS of a CU holds
+    int grid = std::min((a.n_chunks + TR2_NWV - 1) / TR2_NWV, bpc * a.n_cu);   // persistent: as many one-wave workgroups as the LDS of a CU holds
     if (const char* ev = getenv("SD_TRACE_GRID")) grid = std::max(1, atoi(ev));
     int margin = 3;
     if (const char* ev = getenv("SD_TRACE_MARGIN")) margin = atoi(ev);        // developer knob: when block B is skipped
-#define SD_TRACE2(QQ)                                                                                              \
-    hipLaunchKernelGGL(sd_fast_trace_pk<QQ>, dim3(grid), dim3(64 * TR2_NWV), 0, st, chunks, n_chunks, bases2, nmask, \
-                       lane_consts, tcodes, toff, tlen, sc, plan.P, B, ckpt, ckbase, tr2_tab, recs, rec_cnt, queue,  \
-                       order, plan.u16 ? 2 : plan.f16 ? 1 : 0, plan.bshift, margin, plan.tr2_xlim)
-    switch (plan.tr2_qm) {
-        case 1: SD_TRACE2(1); break;
-        case 2: SD_TRACE2(2); break;
-        case 3: SD_TRACE2(3); break;
-        default: SD_TRACE2(4); break;
-    }
-#undef SD_TRACE2
-    return true;
+    with_p(PList<1, 2, 3, 4>(), plan.tr2_qm, [&](auto q) {
+        hipLaunchKernelGGL(sd_fast_trace_pk<decltype(q)::value>, dim3(grid), dim3(64 * TR2_NWV), 0, st, a.chunks, a.n_chunks,
+                           a.bases2, a.nmask, a.lane_consts, a.tcodes, a.toff, a.tlen, a.sc, plan.P, a.B, a.ckpt, a.ckbase,
+                           a.tr2_tab, a.recs, a.rec_cnt, a.queue, a.order, plan.u16 ? 2 : plan.f16 ? 1 : 0, plan.bshift, margin,
+                           plan.tr2_xlim);
+    });
 }
 
 }  // namespace sd

@@ -17,48 +17,15 @@
 //
 // Outputs as sd_fast_fill_wide (checkpoints every FAST_R rows: [checkpoint][wave][P][64]; one word per
 // row, here (B_i << 10) | (wave << 7 | virtual lane)) -> the same traceback kernel (bshift = 10).
-#include "sd_fast_wn_fill.hpp"
+#include "sd_fast_launch.hpp"
 
 namespace sd {
 
-void launch_fast_fill_wn(const FastPlan& plan, hipStream_t st, const ChunkDesc* chunks, int n_chunks,
-                         const uint32_t* bases2, const uint32_t* nmask, const uint32_t* table,
-                         const uint32_t* lane_consts, ScoreArgs sc, int32_t* B, uint32_t* ckpt, int32_t* ckbase,
-                         int* queue, const int* order, int n_cu, const uint32_t* cendoff, const uint32_t* crank,
-                         const int* n_ptr) {
-    const int W = plan.waves;
-    const int per_cu = std::max(1, 8 / W);          // 213 VGPRs: two waves per SIMD, eight per CU
-    const int grid = std::min(n_chunks, per_cu * n_cu);
-    const size_t lds = ((size_t)W * (plan.P / 16) * 512 + 64) * sizeof(uint32_t);
-    const bool ranked = cendoff != nullptr;
-    if (!plan.f16) {   // integer cells (sd_fast_wn_i16.hip)
-        (void)launch_fast_fill_wn_i16(plan, st, grid, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B, ckpt, ckbase,
-                                      queue, order, cendoff, crank, n_ptr);
-        return;
-    }
-    if (!plan.full_floor &&
-        launch_fast_fill_wn_fl(plan, st, grid, lds, chunks, n_chunks, bases2, nmask, table, lane_consts, sc, B, ckpt,
-                               ckbase, queue, order, cendoff, crank, n_ptr))
-        return;
-#define SD_FILLWN_K(PP, RK)                                                                                      \
-    {                                                                                                            \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sd_fast_fill_wn<PP, RK>),                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        hipLaunchKernelGGL((sd_fast_fill_wn<PP, RK>), dim3(grid), dim3(W * 64), lds, st, chunks, n_chunks, bases2, \
-                           nmask, table, lane_consts, sc, W, plan.bf8_match, plan.bf8_mismatch, B, ckpt, ckbase,  \
-                           queue, order, cendoff, crank, n_ptr, nullptr, nullptr, nullptr, nullptr, 0);             \
-    }
-#define SD_FILLWN(PP)                                                   \
-    case PP:                                                            \
-        if (ranked) SD_FILLWN_K(PP, true) else SD_FILLWN_K(PP, false)   \
-        break;
-    switch (plan.P) {
-        SD_FILLWN(80) SD_FILLWN(96) SD_FILLWN(112) SD_FILLWN(128) SD_FILLWN(144) SD_FILLWN(160)
-        SD_FILLWN(176) SD_FILLWN(192) SD_FILLWN(208) SD_FILLWN(224)
-        default: break;
-    }
-#undef SD_FILLWN
-#undef SD_FILLWN_K
+void launch_fast_fill_wn(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, size_t lds) {
+    with_p(FastWideP(), plan.P, [&](auto p) {
+        constexpr int P = decltype(p)::value;
+        launch_wn<P, P, false, false, true>(plan, st, a, grid, plan.waves, lds);
+    });
 }
 
 }  // namespace sd
