@@ -42,24 +42,6 @@ PinPool g_pinpool;
 }  // namespace sdi
 
 
-namespace {
-
-int device_count_checked() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-void ensure_events(std::vector<hipEvent_t>& v, size_t pairs) {
-    while (v.size() < 2 * pairs) {
-        hipEvent_t e;
-        SD_HIP(hipEventCreate(&e));
-        v.push_back(e);
-    }
-}
-
-}  // namespace
-
 // Developer overrides of sd_params.reserved[] from the environment, read HERE and nowhere else (the switches are part
 // of the parameters; the variables exist so that a test or an A/B run can flip one without touching the caller):
 // SD_PIPE_MODE=0|1|2, SD_FILL_CELLS=i16, SD_FILL_FULLFLOOR=1, SD_EDTHR_COMPACT=0, SD_FILTER_GENERAL=1, SD_IDENT_STREAM=0, SD_TRACE=1,
@@ -80,7 +62,22 @@ void apply_env_overrides(sd_params& p) {
         if (const char* ev = getenv("SD_F16_GUARD")) p.reserved[2] = std::max(0, atoi(ev));
 }
 
+
 namespace {
+
+int device_count_checked() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+void ensure_events(std::vector<hipEvent_t>& v, size_t count, unsigned flags = hipEventDefault) {
+    while (v.size() < count) {
+        hipEvent_t e;
+        SD_HIP(hipEventCreateWithFlags(&e, flags));
+        v.push_back(e);
+    }
+}
 
 // Everything must stay above the reference's INF = -1e6 sentinel (main.cpp:156), which makes its
 // `> INF` guards vacuous, and below 2^24 so that its float arithmetic on scores is exact.
@@ -94,6 +91,52 @@ int check_score_range(const sd_params& p, int Lmax, std::string& err) {
         return SD_ERR_UNSUPPORTED;
     }
     return SD_OK;
+}
+
+// What a monomer set and a scoring come to on the host, before any device call: the engine's reduced scores (score_scale,
+// sc) and its template set (tseq: the monomers, then their reverse complements, main.cpp:364-371; tlen, toff, T, sumL,
+// Lmax).  sd_engine_create starts from it, and sd_plan_info on an engine that never meets a device, so the plan a test
+// without a GPU sees is the engine's.  SD_OK, or the code and text of the first monomer that is empty, has a symbol
+// outside the alphabet or no complement.
+int host_templates(sd_engine* e, const sd_params& p, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono, std::string& err) {
+    // A common factor of the four scores scales every DP value, every difference and every tie alike:
+    // the device works with the reduced scores (more scorings fit the packed fp16 / int16 cells) and
+    // the record scores are multiplied back when they are fetched.
+    auto gcd = [](int a, int b) { a = a < 0 ? -a : a; b = b < 0 ? -b : b; while (b) { const int t = a % b; a = b; b = t; } return a; };
+    const int g = std::max(1, gcd(gcd(p.ins, p.del), gcd(p.mismatch, p.match)));
+    e->score_scale = g;
+    e->sc = sd::ScoreArgs{p.ins / g, p.del / g, p.mismatch / g, p.match / g};
+    e->T = 2 * n_mono;
+    e->tseq.resize((size_t)e->T);
+    for (int j = 0; j < n_mono; ++j) {
+        if (mono_lens[j] <= 0) { err = "ERROR: empty monomer sequence"; return SD_ERR_EMPTY; }
+        e->tseq[j].assign(mono_seqs[j], (size_t)mono_lens[j]);
+        const int rc = sd::check_alphabet("<monomer>", mono_seqs[j], mono_lens[j], err);
+        if (rc) return rc;
+        if (!sd::reverse_complement(e->tseq[j], e->tseq[(size_t)n_mono + j])) { err = "map::at"; return SD_ERR_SYMBOL; }
+    }
+    e->tlen.resize((size_t)e->T);
+    e->toff.resize((size_t)e->T + 1);
+    for (int j = 0; j < e->T; ++j) {
+        e->tlen[j] = (int32_t)e->tseq[j].size();
+        e->toff[j + 1] = e->toff[j] + e->tlen[j];
+        e->Lmax = std::max(e->Lmax, (int)e->tlen[j]);
+    }
+    e->sumL = e->toff[e->T];
+    return SD_OK;
+}
+
+// The fast family's layout plan of a template set: sd_params.reserved[1] (after apply_env_overrides) as the arguments of
+// fast_plan_build.  allow_f16 = false: no fp16 cell format; allow_tr2 = false: no packed two-block traceback.
+bool plan_fast_family(const sd_params& p, const std::vector<std::string>& tseq, sd::ScoreArgs sc, bool allow_f16, bool allow_tr2,
+                      sd::FastPlan& plan, std::string& why) {
+    return sd::fast_plan_build(tseq, sc, p.part_size + p.overlap, plan, why, allow_f16 && !(p.reserved[1] & SD_FLAG_NO_F16), allow_tr2,
+                               p.ed_thr > -1 && !(p.reserved[1] & SD_FLAG_NO_EDTHR_COMPACT), !(p.reserved[1] & SD_FLAG_NO_U16));
+}
+
+// the "cells" code of a plan's layout and cell format (sd_plan_info [2], sd_engine_info [4] >> 8)
+int layout_code(const sd::FastPlan& f) {
+    return f.tiled ? (f.f16 ? 6 : 8) : f.waves > 1 ? (f.f16 ? 5 : 7) : f.wide ? (f.f16 ? 4 : 3) : f.u16 ? 9 : f.f16 ? 2 : 1;
 }
 
 void build_generic_tables(sd_engine* e) {
@@ -137,12 +180,9 @@ static int engine_pick_family(sd_engine* e, bool allow_f16, std::string& err) {
     const sd_params* p = &e->p;
     int family = p->kernel;
     std::string why;
-    const bool no_f16 = !allow_f16 || (p->reserved[1] & SD_FLAG_NO_F16);
     // the packed two-block traceback unless switched off, and not after a range guard tripped (its own check raises the same flag)
     const bool tr2 = allow_f16 && !(p->reserved[1] & SD_FLAG_TRACE_V1);
-    const bool fast_ok = sd::fast_plan_build(e->tseq, e->sc, p->part_size + p->overlap, e->fplan, why, !no_f16, tr2,
-                                             p->ed_thr > -1 && !(p->reserved[1] & SD_FLAG_NO_EDTHR_COMPACT),
-                                             !(p->reserved[1] & SD_FLAG_NO_U16));
+    const bool fast_ok = plan_fast_family(*p, e->tseq, e->sc, allow_f16, tr2, e->fplan, why);
     e->fplan.full_floor = (p->reserved[1] & SD_FLAG_FULL_FLOOR) != 0;
     e->sc.rebase_mask = fast_ok ? e->fplan.rebase - 1 : 127;
     if (family == 0) family = fast_ok ? 2 : 1;
@@ -180,197 +220,12 @@ static int engine_pick_family(sd_engine* e, bool allow_f16, std::string& err) {
     return SD_OK;
 }
 
-extern "C" {
-
-void sd_params_default(sd_params* p) {
-    std::memset(p, 0, sizeof *p);
-    p->ins = -1; p->del = -1; p->mismatch = -1; p->match = 1;
-    p->part_size = 5000; p->overlap = 500; p->ed_thr = -1; p->threads = 1; p->device = 0;
-    p->kernel = 0;
-}
-
-const char* sd_version(void) { return "stringdecomposer_amd 0.1.0 (gfx950)"; }
-
-int sd_device_count(void) { return device_count_checked(); }
-
-void sd_free(void* p) { std::free(p); }
-
-// Host only: the layout the fast kernel family would use for a monomer set and scoring -- what sd_engine_create
-// decides before it touches the device.  For tests without a GPU and for users who want to know which kernels a
-// set will run on.
-int sd_plan_info(const sd_params* p, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
-                 int64_t info[8], char* errbuf, size_t errlen) {
-    std::string err;
-    int rc = validate_params(p, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    if (n_mono <= 0 || !mono_seqs || !mono_lens || !info) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
-    auto gcd = [](int a, int b) { a = a < 0 ? -a : a; b = b < 0 ? -b : b; while (b) { const int t = a % b; a = b; b = t; } return a; };
-    int g = gcd(gcd(p->ins, p->del), gcd(p->mismatch, p->match));
-    if (g < 1) g = 1;
-    const sd::ScoreArgs sc{p->ins / g, p->del / g, p->mismatch / g, p->match / g};
-    std::vector<std::string> tseq((size_t)2 * n_mono);
-    for (int j = 0; j < n_mono; ++j) {
-        if (mono_lens[j] <= 0) { set_err(errbuf, errlen, "ERROR: empty monomer sequence"); return SD_ERR_EMPTY; }
-        tseq[(size_t)j].assign(mono_seqs[j], (size_t)mono_lens[j]);
-        rc = sd::check_alphabet("<monomer>", mono_seqs[j], mono_lens[j], err);
-        if (rc) { set_err(errbuf, errlen, err); return rc; }
-        if (!sd::reverse_complement(tseq[(size_t)j], tseq[(size_t)n_mono + j])) { set_err(errbuf, errlen, "map::at"); return SD_ERR_SYMBOL; }
-    }
-    sd::FastPlan plan;
-    std::string why;
-    sd_params pe = *p;
-    apply_env_overrides(pe);
-    const bool ok = sd::fast_plan_build(tseq, sc, p->part_size + p->overlap, plan, why, !(pe.reserved[1] & SD_FLAG_NO_F16), true,
-                                        pe.ed_thr > -1 && !(pe.reserved[1] & SD_FLAG_NO_EDTHR_COMPACT),
-                                        !(pe.reserved[1] & SD_FLAG_NO_U16));
-    for (int i = 0; i < 8; ++i) info[i] = 0;
-    info[0] = ok ? 2 : 1;                       // kernel family "auto" would take: 2 fast, 1 generic
-    if (!ok) { set_err(errbuf, errlen, why); return SD_OK; }
-    info[1] = plan.P;
-    info[2] = plan.tiled ? (plan.f16 ? 6 : 8) : plan.waves > 1 ? (plan.f16 ? 5 : 7) : plan.wide ? (plan.f16 ? 4 : 3) : plan.u16 ? 9 : plan.f16 ? 2 : 1;   // as sd_engine_info [4] >> 8
-    info[3] = plan.floor_slots;
-    info[4] = plan.waves | ((int64_t)plan.range_bound << 8) | ((int64_t)plan.rebase << 40);
-    // narrow layout: cells in the shortest first lane of a template and in the fullest lane (from slot_of)
-    int64_t min_first = 1 << 30, max_lane = 0, x = 0;
-    for (size_t j = 0; j < tseq.size(); ++j) {
-        const int64_t L = (int64_t)tseq[j].size();
-        int64_t run = 0, lanes_seen = 0;
-        for (int64_t k = 0; k < L; ++k, ++x) {
-            const uint32_t so = plan.slot_of[(size_t)x];
-            const bool new_lane = k == 0 || (so & 127u) != (plan.slot_of[(size_t)x - 1] & 127u) || (so >> 16) != (plan.slot_of[(size_t)x - 1] >> 16);
-            if (new_lane && k > 0) {
-                if (lanes_seen == 0) min_first = std::min(min_first, run);
-                max_lane = std::max(max_lane, run);
-                ++lanes_seen;
-                run = 0;
-            }
-            ++run;
-        }
-        if (lanes_seen == 0) min_first = std::min(min_first, run);
-        max_lane = std::max(max_lane, run);
-    }
-    info[5] = min_first;
-    info[6] = max_lane;
-    info[7] = (int64_t)g | ((int64_t)(plan.tr2_ok ? plan.tr2_qm : 0) << 16) | ((int64_t)(plan.tr2_ok ? plan.tr2_bound : 0) << 24) |
-              ((int64_t)((plan.Hx >> 8) & 1) << 56);
-    return SD_OK;
-}
-
-int sd_engine_create(sd_engine** out, const sd_params* p, const char* const* mono_seqs,
-                     const int32_t* mono_lens, int32_t n_mono, char* errbuf, size_t errlen) {
-    if (!out) return SD_ERR_PARAM;
-    *out = nullptr;
-    std::string err;
-    int rc = validate_params(p, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    if (n_mono <= 0) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
-    std::unique_ptr<sd_engine> e(new sd_engine);
-    e->p = *p;
-    apply_env_overrides(e->p);
-    // A common factor of the four scores scales every DP value, every difference and every tie alike:
-    // the device works with the reduced scores (more scorings fit the packed fp16 / int16 cells) and
-    // the record scores are multiplied back when they are fetched.
-    {
-        auto gcd = [](int a, int b) { a = a < 0 ? -a : a; b = b < 0 ? -b : b; while (b) { const int t = a % b; a = b; b = t; } return a; };
-        int g = gcd(gcd(p->ins, p->del), gcd(p->mismatch, p->match));
-        if (g < 1) g = 1;
-        e->score_scale = g;
-        e->sc = sd::ScoreArgs{p->ins / g, p->del / g, p->mismatch / g, p->match / g};
-    }
-    e->T = 2 * n_mono;
-    e->tseq.resize((size_t)e->T);
-    for (int j = 0; j < n_mono; ++j) {
-        if (mono_lens[j] <= 0) { set_err(errbuf, errlen, "ERROR: empty monomer sequence"); return SD_ERR_EMPTY; }
-        e->tseq[j].assign(mono_seqs[j], (size_t)mono_lens[j]);
-        rc = sd::check_alphabet("<monomer>", mono_seqs[j], mono_lens[j], err);
-        if (rc) { set_err(errbuf, errlen, err); return rc; }
-        if (!sd::reverse_complement(e->tseq[j], e->tseq[(size_t)n_mono + j])) {
-            set_err(errbuf, errlen, "map::at");
-            return SD_ERR_SYMBOL;
-        }
-    }
-    e->tlen.resize((size_t)e->T);
-    e->toff.resize((size_t)e->T + 1);
-    e->toff[0] = 0;
-    for (int j = 0; j < e->T; ++j) {
-        e->tlen[j] = (int32_t)e->tseq[j].size();
-        e->toff[j + 1] = e->toff[j] + e->tlen[j];
-        e->Lmax = std::max(e->Lmax, (int)e->tlen[j]);
-    }
-    e->sumL = e->toff[e->T];
-    {
-        const int w0 = (e->tlen[0] - 1) >> 6, h0 = ((e->tlen[0] - 1) >> 5) & 1;
-        bool same = true;
-        for (int j = 1; j < e->T; ++j) same = same && ((e->tlen[j] - 1) >> 6) == w0 && (((e->tlen[j] - 1) >> 5) & 1) == h0;
-        e->filter_uniform = same && w0 == ((e->Lmax + 63) / 64) - 1 ? h0 : -1;
-        if (e->p.reserved[1] & SD_FLAG_FILTER_GENERAL) e->filter_uniform = -1;
-    }
-    rc = check_score_range(*p, e->Lmax, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-
-    if (device_count_checked() <= 0) {
-        set_err(errbuf, errlen, "no HIP device available (libsd_hip has no CPU fallback)");
-        return SD_ERR_NO_DEVICE;
-    }
-    try {
-        SD_HIP(hipSetDevice(p->device));
-        {
-            // Host threads that wait for the device sleep instead of spinning.  A rank of the pipelined path waits
-            // ~14 of every 16 ms; spinning, it burns a whole CPU for that (measured: 34.5 -> 21.5 ms of CPU time
-            // per 16.3-ms step and rank, same step time), which an 8-GPU node whose ranks share the host CPUs
-            // (or a container CPU quota) cannot spare.  SD_HOST_WAIT=spin keeps the runtime's default.
-            const char* hw = getenv("SD_HOST_WAIT");
-            if (!(hw && hw[0] == 's') && hipSetDeviceFlags(hipDeviceScheduleBlockingSync) != hipSuccess)
-                (void)hipGetLastError();
-        }
-        e->device = p->device;
-        {
-            // (hipGetDeviceProperties fills a 1.5-KB struct from the driver: milliseconds; one attribute is enough)
-            static std::atomic<int> cu_of[64];
-            int ncu = (p->device >= 0 && p->device < 64) ? cu_of[p->device].load() : 0;
-            if (ncu <= 0) {
-                SD_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device));
-                if (p->device >= 0 && p->device < 64) cu_of[p->device].store(ncu);
-            }
-            e->n_cu = ncu > 0 ? ncu : 256;
-            e->d_queue.alloc(sd_engine::QS * (size_t)sd_engine::QN);
-            SD_HIP(hipMemset(e->d_queue.p, 0, sizeof(int) * sd_engine::QS * (size_t)sd_engine::QN));
-        }
-        rc = engine_pick_family(e.get(), true, err);
-        if (rc) { set_err(errbuf, errlen, err); return rc; }
-        if (p->ed_thr > -1) {
-            std::vector<unsigned long long> peq;
-            sd::build_peq(e->tseq, peq);
-            e->d_peq.upload(peq);
-        }
-        SD_HIP(hipEventCreate(&e->ev_run0));
-        // the events the host waits on put the waiting thread to sleep (interrupt) instead of spinning: a rank
-        // waits ~14 of 16 ms per step, and on a node where the host CPUs are shared by 8 ranks (or capped by a
-        // cgroup quota) a spinning waiter per rank takes the time the packers need
-        SD_HIP(hipEventCreateWithFlags(&e->ev_run1, hipEventBlockingSync));
-        SD_HIP(hipEventCreate(&e->ev_cmp0));
-        SD_HIP(hipEventCreate(&e->ev_cmp1));
-        SD_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming | hipEventBlockingSync));
-    } catch (const HipFail& f) {
-        set_err(errbuf, errlen, f.msg);
-        return SD_ERR_HIP;
-    }
-    *out = e.release();
-    return SD_OK;
-}
-
-void sd_engine_destroy(sd_engine* e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    delete e;
-}
-
 // In-stream identities (sd_ident.hip).  il_seq = the monomers and their reverse complements interleaved (m0, m0', m1,
 // ..., main.py:79-84), own[t] = interleaved index of the DP's template t; second_best = every template, plain and
 // homopolymer-compressed, instead of the record's own.  Returns false (mode stays 0: the post-processing computes the
 // identities from the read text as before) for template sets the kernel does not take.
-extern "C++" bool engine_set_identity(sd_engine* e, const std::vector<std::string>& il_seq, const std::vector<int32_t>& own,
-                                bool second_best) {
+bool engine_set_identity(sd_engine* e, const std::vector<std::string>& il_seq, const std::vector<int32_t>& own,
+                         bool second_best) {
     e->ident_mode = 0;
     if (il_seq.empty() || (int)own.size() != e->T) return false;
     auto hpc = [](const std::string& x) {
@@ -417,81 +272,72 @@ extern "C++" bool engine_set_identity(sd_engine* e, const std::vector<std::strin
     return true;
 }
 
-// Packs the given chunks (pointer + length each) into the pinned staging buffer, starts their copy to
-// the device on `st` (asynchronous) and sizes the per-batch device buffers.  Chunk c refers to
-// cptr[c][0 .. clen[c]).  The kernels of sd_engine_run must be enqueued on the same stream (or after
-// a synchronisation with it).
-// Device buffers of the loaded batch that depend on the kernel family and its layout plan (throws HipFail).
-// Separate from the packing / upload of load_chunks_impl because a batch is re-run under another plan when the
-// fp16 range guard of the fills trips (engine_rerun_without_f16).
-static void engine_alloc_batch(sd_engine* e, int64_t nck) {
-    const size_t C = e->chunks.size();
-    e->d_B.alloc((size_t)e->rows + C);
-    e->d_argB.alloc((size_t)e->rows + C);
-    e->d_cnt.alloc(C);
-    e->d_roff.alloc(C + 1);
-    e->h_roff.alloc(C + 1);
-    e->d_recs.alloc((size_t)e->rows);
-    e->dense_cap = std::max<int64_t>(4096, e->rows / 16);
-    e->d_dense.alloc((size_t)e->dense_cap);
-    e->dense_cap = (int64_t)e->d_dense.cap;
-    if (e->ident_mode) {
-        // identity outputs for up to one record per 48 rows (a block is about a monomer long: ~170 rows); a batch
-        // with more records falls back to the text-based identities of the post-processing
-        int32_t maxlen = 1;
-        for (const sd::ChunkDesc& cd : e->chunks) maxlen = std::max(maxlen, cd.n);
-        const int per = e->ident_mode == 2 ? e->iT : 1;
-        e->ident_cap = std::min<int64_t>(e->dense_cap, std::max<int64_t>(4096, e->rows / 48));
-        e->d_recchunk.alloc((size_t)e->dense_cap);
-        e->d_ilong.alloc((size_t)e->ident_cap);
-        e->d_ilongcnt.alloc(1);
-        e->d_ident.alloc((size_t)e->ident_cap * per);
-        if (e->ident_mode == 2) e->d_identh.alloc((size_t)e->ident_cap * per);
-        auto fill_args = [&](sd::IdentArgs& a, bool homo) {
-            a = sd::IdentArgs{};
-            a.chunks = e->dp_chunks; a.bases2 = e->dp_bases2; a.nmask = e->dp_nmask;
-            a.dense = e->d_dense.p; a.rec_chunk = e->d_recchunk.p; a.total = e->d_roff.p + C;
-            a.rec_cap = e->ident_cap;
-            a.T = per; a.own = e->ident_mode == 1 ? e->d_iown.p : nullptr;
-            a.peq = homo ? e->d_ihpeq.p : e->d_ipeq.p;
-            a.tlen = homo ? e->d_ihtlen.p : e->d_itlen.p;
-            a.Tmask = e->iT; a.K = homo ? e->iKh : e->iK; a.homo = homo ? 1 : 0;
-            const int S = sd::nw_block_cols(a.K);
-            a.short_max = std::min<int>(512, maxlen);
-            a.cap_short = (a.short_max + S - 1) / S;
-            a.grid_short = e->n_cu * 3;
-            a.cap_long = (maxlen + S - 1) / S;
-            // the long launch: as many lanes as 192 MB of checkpoints allow, at most one workgroup per CU
-            const size_t per_block = (size_t)a.cap_long * 256 * ((size_t)a.K * 16 + 4);
-            a.grid_long = (int)std::max<size_t>(1, std::min<size_t>((size_t)e->n_cu, ((size_t)192 << 20) / per_block));
-            a.long_cnt = e->d_ilongcnt.p; a.long_list = e->d_ilong.p;
-            a.out = homo ? e->d_identh.p : e->d_ident.p;
-            // the homopolymer pass in its pruned form (distances, bounds, full alignments of the possible two best only)
-            if (homo && per >= 3 && (int64_t)e->ident_cap * per < ((int64_t)1 << 32) && !(e->p.reserved[1] & SD_FLAG_NO_IDENT_PRUNE)) {
-                e->d_icand.alloc((size_t)e->ident_cap * per);
-                e->d_icandcnt.alloc(64);
-                a.cand_list = e->d_icand.p;
-                a.cand_cnt = e->d_icandcnt.p;
-                a.grid_cand = e->n_cu * 3;
-                e->d_ick2.alloc((size_t)a.grid_cand * 256 * (size_t)a.cap_short * (size_t)a.K);
-                e->d_ickpos2.alloc((size_t)a.grid_cand * 256 * (size_t)a.cap_short);
-                a.ck_cand = e->d_ick2.p;
-                a.ckpos_cand = e->d_ickpos2.p;
-            }
-        };
-        fill_args(e->ia_plain, false);
-        size_t lanes = sd::ident_ck_lanes(e->ia_plain) * (size_t)e->ia_plain.K;
-        size_t pos = sd::ident_ck_lanes(e->ia_plain);
-        if (e->ident_mode == 2) {
-            fill_args(e->ia_homo, true);
-            lanes = std::max(lanes, sd::ident_ck_lanes(e->ia_homo) * (size_t)e->ia_homo.K);
-            pos = std::max(pos, sd::ident_ck_lanes(e->ia_homo));
-        }
-        e->d_ick.alloc(lanes);
-        e->d_ickpos.alloc(pos);
-        e->ia_plain.ck = e->d_ick.p; e->ia_plain.ckpos = e->d_ickpos.p;
-        e->ia_homo.ck = e->d_ick.p; e->ia_homo.ckpos = e->d_ickpos.p;
+// The operands of one identity pass over the batch (homo: the homopolymer-compressed templates), with the buffers only
+// that pass uses; maxlen = the longest chunk.  The checkpoint workspace the two passes share is set by alloc_identity.
+static void set_ident_args(sd_engine* e, sd::IdentArgs& a, bool homo, int32_t maxlen) {
+    const int per = e->ident_words();
+    a = sd::IdentArgs{};
+    a.chunks = e->dp_chunks; a.bases2 = e->dp_bases2; a.nmask = e->dp_nmask;
+    a.dense = e->d_dense.p; a.rec_chunk = e->d_recchunk.p; a.total = e->d_roff.p + e->chunks.size();
+    a.rec_cap = e->ident_cap;
+    a.T = per; a.own = e->ident_mode == 1 ? e->d_iown.p : nullptr;
+    a.peq = homo ? e->d_ihpeq.p : e->d_ipeq.p;
+    a.tlen = homo ? e->d_ihtlen.p : e->d_itlen.p;
+    a.Tmask = e->iT; a.K = homo ? e->iKh : e->iK; a.homo = homo ? 1 : 0;
+    const int S = sd::nw_block_cols(a.K);
+    a.short_max = std::min<int>(512, maxlen);
+    a.cap_short = (a.short_max + S - 1) / S;
+    a.grid_short = e->n_cu * 3;
+    a.cap_long = (maxlen + S - 1) / S;
+    // the long launch: as many lanes as 192 MB of checkpoints allow, at most one workgroup per CU
+    const size_t per_block = (size_t)a.cap_long * 256 * ((size_t)a.K * 16 + 4);
+    a.grid_long = (int)std::max<size_t>(1, std::min<size_t>((size_t)e->n_cu, ((size_t)192 << 20) / per_block));
+    a.long_cnt = e->d_ilongcnt.p; a.long_list = e->d_ilong.p;
+    a.out = homo ? e->d_identh.p : e->d_ident.p;
+    // the homopolymer pass in its pruned form (distances, bounds, full alignments of the possible two best only)
+    if (homo && per >= 3 && (int64_t)e->ident_cap * per < ((int64_t)1 << 32) && !(e->p.reserved[1] & SD_FLAG_NO_IDENT_PRUNE)) {
+        e->d_icand.alloc((size_t)e->ident_cap * per);
+        e->d_icandcnt.alloc(64);
+        a.cand_list = e->d_icand.p;
+        a.cand_cnt = e->d_icandcnt.p;
+        a.grid_cand = e->n_cu * 3;
+        e->d_ick2.alloc((size_t)a.grid_cand * 256 * (size_t)a.cap_short * (size_t)a.K);
+        e->d_ickpos2.alloc((size_t)a.grid_cand * 256 * (size_t)a.cap_short);
+        a.ck_cand = e->d_ick2.p;
+        a.ckpos_cand = e->d_ickpos2.p;
     }
+}
+
+// identity workspace of the batch: outputs, long-pair list, checkpoints; fills ia_plain / ia_homo
+static void alloc_identity(sd_engine* e) {
+    // identity outputs for up to one record per 48 rows (a block is about a monomer long: ~170 rows); a batch
+    // with more records falls back to the text-based identities of the post-processing
+    int32_t maxlen = 1;
+    for (const sd::ChunkDesc& cd : e->chunks) maxlen = std::max(maxlen, cd.n);
+    e->ident_cap = std::min<int64_t>(e->dense_cap, std::max<int64_t>(4096, e->rows / 48));
+    e->d_recchunk.alloc((size_t)e->dense_cap);
+    e->d_ilong.alloc((size_t)e->ident_cap);
+    e->d_ilongcnt.alloc(1);
+    e->d_ident.alloc((size_t)e->ident_cap * e->ident_words());
+    if (e->ident_mode == 2) e->d_identh.alloc((size_t)e->ident_cap * e->ident_words());
+    set_ident_args(e, e->ia_plain, false, maxlen);
+    size_t lanes = sd::ident_ck_lanes(e->ia_plain) * (size_t)e->ia_plain.K;
+    size_t pos = sd::ident_ck_lanes(e->ia_plain);
+    if (e->ident_mode == 2) {
+        set_ident_args(e, e->ia_homo, true, maxlen);
+        lanes = std::max(lanes, sd::ident_ck_lanes(e->ia_homo) * (size_t)e->ia_homo.K);
+        pos = std::max(pos, sd::ident_ck_lanes(e->ia_homo));
+    }
+    e->d_ick.alloc(lanes);
+    e->d_ickpos.alloc(pos);
+    e->ia_plain.ck = e->d_ick.p; e->ia_plain.ckpos = e->d_ickpos.p;
+    e->ia_homo.ck = e->d_ick.p; e->ia_homo.ckpos = e->d_ickpos.p;
+}
+
+// what the kernel family needs per batch: the generic pointer workspace in sub-batches, or the fast family's
+// checkpoints (nck rows) and --ed_thr tables; the event pairs of the fills and tracebacks
+static void alloc_family(sd_engine* e, int64_t nck) {
+    const size_t C = e->chunks.size();
     e->subs.clear();
     if (e->family == 1) {
         // pointer workspace: sub-batches of consecutive chunks within the budget
@@ -521,8 +367,6 @@ static void engine_alloc_batch(sd_engine* e, int64_t nck) {
             e->d_dist.alloc(C * (size_t)e->T);
             e->d_grank.alloc(C * (size_t)e->T);
         }
-        ensure_events(e->ev_fill, e->subs.size());
-        ensure_events(e->ev_trace, e->subs.size());
     } else {
         if (e->p.ed_thr > -1) {
             e->d_dist.alloc(C * (size_t)e->T);
@@ -542,13 +386,36 @@ static void engine_alloc_batch(sd_engine* e, int64_t nck) {
         }
         e->d_fckpt.alloc((size_t)nck * (size_t)e->fplan.P * 64 * (size_t)e->fplan.waves);
         e->d_fckbase.alloc((size_t)nck + 1);
-        ensure_events(e->ev_fill, 1);
-        ensure_events(e->ev_trace, 1);
     }
+    const size_t pairs = e->family == 1 ? e->subs.size() : 1;   // (as sd_engine_timings reads them)
+    ensure_events(e->ev_fill, 2 * pairs);
+    ensure_events(e->ev_trace, 2 * pairs);
 }
 
-extern "C++" int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
-                            const std::vector<int32_t>& clen, hipStream_t st, char* errbuf, size_t errlen) {
+// Device buffers of the loaded batch (throws HipFail): what every batch needs, then the identity workspace and what depends
+// on the kernel family and its layout plan.  Separate from the packing / upload of load_chunks_impl because a batch is
+// re-run under another plan when the fp16 range guard of the fills trips (fetch_begin).
+static void engine_alloc_batch(sd_engine* e, int64_t nck) {
+    const size_t C = e->chunks.size();
+    e->d_B.alloc((size_t)e->rows + C);
+    e->d_argB.alloc((size_t)e->rows + C);
+    e->d_cnt.alloc(C);
+    e->d_roff.alloc(C + 1);
+    e->h_roff.alloc(C + 1);
+    e->d_recs.alloc((size_t)e->rows);
+    e->dense_cap = std::max<int64_t>(4096, e->rows / 16);
+    e->d_dense.alloc((size_t)e->dense_cap);
+    e->dense_cap = (int64_t)e->d_dense.cap;
+    if (e->ident_mode) alloc_identity(e);
+    alloc_family(e, nck);
+}
+
+// Packs the given chunks (pointer + length each) into the pinned staging buffer, starts their copy to
+// the device on `st` (asynchronous) and sizes the per-batch device buffers.  Chunk c refers to
+// cptr[c][0 .. clen[c]).  The kernels of sd_engine_run must be enqueued on the same stream (or after
+// a synchronisation with it).
+int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
+                     const std::vector<int32_t>& clen, hipStream_t st, char* errbuf, size_t errlen) {
     e->ran = false;
     e->chunks.clear();
     const size_t C = cptr.size();
@@ -636,47 +503,202 @@ extern "C++" int load_chunks_impl(sd_engine* e, const std::vector<const char*>& 
     return SD_OK;
 }
 
-int sd_engine_load_reads(sd_engine* e, const char* const* read_seqs, const int64_t* read_lens,
-                         int32_t n_reads, int64_t* n_chunks, char* errbuf, size_t errlen) {
-    if (!e) return SD_ERR_PARAM;
-    e->chunk_read.clear();
-    e->chunk_off.clear();
-    e->read_nchunks.assign((size_t)std::max(n_reads, 0), 0);
-    e->n_reads = n_reads;
-    // chunk table (main.cpp:70-81)
-    std::vector<const char*> cptr;
-    std::vector<int32_t> clen;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        int cnt = sd::chunk_plan(read_lens[r], e->p.part_size, e->p.overlap, [&](int64_t off, int32_t l) {
-            cptr.push_back(read_seqs[r] + off);
-            clen.push_back(l);
-            e->chunk_read.push_back(r);
-            e->chunk_off.push_back(off);
-        });
-        if (cnt == 0) {
-            set_err(errbuf, errlen, "ERROR: Sequence #" + std::to_string(r) + " is empty");
-            return SD_ERR_EMPTY;
+// ---- what one run enqueues, stage by stage (each throws HipFail; engine_run2 calls them in order) -------------------
+
+// --ed_thr with more than 128 templates: the fast family fills and traces the batch in its compacted classes
+static bool compacted(const sd_engine* e) { return e->p.ed_thr > -1 && e->compact_edthr; }
+
+// the operands of the --ed_thr prefilter (main.cpp:91-93: per-chunk template prefilter) with the outputs of the engine's family
+static sd::FilterArgs filter_args(const sd_engine* e) {
+    sd::FilterArgs a{};
+    a.chunks = e->dp_chunks; a.n_chunks = (int)e->chunks.size(); a.T = e->T; a.Lmax = e->Lmax; a.ed_thr = e->p.ed_thr;
+    a.bases2 = e->dp_bases2; a.nmask = e->dp_nmask; a.peq = e->d_peq.p; a.tlen = e->d_tlen.p; a.dist = e->d_dist.p;
+    a.uniform_half = e->filter_uniform;
+    if (e->family == 1) { a.grank = e->d_grank.p; return a; }
+    a.end_vlane = e->d_endvl.p; a.end_off = e->d_endoff.p; a.vlane0 = e->d_vlane0.p;
+    a.cendoff = e->d_cendoff.p; a.crank = e->d_crank.p; a.waves = e->fplan.waves;
+    if (compacted(e)) { a.kpos = e->d_kpos.p; a.klist = e->d_klist.p; a.nkept = e->d_nkept.p; }
+    return a;
+}
+
+// Generic family: the prefilter with its rank table, then fill + traceback per sub-batch of the pointer workspace
+static void enqueue_generic(sd_engine* e, hipStream_t st) {
+    const bool ranked = e->p.ed_thr > -1;
+    if (ranked) sd::launch_edthr_filter(st, filter_args(e));
+    for (size_t s = 0; s < e->subs.size(); ++s) {
+        const int b = e->subs[s].first, n_sub = e->subs[s].second - b;
+        const uint64_t row0_base = e->chunks[(size_t)b].row0;
+        SD_HIP(hipEventRecord(e->ev_fill[2 * s], st));
+        sd::launch_generic_fill(e->Q, e->threads, n_sub, st, e->dp_chunks, b,
+                                e->dp_bases2, e->dp_nmask, e->d_tmeta.p,
+                                e->d_tend_kd.p, e->d_tend_j.p, e->sc, e->rowBytes,
+                                e->d_ptr.p, row0_base, e->d_B.p, e->d_argB.p,
+                                ranked ? e->d_grank.p : nullptr, e->T, e->n_tiles, e->d_estate.p);
+        SD_HIP(hipEventRecord(e->ev_fill[2 * s + 1], st));
+        SD_HIP(hipEventRecord(e->ev_trace[2 * s], st));
+        sd::launch_generic_trace(n_sub, st, e->dp_chunks, b, e->d_ptr.p, row0_base,
+                                 e->rowBytes, e->d_B.p, e->d_argB.p, e->d_toff.p,
+                                 e->d_tlen.p, e->d_recs.p, e->d_cnt.p);
+        SD_HIP(hipEventRecord(e->ev_trace[2 * s + 1], st));
+        ++e->fill_launches;
+    }
+}
+
+// the operands of the batch's fill / traceback; queue = the zeroed head the launch draws its chunks from
+static sd::FillArgs fill_args(const sd_engine* e, int* queue) {
+    sd::FillArgs fa{};
+    fa.chunks = e->dp_chunks; fa.n_chunks = (int)e->chunks.size(); fa.bases2 = e->dp_bases2; fa.nmask = e->dp_nmask;
+    fa.table = e->d_ftable.p; fa.lane_consts = e->d_flane.p; fa.sc = e->sc;
+    fa.B = e->d_B.p; fa.argV = e->d_argB.p; fa.ckpt = e->d_fckpt.p; fa.ckbase = e->d_fckbase.p;
+    fa.queue = queue; fa.order = e->dp_order; fa.n_cu = e->n_cu;
+    if (e->p.ed_thr > -1) { fa.cendoff = e->d_cendoff.p; fa.crank = e->d_crank.p; }
+    if (compacted(e)) { fa.klist = e->d_klist.p; fa.lane_t = e->fplan.tiled ? e->d_lanet.p : nullptr; }
+    fa.tcodes = e->d_ftcodes.p; fa.toff = e->d_toff.p; fa.tlen = e->d_tlen.p;
+    return fa;
+}
+
+static sd::TraceArgs trace_args(const sd_engine* e, int* queue) {
+    sd::TraceArgs ta{};
+    ta.chunks = e->dp_chunks; ta.n_chunks = (int)e->chunks.size(); ta.bases2 = e->dp_bases2; ta.nmask = e->dp_nmask;
+    ta.slot_of = e->d_fslot.p; ta.tcodes = e->d_ftcodes.p; ta.lane_consts = e->d_flane.p;
+    ta.toff = e->d_toff.p; ta.tlen = e->d_tlen.p; ta.sc = e->sc;
+    ta.B = e->d_B.p; ta.argV = e->d_argB.p; ta.ckpt = e->d_fckpt.p; ta.ckbase = e->d_fckbase.p;
+    ta.recs = e->d_recs.p; ta.rec_cnt = e->d_cnt.p; ta.queue = queue; ta.order = e->dp_order; ta.n_cu = e->n_cu;
+    ta.tr2_tab = e->fplan.tr2_ok ? e->d_ftr2.p : nullptr;
+    if (compacted(e)) { ta.klist = e->d_klist.p; ta.kpos = e->d_kpos.p; ta.nkept = e->d_nkept.p; ta.lane_t = e->fplan.tiled ? e->d_lanet.p : nullptr; }
+    return ta;
+}
+
+// More than 128 templates: a chunk is filled by as many waves as its kept templates need, holding exactly those (the
+// point of the reference's prefilter, main.cpp:128-149: less DP work); chunks that need all W waves by the W-wave
+// ranked kernel.  The class sizes stay on the device.  fa = the batch's operands, fa.queue the run's first head.
+static void enqueue_class_fills(sd_engine* e, hipStream_t st, const sd::FillArgs& fa) {
+    const int C = (int)e->chunks.size(), W = e->fplan.waves;
+    int* ord = e->d_orders.p;   // [W][C]: class w-1 = the chunks whose kept templates need w waves
+    // tiled layout: the kept templates' lanes per chunk (d_kpos becomes "first lane", d_nkept "lanes used")
+    if (e->fplan.tiled)
+        sd::launch_tiled_place(st, C, e->T, e->fplan.P, W, e->d_klist.p, e->d_nkept.p, e->d_tlen.p,
+                               e->d_kpos.p, e->d_lanet.p, e->fplan.filter_only ? e->d_guard.p : nullptr);
+    sd::launch_split_order(st, e->dp_order, C, e->d_nkept.p, ord, e->d_cls.p, W);
+    for (int w = 1; w <= W; ++w) {
+        sd::FillArgs cw = fa;   // class w; queue heads: class 1 the run's fill head, class W the third
+        cw.queue = w == 1 ? fa.queue : w == W ? fa.queue + 2 : fa.queue + 1 + w;
+        cw.order = ord + (size_t)(w - 1) * C;
+        cw.n_ptr = e->d_cls.p + (w - 1);
+        // (FastPlan::filter_only: no layout of the whole set, the chunks that need all W waves are compacted too)
+        if (w < W || e->fplan.filter_only) sd::launch_fast_fill_compact(e->fplan, st, cw, w);
+        else sd::launch_fast_fill(e->fplan, st, cw);
+    }
+}
+
+// Fast family: the prefilter, the fill -- plain or in the classes of --ed_thr -- on st, the traceback behind it on ts
+static void enqueue_fast(sd_engine* e, hipStream_t st, hipStream_t ts) {
+    if (e->q_run == sd_engine::QN) {  // every queue head used once: zero them again (no kernel of this
+        SD_HIP(hipMemsetAsync(e->d_queue.p, 0, sizeof(int) * sd_engine::QS * (size_t)sd_engine::QN, st));  // engine is running)
+        e->q_run = 0;
+    }
+    int* heads = e->d_queue.p + sd_engine::QS * e->q_run++;   // heads of this run: fill, traceback, fill classes 2..8
+    if (e->p.ed_thr > -1) sd::launch_edthr_filter(st, filter_args(e));
+    SD_HIP(hipEventRecord(e->ev_fill[0], st));
+    if (compacted(e)) enqueue_class_fills(e, st, fill_args(e, heads));
+    else sd::launch_fast_fill(e->fplan, st, fill_args(e, heads), e->lds_gate ? 54 * 1024 : 0);
+    SD_HIP(hipEventRecord(e->ev_fill[1], st));
+    if (ts != st) SD_HIP(hipStreamWaitEvent(ts, e->ev_fill[1], 0));
+    SD_HIP(hipEventRecord(e->ev_trace[0], ts));
+    sd::launch_fast_trace(e->fplan, ts, trace_args(e, heads + 1));
+    SD_HIP(hipEventRecord(e->ev_trace[1], ts));
+    e->fill_launches = 1;
+}
+
+// record offsets + compaction of the batch's records in one launch (sd_scan_compact); its workspace on first use
+static void enqueue_compact(sd_engine* e, hipStream_t ts) {
+    SD_HIP(hipEventRecord(e->ev_cmp0, ts));
+    if (!e->d_scanws.p) {
+        e->d_scanws.alloc(520);
+        SD_HIP(hipMemsetAsync(e->d_scanws.p, 0, 520 * sizeof(long long), ts));
+        e->scan_tickets = 0;
+    }
+    sd::launch_compact(ts, e->dp_chunks, (int)e->chunks.size(), e->d_cnt.p, e->d_roff.p, e->d_recs.p,
+                       e->d_dense.p, e->dense_cap, true, e->ident_mode ? e->d_recchunk.p : nullptr,
+                       e->d_scanws.p, ++e->scan_epoch, &e->scan_tickets);
+    SD_HIP(hipEventRecord(e->ev_cmp1, ts));
+}
+
+// the record offsets travel right behind the compaction: the fetch then knows the record
+// count as soon as the stream is idle, without a second round trip
+static void copy_offsets(sd_engine* e, hipStream_t ts) {
+    SD_HIP(hipMemcpyAsync(e->h_roff.p, e->d_roff.p, sizeof(int64_t) * (e->chunks.size() + 1), hipMemcpyDeviceToHost, ts));
+    if (e->family == 2) {   // and the fp16 range guard of the fills (reset for the next run behind the copy)
+        e->h_guard.alloc(1);
+        SD_HIP(hipMemcpyAsync(e->h_guard.p, e->d_guard.p, sizeof(int), hipMemcpyDeviceToHost, ts));
+        SD_HIP(hipMemsetAsync(e->d_guard.p, 0, sizeof(int), ts));
+    }
+}
+
+// identities of the whole batch in one pass per form
+static void enqueue_ident_batch(sd_engine* e, hipStream_t ts) {
+    e->ia_plain.rec_lo = e->ia_homo.rec_lo = e->ia_plain.rec_hi = e->ia_homo.rec_hi = nullptr;
+    sd::launch_ident(ts, e->ia_plain);
+    if (e->ident_mode == 2) {
+        e->ia_homo.cand_cnt = e->ia_homo.cand_list ? e->d_icandcnt.p : nullptr;
+        sd::launch_ident_pruned(ts, e->ia_homo);
+    }
+}
+
+// ... and slice by slice (sd_engine::slice_end), an event behind each slice
+static void enqueue_ident_slices(sd_engine* e, hipStream_t ts) {
+    ensure_events(e->ev_slice, e->slice_end.size(), hipEventBlockingSync | hipEventDisableTiming);
+    // the candidate stage of slice s on its own stream, beside the kernels of slice s + 1 (per-slice counter,
+    // per-slice region of the list, its own checkpoint workspace)
+    const bool side = e->ident_mode == 2 && e->ia_homo.cand_list && e->slice_end.size() <= 64 && !getenv("SD_IDENT_CAND_INLINE");
+    if (side) {
+        if (!e->cand_st) SD_HIP(hipStreamCreateWithFlags(&e->cand_st, hipStreamNonBlocking));
+        ensure_events(e->ev_cand, e->slice_end.size(), hipEventDisableTiming);
+        SD_HIP(hipMemsetAsync(e->d_icandcnt.p, 0, 64 * sizeof(int), ts));
+    }
+    int c_lo = 0;
+    bool on_side = false;
+    for (size_t sl = 0; sl < e->slice_end.size(); ++sl) {
+        const int c_hi = e->slice_end[sl];
+        e->ia_plain.rec_lo = e->ia_homo.rec_lo = e->d_roff.p + c_lo;
+        e->ia_plain.rec_hi = e->ia_homo.rec_hi = e->d_roff.p + c_hi;
+        sd::launch_ident(ts, e->ia_plain);
+        bool rec_on_side = false;
+        if (e->ident_mode == 2) {
+            e->ia_homo.cand_cnt = e->ia_homo.cand_list ? e->d_icandcnt.p + (side ? sl : 0) : nullptr;
+            if (side) {
+                if (sd::launch_ident_pruned_front(ts, e->ia_homo)) {
+                    SD_HIP(hipEventRecord(e->ev_cand[sl], ts));
+                    SD_HIP(hipStreamWaitEvent(e->cand_st, e->ev_cand[sl], 0));
+                    sd::launch_ident_pruned_back(e->cand_st, e->ia_homo);
+                    rec_on_side = on_side = true;
+                }
+            } else {
+                sd::launch_ident_pruned(ts, e->ia_homo);
+            }
         }
-        e->read_nchunks[(size_t)r] = cnt;
+        SD_HIP(hipEventRecord(e->ev_slice[sl], rec_on_side ? e->cand_st : ts));
+        c_lo = c_hi;
     }
-    if (n_chunks) *n_chunks = (int64_t)cptr.size();
-    // default (null) stream: a later sd_engine_run on any blocking stream is ordered behind the copy;
-    // the explicit wait also covers non-blocking streams
-    const int rc = load_chunks_impl(e, cptr, clen, nullptr, errbuf, errlen);
-    if (rc == SD_OK && hipEventSynchronize(e->ev_in) != hipSuccess) {
-        set_err(errbuf, errlen, "H2D copy of the packed reads failed");
-        return SD_ERR_HIP;
-    }
-    e->in_pending = false;
-    return rc;
+    if (on_side) SD_HIP(hipStreamWaitEvent(ts, e->ev_slice.back(), 0));   // what follows on ts follows the last candidates
+}
+
+// identities of the final TSV on the batch's compact records (sd_ident.hip)
+static void enqueue_identities(sd_engine* e, hipStream_t ts) {
+    SD_HIP(hipEventRecord(e->ev_id0, ts));
+    e->ia_plain.dense = e->ia_homo.dense = e->d_dense.p;            // (a fetch may have grown them)
+    e->ia_plain.rec_chunk = e->ia_homo.rec_chunk = e->d_recchunk.p;
+    e->ia_plain.dense_cap = e->ia_homo.dense_cap = e->dense_cap;
+    if (e->sliced_run) enqueue_ident_slices(e, ts);
+    else enqueue_ident_batch(e, ts);
+    SD_HIP(hipEventRecord(e->ev_id1, ts));
 }
 
 // One pass over the loaded batch.  `st` carries the fill (and, for the generic family, everything);
 // with a distinct `ts` the traceback + compaction of the fast family go there behind an event, so that
 // a pipeline can put the next batch's fill on `st` right behind this one: the traceback of batch b
 // then shares the machine with the fill of batch b+1 and runs in the slots its drain leaves free.
-// `in_stream` (may be null) is the stream the batch's H2D copy was issued on.
-extern "C++" int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size_t errlen) {
+int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size_t errlen) {
     const int C = (int)e->chunks.size();
     if (e->family == 1) ts = st;
     try {
@@ -685,177 +707,17 @@ extern "C++" int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char*
         SD_HIP(hipEventRecord(e->ev_run0, st));
         e->fill_launches = 0;
         if (C > 0) {
-            if (e->family == 1) {
-                const bool ranked = e->p.ed_thr > -1;
-                if (ranked)  // main.cpp:91-93: per-chunk template prefilter -> rank table
-                    sd::launch_edthr_filter(st, e->dp_chunks, C, e->T, e->Lmax, e->p.ed_thr, e->dp_bases2, e->dp_nmask,
-                                            e->d_peq.p, e->d_tlen.p, nullptr, nullptr, e->d_dist.p, nullptr, nullptr,
-                                            e->d_grank.p, 1, nullptr, nullptr, nullptr, e->filter_uniform);
-                for (size_t s = 0; s < e->subs.size(); ++s) {
-                    const int b = e->subs[s].first, n_sub = e->subs[s].second - b;
-                    const uint64_t row0_base = e->chunks[(size_t)b].row0;
-                    SD_HIP(hipEventRecord(e->ev_fill[2 * s], st));
-                    sd::launch_generic_fill(e->Q, e->threads, n_sub, st, e->dp_chunks, b,
-                                            e->dp_bases2, e->dp_nmask, e->d_tmeta.p,
-                                            e->d_tend_kd.p, e->d_tend_j.p, e->sc, e->rowBytes,
-                                            e->d_ptr.p, row0_base, e->d_B.p, e->d_argB.p,
-                                            ranked ? e->d_grank.p : nullptr, e->T, e->n_tiles, e->d_estate.p);
-                    SD_HIP(hipEventRecord(e->ev_fill[2 * s + 1], st));
-                    SD_HIP(hipEventRecord(e->ev_trace[2 * s], st));
-                    sd::launch_generic_trace(n_sub, st, e->dp_chunks, b, e->d_ptr.p, row0_base,
-                                             e->rowBytes, e->d_B.p, e->d_argB.p, e->d_toff.p,
-                                             e->d_tlen.p, e->d_recs.p, e->d_cnt.p);
-                    SD_HIP(hipEventRecord(e->ev_trace[2 * s + 1], st));
-                    ++e->fill_launches;
-                }
-            } else {
-                const bool ranked = e->p.ed_thr > -1;
-                if (e->q_run == sd_engine::QN) {  // every queue head used once: zero them again (no kernel of this
-                    SD_HIP(hipMemsetAsync(e->d_queue.p, 0, sizeof(int) * sd_engine::QS * (size_t)sd_engine::QN, st));  // engine is running)
-                    e->q_run = 0;
-                }
-                int* qfill = e->d_queue.p + sd_engine::QS * e->q_run;   // heads of this run: fill, traceback, fill classes 2..8
-                int* qtrace = qfill + 1;
-                ++e->q_run;
-                const bool compact = ranked && e->compact_edthr;
-                if (ranked)  // main.cpp:91-93: per-chunk template prefilter
-                    sd::launch_edthr_filter(st, e->dp_chunks, C, e->T, e->Lmax, e->p.ed_thr, e->dp_bases2,
-                                            e->dp_nmask, e->d_peq.p, e->d_tlen.p, e->d_endvl.p,
-                                            e->d_endoff.p, e->d_dist.p, e->d_cendoff.p, e->d_crank.p, nullptr,
-                                            e->fplan.waves, compact ? e->d_kpos.p : nullptr,
-                                            compact ? e->d_klist.p : nullptr, compact ? e->d_nkept.p : nullptr,
-                                            e->filter_uniform, e->d_vlane0.p);
-                SD_HIP(hipEventRecord(e->ev_fill[0], st));
-                sd::FillArgs fa{};
-                fa.chunks = e->dp_chunks; fa.n_chunks = C; fa.bases2 = e->dp_bases2; fa.nmask = e->dp_nmask;
-                fa.table = e->d_ftable.p; fa.lane_consts = e->d_flane.p; fa.sc = e->sc;
-                fa.B = e->d_B.p; fa.argV = e->d_argB.p; fa.ckpt = e->d_fckpt.p; fa.ckbase = e->d_fckbase.p;
-                fa.queue = qfill; fa.order = e->dp_order; fa.n_cu = e->n_cu;
-                if (ranked) { fa.cendoff = e->d_cendoff.p; fa.crank = e->d_crank.p; }
-                if (compact) { fa.klist = e->d_klist.p; fa.lane_t = e->fplan.tiled ? e->d_lanet.p : nullptr; }
-                fa.tcodes = e->d_ftcodes.p; fa.toff = e->d_toff.p; fa.tlen = e->d_tlen.p;
-                if (compact) {
-                    // more than 128 templates: a chunk is filled by as many waves as its kept templates need, holding
-                    // exactly those (the point of the reference's prefilter, main.cpp:128-149: less DP work); chunks
-                    // that need all W waves by the W-wave ranked kernel.  The class sizes stay on the device.
-                    const int W = e->fplan.waves;
-                    int* ord = e->d_orders.p;   // [W][C]: class w-1 = the chunks whose kept templates need w waves
-                    // tiled layout: the kept templates' lanes per chunk (d_kpos becomes "first lane", d_nkept "lanes used")
-                    if (e->fplan.tiled)
-                        sd::launch_tiled_place(st, C, e->T, e->fplan.P, W, e->d_klist.p, e->d_nkept.p, e->d_tlen.p,
-                                               e->d_kpos.p, e->d_lanet.p, e->fplan.filter_only ? e->d_guard.p : nullptr);
-                    sd::launch_split_order(st, e->dp_order, C, e->d_nkept.p, ord, e->d_cls.p, W);
-                    for (int w = 1; w <= W; ++w) {
-                        sd::FillArgs cw = fa;   // class w; queue heads: class 1 the run's fill head, class W the third
-                        cw.queue = w == 1 ? qfill : w == W ? qfill + 2 : qfill + 1 + w;
-                        cw.order = ord + (size_t)(w - 1) * C;
-                        cw.n_ptr = e->d_cls.p + (w - 1);
-                        // (FastPlan::filter_only: no layout of the whole set, the chunks that need all W waves are compacted too)
-                        if (w < W || e->fplan.filter_only) sd::launch_fast_fill_compact(e->fplan, st, cw, w);
-                        else sd::launch_fast_fill(e->fplan, st, cw);
-                    }
-                } else
-                    sd::launch_fast_fill(e->fplan, st, fa, e->lds_gate ? 54 * 1024 : 0);
-                SD_HIP(hipEventRecord(e->ev_fill[1], st));
-                if (ts != st) SD_HIP(hipStreamWaitEvent(ts, e->ev_fill[1], 0));
-                SD_HIP(hipEventRecord(e->ev_trace[0], ts));
-                sd::TraceArgs ta{};
-                ta.chunks = e->dp_chunks; ta.n_chunks = C; ta.bases2 = e->dp_bases2; ta.nmask = e->dp_nmask;
-                ta.slot_of = e->d_fslot.p; ta.tcodes = e->d_ftcodes.p; ta.lane_consts = e->d_flane.p;
-                ta.toff = e->d_toff.p; ta.tlen = e->d_tlen.p; ta.sc = e->sc;
-                ta.B = e->d_B.p; ta.argV = e->d_argB.p; ta.ckpt = e->d_fckpt.p; ta.ckbase = e->d_fckbase.p;
-                ta.recs = e->d_recs.p; ta.rec_cnt = e->d_cnt.p; ta.queue = qtrace; ta.order = e->dp_order; ta.n_cu = e->n_cu;
-                ta.tr2_tab = e->fplan.tr2_ok ? e->d_ftr2.p : nullptr;
-                if (compact) { ta.klist = e->d_klist.p; ta.kpos = e->d_kpos.p; ta.nkept = e->d_nkept.p; ta.lane_t = fa.lane_t; }
-                sd::launch_fast_trace(e->fplan, ts, ta);
-                SD_HIP(hipEventRecord(e->ev_trace[1], ts));
-                e->fill_launches = 1;
-            }
-            SD_HIP(hipEventRecord(e->ev_cmp0, ts));
-            if (!e->d_scanws.p) {
-                e->d_scanws.alloc(520);
-                SD_HIP(hipMemsetAsync(e->d_scanws.p, 0, 520 * sizeof(long long), ts));
-                e->scan_tickets = 0;
-            }
-            sd::launch_compact(ts, e->dp_chunks, C, e->d_cnt.p, e->d_roff.p, e->d_recs.p,
-                               e->d_dense.p, e->dense_cap, true, e->ident_mode ? e->d_recchunk.p : nullptr,
-                               e->d_scanws.p, ++e->scan_epoch, &e->scan_tickets);
-            SD_HIP(hipEventRecord(e->ev_cmp1, ts));
-            auto copy_offsets = [&]() {
-                // the record offsets travel right behind the compaction: the fetch then knows the record
-                // count as soon as the stream is idle, without a second round trip
-                SD_HIP(hipMemcpyAsync(e->h_roff.p, e->d_roff.p, sizeof(int64_t) * ((size_t)C + 1), hipMemcpyDeviceToHost, ts));
-                if (e->family == 2) {   // and the fp16 range guard of the fills (reset for the next run behind the copy)
-                    e->h_guard.alloc(1);
-                    SD_HIP(hipMemcpyAsync(e->h_guard.p, e->d_guard.p, sizeof(int), hipMemcpyDeviceToHost, ts));
-                    SD_HIP(hipMemsetAsync(e->d_guard.p, 0, sizeof(int), ts));
-                }
-            };
+            if (e->family == 1) enqueue_generic(e, st);
+            else enqueue_fast(e, st, ts);
+            enqueue_compact(e, ts);
             e->sliced_run = e->ident_mode != 0 && !e->slice_end.empty() && e->slice_end.back() == C;
             if (e->sliced_run) {
-                copy_offsets();
+                copy_offsets(e, ts);
                 if (!e->ev_dp) SD_HIP(hipEventCreateWithFlags(&e->ev_dp, hipEventBlockingSync));
                 SD_HIP(hipEventRecord(e->ev_dp, ts));
             }
-            if (e->ident_mode) {   // identities of the final TSV on the batch's compact records (sd_ident.hip)
-                SD_HIP(hipEventRecord(e->ev_id0, ts));
-                e->ia_plain.dense = e->ia_homo.dense = e->d_dense.p;            // (a fetch may have grown them)
-                e->ia_plain.rec_chunk = e->ia_homo.rec_chunk = e->d_recchunk.p;
-                e->ia_plain.dense_cap = e->ia_homo.dense_cap = e->dense_cap;
-                if (e->sliced_run) {
-                    while (e->ev_slice.size() < e->slice_end.size()) {
-                        hipEvent_t ev;
-                        SD_HIP(hipEventCreateWithFlags(&ev, hipEventBlockingSync | hipEventDisableTiming));
-                        e->ev_slice.push_back(ev);
-                    }
-                    // the candidate stage of slice s on its own stream, beside the kernels of slice s + 1 (per-slice counter,
-                    // per-slice region of the list, its own checkpoint workspace)
-                    const bool side = e->ident_mode == 2 && e->ia_homo.cand_list && e->slice_end.size() <= 64 && !getenv("SD_IDENT_CAND_INLINE");
-                    if (side) {
-                        if (!e->cand_st) SD_HIP(hipStreamCreateWithFlags(&e->cand_st, hipStreamNonBlocking));
-                        while (e->ev_cand.size() < e->slice_end.size()) {
-                            hipEvent_t ev;
-                            SD_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                            e->ev_cand.push_back(ev);
-                        }
-                        SD_HIP(hipMemsetAsync(e->d_icandcnt.p, 0, 64 * sizeof(int), ts));
-                    }
-                    int c_lo = 0;
-                    bool on_side = false;
-                    for (size_t sl = 0; sl < e->slice_end.size(); ++sl) {
-                        const int c_hi = e->slice_end[sl];
-                        e->ia_plain.rec_lo = e->ia_homo.rec_lo = e->d_roff.p + c_lo;
-                        e->ia_plain.rec_hi = e->ia_homo.rec_hi = e->d_roff.p + c_hi;
-                        sd::launch_ident(ts, e->ia_plain);
-                        bool rec_on_side = false;
-                        if (e->ident_mode == 2) {
-                            e->ia_homo.cand_cnt = e->ia_homo.cand_list ? e->d_icandcnt.p + (side ? sl : 0) : nullptr;
-                            if (side) {
-                                if (sd::launch_ident_pruned_front(ts, e->ia_homo)) {
-                                    SD_HIP(hipEventRecord(e->ev_cand[sl], ts));
-                                    SD_HIP(hipStreamWaitEvent(e->cand_st, e->ev_cand[sl], 0));
-                                    sd::launch_ident_pruned_back(e->cand_st, e->ia_homo);
-                                    rec_on_side = on_side = true;
-                                }
-                            } else {
-                                sd::launch_ident_pruned(ts, e->ia_homo);
-                            }
-                        }
-                        SD_HIP(hipEventRecord(e->ev_slice[sl], rec_on_side ? e->cand_st : ts));
-                        c_lo = c_hi;
-                    }
-                    if (on_side) SD_HIP(hipStreamWaitEvent(ts, e->ev_slice.back(), 0));   // what follows on ts follows the last candidates
-                } else {
-                    e->ia_plain.rec_lo = e->ia_homo.rec_lo = e->ia_plain.rec_hi = e->ia_homo.rec_hi = nullptr;
-                    sd::launch_ident(ts, e->ia_plain);
-                    if (e->ident_mode == 2) {
-                        e->ia_homo.cand_cnt = e->ia_homo.cand_list ? e->d_icandcnt.p : nullptr;
-                        sd::launch_ident_pruned(ts, e->ia_homo);
-                    }
-                }
-                SD_HIP(hipEventRecord(e->ev_id1, ts));
-            }
-            if (!e->sliced_run) copy_offsets();
+            if (e->ident_mode) enqueue_identities(e, ts);
+            if (!e->sliced_run) copy_offsets(e, ts);
         }
         SD_HIP(hipEventRecord(e->ev_run1, ts));
         SD_HIP(hipGetLastError());
@@ -869,28 +731,18 @@ extern "C++" int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char*
         set_err(errbuf, errlen, f.msg);
         return SD_ERR_HIP;
     }
-    e->last_stream = ts;
     e->run_st = st;
     e->run_ts = ts;
     e->ran = true;
     return SD_OK;
 }
 
-int sd_engine_run(sd_engine* e, void* hip_stream, char* errbuf, size_t errlen) {
-    if (!e) return SD_ERR_PARAM;
-    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-    return engine_run2(e, st, st, errbuf, errlen);
-}
-
-// Waits for the last run and brings its compact records into the pinned buffers h_roff / h_recs
-// (valid until the next load / run of this engine).
-static std::atomic<long long> g_guard_trips{0};
-extern "C" int64_t sd_guard_trips(void) { return (int64_t)g_guard_trips.load(); }
+static std::atomic<long long> g_guard_trips{0};   // batches repeated after a tripped range guard (sd_guard_trips)
 
 // First half of a fetch: wait until the DP of the last run is done and its record offsets are on the host (a sliced run:
 // ev_dp, the identity slices may still be running; else the whole run), repeat the batch if a guard tripped, size the
 // host buffer of the records.
-extern "C++" int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t errlen) {
+int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t errlen) {
     total = 0;
     if (!e->ran) { set_err(errbuf, errlen, "sd_engine_fetch before sd_engine_run"); return SD_ERR_PARAM; }
     const size_t C = e->chunks.size();
@@ -927,9 +779,9 @@ extern "C++" int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t 
             e->d_dense.alloc((size_t)total);
             e->dense_cap = (int64_t)e->d_dense.cap;
             if (e->ident_mode) e->d_recchunk.alloc((size_t)e->dense_cap);   // a later run of the same load compacts into it
-            sd::launch_compact(e->last_stream, e->dp_chunks, (int)C, e->d_cnt.p, e->d_roff.p,
+            sd::launch_compact(e->run_ts, e->dp_chunks, (int)C, e->d_cnt.p, e->d_roff.p,
                                e->d_recs.p, e->d_dense.p, e->dense_cap, false);
-            SD_HIP(hipStreamSynchronize(e->last_stream));
+            SD_HIP(hipStreamSynchronize(e->run_ts));
         }
         e->h_recs.alloc((size_t)std::max<int64_t>(total, 1));
     } catch (const HipFail& f) {
@@ -941,15 +793,15 @@ extern "C++" int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t 
 
 // Second half: the records [r_lo, r_hi) into h_recs (at their own indices) and, if the run has them and the caller gives
 // room (pinned, word 0 = record r_lo), their identity words.
-extern "C++" int fetch_range(sd_engine* e, int64_t r_lo, int64_t r_hi, uint32_t* id_dst, uint32_t* idh_dst, char* errbuf, size_t errlen) {
+int fetch_range(sd_engine* e, int64_t r_lo, int64_t r_hi, uint32_t* id_dst, uint32_t* idh_dst, char* errbuf, size_t errlen) {
     static_assert(sizeof(sd_rec) == sizeof(sd::DevRec), "record layout");
     const int64_t n = r_hi - r_lo;
     if (n <= 0) return SD_OK;
     try {
-        hipStream_t cs = e->copy_stream ? e->copy_stream : e->last_stream;
+        hipStream_t cs = e->copy_stream ? e->copy_stream : e->run_ts;
         SD_HIP(hipMemcpyAsync(e->h_recs.p + r_lo, e->d_dense.p + r_lo, sizeof(sd_rec) * (size_t)n, hipMemcpyDeviceToHost, cs));
         if (e->ident_valid && id_dst) {
-            const size_t per = e->ident_mode == 2 ? (size_t)e->iT : 1;
+            const size_t per = (size_t)e->ident_words();
             const size_t nb = sizeof(uint32_t) * (size_t)n * per;
             SD_HIP(hipMemcpyAsync(id_dst, e->d_ident.p + (size_t)r_lo * per, nb, hipMemcpyDeviceToHost, cs));
             if (e->ident_mode == 2 && idh_dst)
@@ -966,9 +818,9 @@ extern "C++" int fetch_range(sd_engine* e, int64_t r_lo, int64_t r_hi, uint32_t*
 }
 
 // the engine's own identity blocks, large enough for `total` records (throws HipFail)
-extern "C++" void engine_grow_ident(sd_engine* e, int64_t total) {
+static void engine_grow_ident(sd_engine* e, int64_t total) {
     if (!e->ident_valid || total <= 0) return;
-    const size_t nb = sizeof(uint32_t) * (size_t)total * (e->ident_mode == 2 ? (size_t)e->iT : 1);
+    const size_t nb = sizeof(uint32_t) * (size_t)total * (size_t)e->ident_words();
     auto grow = [&](uint32_t** p, size_t* have) {
         if (*have >= nb) return;
         g_pinpool.give(*p, *have);
@@ -980,11 +832,10 @@ extern "C++" void engine_grow_ident(sd_engine* e, int64_t total) {
     if (e->ident_mode == 2) grow(&e->h_identh, &e->h_identh_bytes);
 }
 
-// Waits for the last run and brings its compact records (and identities) into the pinned buffers h_roff / h_recs /
-// h_ident (valid until the next load / run of this engine).
-static int fetch_pinned(sd_engine* e, int64_t& total, char* errbuf, size_t errlen) {
-    int rc = fetch_begin(e, total, errbuf, errlen);
-    if (rc || e->chunks.empty()) return rc;
+// The whole batch in one piece, after fetch_begin: waits for the end of the run where the identities ran in slices, then
+// brings the compact records (and identities) into the pinned buffers h_recs / h_ident (valid until the next load / run
+// of this engine).
+int fetch_whole(sd_engine* e, int64_t total, char* errbuf, size_t errlen) {
     if (e->sliced_run && hipEventSynchronize(e->ev_run1) != hipSuccess) { set_err(errbuf, errlen, "device run failed"); return SD_ERR_HIP; }
     try {
         engine_grow_ident(e, total);
@@ -993,88 +844,6 @@ static int fetch_pinned(sd_engine* e, int64_t& total, char* errbuf, size_t errle
         return SD_ERR_HIP;
     }
     return fetch_range(e, 0, total, e->h_ident, e->h_identh, errbuf, errlen);
-}
-
-int sd_engine_fetch(sd_engine* e, sd_rec** recs, int64_t** rec_off, char* errbuf, size_t errlen) {
-    if (!e || !recs || !rec_off) return SD_ERR_PARAM;
-    *recs = nullptr;
-    *rec_off = nullptr;
-    int64_t total = 0;
-    const int rc = fetch_pinned(e, total, errbuf, errlen);
-    if (rc) return rc;
-    const size_t C = e->chunks.size();
-    int64_t* off = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * (C + 1)));
-    sd_rec* out = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec) * (size_t)std::max<int64_t>(total, 1)));
-    if (!off || !out) { std::free(off); std::free(out); set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
-    std::memcpy(off, e->h_roff.p, sizeof(int64_t) * (C + 1));
-    if (total > 0) std::memcpy(out, e->h_recs.p, sizeof(sd_rec) * (size_t)total);
-    *recs = out;
-    *rec_off = off;
-    return SD_OK;
-}
-
-int sd_engine_assemble(sd_engine* e, const sd_rec* recs, const int64_t* rec_off, sd_rec** rows,
-                       int64_t** row_off, char* errbuf, size_t errlen) {
-    (void)errbuf; (void)errlen;
-    if (!e || !rows || !row_off) return SD_ERR_PARAM;
-    std::vector<sd_rec> all;
-    std::vector<int64_t> offs((size_t)e->n_reads + 1, 0);
-    std::vector<sd_rec> batch;
-    size_t c = 0;
-    for (int32_t r = 0; r < e->n_reads; ++r) {
-        batch.clear();
-        for (int a = 0; a < e->read_nchunks[(size_t)r]; ++a, ++c) {
-            const int32_t add = (int32_t)e->chunk_off[c];  // main.cpp:109-111
-            for (int64_t x = rec_off[c]; x < rec_off[c + 1]; ++x) {
-                sd_rec t = recs[x];
-                t.start += add;
-                t.end += add;
-                batch.push_back(t);
-            }
-        }
-        sd::seam_merge(batch);  // main.cpp:116
-        all.insert(all.end(), batch.begin(), batch.end());
-        offs[(size_t)r + 1] = (int64_t)all.size();
-    }
-    sd_rec* o = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec) * std::max<size_t>(all.size(), 1)));
-    if (!all.empty()) std::memcpy(o, all.data(), sizeof(sd_rec) * all.size());
-    int64_t* ro = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * offs.size()));
-    std::memcpy(ro, offs.data(), sizeof(int64_t) * offs.size());
-    *rows = o;
-    *row_off = ro;
-    return SD_OK;
-}
-
-int sd_engine_timings(sd_engine* e, float ms[4]) {
-    if (!e || !e->ran) return SD_ERR_PARAM;
-    ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
-    if (hipSetDevice(e->device) != hipSuccess) return SD_ERR_HIP;
-    if (hipEventSynchronize(e->ev_run1) != hipSuccess) return SD_ERR_HIP;
-    const size_t pairs = e->family == 1 ? e->subs.size() : (e->chunks.empty() ? 0 : 1);
-    for (size_t s = 0; s < pairs; ++s) {
-        float a = 0.f, b = 0.f;
-        (void)hipEventElapsedTime(&a, e->ev_fill[2 * s], e->ev_fill[2 * s + 1]);
-        (void)hipEventElapsedTime(&b, e->ev_trace[2 * s], e->ev_trace[2 * s + 1]);
-        ms[0] += a;
-        ms[1] += b;
-    }
-    if (!e->chunks.empty()) (void)hipEventElapsedTime(&ms[2], e->ev_cmp0, e->ev_cmp1);
-    (void)hipEventElapsedTime(&ms[3], e->ev_run0, e->ev_run1);
-    return SD_OK;
-}
-
-int sd_engine_info(sd_engine* e, int64_t info[8]) {
-    if (!e) return SD_ERR_PARAM;
-    info[0] = e->T;
-    info[1] = e->sumL;
-    info[2] = (int64_t)e->chunks.size();
-    info[3] = e->rows;
-    info[4] = e->family | ((e->family == 1 ? 0 : e->fplan.tiled ? (e->fplan.f16 ? 6 : 8) : e->fplan.waves > 1 ? (e->fplan.f16 ? 5 : 7) : e->fplan.wide ? (e->fplan.f16 ? 4 : 3) : e->fplan.u16 ? 9 : e->fplan.f16 ? 2 : 1) << 8);
-    info[5] = e->family == 1 ? e->Q : (e->fplan.P | ((int64_t)e->fplan.floor_slots << 16));
-    info[6] = (int64_t)e->workspace_bytes();
-    info[7] = (e->family == 1 ? (int64_t)e->subs.size() : 1) |
-              ((int64_t)(e->family == 1 ? 0 : (e->fplan.tr2_ok && !e->compact_edthr) ? 2 : 1) << 16);
-    return SD_OK;
 }
 
 
@@ -1087,7 +856,6 @@ int sd_engine_info(sd_engine* e, int64_t info[8]) {
 // with (a tripped fp16 guard, an overflowing filter-only batch: the next job should start from the plan again).
 // The entries are never destroyed at process exit (as g_pool / g_pinpool: the HIP runtime may be gone by then);
 // sd_release_cache() is the only place that tears them down.
-extern "C++" {
 namespace {
 struct PipeCacheEntry { std::string key; std::unique_ptr<Pipeline> pipe; int entry; };
 struct PipeCache { std::mutex m; std::vector<PipeCacheEntry> v; };
@@ -1140,7 +908,6 @@ void pipe_cache_clear() {
         drop.swap(c.v);
     }
 }
-}  // extern "C++"
 
 namespace {
 // Records of a chunk range as the C-ABI hands them out (malloc'ed records + offsets), filled batch by batch straight
@@ -1269,6 +1036,366 @@ static int decompose_impl(const std::vector<ReadView>& reads, const std::vector<
     return rc;
 }
 
+// raw_tsv_out: the text `dp` prints; records_out: the same rows as the binary record stream (sd_records.hpp), no text made
+static int decompose_files_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p,
+                                const char* raw_tsv_out, const char* records_out, char* errbuf, size_t errlen) {
+    std::string err;
+    int rc = validate_params(p, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    if (!reads_fa || !monomers_fa || (!raw_tsv_out && !records_out)) return SD_ERR_PARAM;
+    sd::FastaFile rf, mf;
+    rc = rf.open(reads_fa, p->threads, err);                                  // main.cpp:394
+    if (rc == SD_OK) rc = rf.validate(0, rf.recs.size(), p->threads, err);
+    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);              // main.cpp:395
+    if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    std::vector<sd::Seq> monos;
+    for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
+    std::string out;
+    std::vector<ReadView> views;
+    views.reserve(rf.recs.size());
+    for (const auto& r : rf.recs) views.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
+    // The text stays in the pieces the threads formatted and goes to the file after every device batch (write_parts: no
+    // gather), i.e. while the next batch is on the device -- for a chromosome-sized read too, whose rows are merged and
+    // formatted as its chunks arrive (ReadAssembler::stream_advance).
+    std::vector<std::string> parts;
+    int fd = -1;
+    if (raw_tsv_out) {
+        fd = ::open(raw_tsv_out, O_RDWR | O_CREAT | O_TRUNC, 0666);
+        if (fd < 0) { set_err(errbuf, errlen, std::string("cannot write ") + raw_tsv_out); return SD_ERR_IO; }
+    }
+    int64_t off = 0;
+    auto flush = [&](std::vector<std::string>& ps) {
+        const bool ok = fd < 0 || sd::write_parts(fd, off, ps, p->threads);
+        ps.clear();
+        return ok;
+    };
+    rc = decompose_impl(views, monos, p, out, err, records_out, &parts, flush);
+    const bool closed = fd < 0 || ::close(fd) == 0;
+    if (rc) { set_err(errbuf, errlen, err == "short write" ? std::string("short write to ") + raw_tsv_out : err); return rc; }
+    if (!closed) { set_err(errbuf, errlen, std::string("short write to ") + raw_tsv_out); return SD_ERR_IO; }
+    return SD_OK;
+}
+
+// File form of the chunk-range call for a job sharded over ranks: every rank maps and indexes the FASTA
+// (no copy of the sequences), takes the contiguous share block_range(n_chunks, rank, world) of the global
+// chunk table and checks the alphabet of the reads that share touches only (main.cpp:329-341 reports the
+// first offending read in file order: the caller raises the error of the lowest failing rank).
+
+// edge / hout set: the share's records stay with a range assembler (sd_decompose_files_range_begin)
+static int decompose_files_range_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank,
+                                      int32_t world, sd_rec** recs, int64_t** rec_off, int64_t* chunk_lo, int64_t* chunk_hi,
+                                      int64_t* n_chunks_total, sd_seam_edge* edge, sd_range_asm** hout, char* errbuf, size_t errlen) {
+    std::string err;
+    int rc = validate_params(p, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    sd::FastaFile rf, mf;
+    rc = rf.open(reads_fa, p->threads, err);
+    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);
+    if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    std::vector<sd::Seq> monos;
+    for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
+    if (monos.empty()) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
+    std::vector<ReadView> reads;
+    reads.reserve(rf.recs.size());
+    for (const auto& r : rf.recs) {
+        if (r.len <= 0) { set_err(errbuf, errlen, "ERROR: Sequence " + std::string(r.name, r.name_len) + " is empty"); return SD_ERR_EMPTY; }
+        reads.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
+    }
+    RawJob job(reads, monos, p);
+    const int64_t n = (int64_t)job.table.size();
+    const int64_t base = n / world, extra = n % world;
+    const int64_t lo = rank * base + std::min<int64_t>(rank, extra);
+    const int64_t hi = lo + base + (rank < extra ? 1 : 0);
+    if (chunk_lo) *chunk_lo = lo;
+    if (chunk_hi) *chunk_hi = hi;
+    if (n_chunks_total) *n_chunks_total = n;
+    // the reads this share touches are checked under the device's work
+    auto validate = [&](std::string& verr) -> int {
+        return hi > lo ? rf.validate((size_t)job.table[(size_t)lo].read, (size_t)job.table[(size_t)hi - 1].read + 1, p->threads, verr) : SD_OK;
+    };
+    sd_rec* r = nullptr;
+    int64_t* o = nullptr;
+    rc = job.collect((size_t)lo, (size_t)hi, validate, &r, &o, err);
+    if (rc == SD_OK && hout) rc = range_asm_from_files(rf, mf, p, lo, hi, r, o, edge, hout, err);   // (takes r / o over, also when it fails)
+    else if (rc == SD_OK) { *recs = r; *rec_off = o; }
+    if (rc) set_err(errbuf, errlen, err);
+    return rc;
+}
+
+// ---- the C entry points (include/sd_hip.h) ---------------------------------------------------------------------------
+extern "C" {
+
+void sd_params_default(sd_params* p) {
+    std::memset(p, 0, sizeof *p);
+    p->ins = -1; p->del = -1; p->mismatch = -1; p->match = 1;
+    p->part_size = 5000; p->overlap = 500; p->ed_thr = -1; p->threads = 1; p->device = 0;
+    p->kernel = 0;
+}
+
+const char* sd_version(void) { return "stringdecomposer_amd 0.1.0 (gfx950)"; }
+
+int sd_device_count(void) { return device_count_checked(); }
+
+void sd_free(void* p) { std::free(p); }
+
+// Host only: the layout the fast kernel family would use for a monomer set and scoring -- what sd_engine_create
+// decides before it touches the device.  For tests without a GPU and for users who want to know which kernels a
+// set will run on.
+int sd_plan_info(const sd_params* p, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
+                 int64_t info[8], char* errbuf, size_t errlen) {
+    std::string err;
+    int rc = validate_params(p, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    if (n_mono <= 0 || !mono_seqs || !mono_lens || !info) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
+    sd_engine e;   // (host fields only: nothing here or in its destructor calls the device)
+    rc = host_templates(&e, *p, mono_seqs, mono_lens, n_mono, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    sd::FastPlan& plan = e.fplan;
+    std::string why;
+    e.p = *p;
+    apply_env_overrides(e.p);
+    const bool ok = plan_fast_family(e.p, e.tseq, e.sc, true, true, plan, why);
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    info[0] = ok ? 2 : 1;                       // kernel family "auto" would take: 2 fast, 1 generic
+    if (!ok) { set_err(errbuf, errlen, why); return SD_OK; }
+    info[1] = plan.P;
+    info[2] = layout_code(plan);
+    info[3] = plan.floor_slots;
+    info[4] = plan.waves | ((int64_t)plan.range_bound << 8) | ((int64_t)plan.rebase << 40);
+    // narrow layout: cells in the shortest first lane of a template and in the fullest lane (from slot_of)
+    int64_t min_first = 1 << 30, max_lane = 0, x = 0;
+    for (size_t j = 0; j < e.tseq.size(); ++j) {
+        const int64_t L = (int64_t)e.tseq[j].size();
+        int64_t run = 0, lanes_seen = 0;
+        for (int64_t k = 0; k < L; ++k, ++x) {
+            const uint32_t so = plan.slot_of[(size_t)x];
+            const bool new_lane = k == 0 || (so & 127u) != (plan.slot_of[(size_t)x - 1] & 127u) || (so >> 16) != (plan.slot_of[(size_t)x - 1] >> 16);
+            if (new_lane && k > 0) {
+                if (lanes_seen == 0) min_first = std::min(min_first, run);
+                max_lane = std::max(max_lane, run);
+                ++lanes_seen;
+                run = 0;
+            }
+            ++run;
+        }
+        if (lanes_seen == 0) min_first = std::min(min_first, run);
+        max_lane = std::max(max_lane, run);
+    }
+    info[5] = min_first;
+    info[6] = max_lane;
+    info[7] = (int64_t)e.score_scale | ((int64_t)(plan.tr2_ok ? plan.tr2_qm : 0) << 16) | ((int64_t)(plan.tr2_ok ? plan.tr2_bound : 0) << 24) |
+              ((int64_t)((plan.Hx >> 8) & 1) << 56);
+    return SD_OK;
+}
+
+int sd_engine_create(sd_engine** out, const sd_params* p, const char* const* mono_seqs,
+                     const int32_t* mono_lens, int32_t n_mono, char* errbuf, size_t errlen) {
+    if (!out) return SD_ERR_PARAM;
+    *out = nullptr;
+    std::string err;
+    int rc = validate_params(p, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    if (n_mono <= 0) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
+    std::unique_ptr<sd_engine> e(new sd_engine);
+    e->p = *p;
+    apply_env_overrides(e->p);
+    rc = host_templates(e.get(), *p, mono_seqs, mono_lens, n_mono, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    {
+        const int w0 = (e->tlen[0] - 1) >> 6, h0 = ((e->tlen[0] - 1) >> 5) & 1;
+        bool same = true;
+        for (int j = 1; j < e->T; ++j) same = same && ((e->tlen[j] - 1) >> 6) == w0 && (((e->tlen[j] - 1) >> 5) & 1) == h0;
+        e->filter_uniform = same && w0 == ((e->Lmax + 63) / 64) - 1 ? h0 : -1;
+        if (e->p.reserved[1] & SD_FLAG_FILTER_GENERAL) e->filter_uniform = -1;
+    }
+    rc = check_score_range(*p, e->Lmax, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+
+    if (device_count_checked() <= 0) {
+        set_err(errbuf, errlen, "no HIP device available (libsd_hip has no CPU fallback)");
+        return SD_ERR_NO_DEVICE;
+    }
+    try {
+        SD_HIP(hipSetDevice(p->device));
+        {
+            // Host threads that wait for the device sleep instead of spinning.  A rank of the pipelined path waits
+            // ~14 of every 16 ms; spinning, it burns a whole CPU for that (measured: 34.5 -> 21.5 ms of CPU time
+            // per 16.3-ms step and rank, same step time), which an 8-GPU node whose ranks share the host CPUs
+            // (or a container CPU quota) cannot spare.  SD_HOST_WAIT=spin keeps the runtime's default.
+            const char* hw = getenv("SD_HOST_WAIT");
+            if (!(hw && hw[0] == 's') && hipSetDeviceFlags(hipDeviceScheduleBlockingSync) != hipSuccess)
+                (void)hipGetLastError();
+        }
+        e->device = p->device;
+        {
+            // (hipGetDeviceProperties fills a 1.5-KB struct from the driver: milliseconds; one attribute is enough)
+            static std::atomic<int> cu_of[64];
+            int ncu = (p->device >= 0 && p->device < 64) ? cu_of[p->device].load() : 0;
+            if (ncu <= 0) {
+                SD_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device));
+                if (p->device >= 0 && p->device < 64) cu_of[p->device].store(ncu);
+            }
+            e->n_cu = ncu > 0 ? ncu : 256;
+            e->d_queue.alloc(sd_engine::QS * (size_t)sd_engine::QN);
+            SD_HIP(hipMemset(e->d_queue.p, 0, sizeof(int) * sd_engine::QS * (size_t)sd_engine::QN));
+        }
+        rc = engine_pick_family(e.get(), true, err);
+        if (rc) { set_err(errbuf, errlen, err); return rc; }
+        if (p->ed_thr > -1) {
+            std::vector<unsigned long long> peq;
+            sd::build_peq(e->tseq, peq);
+            e->d_peq.upload(peq);
+        }
+        SD_HIP(hipEventCreate(&e->ev_run0));
+        // the events the host waits on put the waiting thread to sleep (interrupt) instead of spinning: a rank
+        // waits ~14 of 16 ms per step, and on a node where the host CPUs are shared by 8 ranks (or capped by a
+        // cgroup quota) a spinning waiter per rank takes the time the packers need
+        SD_HIP(hipEventCreateWithFlags(&e->ev_run1, hipEventBlockingSync));
+        SD_HIP(hipEventCreate(&e->ev_cmp0));
+        SD_HIP(hipEventCreate(&e->ev_cmp1));
+        SD_HIP(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming | hipEventBlockingSync));
+    } catch (const HipFail& f) {
+        set_err(errbuf, errlen, f.msg);
+        return SD_ERR_HIP;
+    }
+    *out = e.release();
+    return SD_OK;
+}
+
+void sd_engine_destroy(sd_engine* e) {
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    delete e;
+}
+
+int sd_engine_load_reads(sd_engine* e, const char* const* read_seqs, const int64_t* read_lens,
+                         int32_t n_reads, int64_t* n_chunks, char* errbuf, size_t errlen) {
+    if (!e) return SD_ERR_PARAM;
+    e->chunk_read.clear();
+    e->chunk_off.clear();
+    e->read_nchunks.assign((size_t)std::max(n_reads, 0), 0);
+    e->n_reads = n_reads;
+    // chunk table (main.cpp:70-81)
+    std::vector<const char*> cptr;
+    std::vector<int32_t> clen;
+    for (int32_t r = 0; r < n_reads; ++r) {
+        int cnt = sd::chunk_plan(read_lens[r], e->p.part_size, e->p.overlap, [&](int64_t off, int32_t l) {
+            cptr.push_back(read_seqs[r] + off);
+            clen.push_back(l);
+            e->chunk_read.push_back(r);
+            e->chunk_off.push_back(off);
+        });
+        if (cnt == 0) {
+            set_err(errbuf, errlen, "ERROR: Sequence #" + std::to_string(r) + " is empty");
+            return SD_ERR_EMPTY;
+        }
+        e->read_nchunks[(size_t)r] = cnt;
+    }
+    if (n_chunks) *n_chunks = (int64_t)cptr.size();
+    // default (null) stream: a later sd_engine_run on any blocking stream is ordered behind the copy;
+    // the explicit wait also covers non-blocking streams
+    const int rc = load_chunks_impl(e, cptr, clen, nullptr, errbuf, errlen);
+    if (rc == SD_OK && hipEventSynchronize(e->ev_in) != hipSuccess) {
+        set_err(errbuf, errlen, "H2D copy of the packed reads failed");
+        return SD_ERR_HIP;
+    }
+    e->in_pending = false;
+    return rc;
+}
+
+int sd_engine_run(sd_engine* e, void* hip_stream, char* errbuf, size_t errlen) {
+    if (!e) return SD_ERR_PARAM;
+    hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+    return engine_run2(e, st, st, errbuf, errlen);
+}
+
+int64_t sd_guard_trips(void) { return (int64_t)g_guard_trips.load(); }
+
+int sd_engine_fetch(sd_engine* e, sd_rec** recs, int64_t** rec_off, char* errbuf, size_t errlen) {
+    if (!e || !recs || !rec_off) return SD_ERR_PARAM;
+    *recs = nullptr;
+    *rec_off = nullptr;
+    int64_t total = 0;
+    int rc = fetch_begin(e, total, errbuf, errlen);
+    if (rc == SD_OK && !e->chunks.empty()) rc = fetch_whole(e, total, errbuf, errlen);
+    if (rc) return rc;
+    const size_t C = e->chunks.size();
+    int64_t* off = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * (C + 1)));
+    sd_rec* out = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec) * (size_t)std::max<int64_t>(total, 1)));
+    if (!off || !out) { std::free(off); std::free(out); set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
+    std::memcpy(off, e->h_roff.p, sizeof(int64_t) * (C + 1));
+    if (total > 0) std::memcpy(out, e->h_recs.p, sizeof(sd_rec) * (size_t)total);
+    *recs = out;
+    *rec_off = off;
+    return SD_OK;
+}
+
+int sd_engine_assemble(sd_engine* e, const sd_rec* recs, const int64_t* rec_off, sd_rec** rows,
+                       int64_t** row_off, char* errbuf, size_t errlen) {
+    (void)errbuf; (void)errlen;
+    if (!e || !rows || !row_off) return SD_ERR_PARAM;
+    std::vector<sd_rec> all;
+    std::vector<int64_t> offs((size_t)e->n_reads + 1, 0);
+    std::vector<sd_rec> batch;
+    size_t c = 0;
+    for (int32_t r = 0; r < e->n_reads; ++r) {
+        batch.clear();
+        for (int a = 0; a < e->read_nchunks[(size_t)r]; ++a, ++c) {
+            const int32_t add = (int32_t)e->chunk_off[c];  // main.cpp:109-111
+            for (int64_t x = rec_off[c]; x < rec_off[c + 1]; ++x) {
+                sd_rec t = recs[x];
+                t.start += add;
+                t.end += add;
+                batch.push_back(t);
+            }
+        }
+        sd::seam_merge(batch);  // main.cpp:116
+        all.insert(all.end(), batch.begin(), batch.end());
+        offs[(size_t)r + 1] = (int64_t)all.size();
+    }
+    sd_rec* o = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec) * std::max<size_t>(all.size(), 1)));
+    if (!all.empty()) std::memcpy(o, all.data(), sizeof(sd_rec) * all.size());
+    int64_t* ro = static_cast<int64_t*>(std::malloc(sizeof(int64_t) * offs.size()));
+    std::memcpy(ro, offs.data(), sizeof(int64_t) * offs.size());
+    *rows = o;
+    *row_off = ro;
+    return SD_OK;
+}
+
+int sd_engine_timings(sd_engine* e, float ms[4]) {
+    if (!e || !e->ran) return SD_ERR_PARAM;
+    ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
+    if (hipSetDevice(e->device) != hipSuccess) return SD_ERR_HIP;
+    if (hipEventSynchronize(e->ev_run1) != hipSuccess) return SD_ERR_HIP;
+    const size_t pairs = e->family == 1 ? e->subs.size() : (e->chunks.empty() ? 0 : 1);
+    for (size_t s = 0; s < pairs; ++s) {
+        float a = 0.f, b = 0.f;
+        (void)hipEventElapsedTime(&a, e->ev_fill[2 * s], e->ev_fill[2 * s + 1]);
+        (void)hipEventElapsedTime(&b, e->ev_trace[2 * s], e->ev_trace[2 * s + 1]);
+        ms[0] += a;
+        ms[1] += b;
+    }
+    if (!e->chunks.empty()) (void)hipEventElapsedTime(&ms[2], e->ev_cmp0, e->ev_cmp1);
+    (void)hipEventElapsedTime(&ms[3], e->ev_run0, e->ev_run1);
+    return SD_OK;
+}
+
+int sd_engine_info(sd_engine* e, int64_t info[8]) {
+    if (!e) return SD_ERR_PARAM;
+    info[0] = e->T;
+    info[1] = e->sumL;
+    info[2] = (int64_t)e->chunks.size();
+    info[3] = e->rows;
+    info[4] = e->family | ((e->family == 1 ? 0 : layout_code(e->fplan)) << 8);
+    info[5] = e->family == 1 ? e->Q : (e->fplan.P | ((int64_t)e->fplan.floor_slots << 16));
+    info[6] = (int64_t)e->workspace_bytes();
+    info[7] = (e->family == 1 ? (int64_t)e->subs.size() : 1) |
+              ((int64_t)(e->family == 1 ? 0 : (e->fplan.tr2_ok && !e->compact_edthr) ? 2 : 1) << 16);
+    return SD_OK;
+}
+
 int sd_decompose(const char* const* read_names, const char* const* read_seqs,
                  const int64_t* read_lens, int32_t n_reads, const char* const* mono_names,
                  const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
@@ -1321,47 +1448,6 @@ int sd_decompose(const char* const* read_names, const char* const* read_seqs,
     return SD_OK;
 }
 
-// raw_tsv_out: the text `dp` prints; records_out: the same rows as the binary record stream (sd_records.hpp), no text made
-static int decompose_files_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p,
-                                const char* raw_tsv_out, const char* records_out, char* errbuf, size_t errlen) {
-    std::string err;
-    int rc = validate_params(p, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    if (!reads_fa || !monomers_fa || (!raw_tsv_out && !records_out)) return SD_ERR_PARAM;
-    sd::FastaFile rf, mf;
-    rc = rf.open(reads_fa, p->threads, err);                                  // main.cpp:394
-    if (rc == SD_OK) rc = rf.validate(0, rf.recs.size(), p->threads, err);
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);              // main.cpp:395
-    if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    std::vector<sd::Seq> monos;
-    for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
-    std::string out;
-    std::vector<ReadView> views;
-    views.reserve(rf.recs.size());
-    for (const auto& r : rf.recs) views.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
-    // The text stays in the pieces the threads formatted and goes to the file after every device batch (write_parts: no
-    // gather), i.e. while the next batch is on the device -- for a chromosome-sized read too, whose rows are merged and
-    // formatted as its chunks arrive (ReadAssembler::stream_advance).
-    std::vector<std::string> parts;
-    int fd = -1;
-    if (raw_tsv_out) {
-        fd = ::open(raw_tsv_out, O_RDWR | O_CREAT | O_TRUNC, 0666);
-        if (fd < 0) { set_err(errbuf, errlen, std::string("cannot write ") + raw_tsv_out); return SD_ERR_IO; }
-    }
-    int64_t off = 0;
-    auto flush = [&](std::vector<std::string>& ps) {
-        const bool ok = fd < 0 || sd::write_parts(fd, off, ps, p->threads);
-        ps.clear();
-        return ok;
-    };
-    rc = decompose_impl(views, monos, p, out, err, records_out, &parts, flush);
-    const bool closed = fd < 0 || ::close(fd) == 0;
-    if (rc) { set_err(errbuf, errlen, err == "short write" ? std::string("short write to ") + raw_tsv_out : err); return rc; }
-    if (!closed) { set_err(errbuf, errlen, std::string("short write to ") + raw_tsv_out); return SD_ERR_IO; }
-    return SD_OK;
-}
-
 int sd_decompose_files(const char* reads_fa, const char* monomers_fa, const sd_params* p,
                        const char* raw_tsv_out, char* errbuf, size_t errlen) {
     if (!raw_tsv_out) return SD_ERR_PARAM;
@@ -1374,9 +1460,6 @@ int sd_decompose_files_records(const char* reads_fa, const char* monomers_fa, co
     return decompose_files_impl(reads_fa, monomers_fa, p, nullptr, records_out, errbuf, errlen);
 }
 
-// -------------------------------------------------------------------------------------------
-// chunk-range form: multi-GPU sharding of one job (SURVEY 8(e)), one process per GPU
-// -------------------------------------------------------------------------------------------
 // Host only (CPU test): the two pieces of pipeline logic that decide WHICH engines a job meets and HOW it is cut, checked
 // against their contracts without a device --
 //   pipe_cache_key: two jobs share cached engines exactly when every parameter that shapes an engine and the monomer set
@@ -1456,8 +1539,9 @@ int sd_pipeline_logic_selftest(char* errbuf, size_t errlen) {
 
 void sd_release_cache(void) { pipe_cache_clear(); g_pool.release_all(); g_pinpool.release_all(); g_deferred.drain(); text_pool_clear(); }
 
-
-
+// -------------------------------------------------------------------------------------------
+// chunk-range form: multi-GPU sharding of one job (SURVEY 8(e)), one process per GPU
+// -------------------------------------------------------------------------------------------
 int sd_decompose_chunk_range(const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads,
                              const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
                              const sd_params* p, int64_t chunk_lo, int64_t chunk_hi, sd_rec** recs,
@@ -1508,53 +1592,6 @@ int sd_decompose_chunk_range(const char* const* read_seqs, const int64_t* read_l
     return rc;
 }
 
-// File form of the chunk-range call for a job sharded over ranks: every rank maps and indexes the FASTA
-// (no copy of the sequences), takes the contiguous share block_range(n_chunks, rank, world) of the global
-// chunk table and checks the alphabet of the reads that share touches only (main.cpp:329-341 reports the
-// first offending read in file order: the caller raises the error of the lowest failing rank).
-
-// edge / hout set: the share's records stay with a range assembler (sd_decompose_files_range_begin)
-static int decompose_files_range_impl(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank,
-                                      int32_t world, sd_rec** recs, int64_t** rec_off, int64_t* chunk_lo, int64_t* chunk_hi,
-                                      int64_t* n_chunks_total, sd_seam_edge* edge, sd_range_asm** hout, char* errbuf, size_t errlen) {
-    std::string err;
-    int rc = validate_params(p, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    sd::FastaFile rf, mf;
-    rc = rf.open(reads_fa, p->threads, err);
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);
-    if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
-    if (rc) { set_err(errbuf, errlen, err); return rc; }
-    std::vector<sd::Seq> monos;
-    for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
-    if (monos.empty()) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
-    std::vector<ReadView> reads;
-    reads.reserve(rf.recs.size());
-    for (const auto& r : rf.recs) {
-        if (r.len <= 0) { set_err(errbuf, errlen, "ERROR: Sequence " + std::string(r.name, r.name_len) + " is empty"); return SD_ERR_EMPTY; }
-        reads.push_back(ReadView{r.name, r.name_len, r.seq, r.len});
-    }
-    RawJob job(reads, monos, p);
-    const int64_t n = (int64_t)job.table.size();
-    const int64_t base = n / world, extra = n % world;
-    const int64_t lo = rank * base + std::min<int64_t>(rank, extra);
-    const int64_t hi = lo + base + (rank < extra ? 1 : 0);
-    if (chunk_lo) *chunk_lo = lo;
-    if (chunk_hi) *chunk_hi = hi;
-    if (n_chunks_total) *n_chunks_total = n;
-    // the reads this share touches are checked under the device's work
-    auto validate = [&](std::string& verr) -> int {
-        return hi > lo ? rf.validate((size_t)job.table[(size_t)lo].read, (size_t)job.table[(size_t)hi - 1].read + 1, p->threads, verr) : SD_OK;
-    };
-    sd_rec* r = nullptr;
-    int64_t* o = nullptr;
-    rc = job.collect((size_t)lo, (size_t)hi, validate, &r, &o, err);
-    if (rc == SD_OK && hout) rc = range_asm_from_files(rf, mf, p, lo, hi, r, o, edge, hout, err);   // (takes r / o over, also when it fails)
-    else if (rc == SD_OK) { *recs = r; *rec_off = o; }
-    if (rc) set_err(errbuf, errlen, err);
-    return rc;
-}
-
 int sd_decompose_files_range(const char* reads_fa, const char* monomers_fa, const sd_params* p, int32_t rank,
                              int32_t world, sd_rec** recs, int64_t** rec_off, int64_t* chunk_lo, int64_t* chunk_hi,
                              int64_t* n_chunks_total, char* errbuf, size_t errlen) {
@@ -1573,6 +1610,5 @@ int sd_decompose_files_range_begin(const char* reads_fa, const char* monomers_fa
     return decompose_files_range_impl(reads_fa, monomers_fa, p, rank, world, nullptr, nullptr, chunk_lo, chunk_hi, n_chunks_total,
                                       edge, h, errbuf, errlen);
 }
-
 
 }  // extern "C"

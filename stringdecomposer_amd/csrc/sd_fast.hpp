@@ -127,14 +127,34 @@ bool fast_plan_build(const std::vector<std::string>& tseq, ScoreArgs sc, int max
 // chunk -> per-chunk lane constants of the fast family (cendoff, crank: [chunk][64] packed {lo,hi}
 // int16; grank == nullptr) or the rank table of the generic family (grank: [chunk][T], 0xffff = dropped)
 void build_peq(const std::vector<std::string>& tseq, std::vector<unsigned long long>& peq);
-void launch_edthr_filter(hipStream_t st, const ChunkDesc* chunks, int n_chunks, int T, int Lmax, int ed_thr,
-                         const uint32_t* bases2, const uint32_t* nmask, const unsigned long long* peq,
-                         const int32_t* tlen, const int32_t* end_vlane, const int32_t* end_off,
-                         int32_t* dist, uint32_t* cendoff, uint32_t* crank, uint16_t* grank, int waves = 1,
-                         uint16_t* kpos = nullptr, uint16_t* klist = nullptr, int32_t* nkept = nullptr,
-                         int uniform_half = -1,    // 0 / 1: every template ends in the low / high half of word ceil(L/64)-1
-                                                   // and all have that many words (sd_hw_dist_u); -1: general kernel
-                         const int32_t* vlane0 = nullptr);   // first virtual lane of each template (narrow layout)
+struct FilterArgs {
+    const ChunkDesc* chunks;
+    int n_chunks;
+    int T;
+    int Lmax;
+    int ed_thr;
+    const uint32_t* bases2;
+    const uint32_t* nmask;
+    const unsigned long long* peq;
+    const int32_t* tlen;
+    int32_t* dist;                     // [chunk][T] infix edit distances
+    int uniform_half = -1;             // 0 / 1: every template ends in the low / high half of word ceil(L/64)-1
+                                       // and all have that many words (sd_hw_dist_u); -1: general kernel
+    // fast family: the templates' end lanes and offsets in, the per-chunk lane constants out
+    const int32_t* end_vlane = nullptr;
+    const int32_t* end_off = nullptr;
+    const int32_t* vlane0 = nullptr;   // first virtual lane of each template (narrow layout)
+    uint32_t* cendoff = nullptr;
+    uint32_t* crank = nullptr;
+    int waves = 1;
+    // ... its compacted classes (more than 128 templates): every template's place, the kept templates in filtered
+    // order and their count per chunk
+    uint16_t* kpos = nullptr;
+    uint16_t* klist = nullptr;
+    int32_t* nkept = nullptr;
+    uint16_t* grank = nullptr;         // generic family: the rank table (set: cendoff / crank are not written)
+};
+void launch_edthr_filter(hipStream_t st, const FilterArgs& a);
 // --ed_thr with more than 128 templates: the chunk order split into W classes by ceil(kept templates / 128)
 // --ed_thr on the tiled multi-wave layout: per chunk, the kept templates' lanes (sd_filter.hip: sd_tiled_place)
 void launch_tiled_place(hipStream_t st, int n_chunks, int T, int P, int W, const uint16_t* klist, int32_t* nkept,

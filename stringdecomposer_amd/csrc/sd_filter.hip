@@ -329,52 +329,45 @@ void launch_split_order(hipStream_t st, const int* order, int n, const int32_t* 
     hipLaunchKernelGGL(sd_split_order, dim3(1), dim3(64), 0, st, order, n, nkept, orders, counts, W);
 }
 
-void launch_edthr_filter(hipStream_t st, const ChunkDesc* chunks, int n_chunks, int T, int Lmax, int ed_thr,
-                         const uint32_t* bases2, const uint32_t* nmask, const unsigned long long* peq,
-                         const int32_t* tlen, const int32_t* end_vlane, const int32_t* end_off,
-                         int32_t* dist, uint32_t* cendoff, uint32_t* crank, uint16_t* grank, int waves,
-                         uint16_t* kpos, uint16_t* klist, int32_t* nkept, int uniform_half, const int32_t* vlane0) {
-    const long long total = (long long)n_chunks * T;
+void launch_edthr_filter(hipStream_t st, const FilterArgs& a) {
+    const long long total = (long long)a.n_chunks * a.T;
     const int grid = (int)((total + 255) / 256);
-    if (!grank) {
-        const size_t words = (size_t)n_chunks * 64 * (size_t)waves;
-        hipLaunchKernelGGL(sd_fill_u32, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, cendoff, words, 0x80008000u);
-        hipLaunchKernelGGL(sd_fill_u32, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, crank, words, 0x7fff7fffu);
+    if (!a.grank) {
+        const size_t words = (size_t)a.n_chunks * 64 * (size_t)a.waves;
+        hipLaunchKernelGGL(sd_fill_u32, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, a.cendoff, words, 0x80008000u);
+        hipLaunchKernelGGL(sd_fill_u32, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, a.crank, words, 0x7fff7fffu);
     }
-    if (klist) {
-        const size_t words = ((size_t)n_chunks * T + 1) / 2;   // [chunk][T] uint16
+    if (a.klist) {
+        const size_t words = ((size_t)a.n_chunks * a.T + 1) / 2;   // [chunk][T] uint16
         hipLaunchKernelGGL(sd_fill_u32, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<uint32_t*>(klist), words, 0xffffffffu);
+                           reinterpret_cast<uint32_t*>(a.klist), words, 0xffffffffu);
     }
-    const int W = std::max(1, (Lmax + 63) / 64);
+    const int W = std::max(1, (a.Lmax + 63) / 64);
     // match masks in LDS: as many templates as fit in 64 KB (all of them up to ~540 at 3 words)
 #define SD_HW(WW)                                                                                              \
     {                                                                                                          \
-        const int lt = std::min(T, (int)((64 * 1024) / (5 * WW * sizeof(unsigned long long))));                \
+        const int lt = std::min(a.T, (int)((64 * 1024) / (5 * WW * sizeof(unsigned long long))));              \
         hipLaunchKernelGGL(sd_hw_dist<WW>, dim3(grid), dim3(256), (size_t)lt * 5 * WW * sizeof(unsigned long long), st, \
-                           chunks, n_chunks, T, bases2, nmask, peq, tlen, dist, lt);                           \
+                           a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, a.dist, lt);         \
     }
     // uniform variant (sd_hw_dist_u): same word count and same half of the last word for every template, masks in LDS
-    bool done = false;
-    if (uniform_half >= 0 && W >= 1 && W <= 4) {   // (SD_FLAG_FILTER_GENERAL: the engine passes uniform_half = -1)
-        const size_t lds = (size_t)std::min(T, 256) * 5 * W * sizeof(unsigned long long);   // <= 40 KB
+    if (a.uniform_half >= 0 && W <= 4) {   // (SD_FLAG_FILTER_GENERAL: the engine passes uniform_half = -1)
+        const size_t lds = (size_t)std::min(a.T, 256) * 5 * W * sizeof(unsigned long long);   // <= 40 KB
 #define SD_HWU(WW)                                                                                             \
         {                                                                                                      \
-            if (uniform_half) hipLaunchKernelGGL((sd_hw_dist_u<WW, true>), dim3(grid), dim3(256), lds, st, chunks, n_chunks, T, bases2, nmask, peq, tlen, dist); \
-            else hipLaunchKernelGGL((sd_hw_dist_u<WW, false>), dim3(grid), dim3(256), lds, st, chunks, n_chunks, T, bases2, nmask, peq, tlen, dist); \
-            done = true;                                                                                       \
+            if (a.uniform_half) hipLaunchKernelGGL((sd_hw_dist_u<WW, true>), dim3(grid), dim3(256), lds, st, a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, a.dist); \
+            else hipLaunchKernelGGL((sd_hw_dist_u<WW, false>), dim3(grid), dim3(256), lds, st, a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, a.dist); \
         }
         if (W == 1) SD_HWU(1) else if (W == 2) SD_HWU(2) else if (W == 3) SD_HWU(3) else SD_HWU(4)
 #undef SD_HWU
-    }
-    if (!done) {
+    } else {
     if (W <= 1) SD_HW(1) else if (W == 2) SD_HW(2) else if (W == 3) SD_HW(3) else if (W == 4) SD_HW(4)
     else if (W <= 8) SD_HW(8) else if (W <= 16) SD_HW(16) else SD_HW(32)   // 16 / 32 words: templates of up to 1024 / 2048 bp
     }
 #undef SD_HW
-    hipLaunchKernelGGL(sd_rank_keep, dim3(grid), dim3(256), 0, st, n_chunks, T, ed_thr, dist, end_vlane, end_off,
-                       reinterpret_cast<uint16_t*>(cendoff), reinterpret_cast<uint16_t*>(crank), grank, waves, kpos, klist,
-                       nkept, vlane0);
+    hipLaunchKernelGGL(sd_rank_keep, dim3(grid), dim3(256), 0, st, a.n_chunks, a.T, a.ed_thr, a.dist, a.end_vlane, a.end_off,
+                       reinterpret_cast<uint16_t*>(a.cendoff), reinterpret_cast<uint16_t*>(a.crank), a.grank, a.waves, a.kpos, a.klist,
+                       a.nkept, a.vlane0);
 }
 
 }  // namespace sd

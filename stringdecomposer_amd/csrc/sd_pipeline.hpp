@@ -247,7 +247,6 @@ struct sd_engine {
     DevBuf<uint8_t> d_tmeta;
     DevBuf<int32_t> d_tend_kd, d_tend_j, d_toff, d_tlen;
     DevBuf<uint8_t> d_ptr;
-    size_t ptr_budget = 0;
     std::vector<std::pair<int, int>> subs;  // [begin, end) chunk ranges of the pointer workspace
 
     // fast family
@@ -309,6 +308,7 @@ struct sd_engine {
     // own template (main.py:112-116), 2 every template, plain and homopolymer-compressed (--second-best)
     int ident_mode = 0;
     int iT = 0, iK = 0, iKh = 0;                 // interleaved templates (m0, m0', m1, ...), words per template
+    int ident_words() const { return ident_mode == 2 ? iT : 1; }   // identity words per record (and per form, mode 2)
     DevBuf<unsigned long long> d_ipeq, d_ihpeq;  // match masks, plain / compressed templates
     DevBuf<int32_t> d_itlen, d_ihtlen, d_iown;   // lengths; DP template index -> interleaved index (mode 1)
     DevBuf<int32_t> d_recchunk, d_ilong;
@@ -342,8 +342,7 @@ struct sd_engine {
     bool sliced_run = false;             // the last run launched its identities in slices
 
     // run state
-    hipStream_t last_stream = nullptr;
-    hipStream_t run_st = nullptr, run_ts = nullptr;   // streams of the last run (a guard trip repeats it on them)
+    hipStream_t run_st = nullptr, run_ts = nullptr;   // streams of the last run (a guard trip repeats it on them); run_ts carried its end
     hipStream_t copy_stream = nullptr;   // pipeline: H2D of the batch / D2H of its records (not owned)
     bool lds_gate = false;               // pipeline mode 2: the fill asks for LDS that admits two workgroups per CU only
     bool ran = false;
@@ -382,7 +381,7 @@ int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr, const s
 int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size_t errlen);
 int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t errlen);
 int fetch_range(sd_engine* e, int64_t r_lo, int64_t r_hi, uint32_t* id_dst, uint32_t* idh_dst, char* errbuf, size_t errlen);
-void engine_grow_ident(sd_engine* e, int64_t total);
+int fetch_whole(sd_engine* e, int64_t total, char* errbuf, size_t errlen);
 
 
 // Device pipeline: up to three batches of chunks in flight on three engines (fills alternate between two streams).
@@ -601,77 +600,80 @@ struct Pipeline {
         const int k = (int)(popped % NS);
         sd_engine* e = eng[k];
         int64_t total = 0;
-        double t0 = now_s();
+        const double t0 = now_s();
         int rc = fetch_begin(e, total, eb, sizeof eb);
         const bool sliced = rc == SD_OK && e->sliced_run && e->ident_valid && !e->chunks.empty();
-        if (rc == SD_OK && !sliced && !e->chunks.empty()) {
-            if (e->sliced_run && hipEventSynchronize(e->ev_run1) != hipSuccess) { std::snprintf(eb, sizeof eb, "device run failed"); rc = SD_ERR_HIP; }
-            if (rc == SD_OK) {
-                try {
-                    engine_grow_ident(e, total);
-                } catch (const HipFail& f) {
-                    std::snprintf(eb, sizeof eb, "%s", f.msg.c_str());
-                    rc = SD_ERR_HIP;
-                }
-            }
-            if (rc == SD_OK) rc = fetch_range(e, 0, total, e->h_ident, e->h_identh, eb, sizeof eb);
-        }
+        if (rc == SD_OK && !sliced && !e->chunks.empty()) rc = fetch_whole(e, total, eb, sizeof eb);
         cnt.wait_s += now_s() - t0;
         ++popped;
-        if (rc) { sinks[k] = nullptr; return rc; }
+        RecSink fn = std::move(sinks[k]);
+        sinks[k] = nullptr;
+        if (rc) return rc;
         cnt.launches += e->fill_launches;
         ++cnt.batches;
         cnt.rows += e->rows;
-        if (sliced) {
-            RecSink fn = std::move(sinks[k]);
-            sinks[k] = nullptr;
-            // The identity words of the whole batch land in ONE pair of pinned blocks, slice by slice; every slice's sink
-            // gets a reference (IdentOut::own_*) and the blocks go back to the pool when the last one lets go (a block per
-            // slice meant 16 hipHostMalloc / hipHostFree of 19 MB per job: 100 ms).
-            const size_t per = e->ident_mode == 2 ? (size_t)e->iT : 1;
-            const size_t nb = sizeof(uint32_t) * (size_t)std::max<int64_t>(total, 1) * per;
-            std::shared_ptr<void> own_id, own_idh;
-            try {
-                size_t got = 0;
-                void* q = g_pinpool.take(nb, got);
-                own_id.reset(q, [got](void* x) { g_pinpool.give(x, got); });
-                if (e->ident_mode == 2) {
-                    q = g_pinpool.take(nb, got);
-                    own_idh.reset(q, [got](void* x) { g_pinpool.give(x, got); });
-                }
-            } catch (const HipFail& f) {
-                std::snprintf(eb, sizeof eb, "%s", f.msg.c_str());
-                rc = SD_ERR_HIP;
-            }
-            int c_lo = 0;
-            std::vector<int64_t> ro;
-            for (size_t sl = 0; sl < e->slice_end.size() && rc == SD_OK; ++sl) {
-                const int c_hi = e->slice_end[sl];
-                const int64_t r_lo = e->h_roff.p[c_lo], r_hi = e->h_roff.p[c_hi];
-                t0 = now_s();
-                uint32_t* idp = static_cast<uint32_t*>(own_id.get()) + (size_t)r_lo * per;
-                uint32_t* idhp = own_idh ? static_cast<uint32_t*>(own_idh.get()) + (size_t)r_lo * per : nullptr;
-                if (hipEventSynchronize(e->ev_slice[sl]) != hipSuccess) { std::snprintf(eb, sizeof eb, "device run failed"); rc = SD_ERR_HIP; }
-                if (rc == SD_OK) rc = fetch_range(e, r_lo, r_hi, idp, idhp, eb, sizeof eb);
-                cnt.wait_s += now_s() - t0;
-                if (rc == SD_OK) {
-                    t0 = now_s();
-                    ro.resize((size_t)(c_hi - c_lo) + 1);
-                    for (int c = c_lo; c <= c_hi; ++c) ro[(size_t)(c - c_lo)] = e->h_roff.p[c] - r_lo;
-                    cur_engine = nullptr;
-                    cur_ident = IdentOut{};
-                    if (r_hi > r_lo) {
-                        cur_ident.id = idp; cur_ident.idh = idhp; cur_ident.per = (int)per;
-                        cur_ident.own_id = own_id; cur_ident.own_idh = own_idh;
-                    }
-                    if (fn) fn(e->h_recs.p + r_lo, ro.data(), (size_t)c_lo, (size_t)(c_hi - c_lo));
-                    cur_ident = IdentOut{};
-                    cnt.sink_s += now_s() - t0;
-                }
-                c_lo = c_hi;
-            }
-            (void)hipEventSynchronize(e->ev_run1);
+        if (sliced) rc = hand_over_slices(e, total, fn);
+        book_batch(e, k, total);
+        if (sliced) return rc;
+        sink_slot = k;
+        sink_fn = std::move(fn);
+        sink_chunks = e->chunks.size();
+        sink_roff.assign(e->h_roff.p, e->h_roff.p + sink_chunks + 1);
+        return SD_OK;
+    }
+    // a sliced batch: every slice is fetched and handed to `fn` as its event completes, then the run's end is awaited
+    int hand_over_slices(sd_engine* e, int64_t total, const RecSink& fn) {
+        int rc = SD_OK;
+        // The identity words of the whole batch land in ONE pair of pinned blocks, slice by slice; every slice's sink
+        // gets a reference (IdentOut::own_*) and the blocks go back to the pool when the last one lets go (a block per
+        // slice meant 16 hipHostMalloc / hipHostFree of 19 MB per job: 100 ms).
+        const size_t per = (size_t)e->ident_words();
+        const size_t nb = sizeof(uint32_t) * (size_t)std::max<int64_t>(total, 1) * per;
+        std::shared_ptr<void> own_id, own_idh;
+        auto take = [nb](std::shared_ptr<void>& own) {
+            size_t got = 0;
+            void* q = g_pinpool.take(nb, got);
+            own.reset(q, [got](void* x) { g_pinpool.give(x, got); });
+        };
+        try {
+            take(own_id);
+            if (e->ident_mode == 2) take(own_idh);
+        } catch (const HipFail& f) {
+            std::snprintf(eb, sizeof eb, "%s", f.msg.c_str());
+            rc = SD_ERR_HIP;
         }
+        int c_lo = 0;
+        std::vector<int64_t> ro;
+        for (size_t sl = 0; sl < e->slice_end.size() && rc == SD_OK; ++sl) {
+            const int c_hi = e->slice_end[sl];
+            const int64_t r_lo = e->h_roff.p[c_lo], r_hi = e->h_roff.p[c_hi];
+            double t0 = now_s();
+            uint32_t* idp = static_cast<uint32_t*>(own_id.get()) + (size_t)r_lo * per;
+            uint32_t* idhp = own_idh ? static_cast<uint32_t*>(own_idh.get()) + (size_t)r_lo * per : nullptr;
+            if (hipEventSynchronize(e->ev_slice[sl]) != hipSuccess) { std::snprintf(eb, sizeof eb, "device run failed"); rc = SD_ERR_HIP; }
+            if (rc == SD_OK) rc = fetch_range(e, r_lo, r_hi, idp, idhp, eb, sizeof eb);
+            cnt.wait_s += now_s() - t0;
+            if (rc == SD_OK) {
+                t0 = now_s();
+                ro.resize((size_t)(c_hi - c_lo) + 1);
+                for (int c = c_lo; c <= c_hi; ++c) ro[(size_t)(c - c_lo)] = e->h_roff.p[c] - r_lo;
+                cur_engine = nullptr;
+                cur_ident = IdentOut{};
+                if (r_hi > r_lo) {
+                    cur_ident.id = idp; cur_ident.idh = idhp; cur_ident.per = (int)per;
+                    cur_ident.own_id = own_id; cur_ident.own_idh = own_idh;
+                }
+                if (fn) fn(e->h_recs.p + r_lo, ro.data(), (size_t)c_lo, (size_t)(c_hi - c_lo));
+                cur_ident = IdentOut{};
+                cnt.sink_s += now_s() - t0;
+            }
+            c_lo = c_hi;
+        }
+        (void)hipEventSynchronize(e->ev_run1);
+        return rc;
+    }
+    // the fetched batch's share of the counters: kernel times, the SD_TIMELINE line, identity pairs
+    void book_batch(sd_engine* e, int k, int64_t total) {
         float ms[4];
         if (sd_engine_timings(e, ms) == SD_OK) { cnt.fill_ms += ms[0]; cnt.trace_ms += ms[1]; cnt.compact_ms += ms[2]; cnt.run_ms += ms[3]; }
         if (timeline && tl_ref && e->family == 2 && !e->chunks.empty()) {
@@ -690,7 +692,8 @@ struct Pipeline {
         if (e->ident_mode && !e->chunks.empty()) {
             float im = 0.f;
             if (hipEventElapsedTime(&im, e->ev_id0, e->ev_id1) == hipSuccess) cnt.ident_ms += im;
-            if (e->ident_valid) cnt.ident_pairs += total * (e->ident_mode == 2 ? 2 * (int64_t)e->iT : 1);
+            // (--second-best: every template in both forms, plain and homopolymer-compressed)
+            if (e->ident_valid) cnt.ident_pairs += total * e->ident_words() * (1 + (e->ident_mode == 2));
             // pruned homopolymer pass: the pairs that were aligned in full (one counter per identity slice)
             if (e->ident_valid && e->ident_mode == 2 && e->ia_homo.cand_list && e->d_icandcnt.p) {
                 int nc[64];
@@ -699,13 +702,6 @@ struct Pipeline {
                 cnt.homo_pairs += total * (int64_t)e->iT;
             }
         }
-        if (sliced) return rc;
-        sink_slot = k;
-        sink_fn = std::move(sinks[k]);
-        sinks[k] = nullptr;
-        sink_chunks = e->chunks.size();
-        sink_roff.assign(e->h_roff.p, e->h_roff.p + sink_chunks + 1);
-        return SD_OK;
     }
     // second half: hand the fetched records to the batch's sink
     void pop_sink() {
@@ -718,10 +714,9 @@ struct Pipeline {
         if (eng[k]->ident_valid)
         {
             cur_ident.id = eng[k]->h_ident;
-            cur_ident.idh = eng[k]->ident_mode == 2 ? eng[k]->h_identh : nullptr;
-            cur_ident.per = eng[k]->ident_mode == 2 ? eng[k]->iT : 1;
+            cur_ident.per = eng[k]->ident_words();
             cur_ident.id_bytes = eng[k]->h_ident_bytes;
-            cur_ident.idh_bytes = eng[k]->ident_mode == 2 ? eng[k]->h_identh_bytes : 0;
+            if (eng[k]->ident_mode == 2) { cur_ident.idh = eng[k]->h_identh; cur_ident.idh_bytes = eng[k]->h_identh_bytes; }
         }
         if (sink_fn) sink_fn(eng[k]->h_recs.p, sink_roff.data(), 0, sink_chunks);
         sink_fn = nullptr;
