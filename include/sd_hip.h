@@ -313,6 +313,13 @@ void sd_engine_destroy(sd_engine* e);
 int sd_engine_load_reads(sd_engine* e, const char* const* read_seqs, const int64_t* read_lens,
                          int32_t n_reads, int64_t* n_chunks, char* errbuf, size_t errlen);
 
+/* The same from reads that already lie in DEVICE memory: read r = d_bases[read_off[r] .. read_off[r] + read_lens[r])
+ * (read_off / read_lens are host arrays), packed by a HIP kernel -- no base passes through the host.  Arguments,
+ * ordering with hip_stream and the alphabet check as sd_stream_submit_dev below; the call returns when the batch is
+ * packed, and a byte outside A C G T N is reported by sd_engine_fetch (SD_ERR_SYMBOL). */
+int sd_engine_load_reads_dev(sd_engine* e, const void* d_bases, const int64_t* read_off, const int64_t* read_lens,
+                             int32_t n_reads, void* hip_stream, int64_t* n_chunks, char* errbuf, size_t errlen);
+
 /* One pass of the hot path over the loaded batch: DP fill + traceback + record compaction, all
  * on `hip_stream` (a hipStream_t cast to void*, NULL = default stream).  Asynchronous. */
 int sd_engine_run(sd_engine* e, void* hip_stream, char* errbuf, size_t errlen);
@@ -380,6 +387,31 @@ void sd_stream_destroy(sd_stream* s);
  * read buffers are no longer needed when it returns. */
 int sd_stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* read_lens,
                      int32_t n_reads, char* errbuf, size_t errlen);
+/* sd_stream_submit for reads that already lie in DEVICE memory (a basecaller's output, a torch tensor, an earlier GPU
+ * stage): read r = d_bases[read_off[r] .. read_off[r] + read_lens[r]); read_off and read_lens are HOST arrays, and
+ * gaps, padding and any order of the offsets are allowed.  The bytes are packed into the 2-bit words by a HIP kernel
+ * (csrc/sd_pack_dev.hip) on the stream's copy streams; no base is copied to the host (final mode: only the reads whose
+ * blocks take the fallback identities, when the rows come back, from a device copy the job keeps).  The rows are those
+ * of sd_stream_submit on the same bytes.  Works on a raw or final-mode stream, with or without a device list.
+ *
+ * ORDERING AND BUFFER LIFETIME.  hip_stream (a hipStream_t cast to void*, NULL = the null stream) is the stream on which
+ * the caller produced the bytes.  The library records an event on it and makes its own streams wait for that event
+ * before the first packer, and before this call returns it makes hip_stream wait for an event recorded behind the
+ * job's last packer.  Work the caller enqueues on hip_stream AFTER the call -- overwriting the buffer, a stream-ordered
+ * free of it -- is therefore ordered behind the library's last read of it; there is no host-side wait.  Work on OTHER
+ * streams is not ordered.  As sd_stream_submit in raw mode, the call returns once every batch of the job is packed,
+ * which here means: its packer is enqueued.
+ *
+ * Checked before any work: SD_ERR_PARAM for a NULL handle, NULL d_bases with n_reads > 0, n_reads < 0, or a d_bases that
+ * hipPointerGetAttributes does not report as device memory; SD_ERR_EMPTY for a read of length <= 0;
+ * SD_ERR_UNSUPPORTED when the memory belongs to another device than one of the stream's entries (errbuf names both
+ * ordinals; {0, 0} is fine, copies between devices are not made).
+ * The alphabet is checked by the packer: a byte outside A C G T N fails the stream with SD_ERR_SYMBOL -- errbuf gives
+ * the read's index within the job, the 0-based position and the byte -- under the stream's failure rule: the submit
+ * or collect that meets it reports it, and every outstanding job is dropped.  (The byte is packed under the same
+ * masked 2-bit formula as any other, so it cannot cause an out-of-range access on the device.) */
+int sd_stream_submit_dev(sd_stream* s, const void* d_bases, const int64_t* read_off, const int64_t* read_lens,
+                         int32_t n_reads, void* hip_stream, char* errbuf, size_t errlen);
 /* Rows of the oldest submitted job (FIFO): read r owns rows[row_off[r] .. row_off[r+1]), read-global
  * coordinates, seam-merged.  Both arrays are malloc'ed (sd_free). */
 int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n_rows, char* errbuf,
@@ -481,6 +513,15 @@ int sd_format_rows(const char* read_name, const char* const* tmpl_names, const s
  * = 0..3, N = 0 + a set bit in the optional 1-bit mask); returns 1 if the chunk holds an N, -1 on bad
  * arguments.  words: (n+15)/16 dwords, nmask (may be NULL): (n+31)/32 dwords. */
 int32_t sd_pack_bases(const char* seq, int64_t n, uint32_t* words, uint32_t* nmask);
+/* The device packer alone, results on the host (for tests): chunk c = d_bases[chunk_off[c] .. chunk_off[c] + chunk_len[c])
+ * in the memory of `device`, packed on hip_stream.  bases2: the chunks' words back to back ((len+15)/16 dwords each);
+ * nmask: (len+31)/32 dwords per chunk back to back, written ONLY for the chunks that hold an N (the others keep what the
+ * caller put there); has_n[c] (may be NULL): 1 / 0; *first_bad (may be NULL): the smallest offset into d_bases of a
+ * byte outside A C G T N, or -1.  SD_ERR_PARAM for bad arguments or memory that is not device memory,
+ * SD_ERR_UNSUPPORTED when it belongs to another device. */
+int sd_pack_bases_dev(const void* d_bases, const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks,
+                      int32_t device, void* hip_stream, uint32_t* bases2, uint32_t* nmask, int32_t* has_n,
+                      int64_t* first_bad);
 /* Self-test of the file writer behind sd_run_files (no device): n_parts parts of part_bytes bytes appended to
  * `path` in two calls, read back and compared.  fail_reserve != 0 makes the page reservation of the mapped
  * (tmpfs) path fail, as on a full /dev/shm -- the text must then arrive through the pwritev loop, which reports

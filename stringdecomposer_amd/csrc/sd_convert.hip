@@ -249,7 +249,6 @@ int PostProcessor::prepare(const PostRead* reads, size_t n_reads, const sd_rec* 
                 seg_len[(size_t)b] = (int32_t)std::min<int64_t>(e1 - s0, 0x7fffffff);
                 bt.read_of[(size_t)b] = (int32_t)r;
             }
-            spans.emplace_back(reads[r].seq, reads[r].len);
             pos += reads[r].len;
         }
     }
@@ -269,6 +268,14 @@ int PostProcessor::prepare(const PostRead* reads, size_t n_reads, const sd_rec* 
     }
     bt.id = have;   // identities came with the rows
     if (prof_on) bt.kept.assign((size_t)nB, 0);
+    // only the fallback identities and the profiles read the text: a caller that holds it elsewhere (a stream job whose
+    // reads lie in device memory) brings it now, into reads[].seq
+    if ((!bt.id || prof_on) && fetch_text) {
+        const int rf = fetch_text(err);
+        if (rf) return rf;
+    }
+    for (size_t r = 0; r < n_reads; ++r)
+        if (row_off[r + 1] != row_off[r]) spans.emplace_back(reads[r].seq, reads[r].len);
     const double t_a = now_seconds();
     int rc;
     if (bt.id) {

@@ -2,6 +2,8 @@
 // rows of final_decomposition.tsv / _alt.tsv (stringdecomposer/main.py:107-165).
 #pragma once
 
+#include <functional>
+
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -97,6 +99,9 @@ class PostProcessor {
     std::string profile_text() const;   // "name\tsequence\n" per monomer, file order
     double t_prepare = 0, t_identity = 0, t_format = 0, t_concat = 0, t_profile = 0;   // seconds spent in process(), by stage
     int64_t fallback_blocks = 0;     // blocks whose identities were computed here, not taken from the rows' words
+    // set by a caller whose PostRead::seq are not filled in yet: called (once per process* call, before the text is
+    // read) only when the text is needed -- fallback identities or profiles; returns SD_OK or an error with err set
+    std::function<int(std::string&)> fetch_text;
 
   private:
     // a batch's identities as the selection reads them: the words that came with the rows (id) or the values

@@ -414,9 +414,14 @@ static void engine_alloc_batch(sd_engine* e, int64_t nck) {
 // the device on `st` (asynchronous) and sizes the per-batch device buffers.  Chunk c refers to
 // cptr[c][0 .. clen[c]).  The kernels of sd_engine_run must be enqueued on the same stream (or after
 // a synchronisation with it).
+// With a DevSrc the pointers are device addresses: the host builds the same table, order and sizes -- every chunk with
+// the mask offset it would have if every chunk held an N -- uploads them with the addresses, and the packer
+// (sd_pack_dev.hip) fills bases2 / nmask on `st` once the caller's stream has produced the text; no base is read here.
 int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
-                     const std::vector<int32_t>& clen, hipStream_t st, char* errbuf, size_t errlen) {
+                     const std::vector<int32_t>& clen, hipStream_t st, char* errbuf, size_t errlen, const DevSrc* ds) {
     e->ran = false;
+    e->dev_src = ds != nullptr;
+    e->dev_cum = ds ? ds->cum : nullptr;
     e->chunks.clear();
     const size_t C = cptr.size();
     e->chunks.resize(C);
@@ -446,16 +451,30 @@ int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t o_chunks = 0;
         const size_t o_order = al(o_chunks + C * sizeof(sd::ChunkDesc));
-        const size_t o_bases = al(o_order + C * sizeof(int));
+        // device source: [chunk addresses][chunk positions][alphabet flag] between the order and the bases
+        const size_t o_src = al(o_order + C * sizeof(int));
+        const size_t o_gpos = o_src + (ds ? C * sizeof(uint64_t) : 0);
+        const size_t o_bad = o_gpos + (ds ? C * sizeof(int64_t) : 0);
+        const size_t o_bases = ds ? al(o_bad + sizeof(uint64_t)) : o_src;
         const size_t o_nmask = al(o_bases + words_total * sizeof(uint32_t));
         // worst-case N mask (every chunk has N): one bit per base
         size_t nwords_max = 0;
         for (size_t c = 0; c < C; ++c) nwords_max += ((size_t)clen[c] + 31) / 32;
-        e->h_in.alloc(o_nmask + nwords_max * sizeof(uint32_t) + 256);
+        e->h_in.alloc(ds ? o_bases : o_nmask + nwords_max * sizeof(uint32_t) + 256);
         uint32_t* bases2 = reinterpret_cast<uint32_t*>(e->h_in.p + o_bases);
         uint32_t* nmask = reinterpret_cast<uint32_t*>(e->h_in.p + o_nmask);
         size_t nwords = 0;
-        {
+        if (ds) {
+            uint64_t* src = reinterpret_cast<uint64_t*>(e->h_in.p + o_src);
+            int64_t* gpos = reinterpret_cast<int64_t*>(e->h_in.p + o_gpos);
+            for (size_t c = 0; c < C; ++c) {
+                e->chunks[c].noff = (int32_t)nwords;
+                nwords += ((size_t)clen[c] + 31) / 32;
+                src[c] = (uint64_t)reinterpret_cast<uintptr_t>(cptr[c]);
+                gpos[c] = ds->gpos[c];
+            }
+            *reinterpret_cast<uint64_t*>(e->h_in.p + o_bad) = ~0ull;
+        } else {
             std::vector<uint8_t> hasn(C, 0);
             sd::parallel_for((int64_t)C, e->p.threads, 16, [&](int64_t c) {
                 const sd::ChunkDesc& cd = e->chunks[(size_t)c];
@@ -486,14 +505,29 @@ int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
             for (size_t c = 0; c < C; ++c) order[c] = (int)c;
             std::stable_sort(order, order + C, [&](int a, int b) { return e->chunks[(size_t)a].n > e->chunks[(size_t)b].n; });
         }
-        const size_t in_bytes = o_nmask + nwords * sizeof(uint32_t);
+        const size_t in_bytes = ds ? o_bad + sizeof(uint64_t) : o_nmask + nwords * sizeof(uint32_t);
         e->d_in.alloc(o_nmask + nwords_max * sizeof(uint32_t) + 256);
         e->dp_chunks = reinterpret_cast<sd::ChunkDesc*>(e->d_in.p + o_chunks);
         e->dp_order = reinterpret_cast<int*>(e->d_in.p + o_order);
         e->dp_bases2 = reinterpret_cast<uint32_t*>(e->d_in.p + o_bases);
         e->dp_nmask = reinterpret_cast<uint32_t*>(e->d_in.p + o_nmask);
+        e->dp_bad = ds ? reinterpret_cast<unsigned long long*>(e->d_in.p + o_bad) : nullptr;
         SD_HIP(hipMemcpyAsync(e->d_in.p, e->h_in.p, in_bytes, hipMemcpyHostToDevice, st));
+        if (ds) {
+            if (ds->ready) SD_HIP(hipStreamWaitEvent(st, ds->ready, 0));
+            sd::PackDevArgs pa{};
+            pa.chunks = e->dp_chunks; pa.n_chunks = (int)C; pa.bases2 = e->dp_bases2; pa.nmask = e->dp_nmask;
+            pa.src = reinterpret_cast<const unsigned long long*>(e->d_in.p + o_src);
+            pa.gpos = reinterpret_cast<const long long*>(e->d_in.p + o_gpos);
+            pa.bad = e->dp_bad;
+            sd::launch_pack_dev(st, pa);
+            SD_HIP(hipGetLastError());
+            e->h_bad.alloc(1);
+            e->h_bad.p[0] = ~0ull;
+        }
         SD_HIP(hipEventRecord(e->ev_in, st));
+        // whatever the caller enqueues on its stream from here on follows the packer: it may overwrite or free the text
+        if (ds && ds->release) SD_HIP(hipStreamWaitEvent(ds->user, e->ev_in, 0));
         e->in_pending = true;
         engine_alloc_batch(e, nck);
     } catch (const HipFail& f) {
@@ -628,6 +662,8 @@ static void enqueue_compact(sd_engine* e, hipStream_t ts) {
 // count as soon as the stream is idle, without a second round trip
 static void copy_offsets(sd_engine* e, hipStream_t ts) {
     SD_HIP(hipMemcpyAsync(e->h_roff.p, e->d_roff.p, sizeof(int64_t) * (e->chunks.size() + 1), hipMemcpyDeviceToHost, ts));
+    if (e->dev_src)         // the device packer's alphabet flag
+        SD_HIP(hipMemcpyAsync(e->h_bad.p, e->dp_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, ts));
     if (e->family == 2) {   // and the fp16 range guard of the fills (reset for the next run behind the copy)
         e->h_guard.alloc(1);
         SD_HIP(hipMemcpyAsync(e->h_guard.p, e->d_guard.p, sizeof(int), hipMemcpyDeviceToHost, ts));
@@ -737,6 +773,22 @@ int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size
     return SD_OK;
 }
 
+// The alphabet flag of a device-packed batch as a message: read index within the job, 0-based position, the byte.
+static std::string dev_symbol_message(unsigned long long key, const std::vector<int64_t>* cum) {
+    const int64_t pos = (int64_t)(key >> 8);
+    const unsigned byte = (unsigned)(key & 0xff);
+    int64_t r = 0, at = pos;
+    if (cum && cum->size() > 1) {
+        r = (int64_t)(std::upper_bound(cum->begin(), cum->end(), pos) - cum->begin()) - 1;
+        r = std::min<int64_t>(std::max<int64_t>(r, 0), (int64_t)cum->size() - 2);
+        at = pos - (*cum)[(size_t)r];
+    }
+    char txt[160];
+    std::snprintf(txt, sizeof txt, "ERROR: Sequence #%lld contains undefined symbol (not ACGT) at position %lld: byte %u (0x%02x)",
+                  (long long)r, (long long)at, byte, byte);
+    return txt;
+}
+
 static std::atomic<long long> g_guard_trips{0};   // batches repeated after a tripped range guard (sd_guard_trips)
 
 // First half of a fetch: wait until the DP of the last run is done and its record offsets are on the host (a sliced run:
@@ -751,6 +803,12 @@ int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t errlen) {
         SD_HIP(hipEventSynchronize(e->sliced_run ? e->ev_dp : e->ev_run1));
         e->in_pending = false;
         if (C == 0) { e->h_roff.alloc(1); e->h_roff.p[0] = 0; return SD_OK; }
+        if (e->dev_src && e->h_bad.p[0] != ~0ull) {   // (nothing of the run is used; it ran on masked codes)
+            set_err(errbuf, errlen, dev_symbol_message(e->h_bad.p[0], e->dev_cum.get()));
+            return SD_ERR_SYMBOL;
+        }
+        // (a batch packed on the device: which chunks run maskless is in the device's table only)
+        const bool dev_table = e->dev_src;
         if (e->family == 2 && e->h_guard.p && e->h_guard.p[0] != 0) {
             // A wave's fp16 cells left the range in which they are exact integers (F16Guard, sd_fast_dev.hpp): the
             // layout plan's bound did not hold for this input.  Nothing of the run is used; the batch (still packed on
@@ -762,6 +820,7 @@ int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t errlen) {
             int rc2 = engine_pick_family(e, false, err2);
             if (rc2) { set_err(errbuf, errlen, "fp16 cell range exceeded, and no integer-cell layout: " + err2); return rc2; }
             const int64_t nck = e->family == 2 ? sd::fast_ckpt_rows_total(e->fplan, e->chunks) : 0;
+            if (dev_table) SD_HIP(hipMemcpy(e->chunks.data(), e->dp_chunks, C * sizeof(sd::ChunkDesc), hipMemcpyDeviceToHost));
             SD_HIP(hipMemcpy(e->dp_chunks, e->chunks.data(), C * sizeof(sd::ChunkDesc), hipMemcpyHostToDevice));
             engine_alloc_batch(e, nck);
             rc2 = engine_run2(e, e->run_st, e->run_ts, errbuf, errlen);
@@ -1303,6 +1362,128 @@ int sd_engine_load_reads(sd_engine* e, const char* const* read_seqs, const int64
     }
     e->in_pending = false;
     return rc;
+}
+
+int sd_engine_load_reads_dev(sd_engine* e, const void* d_bases, const int64_t* read_off, const int64_t* read_lens,
+                             int32_t n_reads, void* hip_stream, int64_t* n_chunks, char* errbuf, size_t errlen) {
+    if (!e || n_reads < 0 || (n_reads > 0 && (!d_bases || !read_off || !read_lens))) return SD_ERR_PARAM;
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_lens[r] <= 0) {
+            set_err(errbuf, errlen, "ERROR: Sequence #" + std::to_string(r) + " is empty");
+            return SD_ERR_EMPTY;
+        }
+    std::string err;
+    int dev = -1;
+    int rc = n_reads > 0 ? device_pointer(d_bases, dev, err) : SD_OK;
+    if (rc == SD_OK && n_reads > 0 && dev != e->device) {
+        err = "the reads lie in the memory of device " + std::to_string(dev) + ", the engine runs on device " + std::to_string(e->device);
+        rc = SD_ERR_UNSUPPORTED;
+    }
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    e->chunk_read.clear();
+    e->chunk_off.clear();
+    e->read_nchunks.assign((size_t)n_reads, 0);
+    e->n_reads = n_reads;
+    std::vector<const char*> cptr;
+    std::vector<int32_t> clen;
+    std::vector<int64_t> gpos;
+    auto cum = std::make_shared<std::vector<int64_t>>((size_t)n_reads + 1, 0);
+    for (int32_t r = 0; r < n_reads; ++r) {
+        (*cum)[(size_t)r + 1] = (*cum)[(size_t)r] + read_lens[r];
+        e->read_nchunks[(size_t)r] = sd::chunk_plan(read_lens[r], e->p.part_size, e->p.overlap, [&](int64_t off, int32_t l) {
+            cptr.push_back(static_cast<const char*>(d_bases) + read_off[r] + off);
+            clen.push_back(l);
+            gpos.push_back((*cum)[(size_t)r] + off);
+            e->chunk_read.push_back(r);
+            e->chunk_off.push_back(off);
+        });
+    }
+    if (n_chunks) *n_chunks = (int64_t)cptr.size();
+    DevSrc ds;
+    ds.user = reinterpret_cast<hipStream_t>(hip_stream);
+    ds.gpos = gpos.data();
+    ds.cum = cum;
+    hipEvent_t ready = nullptr;
+    if (hipSetDevice(e->device) != hipSuccess || hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess ||
+        hipEventRecord(ready, ds.user) != hipSuccess) {
+        (void)hipGetLastError();
+        if (ready) (void)hipEventDestroy(ready);
+        set_err(errbuf, errlen, "cannot record an event on the caller's stream");
+        return SD_ERR_HIP;
+    }
+    ds.ready = ready;
+    rc = load_chunks_impl(e, cptr, clen, nullptr, errbuf, errlen, &ds);
+    if (rc == SD_OK && hipEventSynchronize(e->ev_in) != hipSuccess) {
+        set_err(errbuf, errlen, "packing the reads on the device failed");
+        rc = SD_ERR_HIP;
+    }
+    (void)hipEventDestroy(ready);
+    e->in_pending = false;
+    return rc;
+}
+
+int sd_pack_bases_dev(const void* d_bases, const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks,
+                      int32_t device, void* hip_stream, uint32_t* bases2, uint32_t* nmask, int32_t* has_n,
+                      int64_t* first_bad) {
+    if (n_chunks < 0 || (n_chunks > 0 && (!d_bases || !chunk_off || !chunk_len || !bases2 || !nmask))) return SD_ERR_PARAM;
+    for (int32_t c = 0; c < n_chunks; ++c)
+        if (chunk_len[c] <= 0 || chunk_off[c] < 0) return SD_ERR_PARAM;
+    if (first_bad) *first_bad = -1;
+    if (n_chunks == 0) return SD_OK;
+    std::string err;
+    int dev = -1;
+    int rc = device_pointer(d_bases, dev, err);
+    if (rc) return rc;
+    if (dev != device) return SD_ERR_UNSUPPORTED;
+    try {
+        SD_HIP(hipSetDevice(device));
+        hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+        const size_t C = (size_t)n_chunks;
+        std::vector<sd::ChunkDesc> tab(C);
+        std::vector<unsigned long long> src(C);
+        std::vector<long long> gpos(C);
+        size_t words = 0, nwords = 0;
+        for (size_t c = 0; c < C; ++c) {
+            tab[c] = sd::ChunkDesc{};
+            tab[c].woff = (uint32_t)words;
+            tab[c].n = chunk_len[c];
+            tab[c].noff = (int32_t)nwords;
+            words += ((size_t)chunk_len[c] + 15) / 16;
+            nwords += ((size_t)chunk_len[c] + 31) / 32;
+            src[c] = (unsigned long long)reinterpret_cast<uintptr_t>(static_cast<const char*>(d_bases) + chunk_off[c]);
+            gpos[c] = chunk_off[c];
+        }
+        if (words >= (1ull << 31)) return SD_ERR_UNSUPPORTED;
+        DevBuf<sd::ChunkDesc> d_tab;
+        DevBuf<unsigned long long> d_src, d_bad;
+        DevBuf<long long> d_gpos;
+        DevBuf<uint32_t> d_w, d_m;
+        d_tab.alloc(C); d_src.alloc(C); d_gpos.alloc(C); d_bad.alloc(1); d_w.alloc(words); d_m.alloc(nwords);
+        unsigned long long bad = ~0ull;
+        // (the caller's words go up first: what the packer leaves alone comes back as it was)
+        SD_HIP(hipMemcpyAsync(d_tab.p, tab.data(), C * sizeof(sd::ChunkDesc), hipMemcpyHostToDevice, st));
+        SD_HIP(hipMemcpyAsync(d_src.p, src.data(), C * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        SD_HIP(hipMemcpyAsync(d_gpos.p, gpos.data(), C * sizeof(long long), hipMemcpyHostToDevice, st));
+        SD_HIP(hipMemcpyAsync(d_bad.p, &bad, sizeof bad, hipMemcpyHostToDevice, st));
+        SD_HIP(hipMemcpyAsync(d_w.p, bases2, words * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        SD_HIP(hipMemcpyAsync(d_m.p, nmask, nwords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        sd::PackDevArgs pa{};
+        pa.chunks = d_tab.p; pa.src = d_src.p; pa.gpos = d_gpos.p; pa.n_chunks = n_chunks;
+        pa.bases2 = d_w.p; pa.nmask = d_m.p; pa.bad = d_bad.p;
+        sd::launch_pack_dev(st, pa);
+        SD_HIP(hipGetLastError());
+        SD_HIP(hipMemcpyAsync(tab.data(), d_tab.p, C * sizeof(sd::ChunkDesc), hipMemcpyDeviceToHost, st));
+        SD_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, st));
+        SD_HIP(hipMemcpyAsync(bases2, d_w.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SD_HIP(hipMemcpyAsync(nmask, d_m.p, nwords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        SD_HIP(hipStreamSynchronize(st));
+        if (has_n)
+            for (size_t c = 0; c < C; ++c) has_n[c] = tab[c].noff >= 0 ? 1 : 0;
+        if (first_bad && bad != ~0ull) *first_bad = (int64_t)(bad >> 8);
+    } catch (const HipFail&) {
+        return SD_ERR_HIP;
+    }
+    return SD_OK;
 }
 
 int sd_engine_run(sd_engine* e, void* hip_stream, char* errbuf, size_t errlen) {

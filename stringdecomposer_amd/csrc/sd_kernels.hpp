@@ -25,4 +25,18 @@ void launch_compact(hipStream_t st, const ChunkDesc* chunks, int n_chunks, const
                     long long epoch = 0,            // one launch (sd_scan_compact); a value no earlier launch on scan_ws has used
                     long long* tickets = nullptr);  // host: tickets drawn from scan_ws so far (advanced by the launch)
 
+// device packer (sd_pack_dev.hip): chunk c = the n bytes at device address src[c] -> bases2 at chunks[c].woff and, if it
+// holds an N, nmask at chunks[c].noff (else chunks[c].noff = -1 is stored); a byte outside A C G T N lowers *bad to
+// ((gpos[c] + index) << 8) | byte (*bad starts as all ones)
+struct PackDevArgs {
+    ChunkDesc* chunks;
+    const unsigned long long* src;
+    const long long* gpos;
+    int n_chunks;
+    uint32_t* bases2;
+    uint32_t* nmask;
+    unsigned long long* bad;
+};
+void launch_pack_dev(hipStream_t st, const PackDevArgs& a);
+
 }  // namespace sd

@@ -224,6 +224,33 @@ struct PinBuf {
     ~PinBuf() { free_(); }
 };
 
+// Where the text of a batch lies when it is already in device memory (load_chunks_impl with a DevSrc: the chunk
+// pointers are device addresses, packed there by sd_pack_dev.hip instead of on host threads).
+struct DevSrc {
+    hipStream_t user = nullptr;      // the caller's stream: the text was produced on it
+    hipEvent_t ready = nullptr;      // recorded on it by the submit: the packer's stream waits for this
+    bool release = true;             // the packer reads the CALLER's buffer: `user` is made to wait for the packer
+    const int64_t* gpos = nullptr;   // per chunk: position of its first byte in the job, reads counted back to back
+    std::shared_ptr<const std::vector<int64_t>> cum;   // n_reads + 1: where each read starts in that numbering
+};
+
+// Is p device memory, and of which device?  SD_ERR_PARAM (with a message) for anything else: host memory, pinned or
+// managed memory, an address the runtime does not know.
+inline int device_pointer(const void* p, int& dev, std::string& err) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        err = "the reads are not in device memory (an address the HIP runtime does not know)";
+        return SD_ERR_PARAM;
+    }
+    if (at.type != hipMemoryTypeDevice) {
+        err = "the reads are not in device memory";
+        return SD_ERR_PARAM;
+    }
+    dev = at.device;
+    return SD_OK;
+}
+
 }  // namespace sdi
 using namespace sdi;
 
@@ -296,8 +323,14 @@ struct sd_engine {
     int* dp_order = nullptr;
     uint32_t* dp_bases2 = nullptr;
     uint32_t* dp_nmask = nullptr;
-    hipEvent_t ev_in = nullptr;       // the H2D copy of the staging buffer has completed
+    hipEvent_t ev_in = nullptr;       // the H2D copy of the staging buffer (device source: the packer) has completed
     bool in_pending = false;
+    // device source (DevSrc): the batch was packed by sd_pack_dev.hip.  Its alphabet flag (all ones, or the smallest
+    // (position << 8 | byte) outside A C G T N) comes back behind the record offsets; dev_cum names the read.
+    bool dev_src = false;
+    unsigned long long* dp_bad = nullptr;
+    PinBuf<unsigned long long> h_bad;
+    std::shared_ptr<const std::vector<int64_t>> dev_cum;
     PinBuf<int64_t> h_roff;           // record offsets of the last run (copied right behind the compaction)
     PinBuf<sd_rec> h_recs;            // compact records of the last fetch
     DevBuf<int32_t> d_B, d_argB, d_cnt;
@@ -377,7 +410,7 @@ struct sd_engine {
 void apply_env_overrides(sd_params& p);
 bool engine_set_identity(sd_engine* e, const std::vector<std::string>& il_seq, const std::vector<int32_t>& own, bool second_best);
 int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr, const std::vector<int32_t>& clen, hipStream_t st,
-                     char* errbuf, size_t errlen);
+                     char* errbuf, size_t errlen, const DevSrc* ds = nullptr);
 int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size_t errlen);
 int fetch_begin(sd_engine* e, int64_t& total, char* errbuf, size_t errlen);
 int fetch_range(sd_engine* e, int64_t r_lo, int64_t r_hi, uint32_t* id_dst, uint32_t* idh_dst, char* errbuf, size_t errlen);
@@ -536,8 +569,9 @@ struct Pipeline {
             fill_st2 = nullptr;
     }
     // slice_end (may be empty): chunk indices at which the batch's identities are cut into slices (sd_engine::slice_end)
+    // ds (may be null): the chunk pointers are device addresses (DevSrc)
     int push(const std::vector<const char*>& cptr, const std::vector<int32_t>& clen, RecSink sink,
-             const std::vector<int>& slice_end = std::vector<int>()) {
+             const std::vector<int>& slice_end = std::vector<int>(), const DevSrc* ds = nullptr) {
         int rc = SD_OK;
         // All slots busy: the oldest batch has to leave its engine first.  Only its device work and the copy of its
         // records are waited for here; its sink (per-read assembly, text) runs AFTER the new batch is packed and
@@ -571,7 +605,7 @@ struct Pipeline {
         }
         tl_push0[k] = t0;
         eng[k]->copy_stream = copy_st[k];
-        rc = load_chunks_impl(eng[k], cptr, clen, copy_st[k] ? copy_st[k] : fill_st, eb, sizeof eb);
+        rc = load_chunks_impl(eng[k], cptr, clen, copy_st[k] ? copy_st[k] : fill_st, eb, sizeof eb, ds);
         hipStream_t fs = (fill_st2 && (pushed & 1)) ? fill_st2 : fill_st;
         eng[k]->lds_gate = fill_st2 != nullptr;
         eng[k]->slice_end = slice_end;

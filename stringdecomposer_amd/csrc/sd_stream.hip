@@ -31,6 +31,17 @@ struct StreamJob : RowJob {
     const char* const* reads = nullptr;
     std::vector<const char*> own;
     int to_pack = 0;
+    // A job whose reads lie in device memory (sd_stream_submit_dev): `own` holds DEVICE addresses, which the entries
+    // hand to the device packer with `ds`; gpos = per chunk of the table, where it starts in the job (DevSrc::gpos).  In
+    // final mode the packers read the job's own device copy of the reads (text, read r at text_off[r], made on the
+    // caller's stream), from which the post-processor's fallback fetches the reads it asks for into seq; rlen = the
+    // read lengths.  The copy goes back to the stream's spare list with the job.
+    bool dev = false;
+    DevSrc ds;
+    std::vector<int64_t> gpos, rlen, text_off;
+    std::unique_ptr<DevBuf<uint8_t>> text;
+    std::vector<std::unique_ptr<DevBuf<uint8_t>>>* spare = nullptr;
+    ~StreamJob() { if (text && spare) spare->push_back(std::move(text)); }
 };
 
 // Final mode: the records of the chunks [c0, c1) are assembled into the rows of the reads they complete, which go through
@@ -49,7 +60,23 @@ static void final_sink(FinalMode& fm, const Pipeline& pipe, StreamJob& j, size_t
     if (r1 == r0) return;
     if (j.rc == SD_OK) {
         std::vector<sd::PostRead> pr;
-        for (size_t r = r0; r < r1; ++r) pr.push_back(sd::PostRead{"", 0, j.seq[r].data(), (int64_t)j.seq[r].size()});
+        for (size_t r = r0; r < r1; ++r)
+            pr.push_back(sd::PostRead{"", 0, j.dev ? nullptr : j.seq[r].data(), j.dev ? j.rlen[r] : (int64_t)j.seq[r].size()});
+        // reads in device memory: the text of these reads comes to the host only if the post-processor asks for it
+        // (its fallback identities, the profiles); the rows have come back, so the job's copy is complete
+        if (j.dev)
+            fm.pp.fetch_text = [&j, &pr, r0, r1](std::string& e) -> int {
+                for (size_t r = r0; r < r1; ++r) {
+                    j.seq[r].resize((size_t)j.rlen[r]);
+                    if (hipMemcpy(&j.seq[r][0], j.text->p + j.text_off[r], (size_t)j.rlen[r], hipMemcpyDeviceToHost) != hipSuccess) {
+                        (void)hipGetLastError();
+                        e = "cannot fetch the text of read " + std::to_string(r) + " from the device";
+                        return SD_ERR_HIP;
+                    }
+                    pr[r - r0].seq = j.seq[r].data();
+                }
+                return SD_OK;
+            };
         // a batch without identities (more records than the outputs had room for) sends these rows to the fallback
         const sd::IdentRef iref{j.bid, fm.second_best ? j.bidh : nullptr, j.rsrc, j.xid.data(), j.xidh.data()};
         try {
@@ -58,6 +85,10 @@ static void final_sink(FinalMode& fm, const Pipeline& pipe, StreamJob& j, size_t
         } catch (const std::bad_alloc&) {
             j.rc = SD_ERR_INTERNAL;
             j.err = "out of host memory";
+        }
+        if (j.dev) {
+            fm.pp.fetch_text = nullptr;
+            for (size_t r = r0; r < r1; ++r) std::string().swap(j.seq[r]);
         }
     }
     j.xid.clear();
@@ -88,6 +119,7 @@ struct StreamEntries {
         std::vector<const char*> cptr;
         std::vector<int32_t> clen;
         std::vector<int> slice_end;
+        std::vector<int64_t> gpos;
         uint64_t seen = 0;           // it has drained for failure `gen` when seen == gen
         int inflight = 0;
         int64_t dealt = 0;
@@ -192,6 +224,11 @@ struct StreamEntries {
         // --second-best: the identities of a batch in slices of whole reads, each handed over as the device finishes it
         // (sd_engine::slice_end), so that the host selects slice s while the device computes slice s + 1
         if (fm && fm->second_best && jp->per) ident_slices(jp->table, q.c0, q.c1, e.slice_end);
+        DevSrc ds;
+        if (jp->dev) {
+            ds = jp->ds;
+            ds.gpos = jp->gpos.data() + q.c0;
+        }
         const int32_t dev = devs[i];
         const size_t c0 = q.c0, c1 = q.c1, b = q.b;
         return pq.push(e.cptr, e.clen, [this, &pq, jp, dev, b, c0, c1](const sd_rec* r, const int64_t* ro, size_t first, size_t n) {
@@ -213,7 +250,7 @@ struct StreamEntries {
                 cv.notify_all();
                 turns.done(b);
             }
-        }, e.slice_end);
+        }, e.slice_end, jp->dev ? &ds : nullptr);
     }
 
     // One action of entry i, on the thread that drives it: push q, pop, or drain (after a failure, and at exit); then the
@@ -318,11 +355,15 @@ struct sd_stream {
     std::vector<std::string> mono;       // owned copies
     std::unique_ptr<FinalMode> fin;      // final mode only
     int sub_batches = 1;
+    std::vector<std::unique_ptr<DevBuf<uint8_t>>> spare;   // device copies of reads (StreamJob::text) between jobs
+    hipEvent_t ev_src = nullptr;         // sd_stream_submit_dev: the caller's stream has produced the job's reads
+    int ev_src_dev = -1;
     std::vector<std::unique_ptr<StreamJob>> jobs;   // FIFO: submitted, not collected yet
     int64_t budget = 0;
     double submit_s = 0, collect_s = 0;
     int64_t n_jobs = 0;
     StreamEntries me;                    // destroyed first: its sinks hold pointers to the jobs
+    ~sd_stream() { if (ev_src) (void)hipEventDestroy(ev_src); }
 };
 
 // The four creates.  who: the name of a call with a device list, which is checked as by sd_run_files_devices; without
@@ -395,8 +436,61 @@ static int stream_wait_oldest(sd_stream* s, char* errbuf, size_t errlen) {
 // pushes them all.  Several: a raw-mode submit returns once every batch of the job has been packed by its entry, so that
 // the caller's read buffers are free (the entries pack from them); a final-mode job packs from its own copy and submit
 // returns at once.  A failure of the stream that this call meets is reported here and drops every job, this one too.
+// Reads in device memory (sd_stream_submit_dev): read r = base[off[r] .. off[r] + read_lens[r]) on device `device`,
+// produced on the stream `user`.
+struct DevIn { const char* base; const int64_t* off; hipStream_t user; int device; };
+
+// The device half of a submit: the job's device addresses and chunk positions; in final mode its own device copy of the
+// reads, made on the caller's stream (so it follows what produced them and precedes what overwrites them); the event
+// on that stream the packers wait for.  Runs with the data's device current.
+static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const int64_t* read_lens, std::string& err) {
+    const size_t n = (size_t)job.n_reads;
+    job.dev = true;
+    auto cum = std::make_shared<std::vector<int64_t>>(n + 1, 0);
+    for (size_t r = 0; r < n; ++r) (*cum)[r + 1] = (*cum)[r] + read_lens[r];
+    job.gpos.reserve(job.table.size());
+    for (const CRef& c : job.table) job.gpos.push_back((*cum)[(size_t)c.read] + c.off);
+    job.ds.user = dv.user;
+    job.ds.cum = cum;
+    job.own.resize(n);
+    try {
+        if (s->fin && n > 0) {
+            // one copy of the span the reads lie in where that is not much more than the reads, else read by read
+            int64_t lo = INT64_MAX, hi = 0;
+            for (size_t r = 0; r < n; ++r) { lo = std::min(lo, dv.off[r]); hi = std::max(hi, dv.off[r] + read_lens[r]); }
+            const bool span = hi - lo <= 2 * (*cum)[n] + ((int64_t)1 << 20);
+            if (!s->spare.empty()) { job.text = std::move(s->spare.back()); s->spare.pop_back(); }
+            else job.text.reset(new DevBuf<uint8_t>);
+            job.spare = &s->spare;
+            job.text->alloc((size_t)(span ? hi - lo : (*cum)[n]));
+            job.rlen.assign(read_lens, read_lens + n);
+            job.text_off.resize(n);
+            for (size_t r = 0; r < n; ++r) job.text_off[r] = span ? dv.off[r] - lo : (*cum)[r];
+            if (span) SD_HIP(hipMemcpyAsync(job.text->p, dv.base + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, dv.user));
+            else
+                for (size_t r = 0; r < n; ++r)
+                    SD_HIP(hipMemcpyAsync(job.text->p + job.text_off[r], dv.base + dv.off[r], (size_t)read_lens[r], hipMemcpyDeviceToDevice, dv.user));
+            for (size_t r = 0; r < n; ++r) job.own[r] = reinterpret_cast<const char*>(job.text->p) + job.text_off[r];
+            job.ds.release = false;   // (the packers read the job's copy: the caller's stream need not wait for them)
+        } else {
+            for (size_t r = 0; r < n; ++r) job.own[r] = dv.base + dv.off[r];
+        }
+        if (s->ev_src && s->ev_src_dev != dv.device) { (void)hipEventDestroy(s->ev_src); s->ev_src = nullptr; }
+        if (!s->ev_src) { SD_HIP(hipEventCreateWithFlags(&s->ev_src, hipEventDisableTiming)); s->ev_src_dev = dv.device; }
+        // (every batch of the job is packed -- its wait for this event enqueued -- before the submit returns, so the
+        // next submit may record the event anew)
+        SD_HIP(hipEventRecord(s->ev_src, dv.user));
+        job.ds.ready = s->ev_src;
+    } catch (const HipFail& f) {
+        err = f.msg;
+        return SD_ERR_HIP;
+    }
+    job.reads = job.own.data();
+    return SD_OK;
+}
+
 static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads,
-                         char* errbuf, size_t errlen) {
+                         char* errbuf, size_t errlen, const DevIn* dv = nullptr) {
     std::unique_ptr<StreamJob> job(new StreamJob);
     job->n_reads = n_reads;
     job->threads = s->p.threads;
@@ -410,7 +504,18 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
     if (!job->row_off) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
     FinalMode* fm = s->fin.get();
     job->reads = read_seqs;
-    if (fm) {   // the fallback identities read the text when the rows come back: the job keeps a copy (sd_hip.h)
+    if (dv) {
+        // the data's device is current while the job's events and copies are made (the entries all run on it)
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (cur != dv->device && hipSetDevice(dv->device) != hipSuccess) { (void)hipGetLastError(); set_err(errbuf, errlen, "hipSetDevice failed"); return SD_ERR_HIP; }
+        std::string err;
+        if (fm) job->seq.resize((size_t)n_reads);
+        const int rd = stream_dev_job(s, *job, *dv, read_lens, err);
+        if (cur >= 0 && cur != dv->device) (void)hipSetDevice(cur);
+        if (rd) { set_err(errbuf, errlen, err); return rd; }
+        if (fm && fm->ident) job->per = fm->second_best ? (int)fm->pp.interleaved_seqs().size() : 1;
+    } else if (fm) {   // the fallback identities read the text when the rows come back: the job keeps a copy (sd_hip.h)
         job->seq.resize((size_t)n_reads);
         sd::parallel_for(n_reads, s->p.threads, 1, [&](int64_t r) { job->seq[(size_t)r].assign(read_seqs[r], (size_t)read_lens[r]); });
         for (const std::string& q : job->seq) job->own.push_back(q.data());
@@ -431,7 +536,7 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
         }
     }
     me.cv.notify_all();
-    const bool at_once = fm && !me.th.empty();
+    const bool at_once = fm && !me.th.empty() && !dv;   // (a device job's packers wait for an event of THIS submit)
     std::string err;
     const int rc = me.wait([&] { return at_once || jp->to_pack == 0; }, err);
     if (rc) {
@@ -481,6 +586,35 @@ int sd_stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* 
     int rc;
     try {
         rc = stream_submit(s, read_seqs, read_lens, n_reads, errbuf, errlen);
+    } catch (const std::bad_alloc&) {
+        set_err(errbuf, errlen, "out of host memory");
+        rc = SD_ERR_INTERNAL;
+    }
+    s->submit_s += now_s() - t0;
+    return rc;
+}
+
+int sd_stream_submit_dev(sd_stream* s, const void* d_bases, const int64_t* read_off, const int64_t* read_lens,
+                         int32_t n_reads, void* hip_stream, char* errbuf, size_t errlen) {
+    if (!s || n_reads < 0 || (n_reads > 0 && (!d_bases || !read_off || !read_lens))) return SD_ERR_PARAM;
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_lens[r] <= 0) { set_err(errbuf, errlen, "ERROR: Sequence #" + std::to_string(r) + " is empty"); return SD_ERR_EMPTY; }
+    const double t0 = now_s();
+    int rc = SD_OK;
+    try {
+        std::string err;
+        DevIn dv{static_cast<const char*>(d_bases), read_off, reinterpret_cast<hipStream_t>(hip_stream), s->me.devs[0]};
+        if (n_reads > 0) {
+            rc = device_pointer(d_bases, dv.device, err);
+            for (size_t i = 0; rc == SD_OK && i < s->me.devs.size(); ++i)
+                if (s->me.devs[i] != dv.device) {
+                    err = "the reads lie in the memory of device " + std::to_string(dv.device) + ", the stream runs on device " +
+                          std::to_string(s->me.devs[i]) + ": copies between devices are not made";
+                    rc = SD_ERR_UNSUPPORTED;
+                }
+            if (rc) set_err(errbuf, errlen, err);
+        }
+        if (rc == SD_OK) rc = stream_submit(s, nullptr, read_lens, n_reads, errbuf, errlen, &dv);
     } catch (const std::bad_alloc&) {
         set_err(errbuf, errlen, "out of host memory");
         rc = SD_ERR_INTERNAL;

@@ -46,6 +46,7 @@ EXPORTS = [
     "sd_stream_create_final", "sd_stream_collect_final", "sd_stream_keys", "sd_stream_final_stats",
     "sd_stream_create_devices", "sd_stream_create_final_devices", "sd_stream_device_stats",
     "sd_profile_segments", "sd_profile_segments_dev", "sd_last_run_profile", "sd_stream_profile",
+    "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev",
 ]
 
 
@@ -205,6 +206,12 @@ def load():
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
+    L.sd_stream_submit_dev.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64), C.c_int32, C.c_void_p,
+                                       C.c_char_p, C.c_size_t]
+    L.sd_engine_load_reads_dev.argtypes = [C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64), C.c_int32, C.c_void_p,
+                                           P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_pack_bases_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, P(C.c_int64)]
     _lib = L
     return L
 
@@ -568,6 +575,16 @@ class Engine:
             pass
 
     def load_reads(self, read_seqs):
+        """Loads a batch: a list of sequences (packed on the host), or a DeviceReads (packed on the device)."""
+        if isinstance(read_seqs, DeviceReads):
+            d = read_seqs
+            self._keep = d
+            n = C.c_int64()
+            self._check(self.L.sd_engine_load_reads_dev(self.h, C.c_void_p(d.ptr), d.c_off, d.c_lens, d.n,
+                                                        C.c_void_p(d.stream), C.byref(n), self._err, 4096))
+            self.n_chunks = n.value
+            self.n_reads = d.n
+            return n.value
         rs = [_b(s) for s in read_seqs]
         self._keep = rs
         rl = (C.c_int64 * max(len(rs), 1))(*[len(s) for s in rs])
@@ -653,6 +670,114 @@ class ReadSet:
         self.ptrs = _strs(self.seqs)
         self.lens = (C.c_int64 * max(self.n, 1))(*[len(s) for s in self.seqs])
         self.bp = sum(len(s) for s in self.seqs)
+
+
+def _device_buffer(data, stream):
+    """(ptr, nbytes, device, stream, shape, strides) of `data`: a (ptr, nbytes, device) tuple, or anything with the
+    tensor interface of torch (data_ptr / is_cuda / dtype / shape / stride / device) -- torch itself is not imported
+    here.  stream=None with a tensor: the current stream of the tensor's device, as the tensor's own module gives it."""
+    if isinstance(data, tuple):
+        if len(data) != 3:
+            raise SdError(SD_ERR_PARAM, "device reads: the tuple form is (ptr, nbytes, device)")
+        ptr, nbytes, device = (int(x) for x in data)
+        return ptr, nbytes, device, int(stream or 0), (nbytes,), (1,)
+    if not hasattr(data, "data_ptr"):
+        raise SdError(SD_ERR_PARAM, "device reads: a tensor on a HIP device or a (ptr, nbytes, device) tuple")
+    if not str(data.dtype).endswith("uint8"):
+        raise SdError(SD_ERR_PARAM, "device reads: the tensor must be uint8, not %s" % data.dtype)
+    if not getattr(data, "is_cuda", False):
+        raise SdError(SD_ERR_PARAM, "device reads: the tensor must lie on a HIP device (a CPU tensor goes in as a read list)")
+    shape = tuple(int(x) for x in data.shape)
+    strides = tuple(int(x) for x in data.stride())
+    if len(shape) not in (1, 2):
+        raise SdError(SD_ERR_PARAM, "device reads: a 1-D tensor of concatenated reads or a 2-D [n, width] tensor of padded rows")
+    if shape[-1] > 1 and strides[-1] != 1:
+        raise SdError(SD_ERR_PARAM, "device reads: the last dimension must be contiguous")
+    if len(shape) == 2 and shape[0] > 1 and strides[0] < 0:
+        raise SdError(SD_ERR_PARAM, "device reads: negative row stride")
+    nbytes = shape[0] if len(shape) == 1 else ((shape[0] - 1) * strides[0] + shape[1] if shape[0] > 0 else 0)
+    device = getattr(data.device, "index", None) or 0
+    if stream is None:
+        import sys
+        mod = sys.modules.get(type(data).__module__.split(".")[0])
+        cur = getattr(getattr(mod, "cuda", None), "current_stream", None)
+        stream = cur(device).cuda_stream if cur is not None else 0
+    return int(data.data_ptr()), int(nbytes), int(device), int(stream or 0), shape, strides
+
+
+class DeviceReads:
+    """Reads that already lie in device memory (sd_stream_submit_dev / sd_engine_load_reads_dev): Stream.submit,
+    Stream.imap and Engine.load_reads take one wherever they take a read list or a ReadSet, and the bases are packed by
+    a HIP kernel instead of host threads.
+
+    data: a 1-D uint8 tensor on a HIP device (the reads back to back; offsets default to the running sum of lens), a
+    2-D [n, width] uint8 tensor of padded rows (offsets default to i * row stride), or a (ptr, nbytes, device) tuple.
+    lens: the read lengths; offsets: where each read starts, in bytes from the start of data (any order, gaps allowed).
+    stream: the hipStream_t (an int) on which the bytes were produced; None = the tensor's device's current stream at
+    this moment (0, the null stream, for the tuple form).  The library orders itself behind that stream and makes the
+    stream wait for its last read of the buffer (sd_hip.h), so the tensor may be overwritten or freed on that stream
+    right after a submit returns.  The object keeps a reference to data."""
+
+    def __init__(self, data, lens, offsets=None, stream=None):
+        self.ptr, self.nbytes, self.device, self.stream, shape, strides = _device_buffer(data, stream)
+        self.data = data
+        self.read_lens = [int(x) for x in lens]
+        self.n = len(self.read_lens)
+        if len(shape) == 2:
+            if offsets is None and self.n > shape[0]:
+                raise SdError(SD_ERR_PARAM, "device reads: %d lengths for %d rows" % (self.n, shape[0]))
+            for i, ln in enumerate(self.read_lens):
+                if ln > shape[1]:
+                    raise SdError(SD_ERR_PARAM, "device reads: read %d is longer (%d) than a row (%d)" % (i, ln, shape[1]))
+        if offsets is None:
+            if len(shape) == 2:
+                self.read_off = [i * strides[0] for i in range(self.n)]
+            else:
+                self.read_off, at = [], 0
+                for ln in self.read_lens:
+                    self.read_off.append(at)
+                    at += ln
+        else:
+            self.read_off = [int(x) for x in offsets]
+            if len(self.read_off) != self.n:
+                raise SdError(SD_ERR_PARAM, "device reads: %d offsets for %d lengths" % (len(self.read_off), self.n))
+        for i, (o, ln) in enumerate(zip(self.read_off, self.read_lens)):
+            if o < 0 or ln < 0 or o + ln > self.nbytes:
+                raise SdError(SD_ERR_PARAM, "device reads: read %d (offset %d, length %d) runs past the buffer (%d bytes)"
+                              % (i, o, ln, self.nbytes))
+        if self.n and not self.ptr:
+            raise SdError(SD_ERR_PARAM, "device reads: null device pointer")
+        self.c_off = (C.c_int64 * max(self.n, 1))(*self.read_off)
+        self.c_lens = (C.c_int64 * max(self.n, 1))(*self.read_lens)
+        self.bp = sum(self.read_lens)
+
+
+def pack_bases_device(data, chunk_off, chunk_len, stream=None, fill=0):
+    """The device packer alone (sd_pack_bases_dev): chunk c = data[chunk_off[c] : chunk_off[c] + chunk_len[c]], data as
+    for DeviceReads (or a DeviceReads).  -> (bases2, nmask, has_n, first_bad): the chunks' 2-bit words back to back,
+    their mask words back to back ((len + 31) // 32 each, written only for chunks that hold an N: the others keep
+    `fill`), has_n per chunk, and the smallest offset of a byte outside ACGTN or -1."""
+    import numpy as np
+    L = load()
+    if isinstance(data, DeviceReads):
+        ptr, nbytes, device, st = data.ptr, data.nbytes, data.device, data.stream if stream is None else int(stream)
+    else:
+        ptr, nbytes, device, st, _, _ = _device_buffer(data, stream)
+    off = np.ascontiguousarray(chunk_off, dtype=np.int64)
+    ln = np.ascontiguousarray(chunk_len, dtype=np.int32)
+    if off.shape != ln.shape or off.ndim != 1:
+        raise SdError(SD_ERR_PARAM, "pack_bases_device: chunk_off and chunk_len differ in length")
+    if len(off) and (off.min() < 0 or ln.min() <= 0 or int((off + ln).max()) > nbytes):
+        raise SdError(SD_ERR_PARAM, "pack_bases_device: a chunk runs past the buffer")
+    w = np.full(int(((ln.astype(np.int64) + 15) // 16).sum()), fill, dtype=np.uint32)
+    m = np.full(int(((ln.astype(np.int64) + 31) // 32).sum()), fill, dtype=np.uint32)
+    hn = np.zeros(max(len(ln), 1), dtype=np.int32)
+    bad = C.c_int64(-1)
+    rc = L.sd_pack_bases_dev(C.c_void_p(ptr), off.ctypes.data, ln.ctypes.data, len(ln), device, C.c_void_p(st),
+                             w.ctypes.data, m.ctypes.data, hn.ctypes.data, C.byref(bad))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_pack_bases_dev")
+    return w, m, hn[:len(ln)], int(bad.value)
 
 
 def final_dtype():
@@ -742,6 +867,11 @@ class Stream:
     def submit(self, reads):
         """Enqueues a job.  The library is done with the read buffers when this returns (a final-mode stream keeps
         its own copy of the reads for the identities it computes later), so `reads` may be dropped at once."""
+        if isinstance(reads, DeviceReads):   # packed on the device; the buffer is free for later work on reads.stream
+            self._check(self.L.sd_stream_submit_dev(self.h, C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n,
+                                                    C.c_void_p(reads.stream), self._err, 4096))
+            self._n_reads.append(reads.n)
+            return
         rs = reads if isinstance(reads, ReadSet) else ReadSet(reads)
         self._check(self.L.sd_stream_submit(self.h, rs.ptrs, rs.lens, rs.n, self._err, 4096))
         self._n_reads.append(rs.n)
@@ -809,7 +939,7 @@ class Stream:
     DEPTH = 2   # jobs outstanding before the oldest is collected: all three engines of the pipeline have a batch then
 
     def imap(self, jobs, as_lists=False, depth=None):
-        """Rows of every job of the iterable `jobs` (read lists / ReadSets), in order, with `depth` later jobs submitted
+        """Rows of every job of the iterable `jobs` (read lists / ReadSets / DeviceReads), in order, with `depth` later jobs submitted
         before a job is collected -- the order of calls that keeps the device busy (sd_hip.h at sd_stream_create: the
         traceback of a batch ends with the fill of the next one, so with only ONE job outstanding the job after that is
         enqueued late; bench.py's timed loop is this generator).
