@@ -522,6 +522,15 @@ int32_t sd_pack_bases(const char* seq, int64_t n, uint32_t* words, uint32_t* nma
 int sd_pack_bases_dev(const void* d_bases, const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks,
                       int32_t device, void* hip_stream, uint32_t* bases2, uint32_t* nmask, int32_t* has_n,
                       int64_t* first_bad);
+/* The --ed_thr prefilter's result alone, on the host (for tests): valid after sd_engine_fetch of a batch run with
+ * ed_thr > -1, else SD_ERR_PARAM.  dist[chunk][T]: the infix edit distance of every template against every chunk, chunks
+ * in the order of sd_engine_fetch; rank[chunk][T]: the template's position in the chunk's filtered order (by distance,
+ * then index; the first and every distance <= ed_thr kept), 0xffff = dropped -- decoded here from the table the engine's
+ * kernel family reads (rank table, per-lane constants, or compacted kept list); after a batch that a guard trip made the
+ * engine repeat, the tables of the repeat.  cap: entries each array has room for (>= n_chunks x T, both returned through
+ * n_chunks / n_templates, which may be NULL).  Launches nothing; the copies happen inside this call only. */
+int sd_engine_filter_result(sd_engine* e, int32_t* dist, uint16_t* rank, int64_t cap, int64_t* n_chunks,
+                            int32_t* n_templates, char* errbuf, size_t errlen);
 /* Self-test of the file writer behind sd_run_files (no device): n_parts parts of part_bytes bytes appended to
  * `path` in two calls, read back and compared.  fail_reserve != 0 makes the page reservation of the mapped
  * (tmpfs) path fail, as on a full /dev/shm -- the text must then arrive through the pwritev loop, which reports

@@ -420,6 +420,7 @@ static void engine_alloc_batch(sd_engine* e, int64_t nck) {
 int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
                      const std::vector<int32_t>& clen, hipStream_t st, char* errbuf, size_t errlen, const DevSrc* ds) {
     e->ran = false;
+    e->fetched = false;
     e->dev_src = ds != nullptr;
     e->dev_cum = ds ? ds->cum : nullptr;
     e->chunks.clear();
@@ -770,6 +771,7 @@ int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size
     e->run_st = st;
     e->run_ts = ts;
     e->ran = true;
+    e->fetched = false;
     return SD_OK;
 }
 
@@ -1510,6 +1512,59 @@ int sd_engine_fetch(sd_engine* e, sd_rec** recs, int64_t** rec_off, char* errbuf
     if (total > 0) std::memcpy(out, e->h_recs.p, sizeof(sd_rec) * (size_t)total);
     *recs = out;
     *rec_off = off;
+    e->fetched = true;
+    return SD_OK;
+}
+
+// The prefilter's tables of the run whose rows the last sd_engine_fetch brought (a batch repeated after a guard trip: the
+// repeat's -- the engine's family and plan are those of the repeat, and it wrote the tables last).  No kernel: copies
+// and a host decode of whichever rank form sd_rank_keep wrote for the family.
+int sd_engine_filter_result(sd_engine* e, int32_t* dist, uint16_t* rank, int64_t cap, int64_t* n_chunks, int32_t* n_templates,
+                            char* errbuf, size_t errlen) {
+    if (!e) return SD_ERR_PARAM;
+    if (e->p.ed_thr < 0) { set_err(errbuf, errlen, "sd_engine_filter_result: the engine runs without --ed_thr"); return SD_ERR_PARAM; }
+    if (!e->ran || !e->fetched) { set_err(errbuf, errlen, "sd_engine_filter_result before sd_engine_fetch"); return SD_ERR_PARAM; }
+    const size_t C = e->chunks.size(), T = (size_t)e->T;
+    if (n_chunks) *n_chunks = (int64_t)C;
+    if (n_templates) *n_templates = e->T;
+    if (!dist || !rank || cap < (int64_t)(C * T)) {
+        set_err(errbuf, errlen, "sd_engine_filter_result: room for n_chunks x n_templates entries is needed");
+        return SD_ERR_PARAM;
+    }
+    if (C == 0) return SD_OK;
+    try {
+        SD_HIP(hipSetDevice(e->device));
+        SD_HIP(hipEventSynchronize(e->ev_run1));
+        SD_HIP(hipMemcpy(dist, e->d_dist.p, C * T * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (e->family == 1) {   // rank table [chunk][T], 0xffff = dropped
+            SD_HIP(hipMemcpy(rank, e->d_grank.p, C * T * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        } else if (compacted(e)) {
+            // the kept templates of a chunk in their filtered order, behind them the 0xffff the launcher filled (d_kpos
+            // and d_nkept are not read: the tiled layout turns them into first lanes / lanes used, sd_tiled_place)
+            std::vector<uint16_t> kl(C * T);
+            SD_HIP(hipMemcpy(kl.data(), e->d_klist.p, C * T * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            std::fill(rank, rank + C * T, (uint16_t)0xffff);
+            for (size_t c = 0; c < C; ++c)
+                for (size_t r = 0; r < T && kl[c * T + r] != 0xffff; ++r) {
+                    if (kl[c * T + r] >= T) { set_err(errbuf, errlen, "sd_engine_filter_result: template index beyond the set in the kept list"); return SD_ERR_INTERNAL; }
+                    rank[c * T + kl[c * T + r]] = (uint16_t)r;
+                }
+        } else {
+            // per-lane constants of the ranked fills: the rank at the lane that holds the template's end (sd_rank_keep)
+            const size_t W = (size_t)e->fplan.waves;
+            std::vector<uint16_t> cr(C * W * 64 * 2);
+            SD_HIP(hipMemcpy(cr.data(), e->d_crank.p, cr.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            for (size_t c = 0; c < C; ++c)
+                for (size_t j = 0; j < T; ++j) {
+                    const int v = e->fplan.end_vlane[j];
+                    const size_t at = ((c * W + (size_t)(v >> 7)) * 64 + (size_t)(v & 63)) * 2 + (size_t)((v >> 6) & 1);
+                    rank[c * T + j] = cr[at] == 0x7fff ? (uint16_t)0xffff : cr[at];
+                }
+        }
+    } catch (const HipFail& f) {
+        set_err(errbuf, errlen, f.msg);
+        return SD_ERR_HIP;
+    }
     return SD_OK;
 }
 

@@ -379,6 +379,7 @@ struct sd_engine {
     hipStream_t copy_stream = nullptr;   // pipeline: H2D of the batch / D2H of its records (not owned)
     bool lds_gate = false;               // pipeline mode 2: the fill asks for LDS that admits two workgroups per CU only
     bool ran = false;
+    bool fetched = false;                // sd_engine_fetch brought the rows of the last run (sd_engine_filter_result reads its tables)
     bool replanned = false;              // a guard trip made this engine give up the layout it was created with
     std::vector<hipEvent_t> ev_fill, ev_trace;  // pairs
     hipEvent_t ev_run0 = nullptr, ev_run1 = nullptr, ev_cmp0 = nullptr, ev_cmp1 = nullptr;

@@ -46,7 +46,7 @@ EXPORTS = [
     "sd_stream_create_final", "sd_stream_collect_final", "sd_stream_keys", "sd_stream_final_stats",
     "sd_stream_create_devices", "sd_stream_create_final_devices", "sd_stream_device_stats",
     "sd_profile_segments", "sd_profile_segments_dev", "sd_last_run_profile", "sd_stream_profile",
-    "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev",
+    "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev", "sd_engine_filter_result",
 ]
 
 
@@ -212,6 +212,8 @@ def load():
                                            P(C.c_int64), C.c_char_p, C.c_size_t]
     L.sd_pack_bases_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, P(C.c_int64)]
+    L.sd_engine_filter_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64), P(C.c_int32),
+                                          C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -647,6 +649,20 @@ class Engine:
         v = (C.c_int64 * 8)()
         self.L.sd_engine_info(self.h, v)
         return _info_dict(v)
+
+    def filter_result(self):
+        """The --ed_thr prefilter's result of the fetched batch (sd_engine_filter_result, for tests) -> (dist, rank):
+        int32 / uint16 arrays [n_chunks, T]; rank = place in the chunk's filtered order, 0xffff = dropped."""
+        import numpy as np
+        T = int(self.info()["n_templates"])
+        dist = np.empty((self.n_chunks, T), dtype=np.int32)
+        rank = np.empty((self.n_chunks, T), dtype=np.uint16)
+        n, t = C.c_int64(), C.c_int32()
+        self._check(self.L.sd_engine_filter_result(self.h, dist.ctypes.data, rank.ctypes.data, dist.size, C.byref(n),
+                                                   C.byref(t), self._err, 4096))
+        if (n.value, t.value) != dist.shape:
+            raise SdError(SD_ERR_INTERNAL, "filter_result: %d x %d, expected %d x %d" % ((n.value, t.value) + dist.shape))
+        return dist, rank
 
 
 def _info_dict(v):

@@ -1,7 +1,8 @@
 """Test infrastructure: identity of a (query, target) pair as stringdecomposer/main.py:29-60 gets it from
 python-edlib -- through the reference's vendored edlib (oracle/_ref/libedlib.so, compiled from
 /root/reference by `make -C oracle ref`; it travels to the GPU box) when present, else through the
-oracle's own full-matrix NW (oracle/sd_oracle.c: sdo_nw_identity, pinned against edlib on CPU)."""
+oracle's own full-matrix NW (oracle/sd_oracle.c: sdo_nw_identity, pinned against edlib on CPU).  hw(): the infix
+distance of the --ed_thr prefilter (main.cpp:128-133) the same way."""
 import ctypes
 import os
 
@@ -53,6 +54,20 @@ def nw(q, t):
     r = ed.edlibAlign(q, len(q), t, len(t), _Cfg(-1, 0, 2, None, 0))
     m = bytes(r.alignment[:r.alignmentLength]).count(b"\x00")
     out = (r.editDistance, m, r.alignmentLength)
+    ed.edlibFreeAlignResult(r)
+    return out
+
+
+def hw(t, x):
+    """Edit distance of edlibAlign(t, x, k = -1, EDLIB_MODE_HW, EDLIB_TASK_DISTANCE) as MonomerEditDistance calls it
+    (main.cpp:129): template t anywhere inside text x.  Without the library: the oracle's sdo_hw_edit_distance."""
+    t = t.encode() if isinstance(t, str) else t
+    x = x.encode() if isinstance(x, str) else x
+    if not have_edlib():
+        return oracle.hw_edit_distance(t, x)
+    ed = _edlib()
+    r = ed.edlibAlign(t, len(t), x, len(x), _Cfg(-1, 2, 0, None, 0))
+    out = r.editDistance
     ed.edlibFreeAlignResult(r)
     return out
 
