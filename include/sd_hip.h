@@ -67,6 +67,9 @@ typedef struct sd_params {
 #define SD_FLAG_PROFILE 512        /* sd_run_files*, final-mode streams: per-monomer column profiles of the kept rows
                                       (sd_last_run_profile / sd_stream_profile); a repeated monomer name is SD_ERR_PARAM */
 
+#define SD_FLAG_DEVICE_ROWS 1024   /* raw-mode streams with one device entry: the rows of a job are assembled on the device and
+                                      stay there (sd_stream_peek_dev / sd_stream_collect_dev); no record crosses to the host */
+
 void sd_params_default(sd_params* p); /* -1,-1,-1,1 / 5000 / 500 / -1 / 1 / 0 / auto */
 
 /* One monomer alignment = one raw TSV row (MonomerAlignment, main.cpp:37-49), chunk-local or
@@ -334,6 +337,17 @@ int sd_engine_fetch(sd_engine* e, sd_rec** recs, int64_t** rec_off, char* errbuf
 int sd_engine_assemble(sd_engine* e, const sd_rec* recs, const int64_t* rec_off, sd_rec** rows,
                        int64_t** row_off, char* errbuf, size_t errlen);
 
+/* The same assembly on the DEVICE, straight on the compact records of the last run (csrc/sd_rows_dev.hip): after the
+ * call -- which waits for the run as sd_engine_fetch does, a guard trip's repeat included -- d_rows[0 .. *n_rows) holds the
+ * rows sd_engine_assemble makes of sd_engine_fetch's records (scores in the caller's scale) and d_row_off the n_reads + 1
+ * offsets.  Both are DEVICE buffers of the caller's, on the engine's device.  Every kernel is enqueued on hip_stream (the
+ * stream the buffers are used on), so later work on it follows; the call returns when the host knows *n_rows (one 8-byte
+ * copy).  cap_rows < *n_rows: SD_ERR_PARAM, *n_rows set, nothing written, and the call may be repeated with room: the
+ * assembly of a run is made once, the repeat only copies -- so a first call with cap_rows = 0 (d_rows NULL) is how a
+ * caller learns the exact size without any record crossing to the host. */
+int sd_engine_rows_dev(sd_engine* e, sd_rec* d_rows, int64_t cap_rows, int64_t* d_row_off, void* hip_stream, int64_t* n_rows,
+                       char* errbuf, size_t errlen);
+
 /* HIP-event timings (ms) of the last completed sd_engine_run, measured on its stream:
  * [0] fill kernel(s)  [1] traceback kernel(s)  [2] compaction  [3] whole run.  */
 int sd_engine_timings(sd_engine* e, float ms[4]);
@@ -416,6 +430,29 @@ int sd_stream_submit_dev(sd_stream* s, const void* d_bases, const int64_t* read_
  * coordinates, seam-merged.  Both arrays are malloc'ed (sd_free). */
 int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n_rows, char* errbuf,
                       size_t errlen);
+/* ---- rows that stay on the device (SD_FLAG_DEVICE_ROWS in sd_params.reserved[1] at create) ---------------------
+ * The counterpart of sd_stream_submit_dev: every batch's compact records are appended, on the device and behind the
+ * batch's compaction, to a record store the job keeps in HBM (chunk offsets added, scores in the caller's scale); after
+ * the job's last batch the seam merge runs there in pieces (csrc/sd_seam_dev.hpp, sd_rows_dev.hip).  No record is copied
+ * to the host and no host thread assembles anything (sd_stream_stats [9] stays 0); the per-chunk record counts still
+ * come back, as they always did.  A read that spans several batches is just a longer record list.
+ * Raw mode with ONE device entry only: the flag is SD_ERR_PARAM at sd_stream_create_final* (final rows are selected on
+ * the host) and with a device list of more than one entry (a job's batches would lie on several devices).
+ * sd_stream_collect on such a stream and sd_stream_collect_dev on a plain one are SD_ERR_PARAM.
+ *
+ * sd_stream_peek_dev waits for the oldest job (FIFO) and gives what its buffers need: *n_reads, and *max_rows = its
+ * record count before the merge, an upper bound on its rows.  The job stays.
+ * sd_stream_collect_dev hands the oldest job over: d_rows[0 .. *n_rows) = its rows, read-global and seam-merged, as
+ * sd_stream_collect gives them; d_row_off = the n_reads + 1 offsets.  Both are DEVICE buffers of the caller's on the
+ * stream's device (checked for d_rows: SD_ERR_PARAM / SD_ERR_UNSUPPORTED as in sd_stream_submit_dev).  hip_stream (NULL =
+ * the null stream) is the stream the caller uses the buffers on: the library's copy into them is enqueued on hip_stream
+ * itself, behind an event of its own stream's assembly, so it follows what the caller enqueued before (the allocation,
+ * an earlier use) and precedes what the caller enqueues afterwards -- no host-side wait for it.  The call returns when the
+ * host knows *n_rows, which takes one 8-byte copy.  cap_rows < *n_rows: SD_ERR_PARAM with *n_rows set, nothing is written
+ * and the job stays collectable.  The buffers are the caller's alone from then on: a later job does not touch them. */
+int sd_stream_peek_dev(sd_stream* s, int32_t* n_reads, int64_t* max_rows, char* errbuf, size_t errlen);
+int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_t* d_row_off, void* hip_stream,
+                          int64_t* n_rows, char* errbuf, size_t errlen);
 /* Accumulated over all collected batches: [0] fill [1] traceback [2] compaction [3] whole-run HIP-event
  * ms (per-batch spans; batches on the two streams overlap, so these do not add up to wall time),
  * [4] fill launches [5] batches [6] chunk rows, host ms: [7] pack+enqueue [8] wait for the device
@@ -522,6 +559,16 @@ int32_t sd_pack_bases(const char* seq, int64_t n, uint32_t* words, uint32_t* nma
 int sd_pack_bases_dev(const void* d_bases, const int64_t* chunk_off, const int32_t* chunk_len, int32_t n_chunks,
                       int32_t device, void* hip_stream, uint32_t* bases2, uint32_t* nmask, int32_t* has_n,
                       int64_t* first_bad);
+/* The assembly kernels alone (for tests): read r = d_recs[d_read_off[r] .. d_read_off[r + 1]), records already in
+ * read-global coordinates, d_read_off[0] = 0; all four arrays in the memory of `device`, d_rows with room for every
+ * record.  piece = records per piece of the merge, 0 = the production value, 1..7 SD_ERR_PARAM (a step of the merge
+ * reaches 8 records ahead).  Runs on hip_stream and returns when it is done.  SD_ERR_NO_DEVICE without a device. */
+int sd_seam_merge_dev(const sd_rec* d_recs, const int64_t* d_read_off, int32_t n_reads, int32_t piece, int32_t device,
+                      void* hip_stream, sd_rec* d_rows, int64_t* d_row_off, int64_t* n_rows);
+/* Host only: the same piece functions (exit tables, their composition, keep flags) run by the host, read by read; the
+ * rows must equal sd_seam_merge's.  Arguments as above, in host memory. */
+int sd_seam_pieces_selftest(const sd_rec* recs, const int64_t* read_off, int32_t n_reads, int32_t piece, sd_rec* rows,
+                            int64_t* row_off, int64_t* n_rows);
 /* The --ed_thr prefilter's result alone, on the host (for tests): valid after sd_engine_fetch of a batch run with
  * ed_thr > -1, else SD_ERR_PARAM.  dist[chunk][T]: the infix edit distance of every template against every chunk, chunks
  * in the order of sd_engine_fetch; rank[chunk][T]: the template's position in the chunk's filtered order (by distance,

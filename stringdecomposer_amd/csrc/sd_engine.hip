@@ -421,6 +421,7 @@ int load_chunks_impl(sd_engine* e, const std::vector<const char*>& cptr,
                      const std::vector<int32_t>& clen, hipStream_t st, char* errbuf, size_t errlen, const DevSrc* ds) {
     e->ran = false;
     e->fetched = false;
+    e->rows_done = false;
     e->dev_src = ds != nullptr;
     e->dev_cum = ds ? ds->cum : nullptr;
     e->chunks.clear();
@@ -772,6 +773,7 @@ int engine_run2(sd_engine* e, hipStream_t st, hipStream_t ts, char* errbuf, size
     e->run_ts = ts;
     e->ran = true;
     e->fetched = false;
+    e->rows_done = false;
     return SD_OK;
 }
 

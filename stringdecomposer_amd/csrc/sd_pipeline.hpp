@@ -196,6 +196,7 @@ struct DevBuf {
         if (!h.empty()) SD_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     }
     size_t bytes() const { return cap * sizeof(T); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(dev, o.dev); std::swap(cap, o.cap); }
     ~DevBuf() { free_(); }
 };
 
@@ -223,6 +224,55 @@ struct PinBuf {
     }
     ~PinBuf() { free_(); }
 };
+
+// Row assembly on the device (sd_rows_dev.hip; SD_FLAG_DEVICE_ROWS streams, sd_engine_rows_dev, sd_seam_merge_dev): the
+// record store of one job -- its compact records in chunk-table order, read-global coordinates, scores scaled -- and
+// the workspace of the piecewise seam merge (sd_seam_dev.hpp).  Every device stage of a job runs on one stream in the
+// order append* (rows_append, one per batch) -> rows_assemble (exit tables, chain, keep flags, counts; the row count
+// travels to h_total behind it and ev_asm is recorded) -> rows_scatter (kept records and row offsets into the caller's
+// buffers, on the CALLER's stream; ev_free is recorded behind it).  The scatter reads the store and the workspace
+// whenever the caller's stream gets to it, and a block a DevBuf gives up goes to a pool any engine of the process may
+// take it from, so the HOST waits for ev_free before any of these buffers can be reallocated or released: a stream
+// hands a workspace to a new job only once ev_free has completed (rows_idle), and the destructor waits for it.
+struct RowsWS {
+    DevBuf<sd::DevRec> recs;         // the store
+    DevBuf<int32_t> add;             // per chunk of the job: its offset in its read
+    DevBuf<int64_t> off;             // [read -> first record (n_reads + 1)][read -> first piece (n_reads + 1)]
+    DevBuf<uint32_t> exits;          // per piece: exit table
+    DevBuf<uint8_t> entry, keep;     // per piece: true entry; per record: keep flag
+    DevBuf<int32_t> bsum;            // kept records per tile of ROWS_TILE records
+    DevBuf<int64_t> bbase;           // rows before each tile; [tiles] = the row count
+    PinBuf<int32_t> h_add;
+    PinBuf<int64_t> h_off, h_total;
+    hipEvent_t ev_asm = nullptr, ev_free = nullptr;
+    bool free_recorded = false;      // ev_free has been recorded: a scatter may still read the buffers
+    bool settled = true;             // the host has seen the end of everything enqueued on the buffers (or nothing was)
+    int64_t n_recs = 0, n_pieces = 0, n_tiles = 0;
+    int32_t n_reads = 0, piece = 0;
+    // no scatter can still read the buffers (host-side: true at once when none was enqueued or it has completed)
+    bool idle() {
+        if (free_recorded && hipEventQuery(ev_free) != hipErrorNotReady) { (void)hipGetLastError(); free_recorded = false; }
+        return !free_recorded;
+    }
+    void wait_idle() {
+        if (free_recorded) { if (hipEventSynchronize(ev_free) != hipSuccess) (void)hipGetLastError(); free_recorded = false; }
+    }
+    ~RowsWS() {
+        wait_idle();   // (the members' blocks go to the pool right after this body)
+        if (ev_asm) (void)hipEventDestroy(ev_asm);
+        if (ev_free) (void)hipEventDestroy(ev_free);
+    }
+};
+constexpr int ROWS_PIECE = 16;       // records per piece in production (a test entry takes its own)
+// (all three throw HipFail)
+// records of a batch (chunk-local, as the compaction left them: dense / d_roff, n_chunks chunks) into ws.recs at `base`
+// with the chunks' offsets d_add added and the scores scaled; ws.recs must have room
+void rows_append(RowsWS& ws, hipStream_t st, const sd::DevRec* dense, const int64_t* d_roff, int n_chunks,
+                 const int32_t* d_add, int64_t base, int scale);
+// the merge of `recs` (read-global; read r = records [read_off[r], read_off[r + 1]), a HOST array) up to the row count
+void rows_assemble(RowsWS& ws, hipStream_t st, const sd::DevRec* recs, const int64_t* read_off, int32_t n_reads, int piece);
+// the kept records into rows[0 .. cap) and the n_reads + 1 row offsets
+void rows_scatter(RowsWS& ws, hipStream_t st, const sd::DevRec* recs, sd::DevRec* rows, int64_t cap, int64_t* row_off);
 
 // Where the text of a batch lies when it is already in device memory (load_chunks_impl with a DevSrc: the chunk
 // pointers are device addresses, packed there by sd_pack_dev.hip instead of on host threads).
@@ -337,6 +387,8 @@ struct sd_engine {
     DevBuf<sd::DevRec> d_recs, d_dense;
     DevBuf<int64_t> d_roff;
     int64_t dense_cap = 0;
+    std::unique_ptr<RowsWS> rows_ws;  // sd_engine_rows_dev: the batch's rows assembled on the device
+    bool rows_done = false;           // ... and rows_ws holds the assembly of the LAST run (a load or a run clears it)
     // in-stream identities of the final TSV (sd_ident.hip), set up by engine_set_identity: 0 off, 1 the record's
     // own template (main.py:112-116), 2 every template, plain and homopolymer-compressed (--second-best)
     int ident_mode = 0;
@@ -427,6 +479,11 @@ int fetch_whole(sd_engine* e, int64_t total, char* errbuf, size_t errlen);
 // recs of the chunks [first, first + n) of a batch (word 0 = the first record of chunk `first`), their offsets (n + 1,
 // relative to recs); a batch arrives in one call (first = 0) or, with identity slices, in one call per slice
 using RecSink = std::function<void(const sd_rec*, const int64_t*, size_t, size_t)>;
+// A batch whose records stay on the device (SD_FLAG_DEVICE_ROWS): called by pop_fetch in place of the copy to the host,
+// after fetch_begin has settled the run (a guard trip's repeat included) and before the slot can take another batch;
+// what it enqueues on the given stream (the pipeline's rows_st) is waited for before the engine is loaded again.  `total`
+// = the batch's record count; the record offsets are in the engine's h_roff.  Returns an SD_* code, message in eb.
+using DevSink = std::function<int(sd_engine*, int64_t, hipStream_t)>;
 namespace sdi {
 
 // What a pipeline accumulates over its batches: HIP-event kernel times (ms), host stage times (s) and counts.  The
@@ -464,6 +521,10 @@ struct Pipeline {
     hipStream_t trace_st = nullptr;                // traceback + compaction of all batches (lower priority)
     bool streams_tried = false;
     RecSink sinks[NSMAX];
+    DevSink dev_sinks[NSMAX];
+    hipStream_t rows_st = nullptr;                 // device sinks: appends to the jobs' record stores, their assembly
+    hipEvent_t rows_ev[NSMAX] = {nullptr, nullptr, nullptr};   // per slot: its device sink's work is done
+    bool rows_pending[NSMAX] = {false, false, false};
     std::function<void(sd_engine*)> on_engine;     // called once for every engine the pipeline creates
     // identities that came with the batch a sink is being called for (in-stream, sd_ident.hip); id == nullptr: none
     // a sink may TAKE the blocks (take_ident: they are then its to give back to g_pinpool): the engine fetches its
@@ -571,8 +632,9 @@ struct Pipeline {
     }
     // slice_end (may be empty): chunk indices at which the batch's identities are cut into slices (sd_engine::slice_end)
     // ds (may be null): the chunk pointers are device addresses (DevSrc)
+    // dsink (may be null): the batch's records stay on the device (DevSink); `sink` is still called, with no records
     int push(const std::vector<const char*>& cptr, const std::vector<int32_t>& clen, RecSink sink,
-             const std::vector<int>& slice_end = std::vector<int>(), const DevSrc* ds = nullptr) {
+             const std::vector<int>& slice_end = std::vector<int>(), const DevSrc* ds = nullptr, DevSink dsink = nullptr) {
         int rc = SD_OK;
         // All slots busy: the oldest batch has to leave its engine first.  Only its device work and the copy of its
         // records are waited for here; its sink (per-read assembly, text) runs AFTER the new batch is packed and
@@ -596,6 +658,16 @@ struct Pipeline {
             if (on_engine) on_engine(eng[k]);
         }
         make_streams();
+        if (dsink && !rows_st && hipStreamCreateWithFlags(&rows_st, hipStreamNonBlocking) != hipSuccess) {
+            (void)hipGetLastError();
+            rows_st = nullptr;
+            std::snprintf(eb, sizeof eb, "cannot create the stream of the device rows");
+            return SD_ERR_HIP;
+        }
+        if (rows_pending[k]) {   // the slot's last batch is still being appended from the engine's buffers
+            rows_pending[k] = false;
+            if (hipEventSynchronize(rows_ev[k]) != hipSuccess) { std::snprintf(eb, sizeof eb, "appending a batch's records on the device failed"); return SD_ERR_HIP; }
+        }
         const double t0 = now_s();
         if (timeline && !tl_ref && fill_st) {
             if (hipEventCreate(&tl_ref) == hipSuccess) {
@@ -615,6 +687,7 @@ struct Pipeline {
         tl_push1[k] = now_s();
         if (rc) return rc;
         sinks[k] = std::move(sink);
+        dev_sinks[k] = std::move(dsink);
         ++pushed;
         return SD_OK;
     }
@@ -638,7 +711,9 @@ struct Pipeline {
         const double t0 = now_s();
         int rc = fetch_begin(e, total, eb, sizeof eb);
         const bool sliced = rc == SD_OK && e->sliced_run && e->ident_valid && !e->chunks.empty();
-        if (rc == SD_OK && !sliced && !e->chunks.empty()) rc = fetch_whole(e, total, eb, sizeof eb);
+        DevSink dfn = std::move(dev_sinks[k]);
+        dev_sinks[k] = nullptr;
+        if (rc == SD_OK && !sliced && !e->chunks.empty()) rc = dfn ? dev_sink(e, k, total, dfn) : fetch_whole(e, total, eb, sizeof eb);
         cnt.wait_s += now_s() - t0;
         ++popped;
         RecSink fn = std::move(sinks[k]);
@@ -651,10 +726,24 @@ struct Pipeline {
         book_batch(e, k, total);
         if (sliced) return rc;
         sink_slot = k;
+        sink_dev = dfn != nullptr;
         sink_fn = std::move(fn);
         sink_chunks = e->chunks.size();
         sink_roff.assign(e->h_roff.p, e->h_roff.p + sink_chunks + 1);
         return SD_OK;
+    }
+    bool sink_dev = false;       // ... and its records stayed on the device: its sink assembles nothing
+    // a batch whose records stay on the device: its device sink, and the event the slot's next load waits for
+    int dev_sink(sd_engine* e, int k, int64_t total, const DevSink& dfn) {
+        const int rc = dfn(e, total, rows_st);
+        if (!rows_ev[k] && hipEventCreateWithFlags(&rows_ev[k], hipEventDisableTiming) != hipSuccess) rows_ev[k] = nullptr;
+        if (!rows_ev[k] || hipEventRecord(rows_ev[k], rows_st) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(rows_st);
+        } else {
+            rows_pending[k] = true;
+        }
+        return rc;
     }
     // a sliced batch: every slice is fetched and handed to `fn` as its event completes, then the run's end is awaited
     int hand_over_slices(sd_engine* e, int64_t total, const RecSink& fn) {
@@ -757,10 +846,13 @@ struct Pipeline {
         sink_fn = nullptr;
         cur_ident = IdentOut{};
         cur_engine = nullptr;
-        cnt.sink_s += now_s() - t0;
+        if (!sink_dev) cnt.sink_s += now_s() - t0;   // (records that stayed on the device: no assembly on the host)
+        sink_dev = false;
     }
     ~Pipeline() {
         if (inflight() > 0) (void)hipDeviceSynchronize();  // nothing may still run on buffers we free
+        if (rows_st) { (void)hipStreamSynchronize(rows_st); (void)hipStreamDestroy(rows_st); }
+        for (hipEvent_t ev : rows_ev) if (ev) (void)hipEventDestroy(ev);
         for (sd_engine* e : eng)
             if (e) sd_engine_destroy(e);
         for (hipStream_t s2 : {copy_st[0], copy_st[1], copy_st[2], fill_st, fill_st2, trace_st})

@@ -41,8 +41,79 @@ struct StreamJob : RowJob {
     std::vector<int64_t> gpos, rlen, text_off;
     std::unique_ptr<DevBuf<uint8_t>> text;
     std::vector<std::unique_ptr<DevBuf<uint8_t>>>* spare = nullptr;
-    ~StreamJob() { if (text && spare) spare->push_back(std::move(text)); }
+    // A job of a device-rows stream (SD_FLAG_DEVICE_ROWS): ws = its record store and merge workspace (RowsWS), taken
+    // from and given back to the stream's list.  Layout of the store: the compact records of the job's chunks in
+    // chunk-table order, back to back across its batches, already in read coordinates and the caller's score scale;
+    // appended = records in it, rec_at[c] = first record of chunk c (from the batches' host-side record offsets).
+    // rows_batch appends a batch and, behind the last one, enqueues the merge.
+    std::unique_ptr<RowsWS> ws;
+    std::vector<std::unique_ptr<RowsWS>>* ws_home = nullptr;
+    std::vector<int64_t> rec_at;
+    int64_t appended = 0;
+    bool ws_begun = false, assembled = false;
+    ~StreamJob() {
+        if (text && spare) spare->push_back(std::move(text));
+        if (ws && ws_home) ws_home->push_back(std::move(ws));
+    }
 };
+
+// Device rows: the records of the batch [c0, c1) of job j, still in engine e's buffers after fetch_begin (total of them,
+// offsets in e->h_roff), are appended to the job's store on `st`; behind the job's last batch the merge is enqueued.
+static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st, size_t c0, size_t c1, char* eb, size_t eblen) {
+    RowsWS& ws = *j.ws;
+    const size_t C = c1 - c0, CJ = j.table.size();
+    try {
+        if (!j.ws_begun) {
+            j.ws_begun = true;
+            // The workspace's last user: its scatter ran on ITS caller's stream and reads these buffers; every alloc
+            // below may give a block up to the pool, so the HOST has to have seen that scatter end (stream_take_ws
+            // hands out idle workspaces: this returns at once).  A job that was dropped never settled.
+            ws.wait_idle();
+            if (!ws.settled) { SD_HIP(hipStreamSynchronize(st)); ws.settled = true; }
+            ws.h_add.alloc(CJ);
+            for (size_t c = 0; c < CJ; ++c) ws.h_add.p[c] = (int32_t)j.table[c].off;   // (main.cpp:109-111)
+            ws.add.alloc(CJ);
+            ws.settled = false;
+            SD_HIP(hipMemcpyAsync(ws.add.p, ws.h_add.p, CJ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            j.rec_at.assign(1, 0);
+            j.rec_at.reserve(CJ + 1);
+        }
+        const int64_t need = j.appended + total;
+        if ((size_t)need > ws.recs.cap) {
+            if (j.appended == 0) {
+                // the first batch sizes the store for the whole job by its share of the chunks, with a quarter to spare
+                // (short chunks first: the store grows below)
+                const double share = C < CJ ? 1.25 * (double)CJ / (double)std::max<size_t>(C, 1) : 1.0;
+                ws.recs.alloc((size_t)((double)need * share) + (C < CJ ? 64 : 0));
+            } else {
+                // a later batch outgrew it: a larger block, the records so far copied over; the old block leaves with
+                // nothing in flight on it
+                DevBuf<sd::DevRec> grown;
+                grown.alloc(std::max<size_t>((size_t)need, 2 * ws.recs.cap));
+                SD_HIP(hipMemcpyAsync(grown.p, ws.recs.p, (size_t)j.appended * sizeof(sd::DevRec), hipMemcpyDeviceToDevice, st));
+                SD_HIP(hipStreamSynchronize(st));
+                ws.recs.swap(grown);
+            }
+        }
+        rows_append(ws, st, e->d_dense.p, e->d_roff.p, (int)C, ws.add.p + c0, j.appended, e->score_scale);
+        for (size_t c = 0; c < C; ++c) j.rec_at.push_back(j.appended + e->h_roff.p[c + 1]);
+        j.appended = need;
+        if (c1 == CJ) {
+            std::vector<int64_t> read_off((size_t)j.n_reads + 1, 0);
+            size_t c = 0;
+            for (int32_t r = 0; r < j.n_reads; ++r) {
+                c += (size_t)j.nch[(size_t)r];
+                read_off[(size_t)r + 1] = j.rec_at[c];
+            }
+            rows_assemble(ws, st, ws.recs.p, read_off.data(), j.n_reads, ROWS_PIECE);
+            j.assembled = true;
+        }
+    } catch (const HipFail& f) {
+        std::snprintf(eb, eblen, "%s", f.msg.c_str());
+        return SD_ERR_HIP;
+    }
+    return SD_OK;
+}
 
 // Final mode: the records of the chunks [c0, c1) are assembled into the rows of the reads they complete, which go through
 // the post-processor at once with the identity words that came with them (sd_run_files' assemble without the hand-over:
@@ -231,13 +302,17 @@ struct StreamEntries {
         }
         const int32_t dev = devs[i];
         const size_t c0 = q.c0, c1 = q.c1, b = q.b;
+        // device rows: the records stay in HBM (rows_batch, called when the batch is popped: one entry, so in batch
+        // order); the sink below then only takes its turn and counts the batch off its job
+        DevSink dsink;
+        if (jp->ws) dsink = [&pq, jp, c0, c1](sd_engine* en, int64_t total, hipStream_t st) { return rows_batch(*jp, en, total, st, c0, c1, pq.eb, sizeof pq.eb); };
         return pq.push(e.cptr, e.clen, [this, &pq, jp, dev, b, c0, c1](const sd_rec* r, const int64_t* ro, size_t first, size_t n) {
             const bool mine = turns.wait(b);   // (false: the stream failed; the batch is dropped)
             if (mine) {
                 if (fm) {
                     final_sink(*fm, pq, *jp, c0 + first, c0 + first + n, r, ro);
                     if (dev != devs[0]) (void)hipSetDevice(dev);   // (the fallback identities run on devs[0], sd_nw.hip)
-                } else {
+                } else if (!jp->ws) {
                     jp->add(c0 + first, c0 + first + n, r, ro);
                 }
             }
@@ -250,7 +325,7 @@ struct StreamEntries {
                 cv.notify_all();
                 turns.done(b);
             }
-        }, e.slice_end, jp->dev ? &ds : nullptr);
+        }, e.slice_end, jp->dev ? &ds : nullptr, std::move(dsink));
     }
 
     // One action of entry i, on the thread that drives it: push q, pop, or drain (after a failure, and at exit); then the
@@ -356,6 +431,8 @@ struct sd_stream {
     std::unique_ptr<FinalMode> fin;      // final mode only
     int sub_batches = 1;
     std::vector<std::unique_ptr<DevBuf<uint8_t>>> spare;   // device copies of reads (StreamJob::text) between jobs
+    bool dev_rows = false;               // SD_FLAG_DEVICE_ROWS: the jobs' rows are assembled and collected on the device
+    std::vector<std::unique_ptr<RowsWS>> ws_spare;         // record stores (StreamJob::ws) between jobs
     hipEvent_t ev_src = nullptr;         // sd_stream_submit_dev: the caller's stream has produced the job's reads
     int ev_src_dev = -1;
     std::vector<std::unique_ptr<StreamJob>> jobs;   // FIFO: submitted, not collected yet
@@ -385,6 +462,16 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     }
     if (n_mono <= 0 || !mono_seqs || !mono_lens) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
     if (!final && (p->reserved[1] & SD_FLAG_PROFILE)) { set_err(errbuf, errlen, "SD_FLAG_PROFILE needs a final-mode stream"); return SD_ERR_PARAM; }
+    const bool dev_rows = (p->reserved[1] & SD_FLAG_DEVICE_ROWS) != 0;
+    if (dev_rows && final) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host");
+        return SD_ERR_PARAM;
+    }
+    if (dev_rows && who && n_devices > 1) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a device list of one entry: the batches of a job would lie on several devices");
+        return SD_ERR_PARAM;
+    }
+    q.reserved[1] &= ~SD_FLAG_DEVICE_ROWS;   // (the flag shapes the stream, not its engines)
     if (final && !mono_names) { set_err(errbuf, errlen, "no monomer names"); return SD_ERR_PARAM; }
     if (final && !lr_coef) { set_err(errbuf, errlen, "no logistic-regression coefficients"); return SD_ERR_PARAM; }
     for (int32_t m = 0; m < n_mono; ++m) {
@@ -405,6 +492,7 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
         q.reserved[1] &= ~SD_FLAG_PROFILE;   // (the flag shapes the post-processing only)
     }
     s->p = q;
+    s->dev_rows = dev_rows;
     s->sub_batches = std::max(1, (int)sub_batches);
     std::vector<const char*> ms;
     for (const std::string& m : s->mono) ms.push_back(m.data());
@@ -489,6 +577,26 @@ static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const i
     return SD_OK;
 }
 
+// A record store for a new job of a device-rows stream: a spare one whose last scatter -- enqueued on that job's caller's
+// stream, which may be far behind -- has completed; else a new one, so that a slow consumer never stalls the pipeline
+// and no buffer a pending scatter reads is ever reallocated.  Beyond eight spares the oldest is waited for instead.
+static std::unique_ptr<RowsWS> stream_take_ws(sd_stream* s) {
+    std::vector<std::unique_ptr<RowsWS>>& sp = s->ws_spare;
+    for (size_t i = sp.size(); i-- > 0;)
+        if (sp[i]->idle()) {
+            std::unique_ptr<RowsWS> ws = std::move(sp[i]);
+            sp.erase(sp.begin() + (long)i);
+            return ws;
+        }
+    if (sp.size() >= 8) {
+        std::unique_ptr<RowsWS> ws = std::move(sp.front());
+        sp.erase(sp.begin());
+        ws->wait_idle();
+        return ws;
+    }
+    return std::unique_ptr<RowsWS>(new RowsWS);
+}
+
 static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads,
                          char* errbuf, size_t errlen, const DevIn* dv = nullptr) {
     std::unique_ptr<StreamJob> job(new StreamJob);
@@ -504,6 +612,10 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
     if (!job->row_off) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
     FinalMode* fm = s->fin.get();
     job->reads = read_seqs;
+    if (s->dev_rows) {
+        job->ws = stream_take_ws(s);
+        job->ws_home = &s->ws_spare;
+    }
     if (dv) {
         // the data's device is current while the job's events and copies are made (the entries all run on it)
         int cur = -1;
@@ -633,6 +745,7 @@ int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n
     *row_off = nullptr;
     if (n_rows) *n_rows = 0;
     if (s->fin) { set_err(errbuf, errlen, "a final-mode stream is collected with sd_stream_collect_final"); return SD_ERR_PARAM; }
+    if (s->dev_rows) { set_err(errbuf, errlen, "a device-rows stream (SD_FLAG_DEVICE_ROWS) is collected with sd_stream_collect_dev: its rows are not on the host"); return SD_ERR_PARAM; }
     if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect without a submitted job"); return SD_ERR_PARAM; }
     const double t0 = now_s();
     int rc = stream_wait_oldest(s, errbuf, errlen);
@@ -694,6 +807,82 @@ int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off
         std::free(off);
     }
     s->jobs.erase(s->jobs.begin());
+    s->collect_s += now_s() - t0;
+    return rc;
+}
+
+int sd_stream_peek_dev(sd_stream* s, int32_t* n_reads, int64_t* max_rows, char* errbuf, size_t errlen) {
+    if (!s) return SD_ERR_PARAM;
+    if (!s->dev_rows) { set_err(errbuf, errlen, "sd_stream_peek_dev on a stream made without SD_FLAG_DEVICE_ROWS"); return SD_ERR_PARAM; }
+    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_peek_dev without a submitted job"); return SD_ERR_PARAM; }
+    const double t0 = now_s();
+    const int rc = stream_wait_oldest(s, errbuf, errlen);
+    if (rc == SD_OK) {
+        if (n_reads) *n_reads = s->jobs.front()->n_reads;
+        if (max_rows) *max_rows = s->jobs.front()->appended;
+    }
+    s->collect_s += now_s() - t0;
+    return rc;
+}
+
+int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_t* d_row_off, void* hip_stream,
+                          int64_t* n_rows, char* errbuf, size_t errlen) {
+    if (!s || !d_row_off || cap_rows < 0 || (cap_rows > 0 && !d_rows)) return SD_ERR_PARAM;
+    if (n_rows) *n_rows = 0;
+    if (!s->dev_rows) { set_err(errbuf, errlen, "sd_stream_collect_dev on a stream made without SD_FLAG_DEVICE_ROWS: its rows are on the host (sd_stream_collect)"); return SD_ERR_PARAM; }
+    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_dev without a submitted job"); return SD_ERR_PARAM; }
+    const double t0 = now_s();
+    int rc = stream_wait_oldest(s, errbuf, errlen);
+    if (rc != SD_OK) {
+        s->collect_s += now_s() - t0;
+        return rc;
+    }
+    StreamJob& job = *s->jobs.front();
+    const int dev = s->me.devs[0];
+    if (cap_rows > 0) {
+        std::string err;
+        int at = dev;
+        rc = device_pointer(d_rows, at, err);
+        if (rc == SD_OK && at != dev) {
+            err = "the row buffer lies in the memory of device " + std::to_string(at) + ", the stream runs on device " + std::to_string(dev);
+            rc = SD_ERR_UNSUPPORTED;
+        }
+        if (rc) {
+            set_err(errbuf, errlen, rc == SD_ERR_UNSUPPORTED ? err : "sd_stream_collect_dev: the row buffer is not in device memory");
+            s->collect_s += now_s() - t0;
+            return rc;
+        }
+    }
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    bool keep_job = false;
+    try {
+        if (cur != dev) SD_HIP(hipSetDevice(dev));
+        hipStream_t user = reinterpret_cast<hipStream_t>(hip_stream);
+        RowsWS& ws = *job.ws;
+        int64_t n = 0;
+        if (job.assembled) {
+            SD_HIP(hipEventSynchronize(ws.ev_asm));   // (the row count is on the host)
+            ws.settled = true;
+            n = ws.h_total.p[0];
+        }
+        if (n_rows) *n_rows = n;
+        if (cap_rows < n) {
+            set_err(errbuf, errlen, "sd_stream_collect_dev: the job has " + std::to_string(n) + " rows, the buffer room for " + std::to_string(cap_rows));
+            rc = SD_ERR_PARAM;
+            keep_job = true;
+        } else if (job.assembled) {
+            SD_HIP(hipStreamWaitEvent(user, ws.ev_asm, 0));
+            rows_scatter(ws, user, ws.recs.p, reinterpret_cast<sd::DevRec*>(d_rows), cap_rows, d_row_off);
+        } else {   // (a job without chunks: no reads)
+            SD_HIP(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * ((size_t)job.n_reads + 1), user));
+        }
+    } catch (const HipFail& f) {
+        set_err(errbuf, errlen, f.msg);
+        rc = SD_ERR_HIP;
+    }
+    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+    if (!keep_job) s->jobs.erase(s->jobs.begin());
     s->collect_s += now_s() - t0;
     return rc;
 }

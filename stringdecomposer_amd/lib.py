@@ -47,6 +47,7 @@ EXPORTS = [
     "sd_stream_create_devices", "sd_stream_create_final_devices", "sd_stream_device_stats",
     "sd_profile_segments", "sd_profile_segments_dev", "sd_last_run_profile", "sd_stream_profile",
     "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev", "sd_engine_filter_result",
+    "sd_stream_peek_dev", "sd_stream_collect_dev", "sd_engine_rows_dev", "sd_seam_merge_dev", "sd_seam_pieces_selftest",
 ]
 
 
@@ -214,6 +215,15 @@ def load():
                                     C.c_void_p, C.c_void_p, P(C.c_int64)]
     L.sd_engine_filter_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64), P(C.c_int32),
                                           C.c_char_p, C.c_size_t]
+    L.sd_stream_peek_dev.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_stream_collect_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64),
+                                        C.c_char_p, C.c_size_t]
+    L.sd_engine_rows_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64),
+                                     C.c_char_p, C.c_size_t]
+    L.sd_seam_merge_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, P(C.c_int64)]
+    L.sd_seam_pieces_selftest.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          P(C.c_int64)]
     _lib = L
     return L
 
@@ -234,6 +244,7 @@ FLAG_TRACE_V1 = 64
 FLAG_NO_IDENT_PRUNE = 256   # --second-best: every homopolymer-compressed pair aligned in full (no distance-only pruning)
 FLAG_NO_U16 = 128     # narrow layout: fp16 / int16 cells as in rounds 1-5 instead of the biased-u16 format
 FLAG_PROFILE = 512    # per-monomer column profiles of the kept rows (run_files(profile=True), Stream(profile=True))
+FLAG_DEVICE_ROWS = 1024   # Stream(device_rows=True): the rows are assembled on the device and stay there
 
 
 def make_params(scoring=(-1, -1, -1, 1), part_size=5000, overlap=500, ed_thr=-1, threads=1,
@@ -630,6 +641,28 @@ class Engine:
             self.L.sd_free(p)
         return out
 
+    def rows_device(self, stream=None):
+        """The rows of the run assembled on the DEVICE (sd_engine_rows_dev) -> DeviceRows, what rows() returns as
+        lists; ordered on `stream` as Stream.collect_device."""
+        import torch
+        dev = torch.device("cuda", self.params.device)
+        st = _torch_stream(torch, dev, stream)
+        with torch.cuda.stream(st):
+            row_off = torch.empty(self.n_reads + 1, dtype=torch.int64, device=dev)
+        # the first call assembles and, without room, only reports the exact row count (no record crosses to the
+        # host); the second copies into a tensor of that size
+        n = C.c_int64()
+        rc = self.L.sd_engine_rows_dev(self.h, None, 0, C.c_void_p(row_off.data_ptr()), C.c_void_p(st.cuda_stream),
+                                       C.byref(n), self._err, 4096)
+        if rc != SD_ERR_PARAM or n.value <= 0:
+            self._check(rc)
+        with torch.cuda.stream(st):
+            rows = torch.empty((max(n.value, 1), 4), dtype=torch.int32, device=dev)
+        if n.value > 0:
+            self._check(self.L.sd_engine_rows_dev(self.h, C.c_void_p(rows.data_ptr()), n.value, C.c_void_p(row_off.data_ptr()),
+                                                  C.c_void_p(st.cuda_stream), C.byref(n), self._err, 4096))
+        return DeviceRows(rows[:n.value], row_off, int(n.value))
+
     def total_rows(self):
         """Number of assembled rows (cheap check used by bench.py)."""
         recs, off = self.fetch_raw()
@@ -719,6 +752,22 @@ def _device_buffer(data, stream):
         cur = getattr(getattr(mod, "cuda", None), "current_stream", None)
         stream = cur(device).cuda_stream if cur is not None else 0
     return int(data.data_ptr()), int(nbytes), int(device), int(stream or 0), shape, strides
+
+
+DeviceRows = namedtuple("DeviceRows", "rows row_off n_rows")
+"""Rows that stay in device memory (Stream.collect_device, Engine.rows_device): rows = an int32 [n_rows, 4] torch tensor
+(tmpl, start, end, score per row: the layout of sd_rec), row_off = int64 [n_reads + 1] on the same device (read r owns
+rows[row_off[r]:row_off[r+1]]), n_rows as a Python int."""
+
+
+def _torch_stream(torch, dev, stream):
+    """stream=None: the current stream of the device (DeviceReads' convention); an int: that hipStream_t; else a
+    torch stream."""
+    if stream is None:
+        return torch.cuda.current_stream(dev)
+    if isinstance(stream, int):
+        return torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+    return stream
 
 
 class DeviceReads:
@@ -823,15 +872,22 @@ class Stream:
     the command line reads it).  formats.final_rows turns a FinalRows into FinalRow / AltRow lists.  profile=True
     (final mode only, names unique) also sums the column profiles of the kept rows: profile().
 
+    device_rows=True (raw mode, one device): the rows of a job are assembled on the device and stay there --
+    collect_device() / imap(device=True) return a DeviceRows of torch tensors; with DeviceReads input no base and no row
+    passes through the host.  collect() is refused on such a stream, collect_device() on a plain one.
+
     devices (a list of ordinals, repeats allowed; `device` is then ignored): one pipeline per entry in this process
     (sd_stream_create_devices / sd_stream_create_final_devices), each driven by a thread of its own; every job is cut
     into at least two batches per entry and the rows are those of the plain stream.  [d] is the plain stream on d."""
 
     def __init__(self, mono_seqs, sub_batches=1, final=False, mono_names=None, second_best=False, min_identity=0,
-                 lr_coef=None, devices=None, profile=False, **kw):
+                 lr_coef=None, devices=None, profile=False, device_rows=False, **kw):
         self.L = load()
         if profile:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_PROFILE
+        if device_rows:
+            kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_ROWS
+        self.device_rows = bool(device_rows)
         self.params = make_params(**kw)
         self._err = C.create_string_buffer(4096)
         ms = [_b(s) for s in mono_seqs]
@@ -929,6 +985,28 @@ class Stream:
         self.L.sd_free(off)
         return out
 
+    def collect_device(self, stream=None):
+        """Rows of the oldest job of a device_rows stream -> DeviceRows, on the stream's device.  torch allocates the
+        tensors (rows from the job's record count, an upper bound, then narrowed to n_rows) and the library fills them on
+        `stream` -- a torch stream or a hipStream_t; None: the current stream of that device -- so work enqueued on it
+        afterwards sees the rows and nothing waits on the host beyond the row count.  The tensors are the caller's:
+        later jobs do not touch them.  torch is imported here only."""
+        import torch
+        devs = self.devices if self.devices is not None else [self.params.device]
+        dev = torch.device("cuda", devs[0])
+        st = _torch_stream(torch, dev, stream)
+        nr, cap = C.c_int32(), C.c_int64()
+        self._check(self.L.sd_stream_peek_dev(self.h, C.byref(nr), C.byref(cap), self._err, 4096))
+        with torch.cuda.stream(st):
+            rows = torch.empty((max(cap.value, 1), 4), dtype=torch.int32, device=dev)
+            row_off = torch.empty(nr.value + 1, dtype=torch.int64, device=dev)
+        n = C.c_int64()
+        self._check(self.L.sd_stream_collect_dev(self.h, C.c_void_p(rows.data_ptr()), cap.value,
+                                                 C.c_void_p(row_off.data_ptr()), C.c_void_p(st.cuda_stream), C.byref(n),
+                                                 self._err, 4096))
+        self._n_reads.pop(0)
+        return DeviceRows(rows[:n.value], row_off, int(n.value))
+
     def _collect_final(self):
         import numpy as np
         rows = C.POINTER(FinalRec)()
@@ -954,11 +1032,12 @@ class Stream:
 
     DEPTH = 2   # jobs outstanding before the oldest is collected: all three engines of the pipeline have a batch then
 
-    def imap(self, jobs, as_lists=False, depth=None):
+    def imap(self, jobs, as_lists=False, depth=None, device=False):
         """Rows of every job of the iterable `jobs` (read lists / ReadSets / DeviceReads), in order, with `depth` later jobs submitted
         before a job is collected -- the order of calls that keeps the device busy (sd_hip.h at sd_stream_create: the
         traceback of a batch ends with the fill of the next one, so with only ONE job outstanding the job after that is
-        enqueued late; bench.py's timed loop is this generator).
+        enqueued late; bench.py's timed loop is this generator).  device=True (a device_rows stream): every job is
+        collected with collect_device() on the current stream of the stream's device and yields a DeviceRows.
 
         The default depth is DEPTH = 2 with a device list too.  There every job is cut into at least two batches per
         entry, so two jobs outstanding give each entry at least four batches -- more than its pipeline's three slots --
@@ -966,16 +1045,17 @@ class Stream:
         one pipeline gets from two single-batch jobs.  A deeper queue would only hold more reads and rows in memory
         (a raw-mode submit already waits until its batches are packed, so it cannot run far ahead of the devices)."""
         depth = self.DEPTH if depth is None else max(0, int(depth))
+        collect = self.collect_device if device else (lambda: self.collect(as_lists=as_lists))   # device: DeviceRows
         out = 0
         for reads in jobs:
             self.submit(reads)
             out += 1
             if out > depth:
                 out -= 1
-                yield self.collect(as_lists=as_lists)
+                yield collect()
         while out > 0:
             out -= 1
-            yield self.collect(as_lists=as_lists)
+            yield collect()
 
     def stats(self):
         v = (C.c_double * 16)()
@@ -1071,6 +1151,61 @@ def seam_merge(recs):
         arr[i] = Rec(*[int(x) for x in r])
     m = L.sd_seam_merge(arr, len(recs))
     return [(arr[i].tmpl, arr[i].start, arr[i].end, arr[i].score) for i in range(m)]
+
+
+def _recs_array(recs, read_off):
+    import numpy as np
+    r = np.ascontiguousarray(recs, dtype=np.int32).reshape(-1, 4)
+    o = np.ascontiguousarray(read_off, dtype=np.int64)
+    if o.ndim != 1 or len(o) < 1 or int(o[-1]) != len(r):
+        raise SdError(SD_ERR_PARAM, "read_off: n_reads + 1 offsets, the last = the number of records")
+    return r, o
+
+
+def seam_pieces_host(recs, read_off, piece=0):
+    """The piecewise seam merge run by the host (sd_seam_pieces_selftest: the functions the device kernels run).
+    recs: [n, 4] int32 (tmpl, start, end, score), read-global; read_off: n_reads + 1 offsets from 0; piece: records
+    per piece, 0 = the production value.  -> (rows [m, 4], row_off)."""
+    import numpy as np
+    r, o = _recs_array(recs, read_off)
+    rows = np.empty((max(len(r), 1), 4), dtype=np.int32)
+    row_off = np.empty(len(o), dtype=np.int64)
+    n = C.c_int64()
+    rc = load().sd_seam_pieces_selftest(r.ctypes.data, o.ctypes.data, len(o) - 1, int(piece), rows.ctypes.data,
+                                        row_off.ctypes.data, C.byref(n))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_seam_pieces_selftest")
+    return rows[:n.value], row_off
+
+
+def seam_merge_device(recs, read_off, piece=0, device=0, stream=None, pad=0):
+    """The assembly kernels alone (sd_seam_merge_dev), arguments as seam_pieces_host; the arrays go to `device` through
+    torch and the results come back as numpy.  pad: sentinel words put before and after both outputs on the device;
+    with pad > 0 the result is (rows, row_off, intact) where intact tells whether every sentinel survived."""
+    import numpy as np
+    import torch
+    r, o = _recs_array(recs, read_off)
+    dev = torch.device("cuda", int(device))
+    st = _torch_stream(torch, dev, stream)
+    pad = int(pad)
+    with torch.cuda.stream(st):
+        d_r = torch.from_numpy(r).to(dev)
+        d_o = torch.from_numpy(o).to(dev)
+        d_rows = torch.full((len(r) + 2 * pad, 4), -559038737, dtype=torch.int32, device=dev)
+        d_off = torch.full((len(o) + 2 * pad,), -559038737, dtype=torch.int64, device=dev)
+        n = C.c_int64()
+        rc = load().sd_seam_merge_dev(C.c_void_p(d_r.data_ptr()), C.c_void_p(d_o.data_ptr()), len(o) - 1, int(piece),
+                                      int(device), C.c_void_p(st.cuda_stream), C.c_void_p(d_rows.data_ptr() + 16 * pad),
+                                      C.c_void_p(d_off.data_ptr() + 8 * pad), C.byref(n))
+        if rc != SD_OK:
+            raise SdError(rc, "sd_seam_merge_dev")
+        h_rows, h_off = d_rows.cpu().numpy(), d_off.cpu().numpy()
+    rows, row_off = h_rows[pad:pad + n.value], h_off[pad:pad + len(o)]
+    if not pad:
+        return rows, row_off
+    intact = bool((h_rows[:pad] == -559038737).all() and (h_rows[pad + n.value:] == -559038737).all()
+                  and (h_off[:pad] == -559038737).all() and (h_off[pad + len(o):] == -559038737).all())
+    return rows, row_off, intact
 
 
 def fasta_load(path):
