@@ -69,6 +69,8 @@ typedef struct sd_params {
 
 #define SD_FLAG_DEVICE_ROWS 1024   /* raw-mode streams with one device entry: the rows of a job are assembled on the device and
                                       stay there (sd_stream_peek_dev / sd_stream_collect_dev); no record crosses to the host */
+#define SD_FLAG_DEVICE_FINAL 2048  /* final-mode streams with one device entry: the rows of final_decomposition.tsv / _alt.tsv are
+                                      selected on the device and stay there (sd_stream_peek_final_dev / sd_stream_collect_final_dev) */
 
 void sd_params_default(sd_params* p); /* -1,-1,-1,1 / 5000 / 500 / -1 / 1 / 0 / auto */
 
@@ -437,7 +439,7 @@ int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n
  * to the host and no host thread assembles anything (sd_stream_stats [9] stays 0); the per-chunk record counts still
  * come back, as they always did.  A read that spans several batches is just a longer record list.
  * Raw mode with ONE device entry only: the flag is SD_ERR_PARAM at sd_stream_create_final* (final rows are selected on
- * the host) and with a device list of more than one entry (a job's batches would lie on several devices).
+ * the host; SD_FLAG_DEVICE_FINAL, below, selects them on the device) and with a device list of more than one entry (a job's batches would lie on several devices).
  * sd_stream_collect on such a stream and sd_stream_collect_dev on a plain one are SD_ERR_PARAM.
  *
  * sd_stream_peek_dev waits for the oldest job (FIFO) and gives what its buffers need: *n_reads, and *max_rows = its
@@ -494,6 +496,46 @@ int sd_stream_create_final(sd_stream** out, const sd_params* p, const char* cons
  * SD_ERR_PARAM on a stream made by sd_stream_create (and sd_stream_collect on a final-mode stream). */
 int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off, int64_t* n_rows, double** alt,
                             char* errbuf, size_t errlen);
+/* ---- final rows that stay on the device (SD_FLAG_DEVICE_FINAL in sd_params.reserved[1] at sd_stream_create_final) ------
+ * The chain sd_stream_submit_dev -> final rows with nothing crossing to the host: every batch's compact records are
+ * appended to the job's record store in HBM as with SD_FLAG_DEVICE_ROWS, and the batch's identity words (csrc/sd_ident.hip)
+ * are kept beside them at the same index, device to device.  Behind the job's last batch the seam merge runs, one kernel
+ * writes which record each merged row is, and the selection kernels (csrc/sd_final_dev.hip) apply the rule of
+ * main.py:107-165 -- its arithmetic and the end of the rule are csrc/sd_final_dev.hpp, one text for the host's
+ * PostProcessor::select and the kernels; the maximum searches are lane reductions there -- to every merged row: best
+ * monomer, identity, second best, homopolymer ranks, '+' / '?', the min_identity filter; the kept rows are counted and
+ * scanned.  The rows have the bytes sd_stream_collect_final returns, padding included.  No record, no identity word and
+ * no host thread's assembly is involved (sd_stream_stats [9] stays 0).
+ * Accepted by sd_stream_create_final and by sd_stream_create_final_devices with exactly one entry.  SD_ERR_PARAM, before
+ * any device is touched: at sd_stream_create / sd_stream_create_devices (a raw-mode stream), with a device list of more
+ * than one entry, together with SD_FLAG_PROFILE (the profile pass reads the kept rows and the text on the host), and
+ * together with SD_FLAG_DEVICE_ROWS.  sd_stream_submit, sd_stream_submit_dev, sd_stream_keys, sd_stream_stats and
+ * sd_stream_final_stats work unchanged.
+ *
+ * The text-based path.  Rows the words cannot decide are counted by the kernels, not guessed: a missing word (a pair the
+ * identity kernels left out), a segment long enough for edlib's Hirschberg split against the longest monomer (about 19.6 kb
+ * against 171 bp: -b >= 19000), a batch whose identity outputs had no room (its words are stored as zeroes).  A job with
+ * such a row, and every job of a stream whose engines compute no identities (SD_FLAG_NO_STREAM_IDENT, a monomer set
+ * the in-stream kernels do not take), is finished by the host instead: its merged raw rows and row offsets come to the
+ * host, its reads too (the job keeps its copy, as every final-mode job does), the post-processor of the file path
+ * computes every identity from the text, and the rows are copied into the caller's buffers on the caller's stream, which
+ * the host waits for.  Correct and slow; sd_stream_final_stats [2] counts the blocks of such jobs.
+ *
+ * sd_stream_peek_final_dev waits for the oldest job (FIFO) and gives what its buffers need: *n_reads, *n_rows = the EXACT
+ * number of kept rows (16 bytes from the device once the selection has run; min_identity can drop most rows and alt is
+ * n_rows x n_keys doubles, so an upper bound would not do) and *n_keys.  The job stays.
+ * sd_stream_collect_final_dev hands the oldest job over: d_rows[0 .. *n_rows), d_row_off (n_reads + 1) and, with
+ * second_best, d_alt (n_rows x n_keys, key order; may be NULL and is ignored without second_best) -- DEVICE buffers of the
+ * caller's on the stream's device (SD_ERR_PARAM / SD_ERR_UNSUPPORTED as in sd_stream_collect_dev).  Ordering on
+ * hip_stream and ownership are those of sd_stream_collect_dev: the copy is enqueued on hip_stream behind an event of
+ * the library's selection, nothing waits on the host beyond the count, and the buffers are the caller's alone afterwards.
+ * cap_rows < *n_rows: SD_ERR_PARAM with *n_rows set, nothing is written and the job stays collectable.
+ * The wrong collect for a stream's mode is SD_ERR_PARAM and leaves the job in place: sd_stream_collect,
+ * sd_stream_collect_final and sd_stream_collect_dev on such a stream, these two calls on any other.
+ * Out of scope: several device entries, SD_FLAG_PROFILE, and sd_engine (which has no final mode). */
+int sd_stream_peek_final_dev(sd_stream* s, int32_t* n_reads, int64_t* n_rows, int32_t* n_keys, char* errbuf, size_t errlen);
+int sd_stream_collect_final_dev(sd_stream* s, sd_final_row* d_rows, int64_t cap_rows, int64_t* d_row_off, double* d_alt,
+                                void* hip_stream, int64_t* n_rows, char* errbuf, size_t errlen);
 /* The distinct monomer names in key order (m0, m0', m1, m1', ... first occurrences): up to cap pointers, valid
  * until sd_stream_destroy; *n_keys = the number of keys.  SD_ERR_PARAM on a stream not in final mode. */
 int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys);
@@ -569,6 +611,28 @@ int sd_seam_merge_dev(const sd_rec* d_recs, const int64_t* d_read_off, int32_t n
  * rows must equal sd_seam_merge's.  Arguments as above, in host memory. */
 int sd_seam_pieces_selftest(const sd_rec* recs, const int64_t* read_off, int32_t n_reads, int32_t piece, sd_rec* rows,
                             int64_t* row_off, int64_t* n_rows);
+/* The selection kernels alone (for tests): the rows of n_reads reads (read r = d_rows[d_row_off[r] .. d_row_off[r + 1]),
+ * read-global, already merged), row b's identity words at d_words / d_hwords + d_widx[b] * per (plain / homopolymer-
+ * compressed; per = 1, the word of the row's own monomer, or with second_best 2 * n_mono, one per interleaved template
+ * m0, m0', m1, ...; 0 <= d_widx[b] < n_word_rows) and d_read_len (may be NULL: segments are not clamped to their read),
+ * all in the memory of `device`.  The tables are built from the monomers, min_identity, second_best and lr_coef the way
+ * a final-mode stream builds them.  d_out (room for every row), d_out_off (n_reads + 1) and d_alt (every row x n_keys,
+ * second_best only) receive the kept rows; *n_rows = how many, *n_undecided = the rows the words do not decide (a word
+ * 0 or 0xffffffff, a segment edlib aligns by Hirschberg's split), which are counted and not kept.  Runs on hip_stream and
+ * returns when it is done.  SD_ERR_PARAM for bad arguments (offsets, word indices and templates are checked on the
+ * host before any kernel runs), SD_ERR_NO_DEVICE without a device. */
+int sd_final_select_dev(const char* const* mono_names, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
+                        int32_t min_identity, int32_t second_best, const double* lr_coef, const sd_rec* d_rows,
+                        const int64_t* d_row_off, int32_t n_reads, const int64_t* d_widx, const uint32_t* d_words,
+                        const uint32_t* d_hwords, int64_t n_word_rows, int32_t per, const int64_t* d_read_len, int32_t device,
+                        void* hip_stream, sd_final_row* d_out, int64_t* d_out_off, double* d_alt, int64_t* n_rows,
+                        int64_t* n_undecided);
+/* Host only: the same arguments in host memory, answered by the host's selection (PostProcessor::select) itself. */
+int sd_final_select_host(const char* const* mono_names, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
+                         int32_t min_identity, int32_t second_best, const double* lr_coef, const sd_rec* rows,
+                         const int64_t* row_off, int32_t n_reads, const int64_t* widx, const uint32_t* words,
+                         const uint32_t* hwords, int64_t n_word_rows, int32_t per, const int64_t* read_len,
+                         sd_final_row* out, int64_t* out_off, double* alt, int64_t* n_rows, int64_t* n_undecided);
 /* The --ed_thr prefilter's result alone, on the host (for tests): valid after sd_engine_fetch of a batch run with
  * ed_thr > -1, else SD_ERR_PARAM.  dist[chunk][T]: the infix edit distance of every template against every chunk, chunks
  * in the order of sd_engine_fetch; rank[chunk][T]: the template's position in the chunk's filtered order (by distance,

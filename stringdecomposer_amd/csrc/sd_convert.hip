@@ -65,6 +65,8 @@ int PostProcessor::init(const std::vector<Seq>& monos, int min_identity_, bool s
     own_il32.assign(own_il_of_t.begin(), own_il_of_t.end());
     key_of_il.assign(il_name.size(), -1);
     for (size_t x = 0; x < il_name.size(); ++x) key_of_il[x] = kidx[il_name[x]];
+    tmax = 1;
+    for (const std::string& t : il_seq) tmax = std::max(tmax, (int)t.size());
     return SD_OK;
 }
 
@@ -178,14 +180,8 @@ inline void put_f2(std::string& o, double v) { put_fixed2(o, v); }   // == Pytho
 }  // namespace
 
 namespace {
-// identity in percent of a device word (dist << 16) | matches: the arithmetic of main.py:47-60 on the same integers
-inline double ident_percent(uint32_t w) {
-    const uint32_t d = w >> 16, m = w & 0xffffu;
-    double a = 0.0;
-    a += (double)m;
-    a /= (double)(d + m);
-    return a * 100;
-}
+// identity in percent of a device word (dist << 16) | matches: sd_final_dev.hpp, the text the device kernels run
+inline double ident_percent(uint32_t w) { return final_ident_percent(w); }
 }  // namespace
 
 int PostProcessor::process(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off, TextBuf& fin,
@@ -339,17 +335,63 @@ bool PostProcessor::select(const Batch& bt, const sd_rec* rows, int64_t b, doubl
         h0 = key_of_il[(size_t)i0]; h0s = h[i0];
         if (i1 >= 0) { h1 = key_of_il[(size_t)i1]; h1s = h[i1]; }
     }
-    if (!(score >= (double)min_identity)) return false;     // main.py:156
-    // classify (main.py:95-104): intercept + c1 * identity + c2 * (identity - second best) > 0
-    const double logit = (1.0 * coef[0] + score * coef[1]) + (score - sbs) * coef[2];
-    std::memset(&f, 0, sizeof f);   // (padding too: callers of the C-ABI get the same bytes for the same rows)
-    f.read = bt.read_of[(size_t)b];
-    f.start = x.start;
-    f.end = x.end;
-    f.best = ko; f.second = sb; f.homo_best = h0; f.homo_second = h1;
-    f.ident = score; f.second_ident = sbs; f.homo_ident = h0s; f.homo_second_ident = h1s;
-    f.reliable = logit > 0 ? 1 : 0;
-    return true;
+    // main.py:156 and classify (:95-104), in the text the device kernels run too (sd_final_dev.hpp)
+    return final_fill_row(final_tables(), bt.read_of[(size_t)b], x, ko, score, sb, sbs, h0, h0s, h1, h1s, &f);
+}
+
+FinalTables PostProcessor::final_tables() const {
+    FinalTables tb;
+    tb.key_of_t = key_of_t.data();
+    tb.kcol = kcol.data();
+    tb.key_of_il = key_of_il.data();
+    tb.n_tmpl = (int32_t)il_seq.size();
+    tb.n_keys = (int32_t)keys.size();
+    tb.min_identity = min_identity;
+    tb.second_best = second_best ? 1 : 0;
+    tb.tmax = tmax;
+    tb.coef[0] = coef[0]; tb.coef[1] = coef[1]; tb.coef[2] = coef[2];
+    return tb;
+}
+
+int PostProcessor::select_words(const sd_rec* rows, const int64_t* row_off, int32_t n_reads, const int64_t* widx,
+                                const uint32_t* id, const uint32_t* idh, const int64_t* read_len, sd_final_row* out,
+                                int64_t* out_off, double* alt, int64_t* n_kept, int64_t* n_undecided) const {
+    const int T = (int)il_seq.size();
+    const size_t nK = keys.size();
+    const int64_t nB = row_off[n_reads];
+    const IdentRef ir{id, second_best ? idh : nullptr, widx, nullptr, nullptr};
+    Batch bt;
+    bt.ident = &ir;
+    bt.id = true;
+    bt.per = second_best ? T : 1;
+    bt.read_of.resize((size_t)nB);
+    std::vector<double> kscratch(nK), hbuf((size_t)T);
+    int64_t k = 0, und = 0;
+    out_off[0] = 0;
+    for (int32_t r = 0; r < n_reads; ++r) {
+        for (int64_t b = row_off[r]; b < row_off[r + 1]; ++b) {
+            const sd_rec& x = rows[b];
+            if (x.tmpl < 0 || x.tmpl >= T || widx[b] < 0) return SD_ERR_PARAM;
+            bt.read_of[(size_t)b] = r;
+            // a row the words do not decide is counted and not kept (the stream then takes the text-based path)
+            bool missing = false;
+            const uint32_t* v = bt.words(b, false);
+            for (int j = 0; j < bt.per; ++j) missing |= final_word_missing(v[j]);
+            if (second_best) {
+                const uint32_t* h = bt.words(b, true);
+                for (int j = 0; j < bt.per; ++j) missing |= final_word_missing(h[j]);
+            }
+            if (missing || final_seg_splits(final_seg_len(x.start, x.end, read_len ? read_len[r] : -1), tmax)) { ++und; continue; }
+            sd_final_row f;
+            if (!select(bt, rows, b, second_best && alt ? alt + (size_t)k * nK : kscratch.data(), hbuf.data(), f)) continue;
+            std::memcpy(out + k, &f, sizeof f);
+            ++k;
+        }
+        out_off[r + 1] = k;
+    }
+    if (n_kept) *n_kept = k;
+    if (n_undecided) *n_undecided = und;
+    return SD_OK;
 }
 
 int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd_rec* rows, const int64_t* row_off,

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/sd_hip.h"
+#include "sd_final_dev.hpp"
 #include "sd_host.hpp"
 
 namespace sd {
@@ -86,6 +87,17 @@ class PostProcessor {
     const std::vector<int32_t>& own_interleaved() const { return own_il32; }      // DP template -> interleaved index
     int tmpl_of_name(const std::string& nm) const;   // first template of that name in the DP's order, -1 if none
     std::vector<std::string> tname;                  // the DP's template names: m, ..., m', ...
+    // The tables the selection reads, as pointers into this object (the device selection uploads them: sd_final_dev.hip).
+    FinalTables final_tables() const;
+    // The selection alone, on identity words (sd_final_select_host; what the kernels of sd_final_dev.hip must equal): read
+    // r = rows[row_off[r] .. row_off[r + 1]); row b's words = id / idh + widx[b] * per (per = 1, the row's own monomer,
+    // or with second_best every interleaved template, plain / homopolymer-compressed); read_len may be nullptr.  The
+    // kept rows go to out in order, their offsets per read to out_off (n_reads + 1) and, with second_best, their key
+    // identities to alt (room for every row).  A row the words do not decide -- a missing word, a segment edlib aligns by
+    // Hirschberg's split -- is counted in *n_undecided and not kept.
+    int select_words(const sd_rec* rows, const int64_t* row_off, int32_t n_reads, const int64_t* widx, const uint32_t* id,
+                     const uint32_t* idh, const int64_t* read_len, sd_final_row* out, int64_t* out_off, double* alt,
+                     int64_t* n_kept, int64_t* n_undecided) const;
     // Column profiles of the kept rows (SD_FLAG_PROFILE): SD_ERR_PARAM when a name repeats (a key must name one template).
     // prof: the forward monomers' counters (include/sd_hip.h), summed over every process* call since enable_profile.
     int enable_profile(std::string& err);
@@ -139,6 +151,7 @@ class PostProcessor {
     std::vector<int> key_of_t, own_il_of_t, key_of_il;
     std::vector<int32_t> own_il32;
     int min_identity = 0;
+    int tmax = 1;                                    // the longest template
     bool second_best = false;
     double coef[3] = {0, 0, 0};
     int device = -1;

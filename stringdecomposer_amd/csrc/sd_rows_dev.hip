@@ -10,12 +10,11 @@
 //   sd_rows_scatter                                 kept records -> rows, row offsets per read
 // No look-back and no spinning: a launch per stage, seven for a job (~5 MB of records in the benchmark's step).
 #include "sd_pipeline.hpp"
+#include "sd_rows_scan_dev.hpp"
 #include "sd_seam_dev.hpp"
 
 namespace sd {
 
-constexpr int ROWS_T = 256;                   // threads per workgroup of every kernel here
-constexpr int ROWS_TILE = ROWS_T * 4;         // records per tile of the count / scatter (4 flags = one word per lane)
 
 __global__ __launch_bounds__(ROWS_T) void sd_rows_append(const DevRec* __restrict__ dense, const int64_t* __restrict__ roff,
                                                          int n_chunks, const int32_t* __restrict__ add, DevRec* __restrict__ out,
@@ -89,52 +88,6 @@ __global__ __launch_bounds__(ROWS_T) void sd_seam_keep(const DevRec* __restrict_
     seam_piece_keep(recs + lo, read_off[r + 1] - lo, S, p - piece_start[r], (int)entry[p], keep + lo);
 }
 
-// exclusive scan of v over the workgroup; *total = the sum (valid in every thread)
-__device__ inline int rows_block_scan(int v, int* total) {
-    __shared__ int wsum[ROWS_T / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int sc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int s2 = __shfl_up(sc, off);
-        if (lane >= off) sc += s2;
-    }
-    __syncthreads();   // (the last call's readers are through)
-    if (lane == 63) wsum[w] = sc;
-    __syncthreads();
-    int pre = 0, all = 0;
-    for (int x = 0; x < ROWS_T / 64; ++x) {
-        if (x < w) pre += wsum[x];
-        all += wsum[x];
-    }
-    *total = all;
-    return pre + sc - v;
-}
-
-// the four flags of a lane as one word (keep is allocated and zeroed in whole words), and how many are set
-__device__ inline uint32_t rows_flags(const uint8_t* __restrict__ keep, int64_t n, int64_t i0) {
-    return i0 < n ? *reinterpret_cast<const uint32_t*>(keep + i0) : 0u;
-}
-__device__ inline int rows_flag_count(uint32_t f) { return (int)((f * 0x01010101u) >> 24); }
-
-__global__ __launch_bounds__(ROWS_T) void sd_rows_count(const uint8_t* __restrict__ keep, int64_t n, int32_t* __restrict__ bsum) {
-    int total;
-    (void)rows_block_scan(rows_flag_count(rows_flags(keep, n, (int64_t)blockIdx.x * ROWS_TILE + threadIdx.x * 4)), &total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup: bbase[b] = rows before tile b, bbase[n_tiles] = the row count
-__global__ __launch_bounds__(ROWS_T) void sd_rows_scan(const int32_t* __restrict__ bsum, int64_t n_tiles, int64_t* __restrict__ bbase) {
-    int64_t run = 0;
-    for (int64_t b0 = 0; b0 < n_tiles; b0 += ROWS_T) {
-        const int64_t b = b0 + threadIdx.x;
-        int total;
-        const int ex = rows_block_scan(b < n_tiles ? bsum[b] : 0, &total);   // (a round holds at most 256 * 1024 rows)
-        if (b < n_tiles) bbase[b] = run + ex;
-        run += total;
-    }
-    if (threadIdx.x == 0) bbase[n_tiles] = run;
-}
-
 // workgroups [0, n_tiles): the kept records of a tile to their rows; the workgroups behind them: row_off of the reads
 __global__ __launch_bounds__(ROWS_T) void sd_rows_scatter(const DevRec* __restrict__ recs, const uint8_t* __restrict__ keep,
                                                           int64_t n, int64_t n_tiles, const int64_t* __restrict__ bbase,
@@ -154,12 +107,7 @@ __global__ __launch_bounds__(ROWS_T) void sd_rows_scatter(const DevRec* __restri
     }
     const int64_t r = ((int64_t)blockIdx.x - n_tiles) * ROWS_T + threadIdx.x;
     if (r > n_reads) return;
-    const int64_t idx = read_off[r], t0 = idx / ROWS_TILE;
-    int64_t s = bbase[t0];
-    int64_t x = t0 * ROWS_TILE;
-    for (; x + 4 <= idx; x += 4) s += rows_flag_count(*reinterpret_cast<const uint32_t*>(keep + x));
-    for (; x < idx; ++x) s += keep[x];
-    row_off[r] = s;
+    row_off[r] = rows_flags_before(keep, bbase, read_off[r]);
 }
 
 }  // namespace sd

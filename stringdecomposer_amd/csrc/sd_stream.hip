@@ -4,6 +4,7 @@
 // device list (sd_stream_create_devices, sd_stream_create_final_devices) one pipeline per entry, several of them each
 // driven by a thread of its own.
 #include "sd_devices.hpp"
+#include "sd_final_ws.hpp"
 
 // (lib.py's numpy dtype of the rows mirrors this layout)
 static_assert(sizeof(sd_final_row) == 80 && offsetof(sd_final_row, start) == 8 && offsetof(sd_final_row, ident) == 40 &&
@@ -17,6 +18,10 @@ struct FinalMode {
     bool second_best = false;
     std::atomic<bool> ident{true};   // every engine so far took the identity tables (engine_set_identity)
     int64_t kept = 0;        // rows handed to callers
+    // SD_FLAG_DEVICE_FINAL: the selection runs on the device (sd_final_dev.hip) from these copies of the tables, uploaded
+    // when the first job's rows are assembled
+    bool dtab_up = false;
+    FinalDevTables dtab;
 };
 
 // A submitted job: its rows as they are assembled and, in final mode, its own copy of the reads and its kept rows.
@@ -51,16 +56,30 @@ struct StreamJob : RowJob {
     std::vector<int64_t> rec_at;
     int64_t appended = 0;
     bool ws_begun = false, assembled = false;
+    // A job of a device-final stream (SD_FLAG_DEVICE_FINAL) has a record store too, and fws: the identity words of the
+    // store's records and the selection's workspace.  selected: the selection kernels were enqueued behind the merge.
+    // A job that takes the text-based path (final_dev_slow) leaves its rows in fin / alt / fin_off on the host.
+    std::unique_ptr<FinalWS> fws;
+    std::vector<std::unique_ptr<FinalWS>>* fws_home = nullptr;
+    bool selected = false, slow_done = false;
+    std::vector<int64_t> fin_off;
     ~StreamJob() {
         if (text && spare) spare->push_back(std::move(text));
+        if (fws && fws_home) fws_home->push_back(std::move(fws));
         if (ws && ws_home) ws_home->push_back(std::move(ws));
     }
 };
 
 // Device rows: the records of the batch [c0, c1) of job j, still in engine e's buffers after fetch_begin (total of them,
 // offsets in e->h_roff), are appended to the job's store on `st`; behind the job's last batch the merge is enqueued.
-static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st, size_t c0, size_t c1, char* eb, size_t eblen) {
+// A device-final job (fm given) also keeps the batch's identity words at the records' indices -- zeroes, which decide
+// nothing, for a batch whose identity outputs are not valid -- and behind the merge enqueues the selection.
+static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st, size_t c0, size_t c1, char* eb, size_t eblen,
+                      FinalMode* fm = nullptr) {
     RowsWS& ws = *j.ws;
+    FinalWS* fw = j.fws.get();
+    const size_t per = fw ? (size_t)j.per : 0;   // identity words kept per record (0: a job without in-stream identities)
+    const bool homo = fm && fm->second_best;
     const size_t C = c1 - c0, CJ = j.table.size();
     try {
         if (!j.ws_begun) {
@@ -69,7 +88,8 @@ static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st,
             // below may give a block up to the pool, so the HOST has to have seen that scatter end (stream_take_ws
             // hands out idle workspaces: this returns at once).  A job that was dropped never settled.
             ws.wait_idle();
-            if (!ws.settled) { SD_HIP(hipStreamSynchronize(st)); ws.settled = true; }
+            if (fw) fw->wait_idle();
+            if (!ws.settled || (fw && !fw->settled)) { SD_HIP(hipStreamSynchronize(st)); ws.settled = true; if (fw) fw->settled = true; }
             ws.h_add.alloc(CJ);
             for (size_t c = 0; c < CJ; ++c) ws.h_add.p[c] = (int32_t)j.table[c].off;   // (main.cpp:109-111)
             ws.add.alloc(CJ);
@@ -91,8 +111,39 @@ static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st,
                 DevBuf<sd::DevRec> grown;
                 grown.alloc(std::max<size_t>((size_t)need, 2 * ws.recs.cap));
                 SD_HIP(hipMemcpyAsync(grown.p, ws.recs.p, (size_t)j.appended * sizeof(sd::DevRec), hipMemcpyDeviceToDevice, st));
+                DevBuf<uint32_t> gw, gh;
+                if (per) {
+                    gw.alloc(grown.cap * per);
+                    SD_HIP(hipMemcpyAsync(gw.p, fw->words.p, (size_t)j.appended * per * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+                    if (homo) {
+                        gh.alloc(grown.cap * per);
+                        SD_HIP(hipMemcpyAsync(gh.p, fw->hwords.p, (size_t)j.appended * per * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+                    }
+                }
                 SD_HIP(hipStreamSynchronize(st));
                 ws.recs.swap(grown);
+                if (per) {
+                    fw->words.swap(gw);
+                    if (homo) fw->hwords.swap(gh);
+                }
+            }
+        }
+        if (per && j.appended == 0) {   // the words' room follows the store's (a store kept from an earlier job may be larger)
+            fw->words.alloc(ws.recs.cap * per);
+            if (homo) fw->hwords.alloc(ws.recs.cap * per);
+        }
+        if (per && total > 0) {
+            // (the run is through -- fetch_begin waited for it -- so the batch's words are complete in the engine's outputs)
+            fw->settled = false;
+            const size_t nb = (size_t)total * per * sizeof(uint32_t);
+            const bool valid = e->ident_valid && (size_t)e->ident_words() == per && (!homo || e->ident_mode == 2);
+            uint32_t* w = fw->words.p + (size_t)j.appended * per;
+            if (valid) SD_HIP(hipMemcpyAsync(w, e->d_ident.p, nb, hipMemcpyDeviceToDevice, st));
+            else SD_HIP(hipMemsetAsync(w, 0, nb, st));
+            if (homo) {
+                uint32_t* h = fw->hwords.p + (size_t)j.appended * per;
+                if (valid) SD_HIP(hipMemcpyAsync(h, e->d_identh.p, nb, hipMemcpyDeviceToDevice, st));
+                else SD_HIP(hipMemsetAsync(h, 0, nb, st));
             }
         }
         rows_append(ws, st, e->d_dense.p, e->d_roff.p, (int)C, ws.add.p + c0, j.appended, e->score_scale);
@@ -107,6 +158,19 @@ static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st,
             }
             rows_assemble(ws, st, ws.recs.p, read_off.data(), j.n_reads, ROWS_PIECE);
             j.assembled = true;
+            if (per) {
+                if (!fm->dtab_up) { fm->dtab.upload(fm->pp.final_tables()); fm->dtab_up = true; }
+                const size_t nr = (size_t)j.n_reads;
+                fw->h_rlen.alloc(nr);
+                for (size_t r = 0; r < nr; ++r) fw->h_rlen.p[r] = j.dev ? j.rlen[r] : (int64_t)j.seq[r].size();
+                fw->rlen.alloc(nr);
+                fw->settled = false;
+                SD_HIP(hipMemcpyAsync(fw->rlen.p, fw->h_rlen.p, nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                final_sources(*fw, ws, st);
+                final_select(*fw, st, fm->dtab.tb, ws.recs.p, fw->src.p, fw->src.p, fw->words.p, fw->hwords.p, fw->moff.p,
+                             fw->rlen.p, j.n_reads, ws.n_recs, ws.bbase.p + ws.n_tiles);
+                j.selected = true;
+            }
         }
     } catch (const HipFail& f) {
         std::snprintf(eb, eblen, "%s", f.msg.c_str());
@@ -294,7 +358,8 @@ struct StreamEntries {
         e.slice_end.clear();
         // --second-best: the identities of a batch in slices of whole reads, each handed over as the device finishes it
         // (sd_engine::slice_end), so that the host selects slice s while the device computes slice s + 1
-        if (fm && fm->second_best && jp->per) ident_slices(jp->table, q.c0, q.c1, e.slice_end);
+        // (a device-final job's words stay on the device: nothing to hand over in slices)
+        if (fm && fm->second_best && jp->per && !jp->ws) ident_slices(jp->table, q.c0, q.c1, e.slice_end);
         DevSrc ds;
         if (jp->dev) {
             ds = jp->ds;
@@ -305,14 +370,17 @@ struct StreamEntries {
         // device rows: the records stay in HBM (rows_batch, called when the batch is popped: one entry, so in batch
         // order); the sink below then only takes its turn and counts the batch off its job
         DevSink dsink;
-        if (jp->ws) dsink = [&pq, jp, c0, c1](sd_engine* en, int64_t total, hipStream_t st) { return rows_batch(*jp, en, total, st, c0, c1, pq.eb, sizeof pq.eb); };
+        FinalMode* const fmq = fm;
+        if (jp->ws) dsink = [&pq, jp, c0, c1, fmq](sd_engine* en, int64_t total, hipStream_t st) { return rows_batch(*jp, en, total, st, c0, c1, pq.eb, sizeof pq.eb, fmq); };
         return pq.push(e.cptr, e.clen, [this, &pq, jp, dev, b, c0, c1](const sd_rec* r, const int64_t* ro, size_t first, size_t n) {
             const bool mine = turns.wait(b);   // (false: the stream failed; the batch is dropped)
             if (mine) {
-                if (fm) {
+                if (jp->ws) {
+                    // (the records stayed on the device: rows_batch has them)
+                } else if (fm) {
                     final_sink(*fm, pq, *jp, c0 + first, c0 + first + n, r, ro);
                     if (dev != devs[0]) (void)hipSetDevice(dev);   // (the fallback identities run on devs[0], sd_nw.hip)
-                } else if (!jp->ws) {
+                } else {
                     jp->add(c0 + first, c0 + first + n, r, ro);
                 }
             }
@@ -433,14 +501,20 @@ struct sd_stream {
     std::vector<std::unique_ptr<DevBuf<uint8_t>>> spare;   // device copies of reads (StreamJob::text) between jobs
     bool dev_rows = false;               // SD_FLAG_DEVICE_ROWS: the jobs' rows are assembled and collected on the device
     std::vector<std::unique_ptr<RowsWS>> ws_spare;         // record stores (StreamJob::ws) between jobs
+    bool dev_final = false;              // SD_FLAG_DEVICE_FINAL: the final rows are selected and collected on the device
+    std::vector<std::unique_ptr<FinalWS>> fws_spare;       // selection workspaces (StreamJob::fws) between jobs
     hipEvent_t ev_src = nullptr;         // sd_stream_submit_dev: the caller's stream has produced the job's reads
     int ev_src_dev = -1;
     std::vector<std::unique_ptr<StreamJob>> jobs;   // FIFO: submitted, not collected yet
+    hipStream_t slow_st = nullptr;       // device-final streams: the text-based path's copies to the host (final_dev_slow)
     int64_t budget = 0;
     double submit_s = 0, collect_s = 0;
     int64_t n_jobs = 0;
     StreamEntries me;                    // destroyed first: its sinks hold pointers to the jobs
-    ~sd_stream() { if (ev_src) (void)hipEventDestroy(ev_src); }
+    ~sd_stream() {
+        if (ev_src) (void)hipEventDestroy(ev_src);
+        if (slow_st) (void)hipStreamDestroy(slow_st);
+    }
 };
 
 // The four creates.  who: the name of a call with a device list, which is checked as by sd_run_files_devices; without
@@ -455,6 +529,23 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     sd_params q = *p;
+    const bool dev_final = (p->reserved[1] & SD_FLAG_DEVICE_FINAL) != 0;
+    if (dev_final && (p->reserved[1] & SD_FLAG_DEVICE_ROWS) && final) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host (or, with SD_FLAG_DEVICE_FINAL alone, on the device)");
+        return SD_ERR_PARAM;
+    }
+    if (dev_final && !final) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_FINAL needs a final-mode stream (sd_stream_create_final): a raw-mode stream keeps its rows on the device with SD_FLAG_DEVICE_ROWS");
+        return SD_ERR_PARAM;
+    }
+    if (dev_final && who && n_devices > 1) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_FINAL needs a device list of one entry: the batches of a job would lie on several devices");
+        return SD_ERR_PARAM;
+    }
+    if (dev_final && (p->reserved[1] & SD_FLAG_PROFILE)) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_FINAL and SD_FLAG_PROFILE do not go together: the profile pass reads the kept rows and the read text on the host");
+        return SD_ERR_PARAM;
+    }
     if (who) {
         rc = check_device_list(who, devices, n_devices, errbuf, errlen);
         if (rc) return rc;
@@ -471,7 +562,7 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
         set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a device list of one entry: the batches of a job would lie on several devices");
         return SD_ERR_PARAM;
     }
-    q.reserved[1] &= ~SD_FLAG_DEVICE_ROWS;   // (the flag shapes the stream, not its engines)
+    q.reserved[1] &= ~(SD_FLAG_DEVICE_ROWS | SD_FLAG_DEVICE_FINAL);   // (the flags shape the stream, not its engines)
     if (final && !mono_names) { set_err(errbuf, errlen, "no monomer names"); return SD_ERR_PARAM; }
     if (final && !lr_coef) { set_err(errbuf, errlen, "no logistic-regression coefficients"); return SD_ERR_PARAM; }
     for (int32_t m = 0; m < n_mono; ++m) {
@@ -493,6 +584,7 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     }
     s->p = q;
     s->dev_rows = dev_rows;
+    s->dev_final = dev_final;
     s->sub_batches = std::max(1, (int)sub_batches);
     std::vector<const char*> ms;
     for (const std::string& m : s->mono) ms.push_back(m.data());
@@ -580,21 +672,21 @@ static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const i
 // A record store for a new job of a device-rows stream: a spare one whose last scatter -- enqueued on that job's caller's
 // stream, which may be far behind -- has completed; else a new one, so that a slow consumer never stalls the pipeline
 // and no buffer a pending scatter reads is ever reallocated.  Beyond eight spares the oldest is waited for instead.
-static std::unique_ptr<RowsWS> stream_take_ws(sd_stream* s) {
-    std::vector<std::unique_ptr<RowsWS>>& sp = s->ws_spare;
+template <class WS>
+static std::unique_ptr<WS> stream_take_ws(std::vector<std::unique_ptr<WS>>& sp) {
     for (size_t i = sp.size(); i-- > 0;)
         if (sp[i]->idle()) {
-            std::unique_ptr<RowsWS> ws = std::move(sp[i]);
+            std::unique_ptr<WS> ws = std::move(sp[i]);
             sp.erase(sp.begin() + (long)i);
             return ws;
         }
     if (sp.size() >= 8) {
-        std::unique_ptr<RowsWS> ws = std::move(sp.front());
+        std::unique_ptr<WS> ws = std::move(sp.front());
         sp.erase(sp.begin());
         ws->wait_idle();
         return ws;
     }
-    return std::unique_ptr<RowsWS>(new RowsWS);
+    return std::unique_ptr<WS>(new WS);
 }
 
 static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads,
@@ -612,9 +704,13 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
     if (!job->row_off) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
     FinalMode* fm = s->fin.get();
     job->reads = read_seqs;
-    if (s->dev_rows) {
-        job->ws = stream_take_ws(s);
+    if (s->dev_rows || s->dev_final) {
+        job->ws = stream_take_ws(s->ws_spare);
         job->ws_home = &s->ws_spare;
+    }
+    if (s->dev_final) {
+        job->fws = stream_take_ws(s->fws_spare);
+        job->fws_home = &s->fws_spare;
     }
     if (dv) {
         // the data's device is current while the job's events and copies are made (the entries all run on it)
@@ -744,6 +840,7 @@ int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n
     *rows = nullptr;
     *row_off = nullptr;
     if (n_rows) *n_rows = 0;
+    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: its rows are not on the host"); return SD_ERR_PARAM; }
     if (s->fin) { set_err(errbuf, errlen, "a final-mode stream is collected with sd_stream_collect_final"); return SD_ERR_PARAM; }
     if (s->dev_rows) { set_err(errbuf, errlen, "a device-rows stream (SD_FLAG_DEVICE_ROWS) is collected with sd_stream_collect_dev: its rows are not on the host"); return SD_ERR_PARAM; }
     if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect without a submitted job"); return SD_ERR_PARAM; }
@@ -776,6 +873,7 @@ int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off
     if (n_rows) *n_rows = 0;
     if (alt) *alt = nullptr;
     if (!s->fin) { set_err(errbuf, errlen, "sd_stream_collect_final on a stream made by sd_stream_create"); return SD_ERR_PARAM; }
+    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: its rows are not on the host"); return SD_ERR_PARAM; }
     if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_final without a submitted job"); return SD_ERR_PARAM; }
     const double t0 = now_s();
     int rc = stream_wait_oldest(s, errbuf, errlen);
@@ -813,6 +911,7 @@ int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off
 
 int sd_stream_peek_dev(sd_stream* s, int32_t* n_reads, int64_t* max_rows, char* errbuf, size_t errlen) {
     if (!s) return SD_ERR_PARAM;
+    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is peeked with sd_stream_peek_final_dev"); return SD_ERR_PARAM; }
     if (!s->dev_rows) { set_err(errbuf, errlen, "sd_stream_peek_dev on a stream made without SD_FLAG_DEVICE_ROWS"); return SD_ERR_PARAM; }
     if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_peek_dev without a submitted job"); return SD_ERR_PARAM; }
     const double t0 = now_s();
@@ -829,6 +928,7 @@ int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_
                           int64_t* n_rows, char* errbuf, size_t errlen) {
     if (!s || !d_row_off || cap_rows < 0 || (cap_rows > 0 && !d_rows)) return SD_ERR_PARAM;
     if (n_rows) *n_rows = 0;
+    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: it has final rows, not raw ones"); return SD_ERR_PARAM; }
     if (!s->dev_rows) { set_err(errbuf, errlen, "sd_stream_collect_dev on a stream made without SD_FLAG_DEVICE_ROWS: its rows are on the host (sd_stream_collect)"); return SD_ERR_PARAM; }
     if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_dev without a submitted job"); return SD_ERR_PARAM; }
     const double t0 = now_s();
@@ -887,6 +987,196 @@ int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_
     return rc;
 }
 
+// ---- SD_FLAG_DEVICE_FINAL: the final rows of a job, selected on the device ---------------------------------------
+
+// The text-based path of a device-final job, once per job: a job without in-stream identities (SD_FLAG_NO_STREAM_IDENT, a
+// template set the kernels do not take) or with rows the words do not decide.  The merged raw rows come to the host, the
+// reads too where they lie on the device, and the post-processor of the file path computes every identity from the
+// text; the rows stay in job.fin / alt / fin_off.  Correct and slow.
+static int final_dev_slow(sd_stream* s, StreamJob& job, std::string& err) {
+    if (job.slow_done) { err = job.err; return job.rc; }
+    job.slow_done = true;
+    FinalMode& fm = *s->fin;
+    RowsWS& ws = *job.ws;
+    FinalWS& fw = *job.fws;
+    const size_t nr = (size_t)job.n_reads;
+    const int64_t n = ws.h_total.p[0];
+    std::vector<sd_rec> rows((size_t)std::max<int64_t>(n, 1));
+    std::vector<int64_t> off(nr + 1, 0);
+    // a stream of the stream's own: the pipeline's rows stream may already hold later jobs' appends, merges and
+    // selections, which this job need not wait for (the merge it reads from is through: ev_asm has been waited for)
+    if (!s->slow_st) SD_HIP(hipStreamCreateWithFlags(&s->slow_st, hipStreamNonBlocking));
+    hipStream_t st = s->slow_st;
+    fw.mrows.alloc((size_t)std::max<int64_t>(n, 1));
+    fw.moff.alloc(nr + 1);
+    fw.settled = false;
+    rows_scatter(ws, st, ws.recs.p, fw.mrows.p, n, fw.moff.p);
+    if (n > 0) SD_HIP(hipMemcpyAsync(rows.data(), fw.mrows.p, (size_t)n * sizeof(sd_rec), hipMemcpyDeviceToHost, st));
+    SD_HIP(hipMemcpyAsync(off.data(), fw.moff.p, (nr + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SD_HIP(hipStreamSynchronize(st));
+    fw.settled = true;
+    std::vector<sd::PostRead> pr;
+    for (size_t r = 0; r < nr; ++r) {
+        if (job.dev) {   // the job's device copy of the reads (stream_dev_job)
+            job.seq[r].resize((size_t)job.rlen[r]);
+            SD_HIP(hipMemcpy(&job.seq[r][0], job.text->p + job.text_off[r], (size_t)job.rlen[r], hipMemcpyDeviceToHost));
+        }
+        pr.push_back(sd::PostRead{"", 0, job.seq[r].data(), (int64_t)job.seq[r].size()});
+    }
+    job.rc = fm.pp.process_rows(pr.data(), nr, 0, rows.data(), off.data(), job.fin, job.alt, job.err, nullptr);
+    if (job.dev)
+        for (size_t r = 0; r < nr; ++r) std::string().swap(job.seq[r]);
+    if (job.rc) { err = job.err; return job.rc; }
+    job.fin_off.assign(nr + 1, 0);
+    for (size_t i = 0; i < job.fin.n; ++i) ++job.fin_off[(size_t)job.fin.p[i].read + 1];   // rows come in read order
+    for (size_t r = 0; r < nr; ++r) job.fin_off[r + 1] += job.fin_off[r];
+    return SD_OK;
+}
+
+// The kept-row count of the oldest job, which has been waited for: 16 bytes from the selection, or the text-based path.
+static int final_dev_count(sd_stream* s, StreamJob& job, int64_t& n, std::string& err) {
+    n = 0;
+    if (!job.assembled) return SD_OK;   // (a job without chunks: no reads)
+    RowsWS& ws = *job.ws;
+    FinalWS& fw = *job.fws;
+    SD_HIP(hipEventSynchronize(ws.ev_asm));
+    ws.settled = true;
+    bool slow = !job.selected;
+    if (job.selected) {
+        SD_HIP(hipEventSynchronize(fw.ev_sel));
+        fw.settled = true;
+        slow = fw.h_counts.p[1] != 0;
+    }
+    if (slow) {
+        const int rc = final_dev_slow(s, job, err);
+        if (rc) return rc;
+        n = (int64_t)job.fin.n;
+    } else {
+        n = fw.h_counts.p[0];
+    }
+    return SD_OK;
+}
+
+int sd_stream_peek_final_dev(sd_stream* s, int32_t* n_reads, int64_t* n_rows, int32_t* n_keys, char* errbuf, size_t errlen) {
+    if (!s) return SD_ERR_PARAM;
+    if (!s->dev_final) { set_err(errbuf, errlen, "sd_stream_peek_final_dev on a stream made without SD_FLAG_DEVICE_FINAL"); return SD_ERR_PARAM; }
+    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_peek_final_dev without a submitted job"); return SD_ERR_PARAM; }
+    const double t0 = now_s();
+    int rc = stream_wait_oldest(s, errbuf, errlen);
+    if (rc == SD_OK) {
+        StreamJob& job = *s->jobs.front();
+        const int dev = s->me.devs[0];
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        int64_t n = 0;
+        try {
+            if (cur != dev) SD_HIP(hipSetDevice(dev));
+            std::string err;
+            rc = final_dev_count(s, job, n, err);
+            if (rc) set_err(errbuf, errlen, err);
+        } catch (const HipFail& f) {
+            set_err(errbuf, errlen, f.msg);
+            rc = SD_ERR_HIP;
+        } catch (const std::bad_alloc&) {
+            set_err(errbuf, errlen, "out of host memory");
+            rc = SD_ERR_INTERNAL;
+        }
+        if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+        if (rc == SD_OK) {
+            if (n_reads) *n_reads = job.n_reads;
+            if (n_rows) *n_rows = n;
+            if (n_keys) *n_keys = (int32_t)s->fin->pp.key_names().size();
+        } else {
+            s->jobs.erase(s->jobs.begin());   // (a job whose rows cannot be made is dropped, as collect drops it)
+        }
+    }
+    s->collect_s += now_s() - t0;
+    return rc;
+}
+
+int sd_stream_collect_final_dev(sd_stream* s, sd_final_row* d_rows, int64_t cap_rows, int64_t* d_row_off, double* d_alt,
+                                void* hip_stream, int64_t* n_rows, char* errbuf, size_t errlen) {
+    if (!s || !d_row_off || cap_rows < 0 || (cap_rows > 0 && !d_rows)) return SD_ERR_PARAM;
+    if (n_rows) *n_rows = 0;
+    if (!s->dev_final) { set_err(errbuf, errlen, "sd_stream_collect_final_dev on a stream made without SD_FLAG_DEVICE_FINAL"); return SD_ERR_PARAM; }
+    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_final_dev without a submitted job"); return SD_ERR_PARAM; }
+    const bool sb = s->fin->second_best;
+    if (sb && cap_rows > 0 && !d_alt) { set_err(errbuf, errlen, "sd_stream_collect_final_dev: a second_best stream needs the alt buffer"); return SD_ERR_PARAM; }
+    const double t0 = now_s();
+    int rc = stream_wait_oldest(s, errbuf, errlen);
+    if (rc != SD_OK) {
+        s->collect_s += now_s() - t0;
+        return rc;
+    }
+    StreamJob& job = *s->jobs.front();
+    const int dev = s->me.devs[0];
+    const void* const bufs[3] = {cap_rows > 0 ? d_rows : nullptr, d_row_off, sb && cap_rows > 0 ? d_alt : nullptr};
+    const char* const what[3] = {"row", "row-offset", "alt"};
+    for (int b = 0; b < 3; ++b) {
+        if (!bufs[b]) continue;
+        std::string err;
+        int at = dev;
+        rc = device_pointer(bufs[b], at, err);
+        if (rc == SD_OK && at != dev) {
+            err = std::string("the ") + what[b] + " buffer lies in the memory of device " + std::to_string(at) + ", the stream runs on device " + std::to_string(dev);
+            rc = SD_ERR_UNSUPPORTED;
+        }
+        if (rc) {
+            set_err(errbuf, errlen, rc == SD_ERR_UNSUPPORTED ? err : std::string("sd_stream_collect_final_dev: the ") + what[b] + " buffer is not in device memory");
+            s->collect_s += now_s() - t0;
+            return rc;
+        }
+    }
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    bool keep_job = false;
+    try {
+        if (cur != dev) SD_HIP(hipSetDevice(dev));
+        hipStream_t user = reinterpret_cast<hipStream_t>(hip_stream);
+        int64_t n = 0;
+        std::string err;
+        rc = final_dev_count(s, job, n, err);
+        if (rc) set_err(errbuf, errlen, err);
+        if (rc == SD_OK) {
+            const size_t nk = s->fin->pp.key_names().size();
+            if (n_rows) *n_rows = n;
+            if (cap_rows < n) {
+                set_err(errbuf, errlen, "sd_stream_collect_final_dev: the job has " + std::to_string(n) + " rows, the buffers room for " + std::to_string(cap_rows));
+                rc = SD_ERR_PARAM;
+                keep_job = true;
+            } else if (!job.assembled) {
+                SD_HIP(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * ((size_t)job.n_reads + 1), user));
+            } else if (job.slow_done) {
+                // the rows of the text-based path: pageable memory of the job's, so the host waits for the copies
+                if (n > 0) SD_HIP(hipMemcpyAsync(d_rows, job.fin.p, (size_t)n * sizeof(sd_final_row), hipMemcpyHostToDevice, user));
+                SD_HIP(hipMemcpyAsync(d_row_off, job.fin_off.data(), job.fin_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, user));
+                if (sb && n > 0) SD_HIP(hipMemcpyAsync(d_alt, job.alt.p, (size_t)n * nk * sizeof(double), hipMemcpyHostToDevice, user));
+                SD_HIP(hipStreamSynchronize(user));
+            } else {
+                FinalWS& fw = *job.fws;
+                SD_HIP(hipStreamWaitEvent(user, fw.ev_sel, 0));
+                final_scatter(fw, user, d_rows, cap_rows, d_row_off, sb ? d_alt : nullptr);
+                // (the scatter reads the merged-row count in the record store's workspace: the store waits for it too)
+                RowsWS& ws = *job.ws;
+                if (!ws.ev_free) SD_HIP(hipEventCreateWithFlags(&ws.ev_free, hipEventDisableTiming));
+                SD_HIP(hipEventRecord(ws.ev_free, user));
+                ws.free_recorded = true;
+            }
+            if (rc == SD_OK) s->fin->kept += n;
+        }
+    } catch (const HipFail& f) {
+        set_err(errbuf, errlen, f.msg);
+        rc = SD_ERR_HIP;
+    } catch (const std::bad_alloc&) {
+        set_err(errbuf, errlen, "out of host memory");
+        rc = SD_ERR_INTERNAL;
+    }
+    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+    if (!keep_job) s->jobs.erase(s->jobs.begin());
+    s->collect_s += now_s() - t0;
+    return rc;
+}
+
 int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys) {
     if (!s || !s->fin || (cap > 0 && !keys)) return SD_ERR_PARAM;
     const std::vector<std::string>& k = s->fin->pp.key_names();
@@ -916,7 +1206,8 @@ int sd_stream_final_stats(sd_stream* s, double out[4]) {
     std::lock_guard<std::mutex> g(s->me.m);
     out[0] = fm ? t.ident_ms : 0.0;
     out[1] = fm ? (double)t.ident_pairs : 0.0;
-    out[2] = fm ? (double)s->me.fallback_blocks : 0.0;
+    // (a device-final stream runs the text-based path inside peek / collect, on the caller's thread)
+    out[2] = fm ? (double)(s->dev_final ? fm->pp.fallback_blocks : s->me.fallback_blocks) : 0.0;
     out[3] = fm ? (double)fm->kept : 0.0;
     return SD_OK;
 }

@@ -145,10 +145,13 @@ def format_alt(rows):
 
 
 def final_rows(final, read_names, keys):
-    """The rows of a final-mode stream job (lib.Stream(final=True).collect(): a FinalRows, or its (rows, row_off, alt))
+    """The rows of a final-mode stream job (lib.Stream(final=True).collect(): a FinalRows, or its (rows, row_off, alt);
+    a lib.DeviceFinalRows of a device_final stream is copied to the host first)
     as the command line would write them: ([FinalRow], [AltRow]) -- format_final / format_alt of these are the text of
     <out>.tsv / <out>_alt.tsv.  read_names: the job's reads in submit order; keys: Stream.keys().  The _alt list is
     empty without second_best (alt None)."""
+    if hasattr(final, "n_rows") and hasattr(final.rows, "cpu"):   # a lib.DeviceFinalRows: copied to the host first
+        final = final.to_host()
     rows, _, alt = final
     name = lambda k: keys[k] if k >= 0 else "None"   # noqa: E731
     fin, alts = [], []

@@ -48,6 +48,7 @@ EXPORTS = [
     "sd_profile_segments", "sd_profile_segments_dev", "sd_last_run_profile", "sd_stream_profile",
     "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev", "sd_engine_filter_result",
     "sd_stream_peek_dev", "sd_stream_collect_dev", "sd_engine_rows_dev", "sd_seam_merge_dev", "sd_seam_pieces_selftest",
+    "sd_stream_peek_final_dev", "sd_stream_collect_final_dev", "sd_final_select_dev", "sd_final_select_host",
 ]
 
 
@@ -224,6 +225,14 @@ def load():
                                     C.c_void_p, P(C.c_int64)]
     L.sd_seam_pieces_selftest.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           P(C.c_int64)]
+    L.sd_stream_peek_final_dev.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int64), P(C.c_int32), C.c_char_p, C.c_size_t]
+    L.sd_stream_collect_final_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              P(C.c_int64), C.c_char_p, C.c_size_t]
+    sel = [P(C.c_char_p), P(C.c_char_p), P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, P(C.c_double), C.c_void_p, C.c_void_p,
+           C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    out = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
+    L.sd_final_select_host.argtypes = sel + out
+    L.sd_final_select_dev.argtypes = sel + [C.c_int32, C.c_void_p] + out
     _lib = L
     return L
 
@@ -245,6 +254,7 @@ FLAG_NO_IDENT_PRUNE = 256   # --second-best: every homopolymer-compressed pair a
 FLAG_NO_U16 = 128     # narrow layout: fp16 / int16 cells as in rounds 1-5 instead of the biased-u16 format
 FLAG_PROFILE = 512    # per-monomer column profiles of the kept rows (run_files(profile=True), Stream(profile=True))
 FLAG_DEVICE_ROWS = 1024   # Stream(device_rows=True): the rows are assembled on the device and stay there
+FLAG_DEVICE_FINAL = 2048  # Stream(final=True, device_final=True): the final rows are selected on the device and stay there
 
 
 def make_params(scoring=(-1, -1, -1, 1), part_size=5000, overlap=500, ed_thr=-1, threads=1,
@@ -760,6 +770,19 @@ DeviceRows = namedtuple("DeviceRows", "rows row_off n_rows")
 rows[row_off[r]:row_off[r+1]]), n_rows as a Python int."""
 
 
+class DeviceFinalRows(namedtuple("DeviceFinalRows", "rows row_off alt n_rows")):
+    """Final rows that stay in device memory (Stream.collect_final_device): rows = a uint8 [n_rows, 80] torch tensor (the
+    bytes of sd_final_row: on the host it views as final_dtype()), row_off = int64 [n_reads + 1] on the same device, alt =
+    float64 [n_rows, n_keys] (second_best) or None, n_rows as a Python int."""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> FinalRows (numpy), what Stream(final=True).collect() returns for the same job."""
+        import numpy as np
+        r = np.ascontiguousarray(self.rows.cpu().numpy()).reshape(-1).view(final_dtype())
+        return FinalRows(r, self.row_off.cpu().numpy(), None if self.alt is None else self.alt.cpu().numpy())
+
+
 def _torch_stream(torch, dev, stream):
     """stream=None: the current stream of the device (DeviceReads' convention); an int: that hipStream_t; else a
     torch stream."""
@@ -876,18 +899,27 @@ class Stream:
     collect_device() / imap(device=True) return a DeviceRows of torch tensors; with DeviceReads input no base and no row
     passes through the host.  collect() is refused on such a stream, collect_device() on a plain one.
 
+    device_final=True (final mode, one device): the final rows are selected on the device (csrc/sd_final_dev.hip) and
+    stay there -- collect_final_device() / imap(device=True) return a DeviceFinalRows of torch tensors with the bytes
+    collect() would return; with DeviceReads input no base, record or identity word passes through the host.  Jobs the
+    identity words cannot decide (a block of ~19.6 kb and more, flags=FLAG_NO_STREAM_IDENT) are finished by the host's
+    text-based path: the same rows, slowly (stats()["fallback_blocks"]).  Not with profile, device_rows or several devices.
+
     devices (a list of ordinals, repeats allowed; `device` is then ignored): one pipeline per entry in this process
     (sd_stream_create_devices / sd_stream_create_final_devices), each driven by a thread of its own; every job is cut
     into at least two batches per entry and the rows are those of the plain stream.  [d] is the plain stream on d."""
 
     def __init__(self, mono_seqs, sub_batches=1, final=False, mono_names=None, second_best=False, min_identity=0,
-                 lr_coef=None, devices=None, profile=False, device_rows=False, **kw):
+                 lr_coef=None, devices=None, profile=False, device_rows=False, device_final=False, **kw):
         self.L = load()
         if profile:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_PROFILE
         if device_rows:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_ROWS
+        if device_final:
+            kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_FINAL
         self.device_rows = bool(device_rows)
+        self.device_final = bool(device_final)
         self.params = make_params(**kw)
         self._err = C.create_string_buffer(4096)
         ms = [_b(s) for s in mono_seqs]
@@ -1007,6 +1039,32 @@ class Stream:
         self._n_reads.pop(0)
         return DeviceRows(rows[:n.value], row_off, int(n.value))
 
+    def collect_final_device(self, stream=None):
+        """Final rows of the oldest job of a device_final stream -> DeviceFinalRows, on the stream's device.  The exact
+        row count comes first (sd_stream_peek_final_dev), torch allocates the tensors on `stream` -- a torch stream or a
+        hipStream_t; None: the current stream of that device -- and the library fills them there (collect_device's
+        rules: work enqueued on the stream afterwards sees the rows, the tensors are the caller's)."""
+        import torch
+        devs = self.devices if self.devices is not None else [self.params.device]
+        dev = torch.device("cuda", devs[0])
+        st = _torch_stream(torch, dev, stream)
+        nr, n, nk = C.c_int32(), C.c_int64(), C.c_int32()
+        rc = self.L.sd_stream_peek_final_dev(self.h, C.byref(nr), C.byref(n), C.byref(nk), self._err, 4096)
+        if rc not in (SD_OK, SD_ERR_PARAM) and self._n_reads:
+            self._n_reads.pop(0)   # (a job whose rows could not be made has been dropped; a refused call leaves it)
+        self._check(rc)
+        with torch.cuda.stream(st):
+            rows = torch.empty((n.value, 80), dtype=torch.uint8, device=dev)
+            row_off = torch.empty(nr.value + 1, dtype=torch.int64, device=dev)
+            alt = torch.empty((n.value, nk.value), dtype=torch.float64, device=dev) if self.second_best else None
+        got = C.c_int64()
+        self._check(self.L.sd_stream_collect_final_dev(self.h, C.c_void_p(rows.data_ptr() if n.value else 0), n.value,
+                                                       C.c_void_p(row_off.data_ptr()),
+                                                       C.c_void_p(alt.data_ptr() if alt is not None and n.value else 0),
+                                                       C.c_void_p(st.cuda_stream), C.byref(got), self._err, 4096))
+        self._n_reads.pop(0)
+        return DeviceFinalRows(rows, row_off, alt, int(got.value))
+
     def _collect_final(self):
         import numpy as np
         rows = C.POINTER(FinalRec)()
@@ -1037,7 +1095,8 @@ class Stream:
         before a job is collected -- the order of calls that keeps the device busy (sd_hip.h at sd_stream_create: the
         traceback of a batch ends with the fill of the next one, so with only ONE job outstanding the job after that is
         enqueued late; bench.py's timed loop is this generator).  device=True (a device_rows stream): every job is
-        collected with collect_device() on the current stream of the stream's device and yields a DeviceRows.
+        collected with collect_device() on the current stream of the stream's device and yields a DeviceRows; on a
+        device_final stream with collect_final_device(), yielding a DeviceFinalRows.
 
         The default depth is DEPTH = 2 with a device list too.  There every job is cut into at least two batches per
         entry, so two jobs outstanding give each entry at least four batches -- more than its pipeline's three slots --
@@ -1045,7 +1104,9 @@ class Stream:
         one pipeline gets from two single-batch jobs.  A deeper queue would only hold more reads and rows in memory
         (a raw-mode submit already waits until its batches are packed, so it cannot run far ahead of the devices)."""
         depth = self.DEPTH if depth is None else max(0, int(depth))
-        collect = self.collect_device if device else (lambda: self.collect(as_lists=as_lists))   # device: DeviceRows
+        collect = lambda: self.collect(as_lists=as_lists)   # noqa: E731
+        if device:   # DeviceRows / DeviceFinalRows
+            collect = self.collect_final_device if self.device_final else self.collect_device
         out = 0
         for reads in jobs:
             self.submit(reads)
@@ -1206,6 +1267,88 @@ def seam_merge_device(recs, read_off, piece=0, device=0, stream=None, pad=0):
     intact = bool((h_rows[:pad] == -559038737).all() and (h_rows[pad + n.value:] == -559038737).all()
                   and (h_off[:pad] == -559038737).all() and (h_off[pad + len(o):] == -559038737).all())
     return rows, row_off, intact
+
+
+def _final_select_args(mono_names, mono_seqs, min_identity, second_best, lr_coef):
+    ms = [_b(s) for s in mono_seqs]
+    if lr_coef is None:
+        from .main import _lr_coef
+        lr_coef = _lr_coef()
+    return [_strs(mono_names), _strs(ms), (C.c_int32 * max(len(ms), 1))(*[len(s) for s in ms]), len(ms), int(min_identity),
+            1 if second_best else 0, (C.c_double * 3)(*[float(x) for x in lr_coef])]
+
+
+def _final_select_arrays(rows, row_off, widx, words, hwords, read_len, second_best, n_mono):
+    import numpy as np
+    r, o = _recs_array(rows, row_off)
+    per = 2 * n_mono if second_best else 1
+    wi = np.ascontiguousarray(widx, dtype=np.int64)
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, per)
+    h = np.ascontiguousarray(hwords, dtype=np.uint32).reshape(-1, per) if second_best else None
+    if len(wi) != len(r) or (h is not None and h.shape != w.shape):
+        raise SdError(SD_ERR_PARAM, "final_select: one word index per row, hwords shaped as words")
+    rl = None if read_len is None else np.ascontiguousarray(read_len, dtype=np.int64)
+    if rl is not None and len(rl) != len(o) - 1:
+        raise SdError(SD_ERR_PARAM, "final_select: one length per read")
+    return r, o, wi, w, h, rl, per
+
+
+def final_select_host(mono_names, mono_seqs, rows, row_off, widx, words, hwords=None, read_len=None, min_identity=0,
+                      second_best=False, lr_coef=None):
+    """The host's selection alone on identity words (sd_final_select_host).  rows: [n, 4] int32 (tmpl, start, end,
+    score), merged, read-global; row_off: n_reads + 1 offsets; widx: per row, which row of words / hwords holds its words
+    ([n_word_rows, per] uint32, per = 1 or, with second_best, 2 * monomers).  -> (FinalRows, n_undecided)."""
+    import numpy as np
+    r, o, wi, w, h, rl, per = _final_select_arrays(rows, row_off, widx, words, hwords, read_len, second_best, len(mono_seqs))
+    nk = len(dict.fromkeys(x for n in mono_names for x in (n, n + "'")))
+    out = np.zeros(max(len(r), 1), dtype=final_dtype())
+    out_off = np.zeros(len(o), dtype=np.int64)
+    alt = np.zeros((max(len(r), 1), nk), dtype=np.float64) if second_best else None
+    n, und = C.c_int64(), C.c_int64()
+    rc = load().sd_final_select_host(*_final_select_args(mono_names, mono_seqs, min_identity, second_best, lr_coef),
+                                     r.ctypes.data, o.ctypes.data, len(o) - 1, wi.ctypes.data, w.ctypes.data,
+                                     h.ctypes.data if h is not None else None, len(w), per,
+                                     rl.ctypes.data if rl is not None else None, out.ctypes.data, out_off.ctypes.data,
+                                     alt.ctypes.data if alt is not None else None, C.byref(n), C.byref(und))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_final_select_host")
+    return FinalRows(out[:n.value], out_off, None if alt is None else alt[:n.value]), int(und.value)
+
+
+def final_select_device(mono_names, mono_seqs, rows, row_off, widx, words, hwords=None, read_len=None, min_identity=0,
+                        second_best=False, lr_coef=None, device=0, stream=None):
+    """The selection kernels alone (sd_final_select_dev), arguments and result as final_select_host; the arrays go to
+    `device` through torch and the results come back as numpy.  Every output buffer carries guard bytes behind it: the
+    result is (FinalRows, n_undecided, intact)."""
+    import numpy as np
+    import torch
+    r, o, wi, w, h, rl, per = _final_select_arrays(rows, row_off, widx, words, hwords, read_len, second_best, len(mono_seqs))
+    nk = len(dict.fromkeys(x for n in mono_names for x in (n, n + "'")))
+    dev = torch.device("cuda", int(device))
+    st = _torch_stream(torch, dev, stream)
+    G = 0x5a
+    with torch.cuda.stream(st):
+        up = lambda a: None if a is None else torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev)   # noqa: E731
+        d_r, d_o, d_wi, d_w, d_h, d_rl = up(r), up(o), up(wi), up(w), up(h), up(rl)
+        d_out = torch.full(((len(r) + 1) * 80,), G, dtype=torch.uint8, device=dev)
+        d_off = torch.full(((len(o) + 1) * 8,), G, dtype=torch.uint8, device=dev)
+        d_alt = torch.full(((len(r) * nk + 1) * 8,), G, dtype=torch.uint8, device=dev) if second_best else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)   # noqa: E731
+        n, und = C.c_int64(), C.c_int64()
+        rc = load().sd_final_select_dev(*_final_select_args(mono_names, mono_seqs, min_identity, second_best, lr_coef),
+                                        ptr(d_r), ptr(d_o), len(o) - 1, ptr(d_wi), ptr(d_w), ptr(d_h), len(w), per,
+                                        ptr(d_rl), int(device), C.c_void_p(st.cuda_stream), ptr(d_out), ptr(d_off),
+                                        ptr(d_alt), C.byref(n), C.byref(und))
+        if rc != SD_OK:
+            raise SdError(rc, "sd_final_select_dev")
+        h_out, h_off = d_out.cpu().numpy(), d_off.cpu().numpy()
+        h_alt = d_alt.cpu().numpy() if d_alt is not None else None
+    k = n.value
+    intact = bool((h_out[k * 80:] == G).all() and (h_off[len(o) * 8:] == G).all()
+                  and (h_alt is None or (h_alt[k * nk * 8:] == G).all()))
+    out = h_out[:k * 80].copy().view(final_dtype())
+    alt = None if h_alt is None else h_alt[:k * nk * 8].copy().view(np.float64).reshape(k, nk)
+    return FinalRows(out, h_off[:len(o) * 8].copy().view(np.int64), alt), int(und.value), intact
 
 
 def fasta_load(path):
