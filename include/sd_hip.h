@@ -71,6 +71,8 @@ typedef struct sd_params {
                                       stay there (sd_stream_peek_dev / sd_stream_collect_dev); no record crosses to the host */
 #define SD_FLAG_DEVICE_FINAL 2048  /* final-mode streams with one device entry: the rows of final_decomposition.tsv / _alt.tsv are
                                       selected on the device and stay there (sd_stream_peek_final_dev / sd_stream_collect_final_dev) */
+#define SD_FLAG_DEVICE_PROFILE 4096 /* SD_FLAG_DEVICE_FINAL streams: the column profiles of the kept rows are folded on the device
+                                      from the job's text in HBM (sd_stream_profile / sd_stream_profile_dev) */
 
 void sd_params_default(sd_params* p); /* -1,-1,-1,1 / 5000 / 500 / -1 / 1 / 0 / auto */
 
@@ -548,6 +550,53 @@ int sd_stream_final_stats(sd_stream* s, double out[4]);
  * or one created without the flag. */
 int sd_stream_profile(sd_stream* s, int32_t reset, int32_t* n_monomers, int64_t* n_counts, int64_t* text_bytes,
                       char* text, uint64_t* counts);
+/* ---- profiles folded on the device (SD_FLAG_DEVICE_PROFILE, with SD_FLAG_DEVICE_FINAL, at sd_stream_create_final) ------
+ * A mode of its own beside SD_FLAG_PROFILE, whose pass reads the kept rows and the read text on the host (and stays
+ * refused on a device-final stream).  Here, behind the selection of a job and on the same stream, one kernel plans the
+ * pair of every kept row -- the segment the selection measured (the read's place in the job's text plus the clamped
+ * [start, end]; length 0 is no instance) against the row's own interleaved template; csrc/sd_final_prof_dev.hpp, one
+ * text for host and device -- the pairs of the fold kernel (set's longest template <= 512 bp, segment of 1 .. 1024 bp,
+ * no Hirschberg split) are counted per forward monomer and scattered into groups, the others are compacted into a list
+ * of 16 bytes each, and 4 (monomers + 2) bytes of summary reach pinned memory with the selection's counts.
+ * sd_stream_collect_final_dev then sizes checkpoints, work items and grid from the summary and enqueues the fold kernel
+ * of sd_profile_segments_dev on a stream the sd_stream owns, reading the job's own text in HBM -- the copy a
+ * sd_stream_submit_dev job has anyway; a job submitted from host memory uploads its reads once, asynchronously -- and
+ * adding into the stream's 64-bit counters in HBM.  No base, record or row crosses to the host.  The fold outlives the
+ * collect: the job's workspace and text are not reused before the host has seen an event behind it, and
+ * sd_stream_destroy waits for it.  Rows, row offsets and alt are byte for byte those of the stream without the flag.
+ * What the host still folds, into counters of its own: the listed pairs (only their segments' text is fetched; a job
+ * from host memory reads its own copy), and every job finished by the text-based path (above), through the pass of
+ * SD_FLAG_PROFILE.  Totals = device counters + host counters.
+ * SD_ERR_PARAM before any device is touched, in words that name both flags: on a raw-mode stream, without
+ * SD_FLAG_DEVICE_FINAL, with a device list of more than one entry, with SD_FLAG_PROFILE, with a repeated monomer name.
+ *
+ * sd_stream_profile works on such a stream: it waits for the folds of the jobs whose sd_stream_collect_final_dev has
+ * returned, copies the device counters down and adds the host's; reset zeroes both (the device's in order on the
+ * stream's own stream).  A fold that ran out of checkpoints -- they are sized by the longest segment: it cannot -- is
+ * SD_ERR_INTERNAL.
+ * sd_stream_profile_dev places the same totals (*n_counts of them, the layout of sd_profile_segments) in d_counts, a
+ * DEVICE buffer of the caller's on the stream's device with room for cap_counts, ordered on hip_stream: work enqueued
+ * there afterwards sees them.  cap_counts too small (or d_counts NULL): SD_ERR_PARAM with *n_counts set and a message
+ * that names the exact size; nothing is written.
+ * sd_stream_profile_stats: [0] pairs folded on the device, [1] pairs folded on the host (listed pairs and the kept rows
+ * of text-based jobs), [2] bytes of read text the profile fetched to the host, [3] fold kernels, ms (HIP events, of
+ * the folds that have completed).  All 0 on any other stream. */
+int sd_stream_profile_dev(sd_stream* s, int32_t reset, uint64_t* d_counts, int64_t cap_counts, void* hip_stream,
+                          int64_t* n_counts, char* errbuf, size_t errlen);
+int sd_stream_profile_stats(sd_stream* s, double out[4]);
+/* The plan / group / fold alone, in the manner of sd_final_select_dev / _host: text = the reads back to back, read r =
+ * text[read_off[r] .. read_off[r + 1]) (n_reads + 1 offsets); rows[row_off[r] .. row_off[r + 1]) = the rows of read r
+ * (tmpl in the DP's order: monomer t, T + t = its reverse complement; start / end in read coordinates, clamped as the
+ * selection clamps them), keep[b] != 0 = row b is a kept row; templates = the T FORWARD monomers.  counts (the layout
+ * of sd_profile_segments) is overwritten; pairs[0] = pairs the fold kernel takes, pairs[1] = pairs left to the host.
+ * _dev uploads its inputs (HOST arrays) and runs exactly the kernels the stream runs, then folds the listed pairs on
+ * host threads; _host runs the same plan text on the host and folds every pair there (device is ignored). */
+int sd_final_profile_dev(const char* text, const int64_t* read_off, int32_t n_reads, const sd_rec* rows, const int64_t* row_off,
+                         const uint8_t* keep, const char* const* templates, const int32_t* tlen, int32_t T, int32_t device,
+                         int32_t threads, uint64_t* counts, int64_t pairs[2]);
+int sd_final_profile_host(const char* text, const int64_t* read_off, int32_t n_reads, const sd_rec* rows, const int64_t* row_off,
+                          const uint8_t* keep, const char* const* templates, const int32_t* tlen, int32_t T, int32_t device,
+                          int32_t threads, uint64_t* counts, int64_t pairs[2]);
 
 /* ---- a stream on several devices of this process ----------------------------------------------------------------
  * sd_stream_create / sd_stream_create_final with a device list: one batch pipeline per entry of devices[0 .. n_devices)

@@ -121,6 +121,16 @@ int PostProcessor::profile_kept(const Batch& bt, const sd_rec* rows, std::string
     return SD_OK;
 }
 
+int PostProcessor::profile_pairs(const char* const* q, const int32_t* qlen, const int32_t* il, int64_t n, std::string& err) {
+    if (!prof_on) { err = "profile_pairs without enable_profile"; return SD_ERR_INTERNAL; }
+    std::vector<uint64_t> add(prof.size(), 0);
+    const int rc = profile_host(q, qlen, il, n, il_seq, threads, add.data());
+    if (rc) { err = "profile computation failed (rc " + std::to_string(rc) + ")"; return rc; }
+    std::lock_guard<std::mutex> g(*prof_m);
+    for (size_t i = 0; i < add.size(); ++i) prof[i] += add[i];
+    return SD_OK;
+}
+
 int PostProcessor::tmpl_of_name(const std::string& nm) const {
     for (size_t t = 0; t < tname.size(); ++t)
         if (tname[t] == nm) return (int)t;

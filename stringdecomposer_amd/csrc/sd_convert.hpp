@@ -109,6 +109,9 @@ class PostProcessor {
         return v;
     }
     std::string profile_text() const;   // "name\tsequence\n" per monomer, file order
+    // pairs a caller planned itself (a device-final stream's host pairs): query x against interleaved template il[x],
+    // folded by profile_host into prof
+    int profile_pairs(const char* const* q, const int32_t* qlen, const int32_t* il, int64_t n, std::string& err);
     double t_prepare = 0, t_identity = 0, t_format = 0, t_concat = 0, t_profile = 0;   // seconds spent in process(), by stage
     int64_t fallback_blocks = 0;     // blocks whose identities were computed here, not taken from the rows' words
     // set by a caller whose PostRead::seq are not filled in yet: called (once per process* call, before the text is

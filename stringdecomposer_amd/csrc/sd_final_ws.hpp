@@ -8,6 +8,7 @@
 #pragma once
 
 #include "sd_final_dev.hpp"
+#include "sd_final_prof_ws.hpp"
 #include "sd_pipeline.hpp"
 
 namespace sdi {
@@ -53,17 +54,30 @@ struct FinalWS {
     int32_t n_reads = 0, n_keys = 0;
     const int64_t* n_ptr = nullptr;   // device: the number of merged rows
     const int64_t* d_moff = nullptr;
+    // SD_FLAG_DEVICE_PROFILE: the plan of the job's pairs (sd_final_prof_ws.hpp).  The fold runs on the stream's own
+    // stream after collect has returned and reads prof and the job's text; the upload of a host job's text runs there
+    // too.  ev_prof is recorded behind either (ev_f0 before a fold: its time), and the rule of ev_free holds for it:
+    // the host has seen it before this workspace is reused or released.  The job's text (StreamJob::text) waits here
+    // meanwhile, and goes back to the stream's spare list with the workspace's next job.
+    ProfWS prof;
+    hipEvent_t ev_f0 = nullptr, ev_prof = nullptr;
+    bool prof_recorded = false, fold_timed = false;
+    std::unique_ptr<DevBuf<uint8_t>> held_text;
     bool idle() {
         if (free_recorded && hipEventQuery(ev_free) != hipErrorNotReady) { (void)hipGetLastError(); free_recorded = false; }
-        return !free_recorded;
+        if (prof_recorded && hipEventQuery(ev_prof) != hipErrorNotReady) { (void)hipGetLastError(); prof_recorded = false; }
+        return !free_recorded && !prof_recorded;
     }
     void wait_idle() {
         if (free_recorded) { if (hipEventSynchronize(ev_free) != hipSuccess) (void)hipGetLastError(); free_recorded = false; }
+        if (prof_recorded) { if (hipEventSynchronize(ev_prof) != hipSuccess) (void)hipGetLastError(); prof_recorded = false; }
     }
     ~FinalWS() {
         wait_idle();
         if (ev_sel) (void)hipEventDestroy(ev_sel);
         if (ev_free) (void)hipEventDestroy(ev_free);
+        if (ev_f0) (void)hipEventDestroy(ev_f0);
+        if (ev_prof) (void)hipEventDestroy(ev_prof);
     }
 };
 

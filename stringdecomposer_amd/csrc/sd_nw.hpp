@@ -47,6 +47,13 @@ int nw_profile_device(const std::vector<std::pair<const char*, int64_t>>& spans,
 int profile_host(const char* const* q, const int32_t* qlen, const int32_t* pair_il, int64_t n,
                  const std::vector<std::string>& il, int threads, uint64_t* counts);
 int64_t profile_offsets(const std::vector<int32_t>& fwd_len, std::vector<int64_t>& off);   // -> total counters
+// The fold kernel alone (sd_nw_profile<K>): one-wave workgroups over items[0 .. n_items) = {monomer, first, end} into
+// order[], whose entries index seg_start / seg_len / pair_il; lds = 80 K + 48 (tmax + 1) bytes; ck: grid x 64 lanes x
+// cap slots x K x 16 B; counts: the forward monomers' blocks at off[m], ADDED to; *fails counts pairs beyond `cap`.
+void launch_nw_profile(int K, hipStream_t st, int grid, size_t lds, const uint8_t* seq, const int64_t* seg_start,
+                       const int32_t* seg_len, const int32_t* order, const int32_t* pair_il, const int4* items, int n_items,
+                       const unsigned long long* peq, const int32_t* tlen, const int64_t* off, int cap, void* ck, int* ckpos,
+                       unsigned long long* counts, int* fails);
 // accumulated over the device identity calls of the process: preparation + staging, uploads, kernel, downloads
 void nw_stage_seconds(double out[4]);
 

@@ -22,6 +22,9 @@ struct FinalMode {
     // when the first job's rows are assembled
     bool dtab_up = false;
     FinalDevTables dtab;
+    // SD_FLAG_DEVICE_PROFILE: the stream's templates and counters on the device; the pairs of every selected job are
+    // planned behind its selection (sd_final_prof_dev.hip)
+    ProfDev* pd = nullptr;
 };
 
 // A submitted job: its rows as they are assembled and, in final mode, its own copy of the reads and its kept rows.
@@ -64,6 +67,8 @@ struct StreamJob : RowJob {
     bool selected = false, slow_done = false;
     std::vector<int64_t> fin_off;
     ~StreamJob() {
+        // (a fold or an upload still reads the text: it waits in the workspace, under the workspace's event)
+        if (text && spare && fws && fws->prof_recorded) fws->held_text = std::move(text);
         if (text && spare) spare->push_back(std::move(text));
         if (fws && fws_home) fws_home->push_back(std::move(fws));
         if (ws && ws_home) ws_home->push_back(std::move(ws));
@@ -169,6 +174,19 @@ static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st,
                 final_sources(*fw, ws, st);
                 final_select(*fw, st, fm->dtab.tb, ws.recs.p, fw->src.p, fw->src.p, fw->words.p, fw->hwords.p, fw->moff.p,
                              fw->rlen.p, j.n_reads, ws.n_recs, ws.bbase.p + ws.n_tiles);
+                if (fm->pd) {
+                    // the pairs of the kept rows, planned and grouped behind the selection; their summary travels with
+                    // the selection's counts, ahead of ev_sel (recorded anew behind it)
+                    ProfWS& pw = fw->prof;
+                    pw.h_text_off.alloc(nr + 1);
+                    for (size_t r = 0; r < nr; ++r) pw.h_text_off.p[r] = j.text_off[r];
+                    pw.h_text_off.p[nr] = 0;
+                    pw.text_off.alloc(nr + 1);
+                    SD_HIP(hipMemcpyAsync(pw.text_off.p, pw.h_text_off.p, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                    prof_plan(pw, *fm->pd, st, ws.recs.p, fw->src.p, fw->keep.p, fw->moff.p, fw->rlen.p, j.n_reads, ws.n_recs,
+                              ws.bbase.p + ws.n_tiles);
+                    SD_HIP(hipEventRecord(fw->ev_sel, st));
+                }
                 j.selected = true;
             }
         }
@@ -507,11 +525,29 @@ struct sd_stream {
     int ev_src_dev = -1;
     std::vector<std::unique_ptr<StreamJob>> jobs;   // FIFO: submitted, not collected yet
     hipStream_t slow_st = nullptr;       // device-final streams: the text-based path's copies to the host (final_dev_slow)
+    // SD_FLAG_DEVICE_PROFILE: the profiles of the selected jobs are folded on the device, on prof_st, into pd.counts;
+    // what the host folds (pairs the kernel does not take, jobs of the text-based path) is in the post-processor
+    bool dev_prof = false;
+    ProfDev pd;
+    hipStream_t prof_st = nullptr;
+    double prof_ms = 0;                  // fold kernels, HIP events
+    int64_t prof_pairs_dev = 0, prof_pairs_host = 0, prof_text_to_host = 0;
+    PinBuf<unsigned long long> h_up;     // sd_stream_profile_dev: the host's counters on their way to the device
+    DevBuf<unsigned long long> d_up;
+    hipEvent_t ev_up = nullptr, ev_pd = nullptr;
+    bool up_recorded = false;
     int64_t budget = 0;
     double submit_s = 0, collect_s = 0;
     int64_t n_jobs = 0;
     StreamEntries me;                    // destroyed first: its sinks hold pointers to the jobs
     ~sd_stream() {
+        if (prof_st) {   // the folds of collected jobs read pd and the jobs' workspaces
+            (void)hipStreamSynchronize(prof_st);
+            (void)hipStreamDestroy(prof_st);
+        }
+        if (up_recorded) (void)hipEventSynchronize(ev_up);
+        if (ev_up) (void)hipEventDestroy(ev_up);
+        if (ev_pd) (void)hipEventDestroy(ev_pd);
         if (ev_src) (void)hipEventDestroy(ev_src);
         if (slow_st) (void)hipStreamDestroy(slow_st);
     }
@@ -530,6 +566,23 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     sd_params q = *p;
     const bool dev_final = (p->reserved[1] & SD_FLAG_DEVICE_FINAL) != 0;
+    const bool dev_prof = (p->reserved[1] & SD_FLAG_DEVICE_PROFILE) != 0;
+    if (dev_prof && !final) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE needs a final-mode stream made with SD_FLAG_DEVICE_FINAL (sd_stream_create_final): a raw-mode stream selects no rows to profile");
+        return SD_ERR_PARAM;
+    }
+    if (dev_prof && !dev_final) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE needs SD_FLAG_DEVICE_FINAL: it folds the rows the device selects; the rows of a host final stream are profiled with SD_FLAG_PROFILE");
+        return SD_ERR_PARAM;
+    }
+    if (dev_prof && who && n_devices > 1) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE needs SD_FLAG_DEVICE_FINAL and so a device list of one entry: the batches of a job would lie on several devices");
+        return SD_ERR_PARAM;
+    }
+    if (dev_prof && (p->reserved[1] & SD_FLAG_PROFILE)) {
+        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE and SD_FLAG_PROFILE do not go together: a SD_FLAG_DEVICE_FINAL stream folds its profiles on the device, the host pass of SD_FLAG_PROFILE has no rows there");
+        return SD_ERR_PARAM;
+    }
     if (dev_final && (p->reserved[1] & SD_FLAG_DEVICE_ROWS) && final) {
         set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host (or, with SD_FLAG_DEVICE_FINAL alone, on the device)");
         return SD_ERR_PARAM;
@@ -562,7 +615,7 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
         set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a device list of one entry: the batches of a job would lie on several devices");
         return SD_ERR_PARAM;
     }
-    q.reserved[1] &= ~(SD_FLAG_DEVICE_ROWS | SD_FLAG_DEVICE_FINAL);   // (the flags shape the stream, not its engines)
+    q.reserved[1] &= ~(SD_FLAG_DEVICE_ROWS | SD_FLAG_DEVICE_FINAL | SD_FLAG_DEVICE_PROFILE);   // (the flags shape the stream, not its engines)
     if (final && !mono_names) { set_err(errbuf, errlen, "no monomer names"); return SD_ERR_PARAM; }
     if (final && !lr_coef) { set_err(errbuf, errlen, "no logistic-regression coefficients"); return SD_ERR_PARAM; }
     for (int32_t m = 0; m < n_mono; ++m) {
@@ -579,6 +632,10 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
         fm.second_best = second_best != 0;
         rc = fm.pp.init(monos, min_identity, fm.second_best, lr_coef, q.device, q.threads, err);
         if (rc == SD_OK && (q.reserved[1] & SD_FLAG_PROFILE)) rc = fm.pp.enable_profile(err);
+        if (rc == SD_OK && dev_prof) {   // (the host counters: pairs the kernel does not take, jobs of the text-based path)
+            rc = fm.pp.enable_profile(err);
+            if (rc) err = "SD_FLAG_DEVICE_PROFILE (with SD_FLAG_DEVICE_FINAL): " + err;
+        }
         if (rc) { set_err(errbuf, errlen, err); return rc; }
         q.reserved[1] &= ~SD_FLAG_PROFILE;   // (the flag shapes the post-processing only)
     }
@@ -592,6 +649,22 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     s->me.fm = s->fin.get();
     rc = s->me.open(&q, ms, mono_lens, n_mono, s->budget, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    if (dev_prof) {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        try {
+            if (cur != s->me.devs[0]) SD_HIP(hipSetDevice(s->me.devs[0]));
+            SD_HIP(hipStreamCreateWithFlags(&s->prof_st, hipStreamNonBlocking));
+            s->pd.setup(s->fin->pp.interleaved_seqs(), s->fin->pp.own_interleaved(), s->prof_st);
+        } catch (const HipFail& f) {
+            rc = SD_ERR_HIP;
+            set_err(errbuf, errlen, f.msg);
+        }
+        if (cur >= 0 && cur != s->me.devs[0]) (void)hipSetDevice(cur);
+        if (rc) return rc;
+        s->dev_prof = true;
+        s->fin->pd = &s->pd;
+    }
     *out = s.release();
     return SD_OK;
 } catch (const std::bad_alloc&) {
@@ -642,7 +715,7 @@ static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const i
             if (!s->spare.empty()) { job.text = std::move(s->spare.back()); s->spare.pop_back(); }
             else job.text.reset(new DevBuf<uint8_t>);
             job.spare = &s->spare;
-            job.text->alloc((size_t)(span ? hi - lo : (*cum)[n]));
+            job.text->alloc((size_t)(span ? hi - lo : (*cum)[n]) + (s->dev_prof ? 8 : 0));   // (the fold reads whole dwords)
             job.rlen.assign(read_lens, read_lens + n);
             job.text_off.resize(n);
             for (size_t r = 0; r < n; ++r) job.text_off[r] = span ? dv.off[r] - lo : (*cum)[r];
@@ -672,6 +745,41 @@ static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const i
 // A record store for a new job of a device-rows stream: a spare one whose last scatter -- enqueued on that job's caller's
 // stream, which may be far behind -- has completed; else a new one, so that a slow consumer never stalls the pipeline
 // and no buffer a pending scatter reads is ever reallocated.  Beyond eight spares the oldest is waited for instead.
+// The fold time of a workspace's last job, once its fold has completed.
+static void prof_harvest(sd_stream* s, FinalWS& fw) {
+    if (!fw.fold_timed) return;
+    if (hipEventQuery(fw.ev_prof) != hipSuccess) { (void)hipGetLastError(); return; }
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, fw.ev_f0, fw.ev_prof) == hipSuccess) s->prof_ms += ms;
+    else (void)hipGetLastError();
+    fw.fold_timed = false;
+}
+
+// SD_FLAG_DEVICE_PROFILE, a job submitted from host memory: its reads go up once, back to back, into a buffer of the
+// kind a DeviceReads job has (StreamJob::text), through the workspace's pinned staging, on the stream's own stream.
+static void stream_prof_upload(sd_stream* s, StreamJob& job) {
+    const size_t n = (size_t)job.n_reads;
+    FinalWS& fw = *job.fws;
+    job.text_off.assign(n + 1, 0);
+    for (size_t r = 0; r < n; ++r) job.text_off[r + 1] = job.text_off[r] + (int64_t)job.seq[r].size();
+    const size_t total = (size_t)job.text_off[n];
+    job.text_off.resize(n);
+    if (n == 0) return;
+    if (!s->spare.empty()) { job.text = std::move(s->spare.back()); s->spare.pop_back(); }
+    else job.text.reset(new DevBuf<uint8_t>);
+    job.spare = &s->spare;
+    job.text->alloc(total + 8);
+    fw.prof.h_text.alloc(total);
+    uint8_t* stage = fw.prof.h_text.p;
+    sd::parallel_for((int64_t)n, s->p.threads, 1, [&](int64_t r) {
+        std::memcpy(stage + job.text_off[(size_t)r], job.seq[(size_t)r].data(), job.seq[(size_t)r].size());
+    });
+    SD_HIP(hipMemcpyAsync(job.text->p, stage, total, hipMemcpyHostToDevice, s->prof_st));
+    if (!fw.ev_prof) SD_HIP(hipEventCreate(&fw.ev_prof));
+    SD_HIP(hipEventRecord(fw.ev_prof, s->prof_st));
+    fw.prof_recorded = true;
+}
+
 template <class WS>
 static std::unique_ptr<WS> stream_take_ws(std::vector<std::unique_ptr<WS>>& sp) {
     for (size_t i = sp.size(); i-- > 0;)
@@ -711,6 +819,11 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
     if (s->dev_final) {
         job->fws = stream_take_ws(s->fws_spare);
         job->fws_home = &s->fws_spare;
+        if (s->dev_prof) {   // (the workspace is idle: its last fold is through, the text that waited for it is free)
+            prof_harvest(s, *job->fws);
+            if (job->fws->held_text) s->spare.push_back(std::move(job->fws->held_text));
+            job->fws->prof.planned = false;
+        }
     }
     if (dv) {
         // the data's device is current while the job's events and copies are made (the entries all run on it)
@@ -719,7 +832,13 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
         if (cur != dv->device && hipSetDevice(dv->device) != hipSuccess) { (void)hipGetLastError(); set_err(errbuf, errlen, "hipSetDevice failed"); return SD_ERR_HIP; }
         std::string err;
         if (fm) job->seq.resize((size_t)n_reads);
-        const int rd = stream_dev_job(s, *job, *dv, read_lens, err);
+        int rd = stream_dev_job(s, *job, *dv, read_lens, err);
+        // (the folds of this job and of later ones run behind the copy of its text)
+        if (rd == SD_OK && s->dev_prof && n_reads > 0 && hipStreamWaitEvent(s->prof_st, s->ev_src, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            err = "hipStreamWaitEvent failed";
+            rd = SD_ERR_HIP;
+        }
         if (cur >= 0 && cur != dv->device) (void)hipSetDevice(cur);
         if (rd) { set_err(errbuf, errlen, err); return rd; }
         if (fm && fm->ident) job->per = fm->second_best ? (int)fm->pp.interleaved_seqs().size() : 1;
@@ -729,6 +848,21 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
         for (const std::string& q : job->seq) job->own.push_back(q.data());
         job->reads = job->own.data();
         if (fm->ident) job->per = fm->second_best ? (int)fm->pp.interleaved_seqs().size() : 1;
+        if (s->dev_prof) {
+            int cur = -1;
+            (void)hipGetDevice(&cur);
+            const int dev = s->me.devs[0];
+            int ru = SD_OK;
+            try {
+                if (cur != dev) SD_HIP(hipSetDevice(dev));
+                stream_prof_upload(s, *job);
+            } catch (const HipFail& f) {
+                set_err(errbuf, errlen, f.msg);
+                ru = SD_ERR_HIP;
+            }
+            if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+            if (ru) return ru;
+        }
     }
     StreamEntries& me = s->me;
     std::vector<std::pair<size_t, size_t>> batches;
@@ -1027,6 +1161,12 @@ static int final_dev_slow(sd_stream* s, StreamJob& job, std::string& err) {
     if (job.dev)
         for (size_t r = 0; r < nr; ++r) std::string().swap(job.seq[r]);
     if (job.rc) { err = job.err; return job.rc; }
+    if (s->dev_prof)   // (process_rows folded the kept rows on the host: profile_kept)
+        for (size_t i = 0; i < job.fin.n; ++i) {
+            const sd_final_row& f = job.fin.p[i];
+            const int64_t rl = job.dev ? job.rlen[(size_t)f.read] : (int64_t)job.seq[(size_t)f.read].size();
+            if (sd::final_seg_len(f.start, f.end, rl) > 0) ++s->prof_pairs_host;
+        }
     job.fin_off.assign(nr + 1, 0);
     for (size_t i = 0; i < job.fin.n; ++i) ++job.fin_off[(size_t)job.fin.p[i].read + 1];   // rows come in read order
     for (size_t r = 0; r < nr; ++r) job.fin_off[r + 1] += job.fin_off[r];
@@ -1055,6 +1195,58 @@ static int final_dev_count(sd_stream* s, StreamJob& job, int64_t& n, std::string
         n = fw.h_counts.p[0];
     }
     return SD_OK;
+}
+
+// SD_FLAG_DEVICE_PROFILE: the fold of a selected job, enqueued on the stream's own stream once the host has its summary
+// (ev_sel has been waited for), and the pairs the kernel does not take: their list comes down at 16 bytes a pair, the
+// text of those segments alone is fetched (read from job.seq for a job submitted from host memory), and profile_host
+// folds them into the post-processor's counters under the kernel.
+static int stream_prof_fold(sd_stream* s, StreamJob& job, std::string& err) {
+    FinalWS& fw = *job.fws;
+    ProfWS& pw = fw.prof;
+    if (!pw.planned || !job.text) return SD_OK;
+    pw.planned = false;
+    if (!fw.ev_f0) SD_HIP(hipEventCreate(&fw.ev_f0));
+    if (!fw.ev_prof) SD_HIP(hipEventCreate(&fw.ev_prof));
+    prof_harvest(s, fw);
+    SD_HIP(hipEventRecord(fw.ev_f0, s->prof_st));
+    const int64_t nd = prof_fold(pw, s->pd, s->prof_st, job.text->p);
+    SD_HIP(hipEventRecord(fw.ev_prof, s->prof_st));
+    fw.prof_recorded = true;
+    fw.fold_timed = nd > 0;
+    s->prof_pairs_dev += nd;
+    const int64_t nh = pw.h_sum.p[s->pd.M + 1];
+    if (nh <= 0) return SD_OK;
+    // (the list was written ahead of ev_sel; the text of a DeviceReads job was read by its batches: both are complete)
+    if (!s->slow_st) SD_HIP(hipStreamCreateWithFlags(&s->slow_st, hipStreamNonBlocking));
+    pw.h_hlist.alloc((size_t)nh);
+    SD_HIP(hipMemcpyAsync(pw.h_hlist.p, pw.hlist.p, (size_t)nh * sizeof(sd::FProfHostPair), hipMemcpyDeviceToHost, s->slow_st));
+    SD_HIP(hipStreamSynchronize(s->slow_st));
+    const sd::FProfHostPair* hp = pw.h_hlist.p;
+    std::vector<const char*> q((size_t)nh);
+    std::vector<int32_t> ql((size_t)nh), pil((size_t)nh);
+    std::vector<char> fetched;
+    if (job.dev) {
+        size_t bytes = 0;
+        for (int64_t x = 0; x < nh; ++x) bytes += (size_t)hp[x].len;
+        fetched.resize(std::max<size_t>(bytes, 1));
+        size_t at = 0;
+        for (int64_t x = 0; x < nh; ++x) {
+            SD_HIP(hipMemcpyAsync(fetched.data() + at, job.text->p + hp[x].start, (size_t)hp[x].len, hipMemcpyDeviceToHost, s->slow_st));
+            q[(size_t)x] = fetched.data() + at;
+            at += (size_t)hp[x].len;
+        }
+        SD_HIP(hipStreamSynchronize(s->slow_st));
+        s->prof_text_to_host += (int64_t)bytes;
+    } else {
+        for (int64_t x = 0; x < nh; ++x) {
+            const size_t r = (size_t)(std::upper_bound(job.text_off.begin(), job.text_off.end(), hp[x].start) - job.text_off.begin()) - 1;
+            q[(size_t)x] = job.seq[r].data() + (hp[x].start - job.text_off[r]);
+        }
+    }
+    for (int64_t x = 0; x < nh; ++x) { ql[(size_t)x] = hp[x].len; pil[(size_t)x] = hp[x].il; }
+    s->prof_pairs_host += nh;
+    return s->fin->pp.profile_pairs(q.data(), ql.data(), pil.data(), nh, err);
 }
 
 int sd_stream_peek_final_dev(sd_stream* s, int32_t* n_reads, int64_t* n_rows, int32_t* n_keys, char* errbuf, size_t errlen) {
@@ -1161,6 +1353,10 @@ int sd_stream_collect_final_dev(sd_stream* s, sd_final_row* d_rows, int64_t cap_
                 if (!ws.ev_free) SD_HIP(hipEventCreateWithFlags(&ws.ev_free, hipEventDisableTiming));
                 SD_HIP(hipEventRecord(ws.ev_free, user));
                 ws.free_recorded = true;
+                if (s->dev_prof) {
+                    rc = stream_prof_fold(s, job, err);
+                    if (rc) set_err(errbuf, errlen, err);
+                }
             }
             if (rc == SD_OK) s->fin->kept += n;
         }
@@ -1185,17 +1381,135 @@ int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys
     return SD_OK;
 }
 
+// SD_FLAG_DEVICE_PROFILE: waits for the folds enqueued so far and brings the fold's failure count (and, with dc given,
+// the counters) to the host on the stream's own stream; reset zeroes the device counters behind the copy.  The stream's
+// device is current.
+static int stream_prof_down(sd_stream* s, std::vector<unsigned long long>* dc, bool reset) {
+    const size_t total = (size_t)s->pd.total;
+    std::vector<unsigned long long> tail(8, 0);
+    if (dc) {
+        dc->assign(total + 8, 0);
+        SD_HIP(hipMemcpyAsync(dc->data(), s->pd.counts.p, (total + 8) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->prof_st));
+    } else {
+        SD_HIP(hipMemcpyAsync(tail.data(), s->pd.counts.p + total, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->prof_st));
+    }
+    if (reset) SD_HIP(hipMemsetAsync(s->pd.counts.p, 0, total * sizeof(unsigned long long), s->prof_st));
+    SD_HIP(hipStreamSynchronize(s->prof_st));
+    int fails = 0;
+    std::memcpy(&fails, dc ? dc->data() + total : tail.data(), sizeof fails);
+    return fails ? SD_ERR_INTERNAL : SD_OK;   // cannot happen: the checkpoints are sized by the longest segment
+}
+
 int sd_stream_profile(sd_stream* s, int32_t reset, int32_t* n_monomers, int64_t* n_counts, int64_t* text_bytes,
                       char* text, uint64_t* counts) {
     if (!s || !s->fin || !s->fin->pp.profiling()) return SD_ERR_PARAM;
     sd::PostProcessor& pp = s->fin->pp;
-    const std::vector<uint64_t> v = pp.profile(reset && counts);
+    std::vector<unsigned long long> dc;
+    if (s->dev_prof && counts) {   // device counters + host counters
+        const int dev = s->me.devs[0];
+        int cur = -1, rc = SD_OK;
+        (void)hipGetDevice(&cur);
+        try {
+            if (cur != dev) SD_HIP(hipSetDevice(dev));
+            rc = stream_prof_down(s, &dc, reset != 0);
+        } catch (const HipFail&) {
+            rc = SD_ERR_HIP;
+        } catch (const std::bad_alloc&) {
+            rc = SD_ERR_INTERNAL;
+        }
+        if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+        if (rc) return rc;
+    }
+    std::vector<uint64_t> v = pp.profile(reset && counts);
+    for (size_t i = 0; i < v.size() && i < dc.size(); ++i) v[i] += dc[i];
     const std::string t = pp.profile_text();
     if (n_monomers) *n_monomers = (int32_t)(pp.interleaved_seqs().size() / 2);
     if (n_counts) *n_counts = (int64_t)v.size();
     if (text_bytes) *text_bytes = (int64_t)t.size() + 1;
     if (text) std::memcpy(text, t.c_str(), t.size() + 1);
     if (counts) std::memcpy(counts, v.data(), sizeof(uint64_t) * v.size());
+    return SD_OK;
+}
+
+int sd_stream_profile_dev(sd_stream* s, int32_t reset, uint64_t* d_counts, int64_t cap_counts, void* hip_stream,
+                          int64_t* n_counts, char* errbuf, size_t errlen) {
+    if (!s) return SD_ERR_PARAM;
+    if (n_counts) *n_counts = 0;
+    if (!s->dev_prof) { set_err(errbuf, errlen, "sd_stream_profile_dev on a stream made without SD_FLAG_DEVICE_PROFILE"); return SD_ERR_PARAM; }
+    const int64_t total = s->pd.total;
+    if (n_counts) *n_counts = total;
+    if (!d_counts || cap_counts < total) {
+        set_err(errbuf, errlen, "sd_stream_profile_dev: the profile has " + std::to_string(total) + " counters, the buffer room for " +
+                                    std::to_string(std::max<int64_t>(cap_counts, 0)));
+        return SD_ERR_PARAM;
+    }
+    const int dev = s->me.devs[0];
+    {
+        std::string err;
+        int at = dev;
+        int rc = device_pointer(d_counts, at, err);
+        if (rc == SD_OK && at != dev) {
+            err = "the count buffer lies in the memory of device " + std::to_string(at) + ", the stream runs on device " + std::to_string(dev);
+            rc = SD_ERR_UNSUPPORTED;
+        }
+        if (rc) {
+            set_err(errbuf, errlen, rc == SD_ERR_UNSUPPORTED ? err : "sd_stream_profile_dev: the count buffer is not in device memory");
+            return rc;
+        }
+    }
+    int cur = -1, rc = SD_OK;
+    (void)hipGetDevice(&cur);
+    try {
+        if (cur != dev) SD_HIP(hipSetDevice(dev));
+        hipStream_t user = reinterpret_cast<hipStream_t>(hip_stream);
+        rc = stream_prof_down(s, nullptr, false);   // (the folds so far are through)
+        if (rc) set_err(errbuf, errlen, "a profile fold ran out of checkpoints");
+        if (rc == SD_OK) {
+            const size_t nb = (size_t)total * sizeof(unsigned long long);
+            SD_HIP(hipMemcpyAsync(d_counts, s->pd.counts.p, nb, hipMemcpyDeviceToDevice, user));
+            // the host's counters (pairs the kernel does not take, jobs of the text-based path), added on the caller's stream
+            const std::vector<uint64_t> hv = s->fin->pp.profile(reset != 0);
+            bool any = false;
+            for (uint64_t x : hv) any = any || x != 0;
+            if (any) {
+                if (s->up_recorded) { SD_HIP(hipEventSynchronize(s->ev_up)); s->up_recorded = false; }
+                s->h_up.alloc((size_t)total);
+                s->d_up.alloc((size_t)total);
+                for (int64_t i = 0; i < total; ++i) s->h_up.p[i] = hv[(size_t)i];
+                SD_HIP(hipMemcpyAsync(s->d_up.p, s->h_up.p, nb, hipMemcpyHostToDevice, user));
+                prof_add(user, reinterpret_cast<unsigned long long*>(d_counts), s->d_up.p, total);
+                if (!s->ev_up) SD_HIP(hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming));
+                SD_HIP(hipEventRecord(s->ev_up, user));
+                s->up_recorded = true;
+            }
+            // later folds, and the zeroing, follow the caller's copy on the stream's own stream
+            if (!s->ev_pd) SD_HIP(hipEventCreateWithFlags(&s->ev_pd, hipEventDisableTiming));
+            SD_HIP(hipEventRecord(s->ev_pd, user));
+            SD_HIP(hipStreamWaitEvent(s->prof_st, s->ev_pd, 0));
+            if (reset) SD_HIP(hipMemsetAsync(s->pd.counts.p, 0, nb, s->prof_st));
+        }
+    } catch (const HipFail& f) {
+        set_err(errbuf, errlen, f.msg);
+        rc = SD_ERR_HIP;
+    } catch (const std::bad_alloc&) {
+        set_err(errbuf, errlen, "out of host memory");
+        rc = SD_ERR_INTERNAL;
+    }
+    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+    return rc;
+}
+
+int sd_stream_profile_stats(sd_stream* s, double out[4]) {
+    if (!s || !out) return SD_ERR_PARAM;
+    if (s->dev_prof) {   // (the folds that have completed; a fold in flight is counted by a later call)
+        for (std::unique_ptr<FinalWS>& f : s->fws_spare) prof_harvest(s, *f);
+        for (std::unique_ptr<StreamJob>& j : s->jobs)
+            if (j->fws) prof_harvest(s, *j->fws);
+    }
+    out[0] = (double)s->prof_pairs_dev;
+    out[1] = (double)s->prof_pairs_host;
+    out[2] = (double)s->prof_text_to_host;
+    out[3] = s->prof_ms;
     return SD_OK;
 }
 

@@ -49,6 +49,7 @@ EXPORTS = [
     "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev", "sd_engine_filter_result",
     "sd_stream_peek_dev", "sd_stream_collect_dev", "sd_engine_rows_dev", "sd_seam_merge_dev", "sd_seam_pieces_selftest",
     "sd_stream_peek_final_dev", "sd_stream_collect_final_dev", "sd_final_select_dev", "sd_final_select_host",
+    "sd_stream_profile_dev", "sd_stream_profile_stats", "sd_final_profile_dev", "sd_final_profile_host",
 ]
 
 
@@ -233,6 +234,13 @@ def load():
     out = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
     L.sd_final_select_host.argtypes = sel + out
     L.sd_final_select_dev.argtypes = sel + [C.c_int32, C.c_void_p] + out
+    L.sd_stream_profile_dev.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, P(C.c_int64), C.c_char_p,
+                                        C.c_size_t]
+    L.sd_stream_profile_stats.argtypes = [C.c_void_p, P(C.c_double)]
+    prof = [C.c_char_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_char_p), P(C.c_int32), C.c_int32,
+            C.c_int32, C.c_int32, C.c_void_p, P(C.c_int64)]
+    L.sd_final_profile_dev.argtypes = prof
+    L.sd_final_profile_host.argtypes = prof
     _lib = L
     return L
 
@@ -255,6 +263,7 @@ FLAG_NO_U16 = 128     # narrow layout: fp16 / int16 cells as in rounds 1-5 inste
 FLAG_PROFILE = 512    # per-monomer column profiles of the kept rows (run_files(profile=True), Stream(profile=True))
 FLAG_DEVICE_ROWS = 1024   # Stream(device_rows=True): the rows are assembled on the device and stay there
 FLAG_DEVICE_FINAL = 2048  # Stream(final=True, device_final=True): the final rows are selected on the device and stay there
+FLAG_DEVICE_PROFILE = 4096  # Stream(final=True, device_final=True, device_profile=True): their column profiles are folded there too
 
 
 def make_params(scoring=(-1, -1, -1, 1), part_size=5000, overlap=500, ed_thr=-1, threads=1,
@@ -783,6 +792,18 @@ class DeviceFinalRows(namedtuple("DeviceFinalRows", "rows row_off alt n_rows")):
         return FinalRows(r, self.row_off.cpu().numpy(), None if self.alt is None else self.alt.cpu().numpy())
 
 
+class DeviceProfile(namedtuple("DeviceProfile", "counts offsets names seqs")):
+    """A profile that stays in device memory (Stream.profile_device): counts = a flat int64 torch tensor on the stream's
+    device, monomer m's [L + 1, 12] block at counts[offsets[m]:offsets[m + 1]] (formats.PROFILE_COLUMNS; offsets, names
+    and seqs are host lists)."""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> formats.Profile, what Stream.profile() returns for the same jobs."""
+        from . import formats
+        return formats.profile_from_counts(self.names, self.seqs, self.counts.cpu().numpy())
+
+
 def _torch_stream(torch, dev, stream):
     """stream=None: the current stream of the device (DeviceReads' convention); an int: that hipStream_t; else a
     torch stream."""
@@ -905,12 +926,18 @@ class Stream:
     identity words cannot decide (a block of ~19.6 kb and more, flags=FLAG_NO_STREAM_IDENT) are finished by the host's
     text-based path: the same rows, slowly (stats()["fallback_blocks"]).  Not with profile, device_rows or several devices.
 
+    device_profile=True (with device_final, names unique): the column profiles of the kept rows are folded on the device
+    from the job's text in HBM (csrc/sd_final_prof_dev.hip), behind collect_final_device(): profile() gives their sum as
+    Stream(profile=True) does, profile_device() leaves it on the device.  Pairs the fold kernel does not take and jobs of
+    the text-based path are folded by the host (stats()["profile_pairs_host"]).
+
     devices (a list of ordinals, repeats allowed; `device` is then ignored): one pipeline per entry in this process
     (sd_stream_create_devices / sd_stream_create_final_devices), each driven by a thread of its own; every job is cut
     into at least two batches per entry and the rows are those of the plain stream.  [d] is the plain stream on d."""
 
     def __init__(self, mono_seqs, sub_batches=1, final=False, mono_names=None, second_best=False, min_identity=0,
-                 lr_coef=None, devices=None, profile=False, device_rows=False, device_final=False, **kw):
+                 lr_coef=None, devices=None, profile=False, device_rows=False, device_final=False, device_profile=False,
+                 **kw):
         self.L = load()
         if profile:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_PROFILE
@@ -918,6 +945,8 @@ class Stream:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_ROWS
         if device_final:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_FINAL
+        if device_profile:
+            kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_PROFILE
         self.device_rows = bool(device_rows)
         self.device_final = bool(device_final)
         self.params = make_params(**kw)
@@ -982,8 +1011,34 @@ class Stream:
 
     def profile(self, reset=False):
         """Stream(final=True, profile=True): the formats.Profile of the rows of every job processed so far (summed);
-        reset=True zeroes the sums after the copy."""
+        reset=True zeroes the sums after the copy.  With device_profile=True: of every job collected so far, the device's
+        counters and the host's added."""
         return _profile_from(self.L.sd_stream_profile, self.h, 1 if reset else 0)
+
+    def profile_device(self, reset=False, stream=None):
+        """Stream(device_profile=True): the sums of profile() as a DeviceProfile, placed on the stream's device by
+        sd_stream_profile_dev and ordered on `stream` (a torch stream or a hipStream_t; None: the current stream of
+        that device): work enqueued there afterwards sees them."""
+        import torch
+        nm, nc, tb = C.c_int32(), C.c_int64(), C.c_int64()
+        if self.L.sd_stream_profile(self.h, 0, C.byref(nm), C.byref(nc), C.byref(tb), None, None) != SD_OK:
+            raise SdError(SD_ERR_PARAM, "no profile: the stream was made without device_profile")
+        text = C.create_string_buffer(max(int(tb.value), 1))
+        self.L.sd_stream_profile(self.h, 0, C.byref(nm), C.byref(nc), C.byref(tb), text, None)   # (names and sequences only)
+        lines = [x.split("\t") for x in text.value.decode().split("\n")[:nm.value]]
+        names, seqs = [x[0] for x in lines], [x[1] for x in lines]
+        offsets = [0]
+        for s in seqs:
+            offsets.append(offsets[-1] + (len(s) + 1) * 12)
+        devs = self.devices if self.devices is not None else [self.params.device]
+        dev = torch.device("cuda", devs[0])
+        st = _torch_stream(torch, dev, stream)
+        with torch.cuda.stream(st):
+            counts = torch.empty(offsets[-1], dtype=torch.int64, device=dev)
+        n = C.c_int64()
+        self._check(self.L.sd_stream_profile_dev(self.h, 1 if reset else 0, C.c_void_p(counts.data_ptr()), offsets[-1],
+                                                 C.c_void_p(st.cuda_stream), C.byref(n), self._err, 4096))
+        return DeviceProfile(counts, offsets, names, seqs)
 
     def keys(self):
         """Final mode: the distinct monomer names in the library's key order (what FinalRows' indices refer to)."""
@@ -1127,6 +1182,9 @@ class Stream:
         f = (C.c_double * 4)()
         self.L.sd_stream_final_stats(self.h, f)
         out.update({"ident_ms": f[0], "ident_pairs": int(f[1]), "fallback_blocks": int(f[2]), "final_rows": int(f[3])})
+        self.L.sd_stream_profile_stats(self.h, f)
+        out.update({"profile_pairs_device": int(f[0]), "profile_pairs_host": int(f[1]), "profile_text_to_host": int(f[2]),
+                    "profile_ms": f[3]})
         return out
 
     def info(self):
@@ -1349,6 +1407,45 @@ def final_select_device(mono_names, mono_seqs, rows, row_off, widx, words, hword
     out = h_out[:k * 80].copy().view(final_dtype())
     alt = None if h_alt is None else h_alt[:k * nk * 8].copy().view(np.float64).reshape(k, nk)
     return FinalRows(out, h_off[:len(o) * 8].copy().view(np.int64), alt), int(und.value), intact
+
+
+def _final_profile(fn, name, text, read_off, rows, row_off, keep, templates, device, threads, guard):
+    import numpy as np
+    from . import formats
+    tb = _b(text)
+    ro = np.ascontiguousarray(read_off, dtype=np.int64)
+    r, o = _recs_array(rows, row_off)
+    k = np.ascontiguousarray(keep, dtype=np.uint8)
+    if len(ro) != len(o) or len(k) != len(r) or (len(ro) and int(ro[-1]) > len(tb)):
+        raise SdError(SD_ERR_PARAM, name + ": one keep flag per row, n_reads + 1 offsets of reads and of rows, inside the text")
+    ts = [_b(t) for t in templates]
+    tl = (C.c_int32 * max(len(ts), 1))(*[len(t) for t in ts])
+    total = sum(len(t) + 1 for t in ts) * formats.PROFILE_NCOLS
+    counts = np.full(total + guard, 0x5a5a5a5a5a5a5a5a, dtype=np.uint64)
+    pairs = (C.c_int64 * 2)()
+    rc = fn(tb, ro.ctypes.data, len(ro) - 1, r.ctypes.data, o.ctypes.data, k.ctypes.data, _strs(ts), tl, len(ts), int(device),
+            int(threads), counts.ctypes.data, pairs)
+    if rc != SD_OK:
+        raise SdError(rc, name)
+    intact = bool((counts[total:] == 0x5a5a5a5a5a5a5a5a).all())
+    return formats.split_counts([len(t) for t in ts], counts[:total].astype(np.int64)), (int(pairs[0]), int(pairs[1])), intact
+
+
+def final_profile_host(text, read_off, rows, row_off, keep, templates, threads=1):
+    """The plan of a device-final stream's profiles on the host (sd_final_profile_host): text = the reads back to back,
+    read r = text[read_off[r]:read_off[r + 1]]; rows [n, 4] int32 (tmpl in the DP's order: monomer t, T + t = its
+    reverse complement; start, end in read coordinates), row_off n_reads + 1 offsets, keep one flag per row; templates =
+    the FORWARD monomers.  -> (counts as profile_segments gives them, (pairs of the fold kernel, pairs of the host))."""
+    c, pairs, _ = _final_profile(load().sd_final_profile_host, "sd_final_profile_host", text, read_off, rows, row_off, keep,
+                                 templates, 0, threads, 0)
+    return c, pairs
+
+
+def final_profile_device(text, read_off, rows, row_off, keep, templates, device=0, threads=1):
+    """The plan, group and fold kernels alone (sd_final_profile_dev), arguments as final_profile_host.  The count buffer
+    carries guard words behind it: -> (counts, pairs, intact)."""
+    return _final_profile(load().sd_final_profile_dev, "sd_final_profile_dev", text, read_off, rows, row_off, keep, templates,
+                          device, threads, 16)
 
 
 def fasta_load(path):
