@@ -57,7 +57,7 @@ struct FinalWS {
     // SD_FLAG_DEVICE_PROFILE: the plan of the job's pairs (sd_final_prof_ws.hpp).  The fold runs on the stream's own
     // stream after collect has returned and reads prof and the job's text; the upload of a host job's text runs there
     // too.  ev_prof is recorded behind either (ev_f0 before a fold: its time), and the rule of ev_free holds for it:
-    // the host has seen it before this workspace is reused or released.  The job's text (StreamJob::text) waits here
+    // the host has seen it before this workspace is reused or released.  The job's text (StreamJob::din.text) waits here
     // meanwhile, and goes back to the stream's spare list with the workspace's next job.
     ProfWS prof;
     hipEvent_t ev_f0 = nullptr, ev_prof = nullptr;

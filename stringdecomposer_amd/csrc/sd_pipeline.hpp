@@ -1,7 +1,7 @@
 // sd_pipeline.hpp -- internal to libsd_hip.so: the engine structure, the device / pinned buffer pools, the batch pipeline and
 // the per-read row assembly, shared by the units that drive the device:
 //   sd_engine.hip     engines (create / load / run / fetch), pipeline cache, sd_decompose*, chunk-range calls
-//   sd_stream.hip     sd_stream_*: sequences in host memory -> rows in host memory
+//   sd_stream.hip     sd_stream_*: sequences in host or device memory -> rows in host or device memory
 //   sd_run_files.hip  sd_run_files*: FASTA files -> the three TSV files
 // Split from sd_engine.hip in round 6 (it was one 3 900-line unit); the C-ABI is unchanged.
 #pragma once
@@ -28,6 +28,28 @@ struct HipFail {
         if (_e != hipSuccess)                                                               \
             throw HipFail{std::string(#call) + ": " + hipGetErrorString(_e)};               \
     } while (0)
+
+// The calling thread's current device is `dev` for the life of the guard.  A thread that is already on `dev` makes no
+// hipSetDevice call, and the device it came from is restored only if the guard switched.  A switch that fails throws
+// HipFail (SD_ERR_HIP where it is caught).
+struct DeviceScope {
+    int prev = -1;
+    bool switched = false;
+    explicit DeviceScope(int dev) {
+        (void)hipGetDevice(&prev);
+        if (prev == dev) return;
+        SD_HIP(hipSetDevice(dev));
+        switched = prev >= 0;
+    }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+    ~DeviceScope() { if (switched) (void)hipSetDevice(prev); }
+};
+
+// an event that is created when it is first needed
+inline void ensure_event(hipEvent_t& ev, unsigned flags = hipEventDefault) {
+    if (!ev) SD_HIP(hipEventCreateWithFlags(&ev, flags));
+}
 
 // Process-wide cache of large device buffers.  hipMalloc / hipFree of the multi-GB workspaces
 // (checkpoints: ~280 B per chunk row) cost anything from 10 ms to more than a second per call, so
@@ -62,14 +84,16 @@ struct DevPool {
     }
     void release_all() {
         std::lock_guard<std::mutex> g(m);
-        int cur = 0;
-        (void)hipGetDevice(&cur);
         for (const Block& b : blocks) {
-            (void)hipSetDevice(b.dev);
-            (void)hipFree(b.p);
+            try {
+                DeviceScope on(b.dev);
+                (void)hipFree(b.p);
+            } catch (const HipFail&) {   // (no switch: freed from the device the thread is on)
+                (void)hipGetLastError();
+                (void)hipFree(b.p);
+            }
         }
         blocks.clear();
-        (void)hipSetDevice(cur);
     }
 };
 extern DevPool g_pool;                    // (defined in sd_engine.hip)
@@ -299,6 +323,21 @@ inline int device_pointer(const void* p, int& dev, std::string& err) {
     }
     dev = at.device;
     return SD_OK;
+}
+
+// Is the caller's buffer p (the `what` buffer of the call `who`) device memory, and of the device `dev` the stream runs
+// on?  SD_ERR_PARAM for anything that is not device memory, SD_ERR_UNSUPPORTED for another device's, with the message.
+inline int buffer_on_device(const void* p, int dev, const char* who, const char* what, char* errbuf, size_t errlen) {
+    std::string err;
+    int at = dev;
+    if (device_pointer(p, at, err)) {
+        set_err(errbuf, errlen, std::string(who) + ": the " + what + " buffer is not in device memory");
+        return SD_ERR_PARAM;
+    }
+    if (at == dev) return SD_OK;
+    set_err(errbuf, errlen, std::string("the ") + what + " buffer lies in the memory of device " + std::to_string(at) +
+                                ", the stream runs on device " + std::to_string(dev));
+    return SD_ERR_UNSUPPORTED;
 }
 
 }  // namespace sdi

@@ -1,8 +1,15 @@
-// sd_stream.hip -- sd_stream_*: the streaming form of the job (sequences in host memory -> rows in host memory,
-// AlignReadsSet of main.cpp:67-122 without the text), jobs pipelined through the device in sub-batches; in final mode
-// (sd_stream_create_final) the rows of final_decomposition.tsv / _alt.tsv as typed rows instead of the raw ones; with a
-// device list (sd_stream_create_devices, sd_stream_create_final_devices) one pipeline per entry, several of them each
-// driven by a thread of its own.
+// sd_stream.hip -- sd_stream_*: the streaming form of the job (sequences -> rows, AlignReadsSet of main.cpp:67-122
+// without the text), jobs pipelined through the device in sub-batches; in final mode (sd_stream_create_final) the rows
+// of final_decomposition.tsv / _alt.tsv as typed rows instead of the raw ones; with a device list
+// (sd_stream_create_devices, sd_stream_create_final_devices) one pipeline per entry, several of them each driven by a
+// thread of its own.  The reads of a job lie in host memory (sd_stream_submit) or in device memory
+// (sd_stream_submit_dev).  Where its rows end up is the stream's mode (StreamMode): in host memory (sd_stream_collect,
+// _collect_final), or, on one device, in the caller's device buffers -- the raw rows assembled there
+// (SD_FLAG_DEVICE_ROWS: _peek_dev, _collect_dev), the final rows selected there (SD_FLAG_DEVICE_FINAL: _peek_final_dev,
+// _collect_final_dev) and with SD_FLAG_DEVICE_PROFILE their column profiles folded there (_profile_dev).  The six
+// collect and peek entries share one frame (on_oldest_job).
+#include <optional>
+
 #include "sd_devices.hpp"
 #include "sd_final_ws.hpp"
 
@@ -27,6 +34,22 @@ struct FinalMode {
     ProfDev* pd = nullptr;
 };
 
+// Something on loan from a list of spares (a stream's): it goes back to the list with the lease.
+template <class T>
+struct Lease {
+    std::unique_ptr<T> p;
+    std::vector<std::unique_ptr<T>>* home = nullptr;
+    Lease() = default;
+    Lease(const Lease&) = delete;
+    Lease& operator=(const Lease&) = delete;
+    void take(std::unique_ptr<T> q, std::vector<std::unique_ptr<T>>& from) { p = std::move(q); home = &from; }
+    ~Lease() { if (p) home->push_back(std::move(p)); }
+    T* get() const { return p.get(); }
+    T* operator->() const { return p.get(); }
+    T& operator*() const { return *p; }
+    explicit operator bool() const { return (bool)p; }
+};
+
 // A submitted job: its rows as they are assembled and, in final mode, its own copy of the reads and its kept rows.
 struct StreamJob : RowJob {
     std::vector<std::string> seq;
@@ -43,151 +66,197 @@ struct StreamJob : RowJob {
     // hand to the device packer with `ds`; gpos = per chunk of the table, where it starts in the job (DevSrc::gpos).  In
     // final mode the packers read the job's own device copy of the reads (text, read r at text_off[r], made on the
     // caller's stream), from which the post-processor's fallback fetches the reads it asks for into seq; rlen = the
-    // read lengths.  The copy goes back to the stream's spare list with the job.
-    bool dev = false;
-    DevSrc ds;
-    std::vector<int64_t> gpos, rlen, text_off;
-    std::unique_ptr<DevBuf<uint8_t>> text;
-    std::vector<std::unique_ptr<DevBuf<uint8_t>>>* spare = nullptr;
+    // read lengths.  The copy goes back to the stream's spare list with the job.  (A device-profile job submitted from
+    // host memory has text and text_off too: stream_prof_upload.)
+    struct DevInput {
+        bool dev = false;
+        DevSrc ds;
+        std::vector<int64_t> gpos, rlen, text_off;
+        Lease<DevBuf<uint8_t>> text;
+    } din;
     // A job of a device-rows stream (SD_FLAG_DEVICE_ROWS): ws = its record store and merge workspace (RowsWS), taken
     // from and given back to the stream's list.  Layout of the store: the compact records of the job's chunks in
     // chunk-table order, back to back across its batches, already in read coordinates and the caller's score scale;
     // appended = records in it, rec_at[c] = first record of chunk c (from the batches' host-side record offsets).
     // rows_batch appends a batch and, behind the last one, enqueues the merge.
-    std::unique_ptr<RowsWS> ws;
-    std::vector<std::unique_ptr<RowsWS>>* ws_home = nullptr;
-    std::vector<int64_t> rec_at;
-    int64_t appended = 0;
-    bool ws_begun = false, assembled = false;
+    struct Store {
+        Lease<RowsWS> ws;
+        std::vector<int64_t> rec_at;
+        int64_t appended = 0;
+        bool ws_begun = false, assembled = false;
+    } store;
     // A job of a device-final stream (SD_FLAG_DEVICE_FINAL) has a record store too, and fws: the identity words of the
     // store's records and the selection's workspace.  selected: the selection kernels were enqueued behind the merge.
     // A job that takes the text-based path (final_dev_slow) leaves its rows in fin / alt / fin_off on the host.
-    std::unique_ptr<FinalWS> fws;
-    std::vector<std::unique_ptr<FinalWS>>* fws_home = nullptr;
-    bool selected = false, slow_done = false;
-    std::vector<int64_t> fin_off;
+    struct DevFinal {
+        Lease<FinalWS> fws;
+        bool selected = false, slow_done = false;
+        std::vector<int64_t> fin_off;
+    } dfin;
+    // The one rule of order among the three leases (which go home with the members above, last to first): a fold or an
+    // upload that is still recorded on the text reads it, so the text waits in the final workspace, under the
+    // workspace's event, before that workspace goes home.
     ~StreamJob() {
-        // (a fold or an upload still reads the text: it waits in the workspace, under the workspace's event)
-        if (text && spare && fws && fws->prof_recorded) fws->held_text = std::move(text);
-        if (text && spare) spare->push_back(std::move(text));
-        if (fws && fws_home) fws_home->push_back(std::move(fws));
-        if (ws && ws_home) ws_home->push_back(std::move(ws));
+        if (din.text && dfin.fws && dfin.fws->prof_recorded) dfin.fws->held_text = std::move(din.text.p);
     }
 };
+
+// read r's text, from the job's device copy of the reads into job.seq[r]
+static hipError_t fetch_read_text(StreamJob& job, size_t r) {
+    const StreamJob::DevInput& in = job.din;
+    job.seq[r].resize((size_t)in.rlen[r]);
+    return hipMemcpy(&job.seq[r][0], in.text->p + in.text_off[r], (size_t)in.rlen[r], hipMemcpyDeviceToHost);
+}
 
 // Device rows: the records of the batch [c0, c1) of job j, still in engine e's buffers after fetch_begin (total of them,
 // offsets in e->h_roff), are appended to the job's store on `st`; behind the job's last batch the merge is enqueued.
 // A device-final job (fm given) also keeps the batch's identity words at the records' indices -- zeroes, which decide
-// nothing, for a batch whose identity outputs are not valid -- and behind the merge enqueues the selection.
-static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st, size_t c0, size_t c1, char* eb, size_t eblen,
-                      FinalMode* fm = nullptr) {
-    RowsWS& ws = *j.ws;
-    FinalWS* fw = j.fws.get();
+// nothing, for a batch whose identity outputs are not valid -- and behind the merge enqueues the selection, a
+// device-profile job behind that the plan of its pairs.  The steps, in the order rows_batch takes them:
+struct RowsBatch {
+    StreamJob& j;
+    sd_engine* e;
+    const int64_t total;
+    hipStream_t st;
+    const size_t c0, c1;
+    FinalMode* fm;
+    RowsWS& ws = *j.store.ws;
+    FinalWS* fw = j.dfin.fws.get();
     const size_t per = fw ? (size_t)j.per : 0;   // identity words kept per record (0: a job without in-stream identities)
     const bool homo = fm && fm->second_best;
     const size_t C = c1 - c0, CJ = j.table.size();
-    try {
-        if (!j.ws_begun) {
-            j.ws_begun = true;
-            // The workspace's last user: its scatter ran on ITS caller's stream and reads these buffers; every alloc
-            // below may give a block up to the pool, so the HOST has to have seen that scatter end (stream_take_ws
-            // hands out idle workspaces: this returns at once).  A job that was dropped never settled.
-            ws.wait_idle();
-            if (fw) fw->wait_idle();
-            if (!ws.settled || (fw && !fw->settled)) { SD_HIP(hipStreamSynchronize(st)); ws.settled = true; if (fw) fw->settled = true; }
-            ws.h_add.alloc(CJ);
-            for (size_t c = 0; c < CJ; ++c) ws.h_add.p[c] = (int32_t)j.table[c].off;   // (main.cpp:109-111)
-            ws.add.alloc(CJ);
-            ws.settled = false;
-            SD_HIP(hipMemcpyAsync(ws.add.p, ws.h_add.p, CJ * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            j.rec_at.assign(1, 0);
-            j.rec_at.reserve(CJ + 1);
+
+    // The first batch of the job.  The workspace's last user: its scatter ran on ITS caller's stream and reads these
+    // buffers; every alloc below may give a block up to the pool, so the HOST has to have seen that scatter end
+    // (stream_take_ws hands out idle workspaces: this returns at once).  A job that was dropped never settled.
+    void begin_store() {
+        j.store.ws_begun = true;
+        ws.wait_idle();
+        bool settled = ws.settled;
+        if (fw) { fw->wait_idle(); settled = settled && fw->settled; }
+        if (!settled) { SD_HIP(hipStreamSynchronize(st)); ws.settled = true; if (fw) fw->settled = true; }
+        ws.h_add.alloc(CJ);
+        for (size_t c = 0; c < CJ; ++c) ws.h_add.p[c] = (int32_t)j.table[c].off;   // (main.cpp:109-111)
+        ws.add.alloc(CJ);
+        ws.settled = false;
+        SD_HIP(hipMemcpyAsync(ws.add.p, ws.h_add.p, CJ * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        j.store.rec_at.assign(1, 0);
+        j.store.rec_at.reserve(CJ + 1);
+    }
+
+    // Room for the batch, records and words together.
+    void reserve() {
+        const size_t need = (size_t)(j.store.appended + total);
+        if (j.store.appended == 0) size_first(need);
+        else if (need > ws.recs.cap) regrow(need);
+    }
+    // the first batch sizes the store for the whole job by its share of the chunks, with a quarter to spare (short
+    // chunks first: the store grows below); the words' room follows the store's (a store kept from an earlier job may
+    // be larger)
+    void size_first(size_t need) {
+        if (need > ws.recs.cap) {
+            const double share = C < CJ ? 1.25 * (double)CJ / (double)std::max<size_t>(C, 1) : 1.0;
+            ws.recs.alloc((size_t)((double)need * share) + (C < CJ ? 64 : 0));
         }
-        const int64_t need = j.appended + total;
-        if ((size_t)need > ws.recs.cap) {
-            if (j.appended == 0) {
-                // the first batch sizes the store for the whole job by its share of the chunks, with a quarter to spare
-                // (short chunks first: the store grows below)
-                const double share = C < CJ ? 1.25 * (double)CJ / (double)std::max<size_t>(C, 1) : 1.0;
-                ws.recs.alloc((size_t)((double)need * share) + (C < CJ ? 64 : 0));
-            } else {
-                // a later batch outgrew it: a larger block, the records so far copied over; the old block leaves with
-                // nothing in flight on it
-                DevBuf<sd::DevRec> grown;
-                grown.alloc(std::max<size_t>((size_t)need, 2 * ws.recs.cap));
-                SD_HIP(hipMemcpyAsync(grown.p, ws.recs.p, (size_t)j.appended * sizeof(sd::DevRec), hipMemcpyDeviceToDevice, st));
-                DevBuf<uint32_t> gw, gh;
-                if (per) {
-                    gw.alloc(grown.cap * per);
-                    SD_HIP(hipMemcpyAsync(gw.p, fw->words.p, (size_t)j.appended * per * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-                    if (homo) {
-                        gh.alloc(grown.cap * per);
-                        SD_HIP(hipMemcpyAsync(gh.p, fw->hwords.p, (size_t)j.appended * per * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-                    }
-                }
-                SD_HIP(hipStreamSynchronize(st));
-                ws.recs.swap(grown);
-                if (per) {
-                    fw->words.swap(gw);
-                    if (homo) fw->hwords.swap(gh);
-                }
-            }
+        if (!per) return;
+        fw->words.alloc(ws.recs.cap * per);
+        if (homo) fw->hwords.alloc(ws.recs.cap * per);
+    }
+    // a later batch outgrew it: larger blocks, what was appended so far copied over; the old blocks leave with nothing
+    // in flight on them.  (An allocation that fails leaves the store half swapped: the job fails with it, and the next
+    // job sizes the store anew.)
+    template <class T>
+    void grow(DevBuf<T>& buf, DevBuf<T>& old, size_t count, size_t keep) {
+        old.swap(buf);
+        buf.alloc(count);
+        SD_HIP(hipMemcpyAsync(buf.p, old.p, keep * sizeof(T), hipMemcpyDeviceToDevice, st));
+    }
+    void regrow(size_t need) {
+        DevBuf<sd::DevRec> old;
+        DevBuf<uint32_t> old_w, old_h;
+        const size_t have = (size_t)j.store.appended;
+        grow(ws.recs, old, std::max<size_t>(need, 2 * ws.recs.cap), have);
+        if (per) {
+            grow(fw->words, old_w, ws.recs.cap * per, have * per);
+            if (homo) grow(fw->hwords, old_h, ws.recs.cap * per, have * per);
         }
-        if (per && j.appended == 0) {   // the words' room follows the store's (a store kept from an earlier job may be larger)
-            fw->words.alloc(ws.recs.cap * per);
-            if (homo) fw->hwords.alloc(ws.recs.cap * per);
-        }
-        if (per && total > 0) {
-            // (the run is through -- fetch_begin waited for it -- so the batch's words are complete in the engine's outputs)
-            fw->settled = false;
-            const size_t nb = (size_t)total * per * sizeof(uint32_t);
-            const bool valid = e->ident_valid && (size_t)e->ident_words() == per && (!homo || e->ident_mode == 2);
-            uint32_t* w = fw->words.p + (size_t)j.appended * per;
-            if (valid) SD_HIP(hipMemcpyAsync(w, e->d_ident.p, nb, hipMemcpyDeviceToDevice, st));
+        SD_HIP(hipStreamSynchronize(st));
+    }
+
+    // The batch's identity words behind those of the records so far (a device-final job with in-stream identities; the
+    // run is through -- fetch_begin waited for it -- so they are complete in the engine's outputs).
+    void append_words() {
+        fw->settled = false;
+        const size_t nb = (size_t)total * per * sizeof(uint32_t), at = (size_t)j.store.appended * per;
+        const bool valid = e->ident_valid && (size_t)e->ident_words() == per && (!homo || e->ident_mode == 2);
+        auto put = [&](uint32_t* w, const uint32_t* from) {
+            if (valid) SD_HIP(hipMemcpyAsync(w, from, nb, hipMemcpyDeviceToDevice, st));
             else SD_HIP(hipMemsetAsync(w, 0, nb, st));
-            if (homo) {
-                uint32_t* h = fw->hwords.p + (size_t)j.appended * per;
-                if (valid) SD_HIP(hipMemcpyAsync(h, e->d_identh.p, nb, hipMemcpyDeviceToDevice, st));
-                else SD_HIP(hipMemsetAsync(h, 0, nb, st));
-            }
+        };
+        put(fw->words.p + at, e->d_ident.p);
+        if (homo) put(fw->hwords.p + at, e->d_identh.p);
+    }
+
+    void append_records() {
+        rows_append(ws, st, e->d_dense.p, e->d_roff.p, (int)C, ws.add.p + c0, j.store.appended, e->score_scale);
+        for (size_t c = 0; c < C; ++c) j.store.rec_at.push_back(j.store.appended + e->h_roff.p[c + 1]);
+        j.store.appended += total;
+    }
+
+    // Behind the last batch: the merge,
+    void merge() {
+        std::vector<int64_t> read_off((size_t)j.n_reads + 1, 0);
+        size_t c = 0;
+        for (int32_t r = 0; r < j.n_reads; ++r) {
+            c += (size_t)j.nch[(size_t)r];
+            read_off[(size_t)r + 1] = j.store.rec_at[c];
         }
-        rows_append(ws, st, e->d_dense.p, e->d_roff.p, (int)C, ws.add.p + c0, j.appended, e->score_scale);
-        for (size_t c = 0; c < C; ++c) j.rec_at.push_back(j.appended + e->h_roff.p[c + 1]);
-        j.appended = need;
-        if (c1 == CJ) {
-            std::vector<int64_t> read_off((size_t)j.n_reads + 1, 0);
-            size_t c = 0;
-            for (int32_t r = 0; r < j.n_reads; ++r) {
-                c += (size_t)j.nch[(size_t)r];
-                read_off[(size_t)r + 1] = j.rec_at[c];
-            }
-            rows_assemble(ws, st, ws.recs.p, read_off.data(), j.n_reads, ROWS_PIECE);
-            j.assembled = true;
-            if (per) {
-                if (!fm->dtab_up) { fm->dtab.upload(fm->pp.final_tables()); fm->dtab_up = true; }
-                const size_t nr = (size_t)j.n_reads;
-                fw->h_rlen.alloc(nr);
-                for (size_t r = 0; r < nr; ++r) fw->h_rlen.p[r] = j.dev ? j.rlen[r] : (int64_t)j.seq[r].size();
-                fw->rlen.alloc(nr);
-                fw->settled = false;
-                SD_HIP(hipMemcpyAsync(fw->rlen.p, fw->h_rlen.p, nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                final_sources(*fw, ws, st);
-                final_select(*fw, st, fm->dtab.tb, ws.recs.p, fw->src.p, fw->src.p, fw->words.p, fw->hwords.p, fw->moff.p,
-                             fw->rlen.p, j.n_reads, ws.n_recs, ws.bbase.p + ws.n_tiles);
-                if (fm->pd) {
-                    // the pairs of the kept rows, planned and grouped behind the selection; their summary travels with
-                    // the selection's counts, ahead of ev_sel (recorded anew behind it)
-                    ProfWS& pw = fw->prof;
-                    pw.h_text_off.alloc(nr + 1);
-                    for (size_t r = 0; r < nr; ++r) pw.h_text_off.p[r] = j.text_off[r];
-                    pw.h_text_off.p[nr] = 0;
-                    pw.text_off.alloc(nr + 1);
-                    SD_HIP(hipMemcpyAsync(pw.text_off.p, pw.h_text_off.p, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-                    prof_plan(pw, *fm->pd, st, ws.recs.p, fw->src.p, fw->keep.p, fw->moff.p, fw->rlen.p, j.n_reads, ws.n_recs,
-                              ws.bbase.p + ws.n_tiles);
-                    SD_HIP(hipEventRecord(fw->ev_sel, st));
-                }
-                j.selected = true;
+        rows_assemble(ws, st, ws.recs.p, read_off.data(), j.n_reads, ROWS_PIECE);
+        j.store.assembled = true;
+    }
+    // the selection (a device-final job with in-stream identities),
+    void select() {
+        if (!fm->dtab_up) { fm->dtab.upload(fm->pp.final_tables()); fm->dtab_up = true; }
+        const size_t nr = (size_t)j.n_reads;
+        fw->h_rlen.alloc(nr);
+        for (size_t r = 0; r < nr; ++r) fw->h_rlen.p[r] = j.din.dev ? j.din.rlen[r] : (int64_t)j.seq[r].size();
+        fw->rlen.alloc(nr);
+        fw->settled = false;
+        SD_HIP(hipMemcpyAsync(fw->rlen.p, fw->h_rlen.p, nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        final_sources(*fw, ws, st);
+        final_select(*fw, st, fm->dtab.tb, ws.recs.p, fw->src.p, fw->src.p, fw->words.p, fw->hwords.p, fw->moff.p,
+                     fw->rlen.p, j.n_reads, ws.n_recs, ws.bbase.p + ws.n_tiles);
+    }
+    // and (a device-profile stream) the pairs of the kept rows, planned and grouped behind the selection; their summary
+    // travels with the selection's counts, ahead of ev_sel (recorded anew behind it).
+    void plan_profile() {
+        const size_t nr = (size_t)j.n_reads;
+        ProfWS& pw = fw->prof;
+        pw.h_text_off.alloc(nr + 1);
+        for (size_t r = 0; r < nr; ++r) pw.h_text_off.p[r] = j.din.text_off[r];
+        pw.h_text_off.p[nr] = 0;
+        pw.text_off.alloc(nr + 1);
+        SD_HIP(hipMemcpyAsync(pw.text_off.p, pw.h_text_off.p, (nr + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        prof_plan(pw, *fm->pd, st, ws.recs.p, fw->src.p, fw->keep.p, fw->moff.p, fw->rlen.p, j.n_reads, ws.n_recs,
+                  ws.bbase.p + ws.n_tiles);
+        SD_HIP(hipEventRecord(fw->ev_sel, st));
+    }
+};
+
+static int rows_batch(StreamJob& j, sd_engine* e, int64_t total, hipStream_t st, size_t c0, size_t c1, char* eb, size_t eblen,
+                      FinalMode* fm = nullptr) {
+    RowsBatch b{j, e, total, st, c0, c1, fm};
+    try {
+        if (!j.store.ws_begun) b.begin_store();
+        b.reserve();
+        if (b.per && total > 0) b.append_words();
+        b.append_records();
+        if (c1 == b.CJ) {
+            b.merge();
+            if (b.per) {
+                b.select();
+                if (fm->pd) b.plan_profile();
+                j.dfin.selected = true;
             }
         }
     } catch (const HipFail& f) {
@@ -214,14 +283,13 @@ static void final_sink(FinalMode& fm, const Pipeline& pipe, StreamJob& j, size_t
     if (j.rc == SD_OK) {
         std::vector<sd::PostRead> pr;
         for (size_t r = r0; r < r1; ++r)
-            pr.push_back(sd::PostRead{"", 0, j.dev ? nullptr : j.seq[r].data(), j.dev ? j.rlen[r] : (int64_t)j.seq[r].size()});
+            pr.push_back(sd::PostRead{"", 0, j.din.dev ? nullptr : j.seq[r].data(), j.din.dev ? j.din.rlen[r] : (int64_t)j.seq[r].size()});
         // reads in device memory: the text of these reads comes to the host only if the post-processor asks for it
         // (its fallback identities, the profiles); the rows have come back, so the job's copy is complete
-        if (j.dev)
+        if (j.din.dev)
             fm.pp.fetch_text = [&j, &pr, r0, r1](std::string& e) -> int {
                 for (size_t r = r0; r < r1; ++r) {
-                    j.seq[r].resize((size_t)j.rlen[r]);
-                    if (hipMemcpy(&j.seq[r][0], j.text->p + j.text_off[r], (size_t)j.rlen[r], hipMemcpyDeviceToHost) != hipSuccess) {
+                    if (fetch_read_text(j, r) != hipSuccess) {
                         (void)hipGetLastError();
                         e = "cannot fetch the text of read " + std::to_string(r) + " from the device";
                         return SD_ERR_HIP;
@@ -239,7 +307,7 @@ static void final_sink(FinalMode& fm, const Pipeline& pipe, StreamJob& j, size_t
             j.rc = SD_ERR_INTERNAL;
             j.err = "out of host memory";
         }
-        if (j.dev) {
+        if (j.din.dev) {
             fm.pp.fetch_text = nullptr;
             for (size_t r = r0; r < r1; ++r) std::string().swap(j.seq[r]);
         }
@@ -377,11 +445,11 @@ struct StreamEntries {
         // --second-best: the identities of a batch in slices of whole reads, each handed over as the device finishes it
         // (sd_engine::slice_end), so that the host selects slice s while the device computes slice s + 1
         // (a device-final job's words stay on the device: nothing to hand over in slices)
-        if (fm && fm->second_best && jp->per && !jp->ws) ident_slices(jp->table, q.c0, q.c1, e.slice_end);
+        if (fm && fm->second_best && jp->per && !jp->store.ws) ident_slices(jp->table, q.c0, q.c1, e.slice_end);
         DevSrc ds;
-        if (jp->dev) {
-            ds = jp->ds;
-            ds.gpos = jp->gpos.data() + q.c0;
+        if (jp->din.dev) {
+            ds = jp->din.ds;
+            ds.gpos = jp->din.gpos.data() + q.c0;
         }
         const int32_t dev = devs[i];
         const size_t c0 = q.c0, c1 = q.c1, b = q.b;
@@ -389,11 +457,11 @@ struct StreamEntries {
         // order); the sink below then only takes its turn and counts the batch off its job
         DevSink dsink;
         FinalMode* const fmq = fm;
-        if (jp->ws) dsink = [&pq, jp, c0, c1, fmq](sd_engine* en, int64_t total, hipStream_t st) { return rows_batch(*jp, en, total, st, c0, c1, pq.eb, sizeof pq.eb, fmq); };
+        if (jp->store.ws) dsink = [&pq, jp, c0, c1, fmq](sd_engine* en, int64_t total, hipStream_t st) { return rows_batch(*jp, en, total, st, c0, c1, pq.eb, sizeof pq.eb, fmq); };
         return pq.push(e.cptr, e.clen, [this, &pq, jp, dev, b, c0, c1](const sd_rec* r, const int64_t* ro, size_t first, size_t n) {
             const bool mine = turns.wait(b);   // (false: the stream failed; the batch is dropped)
             if (mine) {
-                if (jp->ws) {
+                if (jp->store.ws) {
                     // (the records stayed on the device: rows_batch has them)
                 } else if (fm) {
                     final_sink(*fm, pq, *jp, c0 + first, c0 + first + n, r, ro);
@@ -411,7 +479,7 @@ struct StreamEntries {
                 cv.notify_all();
                 turns.done(b);
             }
-        }, e.slice_end, jp->dev ? &ds : nullptr, std::move(dsink));
+        }, e.slice_end, jp->din.dev ? &ds : nullptr, std::move(dsink));
     }
 
     // One action of entry i, on the thread that drives it: push q, pop, or drain (after a failure, and at exit); then the
@@ -511,16 +579,24 @@ struct StreamEntries {
 };
 }  // namespace sdi
 
+// Which rows a stream makes and where it leaves them, and so which collect and peek calls belong to it (wrong_call).
+enum class StreamMode {
+    RawHost,       // sd_stream_create: raw rows in host memory
+    RawDevice,     // with SD_FLAG_DEVICE_ROWS: the jobs' rows are assembled and collected on the device
+    FinalHost,     // sd_stream_create_final: final rows in host memory
+    FinalDevice,   // with SD_FLAG_DEVICE_FINAL: the final rows are selected and collected on the device (dev_prof: and folded)
+};
+
 struct sd_stream {
     sd_params p{};
     std::vector<std::string> mono;       // owned copies
-    std::unique_ptr<FinalMode> fin;      // final mode only
+    StreamMode mode = StreamMode::RawHost;
+    bool device_store() const { return mode == StreamMode::RawDevice || mode == StreamMode::FinalDevice; }   // the jobs have a record store
+    std::unique_ptr<FinalMode> fin;      // the final modes only
     int sub_batches = 1;
-    std::vector<std::unique_ptr<DevBuf<uint8_t>>> spare;   // device copies of reads (StreamJob::text) between jobs
-    bool dev_rows = false;               // SD_FLAG_DEVICE_ROWS: the jobs' rows are assembled and collected on the device
-    std::vector<std::unique_ptr<RowsWS>> ws_spare;         // record stores (StreamJob::ws) between jobs
-    bool dev_final = false;              // SD_FLAG_DEVICE_FINAL: the final rows are selected and collected on the device
-    std::vector<std::unique_ptr<FinalWS>> fws_spare;       // selection workspaces (StreamJob::fws) between jobs
+    std::vector<std::unique_ptr<DevBuf<uint8_t>>> spare;   // device copies of reads (StreamJob::din.text) between jobs
+    std::vector<std::unique_ptr<RowsWS>> ws_spare;         // record stores (StreamJob::store.ws) between jobs
+    std::vector<std::unique_ptr<FinalWS>> fws_spare;       // selection workspaces (StreamJob::dfin.fws) between jobs
     hipEvent_t ev_src = nullptr;         // sd_stream_submit_dev: the caller's stream has produced the job's reads
     int ev_src_dev = -1;
     std::vector<std::unique_ptr<StreamJob>> jobs;   // FIFO: submitted, not collected yet
@@ -553,6 +629,48 @@ struct sd_stream {
     }
 };
 
+// The refusals of a combination of modes and flags: the first test that holds gives the text, null: none does.
+// (several: a device list of more than one entry.)  Most stand before the device list is checked (mode_refusal), three
+// behind that check and the one for monomers (mode_refusal_behind_list).
+struct ModeFlags {
+    bool dev_rows, dev_final, dev_prof, profile;
+    explicit ModeFlags(int32_t f) : dev_rows(f & SD_FLAG_DEVICE_ROWS), dev_final(f & SD_FLAG_DEVICE_FINAL),
+                                    dev_prof(f & SD_FLAG_DEVICE_PROFILE), profile(f & SD_FLAG_PROFILE) {}
+};
+
+// SD_FLAG_DEVICE_ROWS on a final-mode stream; with SD_FLAG_DEVICE_FINAL it is refused before the device list, without behind it
+static const char* device_rows_on_final(bool dev_final) {
+    return dev_final ? "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host (or, with SD_FLAG_DEVICE_FINAL alone, on the device)"
+                     : "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host";
+}
+
+static const char* mode_refusal(bool final, ModeFlags f, bool several) {
+    if (f.dev_prof && !final)
+        return "SD_FLAG_DEVICE_PROFILE needs a final-mode stream made with SD_FLAG_DEVICE_FINAL (sd_stream_create_final): a raw-mode stream selects no rows to profile";
+    if (f.dev_prof && !f.dev_final)
+        return "SD_FLAG_DEVICE_PROFILE needs SD_FLAG_DEVICE_FINAL: it folds the rows the device selects; the rows of a host final stream are profiled with SD_FLAG_PROFILE";
+    if (f.dev_prof && several)
+        return "SD_FLAG_DEVICE_PROFILE needs SD_FLAG_DEVICE_FINAL and so a device list of one entry: the batches of a job would lie on several devices";
+    if (f.dev_prof && f.profile)
+        return "SD_FLAG_DEVICE_PROFILE and SD_FLAG_PROFILE do not go together: a SD_FLAG_DEVICE_FINAL stream folds its profiles on the device, the host pass of SD_FLAG_PROFILE has no rows there";
+    if (f.dev_final && final && f.dev_rows) return device_rows_on_final(true);
+    if (f.dev_final && !final)
+        return "SD_FLAG_DEVICE_FINAL needs a final-mode stream (sd_stream_create_final): a raw-mode stream keeps its rows on the device with SD_FLAG_DEVICE_ROWS";
+    if (f.dev_final && several)
+        return "SD_FLAG_DEVICE_FINAL needs a device list of one entry: the batches of a job would lie on several devices";
+    if (f.dev_final && f.profile)
+        return "SD_FLAG_DEVICE_FINAL and SD_FLAG_PROFILE do not go together: the profile pass reads the kept rows and the read text on the host";
+    return nullptr;
+}
+
+static const char* mode_refusal_behind_list(bool final, ModeFlags f, bool several) {
+    if (!final && f.profile) return "SD_FLAG_PROFILE needs a final-mode stream";
+    if (f.dev_rows && final) return device_rows_on_final(false);   // (mode_refusal has taken those with SD_FLAG_DEVICE_FINAL)
+    if (f.dev_rows && several)
+        return "SD_FLAG_DEVICE_ROWS needs a device list of one entry: the batches of a job would lie on several devices";
+    return nullptr;
+}
+
 // The four creates.  who: the name of a call with a device list, which is checked as by sd_run_files_devices; without
 // one (who == nullptr) the stream has the one entry p->device.  final: the final mode, with mono_names .. lr_coef.
 static int stream_create(sd_stream** out, const sd_params* p, const char* who, const int32_t* devices, int32_t n_devices,
@@ -565,56 +683,17 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     sd_params q = *p;
-    const bool dev_final = (p->reserved[1] & SD_FLAG_DEVICE_FINAL) != 0;
-    const bool dev_prof = (p->reserved[1] & SD_FLAG_DEVICE_PROFILE) != 0;
-    if (dev_prof && !final) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE needs a final-mode stream made with SD_FLAG_DEVICE_FINAL (sd_stream_create_final): a raw-mode stream selects no rows to profile");
-        return SD_ERR_PARAM;
-    }
-    if (dev_prof && !dev_final) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE needs SD_FLAG_DEVICE_FINAL: it folds the rows the device selects; the rows of a host final stream are profiled with SD_FLAG_PROFILE");
-        return SD_ERR_PARAM;
-    }
-    if (dev_prof && who && n_devices > 1) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE needs SD_FLAG_DEVICE_FINAL and so a device list of one entry: the batches of a job would lie on several devices");
-        return SD_ERR_PARAM;
-    }
-    if (dev_prof && (p->reserved[1] & SD_FLAG_PROFILE)) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_PROFILE and SD_FLAG_PROFILE do not go together: a SD_FLAG_DEVICE_FINAL stream folds its profiles on the device, the host pass of SD_FLAG_PROFILE has no rows there");
-        return SD_ERR_PARAM;
-    }
-    if (dev_final && (p->reserved[1] & SD_FLAG_DEVICE_ROWS) && final) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host (or, with SD_FLAG_DEVICE_FINAL alone, on the device)");
-        return SD_ERR_PARAM;
-    }
-    if (dev_final && !final) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_FINAL needs a final-mode stream (sd_stream_create_final): a raw-mode stream keeps its rows on the device with SD_FLAG_DEVICE_ROWS");
-        return SD_ERR_PARAM;
-    }
-    if (dev_final && who && n_devices > 1) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_FINAL needs a device list of one entry: the batches of a job would lie on several devices");
-        return SD_ERR_PARAM;
-    }
-    if (dev_final && (p->reserved[1] & SD_FLAG_PROFILE)) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_FINAL and SD_FLAG_PROFILE do not go together: the profile pass reads the kept rows and the read text on the host");
-        return SD_ERR_PARAM;
-    }
+    const ModeFlags flags(p->reserved[1]);
+    const bool several = who && n_devices > 1;
+    if (const char* no = mode_refusal(final, flags, several)) { set_err(errbuf, errlen, no); return SD_ERR_PARAM; }
     if (who) {
         rc = check_device_list(who, devices, n_devices, errbuf, errlen);
         if (rc) return rc;
         q.device = devices[0];   // (also the device of the fallback identities)
     }
     if (n_mono <= 0 || !mono_seqs || !mono_lens) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }
-    if (!final && (p->reserved[1] & SD_FLAG_PROFILE)) { set_err(errbuf, errlen, "SD_FLAG_PROFILE needs a final-mode stream"); return SD_ERR_PARAM; }
-    const bool dev_rows = (p->reserved[1] & SD_FLAG_DEVICE_ROWS) != 0;
-    if (dev_rows && final) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a raw-mode stream: the rows of a final-mode stream are selected on the host");
-        return SD_ERR_PARAM;
-    }
-    if (dev_rows && who && n_devices > 1) {
-        set_err(errbuf, errlen, "SD_FLAG_DEVICE_ROWS needs a device list of one entry: the batches of a job would lie on several devices");
-        return SD_ERR_PARAM;
-    }
+    if (const char* no = mode_refusal_behind_list(final, flags, several)) { set_err(errbuf, errlen, no); return SD_ERR_PARAM; }
+    const bool dev_prof = flags.dev_prof;
     q.reserved[1] &= ~(SD_FLAG_DEVICE_ROWS | SD_FLAG_DEVICE_FINAL | SD_FLAG_DEVICE_PROFILE);   // (the flags shape the stream, not its engines)
     if (final && !mono_names) { set_err(errbuf, errlen, "no monomer names"); return SD_ERR_PARAM; }
     if (final && !lr_coef) { set_err(errbuf, errlen, "no logistic-regression coefficients"); return SD_ERR_PARAM; }
@@ -640,8 +719,8 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
         q.reserved[1] &= ~SD_FLAG_PROFILE;   // (the flag shapes the post-processing only)
     }
     s->p = q;
-    s->dev_rows = dev_rows;
-    s->dev_final = dev_final;
+    s->mode = final ? (flags.dev_final ? StreamMode::FinalDevice : StreamMode::FinalHost)
+                    : (flags.dev_rows ? StreamMode::RawDevice : StreamMode::RawHost);
     s->sub_batches = std::max(1, (int)sub_batches);
     std::vector<const char*> ms;
     for (const std::string& m : s->mono) ms.push_back(m.data());
@@ -650,18 +729,14 @@ static int stream_create(sd_stream** out, const sd_params* p, const char* who, c
     rc = s->me.open(&q, ms, mono_lens, n_mono, s->budget, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     if (dev_prof) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
         try {
-            if (cur != s->me.devs[0]) SD_HIP(hipSetDevice(s->me.devs[0]));
+            DeviceScope on(s->me.devs[0]);
             SD_HIP(hipStreamCreateWithFlags(&s->prof_st, hipStreamNonBlocking));
             s->pd.setup(s->fin->pp.interleaved_seqs(), s->fin->pp.own_interleaved(), s->prof_st);
         } catch (const HipFail& f) {
-            rc = SD_ERR_HIP;
             set_err(errbuf, errlen, f.msg);
+            return SD_ERR_HIP;   // (s is destroyed with the guard's device restored)
         }
-        if (cur >= 0 && cur != s->me.devs[0]) (void)hipSetDevice(cur);
-        if (rc) return rc;
         s->dev_prof = true;
         s->fin->pd = &s->pd;
     }
@@ -693,18 +768,28 @@ static int stream_wait_oldest(sd_stream* s, char* errbuf, size_t errlen) {
 // produced on the stream `user`.
 struct DevIn { const char* base; const int64_t* off; hipStream_t user; int device; };
 
+// A buffer of `bytes` for the job's device copy of its reads, from the stream's spare list where that has one.
+static void take_text(sd_stream* s, StreamJob& job, size_t bytes) {
+    std::unique_ptr<DevBuf<uint8_t>> t;
+    if (!s->spare.empty()) { t = std::move(s->spare.back()); s->spare.pop_back(); }
+    else t.reset(new DevBuf<uint8_t>);
+    job.din.text.take(std::move(t), s->spare);
+    job.din.text->alloc(bytes);
+}
+
 // The device half of a submit: the job's device addresses and chunk positions; in final mode its own device copy of the
 // reads, made on the caller's stream (so it follows what produced them and precedes what overwrites them); the event
 // on that stream the packers wait for.  Runs with the data's device current.
 static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const int64_t* read_lens, std::string& err) {
     const size_t n = (size_t)job.n_reads;
-    job.dev = true;
+    StreamJob::DevInput& in = job.din;
+    in.dev = true;
     auto cum = std::make_shared<std::vector<int64_t>>(n + 1, 0);
     for (size_t r = 0; r < n; ++r) (*cum)[r + 1] = (*cum)[r] + read_lens[r];
-    job.gpos.reserve(job.table.size());
-    for (const CRef& c : job.table) job.gpos.push_back((*cum)[(size_t)c.read] + c.off);
-    job.ds.user = dv.user;
-    job.ds.cum = cum;
+    in.gpos.reserve(job.table.size());
+    for (const CRef& c : job.table) in.gpos.push_back((*cum)[(size_t)c.read] + c.off);
+    in.ds.user = dv.user;
+    in.ds.cum = cum;
     job.own.resize(n);
     try {
         if (s->fin && n > 0) {
@@ -712,28 +797,26 @@ static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const i
             int64_t lo = INT64_MAX, hi = 0;
             for (size_t r = 0; r < n; ++r) { lo = std::min(lo, dv.off[r]); hi = std::max(hi, dv.off[r] + read_lens[r]); }
             const bool span = hi - lo <= 2 * (*cum)[n] + ((int64_t)1 << 20);
-            if (!s->spare.empty()) { job.text = std::move(s->spare.back()); s->spare.pop_back(); }
-            else job.text.reset(new DevBuf<uint8_t>);
-            job.spare = &s->spare;
-            job.text->alloc((size_t)(span ? hi - lo : (*cum)[n]) + (s->dev_prof ? 8 : 0));   // (the fold reads whole dwords)
-            job.rlen.assign(read_lens, read_lens + n);
-            job.text_off.resize(n);
-            for (size_t r = 0; r < n; ++r) job.text_off[r] = span ? dv.off[r] - lo : (*cum)[r];
-            if (span) SD_HIP(hipMemcpyAsync(job.text->p, dv.base + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, dv.user));
+            take_text(s, job, (size_t)(span ? hi - lo : (*cum)[n]) + (s->dev_prof ? 8 : 0));   // (the fold reads whole dwords)
+            in.rlen.assign(read_lens, read_lens + n);
+            in.text_off.resize(n);
+            for (size_t r = 0; r < n; ++r) in.text_off[r] = span ? dv.off[r] - lo : (*cum)[r];
+            if (span) SD_HIP(hipMemcpyAsync(in.text->p, dv.base + lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice, dv.user));
             else
                 for (size_t r = 0; r < n; ++r)
-                    SD_HIP(hipMemcpyAsync(job.text->p + job.text_off[r], dv.base + dv.off[r], (size_t)read_lens[r], hipMemcpyDeviceToDevice, dv.user));
-            for (size_t r = 0; r < n; ++r) job.own[r] = reinterpret_cast<const char*>(job.text->p) + job.text_off[r];
-            job.ds.release = false;   // (the packers read the job's copy: the caller's stream need not wait for them)
+                    SD_HIP(hipMemcpyAsync(in.text->p + in.text_off[r], dv.base + dv.off[r], (size_t)read_lens[r], hipMemcpyDeviceToDevice, dv.user));
+            for (size_t r = 0; r < n; ++r) job.own[r] = reinterpret_cast<const char*>(in.text->p) + in.text_off[r];
+            in.ds.release = false;   // (the packers read the job's copy: the caller's stream need not wait for them)
         } else {
             for (size_t r = 0; r < n; ++r) job.own[r] = dv.base + dv.off[r];
         }
         if (s->ev_src && s->ev_src_dev != dv.device) { (void)hipEventDestroy(s->ev_src); s->ev_src = nullptr; }
-        if (!s->ev_src) { SD_HIP(hipEventCreateWithFlags(&s->ev_src, hipEventDisableTiming)); s->ev_src_dev = dv.device; }
+        ensure_event(s->ev_src, hipEventDisableTiming);
+        s->ev_src_dev = dv.device;
         // (every batch of the job is packed -- its wait for this event enqueued -- before the submit returns, so the
         // next submit may record the event anew)
         SD_HIP(hipEventRecord(s->ev_src, dv.user));
-        job.ds.ready = s->ev_src;
+        in.ds.ready = s->ev_src;
     } catch (const HipFail& f) {
         err = f.msg;
         return SD_ERR_HIP;
@@ -742,9 +825,6 @@ static int stream_dev_job(sd_stream* s, StreamJob& job, const DevIn& dv, const i
     return SD_OK;
 }
 
-// A record store for a new job of a device-rows stream: a spare one whose last scatter -- enqueued on that job's caller's
-// stream, which may be far behind -- has completed; else a new one, so that a slow consumer never stalls the pipeline
-// and no buffer a pending scatter reads is ever reallocated.  Beyond eight spares the oldest is waited for instead.
 // The fold time of a workspace's last job, once its fold has completed.
 static void prof_harvest(sd_stream* s, FinalWS& fw) {
     if (!fw.fold_timed) return;
@@ -756,30 +836,32 @@ static void prof_harvest(sd_stream* s, FinalWS& fw) {
 }
 
 // SD_FLAG_DEVICE_PROFILE, a job submitted from host memory: its reads go up once, back to back, into a buffer of the
-// kind a DeviceReads job has (StreamJob::text), through the workspace's pinned staging, on the stream's own stream.
+// kind a DeviceReads job has (StreamJob::din.text), through the workspace's pinned staging, on the stream's own stream.
 static void stream_prof_upload(sd_stream* s, StreamJob& job) {
     const size_t n = (size_t)job.n_reads;
-    FinalWS& fw = *job.fws;
-    job.text_off.assign(n + 1, 0);
-    for (size_t r = 0; r < n; ++r) job.text_off[r + 1] = job.text_off[r] + (int64_t)job.seq[r].size();
-    const size_t total = (size_t)job.text_off[n];
-    job.text_off.resize(n);
+    FinalWS& fw = *job.dfin.fws;
+    std::vector<int64_t>& text_off = job.din.text_off;
+    text_off.assign(n + 1, 0);
+    for (size_t r = 0; r < n; ++r) text_off[r + 1] = text_off[r] + (int64_t)job.seq[r].size();
+    const size_t total = (size_t)text_off[n];
+    text_off.resize(n);
     if (n == 0) return;
-    if (!s->spare.empty()) { job.text = std::move(s->spare.back()); s->spare.pop_back(); }
-    else job.text.reset(new DevBuf<uint8_t>);
-    job.spare = &s->spare;
-    job.text->alloc(total + 8);
+    take_text(s, job, total + 8);
     fw.prof.h_text.alloc(total);
     uint8_t* stage = fw.prof.h_text.p;
     sd::parallel_for((int64_t)n, s->p.threads, 1, [&](int64_t r) {
-        std::memcpy(stage + job.text_off[(size_t)r], job.seq[(size_t)r].data(), job.seq[(size_t)r].size());
+        std::memcpy(stage + text_off[(size_t)r], job.seq[(size_t)r].data(), job.seq[(size_t)r].size());
     });
-    SD_HIP(hipMemcpyAsync(job.text->p, stage, total, hipMemcpyHostToDevice, s->prof_st));
-    if (!fw.ev_prof) SD_HIP(hipEventCreate(&fw.ev_prof));
+    SD_HIP(hipMemcpyAsync(job.din.text->p, stage, total, hipMemcpyHostToDevice, s->prof_st));
+    ensure_event(fw.ev_prof);
     SD_HIP(hipEventRecord(fw.ev_prof, s->prof_st));
     fw.prof_recorded = true;
 }
 
+// A record store (or a selection workspace) for a new job of a device-rows or device-final stream: a spare one whose
+// last scatter -- enqueued on that job's caller's stream, which may be far behind -- has completed; else a new one, so
+// that a slow consumer never stalls the pipeline and no buffer a pending scatter reads is ever reallocated.  Beyond
+// eight spares the oldest is waited for instead.
 template <class WS>
 static std::unique_ptr<WS> stream_take_ws(std::vector<std::unique_ptr<WS>>& sp) {
     for (size_t i = sp.size(); i-- > 0;)
@@ -797,6 +879,9 @@ static std::unique_ptr<WS> stream_take_ws(std::vector<std::unique_ptr<WS>>& sp) 
     return std::unique_ptr<WS>(new WS);
 }
 
+// identity words per record of a job whose engines compute the identities in-stream
+static int job_ident_words(const FinalMode& fm) { return fm.second_best ? (int)fm.pp.interleaved_seqs().size() : 1; }
+
 static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads,
                          char* errbuf, size_t errlen, const DevIn* dv = nullptr) {
     std::unique_ptr<StreamJob> job(new StreamJob);
@@ -812,56 +897,48 @@ static int stream_submit(sd_stream* s, const char* const* read_seqs, const int64
     if (!job->row_off) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
     FinalMode* fm = s->fin.get();
     job->reads = read_seqs;
-    if (s->dev_rows || s->dev_final) {
-        job->ws = stream_take_ws(s->ws_spare);
-        job->ws_home = &s->ws_spare;
-    }
-    if (s->dev_final) {
-        job->fws = stream_take_ws(s->fws_spare);
-        job->fws_home = &s->fws_spare;
+    if (s->device_store()) job->store.ws.take(stream_take_ws(s->ws_spare), s->ws_spare);
+    if (s->mode == StreamMode::FinalDevice) {
+        job->dfin.fws.take(stream_take_ws(s->fws_spare), s->fws_spare);
         if (s->dev_prof) {   // (the workspace is idle: its last fold is through, the text that waited for it is free)
-            prof_harvest(s, *job->fws);
-            if (job->fws->held_text) s->spare.push_back(std::move(job->fws->held_text));
-            job->fws->prof.planned = false;
+            prof_harvest(s, *job->dfin.fws);
+            if (job->dfin.fws->held_text) s->spare.push_back(std::move(job->dfin.fws->held_text));
+            job->dfin.fws->prof.planned = false;
         }
     }
+    if (fm && fm->ident) job->per = job_ident_words(*fm);
     if (dv) {
         // the data's device is current while the job's events and copies are made (the entries all run on it)
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != dv->device && hipSetDevice(dv->device) != hipSuccess) { (void)hipGetLastError(); set_err(errbuf, errlen, "hipSetDevice failed"); return SD_ERR_HIP; }
-        std::string err;
-        if (fm) job->seq.resize((size_t)n_reads);
-        int rd = stream_dev_job(s, *job, *dv, read_lens, err);
-        // (the folds of this job and of later ones run behind the copy of its text)
-        if (rd == SD_OK && s->dev_prof && n_reads > 0 && hipStreamWaitEvent(s->prof_st, s->ev_src, 0) != hipSuccess) {
+        try {
+            DeviceScope on(dv->device);
+            std::string err;
+            if (fm) job->seq.resize((size_t)n_reads);
+            int rd = stream_dev_job(s, *job, *dv, read_lens, err);
+            // (the folds of this job and of later ones run behind the copy of its text)
+            if (rd == SD_OK && s->dev_prof && n_reads > 0 && hipStreamWaitEvent(s->prof_st, s->ev_src, 0) != hipSuccess) {
+                (void)hipGetLastError();
+                err = "hipStreamWaitEvent failed";
+                rd = SD_ERR_HIP;
+            }
+            if (rd) { set_err(errbuf, errlen, err); return rd; }
+        } catch (const HipFail&) {   // (the guard's; stream_dev_job reports its own)
             (void)hipGetLastError();
-            err = "hipStreamWaitEvent failed";
-            rd = SD_ERR_HIP;
+            set_err(errbuf, errlen, "hipSetDevice failed");
+            return SD_ERR_HIP;
         }
-        if (cur >= 0 && cur != dv->device) (void)hipSetDevice(cur);
-        if (rd) { set_err(errbuf, errlen, err); return rd; }
-        if (fm && fm->ident) job->per = fm->second_best ? (int)fm->pp.interleaved_seqs().size() : 1;
     } else if (fm) {   // the fallback identities read the text when the rows come back: the job keeps a copy (sd_hip.h)
         job->seq.resize((size_t)n_reads);
         sd::parallel_for(n_reads, s->p.threads, 1, [&](int64_t r) { job->seq[(size_t)r].assign(read_seqs[r], (size_t)read_lens[r]); });
         for (const std::string& q : job->seq) job->own.push_back(q.data());
         job->reads = job->own.data();
-        if (fm->ident) job->per = fm->second_best ? (int)fm->pp.interleaved_seqs().size() : 1;
         if (s->dev_prof) {
-            int cur = -1;
-            (void)hipGetDevice(&cur);
-            const int dev = s->me.devs[0];
-            int ru = SD_OK;
             try {
-                if (cur != dev) SD_HIP(hipSetDevice(dev));
+                DeviceScope on(s->me.devs[0]);
                 stream_prof_upload(s, *job);
             } catch (const HipFail& f) {
                 set_err(errbuf, errlen, f.msg);
-                ru = SD_ERR_HIP;
+                return SD_ERR_HIP;
             }
-            if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-            if (ru) return ru;
         }
     }
     StreamEntries& me = s->me;
@@ -967,6 +1044,78 @@ int sd_stream_submit_dev(sd_stream* s, const void* d_bases, const int64_t* read_
 
 }  // extern "C"
 
+// The six collect and peek calls: their names, and whether their work needs the stream's device current.
+enum StreamCall { CALL_COLLECT, CALL_COLLECT_FINAL, CALL_PEEK_DEV, CALL_COLLECT_DEV, CALL_PEEK_FINAL_DEV, CALL_COLLECT_FINAL_DEV };
+static const struct { const char* name; bool on_device; } kStreamCalls[] = {
+    {"sd_stream_collect", false},  {"sd_stream_collect_final", false},  {"sd_stream_peek_dev", false},
+    {"sd_stream_collect_dev", true}, {"sd_stream_peek_final_dev", true}, {"sd_stream_collect_final_dev", true}};
+
+// Why a call does not belong to a stream of this mode, or null: it does.
+static const char* wrong_call(StreamMode m, StreamCall c) {
+    const bool raw = m == StreamMode::RawHost || m == StreamMode::RawDevice, fdev = m == StreamMode::FinalDevice;
+    switch (c) {
+    case CALL_COLLECT:
+        if (fdev) return "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: its rows are not on the host";
+        if (!raw) return "a final-mode stream is collected with sd_stream_collect_final";
+        if (m == StreamMode::RawDevice) return "a device-rows stream (SD_FLAG_DEVICE_ROWS) is collected with sd_stream_collect_dev: its rows are not on the host";
+        return nullptr;
+    case CALL_COLLECT_FINAL:
+        if (raw) return "sd_stream_collect_final on a stream made by sd_stream_create";
+        if (fdev) return "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: its rows are not on the host";
+        return nullptr;
+    case CALL_PEEK_DEV:
+        if (fdev) return "a device-final stream (SD_FLAG_DEVICE_FINAL) is peeked with sd_stream_peek_final_dev";
+        if (m != StreamMode::RawDevice) return "sd_stream_peek_dev on a stream made without SD_FLAG_DEVICE_ROWS";
+        return nullptr;
+    case CALL_COLLECT_DEV:
+        if (fdev) return "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: it has final rows, not raw ones";
+        if (m != StreamMode::RawDevice) return "sd_stream_collect_dev on a stream made without SD_FLAG_DEVICE_ROWS: its rows are on the host (sd_stream_collect)";
+        return nullptr;
+    case CALL_PEEK_FINAL_DEV:
+        return fdev ? nullptr : "sd_stream_peek_final_dev on a stream made without SD_FLAG_DEVICE_FINAL";
+    case CALL_COLLECT_FINAL_DEV:
+        return fdev ? nullptr : "sd_stream_collect_final_dev on a stream made without SD_FLAG_DEVICE_FINAL";
+    }
+    return nullptr;
+}
+
+// The frame of the six collect and peek calls, behind the check of their arguments: the refusals (a call that does not
+// belong to the stream's mode, no job, and `also_refused`, one of the call's own that ranks behind them), the wait for
+// the oldest job, the body -- with the stream's device current where the call needs it, a guard that ends before the
+// job may be destroyed -- and the time of it all.  (The bodies' refusals of a misplaced buffer run under that guard.)
+// The body returns the call's result, its message set, and says whether the job stays; a HipFail or std::bad_alloc it
+// throws becomes the call's result.  What becomes of the oldest job:
+//   kept      a refusal (wrong call for the mode, no job, a buffer in the wrong place, a buffer too small) and a
+//             successful peek: the bodies say keep = true for these;
+//   dropped   a collect that succeeded, or failed on the device, on memory or in the job's post-processing, and a failed
+//             sd_stream_peek_final_dev (a job whose rows cannot be made is dropped, as collect drops it);
+//   a stream-wide failure met in the wait drops every job (stream_wait_oldest).
+template <class Body>
+static int on_oldest_job(sd_stream* s, StreamCall call, char* errbuf, size_t errlen, Body&& body, const char* also_refused = nullptr) {
+    if (const char* wrong = wrong_call(s->mode, call)) { set_err(errbuf, errlen, wrong); return SD_ERR_PARAM; }
+    if (s->jobs.empty()) { set_err(errbuf, errlen, std::string(kStreamCalls[call].name) + " without a submitted job"); return SD_ERR_PARAM; }
+    if (also_refused) { set_err(errbuf, errlen, also_refused); return SD_ERR_PARAM; }
+    const double t0 = now_s();
+    int rc = stream_wait_oldest(s, errbuf, errlen);
+    if (rc == SD_OK) {
+        bool keep = false;
+        try {
+            std::optional<DeviceScope> on;
+            if (kStreamCalls[call].on_device) on.emplace(s->me.devs[0]);
+            rc = body(*s->jobs.front(), keep);
+        } catch (const HipFail& f) {
+            set_err(errbuf, errlen, f.msg);
+            rc = SD_ERR_HIP;
+        } catch (const std::bad_alloc&) {
+            set_err(errbuf, errlen, "out of host memory");
+            rc = SD_ERR_INTERNAL;
+        }
+        if (!keep) s->jobs.erase(s->jobs.begin());
+    }
+    s->collect_s += now_s() - t0;
+    return rc;
+}
+
 extern "C" {
 
 int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n_rows, char* errbuf, size_t errlen) {
@@ -974,29 +1123,16 @@ int sd_stream_collect(sd_stream* s, sd_rec** rows, int64_t** row_off, int64_t* n
     *rows = nullptr;
     *row_off = nullptr;
     if (n_rows) *n_rows = 0;
-    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: its rows are not on the host"); return SD_ERR_PARAM; }
-    if (s->fin) { set_err(errbuf, errlen, "a final-mode stream is collected with sd_stream_collect_final"); return SD_ERR_PARAM; }
-    if (s->dev_rows) { set_err(errbuf, errlen, "a device-rows stream (SD_FLAG_DEVICE_ROWS) is collected with sd_stream_collect_dev: its rows are not on the host"); return SD_ERR_PARAM; }
-    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect without a submitted job"); return SD_ERR_PARAM; }
-    const double t0 = now_s();
-    int rc = stream_wait_oldest(s, errbuf, errlen);
-    if (rc != SD_OK) {
-        s->collect_s += now_s() - t0;
-        return rc;
-    }
-    RowJob* job = s->jobs.front().get();
-    if (rc == SD_OK && job->oom) { set_err(errbuf, errlen, "out of host memory"); rc = SD_ERR_INTERNAL; }
-    if (rc == SD_OK) {
-        if (!job->rows) job->rows = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec)));
-        *rows = job->rows;
-        *row_off = job->row_off;
-        if (n_rows) *n_rows = (int64_t)job->n_rows;
-        job->rows = nullptr;      // ownership moves to the caller (sd_free)
-        job->row_off = nullptr;
-    }
-    s->jobs.erase(s->jobs.begin());
-    s->collect_s += now_s() - t0;
-    return rc;
+    return on_oldest_job(s, CALL_COLLECT, errbuf, errlen, [&](StreamJob& job, bool&) -> int {
+        if (job.oom) { set_err(errbuf, errlen, "out of host memory"); return SD_ERR_INTERNAL; }
+        if (!job.rows) job.rows = static_cast<sd_rec*>(std::malloc(sizeof(sd_rec)));
+        *rows = job.rows;
+        *row_off = job.row_off;
+        if (n_rows) *n_rows = (int64_t)job.n_rows;
+        job.rows = nullptr;      // ownership moves to the caller (sd_free)
+        job.row_off = nullptr;
+        return SD_OK;
+    });
 }
 
 int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off, int64_t* n_rows, double** alt,
@@ -1006,28 +1142,15 @@ int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off
     *row_off = nullptr;
     if (n_rows) *n_rows = 0;
     if (alt) *alt = nullptr;
-    if (!s->fin) { set_err(errbuf, errlen, "sd_stream_collect_final on a stream made by sd_stream_create"); return SD_ERR_PARAM; }
-    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: its rows are not on the host"); return SD_ERR_PARAM; }
-    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_final without a submitted job"); return SD_ERR_PARAM; }
-    const double t0 = now_s();
-    int rc = stream_wait_oldest(s, errbuf, errlen);
-    if (rc != SD_OK) {
-        s->collect_s += now_s() - t0;
-        return rc;
-    }
-    StreamJob& job = *s->jobs.front();
-    rc = job.rc;
-    if (rc) set_err(errbuf, errlen, job.err);
-    const size_t n = job.fin.n;
-    int64_t* off = nullptr;
-    if (rc == SD_OK) {
-        off = static_cast<int64_t*>(std::calloc((size_t)job.n_reads + 1, sizeof(int64_t)));
+    return on_oldest_job(s, CALL_COLLECT_FINAL, errbuf, errlen, [&](StreamJob& job, bool&) -> int {
+        if (job.rc) { set_err(errbuf, errlen, job.err); return job.rc; }
+        const size_t n = job.fin.n;
+        int64_t* off = static_cast<int64_t*>(std::calloc((size_t)job.n_reads + 1, sizeof(int64_t)));
         if (!off || !job.fin.resize(std::max<size_t>(n, 1)) || !job.alt.resize(std::max<size_t>(job.alt.n, 1))) {
+            std::free(off);
             set_err(errbuf, errlen, "out of host memory");
-            rc = SD_ERR_INTERNAL;
+            return SD_ERR_INTERNAL;
         }
-    }
-    if (rc == SD_OK) {
         for (size_t i = 0; i < n; ++i) ++off[(size_t)job.fin.p[i].read + 1];   // rows come in read order
         for (int32_t r = 0; r < job.n_reads; ++r) off[r + 1] += off[r];
         *rows = job.fin.release();   // ownership moves to the caller (sd_free)
@@ -1035,67 +1158,31 @@ int sd_stream_collect_final(sd_stream* s, sd_final_row** rows, int64_t** row_off
         if (n_rows) *n_rows = (int64_t)n;
         if (alt && s->fin->second_best) *alt = job.alt.release();
         s->fin->kept += (int64_t)n;
-    } else {
-        std::free(off);
-    }
-    s->jobs.erase(s->jobs.begin());
-    s->collect_s += now_s() - t0;
-    return rc;
+        return SD_OK;
+    });
 }
 
 int sd_stream_peek_dev(sd_stream* s, int32_t* n_reads, int64_t* max_rows, char* errbuf, size_t errlen) {
     if (!s) return SD_ERR_PARAM;
-    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is peeked with sd_stream_peek_final_dev"); return SD_ERR_PARAM; }
-    if (!s->dev_rows) { set_err(errbuf, errlen, "sd_stream_peek_dev on a stream made without SD_FLAG_DEVICE_ROWS"); return SD_ERR_PARAM; }
-    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_peek_dev without a submitted job"); return SD_ERR_PARAM; }
-    const double t0 = now_s();
-    const int rc = stream_wait_oldest(s, errbuf, errlen);
-    if (rc == SD_OK) {
-        if (n_reads) *n_reads = s->jobs.front()->n_reads;
-        if (max_rows) *max_rows = s->jobs.front()->appended;
-    }
-    s->collect_s += now_s() - t0;
-    return rc;
+    return on_oldest_job(s, CALL_PEEK_DEV, errbuf, errlen, [&](StreamJob& job, bool& keep) -> int {
+        keep = true;
+        if (n_reads) *n_reads = job.n_reads;
+        if (max_rows) *max_rows = job.store.appended;
+        return SD_OK;
+    });
 }
 
 int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_t* d_row_off, void* hip_stream,
                           int64_t* n_rows, char* errbuf, size_t errlen) {
     if (!s || !d_row_off || cap_rows < 0 || (cap_rows > 0 && !d_rows)) return SD_ERR_PARAM;
     if (n_rows) *n_rows = 0;
-    if (s->dev_final) { set_err(errbuf, errlen, "a device-final stream (SD_FLAG_DEVICE_FINAL) is collected with sd_stream_collect_final_dev: it has final rows, not raw ones"); return SD_ERR_PARAM; }
-    if (!s->dev_rows) { set_err(errbuf, errlen, "sd_stream_collect_dev on a stream made without SD_FLAG_DEVICE_ROWS: its rows are on the host (sd_stream_collect)"); return SD_ERR_PARAM; }
-    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_dev without a submitted job"); return SD_ERR_PARAM; }
-    const double t0 = now_s();
-    int rc = stream_wait_oldest(s, errbuf, errlen);
-    if (rc != SD_OK) {
-        s->collect_s += now_s() - t0;
-        return rc;
-    }
-    StreamJob& job = *s->jobs.front();
-    const int dev = s->me.devs[0];
-    if (cap_rows > 0) {
-        std::string err;
-        int at = dev;
-        rc = device_pointer(d_rows, at, err);
-        if (rc == SD_OK && at != dev) {
-            err = "the row buffer lies in the memory of device " + std::to_string(at) + ", the stream runs on device " + std::to_string(dev);
-            rc = SD_ERR_UNSUPPORTED;
-        }
-        if (rc) {
-            set_err(errbuf, errlen, rc == SD_ERR_UNSUPPORTED ? err : "sd_stream_collect_dev: the row buffer is not in device memory");
-            s->collect_s += now_s() - t0;
-            return rc;
-        }
-    }
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    bool keep_job = false;
-    try {
-        if (cur != dev) SD_HIP(hipSetDevice(dev));
+    return on_oldest_job(s, CALL_COLLECT_DEV, errbuf, errlen, [&](StreamJob& job, bool& keep) -> int {
+        if (cap_rows > 0)
+            if (const int rc = buffer_on_device(d_rows, s->me.devs[0], "sd_stream_collect_dev", "row", errbuf, errlen)) { keep = true; return rc; }
         hipStream_t user = reinterpret_cast<hipStream_t>(hip_stream);
-        RowsWS& ws = *job.ws;
+        RowsWS& ws = *job.store.ws;
         int64_t n = 0;
-        if (job.assembled) {
+        if (job.store.assembled) {
             SD_HIP(hipEventSynchronize(ws.ev_asm));   // (the row count is on the host)
             ws.settled = true;
             n = ws.h_total.p[0];
@@ -1103,22 +1190,17 @@ int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_
         if (n_rows) *n_rows = n;
         if (cap_rows < n) {
             set_err(errbuf, errlen, "sd_stream_collect_dev: the job has " + std::to_string(n) + " rows, the buffer room for " + std::to_string(cap_rows));
-            rc = SD_ERR_PARAM;
-            keep_job = true;
-        } else if (job.assembled) {
+            keep = true;
+            return SD_ERR_PARAM;
+        }
+        if (job.store.assembled) {
             SD_HIP(hipStreamWaitEvent(user, ws.ev_asm, 0));
             rows_scatter(ws, user, ws.recs.p, reinterpret_cast<sd::DevRec*>(d_rows), cap_rows, d_row_off);
         } else {   // (a job without chunks: no reads)
             SD_HIP(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * ((size_t)job.n_reads + 1), user));
         }
-    } catch (const HipFail& f) {
-        set_err(errbuf, errlen, f.msg);
-        rc = SD_ERR_HIP;
-    }
-    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-    if (!keep_job) s->jobs.erase(s->jobs.begin());
-    s->collect_s += now_s() - t0;
-    return rc;
+        return SD_OK;
+    });
 }
 
 // ---- SD_FLAG_DEVICE_FINAL: the final rows of a job, selected on the device ---------------------------------------
@@ -1128,11 +1210,11 @@ int sd_stream_collect_dev(sd_stream* s, sd_rec* d_rows, int64_t cap_rows, int64_
 // reads too where they lie on the device, and the post-processor of the file path computes every identity from the
 // text; the rows stay in job.fin / alt / fin_off.  Correct and slow.
 static int final_dev_slow(sd_stream* s, StreamJob& job, std::string& err) {
-    if (job.slow_done) { err = job.err; return job.rc; }
-    job.slow_done = true;
+    if (job.dfin.slow_done) { err = job.err; return job.rc; }
+    job.dfin.slow_done = true;
     FinalMode& fm = *s->fin;
-    RowsWS& ws = *job.ws;
-    FinalWS& fw = *job.fws;
+    RowsWS& ws = *job.store.ws;
+    FinalWS& fw = *job.dfin.fws;
     const size_t nr = (size_t)job.n_reads;
     const int64_t n = ws.h_total.p[0];
     std::vector<sd_rec> rows((size_t)std::max<int64_t>(n, 1));
@@ -1151,38 +1233,36 @@ static int final_dev_slow(sd_stream* s, StreamJob& job, std::string& err) {
     fw.settled = true;
     std::vector<sd::PostRead> pr;
     for (size_t r = 0; r < nr; ++r) {
-        if (job.dev) {   // the job's device copy of the reads (stream_dev_job)
-            job.seq[r].resize((size_t)job.rlen[r]);
-            SD_HIP(hipMemcpy(&job.seq[r][0], job.text->p + job.text_off[r], (size_t)job.rlen[r], hipMemcpyDeviceToHost));
-        }
+        if (job.din.dev) SD_HIP(fetch_read_text(job, r));   // (stream_dev_job made the copy)
         pr.push_back(sd::PostRead{"", 0, job.seq[r].data(), (int64_t)job.seq[r].size()});
     }
     job.rc = fm.pp.process_rows(pr.data(), nr, 0, rows.data(), off.data(), job.fin, job.alt, job.err, nullptr);
-    if (job.dev)
+    if (job.din.dev)
         for (size_t r = 0; r < nr; ++r) std::string().swap(job.seq[r]);
     if (job.rc) { err = job.err; return job.rc; }
     if (s->dev_prof)   // (process_rows folded the kept rows on the host: profile_kept)
         for (size_t i = 0; i < job.fin.n; ++i) {
             const sd_final_row& f = job.fin.p[i];
-            const int64_t rl = job.dev ? job.rlen[(size_t)f.read] : (int64_t)job.seq[(size_t)f.read].size();
+            const int64_t rl = job.din.dev ? job.din.rlen[(size_t)f.read] : (int64_t)job.seq[(size_t)f.read].size();
             if (sd::final_seg_len(f.start, f.end, rl) > 0) ++s->prof_pairs_host;
         }
-    job.fin_off.assign(nr + 1, 0);
-    for (size_t i = 0; i < job.fin.n; ++i) ++job.fin_off[(size_t)job.fin.p[i].read + 1];   // rows come in read order
-    for (size_t r = 0; r < nr; ++r) job.fin_off[r + 1] += job.fin_off[r];
+    std::vector<int64_t>& fin_off = job.dfin.fin_off;
+    fin_off.assign(nr + 1, 0);
+    for (size_t i = 0; i < job.fin.n; ++i) ++fin_off[(size_t)job.fin.p[i].read + 1];   // rows come in read order
+    for (size_t r = 0; r < nr; ++r) fin_off[r + 1] += fin_off[r];
     return SD_OK;
 }
 
 // The kept-row count of the oldest job, which has been waited for: 16 bytes from the selection, or the text-based path.
 static int final_dev_count(sd_stream* s, StreamJob& job, int64_t& n, std::string& err) {
     n = 0;
-    if (!job.assembled) return SD_OK;   // (a job without chunks: no reads)
-    RowsWS& ws = *job.ws;
-    FinalWS& fw = *job.fws;
+    if (!job.store.assembled) return SD_OK;   // (a job without chunks: no reads)
+    RowsWS& ws = *job.store.ws;
+    FinalWS& fw = *job.dfin.fws;
     SD_HIP(hipEventSynchronize(ws.ev_asm));
     ws.settled = true;
-    bool slow = !job.selected;
-    if (job.selected) {
+    bool slow = !job.dfin.selected;
+    if (job.dfin.selected) {
         SD_HIP(hipEventSynchronize(fw.ev_sel));
         fw.settled = true;
         slow = fw.h_counts.p[1] != 0;
@@ -1202,15 +1282,16 @@ static int final_dev_count(sd_stream* s, StreamJob& job, int64_t& n, std::string
 // text of those segments alone is fetched (read from job.seq for a job submitted from host memory), and profile_host
 // folds them into the post-processor's counters under the kernel.
 static int stream_prof_fold(sd_stream* s, StreamJob& job, std::string& err) {
-    FinalWS& fw = *job.fws;
+    FinalWS& fw = *job.dfin.fws;
     ProfWS& pw = fw.prof;
-    if (!pw.planned || !job.text) return SD_OK;
+    const StreamJob::DevInput& in = job.din;
+    if (!pw.planned || !in.text) return SD_OK;
     pw.planned = false;
-    if (!fw.ev_f0) SD_HIP(hipEventCreate(&fw.ev_f0));
-    if (!fw.ev_prof) SD_HIP(hipEventCreate(&fw.ev_prof));
+    ensure_event(fw.ev_f0);
+    ensure_event(fw.ev_prof);
     prof_harvest(s, fw);
     SD_HIP(hipEventRecord(fw.ev_f0, s->prof_st));
-    const int64_t nd = prof_fold(pw, s->pd, s->prof_st, job.text->p);
+    const int64_t nd = prof_fold(pw, s->pd, s->prof_st, in.text->p);
     SD_HIP(hipEventRecord(fw.ev_prof, s->prof_st));
     fw.prof_recorded = true;
     fw.fold_timed = nd > 0;
@@ -1226,13 +1307,13 @@ static int stream_prof_fold(sd_stream* s, StreamJob& job, std::string& err) {
     std::vector<const char*> q((size_t)nh);
     std::vector<int32_t> ql((size_t)nh), pil((size_t)nh);
     std::vector<char> fetched;
-    if (job.dev) {
+    if (in.dev) {
         size_t bytes = 0;
         for (int64_t x = 0; x < nh; ++x) bytes += (size_t)hp[x].len;
         fetched.resize(std::max<size_t>(bytes, 1));
         size_t at = 0;
         for (int64_t x = 0; x < nh; ++x) {
-            SD_HIP(hipMemcpyAsync(fetched.data() + at, job.text->p + hp[x].start, (size_t)hp[x].len, hipMemcpyDeviceToHost, s->slow_st));
+            SD_HIP(hipMemcpyAsync(fetched.data() + at, in.text->p + hp[x].start, (size_t)hp[x].len, hipMemcpyDeviceToHost, s->slow_st));
             q[(size_t)x] = fetched.data() + at;
             at += (size_t)hp[x].len;
         }
@@ -1240,8 +1321,8 @@ static int stream_prof_fold(sd_stream* s, StreamJob& job, std::string& err) {
         s->prof_text_to_host += (int64_t)bytes;
     } else {
         for (int64_t x = 0; x < nh; ++x) {
-            const size_t r = (size_t)(std::upper_bound(job.text_off.begin(), job.text_off.end(), hp[x].start) - job.text_off.begin()) - 1;
-            q[(size_t)x] = job.seq[r].data() + (hp[x].start - job.text_off[r]);
+            const size_t r = (size_t)(std::upper_bound(in.text_off.begin(), in.text_off.end(), hp[x].start) - in.text_off.begin()) - 1;
+            q[(size_t)x] = job.seq[r].data() + (hp[x].start - in.text_off[r]);
         }
     }
     for (int64_t x = 0; x < nh; ++x) { ql[(size_t)x] = hp[x].len; pil[(size_t)x] = hp[x].il; }
@@ -1251,126 +1332,68 @@ static int stream_prof_fold(sd_stream* s, StreamJob& job, std::string& err) {
 
 int sd_stream_peek_final_dev(sd_stream* s, int32_t* n_reads, int64_t* n_rows, int32_t* n_keys, char* errbuf, size_t errlen) {
     if (!s) return SD_ERR_PARAM;
-    if (!s->dev_final) { set_err(errbuf, errlen, "sd_stream_peek_final_dev on a stream made without SD_FLAG_DEVICE_FINAL"); return SD_ERR_PARAM; }
-    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_peek_final_dev without a submitted job"); return SD_ERR_PARAM; }
-    const double t0 = now_s();
-    int rc = stream_wait_oldest(s, errbuf, errlen);
-    if (rc == SD_OK) {
-        StreamJob& job = *s->jobs.front();
-        const int dev = s->me.devs[0];
-        int cur = -1;
-        (void)hipGetDevice(&cur);
+    return on_oldest_job(s, CALL_PEEK_FINAL_DEV, errbuf, errlen, [&](StreamJob& job, bool& keep) -> int {
         int64_t n = 0;
-        try {
-            if (cur != dev) SD_HIP(hipSetDevice(dev));
-            std::string err;
-            rc = final_dev_count(s, job, n, err);
-            if (rc) set_err(errbuf, errlen, err);
-        } catch (const HipFail& f) {
-            set_err(errbuf, errlen, f.msg);
-            rc = SD_ERR_HIP;
-        } catch (const std::bad_alloc&) {
-            set_err(errbuf, errlen, "out of host memory");
-            rc = SD_ERR_INTERNAL;
-        }
-        if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-        if (rc == SD_OK) {
-            if (n_reads) *n_reads = job.n_reads;
-            if (n_rows) *n_rows = n;
-            if (n_keys) *n_keys = (int32_t)s->fin->pp.key_names().size();
-        } else {
-            s->jobs.erase(s->jobs.begin());   // (a job whose rows cannot be made is dropped, as collect drops it)
-        }
-    }
-    s->collect_s += now_s() - t0;
-    return rc;
+        std::string err;
+        if (const int rc = final_dev_count(s, job, n, err)) { set_err(errbuf, errlen, err); return rc; }
+        keep = true;
+        if (n_reads) *n_reads = job.n_reads;
+        if (n_rows) *n_rows = n;
+        if (n_keys) *n_keys = (int32_t)s->fin->pp.key_names().size();
+        return SD_OK;
+    });
 }
 
 int sd_stream_collect_final_dev(sd_stream* s, sd_final_row* d_rows, int64_t cap_rows, int64_t* d_row_off, double* d_alt,
                                 void* hip_stream, int64_t* n_rows, char* errbuf, size_t errlen) {
     if (!s || !d_row_off || cap_rows < 0 || (cap_rows > 0 && !d_rows)) return SD_ERR_PARAM;
     if (n_rows) *n_rows = 0;
-    if (!s->dev_final) { set_err(errbuf, errlen, "sd_stream_collect_final_dev on a stream made without SD_FLAG_DEVICE_FINAL"); return SD_ERR_PARAM; }
-    if (s->jobs.empty()) { set_err(errbuf, errlen, "sd_stream_collect_final_dev without a submitted job"); return SD_ERR_PARAM; }
-    const bool sb = s->fin->second_best;
-    if (sb && cap_rows > 0 && !d_alt) { set_err(errbuf, errlen, "sd_stream_collect_final_dev: a second_best stream needs the alt buffer"); return SD_ERR_PARAM; }
-    const double t0 = now_s();
-    int rc = stream_wait_oldest(s, errbuf, errlen);
-    if (rc != SD_OK) {
-        s->collect_s += now_s() - t0;
-        return rc;
-    }
-    StreamJob& job = *s->jobs.front();
-    const int dev = s->me.devs[0];
-    const void* const bufs[3] = {cap_rows > 0 ? d_rows : nullptr, d_row_off, sb && cap_rows > 0 ? d_alt : nullptr};
-    const char* const what[3] = {"row", "row-offset", "alt"};
-    for (int b = 0; b < 3; ++b) {
-        if (!bufs[b]) continue;
-        std::string err;
-        int at = dev;
-        rc = device_pointer(bufs[b], at, err);
-        if (rc == SD_OK && at != dev) {
-            err = std::string("the ") + what[b] + " buffer lies in the memory of device " + std::to_string(at) + ", the stream runs on device " + std::to_string(dev);
-            rc = SD_ERR_UNSUPPORTED;
-        }
-        if (rc) {
-            set_err(errbuf, errlen, rc == SD_ERR_UNSUPPORTED ? err : std::string("sd_stream_collect_final_dev: the ") + what[b] + " buffer is not in device memory");
-            s->collect_s += now_s() - t0;
-            return rc;
-        }
-    }
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    bool keep_job = false;
-    try {
-        if (cur != dev) SD_HIP(hipSetDevice(dev));
+    const bool sb = s->fin && s->fin->second_best;
+    const char* no_alt = sb && cap_rows > 0 && !d_alt ? "sd_stream_collect_final_dev: a second_best stream needs the alt buffer" : nullptr;
+    return on_oldest_job(s, CALL_COLLECT_FINAL_DEV, errbuf, errlen, [&](StreamJob& job, bool& keep) -> int {
+        const void* const bufs[3] = {cap_rows > 0 ? d_rows : nullptr, d_row_off, sb && cap_rows > 0 ? d_alt : nullptr};
+        const char* const what[3] = {"row", "row-offset", "alt"};
+        for (int b = 0; b < 3; ++b)
+            if (bufs[b])
+                if (const int rc = buffer_on_device(bufs[b], s->me.devs[0], "sd_stream_collect_final_dev", what[b], errbuf, errlen)) { keep = true; return rc; }
         hipStream_t user = reinterpret_cast<hipStream_t>(hip_stream);
         int64_t n = 0;
         std::string err;
-        rc = final_dev_count(s, job, n, err);
-        if (rc) set_err(errbuf, errlen, err);
-        if (rc == SD_OK) {
-            const size_t nk = s->fin->pp.key_names().size();
-            if (n_rows) *n_rows = n;
-            if (cap_rows < n) {
-                set_err(errbuf, errlen, "sd_stream_collect_final_dev: the job has " + std::to_string(n) + " rows, the buffers room for " + std::to_string(cap_rows));
-                rc = SD_ERR_PARAM;
-                keep_job = true;
-            } else if (!job.assembled) {
-                SD_HIP(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * ((size_t)job.n_reads + 1), user));
-            } else if (job.slow_done) {
-                // the rows of the text-based path: pageable memory of the job's, so the host waits for the copies
-                if (n > 0) SD_HIP(hipMemcpyAsync(d_rows, job.fin.p, (size_t)n * sizeof(sd_final_row), hipMemcpyHostToDevice, user));
-                SD_HIP(hipMemcpyAsync(d_row_off, job.fin_off.data(), job.fin_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, user));
-                if (sb && n > 0) SD_HIP(hipMemcpyAsync(d_alt, job.alt.p, (size_t)n * nk * sizeof(double), hipMemcpyHostToDevice, user));
-                SD_HIP(hipStreamSynchronize(user));
-            } else {
-                FinalWS& fw = *job.fws;
-                SD_HIP(hipStreamWaitEvent(user, fw.ev_sel, 0));
-                final_scatter(fw, user, d_rows, cap_rows, d_row_off, sb ? d_alt : nullptr);
-                // (the scatter reads the merged-row count in the record store's workspace: the store waits for it too)
-                RowsWS& ws = *job.ws;
-                if (!ws.ev_free) SD_HIP(hipEventCreateWithFlags(&ws.ev_free, hipEventDisableTiming));
-                SD_HIP(hipEventRecord(ws.ev_free, user));
-                ws.free_recorded = true;
-                if (s->dev_prof) {
-                    rc = stream_prof_fold(s, job, err);
-                    if (rc) set_err(errbuf, errlen, err);
-                }
-            }
-            if (rc == SD_OK) s->fin->kept += n;
+        int rc = final_dev_count(s, job, n, err);
+        if (rc) { set_err(errbuf, errlen, err); return rc; }
+        const size_t nk = s->fin->pp.key_names().size();
+        if (n_rows) *n_rows = n;
+        if (cap_rows < n) {
+            set_err(errbuf, errlen, "sd_stream_collect_final_dev: the job has " + std::to_string(n) + " rows, the buffers room for " + std::to_string(cap_rows));
+            keep = true;
+            return SD_ERR_PARAM;
         }
-    } catch (const HipFail& f) {
-        set_err(errbuf, errlen, f.msg);
-        rc = SD_ERR_HIP;
-    } catch (const std::bad_alloc&) {
-        set_err(errbuf, errlen, "out of host memory");
-        rc = SD_ERR_INTERNAL;
-    }
-    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-    if (!keep_job) s->jobs.erase(s->jobs.begin());
-    s->collect_s += now_s() - t0;
-    return rc;
+        if (!job.store.assembled) {
+            SD_HIP(hipMemsetAsync(d_row_off, 0, sizeof(int64_t) * ((size_t)job.n_reads + 1), user));
+        } else if (job.dfin.slow_done) {
+            // the rows of the text-based path: pageable memory of the job's, so the host waits for the copies
+            const std::vector<int64_t>& fin_off = job.dfin.fin_off;
+            if (n > 0) SD_HIP(hipMemcpyAsync(d_rows, job.fin.p, (size_t)n * sizeof(sd_final_row), hipMemcpyHostToDevice, user));
+            SD_HIP(hipMemcpyAsync(d_row_off, fin_off.data(), fin_off.size() * sizeof(int64_t), hipMemcpyHostToDevice, user));
+            if (sb && n > 0) SD_HIP(hipMemcpyAsync(d_alt, job.alt.p, (size_t)n * nk * sizeof(double), hipMemcpyHostToDevice, user));
+            SD_HIP(hipStreamSynchronize(user));
+        } else {
+            FinalWS& fw = *job.dfin.fws;
+            SD_HIP(hipStreamWaitEvent(user, fw.ev_sel, 0));
+            final_scatter(fw, user, d_rows, cap_rows, d_row_off, sb ? d_alt : nullptr);
+            // (the scatter reads the merged-row count in the record store's workspace: the store waits for it too)
+            RowsWS& ws = *job.store.ws;
+            ensure_event(ws.ev_free, hipEventDisableTiming);
+            SD_HIP(hipEventRecord(ws.ev_free, user));
+            ws.free_recorded = true;
+            if (s->dev_prof) {
+                rc = stream_prof_fold(s, job, err);
+                if (rc) set_err(errbuf, errlen, err);
+            }
+        }
+        if (rc == SD_OK) s->fin->kept += n;
+        return rc;
+    }, no_alt);
 }
 
 int sd_stream_keys(sd_stream* s, const char** keys, int32_t cap, int32_t* n_keys) {
@@ -1406,19 +1429,14 @@ int sd_stream_profile(sd_stream* s, int32_t reset, int32_t* n_monomers, int64_t*
     sd::PostProcessor& pp = s->fin->pp;
     std::vector<unsigned long long> dc;
     if (s->dev_prof && counts) {   // device counters + host counters
-        const int dev = s->me.devs[0];
-        int cur = -1, rc = SD_OK;
-        (void)hipGetDevice(&cur);
         try {
-            if (cur != dev) SD_HIP(hipSetDevice(dev));
-            rc = stream_prof_down(s, &dc, reset != 0);
+            DeviceScope on(s->me.devs[0]);
+            if (const int rc = stream_prof_down(s, &dc, reset != 0)) return rc;
         } catch (const HipFail&) {
-            rc = SD_ERR_HIP;
+            return SD_ERR_HIP;
         } catch (const std::bad_alloc&) {
-            rc = SD_ERR_INTERNAL;
+            return SD_ERR_INTERNAL;
         }
-        if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-        if (rc) return rc;
     }
     std::vector<uint64_t> v = pp.profile(reset && counts);
     for (size_t i = 0; i < v.size() && i < dc.size(); ++i) v[i] += dc[i];
@@ -1443,24 +1461,10 @@ int sd_stream_profile_dev(sd_stream* s, int32_t reset, uint64_t* d_counts, int64
                                     std::to_string(std::max<int64_t>(cap_counts, 0)));
         return SD_ERR_PARAM;
     }
-    const int dev = s->me.devs[0];
-    {
-        std::string err;
-        int at = dev;
-        int rc = device_pointer(d_counts, at, err);
-        if (rc == SD_OK && at != dev) {
-            err = "the count buffer lies in the memory of device " + std::to_string(at) + ", the stream runs on device " + std::to_string(dev);
-            rc = SD_ERR_UNSUPPORTED;
-        }
-        if (rc) {
-            set_err(errbuf, errlen, rc == SD_ERR_UNSUPPORTED ? err : "sd_stream_profile_dev: the count buffer is not in device memory");
-            return rc;
-        }
-    }
-    int cur = -1, rc = SD_OK;
-    (void)hipGetDevice(&cur);
+    int rc = buffer_on_device(d_counts, s->me.devs[0], "sd_stream_profile_dev", "count", errbuf, errlen);
+    if (rc) return rc;
     try {
-        if (cur != dev) SD_HIP(hipSetDevice(dev));
+        DeviceScope on(s->me.devs[0]);
         hipStream_t user = reinterpret_cast<hipStream_t>(hip_stream);
         rc = stream_prof_down(s, nullptr, false);   // (the folds so far are through)
         if (rc) set_err(errbuf, errlen, "a profile fold ran out of checkpoints");
@@ -1478,12 +1482,12 @@ int sd_stream_profile_dev(sd_stream* s, int32_t reset, uint64_t* d_counts, int64
                 for (int64_t i = 0; i < total; ++i) s->h_up.p[i] = hv[(size_t)i];
                 SD_HIP(hipMemcpyAsync(s->d_up.p, s->h_up.p, nb, hipMemcpyHostToDevice, user));
                 prof_add(user, reinterpret_cast<unsigned long long*>(d_counts), s->d_up.p, total);
-                if (!s->ev_up) SD_HIP(hipEventCreateWithFlags(&s->ev_up, hipEventDisableTiming));
+                ensure_event(s->ev_up, hipEventDisableTiming);
                 SD_HIP(hipEventRecord(s->ev_up, user));
                 s->up_recorded = true;
             }
             // later folds, and the zeroing, follow the caller's copy on the stream's own stream
-            if (!s->ev_pd) SD_HIP(hipEventCreateWithFlags(&s->ev_pd, hipEventDisableTiming));
+            ensure_event(s->ev_pd, hipEventDisableTiming);
             SD_HIP(hipEventRecord(s->ev_pd, user));
             SD_HIP(hipStreamWaitEvent(s->prof_st, s->ev_pd, 0));
             if (reset) SD_HIP(hipMemsetAsync(s->pd.counts.p, 0, nb, s->prof_st));
@@ -1495,7 +1499,6 @@ int sd_stream_profile_dev(sd_stream* s, int32_t reset, uint64_t* d_counts, int64
         set_err(errbuf, errlen, "out of host memory");
         rc = SD_ERR_INTERNAL;
     }
-    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -1504,7 +1507,7 @@ int sd_stream_profile_stats(sd_stream* s, double out[4]) {
     if (s->dev_prof) {   // (the folds that have completed; a fold in flight is counted by a later call)
         for (std::unique_ptr<FinalWS>& f : s->fws_spare) prof_harvest(s, *f);
         for (std::unique_ptr<StreamJob>& j : s->jobs)
-            if (j->fws) prof_harvest(s, *j->fws);
+            if (j->dfin.fws) prof_harvest(s, *j->dfin.fws);
     }
     out[0] = (double)s->prof_pairs_dev;
     out[1] = (double)s->prof_pairs_host;
@@ -1521,7 +1524,7 @@ int sd_stream_final_stats(sd_stream* s, double out[4]) {
     out[0] = fm ? t.ident_ms : 0.0;
     out[1] = fm ? (double)t.ident_pairs : 0.0;
     // (a device-final stream runs the text-based path inside peek / collect, on the caller's thread)
-    out[2] = fm ? (double)(s->dev_final ? fm->pp.fallback_blocks : s->me.fallback_blocks) : 0.0;
+    out[2] = fm ? (double)(s->mode == StreamMode::FinalDevice ? fm->pp.fallback_blocks : s->me.fallback_blocks) : 0.0;
     out[3] = fm ? (double)fm->kept : 0.0;
     return SD_OK;
 }

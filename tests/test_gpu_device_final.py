@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import final_select_cases as fsc
+import regrow_case
 from conftest import GOLDEN
 
 from stringdecomposer_amd import formats, lib, synth
@@ -398,3 +399,37 @@ def test_modes_do_not_mix(job):
             assert (got.n_rows if kw.get("device_rows") else (len(got.rows) if kw.get("final") else got)) > 0
         finally:
             st.close()
+
+
+# ---- 4. the store and the identity words regrown behind a later batch -------------------------------------------------
+
+@pytest.fixture(scope="module")
+def regrow_host_rows():
+    """FinalRows of the host final stream for regrow_case's job, by second_best; computed on demand, once"""
+    have = {}
+
+    def get(second_best):
+        if second_best not in have:
+            mono, job = regrow_case.job()
+            st = _stream(mono, device_final=False, second_best=second_best, max_batch_rows=regrow_case.MAX_BATCH_ROWS)
+            try:
+                st.submit(job)
+                have[second_best] = st.collect()
+            finally:
+                st.close()
+        return have[second_best]
+    return get
+
+
+@pytest.mark.parametrize("source", ["host", "device"])
+@pytest.mark.parametrize("second_best", [False, True])
+def test_store_and_words_regrown_with_records_in_them(regrow_host_rows, second_best, source):
+    """regrow_case's job on a fresh stream: six chunks in six batches, and the first sizing of the store is provably too
+    small for them, so a later batch moves the records and the identity words kept so far (with second_best the
+    homopolymer words too) into larger blocks."""
+    mono, job = regrow_case.job()
+    got, stats = _one(mono, job if source == "host" else _device_reads(job), len(job), second_best=second_best,
+                      max_batch_rows=regrow_case.MAX_BATCH_ROWS)
+    assert stats["batches"] == regrow_case.n_chunks(job)
+    _same(got, regrow_host_rows(second_best))
+    assert len(got.rows) > 0 and stats["fallback_blocks"] == 0 and stats["ident_pairs"] > 0

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import regrow_case
 import seam_cases
 from conftest import load_case
 
@@ -403,3 +404,22 @@ def test_close_right_after_collect_with_the_copy_still_queued(mono, reads, defau
     s.synchronize()
     assert _lists(got) == default_rows and _lists(got_e) == default_rows
     assert other[0] == default_rows[::-1]
+
+
+# ---- 8. the store regrown behind a later batch ----------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def regrow_rows():
+    (_, ms), job = regrow_case.job()
+    return _host_rows(ms, [job])[0]
+
+
+@pytest.mark.parametrize("source", ["host", "device"])
+def test_store_regrown_with_records_in_it(regrow_rows, source):
+    """regrow_case's job on a fresh stream: six chunks in six batches, and the first sizing of the store is provably too
+    small for them, so a later batch moves the records appended so far into a larger block."""
+    (_, ms), job = regrow_case.job()
+    got, stats = _device_rows(ms, [job if source == "host" else _device_reads(job)], max_batch_rows=regrow_case.MAX_BATCH_ROWS)
+    assert stats["batches"] == regrow_case.n_chunks(job)
+    assert got == regrow_rows
+    assert len(regrow_rows[0][0]) > 0 and len(regrow_rows[0][1]) > 0
