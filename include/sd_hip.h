@@ -385,6 +385,17 @@ int sd_engine_info(sd_engine* e, int64_t info[8]);
 int sd_plan_info(const sd_params* p, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
                  int64_t info[8], char* errbuf, size_t errlen);
 
+/* Host only: the floor levels of that layout -- per read symbol A C G T N the last slot of a lane whose diagonal input needs
+ * the maximum with the start term (floor_sym), the same by previous and current read symbol (floor_pair[5 * previous +
+ * current], <= floor_sym[current]) -- and the lanes they were computed over: the templates are the monomers followed by
+ * their reverse complements, template j has the lanes lane_off[j] .. lane_off[j + 1] - 1 (lane_off: 2 * n_mono + 1 words),
+ * and lane_start[] is the first template cell of each (lane_cap words; the sum of the template lengths always suffices).
+ * info: [0] kernel family of "auto" as in sd_plan_info (generic: everything else is 0) [1] slots per lane P [2] 1 where the
+ * scoring meets the conditions of the pair levels, else floor_pair[a][b] == floor_sym[b] [3] number of lanes. */
+int sd_plan_floor_levels(const sd_params* p, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
+                         int32_t floor_sym[5], int32_t floor_pair[25], int32_t* lane_off, int32_t* lane_start, int64_t lane_cap,
+                         int64_t info[4], char* errbuf, size_t errlen);
+
 /* ---- streaming form: sequences in host memory -> rows in host memory ------------------------
  * AlignReadsSet (main.cpp:67-122) without the text: chunk table (:70-81), DP + traceback per chunk
  * (:84-102), per-read flush with chunk offsets and seam merge (:104-117).  A stream keeps up to three device

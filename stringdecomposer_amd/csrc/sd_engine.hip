@@ -1253,6 +1253,49 @@ int sd_plan_info(const sd_params* p, const char* const* mono_seqs, const int32_t
     return SD_OK;
 }
 
+// Host only: the floor levels of the narrow fills for a monomer set and scoring, and the lane layout they were computed
+// over (FastPlan::floor_sym, floor_pair, lane_bounds).
+int sd_plan_floor_levels(const sd_params* p, const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono,
+                         int32_t floor_sym[5], int32_t floor_pair[25], int32_t* lane_off, int32_t* lane_start, int64_t lane_cap,
+                         int64_t info[4], char* errbuf, size_t errlen) {
+    std::string err;
+    int rc = validate_params(p, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    if (n_mono <= 0 || !mono_seqs || !mono_lens || !floor_sym || !floor_pair || !lane_off || !lane_start || !info) {
+        set_err(errbuf, errlen, "no monomers");
+        return SD_ERR_PARAM;
+    }
+    sd_engine e;   // (host fields only, as in sd_plan_info)
+    rc = host_templates(&e, *p, mono_seqs, mono_lens, n_mono, err);
+    if (rc) { set_err(errbuf, errlen, err); return rc; }
+    sd::FastPlan& plan = e.fplan;
+    std::string why;
+    e.p = *p;
+    apply_env_overrides(e.p);
+    const bool ok = plan_fast_family(e.p, e.tseq, e.sc, true, true, plan, why);
+    for (int i = 0; i < 4; ++i) info[i] = 0;
+    for (int i = 0; i < 5; ++i) floor_sym[i] = 0;
+    for (int i = 0; i < 25; ++i) floor_pair[i] = 0;
+    for (int j = 0; j <= e.T; ++j) lane_off[j] = 0;
+    info[0] = ok ? 2 : 1;
+    if (!ok) { set_err(errbuf, errlen, why); return SD_OK; }
+    info[1] = plan.P;
+    info[2] = plan.pair_rule ? 1 : 0;
+    for (int b = 0; b < 5; ++b) floor_sym[b] = plan.floor_sym[b];
+    for (int a = 0; a < 5; ++a)
+        for (int b = 0; b < 5; ++b) floor_pair[5 * a + b] = plan.floor_pair[a][b];
+    int64_t n = 0;
+    for (int j = 0; j < e.T; ++j) {
+        const std::vector<int32_t>& bj = plan.lane_bounds[(size_t)j];
+        for (size_t u = 0; u + 1 < bj.size(); ++u, ++n)
+            if (n < lane_cap) lane_start[n] = bj[u];
+        lane_off[j + 1] = (int32_t)n;
+    }
+    info[3] = n;
+    if (n > lane_cap) { set_err(errbuf, errlen, "lane_start too small"); return SD_ERR_PARAM; }
+    return SD_OK;
+}
+
 int sd_engine_create(sd_engine** out, const sd_params* p, const char* const* mono_seqs,
                      const int32_t* mono_lens, int32_t n_mono, char* errbuf, size_t errlen) {
     if (!out) return SD_ERR_PARAM;

@@ -603,9 +603,48 @@ bool fast_plan_build(const std::vector<std::string>& tseq, ScoreArgs sc, int max
                     }
                 }
         }
-    if (getenv("SD_PLAN_DEBUG"))
+    // ... and by the PREVIOUS row's symbol a too (sd_fast_fill.hpp: "floor level by symbol pair"): a record slot q of symbol
+    // b counts only in lanes where no earlier slot holds the largest table value under a -- where one does, the old
+    // neighbour L[q-1] is already at or above the start term of the next row.  The proof needs table values >= 0, del <= 0
+    // and end offsets (L - 1) * del with del on top <= 0; elsewhere, and behind an N (whose row the proof does not use), the
+    // pair level is the level of the current symbol.
+    plan.pair_rule = plan.table_nonneg && sc.del <= 0 && !plan.filter_only;
+    for (int j = 0; j < T && plan.pair_rule; ++j) plan.pair_rule = ((int)tseq[(size_t)j].size() - 1) * sc.del + sc.del <= 0;
+    for (int a = 0; a < 5; ++a)
+        for (int b = 0; b < 5; ++b) plan.floor_pair[a][b] = plan.pair_rule && a < 4 ? 1 : plan.floor_sym[b];
+    if (plan.pair_rule) {
+        const int tmax = std::max(sc.match, sc.mismatch);   // (the table's - del - ins is common to every value)
+        for (int j = 0; j < T; ++j) {
+            const std::string& sq = tseq[(size_t)j];
+            const std::vector<int>& bj = bnd[(size_t)j];
+            for (size_t u = 0; u + 1 < bj.size(); ++u)
+                for (int b = 0; b < 5; ++b) {
+                    int run = code_of(sq[(size_t)bj[u]]) == b ? sc.match : sc.mismatch;
+                    bool top[4] = {false, false, false, false};   // symbol a met its largest table value in slots 0..q-1
+                    for (int q = 1; bj[u] + q < bj[u + 1]; ++q) {
+                        const int cp = code_of(sq[(size_t)(bj[u] + q - 1)]);
+                        for (int a = 0; a < 4; ++a) top[a] = top[a] || (cp == a ? sc.match : sc.mismatch) == tmax;
+                        const int val = code_of(sq[(size_t)(bj[u] + q)]) == b ? sc.match : sc.mismatch;
+                        if (val > run) {
+                            run = val;
+                            for (int a = 0; a < 4; ++a)
+                                if (!top[a]) plan.floor_pair[a][b] = std::max(plan.floor_pair[a][b], q);
+                        }
+                    }
+                }
+        }
+    }
+    plan.lane_bounds.assign((size_t)T, std::vector<int32_t>());
+    if (!plan.filter_only)
+        for (int j = 0; j < T; ++j) plan.lane_bounds[(size_t)j].assign(bnd[(size_t)j].begin(), bnd[(size_t)j].end());
+    if (getenv("SD_PLAN_DEBUG")) {
         std::fprintf(stderr, "[sd plan] P = %d: floor slots %d; per read symbol A C G T N: %d %d %d %d %d\n", P, plan.floor_slots,
                      plan.floor_sym[0], plan.floor_sym[1], plan.floor_sym[2], plan.floor_sym[3], plan.floor_sym[4]);
+        for (int a = 0; a < 5; ++a)
+            std::fprintf(stderr, "[sd plan]   after %c: %d %d %d %d %d%s\n", "ACGTN"[a], plan.floor_pair[a][0], plan.floor_pair[a][1],
+                         plan.floor_pair[a][2], plan.floor_pair[a][3], plan.floor_pair[a][4],
+                         a == 0 ? (plan.pair_rule ? "   (by previous and current symbol)" : "   (pair rule off: per-symbol levels)") : "");
+    }
     plan.T = T;
     plan.split = split;
     plan.Lmax = Lmax;
@@ -817,15 +856,18 @@ int64_t fast_ckpt_rows_total(const FastPlan& plan, std::vector<ChunkDesc>& chunk
 // ---------------------------------------------------------------------------------------------
 // launch: which fill kernel runs for a plan, with which geometry
 // ---------------------------------------------------------------------------------------------
-uint32_t fast_fill_hx(const FastPlan& plan, int fl, int step) {
-    uint32_t hx = plan.Hx;
-    if (step > 0)
+uint64_t fast_fill_levels(const FastPlan& plan, int fl, int step) {
+    uint64_t levels = 0;
+    if (step <= 0) return levels;
+    const bool by_symbol = getenv("SD_FILL_SYMBOL_LEVEL") != nullptr;   // developer A/B, parity test: the levels of round 6
+    for (int a = 0; a < 5; ++a)
         for (int b = 0; b < 5; ++b) {
-            uint32_t lv = 0;
-            while (lv < 3 && fl - (int)(lv + 1) * step >= std::max(1, plan.floor_sym[b])) ++lv;
-            hx |= lv << (22 + 2 * b);
+            const int need = std::max(1, by_symbol ? plan.floor_sym[b] : plan.floor_pair[a][b]);
+            uint64_t lv = 0;
+            while (lv < 3 && fl - (int)(lv + 1) * step >= need) ++lv;
+            levels |= lv << (2 * (5 * a + b));
         }
-    return hx;
+    return levels;
 }
 
 // the first floor level of the list that covers FastPlan::floor_slots and leaves two slots behind it; 0 = none

@@ -53,8 +53,7 @@ struct FastPlan {
     //   bit 10       the set has 1-bp templates (FLC_ONE: fast_has_1bp)
     //   bit 11       rebase every 64 rows instead of 128 (FastPlan::rebase)
     //   bits 16..21  with bit 8: a virtual lane that is idle in both planes
-    //   bits 22..31  0 in the plan; the u16 fills with floor levels by read symbol get two bits per symbol A C G T N there,
-    //                level l = the start-term maximum in the first FL - l * step slots (fast_fill_hx; sd_fast_fill.hpp: FLS)
+    //   bits 22..31  0 (the floor levels of the u16 fills travel in a kernel argument of their own: fast_fill_levels)
     uint32_t Hx = 0;
     int T = 0;
     int split = 0;        // templates [0,split) in the lo plane
@@ -72,6 +71,11 @@ struct FastPlan {
     int floor_slots = 0;  // last slot of a lane whose diagonal input needs the max with the start term (see sd_fast_fill)
     int floor_sym[5] = {0, 0, 0, 0, 0};   // the same per read symbol (A C G T N); floor_slots = their maximum
     bool table_nonneg = false;            // every table value (mm - del - ins) >= 0: the fills may apply the floor in place (sd_fast_fill: FLS)
+    int floor_pair[5][5] = {};            // [previous][current read symbol]: the last slot that needs the floor in a row whose neighbour above had
+                                          // symbol `previous` (<= floor_sym[current]; == floor_sym[current] on the diagonal and behind an N)
+    bool pair_rule = false;               // the conditions of the pair levels hold (table_nonneg, del <= 0, end offsets + del <= 0); else
+                                          // floor_pair[a][b] == floor_sym[b]
+    std::vector<std::vector<int32_t>> lane_bounds;   // narrow layout, per template: first cell of each of its lanes, then its length
     uint32_t bf8_match = 0, bf8_mismatch = 0;   // multi-wave wide layout: the two table values as bf8 bytes (f16) or int8 bytes (integer cells)
     std::vector<int32_t> vlane0;         // first virtual lane of template j
     std::vector<uint32_t> table;         // narrow: [5][P4/4][64][4] packed int16 (mm - del - ins), NEG on padding
@@ -230,8 +234,11 @@ struct TraceArgs {
 void launch_fast_fill(const FastPlan& plan, hipStream_t st, const FillArgs& a, size_t min_lds = 0);
 // --ed_thr, multi-wave layouts: one class of chunks (a.order, a.n_ptr) filled by wb waves holding their kept templates
 void launch_fast_fill_compact(const FastPlan& plan, hipStream_t st, const FillArgs& a, int wb);
-// the Hx of a narrow FL launch: FastPlan::Hx and, for step > 0, the floor level of every read symbol in bits 22..31
-uint32_t fast_fill_hx(const FastPlan& plan, int fl, int step);
+// the `levels` argument of a narrow FL launch with levels per row (step > 0; else 0): two bits per (previous, current) read
+// symbol at bit 2 * (5 * previous + current), level l = the start-term maximum in the first fl - l * step slots
+// (sd_fast_fill.hpp: FLS).  From FastPlan::floor_pair; with SD_FILL_SYMBOL_LEVEL set from floor_sym[current] for every
+// previous symbol (developer A/B, parity test).
+uint64_t fast_fill_levels(const FastPlan& plan, int fl, int step);
 
 // The kernels of one family at plan.P, launched by the two choosers above.
 // Narrow layout, the start-term maximum in the first fl slots of a lane only: fp16 cells (sd_fast_fl.hip: P <= 40,

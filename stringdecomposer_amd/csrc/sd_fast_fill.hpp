@@ -45,17 +45,47 @@ namespace sd {
 // sd_fast.hip only -- as a run-time branch in every kernel it cost the C2 fill 3 % (12.3 against 11.9 ms, same box)
 // FLS > 0 (round 6, u16 cells): the floor level of a template set is the maximum over the five read symbols, and single symbols
 // are often far below it (C2's set: A 16, C 15, G 10, T 6), so a ROW takes the floor in the first FL, FL - FLS, FL - 2 FLS or
-// FL - 3 FLS slots by its read symbol (Hx bits 22..31: two bits per symbol, 0 = FL).  Three copies of the slot loop behind a scalar
+// FL - 3 FLS slots by its read symbol (two bits per symbol, 0 = FL; since the pair rule below: `levels`).  Three copies of the slot loop behind a scalar
 // branch were built first and lost 13 %: the register allocator gives the three loops different registers and joins them
 // with 27 moves per row.  Instead the floors are applied IN PLACE before the one slot loop, L[q-1] = max(L[q-1], KB), two
 // scalar branches skipping the upper groups.  That also raises the "keep" operand of slot q-1 to KB, which changes nothing
 // while every table value is >= 0: S'[q-1] >= S'[0] >= KB + tbl[0] >= KB anyway (the launchers check tmin >= 0; scorings
 // whose mismatch costs more than a deletion plus an insertion take the one-level kernels).
+//
+// Floor level by symbol pair.  The level of row i+1 is looked up by the read symbols of rows i and i+1 (`levels`: 25 two-bit
+// fields at bit 2 * (5 * previous + current), a scalar shift per row; Hx bits 22..31 are free again).  A floor at slot q of
+// row i+1 does work only if (a) tbl_{i+1}[q] exceeds every earlier table value of the lane -- the criterion above -- AND
+// (b) the old neighbour L_i[q-1] is below KB_{i+1}.  (b) is ruled out where the previous symbol r_i meets the largest table
+// value tmax in some slot x <= q-1 of the lane (FastPlan::floor_pair counts a record slot only in lanes where it does not):
+//   Invariant I(i), i >= 1, stored values, every lane: if r_i has tbl_i[x] == tmax at a slot x of the lane, then
+//   L_i[q'] >= KB_i + tmax for every q' >= x.
+//   I(i) holds when every record slot of row i that (a) and (b) ask for took its floor.  Let x0 be the FIRST slot with
+//   tbl_i[x0] == tmax.  x0 == 0: slot 0's u is KB_i itself.  x0 >= 1: x0 is a record slot of r_i; either its floor was
+//   applied (in place: L_{i-1}[x0-1] := max(., KB_i), the value the slot then reads), or it was left out by (b), which is
+//   I(i-1) and step (4) below: L_{i-1}[x0-1] >= KB_{i-1} + tmax >= KB_i.  Both ways L_i[x0] >= KB_i + tmax, and the chain
+//   L_i[q'] >= L_i[q'-1] carries it on.  A floor applied in a slot that did not need it (the levels come in groups of FLS
+//   slots) only raises a stored value to KB, which the true cell max(L, K) and the chain are above anyway (table >= 0).
+//   Row 1 runs with previous symbol N = the per-symbol level (every record floor): row 0 is computed by another formula,
+//   so the induction starts with I(1); a row behind an N in the read takes the per-symbol level as well.
+//   (1) I(i) gives L_i[q-1] >= KB_i + tmax for the slots behind x.
+//   (2) The row maximum b (bdel16, stored domain: the insertion move is "keep") grows by at most tmax per row: a lane total
+//       is a_i <= max(a_{i-1}, KB_i) + tmax, and with the template's end offset e (+ del) <= 0 on every lane (FLC_ENDALL)
+//       a_{i-1} + e <= b_i, K_{i-1} + e <= b_i, b_i + e <= b_i.  This is where tmax >= 0, del <= 0 and e + del <= 0 enter.
+//   (3) The lazy carry K (exclusive prefix maximum of the totals of the template's earlier lanes; it replaces the old one
+//       without a max) grows by at most tmax too: K_i <= max(K_{i-1}, b_i) + tmax, the KB of an earlier lane being at most
+//       the KB of a later one of the same template.
+//   (4) KB_{i+1} = max(K_i, b_{i+1}) <= KB_i + tmax.
+//   (5) (1) and (4): KB_{i+1} <= L_i[q-1] -- the floor of slot q changes nothing in row i+1.
+// Rebase: K, every L and the row maximum move by the same amount in the same row group boundary, all inequalities are
+// between values of one row or of neighbouring rows read after the shift.  --ed_thr (RANKED): a dropped template's end
+// offset is "-inf" (masked out of the row maximum), which only lowers b; (2) holds for the kept templates, and the dropped
+// ones' cells are compared with the same, smaller KB.  The u16 bias is common to every term.  The plan falls back to the
+// per-symbol levels where a condition fails (FastPlan::pair_rule); SD_FILL_SYMBOL_LEVEL=1 does so for A/B runs.
 template <int P, bool RANKED, int CF, int FL = P, bool ONE = false, int FLS = 0>
 __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     const ChunkDesc* __restrict__ chunks, int n_chunks, const uint32_t* __restrict__ bases2,
     const uint32_t* __restrict__ nmask, const uint32_t* __restrict__ table,
-    const uint32_t* __restrict__ lane_consts, ScoreArgs sc, int Hx, int32_t* __restrict__ Bout,
+    const uint32_t* __restrict__ lane_consts, ScoreArgs sc, uint32_t Hx, unsigned long long levels, int32_t* __restrict__ Bout,
     int32_t* __restrict__ argV, uint32_t* __restrict__ ckpt, int32_t* __restrict__ ckbase,
     int* __restrict__ queue, const int* __restrict__ order, const uint32_t* __restrict__ cendoff,
     const uint32_t* __restrict__ crank) {
@@ -89,7 +119,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nw = (int)(blockDim.x >> 6);
     const int lane = threadIdx.x & 63;
-    (void)wave; (void)nw;
+    (void)wave; (void)nw; (void)levels;
     const int H = Hx & 0xff;                    // carry hops (FastPlan::Hx)
     const bool bperm_ok = (Hx >> 8) & 1;        // both planes segment alike and lane Hx >> 16 is idle in both
     // Issue fairness among the waves of a SIMD (FairShare, sd_fast_dev.hpp): the rows a wave still has to fill, one
@@ -180,7 +210,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     // planes) where that lane belongs to another template: the shifted operands of the scan then cost no VALU
     // instruction and need no mask (the LDS crossbar is otherwise idle in this kernel; the scan's latency hides
     // under the B reduction, which depends on the same lane totals only)
-    const int idle4 = (Hx >> 16) << 2;
+    const int idle4 = (int)(((Hx >> 16) & 63u) << 2);
     int bp1 = (contMask & 0xffffu) ? (lane - 1) << 2 : idle4;
     int bp2 = (cont2Mask & 0xffffu) ? (lane - 2) << 2 : idle4;
     asm volatile("" : "+v"(bp1), "+v"(bp2));
@@ -296,6 +326,9 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     for (int q = 1; q < P; ++q) L[q] = CO::mx(L[q - 1], CO::add(tb[q], ins2));
     }
     int rcur = rs.code(1);   // read symbol of the row the loop is about to fill
+    int rprev = 4;           // ... and of the row above it, for the floor level (FLS > 0); N = "the level of rcur alone": row 0 is
+                             // computed by another formula, the pair rule's invariant starts with row 1
+    (void)rprev;
     load_table(rcur, L[P - 1]);
     rs.advance(1);
     std::conditional_t<U16, U16Guard<P>, F16Guard<P>> guard;
@@ -389,7 +422,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 constexpr int FL3 = FL - 3 * FLS > 1 ? FL - 3 * FLS : 1;
                 constexpr int FL2 = FL - 2 * FLS > FL3 ? FL - 2 * FLS : FL3;
                 constexpr int FL1 = FL - FLS > FL2 ? FL - FLS : FL2;
-                const int lv = (Hx >> (22 + 2 * rcur)) & 3;   // scalar: the level of this row's read symbol
+                const int lv = (int)(levels >> (2 * (5 * rprev + rcur))) & 3;   // scalar: the level of this row by the previous and its own read symbol
 #pragma unroll
                 for (int q = 1; q <= FL3 && q < P; ++q) L[q - 1] = CO::mx(L[q - 1], KB);
                 if (lv <= 2) {
@@ -454,6 +487,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
             __builtin_amdgcn_sched_barrier(0);
         }
         }
+        rprev = rcur;
         rcur = rs.code(i + 1);
         load_table(rcur, L[P - 1]);  // unconditional (clamped): keeps tb[] out of phi copies
         rs.advance(i + 1);

@@ -12,10 +12,10 @@
 namespace sd {
 
 void SD_FL_ENTRY(const FastPlan& plan, hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, int fl) {
-    const uint32_t hx = fast_fill_hx(plan, fl, SD_FL_STEP);
+    const uint64_t levels = fast_fill_levels(plan, fl, SD_FL_STEP);
     with_p(FastFlLongP(), plan.P, [&](auto p) {
         with_p(FlLongLevels(), fl, [&](auto f) {
-            launch_narrow<decltype(p)::value, SD_FL_CF, decltype(f)::value, false, SD_FL_STEP>(st, a, grid, nw, lds, hx);
+            launch_narrow<decltype(p)::value, SD_FL_CF, decltype(f)::value, false, SD_FL_STEP>(st, a, grid, nw, lds, plan.Hx, levels);
         });
     });
 }

@@ -11,13 +11,13 @@ namespace sd {
 
 // narrow layout (sd_fast_fill), the RANKED form where the batch has --ed_thr ranks
 template <int P, int CF, int FL, bool ONE, int FLS>
-void launch_narrow(hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, uint32_t hx) {
+void launch_narrow(hipStream_t st, const FillArgs& a, int grid, int nw, size_t lds, uint32_t hx, uint64_t levels = 0) {
     with_bool(a.cendoff != nullptr, [&](auto rk) {
         constexpr bool RK = decltype(rk)::value;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sd_fast_fill<P, RK, CF, FL, ONE, FLS>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((sd_fast_fill<P, RK, CF, FL, ONE, FLS>), dim3(grid), dim3(nw * 64), lds, st, a.chunks, a.n_chunks,
-                           a.bases2, a.nmask, a.table, a.lane_consts, a.sc, (int)hx, a.B, a.argV, a.ckpt, a.ckbase, a.queue,
+                           a.bases2, a.nmask, a.table, a.lane_consts, a.sc, hx, levels, a.B, a.argV, a.ckpt, a.ckbase, a.queue,
                            a.order, a.cendoff, a.crank);
     });
 }

@@ -50,6 +50,7 @@ EXPORTS = [
     "sd_stream_peek_dev", "sd_stream_collect_dev", "sd_engine_rows_dev", "sd_seam_merge_dev", "sd_seam_pieces_selftest",
     "sd_stream_peek_final_dev", "sd_stream_collect_final_dev", "sd_final_select_dev", "sd_final_select_host",
     "sd_stream_profile_dev", "sd_stream_profile_stats", "sd_final_profile_dev", "sd_final_profile_host",
+    "sd_plan_floor_levels",
 ]
 
 
@@ -130,6 +131,8 @@ def load():
     L.sd_engine_timings.argtypes = [C.c_void_p, P(C.c_float)]
     L.sd_engine_info.argtypes = [C.c_void_p, P(C.c_int64)]
     L.sd_plan_info.argtypes = [P(Params), P(C.c_char_p), P(C.c_int32), C.c_int32, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_plan_floor_levels.argtypes = [P(Params), P(C.c_char_p), P(C.c_int32), C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                       P(C.c_int32), C.c_int64, P(C.c_int64), C.c_char_p, C.c_size_t]
     L.sd_chunk_plan.restype = C.c_int32
     L.sd_chunk_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, P(C.c_int64), P(C.c_int32), C.c_int32]
     L.sd_seam_merge.restype = C.c_int32
@@ -310,6 +313,29 @@ def plan_info(mono_seqs, **kw):
             "floor_slots": v[3], "waves": v[4] & 0xff, "range_bound": (v[4] >> 8) & 0xffffffff, "rebase": v[4] >> 40, "min_first_lane_cells": v[5], "max_lane_cells": v[6],
             "score_factor": v[7] & 0xffff, "trace_regs": (v[7] >> 16) & 0xff, "trace_bound": (v[7] >> 24) & 0xffffffff,
             "bperm_scan": bool((v[7] >> 56) & 1), "why": err.value.decode(errors="replace") if v[0] == 1 else ""}
+
+
+def plan_floor_levels(mono_seqs, **kw):
+    """The floor levels of the narrow fills for this monomer set and scoring (host only, no GPU needed; sd_plan_floor_levels):
+    {"family", "cells_per_lane", "pair_rule" (the scoring meets the conditions of the levels by symbol pair), "floor_sym"
+    [5] (read symbols A C G T N), "floor_pair" [previous][current], "lane_starts" (per template -- the monomers, then their
+    reverse complements -- the first cell of each of its lanes), "why"}; family "generic" carries the reason in "why"."""
+    L = load()
+    p = make_params(**kw)
+    ms = [_b(s) for s in mono_seqs]
+    ml = (C.c_int32 * max(len(ms), 1))(*[len(s) for s in ms])
+    T, cap = 2 * len(ms), 2 * sum(len(s) for s in ms) + 1
+    sym, pair = (C.c_int32 * 5)(), (C.c_int32 * 25)()
+    off, start = (C.c_int32 * (T + 1))(), (C.c_int32 * cap)()
+    v = (C.c_int64 * 4)()
+    err = C.create_string_buffer(4096)
+    rc = L.sd_plan_floor_levels(C.byref(p), _strs(ms), ml, len(ms), sym, pair, off, start, cap, v, err, 4096)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace"))
+    return {"family": {1: "generic", 2: "fast"}[v[0]], "cells_per_lane": v[1], "pair_rule": bool(v[2]),
+            "floor_sym": list(sym), "floor_pair": [list(pair[5 * a:5 * a + 5]) for a in range(5)],
+            "lane_starts": [list(start[off[j]:off[j + 1]]) for j in range(T)],
+            "why": err.value.decode(errors="replace") if v[0] == 1 else ""}
 
 
 def release_cache():
