@@ -609,6 +609,66 @@ int sd_final_profile_host(const char* text, const int64_t* read_off, int32_t n_r
                           const uint8_t* keep, const char* const* templates, const int32_t* tlen, int32_t T, int32_t device,
                           int32_t threads, uint64_t* counts, int64_t pairs[2]);
 
+/* ---- the TSV text of device rows, formatted on the device (csrc/sd_text_dev.hip) -------------------------------------
+ * The last link of the device chain: the bytes of final_decomposition.tsv / _alt.tsv from the rows of
+ * sd_stream_collect_final_dev, and of _raw.tsv from the rows of sd_stream_collect_dev / sd_engine_rows_dev, written into
+ * DEVICE buffers of the caller's.  The bytes are those of the existing formatters (sd_format_rows for a raw row; the
+ * twelve columns of main.py:153-160 and the six of :161-165, identities with "%.2f", "None" for key -1, '+' / '?', '*' /
+ * '-'); csrc/sd_text_dev.hpp is their one text for the kernels and the _host calls below.
+ *
+ * Name tables.  An sd_text_tables holds the read names of a job (n_reads of them, the job's reads in submit order) and
+ * the column names -- the keys of sd_stream_keys for final rows (n_cols = n_keys; "None" is added by the library), the
+ * DP templates (monomers, then monomers + "'") for raw rows -- as byte strings plus offsets.  Creating one touches no
+ * device; the first _dev call uploads it to that call's device, later calls reuse the upload (another device:
+ * SD_ERR_PARAM), so a caller formatting many jobs of the same reads and monomers uploads once.  The object also owns
+ * the small scratch of the size calls (tile sums, counters, 32 pinned bytes): calls on one object take turns, and
+ * nothing is allocated per call once its buffers have grown.  The destroy call waits for the last write call's kernels.
+ *
+ * Two calls per job, both enqueued on hip_stream (NULL = the null stream) of `device`:
+ *   1. the size call: a length pass over the rows, an exclusive int64 scan, and the positions --
+ *      d_row_pos[n_rows + 1] (where the text of row i begins; for _alt: d_alt_pos, where the n_keys lines of final row
+ *      i begin), d_read_pos[n_reads + 1] (where the text of read r begins: row_pos[row_off[r]]; _alt: d_alt_read_pos),
+ *      and for raw rows d_row_read[n_rows] (the read of every row) -- all DEVICE scratch of the caller's, which the
+ *      write call reads.  The host waits for 32 bytes and nothing else: *final_bytes / *alt_bytes (*text_bytes), the
+ *      count of unprintable identities and the count of failed checks.
+ *   2. the write call, with text buffers of exactly those sizes: returns without waiting; work enqueued on hip_stream
+ *      afterwards sees the text.  Nothing is written at or behind final_bytes / alt_bytes / text_bytes.  rows, alt and
+ *      the positions must be what the size call saw.
+ * d_alt NULL (a job without second_best): no _alt text, d_alt_pos / d_alt_read_pos / d_alt_text are ignored.
+ * Checked by the host before any kernel runs (SD_ERR_PARAM): NULL arguments, n_keys != the table's n_cols, a buffer that
+ * is not device memory (SD_ERR_UNSUPPORTED: of another device, as in sd_stream_collect_dev).  Checked by the length
+ * pass, which follows no index it has not checked, so before any byte of text is written (the size call returns
+ * SD_ERR_PARAM): a read, key or template index outside its table, a final row outside its read's rows, row offsets that
+ * do not rise from 0 to n_rows.  An identity that is infinite, NaN or >= 2^40 in size is printed by snprintf on the host;
+ * the device counts it and the size call returns SD_ERR_UNSUPPORTED (no row the library produces holds one).
+ * Without a device: SD_ERR_NO_DEVICE.  Every offset is 64-bit; a text of more than 4 GB per call is not tested. */
+typedef struct sd_text_tables sd_text_tables;
+int sd_text_tables_create(sd_text_tables** out, const char* const* read_names, int32_t n_reads, const char* const* col_names,
+                          int32_t n_cols, char* errbuf, size_t errlen);
+void sd_text_tables_destroy(sd_text_tables* t);
+int sd_text_final_size_dev(sd_text_tables* t, const sd_final_row* d_rows, int64_t n_rows, const int64_t* d_row_off, const double* d_alt,
+                           int32_t n_keys, int32_t device, void* hip_stream, int64_t* d_row_pos, int64_t* d_alt_pos,
+                           int64_t* d_read_pos, int64_t* d_alt_read_pos, int64_t* final_bytes, int64_t* alt_bytes, char* errbuf,
+                           size_t errlen);
+int sd_text_final_write_dev(sd_text_tables* t, const sd_final_row* d_rows, int64_t n_rows, const double* d_alt, int32_t n_keys,
+                            int32_t device, void* hip_stream, const int64_t* d_row_pos, const int64_t* d_alt_pos, char* d_final_text,
+                            int64_t final_bytes, char* d_alt_text, int64_t alt_bytes, char* errbuf, size_t errlen);
+int sd_text_raw_size_dev(sd_text_tables* t, const sd_rec* d_rows, int64_t n_rows, const int64_t* d_row_off, int32_t device,
+                         void* hip_stream, int32_t* d_row_read, int64_t* d_row_pos, int64_t* d_read_pos, int64_t* text_bytes,
+                         char* errbuf, size_t errlen);
+int sd_text_raw_write_dev(sd_text_tables* t, const sd_rec* d_rows, int64_t n_rows, const int64_t* d_row_off, int32_t device,
+                          void* hip_stream, const int32_t* d_row_read, const int64_t* d_row_pos, char* d_text, int64_t text_bytes,
+                          char* errbuf, size_t errlen);
+/* The same text from HOST arrays on `threads` host threads, without a device: *final_text / *alt_text / *text are
+ * malloc'ed (sd_free) and hold *final_bytes / *alt_bytes / *text_bytes bytes; row_pos, alt_pos (n_rows + 1), read_pos
+ * and alt_read_pos (n_reads + 1) may be NULL, else they are filled as the size calls fill theirs.  alt NULL: no _alt
+ * text.  The same checks (SD_ERR_PARAM, nothing returned); unprintable identities are printed by snprintf. */
+int sd_text_final_host(sd_text_tables* t, const sd_final_row* rows, int64_t n_rows, const int64_t* row_off, const double* alt,
+                       int32_t n_keys, int32_t threads, char** final_text, int64_t* final_bytes, char** alt_text, int64_t* alt_bytes,
+                       int64_t* row_pos, int64_t* alt_pos, int64_t* read_pos, int64_t* alt_read_pos, char* errbuf, size_t errlen);
+int sd_text_raw_host(sd_text_tables* t, const sd_rec* rows, int64_t n_rows, const int64_t* row_off, int32_t threads, char** text,
+                     int64_t* text_bytes, int64_t* row_pos, int64_t* read_pos, char* errbuf, size_t errlen);
+
 /* ---- a stream on several devices of this process ----------------------------------------------------------------
  * sd_stream_create / sd_stream_create_final with a device list: one batch pipeline per entry of devices[0 .. n_devices)
  * (repeats allowed, as in sd_run_files_devices; p->device is ignored).  1 <= n_devices <= 16; every ordinal must exist

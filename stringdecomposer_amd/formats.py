@@ -149,7 +149,11 @@ def final_rows(final, read_names, keys):
     a lib.DeviceFinalRows of a device_final stream is copied to the host first)
     as the command line would write them: ([FinalRow], [AltRow]) -- format_final / format_alt of these are the text of
     <out>.tsv / <out>_alt.tsv.  read_names: the job's reads in submit order; keys: Stream.keys().  The _alt list is
-    empty without second_best (alt None)."""
+    empty without second_best (alt None).
+
+    This is the host route, a Python loop over every row and key.  The same bytes without it: lib.format_final_device /
+    Stream.collect_final_text_device format a DeviceFinalRows on its device (lib.format_raw_device / collect_text_device:
+    a DeviceRows), lib.format_final_host / format_raw_host are the compiled host twin."""
     if hasattr(final, "n_rows") and hasattr(final.rows, "cpu"):   # a lib.DeviceFinalRows: copied to the host first
         final = final.to_host()
     rows, _, alt = final

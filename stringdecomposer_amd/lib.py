@@ -51,6 +51,8 @@ EXPORTS = [
     "sd_stream_peek_final_dev", "sd_stream_collect_final_dev", "sd_final_select_dev", "sd_final_select_host",
     "sd_stream_profile_dev", "sd_stream_profile_stats", "sd_final_profile_dev", "sd_final_profile_host",
     "sd_plan_floor_levels",
+    "sd_text_tables_create", "sd_text_tables_destroy", "sd_text_final_size_dev", "sd_text_final_write_dev",
+    "sd_text_raw_size_dev", "sd_text_raw_write_dev", "sd_text_final_host", "sd_text_raw_host",
 ]
 
 
@@ -244,6 +246,18 @@ def load():
             C.c_int32, C.c_int32, C.c_void_p, P(C.c_int64)]
     L.sd_final_profile_dev.argtypes = prof
     L.sd_final_profile_host.argtypes = prof
+    V, I64 = C.c_void_p, C.c_int64
+    L.sd_text_tables_create.argtypes = [P(V), P(C.c_char_p), C.c_int32, P(C.c_char_p), C.c_int32, C.c_char_p, C.c_size_t]
+    L.sd_text_tables_destroy.argtypes = [V]
+    L.sd_text_tables_destroy.restype = None
+    L.sd_text_final_size_dev.argtypes = [V, V, I64, V, V, C.c_int32, C.c_int32, V, V, V, V, V, P(I64), P(I64), C.c_char_p,
+                                         C.c_size_t]
+    L.sd_text_final_write_dev.argtypes = [V, V, I64, V, C.c_int32, C.c_int32, V, V, V, V, I64, V, I64, C.c_char_p, C.c_size_t]
+    L.sd_text_raw_size_dev.argtypes = [V, V, I64, V, C.c_int32, V, V, V, V, P(I64), C.c_char_p, C.c_size_t]
+    L.sd_text_raw_write_dev.argtypes = [V, V, I64, V, C.c_int32, V, V, V, V, I64, C.c_char_p, C.c_size_t]
+    L.sd_text_final_host.argtypes = [V, V, I64, V, V, C.c_int32, C.c_int32, P(V), P(I64), P(V), P(I64), V, V, V, V,
+                                     C.c_char_p, C.c_size_t]
+    L.sd_text_raw_host.argtypes = [V, V, I64, V, C.c_int32, P(V), P(I64), V, V, C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -830,6 +844,200 @@ class DeviceProfile(namedtuple("DeviceProfile", "counts offsets names seqs")):
         return formats.profile_from_counts(self.names, self.seqs, self.counts.cpu().numpy())
 
 
+class DeviceText(namedtuple("DeviceText", "text row_pos read_pos")):
+    """TSV text that stays in device memory (format_final_device / format_raw_device): text = a uint8 torch tensor of
+    exactly the text's length, row_pos = int64 [n_rows + 1] (where the text of row i begins; for the _alt text: where the
+    n_keys lines of final row i begin), read_pos = int64 [n_reads + 1] (where the text of read r begins), all on the rows'
+    device."""
+    __slots__ = ()
+
+    def to_bytes(self):
+        """The text copied to the host."""
+        return self.text.cpu().numpy().tobytes()
+
+
+class TextTables:
+    """The name tables of the text calls (sd_text_tables): the read names of a job in submit order and the column
+    names -- Stream.keys() for final rows, the DP's template names (monomers, then monomers + "'") for raw rows.  Uploaded
+    to the device by the first format_*_device call that uses them and reused by later ones; close() waits for the last
+    of those calls' kernels."""
+
+    def __init__(self, read_names, col_names):
+        self.L = load()
+        self.n_reads, self.n_cols = len(read_names), len(col_names)
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        rc = self.L.sd_text_tables_create(C.byref(self.h), _strs(read_names), self.n_reads, _strs(col_names), self.n_cols,
+                                          err, 1024)
+        if rc != SD_OK:
+            raise SdError(rc, err.value.decode(errors="replace"))
+
+    def close(self):
+        if self.h:
+            self.L.sd_text_tables_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _text_check(rc, err):
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace"))
+
+
+def _text_tables(tables, read_names, col_names):
+    """(tables, own): the caller's, or fresh ones this call closes"""
+    if tables is not None:
+        if tables.n_reads != len(read_names) or tables.n_cols != len(col_names):
+            raise SdError(SD_ERR_PARAM, "tables: %d reads and %d columns, the call has %d and %d"
+                          % (tables.n_reads, tables.n_cols, len(read_names), len(col_names)))
+        return tables, False
+    return TextTables(read_names, col_names), True
+
+
+def format_final_device(dfr, read_names, keys, stream=None, tables=None):
+    """The text of final_decomposition.tsv / _alt.tsv of a DeviceFinalRows, formatted on its device (sd_text_final_size_dev
+    / sd_text_final_write_dev) -> (final, alt): DeviceText, alt None for rows without second_best.  read_names: the job's
+    reads in submit order; keys: Stream.keys(); tables: a TextTables over the same names, to upload them once for many
+    jobs.  torch allocates the tensors on `stream` (Stream.collect_final_device's convention) and the library fills them
+    there: the host waits for the text's size only, and work enqueued on the stream afterwards sees the text."""
+    import torch
+    L = load()
+    dev = dfr.row_off.device
+    st = _torch_stream(torch, dev, stream)
+    n, nr, nk = int(dfr.n_rows), len(read_names), len(keys)
+    if dfr.row_off.shape[0] != nr + 1:
+        raise SdError(SD_ERR_PARAM, "format_final_device: %d read names for %d reads" % (nr, dfr.row_off.shape[0] - 1))
+    has_alt = dfr.alt is not None
+    t, own = _text_tables(tables, read_names, keys)
+    err = C.create_string_buffer(1024)
+    ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)   # noqa: E731
+    try:
+        with torch.cuda.stream(st):
+            row_pos = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            read_pos = torch.empty(nr + 1, dtype=torch.int64, device=dev)
+            alt_pos = torch.empty(n + 1, dtype=torch.int64, device=dev) if has_alt else None
+            alt_read_pos = torch.empty(nr + 1, dtype=torch.int64, device=dev) if has_alt else None
+        # (an empty alt still means "with _alt text": a pointer that is not NULL)
+        alt_ptr = C.c_void_p((dfr.alt.data_ptr() if n and nk else alt_pos.data_ptr()) if has_alt else 0)
+        fb, ab = C.c_int64(), C.c_int64()
+        _text_check(L.sd_text_final_size_dev(t.h, ptr(dfr.rows), n, ptr(dfr.row_off), alt_ptr, nk, dev.index or 0,
+                                             C.c_void_p(st.cuda_stream), ptr(row_pos), ptr(alt_pos), ptr(read_pos),
+                                             ptr(alt_read_pos), C.byref(fb), C.byref(ab), err, 1024), err)
+        with torch.cuda.stream(st):
+            ftext = torch.empty(fb.value, dtype=torch.uint8, device=dev)
+            atext = torch.empty(ab.value, dtype=torch.uint8, device=dev) if has_alt else None
+        _text_check(L.sd_text_final_write_dev(t.h, ptr(dfr.rows), n, alt_ptr, nk, dev.index or 0, C.c_void_p(st.cuda_stream),
+                                              ptr(row_pos), ptr(alt_pos), ptr(ftext), fb.value, ptr(atext), ab.value, err, 1024),
+                    err)
+    finally:
+        if own:
+            t.close()
+    return DeviceText(ftext, row_pos, read_pos), (DeviceText(atext, alt_pos, alt_read_pos) if has_alt else None)
+
+
+def format_raw_device(drows, read_names, tmpl_names, stream=None, tables=None):
+    """The text of _raw.tsv of a DeviceRows, formatted on its device (sd_text_raw_size_dev / sd_text_raw_write_dev) ->
+    DeviceText.  tmpl_names: the DP's templates (monomers, then monomers + "'"); the rest as format_final_device."""
+    import torch
+    L = load()
+    dev = drows.row_off.device
+    st = _torch_stream(torch, dev, stream)
+    n, nr = int(drows.n_rows), len(read_names)
+    if drows.row_off.shape[0] != nr + 1:
+        raise SdError(SD_ERR_PARAM, "format_raw_device: %d read names for %d reads" % (nr, drows.row_off.shape[0] - 1))
+    t, own = _text_tables(tables, read_names, tmpl_names)
+    err = C.create_string_buffer(1024)
+    ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)   # noqa: E731
+    try:
+        with torch.cuda.stream(st):
+            row_pos = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            read_pos = torch.empty(nr + 1, dtype=torch.int64, device=dev)
+            row_read = torch.empty(n, dtype=torch.int32, device=dev)
+        nb = C.c_int64()
+        _text_check(L.sd_text_raw_size_dev(t.h, ptr(drows.rows), n, ptr(drows.row_off), dev.index or 0, C.c_void_p(st.cuda_stream),
+                                           ptr(row_read), ptr(row_pos), ptr(read_pos), C.byref(nb), err, 1024), err)
+        with torch.cuda.stream(st):
+            text = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        _text_check(L.sd_text_raw_write_dev(t.h, ptr(drows.rows), n, ptr(drows.row_off), dev.index or 0, C.c_void_p(st.cuda_stream),
+                                            ptr(row_read), ptr(row_pos), ptr(text), nb.value, err, 1024), err)
+    finally:
+        if own:
+            t.close()
+    return DeviceText(text, row_pos, read_pos)
+
+
+def _take_text(L, p, n):
+    out = C.string_at(p, n.value) if p.value and n.value else b""
+    L.sd_free(p)
+    return out
+
+
+def format_final_host(final_rows, read_names, keys, threads=1, positions=False):
+    """The host twin of format_final_device (sd_text_final_host: the same source text, compiled for the host) on a
+    FinalRows or its (rows, row_off, alt) -> (final bytes, alt bytes or None).  positions=True: ((bytes, row_pos,
+    read_pos), (bytes, alt_pos, alt_read_pos) or None), the arrays of a DeviceText as numpy."""
+    import numpy as np
+    L = load()
+    rows, row_off, alt = final_rows
+    rows = np.ascontiguousarray(rows, dtype=final_dtype())
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+    n, nr, nk = len(rows), len(read_names), len(keys)
+    if len(row_off) != nr + 1:
+        raise SdError(SD_ERR_PARAM, "format_final_host: %d read names for %d reads" % (nr, len(row_off) - 1))
+    if alt is not None:
+        alt = np.ascontiguousarray(alt, dtype=np.float64).reshape(-1)
+        if len(alt) != n * nk:
+            raise SdError(SD_ERR_PARAM, "format_final_host: alt is not n_rows x n_keys")
+        alt = np.concatenate([alt, np.zeros(1)])   # (never NULL, also without rows)
+    pos = [np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64), np.zeros(nr + 1, dtype=np.int64),
+           np.zeros(nr + 1, dtype=np.int64)]
+    t = TextTables(read_names, keys)
+    err = C.create_string_buffer(1024)
+    ft, at, fb, ab = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
+    try:
+        rc = L.sd_text_final_host(t.h, rows.ctypes.data, n, row_off.ctypes.data, None if alt is None else alt.ctypes.data, nk,
+                                  int(threads), C.byref(ft), C.byref(fb), C.byref(at), C.byref(ab), pos[0].ctypes.data,
+                                  pos[1].ctypes.data, pos[2].ctypes.data, pos[3].ctypes.data, err, 1024)
+        _text_check(rc, err)
+        ftext, atext = _take_text(L, ft, fb), _take_text(L, at, ab)
+    finally:
+        t.close()
+    if positions:
+        return (ftext, pos[0], pos[2]), (None if alt is None else (atext, pos[1], pos[3]))
+    return ftext, (None if alt is None else atext)
+
+
+def format_raw_host(rows, row_off, read_names, tmpl_names, threads=1, positions=False):
+    """The host twin of format_raw_device (sd_text_raw_host) on rows ([n, 4] int32: tmpl, start, end, score, or a
+    structured sd_rec array) and row_off -> bytes; positions=True: (bytes, row_pos, read_pos)."""
+    import numpy as np
+    L = load()
+    rows = np.ascontiguousarray(rows)
+    if rows.dtype != _rec_dtype():
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 4)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+    n, nr = len(rows), len(read_names)
+    if len(row_off) != nr + 1:
+        raise SdError(SD_ERR_PARAM, "format_raw_host: %d read names for %d reads" % (nr, len(row_off) - 1))
+    row_pos, read_pos = np.zeros(n + 1, dtype=np.int64), np.zeros(nr + 1, dtype=np.int64)
+    t = TextTables(read_names, tmpl_names)
+    err = C.create_string_buffer(1024)
+    tx, nb = C.c_void_p(), C.c_int64()
+    try:
+        rc = L.sd_text_raw_host(t.h, rows.ctypes.data if n else None, n, row_off.ctypes.data, int(threads), C.byref(tx),
+                                C.byref(nb), row_pos.ctypes.data, read_pos.ctypes.data, err, 1024)
+        _text_check(rc, err)
+        text = _take_text(L, tx, nb)
+    finally:
+        t.close()
+    return (text, row_pos, read_pos) if positions else text
+
+
 def _torch_stream(torch, dev, stream):
     """stream=None: the current stream of the device (DeviceReads' convention); an int: that hipStream_t; else a
     torch stream."""
@@ -975,6 +1183,7 @@ class Stream:
             kw["flags"] = int(kw.get("flags", 0)) | FLAG_DEVICE_PROFILE
         self.device_rows = bool(device_rows)
         self.device_final = bool(device_final)
+        self.mono_names = None if mono_names is None else [n if isinstance(n, str) else n.decode() for n in mono_names]
         self.params = make_params(**kw)
         self._err = C.create_string_buffer(4096)
         ms = [_b(s) for s in mono_seqs]
@@ -1145,6 +1354,25 @@ class Stream:
                                                        C.c_void_p(st.cuda_stream), C.byref(got), self._err, 4096))
         self._n_reads.pop(0)
         return DeviceFinalRows(rows, row_off, alt, int(got.value))
+
+    def collect_final_text_device(self, read_names, stream=None, tables=None):
+        """collect_final_device() and format_final_device() of its rows on the same stream -> (rows, (final, alt)): a
+        DeviceFinalRows and its text as DeviceText (alt None without second_best).  read_names: the job's reads in submit
+        order."""
+        dfr = self.collect_final_device(stream=stream)
+        return dfr, format_final_device(dfr, read_names, self.keys(), stream=stream, tables=tables)
+
+    def collect_text_device(self, read_names, stream=None, tables=None):
+        """collect_device() and format_raw_device() of its rows on the same stream -> (rows, text): a DeviceRows and the
+        text of its _raw.tsv as a DeviceText.  The template names come from the stream's mono_names."""
+        drows = self.collect_device(stream=stream)
+        return drows, format_raw_device(drows, read_names, self.tmpl_names(), stream=stream, tables=tables)
+
+    def tmpl_names(self):
+        """Column 2 of the raw TSV by template index: the monomer names, then the same names with "'"."""
+        if self.mono_names is None:
+            raise SdError(SD_ERR_PARAM, "the raw text needs the monomer names: Stream(..., mono_names=...)")
+        return self.mono_names + [n + "'" for n in self.mono_names]
 
     def _collect_final(self):
         import numpy as np
