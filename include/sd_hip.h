@@ -853,6 +853,78 @@ int sd_profile_segments(const char* seq, int64_t seqlen, const int64_t* starts, 
 int sd_profile_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends,
                             int64_t n_seg, const char* const* tmpl, const int32_t* tlen, int32_t T,
                             const int32_t* pair_tmpl, int32_t device, int32_t threads, uint64_t* counts);
+/* ---- one row per instance (--msa): the same alignment, not summed ------------------------------------------------
+ * The per-instance counterpart of the profile: the row of a pair (segment, interleaved template il) against the
+ * FORWARD monomer il >> 1 of length L, SD_MSA_PITCH(L) bytes:
+ *   [0, L)       per forward position g: 0..4 = the read base aligned there (A C G T N), SD_MSA_DEL = the position is
+ *                deleted, SD_MSA_NONE = the pair is no instance or was not computed
+ *   [L, 2L + 1)  per insertion slot g = 0..L: the read bases inserted before position g, saturating at 255
+ *   padding      0, up to a multiple of 16 bytes
+ * A pair against rc(m) lands reversed and complemented, exactly as in the profile (position p at L-1-p, slot h at L-h).
+ * Per pair a status byte: 0 = no instance (an empty side), 1 = computed, 2 = left out by a device-resident call (the row
+ * is then SD_MSA_NONE / 0).  The rows of a job, summed per monomer, are its profile: columns 0..6 exactly, and the
+ * inserted bases as one number (the sum of columns 7..11) wherever no count saturated. */
+#define SD_MSA_DEL 5
+#define SD_MSA_NONE 7
+#define SD_MSA_PITCH(L) ((2 * (L) + 1 + 15) & ~15)
+
+/* row_at[0 .. n_seg]: where the row of each pair begins when the rows lie back to back in the pairs' order (tlen / T:
+ * the FORWARD monomers, pair_tmpl: interleaved).  Returns the total bytes (row_at[n_seg]), or -SD_ERR_PARAM for a
+ * template out of range. */
+int64_t sd_msa_row_offsets(const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int64_t n_seg, int64_t* row_at);
+/* The arguments of sd_profile_segments[_dev]; rows (sd_msa_row_offsets' total bytes), row_at (n_seg + 1) and status
+ * (n_seg) are overwritten.  Host threads (sd_msa_segments: every pair, any length, any byte alphabet -- a read byte
+ * outside ACGT counts as N) or the device (sd_msa_segments_dev: the row kernel of csrc/sd_msa.hip, and under it the host
+ * form for the pairs it does not take -- a set with a monomer over 512 bp, segments over 1024 bp, pairs edlib splits, a
+ * text outside ACGTN).  Every status is 0 or 1 and the two calls give the same bytes. */
+int sd_msa_segments(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                    const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int32_t threads,
+                    uint8_t* rows, int64_t* row_at, uint8_t* status);
+int sd_msa_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                        const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int32_t device,
+                        int32_t threads, uint8_t* rows, int64_t* row_at, uint8_t* status);
+
+/* Developer entry (tools/msa_bench.py): the arguments of sd_msa_segments_dev; on the pairs the row kernel takes, the row
+ * kernel and the profile kernel run warmup + reps times in turn, each launch between two HIP events: ms_msa[reps],
+ * ms_profile[reps]; info = K, grid, work items, pairs, LDS bytes of the row kernel, rows staged in LDS (1) or written
+ * through (0), LDS bytes of the profile kernel, checkpoint slots per lane.  SD_ERR_UNSUPPORTED when no pair is the kernels'. */
+int sd_msa_kernel_bench(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                        const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int32_t device,
+                        int32_t warmup, int32_t reps, float* ms_msa, float* ms_profile, int64_t info[8]);
+
+/* ---- the rows of a device-final job, device to device ----------------------------------------------------------------
+ * The last link of the chain sd_stream_submit_dev -> sd_stream_collect_final_dev: the final rows in HBM and the reads'
+ * text in HBM give the rows of --msa in the caller's device buffers, in the manner of sd_text_final_size_dev /
+ * sd_text_final_write_dev.  An sd_msa_tables holds what does not change between jobs: key_il[k] = the interleaved
+ * template that key k (sd_stream_keys) names -- a key must name ONE template, so a set with a repeated monomer name has
+ * no such table -- and the FORWARD monomers; the first size pass uploads them to its device.  The object also owns the
+ * plan between a size pass and its write pass, so the two are called in pairs, one pair at a time per object; a size
+ * pass waits for the object's previous write pass.  Destroy waits for the last write pass.
+ *
+ * sd_msa_final_size_dev: d_rows[0 .. n_rows) as sd_stream_collect_final_dev delivers them; d_text / read_off / read_lens
+ * (host arrays, n_reads each) as sd_stream_submit_dev takes them: read r is d_text[read_off[r] .. + read_lens[r]), complete
+ * on hip_stream.  On hip_stream: the reads are copied back to back into the object's own text, one kernel plans each
+ * row's pair -- the segment the selection measured (csrc/sd_final_prof_dev.hpp: final_prof_pair, the same clamp and
+ * limits) against the row's own template keys[best] -- and the pitches are scanned into d_row_at (n_rows + 1, the
+ * caller's).  *total_bytes and classes[3] = rows that are no instance (status 0), pairs of the row kernel (status 1),
+ * pairs the kernel does not take (a set with a monomer over 512 bp, a segment over 1024 bp, a pair edlib splits: status 2)
+ * come to the host: the only wait.  SD_ERR_PARAM for a row whose read or key index lies outside its table.
+ * sd_msa_final_write_dev (same d_rows, n_rows, device): groups the kernel's pairs by forward monomer on the device
+ * (csrc/sd_final_prof_dev.hip) and runs the row kernel (csrc/sd_msa.hip) into d_out (cap bytes, 16-byte aligned) at
+ * d_row_at, with d_status (n_rows); rows of status 0 and 2 are filled with SD_MSA_NONE / 0 -- counted, never guessed
+ * (sd_msa_segments on the host computes them).  Everything is ordered on hip_stream and nothing waits on the host.
+ * cap < *total_bytes: SD_ERR_PARAM with the exact size in the message, nothing written.  Buffers that are not device
+ * memory: SD_ERR_PARAM; another device's: SD_ERR_UNSUPPORTED. */
+typedef struct sd_msa_tables sd_msa_tables;
+int sd_msa_tables_create(sd_msa_tables** out, const int32_t* key_il, int32_t n_keys, const char* const* mono_seqs,
+                         const int32_t* mono_lens, int32_t n_mono, char* errbuf, size_t errlen);
+void sd_msa_tables_destroy(sd_msa_tables* t);
+int sd_msa_final_size_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t n_rows, const void* d_text, const int64_t* read_off,
+                          const int64_t* read_lens, int32_t n_reads, int32_t device, void* hip_stream, int64_t* d_row_at,
+                          int64_t* total_bytes, int64_t classes[3], char* errbuf, size_t errlen);
+int sd_msa_final_write_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t n_rows, int32_t device, void* hip_stream,
+                           const int64_t* d_row_at, uint8_t* d_out, int64_t cap, uint8_t* d_status, char* errbuf, size_t errlen);
+
 /* The profile of the last successful sd_run_files* call of this process made with SD_FLAG_PROFILE (summed over its
  * device entries).  Every output may be NULL: *n_monomers, *n_counts and *text_bytes size the buffers of a second
  * call.  text: "name\tsequence\n" per monomer in FASTA order, NUL-terminated (text_bytes counts the NUL); counts as

@@ -213,6 +213,21 @@ void ProfDev::setup(const std::vector<std::string>& il, const std::vector<int32_
     SD_HIP(hipStreamSynchronize(st));   // (the vectors above leave)
 }
 
+void prof_group(ProfWS& w, int M, hipStream_t st, int64_t cap, const int64_t* n_ptr) {
+    hipLaunchKernelGGL(sd::sd_fprof_scan, dim3(1), dim3(64), 0, st, w.sum.p, M, w.base.p, w.cursor.p);
+    if (cap > 0)
+        hipLaunchKernelGGL(sd::sd_fprof_scatter, dim3(fprof_grid(cap)), dim3(sd::FPROF_T), 0, st, w.cls.p, w.pair_il.p, w.seg_start.p,
+                           w.seg_len.p, n_ptr, cap, M, w.cursor.p, w.order.p, w.hlist.p);
+    SD_HIP(hipGetLastError());
+}
+
+void prof_items(ProfWS& w, int M, int per, int64_t n_items, hipStream_t st, bool clear) {
+    w.items.alloc((size_t)n_items);
+    if (clear) SD_HIP(hipMemsetAsync(w.items.p, 0, (size_t)std::max<int64_t>(n_items, 1) * sizeof(int4), st));
+    hipLaunchKernelGGL(sd::sd_fprof_items, dim3((unsigned)M), dim3(64), 0, st, w.base.p, M, per, w.items.p, (int)n_items);
+    SD_HIP(hipGetLastError());
+}
+
 void prof_plan(ProfWS& w, const ProfDev& d, hipStream_t st, const sd::DevRec* recs, const int64_t* src, const uint8_t* keep,
                const int64_t* moff, const int64_t* rlen, int32_t n_reads, int64_t cap_rows, const int64_t* n_ptr) {
     const int64_t cap = std::max<int64_t>(cap_rows, 0);
@@ -234,11 +249,7 @@ void prof_plan(ProfWS& w, const ProfDev& d, hipStream_t st, const sd::DevRec* re
                         (int)d.own_il.n, d.tmax, M, w.seg_start.p, w.seg_len.p, w.pair_il.p, w.cls.p, w.sum.p};
         hipLaunchKernelGGL(sd::sd_fprof_plan, dim3(fprof_grid(cap)), dim3(sd::FPROF_T), 0, st, a);
     }
-    hipLaunchKernelGGL(sd::sd_fprof_scan, dim3(1), dim3(64), 0, st, w.sum.p, M, w.base.p, w.cursor.p);
-    if (rows)
-        hipLaunchKernelGGL(sd::sd_fprof_scatter, dim3(fprof_grid(cap)), dim3(sd::FPROF_T), 0, st, w.cls.p, w.pair_il.p, w.seg_start.p,
-                           w.seg_len.p, n_ptr, cap, M, w.cursor.p, w.order.p, w.hlist.p);
-    SD_HIP(hipGetLastError());
+    prof_group(w, M, st, rows ? cap : 0, n_ptr);
     SD_HIP(hipMemcpyAsync(w.h_sum.p, w.sum.p, ((size_t)M + 2) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     w.planned = true;
 }
@@ -266,8 +277,7 @@ int64_t prof_fold(ProfWS& w, ProfDev& d, hipStream_t st, const uint8_t* text) {
         SD_HIP(hipStreamSynchronize(st));
         d.ck.alloc(need);
     }
-    w.items.alloc((size_t)n_items);
-    hipLaunchKernelGGL(sd::sd_fprof_items, dim3((unsigned)M), dim3(64), 0, st, w.base.p, M, per, w.items.p, (int)n_items);
+    prof_items(w, M, per, n_items, st, false);
     sd::launch_nw_profile(K, st, grid, lds, text, w.seg_start.p, w.seg_len.p, w.order.p, w.pair_il.p, w.items.p, (int)n_items,
                           d.peq.p, d.tlen.p, d.poff.p, cap, d.ck.p, d.ckpos.p, d.counts.p, d.fails());
     SD_HIP(hipGetLastError());

@@ -49,6 +49,12 @@ struct ProfWS {
 // (n_reads + 1), rlen and w.text_off per read (w.text_off uploaded on st before).  Leaves the summary on its way to w.h_sum.
 void prof_plan(ProfWS& w, const ProfDev& d, hipStream_t st, const sd::DevRec* recs, const int64_t* src, const uint8_t* keep,
                const int64_t* moff, const int64_t* rlen, int32_t n_reads, int64_t cap, const int64_t* n_ptr);
+// The grouping alone, on a plan already in w (cls, pair_il, seg_start, seg_len per row and the counts w.sum[0 .. M)): the
+// scan of the monomer counts and, over rows [0, min(*n_ptr, cap)), the scatter into w.order / w.hlist (cap 0: the scan only).
+void prof_group(ProfWS& w, int M, hipStream_t st, int64_t cap, const int64_t* n_ptr);
+// w.items[0 .. n_items) = the work items of up to `per` pairs from w.base.  clear: n_items is an upper bound taken without
+// the counts -- the entries behind the last item are empty items (no pair).
+void prof_items(ProfWS& w, int M, int per, int64_t n_items, hipStream_t st, bool clear);
 // The work items and the fold on st, sized from w.h_sum (the host has seen the plan end).  text: the job's text on the
 // device, readable up to the next multiple of 4 past its end.  Returns the pairs folded.  Grows d.ck after waiting for st.
 int64_t prof_fold(ProfWS& w, ProfDev& d, hipStream_t st, const uint8_t* text);

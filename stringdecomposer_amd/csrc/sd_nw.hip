@@ -92,7 +92,7 @@ void launch_nw_pairs(int K, hipStream_t st, int grid, const uint8_t* seq, const 
 #undef SD_NW
 }
 
-// Column profiles (--profile): the walk of sd_nw_pairs with every step counted (nw_pair<K, Query, true>).  A work item is
+// Column profiles (--profile): the walk of sd_nw_pairs with every step counted (nw_pair<K, Query, NwProf>).  A work item is
 // up to `per` pairs of ONE forward monomer -- the host groups the pairs by monomer -- and a one-wave workgroup (the kept rows
 // of a batch are only tens of thousands of pairs: waves, not workgroups of 256, spread them over the CUs) keeps that monomer's
 // counters in LDS ((L + 1) x 12 dwords, 8.3 KB at 171 bp) and adds them to the global 64-bit counters once per item:
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64) void sd_nw_profile(const uint8_t* __restrict__ 
             NwQueryAscii q{seq, seg_start[sg]};
             NwProf pr{cnt, L, rc != 0};
             int d = 0, mm = 0;
-            if (!nw_pair<K, NwQueryAscii, true>(q, seg_len[sg], reinterpret_cast<const uint2*>(smem + rc * 5 * K), L, false, ckl,
+            if (!nw_pair<K, NwQueryAscii, NwProf>(q, seg_len[sg], reinterpret_cast<const uint2*>(smem + rc * 5 * K), L, false, ckl,
                                                 ckp, (size_t)64, cap, d, mm, &pr))
                 atomicAdd(fails, 1);
         }

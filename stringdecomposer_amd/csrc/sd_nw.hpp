@@ -54,6 +54,32 @@ void launch_nw_profile(int K, hipStream_t st, int grid, size_t lds, const uint8_
                        const int32_t* seg_len, const int32_t* order, const int32_t* pair_il, const int4* items, int n_items,
                        const unsigned long long* peq, const int32_t* tlen, const int64_t* off, int cap, void* ck, int* ckpos,
                        unsigned long long* counts, int* fails);
+// Rows of --msa (include/sd_hip.h: SD_MSA_PITCH; sd_msa.hpp).  msa_row_offsets: row_at[0 .. n] for pairs of interleaved
+// templates pair_il over forward lengths tlen[0 .. T) -> total bytes, -1 for a template out of range.  msa_host
+// (sd_post.hip): pair x's row at rows + at[x], status[x] 0 / 1.  nw_msa_device (sd_msa.hip): the split of
+// nw_profile_device; rows and status of every segment cleared by the caller, row_at holds n_seg + 1 offsets.
+int64_t msa_row_offsets(const int32_t* tlen, int32_t T, const int32_t* pair_il, int64_t n, int64_t* row_at);
+int msa_host(const char* const* q, const int32_t* qlen, const int32_t* pair_il, int64_t n, const std::vector<std::string>& il,
+             int threads, uint8_t* rows, const int64_t* at, uint8_t* status);
+// bench (sd_msa_kernel_bench): before the rows are made, the row kernel and the profile kernel run warmup + reps times
+// in turn on the kernel's pairs, each between two HIP events; info = K, grid, items, pairs, LDS bytes of the row kernel,
+// rows staged (1) or written through (0), LDS bytes of the profile kernel, checkpoint slots.
+struct MsaBench {
+    int warmup, reps;
+    float* ms_msa;
+    float* ms_profile;
+    int64_t* info;
+};
+int nw_msa_device(const char* seq, int64_t seqlen, const int64_t* seg_start, const int32_t* seg_len, int64_t n_seg,
+                  const std::vector<std::string>& il, const int32_t* pair_il, int device, int threads, uint8_t* rows,
+                  const int64_t* row_at, uint8_t* status, const MsaBench* bench = nullptr);
+// The row kernel alone (sd_nw_msa<K>): the items, order[] and checkpoints of launch_nw_profile; tmax sizes the LDS
+// (nw_msa_lds_bytes; *stage = rows staged in LDS); a pair's row goes to out + row_at[segment], its status byte becomes 1.
+size_t nw_msa_lds_bytes(int K, int tmax, int* stage);
+void launch_nw_msa(int K, hipStream_t st, int grid, int tmax, const uint8_t* seq, const int64_t* seg_start, const int32_t* seg_len,
+                   const int32_t* order, const int32_t* pair_il, const int4* items, int n_items, const unsigned long long* peq,
+                   const int32_t* tlen, int cap, void* ck, int* ckpos, uint8_t* out, const int64_t* row_at, uint8_t* status,
+                   int* fails);
 // accumulated over the device identity calls of the process: preparation + staging, uploads, kernel, downloads
 void nw_stage_seconds(double out[4]);
 

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "sd_nw.hpp"
 
@@ -127,7 +128,7 @@ struct NwQueryPacked {
     }
 };
 
-// Sink of the profile variant of nw_pair (PROF = true): the walk's steps of one pair, folded into the counters of its
+// Sink of the profile variant of nw_pair (Sink = NwProf): the walk's steps of one pair, folded into the counters of its
 // forward monomer (include/sd_hip.h: SD_PROFILE_COLS per slot) -- cnt in LDS, one workgroup's privatised copy.  A pair
 // against rc(m): position p -> L-1-p, insertion slot h -> L-h, bases complemented.  The walk meets the insertions of a
 // slot consecutively (the row only decreases), so `last` is enough to count each instance once per slot.
@@ -152,12 +153,15 @@ struct NwProf {
 // x (PvL, PvH, MvL, MvH) of word b of slot s at ck[((s * K + b) * 4 + x) * ckstride] -- planar dwords, so that a
 // wave's store is 256 contiguous bytes AND the four components need not sit in consecutive registers (as one 16-byte
 // store per word they cost a dozen register moves per column to keep them there); ckpos[s * ckstride]; `cap` slots.
-// Returns false when the pair needs more than `cap` checkpoints (nothing computed).  PROF: every step of the walk also
-// goes to *prof (homo must be false: a profile counts read bases).
-template <int K, class Query, bool PROF = false>
+// Returns false when the pair needs more than `cap` checkpoints (nothing computed).  Sink (NwNoSink: none): every step of
+// the walk also goes to *prof -- diag(p, base), del(p), ins(slot, base) as NwProf has them (homo must be false: a sink
+// sees read bases).
+struct NwNoSink {};
+template <int K, class Query, class Sink = NwNoSink>
 __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restrict__ eqt, int tl, bool homo,
                                         uint32_t* __restrict__ ck, int* __restrict__ ckpos, size_t ckstride, int cap,
-                                        int& dist_out, int& matches_out, NwProf* prof = nullptr) {
+                                        int& dist_out, int& matches_out, Sink* prof = nullptr) {
+    constexpr bool PROF = !std::is_same<Sink, NwNoSink>::value;
     constexpr int S = nw_block_cols(K);
     const int pad = 64 * K - tl;           // padding rows below the template
     auto init = [&](NwState<K>& s) {

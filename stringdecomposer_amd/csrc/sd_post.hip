@@ -13,6 +13,7 @@
 
 #include "../../include/sd_hip.h"
 #include "sd_host.hpp"
+#include "sd_msa.hpp"
 #include "sd_nw.hpp"
 
 namespace {
@@ -330,6 +331,17 @@ void fold_path(const std::vector<uint8_t>& ops, const char* q, int L, bool rc, u
         }
     }
 }
+// The same path -> the pair's own row (sd_msa.hpp; row cleared by the caller): the steps of fold_path through MsaRow.
+void fold_path_msa(const std::vector<uint8_t>& ops, const char* q, int L, bool rc, uint8_t* row) {
+    MsaRow r{row, L, rc};
+    int i = 0, j = 0;
+    for (uint8_t op : ops) {
+        if (op == 2) { r.del(j++); continue; }
+        const int b = prof_code(q[i++]);
+        if (op == 1) r.ins(j, b);
+        else r.diag(j++, b);
+    }
+}
 }  // namespace
 
 int profile_host(const char* const* q, const int32_t* qlen, const int32_t* pair_il, int64_t n,
@@ -383,6 +395,55 @@ int profile_host(const char* const* q, const int32_t* qlen, const int32_t* pair_
     for (const std::vector<uint64_t>& a : part)
         for (int64_t i = 0; i < total; ++i) counts[i] += a[(size_t)i];
     return SD_OK;
+}
+
+// Rows of --msa on the host: pair x's row at rows + at[x] (cleared here), status[x] = 1 where it was computed and 0 for
+// an empty side.  Every pair, any length (Hirschberg's split where edlib takes it), any byte alphabet.
+int msa_host(const char* const* q, const int32_t* qlen, const int32_t* pair_il, int64_t n, const std::vector<std::string>& il_seq,
+             int threads, uint8_t* rows, const int64_t* at, uint8_t* status) {
+    const size_t M = il_seq.size() / 2;
+    for (int64_t x = 0; x < n; ++x) {
+        if (pair_il[x] < 0 || (size_t)pair_il[x] >= 2 * M) return SD_ERR_PARAM;
+        if (qlen[x] > SD_NW_HOST_MAX) return SD_ERR_UNSUPPORTED;
+    }
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads, n / 16 + 1));
+    std::atomic<int64_t> next{0};
+    std::atomic<int> bad{0};
+    auto work = [&]() {
+        BitNW nw;
+        std::vector<uint8_t> ops;
+        nw.ops = &ops;
+        for (;;) {
+            const int64_t x = next.fetch_add(1);
+            if (x >= n) break;
+            const int il = pair_il[x];
+            const std::string& t = il_seq[(size_t)il];
+            const int ql = qlen[x], tl = (int)t.size();
+            uint8_t* row = rows + at[x];
+            msa_row_clear(row, (int)il_seq[(size_t)(il & ~1)].size());
+            status[x] = MSA_ST_NONE;
+            if (ql <= 0 || tl <= 0) continue;   // no alignment (main.py:30-33): not an instance
+            ops.clear();
+            int32_t m = 0;
+            if (!edlib_splits(ql, tl)) {
+                nw.traceback(q[x], ql, t.data(), tl, m);
+            } else {
+                std::vector<int32_t> col;
+                nw.column_scores(q[x], ql, t.data(), tl, col);
+                if (!nw.path(q[x], ql, t.data(), tl, col[(size_t)ql], m)) { bad = 1; continue; }
+            }
+            fold_path_msa(ops, q[x], tl, (il & 1) != 0, row);
+            status[x] = MSA_ST_DONE;
+        }
+    };
+    if (nt == 1) {
+        work();
+    } else {
+        std::vector<std::thread> th;
+        for (int k = 0; k < nt; ++k) th.emplace_back(work);
+        for (auto& x : th) x.join();
+    }
+    return bad ? SD_ERR_INTERNAL : SD_OK;
 }
 
 }  // namespace sd
@@ -441,6 +502,73 @@ extern "C" int sd_profile_segments_dev(const char* seq, int64_t seqlen, const in
                                        const int32_t* pair_tmpl, int32_t device, int32_t threads, uint64_t* counts) {
     if (device < 0) return SD_ERR_PARAM;
     return profile_segments_impl(seq, seqlen, starts, ends, n_seg, tmpl, tlen, T, pair_tmpl, device, threads, counts);
+}
+
+
+// ---- rows of --msa: the same pairs, one row each (sd_msa.hpp) ----
+extern "C" int64_t sd_msa_row_offsets(const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int64_t n_seg, int64_t* row_at) {
+    if (n_seg < 0 || T < 1 || !tlen || !row_at || (n_seg && !pair_tmpl)) return -(int64_t)SD_ERR_PARAM;
+    const int64_t total = sd::msa_row_offsets(tlen, T, pair_tmpl, n_seg, row_at);
+    return total < 0 ? -(int64_t)SD_ERR_PARAM : total;
+}
+
+static int msa_segments_impl(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                             const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int32_t device,
+                             int32_t threads, uint8_t* rows, int64_t* row_at, uint8_t* status, const sd::MsaBench* bench = nullptr) {
+    if (n_seg < 0 || T < 1 || !seq || !tmpl || !tlen || !row_at || (n_seg && (!starts || !ends || !pair_tmpl || !rows || !status)))
+        return SD_ERR_PARAM;
+    std::vector<std::string> il;
+    int rc = profile_templates(tmpl, tlen, T, il);
+    if (rc) return rc;
+    std::vector<int64_t> st((size_t)n_seg);
+    std::vector<int32_t> ln((size_t)n_seg);
+    for (int64_t s = 0; s < n_seg; ++s) {
+        if (starts[s] < 0 || ends[s] >= seqlen || pair_tmpl[s] < 0 || pair_tmpl[s] >= 2 * T) return SD_ERR_PARAM;
+        const int64_t l = std::max<int64_t>(0, ends[s] - starts[s] + 1);
+        if (l > SD_NW_HOST_MAX) return SD_ERR_UNSUPPORTED;
+        st[(size_t)s] = starts[s];
+        ln[(size_t)s] = (int32_t)l;
+    }
+    if (sd::msa_row_offsets(tlen, T, pair_tmpl, n_seg, row_at) < 0) return SD_ERR_PARAM;
+    if (device >= 0) {
+        for (int64_t s = 0; s < n_seg; ++s) {
+            sd::msa_row_clear(rows + row_at[s], tlen[pair_tmpl[s] >> 1]);
+            status[s] = sd::MSA_ST_NONE;
+        }
+        return sd::nw_msa_device(seq, seqlen, st.data(), ln.data(), n_seg, il, pair_tmpl, device, threads, rows, row_at, status, bench);
+    }
+    std::vector<const char*> qp((size_t)n_seg);
+    for (int64_t s = 0; s < n_seg; ++s) qp[(size_t)s] = seq + st[(size_t)s];
+    return sd::msa_host(qp.data(), ln.data(), pair_tmpl, n_seg, il, threads, rows, row_at, status);
+}
+
+extern "C" int sd_msa_segments(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                               const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl, int32_t threads,
+                               uint8_t* rows, int64_t* row_at, uint8_t* status) {
+    return msa_segments_impl(seq, seqlen, starts, ends, n_seg, tmpl, tlen, T, pair_tmpl, -1, threads, rows, row_at, status);
+}
+
+extern "C" int sd_msa_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                                   const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl,
+                                   int32_t device, int32_t threads, uint8_t* rows, int64_t* row_at, uint8_t* status) {
+    if (device < 0) return SD_ERR_PARAM;
+    return msa_segments_impl(seq, seqlen, starts, ends, n_seg, tmpl, tlen, T, pair_tmpl, device, threads, rows, row_at, status);
+}
+
+extern "C" int sd_msa_kernel_bench(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                                   const char* const* tmpl, const int32_t* tlen, int32_t T, const int32_t* pair_tmpl,
+                                   int32_t device, int32_t warmup, int32_t reps, float* ms_msa, float* ms_profile, int64_t info[8]) {
+    if (device < 0 || warmup < 0 || reps < 1 || !ms_msa || !ms_profile || !info || n_seg < 1 || T < 1 || !tlen || !pair_tmpl)
+        return SD_ERR_PARAM;
+    std::memset(info, 0, 8 * sizeof(int64_t));
+    std::vector<int64_t> at((size_t)n_seg + 1);
+    const int64_t total = sd::msa_row_offsets(tlen, T, pair_tmpl, n_seg, at.data());
+    if (total < 0) return SD_ERR_PARAM;
+    std::vector<uint8_t> rows((size_t)total + 1), status((size_t)n_seg);
+    const sd::MsaBench b{warmup, reps, ms_msa, ms_profile, info};
+    const int rc = msa_segments_impl(seq, seqlen, starts, ends, n_seg, tmpl, tlen, T, pair_tmpl, device, 1, rows.data(), at.data(),
+                                     status.data(), &b);
+    return rc ? rc : (info[3] > 0 ? SD_OK : SD_ERR_UNSUPPORTED);   // (no pair for the kernels: nothing was timed)
 }
 
 

@@ -21,6 +21,13 @@ Two more text files are this package's own (opt-in, `--profile`):
                       Instances of m' are folded into m (reverse-complemented).  read_profile / write_profile below.
   <out>_consensus.fa  one record per monomer, ">name instances=n", the consensus of its profile (consensus below).
 
+  <out>_msa.tsv       (`--msa`) one line per row of <out>.tsv, in its order, behind a header line: read, start, end,
+                      monomer (as printed there), columns (one character per position of the FORWARD monomer over
+                      ACGTN-: the read base aligned there, '-' a deleted position; '.' throughout for a row that is no
+                      instance), insertions ("slot:count,..." -- count read bases inserted before position slot, 255
+                      meaning 255 or more -- or '.').  Instances of m' are reverse-complemented onto m, as in the
+                      profile, so the lines of one monomer are a multiple alignment.  read_msa / write_msa below.
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -423,3 +430,132 @@ def format_consensus(prof):
 def write_consensus(path, prof):
     with open(path, "w") as f:
         f.write(format_consensus(prof))
+
+
+# ---- one row per instance (--msa) ------------------------------------------------------------------------------------
+MSA_DEL, MSA_NONE = 5, 7            # SD_MSA_DEL, SD_MSA_NONE (include/sd_hip.h)
+MSA_COLUMNS = ("A", "C", "G", "T", "N", "del", "ins_n", "ins_bases")
+MSA_HEADER = "read\tstart\tend\tmonomer\tcolumns\tinsertions\n"
+_MSA_CHARS = "ACGTN-?."             # the column byte -> its character ('.' = MSA_NONE)
+# rows: the flat bytes of the C-ABI (uint8), row_at: n + 1 offsets, status: n bytes (0 no instance, 1 computed, 2 left
+# out by a device-resident call), tlen: the lengths of the FORWARD monomers.  Pair i against interleaved template il
+# owns rows[row_at[i]:row_at[i + 1]]: tlen[il >> 1] column bytes, then tlen[il >> 1] + 1 insertion counts, then padding.
+Msa = namedtuple("Msa", "rows row_at status tlen")
+MsaRow = namedtuple("MsaRow", "read start end monomer columns insertions")   # a line of <out>_msa.tsv; insertions: ((slot, count), ...)
+
+
+def msa_pitch(L):
+    """SD_MSA_PITCH: the bytes of a row of a monomer of L bases."""
+    return (2 * int(L) + 1 + 15) & ~15
+
+
+def msa_row(msa, i, il):
+    """(columns [L], insertions [L + 1]) of pair i (uint8 views)."""
+    L = int(msa.tlen[int(il) >> 1])
+    at = int(msa.row_at[i])
+    return msa.rows[at:at + L], msa.rows[at + L:at + 2 * L + 1]
+
+
+def msa_matrix(msa, pair_tmpl, m):
+    """The [n, L] column matrix of monomer m's computed rows (either orientation), in the pairs' order."""
+    import numpy as np
+    L = int(msa.tlen[m])
+    pick = [i for i, il in enumerate(pair_tmpl) if int(il) >> 1 == m and int(msa.status[i]) == 1]
+    out = np.zeros((len(pick), L), dtype=np.uint8)
+    for k, i in enumerate(pick):
+        out[k] = msa_row(msa, i, pair_tmpl[i])[0]
+    return out
+
+
+def msa_counts(msa, pair_tmpl, n_mono):
+    """The computed rows summed per monomer: a list of int64 [L + 1, 8] arrays (MSA_COLUMNS) -- columns 0..6 are those
+    of the job's profile, ins_bases the sum of its columns 7..11 wherever no row's count saturated."""
+    import numpy as np
+    out = [np.zeros((int(msa.tlen[m]) + 1, len(MSA_COLUMNS)), dtype=np.int64) for m in range(n_mono)]
+    for i, il in enumerate(pair_tmpl):
+        if int(msa.status[i]) != 1:
+            continue
+        c = out[int(il) >> 1]
+        col, ins = msa_row(msa, i, il)
+        L = len(col)
+        np.add.at(c, (np.arange(L), col.astype(np.int64)), 1)
+        c[:, 6] += ins > 0
+        c[:, 7] += ins
+    return out
+
+
+def msa_rows(msa, pair_tmpl, meta):
+    """The lines of <out>_msa.tsv: meta = (read, start, end, monomer) per pair."""
+    out = []
+    for i, (il, (read, start, end, monomer)) in enumerate(zip(pair_tmpl, meta)):
+        col, ins = msa_row(msa, i, il)
+        if int(msa.status[i]) != 1:
+            out.append(MsaRow(read, int(start), int(end), monomer, "." * len(col), ()))
+            continue
+        out.append(MsaRow(read, int(start), int(end), monomer, "".join(_MSA_CHARS[v] for v in col.tolist()),
+                          tuple((g, v) for g, v in enumerate(ins.tolist()) if v)))
+    return out
+
+
+def msa_from_rows(rows, mono_names, mono_lens):
+    """The inverse of msa_rows: lines of <out>_msa.tsv -> (Msa, pair_tmpl).  A name with a trailing ' is the reverse
+    complement's: its line is already on the forward monomer."""
+    import numpy as np
+    idx = {}
+    for m, n in enumerate(mono_names):
+        idx[n], idx[n + "'"] = 2 * m, 2 * m + 1
+    pt = [idx[r.monomer] for r in rows]
+    at = np.zeros(len(rows) + 1, dtype=np.int64)
+    for i, il in enumerate(pt):
+        at[i + 1] = at[i] + msa_pitch(mono_lens[il >> 1])
+    data = np.zeros(int(at[-1]), dtype=np.uint8)
+    status = np.zeros(len(rows), dtype=np.uint8)
+    for i, (r, il) in enumerate(zip(rows, pt)):
+        L = int(mono_lens[il >> 1])
+        if len(r.columns) != L:
+            raise ValueError("row %d: %d columns for a monomer of %d bases" % (i, len(r.columns), L))
+        o = int(at[i])
+        data[o:o + L] = [_MSA_CHARS.index(ch) for ch in r.columns]
+        status[i] = 0 if r.columns == "." * L and L > 0 else 1
+        for g, v in r.insertions:
+            data[o + L + g] = v
+    return Msa(data, at, status, [int(x) for x in mono_lens]), pt
+
+
+def format_msa(rows, header=True):
+    return (MSA_HEADER if header else "") + "".join("%s\t%d\t%d\t%s\t%s\t%s\n" % (
+        r.read, r.start, r.end, r.monomer, r.columns, ",".join("%d:%d" % x for x in r.insertions) or ".") for r in rows)
+
+
+def write_msa(path, rows):
+    with open(path, "w") as f:
+        f.write(format_msa(rows))
+
+
+def _msa_ins(x):
+    if x == ".":
+        return ()
+    out = []
+    for item in x.split(","):
+        g, v = item.split(":")
+        out.append((int(g), int(v)))
+    return tuple(out)
+
+
+def read_msa(path):
+    """<out>_msa.tsv -> [MsaRow]."""
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            if lineno == 1 and line == MSA_HEADER:
+                continue
+            x = line.rstrip("\n").split("\t")
+            if len(x) != 6:
+                raise FormatError(path, lineno, "expected 6 columns, got %d" % len(x))
+            try:
+                if x[4].strip("ACGTN-") and x[4] != "." * len(x[4]):
+                    raise ValueError("columns must be over ACGTN- or all '.', found %r" % x[4])
+                out.append(MsaRow(x[0], int(x[1]), int(x[2]), x[3], x[4], _msa_ins(x[5])))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out

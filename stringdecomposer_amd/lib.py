@@ -53,6 +53,8 @@ EXPORTS = [
     "sd_plan_floor_levels",
     "sd_text_tables_create", "sd_text_tables_destroy", "sd_text_final_size_dev", "sd_text_final_write_dev",
     "sd_text_raw_size_dev", "sd_text_raw_write_dev", "sd_text_final_host", "sd_text_raw_host",
+    "sd_msa_row_offsets", "sd_msa_segments", "sd_msa_segments_dev", "sd_msa_tables_create", "sd_msa_tables_destroy",
+    "sd_msa_final_size_dev", "sd_msa_final_write_dev", "sd_msa_kernel_bench",
 ]
 
 
@@ -211,6 +213,24 @@ def load():
                                       P(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     L.sd_profile_segments_dev.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_char_p),
                                           P(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    L.sd_msa_row_offsets.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    L.sd_msa_row_offsets.restype = C.c_int64
+    L.sd_msa_segments.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_char_p),
+                                  P(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sd_msa_segments_dev.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_char_p),
+                                      P(C.c_int32), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+    L.sd_msa_kernel_bench.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_char_p), P(C.c_int32),
+                                      C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float),
+                                      P(C.c_int64)]
+    L.sd_msa_tables_create.argtypes = [P(C.c_void_p), C.c_void_p, C.c_int32, P(C.c_char_p), P(C.c_int32), C.c_int32, C.c_char_p,
+                                       C.c_size_t]
+    L.sd_msa_tables_destroy.argtypes = [C.c_void_p]
+    L.sd_msa_tables_destroy.restype = None
+    L.sd_msa_final_size_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_msa_final_write_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_char_p, C.c_size_t]
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
@@ -458,6 +478,225 @@ def profile_segments(seq, starts, ends, templates, pair_tmpl, threads=1, device=
     if rc != SD_OK:
         raise SdError(rc, "sd_profile_segments" + ("" if device is None else "_dev"))
     return formats.split_counts([len(t) for t in tb], counts.astype(np.int64))
+
+
+def msa_row_offsets(tlen, pair_tmpl):
+    """sd_msa_row_offsets: where the row of each pair begins (n + 1 offsets; the last is the total bytes); tlen = the
+    lengths of the FORWARD monomers, pair_tmpl interleaved."""
+    import numpy as np
+    L = load()
+    tl = np.ascontiguousarray(tlen, dtype=np.int32)
+    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
+    at = np.zeros(len(pt) + 1, dtype=np.int64)
+    rc = L.sd_msa_row_offsets(tl.ctypes.data, len(tl), pt.ctypes.data, len(pt), at.ctypes.data)
+    if rc < 0:
+        raise SdError(int(-rc), "sd_msa_row_offsets")
+    return at
+
+
+def msa_segments(seq, starts, ends, templates, pair_tmpl, threads=1, device=None):
+    """One row per pair (sd_msa_segments[_dev]; include/sd_hip.h: SD_MSA_PITCH), the arguments of profile_segments:
+    segment seq[starts[s] .. ends[s]] against monomer pair_tmpl[s] >> 1, its reverse complement when pair_tmpl[s] & 1 ->
+    formats.Msa(rows, row_at, status, tlen).  device=None: host threads; device=<ordinal>: the HIP kernel, with the
+    host form for the pairs it does not take -- the same bytes."""
+    import numpy as np
+    from . import formats
+    L = load()
+    sb = _b(seq)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
+    n = int(st.shape[0])
+    if en.shape[0] != n or pt.shape[0] != n:
+        raise SdError(SD_ERR_PARAM, "msa_segments: starts, ends and pair_tmpl differ in length")
+    tb = [_b(t) for t in templates]
+    T = len(tb)
+    if n and (T < 1 or int(pt.min()) < 0 or int(pt.max()) >= 2 * T):
+        raise SdError(SD_ERR_PARAM, "msa_segments: pair_tmpl outside the %d interleaved templates" % (2 * T))
+    tl = (C.c_int32 * max(T, 1))(*[len(t) for t in tb])
+    lens = [len(t) for t in tb]
+    total = sum(formats.msa_pitch(lens[int(p) >> 1]) for p in pt.tolist())
+    rows = np.zeros(max(total, 1), dtype=np.uint8)
+    row_at = np.zeros(n + 1, dtype=np.int64)
+    status = np.zeros(max(n, 1), dtype=np.uint8)
+    if device is None:
+        rc = L.sd_msa_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data, int(threads),
+                               rows.ctypes.data, row_at.ctypes.data, status.ctypes.data)
+    else:
+        rc = L.sd_msa_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data,
+                                   int(device), int(threads), rows.ctypes.data, row_at.ctypes.data, status.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_msa_segments" + ("" if device is None else "_dev"))
+    return formats.Msa(rows[:total], row_at, status[:n], lens)
+
+
+def msa_kernel_bench(seq, starts, ends, templates, pair_tmpl, device=0, warmup=2, reps=5):
+    """sd_msa_kernel_bench: the row kernel and the profile kernel timed in turn on the same pairs (HIP events) ->
+    {"msa_ms": [...], "profile_ms": [...], "K", "grid", "items", "pairs", "msa_lds_bytes", "staged", "profile_lds_bytes",
+    "ck_slots"}."""
+    import numpy as np
+    L = load()
+    sb = _b(seq)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
+    tb = [_b(t) for t in templates]
+    tl = (C.c_int32 * max(len(tb), 1))(*[len(t) for t in tb])
+    a, b, info = (C.c_float * reps)(), (C.c_float * reps)(), (C.c_int64 * 8)()
+    rc = L.sd_msa_kernel_bench(sb, len(sb), st.ctypes.data, en.ctypes.data, len(st), _strs(tb), tl, len(tb), pt.ctypes.data,
+                               int(device), int(warmup), int(reps), a, b, info)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_msa_kernel_bench")
+    out = {"msa_ms": [float(x) for x in a], "profile_ms": [float(x) for x in b]}
+    out.update(zip(("K", "grid", "items", "pairs", "msa_lds_bytes", "staged", "profile_lds_bytes", "ck_slots"), [int(x) for x in info]))
+    return out
+
+
+def _msa_key_table(keys, mono_names):
+    """key -> interleaved template, by name; a repeated monomer name is refused: a row's key must name one template."""
+    il = {}
+    for m, n in enumerate(mono_names):
+        n = n if isinstance(n, str) else n.decode()
+        for x, name in ((2 * m, n), (2 * m + 1, n + "'")):
+            if name in il:
+                raise SdError(SD_ERR_PARAM, "monomer name %s is not unique: a row's key must name one template" % name)
+            il[name] = x
+    try:
+        return [il[k if isinstance(k, str) else k.decode()] for k in keys]
+    except KeyError as e:
+        raise SdError(SD_ERR_PARAM, "key %s names no monomer" % e)
+
+
+def final_msa_host(final_rows, read_seqs, keys, mono_names, mono_seqs, threads=1):
+    """The rows (formats.Msa) of the kept rows of a final-mode job -- a FinalRows or its (rows, row_off, alt) -- without
+    a device: row i's segment read[start : end + 1], clamped as the selection measured it, against its own template
+    keys[best].  read_seqs: the job's reads in submit order; keys: Stream.keys().  -> (Msa, pair_tmpl); every status is
+    0 or 1."""
+    import numpy as np
+    kil = _msa_key_table(keys, mono_names)
+    rows = final_rows[0]
+    rs = [_b(s) for s in read_seqs]
+    off, at = [], 0
+    for s in rs:
+        off.append(at)
+        at += len(s)
+    st, en, pt = [], [], []
+    for read, start, end, best in zip(rows["read"].tolist(), rows["start"].tolist(), rows["end"].tolist(), rows["best"].tolist()):
+        n = len(rs[read])
+        s0 = min(max(start, 0), n)
+        e1 = min(max(end + 1, s0), n)
+        st.append(off[read] + s0)
+        en.append(off[read] + e1 - 1)   # (an empty segment: end = start - 1)
+        pt.append(kil[best])
+    text = b"".join(rs)
+    if not text:
+        text, st, en = b"N", [0] * len(st), [-1] * len(en)
+    return msa_segments(text, st, en, mono_seqs, pt, threads=threads), np.asarray(pt, dtype=np.int32)
+
+
+class DeviceMsa(namedtuple("DeviceMsa", "rows row_at status tlen classes")):
+    """The rows of --msa in device memory (final_msa_device): rows = a flat uint8 torch tensor, row_at = int64 [n + 1],
+    status = uint8 [n] (0 no instance, 1 computed, 2 left out: a pair the row kernel does not take), all on the final rows'
+    device; tlen = the forward monomers' lengths and classes = (status-0 rows, kernel pairs, pairs left out) on the host."""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> formats.Msa"""
+        from . import formats
+        return formats.Msa(self.rows.cpu().numpy(), self.row_at.cpu().numpy(), self.status.cpu().numpy(), list(self.tlen))
+
+
+class MsaTables:
+    """What final_msa_device needs of a monomer set (sd_msa_tables): key -> interleaved template and the forward monomers,
+    uploaded by the first call that uses them and reused by later ones; close() waits for the last of those calls'
+    kernels.  A repeated monomer name is refused: a row's key must name one template."""
+
+    def __init__(self, keys, mono_names, mono_seqs):
+        import numpy as np
+        self.L = load()
+        kil = np.ascontiguousarray(_msa_key_table(keys, mono_names), dtype=np.int32)
+        ms = [_b(s) for s in mono_seqs]
+        self.tlen = [len(s) for s in ms]
+        self.n_keys = len(kil)
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        rc = self.L.sd_msa_tables_create(C.byref(self.h), kil.ctypes.data, len(kil), _strs(ms),
+                                         (C.c_int32 * max(len(ms), 1))(*self.tlen), len(ms), err, 1024)
+        if rc != SD_OK:
+            raise SdError(rc, err.value.decode(errors="replace"))
+
+    def close(self):
+        if self.h:
+            self.L.sd_msa_tables_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def final_msa_device(dfr, reads, keys, mono_names, mono_seqs, stream=None, tables=None, cap=None):
+    """The rows of --msa of a DeviceFinalRows, computed on its device from the reads it was selected from (sd_msa_final_size_dev
+    / sd_msa_final_write_dev) -> DeviceMsa.  reads: the DeviceReads that was submitted; keys: Stream.keys(); tables: an
+    MsaTables over the same set, to upload it once for many jobs.  torch allocates the outputs on `stream` (the
+    convention of format_final_device) and the library fills them there: the host waits for the size and the class
+    counts only.  Pairs the row kernel does not take keep status 2 and an empty row (final_msa_host computes them).
+    cap: the bytes to allocate for the rows (default: what the size pass asks for)."""
+    import torch
+    L = load()
+    dev = dfr.row_off.device
+    st = _torch_stream(torch, dev, stream)
+    n = int(dfr.n_rows)
+    if dfr.row_off.shape[0] != reads.n + 1:
+        raise SdError(SD_ERR_PARAM, "final_msa_device: %d reads for the rows of %d" % (reads.n, dfr.row_off.shape[0] - 1))
+    t = tables if tables is not None else MsaTables(keys, mono_names, mono_seqs)
+    err = C.create_string_buffer(1024)
+    ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)   # noqa: E731
+    try:
+        if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+            ev = torch.cuda.Event()
+            ev.record(_torch_stream(torch, dev, reads.stream))
+            st.wait_event(ev)
+        with torch.cuda.stream(st):
+            row_at = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            status = torch.empty(n, dtype=torch.uint8, device=dev)
+        total, cls = C.c_int64(), (C.c_int64 * 3)()
+        _text_check(L.sd_msa_final_size_dev(t.h, ptr(dfr.rows), n, C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n,
+                                            dev.index or 0, C.c_void_p(st.cuda_stream), ptr(row_at), C.byref(total), cls, err, 1024),
+                    err)
+        nbytes = total.value if cap is None else int(cap)
+        with torch.cuda.stream(st):
+            rows = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _text_check(L.sd_msa_final_write_dev(t.h, ptr(dfr.rows), n, dev.index or 0, C.c_void_p(st.cuda_stream), ptr(row_at),
+                                             ptr(rows), nbytes, ptr(status), err, 1024), err)
+    finally:
+        if tables is None:
+            t.close()
+    return DeviceMsa(rows, row_at, status, t.tlen, tuple(int(x) for x in cls))
+
+
+def final_msa_classes(final_rows, read_lens, keys, mono_names, mono_seqs):
+    """The host's plan of final_msa_device: (rows that are no instance, pairs of the row kernel, pairs it leaves out) by
+    the rule of csrc/sd_final_prof_dev.hpp, and the per-row class (0 / 1 / 2) as a list."""
+    kil = _msa_key_table(keys, mono_names)
+    tl = [len(_b(s)) for s in mono_seqs]
+    tmax = max(tl)
+    rows = final_rows[0]
+    out = []
+    for read, start, end, best in zip(rows["read"].tolist(), rows["start"].tolist(), rows["end"].tolist(), rows["best"].tolist()):
+        n = int(read_lens[read])
+        s0 = min(max(start, 0), n)
+        q = min(max(end + 1, s0), n) - s0
+        t = tl[kil[best] >> 1]
+        if q <= 0 or t <= 0:
+            out.append(0)
+        elif tmax <= 512 and q <= 1024 and not 20 * ((q + 63) // 64) * t + 8 * t >= 1024 * 1024:
+            out.append(1)
+        else:
+            out.append(2)
+    return (out.count(0), out.count(1), out.count(2)), out
 
 
 def decompose_files_records(reads_fa, monomers_fa, records_out, **kw):

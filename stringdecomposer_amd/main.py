@@ -473,11 +473,12 @@ def _device_list(args):
     return devs
 
 
-def _check_profile(args):
-    """--profile requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
+def _check_profile(args, flag="--profile", why="a profile needs one template per name"):
+    """--profile (and --msa) requests this process cannot serve end it here, with one line on stderr, before any work on a
+    GPU."""
     if shard.world()[2] > 1:
-        sys.stderr.write("stringdecomposer: --profile cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)\n"
-                         % shard.world()[2])
+        sys.stderr.write("stringdecomposer: %s cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)\n"
+                         % (flag, shard.world()[2]))
         sys.exit(2)
     try:
         names = lib.fasta_load(args.monomers)[0]
@@ -486,10 +487,36 @@ def _check_profile(args):
     seen = set()
     for n in names + [x + "'" for x in names]:
         if n in seen:
-            sys.stderr.write("stringdecomposer: --profile: monomer name %s is not unique: a profile needs one template "
-                             "per name\n" % n)
+            sys.stderr.write("stringdecomposer: %s: monomer name %s is not unique: %s\n" % (flag, n, why))
             sys.exit(lib.SD_ERR_PARAM)
         seen.add(n)
+
+
+def _write_msa(args, final_fn, msa_fn, device):
+    """--msa: one line per row of the final TSV just written (formats.MSA_HEADER), the rows computed read by read on
+    `device` (lib.msa_segments: the row kernel, the host form for the pairs it does not take)."""
+    from . import formats
+    rn, rs, _ = lib.fasta_load(args.sequences)
+    mn, ms, _ = lib.fasta_load(args.monomers)
+    reads, il = {}, {}
+    for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
+        reads.setdefault(n, s.upper())
+        reads.setdefault(n.split()[0], s.upper())
+    ms = [s.upper() for s in ms]
+    for m, n in enumerate(mn):
+        for x in (n, n.split()[0]):
+            il.setdefault(x, 2 * m)
+            il.setdefault(x + "'", 2 * m + 1)
+    with open(msa_fn, "w") as f:
+        f.write(formats.MSA_HEADER)
+        for read, rows in formats.by_read(formats.read_final(final_fn)):
+            seq = reads[read]
+            st = [min(max(r.start, 0), len(seq)) for r in rows]
+            en = [min(max(r.end + 1, s), len(seq)) - 1 for r, s in zip(rows, st)]   # (an empty segment: end = start - 1)
+            pt = [il[r.monomer] for r in rows]
+            msa = lib.msa_segments(seq or b"N", st, en, ms, pt, threads=max(1, int(args.threads)), device=device)
+            f.write(formats.format_msa(formats.msa_rows(msa, pt, [(r.read, r.start, r.end, r.monomer) for r in rows]),
+                                       header=False))
 
 
 def main(argv=None):
@@ -533,9 +560,15 @@ def main(argv=None):
     parser.add_argument("--profile", action="store_true",
                         help="also write <out-file>_profile.tsv (per-monomer column profiles of the rows of <out-file>.tsv) "
                              "and <out-file>_consensus.fa (their consensus sequences)")
+    parser.add_argument("--msa", action="store_true",
+                        help="also write <out-file>_msa.tsv: one line per row of <out-file>.tsv with the read's bases by column "
+                             "of the forward monomer (ACGTN, '-' = deleted) and its insertions as slot:count (a count of 255 "
+                             "means 255 or more)")
     args = parser.parse_args(argv)
     if args.profile:
         _check_profile(args)
+    if args.msa:
+        _check_profile(args, "--msa", "a row's key must name one template")
     devices = _device_list(args)
     pathlib.Path(args.out_dir).mkdir(parents=True, exist_ok=True)
 
@@ -601,6 +634,16 @@ def main(argv=None):
         formats.write_consensus(cons_fn, prof)
         logger.info("Saved the monomer column profiles to " + prof_fn)
         logger.info("Saved the monomer consensus sequences to " + cons_fn)
+
+    if args.msa:
+        msa_fn = os.path.join(args.out_dir, args.out_file + "_msa.tsv")
+        try:
+            _write_msa(args, convert_tsv_fn, msa_fn, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--msa failed: " + e.msg + "\n")
+            logger.info("--msa failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the per-instance monomer columns to " + msa_fn)
 
     logger.info("Thank you for using StringDecomposer!")
 
