@@ -925,6 +925,82 @@ int sd_msa_final_size_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t 
 int sd_msa_final_write_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t n_rows, int32_t device, void* hip_stream,
                            const int64_t* d_row_at, uint8_t* d_out, int64_t cap, uint8_t* d_status, char* errbuf, size_t errlen);
 
+/* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
+ * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
+ * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the
+ * infix unit-cost edit distance of template j against the chunk; templates are the monomers in the given order, then
+ * their reverse complements.  A chunk passes a threshold thr >= 0 when key >> 16 <= thr.  The distances come from the
+ * prefilter's kernels with a sink that reduces in LDS and issues one atomic minimum per (workgroup, chunk): no
+ * [chunk][template] matrix is written, 4 bytes per chunk come back.  At most 32 767 monomers of at most 2 048 bp.
+ * A handle holds templates, match masks and scratch on one device; calls on one handle serialise. */
+typedef struct sd_screen sd_screen;
+typedef struct sd_screen_region {
+    int32_t read;        /* index of the read                                                       */
+    int64_t start;       /* first byte of the region in the read                                    */
+    int64_t end_incl;    /* last byte of the region                                                 */
+    int32_t n_chunks;    /* passing chunks the region was made of                                   */
+    uint32_t best_key;   /* the smallest key among them                                             */
+} sd_screen_region;
+int sd_screen_create(const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono, int32_t device, sd_screen** out,
+                     char* errbuf, size_t errlen);
+void sd_screen_destroy(sd_screen* h);
+/* on != 0: the general distance kernel where the uniform one would run (A/B and tests; the keys are the same) */
+int sd_screen_set_general(sd_screen* h, int32_t on);
+/* the kernel the next call launches: 0 = sd_hw_dist<W>, 1 = sd_hw_dist_u<W, lo>, 2 = sd_hw_dist_u<W, hi>; *words = W */
+int sd_screen_kernel(sd_screen* h, int32_t* words);
+/* device time (ms) of the kernels of the calls so far whose keys came back to the host; reset != 0 zeroes the sum */
+double sd_screen_kernel_ms(sd_screen* h, int32_t reset);
+/* For tools/screen_bench.py: the screen's launch (key fill + distance kernel with the key sink) beside the distance
+ * kernel of --ed_thr alone (the same instantiation, writing its [chunk][template] matrix) on the batch of the last
+ * sd_screen_chunks call, alternating in one process, each between two HIP events; warmup untimed rounds, then reps
+ * timed ones into screen_ms[reps] / dist_ms[reps]. */
+int sd_screen_kernel_bench(sd_screen* h, int32_t warmup, int32_t reps, float* screen_ms, float* dist_ms, char* errbuf,
+                           size_t errlen);
+/* Reads in host memory: packed on host threads, one launch, the keys copied back.  key_out: room for cap keys;
+ * *n_chunks (may be NULL) is set even when cap is too small (SD_ERR_PARAM).  SD_ERR_EMPTY for a read of length <= 0,
+ * SD_ERR_SYMBOL for a byte outside A C G T N. */
+int sd_screen_chunks(sd_screen* h, const char* const* read_seqs, const int64_t* read_lens, int32_t n_reads, int32_t part_size,
+                     int32_t overlap, uint32_t* key_out, int64_t cap, int64_t* n_chunks, char* errbuf, size_t errlen);
+/* Reads in device memory, the arguments of sd_stream_submit_dev: read r = d_bases[read_off[r] .. read_off[r] + read_lens[r]),
+ * read_off and read_lens HOST arrays.  The handle's stream waits for an event recorded on hip_stream, packs the bases
+ * with the device packer and screens them; hip_stream is made to wait for the last kernel, so the text may be
+ * overwritten or freed on it right after the call.  key_out is device memory of the handle's device -- then the keys are
+ * written there, in order with hip_stream, and there is no host-side wait -- or host memory, then the call returns
+ * when they have arrived.  The alphabet is not checked here (a byte outside A C G T N is packed under the masked
+ * formula of the packer; the decomposition of the same bytes reports it). */
+int sd_screen_chunks_dev(sd_screen* h, const void* d_bases, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads,
+                         int32_t part_size, int32_t overlap, void* hip_stream, uint32_t* key_out, int64_t cap,
+                         int64_t* n_chunks, char* errbuf, size_t errlen);
+/* Host only: the same keys by a plain dynamic program (exact, not fast; for tests). */
+int sd_screen_chunks_host(const char* const* mono_seqs, const int32_t* mono_lens, int32_t n_mono, const char* const* read_seqs,
+                          const int64_t* read_lens, int32_t n_reads, int32_t part_size, int32_t overlap, uint32_t* key_out,
+                          int64_t cap, int64_t* n_chunks, char* errbuf, size_t errlen);
+/* Host only: the regions of a threshold.  chunk_read[c] = the read of chunk c (ascending: a chunk table); a region is a
+ * maximal run a..b of consecutive passing chunks of one read and covers its bytes [a * part_size, min(len, (b + 1) *
+ * part_size + overlap)); regions come in read order, then position order.  SD_ERR_PARAM for thr < 0 and for overlap >=
+ * part_size (the regions of a read must not overlap).  *n_regions is set even when cap is too small (SD_ERR_PARAM). */
+int sd_screen_regions(const uint32_t* keys, const int32_t* chunk_read, int64_t n_chunks, const int64_t* read_lens,
+                      int32_t n_reads, int32_t part_size, int32_t overlap, int32_t thr, sd_screen_region* regions_out,
+                      int64_t cap, int64_t* n_regions, char* errbuf, size_t errlen);
+
+/* sd_run_files behind the screen: the job runs in two phases inside the one call.  Phase 1 packs and screens every
+ * chunk of the reads file in batches dealt over the device entries (devices / n_devices as sd_run_files_devices takes
+ * them; NULL / 0: p->device).  Phase 2 is the job of sd_run_files over a read list in which every region of screen_thr
+ * replaces its read: for every region, in read order and then position order, exactly the rows of the plain job on the
+ * region's substring as a read of its own, with the parent's name and every start and end increased by the region's
+ * start; a read without a region contributes no row; nothing is merged across regions.  An input whose chunks all pass
+ * gives the files of sd_run_files byte for byte.  p->ed_thr and the scoring keep their meaning inside the regions; the
+ * screen's distances depend on neither.  screen_tsv_out (may be NULL): one line per region -- read, start, end (0-based,
+ * inclusive), chunks, best distance, best template (' = reverse complement).  SD_FLAG_PROFILE works as in sd_run_files.
+ * counts (may be NULL): [0] reads, [1] reads with a region, [2] bases read, [3] bases decomposed; sd_last_run_stats
+ * [20..23]: the screen's wall ms, the device ms of its kernels, bases read, bases decomposed.
+ * SD_ERR_PARAM, before any device is touched: screen_thr < 0, overlap >= part_size, records_out != NULL ("the record
+ * stream holds whole reads"). */
+int sd_run_files_screen(const char* reads_fa, const char* monomers_fa, const sd_params* p, const int32_t* devices,
+                        int32_t n_devices, const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
+                        int32_t min_identity, int32_t second_best, const double* lr_coef, int32_t screen_thr,
+                        const char* screen_tsv_out, const char* records_out, int64_t* counts, char* errbuf, size_t errlen);
+
 /* The profile of the last successful sd_run_files* call of this process made with SD_FLAG_PROFILE (summed over its
  * device entries).  Every output may be NULL: *n_monomers, *n_counts and *text_bytes size the buffers of a second
  * call.  text: "name\tsequence\n" per monomer in FASTA order, NUL-terminated (text_bytes counts the NUL); counts as

@@ -448,8 +448,8 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
             const PostRead& rd = reads[(size_t)f.read];
             of.append(rd.name, rd.name_len); of.push_back('\t');
             of.append(keys[(size_t)f.best]); of.push_back('\t');
-            put_int(of, f.start); of.push_back('\t');
-            put_int(of, f.end); of.push_back('\t');
+            put_int(of, f.start + rd.base); of.push_back('\t');
+            put_int(of, f.end + rd.base); of.push_back('\t');
             put_f2(of, f.ident); of.push_back('\t');
             of.append(name(f.second)); of.push_back('\t');
             put_f2(of, f.second_ident); of.push_back('\t');
@@ -460,11 +460,11 @@ int PostProcessor::process_parts(const PostRead* reads, size_t n_reads, const sd
             of.push_back(f.reliable ? '+' : '?');
             of.push_back('\n');
             if (second_best) {   // main.py:161-165: one row per name of the dict
-                char mid[32];    // "\t<start>\t<end>\t": the same for the nK rows of the block
+                char mid[48];    // "\t<start>\t<end>\t": the same for the nK rows of the block
                 size_t ml = 0;
                 {
                     std::string t;
-                    t.push_back('\t'); put_int(t, f.start); t.push_back('\t'); put_int(t, f.end); t.push_back('\t');
+                    t.push_back('\t'); put_int(t, f.start + rd.base); t.push_back('\t'); put_int(t, f.end + rd.base); t.push_back('\t');
                     ml = t.size();
                     std::memcpy(mid, t.data(), ml);
                 }

@@ -22,6 +22,7 @@ namespace sd {
 struct PostRead {
     const char* name; size_t name_len;
     const char* seq; int64_t len;       // upper-case sequence (main.py:66-67)
+    int64_t base = 0;                   // a region of a screened job: added to the starts and ends of the text
 };
 
 // Identities that came with the rows from the device (sd_ident.hip): one word (dist << 16) | matches per row (light

@@ -50,6 +50,8 @@ struct ReadView {  // borrowed for the duration of the call
     size_t name_len;
     const char* seq;
     int64_t len;
+    int64_t base = 0;   // a region of a screened job (sd_run_files_screen): where seq starts in the read `name`; added
+                        // wherever a row's start or end becomes text
 };
 struct CRef { int32_t read; int64_t off; int32_t len; };
 

@@ -157,6 +157,10 @@ struct FilterArgs {
     uint16_t* klist = nullptr;
     int32_t* nkept = nullptr;
     uint16_t* grank = nullptr;         // generic family: the rank table (set: cendoff / crank are not written)
+    // the screen (sd_screen.hip): set, the launch reduces the distances to key[chunk] = (min distance << 16) | first
+    // template that has it and writes nothing else (dist, ranks and ed_thr are not used)
+    uint32_t* screen_key = nullptr;
+    bool dist_only = false;            // the distance kernel alone into dist: no fills, no sd_rank_keep (tools/screen_bench.py)
 };
 void launch_edthr_filter(hipStream_t st, const FilterArgs& a);
 // --ed_thr with more than 128 templates: the chunk order split into W classes by ceil(kept templates / 128)

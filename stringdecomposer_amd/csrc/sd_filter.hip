@@ -26,29 +26,73 @@
 
 namespace sd {
 
+// Where a pair's distance goes.  DistStore: the matrix dist[chunk][T] sd_rank_keep reads (--ed_thr).  KeyMin: the
+// screen (--screen, sd_screen.hip) -- no matrix, one key per chunk, (smallest distance << 16) | first template that has
+// it: with T <= 65 535 and distances <= 2 048 one unsigned minimum gives both.  The lanes of a workgroup are consecutive
+// (chunk, template) pairs, so they touch at most 256 / T + 2 chunks; a chunk's templates may lie in several waves and
+// workgroups.  The minimum is taken in LDS first (slot = chunk - first chunk of the workgroup), then one global
+// atomicMin per (workgroup, chunk) into key[], which the launcher has filled with 0xffffffff.  kReduce: every lane of
+// the workgroup stays to the end (the barrier in front of the global atomics); a lane past the last pair walks no column.
+struct DistStore {
+    static constexpr bool kReduce = false;
+    int32_t* __restrict__ dist;
+    __device__ __forceinline__ void init() const {}
+    __device__ __forceinline__ void put(long long g0, int c, int j, int T, int best) const { dist[(size_t)c * T + j] = best; }
+    __device__ __forceinline__ void flush(long long g0, int T) const {}
+};
+constexpr int SCREEN_SLOTS = 258;   // 256 / T + 2 at T = 1
+struct KeyMin {
+    static constexpr bool kReduce = true;
+    uint32_t* __restrict__ key;
+    __device__ __forceinline__ uint32_t* slots() const {
+        __shared__ uint32_t smin[SCREEN_SLOTS];
+        return smin;
+    }
+    __device__ __forceinline__ void init() const {   // (in front of the kernel's first barrier)
+        uint32_t* smin = slots();
+        for (int s = threadIdx.x; s < SCREEN_SLOTS; s += blockDim.x) smin[s] = 0xffffffffu;
+    }
+    __device__ __forceinline__ void put(long long g0, int c, int j, int T, int best) const {
+        atomicMin(slots() + (c - (int)(g0 / T)), ((uint32_t)best << 16) | (uint32_t)j);
+    }
+    __device__ __forceinline__ void flush(long long g0, int T) const {
+        uint32_t* smin = slots();
+        __syncthreads();
+        const int c0 = (int)(g0 / T);
+        for (int s = threadIdx.x; s < SCREEN_SLOTS; s += blockDim.x) {
+            const uint32_t v = smin[s];
+            if (v != 0xffffffffu) atomicMin(key + (size_t)(c0 + s), v);   // (only slots a live lane wrote: chunks of the batch)
+        }
+    }
+};
+
 // One lane per (chunk, template) pair, consecutive lanes = consecutive templates of a chunk: the lanes of a
 // wave then read the same few chunks' bases (one broadcast load per 16 columns) and every lane does useful
 // work for any template count (a wave per chunk with the templates across the lanes would idle 40 of 64
 // lanes at 24 templates).  W = 64-bit words per template, a template parameter so that the delta vectors
 // live in exactly 4*W registers; the match masks of all templates sit in LDS ([template][symbol][word]).
-template <int W>
+template <int W, class Sink = DistStore>
 __global__ __launch_bounds__(256) void sd_hw_dist(const ChunkDesc* __restrict__ chunks, int n_chunks,
                                                   int T, const uint32_t* __restrict__ bases2,
                                                   const uint32_t* __restrict__ nmask,
                                                   const unsigned long long* __restrict__ peq,
                                                   const int32_t* __restrict__ tlen,
-                                                  int32_t* __restrict__ dist, int lds_templates) {
+                                                  Sink sink, int lds_templates) {
     constexpr int PS = W <= 8 ? 8 : W;             // words per (template, symbol) row of peq (build_peq)
     extern __shared__ unsigned long long speq[];   // [min(T, lds_templates)][5][W]
     for (int idx = threadIdx.x; idx < lds_templates * 5 * W; idx += blockDim.x) {
         const int j = idx / (5 * W), rem = idx % (5 * W);
         speq[idx] = peq[(size_t)j * 5 * PS + (size_t)(rem / W) * PS + (rem % W)];
     }
+    sink.init();
     __syncthreads();
-    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= (long long)n_chunks * T) return;
-    const int c = (int)(g / T), j = (int)(g % T);
-    const ChunkDesc cd = chunks[c];
+    const long long g0 = (long long)blockIdx.x * blockDim.x;
+    const long long g = g0 + threadIdx.x;
+    const bool live = g < (long long)n_chunks * T;
+    if (!Sink::kReduce && !live) return;
+    const int c = live ? (int)(g / T) : n_chunks - 1, j = (int)(g % T);
+    ChunkDesc cd = chunks[c];
+    if (Sink::kReduce && !live) cd.n = 0;
     const int m = tlen[j];
     const int lastW = (m - 1) >> 6;
     const unsigned long long lastBit = 1ull << ((m - 1) & 63);
@@ -96,7 +140,8 @@ __global__ __launch_bounds__(256) void sd_hw_dist(const ChunkDesc* __restrict__ 
         score += hin;  // vertical delta of the pattern's last row
         best = min(best, score);
     }
-    dist[(size_t)c * T + j] = best;
+    if (live) sink.put(g0, c, j, T, best);
+    sink.flush(g0, T);
 }
 
 // The common case made cheap: every template occupies the same number of 64-bit words, the end of every template
@@ -105,12 +150,12 @@ __global__ __launch_bounds__(256) void sd_hw_dist(const ChunkDesc* __restrict__ 
 // vectors live as 32-bit halves, the three-input boolean steps are single v_bitop3_b32 instructions (truth table
 // over a = 0xF0, b = 0xCC, c = 0xAA), the carries between words are plain 0/1 values, and the masks come straight
 // from LDS -- about 80 VALU instructions per column at three words instead of 136.  Same result as sd_hw_dist.
-template <int W, bool HI>
+template <int W, bool HI, class Sink = DistStore>
 __global__ __launch_bounds__(256) void sd_hw_dist_u(const ChunkDesc* __restrict__ chunks, int n_chunks, int T,
                                                     const uint32_t* __restrict__ bases2,
                                                     const uint32_t* __restrict__ nmask,
                                                     const unsigned long long* __restrict__ peq,
-                                                    const int32_t* __restrict__ tlen, int32_t* __restrict__ dist) {
+                                                    const int32_t* __restrict__ tlen, Sink sink) {
     // the 256 pairs of a workgroup are consecutive templates (of one or two chunks): only their masks are staged,
     // min(T, 256) x 5 x W words, whatever the size of the set
     extern __shared__ unsigned long long speq[];
@@ -123,11 +168,14 @@ __global__ __launch_bounds__(256) void sd_hw_dist_u(const ChunkDesc* __restrict_
         if (j >= T) j -= T;
         speq[idx] = peq[(size_t)j * 40 + (size_t)(rem / W) * 8 + (rem % W)];
     }
+    sink.init();
     __syncthreads();
     const long long g = g0 + threadIdx.x;
-    if (g >= (long long)n_chunks * T) return;
-    const int c = (int)(g / T), j = (int)(g % T);
-    const ChunkDesc cd = chunks[c];
+    const bool live = g < (long long)n_chunks * T;
+    if (!Sink::kReduce && !live) return;
+    const int c = live ? (int)(g / T) : n_chunks - 1, j = (int)(g % T);
+    ChunkDesc cd = chunks[c];
+    if (Sink::kReduce && !live) cd.n = 0;
     const int m = tlen[j];
     const uint32_t sh = (uint32_t)((m - 1) & 31);           // end of the template inside its half
     int jl = j - j0;
@@ -188,7 +236,8 @@ __global__ __launch_bounds__(256) void sd_hw_dist_u(const ChunkDesc* __restrict_
         score += (int)cP - (int)cM;  // vertical delta of the pattern's last row
         best = min(best, score);
     }
-    dist[(size_t)c * T + j] = best;
+    if (live) sink.put(g0, c, j, T, best);
+    sink.flush(g0, T);
 }
 
 // Kept set and order of a chunk (main.cpp:141-147): first = smallest (distance, index); kept = first or
@@ -329,7 +378,45 @@ void launch_split_order(hipStream_t st, const int* order, int n, const int32_t* 
     hipLaunchKernelGGL(sd_split_order, dim3(1), dim3(64), 0, st, order, n, nkept, orders, counts, W);
 }
 
+// The distance kernel of the batch with the given sink: W, uniform or general and the templates whose masks lie in LDS
+// are chosen here, for --ed_thr and the screen alike (lds_static: LDS the sink declares itself).
+template <class Sink>
+static void launch_hw_dist(hipStream_t st, const FilterArgs& a, Sink sink, size_t lds_static) {
+    const long long total = (long long)a.n_chunks * a.T;
+    const int grid = (int)((total + 255) / 256);
+    const int W = std::max(1, (a.Lmax + 63) / 64);
+    // match masks in LDS: as many templates as fit in 64 KB (all of them up to ~540 at 3 words)
+#define SD_HW(WW)                                                                                              \
+    {                                                                                                          \
+        const int lt = std::min(a.T, (int)((64 * 1024 - lds_static) / (5 * WW * sizeof(unsigned long long))));  \
+        hipLaunchKernelGGL((sd_hw_dist<WW, Sink>), dim3(grid), dim3(256), (size_t)lt * 5 * WW * sizeof(unsigned long long), st, \
+                           a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, sink, lt);             \
+    }
+    // uniform variant (sd_hw_dist_u): same word count and same half of the last word for every template, masks in LDS
+    if (a.uniform_half >= 0 && W <= 4) {   // (SD_FLAG_FILTER_GENERAL: the engine passes uniform_half = -1)
+        const size_t lds = (size_t)std::min(a.T, 256) * 5 * W * sizeof(unsigned long long);   // <= 40 KB
+#define SD_HWU(WW)                                                                                             \
+        {                                                                                                      \
+            if (a.uniform_half) hipLaunchKernelGGL((sd_hw_dist_u<WW, true, Sink>), dim3(grid), dim3(256), lds, st, a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, sink); \
+            else hipLaunchKernelGGL((sd_hw_dist_u<WW, false, Sink>), dim3(grid), dim3(256), lds, st, a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, sink); \
+        }
+        if (W == 1) SD_HWU(1) else if (W == 2) SD_HWU(2) else if (W == 3) SD_HWU(3) else SD_HWU(4)
+#undef SD_HWU
+    } else {
+    if (W <= 1) SD_HW(1) else if (W == 2) SD_HW(2) else if (W == 3) SD_HW(3) else if (W == 4) SD_HW(4)
+    else if (W <= 8) SD_HW(8) else if (W <= 16) SD_HW(16) else SD_HW(32)   // 16 / 32 words: templates of up to 1024 / 2048 bp
+    }
+#undef SD_HW
+}
+
 void launch_edthr_filter(hipStream_t st, const FilterArgs& a) {
+    if (a.n_chunks <= 0 || a.T <= 0) return;
+    if (a.screen_key) {   // the screen: one key per chunk and nothing else (no matrix, no ranks)
+        (void)hipMemsetAsync(a.screen_key, 0xff, (size_t)a.n_chunks * sizeof(uint32_t), st);
+        launch_hw_dist(st, a, KeyMin{a.screen_key}, SCREEN_SLOTS * sizeof(uint32_t));
+        return;
+    }
+    if (a.dist_only) { launch_hw_dist(st, a, DistStore{a.dist}, 0); return; }
     const long long total = (long long)a.n_chunks * a.T;
     const int grid = (int)((total + 255) / 256);
     if (!a.grank) {
@@ -342,29 +429,7 @@ void launch_edthr_filter(hipStream_t st, const FilterArgs& a) {
         hipLaunchKernelGGL(sd_fill_u32, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st,
                            reinterpret_cast<uint32_t*>(a.klist), words, 0xffffffffu);
     }
-    const int W = std::max(1, (a.Lmax + 63) / 64);
-    // match masks in LDS: as many templates as fit in 64 KB (all of them up to ~540 at 3 words)
-#define SD_HW(WW)                                                                                              \
-    {                                                                                                          \
-        const int lt = std::min(a.T, (int)((64 * 1024) / (5 * WW * sizeof(unsigned long long))));              \
-        hipLaunchKernelGGL(sd_hw_dist<WW>, dim3(grid), dim3(256), (size_t)lt * 5 * WW * sizeof(unsigned long long), st, \
-                           a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, a.dist, lt);         \
-    }
-    // uniform variant (sd_hw_dist_u): same word count and same half of the last word for every template, masks in LDS
-    if (a.uniform_half >= 0 && W <= 4) {   // (SD_FLAG_FILTER_GENERAL: the engine passes uniform_half = -1)
-        const size_t lds = (size_t)std::min(a.T, 256) * 5 * W * sizeof(unsigned long long);   // <= 40 KB
-#define SD_HWU(WW)                                                                                             \
-        {                                                                                                      \
-            if (a.uniform_half) hipLaunchKernelGGL((sd_hw_dist_u<WW, true>), dim3(grid), dim3(256), lds, st, a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, a.dist); \
-            else hipLaunchKernelGGL((sd_hw_dist_u<WW, false>), dim3(grid), dim3(256), lds, st, a.chunks, a.n_chunks, a.T, a.bases2, a.nmask, a.peq, a.tlen, a.dist); \
-        }
-        if (W == 1) SD_HWU(1) else if (W == 2) SD_HWU(2) else if (W == 3) SD_HWU(3) else SD_HWU(4)
-#undef SD_HWU
-    } else {
-    if (W <= 1) SD_HW(1) else if (W == 2) SD_HW(2) else if (W == 3) SD_HW(3) else if (W == 4) SD_HW(4)
-    else if (W <= 8) SD_HW(8) else if (W <= 16) SD_HW(16) else SD_HW(32)   // 16 / 32 words: templates of up to 1024 / 2048 bp
-    }
-#undef SD_HW
+    launch_hw_dist(st, a, DistStore{a.dist}, 0);
     hipLaunchKernelGGL(sd_rank_keep, dim3(grid), dim3(256), 0, st, a.n_chunks, a.T, a.ed_thr, a.dist, a.end_vlane, a.end_off,
                        reinterpret_cast<uint16_t*>(a.cendoff), reinterpret_cast<uint16_t*>(a.crank), a.grank, a.waves, a.kpos, a.klist,
                        a.nkept, a.vlane0);

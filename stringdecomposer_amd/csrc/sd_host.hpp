@@ -280,7 +280,8 @@ inline char* put_int_at(char* w, int64_t v) {
 
 inline void format_rows(std::string& o, const char* read_name, size_t read_name_len,
                         const std::vector<std::string>& tnames, const sd_rec* rows, size_t n,
-                        int prev_end = 0) {  // prev_end: end of the row before rows[0] (0 at a read's start)
+                        int prev_end = 0,    // prev_end: end of the row before rows[0] (0 at a read's start)
+                        int64_t base = 0) {  // added to the printed start and end (a region of a screened job)
     // Written through a pointer into room reserved for the worst case (a std::string that grows field by field spent
     // 580 ns per row on appends and reallocations: 61 ms for the 1.17 M rows of a 200-Mb sequence on 16 threads).
     size_t tmax = 0;
@@ -296,9 +297,9 @@ inline void format_rows(std::string& o, const char* read_name, size_t read_name_
         const std::string& tn = tnames[(size_t)r.tmpl];
         std::memcpy(w, tn.data(), tn.size()); w += tn.size();
         *w++ = '\t';
-        w = put_int_at(w, r.start);
+        w = put_int_at(w, r.start + base);
         *w++ = '\t';
-        w = put_int_at(w, r.end);
+        w = put_int_at(w, r.end + base);
         *w++ = '\t';
         w = put_int_at(w, r.score);
         std::memcpy(w, ".000000\t", 8); w += 8;

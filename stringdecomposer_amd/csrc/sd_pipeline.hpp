@@ -298,6 +298,12 @@ void rows_assemble(RowsWS& ws, hipStream_t st, const sd::DevRec* recs, const int
 // the kept records into rows[0 .. cap) and the n_reads + 1 row offsets
 void rows_scatter(RowsWS& ws, hipStream_t st, const sd::DevRec* recs, sd::DevRec* rows, int64_t cap, int64_t* row_off);
 
+// Phase 1 of sd_run_files_screen (sd_screen.hip): the screen's key of every chunk of the reads' chunk plan, the batches
+// dealt over the device entries; *kernel_ms: device time of the distance kernels, summed over the entries
+int screen_file_reads(const char* const* seqs, const int64_t* lens, size_t n_reads, const char* const* mono_seqs,
+                      const int32_t* mono_lens, int32_t n_mono, const sd_params* p, const std::vector<int32_t>& devs,
+                      std::vector<uint32_t>& keys, double* kernel_ms, std::string& err);
+
 // Where the text of a batch lies when it is already in device memory (load_chunks_impl with a DevSrc: the chunk
 // pointers are device addresses, packed there by sd_pack_dev.hip instead of on host threads).
 struct DevSrc {

@@ -46,6 +46,7 @@ static std::vector<uint64_t> g_last_prof;
 static std::string g_last_prof_text;
 static int32_t g_last_prof_n = 0;
 static int g_last_ndev = 0;
+static int64_t g_last_screen[2] = {0, 0};   // reads, reads with a region of the last screened job
 static int64_t g_last_dev_batches[kMaxDevices] = {0};
 static double g_last_dev_busy[kMaxDevices] = {0};
 
@@ -362,7 +363,7 @@ struct TextStages {
         sd::parallel_for((int64_t)slices.size(), files.threads, 1, [&](int64_t x) {
             const Slice& sl = slices[(size_t)x];
             sd::format_rows(wj.raw[(size_t)x], reads[sl.r].name, reads[sl.r].name_len, ts.tnames, w.rows + sl.a,
-                            (size_t)(sl.b - sl.a), sl.a > off[sl.r - w.r0] ? w.rows[sl.a - 1].end : 0);
+                            (size_t)(sl.b - sl.a), sl.a > off[sl.r - w.r0] ? w.rows[sl.a - 1].end : 0, reads[sl.r].base);
         });
         if (rec)
             for (size_t r = w.r0; r < w.r1; ++r)
@@ -371,7 +372,7 @@ struct TextStages {
         t0 = now_s();
         preads.clear();
         for (size_t r = w.r0; r < w.r1; ++r)
-            preads.push_back(sd::PostRead{reads[r].name, reads[r].name_len, reads[r].seq, reads[r].len});
+            preads.push_back(sd::PostRead{reads[r].name, reads[r].name_len, reads[r].seq, reads[r].len, reads[r].base});
         std::string e2;
         sd::IdentRef iref;
         if (w.have_ident)
@@ -509,6 +510,70 @@ static void report_stats(const std::vector<std::unique_ptr<Pipeline>>& pipes, co
     }
 }
 
+// --screen (sd_run_files_screen): the threshold and where the region file goes
+struct ScreenOpt { int32_t thr; const char* tsv_out; };
+
+// Phase 1 of a screened job: the key of every chunk of the file (sd_screen.hip, the batches dealt over the device
+// entries), the regions of the threshold, the region file; `reads` becomes the region list -- each region a ReadView into
+// its parent's mapped bases, with the parent's name and its start as `base` -- which phase 2, the job as it always was,
+// decomposes as reads of their own.  stats: [0] wall ms, [1] device ms of the distance kernels, [2] bases read, [3] bases
+// of the regions, [4] reads, [5] reads with a region.
+static int screen_phase(const JobInput& in, const TemplateSet& ts, const sd_params* p, const std::vector<int32_t>& devs,
+                        const ScreenOpt& so, std::vector<ReadView>& reads, double stats[6], std::string& err) {
+    const double t0 = now_s();
+    const size_t n = reads.size();
+    std::vector<const char*> seqs(n);
+    std::vector<int64_t> lens(n);
+    for (size_t r = 0; r < n; ++r) { seqs[r] = reads[r].seq; lens[r] = reads[r].len; }
+    std::vector<uint32_t> keys;
+    int rc = screen_file_reads(seqs.data(), lens.data(), n, ts.mseq.data(), ts.mlen.data(), (int32_t)ts.mseq.size(), p, devs, keys,
+                               &stats[1], err);
+    if (rc) return rc;
+    std::vector<int32_t> chunk_read;
+    chunk_read.reserve(keys.size());
+    for (size_t r = 0; r < n; ++r)
+        sd::chunk_plan(lens[r], p->part_size, p->overlap, [&](int64_t, int32_t) { chunk_read.push_back((int32_t)r); });
+    std::vector<sd_screen_region> reg(keys.size() + 1);
+    int64_t n_reg = 0;
+    char eb[256] = {0};
+    rc = sd_screen_regions(keys.data(), chunk_read.data(), (int64_t)keys.size(), lens.data(), (int32_t)n, p->part_size, p->overlap,
+                           so.thr, reg.data(), (int64_t)reg.size(), &n_reg, eb, sizeof eb);
+    if (rc) { err = eb; return rc; }
+    std::string txt;
+    std::vector<ReadView> out;
+    out.reserve((size_t)n_reg);
+    int64_t bases = 0, with_region = 0;
+    for (int64_t g = 0; g < n_reg; ++g) {
+        const sd_screen_region& x = reg[(size_t)g];
+        const ReadView& rd = reads[(size_t)x.read];
+        if (g == 0 || reg[(size_t)g - 1].read != x.read) ++with_region;
+        bases += x.end_incl - x.start + 1;
+        out.push_back(ReadView{rd.name, rd.name_len, rd.seq + x.start, x.end_incl - x.start + 1, x.start});
+        txt.append(rd.name, rd.name_len); txt.push_back('\t');
+        sd::put_int(txt, x.start); txt.push_back('\t');
+        sd::put_int(txt, x.end_incl); txt.push_back('\t');
+        sd::put_int(txt, x.n_chunks); txt.push_back('\t');
+        sd::put_int(txt, (int64_t)(x.best_key >> 16)); txt.push_back('\t');
+        txt.append(ts.tnames[(size_t)(x.best_key & 0xffffu)]); txt.push_back('\n');
+    }
+    if (so.tsv_out) {
+        const int fd = ::open(so.tsv_out, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        bool ok = fd >= 0;
+        for (size_t at = 0; ok && at < txt.size();) {
+            const ssize_t w = ::write(fd, txt.data() + at, txt.size() - at);
+            if (w <= 0) ok = false; else at += (size_t)w;
+        }
+        if (fd >= 0 && ::close(fd) != 0) ok = false;
+        if (!ok) { err = std::string("cannot write ") + so.tsv_out; return SD_ERR_IO; }
+    }
+    int64_t read_bases = 0;
+    for (int64_t l : lens) read_bases += l;
+    stats[0] = (now_s() - t0) * 1e3;
+    stats[2] = (double)read_bases; stats[3] = (double)bases; stats[4] = (double)n; stats[5] = (double)with_region;
+    reads.swap(out);
+    return SD_OK;
+}
+
 // The whole CLI job as one native call: FASTA files -> raw TSV + final TSV + _alt TSV, streamed per device batch
 // (main.py:186-197 run + :168-184 convert_tsv without the round trip through the raw file).  devs: the device entries,
 // one pipeline each ({p->device} for the single-device calls); their batches are dealt and consumed in order below.
@@ -520,7 +585,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
                           const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
                           int32_t min_identity, int32_t second_best, const double* lr_coef, int64_t* info,
                           char* errbuf, size_t errlen, const char* records_out = nullptr,
-                          const std::vector<int32_t>* dev_list = nullptr) try {
+                          const std::vector<int32_t>* dev_list = nullptr, const ScreenOpt* screen = nullptr) try {
     std::string err;
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
@@ -540,6 +605,13 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
         return SD_ERR_PARAM;
     if (records_out && world != 1) { set_err(errbuf, errlen, "the record stream is written by a single process"); return SD_ERR_PARAM; }
     if (nd > 1 && world != 1) return SD_ERR_PARAM;
+    if (screen) {   // (checked before any device is touched)
+        const char* why = records_out ? "--screen: the record stream holds whole reads" :
+                          world != 1 ? "--screen: a screened job is not split over ranks" :
+                          screen->thr < 0 ? "--screen: the threshold must be >= 0" :
+                          p->overlap >= p->part_size ? "--screen needs overlap < part_size (the regions of a read must not overlap)" : nullptr;
+        if (why) { set_err(errbuf, errlen, why); return SD_ERR_PARAM; }
+    }
     const bool timing = getenv("SD_TIMING") != nullptr;
     const double t_begin = now_s();
     double t_prev = t_begin;
@@ -554,8 +626,14 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     rc = in.load(reads_fa, monomers_fa, p, rank, world, progress, info, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     lap("FASTA index + alphabet check");
-    const std::vector<ReadView>& reads = in.reads;
     TemplateSet ts(in.monos);
+    double screen_stats[6] = {0, 0, 0, 0, 0, 0};
+    if (screen) {
+        rc = screen_phase(in, ts, p, devs, *screen, in.reads, screen_stats, err);
+        if (rc) { set_err(errbuf, errlen, err); return rc; }
+        lap("screen: keys of every chunk, regions");
+    }
+    const std::vector<ReadView>& reads = in.reads;
     sd::PostProcessor pp;
     rc = pp.init(in.monos, min_identity, second_best != 0, lr_coef, devs[0], p->threads, err);
     if (rc == SD_OK && profile) rc = pp.enable_profile(err);
@@ -564,6 +642,22 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     if (!files.open(raw_tsv_out, final_tsv_out, alt_tsv_out, p->threads)) {
         set_err(errbuf, errlen, std::string("cannot write ") + raw_tsv_out);
         return SD_ERR_IO;
+    }
+    if (screen && reads.empty()) {   // nothing passed: three empty files, an empty profile
+        if (!files.close()) { set_err(errbuf, errlen, std::string("short write to ") + raw_tsv_out); return SD_ERR_IO; }
+        std::lock_guard<std::mutex> lk(g_last_m);
+        std::memset(g_last_run, 0, sizeof g_last_run);
+        for (int i = 0; i < 4; ++i) g_last_run[20 + i] = screen_stats[i];
+        g_last_screen[0] = (int64_t)screen_stats[4];
+        g_last_screen[1] = 0;
+        g_last_ndev = 0;
+        if (profile) {
+            g_last_prof = pp.profile();
+            g_last_prof_text = pp.profile_text();
+            g_last_prof_n = (int32_t)in.monos.size();
+            g_last_prof_on = true;
+        }
+        return SD_OK;
     }
     sd::RecordsWriter rec_w;   // the rows once more as the binary record stream (sd_records.hpp), written as reads complete
     if (records_out) {
@@ -615,6 +709,12 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     if (!files.close() && rc == SD_OK) { rc = SD_ERR_IO; err = std::string("short write to ") + raw_tsv_out; }
     if (records_out && rc == SD_OK) rc = rec_w.close(err, records_out);
     report_stats(jp.pipes, jp.dealt, text, pp, batches.size(), t_setup);
+    if (screen) {
+        std::lock_guard<std::mutex> lk(g_last_m);
+        for (int i = 0; i < 4; ++i) g_last_run[20 + i] = screen_stats[i];   // (sd_last_run_stats: screen wall ms, kernel ms, bases read, bases decomposed)
+        g_last_screen[0] = (int64_t)screen_stats[4];
+        g_last_screen[1] = (int64_t)screen_stats[5];
+    }
     for (std::unique_ptr<Pipeline>& q : jp.pipes) q->ident_ok = stream_ident;
     jp.give_back(rc == SD_OK);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
@@ -682,6 +782,35 @@ int sd_run_files_devices(const char* reads_fa, const char* monomers_fa, const sd
     const std::vector<int32_t> devs(devices, devices + n_devices);
     return run_files_impl(reads_fa, monomers_fa, &q, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
                           lr_coef, nullptr, errbuf, errlen, records_out, &devs);
+}
+
+int sd_run_files_screen(const char* reads_fa, const char* monomers_fa, const sd_params* p, const int32_t* devices,
+                        int32_t n_devices, const char* raw_tsv_out, const char* final_tsv_out, const char* alt_tsv_out,
+                        int32_t min_identity, int32_t second_best, const double* lr_coef, int32_t screen_thr,
+                        const char* screen_tsv_out, const char* records_out, int64_t* counts, char* errbuf, size_t errlen) {
+    if (!p) return SD_ERR_PARAM;
+    const ScreenOpt so{screen_thr, screen_tsv_out};
+    sd_params q = *p;
+    std::vector<int32_t> devs{q.device};
+    if (devices || n_devices > 0) {
+        // parameter errors of the screen come before the device list is looked at (they need no device)
+        if (records_out) { set_err(errbuf, errlen, "--screen: the record stream holds whole reads"); return SD_ERR_PARAM; }
+        if (screen_thr < 0) { set_err(errbuf, errlen, "--screen: the threshold must be >= 0"); return SD_ERR_PARAM; }
+        const int rc = check_device_list("sd_run_files_screen", devices, n_devices, errbuf, errlen);
+        if (rc) return rc;
+        devs.assign(devices, devices + n_devices);
+        q.device = devices[0];
+    }
+    const int rc = run_files_impl(reads_fa, monomers_fa, &q, 0, 1, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity, second_best,
+                                  lr_coef, nullptr, errbuf, errlen, records_out, &devs, &so);
+    if (rc == SD_OK && counts) {
+        std::lock_guard<std::mutex> lk(g_last_m);
+        counts[0] = g_last_screen[0];
+        counts[1] = g_last_screen[1];
+        counts[2] = (int64_t)g_last_run[22];
+        counts[3] = (int64_t)g_last_run[23];
+    }
+    return rc;
 }
 
 int sd_last_run_device_stats(int64_t* batches, double* busy_ms, int32_t cap) {

@@ -28,6 +28,11 @@ Two more text files are this package's own (opt-in, `--profile`):
                       meaning 255 or more -- or '.').  Instances of m' are reverse-complemented onto m, as in the
                       profile, so the lines of one monomer are a multiple alignment.  read_msa / write_msa below.
 
+  <out>_screen.tsv    (`--screen THR`) one line per region that was decomposed, no header: read, start, end (0-based,
+                      inclusive), chunks (passing chunks the region was made of), best_distance (the smallest infix
+                      edit distance of a monomer or reverse complement against one of them), best_template (its name,
+                      with ' for a reverse complement).  read_screen / write_screen below.
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -558,4 +563,40 @@ def read_msa(path):
                 out.append(MsaRow(x[0], int(x[1]), int(x[2]), x[3], x[4], _msa_ins(x[5])))
             except ValueError as e:
                 raise FormatError(path, lineno, str(e))
+    return out
+
+
+# ---- screen ---------------------------------------------------------------------------------------
+ScreenRow = namedtuple("ScreenRow", "read start end chunks best_distance best_template")   # a line of <out>_screen.tsv
+
+
+def format_screen(rows):
+    """One line per region: read, start, end (0-based, inclusive), passing chunks, the smallest infix edit distance of
+    a template against one of them, and that template's name (' marks a reverse complement).  No header."""
+    return "".join("%s\t%d\t%d\t%d\t%d\t%s\n" % (r.read, r.start, r.end, r.chunks, r.best_distance, r.best_template)
+                   for r in rows)
+
+
+def write_screen(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_screen(rows))
+
+
+def parse_screen(text):
+    return _parse(text, True, 6, (_ident, int, int, int, int, _ident), ScreenRow)
+
+
+def read_screen(path):
+    """<out>_screen.tsv -> [ScreenRow]."""
+    return _parse(path, False, 6, (_ident, int, int, int, int, _ident), ScreenRow)
+
+
+def screen_rows(regions, read_names, mono_names):
+    """lib.screen_regions' array -> [ScreenRow]; template j >= len(mono_names) is the reverse complement of j - len."""
+    n = len(mono_names)
+    out = []
+    for g in regions:
+        j = int(g["best_key"]) & 0xffff
+        out.append(ScreenRow(read_names[int(g["read"])], int(g["start"]), int(g["end_incl"]), int(g["n_chunks"]),
+                             int(g["best_key"]) >> 16, mono_names[j] if j < n else mono_names[j - n] + "'"))
     return out

@@ -55,6 +55,9 @@ EXPORTS = [
     "sd_text_raw_size_dev", "sd_text_raw_write_dev", "sd_text_final_host", "sd_text_raw_host",
     "sd_msa_row_offsets", "sd_msa_segments", "sd_msa_segments_dev", "sd_msa_tables_create", "sd_msa_tables_destroy",
     "sd_msa_final_size_dev", "sd_msa_final_write_dev", "sd_msa_kernel_bench",
+    "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
+    "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
+    "sd_screen_kernel_bench",
 ]
 
 
@@ -278,11 +281,32 @@ def load():
     L.sd_text_final_host.argtypes = [V, V, I64, V, V, C.c_int32, C.c_int32, P(V), P(I64), P(V), P(I64), V, V, V, V,
                                      C.c_char_p, C.c_size_t]
     L.sd_text_raw_host.argtypes = [V, V, I64, V, C.c_int32, P(V), P(I64), V, V, C.c_char_p, C.c_size_t]
+    L.sd_screen_create.argtypes = [P(C.c_char_p), P(C.c_int32), C.c_int32, C.c_int32, P(V), C.c_char_p, C.c_size_t]
+    L.sd_screen_destroy.argtypes = [V]
+    L.sd_screen_destroy.restype = None
+    L.sd_screen_set_general.argtypes = [V, C.c_int32]
+    L.sd_screen_kernel.argtypes = [V, P(C.c_int32)]
+    L.sd_screen_kernel_ms.argtypes = [V, C.c_int32]
+    L.sd_screen_kernel_ms.restype = C.c_double
+    L.sd_screen_kernel_bench.argtypes = [V, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), C.c_char_p, C.c_size_t]
+    L.sd_run_files_screen.argtypes = [C.c_char_p, C.c_char_p, P(Params), P(C.c_int32), C.c_int32, C.c_char_p, C.c_char_p,
+                                      C.c_char_p, C.c_int32, C.c_int32, P(C.c_double), C.c_int32, C.c_char_p, C.c_char_p,
+                                      P(I64), C.c_char_p, C.c_size_t]
+    L.sd_screen_chunks.argtypes = [V, P(C.c_char_p), P(I64), C.c_int32, C.c_int32, C.c_int32, V, I64, P(I64), C.c_char_p,
+                                   C.c_size_t]
+    L.sd_screen_chunks_dev.argtypes = [V, V, P(I64), P(I64), C.c_int32, C.c_int32, C.c_int32, V, V, I64, P(I64), C.c_char_p,
+                                       C.c_size_t]
+    L.sd_screen_chunks_host.argtypes = [P(C.c_char_p), P(C.c_int32), C.c_int32, P(C.c_char_p), P(I64), C.c_int32, C.c_int32,
+                                        C.c_int32, V, I64, P(I64), C.c_char_p, C.c_size_t]
+    L.sd_screen_regions.argtypes = [V, V, I64, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, I64, P(I64), C.c_char_p,
+                                    C.c_size_t]
     _lib = L
     return L
 
 
 def _b(s):
+    if isinstance(s, (memoryview, bytearray)):   # (region_reads' slices)
+        return bytes(s)
     return s if isinstance(s, bytes) else s.encode()
 
 
@@ -393,18 +417,36 @@ def decompose_files(reads_fa, monomers_fa, raw_tsv_out, **kw):
 
 
 def run_files(reads_fa, monomers_fa, raw_tsv_out, final_tsv_out, alt_tsv_out, min_identity=0, second_best=False,
-              lr_coef=(-31.48494996, 0.41784018, 0.69186882), records_out=None, devices=None, profile=False, **kw):
+              lr_coef=(-31.48494996, 0.41784018, 0.69186882), records_out=None, devices=None, profile=False, screen=None,
+              screen_tsv_out=None, **kw):
     """The whole CLI job natively (sd_run_files): raw, final and _alt TSV files from the two FASTA files; with
     records_out also the binary record stream of the raw rows (sd_run_files_records).  devices (a list of ordinals,
     repeats allowed): one pipeline per entry in this process (sd_run_files_devices; `device` is then ignored), the
     same output bytes.  profile=True (SD_FLAG_PROFILE): also the column profiles of the monomers over the rows of the
-    final TSV, returned as a formats.Profile (and by last_run_profile()); the three files are unchanged."""
+    final TSV, returned as a formats.Profile (and by last_run_profile()); the three files are unchanged.
+    screen=THR (sd_run_files_screen): only the regions of the reads whose chunks come within infix edit distance THR of a
+    monomer are decomposed -- per region the rows of the plain job on its substring, positions in the parent read;
+    screen_tsv_out: the region file (formats.read_screen).  last_run_screen() gives the job's counts."""
     L = load()
     if profile:
         kw["flags"] = int(kw.get("flags", 0)) | FLAG_PROFILE
     p = make_params(**kw)
     err = C.create_string_buffer(4096)
     coef = (C.c_double * 3)(*[float(x) for x in lr_coef])
+    if screen is not None:
+        devs = None if devices is None else [int(d) for d in devices]
+        arr = None if devs is None else (C.c_int32 * max(len(devs), 1))(*devs)
+        counts = (C.c_int64 * 4)()
+        rc = L.sd_run_files_screen(os.fsencode(reads_fa), os.fsencode(monomers_fa), C.byref(p), arr, 0 if devs is None else len(devs),
+                                   os.fsencode(raw_tsv_out), os.fsencode(final_tsv_out), os.fsencode(alt_tsv_out),
+                                   int(min_identity), 1 if second_best else 0, coef, int(screen),
+                                   None if screen_tsv_out is None else os.fsencode(screen_tsv_out),
+                                   None if records_out is None else os.fsencode(records_out), counts, err, 4096)
+        if rc != SD_OK:
+            raise SdError(rc, err.value.decode(errors="replace"))
+        global _last_screen
+        _last_screen = {"reads": counts[0], "reads_with_region": counts[1], "bases_read": counts[2], "bases_decomposed": counts[3]}
+        return last_run_profile() if profile else None
     if devices is not None:
         devs = [int(d) for d in devices]
         arr = (C.c_int32 * max(len(devs), 1))(*devs)
@@ -423,6 +465,14 @@ def run_files(reads_fa, monomers_fa, raw_tsv_out, final_tsv_out, alt_tsv_out, mi
     if rc != SD_OK:
         raise SdError(rc, err.value.decode(errors="replace"))
     return last_run_profile() if profile else None
+
+
+_last_screen = None
+
+
+def last_run_screen():
+    """Counts of the last run_files(screen=...) of this process: reads, reads_with_region, bases_read, bases_decomposed."""
+    return _last_screen
 
 
 def _profile_from(fn, *lead, numpy=True):
@@ -766,7 +816,9 @@ def last_run_stats():
     L.sd_last_run_stats(v)
     keys = ("fill_ms", "trace_ms", "compact_ms", "ident_ms", "ident_pairs", "batches", "rows", "pack_ms", "wait_ms",
             "raw_text_ms", "post_ms", "io_ms", "text_identity_ms", "final_text_ms", "total_ms", "alloc_ms", "setup_ms",
-            "assemble_ms", "homo_pairs", "homo_full_pairs")
+            "assemble_ms", "homo_pairs", "homo_full_pairs",
+            # a screened job (run_files(screen=...)): the screen's wall and kernel time, bases read and decomposed
+            "screen_ms", "screen_kernel_ms", "screen_bases_read", "screen_bases_decomposed")
     return dict(zip(keys, [float(x) for x in v]))
 
 
@@ -2293,3 +2345,228 @@ def format_alt_rows(read_name, key_names, starts, ends, own_key, vals, threads=1
     data = C.string_at(out, ln.value).decode()
     L.sd_free(out)
     return data
+
+
+# ---- the screen: decompose only the stretches where a monomer occurs (csrc/sd_screen.hip) ----------------------------
+ScreenKeys = namedtuple("ScreenKeys", "chunk_read chunk_off chunk_len key")
+"""The chunks of a read set in chunk-table order: chunk_read (int32), chunk_off (int64, in the read), chunk_len (int32)
+and key (uint32: (smallest infix edit distance of a template against the chunk) << 16 | the first template that has
+it; templates = the monomers, then their reverse complements).  key is a numpy array, or an int32 torch tensor on the
+device (the same bits) when Screener.chunks(device_out=True) made it."""
+
+
+def screen_region_dtype():
+    """numpy dtype of sd_screen_region (include/sd_hip.h)."""
+    import numpy as np
+    return np.dtype([("read", "<i4"), ("start", "<i8"), ("end_incl", "<i8"), ("n_chunks", "<i4"), ("best_key", "<u4")],
+                    align=True)
+
+
+def chunk_table(read_lens, part_size=5000, overlap=500):
+    """(chunk_read, chunk_off, chunk_len) of the reads' standard chunk plan (main.cpp:70-81), as numpy arrays."""
+    import numpy as np
+    cr, co, cl = [], [], []
+    for r, n in enumerate(read_lens):
+        for o, ln in chunk_plan(int(n), int(part_size), int(overlap)):
+            cr.append(r)
+            co.append(o)
+            cl.append(ln)
+    return np.array(cr, dtype=np.int32), np.array(co, dtype=np.int64), np.array(cl, dtype=np.int32)
+
+
+def _mono_args(mono_seqs):
+    ms = [_b(s) for s in mono_seqs]
+    return ms, _strs(ms), (C.c_int32 * max(len(ms), 1))(*[len(s) for s in ms])
+
+
+def screen_chunks_host(mono_seqs, reads, part_size=5000, overlap=500):
+    """The screen's keys without a device (sd_screen_chunks_host: a plain DP, exact and slow) -> ScreenKeys."""
+    import numpy as np
+    L = load()
+    ms, mp, ml = _mono_args(mono_seqs)
+    rs = reads if isinstance(reads, ReadSet) else ReadSet(reads)
+    cr, co, cl = chunk_table([len(s) for s in rs.seqs], part_size, overlap)
+    key = np.zeros(max(len(cr), 1), dtype=np.uint32)
+    n = C.c_int64()
+    err = C.create_string_buffer(4096)
+    rc = L.sd_screen_chunks_host(mp, ml, len(ms), rs.ptrs, rs.lens, rs.n, int(part_size), int(overlap), key.ctypes.data,
+                                 len(key), C.byref(n), err, 4096)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace"))
+    assert n.value == len(cr)
+    return ScreenKeys(cr, co, cl, key[:len(cr)])
+
+
+class Screener:
+    """The screen on one device (sd_screen_*): the handle holds the templates, their match masks and scratch.
+    chunks() gives one key per chunk of the reads' chunk plan; screen_regions() turns keys and a threshold into regions,
+    region_reads() / rows_from_regions() carry them through an unchanged Stream or Engine."""
+
+    def __init__(self, mono_seqs, device=0, general=False):
+        self.L = load()
+        self._err = C.create_string_buffer(4096)
+        ms, mp, ml = _mono_args(mono_seqs)
+        self.h = C.c_void_p()
+        self.device = int(device)
+        self._check(self.L.sd_screen_create(mp, ml, len(ms), self.device, C.byref(self.h), self._err, 4096))
+        if general:   # the general distance kernel where the uniform one would run (A/B, tests)
+            self._check(self.L.sd_screen_set_general(self.h, 1))
+
+    def _check(self, rc):
+        if rc != SD_OK:
+            raise SdError(rc, self._err.value.decode(errors="replace"))
+
+    def close(self):
+        if self.h:
+            self.L.sd_screen_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def kernel_ms(self, reset=False):
+        """Device time of the kernels of the calls so far whose keys came back to the host (ms)."""
+        return float(self.L.sd_screen_kernel_ms(self.h, 1 if reset else 0))
+
+    def kernel_bench(self, warmup=2, reps=5):
+        """(screen_ms, dist_ms): the screen's launch beside the --ed_thr distance kernel alone on the batch of the last
+        chunks() call with host reads, alternating, each between two HIP events (sd_screen_kernel_bench)."""
+        a, b = (C.c_float * reps)(), (C.c_float * reps)()
+        self._check(self.L.sd_screen_kernel_bench(self.h, int(warmup), int(reps), a, b, self._err, 4096))
+        return list(a), list(b)
+
+    def kernel(self):
+        """The instantiation a call launches, named as tests/prefilter_cases.kernel_of names it."""
+        w = C.c_int32()
+        k = self.L.sd_screen_kernel(self.h, C.byref(w))
+        return "sd_hw_dist<%d>" % w.value if k == 0 else "sd_hw_dist_u<%d,%s>" % (w.value, "hi" if k == 2 else "lo")
+
+    def chunks(self, reads, part_size=5000, overlap=500, stream=None, device_out=False):
+        """-> ScreenKeys of the reads: a read list, a ReadSet, or a DeviceReads (packed on the device, ordered behind
+        reads.stream -- or `stream` -- by events; the buffer is free for later work on that stream when this returns).
+        device_out=True (DeviceReads only): key stays on the device as an int32 torch tensor, written in order with
+        that stream and without a host-side wait."""
+        import numpy as np
+        n = C.c_int64()
+        if isinstance(reads, DeviceReads):
+            cr, co, cl = chunk_table(reads.read_lens, part_size, overlap)
+            st = reads.stream if stream is None else (stream if isinstance(stream, int) else int(stream.cuda_stream))
+            if device_out:
+                import torch
+                dev = torch.device("cuda", reads.device)
+                with torch.cuda.stream(_torch_stream(torch, dev, st)):
+                    key = torch.empty(max(len(cr), 1), dtype=torch.int32, device=dev)
+                kp, cap = C.c_void_p(key.data_ptr()), key.numel()
+            else:
+                key = np.zeros(max(len(cr), 1), dtype=np.uint32)
+                kp, cap = C.c_void_p(key.ctypes.data), len(key)
+            self._check(self.L.sd_screen_chunks_dev(self.h, C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n,
+                                                    int(part_size), int(overlap), C.c_void_p(st), kp, cap, C.byref(n),
+                                                    self._err, 4096))
+            assert n.value == len(cr)
+            return ScreenKeys(cr, co, cl, key[:len(cr)])
+        if device_out:
+            raise SdError(SD_ERR_PARAM, "Screener.chunks: device_out needs reads in device memory (a DeviceReads)")
+        rs = reads if isinstance(reads, ReadSet) else ReadSet(reads)
+        cr, co, cl = chunk_table([len(s) for s in rs.seqs], part_size, overlap)
+        key = np.zeros(max(len(cr), 1), dtype=np.uint32)
+        self._check(self.L.sd_screen_chunks(self.h, rs.ptrs, rs.lens, rs.n, int(part_size), int(overlap), key.ctypes.data,
+                                            len(key), C.byref(n), self._err, 4096))
+        assert n.value == len(cr)
+        return ScreenKeys(cr, co, cl, key[:len(cr)])
+
+
+def screen_regions(keys, read_lens, thr, part_size=5000, overlap=500):
+    """The regions of a threshold (sd_screen_regions, host only): a maximal run a..b of consecutive chunks of one read
+    with key >> 16 <= thr is the bytes [a * part_size, min(len, (b + 1) * part_size + overlap)) of that read.  keys: a
+    ScreenKeys (a device key is copied to the host: 4 bytes per chunk).  -> structured array (screen_region_dtype()):
+    read, start, end_incl, n_chunks, best_key, in read order, then position order."""
+    import numpy as np
+    L = load()
+    key = keys.key
+    if hasattr(key, "cpu"):
+        key = key.cpu().numpy().view(np.uint32)
+    key = np.ascontiguousarray(key, dtype=np.uint32)
+    cr = np.ascontiguousarray(keys.chunk_read, dtype=np.int32)
+    if len(cr) != len(key):
+        raise SdError(SD_ERR_PARAM, "screen_regions: %d keys for %d chunks" % (len(key), len(cr)))
+    lens = np.ascontiguousarray(read_lens, dtype=np.int64)
+    out = np.zeros(max(len(key), 1), dtype=screen_region_dtype())
+    n = C.c_int64()
+    err = C.create_string_buffer(4096)
+    rc = L.sd_screen_regions(key.ctypes.data, cr.ctypes.data, len(key), lens.ctypes.data, len(lens), int(part_size),
+                             int(overlap), int(thr), out.ctypes.data, len(out), C.byref(n), err, 4096)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace"))
+    return out[:n.value].copy()
+
+
+def region_reads(reads, regions):
+    """The regions as reads of their own, without moving a base: for a read list memoryview slices of the parents' bytes,
+    for a DeviceReads a DeviceReads on the same buffer and stream with the regions' offsets and lengths."""
+    if isinstance(reads, DeviceReads):
+        off = [reads.read_off[int(g["read"])] + int(g["start"]) for g in regions]
+        lens = [int(g["end_incl"]) - int(g["start"]) + 1 for g in regions]
+        return DeviceReads(_KeepAlive((reads.ptr, reads.nbytes, reads.device), reads.data), lens, offsets=off,
+                           stream=reads.stream)
+    seqs = reads.seqs if isinstance(reads, ReadSet) else [_b(s) for s in reads]
+    return [memoryview(seqs[int(g["read"])])[int(g["start"]):int(g["end_incl"]) + 1] for g in regions]
+
+
+class _KeepAlive(tuple):
+    """DeviceReads' (ptr, nbytes, device) form of a buffer, with the object that owns it kept alive."""
+
+    def __new__(cls, t, keep):
+        self = super().__new__(cls, t)
+        self.keep = keep
+        return self
+
+
+def rows_from_regions(rows, row_off, regions, n_reads):
+    """Rows of a job whose reads were regions (region_reads) -> rows of the parent reads: starts and ends shifted by
+    the region's start, row_off rebuilt per parent read (n_reads + 1).  Host rows: a structured array with start / end
+    fields (final_dtype() rows also get their read index mapped back) or an int32 [n, 4] array (tmpl, start, end, score),
+    with a numpy row_off -> (rows, row_off).  A DeviceRows or DeviceFinalRows (row_off ignored): torch ops on its device
+    -> the same type."""
+    import numpy as np
+    g_read = np.ascontiguousarray(regions["read"], dtype=np.int64)
+    g_start = np.ascontiguousarray(regions["start"], dtype=np.int64)
+    if isinstance(rows, (DeviceRows, DeviceFinalRows)):
+        import torch
+        dr = rows
+        dev = dr.rows.device
+        off = dr.row_off.to(torch.int64)
+        cnt = off[1:] - off[:-1]
+        shift = torch.repeat_interleave(torch.as_tensor(g_start, device=dev), cnt)
+        per_read = torch.zeros(n_reads, dtype=torch.int64, device=dev)
+        if len(g_read):
+            per_read.index_add_(0, torch.as_tensor(g_read, device=dev), cnt)
+        new_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(per_read, 0)])
+        out = dr.rows.clone()
+        if isinstance(dr, DeviceRows):
+            out[:, 1:3] += shift.to(torch.int32)[:, None]
+            return DeviceRows(out, new_off, dr.n_rows)
+        w = out.view(torch.int64)            # sd_final_row: read (int32) at 0, start at 8, end at 16
+        w[:, 1:3] += shift[:, None]
+        rd = torch.repeat_interleave(torch.as_tensor(g_read, device=dev), cnt).to(torch.int32)
+        out.view(torch.int32)[:, 0] = rd
+        return DeviceFinalRows(out, new_off, dr.alt, dr.n_rows)
+    off = np.ascontiguousarray(row_off, dtype=np.int64)
+    if len(off) != len(g_read) + 1:
+        raise SdError(SD_ERR_PARAM, "rows_from_regions: row_off has %d entries for %d regions" % (len(off), len(g_read)))
+    cnt = off[1:] - off[:-1]
+    shift = np.repeat(g_start, cnt)
+    out = np.array(rows, copy=True)
+    if out.dtype.names:
+        out["start"] += shift.astype(out.dtype["start"])
+        out["end"] += shift.astype(out.dtype["end"])
+        if "read" in out.dtype.names:
+            out["read"] = np.repeat(g_read, cnt)
+    else:
+        out = out.reshape(-1, 4)
+        out[:, 1:3] += shift.astype(out.dtype)[:, None]
+    per_read = np.bincount(g_read, weights=cnt, minlength=n_reads).astype(np.int64) if len(g_read) else np.zeros(n_reads, dtype=np.int64)
+    return out, np.concatenate([[0], np.cumsum(per_read)]).astype(np.int64)

@@ -356,7 +356,7 @@ def convert_tsv(decomposition, reads, monomers, outfile, identity_th, light, thr
 
 def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr, overlap, logger,
         ref_compat=False, device=0, kernel=0, final_file=None, min_identity=0, second_best=False, records_file=None,
-        devices=None, profile=False):
+        devices=None, profile=False, screen=None, screen_file=None):
     """main.py:186-197 with the subprocess replaced by libsd_hip.so.
 
     Single process with final_file given: ONE native call (sd_run_files) streams the job through the
@@ -422,7 +422,11 @@ def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr,
                       # the dp binary's progress lines on stderr (main.cpp:82,115,393); --profile: the counters stay in the
                       # library until main() writes them (lib.last_run_profile(numpy=False): no numpy import on this path)
                       flags=lib.FLAG_PROGRESS | (lib.FLAG_PROFILE if profile else 0),
-                      records_out=records_file, devices=devices)
+                      records_out=records_file, devices=devices, screen=screen, screen_tsv_out=screen_file)
+        if screen is not None:
+            c = lib.last_run_screen()
+            logger.info("Screen (threshold %d): %d reads, %d with a region, %d bases read, %d bases decomposed"
+                        % (screen, c["reads"], c["reads_with_region"], c["bases_read"], c["bases_decomposed"]))
         return True
     lib.decompose_files(sequences, monomers, raw_file, scoring=(ins, dels, mm, match),
                         part_size=int(batch_size), overlap=int(overlap), ed_thr=int(ed_thr),
@@ -490,6 +494,21 @@ def _check_profile(args, flag="--profile", why="a profile needs one template per
             sys.stderr.write("stringdecomposer: %s: monomer name %s is not unique: %s\n" % (flag, n, why))
             sys.exit(lib.SD_ERR_PARAM)
         seen.add(n)
+
+
+def _check_screen(args):
+    """--screen requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
+    def refuse(msg):
+        sys.stderr.write("stringdecomposer: %s\n" % msg)
+        sys.exit(2)
+    if shard.world()[2] > 1:
+        refuse("--screen cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
+    if args.screen < 0:
+        refuse("--screen %d: the threshold is an edit distance, at least 0" % args.screen)
+    if args.records:
+        refuse("--screen cannot be combined with --records: the record stream holds whole reads")
+    if args.overlap.isdigit() and args.batch_size.isdigit() and int(args.overlap) >= int(args.batch_size):
+        refuse("--screen needs -v/--overlap smaller than -b/--batch-size (the regions of a read must not overlap)")
 
 
 def _write_msa(args, final_fn, msa_fn, device):
@@ -564,7 +583,14 @@ def main(argv=None):
                         help="also write <out-file>_msa.tsv: one line per row of <out-file>.tsv with the read's bases by column "
                              "of the forward monomer (ACGTN, '-' = deleted) and its insertions as slot:count (a count of 255 "
                              "means 255 or more)")
+    parser.add_argument("--screen", type=int, default=None, metavar="THR",
+                        help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
+                             "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
+                             "decomposed as reads of their own (positions stay those of the whole read); also writes "
+                             "<out-file>_screen.tsv, one line per stretch")
     args = parser.parse_args(argv)
+    if args.screen is not None:
+        _check_screen(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -592,7 +618,8 @@ def main(argv=None):
                                 final_file=convert_tsv_fn, min_identity=int(args.min_identity),
                                 second_best=args.second_best,
                                 records_file=records_fn if shard.world()[2] == 1 else None, devices=devices,
-                                profile=args.profile)
+                                profile=args.profile, screen=args.screen,
+                                screen_file=os.path.join(args.out_dir, args.out_file + "_screen.tsv") if args.screen is not None else None)
     except lib.SdError as e:
         # the reference dies with CalledProcessError after the binary printed its message on stderr
         sys.stderr.write(e.msg + "\n")
@@ -611,6 +638,8 @@ def main(argv=None):
             part_size=int(args.batch_size), overlap=int(args.overlap), ed_thr=int(args.ed_thr)))
     if records_fn:
         logger.info("Saved the binary record stream to " + records_fn)
+    if args.screen is not None:
+        logger.info("Saved the screened regions to " + os.path.join(args.out_dir, args.out_file + "_screen.tsv"))
     logger.info("Transforming raw alignments...")
     if raw_decomposition is not True:
         # multi-GPU launch: rank 0 holds the raw TSV of the whole job; convert_tsv (main.py:168-184) natively,
