@@ -73,6 +73,40 @@ typedef struct sd_params {
                                       selected on the device and stay there (sd_stream_peek_final_dev / sd_stream_collect_final_dev) */
 #define SD_FLAG_DEVICE_PROFILE 4096 /* SD_FLAG_DEVICE_FINAL streams: the column profiles of the kept rows are folded on the device
                                       from the job's text in HBM (sd_stream_profile / sd_stream_profile_dev) */
+#define SD_FLAG_LENIENT 8192       /* every entry point that opens the two files: the lenient reading of both (below); the
+                                      default, without it, reproduces the reference's errors byte for byte */
+
+/* ---- lenient input (a documented superset of the reference, never the default) -------------------------------
+ * The rule for a sequence byte (csrc/sd_normalize.hpp, one text for host and device): a-z becomes the upper-case
+ * letter; then any of R Y S W K M B D H V becomes N; every other byte stays, so U, digits, '*', '-', a stray CR and
+ * bytes >= 0x80 are still reported by the checks that exist, in their words.  N keeps the reference's meaning: an
+ * ordinary symbol that matches N only (main.cpp:190) -- a monomer that holds an ambiguity code matches a read's N
+ * there and nothing else.
+ * Files (SD_FLAG_LENIENT): besides the rule, a CR directly in front of a newline is dropped from header and sequence
+ * lines.  A record the rule changes gets a buffer of its own; a canonical one-line record stays in the mapping.
+ * FASTQ needs no flag: a file whose first non-blank byte is '@' is read as four-line records (name = first whitespace
+ * token behind '@'; the third line must begin with '+' -- multi-line FASTQ is SD_ERR_FORMAT; the fourth must have the
+ * sequence's length and is never looked at otherwise).  Its sequences are strict without the flag, lenient with it.
+ * Not read: gzip / BGZF. */
+
+/* out[0, n) = the rule applied to in[0, n); out may equal in.  stats (may be NULL) are ADDED to: [0] lower-case bytes
+ * folded, [1] ambiguity codes turned into N, [2] bytes still outside A C G T N afterwards, [3] bytes examined.
+ * SD_ERR_PARAM for n < 0 or a NULL buffer with n > 0. */
+int sd_normalize_host(const char* in, char* out, int64_t n, uint64_t stats[4]);
+/* The same for reads that lie in the memory of `device`: read r = the read_lens[r] bytes at d_in + read_off[r] (host
+ * arrays, as in sd_stream_submit_dev: gaps, padding and any order are allowed, overlapping reads are not), written at
+ * d_out + read_off[r].  Only the bytes of the reads are read or written; d_out == d_in normalises in place, otherwise
+ * the two must not overlap.  d_stats (may be NULL): four uint64 counters in device memory, added to as above.  The
+ * kernel is enqueued on hip_stream and the call returns without waiting for it.
+ * SD_ERR_PARAM for a bad argument or memory that is not device memory (or reads that end outside the allocation),
+ * SD_ERR_UNSUPPORTED for another device's memory, SD_ERR_NO_DEVICE without a device. */
+int sd_normalize_dev(const void* d_in, void* d_out, const int64_t* read_off, const int64_t* read_lens,
+                     int32_t n_reads, int32_t device, void* hip_stream, uint64_t* d_stats,
+                     char* errbuf, size_t errlen);
+/* What the file indexes of the last call of this process that opened a reads and a monomers file met, summed over the
+ * two: [0] lower-case bases folded, [1] ambiguity codes turned into N, [2] CRs dropped, [3] records copied because the
+ * rule changed them, [4] FASTQ records, [5] 1 if the call was lenient, [6..7] 0. */
+void sd_last_run_input_stats(int64_t out[8]);
 
 void sd_params_default(sd_params* p); /* -1,-1,-1,1 / 5000 / 500 / -1 / 1 / 0 / auto */
 
@@ -792,6 +826,8 @@ typedef struct sd_fasta {
     int32_t has_n;
 } sd_fasta;
 int sd_fasta_load(const char* path, sd_fasta* out, char* errbuf, size_t errlen);
+/* The same with flags: SD_FLAG_LENIENT reads the file leniently (above); sd_fasta_load is flags == 0.  Both read FASTQ. */
+int sd_fasta_load_ex(const char* path, int32_t flags, sd_fasta* out, char* errbuf, size_t errlen);
 void sd_fasta_free(sd_fasta* f);
 
 /* ---- post-processing helper (host): identity of a read segment vs a template ---------------

@@ -1107,11 +1107,15 @@ static int decompose_files_impl(const char* reads_fa, const char* monomers_fa, c
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     if (!reads_fa || !monomers_fa || (!raw_tsv_out && !records_out)) return SD_ERR_PARAM;
     sd::FastaFile rf, mf;
-    rc = rf.open(reads_fa, p->threads, err);                                  // main.cpp:394
+    rc = rf.open(reads_fa, p->threads, err, lenient_of(p));                   // main.cpp:394
     if (rc == SD_OK) rc = rf.validate(0, rf.recs.size(), p->threads, err);
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);              // main.cpp:395
+    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err, lenient_of(p));   // main.cpp:395
     if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    sd_note_input_stats(rf, mf, lenient_of(p));
+    sd_params p_job = *p;   // (the files are read: the pipelines and their cache keys never see the flag)
+    p_job.reserved[1] &= ~SD_FLAG_LENIENT;
+    p = &p_job;
     std::vector<sd::Seq> monos;
     for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
     std::string out;
@@ -1153,10 +1157,14 @@ static int decompose_files_range_impl(const char* reads_fa, const char* monomers
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     sd::FastaFile rf, mf;
-    rc = rf.open(reads_fa, p->threads, err);
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);
+    rc = rf.open(reads_fa, p->threads, err, lenient_of(p));
+    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err, lenient_of(p));
     if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    sd_note_input_stats(rf, mf, lenient_of(p));
+    sd_params p_job = *p;   // (the files are read: the pipelines and their cache keys never see the flag)
+    p_job.reserved[1] &= ~SD_FLAG_LENIENT;
+    p = &p_job;
     std::vector<sd::Seq> monos;
     for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
     if (monos.empty()) { set_err(errbuf, errlen, "no monomers"); return SD_ERR_PARAM; }

@@ -28,7 +28,12 @@
 #include "sd_records.hpp"
 #include "sd_seam.hpp"
 
+// what the indexes of a job's two files met (sd_last_run_input_stats; defined in sd_host_api.hip)
+void sd_note_input_stats(const sd::FastaFile& reads, const sd::FastaFile& monomers, bool lenient);
+
 namespace {
+
+inline bool lenient_of(const sd_params* p) { return (p->reserved[1] & SD_FLAG_LENIENT) != 0; }
 
 inline void set_err(char* buf, size_t len, const std::string& m) {
     if (buf && len) {

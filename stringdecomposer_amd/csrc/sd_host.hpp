@@ -33,6 +33,7 @@
 
 #include "../../include/sd_hip.h"
 #include "sd_final_dev.hpp"
+#include "sd_normalize.hpp"
 
 namespace sd {
 
@@ -572,6 +573,16 @@ inline bool pack_chunk(const char* s, int32_t l, uint32_t* out) {
 // multi-line sequence is concatenated into a buffer of its own.  The alphabet {A,C,G,T,N} is enforced
 // per record (validate()); the first offending record in file order is reported with the reference's
 // text.  For a job sharded over ranks only the records a rank's chunk range touches need validating.
+//
+// FASTQ: a file whose first non-blank byte is '@' is read as four-line records (name line, sequence, a line that
+// begins with '+', a quality line of the sequence's length, which is never looked at otherwise).  A quality line may
+// begin with '@', '>' or '+', so record starts are every fourth LINE: the slabs count their newlines, a prefix sum
+// numbers the lines, and a second pass over the slabs takes the starts.  The sequence is used where it lies.
+//
+// Lenient mode (open(..., lenient = true); SD_FLAG_LENIENT): a '\r' directly in front of a '\n' is dropped, and the
+// rule of sd_normalize.hpp (lower case folded, IUPAC codes -> N) is applied to every sequence.  A record whose bytes
+// the rule changes gets a buffer of its own (as a multi-line record always does); one that is canonical on one line
+// stays in the mapping.  validate() then sees the normalised text, so a byte the rule leaves alone fails as ever.
 // ---------------------------------------------------------------------------------------------
 class FastaFile {
   public:
@@ -581,14 +592,19 @@ class FastaFile {
     };
     std::vector<Rec> recs;
     bool has_n = false;
+    bool fastq = false;
+    // what the index met: [0] lower-case bases folded, [1] ambiguity codes -> N, [2] CRs dropped, [3] records copied
+    // because the rule changed them (single-line FASTA, FASTQ), [4] FASTQ records
+    std::atomic<int64_t> in_stats[5] = {};
 
     FastaFile() = default;
     FastaFile(const FastaFile&) = delete;
     FastaFile& operator=(const FastaFile&) = delete;
     ~FastaFile() { close_(); }
 
-    int open(const std::string& path, int threads, std::string& err) {
+    int open(const std::string& path, int threads, std::string& err, bool lenient = false) {
         close_();
+        lenient_ = lenient;
         fd_ = ::open(path.c_str(), O_RDONLY);
         if (fd_ < 0) { err = "cannot open " + path; return SD_ERR_IO; }
         struct stat sb;
@@ -664,7 +680,8 @@ class FastaFile {
     const char* data_ = nullptr;
     size_t size_ = 0;
     std::string fallback_;
-    std::vector<std::string> owned_;   // concatenated multi-line sequences
+    std::vector<std::string> owned_;   // concatenated multi-line sequences, sequences the lenient rule changed
+    bool lenient_ = false;
 
     void close_() {
         if (map_) munmap(map_, size_);
@@ -676,10 +693,37 @@ class FastaFile {
         recs.clear();
         owned_.clear();
         fallback_.clear();
+        has_n = false;
+        fastq = false;
+        for (auto& c : in_stats) c.store(0, std::memory_order_relaxed);
+    }
+    void count(int which, int64_t v) { if (v) in_stats[which].fetch_add(v, std::memory_order_relaxed); }
+    // the end of the line [q, le) whose newline (if any) lies at le: lenient mode drops a CR in front of that newline
+    size_t line_end(size_t q, size_t le, int64_t& crs) const {
+        if (lenient_ && le > q && le < size_ && data_[le] == '\n' && data_[le - 1] == '\r') { ++crs; return le - 1; }
+        return le;
+    }
+    // lenient mode: the one-line sequence d[b, b + l) of record r, left in the mapping when the rule changes nothing
+    void take_line(size_t r, size_t b, size_t l) {
+        Rec& rc = recs[r];
+        rc.seq = data_ + b;
+        rc.len = (int64_t)l;
+        if (!lenient_ || !normalize_changes(rc.seq, rc.len)) return;
+        std::string& o = owned_[r];
+        o.resize(l);
+        uint64_t k[3] = {0, 0, 0};
+        normalize_span(data_ + b, &o[0], (int64_t)l, k);
+        count(0, (int64_t)k[0]); count(1, (int64_t)k[1]); count(3, 1);
+        rc.seq = o.data();
     }
     int index(int threads, std::string& err) {
         const char* d = data_;
         const size_t N = size_;
+        {
+            size_t f = 0;
+            while (f < N && (d[f] == '\n' || (lenient_ && d[f] == '\r'))) ++f;
+            if (f < N && d[f] == '@') return index_fastq(f, threads, err);
+        }
         // (1) record starts: '>' at offset 0 or right after a newline
         const size_t slab = (size_t)8 << 20;
         const int64_t n_slabs = (int64_t)((N + slab - 1) / slab);
@@ -704,7 +748,7 @@ class FastaFile {
             // record that does not exist, main.cpp:327)
             const size_t first = starts.empty() ? N : starts[0];
             for (size_t i = 0; i < first; ++i)
-                if (d[i] != '\n') { err = "FASTA does not start with a header"; return SD_ERR_FORMAT; }
+                if (d[i] != '\n' && !(lenient_ && d[i] == '\r')) { err = "FASTA does not start with a header"; return SD_ERR_FORMAT; }
         }
         const size_t R = starts.size();
         recs.assign(R, Rec{nullptr, 0, nullptr, 0});
@@ -726,28 +770,35 @@ class FastaFile {
             size_t pos = hdr_end < e ? hdr_end + 1 : e;
             // sequence lines: [pos, e)
             // fast path: exactly one non-empty line
+            int64_t crs = 0;
+            if (nl) (void)line_end(b, hdr_end, crs);
             size_t lines = 0, total = 0, first_b = 0, first_l = 0;
             for (size_t q = pos; q < e;) {
                 const char* n2 = static_cast<const char*>(std::memchr(d + q, '\n', e - q));
-                const size_t le = n2 ? (size_t)(n2 - d) : e;
+                const size_t nx = n2 ? (size_t)(n2 - d) : e, le = line_end(q, nx, crs);
                 if (le > q) {
                     if (lines == 0) { first_b = q; first_l = le - q; }
                     ++lines;
                     total += le - q;
                 }
-                q = le + 1;
+                q = nx + 1;
             }
+            count(2, crs);
             if (lines <= 1) {
-                rc.seq = d + first_b;
-                rc.len = (int64_t)first_l;
+                take_line((size_t)r, first_b, first_l);
             } else {
                 std::string& o = owned_[(size_t)r];
                 o.reserve(total);
                 for (size_t q = pos; q < e;) {
                     const char* n2 = static_cast<const char*>(std::memchr(d + q, '\n', e - q));
-                    const size_t le = n2 ? (size_t)(n2 - d) : e;
+                    const size_t nx = n2 ? (size_t)(n2 - d) : e, le = line_end(q, nx, crs);
                     if (le > q) o.append(d + q, le - q);
-                    q = le + 1;
+                    q = nx + 1;
+                }
+                if (lenient_) {
+                    uint64_t k[3] = {0, 0, 0};
+                    normalize_span(o.data(), &o[0], (int64_t)o.size(), k);
+                    count(0, (int64_t)k[0]); count(1, (int64_t)k[1]);
                 }
                 rc.seq = o.data();
                 rc.len = (int64_t)o.size();
@@ -755,6 +806,108 @@ class FastaFile {
         });
         for (size_t r = 0; r < R; ++r)
             if (bad[r]) { err = "FASTA header without a name"; return SD_ERR_FORMAT; }
+        return SD_OK;
+    }
+    // four-line FASTQ from offset `first` (the first '@')
+    int index_fastq(size_t first, int threads, std::string& err) {
+        fastq = true;
+        const char* d = data_ + first;
+        const size_t N = size_ - first;
+        // (1) line starts: a line starts at 0 and behind every newline; slab sl owns the starts in [b, e), found from
+        // the newlines in [b - 1, e - 1)
+        const size_t slab = (size_t)8 << 20;
+        const int64_t n_slabs = (int64_t)((N + slab - 1) / slab);
+        std::vector<int64_t> nl_before((size_t)n_slabs + 1, 0);
+        auto window = [&](int64_t sl, size_t& w0, size_t& w1) {
+            const size_t b = (size_t)sl * slab, e = std::min(N, b + slab);
+            w0 = b ? b - 1 : 0;
+            w1 = e - 1;               // (a newline at N - 1 starts no line)
+        };
+        parallel_for(n_slabs, threads, 1, [&](int64_t sl) {
+            size_t w0, w1;
+            window(sl, w0, w1);
+            int64_t c = 0;
+            for (const char* p = d + w0; p < d + w1;) {
+                p = static_cast<const char*>(std::memchr(p, '\n', (size_t)(d + w1 - p)));
+                if (!p) break;
+                ++c; ++p;
+            }
+            nl_before[(size_t)sl + 1] = c;
+        });
+        for (int64_t sl = 0; sl < n_slabs; ++sl) nl_before[(size_t)sl + 1] += nl_before[(size_t)sl];
+        std::vector<std::vector<size_t>> found((size_t)n_slabs);
+        parallel_for(n_slabs, threads, 1, [&](int64_t sl) {
+            size_t w0, w1;
+            window(sl, w0, w1);
+            std::vector<size_t>& out = found[(size_t)sl];
+            int64_t line = nl_before[(size_t)sl];   // number of the next line that starts
+            if (sl == 0) { out.push_back(0); }
+            for (const char* p = d + w0; p < d + w1;) {
+                p = static_cast<const char*>(std::memchr(p, '\n', (size_t)(d + w1 - p)));
+                if (!p) break;
+                ++line; ++p;
+                if ((line & 3) == 0) out.push_back((size_t)(p - d));
+            }
+        });
+        std::vector<size_t> starts;
+        for (auto& v : found) starts.insert(starts.end(), v.begin(), v.end());
+        // blank lines behind the last record are no record
+        size_t Nend = N;
+        while (!starts.empty()) {
+            bool blank = true;
+            for (size_t i = starts.back(); i < Nend && blank; ++i) blank = d[i] == '\n' || (lenient_ && d[i] == '\r');
+            if (!blank) break;
+            Nend = starts.back();
+            starts.pop_back();
+        }
+        const size_t R = starts.size();
+        recs.assign(R, Rec{nullptr, 0, nullptr, 0});
+        owned_.assign(R, std::string());
+        std::vector<uint8_t> bad(R, 0);   // 1 truncated, 2 no '@', 3 no name, 4 no '+', 5 quality length
+        // (2) every record on its own
+        parallel_for((int64_t)R, threads, 16, [&](int64_t r) {
+            const size_t b = starts[(size_t)r], e = (size_t)r + 1 < R ? starts[(size_t)r + 1] : Nend;
+            size_t lb[4], ll[4];
+            int64_t crs = 0;
+            size_t q = b;
+            for (int i = 0; i < 4; ++i) {
+                // (the quality line may be cut off or lack its newline: its length decides; the others need theirs)
+                const char* n2 = q < e ? static_cast<const char*>(std::memchr(d + q, '\n', e - q)) : nullptr;
+                if (!n2 && i < 3) { bad[(size_t)r] = 1; break; }
+                const size_t nx = n2 ? (size_t)(n2 - d) : e;
+                lb[i] = q;
+                ll[i] = line_end(first + q, first + nx, crs) - first - q;
+                q = nx + 1;
+            }
+            if (bad[(size_t)r]) {
+                if (d[b] != '@') bad[(size_t)r] = 2;
+                return;
+            }
+            if (d[lb[0]] != '@') { bad[(size_t)r] = 2; return; }
+            size_t a = lb[0] + 1;
+            const size_t hdr_end = lb[0] + ll[0];
+            while (a < hdr_end && is_ws(d[a])) ++a;
+            size_t z = a;
+            while (z < hdr_end && !is_ws(d[z])) ++z;
+            Rec& rc = recs[(size_t)r];
+            rc.name = d + a;
+            rc.name_len = z - a;
+            if (a == z) { bad[(size_t)r] = 3; return; }
+            if (ll[2] == 0 || d[lb[2]] != '+') { bad[(size_t)r] = 4; return; }
+            if (ll[3] != ll[1]) { bad[(size_t)r] = 5; return; }
+            count(2, crs);
+            take_line((size_t)r, first + lb[1], ll[1]);
+        });
+        count(4, (int64_t)R);
+        for (size_t r = 0; r < R; ++r) {
+            if (!bad[r]) continue;
+            static const char* const what[] = {"", "is truncated", "does not begin with '@'", "has a header without a name",
+                                               "has no '+' line behind its sequence (multi-line FASTQ is not supported)",
+                                               "has a quality line of another length than its sequence"};
+            err = "FASTQ record " + std::to_string(r + 1) +
+                  (recs[r].name_len ? " (" + std::string(recs[r].name, recs[r].name_len) + ")" : std::string()) + " " + what[bad[r]];
+            return SD_ERR_FORMAT;
+        }
         return SD_OK;
     }
 };

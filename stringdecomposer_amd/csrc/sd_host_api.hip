@@ -245,12 +245,16 @@ int sd_format_rows(const char* read_name, const char* const* tmpl_names, const s
 }
 
 int sd_fasta_load(const char* path, sd_fasta* out, char* errbuf, size_t errlen) {
+    return sd_fasta_load_ex(path, 0, out, errbuf, errlen);
+}
+
+int sd_fasta_load_ex(const char* path, int32_t flags, sd_fasta* out, char* errbuf, size_t errlen) {
     if (!out || !path) return SD_ERR_PARAM;
     std::memset(out, 0, sizeof *out);
     sd::FastaFile ff;
     std::string err;
     const int threads = std::max(1, std::min(32, (int)std::thread::hardware_concurrency()));
-    int rc = ff.open(path, threads, err);
+    int rc = ff.open(path, threads, err, (flags & SD_FLAG_LENIENT) != 0);
     if (rc == SD_OK) rc = ff.validate(0, ff.recs.size(), threads, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     const size_t n = ff.recs.size();
@@ -272,6 +276,21 @@ int sd_fasta_load(const char* path, sd_fasta* out, char* errbuf, size_t errlen) 
     return SD_OK;
 }
 
+int sd_normalize_host(const char* in, char* out, int64_t n, uint64_t stats[4]) {
+    if (n < 0 || (n > 0 && (!in || !out))) return SD_ERR_PARAM;
+    uint64_t k[3] = {0, 0, 0};
+    sd::normalize_span(in, out, n, k);
+    if (stats) { stats[0] += k[0]; stats[1] += k[1]; stats[2] += k[2]; stats[3] += (uint64_t)n; }
+    return SD_OK;
+}
+
+static std::mutex g_input_m;
+static int64_t g_input_stats[8] = {0};
+void sd_last_run_input_stats(int64_t out[8]) {
+    std::lock_guard<std::mutex> lk(g_input_m);
+    std::memcpy(out, g_input_stats, sizeof g_input_stats);
+}
+
 void sd_fasta_free(sd_fasta* f) {
     if (!f) return;
     for (int32_t i = 0; i < f->n; ++i) { std::free(f->names[i]); std::free(f->seqs[i]); }
@@ -283,3 +302,9 @@ void sd_fasta_free(sd_fasta* f) {
 
 
 }  // extern "C"
+
+void sd_note_input_stats(const sd::FastaFile& reads, const sd::FastaFile& monomers, bool lenient) {
+    std::lock_guard<std::mutex> lk(g_input_m);
+    for (int i = 0; i < 5; ++i) g_input_stats[i] = reads.in_stats[i].load() + monomers.in_stats[i].load();
+    g_input_stats[5] = lenient ? 1 : 0;
+}

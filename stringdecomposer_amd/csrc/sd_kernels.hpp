@@ -39,4 +39,21 @@ struct PackDevArgs {
 };
 void launch_pack_dev(hipStream_t st, const PackDevArgs& a);
 
+// lenient normalisation of read text in device memory (sd_normalize_dev.hip): piece x = the len bytes at src + off, the
+// rule of sd_normalize.hpp applied, written at dst + off (dst == src: in place); a piece lies inside one read and holds
+// at most kNormPiece bytes.  stats (may be null): four counters the kernel adds to (sd_normalize_dev in sd_hip.h).
+constexpr int32_t kNormPiece = 16384;
+struct NormPiece {
+    long long off;
+    int32_t len, pad;
+};
+struct NormDevArgs {
+    unsigned long long src, dst;
+    const NormPiece* pieces;
+    long long n_pieces;
+    unsigned long long* stats;
+    unsigned long long total;   // bytes of all pieces: what stats[3] grows by, added once
+};
+void launch_normalize_dev(hipStream_t st, const NormDevArgs& a);
+
 }  // namespace sd

@@ -16,8 +16,8 @@ int sd_assemble_files_tsv(const char* reads_fa, const char* monomers_fa, const s
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     sd::FastaFile rf, mf;
-    rc = rf.open(reads_fa, p->threads, err);
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);
+    rc = rf.open(reads_fa, p->threads, err, lenient_of(p));
+    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err, lenient_of(p));
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     std::vector<std::string> rnames, mnames;
     std::vector<const char*> rn, mn;
@@ -273,8 +273,8 @@ int sd_range_assemble_begin_files(const char* reads_fa, const char* monomers_fa,
     int rc = validate_params(p, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     sd::FastaFile rf, mf;
-    rc = rf.open(reads_fa, p->threads, err);
-    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);
+    rc = rf.open(reads_fa, p->threads, err, lenient_of(p));
+    if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err, lenient_of(p));
     if (rc) { set_err(errbuf, errlen, err); return rc; }
     std::unique_ptr<sd_range_asm> h(new sd_range_asm);
     h->rname_store.reserve(rf.recs.size());

@@ -60,11 +60,13 @@ struct JobInput {
              int64_t* info, std::string& err) {
         if (progress)   // main.cpp:393
             std::fprintf(stderr, "Scores: insertion=%d deletion=%d mismatch=%d match=%d\n", p->ins, p->del, p->mismatch, p->match);
-        int rc = rf.open(reads_fa, p->threads, err);                              // main.cpp:394
+        const bool lenient = lenient_of(p);
+        int rc = rf.open(reads_fa, p->threads, err, lenient);                     // main.cpp:394
         if (rc == SD_OK && world == 1) rc = rf.validate(0, rf.recs.size(), p->threads, err);   // reads are checked first, as there
-        if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err);              // main.cpp:395
+        if (rc == SD_OK) rc = mf.open(monomers_fa, p->threads, err, lenient);     // main.cpp:395
         if (rc == SD_OK) rc = mf.validate(0, mf.recs.size(), p->threads, err);
         if (rc) return rc;
+        sd_note_input_stats(rf, mf, lenient);
         for (const auto& r : mf.recs) monos.push_back(sd::Seq{std::string(r.name, r.name_len), std::string(r.seq, (size_t)r.len)});
         if (monos.empty()) { err = "no monomers"; return SD_ERR_PARAM; }
         std::vector<ReadView> all_reads;
@@ -625,6 +627,7 @@ static int run_files_impl(const char* reads_fa, const char* monomers_fa, const s
     JobInput in;
     rc = in.load(reads_fa, monomers_fa, p, rank, world, progress, info, err);
     if (rc) { set_err(errbuf, errlen, err); return rc; }
+    p_job.reserved[1] &= ~SD_FLAG_LENIENT;   // (the files are read: the pipelines and their cache keys never see the flag)
     lap("FASTA index + alphabet check");
     TemplateSet ts(in.monos);
     double screen_stats[6] = {0, 0, 0, 0, 0, 0};

@@ -47,6 +47,7 @@ EXPORTS = [
     "sd_stream_create_devices", "sd_stream_create_final_devices", "sd_stream_device_stats",
     "sd_profile_segments", "sd_profile_segments_dev", "sd_last_run_profile", "sd_stream_profile",
     "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev", "sd_engine_filter_result",
+    "sd_fasta_load_ex", "sd_normalize_host", "sd_normalize_dev", "sd_last_run_input_stats",
     "sd_stream_peek_dev", "sd_stream_collect_dev", "sd_engine_rows_dev", "sd_seam_merge_dev", "sd_seam_pieces_selftest",
     "sd_stream_peek_final_dev", "sd_stream_collect_final_dev", "sd_final_select_dev", "sd_final_select_host",
     "sd_stream_profile_dev", "sd_stream_profile_stats", "sd_final_profile_dev", "sd_final_profile_host",
@@ -146,7 +147,13 @@ def load():
     L.sd_seam_merge.argtypes = [P(Rec), C.c_int32]
     L.sd_format_rows.argtypes = [C.c_char_p, P(C.c_char_p), P(Rec), C.c_int32, P(C.c_void_p), P(C.c_size_t)]
     L.sd_fasta_load.argtypes = [C.c_char_p, P(Fasta), C.c_char_p, C.c_size_t]
+    L.sd_fasta_load_ex.argtypes = [C.c_char_p, C.c_int32, P(Fasta), C.c_char_p, C.c_size_t]
     L.sd_fasta_free.argtypes = [P(Fasta)]
+    L.sd_normalize_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.sd_normalize_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_last_run_input_stats.argtypes = [P(C.c_int64)]
+    L.sd_last_run_input_stats.restype = None
     L.sd_nw_identity_batch.argtypes = [P(C.c_char_p), P(C.c_int32), P(C.c_char_p), P(C.c_int32),
                                        C.c_int64, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32)]
     L.sd_identity_segments.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
@@ -325,12 +332,15 @@ FLAG_PROFILE = 512    # per-monomer column profiles of the kept rows (run_files(
 FLAG_DEVICE_ROWS = 1024   # Stream(device_rows=True): the rows are assembled on the device and stay there
 FLAG_DEVICE_FINAL = 2048  # Stream(final=True, device_final=True): the final rows are selected on the device and stay there
 FLAG_DEVICE_PROFILE = 4096  # Stream(final=True, device_final=True, device_profile=True): their column profiles are folded there too
+FLAG_LENIENT = 8192   # files are read leniently (make_params(lenient=True)): lower case folded, IUPAC codes -> N, CRLF
 
 
 def make_params(scoring=(-1, -1, -1, 1), part_size=5000, overlap=500, ed_thr=-1, threads=1,
-                device=0, kernel=KERNEL_AUTO, max_batch_rows=0, pipe_mode=None, flags=0, f16_guard=0):
+                device=0, kernel=KERNEL_AUTO, max_batch_rows=0, pipe_mode=None, flags=0, f16_guard=0, lenient=False):
     """sd_params; pipe_mode (None = the library default, 0 / 1 / 2), flags (FLAG_* bits) and f16_guard (magnitude
-    limit of the fills' fp16 range guard, 0 = 2040) are the reserved[] switches of include/sd_hip.h."""
+    limit of the fills' fp16 range guard, 0 = 2040) are the reserved[] switches of include/sd_hip.h.  lenient=True sets
+    FLAG_LENIENT: the calls that open the two files fold lower case, turn IUPAC ambiguity codes into N and drop the CR
+    of CRLF line ends (sd_hip.h, "lenient input"); the default reproduces the reference's errors."""
     L = load()
     p = Params()
     L.sd_params_default(C.byref(p))
@@ -339,7 +349,7 @@ def make_params(scoring=(-1, -1, -1, 1), part_size=5000, overlap=500, ed_thr=-1,
     p.threads, p.device, p.kernel = int(threads), int(device), int(kernel)
     p.max_batch_rows = int(max_batch_rows)
     p.reserved[0] = 0 if pipe_mode is None else int(pipe_mode) + 1
-    p.reserved[1] = int(flags)
+    p.reserved[1] = int(flags) | (FLAG_LENIENT if lenient else 0)
     p.reserved[2] = int(f16_guard)
     return p
 
@@ -468,6 +478,15 @@ def run_files(reads_fa, monomers_fa, raw_tsv_out, final_tsv_out, alt_tsv_out, mi
 
 
 _last_screen = None
+
+
+def last_run_input_stats():
+    """What the file indexes of the last file job of this process met (sd_last_run_input_stats), summed over reads and
+    monomers: lower (lower-case bases folded), ambiguity (codes turned into N), cr (CRs dropped), copied (records that
+    got a buffer of their own because the rule changed them), fastq (FASTQ records), lenient (was the mode on)."""
+    v = (C.c_int64 * 8)()
+    load().sd_last_run_input_stats(v)
+    return {"lower": v[0], "ambiguity": v[1], "cr": v[2], "copied": v[3], "fastq": v[4], "lenient": bool(v[5])}
 
 
 def last_run_screen():
@@ -1350,11 +1369,21 @@ class DeviceReads:
     stream: the hipStream_t (an int) on which the bytes were produced; None = the tensor's device's current stream at
     this moment (0, the null stream, for the tuple form).  The library orders itself behind that stream and makes the
     stream wait for its last read of the buffer (sd_hip.h), so the tensor may be overwritten or freed on that stream
-    right after a submit returns.  The object keeps a reference to data."""
+    right after a submit returns.  The object keeps a reference to data.
 
-    def __init__(self, data, lens, offsets=None, stream=None):
+    lenient=True: the reads are normalised on `stream` by sd_normalize_dev (lower case folded, IUPAC ambiguity codes ->
+    N) before anything else uses them.  For a tensor the normalised text goes into a new tensor that this object owns
+    (self.data; the caller's bytes stay untouched); inplace=True normalises the caller's buffer instead, and is required
+    for the tuple form (SdError(SD_ERR_PARAM) otherwise).  self.norm_stats: a 4 x int64 device tensor with the counters
+    of sd_normalize_dev (tensor form only).  A byte the rule leaves alone still fails the stream with SD_ERR_SYMBOL."""
+
+    def __init__(self, data, lens, offsets=None, stream=None, lenient=False, inplace=False):
         self.ptr, self.nbytes, self.device, self.stream, shape, strides = _device_buffer(data, stream)
         self.data = data
+        self.norm_stats = None
+        if lenient and isinstance(data, tuple) and not inplace:
+            raise SdError(SD_ERR_PARAM, "device reads: lenient=True on a (ptr, nbytes, device) tuple needs inplace=True "
+                                        "(the library owns no memory to put the normalised text in)")
         self.read_lens = [int(x) for x in lens]
         self.n = len(self.read_lens)
         if len(shape) == 2:
@@ -1384,6 +1413,71 @@ class DeviceReads:
         self.c_off = (C.c_int64 * max(self.n, 1))(*self.read_off)
         self.c_lens = (C.c_int64 * max(self.n, 1))(*self.read_lens)
         self.bp = sum(self.read_lens)
+        if lenient and self.n:
+            self._normalize(inplace)
+
+    def _normalize(self, inplace):
+        dst, stats = self.ptr, None
+        if not isinstance(self.data, tuple):
+            import torch
+            dev = torch.device("cuda", self.device)
+            with torch.cuda.stream(_torch_stream(torch, dev, self.stream)):   # (the blocks belong to the reads' stream)
+                self.norm_stats = torch.zeros(4, dtype=torch.int64, device=dev)
+                if not inplace:
+                    own = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+                    dst = int(own.data_ptr())
+            stats = C.c_void_p(int(self.norm_stats.data_ptr()))
+        err = C.create_string_buffer(4096)
+        rc = load().sd_normalize_dev(C.c_void_p(self.ptr), C.c_void_p(dst), self.c_off, self.c_lens, self.n, self.device,
+                                     C.c_void_p(self.stream), stats, err, 4096)
+        if rc != SD_OK:
+            raise SdError(rc, err.value.decode(errors="replace"))
+        if dst != self.ptr:
+            self.ptr, self.data = dst, own
+
+
+def normalize_host(data, inplace=False):
+    """The lenient rule on host bytes (sd_normalize_host) -> (bytes, stats): stats = [lower-case bytes folded, ambiguity
+    codes turned into N, bytes still outside ACGTN, bytes examined].  inplace=True: data is a writable buffer (bytearray,
+    numpy uint8 array) that is normalised where it lies and returned."""
+    L = load()
+    stats = (C.c_uint64 * 4)()
+    if inplace:
+        mv = memoryview(data).cast("B")
+        n = len(mv)
+        buf = (C.c_char * n).from_buffer(data) if n else None
+        rc = L.sd_normalize_host(buf and C.addressof(buf), buf and C.addressof(buf), n, stats)
+        out = data
+    else:
+        src = bytes(data)
+        n = len(src)
+        dst = C.create_string_buffer(max(n, 1))
+        rc = L.sd_normalize_host(C.cast(C.c_char_p(src), C.c_void_p), C.addressof(dst), n, stats)
+        out = dst.raw[:n]
+    if rc != SD_OK:
+        raise SdError(rc, "sd_normalize_host")
+    return out, [int(x) for x in stats]
+
+
+def normalize_device(data, lens, offsets=None, out=None, stream=None, stats=None):
+    """The lenient rule on reads in device memory (sd_normalize_dev): data, lens, offsets and stream as for DeviceReads
+    (or data = a DeviceReads); out = None normalises in place, else a buffer of the same form that takes the reads at
+    the same offsets; stats = a 4 x int64 / uint64 device tensor (or device address) the counters are added to.  The
+    kernel is enqueued on the stream; nothing waits."""
+    L = load()
+    dr = data if isinstance(data, DeviceReads) else DeviceReads(data, lens, offsets=offsets, stream=stream)
+    st = dr.stream if stream is None else (stream if isinstance(stream, int) else int(stream.cuda_stream))
+    dst = dr.ptr
+    if out is not None:
+        dst, nb, dev, _, _, _ = _device_buffer(out, st)
+        if nb < max([o + n for o, n in zip(dr.read_off, dr.read_lens)] or [0]):
+            raise SdError(SD_ERR_PARAM, "normalize_device: the output buffer is shorter than the reads reach")
+    sp = None if stats is None else C.c_void_p(int(stats.data_ptr()) if hasattr(stats, "data_ptr") else int(stats))
+    err = C.create_string_buffer(4096)
+    rc = L.sd_normalize_dev(C.c_void_p(dr.ptr), C.c_void_p(dst), dr.c_off, dr.c_lens, dr.n, dr.device, C.c_void_p(st), sp,
+                            err, 4096)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace"))
 
 
 def pack_bases_device(data, chunk_off, chunk_len, stream=None, fill=0):
@@ -1993,12 +2087,14 @@ def final_profile_device(text, read_off, rows, row_off, keep, templates, device=
                           device, threads, 16)
 
 
-def fasta_load(path):
-    """-> (names, seqs, has_n) with the reference binary's FASTA semantics (main.cpp:314-346)."""
+def fasta_load(path, lenient=False):
+    """-> (names, seqs, has_n) with the reference binary's FASTA semantics (main.cpp:314-346).  A file that begins with
+    '@' is read as four-line FASTQ.  lenient=True (sd_fasta_load_ex with SD_FLAG_LENIENT): lower case is folded, IUPAC
+    ambiguity codes become N and the CR of a CRLF line end is dropped; has_n reflects the normalised text."""
     L = load()
     f = Fasta()
     err = C.create_string_buffer(4096)
-    rc = L.sd_fasta_load(os.fsencode(path), C.byref(f), err, 4096)
+    rc = L.sd_fasta_load_ex(os.fsencode(path), FLAG_LENIENT if lenient else 0, C.byref(f), err, 4096)
     if rc != SD_OK:
         raise SdError(rc, err.value.decode(errors="replace"))
     names = [f.names[i].decode() for i in range(f.n)]

@@ -356,7 +356,7 @@ def convert_tsv(decomposition, reads, monomers, outfile, identity_th, light, thr
 
 def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr, overlap, logger,
         ref_compat=False, device=0, kernel=0, final_file=None, min_identity=0, second_best=False, records_file=None,
-        devices=None, profile=False, screen=None, screen_file=None):
+        devices=None, profile=False, screen=None, screen_file=None, lenient=False):
     """main.py:186-197 with the subprocess replaced by libsd_hip.so.
 
     Single process with final_file given: ONE native call (sd_run_files) streams the job through the
@@ -422,7 +422,9 @@ def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr,
                       # the dp binary's progress lines on stderr (main.cpp:82,115,393); --profile: the counters stay in the
                       # library until main() writes them (lib.last_run_profile(numpy=False): no numpy import on this path)
                       flags=lib.FLAG_PROGRESS | (lib.FLAG_PROFILE if profile else 0),
-                      records_out=records_file, devices=devices, screen=screen, screen_tsv_out=screen_file)
+                      records_out=records_file, devices=devices, screen=screen, screen_tsv_out=screen_file,
+                      lenient=lenient)
+        _log_input_stats(logger)
         if screen is not None:
             c = lib.last_run_screen()
             logger.info("Screen (threshold %d): %d reads, %d with a region, %d bases read, %d bases decomposed"
@@ -430,10 +432,21 @@ def run(sequences, monomers, num_threads, scoring, batch_size, raw_file, ed_thr,
         return True
     lib.decompose_files(sequences, monomers, raw_file, scoring=(ins, dels, mm, match),
                         part_size=int(batch_size), overlap=int(overlap), ed_thr=int(ed_thr),
-                        threads=int(num_threads), device=devices[0] if devices else device, kernel=kernel)
+                        threads=int(num_threads), device=devices[0] if devices else device, kernel=kernel,
+                        lenient=lenient)
+    _log_input_stats(logger)
     with open(raw_file, "r") as f:
         raw_decomposition = "".join(f.readlines())
     return raw_decomposition
+
+
+def _log_input_stats(logger):
+    """One line with what the file indexes met (lib.last_run_input_stats), when any count is non-zero."""
+    c = lib.last_run_input_stats()
+    if any(c[k] for k in ("lower", "ambiguity", "cr", "copied", "fastq")):
+        logger.info("Input%s: %d lower-case bases folded, %d ambiguity codes read as N, %d CRs dropped, %d records copied, "
+                    "%d FASTQ records" % (" (--lenient)" if c["lenient"] else "", c["lower"], c["ambiguity"], c["cr"],
+                                          c["copied"], c["fastq"]))
 
 
 MAX_DEVICE_ENTRIES = 16   # sd_run_files_devices
@@ -511,12 +524,25 @@ def _check_screen(args):
         refuse("--screen needs -v/--overlap smaller than -b/--batch-size (the regions of a read must not overlap)")
 
 
+def _check_lenient(args):
+    """--lenient requests this process cannot serve end it here, with one line on stderr, before any work."""
+    def refuse(msg):
+        sys.stderr.write("stringdecomposer: %s\n" % msg)
+        sys.exit(lib.SD_ERR_PARAM)
+    if args.ref_compat:
+        refuse("--lenient cannot be combined with --ref-compat, whose purpose is the reference's behaviour (its error for "
+               "lower case, IUPAC codes and CRLF included): drop one of the two, or convert the input to upper-case ACGTN first")
+    if shard.world()[2] > 1:
+        refuse("--lenient cannot be combined with a torch.distributed launch (WORLD_SIZE=%d): the ranks' convert step reads "
+               "the files strictly; use --gpus N / --devices LIST, several GPUs in one process" % shard.world()[2])
+
+
 def _write_msa(args, final_fn, msa_fn, device):
     """--msa: one line per row of the final TSV just written (formats.MSA_HEADER), the rows computed read by read on
     `device` (lib.msa_segments: the row kernel, the host form for the pairs it does not take)."""
     from . import formats
-    rn, rs, _ = lib.fasta_load(args.sequences)
-    mn, ms, _ = lib.fasta_load(args.monomers)
+    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
+    mn, ms, _ = lib.fasta_load(args.monomers, lenient=args.lenient)
     reads, il = {}, {}
     for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
         reads.setdefault(n, s.upper())
@@ -588,7 +614,14 @@ def main(argv=None):
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
                              "decomposed as reads of their own (positions stay those of the whole read); also writes "
                              "<out-file>_screen.tsv, one line per stretch")
+    parser.add_argument("--lenient", action="store_true",
+                        help="read both files leniently: lower-case (soft-masked) bases are folded to upper case, the IUPAC "
+                             "ambiguity codes RYSWKMBDHV are read as N (which matches N only), and the CR of CRLF line ends is "
+                             "dropped.  Without it such input ends with the reference's error.  FASTQ (four lines per "
+                             "record) is read with or without it")
     args = parser.parse_args(argv)
+    if args.lenient:
+        _check_lenient(args)
     if args.screen is not None:
         _check_screen(args)
     if args.profile:
@@ -618,7 +651,7 @@ def main(argv=None):
                                 final_file=convert_tsv_fn, min_identity=int(args.min_identity),
                                 second_best=args.second_best,
                                 records_file=records_fn if shard.world()[2] == 1 else None, devices=devices,
-                                profile=args.profile, screen=args.screen,
+                                profile=args.profile, screen=args.screen, lenient=args.lenient,
                                 screen_file=os.path.join(args.out_dir, args.out_file + "_screen.tsv") if args.screen is not None else None)
     except lib.SdError as e:
         # the reference dies with CalledProcessError after the binary printed its message on stderr
