@@ -9,6 +9,7 @@ lies), `Bio` = the handful of SeqIO / SeqRecord / Seq calls main.py makes.  The 
 bin/stringdecomposer then runs unchanged; its outputs are committed as data:
 
   tests/golden/final/<case>/{params.json, final.tsv[, alt.tsv.gz]}   (+ sha256 of every output)
+  tests/golden/final/ident_<case>/ also {params_light.json, final_light.tsv}: the same inputs without --second-best
 
 usage: python tests/golden/make_final_golden.py
 """
@@ -24,6 +25,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import binding as ob  # noqa: E402
 from stringdecomposer_amd import synth  # noqa: E402
@@ -127,18 +129,18 @@ def run_reference(work, reads_fa, mono_fa, extra):
     return rd("final_decomposition_raw.tsv"), rd("final_decomposition.tsv"), rd("final_decomposition_alt.tsv")
 
 
-def emit(work, name, reads_fa, mono_fa, extra, inputs_rel, keep_alt):
+def emit(work, name, reads_fa, mono_fa, extra, inputs_rel, keep_alt, suffix="", alt_limit=None):
     raw, final, alt = run_reference(work, reads_fa, mono_fa, extra)
     d = os.path.join(OUT, name)
     os.makedirs(d, exist_ok=True)
-    with open(os.path.join(d, "final.tsv"), "wb") as f:
+    with open(os.path.join(d, "final%s.tsv" % suffix), "wb") as f:
         f.write(final)
-    if keep_alt and alt:
+    if keep_alt and alt and (alt_limit is None or len(alt) < alt_limit):
         with gzip.GzipFile(os.path.join(d, "alt.tsv.gz"), "wb", mtime=0) as f:
             f.write(alt)
     meta = {"args": extra, "inputs": inputs_rel, "raw_sha256": sha(raw), "final_sha256": sha(final),
             "alt_sha256": sha(alt), "alt_bytes": len(alt), "final_rows": final.count(b"\n")}
-    with open(os.path.join(d, "params.json"), "w") as f:
+    with open(os.path.join(d, "params%s.json" % suffix), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
         f.write("\n")
     print("%-28s final %s (%d rows)  alt %s (%d B)" % (name, meta["final_sha256"][:16], meta["final_rows"],
@@ -203,6 +205,19 @@ def main():
     synth.write_fasta(os.path.join(d, "monomers.fa"), mn, ms)
     emit(work, "tiled_second_best", os.path.join(d, "reads.fa"), os.path.join(d, "monomers.fa"), ["--second-best"],
          ["final/tiled_second_best/reads.fa", "final/tiled_second_best/monomers.fa"], keep_alt=True)
+    # the routes of the in-stream identity kernels (tests/ident_cases.py: every word count, the padding edges, masks in
+    # LDS / global memory, the forms of the selection pass), each with --second-best and without it (own template only)
+    import ident_cases
+    for c in ident_cases.GOLDEN_CASES:
+        name = "ident_" + c.name
+        d = os.path.join(OUT, name)
+        os.makedirs(d, exist_ok=True)
+        synth.write_fasta(os.path.join(d, "reads.fa"), *c.reads(), width=80)
+        synth.write_fasta(os.path.join(d, "monomers.fa"), *c.monomers())
+        rel = ["final/%s/reads.fa" % name, "final/%s/monomers.fa" % name]
+        emit(work, name, os.path.join(d, "reads.fa"), os.path.join(d, "monomers.fa"), ["--second-best"], rel,
+             keep_alt=True, alt_limit=100 * 1000)   # (the _alt text of the widest sets is kept as its sha256 only)
+        emit(work, name, os.path.join(d, "reads.fa"), os.path.join(d, "monomers.fa"), [], rel, keep_alt=False, suffix="_light")
     shutil.rmtree(work, ignore_errors=True)
 
 
