@@ -961,6 +961,60 @@ int sd_msa_final_size_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t 
 int sd_msa_final_write_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t n_rows, int32_t device, void* hip_stream,
                            const int64_t* d_row_at, uint8_t* d_out, int64_t cap, uint8_t* d_status, char* errbuf, size_t errlen);
 
+/* ---- identity against lag (--lags): every row against its next D neighbours in the same read ---------------------------
+ * Rows in file order; a read (group) owns rows x = 0 .. n-1.  For 1 <= d <= D and x + d < n the pair (x, d) aligns
+ * query = the segment of row x against target = the segment of row x + d -- both as they stand in the read, nothing is
+ * reverse-complemented, so a pair across an inversion scores low -- and yields (dist, matches) exactly as
+ * sd_nw_identity_batch defines them.  Result index s * D + (d - 1) for segment s:
+ *   dist >= 0   computed              dist = -1, matches = 0   no partner at that lag (the read ends), or an empty side
+ *   dist = -2, matches = 0            left out by a device-resident call (below)
+ * sums[(g * D + d - 1) * 3 + {0, 1, 2}] = over the pairs of group g at lag d with dist >= 0: their number n, the sum M of
+ * matches, the sum C of dist + matches.  The pooled identity of a lag is M / C; a read's period is the lag with the largest
+ * pooled identity among the lags with n > 0, compared by 128-bit cross products, ties to the smallest lag, 0 when the read
+ * has fewer than two rows (csrc/sd_lags.hpp: one text for host and device).  1 <= D <= 255, else SD_ERR_PARAM before any
+ * device work.  segments x D must stay below 2^31 (SD_ERR_UNSUPPORTED).
+ *
+ * sd_lag_segments: host threads, any length, any byte alphabet.  Segment s = seq[starts[s] .. ends[s]] (inclusive);
+ * segments group_off[g] .. group_off[g + 1] are the rows of one read (group_off[0] = 0, group_off[n_groups] = n_seg).
+ * dist / matches (n_seg x D) and sums (n_groups x D x 3) are overwritten.
+ * sd_lag_segments_dev: the lane kernel of csrc/sd_lags.hip -- one lane per pair, which builds the match masks of its own
+ * target in LDS and runs the identity kernel's walk on them -- for targets up to 512 bp and queries up to 1024 bp that
+ * edlib does not split, over a text in ACGTN; the host form under it for every other pair.  The same arrays byte for byte,
+ * no -2 ever appears. */
+int sd_lag_segments(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                    const int64_t* group_off, int32_t n_groups, int32_t D, int32_t threads, int32_t* dist, int32_t* matches,
+                    int64_t* sums);
+int sd_lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                        const int64_t* group_off, int32_t n_groups, int32_t D, int32_t device, int32_t threads, int32_t* dist,
+                        int32_t* matches, int64_t* sums);
+/* The device-resident form, the last link of sd_stream_submit_dev -> sd_stream_collect_final_dev: d_rows[0 .. n_rows) as
+ * sd_stream_collect_final_dev delivers them (rows of a read adjacent; partners are found from sd_final_row.read), d_text /
+ * read_off / read_lens (host arrays, n_reads each) as sd_stream_submit_dev takes them.  A row's segment is the one its
+ * identity column measured (read[start : end + 1] as Python clamps it).  d_dist / d_matches (n_rows x D int32) and d_sums
+ * (n_reads x D x 3 int64) are the caller's, on `device`.  Everything is ordered on hip_stream; the host waits once, for
+ * classes[3] = entries with dist -1 / pairs of the lane kernel / pairs left out as -2 (they add up to n_rows x D), which
+ * also size the kernel's launches.  The call returns with the kernels in flight; its workspace is kept per device, and the
+ * next call on that device first waits for them.  Buffers not in device memory: SD_ERR_PARAM; another device's:
+ * SD_ERR_UNSUPPORTED; a row whose read index lies outside the reads: SD_ERR_PARAM.
+ * sd_lag_final_host: the same from host arrays (text: the reads at read_off), every pair computed, no device needed. */
+int sd_lag_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_text, const int64_t* read_off,
+                     const int64_t* read_lens, int32_t n_reads, int32_t D, int32_t device, void* hip_stream, int32_t* d_dist,
+                     int32_t* d_matches, int64_t* d_sums, int64_t classes[3], char* errbuf, size_t errlen);
+int sd_lag_final_host(const sd_final_row* rows, int64_t n_rows, const char* text, const int64_t* read_off, const int64_t* read_lens,
+                      int32_t n_reads, int32_t D, int32_t threads, int32_t* dist, int32_t* matches, int64_t* sums);
+/* What the two files of --lags print: out[i] = the identity in percent of (dist[i], matches[i]) by the identity column's
+ * arithmetic, -1 for dist < 0; period[g] and pooled[g * D + d - 1] (-1 for a lag without pairs) of each group's sums. */
+void sd_lag_identities(const int32_t* dist, const int32_t* matches, int64_t n, double* out);
+void sd_lag_periods(const int64_t* sums, int64_t n_groups, int32_t D, int32_t* period, double* pooled);
+/* Developer entry (tools/lags_bench.py): the arguments of sd_lag_segments_dev; warmup + reps times each, between two HIP
+ * events: ms_group = plan + scan + scatter, ms_pairs = the lane kernels with their reduction, ms_walk = the same without
+ * it, ms_ident = the light identity kernel (csrc/sd_nw.hip) on as many pairs -- the same queries against one target of the
+ * most frequent word class.  info = lane-kernel pairs, host pairs, K of the most frequent class, its pairs, checkpoint
+ * slots and grid of the yardstick, grid and checkpoint slots of that class.  SD_ERR_UNSUPPORTED when no pair is the kernel's. */
+int sd_lag_kernel_bench(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                        const int64_t* group_off, int32_t n_groups, int32_t D, int32_t device, int32_t warmup, int32_t reps,
+                        float* ms_group, float* ms_pairs, float* ms_walk, float* ms_ident, int64_t info[8]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

@@ -39,14 +39,19 @@ struct FinalTables {
     double coef[3] = {0, 0, 0};
 };
 
-// identity in percent of a word: the arithmetic of main.py:47-60 on the same integers
-SD_HD inline double final_ident_percent(uint32_t w) {
+// identity in percent of m '=' columns among `cols` columns: the arithmetic of main.py:47-60 (both are integers a double holds)
+SD_HD inline double final_ident_ratio(double m, double cols) {
 #pragma clang fp contract(off)
-    const uint32_t d = w >> 16, m = w & 0xffffu;
     double a = 0.0;
-    a += (double)m;
-    a /= (double)(d + m);
+    a += m;
+    a /= cols;
     return a * 100;
+}
+
+// identity in percent of a word, on the same integers
+SD_HD inline double final_ident_percent(uint32_t w) {
+    const uint32_t d = w >> 16, m = w & 0xffffu;
+    return final_ident_ratio((double)m, (double)(d + m));
 }
 
 // a word that decides nothing: left out by the kernels, or dist + matches == 0, which no alignment has

@@ -5,11 +5,12 @@
 //                      forward monomer the number of kernel pairs (workgroup histogram in LDS, then global adds), the
 //                      longest such segment, the number of host pairs
 //   sd_fprof_scan      exclusive prefix of the monomer counts, the scatter's cursors
-//   sd_fprof_scatter   kernel pairs -> order[], grouped by forward monomer (a workgroup reserves its ranges with one
-//                      atomic per monomer); host pairs -> a compact list of (start, len, template)
+//   sd_fprof_scatter   kernel pairs -> order[], grouped by forward monomer (group_scatter of sd_group_dev.hpp: a workgroup
+//                      reserves its ranges with one atomic per monomer); host pairs -> a compact list of (start, len, template)
 //   sd_fprof_items     work items {monomer, first, end} of up to `per` pairs from the same prefix
 // Order inside a group depends on the atomics; the counters are integer sums, so the profile does not.
 #include "sd_final_ws.hpp"
+#include "sd_group_dev.hpp"
 
 namespace sd {
 
@@ -102,48 +103,32 @@ __global__ void sd_fprof_scan(const int32_t* __restrict__ sum, int M, int32_t* _
     cursor[M] = 0;
 }
 
+// the pairs of a plan as group_scatter reads them (sd_group_dev.hpp): kernel pairs by forward monomer, host pairs aside
+struct FProfSrc {
+    const uint8_t* cls;
+    const int32_t* pair_il;
+    const int64_t* seg_start;
+    const int32_t* seg_len;
+    FProfHostPair* hlist;
+    __device__ int kind(int64_t m) const { return cls[m] == FPROF_DEV ? GROUP_IN : cls[m] == FPROF_HOST ? GROUP_ASIDE : GROUP_OUT; }
+    __device__ int group(int64_t m) const { return pair_il[m] >> 1; }
+    __device__ void aside(int64_t m, int64_t pos) const {
+        FProfHostPair h;
+        h.start = seg_start[m];
+        h.len = seg_len[m];
+        h.il = pair_il[m];
+        hlist[pos] = h;
+    }
+};
+
 __global__ __launch_bounds__(FPROF_T) void sd_fprof_scatter(const uint8_t* __restrict__ cls, const int32_t* __restrict__ pair_il,
                                                           const int64_t* __restrict__ seg_start, const int32_t* __restrict__ seg_len,
                                                           const int64_t* __restrict__ n_ptr, int64_t cap, int M,
                                                           int32_t* __restrict__ cursor, int32_t* __restrict__ order,
                                                           FProfHostPair* __restrict__ hlist) {
-    __shared__ int hist[FPROF_HIST];
-    __shared__ int nh_s, nh_base;
-    const int nb = M < FPROF_HIST ? M : FPROF_HIST;
-    for (int i = threadIdx.x; i < nb; i += FPROF_T) hist[i] = 0;
-    if (threadIdx.x == 0) { nh_s = 0; nh_base = 0; }
-    __syncthreads();
-    const int64_t m = (int64_t)blockIdx.x * FPROF_T + threadIdx.x;
+    static_assert(FPROF_T == GROUP_T && FPROF_HIST == GROUP_HIST, "group_scatter's workgroup");
     const int64_t n = *n_ptr < cap ? *n_ptr : cap;
-    const uint8_t c = m < n ? cls[m] : (uint8_t)FPROF_NONE;
-    int mono = -1, rank = 0;
-    if (c == FPROF_DEV) {
-        mono = pair_il[m] >> 1;
-        if (mono < FPROF_HIST) rank = atomicAdd(&hist[mono], 1);
-    } else if (c == FPROF_HOST) {
-        rank = atomicAdd(&nh_s, 1);
-    }
-    __syncthreads();
-    // the workgroup's range in each monomer's group: hist[i] becomes its first place
-    for (int i = threadIdx.x; i < nb; i += FPROF_T) {
-        const int k = hist[i];
-        if (k) hist[i] = atomicAdd(&cursor[i], k);
-    }
-    if (threadIdx.x == 0 && nh_s) nh_base = atomicAdd(&cursor[M], nh_s);
-    __syncthreads();
-    if (c == FPROF_DEV) {
-        const int64_t pos = mono < FPROF_HIST ? hist[mono] + rank : atomicAdd(&cursor[mono], 1);
-        if (pos < cap) order[pos] = (int32_t)m;
-    } else if (c == FPROF_HOST) {
-        const int64_t pos = (int64_t)nh_base + rank;
-        if (pos < cap) {
-            FProfHostPair h;
-            h.start = seg_start[m];
-            h.len = seg_len[m];
-            h.il = pair_il[m];
-            hlist[pos] = h;
-        }
-    }
+    group_scatter(FProfSrc{cls, pair_il, seg_start, seg_len, hlist}, n, cap, M, cursor, order);
 }
 
 // workgroup m: the items of monomer m, behind those of the monomers before it
@@ -213,8 +198,12 @@ void ProfDev::setup(const std::vector<std::string>& il, const std::vector<int32_
     SD_HIP(hipStreamSynchronize(st));   // (the vectors above leave)
 }
 
+void group_scan(hipStream_t st, const int32_t* sum, int M, int32_t* base, int32_t* cursor) {
+    hipLaunchKernelGGL(sd::sd_fprof_scan, dim3(1), dim3(64), 0, st, sum, M, base, cursor);
+}
+
 void prof_group(ProfWS& w, int M, hipStream_t st, int64_t cap, const int64_t* n_ptr) {
-    hipLaunchKernelGGL(sd::sd_fprof_scan, dim3(1), dim3(64), 0, st, w.sum.p, M, w.base.p, w.cursor.p);
+    group_scan(st, w.sum.p, M, w.base.p, w.cursor.p);
     if (cap > 0)
         hipLaunchKernelGGL(sd::sd_fprof_scatter, dim3(fprof_grid(cap)), dim3(sd::FPROF_T), 0, st, w.cls.p, w.pair_il.p, w.seg_start.p,
                            w.seg_len.p, n_ptr, cap, M, w.cursor.p, w.order.p, w.hlist.p);

@@ -52,6 +52,9 @@ void prof_plan(ProfWS& w, const ProfDev& d, hipStream_t st, const sd::DevRec* re
 // The grouping alone, on a plan already in w (cls, pair_il, seg_start, seg_len per row and the counts w.sum[0 .. M)): the
 // scan of the monomer counts and, over rows [0, min(*n_ptr, cap)), the scatter into w.order / w.hlist (cap 0: the scan only).
 void prof_group(ProfWS& w, int M, hipStream_t st, int64_t cap, const int64_t* n_ptr);
+// The scan alone: base[0 .. M] = the exclusive prefix of sum[0 .. M), cursor[0 .. M) = base, cursor[M] = 0 (one lane: M is
+// tens to hundreds) -- the start of every grouping (sd_group_dev.hpp).
+void group_scan(hipStream_t st, const int32_t* sum, int M, int32_t* base, int32_t* cursor);
 // w.items[0 .. n_items) = the work items of up to `per` pairs from w.base.  clear: n_items is an upper bound taken without
 // the counts -- the entries behind the last item are empty items (no pair).
 void prof_items(ProfWS& w, int M, int per, int64_t n_items, hipStream_t st, bool clear);

@@ -365,6 +365,12 @@ __global__ __launch_bounds__(MSA_T) void sd_msa_gather(const uint8_t* __restrict
     dst[i] = src[roff[lo] + (i - toff[lo])];
 }
 
+void launch_text_gather(hipStream_t st, const uint8_t* src, const int64_t* roff, const int64_t* toff, int n_reads, int64_t text,
+                        uint8_t* dst) {
+    if (text <= 0) return;
+    hipLaunchKernelGGL(sd_msa_gather, dim3((unsigned)((text + MSA_T - 1) / MSA_T)), dim3(MSA_T), 0, st, src, roff, toff, n_reads, dst);
+}
+
 struct MsaPlanArgs {
     const sd_final_row* rows;
     int64_t n;
@@ -587,9 +593,7 @@ int sd_msa_final_size_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t 
         roff[n_reads] = 0; rlen[n_reads] = 0; toff[n_reads] = at;
         SD_HIP(hipMemcpyAsync(t->reads.p, t->h_reads.p, 3 * nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
         SD_HIP(hipMemsetAsync(w.sum.p, 0, ((size_t)M + 4) * sizeof(int32_t), st));
-        if (text > 0)
-            hipLaunchKernelGGL(sd::sd_msa_gather, dim3(msa_grid(text)), dim3(sd::MSA_T), 0, st, static_cast<const uint8_t*>(d_text),
-                               t->reads.p, t->reads.p + 2 * nr, (int)n_reads, t->text.p);
+        sd::launch_text_gather(st, static_cast<const uint8_t*>(d_text), t->reads.p, t->reads.p + 2 * nr, (int)n_reads, text, t->text.p);
         if (n_rows > 0) {
             sd::MsaPlanArgs a{d_rows, n_rows, t->d.own_il.p, (int)t->key_il.size(), t->d.tlen.p, t->d.tmax, M, t->reads.p + nr,
                               t->reads.p + 2 * nr, (int)n_reads, w.seg_start.p, w.seg_len.p, w.pair_il.p, w.cls.p, w.sum.p, d_row_at};

@@ -80,6 +80,11 @@ void launch_nw_msa(int K, hipStream_t st, int grid, int tmax, const uint8_t* seq
                    const int32_t* order, const int32_t* pair_il, const int4* items, int n_items, const unsigned long long* peq,
                    const int32_t* tlen, int cap, void* ck, int* ckpos, uint8_t* out, const int64_t* row_at, uint8_t* status,
                    int* fails);
+// The reads of a caller's device buffer (read r at src + roff[r]; roff and toff device arrays), copied back to back into dst:
+// read r at dst + toff[r], toff[n_reads] = text bytes.  The walks read aligned dwords up to the next multiple of 4 past a
+// segment's end, so they work on such a copy of their own (sd_msa.hip, sd_lags.hip), 8 bytes longer than the text.
+void launch_text_gather(hipStream_t st, const uint8_t* src, const int64_t* roff, const int64_t* toff, int n_reads, int64_t text,
+                        uint8_t* dst);
 // accumulated over the device identity calls of the process: preparation + staging, uploads, kernel, downloads
 void nw_stage_seconds(double out[4]);
 

@@ -1,5 +1,6 @@
-// sd_nw_kernel.hpp -- the identity kernel (device side), shared by sd_nw.hip (segments of an ASCII text) and
-// sd_ident.hip (in-stream: the records of a device batch against the 2-bit reads that are already resident).
+// sd_nw_kernel.hpp -- the identity kernel (device side), shared by sd_nw.hip (segments of an ASCII text),
+// sd_ident.hip (in-stream: the records of a device batch against the 2-bit reads that are already resident), sd_msa.hip
+// and sd_lags.hip (block against block: a lane's own masks, nw_pair's LS).
 //
 // What it computes (stringdecomposer/main.py:29-60, `edist` + `aai` through python-edlib): for a pair (read
 // segment q, template t) the unit-cost global alignment that edlib's traceback picks -- priority
@@ -43,15 +44,15 @@ struct NwState {
 };
 
 // One column: state -> state, returns the horizontal delta of the template's last row (+1 / 0 / -1).
-// eq = the K match-mask words of the column's symbol; PhU* (optional) receive Ph before its shift.
-template <int K, bool HIST>
+// eq = the K match-mask words of the column's symbol, LS words apart (nw_pair); PhU* (optional) receive Ph before its shift.
+template <int K, bool HIST, int LS = 1>
 __device__ __forceinline__ int nw_column(NwState<K>& s, const uint2* __restrict__ eq, uint32_t* PhUL, uint32_t* PhUH) {
     constexpr uint32_t TT_XH = (0xF0 ^ 0xCC) | 0xAA;               // (a ^ b) | c
     constexpr uint32_t TT_ORN = 0xF0 | (~(0xCC | 0xAA) & 0xFF);    // a | ~(b | c)
     uint32_t cP = 1, cM = 0;   // global alignment: D[c][0] - D[c-1][0] = +1 enters row 1
 #pragma unroll
     for (int b = 0; b < K; ++b) {
-        const uint2 e = eq[b];
+        const uint2 e = eq[b * LS];
         uint32_t EqL = e.x;
         const uint32_t EqH = e.y;
         const uint32_t pvL = s.PvL[b], pvH = s.PvH[b], mvL = s.MvL[b], mvH = s.MvH[b];
@@ -147,7 +148,10 @@ struct NwProf {
     }
 };
 
-// The pair: ql query symbols (before compression), template masks eqt ([5][K] words, LDS or global), template
+// The pair: ql query symbols (before compression), template masks eqt ([5][K] words, LDS or global; word b of symbol s at
+// eqt[(s * K + b) * LS] -- LS = 1: one set back to back, shared by the lanes (nw_build_masks); LS = T: a set PER LANE in LDS,
+// word index major and lane minor, eqt pointing at the lane's own word 0, so that a wave's read of "word b of symbol s"
+// is 64 consecutive 8-byte slots (sd_lags.hip: block against block has no table the lanes could share)), template
 // length tl (1 <= tl <= 64 K), homo = homopolymer-compress the query on the fly (main.py:87-92; the templates are
 // compressed by the host).  ck / ckpos: this lane's checkpoint slots, element stride `ckstride` in dwords: component
 // x (PvL, PvH, MvL, MvH) of word b of slot s at ck[((s * K + b) * 4 + x) * ckstride] -- planar dwords, so that a
@@ -157,7 +161,7 @@ struct NwProf {
 // the walk also goes to *prof -- diag(p, base), del(p), ins(slot, base) as NwProf has them (homo must be false: a sink
 // sees read bases).
 struct NwNoSink {};
-template <int K, class Query, class Sink = NwNoSink>
+template <int K, class Query, class Sink = NwNoSink, int LS = 1>
 __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restrict__ eqt, int tl, bool homo,
                                         uint32_t* __restrict__ ck, int* __restrict__ ckpos, size_t ckstride, int cap,
                                         int& dist_out, int& matches_out, Sink* prof = nullptr) {
@@ -205,13 +209,13 @@ __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restric
             }
             if (homo) ckpos[(size_t)slot * ckstride] = i - 1;   // where the block's first symbol is (plain: column c is symbol c)
         }
-        score += nw_column<K, false>(st, eqt + r0 * K, nullptr, nullptr);
+        score += nw_column<K, false, LS>(st, eqt + r0 * K * LS, nullptr, nullptr);
         ++c;
 #pragma unroll
         for (int x = 1; x < S; ++x) {
             int r = 0;
             const bool got = next_kept(r);
-            const int h = nw_column<K, false>(st, eqt + (got ? r : 0) * K, nullptr, nullptr);
+            const int h = nw_column<K, false, LS>(st, eqt + (got ? r : 0) * K * LS, nullptr, nullptr);
             score += got ? h : 0;
             c += got ? 1 : 0;
         }
@@ -260,7 +264,7 @@ __device__ __forceinline__ bool nw_pair(Query& q, int ql, const uint2* __restric
                 in.MvL[b2] = st.MvL[b2];
                 in.MvH[b2] = st.MvH[b2];
             }
-            (void)nw_column<K, true>(in, eqt + r * K, hPhL[x], hPhH[x]);
+            (void)nw_column<K, true, LS>(in, eqt + r * K * LS, hPhL[x], hPhH[x]);
 #pragma unroll
             for (int b2 = 0; b2 < K; ++b2) {
                 hPvL[x][b2] = in.PvL[b2]; hPvH[x][b2] = in.PvH[b2];

@@ -566,6 +566,79 @@ def read_msa(path):
     return out
 
 
+# ---- lags -----------------------------------------------------------------------------------------
+# --lags D: <out>_lags.tsv, one line per row of <out>.tsv -- read, start, end, then the identity of the row's segment (the
+# query) to that of each of its next D neighbours in the same read (the target), "-1.00" where the read ends first -- and
+# <out>_period.tsv, one line per read -- read, rows, period, then the D pooled identities (sum of matches / sum of columns
+# over the read's pairs at that lag, "-1.00" for a lag without pairs).  No headers; D is the number of identity columns.
+Lags = namedtuple("Lags", "dist matches sums")
+"""lib.lag_segments / final_lags_host / DeviceLags.to_host(): dist, matches = int32 [n, D] (dist -1: no partner, -2: left out
+by a device-resident call), sums = int64 [groups, D, 3] = (pairs, sum of matches, sum of dist + matches)."""
+LagRow = namedtuple("LagRow", "read start end identities")          # a line of <out>_lags.tsv
+PeriodRow = namedtuple("PeriodRow", "read rows period identities")  # a line of <out>_period.tsv
+# (the identities of a Lags: lib.lag_identities(dist, matches); periods and pooled identities: lib.lag_periods(sums))
+
+
+def lag_period(sums):
+    """The period of a read from its sums ([D][3] = pairs, sum of matches, sum of columns per lag): the lag with the largest
+    pooled identity M / C among the lags with pairs, compared as integers (M1 * C2 > M2 * C1, never in floating point), ties
+    to the smallest lag; 0 when no lag has a pair.  A [groups][D][3] array gives a list."""
+    rows = sums.tolist() if hasattr(sums, "tolist") else sums
+    if rows and rows[0] and isinstance(rows[0][0], (list, tuple)):
+        return [lag_period(r) for r in rows]
+    best = 0
+    for d, (n, m, c) in enumerate(rows, 1):
+        if n <= 0 or c <= 0:
+            continue
+        if best == 0 or int(m) * int(rows[best - 1][2]) > int(rows[best - 1][1]) * int(c):
+            best = d
+    return best
+
+
+def format_lags(rows):
+    f2 = "{:.2f}".format
+    return "".join("%s\t%d\t%d\t%s\n" % (r.read, r.start, r.end, "\t".join(f2(v) for v in r.identities)) for r in rows)
+
+
+def format_periods(rows):
+    f2 = "{:.2f}".format
+    return "".join("%s\t%d\t%d\t%s\n" % (r.read, r.rows, r.period, "\t".join(f2(v) for v in r.identities)) for r in rows)
+
+
+def write_lags(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_lags(rows))
+
+
+def write_periods(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_periods(rows))
+
+
+def _read_lag_file(path, make):
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            x = line.rstrip("\n").split("\t")
+            if len(x) < 4 or (out and len(x) != 3 + len(out[0].identities)):
+                raise FormatError(path, lineno, "expected 3 columns and the same number of identities on every line, got %d" % len(x))
+            try:
+                out.append(make(x[0], int(x[1]), int(x[2]), tuple(float(v) for v in x[3:])))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out
+
+
+def read_lags(path):
+    """<out>_lags.tsv -> [LagRow]."""
+    return _read_lag_file(path, LagRow)
+
+
+def read_periods(path):
+    """<out>_period.tsv -> [PeriodRow]."""
+    return _read_lag_file(path, PeriodRow)
+
+
 # ---- screen ---------------------------------------------------------------------------------------
 ScreenRow = namedtuple("ScreenRow", "read start end chunks best_distance best_template")   # a line of <out>_screen.tsv
 

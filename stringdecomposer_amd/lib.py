@@ -56,6 +56,8 @@ EXPORTS = [
     "sd_text_raw_size_dev", "sd_text_raw_write_dev", "sd_text_final_host", "sd_text_raw_host",
     "sd_msa_row_offsets", "sd_msa_segments", "sd_msa_segments_dev", "sd_msa_tables_create", "sd_msa_tables_destroy",
     "sd_msa_final_size_dev", "sd_msa_final_write_dev", "sd_msa_kernel_bench",
+    "sd_lag_segments", "sd_lag_segments_dev", "sd_lag_final_dev", "sd_lag_final_host", "sd_lag_identities", "sd_lag_periods",
+    "sd_lag_kernel_bench",
     "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
     "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
     "sd_screen_kernel_bench",
@@ -241,6 +243,21 @@ def load():
                                         C.c_int32, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_size_t]
     L.sd_msa_final_write_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_lag_segments.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sd_lag_segments_dev.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sd_lag_final_dev.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_lag_final_host.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sd_lag_identities.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.sd_lag_identities.restype = None
+    L.sd_lag_periods.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+    L.sd_lag_periods.restype = None
+    L.sd_lag_kernel_bench.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                      P(C.c_int64)]
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
@@ -766,6 +783,161 @@ def final_msa_classes(final_rows, read_lens, keys, mono_names, mono_seqs):
         else:
             out.append(2)
     return (out.count(0), out.count(1), out.count(2)), out
+
+
+LAG_DMAX = 255
+
+
+def _lag_d(D, who):
+    """1 <= D <= 255, refused here before any array is made or any device is touched"""
+    if not isinstance(D, int) or isinstance(D, bool) or not 1 <= D <= LAG_DMAX:
+        raise SdError(SD_ERR_PARAM, "%s: D = %r, must be an integer 1 .. %d" % (who, D, LAG_DMAX))
+    return D
+
+
+def lag_segments(text, starts, ends, group_off, D, device=None, threads=1):
+    """Identity of every segment to its next D neighbours in the same group (sd_lag_segments[_dev]; include/sd_hip.h):
+    segment s = text[starts[s] .. ends[s]] (inclusive), segments group_off[g] .. group_off[g + 1] are the rows of one read,
+    pair (s, d) aligns segment s as the query against segment s + d as the target -> formats.Lags(dist, matches, sums) with
+    dist / matches int32 [n, D] (-1 / 0: no partner) and sums int64 [groups, D, 3] = (pairs, sum of matches, sum of dist +
+    matches).  device=None: host threads; device=<ordinal>: the lane kernel, with the host form for the pairs it does not
+    take -- the same bytes."""
+    import numpy as np
+    from . import formats
+    D = _lag_d(D, "lag_segments")
+    L = load()
+    sb = _b(text)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    go = np.ascontiguousarray(group_off, dtype=np.int64)
+    n = int(st.shape[0])
+    if en.shape[0] != n or go.ndim != 1 or go.shape[0] < 1:
+        raise SdError(SD_ERR_PARAM, "lag_segments: starts and ends differ in length, or group_off is empty")
+    G = int(go.shape[0]) - 1
+    dist = np.zeros((n, D), dtype=np.int32)
+    matches = np.zeros((n, D), dtype=np.int32)
+    sums = np.zeros((G, D, 3), dtype=np.int64)
+    if device is None:
+        rc = L.sd_lag_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, D, int(threads),
+                               dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
+    else:
+        rc = L.sd_lag_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, D, int(device), int(threads),
+                                   dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_lag_segments" + ("" if device is None else "_dev"))
+    return formats.Lags(dist, matches, sums)
+
+
+def lag_identities(dist, matches):
+    """float64 identities in percent of (dist, matches), -1 where dist < 0: the identity column's arithmetic
+    (sd_lag_identities)"""
+    import numpy as np
+    d = np.ascontiguousarray(dist, dtype=np.int32)
+    m = np.ascontiguousarray(matches, dtype=np.int32)
+    out = np.zeros(d.shape, dtype=np.float64)
+    load().sd_lag_identities(d.ctypes.data, m.ctypes.data, d.size, out.ctypes.data)
+    return out
+
+
+def lag_periods(sums):
+    """(period int32 [groups], pooled identity float64 [groups, D]) of sums [groups, D, 3] by the library's rule
+    (sd_lag_periods; csrc/sd_lags.hpp).  formats.lag_period is the same rule in Python integers."""
+    import numpy as np
+    s = np.ascontiguousarray(sums, dtype=np.int64)
+    G, D = int(s.shape[0]), int(s.shape[1])
+    period = np.zeros(G, dtype=np.int32)
+    pooled = np.zeros((G, D), dtype=np.float64)
+    load().sd_lag_periods(s.ctypes.data, G, D, period.ctypes.data, pooled.ctypes.data)
+    return period, pooled
+
+
+def lag_kernel_bench(text, starts, ends, group_off, D, device=0, warmup=2, reps=5):
+    """sd_lag_kernel_bench -> {"group_ms", "pairs_ms", "walk_ms", "ident_ms": [...], "pairs", "host_pairs", "K", "K_pairs",
+    "ident_ck_slots", "ident_grid", "grid", "ck_slots"}."""
+    import numpy as np
+    D = _lag_d(D, "lag_kernel_bench")
+    L = load()
+    sb = _b(text)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    go = np.ascontiguousarray(group_off, dtype=np.int64)
+    a, b, c, d = ((C.c_float * reps)() for _ in range(4))
+    info = (C.c_int64 * 8)()
+    rc = L.sd_lag_kernel_bench(sb, len(sb), st.ctypes.data, en.ctypes.data, len(st), go.ctypes.data, len(go) - 1, D, int(device),
+                               int(warmup), int(reps), a, b, c, d, info)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_lag_kernel_bench")
+    out = {"group_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b], "walk_ms": [float(x) for x in c],
+           "ident_ms": [float(x) for x in d]}
+    out.update(zip(("pairs", "host_pairs", "K", "K_pairs", "ident_ck_slots", "ident_grid", "grid", "ck_slots"), [int(x) for x in info]))
+    return out
+
+
+class DeviceLags(namedtuple("DeviceLags", "dist matches sums classes")):
+    """The lag identities of a DeviceFinalRows in device memory (final_lags_device): dist / matches = int32 [n_rows, D] torch
+    tensors, sums = int64 [n_reads, D, 3], on the rows' device; classes = (entries with dist -1, pairs of the lane kernel,
+    pairs left out as -2) on the host."""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> formats.Lags"""
+        from . import formats
+        return formats.Lags(self.dist.cpu().numpy(), self.matches.cpu().numpy(), self.sums.cpu().numpy())
+
+
+def final_lags_device(dfr, reads, D, stream=None):
+    """Identity of every final row to its next D neighbours in the same read, computed on the rows' device from the reads
+    they were selected from (sd_lag_final_dev) -> DeviceLags.  dfr: a DeviceFinalRows; reads: the DeviceReads that was
+    submitted.  torch allocates the outputs on `stream` and the library fills them there; the host waits once, for the
+    class counts.  Pairs the lane kernel does not take keep dist -2 (final_lags_host computes them)."""
+    D = _lag_d(D, "final_lags_device")
+    import torch
+    L = load()
+    dev = dfr.row_off.device
+    st = _torch_stream(torch, dev, stream)
+    n = int(dfr.n_rows)
+    if dfr.row_off.shape[0] != reads.n + 1:
+        raise SdError(SD_ERR_PARAM, "final_lags_device: %d reads for the rows of %d" % (reads.n, dfr.row_off.shape[0] - 1))
+    err = C.create_string_buffer(1024)
+    ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)   # noqa: E731
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    with torch.cuda.stream(st):
+        dist = torch.empty((n, D), dtype=torch.int32, device=dev)
+        matches = torch.empty((n, D), dtype=torch.int32, device=dev)
+        sums = torch.empty((reads.n, D, 3), dtype=torch.int64, device=dev)
+    cls = (C.c_int64 * 3)()
+    _text_check(L.sd_lag_final_dev(ptr(dfr.rows), n, C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, D, dev.index or 0,
+                                   C.c_void_p(st.cuda_stream), ptr(dist), ptr(matches), ptr(sums), cls, err, 1024), err)
+    return DeviceLags(dist, matches, sums, tuple(int(x) for x in cls))
+
+
+def final_lags_host(final_rows, read_seqs, D, threads=1):
+    """final_lags_device without a device (sd_lag_final_host): final_rows = a FinalRows or its (rows, row_off, alt),
+    read_seqs = the job's reads in submit order -> formats.Lags; every pair is computed."""
+    import numpy as np
+    from . import formats
+    D = _lag_d(D, "final_lags_host")
+    L = load()
+    rows = np.ascontiguousarray(final_rows[0])
+    rs = [_b(s) for s in read_seqs]
+    off, at = [], 0
+    for s in rs:
+        off.append(at)
+        at += len(s)
+    n, R = int(rows.shape[0]), len(rs)
+    ro = np.ascontiguousarray(off, dtype=np.int64)
+    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64)
+    dist = np.zeros((n, D), dtype=np.int32)
+    matches = np.zeros((n, D), dtype=np.int32)
+    sums = np.zeros((R, D, 3), dtype=np.int64)
+    rc = L.sd_lag_final_host(rows.ctypes.data, n, b"".join(rs) or b"N", ro.ctypes.data, rl.ctypes.data, R, D, int(threads),
+                             dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_lag_final_host")
+    return formats.Lags(dist, matches, sums)
 
 
 def decompose_files_records(reads_fa, monomers_fa, records_out, **kw):

@@ -524,6 +524,19 @@ def _check_screen(args):
         refuse("--screen needs -v/--overlap smaller than -b/--batch-size (the regions of a read must not overlap)")
 
 
+def _check_lags(args):
+    """--lags requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
+    def refuse(msg):
+        sys.stderr.write("stringdecomposer: %s\n" % msg)
+        sys.exit(2)
+    if shard.world()[2] > 1:
+        refuse("--lags cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
+    if not 1 <= args.lags <= lib.LAG_DMAX:
+        refuse("--lags %d: the number of neighbours is 1 .. %d" % (args.lags, lib.LAG_DMAX))
+    if args.records:
+        refuse("--lags cannot be combined with --records: it is a post-pass over the rows of the final TSV")
+
+
 def _check_lenient(args):
     """--lenient requests this process cannot serve end it here, with one line on stderr, before any work."""
     def refuse(msg):
@@ -562,6 +575,43 @@ def _write_msa(args, final_fn, msa_fn, device):
             msa = lib.msa_segments(seq or b"N", st, en, ms, pt, threads=max(1, int(args.threads)), device=device)
             f.write(formats.format_msa(formats.msa_rows(msa, pt, [(r.read, r.start, r.end, r.monomer) for r in rows]),
                                        header=False))
+
+
+def _write_lags(args, final_fn, lags_fn, period_fn, device):
+    """--lags D: the identity of every row of the final TSV just written to its next D neighbours in the same read
+    (lib.lag_segments on `device`: the lane kernel, the host form for the pairs it does not take) -> <out>_lags.tsv, one
+    line per row, and <out>_period.tsv, one line per read."""
+    from . import formats
+    D = int(args.lags)
+    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
+    reads = {}
+    for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
+        reads.setdefault(n, s.upper())
+        reads.setdefault(n.split()[0], s.upper())
+    groups = formats.by_read(formats.read_final(final_fn))
+    with open(lags_fn, "w", newline="") as fl, open(period_fn, "w", newline="") as fp:
+        at = 0
+        while at < len(groups):   # a call's share: whole reads, rows x D and text bounded
+            text, st, en, off, rows, base, e = [], [], [], [0], [], 0, at
+            while e < len(groups) and (e == at or ((len(rows) + len(groups[e][1])) * D < (1 << 26) and base < (1 << 28))):
+                seq = reads[groups[e][0]]
+                seq = seq if isinstance(seq, bytes) else seq.encode()
+                for r in groups[e][1]:
+                    s0 = min(max(r.start, 0), len(seq))
+                    st.append(base + s0)
+                    en.append(base + min(max(r.end + 1, s0), len(seq)) - 1)   # (an empty segment: end = start - 1)
+                    rows.append((r.read, r.start, r.end))
+                text.append(seq)
+                base += len(seq)
+                off.append(len(rows))
+                e += 1
+            lags = lib.lag_segments(b"".join(text) or b"N", st, en, off, D, device=device, threads=max(1, int(args.threads)))
+            ident = lib.lag_identities(lags.dist, lags.matches).tolist()
+            period, pooled = lib.lag_periods(lags.sums)
+            fl.write(formats.format_lags(formats.LagRow(r[0], r[1], r[2], v) for r, v in zip(rows, ident)))
+            fp.write(formats.format_periods(formats.PeriodRow(g[0], len(g[1]), int(p), v)
+                                            for g, p, v in zip(groups[at:e], period.tolist(), pooled.tolist())))
+            at = e
 
 
 def main(argv=None):
@@ -609,6 +659,12 @@ def main(argv=None):
                         help="also write <out-file>_msa.tsv: one line per row of <out-file>.tsv with the read's bases by column "
                              "of the forward monomer (ACGTN, '-' = deleted) and its insertions as slot:count (a count of 255 "
                              "means 255 or more)")
+    parser.add_argument("--lags", type=int, default=None, metavar="D",
+                        help="also write <out-file>_lags.tsv (one line per row of <out-file>.tsv: read, start, end, then the "
+                             "identity of the row's stretch of the read to that of each of its next D neighbours in the same "
+                             "read, -1.00 where the read ends; nothing is reverse-complemented, so a pair across an inversion "
+                             "scores low) and <out-file>_period.tsv (one line per read: read, rows, the lag with the largest "
+                             "pooled identity, then the D pooled identities); 1 <= D <= 255")
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
@@ -624,6 +680,8 @@ def main(argv=None):
         _check_lenient(args)
     if args.screen is not None:
         _check_screen(args)
+    if args.lags is not None:
+        _check_lags(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -706,6 +764,17 @@ def main(argv=None):
             logger.info("--msa failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the per-instance monomer columns to " + msa_fn)
+
+    if args.lags is not None:
+        lags_fn = os.path.join(args.out_dir, args.out_file + "_lags.tsv")
+        period_fn = os.path.join(args.out_dir, args.out_file + "_period.tsv")
+        try:
+            _write_lags(args, convert_tsv_fn, lags_fn, period_fn, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--lags failed: " + e.msg + "\n")
+            logger.info("--lags failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the identities against lag to " + lags_fn + " and the periods to " + period_fn)
 
     logger.info("Thank you for using StringDecomposer!")
 
