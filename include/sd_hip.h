@@ -1015,6 +1015,62 @@ int sd_lag_kernel_bench(const char* seq, int64_t seqlen, const int64_t* starts, 
                         const int64_t* group_off, int32_t n_groups, int32_t D, int32_t device, int32_t warmup, int32_t reps,
                         float* ms_group, float* ms_pairs, float* ms_walk, float* ms_ident, int64_t info[8]);
 
+/* ---- all-against-all identity in bins (--heatmap): every row against every earlier row of the same read -----------------
+ * Rows in file order; a read (group) owns rows x = 0 .. n-1.  B rows per bin (1 <= B <= 2^20): row x lies in bin x / B, the
+ * group has nb = ceil(n / B) bins.  The pairs of a group are all (x, y) with x < y, and with y - x <= W when W > 0 (W = 0:
+ * no limit).  Query = the segment of row x, the earlier one; target = the segment of row y; (dist, matches) exactly as
+ * sd_nw_identity_batch defines them, so pair (x, y) is the pair (x, d = y - x) of sd_lag_segments bit for bit.  A pair with
+ * an empty side does not exist.  Cell (I, J), I <= J, of a group holds {n, M, C}: the number of pairs with x in bin I and y
+ * in bin J, the sum of their matches, the sum of their dist + matches.  The cells of a group are the row-major upper
+ * triangle, cell I * nb - I (I - 1) / 2 + (J - I); group g starts at cell_off[g], the prefix sum of nb (nb + 1) / 2:
+ * sums[(cell_off[g] + cell) * 3 + {0, 1, 2}].  The pooled identity of a cell is M / C by the identity column's arithmetic,
+ * -1 for a cell without pairs (sd_heat_identities).  No per-pair result exists anywhere: memory is O(rows + cells).
+ * Refused with SD_ERR_PARAM and the numbers in errbuf, before any pair is aligned: B, W or max_pairs out of range; more
+ * than SD_HEAT_CELLS_MAX cells in the call (805 MB of sums); more pairs than max_pairs (0: no limit).
+ *
+ * sd_heat_layout: the closed forms, host only: cell_off[0 .. n_groups] (may be NULL), the cells and the pairs of the groups.
+ * sd_heat_segments: host threads, any length, any byte alphabet; segments and groups as sd_lag_segments takes them.
+ * which = 0: every pair; which = 1: only the pairs the kernel does not take (below).  sums (cells x 3) is overwritten.
+ * sd_heat_segments_dev: the kernel of csrc/sd_heat.hip -- a wave per (target, strip of up to 64 consecutive queries): the
+ * wave builds the target's match masks once, in LDS, every lane walks its own query against them, and the wave reduces
+ * {1, matches, dist + matches} per cell before one triple of 64-bit atomic adds -- for targets up to 512 bp and queries up to
+ * 1024 bp that edlib does not split, over a text in ACGTN; the host form with which = 1 added to it.  The same bytes as
+ * sd_heat_segments(which = 0).  classes = {pairs of the kernel, pairs of the host, pairs with an empty side}. */
+#define SD_HEAT_CELLS_MAX ((int64_t)1 << 25)
+int sd_heat_layout(const int64_t* group_off, int32_t n_groups, int64_t B, int64_t W, int64_t* cell_off, int64_t* cells_total,
+                   int64_t* pairs);
+int sd_heat_segments(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                     const int64_t* group_off, int32_t n_groups, int64_t B, int64_t W, int64_t max_pairs, int32_t which,
+                     int32_t threads, int64_t* sums, char* errbuf, size_t errlen);
+int sd_heat_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                         const int64_t* group_off, int32_t n_groups, int64_t B, int64_t W, int64_t max_pairs, int32_t device,
+                         int32_t threads, int64_t* sums, int64_t classes[3], char* errbuf, size_t errlen);
+/* The device-resident form, behind sd_stream_submit_dev -> sd_stream_collect_final_dev: d_rows, d_text, read_off and
+ * read_lens as sd_lag_final_dev takes them; a group is a read, its rows adjacent and the reads ascending (else
+ * SD_ERR_PARAM).  d_sums (n_cells x 3 int64) is the caller's, on `device`; n_cells must be what sd_heat_layout gives for
+ * the rows per read (else SD_ERR_PARAM: nothing is written).  Everything is ordered on hip_stream.  The host waits twice:
+ * for the rows per read and their lengths (the closed forms, the two refusals and classes), then for the work items per
+ * word class, which size the launches.  The pairs the kernel does not take are left out and counted in classes[1].  The
+ * call returns with the kernels in flight; its workspace is kept per device, and the next call on that device first waits
+ * for them.
+ * sd_heat_final_host: the same from host arrays, with the `which` of sd_heat_segments: the device sums plus the sums of
+ * which = 1 are the sums of which = 0. */
+int sd_heat_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_text, const int64_t* read_off,
+                      const int64_t* read_lens, int32_t n_reads, int64_t B, int64_t W, int64_t max_pairs, int32_t device,
+                      void* hip_stream, int64_t* d_sums, int64_t n_cells, int64_t classes[3], char* errbuf, size_t errlen);
+int sd_heat_final_host(const sd_final_row* rows, int64_t n_rows, const char* text, const int64_t* read_off, const int64_t* read_lens,
+                       int32_t n_reads, int64_t B, int64_t W, int64_t max_pairs, int32_t which, int32_t threads, int64_t* sums,
+                       int64_t n_cells, int64_t classes[3], char* errbuf, size_t errlen);
+/* out[i] = the pooled identity in percent of cell i (sums + 3 i), -1 for a cell without pairs. */
+void sd_heat_identities(const int64_t* sums, int64_t n_cells, double* out);
+/* Developer entry (tools/heat_bench.py): the arguments of sd_heat_segments_dev; warmup + reps times each, between two HIP
+ * events: ms_group = plan + scatter + scan, ms_pairs = the pair kernels, ms_walk = the same with the masks built once per
+ * wave and without the reduction (the walk alone; its sums mean nothing).  info = kernel pairs, host pairs, K of the word
+ * class with most work items, work items, cells, work items / grid / checkpoint slots of that class. */
+int sd_heat_kernel_bench(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
+                         const int64_t* group_off, int32_t n_groups, int64_t B, int64_t W, int32_t device, int32_t warmup,
+                         int32_t reps, float* ms_group, float* ms_pairs, float* ms_walk, int64_t info[8]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

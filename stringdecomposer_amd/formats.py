@@ -639,6 +639,93 @@ def read_periods(path):
     return _read_lag_file(path, PeriodRow)
 
 
+# ---- heatmap --------------------------------------------------------------------------------------
+# --heatmap B[,W]: <out>_heatmap.tsv, one line per cell with pairs -- read, bin_i, bin_j (bin_i <= bin_j), start and end of
+# bin i (the start of its first row, the end of its last row, as <out>.tsv prints them), start and end of bin j, the number
+# of pairs, and their pooled identity (sum of matches / sum of columns, "%.2f").  Lines in the order read, bin_i, bin_j.
+class Heat:
+    """lib.heat_segments / final_heat_host / DeviceHeat.to_host(): sums = int64 [cells, 3] = (pairs, sum of matches, sum of
+    dist + matches) per cell; group g owns nb[g] bins of B rows and the cells cell_off[g] .. cell_off[g + 1], the row-major
+    upper triangle of its nb x nb bins: cell (I, J), I <= J, at I * nb - I * (I - 1) // 2 + (J - I).  W: the largest row
+    distance of a pair, 0 = no limit.  classes (where the call counts them): (kernel pairs, host pairs, pairs with an
+    empty side)."""
+
+    def __init__(self, sums, cell_off, nb, B, W=0):
+        self.sums, self.cell_off, self.nb, self.B, self.W = sums, cell_off, nb, int(B), int(W)
+        self.classes = None
+
+    def index(self, g, I, J):
+        nb = int(self.nb[g])
+        if not 0 <= I <= J < nb:
+            raise IndexError("cell (%d, %d) of a group of %d bins" % (I, J, nb))
+        return int(self.cell_off[g]) + I * nb - I * (I - 1) // 2 + (J - I)
+
+    def cell(self, g, I, J):
+        """(pairs, sum of matches, sum of dist + matches) of cell (I, J), I <= J, of group g, as Python integers"""
+        return tuple(int(v) for v in self.sums[self.index(g, I, J)])
+
+    def matrix(self, g):
+        """dense nb x nb float64 array of the pooled identities in percent of group g, the upper triangle mirrored, nan
+        where a cell has no pair"""
+        import numpy as np
+        nb = int(self.nb[g])
+        out = np.full((nb, nb), np.nan, dtype=np.float64)
+        for I in range(nb):
+            for J in range(I, nb):
+                n, m, c = self.cell(g, I, J)
+                if n > 0 and c > 0:
+                    out[I, J] = out[J, I] = heat_pooled(m, c)
+        return out
+
+
+HeatRow = namedtuple("HeatRow", "read bin_i bin_j start_i end_i start_j end_j pairs identity")   # a line of <out>_heatmap.tsv
+
+
+def heat_pooled(m, c):
+    """the identity column's arithmetic on the sums of a cell: 0.0 + m, / c, * 100 in doubles"""
+    a = 0.0
+    a += m
+    a /= c
+    return a * 100
+
+
+def heat_rows(heat, g, read, rows):
+    """The HeatRows of group g of a Heat: rows = the group's (start, end) pairs in row order; cells without pairs are left out"""
+    out = []
+    nb, B = int(heat.nb[g]), heat.B
+    for I in range(nb):
+        for J in range(I, nb):
+            n, m, c = heat.cell(g, I, J)
+            if n > 0:
+                out.append(HeatRow(read, I, J, rows[I * B][0], rows[min((I + 1) * B, len(rows)) - 1][1], rows[J * B][0],
+                                   rows[min((J + 1) * B, len(rows)) - 1][1], n, heat_pooled(m, c) if c > 0 else -1.0))
+    return out
+
+
+def format_heatmap(rows):
+    return "".join("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\n" % tuple(r) for r in rows)
+
+
+def write_heatmap(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_heatmap(rows))
+
+
+def read_heatmap(path):
+    """<out>_heatmap.tsv -> [HeatRow]."""
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            x = line.rstrip("\n").split("\t")
+            if len(x) != 9:
+                raise FormatError(path, lineno, "expected 9 columns, got %d" % len(x))
+            try:
+                out.append(HeatRow(x[0], *[int(v) for v in x[1:8]], float(x[8])))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out
+
+
 # ---- screen ---------------------------------------------------------------------------------------
 ScreenRow = namedtuple("ScreenRow", "read start end chunks best_distance best_template")   # a line of <out>_screen.tsv
 

@@ -58,6 +58,8 @@ EXPORTS = [
     "sd_msa_final_size_dev", "sd_msa_final_write_dev", "sd_msa_kernel_bench",
     "sd_lag_segments", "sd_lag_segments_dev", "sd_lag_final_dev", "sd_lag_final_host", "sd_lag_identities", "sd_lag_periods",
     "sd_lag_kernel_bench",
+    "sd_heat_layout", "sd_heat_segments", "sd_heat_segments_dev", "sd_heat_final_dev", "sd_heat_final_host", "sd_heat_identities",
+    "sd_heat_kernel_bench",
     "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
     "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
     "sd_screen_kernel_bench",
@@ -258,6 +260,20 @@ def load():
     L.sd_lag_kernel_bench.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                       P(C.c_int64)]
+    L.sd_heat_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, P(C.c_int64), P(C.c_int64)]
+    L.sd_heat_segments.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                   C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_heat_segments_dev.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                       C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_heat_final_dev.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                    C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_heat_final_host.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_heat_identities.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.sd_heat_identities.restype = None
+    L.sd_heat_kernel_bench.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                       C.c_int64, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float),
+                                       P(C.c_int64)]
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
@@ -938,6 +954,191 @@ def final_lags_host(final_rows, read_seqs, D, threads=1):
     if rc != SD_OK:
         raise SdError(rc, "sd_lag_final_host")
     return formats.Lags(dist, matches, sums)
+
+
+HEAT_CELLS_MAX = 1 << 25
+HEAT_BMAX = 1 << 20
+
+
+def _heat_args(B, W, max_pairs, who):
+    """1 <= B <= 2^20, W >= 0, max_pairs >= 0, refused here before any array is made or any device is touched"""
+    def is_int(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+    if not is_int(B) or not 1 <= B <= HEAT_BMAX:
+        raise SdError(SD_ERR_PARAM, "%s: B = %r, must be an integer 1 .. %d" % (who, B, HEAT_BMAX))
+    if not is_int(W) or not 0 <= W < (1 << 62):
+        raise SdError(SD_ERR_PARAM, "%s: W = %r, must be an integer, 0 (no limit) or more" % (who, W))
+    if not is_int(max_pairs) or not 0 <= max_pairs < (1 << 62):
+        raise SdError(SD_ERR_PARAM, "%s: max_pairs = %r, must be an integer, 0 (no limit) or more" % (who, max_pairs))
+    return B, W, max_pairs
+
+
+def heat_layout(group_off, B, W=0):
+    """The closed forms of the heatmap (sd_heat_layout; include/sd_hip.h): for groups of group_off[g + 1] - group_off[g] rows,
+    B rows per bin and pairs up to W rows apart (0: no limit) -> (cell_off int64 [groups + 1], nb int64 [groups], cells, pairs).
+    No device is touched, nothing is refused for size."""
+    import numpy as np
+    B, W, _ = _heat_args(B, W, 0, "heat_layout")
+    go = np.ascontiguousarray(group_off, dtype=np.int64)
+    if go.ndim != 1 or go.shape[0] < 1:
+        raise SdError(SD_ERR_PARAM, "heat_layout: group_off is empty")
+    G = int(go.shape[0]) - 1
+    cell_off = np.zeros(G + 1, dtype=np.int64)
+    cells, pairs = C.c_int64(0), C.c_int64(0)
+    rc = load().sd_heat_layout(go.ctypes.data, G, B, W, cell_off.ctypes.data, C.byref(cells), C.byref(pairs))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_heat_layout")
+    nb = (np.diff(go) + B - 1) // B
+    return cell_off, nb.astype(np.int64), int(cells.value), int(pairs.value)
+
+
+def heat_segments(text, starts, ends, group_off, B, W=0, device=None, threads=1, max_pairs=0, which=0):
+    """All-against-all identity of the segments of each group, as sums per bin (sd_heat_segments[_dev]; include/sd_hip.h):
+    segments and groups as lag_segments takes them, B rows per bin, pairs (x, y), x < y, up to W rows apart (0: no limit);
+    query = the earlier segment -> formats.Heat(sums, cell_off, nb, B, W), sums int64 [cells, 3] = (pairs, sum of matches, sum
+    of dist + matches) per cell of each group's upper triangle.  device=None: host threads (which=1: only the pairs the
+    kernel would leave to the host); device=<ordinal>: the kernel plus the host form for the pairs it does not take -- the
+    same bytes; the Heat then carries .classes = (kernel pairs, host pairs, pairs with an empty side).  More than
+    HEAT_CELLS_MAX cells, or more than max_pairs pairs (0: no limit), are refused before any alignment."""
+    import numpy as np
+    from . import formats
+    B, W, max_pairs = _heat_args(B, W, max_pairs, "heat_segments")
+    L = load()
+    sb = _b(text)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    go = np.ascontiguousarray(group_off, dtype=np.int64)
+    n = int(st.shape[0])
+    if en.shape[0] != n or go.ndim != 1 or go.shape[0] < 1:
+        raise SdError(SD_ERR_PARAM, "heat_segments: starts and ends differ in length, or group_off is empty")
+    G = int(go.shape[0]) - 1
+    err = C.create_string_buffer(1024)
+    # the sums are sized by the closed forms; a layout the library would refuse gets one cell, and the library's refusal
+    cell_off = np.zeros(G + 1, dtype=np.int64)
+    cells, pairs = C.c_int64(0), C.c_int64(0)
+    ok = bool((np.diff(go) >= 0).all()) and L.sd_heat_layout(go.ctypes.data, G, B, W, cell_off.ctypes.data, C.byref(cells), C.byref(pairs)) == SD_OK
+    n_cells = int(cells.value) if ok and cells.value <= HEAT_CELLS_MAX and (max_pairs == 0 or pairs.value <= max_pairs) else 0
+    sums = np.zeros((max(n_cells, 1), 3), dtype=np.int64)
+    cls = (C.c_int64 * 3)()
+    if device is None:
+        rc = L.sd_heat_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, B, W, max_pairs, int(which),
+                                int(threads), sums.ctypes.data, err, 1024)
+    else:
+        rc = L.sd_heat_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, B, W, max_pairs, int(device),
+                                    int(threads), sums.ctypes.data, cls, err, 1024)
+    _text_check(rc, err)
+    heat = formats.Heat(sums[:n_cells], cell_off, (np.diff(go) + B - 1) // B, B, W)
+    heat.classes = tuple(int(x) for x in cls) if device is not None else None
+    return heat
+
+
+def heat_identities(sums):
+    """float64 pooled identities in percent of sums [cells, 3], -1 for a cell without pairs (sd_heat_identities)"""
+    import numpy as np
+    s = np.ascontiguousarray(sums, dtype=np.int64).reshape(-1, 3)
+    out = np.zeros(s.shape[0], dtype=np.float64)
+    load().sd_heat_identities(s.ctypes.data, s.shape[0], out.ctypes.data)
+    return out
+
+
+def heat_kernel_bench(text, starts, ends, group_off, B, W=0, device=0, warmup=2, reps=5):
+    """sd_heat_kernel_bench -> {"group_ms", "pairs_ms", "walk_ms": [...], "pairs", "host_pairs", "K", "items", "cells", "K_items",
+    "grid", "ck_slots"}."""
+    import numpy as np
+    B, W, _ = _heat_args(B, W, 0, "heat_kernel_bench")
+    L = load()
+    sb = _b(text)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    go = np.ascontiguousarray(group_off, dtype=np.int64)
+    a, b, c = ((C.c_float * reps)() for _ in range(3))
+    info = (C.c_int64 * 8)()
+    rc = L.sd_heat_kernel_bench(sb, len(sb), st.ctypes.data, en.ctypes.data, len(st), go.ctypes.data, len(go) - 1, B, W, int(device),
+                                int(warmup), int(reps), a, b, c, info)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_heat_kernel_bench")
+    out = {"group_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b], "walk_ms": [float(x) for x in c]}
+    out.update(zip(("pairs", "host_pairs", "K", "items", "cells", "K_items", "grid", "ck_slots"), [int(x) for x in info]))
+    return out
+
+
+class DeviceHeat(namedtuple("DeviceHeat", "sums cell_off nb classes")):
+    """The heatmap sums of a DeviceFinalRows in device memory (final_heat_device): sums = int64 [cells, 3], cell_off = int64
+    [n_reads + 1], nb = int64 [n_reads] torch tensors on the rows' device; classes = (pairs of the kernel, pairs left out for
+    the host, pairs with an empty side) on the host."""
+    __slots__ = ()
+
+    def to_host(self, B, W=0):
+        """-> formats.Heat"""
+        from . import formats
+        return formats.Heat(self.sums.cpu().numpy(), self.cell_off.cpu().numpy(), self.nb.cpu().numpy(), B, W)
+
+
+def final_heat_device(dfr, reads, B, W=0, stream=None, max_pairs=0):
+    """All-against-all identity of the final rows of each read, as sums per bin, computed on the rows' device from the reads
+    they were selected from (sd_heat_final_dev) -> DeviceHeat.  dfr: a DeviceFinalRows; reads: the DeviceReads that was
+    submitted.  The cells come from the rows per read (dfr.row_off, read once); torch allocates the outputs on `stream` and
+    the library fills them there.  Pairs the kernel does not take are left out and counted in classes[1]
+    (final_heat_host(which=1) computes them)."""
+    B, W, max_pairs = _heat_args(B, W, max_pairs, "final_heat_device")
+    import numpy as np
+    import torch
+    L = load()
+    dev = dfr.row_off.device
+    st = _torch_stream(torch, dev, stream)
+    n = int(dfr.n_rows)
+    if dfr.row_off.shape[0] != reads.n + 1:
+        raise SdError(SD_ERR_PARAM, "final_heat_device: %d reads for the rows of %d" % (reads.n, dfr.row_off.shape[0] - 1))
+    cell_off, nb, cells, pairs = heat_layout(dfr.row_off.cpu().numpy(), B, W)
+    if cells > HEAT_CELLS_MAX:
+        raise SdError(SD_ERR_PARAM, "final_heat_device: %d cells, the cap is %d (HEAT_CELLS_MAX): use more rows per bin" % (cells, HEAT_CELLS_MAX))
+    err = C.create_string_buffer(1024)
+    ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)   # noqa: E731
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    with torch.cuda.stream(st):
+        sums = torch.empty((cells, 3), dtype=torch.int64, device=dev)
+        d_off = torch.from_numpy(cell_off).to(dev, non_blocking=False)
+        d_nb = torch.from_numpy(np.ascontiguousarray(nb)).to(dev, non_blocking=False)
+    cls = (C.c_int64 * 3)()
+    _text_check(L.sd_heat_final_dev(ptr(dfr.rows), n, C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, B, W, max_pairs,
+                                    dev.index or 0, C.c_void_p(st.cuda_stream), ptr(sums), cells, cls, err, 1024), err)
+    return DeviceHeat(sums, d_off, d_nb, tuple(int(x) for x in cls))
+
+
+def final_heat_host(final_rows, read_seqs, B, W=0, threads=1, max_pairs=0, which=0):
+    """final_heat_device without a device (sd_heat_final_host): final_rows = a FinalRows or its (rows, row_off, alt),
+    read_seqs = the job's reads in submit order -> formats.Heat with .classes; which=0: every pair, which=1: only the pairs
+    the kernel leaves out."""
+    import numpy as np
+    from . import formats
+    B, W, max_pairs = _heat_args(B, W, max_pairs, "final_heat_host")
+    L = load()
+    rows = np.ascontiguousarray(final_rows[0])
+    rs = [_b(s) for s in read_seqs]
+    off, at = [], 0
+    for s in rs:
+        off.append(at)
+        at += len(s)
+    n, R = int(rows.shape[0]), len(rs)
+    ro = np.ascontiguousarray(off, dtype=np.int64)
+    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64)
+    counts = np.bincount(rows["read"], minlength=R) if n else np.zeros(R, dtype=np.int64)
+    if counts.shape[0] != R:
+        raise SdError(SD_ERR_PARAM, "final_heat_host: a row's read index lies outside the %d reads" % R)
+    go = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cell_off, nb, cells, pairs = heat_layout(go, B, W)
+    n_cells = cells if cells <= HEAT_CELLS_MAX else 0   # (over the cap: the library refuses before it writes)
+    sums = np.zeros((max(n_cells, 1), 3), dtype=np.int64)
+    cls = (C.c_int64 * 3)()
+    err = C.create_string_buffer(1024)
+    _text_check(L.sd_heat_final_host(rows.ctypes.data, n, b"".join(rs) or b"N", ro.ctypes.data, rl.ctypes.data, R, B, W, max_pairs,
+                                     int(which), int(threads), sums.ctypes.data, n_cells, cls, err, 1024), err)
+    heat = formats.Heat(sums[:n_cells], cell_off, nb, B, W)
+    heat.classes = tuple(int(x) for x in cls)
+    return heat
 
 
 def decompose_files_records(reads_fa, monomers_fa, records_out, **kw):

@@ -537,6 +537,31 @@ def _check_lags(args):
         refuse("--lags cannot be combined with --records: it is a post-pass over the rows of the final TSV")
 
 
+def _heatmap_arg(text):
+    """'B' or 'B,W' -> (B, W), None when the text is neither"""
+    parts = text.split(",")
+    if not 1 <= len(parts) <= 2 or not all(x.strip().isdigit() for x in parts):
+        return None
+    return int(parts[0]), int(parts[1]) if len(parts) == 2 else 0
+
+
+def _check_heatmap(args):
+    """--heatmap requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
+    def refuse(msg):
+        sys.stderr.write("stringdecomposer: %s\n" % msg)
+        sys.exit(2)
+    if shard.world()[2] > 1:
+        refuse("--heatmap cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
+    bw = _heatmap_arg(args.heatmap)
+    if bw is None or not 1 <= bw[0] <= lib.HEAT_BMAX or bw[1] >= (1 << 62):
+        refuse("--heatmap %s: expected B or B,W with 1 <= B <= %d rows per bin and W >= 0 (0: no limit) the largest row "
+               "distance of a pair" % (args.heatmap, lib.HEAT_BMAX))
+    if args.heatmap_max_pairs < 0:
+        refuse("--heatmap-max-pairs %d: the cap is 0 (no limit) or more" % args.heatmap_max_pairs)
+    if args.records:
+        refuse("--heatmap cannot be combined with --records: it is a post-pass over the rows of the final TSV")
+
+
 def _check_lenient(args):
     """--lenient requests this process cannot serve end it here, with one line on stderr, before any work."""
     def refuse(msg):
@@ -614,6 +639,38 @@ def _write_lags(args, final_fn, lags_fn, period_fn, device):
             at = e
 
 
+def _write_heatmap(args, final_fn, heat_fn, device):
+    """--heatmap B[,W]: the identity of every row of the final TSV just written to every earlier row of the same read
+    (up to W rows back), pooled per pair of bins of B rows (lib.heat_segments on `device`: the kernel, the host form for
+    the pairs it does not take) -> <out>_heatmap.tsv, one line per cell with pairs, read by read."""
+    from . import formats
+    B, W = _heatmap_arg(args.heatmap)
+    cap = int(args.heatmap_max_pairs)
+    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
+    reads = {}
+    for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
+        reads.setdefault(n, s.upper())
+        reads.setdefault(n.split()[0], s.upper())
+    groups = formats.by_read(formats.read_final(final_fn))
+    for read, rows in groups:   # every read's size first: a refusal leaves no half-written file
+        _, _, cells, pairs = lib.heat_layout([0, len(rows)], B, W)
+        if cells > lib.HEAT_CELLS_MAX:
+            raise lib.SdError(lib.SD_ERR_PARAM, "read %s: %d rows in bins of %d give %d cells, the cap is %d: use more rows per bin"
+                              % (read, len(rows), B, cells, lib.HEAT_CELLS_MAX))
+        if cap > 0 and pairs > cap:
+            raise lib.SdError(lib.SD_ERR_PARAM, "read %s: %d rows give %d pairs, the cap is %d (--heatmap-max-pairs): give a row "
+                              "distance limit (--heatmap B,W) or raise the cap" % (read, len(rows), pairs, cap))
+    with open(heat_fn, "w", newline="") as f:
+        for read, rows in groups:
+            seq = reads[read]
+            seq = seq if isinstance(seq, bytes) else seq.encode()
+            st = [min(max(r.start, 0), len(seq)) for r in rows]
+            en = [min(max(r.end + 1, s), len(seq)) - 1 for r, s in zip(rows, st)]   # (an empty segment: end = start - 1)
+            heat = lib.heat_segments(seq or b"N", st, en, [0, len(rows)], B, W, device=device, threads=max(1, int(args.threads)),
+                                     max_pairs=cap)
+            f.write(formats.format_heatmap(formats.heat_rows(heat, 0, read, [(r.start, r.end) for r in rows])))
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Decomposes string into blocks alphabet")
     parser.add_argument("sequences", help="fasta-file with long reads or genomic sequences")
@@ -665,6 +722,15 @@ def main(argv=None):
                              "read, -1.00 where the read ends; nothing is reverse-complemented, so a pair across an inversion "
                              "scores low) and <out-file>_period.tsv (one line per read: read, rows, the lag with the largest "
                              "pooled identity, then the D pooled identities); 1 <= D <= 255")
+    parser.add_argument("--heatmap", default=None, metavar="B[,W]",
+                        help="also write <out-file>_heatmap.tsv: the identity of every row of <out-file>.tsv to every other row "
+                             "of the same read (with W: to the rows up to W rows away), pooled in bins of B consecutive rows; "
+                             "one line per pair of bins with pairs: read, bin_i, bin_j, start_i, end_i, start_j, end_j, pairs, "
+                             "identity (sum of matches / sum of alignment columns).  The earlier row is the query; nothing is "
+                             "reverse-complemented.  1 <= B <= 1048576; at most 33554432 cells per read")
+    parser.add_argument("--heatmap-max-pairs", dest="heatmap_max_pairs", type=int, default=4000000000, metavar="N",
+                        help="refuse a read whose heatmap needs more than N pairs (by default 4000000000, about 8 s of device "
+                             "time on 171-bp blocks; 0: no limit)")
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
@@ -682,6 +748,8 @@ def main(argv=None):
         _check_screen(args)
     if args.lags is not None:
         _check_lags(args)
+    if args.heatmap is not None:
+        _check_heatmap(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -775,6 +843,16 @@ def main(argv=None):
             logger.info("--lags failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the identities against lag to " + lags_fn + " and the periods to " + period_fn)
+
+    if args.heatmap is not None:
+        heat_fn = os.path.join(args.out_dir, args.out_file + "_heatmap.tsv")
+        try:
+            _write_heatmap(args, convert_tsv_fn, heat_fn, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--heatmap failed: " + e.msg + "\n")
+            logger.info("--heatmap failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the binned all-against-all identities to " + heat_fn)
 
     logger.info("Thank you for using StringDecomposer!")
 
