@@ -1071,6 +1071,64 @@ int sd_heat_kernel_bench(const char* seq, int64_t seqlen, const int64_t* starts,
                          const int64_t* group_off, int32_t n_groups, int64_t B, int64_t W, int32_t device, int32_t warmup,
                          int32_t reps, float* ms_group, float* ms_pairs, float* ms_walk, int64_t info[8]);
 
+/* ---- k-mer autocorrelation of every read against itself (--autocorr): no monomer file, a period in bases ----------------
+ * A read is a text T[0 .. n).  Two positions match when they hold the same byte and that byte is one of A C G T; N and
+ * every other byte match nothing, themselves included.  For 1 <= k <= SD_AUTOCORR_KMAX and a lag d >= 1, position i is a hit
+ * at lag d when 0 <= i <= n - d - k and T[i + j] matches T[i + d + j] for j = 0 .. k - 1: the k-mer at i recurs at i + d
+ * and neither copy holds an N.  With a window length W in bases (W = 0: one window, the whole read) read r has
+ * max(1, ceil(n / W)) windows, window w = [w W, min(n, (w + 1) W)), and starts at window win_off[r] of the call.
+ * counts[(win_off[r] + w) * D + d - 1], d = 1 .. D, is the number of hits at lag d whose i lies in window w; the partner
+ * at i + d may lie beyond the window, so the windows of a read sum to its W = 0 spectrum.  Lags above n - k count 0.
+ * Reads are text + read_off[r], read_lens[r] bytes each: any byte alphabet, gaps, padding and any order of offsets, as
+ * sd_stream_submit_dev takes them.  Every count is an exact integer; host and device forms return the same bytes.
+ * Refused with SD_ERR_PARAM and the numbers in errbuf, before any device work: k outside 1 .. SD_AUTOCORR_KMAX, D outside
+ * 1 .. SD_AUTOCORR_DMAX, W < 0, more than SD_AUTOCORR_CELLS_MAX cells (windows x D) in the call (1 GB of counters).
+ *
+ * sd_autocorr_layout: host only: win_off[0 .. n_reads] (may be NULL) and the windows of the call.
+ * sd_autocorr_host: host threads.  counts (windows x D) is overwritten.
+ * sd_autocorr_dev: the kernels of csrc/sd_autocorr.hip -- the text becomes three bit planes (code low bit, code high bit,
+ * valid), 64 bases per word; a workgroup takes a tile of a window and a block of lags, a lane one lag: per tile word it
+ * shifts the partner planes by its lag, forms the equality word, finds the starts of k-runs by shift-and doubling and adds
+ * a population count; one 64-bit atomic add per (window, lag) and workgroup.  The reads are uploaded, the counts come
+ * back; every cell is the kernel's (threads is unused).  No launch exceeds a fixed amount of work (sd_autocorr_info). */
+#define SD_AUTOCORR_KMAX 32
+#define SD_AUTOCORR_DMAX (1 << 20)
+#define SD_AUTOCORR_CELLS_MAX ((int64_t)1 << 27)
+int sd_autocorr_layout(const int64_t* read_lens, int32_t n_reads, int64_t W, int64_t* win_off, int64_t* windows_total);
+int sd_autocorr_host(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k, int64_t D,
+                     int64_t W, int32_t threads, int64_t* counts, char* errbuf, size_t errlen);
+int sd_autocorr_dev(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k, int64_t D,
+                    int64_t W, int32_t device, int32_t threads, int64_t* counts, char* errbuf, size_t errlen);
+/* The device-resident form: d_text is device memory of `device` (read_off and read_lens HOST arrays), d_counts (windows x D
+ * int64) the caller's, on `device`, zeroed by the call whatever it held.  Everything is ordered on hip_stream; the host
+ * waits for nothing and the call returns with the kernels in flight.  Its workspace (planes, tables) is kept per device,
+ * and the next call on that device first waits for them.  SD_ERR_PARAM for a buffer that is not device memory,
+ * SD_ERR_UNSUPPORTED for another device's. */
+int sd_autocorr_reads_dev(const void* d_text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k,
+                          int64_t D, int64_t W, int32_t device, void* hip_stream, int64_t* d_counts, char* errbuf, size_t errlen);
+/* positions[(win_off[r] + w) * D + d - 1] = the number of i in window w with i <= n - d - k: what a count is out of. */
+int sd_autocorr_positions(const int64_t* read_lens, int32_t n_reads, int32_t k, int64_t D, int64_t W, int64_t* positions);
+/* Peaks, integers only (csrc/sd_autocorr.hpp).  In a spectrum A[1 .. D] with smallest lag LO >= 1 and radius R >= 0, lag
+ * d >= LO is a peak when A[d] > 0, A[d] >= A[e] for every e in [max(LO, d - R), min(D, d + R)], and A[d] > A[e] for every
+ * such e < d (ties go to the smaller lag).  Peaks are ordered by count descending, then lag ascending; the first P of
+ * each of the n_windows spectra of counts go to lag / count [n_windows x P], the tails filled with 0.  The period of a
+ * spectrum is its first peak's lag, 0 when it has none. */
+int sd_autocorr_peaks(const int64_t* counts, int64_t n_windows, int64_t D, int64_t LO, int64_t R, int64_t P, int64_t* lag,
+                      int64_t* count);
+/* The seed of a read with period p: with E[i] = 1 where i is a hit at lag p, the longest run of consecutive ones in E (of
+ * equal runs the first) starts at *start and has *run ones; T[*start .. *start + p) is the seed.  *start = -1, *run = 0
+ * when no position is a hit.  Host only. */
+int sd_autocorr_seed(const char* text, int64_t n, int32_t k, int64_t p, int64_t* start, int64_t* run);
+/* info = {bases of a tile, lags of a workgroup, the most base-lag products one launch of the pair kernel takes, launches
+ * of the pair kernel in this process so far}. */
+void sd_autocorr_info(int64_t info[4]);
+/* Developer entry (tools/autocorr_bench.py): the arguments of sd_autocorr_dev; warmup + reps times each, between two HIP
+ * events: ms_prep = the plane kernel, ms_pairs = every launch of the pair kernel.  info = launches, workgroups, cells,
+ * plane words. */
+int sd_autocorr_kernel_bench(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k,
+                             int64_t D, int64_t W, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_pairs,
+                             int64_t info[4]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

@@ -33,6 +33,12 @@ Two more text files are this package's own (opt-in, `--profile`):
                       edit distance of a monomer or reverse complement against one of them), best_template (its name,
                       with ' for a reverse complement).  read_screen / write_screen below.
 
+  <out>_autocorr.tsv  (`--autocorr K[,D]`) one line per (read, window), no header: read, start, end (the window's bases
+                      [start, end), 0-based), k, period (the lag of the first peak, 0 = none), count (positions whose k-mer
+                      recurs `period` bases on), positions (how many could), then up to P columns lag:count, the peaks.
+                      <out>_autocorr_spectrum.tsv (`--autocorr-spectrum`): read, start, end, lag, count, positions for
+                      every lag of every window with a count.  read_autocorr / read_autocorr_spectrum below.
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -726,8 +732,90 @@ def read_heatmap(path):
     return out
 
 
+# ---- autocorr -------------------------------------------------------------------------------------
+# --autocorr K[,D]: <out>_autocorr.tsv, one line per (read, window) -- read, start, end (the window's bases [start, end),
+# 0-based), k, period (the lag of the first peak, 0 = none), count (hits at the period), positions (the i of the window that
+# could be a hit at the period), then up to P further columns lag:count, the peaks in their order.  Lines in the order
+# read, window.  <out>_autocorr_spectrum.tsv (--autocorr-spectrum): read, start, end, lag, count, positions for every lag
+# of every window with count > 0, in the order read, window, lag.
+class Autocorr:
+    """lib.autocorr / DeviceAutocorr.to_host(): counts = int64 [windows, D], counts[w, d - 1] = the hits at lag d whose first
+    position lies in window w (include/sd_hip.h: sd_autocorr_*); read r owns the windows win_off[r] .. win_off[r + 1], window
+    w covers the bases [win_start[w], win_end[w]) of its read; k: the k-mer length."""
+
+    def __init__(self, counts, win_off, win_start, win_end, k):
+        self.counts, self.win_off, self.win_start, self.win_end, self.k = counts, win_off, win_start, win_end, int(k)
+
+    @property
+    def D(self):
+        return int(self.counts.shape[1])
+
+    def windows(self, r):
+        return range(int(self.win_off[r]), int(self.win_off[r + 1]))
+
+    def spectrum(self, r):
+        """the whole-read spectrum of read r: the sum of its windows, int64 [D]"""
+        return self.counts[int(self.win_off[r]):int(self.win_off[r + 1])].sum(axis=0)
+
+
+AutocorrRow = namedtuple("AutocorrRow", "read start end k period count positions peaks")   # a line of <out>_autocorr.tsv
+AutocorrSpectrumRow = namedtuple("AutocorrSpectrumRow", "read start end lag count positions")   # ... of <out>_autocorr_spectrum.tsv
+
+
+def format_autocorr(rows):
+    return "".join("%s\t%d\t%d\t%d\t%d\t%d\t%d%s\n" % (tuple(r)[:7] + ("".join("\t%d:%d" % tuple(p) for p in r.peaks),)) for r in rows)
+
+
+def write_autocorr(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_autocorr(rows))
+
+
+def read_autocorr(path):
+    """<out>_autocorr.tsv -> [AutocorrRow]; peaks = a tuple of (lag, count)."""
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            x = line.rstrip("\n").split("\t")
+            if len(x) < 7:
+                raise FormatError(path, lineno, "expected at least 7 columns, got %d" % len(x))
+            try:
+                peaks = []
+                for p in x[7:]:
+                    lag, _, count = p.partition(":")
+                    peaks.append((int(lag), int(count)))
+                out.append(AutocorrRow(x[0], *[int(v) for v in x[1:7]], tuple(peaks)))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out
+
+
+def format_autocorr_spectrum(rows):
+    return "".join("%s\t%d\t%d\t%d\t%d\t%d\n" % tuple(r) for r in rows)
+
+
+def write_autocorr_spectrum(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_autocorr_spectrum(rows))
+
+
+def read_autocorr_spectrum(path):
+    """<out>_autocorr_spectrum.tsv -> [AutocorrSpectrumRow]."""
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            x = line.rstrip("\n").split("\t")
+            if len(x) != 6:
+                raise FormatError(path, lineno, "expected 6 columns, got %d" % len(x))
+            try:
+                out.append(AutocorrSpectrumRow(x[0], *[int(v) for v in x[1:]]))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out
+
+
 # ---- screen ---------------------------------------------------------------------------------------
-ScreenRow = namedtuple("ScreenRow", "read start end chunks best_distance best_template")   # a line of <out>_screen.tsv
+ScreenRow =namedtuple("ScreenRow", "read start end chunks best_distance best_template")   # a line of <out>_screen.tsv
 
 
 def format_screen(rows):

@@ -60,6 +60,8 @@ EXPORTS = [
     "sd_lag_kernel_bench",
     "sd_heat_layout", "sd_heat_segments", "sd_heat_segments_dev", "sd_heat_final_dev", "sd_heat_final_host", "sd_heat_identities",
     "sd_heat_kernel_bench",
+    "sd_autocorr_layout", "sd_autocorr_host", "sd_autocorr_dev", "sd_autocorr_reads_dev", "sd_autocorr_positions", "sd_autocorr_peaks",
+    "sd_autocorr_seed", "sd_autocorr_info", "sd_autocorr_kernel_bench",
     "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
     "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
     "sd_screen_kernel_bench",
@@ -274,6 +276,20 @@ def load():
     L.sd_heat_kernel_bench.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
                                        C.c_int64, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float),
                                        P(C.c_int64)]
+    L.sd_autocorr_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, P(C.c_int64)]
+    L.sd_autocorr_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                   C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_autocorr_dev.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                  C.c_int32, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_autocorr_reads_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_autocorr_positions.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
+    L.sd_autocorr_peaks.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sd_autocorr_seed.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_int64, P(C.c_int64), P(C.c_int64)]
+    L.sd_autocorr_info.argtypes = [P(C.c_int64)]
+    L.sd_autocorr_info.restype = None
+    L.sd_autocorr_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                           C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_int64)]
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
@@ -1139,6 +1155,260 @@ def final_heat_host(final_rows, read_seqs, B, W=0, threads=1, max_pairs=0, which
     heat = formats.Heat(sums[:n_cells], cell_off, nb, B, W)
     heat.classes = tuple(int(x) for x in cls)
     return heat
+
+
+AUTOCORR_KMAX = 32
+AUTOCORR_DMAX = 1 << 20
+AUTOCORR_CELLS_MAX = 1 << 27
+
+
+def _autocorr_args(k, D, W, who):
+    """1 <= k <= 32, 1 <= D <= 2^20, W >= 0, refused here before any array is made or any device is touched"""
+    def is_int(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+    if not is_int(k) or not 1 <= k <= AUTOCORR_KMAX:
+        raise SdError(SD_ERR_PARAM, "%s: k = %r, must be an integer 1 .. %d" % (who, k, AUTOCORR_KMAX))
+    if not is_int(D) or not 1 <= D <= AUTOCORR_DMAX:
+        raise SdError(SD_ERR_PARAM, "%s: D = %r, must be an integer 1 .. %d" % (who, D, AUTOCORR_DMAX))
+    if not is_int(W) or not 0 <= W < (1 << 62):
+        raise SdError(SD_ERR_PARAM, "%s: window = %r, must be an integer, 0 (one window) or more" % (who, W))
+    return k, D, W
+
+
+def autocorr_info():
+    """sd_autocorr_info -> {"tile": bases of a workgroup's tile, "lags": lags of a workgroup, "launch_work": the most
+    base-lag products of one launch of the pair kernel, "launches": its launches in this process so far}"""
+    info = (C.c_int64 * 4)()
+    load().sd_autocorr_info(info)
+    return dict(zip(("tile", "lags", "launch_work", "launches"), (int(x) for x in info)))
+
+
+def autocorr_layout(read_lens, window=0):
+    """The windows of reads of the given lengths (sd_autocorr_layout) -> (win_off int64 [n + 1], win_start, win_end int64
+    [windows], windows): read r owns the windows win_off[r] .. win_off[r + 1], each [win_start, win_end) in its read."""
+    import numpy as np
+    _, _, W = _autocorr_args(1, 1, window, "autocorr_layout")
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    win_off = np.zeros(len(rl) + 1, dtype=np.int64)
+    total = C.c_int64(0)
+    rc = load().sd_autocorr_layout(rl.ctypes.data, len(rl), W, win_off.ctypes.data, C.byref(total))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_autocorr_layout: a negative read length, or 2^62 windows or more")
+    nw = np.diff(win_off)
+    w = np.arange(int(total.value), dtype=np.int64) - np.repeat(win_off[:-1], nw)
+    n = np.repeat(rl, nw)
+    start = w * W
+    end = np.minimum(n, start + W) if W > 0 else n
+    return win_off, start, end, int(total.value)
+
+
+def _autocorr_reads(reads):
+    """a list of bytes / str -> (text, offsets, lengths): the reads back to back"""
+    import numpy as np
+    rs = [_b(s) for s in reads]
+    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64).reshape(-1)
+    ro = np.zeros(len(rs), dtype=np.int64)
+    if len(rs) > 1:
+        np.cumsum(rl[:-1], out=ro[1:])
+    return b"".join(rs), ro, rl
+
+
+def autocorr_text(text, read_off, read_lens, k, D=4096, window=0, device=None, threads=1):
+    """autocorr on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any order
+    of offsets are allowed) -> formats.Autocorr"""
+    import numpy as np
+    from . import formats
+    k, D, W = _autocorr_args(k, D, window, "autocorr")
+    L = load()
+    tb = _b(text)
+    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
+        raise SdError(SD_ERR_PARAM, "autocorr: offsets and lengths differ in number, or a read lies outside the text")
+    win_off, start, end, windows = autocorr_layout(rl, W)
+    cells = windows * D if windows * D <= AUTOCORR_CELLS_MAX else 0   # (over the cap: the library refuses before it writes)
+    counts = np.zeros(max(cells, 1), dtype=np.int64)
+    err = C.create_string_buffer(1024)
+    if device is None:
+        rc = L.sd_autocorr_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, D, W, int(threads), counts.ctypes.data, err, 1024)
+    else:
+        rc = L.sd_autocorr_dev(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, D, W, int(device), int(threads),
+                               counts.ctypes.data, err, 1024)
+    _text_check(rc, err)
+    return formats.Autocorr(counts[:cells].reshape(windows, D), win_off, start, end, k)
+
+
+def autocorr(reads, k, D=4096, window=0, device=None, threads=1):
+    """The k-mer autocorrelation of every read against itself (include/sd_hip.h: sd_autocorr_*): counts[w, d - 1] = the
+    positions i of window w whose k-mer recurs at i + d, neither copy holding a byte outside ACGT, for d = 1 .. D.  reads: a
+    list of bytes / str, or a DeviceReads (then the kernels read the device text where it lies, on the reads' device).
+    window: bases per window, 0 = the whole read.  device=None: host threads (sd_autocorr_host); else the kernels of
+    csrc/sd_autocorr.hip on that device.  Both give the same integers.  -> formats.Autocorr"""
+    if isinstance(reads, DeviceReads):
+        return autocorr_device(reads, k, D, window).to_host(k, reads.read_lens, window)
+    text, ro, rl = _autocorr_reads(reads)
+    return autocorr_text(text, ro, rl, k, D, window, device, threads)
+
+
+class DeviceAutocorr(namedtuple("DeviceAutocorr", "counts win_off")):
+    """The autocorrelation counts of a DeviceReads in device memory (autocorr_device): counts = int64 [windows, D], win_off =
+    int64 [n + 1], torch tensors on the reads' device; nothing has been copied to the host."""
+    __slots__ = ()
+
+    def to_host(self, k, read_lens, window=0):
+        """-> formats.Autocorr (waits for the device); read_lens and window: those of the call, for the windows' bounds"""
+        from . import formats
+        _, start, end, _ = autocorr_layout(read_lens, window)
+        return formats.Autocorr(self.counts.cpu().numpy(), self.win_off.cpu().numpy(), start, end, k)
+
+
+def autocorr_device(reads, k, D=4096, window=0, stream=None, counts=None):
+    """autocorr on a DeviceReads, everything on the reads' device (sd_autocorr_reads_dev) -> DeviceAutocorr.  torch allocates
+    the counters on `stream` (None: the device's current stream) -- or counts = an int64 tensor of windows x D elements on
+    that device is used, whatever it holds -- and the library zeroes and fills them there; the call returns with the kernels
+    in flight and nothing is copied to the host."""
+    k, D, W = _autocorr_args(k, D, window, "autocorr_device")
+    import torch
+    L = load()
+    dev = torch.device("cuda", reads.device)
+    st = _torch_stream(torch, dev, stream)
+    win_off, _, _, windows = autocorr_layout(reads.read_lens, W)
+    if windows * D > AUTOCORR_CELLS_MAX:
+        raise SdError(SD_ERR_PARAM, "autocorr_device: %d windows x %d lags, the cap is %d cells (AUTOCORR_CELLS_MAX): use longer "
+                                    "windows, fewer lags or fewer reads per call" % (windows, D, AUTOCORR_CELLS_MAX))
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    with torch.cuda.stream(st):
+        if counts is None:
+            counts = torch.empty((windows, D), dtype=torch.int64, device=dev)
+        elif counts.dtype != torch.int64 or counts.numel() != windows * D or counts.device != dev or not counts.is_contiguous():
+            raise SdError(SD_ERR_PARAM, "autocorr_device: counts must be a contiguous int64 tensor of %d x %d elements on %s" % (windows, D, dev))
+        d_off = torch.from_numpy(win_off).to(dev, non_blocking=True)
+    err = C.create_string_buffer(1024)
+    _text_check(L.sd_autocorr_reads_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, k, D, W, dev.index or 0,
+                                        C.c_void_p(st.cuda_stream), C.c_void_p(counts.data_ptr() if counts.numel() else 0), err, 1024), err)
+    return DeviceAutocorr(counts.view(windows, D), d_off)
+
+
+def autocorr_positions(read_lens, k, D, window=0):
+    """positions[w, d - 1] = the i of window w with i <= n - d - k: what counts[w, d - 1] is out of (sd_autocorr_positions)"""
+    import numpy as np
+    k, D, W = _autocorr_args(k, D, window, "autocorr_positions")
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    windows = autocorr_layout(rl, W)[3]
+    if windows * D > AUTOCORR_CELLS_MAX:
+        raise SdError(SD_ERR_PARAM, "autocorr_positions: %d windows x %d lags, the cap is %d cells" % (windows, D, AUTOCORR_CELLS_MAX))
+    out = np.zeros((windows, D), dtype=np.int64)
+    rc = load().sd_autocorr_positions(rl.ctypes.data, len(rl), k, D, W, out.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_autocorr_positions")
+    return out
+
+
+def autocorr_peaks(counts, lo=1, radius=8, peaks=8):
+    """The peaks of every spectrum (row) of counts [windows, D] by the integer rule of csrc/sd_autocorr.hpp
+    (sd_autocorr_peaks): lag d >= lo is a peak when its count is positive, no count within `radius` lags (and >= lo) is
+    larger, and none of those at a smaller lag is equal.  -> (lag, count) int64 [windows, peaks], by count descending then
+    lag ascending, 0-filled; lag[:, 0] is the period, 0 where a spectrum has no peak."""
+    import numpy as np
+    c = np.ascontiguousarray(counts, dtype=np.int64)
+    if c.ndim == 1:
+        c = c.reshape(1, -1)
+    for name, v, low in (("lo", lo, 1), ("radius", radius, 0), ("peaks", peaks, 0)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < low or v >= (1 << 31):
+            raise SdError(SD_ERR_PARAM, "autocorr_peaks: %s = %r, must be an integer, %d or more" % (name, v, low))
+    if c.ndim != 2 or not 1 <= c.shape[1] <= AUTOCORR_DMAX:
+        raise SdError(SD_ERR_PARAM, "autocorr_peaks: counts must be [windows, D] with 1 <= D <= %d" % AUTOCORR_DMAX)
+    lag = np.zeros((c.shape[0], peaks), dtype=np.int64)
+    cnt = np.zeros((c.shape[0], peaks), dtype=np.int64)
+    rc = load().sd_autocorr_peaks(c.ctypes.data, c.shape[0], c.shape[1], lo, radius, peaks, lag.ctypes.data, cnt.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_autocorr_peaks")
+    return lag, cnt
+
+
+def autocorr_seed(seq, k, p):
+    """(s, run): the longest run of consecutive hits at lag p in seq starts at s and has run positions, the first of equal
+    runs; (-1, 0) when there is no hit (sd_autocorr_seed)"""
+    k, _, _ = _autocorr_args(k, 1, 0, "autocorr_seed")
+    if not isinstance(p, int) or p < 1:
+        raise SdError(SD_ERR_PARAM, "autocorr_seed: p = %r, must be an integer, 1 or more" % (p,))
+    sb = _b(seq)
+    s, run = C.c_int64(0), C.c_int64(0)
+    rc = load().sd_autocorr_seed(sb or b"N", len(sb), k, p, C.byref(s), C.byref(run))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_autocorr_seed")
+    return int(s.value), int(run.value)
+
+
+def autocorr_seeds(reads, names, ac, lo=1, min_count=1, radius=8):
+    """Seed monomers from the whole-read spectra of a formats.Autocorr: for every read whose spectrum has a period p (the
+    first peak at a lag >= lo) with at least min_count hits, the p bases from the start s of the longest run of consecutive
+    hits at lag p; a seed with a byte outside ACGT is dropped.  -> [(name, sequence)] with name =
+    "{read}/{s}_{s + p} period={p} count={hits}", ready for a FASTA file that `--profile` then polishes."""
+    out = []
+    for r, (seq, name) in enumerate(zip(reads, names)):
+        spec = ac.spectrum(r)
+        lag, cnt = autocorr_peaks(spec, lo, radius, 1)
+        p, c = int(lag[0, 0]), int(cnt[0, 0])
+        if p <= 0 or c < min_count:
+            continue
+        sb = _b(seq)
+        s, run = autocorr_seed(sb, ac.k, p)
+        seed = sb[s:s + p] if s >= 0 else b""
+        if len(seed) != p or seed.strip(b"ACGT"):
+            continue
+        out.append(("%s/%d_%d period=%d count=%d" % (name, s, s + p, p, c), seed.decode()))
+    return out
+
+
+def autocorr_rows(ac, names, read_lens, lo=1, radius=8, peaks=8):
+    """The lines of <out>_autocorr.tsv for a formats.Autocorr -> [formats.AutocorrRow], one per (read, window)"""
+    from . import formats
+    lag, cnt = autocorr_peaks(ac.counts, lo, radius, max(peaks, 1))
+    out = []
+    for r, name in enumerate(names):
+        n = int(read_lens[r])
+        for w in ac.windows(r):
+            ws, we = int(ac.win_start[w]), int(ac.win_end[w])
+            p, c = int(lag[w, 0]), int(cnt[w, 0])
+            pos = max(0, min(we, n - p - ac.k + 1) - ws) if p > 0 else 0
+            pk = tuple((int(a), int(b)) for a, b in zip(lag[w, :peaks], cnt[w, :peaks]) if a > 0)
+            out.append(formats.AutocorrRow(name, ws, we, ac.k, p, c, pos, pk))
+    return out
+
+
+def autocorr_spectrum_rows(ac, names, read_lens):
+    """The lines of <out>_autocorr_spectrum.tsv -> [formats.AutocorrSpectrumRow]: every lag of every window with a count"""
+    import numpy as np
+    from . import formats
+    out = []
+    for r, name in enumerate(names):
+        n = int(read_lens[r])
+        for w in ac.windows(r):
+            ws, we = int(ac.win_start[w]), int(ac.win_end[w])
+            row = ac.counts[w]
+            for d0 in np.nonzero(row)[0].tolist():
+                d = d0 + 1
+                out.append(formats.AutocorrSpectrumRow(name, ws, we, d, int(row[d0]), max(0, min(we, n - d - ac.k + 1) - ws)))
+    return out
+
+
+def autocorr_kernel_bench(reads, k, D=4096, window=0, device=0, warmup=2, reps=5):
+    """sd_autocorr_kernel_bench -> {"prep_ms", "pairs_ms": [...], "launches", "workgroups", "cells", "words"}."""
+    k, D, W = _autocorr_args(k, D, window, "autocorr_kernel_bench")
+    text, ro, rl = _autocorr_reads(reads)
+    a, b = ((C.c_float * reps)() for _ in range(2))
+    info = (C.c_int64 * 4)()
+    rc = load().sd_autocorr_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, D, W, int(device), int(warmup),
+                                         int(reps), a, b, info)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_autocorr_kernel_bench")
+    out = {"prep_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b]}
+    out.update(zip(("launches", "workgroups", "cells", "words"), [int(x) for x in info]))
+    return out
 
 
 def decompose_files_records(reads_fa, monomers_fa, records_out, **kw):

@@ -38,6 +38,7 @@ class _LazyNumpy:
 
 np = _LazyNumpy()
 
+from . import autocorr
 from . import lib
 from . import shard
 
@@ -731,6 +732,7 @@ def main(argv=None):
     parser.add_argument("--heatmap-max-pairs", dest="heatmap_max_pairs", type=int, default=4000000000, metavar="N",
                         help="refuse a read whose heatmap needs more than N pairs (by default 4000000000, about 8 s of device "
                              "time on 171-bp blocks; 0: no limit)")
+    autocorr.add_arguments(parser)
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
@@ -750,6 +752,8 @@ def main(argv=None):
         _check_lags(args)
     if args.heatmap is not None:
         _check_heatmap(args)
+    if args.autocorr is not None:
+        autocorr.check(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -853,6 +857,15 @@ def main(argv=None):
             logger.info("--heatmap failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the binned all-against-all identities to " + heat_fn)
+
+    if args.autocorr is not None:
+        try:
+            saved = autocorr.write(args, args.out_dir, args.out_file, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--autocorr failed: " + e.msg + "\n")
+            logger.info("--autocorr failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the k-mer autocorrelation of the reads to " + ", ".join(saved))
 
     logger.info("Thank you for using StringDecomposer!")
 
