@@ -1129,6 +1129,48 @@ int sd_autocorr_kernel_bench(const char* text, const int64_t* read_off, const in
                              int64_t D, int64_t W, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_pairs,
                              int64_t info[4]);
 
+/* ---- subfamilies of a monomer's instances (--split; csrc/sd_split.hpp holds the rule) ---------------------------------
+ * The member rows of one forward monomer of L bases -- rows of --msa with status 1, bytes [0, L): 0..4 = A C G T N,
+ * SD_MSA_DEL; insertion slots take no part -- are clustered by column distance H.  centres = [per-column mode of all
+ * members] (ties: the smallest code); then rounds while fewer than K centres and fewer than 4 K rounds: the candidate row
+ * farthest from its centre (ties: the smallest row) is tried as a new centre when its distance is at least the radius R:
+ * assign (ties: the smallest centre), then at most I times (mode per cluster -- an empty one keeps its centre --, assign)
+ * until nothing changes; a new cluster of fewer than S rows discards the trial and retires the row as a candidate.
+ * Results: centres (k rows of L symbol bytes, K x L allocated), per row assign, d1 (its distance) and d2 (the smallest
+ * distance to another centre, -1 with one centre), sizes (K), info = {k, rounds, Lloyd iterations, 1 when kernels ran}.
+ * n = 0 gives k = 0.  Refused with SD_ERR_PARAM and the numbers in errbuf: R, S, I < 1, K outside 1 .. SD_SPLIT_KMAX,
+ * more than SD_SPLIT_NMAX member rows of one monomer.
+ *
+ * sd_split_host: host threads, any L >= 1; sym is n rows of `pitch` >= L bytes.
+ * sd_split_dev: the same call on a device (csrc/sd_split.hip): rows become three bit planes; a lane per row measures
+ * popcount((a0 ^ b0) | (a1 ^ b1) | (a2 ^ b2)) against the centres in LDS; the modes come from ballots over rows grouped
+ * by cluster.  Per pass 16 bytes reach the host.  L > SD_SPLIT_LMAX is computed by the host form, with the same results. */
+#define SD_SPLIT_KMAX 64
+#define SD_SPLIT_LMAX 512
+#define SD_SPLIT_NMAX ((int64_t)1 << 26)
+int sd_split_host(const uint8_t* sym, int64_t n, int64_t pitch, int32_t L, int32_t R, int32_t K, int32_t S, int32_t I, int32_t threads,
+                  uint8_t* centres, int32_t* assign, int32_t* d1, int32_t* d2, int32_t* sizes, int64_t info[4], char* errbuf, size_t errlen);
+int sd_split_dev(const uint8_t* sym, int64_t n, int64_t pitch, int32_t L, int32_t R, int32_t K, int32_t S, int32_t I, int32_t device,
+                 int32_t threads, uint8_t* centres, int32_t* assign, int32_t* d1, int32_t* d2, int32_t* sizes, int64_t info[4], char* errbuf,
+                 size_t errlen);
+/* All monomers of a job in one call, host only, on the buffers of --msa (rows, row_at [n_rows], status) and fmono (int32
+ * [n_rows]: the forward monomer a row is an instance of, -1 for none).  Members of monomer m: status 1 and fmono = m;
+ * mono_len[m] its length, radius[m] its R.  Per row: sub (the subfamily, -1 for a non-member), d1, d2 (-1 for a
+ * non-member).  centres: the centres of monomer 0, 1, ... back to back, k_m x mono_len[m] bytes from cen_off[m]
+ * (cen_off: n_mono + 1; centres_cap: the bytes allocated -- K x the sum of the lengths always suffices).  sizes:
+ * n_mono x K, info: n_mono x 4 = {member rows, k, rounds, iterations}. */
+int sd_split_final_host(const uint8_t* rows, const int64_t* row_at, const uint8_t* status, const int32_t* fmono, int64_t n_rows,
+                        const int32_t* mono_len, const int32_t* radius, int32_t n_mono, int32_t K, int32_t S, int32_t I, int32_t threads,
+                        int32_t* sub, int32_t* d1, int32_t* d2, uint8_t* centres, int64_t centres_cap, int64_t* cen_off, int32_t* sizes,
+                        int64_t* info, char* errbuf, size_t errlen);
+/* info = {SD_SPLIT_KMAX, SD_SPLIT_LMAX, SD_SPLIT_NMAX, launches of the assign kernel in this process so far}. */
+void sd_split_info(int64_t info[4]);
+/* Developer entry (tools/split_bench.py): the arguments of sd_split_dev; the whole split once, then warmup + reps times
+ * each, between two HIP events, on its final centres: ms_prep = the plane kernel, ms_assign = one assign pass, ms_modes =
+ * one pass of the modes (scan, group, count, centres).  info = k, rounds, iterations, assign launches. */
+int sd_split_kernel_bench(const uint8_t* sym, int64_t n, int64_t pitch, int32_t L, int32_t R, int32_t K, int32_t S, int32_t I,
+                          int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_assign, float* ms_modes, int64_t info[4]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

@@ -39,6 +39,12 @@ Two more text files are this package's own (opt-in, `--profile`):
                       <out>_autocorr_spectrum.tsv (`--autocorr-spectrum`): read, start, end, lag, count, positions for
                       every lag of every window with a count.  read_autocorr / read_autocorr_spectrum below.
 
+  <out>_split.tsv     (`--split P[,K]`) one line per row of <out>.tsv, no header: read, start, end, monomer, subfamily
+                      ("<name>.<j>", '*' for a row that is no instance), d1, d2 (columns in which the row differs from its
+                      subfamily's centre and from the nearest other one), columns (as in <out>_msa.tsv).
+                      <out>_split_summary.tsv: monomer, subfamily, size, sum of d1, largest d1, nearest subfamily, distance.
+                      read_split / read_split_summary below; <out>_split_monomers.fa is a monomer file.
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -812,6 +818,162 @@ def read_autocorr_spectrum(path):
             except ValueError as e:
                 raise FormatError(path, lineno, str(e))
     return out
+
+
+# ---- subfamilies (--split) -------------------------------------------------------------------------
+# --split P[,K]: <out>_split.tsv, one line per row of <out>.tsv in its order, no header -- read, start, end, monomer (as
+# printed there), subfamily ("<name>.<j>" on the forward monomer's name, '*' for a row that is no instance), d1 (columns
+# in which the row differs from its subfamily's centre), d2 (from the nearest other centre; -1: none, or no instance),
+# columns (as in <out>_msa.tsv).  <out>_split_summary.tsv, one line per subfamily, integers -- monomer, subfamily, size,
+# sum of d1, largest d1, nearest (the other subfamily of the monomer whose centre is closest, '*' when alone), distance
+# (the columns in which the two centres differ, -1 when alone).  <out>_split_monomers.fa: a monomer file.
+Split = namedtuple("Split", "centres assign d1 d2 sizes rounds iters")
+"""lib.split_rows / split_msa: centres = uint8 [k, L] (0..4 = A C G T N, 5 = deleted), assign / d1 / d2 = int32 [n] per
+member row in the given order (d2 -1: one centre), sizes = int32 [k], rounds and iters = the rounds and Lloyd iterations
+that ran (csrc/sd_split.hpp)."""
+SplitRow = namedtuple("SplitRow", "read start end monomer subfamily d1 d2 columns")            # a line of <out>_split.tsv
+SplitSummaryRow = namedtuple("SplitSummaryRow", "monomer subfamily size sum_d1 max_d1 nearest distance")   # ... of <out>_split_summary.tsv
+
+
+def split_members(msa, pair_tmpl, m):
+    """The pairs that are members of forward monomer m, in order: status 1 and either strand of m."""
+    return [i for i, il in enumerate(pair_tmpl) if int(il) >> 1 == m and int(msa.status[i]) == 1]
+
+
+def split_rows(msa, pair_tmpl, mono_names, splits, meta):
+    """The lines of <out>_split.tsv: splits = one Split per forward monomer over split_members, meta = (read, start, end,
+    monomer) per pair."""
+    sub, d1, d2 = {}, {}, {}
+    for m, sp in enumerate(splits):
+        for x, i in enumerate(split_members(msa, pair_tmpl, m)):
+            sub[i], d1[i], d2[i] = "%s.%d" % (mono_names[m], int(sp.assign[x])), int(sp.d1[x]), int(sp.d2[x])
+    out = []
+    for i, (il, (read, start, end, monomer)) in enumerate(zip(pair_tmpl, meta)):
+        col = msa_row(msa, i, il)[0]
+        if i in sub:
+            out.append(SplitRow(read, int(start), int(end), monomer, sub[i], d1[i], d2[i], "".join(_MSA_CHARS[v] for v in col.tolist())))
+        else:
+            out.append(SplitRow(read, int(start), int(end), monomer, "*", -1, -1, "." * len(col)))
+    return out
+
+
+def format_split(rows):
+    return "".join("%s\t%d\t%d\t%s\t%s\t%d\t%d\t%s\n" % tuple(r) for r in rows)
+
+
+def write_split(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_split(rows))
+
+
+def read_split(path):
+    """<out>_split.tsv -> [SplitRow]."""
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            x = line.rstrip("\n").split("\t")
+            if len(x) != 8:
+                raise FormatError(path, lineno, "expected 8 columns, got %d" % len(x))
+            try:
+                if x[7].strip("ACGTN-") and x[7] != "." * len(x[7]):
+                    raise ValueError("columns must be over ACGTN- or all '.', found %r" % x[7])
+                out.append(SplitRow(x[0], int(x[1]), int(x[2]), x[3], x[4], int(x[5]), int(x[6]), x[7]))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out
+
+
+def split_summary(mono_names, splits):
+    """The lines of <out>_split_summary.tsv -> [SplitSummaryRow]; the nearest other centre, ties to the smallest index."""
+    out = []
+    for name, sp in zip(mono_names, splits):
+        k = len(sp.centres)
+        for j in range(k):
+            mine = [int(v) for v, a in zip(sp.d1, sp.assign) if int(a) == j]
+            best, at = -1, -1
+            for o in range(k):
+                if o != j:
+                    h = int((sp.centres[j] != sp.centres[o]).sum())
+                    if at < 0 or h < best:
+                        best, at = h, o
+            out.append(SplitSummaryRow(name, "%s.%d" % (name, j), len(mine), sum(mine), max(mine) if mine else 0,
+                                       "%s.%d" % (name, at) if at >= 0 else "*", best))
+    return out
+
+
+def format_split_summary(rows):
+    return "".join("%s\t%s\t%d\t%d\t%d\t%s\t%d\n" % tuple(r) for r in rows)
+
+
+def write_split_summary(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_split_summary(rows))
+
+
+def read_split_summary(path):
+    """<out>_split_summary.tsv -> [SplitSummaryRow]."""
+    out = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            x = line.rstrip("\n").split("\t")
+            if len(x) != 7:
+                raise FormatError(path, lineno, "expected 7 columns, got %d" % len(x))
+            try:
+                out.append(SplitSummaryRow(x[0], x[1], int(x[2]), int(x[3]), int(x[4]), x[5], int(x[6])))
+            except ValueError as e:
+                raise FormatError(path, lineno, str(e))
+    return out
+
+
+_COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+
+def msa_inserted(msa, i, il, segment):
+    """The bases a pair inserts, by slot, read back from its row and its stretch of the read (`segment`, as it stands in
+    the read): {slot: bases} on the forward monomer.  None when the row does not say -- a saturated count (255), or a row
+    that does not add up to the stretch."""
+    col, ins = msa_row(msa, i, il)
+    seg = segment if isinstance(segment, str) else segment.decode()
+    if int(il) & 1:
+        seg = "".join(_COMP.get(c, c) for c in reversed(seg))
+    cols, counts = col.tolist(), ins.tolist()
+    if max(counts) >= 255 or sum(counts) + sum(1 for v in cols if v != MSA_DEL) != len(seg):
+        return None
+    out, at = {}, 0
+    for g in range(len(counts)):
+        if counts[g]:
+            out[g] = seg[at:at + counts[g]]
+            at += counts[g]
+        if g < len(cols) and cols[g] != MSA_DEL:
+            at += 1
+    return out
+
+
+def split_profile(msa, pair_tmpl, m, name, seq, split, inserted=None):
+    """The column profile of every subfamily of monomer m (Profile of "<name>.<j>", all with the monomer's sequence): per
+    subfamily the msa_counts of its rows, columns 0..6 those of --profile; the inserted bases (columns 7..11) come from
+    `inserted` = {pair: msa_inserted(...)}, for the pairs that insert."""
+    import numpy as np
+    L = int(msa.tlen[m])
+    k = len(split.centres)
+    counts = [np.zeros((L + 1, PROFILE_NCOLS), dtype=np.int64) for _ in range(k)]
+    for x, i in enumerate(split_members(msa, pair_tmpl, m)):
+        c = counts[int(split.assign[x])]
+        col, ins = msa_row(msa, i, pair_tmpl[i])
+        np.add.at(c, (np.arange(L), col.astype(np.int64)), 1)
+        c[:, 6] += ins > 0
+        for g, bases in ((inserted or {}).get(i) or {}).items():
+            for ch in bases:
+                c[g, 7 + "ACGTN".index(ch if ch in "ACGT" else "N")] += 1
+    return Profile(["%s.%d" % (name, j) for j in range(k)], [seq] * k, counts)
+
+
+def split_consensus(msa, pair_tmpl, m, name, seq, split, inserted=None):
+    """[(subfamily name, rows, sequence)] of monomer m: the rule of consensus() on split_profile, so insertions are
+    honoured as --profile honours them.  A monomer without instances: [("<name>.0", 0, seq)]."""
+    if len(split.centres) == 0:
+        return [("%s.0" % name, 0, seq)]
+    return consensus(split_profile(msa, pair_tmpl, m, name, seq, split, inserted))
 
 
 # ---- screen ---------------------------------------------------------------------------------------

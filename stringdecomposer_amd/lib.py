@@ -62,6 +62,7 @@ EXPORTS = [
     "sd_heat_kernel_bench",
     "sd_autocorr_layout", "sd_autocorr_host", "sd_autocorr_dev", "sd_autocorr_reads_dev", "sd_autocorr_positions", "sd_autocorr_peaks",
     "sd_autocorr_seed", "sd_autocorr_info", "sd_autocorr_kernel_bench",
+    "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
     "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
     "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
     "sd_screen_kernel_bench",
@@ -290,6 +291,17 @@ def load():
     L.sd_autocorr_info.restype = None
     L.sd_autocorr_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_int64)]
+    L.sd_split_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_split_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_split_final_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_split_info.argtypes = [P(C.c_int64)]
+    L.sd_split_info.restype = None
+    L.sd_split_kernel_bench.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64)]
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
@@ -1408,6 +1420,161 @@ def autocorr_kernel_bench(reads, k, D=4096, window=0, device=0, warmup=2, reps=5
         raise SdError(rc, "sd_autocorr_kernel_bench")
     out = {"prep_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b]}
     out.update(zip(("launches", "workgroups", "cells", "words"), [int(x) for x in info]))
+    return out
+
+
+SPLIT_KMAX = 64
+SPLIT_LMAX = 512
+SPLIT_NMAX = 1 << 26
+
+
+def _split_args(R, K, min_size, max_iter, who):
+    """R, min_size, max_iter >= 1 and 1 <= K <= 64, refused here before any array is made or any device is touched"""
+    def is_int(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+    for name, v in (("R", R), ("min_size", min_size), ("max_iter", max_iter)):
+        if not is_int(v) or not 1 <= v < (1 << 31):
+            raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer, 1 or more" % (who, name, v))
+    if not is_int(K) or not 1 <= K <= SPLIT_KMAX:
+        raise SdError(SD_ERR_PARAM, "%s: K = %r, must be an integer 1 .. %d" % (who, K, SPLIT_KMAX))
+    return R, K, min_size, max_iter
+
+
+def split_radius(P, L):
+    """--split P: the radius of a monomer of L bases, max(1, ceil(P L / 100)) (csrc/sd_split.hpp: split_radius)"""
+    return max(1, (int(P) * int(L) + 99) // 100)
+
+
+def split_info():
+    """sd_split_info -> {"kmax", "lmax": the longest monomer of the kernels, "nmax": the most member rows of a monomer,
+    "launches": launches of the assign kernel in this process so far}"""
+    info = (C.c_int64 * 4)()
+    load().sd_split_info(info)
+    return dict(zip(("kmax", "lmax", "nmax", "launches"), (int(x) for x in info)))
+
+
+def split_rows(sym, R, K=64, min_size=8, max_iter=16, device=None, threads=1):
+    """The subfamilies of the rows of a symbol matrix (csrc/sd_split.hpp; include/sd_hip.h: sd_split_*): sym = uint8 [n, L],
+    0..4 = A C G T N, 5 = deleted; R the radius in columns, K the most subfamilies, min_size the fewest rows of a new one,
+    max_iter the Lloyd iterations per round.  device=None: host threads (sd_split_host); else the kernels of
+    csrc/sd_split.hip on that device (L > 512: the host form inside the call).  Both give the same integers.
+    -> formats.Split"""
+    import numpy as np
+    from . import formats
+    who = "split_rows"
+    R, K, S, I = _split_args(R, K, min_size, max_iter, who)
+    a = np.ascontiguousarray(sym, dtype=np.uint8)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise SdError(SD_ERR_PARAM, "%s: sym must be [n, L] with L >= 1" % who)
+    n, L = int(a.shape[0]), int(a.shape[1])
+    if n > SPLIT_NMAX:
+        raise SdError(SD_ERR_PARAM, "%s: %d member rows, the cap is %d (SPLIT_NMAX)" % (who, n, SPLIT_NMAX))
+    if n and int(a.max()) > 5:
+        raise SdError(SD_ERR_PARAM, "%s: a symbol above 5 (0..4 = A C G T N, 5 = deleted)" % who)
+    cen = np.zeros((K, L), dtype=np.uint8)
+    asg, d1, d2 = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+    sizes = np.zeros(K, dtype=np.int32)
+    info = (C.c_int64 * 4)()
+    err = C.create_string_buffer(1024)
+    L_ = load()
+    base = a.ctypes.data if n else cen.ctypes.data
+    if device is None:
+        rc = L_.sd_split_host(base, n, L, L, R, K, S, I, int(threads), cen.ctypes.data, asg.ctypes.data, d1.ctypes.data, d2.ctypes.data,
+                              sizes.ctypes.data, info, err, 1024)
+    else:
+        rc = L_.sd_split_dev(base, n, L, L, R, K, S, I, int(device), int(threads), cen.ctypes.data, asg.ctypes.data, d1.ctypes.data,
+                             d2.ctypes.data, sizes.ctypes.data, info, err, 1024)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace") or "sd_split" + ("_host" if device is None else "_dev"))
+    k = int(info[0])
+    return formats.Split(cen[:k].copy(), asg[:n], d1[:n], d2[:n], sizes[:k].copy(), int(info[1]), int(info[2]))
+
+
+def split_msa(msa, pair_tmpl, mono_lens, P, K=64, min_size=8, max_iter=16, device=None, threads=1):
+    """The subfamilies of every forward monomer's instances in a host formats.Msa: per monomer m the rows of
+    formats.split_members (status 1, either strand), radius split_radius(P, mono_lens[m]) -> [formats.Split], one per
+    monomer (k = 0 for a monomer without instances)."""
+    import numpy as np
+    from . import formats
+    if not isinstance(P, int) or isinstance(P, bool) or not 1 <= P <= 100:
+        raise SdError(SD_ERR_PARAM, "split_msa: P = %r, must be an integer 1 .. 100 (a percentage of the monomer's length)" % (P,))
+    _split_args(1, K, min_size, max_iter, "split_msa")
+    groups = [[] for _ in mono_lens]
+    for i, il in enumerate(pair_tmpl):
+        if int(msa.status[i]) == 1:
+            groups[int(il) >> 1].append(i)
+    out = []
+    for m, L in enumerate(mono_lens):
+        L = int(L)
+        sym = np.zeros((len(groups[m]), max(L, 1)), dtype=np.uint8)
+        for x, i in enumerate(groups[m]):
+            at = int(msa.row_at[i])
+            sym[x, :L] = msa.rows[at:at + L]
+        out.append(split_rows(sym, split_radius(P, L), K, min_size, max_iter, device=device, threads=threads))
+    return out
+
+
+class JobSplit(namedtuple("JobSplit", "sub d1 d2 centres cen_off sizes info")):
+    """The subfamilies of all monomers of a job (final_split_host): sub / d1 / d2 = int32 [n_rows] (-1 for a row that is no
+    member), centres = flat uint8, monomer m's k_m x L_m symbol bytes at centres[cen_off[m]:cen_off[m + 1]]; cen_off = int64
+    [n_mono + 1], sizes = int32 [n_mono, K], info = int64 [n_mono, 4] = (member rows, k, rounds, Lloyd iterations)."""
+    __slots__ = ()
+
+
+def _split_job_args(mono_lens, P, K, min_size, max_iter, who):
+    import numpy as np
+    if not isinstance(P, int) or isinstance(P, bool) or not 1 <= P <= 100:
+        raise SdError(SD_ERR_PARAM, "%s: P = %r, must be an integer 1 .. 100 (a percentage of the monomer's length)" % (who, P))
+    _, K, S, I = _split_args(1, K, min_size, max_iter, who)
+    ml = np.ascontiguousarray(mono_lens, dtype=np.int32)
+    if len(ml) and int(ml.min()) < 1:
+        raise SdError(SD_ERR_PARAM, "%s: an empty monomer" % who)
+    rad = np.ascontiguousarray([split_radius(P, x) for x in ml.tolist()], dtype=np.int32)
+    return ml, rad, K, S, I
+
+
+def final_split_host(msa, pair_tmpl, mono_lens, P, K=64, min_size=8, max_iter=16, threads=1):
+    """All monomers of a job in one call, on host threads (sd_split_final_host): msa = a formats.Msa (final_msa_host, or
+    DeviceMsa.to_host()), pair_tmpl = its interleaved templates -> JobSplit (numpy arrays)."""
+    import numpy as np
+    who = "final_split_host"
+    ml, rad, K, S, I = _split_job_args(mono_lens, P, K, min_size, max_iter, who)
+    n, M = len(pair_tmpl), len(ml)
+    fmono = np.ascontiguousarray(np.asarray(pair_tmpl, dtype=np.int32).reshape(-1) >> 1)
+    rows = np.ascontiguousarray(msa.rows, dtype=np.uint8)
+    row_at = np.ascontiguousarray(msa.row_at, dtype=np.int64)
+    status = np.ascontiguousarray(msa.status, dtype=np.uint8)
+    cap = int(K) * int(ml.sum()) if M else 0
+    sub, d1, d2 = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+    centres = np.zeros(max(cap, 1), dtype=np.uint8)
+    cen_off = np.zeros(M + 1, dtype=np.int64)
+    sizes = np.zeros((M, K), dtype=np.int32)
+    info = np.zeros((M, 4), dtype=np.int64)
+    err = C.create_string_buffer(1024)
+    rc = load().sd_split_final_host(rows.ctypes.data, row_at.ctypes.data, status.ctypes.data, fmono.ctypes.data, n, ml.ctypes.data,
+                                    rad.ctypes.data, M, K, S, I, int(threads), sub.ctypes.data, d1.ctypes.data, d2.ctypes.data,
+                                    centres.ctypes.data, cap, cen_off.ctypes.data, sizes.ctypes.data, info.ctypes.data, err, 1024)
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace") or "sd_split_final_host")
+    return JobSplit(sub[:n], d1[:n], d2[:n], centres[:int(cen_off[-1])], cen_off, sizes, info)
+
+
+def split_kernel_bench(sym, R, K=64, min_size=8, max_iter=16, device=0, warmup=2, reps=5):
+    """sd_split_kernel_bench -> {"prep_ms", "assign_ms", "modes_ms": [...], "k", "rounds", "iters", "launches"}: the whole
+    split once, then each stage timed on its final centres."""
+    import numpy as np
+    R, K, S, I = _split_args(R, K, min_size, max_iter, "split_kernel_bench")
+    a = np.ascontiguousarray(sym, dtype=np.uint8)
+    if a.ndim != 2 or a.shape[0] < 1 or not 1 <= a.shape[1] <= SPLIT_LMAX:
+        raise SdError(SD_ERR_PARAM, "split_kernel_bench: sym must be [n, L] with n >= 1 and 1 <= L <= %d" % SPLIT_LMAX)
+    x, y, z = ((C.c_float * reps)() for _ in range(3))
+    info = (C.c_int64 * 4)()
+    rc = load().sd_split_kernel_bench(a.ctypes.data, a.shape[0], a.shape[1], a.shape[1], R, K, S, I, int(device), int(warmup), int(reps),
+                                      x, y, z, info)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_split_kernel_bench")
+    out = {"prep_ms": [float(v) for v in x], "assign_ms": [float(v) for v in y], "modes_ms": [float(v) for v in z]}
+    out.update(zip(("k", "rounds", "iters", "launches"), [int(v) for v in info]))
     return out
 
 

@@ -39,6 +39,7 @@ class _LazyNumpy:
 np = _LazyNumpy()
 
 from . import autocorr
+from . import split
 from . import lib
 from . import shard
 
@@ -733,6 +734,7 @@ def main(argv=None):
                         help="refuse a read whose heatmap needs more than N pairs (by default 4000000000, about 8 s of device "
                              "time on 171-bp blocks; 0: no limit)")
     autocorr.add_arguments(parser)
+    split.add_arguments(parser)
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
@@ -754,6 +756,8 @@ def main(argv=None):
         _check_heatmap(args)
     if args.autocorr is not None:
         autocorr.check(args)
+    if args.split is not None:
+        split.check(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -866,6 +870,15 @@ def main(argv=None):
             logger.info("--autocorr failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the k-mer autocorrelation of the reads to " + ", ".join(saved))
+
+    if args.split is not None:
+        try:
+            saved = split.write(args, convert_tsv_fn, args.out_dir, args.out_file, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--split failed: " + e.msg + "\n")
+            logger.info("--split failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the subfamilies of the monomers' instances to " + ", ".join(saved))
 
     logger.info("Thank you for using StringDecomposer!")
 
