@@ -1129,6 +1129,68 @@ int sd_autocorr_kernel_bench(const char* text, const int64_t* read_off, const in
                              int64_t D, int64_t W, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_pairs,
                              int64_t info[4]);
 
+/* ---- windowed k-mer identity of every read against itself (--dotplot): no monomer file, both strands -------------------
+ * A read is a text T[0 .. n).  The k-mer at i (1 <= k <= SD_DOTPLOT_KMAX) exists when i + k <= n and T[i .. i + k) are all
+ * A C G T (the byte rule of sd_autocorr_*).  Its forward code f is the 2k-bit number with A C G T = 0 1 2 3, first base most
+ * significant; its reverse code r is the code of its reverse complement.  Window w of a read covers the positions
+ * [w W, min(n, (w + 1) W)), nw = ceil(n / W) (a read of 0 bases has none), 1 <= W <= SD_DOTPLOT_WMAX; a k-mer belongs to the
+ * window its start lies in.  h is the splitmix64 finaliser (csrc/sd_dotplot.hpp: dotplot_hash); with the modulus M,
+ * 1 <= M <= SD_DOTPLOT_MMAX, a code x is selected when h(x) % M == 0 -- always the value that is compared: S_w is the set of
+ * distinct selected forward codes of window w, R_w the set of distinct selected reverse codes (selected by h(r)).
+ * For windows j <= i of a read, with i - j <= B when a band 0 < B <= SD_DOTPLOT_BMAX is given (B = 0: all), the cell (i, j)
+ * holds shared = |S_i & S_j| and, with rc != 0, shared_rc = |S_i & R_j|, the diagonal included.  Read r owns the windows
+ * win_off[r] .. win_off[r + 1] and the cells cell_off[r] .. cell_off[r + 1] of the call, its cells ordered by i, then j.
+ * Results, all int32: kmers[windows] = |S_w|, kmers_rc[windows] = |R_w|, shared[cells], shared_rc[cells]; with rc == 0
+ * kmers_rc and shared_rc are not touched and may be NULL.  Every number is an exact integer; host and device forms return the
+ * same bytes.  Reads are text + read_off[r], read_lens[r] bytes each, as sd_autocorr_* takes them.
+ * Refused with SD_ERR_PARAM and the numbers in errbuf: k, W, M or B out of range and more than SD_DOTPLOT_CELLS_MAX cells in
+ * the call, before any device work; a window with more than SD_DOTPLOT_SET_MAX selected positions on a strand, counted
+ * before duplicates are removed -- the refusal names the read, the window, the count and the cap and advises a larger M; the
+ * counting pass is the only device work before it (W <= 4096 with M = 1 cannot hit it).
+ *
+ * sd_dotplot_layout: host only: win_off, cell_off [0 .. n_reads] (each may be NULL) and the totals.
+ * sd_dotplot_host: host threads: sets by sort and unique, cells by merge.
+ * sd_dotplot_dev: the kernels of csrc/sd_dotplot.hip -- a counting pass per tile of 1 024 positions, one scan for the sets'
+ * offsets, a gather, a sort of 64-bit keys in LDS per (window, strand), and the pair kernel: a workgroup holds S_i sorted in
+ * LDS and looks the elements of S_j (and R_j) up in it, a ballot and a population count per 64 of them, one store per cell.
+ * No kernel uses an atomic.  The reads are uploaded, the arrays come back.  No launch of the pair kernel exceeds a fixed
+ * amount of work (sd_dotplot_info). */
+#define SD_DOTPLOT_KMAX 32
+#define SD_DOTPLOT_WMAX (1 << 30)
+#define SD_DOTPLOT_MMAX (1 << 20)
+#define SD_DOTPLOT_BMAX (1 << 30)
+#define SD_DOTPLOT_CELLS_MAX ((int64_t)1 << 27)
+#define SD_DOTPLOT_SET_MAX 4096
+int sd_dotplot_layout(const int64_t* read_lens, int32_t n_reads, int64_t W, int64_t B, int64_t* win_off, int64_t* cell_off,
+                      int64_t* windows_total, int64_t* cells_total);
+int sd_dotplot_host(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k, int64_t W,
+                    int64_t B, int64_t M, int32_t rc, int32_t threads, int32_t* kmers, int32_t* kmers_rc, int32_t* shared,
+                    int32_t* shared_rc, char* errbuf, size_t errlen);
+int sd_dotplot_dev(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k, int64_t W,
+                   int64_t B, int64_t M, int32_t rc, int32_t device, int32_t* kmers, int32_t* kmers_rc, int32_t* shared,
+                   int32_t* shared_rc, char* errbuf, size_t errlen);
+/* The device-resident form: d_text is device memory of `device` (read_off and read_lens HOST arrays), the four result
+ * arrays the caller's, on `device`, every element written by the call.  Everything is ordered on hip_stream.  The host
+ * waits once, for the counting pass's summary (four numbers: the total and the largest count, which size the sets and bound
+ * the launches, and the first window over the cap); the call returns with the other kernels in flight.  Its workspace is
+ * kept per device, and the next call on that device first waits for them.  SD_ERR_PARAM for a buffer that is not device
+ * memory, SD_ERR_UNSUPPORTED for another device's. */
+int sd_dotplot_reads_dev(const void* d_text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k,
+                         int64_t W, int64_t B, int64_t M, int32_t rc, int32_t device, void* hip_stream, int32_t* d_kmers,
+                         int32_t* d_kmers_rc, int32_t* d_shared, int32_t* d_shared_rc, char* errbuf, size_t errlen);
+/* info = {positions of a tile of the counting pass, cells of a row a workgroup of the pair kernel takes, SD_DOTPLOT_SET_MAX,
+ * the most pair-elements (elements looked up, counted with the call's largest set) of one launch of the pair kernel,
+ * SD_DOTPLOT_CELLS_MAX, launches of the pair kernel in this process so far}. */
+void sd_dotplot_info(int64_t info[6]);
+/* h(x), the splitmix64 finaliser the selection uses. */
+uint64_t sd_dotplot_hash(uint64_t x);
+/* Developer entry (tools/dotplot_bench.py): the arguments of sd_dotplot_dev; warmup + reps times each, between two HIP
+ * events: ms_count = the counting pass and the scan, ms_sets = gather and sort, ms_pairs = every launch of the pair kernel.
+ * info = launches, workgroups, cells, windows, selected positions, the largest set before duplicates are removed. */
+int sd_dotplot_kernel_bench(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k,
+                            int64_t W, int64_t B, int64_t M, int32_t rc, int32_t device, int32_t warmup, int32_t reps,
+                            float* ms_count, float* ms_sets, float* ms_pairs, int64_t info[6]);
+
 /* ---- subfamilies of a monomer's instances (--split; csrc/sd_split.hpp holds the rule) ---------------------------------
  * The member rows of one forward monomer of L bases -- rows of --msa with status 1, bytes [0, L): 0..4 = A C G T N,
  * SD_MSA_DEL; insertion slots take no part -- are clustered by column distance H.  centres = [per-column mode of all

@@ -39,6 +39,10 @@ Two more text files are this package's own (opt-in, `--profile`):
                       <out>_autocorr_spectrum.tsv (`--autocorr-spectrum`): read, start, end, lag, count, positions for
                       every lag of every window with a count.  read_autocorr / read_autocorr_spectrum below.
 
+  <out>_dotplot.tsv   (`--dotplot W[,B]`) one line per pair of windows of a read that share a k-mer, no header: read,
+                      start_i, end_i, start_j, end_j, kmers_i, kmers_j, shared, identity; with `--dotplot-rc` kmers_rc_j,
+                      shared_rc, identity_rc.  read_dotplot / write_dotplot below.
+
   <out>_split.tsv     (`--split P[,K]`) one line per row of <out>.tsv, no header: read, start, end, monomer, subfamily
                       ("<name>.<j>", '*' for a row that is no instance), d1, d2 (columns in which the row differs from its
                       subfamily's centre and from the nearest other one), columns (as in <out>_msa.tsv).
@@ -817,6 +821,120 @@ def read_autocorr_spectrum(path):
                 out.append(AutocorrSpectrumRow(x[0], *[int(v) for v in x[1:]]))
             except ValueError as e:
                 raise FormatError(path, lineno, str(e))
+    return out
+
+
+# ---- dotplot --------------------------------------------------------------------------------------
+# --dotplot W[,B]: <out>_dotplot.tsv, one line per cell (i, j), j <= i, of a read's windows of W bases whose shared or
+# shared_rc is not 0, no header -- read, start_i, end_i, start_j, end_j (the windows' bases, 0-based, end exclusive),
+# kmers_i, kmers_j (distinct selected k-mers of the two windows), shared (those in both), identity; with --dotplot-rc
+# kmers_rc_j, shared_rc, identity_rc follow (the k-mers of window i whose reverse complement lies in window j).  Lines in
+# the order read, i, j.  The identity is the one conversion below, printed %.2f.
+def dotplot_identity(shared, a, b, k):
+    """100 * (shared / min(a, b)) ** (1 / k): containment of the smaller set turned into a per-base identity, the conversion
+    ModDotPlot uses; 0 when nothing is shared"""
+    return 100.0 * (shared / min(a, b)) ** (1.0 / k) if shared > 0 else 0.0
+
+
+def dotplot_reaches(shared, a, b, k, P):
+    """dotplot_identity(shared, a, b, k) >= P, decided in integers: shared * 100^k >= P^k * min(a, b)"""
+    return P <= 0 or (shared > 0 and shared * 100 ** k >= P ** k * min(a, b))
+
+
+class Dotplot:
+    """lib.dotplot / DeviceDotplot.to_host(): kmers, kmers_rc = int32 [windows], shared, shared_rc = int32 [cells] (the two
+    reverse-strand arrays None without rc); read r owns the windows win_off[r] .. win_off[r + 1] and the cells
+    cell_off[r] .. cell_off[r + 1], ordered by i, then j, j = max(0, i - B) .. i when B > 0, j = 0 .. i otherwise
+    (include/sd_hip.h: sd_dotplot_*)."""
+
+    def __init__(self, kmers, kmers_rc, shared, shared_rc, win_off, cell_off, read_lens, k, W, B=0, M=1):
+        self.kmers, self.kmers_rc, self.shared, self.shared_rc = kmers, kmers_rc, shared, shared_rc
+        self.win_off, self.cell_off, self.read_lens = win_off, cell_off, read_lens
+        self.k, self.W, self.B, self.M = int(k), int(W), int(B), int(M)
+
+    @property
+    def rc(self):
+        return self.shared_rc is not None
+
+    def n_windows(self, r):
+        return int(self.win_off[r + 1] - self.win_off[r])
+
+    def first(self, i):
+        """the smallest j of row i"""
+        return max(0, i - self.B) if self.B > 0 else 0
+
+    def cell(self, r, i, j):
+        """the index of the cell (i, j) of read r in shared / shared_rc"""
+        B = self.B
+        if not 0 <= i < self.n_windows(r) or not self.first(i) <= j <= i:
+            raise IndexError("read %d has no cell (%d, %d)" % (r, i, j))
+        before = i * (i + 1) // 2 if B <= 0 or i <= B + 1 else (B + 1) * (B + 2) // 2 + (i - B - 1) * (B + 1)
+        return int(self.cell_off[r]) + before + j - self.first(i)
+
+    def matrix(self, r, rc=False):
+        """int32 [nw, nw]: shared (rc: shared_rc) of read r at [i, j], j <= i; -1 where there is no cell"""
+        import numpy as np
+        nw = self.n_windows(r)
+        out = np.full((nw, nw), -1, dtype=np.int32)
+        src = self.shared_rc if rc else self.shared
+        for i in range(nw):
+            a = self.cell(r, i, self.first(i))
+            out[i, self.first(i):i + 1] = src[a:a + i - self.first(i) + 1]
+        return out
+
+
+DotplotRow = namedtuple("DotplotRow", "read start_i end_i start_j end_j kmers_i kmers_j shared identity kmers_rc_j shared_rc identity_rc")
+
+
+def dotplot_rows(dp, names, min_identity=0):
+    """The lines of <out>_dotplot.tsv for a Dotplot -> [DotplotRow] (the last three fields None without rc): the cells whose
+    shared or shared_rc is not 0 and, with min_identity = P > 0, one of whose identities reaches P (dotplot_reaches)."""
+    out = []
+    k, W, P = dp.k, dp.W, int(min_identity)
+    for r, name in enumerate(names):
+        n, w0, at = int(dp.read_lens[r]), int(dp.win_off[r]), int(dp.cell_off[r])
+        for i in range(dp.n_windows(r)):
+            ki = int(dp.kmers[w0 + i])
+            for j in range(dp.first(i), i + 1):
+                s, kj = int(dp.shared[at]), int(dp.kmers[w0 + j])
+                s2, kr = (int(dp.shared_rc[at]), int(dp.kmers_rc[w0 + j])) if dp.rc else (0, 0)
+                at += 1
+                if (s == 0 and s2 == 0) or not (dotplot_reaches(s, ki, kj, k, P) or (dp.rc and dotplot_reaches(s2, ki, kr, k, P))):
+                    continue
+                tail = (kr, s2, dotplot_identity(s2, ki, kr, k)) if dp.rc else (None, None, None)
+                out.append(DotplotRow(name, i * W, min(n, (i + 1) * W), j * W, min(n, (j + 1) * W), ki, kj, s,
+                                      dotplot_identity(s, ki, kj, k), *tail))
+    return out
+
+
+def format_dotplot(rows):
+    return "".join(("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f" % tuple(r)[:9]) + ("\t%d\t%d\t%.2f" % tuple(r)[9:] if r.shared_rc is not None else "") + "\n"
+                   for r in rows)
+
+
+def write_dotplot(path, rows):
+    with open(path, "w", newline="") as f:
+        f.write(format_dotplot(rows))
+
+
+def read_dotplot(path):
+    """<out>_dotplot.tsv -> [DotplotRow]; the identities as printed."""
+    with open(path) as f:
+        return read_dotplot_text(f.read(), path)
+
+
+def read_dotplot_text(text, path="<text>"):
+    """the text of an <out>_dotplot.tsv (format_dotplot) -> [DotplotRow]"""
+    out = []
+    for lineno, line in enumerate(text.splitlines(), 1):
+        x = line.split("\t")
+        if len(x) not in (9, 12):
+            raise FormatError(path, lineno, "expected 9 or 12 columns, got %d" % len(x))
+        try:
+            tail = (int(x[9]), int(x[10]), float(x[11])) if len(x) == 12 else (None, None, None)
+            out.append(DotplotRow(x[0], *[int(v) for v in x[1:8]], float(x[8]), *tail))
+        except ValueError as e:
+            raise FormatError(path, lineno, str(e))
     return out
 
 

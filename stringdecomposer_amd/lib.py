@@ -63,6 +63,7 @@ EXPORTS = [
     "sd_autocorr_layout", "sd_autocorr_host", "sd_autocorr_dev", "sd_autocorr_reads_dev", "sd_autocorr_positions", "sd_autocorr_peaks",
     "sd_autocorr_seed", "sd_autocorr_info", "sd_autocorr_kernel_bench",
     "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
+    "sd_dotplot_layout", "sd_dotplot_host", "sd_dotplot_dev", "sd_dotplot_reads_dev", "sd_dotplot_info", "sd_dotplot_hash", "sd_dotplot_kernel_bench",
     "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
     "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
     "sd_screen_kernel_bench",
@@ -291,6 +292,21 @@ def load():
     L.sd_autocorr_info.restype = None
     L.sd_autocorr_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_int64)]
+    L.sd_dotplot_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
+    L.sd_dotplot_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_dotplot_dev.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_dotplot_reads_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
+                                       C.c_size_t]
+    L.sd_dotplot_info.argtypes = [P(C.c_int64)]
+    L.sd_dotplot_info.restype = None
+    L.sd_dotplot_hash.argtypes = [C.c_uint64]
+    L.sd_dotplot_hash.restype = C.c_uint64
+    L.sd_dotplot_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float),
+                                          P(C.c_int64)]
     L.sd_split_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64), C.c_char_p, C.c_size_t]
     L.sd_split_dev.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -1420,6 +1436,165 @@ def autocorr_kernel_bench(reads, k, D=4096, window=0, device=0, warmup=2, reps=5
         raise SdError(rc, "sd_autocorr_kernel_bench")
     out = {"prep_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b]}
     out.update(zip(("launches", "workgroups", "cells", "words"), [int(x) for x in info]))
+    return out
+
+
+DOTPLOT_KMAX = 32
+DOTPLOT_WMAX = 1 << 30
+DOTPLOT_MMAX = 1 << 20
+DOTPLOT_BMAX = 1 << 30
+DOTPLOT_CELLS_MAX = 1 << 27
+DOTPLOT_SET_MAX = 4096
+
+
+def _dotplot_args(k, W, B, M, who):
+    """1 <= k <= 32, 1 <= W <= 2^30, 0 <= B <= 2^30, 1 <= M <= 2^20, refused here before any array is made or any device
+    is touched"""
+    for name, v, lo, hi in (("k", k, 1, DOTPLOT_KMAX), ("W", W, 1, DOTPLOT_WMAX), ("B", B, 0, DOTPLOT_BMAX), ("M", M, 1, DOTPLOT_MMAX)):
+        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+            raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer %d .. %d" % (who, name, v, lo, hi))
+    return k, W, B, M
+
+
+def dotplot_info():
+    """sd_dotplot_info -> {"tile": positions of a tile of the counting pass, "jseg": cells of a row a workgroup of the pair
+    kernel takes, "set_max", "launch_work": the most pair-elements of one launch of the pair kernel, "cells_max",
+    "launches": its launches in this process so far}"""
+    info = (C.c_int64 * 6)()
+    load().sd_dotplot_info(info)
+    return dict(zip(("tile", "jseg", "set_max", "launch_work", "cells_max", "launches"), (int(x) for x in info)))
+
+
+def dotplot_hash(x):
+    """h(x) of the selection rule, the splitmix64 finaliser (sd_dotplot_hash)"""
+    return int(load().sd_dotplot_hash(C.c_uint64(x & ((1 << 64) - 1))))
+
+
+def dotplot_layout(read_lens, W, B=0):
+    """The windows and cells of reads of the given lengths (sd_dotplot_layout) -> (win_off, cell_off int64 [n + 1], windows,
+    cells): read r owns the windows win_off[r] .. win_off[r + 1] and the cells cell_off[r] .. cell_off[r + 1]."""
+    import numpy as np
+    _, W, B, _ = _dotplot_args(1, W, B, 1, "dotplot_layout")
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    win_off = np.zeros(len(rl) + 1, dtype=np.int64)
+    cell_off = np.zeros(len(rl) + 1, dtype=np.int64)
+    nw, nc = C.c_int64(0), C.c_int64(0)
+    rc = load().sd_dotplot_layout(rl.ctypes.data, len(rl), W, B, win_off.ctypes.data, cell_off.ctypes.data, C.byref(nw), C.byref(nc))
+    if rc != SD_OK:
+        raise SdError(rc, "sd_dotplot_layout: a negative read length, or 2^62 windows or cells, or more")
+    return win_off, cell_off, int(nw.value), int(nc.value)
+
+
+def _dotplot_cells_check(who, windows, cells):
+    if cells > DOTPLOT_CELLS_MAX:
+        raise SdError(SD_ERR_PARAM, "%s: %d windows make %d cells, the cap is %d (SD_DOTPLOT_CELLS_MAX): use longer windows, a band "
+                                    "or fewer reads per call" % (who, windows, cells, DOTPLOT_CELLS_MAX))
+
+
+def dotplot_text(text, read_off, read_lens, k, W, B=0, M=1, rc=False, device=None, threads=1):
+    """dotplot on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any order of
+    offsets are allowed) -> formats.Dotplot"""
+    import numpy as np
+    from . import formats
+    k, W, B, M = _dotplot_args(k, W, B, M, "dotplot")
+    L = load()
+    tb = _b(text)
+    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
+        raise SdError(SD_ERR_PARAM, "dotplot: offsets and lengths differ in number, or a read lies outside the text")
+    win_off, cell_off, windows, cells = dotplot_layout(rl, W, B)
+    _dotplot_cells_check("dotplot", windows, cells)
+    kmers, shared = np.zeros(max(windows, 1), dtype=np.int32), np.zeros(max(cells, 1), dtype=np.int32)
+    kmers_rc, shared_rc = (np.zeros_like(kmers), np.zeros_like(shared)) if rc else (None, None)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    err = C.create_string_buffer(1024)
+    if device is None:
+        e = L.sd_dotplot_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, W, B, M, int(bool(rc)), int(threads), ptr(kmers),
+                              ptr(kmers_rc), ptr(shared), ptr(shared_rc), err, 1024)
+    else:
+        e = L.sd_dotplot_dev(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, W, B, M, int(bool(rc)), int(device), ptr(kmers),
+                             ptr(kmers_rc), ptr(shared), ptr(shared_rc), err, 1024)
+    _text_check(e, err)
+    return formats.Dotplot(kmers[:windows], kmers_rc[:windows] if rc else None, shared[:cells], shared_rc[:cells] if rc else None,
+                           win_off, cell_off, rl.copy(), k, W, B, M)
+
+
+def dotplot(reads, k, W, B=0, M=1, rc=False, device=None, threads=1):
+    """The windowed k-mer identity of every read against itself (include/sd_hip.h: sd_dotplot_*): the read cut into windows
+    of W bases, the cell (i, j), j <= i (i - j <= B when B > 0), = the distinct selected k-mers windows i and j share, with
+    rc also those of window i whose reverse complement lies in window j.  M: keep a code when h(code) % M == 0.  reads: a
+    list of bytes / str, or a DeviceReads (then the kernels read the device text where it lies).  device=None: host threads
+    (sd_dotplot_host); else the kernels of csrc/sd_dotplot.hip on that device.  Both give the same integers.
+    -> formats.Dotplot"""
+    if isinstance(reads, DeviceReads):
+        return dotplot_device(reads, k, W, B, M, rc).to_host(reads.read_lens, k, W, B, M)
+    text, ro, rl = _autocorr_reads(reads)
+    return dotplot_text(text, ro, rl, k, W, B, M, rc, device, threads)
+
+
+class DeviceDotplot(namedtuple("DeviceDotplot", "kmers kmers_rc shared shared_rc win_off cell_off")):
+    """The dotplot of a DeviceReads in device memory (dotplot_device): kmers, kmers_rc int32 [windows], shared, shared_rc
+    int32 [cells] (the two reverse-strand tensors None without rc), win_off, cell_off int64 [n + 1], torch tensors on the
+    reads' device."""
+    __slots__ = ()
+
+    def to_host(self, read_lens, k, W, B=0, M=1):
+        """-> formats.Dotplot (waits for the device)"""
+        import numpy as np
+        from . import formats
+        h = lambda t: t.cpu().numpy() if t is not None else None
+        return formats.Dotplot(h(self.kmers), h(self.kmers_rc), h(self.shared), h(self.shared_rc), h(self.win_off), h(self.cell_off),
+                               np.asarray(read_lens, dtype=np.int64), k, W, B, M)
+
+
+def dotplot_device(reads, k, W, B=0, M=1, rc=False, stream=None):
+    """dotplot on a DeviceReads (or a list of bytes / str, uploaded first), everything on the reads' device
+    (sd_dotplot_reads_dev) -> DeviceDotplot.  torch allocates the results on `stream` (None: the device's current stream)
+    and the library fills them there.  The host waits once, for the counting pass's summary; the call returns with the other
+    kernels in flight and no result is copied to the host."""
+    k, W, B, M = _dotplot_args(k, W, B, M, "dotplot_device")
+    import torch
+    L = load()
+    if not isinstance(reads, DeviceReads):
+        import numpy as np
+        rs = [_b(s) for s in reads]
+        flat = np.frombuffer(b"".join(rs) or b"N", dtype=np.uint8).copy()   # (back to back; one byte when there is no base)
+        reads = DeviceReads(torch.from_numpy(flat).to("cuda"), [len(s) for s in rs])
+    dev = torch.device("cuda", reads.device)
+    st = _torch_stream(torch, dev, stream)
+    win_off, cell_off, windows, cells = dotplot_layout(reads.read_lens, W, B)
+    _dotplot_cells_check("dotplot_device", windows, cells)
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    with torch.cuda.stream(st):
+        kmers = torch.empty(windows, dtype=torch.int32, device=dev)
+        shared = torch.empty(cells, dtype=torch.int32, device=dev)
+        kmers_rc, shared_rc = (torch.empty_like(kmers), torch.empty_like(shared)) if rc else (None, None)
+        d_win = torch.from_numpy(win_off).to(dev, non_blocking=True)
+        d_cell = torch.from_numpy(cell_off).to(dev, non_blocking=True)
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+    err = C.create_string_buffer(1024)
+    _text_check(L.sd_dotplot_reads_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, k, W, B, M, int(bool(rc)), dev.index or 0,
+                                       C.c_void_p(st.cuda_stream), ptr(kmers), ptr(kmers_rc), ptr(shared), ptr(shared_rc), err, 1024), err)
+    return DeviceDotplot(kmers, kmers_rc, shared, shared_rc, d_win, d_cell)
+
+
+def dotplot_kernel_bench(reads, k, W, B=0, M=1, rc=False, device=0, warmup=2, reps=5):
+    """sd_dotplot_kernel_bench -> {"count_ms", "sets_ms", "pairs_ms": [...], "launches", "workgroups", "cells", "windows",
+    "selected", "largest"}."""
+    k, W, B, M = _dotplot_args(k, W, B, M, "dotplot_kernel_bench")
+    text, ro, rl = _autocorr_reads(reads)
+    a, b, c = ((C.c_float * reps)() for _ in range(3))
+    info = (C.c_int64 * 6)()
+    e = load().sd_dotplot_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, W, B, M, int(bool(rc)), int(device),
+                                       int(warmup), int(reps), a, b, c, info)
+    if e != SD_OK:
+        raise SdError(e, "sd_dotplot_kernel_bench")
+    out = {"count_ms": [float(x) for x in a], "sets_ms": [float(x) for x in b], "pairs_ms": [float(x) for x in c]}
+    out.update(zip(("launches", "workgroups", "cells", "windows", "selected", "largest"), [int(x) for x in info]))
     return out
 
 

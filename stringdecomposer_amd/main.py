@@ -39,6 +39,7 @@ class _LazyNumpy:
 np = _LazyNumpy()
 
 from . import autocorr
+from . import dotplot
 from . import split
 from . import lib
 from . import shard
@@ -734,6 +735,7 @@ def main(argv=None):
                         help="refuse a read whose heatmap needs more than N pairs (by default 4000000000, about 8 s of device "
                              "time on 171-bp blocks; 0: no limit)")
     autocorr.add_arguments(parser)
+    dotplot.add_arguments(parser)
     split.add_arguments(parser)
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
@@ -756,6 +758,8 @@ def main(argv=None):
         _check_heatmap(args)
     if args.autocorr is not None:
         autocorr.check(args)
+    if args.dotplot is not None:
+        dotplot.check(args)
     if args.split is not None:
         split.check(args)
     if args.profile:
@@ -870,6 +874,15 @@ def main(argv=None):
             logger.info("--autocorr failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the k-mer autocorrelation of the reads to " + ", ".join(saved))
+
+    if args.dotplot is not None:
+        try:
+            saved = dotplot.write(args, args.out_dir, args.out_file, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--dotplot failed: " + e.msg + "\n")
+            logger.info("--dotplot failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the windowed k-mer identities of the reads to " + ", ".join(saved))
 
     if args.split is not None:
         try:
