@@ -150,6 +150,11 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     // fp16, unranked: the whole B reduction stays in fp16 (no per-row int conversions); `del` is folded
     // into the end offsets so that the wave maximum is directly the start term B_i + del of the next row
     constexpr bool HRED = F16 || U16;   // (ranked too: sd_rank_keep writes the per-chunk end offsets on every lane of a template)
+    // u16 cells with the floors applied in place (FLS > 0): the slot loop is a run of adds, then the maximum chain (see there).
+    // The fp16 / int16 cells' add is a packed instruction, which gains nothing in a run, and the FLS == 0 u16 kernels take
+    // their floor maximum inside the slots: a run would need the FL floored operands in temporaries, 12-37 registers on top
+    // of the 90-118 the P >= 30 kernels of that kind hold (four waves per SIMD end at 128).  Both keep the skewed loop.
+    constexpr bool SLOT_RUNS = U16 && FLS > 0;
     // HRED row tail.  With a_l = max(last slot, K_l) the total of virtual lane l:
     //   * the end cell of a template is the maximum of a_l over ALL its lanes (prefix maximum along the
     //     template), so the B reduction takes every lane's total with its template's end offset
@@ -413,8 +418,14 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
         const uint32_t w0 = U16 ? (L[0] & notStart) : bfi(startMask, NEGC, L[0]);
         uint32_t u_[P], v_[P], c_[P];
         uint32_t run = 0;
-        // software-pipelined over the slots so that no packed op consumes the result of the
-        // instruction right before it (gfx950 needs a wait state there)
+        // Skewed loop (fp16 / int16 cells, u16 cells with the floor inside the slots): software-pipelined over the slots so
+        // that no packed op consumes the result of the instruction right before it (gfx950 needs a wait state there).
+        // Run loop (SLOT_RUNS: u16 cells, floors in place): the adds of all slots first, then the maximum chain.  A plain
+        // VOP2 v_add_u32 between two packed maxima issues at the packed rate (3.9-4.0 cycles per instruction per SIMD at
+        // four waves); in a run of its own kind it issues at 2.2-2.3, and the chain pays its wait states (s_nop 0, no
+        // VALU slot) without losing throughput: 3.09 cycles per instruction for 35 adds + 35 chained maxima against 4.00
+        // for the skewed order and 4.05 alternating with the wait state (tools/ubench_issue.hip,
+        // profiles/ubench_issue_runs.txt).  The instruction count of the row is the same.
         if constexpr (HRED) {
             if constexpr (FLS > 0) {
                 // four levels: FL, FL - FLS, FL - 2 FLS, FL - 3 FLS (not below 1); the floors of a level's group are skipped
@@ -439,6 +450,21 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 }
             }
             const uint32_t w0f = FLS > 0 ? (U16 ? (L[0] & notStart) : bfi(startMask, NEGC, L[0])) : w0;   // (slot 0's keep operand, after the in-place floor)
+            if constexpr (SLOT_RUNS) {
+                // u16 cells, floors already in place: every slot's sum reads the OLD row and the table only, so the P adds
+                // go first, as one run of plain v_add_u32 in the table registers (reloaded at the end of the row anyway),
+                // and the maximum chain follows.  `asm volatile` pins the two runs: the scheduler interleaves them again
+                // through any sched_barrier.  Each maximum consumes the one before it; the compiler puts the wait state
+                // (s_nop 0, no VALU slot) in front.
+#pragma unroll
+                for (int q = P - 1; q >= 1; --q) asm volatile("v_add_u32 %0, %0, %1" : "+v"(tb[q]) : "v"(L[q - 1]));
+                asm volatile("v_add_u32 %0, %0, %1" : "+v"(tb[0]) : "v"(KB));
+                // slot 0: the old carry K joins the chain here (see the skewed loop below)
+                asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(L[0]) : "v"(tb[0]), "v"(w0f), "v"(K));
+#pragma unroll
+                for (int q = 1; q < P; ++q)
+                    asm volatile("v_pk_maximum3_f16 %0, %1, %2, %0" : "+v"(L[q]) : "v"(L[q - 1]), "v"(tb[q]));
+            } else {
 #pragma unroll
             for (int s = 0; s < P + 4; ++s) {
                 if (s >= 4) {
@@ -463,7 +489,8 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            (void)c_; (void)run;
+            }
+            (void)c_; (void)run; (void)u_; (void)v_;
         } else {
 #pragma unroll
         for (int s = 0; s < P + 3; ++s) {

@@ -10,7 +10,11 @@
 //     cycles per wave-instruction per SIMD = (last end - first start) / (W * instructions per wave)
 // next to the wall-clock figure of the whole launch (all 1024 SIMDs busy, so DVFS is included).
 //
-// Build: hipcc -O3 --offload-arch=gfx950 tools/ubench_issue.hip -o tools/ubench_issue ; run on the GPU box.
+// The run-shaped legs (KERNEL_RUNS below) ask what a MIX costs by its order: R plain adds in a row, then R chained
+// packed maxima, against the same instructions alternating -> profiles/ubench_issue_runs.txt.
+//
+// Build: hipcc -O3 --offload-arch=gfx950 tools/ubench_issue.hip -o tools/ubench_issue ; run on the GPU box:
+// tools/ubench_issue [out.csv [passes]].
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -252,9 +256,71 @@ KERNEL_INDEP64(k_lshl_add_u64, I_LSHL_ADD_U64)
 KERNEL_INDEP64(k_add_f64, I_ADD_F64)
 KERNEL_INDEP64(k_pk_add_f32, I_PK_ADD_F32)
 
+// Run-shaped mixes (the narrow u16 fill's slot loop): R independent plain v_add_u32 (VGPR operands, e32), then R
+// v_pk_maximum3_f16 that each consume the previous instruction's result (one chain through %0, the add's register as
+// the second operand) with the wait state `s_nop 0` in front -- against the same instructions alternating.  The R add
+// registers are fixed (v24..v58, clobbered) so that a leg needs no 35 asm operands and fits 8 waves per SIMD; REPS
+// runs per loop trip keep a trip near 256 instructions.  The s_nop is not counted as an instruction.
+// "skewed" is the shipped order: maximum, add, maximum, add ..., the add two instructions ahead of the maximum that
+// reads it and the chain's maxima one add apart, so no wait state.  PRE: the row's other plain ops ahead of the run.
+#define R_ADD(n) "v_add_u32 v" #n ", v" #n ", %4\n\t"
+#define R_MAX(n) "s_nop 0\n\tv_pk_maximum3_f16 %0, %0, v" #n ", %5\n\t"
+#define R_INIT(n) "v_mov_b32 v" #n ", %4\n\t"
+#define RUN1(A) A(24)
+#define RUN2(A) RUN1(A) A(25)
+#define RUN4(A) RUN2(A) A(26) A(27)
+#define RUN8(A) RUN4(A) A(28) A(29) A(30) A(31)
+#define RUN16(A) RUN8(A) A(32) A(33) A(34) A(35) A(36) A(37) A(38) A(39)
+#define RUN35(A) RUN16(A) A(40) A(41) A(42) A(43) A(44) A(45) A(46) A(47) A(48) A(49) A(50) A(51) A(52) A(53) A(54) \
+                 A(55) A(56) A(57) A(58)
+#define R_SK(m, a) "v_pk_maximum3_f16 %0, %0, v" #m ", %5\n\tv_add_u32 v" #a ", v" #a ", %4\n\t"
+#define SKEW35 R_SK(24, 26) R_SK(25, 27) R_SK(26, 28) R_SK(27, 29) R_SK(28, 30) R_SK(29, 31) R_SK(30, 32) R_SK(31, 33) \
+               R_SK(32, 34) R_SK(33, 35) R_SK(34, 36) R_SK(35, 37) R_SK(36, 38) R_SK(37, 39) R_SK(38, 40) R_SK(39, 41) \
+               R_SK(40, 42) R_SK(41, 43) R_SK(42, 44) R_SK(43, 45) R_SK(44, 46) R_SK(45, 47) R_SK(46, 48) R_SK(47, 49) \
+               R_SK(48, 50) R_SK(49, 51) R_SK(50, 52) R_SK(51, 53) R_SK(52, 54) R_SK(53, 55) R_SK(54, 56) R_SK(55, 57) \
+               R_SK(56, 58) R_SK(57, 24) R_SK(58, 25)
+#define R_PRE "v_and_b32 %1, %1, %4\n\tv_and_b32 %2, %2, %5\n\tv_add_u32 %3, %3, %4\n\t"
+#define R_CLOBBERS                                                                                                  \
+    "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39",  \
+    "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55",  \
+    "v56", "v57", "v58"
+#define KERNEL_RUNS(NAME, BODY, REPS)                                                                               \
+    __global__ __launch_bounds__(256) void NAME(unsigned* out, Stamp* stamps, int iters, unsigned seed) {           \
+        unsigned a[4];                                                                                              \
+        for (int i = 0; i < 4; ++i) a[i] = seed * (i + 1) + threadIdx.x;                                            \
+        unsigned b = seed ^ 0x3c003c00u, c = seed + 0x40004000u;                                                    \
+        asm volatile(RUN35(R_INIT) : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "v"(b), "v"(c) : R_CLOBBERS);                                    \
+        __syncthreads();                                                                                            \
+        const unsigned long long t0 = __builtin_readcyclecounter();                                                 \
+        for (int it = 0; it < iters; ++it) {                                                                        \
+            _Pragma("unroll") for (int r = 0; r < REPS; ++r)                                                        \
+                asm volatile(BODY : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "v"(b), "v"(c) : R_CLOBBERS);     \
+        }                                                                                                           \
+        const unsigned long long t1 = __builtin_readcyclecounter();                                                 \
+        unsigned s = 0;                                                                                             \
+        asm volatile("v_xor_b32 %0, v24, v58" : "=v"(s) : : R_CLOBBERS);                                            \
+        for (int i = 0; i < 4; ++i) s ^= a[i];                                                                      \
+        if (s == 0x12345678u) out[threadIdx.x] = s;                                                                 \
+        if ((threadIdx.x & 63) == 0) {                                                                              \
+            unsigned hw, xc;                                                                                        \
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                                        \
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xc));                                       \
+            Stamp st{t0, t1, hw, xc};                                                                               \
+            stamps[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = st;                                              \
+        }                                                                                                           \
+    }
+KERNEL_RUNS(k_runs_1, RUN1(R_ADD) RUN1(R_MAX), 128)
+KERNEL_RUNS(k_runs_2, RUN2(R_ADD) RUN2(R_MAX), 64)
+KERNEL_RUNS(k_runs_4, RUN4(R_ADD) RUN4(R_MAX), 32)
+KERNEL_RUNS(k_runs_8, RUN8(R_ADD) RUN8(R_MAX), 16)
+KERNEL_RUNS(k_runs_16, RUN16(R_ADD) RUN16(R_MAX), 8)
+KERNEL_RUNS(k_runs_35, RUN35(R_ADD) RUN35(R_MAX), 4)
+KERNEL_RUNS(k_runs_35_pre, R_PRE RUN35(R_ADD) RUN35(R_MAX), 4)
+KERNEL_RUNS(k_skew_35, SKEW35, 4)
+
 typedef void (*kern_t)(unsigned*, Stamp*, int, unsigned);
 
-static void run(const char* name, kern_t k, int inst_per_trip, int W, FILE* csv) {
+static void run(const char* name, kern_t k, int inst_per_trip, int W, FILE* csv, int pass = 1) {
     const int blocks = 256 * W;   // 256-thread blocks: the dispatcher puts the 4 waves on the 4 SIMDs of a CU
     const int waves = blocks * 4;
     const int iters = 400;
@@ -307,16 +373,19 @@ static void run(const char* name, kern_t k, int inst_per_trip, int W, FILE* csv)
     const double ns = ms * 1e6 / (n_inst * W);
     printf("%-26s W=%d  simds=%4zu (with exactly W: %4d)  cyc/inst/SIMD=%6.2f  cyc/inst/wave=%6.2f  wall %.3f ms = %.3f ns/inst/SIMD (%.2f GHz implied)\n",
            name, W, groups.size(), exact, med, medw, ms, ns, med > 0 ? med / ns : 0.0);
-    if (csv) fprintf(csv, "%s,%d,%zu,%d,%.3f,%.3f,%.4f,%.4f\n", name, W, groups.size(), exact, med, medw, ms, ns);
+    if (csv) fprintf(csv, "%s,%d,%zu,%d,%.3f,%.3f,%.4f,%.4f,%d\n", name, W, groups.size(), exact, med, medw, ms, ns, pass);
     hipFree(d);
     hipFree(ds);
     hipEventDestroy(e0);
     hipEventDestroy(e1);
 }
 
+// usage: ubench_issue [out.csv [passes]]: every leg once, then passes - 1 more passes over the run-shaped legs and the
+// mixes they are compared with (the spread of the go/no-go pair)
 int main(int argc, char** argv) {
     FILE* csv = argc > 1 ? fopen(argv[1], "w") : nullptr;
-    if (csv) fprintf(csv, "kernel,waves_per_simd,simds_seen,simds_with_W,cyc_per_inst_per_simd,cyc_per_inst_per_wave,wall_ms,wall_ns_per_inst_per_simd\n");
+    const int passes = argc > 2 ? atoi(argv[2]) : 1;
+    if (csv) fprintf(csv, "kernel,waves_per_simd,simds_seen,simds_with_W,cyc_per_inst_per_simd,cyc_per_inst_per_wave,wall_ms,wall_ns_per_inst_per_simd,pass\n");
     hipDeviceProp_t p;
     hipGetDeviceProperties(&p, 0);
     printf("device %s  CUs %d  clock %d kHz\n", p.gcnArchName, p.multiProcessorCount, p.clockRate);
@@ -358,8 +427,21 @@ int main(int argc, char** argv) {
         {"dep v_add_f32", k_dep_add_f32, 128}, {"dep v_max_i32", k_dep_max_i32, 128},
         {"dep s_nop1+v_max_f16_dpp", k_dep_dpp, 128},
     };
+    // instructions per trip: REPS x (R adds + R maxima) (+ 3 plain ops)
+    const E runs[] = {
+        {"mix: add_u32 + pk_maximum3", k_mix_addu32_max3, 256},
+        {"skewed: 35 x (max3 chain, add)", k_skew_35, 280},
+        {"runs: R=1 add, nop+max3 chain", k_runs_1, 256}, {"runs: R=2", k_runs_2, 256}, {"runs: R=4", k_runs_4, 256},
+        {"runs: R=8", k_runs_8, 256}, {"runs: R=16", k_runs_16, 256}, {"runs: R=35", k_runs_35, 280},
+        {"runs: 2 and + add, R=35", k_runs_35_pre, 292},
+    };
     for (int W : {1, 2, 4, 8})
         for (const E& e : list) run(e.n, e.k, e.per, W, csv);
+    for (int pass = 1; pass <= passes; ++pass) {
+        printf("-- run-shaped mixes, pass %d\n", pass);
+        for (int W : {1, 2, 4, 8})
+            for (const E& e : runs) run(e.n, e.k, e.per, W, csv, pass);
+    }
     if (csv) fclose(csv);
     return 0;
 }
