@@ -18,12 +18,10 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <map>
-#include <mutex>
 
 #include "sd_autocorr.hpp"
 #include "sd_host.hpp"
-#include "sd_pipeline.hpp"
+#include "sd_job_dev.hpp"
 
 namespace sd {
 
@@ -127,37 +125,12 @@ namespace {
 
 std::atomic<int64_t> g_ac_launches{0};   // launches of sd_autocorr_pairs in this process (sd_autocorr_info)
 
-// Per device, kept between calls: the planes and the per-read tables.  The device-resident call returns with its kernels in
-// flight on the caller's stream, so the buffers cannot be the call's own; ev_use is recorded behind the last kernel and the
-// next call on the device waits for it before it touches them.
-struct AcCtx {
-    std::mutex m;
+// Per device, kept between calls (sd_job_dev.hpp: DevWork): the planes and the per-read tables
+// [roff | rlen | pw | win_off | tile_off].
+struct AcCtx : DevWork, ReadTable {
     DevBuf<uint64_t> planes;
-    DevBuf<int64_t> reads;      // [roff | rlen | pw | win_off | tile_off], n_reads + 1 each
     DevBuf<uint8_t> text;       // sd_autocorr_dev: the reads, back to back
-    PinBuf<int64_t> h_reads;
-    hipEvent_t ev_use = nullptr;
-    bool used = false;
-    int n_cu = 256;
-    void settle() {
-        if (used && hipEventSynchronize(ev_use) != hipSuccess) (void)hipGetLastError();
-        used = false;
-    }
 };
-
-AcCtx& ac_ctx(int device) {
-    static std::mutex m;
-    static std::map<int, AcCtx*>* all = new std::map<int, AcCtx*>;   // (never destroyed: no HIP call at process exit)
-    std::lock_guard<std::mutex> g(m);
-    AcCtx*& c = (*all)[device];
-    if (!c) {
-        c = new AcCtx;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
-        else (void)hipGetLastError();
-    }
-    return *c;
-}
 
 // win_off (n_reads + 1, may be null) and the windows of the reads; SD_ERR_UNSUPPORTED when the count leaves 62 bits
 int ac_layout(const int64_t* read_lens, int32_t n_reads, int64_t W, int64_t* win_off, int64_t& windows) {
@@ -193,13 +166,6 @@ int ac_limits(const char* who, const int64_t* read_lens, int32_t n_reads, int64_
                                     std::to_string(sd::AUTOCORR_CELLS_MAX) + " cells (AUTOCORR_CELLS_MAX): use longer windows, fewer lags or fewer reads per call");
         return SD_ERR_PARAM;
     }
-    return SD_OK;
-}
-
-int ac_device_check(int32_t device, char* errbuf, size_t errlen) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_err(errbuf, errlen, "no usable HIP device"); return SD_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) { set_err(errbuf, errlen, "device " + std::to_string(device) + " does not exist"); return SD_ERR_PARAM; }
     return SD_OK;
 }
 
@@ -280,10 +246,8 @@ struct AcBench {
 // Nothing waits (bench: the timed repetitions do).  Throws HipFail.
 void ac_enqueue(AcCtx& c, hipStream_t st, const uint8_t* d_text, const int64_t* roff, const int64_t* read_lens, int32_t n_reads, int k,
                 int64_t D, int64_t W, const int64_t* win_off, int64_t windows, int64_t* d_counts, const AcBench* bench) {
-    const size_t nr = (size_t)n_reads + 1;
-    c.h_reads.alloc(5 * nr);
-    c.reads.alloc(5 * nr);
-    int64_t *h_off = c.h_reads.p, *h_len = h_off + nr, *h_pw = h_len + nr, *h_win = h_pw + nr, *h_tile = h_win + nr;
+    c.shape(5, n_reads);
+    int64_t *h_off = c.h(0), *h_len = c.h(1), *h_pw = c.h(2), *h_win = c.h(3), *h_tile = c.h(4);
     int64_t words = 0, tiles = 0, maxn = 0;
     for (int32_t r = 0; r < n_reads; ++r) {
         h_off[r] = roff[r];
@@ -297,12 +261,12 @@ void ac_enqueue(AcCtx& c, hipStream_t st, const uint8_t* d_text, const int64_t* 
     }
     h_off[n_reads] = 0; h_len[n_reads] = 0; h_pw[n_reads] = words; h_win[n_reads] = windows; h_tile[n_reads] = tiles;
     c.planes.alloc(3 * (size_t)words);
-    SD_HIP(hipMemcpyAsync(c.reads.p, c.h_reads.p, 5 * nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    c.upload(5, st);
     const size_t cells = (size_t)windows * (size_t)D;
     if (cells) SD_HIP(hipMemsetAsync(d_counts, 0, cells * sizeof(int64_t), st));
     if (n_reads == 0 || words == 0) return;
     uint64_t *lo = c.planes.p, *hi = lo + words, *v = hi + words;
-    const int64_t *d_off = c.reads.p, *d_len = d_off + nr, *d_pw = d_len + nr, *d_win = d_pw + nr, *d_tile = d_win + nr;
+    const int64_t *d_off = c.d(0), *d_len = c.d(1), *d_pw = c.d(2), *d_win = c.d(3), *d_tile = c.d(4);
     const unsigned prep_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((words + 3) / 4, (int64_t)c.n_cu * 32));
     auto prep = [&]() {
         hipLaunchKernelGGL(sd::sd_autocorr_prep, dim3(prep_grid), dim3(sd::AC_T), 0, st, d_text, d_off, d_len, d_pw, (int)n_reads, words, lo, hi, v);
@@ -345,47 +309,15 @@ void ac_enqueue(AcCtx& c, hipStream_t st, const uint8_t* d_text, const int64_t* 
         pairs();
         return;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    SD_HIP(hipEventCreate(&e0));
-    SD_HIP(hipEventCreate(&e1));
-    try {
-        for (int pass = 0; pass < 2; ++pass)   // the planes, then the pairs on them
-            for (int it = 0; it < bench->warmup + bench->reps; ++it) {
-                if (pass == 1 && cells) SD_HIP(hipMemsetAsync(d_counts, 0, cells * sizeof(int64_t), st));
-                SD_HIP(hipEventRecord(e0, st));
-                if (pass == 0) prep(); else pairs();
-                SD_HIP(hipEventRecord(e1, st));
-                SD_HIP(hipEventSynchronize(e1));
-                if (it >= bench->warmup) SD_HIP(hipEventElapsedTime(&(pass == 0 ? bench->ms_prep : bench->ms_pairs)[it - bench->warmup], e0, e1));
-            }
-    } catch (...) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        throw;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    StageClock clock;   // the planes, then the pairs on them
+    clock.time(st, bench->warmup, bench->reps, bench->ms_prep, prep);
+    clock.time(st, bench->warmup, bench->reps, bench->ms_pairs, pairs, [&]() {
+        if (cells) SD_HIP(hipMemsetAsync(d_counts, 0, cells * sizeof(int64_t), st));
+    });
     bench->info[0] = launches;
     bench->info[1] = wgs;
     bench->info[2] = (int64_t)cells;
     bench->info[3] = words;
-}
-
-void ac_used(AcCtx& c, hipStream_t st) {
-    ensure_event(c.ev_use, hipEventDisableTiming);
-    SD_HIP(hipEventRecord(c.ev_use, st));
-    c.used = true;
-}
-
-int ac_text_args(const char* who, const void* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const void* counts,
-                 int64_t cells, char* errbuf, size_t errlen) {
-    int64_t bases = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (!read_off || read_off[r] < 0) { set_err(errbuf, errlen, std::string(who) + ": missing or negative read offset"); return SD_ERR_PARAM; }
-        bases += read_lens[r];
-    }
-    if ((bases > 0 && !text) || (cells > 0 && !counts)) { set_err(errbuf, errlen, std::string(who) + ": missing argument"); return SD_ERR_PARAM; }
-    return SD_OK;
 }
 
 int ac_dev(const char* who, const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int32_t k, int64_t D,
@@ -395,18 +327,17 @@ int ac_dev(const char* who, const char* text, const int64_t* read_off, const int
     int rc = ac_limits(who, read_lens, n_reads, k, D, W, win_off.data(), windows, errbuf, errlen);
     if (rc) return rc;
     const int64_t cells = windows * D;
-    if ((rc = ac_text_args(who, text, read_off, read_lens, n_reads, counts, cells, errbuf, errlen))) return rc;
-    if ((rc = ac_device_check(device, errbuf, errlen))) return rc;
+    if ((rc = reads_text_args(who, text, read_off, read_lens, n_reads, cells > 0 && !counts, errbuf, errlen))) return rc;
+    if ((rc = device_check(device, errbuf, errlen))) return rc;
     std::vector<int64_t> off((size_t)n_reads + 1, 0);
     for (int32_t r = 0; r < n_reads; ++r) off[(size_t)r + 1] = off[(size_t)r] + read_lens[r];
     const int64_t bases = off[(size_t)n_reads];
-    hipStream_t st = nullptr;
     try {
         DeviceScope on(device);
-        AcCtx& c = ac_ctx(device);
+        AcCtx& c = device_ctx<AcCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();
-        SD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        OwnedStream st;
         DevBuf<int64_t> d_counts;
         d_counts.alloc((size_t)cells);
         c.text.alloc((size_t)bases);
@@ -414,14 +345,12 @@ int ac_dev(const char* who, const char* text, const int64_t* read_off, const int
             if (read_lens[r] > 0)
                 SD_HIP(hipMemcpyAsync(c.text.p + off[(size_t)r], text + read_off[r], (size_t)read_lens[r], hipMemcpyHostToDevice, st));
         ac_enqueue(c, st, c.text.p, off.data(), read_lens, n_reads, k, D, W, win_off.data(), windows, d_counts.p, bench);
-        ac_used(c, st);
+        c.in_flight(st);
         if (cells) SD_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof(int64_t) * (size_t)cells, hipMemcpyDeviceToHost, st));
         SD_HIP(hipStreamSynchronize(st));
-        c.used = false;   // (the stream has been waited for)
-        (void)hipStreamDestroy(st);
+        c.waited();
         return SD_OK;
     } catch (const HipFail& f) {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
         set_err(errbuf, errlen, f.msg);
         return SD_ERR_HIP;
     }
@@ -446,7 +375,7 @@ int sd_autocorr_host(const char* text, const int64_t* read_off, const int64_t* r
     int64_t windows = 0;
     int rc = ac_limits(who, read_lens, n_reads, k, D, W, win_off.data(), windows, errbuf, errlen);
     if (rc) return rc;
-    if ((rc = ac_text_args(who, text, read_off, read_lens, n_reads, counts, windows * D, errbuf, errlen))) return rc;
+    if ((rc = reads_text_args(who, text, read_off, read_lens, n_reads, windows * D > 0 && !counts, errbuf, errlen))) return rc;
     std::memset(counts, 0, sizeof(int64_t) * (size_t)(windows * D));
     ac_host(reinterpret_cast<const uint8_t*>(text), read_off, read_lens, n_reads, k, D, W, win_off.data(), std::max(1, threads), counts);
     return SD_OK;
@@ -470,19 +399,19 @@ int sd_autocorr_reads_dev(const void* d_text, const int64_t* read_off, const int
     int rc = ac_limits(who, read_lens, n_reads, k, D, W, win_off.data(), windows, errbuf, errlen);
     if (rc) return rc;
     const int64_t cells = windows * D;
-    if ((rc = ac_text_args(who, d_text, read_off, read_lens, n_reads, d_counts, cells, errbuf, errlen))) return rc;
-    if ((rc = ac_device_check(device, errbuf, errlen))) return rc;
+    if ((rc = reads_text_args(who, d_text, read_off, read_lens, n_reads, cells > 0 && !d_counts, errbuf, errlen))) return rc;
+    if ((rc = device_check(device, errbuf, errlen))) return rc;
     for (int32_t r = 0; r < n_reads; ++r) bases += read_lens[r];
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     try {
         DeviceScope on(device);
         if (cells > 0 && (rc = buffer_on_device(d_counts, device, who, "count", errbuf, errlen))) return rc;
         if (bases > 0 && (rc = buffer_on_device(d_text, device, who, "text", errbuf, errlen))) return rc;
-        AcCtx& c = ac_ctx(device);
+        AcCtx& c = device_ctx<AcCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();   // the previous call's kernels read the buffers this one overwrites
         ac_enqueue(c, st, static_cast<const uint8_t*>(d_text), read_off, read_lens, n_reads, k, D, W, win_off.data(), windows, d_counts, nullptr);
-        ac_used(c, st);
+        c.in_flight(st);
         return SD_OK;
     } catch (const HipFail& f) {
         set_err(errbuf, errlen, f.msg);

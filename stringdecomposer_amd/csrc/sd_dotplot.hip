@@ -29,12 +29,10 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <map>
-#include <mutex>
 
 #include "sd_dotplot.hpp"
 #include "sd_host.hpp"
-#include "sd_pipeline.hpp"
+#include "sd_job_dev.hpp"
 
 namespace sd {
 
@@ -317,34 +315,17 @@ namespace {
 
 std::atomic<int64_t> g_dp_launches{0};   // launches of sd_dotplot_pairs in this process (sd_dotplot_info)
 
-// Per device, kept between calls.  The device-resident call returns with its kernels in flight on the caller's stream, so
-// the buffers cannot be the call's own; ev_use is recorded behind the last kernel and the next call on the device waits
-// for it before it touches them.
-struct DpCtx {
-    std::mutex m;
-    DevBuf<int64_t> reads;      // [roff | rlen | win_off | tile_off | cell_off], n_reads + 1 each
+// Per device, kept between calls (sd_job_dev.hpp: DevWork); the per-read tables are
+// [roff | rlen | win_off | tile_off | cell_off].
+struct DpCtx : DevWork, ReadTable {
     DevBuf<int32_t> tcnt, wraw;
     DevBuf<int64_t> toff, woff, summary;
     DevBuf<uint64_t> sets;
     DevBuf<uint8_t> text;       // sd_dotplot_dev: the reads, back to back
     DevBuf<int32_t> out;        // sd_dotplot_dev: kmers | kmers_rc | shared | shared_rc
-    PinBuf<int64_t> h_reads, h_summary;
-    hipEvent_t ev_use = nullptr, ev_sum = nullptr;
-    bool used = false;
-    void settle() {
-        if (used && hipEventSynchronize(ev_use) != hipSuccess) (void)hipGetLastError();
-        used = false;
-    }
+    PinBuf<int64_t> h_summary;
+    hipEvent_t ev_sum = nullptr;
 };
-
-DpCtx& dp_ctx(int device) {
-    static std::mutex m;
-    static std::map<int, DpCtx*>* all = new std::map<int, DpCtx*>;   // (never destroyed: no HIP call at process exit)
-    std::lock_guard<std::mutex> g(m);
-    DpCtx*& c = (*all)[device];
-    if (!c) c = new DpCtx;
-    return *c;
-}
 
 // win_off, cell_off (n_reads + 1 each, may be null) and the totals; SD_ERR_UNSUPPORTED when a count leaves 62 bits
 int dp_layout(const int64_t* read_lens, int32_t n_reads, int64_t W, int64_t B, int64_t* win_off, int64_t* cell_off, int64_t& windows,
@@ -395,25 +376,11 @@ int dp_refuse_set(const char* who, const int64_t* win_off, int32_t n_reads, int6
     return SD_ERR_PARAM;
 }
 
-int dp_device_check(int32_t device, char* errbuf, size_t errlen) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_err(errbuf, errlen, "no usable HIP device"); return SD_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) { set_err(errbuf, errlen, "device " + std::to_string(device) + " does not exist"); return SD_ERR_PARAM; }
-    return SD_OK;
-}
-
+// the text of the reads and, where there are windows or cells, a place for every result
 int dp_text_args(const char* who, const void* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, int rc, int64_t windows,
                  int64_t cells, const void* kmers, const void* kmers_rc, const void* shared, const void* shared_rc, char* errbuf, size_t errlen) {
-    int64_t bases = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (!read_off || read_off[r] < 0) { set_err(errbuf, errlen, std::string(who) + ": missing or negative read offset"); return SD_ERR_PARAM; }
-        bases += read_lens[r];
-    }
-    if ((bases > 0 && !text) || (windows > 0 && (!kmers || (rc && !kmers_rc))) || (cells > 0 && (!shared || (rc && !shared_rc)))) {
-        set_err(errbuf, errlen, std::string(who) + ": missing argument");
-        return SD_ERR_PARAM;
-    }
-    return SD_OK;
+    const bool no_output = (windows > 0 && (!kmers || (rc && !kmers_rc))) || (cells > 0 && (!shared || (rc && !shared_rc)));
+    return reads_text_args(who, text, read_off, read_lens, n_reads, no_output, errbuf, errlen);
 }
 
 // ---- the host form ------------------------------------------------------------------------------------------------------
@@ -493,10 +460,8 @@ struct DpJob {
 // tables up; `a` filled but for the sets and the results
 void dp_tables(DpCtx& c, hipStream_t st, DpJob& j, const uint8_t* d_text, const int64_t* roff, const int64_t* read_lens, int32_t n_reads, int k,
                int64_t W, int64_t B, uint32_t M, int rc, int64_t windows) {
-    const size_t nr = (size_t)n_reads + 1;
-    c.h_reads.alloc(5 * nr);
-    c.reads.alloc(5 * nr);
-    int64_t *h_off = c.h_reads.p, *h_len = h_off + nr, *h_win = h_len + nr, *h_tile = h_win + nr, *h_cell = h_tile + nr;
+    c.shape(5, n_reads);
+    int64_t *h_off = c.h(0), *h_len = c.h(1), *h_win = c.h(2), *h_tile = c.h(3), *h_cell = c.h(4);
     int64_t tiles = 0;
     for (int32_t r = 0; r < n_reads; ++r) {
         h_off[r] = roff[r];
@@ -507,7 +472,7 @@ void dp_tables(DpCtx& c, hipStream_t st, DpJob& j, const uint8_t* d_text, const 
         tiles += sd::dotplot_tiles(read_lens[r], W);
     }
     h_off[n_reads] = 0; h_len[n_reads] = 0; h_win[n_reads] = windows; h_cell[n_reads] = j.cells; h_tile[n_reads] = tiles;
-    SD_HIP(hipMemcpyAsync(c.reads.p, c.h_reads.p, 5 * nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    c.upload(5, st);
     const size_t strands = rc ? 2 : 1;
     c.tcnt.alloc(strands * (size_t)tiles);
     c.toff.alloc(strands * (size_t)tiles + 1);
@@ -515,8 +480,7 @@ void dp_tables(DpCtx& c, hipStream_t st, DpJob& j, const uint8_t* d_text, const 
     c.wraw.alloc(strands * (size_t)windows);
     c.summary.alloc(4);
     c.h_summary.alloc(4);
-    const int64_t* d = c.reads.p;
-    j.a = sd::DpArgs{d_text, d, d + nr, d + 2 * nr, d + 3 * nr, d + 4 * nr, (int)n_reads, k, rc, M, W, B, windows, tiles,
+    j.a = sd::DpArgs{d_text, c.d(0), c.d(1), c.d(2), c.d(3), c.d(4), (int)n_reads, k, rc, M, W, B, windows, tiles,
                      c.tcnt.p, c.toff.p, c.woff.p, c.wraw.p, c.summary.p, nullptr, nullptr, nullptr, nullptr, nullptr};
 }
 
@@ -590,35 +554,12 @@ int dp_begin(const char* who, DpCtx& c, hipStream_t st, DpJob& j, int32_t n_read
     return SD_OK;
 }
 
-void dp_used(DpCtx& c, hipStream_t st) {
-    ensure_event(c.ev_use, hipEventDisableTiming);
-    SD_HIP(hipEventRecord(c.ev_use, st));
-    c.used = true;
-}
-
+// the timed repetitions of the three passes, each on the results of the one before
 void dp_bench(DpJob& j, hipStream_t st, int32_t n_reads, const DpBench& b) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    SD_HIP(hipEventCreate(&e0));
-    SD_HIP(hipEventCreate(&e1));
-    try {
-        for (int pass = 0; pass < 3; ++pass)   // each pass on the results of the one before
-            for (int it = 0; it < b.warmup + b.reps; ++it) {
-                SD_HIP(hipEventRecord(e0, st));
-                if (pass == 0) dp_count(j, st);
-                else if (pass == 1) dp_sets(j, st);
-                else dp_pairs(j, st, n_reads);
-                SD_HIP(hipEventRecord(e1, st));
-                SD_HIP(hipEventSynchronize(e1));
-                float* ms = pass == 0 ? b.ms_count : pass == 1 ? b.ms_sets : b.ms_pairs;
-                if (it >= b.warmup) SD_HIP(hipEventElapsedTime(&ms[it - b.warmup], e0, e1));
-            }
-    } catch (...) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        throw;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    StageClock clock;
+    clock.time(st, b.warmup, b.reps, b.ms_count, [&]() { dp_count(j, st); });
+    clock.time(st, b.warmup, b.reps, b.ms_sets, [&]() { dp_sets(j, st); });
+    clock.time(st, b.warmup, b.reps, b.ms_pairs, [&]() { dp_pairs(j, st, n_reads); });
     b.info[0] = j.launches;
     b.info[1] = j.workgroups;
     b.info[2] = j.cells;
@@ -638,17 +579,16 @@ int dp_dev(const char* who, const char* text, const int64_t* read_off, const int
     if (e) return e;
     rc = rc ? 1 : 0;
     if ((e = dp_text_args(who, text, read_off, read_lens, n_reads, rc, windows, j.cells, kmers, kmers_rc, shared, shared_rc, errbuf, errlen))) return e;
-    if ((e = dp_device_check(device, errbuf, errlen))) return e;
+    if ((e = device_check(device, errbuf, errlen))) return e;
     std::vector<int64_t> off((size_t)n_reads + 1, 0);
     for (int32_t r = 0; r < n_reads; ++r) off[(size_t)r + 1] = off[(size_t)r] + read_lens[r];
     const int64_t bases = off[(size_t)n_reads];
-    hipStream_t st = nullptr;
     try {
         DeviceScope on(device);
-        DpCtx& c = dp_ctx(device);
+        DpCtx& c = device_ctx<DpCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();
-        SD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        OwnedStream st;
         c.text.alloc((size_t)bases);
         for (int32_t r = 0; r < n_reads; ++r)   // the reads back to back, whatever their order and gaps in the caller's buffer
             if (read_lens[r] > 0)
@@ -676,10 +616,8 @@ int dp_dev(const char* who, const char* text, const int64_t* read_off, const int
             }
         }
         SD_HIP(hipStreamSynchronize(st));
-        (void)hipStreamDestroy(st);
         return e;
     } catch (const HipFail& f) {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
         set_err(errbuf, errlen, f.msg);
         return SD_ERR_HIP;
     }
@@ -736,7 +674,7 @@ int sd_dotplot_reads_dev(const void* d_text, const int64_t* read_off, const int6
     rc = rc ? 1 : 0;
     if ((e = dp_text_args(who, d_text, read_off, read_lens, n_reads, rc, windows, j.cells, d_kmers, d_kmers_rc, d_shared, d_shared_rc, errbuf, errlen)))
         return e;
-    if ((e = dp_device_check(device, errbuf, errlen))) return e;
+    if ((e = device_check(device, errbuf, errlen))) return e;
     for (int32_t r = 0; r < n_reads; ++r) bases += read_lens[r];
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     try {
@@ -746,7 +684,7 @@ int sd_dotplot_reads_dev(const void* d_text, const int64_t* read_off, const int6
         if (windows > 0 && rc && (e = buffer_on_device(d_kmers_rc, device, who, "kmers_rc", errbuf, errlen))) return e;
         if (j.cells > 0 && (e = buffer_on_device(d_shared, device, who, "shared", errbuf, errlen))) return e;
         if (j.cells > 0 && rc && (e = buffer_on_device(d_shared_rc, device, who, "shared_rc", errbuf, errlen))) return e;
-        DpCtx& c = dp_ctx(device);
+        DpCtx& c = device_ctx<DpCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();   // the previous call's kernels read the buffers this one overwrites
         dp_tables(c, st, j, static_cast<const uint8_t*>(d_text), read_off, read_lens, n_reads, k, W, B, (uint32_t)M, rc, windows);
@@ -759,7 +697,7 @@ int sd_dotplot_reads_dev(const void* d_text, const int64_t* read_off, const int6
             dp_sets(j, st);
             dp_pairs(j, st, n_reads);
         }
-        dp_used(c, st);
+        c.in_flight(st);
         return e;
     } catch (const HipFail& f) {
         set_err(errbuf, errlen, f.msg);

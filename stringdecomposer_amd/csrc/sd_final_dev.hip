@@ -12,6 +12,7 @@
 // A row the words do not decide (a missing word, a segment edlib aligns by Hirschberg's split) is counted, not guessed.
 #include "sd_convert.hpp"
 #include "sd_final_ws.hpp"
+#include "sd_job_dev.hpp"
 #include "sd_rows_scan_dev.hpp"
 
 namespace sd {
@@ -334,9 +335,7 @@ int sd_final_select_dev(const char* const* mono_names, const char* const* mono_s
     sd::PostProcessor pp;
     int rc = final_entry_pp(pp, mono_names, mono_seqs, mono_lens, n_mono, min_identity, second_best, lr_coef, per);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SD_ERR_NO_DEVICE; }
-    if (device >= ndev) return SD_ERR_PARAM;
+    if ((rc = device_check(device, nullptr, 0))) return rc;   // (device < 0: refused above)
     try {
         SD_HIP(hipSetDevice(device));
         hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);

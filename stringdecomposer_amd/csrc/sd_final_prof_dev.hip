@@ -11,6 +11,7 @@
 // Order inside a group depends on the atomics; the counters are integer sums, so the profile does not.
 #include "sd_final_ws.hpp"
 #include "sd_group_dev.hpp"
+#include "sd_job_dev.hpp"
 
 namespace sd {
 
@@ -352,9 +353,7 @@ int sd_final_profile_dev(const char* text, const int64_t* read_off, int32_t n_re
     int rc = fprof_entry_args(text, read_off, n_reads, rows, row_off, keep, templates, tlen, T, counts, il, own, poff);
     if (rc) return rc;
     if (device < 0) return SD_ERR_PARAM;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SD_ERR_NO_DEVICE; }
-    if (device >= ndev) return SD_ERR_PARAM;
+    if ((rc = device_check(device, nullptr, 0))) return rc;   // (device < 0: refused above)
     hipStream_t st = nullptr;
     try {
         SD_HIP(hipSetDevice(device));

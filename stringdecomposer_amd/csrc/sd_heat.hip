@@ -28,14 +28,13 @@
 // slower per pair than sd_lag_pairs; on an array of 16 384 rows (63.8 lanes) it is faster (the same file).
 #include <algorithm>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
 
 #include "sd_final_ws.hpp"
 #include "sd_group_dev.hpp"
 #include "sd_heat.hpp"
 #include "sd_host.hpp"
+#include "sd_job_dev.hpp"
 #include "sd_nw_kernel.hpp"
 
 namespace sd {
@@ -274,38 +273,15 @@ __global__ __launch_bounds__(HEAT_STRIP, 3) void sd_heat_pairs(HeatArgs a) {
 namespace sdi {
 namespace {
 
-// Per device, kept between calls: segments, plan, grouping, scan and checkpoints.  A device-resident call returns with its
-// kernels in flight on the caller's stream, so the buffers cannot be the call's own; ev_use is recorded behind the last
-// kernel and the next call on the device waits for it before it touches them.
-struct HeatCtx {
-    std::mutex m;
-    DevBuf<uint8_t> text, cls, ck;
-    DevBuf<int64_t> seg_start, reads, grp, scan, bsum, bound;   // reads: [roff | rlen | toff]; grp: [group_off | cell_off]
+// Per device, kept between calls (sd_job_dev.hpp: DevWork): text, segments, plan, grouping, scan and checkpoints.
+struct HeatCtx : DevWork, FinalText {
+    DevBuf<uint8_t> cls, ck;
+    DevBuf<int64_t> seg_start, grp, scan, bsum, bound;   // grp: [group_off | cell_off]
     DevBuf<int32_t> seg_len, seg_grp, strips, order, sum, base, cursor, per_read;
-    PinBuf<int64_t> h_reads, h_grp, h_bound;
+    PinBuf<int64_t> h_grp, h_bound;
     PinBuf<int32_t> h_sum, h_len, h_per_read;
-    hipEvent_t ev_plan = nullptr, ev_use = nullptr;
-    bool used = false;
-    int n_cu = 256;
-    void settle() {
-        if (used && hipEventSynchronize(ev_use) != hipSuccess) (void)hipGetLastError();
-        used = false;
-    }
+    hipEvent_t ev_plan = nullptr;
 };
-
-HeatCtx& heat_ctx(int device) {
-    static std::mutex m;
-    static std::map<int, HeatCtx*>* all = new std::map<int, HeatCtx*>;   // (never destroyed: no HIP call at process exit)
-    std::lock_guard<std::mutex> g(m);
-    HeatCtx*& c = (*all)[device];
-    if (!c) {
-        c = new HeatCtx;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
-        else (void)hipGetLastError();
-    }
-    return *c;
-}
 
 inline unsigned heat_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, (items + sd::HEAT_T - 1) / sd::HEAT_T); }
 
@@ -445,39 +421,6 @@ int heat_host(const HeatJob& j, int which, int threads, int64_t* sums) {
     return flush();
 }
 
-// the checked segments of the segment calls: start (in seq + lo) / length per segment
-int heat_segment_args(const char* who, const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg,
-                      const int64_t* group_off, int32_t n_groups, int64_t* sums, std::vector<int64_t>& st, std::vector<int32_t>& ln,
-                      int64_t& lo, int64_t& hi, char* errbuf, size_t errlen) {
-    if (n_seg < 0 || n_groups < 0 || seqlen < 0 || !group_off || !sums || (seqlen > 0 && !seq) || (n_seg > 0 && (!starts || !ends))) {
-        set_err(errbuf, errlen, std::string(who) + ": missing argument");
-        return SD_ERR_PARAM;
-    }
-    if (group_off[0] != 0 || group_off[n_groups] != n_seg) { set_err(errbuf, errlen, std::string(who) + ": the groups do not cover the segments"); return SD_ERR_PARAM; }
-    if (n_seg >= ((int64_t)1 << 31)) { set_err(errbuf, errlen, std::string(who) + ": 2^31 segments or more"); return SD_ERR_UNSUPPORTED; }
-    st.resize((size_t)n_seg);
-    ln.resize((size_t)n_seg);
-    lo = seqlen;
-    hi = 0;
-    for (int64_t s = 0; s < n_seg; ++s) {
-        if (starts[s] < 0 || ends[s] >= seqlen) { set_err(errbuf, errlen, std::string(who) + ": segment " + std::to_string(s) + " lies outside the text"); return SD_ERR_PARAM; }
-        const int64_t l = std::max<int64_t>(0, ends[s] - starts[s] + 1);
-        if (l >= ((int64_t)1 << 27)) { set_err(errbuf, errlen, std::string(who) + ": a segment of 2^27 bases or more"); return SD_ERR_UNSUPPORTED; }
-        ln[(size_t)s] = (int32_t)l;
-        if (l > 0) { lo = std::min(lo, starts[s]); hi = std::max(hi, ends[s] + 1); }
-    }
-    if (hi < lo) { lo = 0; hi = 0; }
-    for (int64_t s = 0; s < n_seg; ++s) st[(size_t)s] = ln[(size_t)s] > 0 ? starts[s] - lo : 0;
-    return SD_OK;
-}
-
-int heat_device_check(int32_t device, char* errbuf, size_t errlen) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_err(errbuf, errlen, "no usable HIP device"); return SD_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) { set_err(errbuf, errlen, "device " + std::to_string(device) + " does not exist"); return SD_ERR_PARAM; }
-    return SD_OK;
-}
-
 // ---- the device passes --------------------------------------------------------------------------------------------------
 // plan + grouping + scan on st over the segments in c (seg_len, seg_grp, grp); the summary and the classes' item bounds on
 // their way to c.h_sum / c.h_bound, ev_plan recorded
@@ -541,23 +484,10 @@ void heat_walk(HeatCtx& c, hipStream_t st, const HeatLaunch& L, int32_t n_groups
     const sd::HeatArgs a{c.text.p, c.seg_start.p, c.seg_len.p, c.seg_grp.p, c.grp.p, c.grp.p + n_groups + 1, c.order.p + L.first,
                          c.scan.p + L.first, L.count, L.items, B, W, L.cap, reinterpret_cast<uint32_t*>(c.ck.p),
                          reinterpret_cast<unsigned long long*>(d_sums), c.sum.p + sd::HEAT_SUM_FAIL, mode};
-#define SD_HEAT(KK) hipLaunchKernelGGL(sd::sd_heat_pairs<KK>, dim3(L.grid), dim3(sd::HEAT_STRIP), 0, st, a)
-    switch (L.K) {
-        case 1: SD_HEAT(1); break;
-        case 2: SD_HEAT(2); break;
-        case 3: SD_HEAT(3); break;
-        case 4: SD_HEAT(4); break;
-        case 6: SD_HEAT(6); break;
-        default: SD_HEAT(8); break;
-    }
-#undef SD_HEAT
+    with_words(L.K, [&](auto words) {
+        hipLaunchKernelGGL(sd::sd_heat_pairs<decltype(words)::value>, dim3(L.grid), dim3(sd::HEAT_STRIP), 0, st, a);
+    });
     SD_HIP(hipGetLastError());
-}
-
-void heat_used(HeatCtx& c, hipStream_t st) {
-    ensure_event(c.ev_use, hipEventDisableTiming);
-    SD_HIP(hipEventRecord(c.ev_use, st));
-    c.used = true;
 }
 
 // group_off | cell_off of the job, pinned, on their way to c.grp
@@ -591,16 +521,13 @@ int sd_heat_segments(const char* seq, int64_t seqlen, const int64_t* starts, con
     std::vector<int64_t> st, coff((size_t)std::max(n_groups, 0) + 1);
     std::vector<int32_t> ln;
     int64_t lo = 0, hi = 0, cells = 0, pairs = 0;
-    int rc = heat_segment_args(who, seq, seqlen, starts, ends, n_seg, group_off, n_groups, sums, st, ln, lo, hi, errbuf, errlen);
+    int rc = segment_args(who, seq, seqlen, starts, ends, n_seg, group_off, n_groups, sums, (int64_t)1 << 31, "2^31 segments or more", st, ln,
+                          nullptr, lo, hi, errbuf, errlen);
     if (rc) return rc;
     if ((rc = heat_limits(who, group_off, n_groups, B, W, max_pairs, coff.data(), cells, pairs, errbuf, errlen))) return rc;
     std::memset(sums, 0, sizeof(int64_t) * 3 * (size_t)cells);
     const HeatJob j{seq + lo, st.data(), ln.data(), group_off, coff.data(), n_groups, B, W};
-    if (which == 1) {   // (a text outside ACGTN: every pair is the host's)
-        bool acgtn = true;
-        for (int64_t i = 0; i < hi - lo && acgtn; ++i) acgtn = j.text[i] == 'A' || j.text[i] == 'C' || j.text[i] == 'G' || j.text[i] == 'T' || j.text[i] == 'N';
-        if (!acgtn) which = 0;
-    }
+    if (which == 1 && !text_is_acgtn(j.text, hi - lo)) which = 0;   // (a text outside ACGTN: every pair is the host's)
     if ((rc = heat_host(j, which, threads, sums))) set_err(errbuf, errlen, std::string(who) + ": the host alignment failed");
     return rc;
 } catch (const std::bad_alloc&) {
@@ -618,18 +545,18 @@ static int heat_segments_dev(const char* who, const char* seq, int64_t seqlen, c
                              const int64_t* group_off, int32_t n_groups, int64_t B, int64_t W, int64_t max_pairs, int32_t device,
                              int32_t threads, int64_t* sums, int64_t classes[3], char* errbuf, size_t errlen, const sd_heat_bench* bench) {
     std::vector<int64_t> sst, coff((size_t)std::max(n_groups, 0) + 1);
-    std::vector<int32_t> ln;
+    std::vector<int32_t> ln, grp;
     int64_t lo = 0, hi = 0, cells = 0, pairs = 0;
-    int rc = heat_segment_args(who, seq, seqlen, starts, ends, n_seg, group_off, n_groups, sums, sst, ln, lo, hi, errbuf, errlen);
+    int rc = segment_args(who, seq, seqlen, starts, ends, n_seg, group_off, n_groups, sums, (int64_t)1 << 31, "2^31 segments or more", sst, ln,
+                          &grp, lo, hi, errbuf, errlen);
     if (rc) return rc;
     if ((rc = heat_limits(who, group_off, n_groups, B, W, max_pairs, coff.data(), cells, pairs, errbuf, errlen))) return rc;
-    if ((rc = heat_device_check(device, errbuf, errlen))) return rc;
+    if ((rc = device_check(device, errbuf, errlen))) return rc;
     std::memset(sums, 0, sizeof(int64_t) * 3 * (size_t)cells);
     const int64_t text = hi - lo;
     const char* tx = seq + lo;
     const HeatJob j{tx, sst.data(), ln.data(), group_off, coff.data(), n_groups, B, W};
-    bool acgtn = true;
-    for (int64_t i = 0; i < text && acgtn; ++i) acgtn = tx[i] == 'A' || tx[i] == 'C' || tx[i] == 'G' || tx[i] == 'T' || tx[i] == 'N';
+    const bool acgtn = text_is_acgtn(tx, text);
     int64_t cl[3];
     heat_classes(j, acgtn, cl);
     if (classes) { classes[0] = cl[0]; classes[1] = cl[1]; classes[2] = cl[2]; }
@@ -638,17 +565,12 @@ static int heat_segments_dev(const char* who, const char* seq, int64_t seqlen, c
         if ((rc = heat_host(j, 0, threads, sums))) set_err(errbuf, errlen, std::string(who) + ": the host alignment failed");
         return rc;
     }
-    std::vector<int32_t> grp((size_t)n_seg);
-    for (int32_t g = 0; g < n_groups; ++g)
-        for (int64_t s = group_off[g]; s < group_off[g + 1]; ++s) grp[(size_t)s] = g;
-    hipStream_t st = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     try {
         DeviceScope on(device);
-        HeatCtx& c = heat_ctx(device);
+        HeatCtx& c = device_ctx<HeatCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();
-        SD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        OwnedStream st;
         DevBuf<int64_t> d_sums;
         const size_t n_sums = (size_t)cells * 3;
         c.text.alloc((size_t)text + 8);
@@ -663,45 +585,32 @@ static int heat_segments_dev(const char* who, const char* seq, int64_t seqlen, c
         SD_HIP(hipMemcpyAsync(c.seg_len.p, ln.data(), sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice, st));
         SD_HIP(hipMemcpyAsync(c.seg_grp.p, grp.data(), sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice, st));
         heat_upload_groups(c, st, group_off, coff.data(), n_groups);
-        SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st));
-        if (bench) {
-            SD_HIP(hipEventCreate(&e0));
-            SD_HIP(hipEventCreate(&e1));
-            for (int it = 0; it < bench->warmup + bench->reps; ++it) {   // plan, scatter and scan
-                SD_HIP(hipEventRecord(e0, st));
-                heat_plan(c, st, n_seg, n_groups, W, true);
-                SD_HIP(hipEventRecord(e1, st));
-                SD_HIP(hipEventSynchronize(e1));
-                if (it >= bench->warmup) SD_HIP(hipEventElapsedTime(&bench->ms_group[it - bench->warmup], e0, e1));
-            }
-        } else {
-            heat_plan(c, st, n_seg, n_groups, W, true);
-        }
+        StageClock clock;
+        const auto clear_sums = [&]() { SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st)); };
+        clear_sums();
+        const auto plan = [&]() { heat_plan(c, st, n_seg, n_groups, W, true); };   // plan, scatter and scan
+        if (bench) clock.time(st, bench->warmup, bench->reps, bench->ms_group, plan);
+        else plan();
         SD_HIP(hipEventSynchronize(c.ev_plan));
         const std::vector<HeatLaunch> launches = heat_launches(c);
         if (bench) {
             int64_t items = 0, Kmost = 0, imost = -1;
             for (const HeatLaunch& L : launches) { items += L.items; if (L.items > imost) { imost = L.items; Kmost = L.K; } }
             for (int pass = 0; pass < 2; ++pass)   // the whole kernel, then the walk alone: masks built once per wave, no sink
-                for (int it = 0; it < bench->warmup + bench->reps; ++it) {
-                    SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st));
-                    SD_HIP(hipEventRecord(e0, st));
+                clock.time(st, bench->warmup, bench->reps, pass == 0 ? bench->ms_pairs : bench->ms_walk, [&]() {
                     for (const HeatLaunch& L : launches)
                         heat_walk(c, st, L, n_groups, B, W, d_sums.p, pass == 0 ? 0 : sd::HEAT_MODE_KEEP_MASKS | sd::HEAT_MODE_NO_SINK);
-                    SD_HIP(hipEventRecord(e1, st));
-                    SD_HIP(hipEventSynchronize(e1));
-                    if (it >= bench->warmup) SD_HIP(hipEventElapsedTime(&(pass == 0 ? bench->ms_pairs : bench->ms_walk)[it - bench->warmup], e0, e1));
-                }
+                }, clear_sums);
             bench->info[0] = cl[0];
             bench->info[1] = cl[1];
             bench->info[2] = Kmost;
             bench->info[3] = items;
             bench->info[4] = cells;
             for (const HeatLaunch& L : launches) if (L.K == Kmost) { bench->info[5] = L.items; bench->info[6] = L.grid; bench->info[7] = L.cap; }
-            SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st));
+            clear_sums();
         }
         for (const HeatLaunch& L : launches) heat_walk(c, st, L, n_groups, B, W, d_sums.p, 0);
-        heat_used(c, st);
+        c.in_flight(st);
         // the host's pairs, under the kernel
         std::vector<int64_t> hsums;
         int hrc = SD_OK;
@@ -713,17 +622,12 @@ static int heat_segments_dev(const char* who, const char* seq, int64_t seqlen, c
         SD_HIP(hipStreamSynchronize(st));
         int32_t fails = 0;
         SD_HIP(hipMemcpy(&fails, c.sum.p + sd::HEAT_SUM_FAIL, sizeof fails, hipMemcpyDeviceToHost));
-        c.used = false;   // (the stream has been waited for)
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        (void)hipStreamDestroy(st);
-        st = nullptr;
+        c.waited();
         if (hrc) { set_err(errbuf, errlen, std::string(who) + ": the host alignment failed"); return hrc; }
         for (size_t i = 0; i < hsums.size(); ++i) sums[i] += hsums[i];
         if (fails) { set_err(errbuf, errlen, std::string(who) + ": " + std::to_string(fails) + " pairs ran out of checkpoint slots"); return SD_ERR_INTERNAL; }
         return SD_OK;
     } catch (const HipFail& f) {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
         set_err(errbuf, errlen, f.msg);
         return SD_ERR_HIP;
     }
@@ -788,7 +692,6 @@ int sd_heat_final_host(const sd_final_row* rows, int64_t n_rows, const char* tex
     if (rc) return rc;
     if ((rc = heat_limits(who, goff.data(), n_reads, B, W, max_pairs, coff.data(), cells, pairs, errbuf, errlen))) return rc;
     if (cells != n_cells) { set_err(errbuf, errlen, std::string(who) + ": " + std::to_string(cells) + " cells, the caller's sums hold " + std::to_string(n_cells)); return SD_ERR_PARAM; }
-    bool acgtn = true;
     for (int64_t i = 0; i < n_rows; ++i) {
         const int32_t r = rows[i].read;
         st[(size_t)i] = read_off[r] + sd::final_seg_first(rows[i].start, read_lens[r]);
@@ -796,11 +699,8 @@ int sd_heat_final_host(const sd_final_row* rows, int64_t n_rows, const char* tex
         if (l >= (1 << 27)) { set_err(errbuf, errlen, std::string(who) + ": a segment of 2^27 bases or more"); return SD_ERR_UNSUPPORTED; }
         ln[(size_t)i] = (int32_t)l;
     }
-    for (int32_t r = 0; r < n_reads && acgtn; ++r)
-        for (int64_t i = 0; i < read_lens[r] && acgtn; ++i) {
-            const char ch = text[read_off[r] + i];
-            acgtn = ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T' || ch == 'N';
-        }
+    bool acgtn = true;
+    for (int32_t r = 0; r < n_reads && acgtn; ++r) acgtn = text_is_acgtn(text + read_off[r], read_lens[r]);
     std::memset(sums, 0, sizeof(int64_t) * 3 * (size_t)cells);
     const HeatJob j{text, st.data(), ln.data(), goff.data(), coff.data(), n_reads, B, W};
     if (classes) heat_classes(j, acgtn, classes);
@@ -825,26 +725,19 @@ int sd_heat_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_
         return SD_ERR_PARAM;
     }
     int64_t text = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (read_off[r] < 0 || read_lens[r] < 0) { set_err(errbuf, errlen, std::string(who) + ": negative read offset or length"); return SD_ERR_PARAM; }
-        text += read_lens[r];
-    }
-    if (text > 0 && !d_text) { set_err(errbuf, errlen, std::string(who) + ": missing text"); return SD_ERR_PARAM; }
-    int rc = heat_device_check(device, errbuf, errlen);
+    int rc = final_reads_args(who, d_text, read_off, read_lens, n_reads, text, errbuf, errlen);
     if (rc) return rc;
+    if ((rc = device_check(device, errbuf, errlen))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     try {
         DeviceScope on(device);
         if (n_rows > 0 && (rc = buffer_on_device(d_rows, device, who, "row", errbuf, errlen))) return rc;
         if (n_cells > 0 && (rc = buffer_on_device(d_sums, device, who, "sum", errbuf, errlen))) return rc;
         if (text > 0 && (rc = buffer_on_device(d_text, device, who, "text", errbuf, errlen))) return rc;
-        HeatCtx& c = heat_ctx(device);
+        HeatCtx& c = device_ctx<HeatCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();   // the previous call's kernels read the buffers this one overwrites
         const size_t nr = (size_t)n_reads + 1;
-        c.h_reads.alloc(3 * nr);
-        c.reads.alloc(3 * nr);
-        c.text.alloc((size_t)text + 8);
         c.seg_start.alloc((size_t)n_rows);
         c.seg_len.alloc((size_t)n_rows);
         c.seg_grp.alloc((size_t)n_rows);
@@ -853,17 +746,11 @@ int sd_heat_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_
         c.h_len.alloc((size_t)n_rows);
         c.sum.alloc(sd::HEAT_SUM_N);
         c.h_sum.alloc(sd::HEAT_SUM_N);
-        int64_t* roff = c.h_reads.p, *rlen = roff + nr, *toff = rlen + nr;
-        int64_t at = 0;
-        for (int32_t r = 0; r < n_reads; ++r) { roff[r] = read_off[r]; rlen[r] = read_lens[r]; toff[r] = at; at += read_lens[r]; }
-        roff[n_reads] = 0; rlen[n_reads] = 0; toff[n_reads] = at;
-        SD_HIP(hipMemcpyAsync(c.reads.p, c.h_reads.p, 3 * nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        final_text_gather(c, st, d_text, read_off, read_lens, n_reads, text);
         SD_HIP(hipMemsetAsync(c.sum.p, 0, sd::HEAT_SUM_N * sizeof(int32_t), st));
         SD_HIP(hipMemsetAsync(c.per_read.p, 0, nr * sizeof(int32_t), st));
-        SD_HIP(hipMemsetAsync(c.text.p + text, 0, 8, st));
-        sd::launch_text_gather(st, static_cast<const uint8_t*>(d_text), c.reads.p, c.reads.p + 2 * nr, (int)n_reads, text, c.text.p);
         if (n_rows > 0) {
-            sd::HeatRowsArgs a{d_rows, n_rows, c.reads.p + nr, c.reads.p + 2 * nr, (int)n_reads, c.seg_start.p, c.seg_len.p, c.seg_grp.p,
+            sd::HeatRowsArgs a{d_rows, n_rows, c.rlen(), c.toff(), (int)n_reads, c.seg_start.p, c.seg_len.p, c.seg_grp.p,
                                c.per_read.p, c.sum.p};
             hipLaunchKernelGGL(sd::sd_heat_rows, dim3(heat_grid(n_rows)), dim3(sd::HEAT_T), 0, st, a);
             SD_HIP(hipGetLastError());
@@ -871,7 +758,7 @@ int sd_heat_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_
         }
         SD_HIP(hipMemcpyAsync(c.h_per_read.p, c.per_read.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         SD_HIP(hipMemcpyAsync(c.h_sum.p, c.sum.p, sd::HEAT_SUM_N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        heat_used(c, st);
+        c.in_flight(st);
         SD_HIP(hipStreamSynchronize(st));   // the first wait: rows per read and the rows' lengths, for the closed forms
         if (c.h_sum.p[sd::HEAT_SUM_BAD] || c.h_sum.p[sd::HEAT_SUM_ORDER]) {
             set_err(errbuf, errlen, std::string(who) + ": " + std::to_string(c.h_sum.p[sd::HEAT_SUM_BAD]) + " rows with a read index outside the reads, " +
@@ -893,11 +780,11 @@ int sd_heat_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_
         if (classes) { classes[0] = cl[0]; classes[1] = cl[1]; classes[2] = cl[2]; }
         heat_upload_groups(c, st, goff.data(), coff.data(), n_reads);
         heat_plan(c, st, n_rows, n_reads, W, false);
-        heat_used(c, st);
+        c.in_flight(st);
         SD_HIP(hipEventSynchronize(c.ev_plan));   // the second wait: targets and work items per class, which size the launches
         c.settle();   // (nothing behind the plan yet: the checkpoints may grow)
         for (const HeatLaunch& L : heat_launches(c)) heat_walk(c, st, L, n_reads, B, W, d_sums, 0);
-        heat_used(c, st);
+        c.in_flight(st);
         return SD_OK;
     } catch (const HipFail& f) {
         set_err(errbuf, errlen, f.msg);

@@ -20,13 +20,12 @@
 // leave two / one).
 #include <algorithm>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <mutex>
 
 #include "sd_final_ws.hpp"
 #include "sd_group_dev.hpp"
 #include "sd_host.hpp"
+#include "sd_job_dev.hpp"
 #include "sd_lags.hpp"
 #include "sd_nw_kernel.hpp"
 
@@ -204,38 +203,14 @@ __global__ __launch_bounds__(lag_threads<K>(), K <= 4 ? 3 : 1) void sd_lag_pairs
 namespace sdi {
 namespace {
 
-// Per device, kept between calls: the plan, the grouping and the checkpoints.  A device-resident call returns with its
-// kernels in flight on the caller's stream, so the buffers cannot be the call's own; ev_use is recorded behind the last
-// kernel and the next call on the device waits for it before it touches them.
-struct LagCtx {
-    std::mutex m;
-    DevBuf<uint8_t> text, cls, ck;
-    DevBuf<int64_t> seg_start, reads;        // reads: [roff | rlen | toff] (n_reads + 1 each)
+// Per device, kept between calls (sd_job_dev.hpp: DevWork): the text, the plan, the grouping and the checkpoints.
+struct LagCtx : DevWork, FinalText {
+    DevBuf<uint8_t> cls, ck;
+    DevBuf<int64_t> seg_start;
     DevBuf<int32_t> seg_len, seg_read, order, hlist, sum, base, cursor;
-    PinBuf<int64_t> h_reads;
     PinBuf<int32_t> h_sum;
-    hipEvent_t ev_plan = nullptr, ev_use = nullptr;
-    bool used = false;
-    int n_cu = 256;
-    void settle() {
-        if (used && hipEventSynchronize(ev_use) != hipSuccess) (void)hipGetLastError();
-        used = false;
-    }
+    hipEvent_t ev_plan = nullptr;
 };
-
-LagCtx& lag_ctx(int device) {
-    static std::mutex m;
-    static std::map<int, LagCtx*>* all = new std::map<int, LagCtx*>;   // (never destroyed: no HIP call at process exit)
-    std::lock_guard<std::mutex> g(m);
-    LagCtx*& c = (*all)[device];
-    if (!c) {
-        c = new LagCtx;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
-        else (void)hipGetLastError();
-    }
-    return *c;
-}
 
 inline unsigned lag_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, (items + sd::LAG_T - 1) / sd::LAG_T); }
 
@@ -289,26 +264,13 @@ std::vector<LagLaunch> lag_launches(LagCtx& c) {
 }
 
 void lag_walk(LagCtx& c, hipStream_t st, const LagLaunch& L, int D, int32_t* d_dist, int32_t* d_matches, int64_t* d_sums) {
-#define SD_LAG(KK)                                                                                                              \
-    hipLaunchKernelGGL(sd::sd_lag_pairs<KK>, dim3(L.grid), dim3(sd::lag_threads<KK>()), 0, st, c.text.p, c.seg_start.p, c.seg_len.p, \
-                       c.seg_read.p, c.order.p + L.first, L.count, D, L.cap, reinterpret_cast<uint32_t*>(c.ck.p), d_dist, d_matches,  \
-                       reinterpret_cast<unsigned long long*>(d_sums), c.sum.p + sd::LAG_SUM_FAIL)
-    switch (L.K) {
-        case 1: SD_LAG(1); break;
-        case 2: SD_LAG(2); break;
-        case 3: SD_LAG(3); break;
-        case 4: SD_LAG(4); break;
-        case 6: SD_LAG(6); break;
-        default: SD_LAG(8); break;
-    }
-#undef SD_LAG
+    with_words(L.K, [&](auto words) {
+        constexpr int K = decltype(words)::value;
+        hipLaunchKernelGGL(sd::sd_lag_pairs<K>, dim3(L.grid), dim3(sd::lag_threads<K>()), 0, st, c.text.p, c.seg_start.p, c.seg_len.p,
+                           c.seg_read.p, c.order.p + L.first, L.count, D, L.cap, reinterpret_cast<uint32_t*>(c.ck.p), d_dist, d_matches,
+                           reinterpret_cast<unsigned long long*>(d_sums), c.sum.p + sd::LAG_SUM_FAIL);
+    });
     SD_HIP(hipGetLastError());
-}
-
-void lag_used(LagCtx& c, hipStream_t st) {
-    ensure_event(c.ev_use, hipEventDisableTiming);
-    SD_HIP(hipEventRecord(c.ev_use, st));
-    c.used = true;
 }
 
 // ---- the host form --------------------------------------------------------------------------------------------------
@@ -352,41 +314,21 @@ void lag_host_sums(const int32_t* seg_read, int64_t n_seg, int D, const int32_t*
     else for (int64_t p = 0; p < n_seg * D; ++p) add(p);
 }
 
-// the checked segments of the two segment calls: start (in seq + lo) / len / group per segment
+// the checked segments of the two segment calls: start (in seq + lo) / len / group per segment, sums zeroed
 int lag_segment_args(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends, int64_t n_seg, const int64_t* group_off,
                      int32_t n_groups, int32_t D, int32_t* dist, int32_t* matches, int64_t* sums,
                      std::vector<int64_t>& st, std::vector<int32_t>& ln, std::vector<int32_t>& rd, int64_t& lo, int64_t& hi) {
-    if (!sd::lag_d_ok(D)) return SD_ERR_PARAM;
-    if (n_seg < 0 || n_groups < 0 || seqlen < 0 || !group_off || !sums || (seqlen > 0 && !seq) || (n_seg > 0 && (!starts || !ends || !dist || !matches)))
-        return SD_ERR_PARAM;
-    if (group_off[0] != 0 || group_off[n_groups] != n_seg) return SD_ERR_PARAM;
-    for (int32_t g = 0; g < n_groups; ++g)
-        if (group_off[g + 1] < group_off[g]) return SD_ERR_PARAM;
-    if (n_seg * (int64_t)D >= ((int64_t)1 << 31)) return SD_ERR_UNSUPPORTED;
-    st.resize((size_t)n_seg);
-    ln.resize((size_t)n_seg);
-    rd.resize((size_t)n_seg);
-    lo = seqlen;
-    hi = 0;
-    for (int64_t s = 0; s < n_seg; ++s) {
-        if (starts[s] < 0 || ends[s] >= seqlen) return SD_ERR_PARAM;
-        const int64_t l = std::max<int64_t>(0, ends[s] - starts[s] + 1);
-        if (l >= ((int64_t)1 << 27)) return SD_ERR_UNSUPPORTED;
-        ln[(size_t)s] = (int32_t)l;
-        if (l > 0) { lo = std::min(lo, starts[s]); hi = std::max(hi, ends[s] + 1); }
-    }
-    if (hi < lo) { lo = 0; hi = 0; }
-    for (int64_t s = 0; s < n_seg; ++s) st[(size_t)s] = ln[(size_t)s] > 0 ? starts[s] - lo : 0;
-    for (int32_t g = 0; g < n_groups; ++g)
-        for (int64_t s = group_off[g]; s < group_off[g + 1]; ++s) rd[(size_t)s] = g;
+    if (!sd::lag_d_ok(D) || (n_seg > 0 && (!dist || !matches))) return SD_ERR_PARAM;
+    if (group_off && n_groups >= 0)
+        for (int32_t g = 0; g < n_groups; ++g)
+            if (group_off[g + 1] < group_off[g]) return SD_ERR_PARAM;
+    // (no errbuf in the C-ABI of these calls: the codes alone)
+    const int64_t limit = (((int64_t)1 << 31) + D - 1) / D;
+    const int rc = segment_args("sd_lag_segments", seq, seqlen, starts, ends, n_seg, group_off, n_groups, sums, limit,
+                                "segments x D must stay below 2^31", st, ln, &rd, lo, hi, nullptr, 0);
+    if (rc) return rc;
     std::memset(sums, 0, sizeof(int64_t) * 3 * (size_t)n_groups * (size_t)D);
     return SD_OK;
-}
-
-int lag_device_check(int32_t device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SD_ERR_NO_DEVICE; }
-    return device < 0 || device >= ndev ? SD_ERR_PARAM : SD_OK;
 }
 
 }  // namespace
@@ -424,25 +366,22 @@ static int lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* star
     int64_t lo = 0, hi = 0;
     int rc = lag_segment_args(seq, seqlen, starts, ends, n_seg, group_off, n_groups, D, dist, matches, sums, sst, ln, rd, lo, hi);
     if (rc) return rc;
-    if ((rc = lag_device_check(device))) return rc;
+    if ((rc = device_check(device, nullptr, 0))) return rc;
     if (n_seg == 0) return SD_OK;
     const int64_t n_pairs = n_seg * D, text = hi - lo;
     const char* tx = seq + lo;
-    bool acgtn = true;
-    for (int64_t i = 0; i < text && acgtn; ++i) acgtn = tx[i] == 'A' || tx[i] == 'C' || tx[i] == 'G' || tx[i] == 'T' || tx[i] == 'N';
-    if (!acgtn) {   // a byte the lane kernel does not read: every pair is the host's
+    if (!text_is_acgtn(tx, text)) {   // a byte the lane kernel does not read: every pair is the host's
         if (bench) return SD_ERR_UNSUPPORTED;
         rc = lag_host_pairs(tx, sst.data(), ln.data(), rd.data(), n_seg, D, nullptr, 0, threads, dist, matches);
         if (rc == SD_OK) lag_host_sums(rd.data(), n_seg, D, nullptr, 0, dist, matches, sums);
         return rc;
     }
-    hipStream_t st = nullptr;
     try {
         DeviceScope on(device);
-        LagCtx& c = lag_ctx(device);
+        LagCtx& c = device_ctx<LagCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();
-        SD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        OwnedStream st;
         DevBuf<int32_t> d_dist, d_matches;
         DevBuf<int64_t> d_sums;
         const size_t n_sums = (size_t)n_groups * D * 3;
@@ -459,21 +398,12 @@ static int lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* star
         SD_HIP(hipMemcpyAsync(c.seg_start.p, sst.data(), sizeof(int64_t) * (size_t)n_seg, hipMemcpyHostToDevice, st));
         SD_HIP(hipMemcpyAsync(c.seg_len.p, ln.data(), sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice, st));
         SD_HIP(hipMemcpyAsync(c.seg_read.p, rd.data(), sizeof(int32_t) * (size_t)n_seg, hipMemcpyHostToDevice, st));
-        SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (bench) {
-            SD_HIP(hipEventCreate(&e0));
-            SD_HIP(hipEventCreate(&e1));
-            for (int it = 0; it < bench->warmup + bench->reps; ++it) {   // plan, scan and scatter
-                SD_HIP(hipEventRecord(e0, st));
-                lag_plan(c, st, n_seg, D, d_dist.p, d_matches.p, true);
-                SD_HIP(hipEventRecord(e1, st));
-                SD_HIP(hipEventSynchronize(e1));
-                if (it >= bench->warmup) SD_HIP(hipEventElapsedTime(&bench->ms_group[it - bench->warmup], e0, e1));
-            }
-        } else {
-            lag_plan(c, st, n_seg, D, d_dist.p, d_matches.p, true);
-        }
+        StageClock clock;
+        const auto clear_sums = [&]() { SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st)); };
+        clear_sums();
+        const auto plan = [&]() { lag_plan(c, st, n_seg, D, d_dist.p, d_matches.p, true); };   // plan, scan and scatter
+        if (bench) clock.time(st, bench->warmup, bench->reps, bench->ms_group, plan);
+        else plan();
         SD_HIP(hipEventSynchronize(c.ev_plan));
         const std::vector<LagLaunch> launches = lag_launches(c);
         const int64_t nh = c.h_sum.p[sd::LAG_SUM_HOST];
@@ -482,16 +412,11 @@ static int lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* star
         if (bench) {
             int64_t nd = 0, Kmost = 0, cmost = -1;
             for (const LagLaunch& L : launches) { nd += L.count; if (L.count > cmost) { cmost = L.count; Kmost = L.K; } }
-            if (nd == 0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(st); return SD_ERR_UNSUPPORTED; }
+            if (nd == 0) return SD_ERR_UNSUPPORTED;
             for (int pass = 0; pass < 2; ++pass)   // with the reduction, then the walk alone
-                for (int it = 0; it < bench->warmup + bench->reps; ++it) {
-                    SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st));
-                    SD_HIP(hipEventRecord(e0, st));
+                clock.time(st, bench->warmup, bench->reps, pass == 0 ? bench->ms_pairs : bench->ms_walk, [&]() {
                     for (const LagLaunch& L : launches) lag_walk(c, st, L, D, d_dist.p, d_matches.p, pass == 0 ? d_sums.p : nullptr);
-                    SD_HIP(hipEventRecord(e1, st));
-                    SD_HIP(hipEventSynchronize(e1));
-                    if (it >= bench->warmup) SD_HIP(hipEventElapsedTime(&(pass == 0 ? bench->ms_pairs : bench->ms_walk)[it - bench->warmup], e0, e1));
-                }
+                }, clear_sums);
             // the yardstick: the light identity kernel (sd_nw_pairs: one template per segment) on as many pairs -- every
             // pair's query against the first target of the most frequent class as the one template, its masks in LDS
             int32_t first_p = 0, first_at = 0;
@@ -524,15 +449,11 @@ static int lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* star
                 d_m.alloc((size_t)n_seg);
                 d_ck.alloc((size_t)lanes * cap * K * 16);
                 d_ckpos.alloc((size_t)lanes * cap);
-                for (int it = 0; it < bench->warmup + bench->reps; ++it) {
-                    SD_HIP(hipEventRecord(e0, st));
+                clock.time(st, bench->warmup, bench->reps, bench->ms_ident, [&]() {
                     sd::launch_nw_pairs(K, st, (int)(lanes / 256), c.text.p, c.seg_start.p, c.seg_len.p, d_idx.p, nd, 1, d_pt.p, d_peq.p, d_tl.p,
                                         0, cap, d_ck.p, d_ckpos.p, d_d.p, d_m.p);
                     SD_HIP(hipGetLastError());
-                    SD_HIP(hipEventRecord(e1, st));
-                    SD_HIP(hipEventSynchronize(e1));
-                    if (it >= bench->warmup) SD_HIP(hipEventElapsedTime(&bench->ms_ident[it - bench->warmup], e0, e1));
-                }
+                });
                 SD_HIP(hipStreamSynchronize(st));
                 bench->info[4] = cap;
                 bench->info[5] = lanes / 256;
@@ -542,10 +463,10 @@ static int lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* star
             bench->info[2] = Kmost;
             bench->info[3] = cmost;
             for (const LagLaunch& L : launches) if (L.K == Kmost) { bench->info[6] = L.grid; bench->info[7] = L.cap; }
-            SD_HIP(hipMemsetAsync(d_sums.p, 0, sizeof(int64_t) * std::max<size_t>(n_sums, 1), st));
+            clear_sums();
         }
         for (const LagLaunch& L : launches) lag_walk(c, st, L, D, d_dist.p, d_matches.p, d_sums.p);
-        lag_used(c, st);
+        c.in_flight(st);
         // the host's pairs, under the kernel
         int hrc = SD_OK;
         if (nh > 0) {
@@ -567,15 +488,10 @@ static int lag_segments_dev(const char* seq, int64_t seqlen, const int64_t* star
         }
         int32_t fails = 0;
         SD_HIP(hipMemcpy(&fails, c.sum.p + sd::LAG_SUM_FAIL, sizeof fails, hipMemcpyDeviceToHost));
-        c.used = false;   // (the stream has been waited for)
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        (void)hipStreamDestroy(st);
-        st = nullptr;
+        c.waited();
         if (hrc) return hrc;
         return fails ? SD_ERR_INTERNAL : SD_OK;
     } catch (const HipFail&) {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
         return SD_ERR_HIP;
     }
 }
@@ -647,13 +563,9 @@ int sd_lag_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_t
         return SD_ERR_UNSUPPORTED;
     }
     int64_t text = 0;
-    for (int32_t r = 0; r < n_reads; ++r) {
-        if (read_off[r] < 0 || read_lens[r] < 0) { set_err(errbuf, errlen, std::string(who) + ": negative read offset or length"); return SD_ERR_PARAM; }
-        text += read_lens[r];
-    }
-    if (text > 0 && !d_text) { set_err(errbuf, errlen, std::string(who) + ": missing text"); return SD_ERR_PARAM; }
-    int rc = lag_device_check(device);
-    if (rc) { set_err(errbuf, errlen, rc == SD_ERR_NO_DEVICE ? "no usable HIP device" : "device " + std::to_string(device) + " does not exist"); return rc; }
+    int rc = final_reads_args(who, d_text, read_off, read_lens, n_reads, text, errbuf, errlen);
+    if (rc) return rc;
+    if ((rc = device_check(device, errbuf, errlen))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
     try {
         DeviceScope on(device);
@@ -666,30 +578,20 @@ int sd_lag_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_t
         const size_t n_sums = (size_t)n_reads * D * 3;
         if (n_sums) SD_HIP(hipMemsetAsync(d_sums, 0, sizeof(int64_t) * n_sums, st));
         if (n_rows == 0) return SD_OK;
-        LagCtx& c = lag_ctx(device);
+        LagCtx& c = device_ctx<LagCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();   // the previous call's kernels read the buffers this one overwrites
-        const size_t nr = (size_t)n_reads + 1;
-        c.h_reads.alloc(3 * nr);
-        c.reads.alloc(3 * nr);
-        c.text.alloc((size_t)text + 8);
         c.seg_start.alloc((size_t)n_rows);
         c.seg_len.alloc((size_t)n_rows);
         c.seg_read.alloc((size_t)n_rows);
         c.sum.alloc(sd::LAG_SUM_N);
-        int64_t* roff = c.h_reads.p, *rlen = roff + nr, *toff = rlen + nr;
-        int64_t at = 0;
-        for (int32_t r = 0; r < n_reads; ++r) { roff[r] = read_off[r]; rlen[r] = read_lens[r]; toff[r] = at; at += read_lens[r]; }
-        roff[n_reads] = 0; rlen[n_reads] = 0; toff[n_reads] = at;
-        SD_HIP(hipMemcpyAsync(c.reads.p, c.h_reads.p, 3 * nr * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        final_text_gather(c, st, d_text, read_off, read_lens, n_reads, text);
         SD_HIP(hipMemsetAsync(c.sum.p, 0, sd::LAG_SUM_N * sizeof(int32_t), st));
-        SD_HIP(hipMemsetAsync(c.text.p + text, 0, 8, st));
-        sd::launch_text_gather(st, static_cast<const uint8_t*>(d_text), c.reads.p, c.reads.p + 2 * nr, (int)n_reads, text, c.text.p);
-        sd::LagRowsArgs a{d_rows, n_rows, c.reads.p + nr, c.reads.p + 2 * nr, (int)n_reads, c.seg_start.p, c.seg_len.p, c.seg_read.p, c.sum.p};
+        sd::LagRowsArgs a{d_rows, n_rows, c.rlen(), c.toff(), (int)n_reads, c.seg_start.p, c.seg_len.p, c.seg_read.p, c.sum.p};
         hipLaunchKernelGGL(sd::sd_lag_rows, dim3(lag_grid(n_rows)), dim3(sd::LAG_T), 0, st, a);
         SD_HIP(hipGetLastError());
         lag_plan(c, st, n_rows, D, d_dist, d_matches, false);
-        lag_used(c, st);
+        c.in_flight(st);
         SD_HIP(hipEventSynchronize(c.ev_plan));   // the only wait: the class counts, which size the launches
         const int32_t* hs = c.h_sum.p;
         if (hs[sd::LAG_SUM_BAD]) {
@@ -701,7 +603,7 @@ int sd_lag_final_dev(const sd_final_row* d_rows, int64_t n_rows, const void* d_t
         if (classes) { classes[0] = hs[sd::LAG_SUM_NONE]; classes[1] = nd; classes[2] = hs[sd::LAG_SUM_HOST]; }
         c.settle();   // (nothing behind the plan yet: the checkpoints may grow)
         for (const LagLaunch& L : lag_launches(c)) lag_walk(c, st, L, D, d_dist, d_matches, d_sums);
-        lag_used(c, st);
+        c.in_flight(st);
         return SD_OK;
     } catch (const HipFail& f) {
         set_err(errbuf, errlen, f.msg);

@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "sd_final_ws.hpp"
+#include "sd_job_dev.hpp"
 #include "sd_msa.hpp"
 #include "sd_nw_kernel.hpp"
 
@@ -149,9 +150,7 @@ int nw_msa_device(const char* seq, int64_t seqlen, const int64_t* seg_start, con
     const int M = (int)il.size() / 2;
     if (n_seg == 0 || M == 0) return SD_OK;
     if (n_seg > 0x7fffffff) return SD_ERR_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SD_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) return SD_ERR_PARAM;
+    if (const int rc = sdi::device_check(device, nullptr, 0)) return rc;
     int tmax = 1;
     bool dev_ok = true;
     for (const std::string& t : il) {
@@ -485,16 +484,7 @@ static void msa_used(sd_msa_tables* t, hipStream_t st) {
     t->used = true;
 }
 static int msa_dev_check(sd_msa_tables* t, int32_t device, hipStream_t st, char* eb, size_t el) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        set_err(eb, el, "no usable HIP device");
-        return SD_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        set_err(eb, el, "device " + std::to_string(device) + " does not exist");
-        return SD_ERR_PARAM;
-    }
+    if (const int rc = device_check(device, eb, el)) return rc;
     if (t->device >= 0 && t->device != device) {
         set_err(eb, el, "the templates lie on device " + std::to_string(t->device) + ", the call names device " + std::to_string(device));
         return SD_ERR_PARAM;

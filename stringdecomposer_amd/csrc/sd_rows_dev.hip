@@ -9,7 +9,7 @@
 //   sd_rows_count, sd_rows_scan                     kept records per tile, rows before each tile, the row count
 //   sd_rows_scatter                                 kept records -> rows, row offsets per read
 // No look-back and no spinning: a launch per stage, seven for a job (~5 MB of records in the benchmark's step).
-#include "sd_pipeline.hpp"
+#include "sd_job_dev.hpp"
 #include "sd_rows_scan_dev.hpp"
 #include "sd_seam_dev.hpp"
 
@@ -227,9 +227,7 @@ int sd_seam_merge_dev(const sd_rec* d_recs, const int64_t* d_read_off, int32_t n
                       void* hip_stream, sd_rec* d_rows, int64_t* d_row_off, int64_t* n_rows) {
     static_assert(sizeof(sd_rec) == sizeof(sd::DevRec), "record layout");
     if (n_reads < 0 || !d_read_off || !d_row_off || device < 0 || (piece != 0 && piece < sd::SEAM_REACH)) return SD_ERR_PARAM;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SD_ERR_NO_DEVICE; }
-    if (device >= ndev) return SD_ERR_PARAM;
+    if (const int rc = device_check(device, nullptr, 0)) return rc;   // (device < 0: refused above)
     try {
         SD_HIP(hipSetDevice(device));
         hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);

@@ -23,13 +23,11 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <numeric>
 
 #include "sd_group_dev.hpp"
 #include "sd_host.hpp"
-#include "sd_pipeline.hpp"
+#include "sd_job_dev.hpp"
 #include "sd_split.hpp"
 
 namespace sd {
@@ -449,9 +447,9 @@ struct SpBench {
     float *ms_prep, *ms_assign, *ms_modes;
 };
 
-// Per device, kept between calls (the manner of sd_autocorr.hip); every call is done with it when it returns.
-struct SpCtx {
-    std::mutex m;
+// Per device, kept between calls (sd_job_dev.hpp: DevWork).  Every call is done with it when it returns: nothing is left
+// in flight, so no call settles.
+struct SpCtx : DevWork {
     DevBuf<uint64_t> planes, cen;
     DevBuf<int32_t> slots, counts, tabs, order, mcount;
     DevBuf<uint8_t> cand, up_rows, up_status, cen_sym;
@@ -460,22 +458,7 @@ struct SpCtx {
     DevBuf<sd::SplitStat> stat;   // two states and the key of a rejected round
     PinBuf<sd::SplitStat> h_stat;
     PinBuf<int32_t> h_counts;
-    int n_cu = 256;
 };
-
-SpCtx& sp_ctx(int device) {
-    static std::mutex m;
-    static std::map<int, SpCtx*>* all = new std::map<int, SpCtx*>;   // (never destroyed: no HIP call at process exit)
-    std::lock_guard<std::mutex> g(m);
-    SpCtx*& c = (*all)[device];
-    if (!c) {
-        c = new SpCtx;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
-        else (void)hipGetLastError();
-    }
-    return *c;
-}
 
 inline unsigned sp_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + sd::SP_T - 1) / sd::SP_T); }
 
@@ -579,28 +562,12 @@ static_assert(offsetof(sd::SplitStat, sizes) == 16, "the host reads the first 16
 
 // the timed repetitions of the three stages on the trial state of a finished monomer (its results are out already)
 void sp_bench(SpDev& d, int k, const SpBench& b) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    SD_HIP(hipEventCreate(&e0));
-    SD_HIP(hipEventCreate(&e1));
-    try {
-        SD_HIP(hipMemcpyAsync(d.tr->cen, d.cur->cen, sizeof(uint64_t) * sd::SPLIT_KMAX * 3 * sd::SPLIT_WMAX, hipMemcpyDeviceToDevice, d.st));
-        d.assign_launch(k, true);
-        for (int pass = 0; pass < 3; ++pass)
-            for (int it = 0; it < b.warmup + b.reps; ++it) {
-                SD_HIP(hipEventRecord(e0, d.st));
-                if (pass == 0) d.prep(); else if (pass == 1) d.assign_launch(k, false); else d.modes(k);
-                SD_HIP(hipEventRecord(e1, d.st));
-                SD_HIP(hipEventSynchronize(e1));
-                float* ms = pass == 0 ? b.ms_prep : pass == 1 ? b.ms_assign : b.ms_modes;
-                if (it >= b.warmup) SD_HIP(hipEventElapsedTime(&ms[it - b.warmup], e0, e1));
-            }
-    } catch (...) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        throw;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    SD_HIP(hipMemcpyAsync(d.tr->cen, d.cur->cen, sizeof(uint64_t) * sd::SPLIT_KMAX * 3 * sd::SPLIT_WMAX, hipMemcpyDeviceToDevice, d.st));
+    d.assign_launch(k, true);
+    StageClock clock;
+    clock.time(d.st, b.warmup, b.reps, b.ms_prep, [&]() { d.prep(); });
+    clock.time(d.st, b.warmup, b.reps, b.ms_assign, [&]() { d.assign_launch(k, false); });
+    clock.time(d.st, b.warmup, b.reps, b.ms_modes, [&]() { d.modes(k); });
 }
 
 struct SpJob {
@@ -697,13 +664,6 @@ int sp_run(const char* who, SpCtx& c, hipStream_t st, const SpJob& j, const SpBe
     return SD_OK;
 }
 
-int sp_device_check(int32_t device, char* errbuf, size_t errlen) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_err(errbuf, errlen, "no usable HIP device"); return SD_ERR_NO_DEVICE; }
-    if (device < 0 || device >= ndev) { set_err(errbuf, errlen, "device " + std::to_string(device) + " does not exist"); return SD_ERR_PARAM; }
-    return SD_OK;
-}
-
 // a symbol matrix as the one monomer of a job on `device`: uploaded, split by the kernels, the results back
 int sp_matrix_dev(const char* who, const uint8_t* sym, int64_t n, int64_t pitch, int32_t L, int32_t R, int32_t K, int32_t S, int32_t I, int32_t device,
                   int32_t threads, uint8_t* centres, int32_t* asg, int32_t* d1, int32_t* d2, int32_t* sizes, int64_t* info, char* errbuf, size_t errlen,
@@ -715,13 +675,12 @@ int sp_matrix_dev(const char* who, const uint8_t* sym, int64_t n, int64_t pitch,
         sp_host_core(sym, n, pitch, L, R, K, S, I, std::max(1, threads), centres, asg, d1, d2, sizes, info);
         return SD_OK;
     }
-    if ((rc = sp_device_check(device, errbuf, errlen))) return rc;
-    hipStream_t st = nullptr;
+    if ((rc = device_check(device, errbuf, errlen))) return rc;
     try {
         DeviceScope on(device);
-        SpCtx& c = sp_ctx(device);
+        SpCtx& c = device_ctx<SpCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
-        SD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        OwnedStream st;
         std::vector<int64_t> at((size_t)n);
         for (int64_t i = 0; i < n; ++i) at[(size_t)i] = i * pitch;
         c.up_rows.alloc((size_t)n * pitch);
@@ -747,11 +706,9 @@ int sp_matrix_dev(const char* who, const uint8_t* sym, int64_t n, int64_t pitch,
             SD_HIP(hipMemcpyAsync(centres, c.cen_sym.p, (size_t)inf[1] * L, hipMemcpyDeviceToHost, st));
         }
         SD_HIP(hipStreamSynchronize(st));
-        (void)hipStreamDestroy(st);
         info[0] = inf[1]; info[1] = inf[2]; info[2] = inf[3]; info[3] = 1;
         return rc;
     } catch (const HipFail& f) {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
         set_err(errbuf, errlen, f.msg);
         return SD_ERR_HIP;
     }
