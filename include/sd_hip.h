@@ -1233,6 +1233,54 @@ void sd_split_info(int64_t info[4]);
 int sd_split_kernel_bench(const uint8_t* sym, int64_t n, int64_t pitch, int32_t L, int32_t R, int32_t K, int32_t S, int32_t I,
                           int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_assign, float* ms_modes, int64_t info[4]);
 
+/* ---- higher-order repeat units of the final rows (--hor; csrc/sd_hor.hpp holds the rule) ------------------------------
+ * Input: the rows of the final TSV in file order.  key = 2 m + s: monomer m of the monomer file, s = 1 its reverse
+ * complement (the order of sd_stream_keys for a set without a repeated name), -1 = none.  A row is usable when usable != 0
+ * (sd_final_row: reliable == 1) and key >= 0.  Rows x, x + 1 are adjacent when they share read and strand, both are
+ * usable and 0 <= start[x+1] - end[x] - 1 <= G.
+ *   T [n_mono x n_mono]: an adjacent pair adds 1 to T[m_x][m_x+1] on the forward strand, to T[m_x+1][m_x] on the reverse
+ *   strand; rows[m] = the usable rows of m.
+ *   succ(a) = the b of largest T[a][b], pred(b) = the a of largest T[a][b], ties to the smallest index, each defined from
+ *   a count of C on.  The edge a -> b is kept when succ(a) = b and pred(b) = a; the components with an edge are simple
+ *   cycles (kind 0, rotated to the smallest monomer) and simple paths (kind 1, from the head): the orders, sorted by their
+ *   smallest monomer.  hor[m] = the order of m (0-based; H1 is order 0) or -1, pos[m] = its position, 1-based, or 0;
+ *   order_kind / order_len [n_mono allocated].  An order of more than SD_HOR_PMAX monomers is not numbered: its monomers
+ *   are on no order, long_first / long_len [n_mono allocated] name its first monomer and its length.
+ *   A unit is a maximal run of rows whose consecutive pairs are adjacent, on one order, with positions rising (forward
+ *   strand) or falling (reverse strand); a usable row alone on an order is a unit.  row_unit[x] = the unit of row x (units
+ *   are numbered by their first row) or -1; units [cap_units allocated].
+ *   info = {orders, units, long orders, 0}.
+ * cap_units smaller than the units: SD_ERR_PARAM, info[1] and errbuf give the exact count, T / rows / the orders and
+ * row_unit are complete, no unit is written.  n_rows always suffices.
+ * Refused before any other work, errbuf naming the value: n_mono < 1 (SD_ERR_PARAM), n_mono > SD_HOR_MMAX
+ * (SD_ERR_UNSUPPORTED), G < 0, C < 1, n_rows < 0 or >= 2^31, a key outside -1 .. 2 n_mono - 1 (SD_ERR_PARAM).
+ *
+ * sd_hor_rows: host threads (csrc/sd_hor.hip).  sd_hor_final_host: the same call on sd_final_row records (key = best, usable =
+ * reliable == 1).  The rule is written for host and device (csrc/sd_hor.hpp); the library has no device form of it yet. */
+#define SD_HOR_MMAX 2048
+#define SD_HOR_PMAX 64
+#define SD_HOR_NAME_MAX 192
+typedef struct sd_hor_unit {
+    int64_t first_row;               /* its first row                                                         */
+    int64_t start, end;              /* start of its first row, end of its last                               */
+    uint64_t mask;                   /* bit pos - 1 per row                                                   */
+    int32_t read, n_rows, order;     /* order: 0-based                                                        */
+    int32_t strand;                  /* 0: '+', 1: '-'                                                        */
+} sd_hor_unit;
+int sd_hor_rows(const int32_t* read, const int64_t* start, const int64_t* end, const int32_t* key, const uint8_t* usable, int64_t n_rows,
+                int32_t n_mono, int64_t G, int64_t C, int32_t threads, int64_t* T, int64_t* rows, int32_t* hor, int32_t* pos,
+                int32_t* order_kind, int32_t* order_len, int32_t* long_first, int32_t* long_len, int32_t* row_unit, sd_hor_unit* units,
+                int64_t cap_units, int64_t info[4], char* errbuf, size_t errlen);
+int sd_hor_final_host(const sd_final_row* rows_in, int64_t n_rows, int32_t n_mono, int64_t G, int64_t C, int32_t threads, int64_t* T,
+                      int64_t* rows, int32_t* hor, int32_t* pos, int32_t* order_kind, int32_t* order_len, int32_t* long_first,
+                      int32_t* long_len, int32_t* row_unit, sd_hor_unit* units, int64_t cap_units, int64_t info[4], char* errbuf,
+                      size_t errlen);
+/* The name of a mask: the positions present, ascending, as ranges joined by '_' ("1-12", "1-4_7-12", "3"); buf holds
+ * SD_HOR_NAME_MAX bytes; returns the length. */
+int sd_hor_name(uint64_t mask, char* buf);
+/* info = {SD_HOR_MMAX, SD_HOR_PMAX, SD_HOR_NAME_MAX, 0}. */
+void sd_hor_info(int64_t info[4]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

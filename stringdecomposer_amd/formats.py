@@ -49,6 +49,14 @@ Two more text files are this package's own (opt-in, `--profile`):
                       <out>_split_summary.tsv: monomer, subfamily, size, sum of d1, largest d1, nearest subfamily, distance.
                       read_split / read_split_summary below; <out>_split_monomers.fa is a monomer file.
 
+  <out>_hor.tsv       (`--hor`) one line per higher-order repeat unit, no header: read, start, end, strand ('+' / '-'),
+                      order (H1, H2, ...), name (the positions of the order present, as ranges: 1-12, 1-4_7-12, 3), rows,
+                      complete (1 when every position is present, else 0).
+                      <out>_hor_orders.tsv, one line per (order, position): order, kind (cycle / path), length, position,
+                      monomer, usable rows of the monomer, count of the edge to the next position (0 at a path's end).
+                      <out>_hor_variants.tsv, one line per (order, name): order, name, units, rows, bases.
+                      read_hor / read_hor_orders / read_hor_variants below.
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -1041,6 +1049,150 @@ def read_split_summary(path):
             except ValueError as e:
                 raise FormatError(path, lineno, str(e))
     return out
+
+
+# ---- higher-order repeat units (--hor; csrc/sd_hor.hpp holds the rule) ------------------------------------------------
+Hor = namedtuple("Hor", "T rows hor pos kinds lens long row_unit units")
+"""lib.hor_rows / final_hor_host: T = int64 [M, M] transitions, rows = int64 [M] usable rows per monomer, hor / pos = int32
+[M] the order (0-based, -1: none) and position (1-based, 0: none) of a monomer, kinds (0 cycle, 1 path) / lens per order,
+long = [(first monomer, length)] of the orders too long to number, row_unit = int32 [n_rows] (-1: in no unit), units = a
+numpy array of lib.hor_unit_dtype() (first_row, start, end, mask, read, n_rows, order, strand)."""
+HorUnitRow = namedtuple("HorUnitRow", "read start end strand order name rows complete")        # a line of <out>_hor.tsv
+HorOrderRow = namedtuple("HorOrderRow", "order kind length position monomer rows count")       # ... of <out>_hor_orders.tsv
+HorVariantRow = namedtuple("HorVariantRow", "order name units rows bases")                     # ... of <out>_hor_variants.tsv
+HOR_KINDS = ("cycle", "path")
+
+
+def hor_mask_name(mask):
+    """The name of a unit's mask: the positions present (bit pos - 1), ascending, as ranges joined by '_'."""
+    out, p, mask = [], 1, int(mask)
+    while mask >> (p - 1):
+        if not (mask >> (p - 1)) & 1:
+            p += 1
+            continue
+        q = p
+        while (mask >> q) & 1:
+            q += 1
+        out.append("%d-%d" % (p, q) if q > p else "%d" % p)
+        p = q + 1
+    return "_".join(out)
+
+
+def hor_mask_of(name):
+    """The mask of a name (the inverse of hor_mask_name)."""
+    mask = 0
+    for part in name.split("_"):
+        lo, _, hi = part.partition("-")
+        lo, hi = int(lo), int(hi or lo)
+        if not 1 <= lo <= hi <= 64:
+            raise ValueError("a range of positions must lie in 1 .. 64, found %r" % part)
+        for p in range(lo, hi + 1):
+            mask |= 1 << (p - 1)
+    if hor_mask_name(mask) != name:
+        raise ValueError("%r is not the name of a set of positions" % name)
+    return mask
+
+
+def hor_units(hor, read_names):
+    """The lines of <out>_hor.tsv -> [HorUnitRow]; read_names: the reads by index."""
+    lens = [int(x) for x in hor.lens]
+    out = []
+    for first_row, start, end, mask, read, n_rows, order, strand in hor.units.tolist():
+        out.append(HorUnitRow(read_names[read], start, end, "-" if strand else "+", "H%d" % (order + 1), hor_mask_name(mask), n_rows,
+                              1 if mask == (1 << lens[order]) - 1 else 0))
+    return out
+
+
+def hor_orders(hor, mono_names):
+    """The lines of <out>_hor_orders.tsv -> [HorOrderRow]; count = T[monomer][the next position's], 0 at a path's end."""
+    at = {}
+    for m, (h, p) in enumerate(zip(hor.hor.tolist(), hor.pos.tolist())):
+        if h >= 0:
+            at[(h, p)] = m
+    out = []
+    for o, (kind, n) in enumerate(zip([int(x) for x in hor.kinds], [int(x) for x in hor.lens])):
+        for p in range(1, n + 1):
+            m = at[(o, p)]
+            nxt = at[(o, p + 1)] if p < n else (at[(o, 1)] if kind == 0 else None)
+            out.append(HorOrderRow("H%d" % (o + 1), HOR_KINDS[kind], n, p, mono_names[m], int(hor.rows[m]),
+                                   int(hor.T[m][nxt]) if nxt is not None else 0))
+    return out
+
+
+def hor_variants(hor):
+    """The lines of <out>_hor_variants.tsv -> [HorVariantRow]: per (order, mask) its units, rows and bases, sorted by order,
+    then units descending, then mask ascending."""
+    acc = {}
+    for first_row, start, end, mask, read, n_rows, order, strand in hor.units.tolist():
+        a = acc.setdefault((order, mask), [0, 0, 0])
+        a[0] += 1
+        a[1] += n_rows
+        a[2] += end - start + 1
+    keys = sorted(acc, key=lambda k: (k[0], -acc[k][0], k[1]))
+    return [HorVariantRow("H%d" % (o + 1), hor_mask_name(mask), *acc[(o, mask)]) for o, mask in keys]
+
+
+def format_hor(rows):
+    return "".join("%s\t%d\t%d\t%s\t%s\t%s\t%d\t%d\n" % tuple(r) for r in rows)
+
+
+def format_hor_orders(rows):
+    return "".join("%s\t%s\t%d\t%d\t%s\t%d\t%d\n" % tuple(r) for r in rows)
+
+
+def format_hor_variants(rows):
+    return "".join("%s\t%s\t%d\t%d\t%d\n" % tuple(r) for r in rows)
+
+
+def _write_text(path, text):
+    with open(path, "w", newline="") as f:
+        f.write(text)
+
+
+def write_hor(path, rows):
+    _write_text(path, format_hor(rows))
+
+
+def write_hor_orders(path, rows):
+    _write_text(path, format_hor_orders(rows))
+
+
+def write_hor_variants(path, rows):
+    _write_text(path, format_hor_variants(rows))
+
+
+def _hor_order_name(x):
+    if not (x.startswith("H") and x[1:].isdigit() and int(x[1:]) >= 1):
+        raise ValueError("an order is H1, H2, ..., found %r" % x)
+    return x
+
+
+def _hor_name(x):
+    hor_mask_of(x)
+    return x
+
+
+def _hor_choice(*allowed):
+    def conv(x):
+        if x not in allowed:
+            raise ValueError("expected one of %s, found %r" % (", ".join(allowed), x))
+        return x
+    return conv
+
+
+def read_hor(path):
+    """<out>_hor.tsv -> [HorUnitRow]."""
+    return _parse(path, False, 8, (_ident, int, int, _hor_choice("+", "-"), _hor_order_name, _hor_name, int, int), HorUnitRow)
+
+
+def read_hor_orders(path):
+    """<out>_hor_orders.tsv -> [HorOrderRow]."""
+    return _parse(path, False, 7, (_hor_order_name, _hor_choice(*HOR_KINDS), int, int, _ident, int, int), HorOrderRow)
+
+
+def read_hor_variants(path):
+    """<out>_hor_variants.tsv -> [HorVariantRow]."""
+    return _parse(path, False, 5, (_hor_order_name, _hor_name, int, int, int), HorVariantRow)
 
 
 _COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}

@@ -63,6 +63,7 @@ EXPORTS = [
     "sd_autocorr_layout", "sd_autocorr_host", "sd_autocorr_dev", "sd_autocorr_reads_dev", "sd_autocorr_positions", "sd_autocorr_peaks",
     "sd_autocorr_seed", "sd_autocorr_info", "sd_autocorr_kernel_bench",
     "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
+    "sd_hor_rows", "sd_hor_final_host", "sd_hor_name", "sd_hor_info",
     "sd_dotplot_layout", "sd_dotplot_host", "sd_dotplot_dev", "sd_dotplot_reads_dev", "sd_dotplot_info", "sd_dotplot_hash", "sd_dotplot_kernel_bench",
     "sd_screen_create", "sd_screen_destroy", "sd_screen_set_general", "sd_screen_kernel", "sd_screen_chunks",
     "sd_screen_chunks_dev", "sd_screen_chunks_host", "sd_screen_regions", "sd_screen_kernel_ms", "sd_run_files_screen",
@@ -318,6 +319,12 @@ def load():
     L.sd_split_info.restype = None
     L.sd_split_kernel_bench.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64)]
+    hor_out = [C.c_void_p] * 10 + [C.c_int64, P(C.c_int64), C.c_char_p, C.c_size_t]   # T .. units, cap_units, info, errbuf
+    L.sd_hor_rows.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32] + hor_out
+    L.sd_hor_final_host.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32] + hor_out
+    L.sd_hor_name.argtypes = [C.c_uint64, C.c_char_p]
+    L.sd_hor_info.argtypes = [P(C.c_int64)]
+    L.sd_hor_info.restype = None
     L.sd_last_run_profile.argtypes = [P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p, C.c_void_p]
     L.sd_stream_profile.argtypes = [C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int64), P(C.c_int64), C.c_char_p,
                                     C.c_void_p]
@@ -1751,6 +1758,114 @@ def split_kernel_bench(sym, R, K=64, min_size=8, max_iter=16, device=0, warmup=2
     out = {"prep_ms": [float(v) for v in x], "assign_ms": [float(v) for v in y], "modes_ms": [float(v) for v in z]}
     out.update(zip(("k", "rounds", "iters", "launches"), [int(v) for v in info]))
     return out
+
+
+HOR_MMAX = 2048
+HOR_PMAX = 64
+HOR_NAME_MAX = 192
+
+
+def hor_unit_dtype():
+    """numpy dtype of sd_hor_unit (include/sd_hip.h): first_row, start, end, mask, read, n_rows, order (0-based), strand
+    (0 '+', 1 '-'); 48 bytes, no padding."""
+    import numpy as np
+    dt = np.dtype([("first_row", "<i8"), ("start", "<i8"), ("end", "<i8"), ("mask", "<u8"), ("read", "<i4"), ("n_rows", "<i4"),
+                   ("order", "<i4"), ("strand", "<i4")])
+    assert dt.itemsize == 48
+    return dt
+
+
+def hor_info():
+    """sd_hor_info -> {"mmax": the most monomers, "pmax": the most monomers of an order and rows of a unit, "name_max": the
+    bytes a name needs}"""
+    info = (C.c_int64 * 4)()
+    load().sd_hor_info(info)
+    return dict(zip(("mmax", "pmax", "name_max"), (int(x) for x in info)))
+
+
+def hor_name(mask):
+    """The name of a unit's mask: the positions present as ascending ranges joined by '_' (sd_hor_name)"""
+    buf = C.create_string_buffer(HOR_NAME_MAX)
+    load().sd_hor_name(int(mask) & 0xFFFFFFFFFFFFFFFF, buf)
+    return buf.value.decode()
+
+
+def _hor_args(n_mono, G, C_, who):
+    """integers that fit the C types; the ranges are the library's to refuse, with its texts"""
+    def is_int(x):
+        return isinstance(x, int) and not isinstance(x, bool)
+    for name, v, bits in (("n_mono", n_mono, 31), ("G", G, 63), ("C", C_, 63)):
+        if not is_int(v) or not -(1 << bits) <= v < (1 << bits):
+            raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer" % (who, name, v))
+    return n_mono, G, C_
+
+
+class _HorOut:
+    """the host arrays a sd_hor_* call fills, and the formats.Hor made of them"""
+
+    def __init__(self, n, M):
+        import numpy as np
+        M1 = max(M, 1) if 0 < M <= HOR_MMAX else 1
+        self.n, self.M = n, M1
+        self.T = np.zeros((M1, M1), dtype=np.int64)
+        self.rows = np.zeros(M1, dtype=np.int64)
+        self.hor, self.pos, self.kind, self.len, self.lfirst, self.llen = (np.zeros(M1, dtype=np.int32) for _ in range(6))
+        self.info = (C.c_int64 * 4)()
+        self.err = C.create_string_buffer(1024)
+        self.row_unit = np.zeros(max(n, 1), dtype=np.int32)
+        self.units = np.zeros(max(n, 1), dtype=hor_unit_dtype())   # (n_rows always suffices)
+
+    def orders(self):
+        return [x.ctypes.data for x in (self.rows, self.hor, self.pos, self.kind, self.len, self.lfirst, self.llen)]
+
+    def tail(self):
+        return [self.T.ctypes.data] + self.orders() + [self.row_unit.ctypes.data, self.units.ctypes.data, self.n, self.info, self.err, 1024]
+
+    def result(self):
+        from . import formats
+        no, nl = int(self.info[0]), int(self.info[2])
+        return formats.Hor(self.T, self.rows, self.hor, self.pos, self.kind[:no].copy(), self.len[:no].copy(),
+                           [(int(a), int(b)) for a, b in zip(self.lfirst[:nl], self.llen[:nl])], self.row_unit[:self.n],
+                           self.units[:int(self.info[1])].copy())
+
+
+def hor_rows(read, start, end, key, usable, n_mono, G=0, C_=2, threads=1, cap_units=None):
+    """The higher-order repeat units of final rows given as columns (csrc/sd_hor.hpp; include/sd_hip.h: sd_hor_*): read,
+    start, end (inclusive), key = 2 m + s (monomer m, s = 1 the reverse complement; -1: none), usable (reliable); n_mono
+    monomers, G the widest gap adjacency bridges, C_ the fewest pairs behind an edge of an order.  Runs on host threads
+    (sd_hor_rows).  cap_units: the units allocated (None: one per row, which always suffices; fewer than the job has is
+    SD_ERR_PARAM with the count).  -> formats.Hor"""
+    import numpy as np
+    who = "hor_rows"
+    M, G, C_ = _hor_args(n_mono, G, C_, who)
+    cols = [np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in ((read, np.int32), (start, np.int64), (end, np.int64),
+                                                                      (key, np.int32), (usable, np.uint8))]
+    n = int(cols[0].shape[0])
+    if any(int(a.shape[0]) != n for a in cols):
+        raise SdError(SD_ERR_PARAM, "%s: the five columns differ in length" % who)
+    o = _HorOut(n, M)
+    ptrs = [a.ctypes.data if n else o.T.ctypes.data for a in cols]
+    tail = o.tail()
+    if cap_units is not None:
+        tail[10] = min(int(cap_units), max(n, 1))
+    rc = load().sd_hor_rows(*ptrs, n, M, G, C_, int(threads), *tail)
+    if rc != SD_OK:
+        raise SdError(rc, o.err.value.decode(errors="replace") or "sd_hor_rows")
+    return o.result()
+
+
+def final_hor_host(final_rows, n_mono, G=0, C_=2, threads=1):
+    """hor_rows on the rows of a final-mode job (sd_hor_final_host): final_rows = a FinalRows or its (rows, row_off, alt); key =
+    best, usable = reliable == 1 -> formats.Hor"""
+    import numpy as np
+    M, G, C_ = _hor_args(n_mono, G, C_, "final_hor_host")
+    rows = np.ascontiguousarray(final_rows[0])
+    n = int(rows.shape[0])
+    o = _HorOut(n, M)
+    rc = load().sd_hor_final_host(rows.ctypes.data if n else o.T.ctypes.data, n, M, G, C_, int(threads), *o.tail())
+    if rc != SD_OK:
+        raise SdError(rc, o.err.value.decode(errors="replace") or "sd_hor_final_host")
+    return o.result()
 
 
 def decompose_files_records(reads_fa, monomers_fa, records_out, **kw):

@@ -41,6 +41,7 @@ np = _LazyNumpy()
 from . import autocorr
 from . import dotplot
 from . import split
+from . import hor
 from . import lib
 from . import shard
 
@@ -737,6 +738,7 @@ def main(argv=None):
     autocorr.add_arguments(parser)
     dotplot.add_arguments(parser)
     split.add_arguments(parser)
+    hor.add_arguments(parser)
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
@@ -762,6 +764,8 @@ def main(argv=None):
         dotplot.check(args)
     if args.split is not None:
         split.check(args)
+    if args.hor:
+        hor.check(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -892,6 +896,15 @@ def main(argv=None):
             logger.info("--split failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the subfamilies of the monomers' instances to " + ", ".join(saved))
+
+    if args.hor:
+        try:
+            saved = hor.write(args, convert_tsv_fn, args.out_dir, args.out_file)
+        except lib.SdError as e:
+            sys.stderr.write("--hor failed: " + e.msg + "\n")
+            logger.info("--hor failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the higher-order repeat units to " + ", ".join(saved))
 
     logger.info("Thank you for using StringDecomposer!")
 
