@@ -1281,6 +1281,70 @@ int sd_hor_name(uint64_t mask, char* buf);
 /* info = {SD_HOR_MMAX, SD_HOR_PMAX, SD_HOR_NAME_MAX, 0}. */
 void sd_hor_info(int64_t info[4]);
 
+/* ---- IUPAC motif hits on both strands of every read (--motif; csrc/sd_motif.hpp holds the rule) -----------------------
+ * A motif is a pattern of L codes from ACGTRYSWKMBDHVN, 1 <= L <= SD_MOTIF_LMAX, lower case folded.  N matches every text
+ * byte; every other code is a set of bases and matches a text byte only when the byte is an upper-case A C G T of the set.
+ * With E mismatches allowed (0 <= E <= SD_MOTIF_EMAX, one value for the request), position i of a read of n bases is a hit
+ * on strand + when i + L <= n and at most E constrained positions j have T[i + j] outside the set of P[j]; on strand - by
+ * the same rule against the reverse complement of P.  A pattern equal to its reverse complement is reported on + only.
+ * Every hit is reported, overlapping ones included: Hamming matches, no indels.
+ * Reads as the sd_autocorr_* calls take them: read r is text[read_off[r] .. + read_lens[r]), gaps and any order allowed.
+ * hits: sd_motif_hit records in canonical order -- read, then motif in request order, then + before -, then start;
+ * per[(r * n_motifs + m) * 2 + strand] (int64) = the hits of read r and motif m on that strand.
+ * Limits, each refused (SD_ERR_PARAM) with its numbers in errbuf: at most SD_MOTIF_MAX motifs; every motif needs more than
+ * E constrained positions; at most SD_MOTIF_ITEMS_MAX (tile of SD_MOTIF_TILE_WORDS words of a read, pattern-strand) items
+ * per call, refused before any device work; at most SD_MOTIF_HITS_MAX hits per call, refused when the size pass has
+ * counted them and before a record is written.
+ * sd_motif_compile: host only.  Checks names ([A-Za-z0-9_.-]+, unique), patterns and E; *n_strands = the pattern-strands
+ *   of the request (two per motif, one for a palindrome) and, where table is not NULL (5 x 2 x n_motifs int32), per
+ *   pattern-strand {motif, strand, L, constrained positions, palindrome}.
+ * sd_motif_host: text in host memory, `threads` host threads.  *hits is malloc'ed (sd_free), *n_hits its records; per is
+ *   the caller's (n_reads x n_motifs x 2).
+ * sd_motif_dev: the same from the kernels of csrc/sd_motif.hip on `device`: the reads are uploaded, the call owns its
+ *   stream and returns hits and per in host memory.  The same arrays as sd_motif_host.
+ * sd_motif_reads_size_dev / sd_motif_reads_write_dev: d_text in the memory of `device`, complete on hip_stream, as
+ *   sd_autocorr_reads_dev takes it.  The size call builds the planes, counts every item, scans the counts and fills d_per
+ *   (device memory, n_reads x n_motifs x 2 int64) on hip_stream; *n_hits comes to the host: 8 bytes, the only wait.  The
+ *   write call -- the next motif call on that device, with the same reads and request -- writes the records into d_hits
+ *   (device memory, cap records) on hip_stream and returns with its kernels in flight.  cap < *n_hits: SD_ERR_PARAM with
+ *   the exact size in the message, nothing written.  A buffer that is not in device memory: SD_ERR_PARAM ("not in device
+ *   memory"); another device's: SD_ERR_UNSUPPORTED.
+ * sd_motif_info: info = {SD_MOTIF_TILE_WORDS, pattern-strands a workgroup takes, the most start x pattern-strand products
+ *   of one launch, launches of the size and write kernels in this process so far}.
+ * sd_motif_kernel_bench: the stages of sd_motif_dev between events, warmup + reps rounds each: ms_prep (the planes),
+ *   ms_size (counts, scan, per), ms_write (the records), `reps` floats each; info = {launches of a write round, items,
+ *   hits, plane words}. */
+#define SD_MOTIF_LMAX 64
+#define SD_MOTIF_EMAX 7
+#define SD_MOTIF_MAX 1024
+#define SD_MOTIF_ITEMS_MAX (1 << 24)
+#define SD_MOTIF_HITS_MAX (1 << 28)
+#define SD_MOTIF_TILE_WORDS 256
+typedef struct {
+    int64_t start;        /* leftmost base, 0-based; the hit ends at start + L - 1 (inclusive) */
+    int32_t read;
+    uint16_t motif;       /* index in the request */
+    uint8_t strand;       /* 0: '+', 1: '-' */
+    uint8_t mismatches;
+} sd_motif_hit;
+int sd_motif_compile(const char* const* names, const char* const* patterns, int32_t n_motifs, int32_t E, int32_t* n_strands, int32_t* table,
+                     char* errbuf, size_t errlen);
+int sd_motif_host(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                  int32_t n_motifs, int32_t E, int32_t threads, sd_motif_hit** hits, int64_t* n_hits, int64_t* per, char* errbuf,
+                  size_t errlen);
+int sd_motif_dev(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                 int32_t n_motifs, int32_t E, int32_t device, sd_motif_hit** hits, int64_t* n_hits, int64_t* per, char* errbuf, size_t errlen);
+int sd_motif_reads_size_dev(const void* d_text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                            int32_t n_motifs, int32_t E, int32_t device, void* hip_stream, int64_t* d_per, int64_t* n_hits, char* errbuf,
+                            size_t errlen);
+int sd_motif_reads_write_dev(const void* d_text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                             int32_t n_motifs, int32_t E, int32_t device, void* hip_stream, sd_motif_hit* d_hits, int64_t cap, char* errbuf,
+                             size_t errlen);
+void sd_motif_info(int64_t info[4]);
+int sd_motif_kernel_bench(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                          int32_t n_motifs, int32_t E, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_size,
+                          float* ms_write, int64_t info[4]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

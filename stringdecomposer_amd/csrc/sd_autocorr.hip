@@ -56,6 +56,11 @@ __global__ __launch_bounds__(AC_T) void sd_autocorr_prep(const uint8_t* __restri
     }
 }
 
+void launch_autocorr_prep(hipStream_t st, unsigned grid, const uint8_t* text, const int64_t* roff, const int64_t* rlen, const int64_t* pw,
+                          int n_reads, int64_t words, uint64_t* lo, uint64_t* hi, uint64_t* v) {
+    hipLaunchKernelGGL(sd_autocorr_prep, dim3(grid), dim3(AC_T), 0, st, text, roff, rlen, pw, n_reads, words, lo, hi, v);
+}
+
 struct AcArgs {
     const uint64_t *lo, *hi, *v;                      // the planes of the job
     const int64_t *rlen, *pw, *win_off, *tile_off;    // per read (tile_off, pw, win_off: n_reads + 1)

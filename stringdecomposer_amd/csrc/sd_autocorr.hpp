@@ -17,6 +17,10 @@
 
 #include <cstdint>
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>   // hipStream_t of launch_autocorr_prep
+#endif
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #ifndef SD_HD
 #define SD_HD __host__ __device__
@@ -143,5 +147,12 @@ SD_HD inline bool autocorr_is_peak(const int64_t* a, int64_t D, int64_t LO, int6
 SD_HD inline bool autocorr_peak_before(int64_t count_a, int64_t lag_a, int64_t count_b, int64_t lag_b) {
     return count_a != count_b ? count_a > count_b : lag_a < lag_b;
 }
+
+#if defined(__HIPCC__)
+// sd_autocorr_prep (sd_autocorr.hip) for the other passes that read the planes (sd_motif.hip): the text of n_reads reads
+// (read r at text + roff[r], rlen[r] bases, its planes from word pw[r] on; device arrays) into lo | hi | v of `words` words.
+void launch_autocorr_prep(hipStream_t st, unsigned grid, const uint8_t* text, const int64_t* roff, const int64_t* rlen, const int64_t* pw,
+                          int n_reads, int64_t words, uint64_t* lo, uint64_t* hi, uint64_t* v);
+#endif
 
 }  // namespace sd

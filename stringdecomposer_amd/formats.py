@@ -1280,3 +1280,165 @@ def screen_rows(regions, read_names, mono_names):
         out.append(ScreenRow(read_names[int(g["read"])], int(g["start"]), int(g["end_incl"]), int(g["n_chunks"]),
                              int(g["best_key"]) >> 16, mono_names[j] if j < n else mono_names[j - n] + "'"))
     return out
+
+
+# ---- motif hits (--motif): <out>_motif.tsv, <out>_motif_rows.tsv, <out>_motif_monomers.tsv -----------------------------------
+# <out>_motif.tsv: read, start, end (inclusive, like the final TSV), strand, motif, mismatches, sequence -- the matched
+# bases as the read has them, on - their reverse complement (a byte outside ACGT complements to N) -- in the order read,
+# start, motif (request order), strand.  <out>_motif_rows.tsv: one line per row of the final TSV: read, start, end, monomer,
+# then name:count of the motifs with a hit inside the row, in request order, comma-separated, * for none.
+# <out>_motif_monomers.tsv: monomer, motif, rows, rows with a hit, hits -- per monomer name as the final TSV prints it
+# (monomer-file order, forward before ') and per motif in request order.
+class Motifs:
+    """lib.motif / DeviceMotifs.to_host(): hits = a numpy record array (start, read, motif, strand, mismatches: sd_motif_hit
+    of include/sd_hip.h) in canonical order -- read, motif in request order, + before -, start; per = int64 [reads, motifs,
+    2], the hits per read, motif and strand; names, patterns: the request; E: the mismatches allowed."""
+
+    def __init__(self, hits, per, names, patterns, E):
+        self.hits, self.per, self.names, self.patterns, self.E = hits, per, list(names), list(patterns), int(E)
+
+    @property
+    def lengths(self):
+        return [len(p) for p in self.patterns]
+
+
+MotifRow = namedtuple("MotifRow", "read start end strand motif mismatches sequence")   # a line of <out>_motif.tsv
+MotifRowsRow = namedtuple("MotifRowsRow", "read start end monomer counts")              # ... of <out>_motif_rows.tsv; counts: ((motif, n), ...)
+MotifMonomerRow = namedtuple("MotifMonomerRow", "monomer motif rows rows_hit hits")     # ... of <out>_motif_monomers.tsv
+
+_MOTIF_RC = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def motif_sequence(seq, strand):
+    """the matched bases of a hit as a str: as they stand on +, the reverse complement on - (outside ACGT: N)"""
+    b = bytes(seq)
+    if strand in (1, "-"):
+        b = bytes(c if c in b"ACGT" else 78 for c in b).translate(_MOTIF_RC)[::-1]
+    return b.decode("latin-1")
+
+
+def motif_rows(motifs, read_names, reads):
+    """The lines of <out>_motif.tsv for a Motifs -> [MotifRow], in the order read, start, motif, strand"""
+    import numpy as np
+    h = motifs.hits
+    order = np.lexsort((h["strand"], h["motif"], h["start"], h["read"]))
+    lens = motifs.lengths
+    out = []
+    for x in h[order].tolist():   # (start, read, motif, strand, mismatches)
+        start, r, m, strand, mm = x
+        seq = reads[r]
+        seq = seq.encode() if isinstance(seq, str) else seq
+        out.append(MotifRow(read_names[r], start, start + lens[m] - 1, "-" if strand else "+", motifs.names[m], mm,
+                            motif_sequence(seq[start:start + lens[m]], strand)))
+    return out
+
+
+def format_motif(rows):
+    return "".join("%s\t%d\t%d\t%s\t%s\t%d\t%s\n" % tuple(r) for r in rows)
+
+
+def write_motif(path, rows):
+    _write_text(path, format_motif(rows))
+
+
+def _strand(x):
+    if x not in ("+", "-"):
+        raise ValueError("a strand is + or -, found %r" % x)
+    return x
+
+
+def read_motif(path):
+    """<out>_motif.tsv -> [MotifRow]."""
+    return _parse(path, False, 7, (_ident, int, int, _strand, _ident, int, _ident), MotifRow)
+
+
+def motif_row_counts(hits, final_rows, lengths, read_names=None):
+    """Per row of the final TSV and per motif, the hits that lie wholly inside the row: row.start <= start and end <=
+    row.end, with end = start + lengths[motif] - 1 -> int64 [rows, motifs].  A hit across a row boundary belongs to no row.
+    final_rows: FinalRow-like tuples (read, monomer, start, end, ...) whose read is an index into the job's reads, or a name
+    of read_names; the rows of a read ascending and disjoint, as the final TSV has them.  Plain numpy over two sorted
+    lists: the rows by (read, start), and for every hit the last row that starts at or before it."""
+    import numpy as np
+    lengths = np.asarray(lengths, dtype=np.int64)
+    index = {n: i for i, n in enumerate(read_names)} if read_names is not None else None
+    n = len(final_rows)
+    rr = np.fromiter(((index[r[0]] if index is not None else r[0]) for r in final_rows), dtype=np.int64, count=n)
+    rs = np.fromiter((r[2] for r in final_rows), dtype=np.int64, count=n)
+    re_ = np.fromiter((r[3] for r in final_rows), dtype=np.int64, count=n)
+    out = np.zeros((n, len(lengths)), dtype=np.int64)
+    if n == 0 or len(hits) == 0:
+        return out
+    order = np.lexsort((rs, rr))
+    key = (rr[order] << 42) + rs[order]
+    hs = hits["start"].astype(np.int64)
+    hm = hits["motif"].astype(np.int64)
+    at = np.searchsorted(key, (hits["read"].astype(np.int64) << 42) + hs, side="right") - 1
+    row = order[np.maximum(at, 0)]
+    inside = (at >= 0) & (rr[row] == hits["read"]) & (rs[row] <= hs) & (hs + lengths[hm] - 1 <= re_[row])
+    np.add.at(out, (row[inside], hm[inside]), 1)
+    return out
+
+
+def motif_row_lines(counts, final_rows, names):
+    """The lines of <out>_motif_rows.tsv -> [MotifRowsRow], one per row of the final TSV"""
+    return [MotifRowsRow(r[0], r[2], r[3], r[1], tuple((names[m], int(c)) for m, c in enumerate(counts[i]) if c > 0))
+            for i, r in enumerate(final_rows)]
+
+
+def motif_monomers(counts, final_rows, names, mono_names=None):
+    """The lines of <out>_motif_monomers.tsv -> [MotifMonomerRow]: per monomer name as the final rows print it and per
+    motif, the rows, the rows with a hit and the hits.  Order: mono_names (the monomer file's), each forward then with ',
+    then any other name as it first appears; motifs in request order."""
+    import numpy as np
+    seen = {}
+    for i, r in enumerate(final_rows):
+        seen.setdefault(r[1], []).append(i)
+    order = []
+    for m in (mono_names or ()):
+        order += [x for x in (m, m + "'") if x in seen]
+    order += [x for x in seen if x not in set(order)]
+    out = []
+    for mono in order:
+        c = np.asarray(counts)[seen[mono]]
+        for m, name in enumerate(names):
+            out.append(MotifMonomerRow(mono, name, len(seen[mono]), int((c[:, m] > 0).sum()), int(c[:, m].sum())))
+    return out
+
+
+def format_motif_rows(rows):
+    return "".join("%s\t%d\t%d\t%s\t%s\n" % (r.read, r.start, r.end, r.monomer, ",".join("%s:%d" % c for c in r.counts) or "*")
+                   for r in rows)
+
+
+def write_motif_rows(path, rows):
+    _write_text(path, format_motif_rows(rows))
+
+
+def _motif_counts(x):
+    if x == "*":
+        return ()
+    out = []
+    for item in x.split(","):
+        name, sep, c = item.rpartition(":")
+        if not sep or not name or int(c) < 1:
+            raise ValueError("expected name:count, found %r" % item)
+        out.append((name, int(c)))
+    return tuple(out)
+
+
+def read_motif_rows(path):
+    """<out>_motif_rows.tsv -> [MotifRowsRow]."""
+    return _parse(path, False, 5, (_ident, int, int, _ident, _motif_counts), MotifRowsRow)
+
+
+def format_motif_monomers(rows):
+    return "".join("%s\t%s\t%d\t%d\t%d\n" % tuple(r) for r in rows)
+
+
+def write_motif_monomers(path, rows):
+    _write_text(path, format_motif_monomers(rows))
+
+
+def read_motif_monomers(path):
+    """<out>_motif_monomers.tsv -> [MotifMonomerRow]."""
+    return _parse(path, False, 5, (_ident, _ident, int, int, int), MotifMonomerRow)

@@ -62,6 +62,8 @@ EXPORTS = [
     "sd_heat_kernel_bench",
     "sd_autocorr_layout", "sd_autocorr_host", "sd_autocorr_dev", "sd_autocorr_reads_dev", "sd_autocorr_positions", "sd_autocorr_peaks",
     "sd_autocorr_seed", "sd_autocorr_info", "sd_autocorr_kernel_bench",
+    "sd_motif_compile", "sd_motif_host", "sd_motif_dev", "sd_motif_reads_size_dev", "sd_motif_reads_write_dev", "sd_motif_info",
+    "sd_motif_kernel_bench",
     "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
     "sd_hor_rows", "sd_hor_final_host", "sd_hor_name", "sd_hor_info",
     "sd_dotplot_layout", "sd_dotplot_host", "sd_dotplot_dev", "sd_dotplot_reads_dev", "sd_dotplot_info", "sd_dotplot_hash", "sd_dotplot_kernel_bench",
@@ -293,6 +295,19 @@ def load():
     L.sd_autocorr_info.restype = None
     L.sd_autocorr_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_int64)]
+    L.sd_motif_compile.argtypes = [P(C.c_char_p), P(C.c_char_p), C.c_int32, C.c_int32, P(C.c_int32), C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_motif_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
+                                P(C.c_void_p), P(C.c_int64), C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_motif_dev.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
+                               P(C.c_void_p), P(C.c_int64), C.c_void_p, C.c_char_p, C.c_size_t]
+    L.sd_motif_reads_size_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, P(C.c_int64), C.c_char_p, C.c_size_t]
+    L.sd_motif_reads_write_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_char_p, C.c_size_t]
+    L.sd_motif_info.argtypes = [P(C.c_int64)]
+    L.sd_motif_info.restype = None
+    L.sd_motif_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64)]
     L.sd_dotplot_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
     L.sd_dotplot_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -1443,6 +1458,184 @@ def autocorr_kernel_bench(reads, k, D=4096, window=0, device=0, warmup=2, reps=5
         raise SdError(rc, "sd_autocorr_kernel_bench")
     out = {"prep_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b]}
     out.update(zip(("launches", "workgroups", "cells", "words"), [int(x) for x in info]))
+    return out
+
+
+MOTIF_BUILTIN = {"cenpb": "NTTCGNNNNANNCGGGN"}   # the CENP-B box of alpha-satellite monomers
+MOTIF_LMAX = 64
+MOTIF_EMAX = 7
+MOTIF_MAX = 1024
+MOTIF_ITEMS_MAX = 1 << 24
+MOTIF_HITS_MAX = 1 << 28
+MOTIF_TILE_WORDS = 256
+
+
+def motif_hit_dtype():
+    """sd_motif_hit (include/sd_hip.h) as a numpy dtype: 16 bytes"""
+    import numpy as np
+    return np.dtype([("start", "<i8"), ("read", "<i4"), ("motif", "<u2"), ("strand", "u1"), ("mismatches", "u1")])
+
+
+def motif_request(motifs):
+    """The motifs of a request -> (names, patterns).  motifs: a dict name -> pattern, or a list whose items are (name,
+    pattern) pairs, built-in names (MOTIF_BUILTIN) or "NAME=PATTERN" strings, in request order."""
+    if isinstance(motifs, dict):
+        motifs = list(motifs.items())
+    elif isinstance(motifs, (str, bytes)):
+        motifs = [motifs]
+    names, patterns = [], []
+    for m in motifs:
+        if isinstance(m, (tuple, list)) and len(m) == 2:
+            name, pat = m
+        else:
+            spec = m.decode() if isinstance(m, bytes) else str(m)
+            if "=" in spec:
+                name, pat = spec.split("=", 1)
+            elif spec in MOTIF_BUILTIN:
+                name, pat = spec, MOTIF_BUILTIN[spec]
+            else:
+                raise SdError(SD_ERR_PARAM, "motif '%s' is neither NAME=PATTERN nor one of the built-in motifs (%s)"
+                              % (spec, ", ".join(sorted(MOTIF_BUILTIN))))
+        names.append(name.decode() if isinstance(name, bytes) else str(name))
+        patterns.append(pat.decode() if isinstance(pat, bytes) else str(pat))
+    return names, patterns
+
+
+def _motif_mismatches(E, who):
+    if not isinstance(E, int) or isinstance(E, bool) or not -(1 << 31) <= E < (1 << 31):
+        raise SdError(SD_ERR_PARAM, "%s: mismatches = %r, must be an integer 0 .. %d" % (who, E, MOTIF_EMAX))
+    return E
+
+
+MotifStrand = namedtuple("MotifStrand", "motif strand length constrained palindrome")
+
+
+def motif_compile(motifs, E=0):
+    """sd_motif_compile: the request checked -- names, patterns, E, the library's refusal as SdError -- and its
+    pattern-strands -> (names, patterns, [MotifStrand]): two per motif (+ then -), one for a palindrome."""
+    import numpy as np
+    names, patterns = motif_request(motifs)
+    E = _motif_mismatches(E, "motif_compile")
+    n = len(names)
+    table = np.zeros((2 * max(n, 1), 5), dtype=np.int32)
+    ns = C.c_int32(0)
+    err = C.create_string_buffer(1024)
+    _text_check(load().sd_motif_compile(_strs(names), _strs(patterns), n, E, C.byref(ns), table.ctypes.data, err, 1024), err)
+    return names, patterns, [MotifStrand(*(int(x) for x in row)) for row in table[:ns.value]]
+
+
+def motif_info():
+    """sd_motif_info -> {"tile": words of a workgroup's tile (64 starts each), "pattern_block": pattern-strands a workgroup
+    takes, "launch_work": the most start x pattern-strand products of one launch, "launches": launches of the size and
+    write kernels in this process so far}"""
+    info = (C.c_int64 * 4)()
+    load().sd_motif_info(info)
+    return dict(zip(("tile", "pattern_block", "launch_work", "launches"), (int(x) for x in info)))
+
+
+def motif_text(text, read_off, read_lens, motifs, E=0, device=None, threads=1):
+    """motif on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any order
+    of offsets are allowed) -> formats.Motifs"""
+    import numpy as np
+    from . import formats
+    names, patterns, _ = motif_compile(motifs, E)
+    L = load()
+    tb = _b(text)
+    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
+        raise SdError(SD_ERR_PARAM, "motif: offsets and lengths differ in number, or a read lies outside the text")
+    per = np.zeros((len(rl), len(names), 2), dtype=np.int64)
+    out, n = C.c_void_p(0), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    if device is None:
+        rc = L.sd_motif_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(threads),
+                             C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
+    else:
+        rc = L.sd_motif_dev(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(device),
+                            C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
+    _text_check(rc, err)
+    try:
+        hits = np.frombuffer(C.string_at(out.value, 16 * n.value), dtype=motif_hit_dtype()).copy() if n.value else np.zeros(0, dtype=motif_hit_dtype())
+    finally:
+        L.sd_free(out)
+    return formats.Motifs(hits, per, names, patterns, E)
+
+
+def motif(reads, motifs, E=0, device=None, threads=1):
+    """The hits of IUPAC motifs on both strands of every read (include/sd_hip.h: sd_motif_*): Hamming matches with at most E
+    mismatches at the constrained positions, every hit reported.  reads: a list of bytes / str, or a DeviceReads (then the
+    kernels read the device text where it lies).  motifs: see motif_request.  device=None: host threads (sd_motif_host);
+    else the kernels of csrc/sd_motif.hip on that device.  Both give the same arrays.  -> formats.Motifs"""
+    if isinstance(reads, DeviceReads):
+        return motif_device(reads, motifs, E).to_host()
+    text, ro, rl = _autocorr_reads(reads)
+    return motif_text(text, ro, rl, motifs, E, device, threads)
+
+
+class DeviceMotifs(namedtuple("DeviceMotifs", "hits per n_hits names patterns E")):
+    """The motif hits of a DeviceReads in device memory (motif_device): hits = uint8 [n_hits, 16], the sd_motif_hit records
+    in canonical order; per = int64 [reads, motifs, 2]; torch tensors on the reads' device.  names, patterns, E: the request
+    they answer."""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> formats.Motifs (waits for the device)"""
+        import numpy as np
+        from . import formats
+        raw = self.hits.cpu().numpy()
+        hits = np.frombuffer(raw.tobytes(), dtype=motif_hit_dtype()).copy() if self.n_hits else np.zeros(0, dtype=motif_hit_dtype())
+        return formats.Motifs(hits, self.per.cpu().numpy(), self.names, self.patterns, self.E)
+
+
+def motif_device(reads, motifs, E=0, stream=None, hits=None, per=None):
+    """motif on a DeviceReads, everything on the reads' device (sd_motif_reads_size_dev / sd_motif_reads_write_dev) ->
+    DeviceMotifs(hits, per, n_hits, ...).  torch allocates the results on `stream` (None: the device's current stream) -- or hits (uint8, at least
+    16 bytes per hit) and per (int64, reads x motifs x 2) are used, whatever they hold -- and the library fills them there.
+    The host waits once, for the number of hits; the call returns with the write kernels in flight."""
+    names, patterns, _ = motif_compile(motifs, E)
+    import torch
+    L = load()
+    dev = torch.device("cuda", reads.device)
+    st = _torch_stream(torch, dev, stream)
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    nm = len(names)
+    with torch.cuda.stream(st):
+        if per is None:
+            per = torch.empty((reads.n, nm, 2), dtype=torch.int64, device=dev)
+        elif per.dtype != torch.int64 or per.numel() != reads.n * nm * 2 or per.device != dev or not per.is_contiguous():
+            raise SdError(SD_ERR_PARAM, "motif_device: per must be a contiguous int64 tensor of %d x %d x 2 elements on %s" % (reads.n, nm, dev))
+    pats = _strs(patterns)
+    n = C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    dptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else 0)
+    _text_check(L.sd_motif_reads_size_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, E, dev.index or 0,
+                                          C.c_void_p(st.cuda_stream), dptr(per), C.byref(n), err, 1024), err)
+    if hits is None:
+        with torch.cuda.stream(st):
+            hits = torch.empty((n.value, 16), dtype=torch.uint8, device=dev)
+    elif hits.dtype != torch.uint8 or hits.device != dev or not hits.is_contiguous():
+        raise SdError(SD_ERR_PARAM, "motif_device: hits must be a contiguous uint8 tensor on %s" % (dev,))
+    _text_check(L.sd_motif_reads_write_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, E, dev.index or 0,
+                                           C.c_void_p(st.cuda_stream), dptr(hits), hits.numel() // 16, err, 1024), err)
+    return DeviceMotifs(hits.view(-1)[:16 * n.value].view(n.value, 16), per.view(reads.n, nm, 2), int(n.value), names, patterns, E)
+
+
+def motif_kernel_bench(reads, motifs, E=0, device=0, warmup=2, reps=5):
+    """sd_motif_kernel_bench -> {"prep_ms", "size_ms", "write_ms": [...], "launches", "items", "hits", "words"}."""
+    names, patterns, _ = motif_compile(motifs, E)
+    text, ro, rl = _autocorr_reads(reads)
+    a, b, c = ((C.c_float * reps)() for _ in range(3))
+    info = (C.c_int64 * 4)()
+    rc = load().sd_motif_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(device),
+                                      int(warmup), int(reps), a, b, c, info)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_motif_kernel_bench")
+    out = {"prep_ms": [float(x) for x in a], "size_ms": [float(x) for x in b], "write_ms": [float(x) for x in c]}
+    out.update(zip(("launches", "items", "hits", "words"), [int(x) for x in info]))
     return out
 
 

@@ -39,6 +39,7 @@ class _LazyNumpy:
 np = _LazyNumpy()
 
 from . import autocorr
+from . import motif
 from . import dotplot
 from . import split
 from . import hor
@@ -739,6 +740,7 @@ def main(argv=None):
     dotplot.add_arguments(parser)
     split.add_arguments(parser)
     hor.add_arguments(parser)
+    motif.add_arguments(parser)
     parser.add_argument("--screen", type=int, default=None, metavar="THR",
                         help="decompose only the stretches where a monomer occurs: a chunk (-b, -v) is kept when some monomer "
                              "or reverse complement lies within infix edit distance THR of it, runs of kept chunks are "
@@ -766,6 +768,8 @@ def main(argv=None):
         split.check(args)
     if args.hor:
         hor.check(args)
+    if motif.wanted(args):
+        motif.check(args)
     if args.profile:
         _check_profile(args)
     if args.msa:
@@ -905,6 +909,15 @@ def main(argv=None):
             logger.info("--hor failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
             sys.exit(e.code if 0 < e.code < 256 else 1)
         logger.info("Saved the higher-order repeat units to " + ", ".join(saved))
+
+    if motif.wanted(args):
+        try:
+            saved = motif.write(args, convert_tsv_fn, args.out_dir, args.out_file, devices[0] if devices else args.device)
+        except lib.SdError as e:
+            sys.stderr.write("--motif failed: " + e.msg + "\n")
+            logger.info("--motif failed (%s); the decomposition is in %s" % (e.msg, convert_tsv_fn))
+            sys.exit(e.code if 0 < e.code < 256 else 1)
+        logger.info("Saved the motif hits of the reads to " + ", ".join(saved))
 
     logger.info("Thank you for using StringDecomposer!")
 
