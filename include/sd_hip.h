@@ -854,17 +854,36 @@ int sd_identity_segments(const char* seq, int64_t seqlen, const int64_t* starts,
                          const int32_t* pair_tmpl, int32_t homo, int32_t threads, int32_t* dist,
                          int32_t* matches, int32_t* columns);
 
-/* The same on the device (csrc/sd_nw.hip: one lane per (segment, template) pair, Myers bit-vectors with
- * a per-lane delta history in HBM and edlib's traceback priority): identical results.  Returns
- * SD_ERR_NO_DEVICE without a GPU and SD_ERR_UNSUPPORTED for input the kernel does not take (a symbol
- * outside ACGTN, a template longer than 512 bp, a segment longer than 65000 bp, a pair long enough for
- * edlib's Hirschberg split) -- callers then use
- * sd_identity_segments.  Device buffers are kept between calls (sd_nw_release_cache frees them). */
+/* The same on the device (csrc/sd_nw.hip, Myers bit-vectors and edlib's traceback priority): identical results.
+ * The route follows the longest template AFTER the homopolymer compression of a homo call:
+ *   up to 512 bp   one lane per (segment, template) pair, a per-lane delta history in HBM.  The call as a whole is
+ *                  SD_ERR_UNSUPPORTED when the longest segment against the longest template (lengths before
+ *                  compression) is long enough for edlib's Hirschberg split: 20 * ceil(q / 64) * t + 8 * t >= 2^20.
+ *   513 .. 2048 bp a pair across 16 or 32 lanes (csrc/sd_nw_long.hip).  The pairs are dealt one by one, by their
+ *                  lengths before compression: a pair edlib would split, and every pair of a segment longer than 8192
+ *                  symbols, is aligned by host threads inside the same call (under the kernel); the others go to
+ *                  the device.  The results are the same wherever a pair went.
+ *   beyond 2048 bp SD_ERR_UNSUPPORTED.
+ * Also SD_ERR_UNSUPPORTED: a symbol outside ACGTN in a template or the text, a segment longer than 65000 bp, no
+ * device memory for the call's buffers.  Callers then use sd_identity_segments.
+ * SD_ERR_NO_DEVICE without a GPU.  Device buffers are kept between calls (sd_nw_release_cache frees them). */
 int sd_identity_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends,
                              int64_t n_seg, const char* const* tmpl, const int32_t* tlen, int32_t T,
                              const int32_t* pair_tmpl, int32_t homo, int32_t device, int32_t threads,
                              int32_t* dist, int32_t* matches, int32_t* columns);
 void sd_nw_release_cache(void);
+
+/* Which route the device identity calls of this process took (sd_identity_segments_dev and every caller of the same
+ * driver: the file job's post-processing, the stream's fallback).  Cumulative, read-only, never reset:
+ *   [0] long_calls       calls that took the 513 .. 2048 bp route
+ *   [1] long_pairs       pairs of those calls handed to the kernel of csrc/sd_nw_long.hip
+ *   [2] long_host_pairs  pairs of those calls dealt to host threads (pairs with an empty side are in neither count)
+ *   [3] long_rounds_max  the most rounds of pairs a workgroup of one long launch took: ceil(pairs / (grid * slots))
+ *   [4] short_calls      calls that took the route of templates up to 512 bp
+ *   [5] short_pairs      their pairs (all of them: that route deals nothing to the host)
+ *   [6] declined_calls   calls that returned SD_ERR_UNSUPPORTED
+ *   [7] 0 (reserved) */
+void sd_nw_route_counts(int64_t out[8]);
 
 /* ---- monomer column profiles (--profile) -----------------------------------------------------------------------
  * The alignment behind a row's identity (edlib NW path of the block against its monomer, Hirschberg's split where

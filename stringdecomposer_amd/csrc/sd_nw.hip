@@ -268,10 +268,26 @@ struct NwLap {
 };
 }  // namespace
 
+// which route the calls of this process took (sd_nw_route_counts): [0] long calls, [1] pairs handed to sd_nw_long,
+// [2] pairs of those calls dealt to host threads, [3] largest number of rounds a workgroup of a long launch took,
+// [4] short calls, [5] their pairs, [6] calls that returned SD_ERR_UNSUPPORTED, [7] 0
+static std::atomic<long long> g_nw_routes[8];
+static int nw_identity_device_routed(const std::vector<std::pair<const char*, int64_t>>& spans, const int64_t* seg_start,
+                                     const int32_t* seg_len, int64_t n_seg, const std::vector<std::string>& tmpl,
+                                     const int32_t* pair_tmpl, bool homo, int device, int threads, int32_t* dist,
+                                     int32_t* matches);
 int nw_identity_device(const std::vector<std::pair<const char*, int64_t>>& spans, const int64_t* seg_start,
                        const int32_t* seg_len, int64_t n_seg, const std::vector<std::string>& tmpl,
                        const int32_t* pair_tmpl, bool homo, int device, int threads, int32_t* dist,
                        int32_t* matches) {
+    const int rc = nw_identity_device_routed(spans, seg_start, seg_len, n_seg, tmpl, pair_tmpl, homo, device, threads, dist, matches);
+    if (rc == SD_ERR_UNSUPPORTED) ++g_nw_routes[6];
+    return rc;
+}
+static int nw_identity_device_routed(const std::vector<std::pair<const char*, int64_t>>& spans, const int64_t* seg_start,
+                                     const int32_t* seg_len, int64_t n_seg, const std::vector<std::string>& tmpl,
+                                     const int32_t* pair_tmpl, bool homo, int device, int threads, int32_t* dist,
+                                     int32_t* matches) {
     const int T = (int)tmpl.size();
     const int64_t n_pairs = pair_tmpl ? n_seg : n_seg * (int64_t)T;
     if (n_pairs == 0) return SD_OK;
@@ -405,6 +421,13 @@ int nw_identity_device(const std::vector<std::pair<const char*, int64_t>>& spans
                                homo ? 1 : 0, qcap_dev, cap, g_nw.ck.p, static_cast<int32_t*>(g_nw.dist.p), static_cast<int32_t*>(g_nw.matches.p));
             if (hipGetLastError() != hipSuccess) return SD_ERR_HIP;
         }
+        {   // (under the lock: the maximum needs no compare-and-swap loop)
+            const long long rounds = (long long)((nd + (int64_t)grid * slots - 1) / ((int64_t)grid * slots));
+            ++g_nw_routes[0];
+            g_nw_routes[1] += (long long)nd;
+            g_nw_routes[2] += (long long)host_pairs.size();
+            if (rounds > g_nw_routes[3].load()) g_nw_routes[3] = rounds;
+        }
         // the pairs edlib splits: host threads, under the kernel
         int hrc = SD_OK;
         if (!host_pairs.empty()) {
@@ -503,6 +526,8 @@ int nw_identity_device(const std::vector<std::pair<const char*, int64_t>>& spans
                             static_cast<int32_t*>(g_nw.dist.p), static_cast<int32_t*>(g_nw.matches.p));
         if (hipGetLastError() != hipSuccess) return SD_ERR_HIP;
     }
+    ++g_nw_routes[4];
+    g_nw_routes[5] += (long long)n_pairs;
     lap.to(2);
     if (hipMemcpy(dist, g_nw.dist.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(matches, g_nw.matches.p, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost) != hipSuccess)
@@ -671,6 +696,10 @@ int nw_profile_device(const std::vector<std::pair<const char*, int64_t>>& spans,
 }
 }  // namespace sd
 
+extern "C" void sd_nw_route_counts(int64_t out[8]) {
+    for (int i = 0; i < 8; ++i) out[i] = (int64_t)sd::g_nw_routes[i].load();
+}
+
 extern "C" int sd_identity_segments_dev(const char* seq, int64_t seqlen, const int64_t* starts, const int64_t* ends,
                                         int64_t n_seg, const char* const* tmpl, const int32_t* tlen, int32_t T,
                                         const int32_t* pair_tmpl, int32_t homo, int32_t device, int32_t threads,
@@ -691,7 +720,7 @@ extern "C" int sd_identity_segments_dev(const char* seq, int64_t seqlen, const i
     for (int64_t s = 0; s < n_seg; ++s) {
         if (starts[s] < 0 || ends[s] >= seqlen) return SD_ERR_PARAM;
         const int64_t l = std::max<int64_t>(0, ends[s] - starts[s] + 1);
-        if (l > 65000) return SD_ERR_UNSUPPORTED;
+        if (l > 65000) { ++sd::g_nw_routes[6]; return SD_ERR_UNSUPPORTED; }
         ln[(size_t)s] = (int32_t)l;
         if (l > 0) { lo = std::min(lo, starts[s]); hi = std::max(hi, ends[s] + 1); }
     }

@@ -35,6 +35,7 @@ EXPORTS = [
     "sd_decompose_chunk_range", "sd_assemble_tsv", "sd_release_cache", "sd_format_alt_rows",
     "sd_stream_create", "sd_stream_destroy", "sd_stream_submit", "sd_stream_collect", "sd_stream_stats",
     "sd_stream_info", "sd_pack_bases", "sd_identity_segments_dev", "sd_nw_release_cache", "sd_last_run_stats", "sd_guard_trips",
+    "sd_nw_route_counts",
     "sd_run_files", "sd_convert_raw_tsv", "sd_decompose_files_range", "sd_assemble_files_tsv",
     "sd_host_stage_rates", "sd_run_files_range", "sd_plan_info", "sd_write_parts_selftest", "sd_convert_raw_tsv_range",
     "sd_write_records", "sd_read_records", "sd_records_free", "sd_records_to_raw_tsv", "sd_decompose_files_records",
@@ -458,6 +459,19 @@ def guard_trips():
     L = load()
     L.sd_guard_trips.restype = C.c_int64
     return int(L.sd_guard_trips())
+
+
+NW_ROUTE_KEYS = ("long_calls", "long_pairs", "long_host_pairs", "long_rounds_max", "short_calls", "short_pairs", "declined_calls")
+
+
+def nw_route_counts():
+    """Which route the device identity calls of this process took so far (sd_nw_route_counts): a dict of the cumulative
+    counts NW_ROUTE_KEYS.  Host only; all zero before the first device call."""
+    L = load()
+    v = (C.c_int64 * 8)()
+    L.sd_nw_route_counts.restype = None
+    L.sd_nw_route_counts(v)
+    return {k: int(v[i]) for i, k in enumerate(NW_ROUTE_KEYS)}
 
 
 def plan_info(mono_seqs, **kw):

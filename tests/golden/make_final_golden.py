@@ -218,7 +218,24 @@ def main():
         emit(work, name, os.path.join(d, "reads.fa"), os.path.join(d, "monomers.fa"), ["--second-best"], rel,
              keep_alt=True, alt_limit=100 * 1000)   # (the _alt text of the widest sets is kept as its sha256 only)
         emit(work, name, os.path.join(d, "reads.fa"), os.path.join(d, "monomers.fa"), [], rel, keep_alt=False, suffix="_light")
+    long_monomer_jobs(work)
     shutil.rmtree(work, ignore_errors=True)
+
+
+def long_monomer_jobs(work):
+    """Monomers of 513 .. 2048 bp (random ACGT), two reads each: the identities of such a job come from csrc/sd_nw_long.hip
+    through the post-processing (tests/test_gpu_long_ident.py), the decomposition from the fast family's widest layouts.
+    long_k17: K = 17 words with both lane-group edges (1024 / 1025 bp) and no block that edlib splits against a monomer;
+    long_k32_mixed: K = 32, and blocks of ~2 kb against the 2-kb monomers pass 1 MB of traceback data (host threads)."""
+    for name, lens, seed, read_len in (("long_k17", [513, 1024, 1025], 81, 9000), ("long_k32_mixed", [640, 1500, 2048], 83, 10000)):
+        d = os.path.join(OUT, name)
+        os.makedirs(d, exist_ok=True)
+        ms = [synth._ACGT[synth.Stream(seed, 10 + j).below(ln, 4)].tobytes() for j, ln in enumerate(lens)]
+        rn, rs = synth.make_reads(ms, 2, read_len=read_len, seed=seed)
+        synth.write_fasta(os.path.join(d, "reads.fa"), rn, rs, width=80)
+        synth.write_fasta(os.path.join(d, "monomers.fa"), ["K%d" % j for j in range(len(ms))], ms)
+        emit(work, name, os.path.join(d, "reads.fa"), os.path.join(d, "monomers.fa"), ["--second-best"],
+             ["final/%s/reads.fa" % name, "final/%s/monomers.fa" % name], keep_alt=True)
 
 
 if __name__ == "__main__":

@@ -144,6 +144,9 @@ def test_device_final_equals_reference_goldens(name, sub_batches):
             assert alt == f.read()
     assert hashlib.sha256(alt).hexdigest() == c["alt_sha256"]
     assert len(fr.rows) == c["final_rows"] == stats["final_rows"]
+    if name in ("long_k17", "long_k32_mixed"):   # monomers beyond 512 bp: the in-stream kernels decline the set, every
+        assert stats["ident_pairs"] == 0 and stats["fallback_blocks"] > 0   # identity comes from the text-based path
+        return
     assert stats["ident_pairs"] > 0
     if name == "long_block":
         assert stats["fallback_blocks"] > 0

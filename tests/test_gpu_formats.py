@@ -22,7 +22,8 @@ def _sha(b):
     return hashlib.sha256(b).hexdigest()
 
 
-@pytest.mark.parametrize("name", ["td_light", "td_second_best", "td_second_best_i95", "syn64_second_best", "tiled_second_best"])
+@pytest.mark.parametrize("name", ["td_light", "td_second_best", "td_second_best_i95", "syn64_second_best", "tiled_second_best",
+                                  "long_k17", "long_k32_mixed"])
 def test_cli_files_parse_and_re_emit_through_the_formats_api(name, tmp_path):
     """bin/stringdecomposer ... --records on a golden job of the unmodified reference command line: each of the three
     text files parses with formats.read_* and re-emits byte for byte (= the golden), the starred _alt rows are the

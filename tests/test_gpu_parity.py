@@ -567,7 +567,8 @@ def test_stream_rows_equal_oracle(oracle, sub, cap):
 def test_nw_identity_kernel_equals_host_and_edlib(shape):
     """K3 (main.py:29-60,107-150): the device identity kernel (one lane per (segment, template) pair) against
     the host implementation -- itself pinned against the reference's vendored edlib on CPU -- for every pair,
-    all-vs-all and own-template, plain and homopolymer-compressed, and against edlib directly on a sample."""
+    all-vs-all and own-template, plain and homopolymer-compressed, and against edlib directly on a sample.  Every device
+    call moves the route counters (lib.nw_route_counts) by what the dealing rule of tests/long_ident_cases.py gives for it."""
     import edlib_ref
     nm, lo, hi = shape
     st = synth.Stream(77, nm * 100 + lo)
@@ -593,13 +594,34 @@ def test_nw_identity_kernel_equals_host_and_edlib(shape):
     starts[5:7] = np.minimum(starts[5:7], len(seq) - 2700)
     ends = starts + lens - 1
     pair = st.below(n, len(tm)).astype(np.int32)
+    import long_ident_cases as lc
+    tmb = [t.encode() for t in tm]
+
+    def routed(before, pt):
+        """The device call between `before` and now took the route the dealing rule gives it (lib.identity_segments runs the
+        host form without a word when the device declines: equal results alone do not show which code ran)."""
+        after = lib.nw_route_counts()
+        moved = {k: after[k] - before[k] for k in lc.COUNT_KEYS}
+        exp = lc.expected_counts([int(x) for x in lens], tmb, homo, pt)
+        assert moved == exp, (shape, homo, moved, exp)
+        if hi > 512 and not homo:
+            assert moved["long_calls"] == 1
+        if moved["long_calls"]:      # by the rule no pair of (4, 520, 1000) splits, about a tenth of the other two shapes' do
+            assert moved["long_pairs"] > 0 and moved["short_pairs"] == 0
+            assert (moved["long_host_pairs"] > 0) == (hi > 1000)
+        else:
+            assert moved["short_pairs"] > 0 and moved["declined_calls"] == 0
     for homo in (False, True):
         h = lib.identity_segments(seq, starts, ends, tm, homo, threads=8)
+        before = lib.nw_route_counts()
         d = lib.identity_segments(seq, starts, ends, tm, homo, threads=8, device=0)
+        routed(before, None)
         for a, b in zip(h, d):
             assert (a == b).all(), (shape, homo)
         hp = lib.identity_segments(seq, starts, ends, tm, homo, threads=8, pair_tmpl=pair)
+        before = lib.nw_route_counts()
         dp = lib.identity_segments(seq, starts, ends, tm, homo, threads=8, pair_tmpl=pair, device=0)
+        routed(before, pair)
         for a, b in zip(hp, dp):
             assert (a == b).all(), (shape, homo, "pair")
         for s_ in range(0, n, 37):

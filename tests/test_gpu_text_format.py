@@ -224,7 +224,8 @@ def test_final_goldens_from_device_streams(name):
         if os.path.exists(gz):
             with gzip.open(gz, "rb") as f:
                 assert text == f.read()
-    assert (stats["fallback_blocks"] > 0) == (name == "long_block")
+    # (long_k17 / long_k32_mixed: monomers beyond 512 bp, which the in-stream identity kernels decline)
+    assert (stats["fallback_blocks"] > 0) == (name in ("long_block", "long_k17", "long_k32_mixed"))
 
 
 @pytest.mark.parametrize("name", ["td_default", "syn12_ties", "syn64_10kb"])
