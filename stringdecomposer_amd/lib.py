@@ -424,6 +424,132 @@ def _strs(seq):
     return arr
 
 
+# ---- the call frame of the analyses: what profile, msa, lags, heat, autocorr, motif, dotplot, split and hor share on this side
+# of the C-ABI (csrc/sd_job_dev.hpp is the frame on the other side; DESIGN.md, "the Python side of the frame") ----------------
+def _err():
+    """the buffer an entry writes its refusal into (errbuf, 1024)"""
+    return C.create_string_buffer(1024)
+
+
+def _check(rc, what):
+    """an entry without errbuf: the refusal names the entry"""
+    if rc != SD_OK:
+        raise SdError(rc, what)
+
+
+def _text_check(rc, err, fallback=""):
+    """an entry with errbuf: its text, or `fallback` where it left none"""
+    if rc != SD_OK:
+        raise SdError(rc, err.value.decode(errors="replace") or fallback)
+
+
+def _is_int(x):
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def _int_arg(who, name, v, lo, hi, say=None, bools=False):
+    """who: name = v, must be an integer lo .. hi -- refused before any array is made or any device is touched.  say: the
+    words behind "must be an integer" where they are not the range checked (", 1 or more" with hi the C type's limit);
+    hi=None, no upper limit, needs them."""
+    assert hi is not None or say is not None
+    if not (_is_int(v) or (bools and isinstance(v, bool))) or v < lo or (hi is not None and v > hi):
+        raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer%s" % (who, name, v, " %d .. %d" % (lo, hi) if say is None else say))
+    return v
+
+
+_Segments = namedtuple("_Segments", "lead n G go pt tb arrays")
+
+
+def _segments(who, text, starts, ends, group_off=None, pair_tmpl=None, templates=None):
+    """The arguments of a segment call as ctypes takes them: .lead = (text, its length, starts, ends, n), then (group_off,
+    groups) and (templates, their lengths, T, pair_tmpl or NULL) for those given -- the order of every sd_*_segments entry;
+    .n segments, .G groups, .go / .pt the int64 group_off / int32 pair_tmpl arrays, .tb the templates as bytes.  who: the
+    caller's name for the refusal of lengths that differ; None: no check (the kernel benches).  The result owns the arrays
+    behind the addresses: keep it until the call has returned."""
+    import numpy as np
+    sb = _b(text)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    en = np.ascontiguousarray(ends, dtype=np.int64)
+    n = int(st.shape[0])
+    lead, G, go, pt, tb = [sb, len(sb), st.ctypes.data, en.ctypes.data, n], None, None, None, None
+    if group_off is not None:
+        go = np.ascontiguousarray(group_off, dtype=np.int64)
+        if who and (en.shape[0] != n or go.ndim != 1 or go.shape[0] < 1):
+            raise SdError(SD_ERR_PARAM, "%s: starts and ends differ in length, or group_off is empty" % who)
+        G = len(go) - 1
+        lead += [go.ctypes.data, G]
+    if pair_tmpl is not None:
+        pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
+        if who and (en.shape[0] != n or pt.shape[0] != n):
+            raise SdError(SD_ERR_PARAM, "%s: starts, ends and pair_tmpl differ in length" % who)
+    if templates is not None:
+        tb = [_b(t) for t in templates]
+        tl = (C.c_int32 * max(len(tb), 1))(*[len(t) for t in tb])
+        lead += [_strs(tb), tl, len(tb), None if pt is None else pt.ctypes.data]
+    return _Segments(tuple(lead), n, G, go, pt, tb, (st, en))
+
+
+def _reads_text(reads):
+    """a list of bytes / str -> (text, offsets, lengths): the reads back to back"""
+    import numpy as np
+    rs = [_b(s) for s in reads]
+    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64).reshape(-1)
+    ro = np.zeros(len(rs), dtype=np.int64)
+    if len(rs) > 1:
+        np.cumsum(rl[:-1], out=ro[1:])
+    return b"".join(rs), ro, rl
+
+
+def _text_reads(who, text, read_off, read_lens):
+    """reads given as one buffer with offsets and lengths, as the *_text calls take them -> (text, offsets, lengths), every
+    read inside the text"""
+    import numpy as np
+    tb = _b(text)
+    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
+    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
+    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
+        raise SdError(SD_ERR_PARAM, "%s: offsets and lengths differ in number, or a read lies outside the text" % who)
+    return tb, ro, rl
+
+
+def segment_clamp(start, end, n):
+    """A final row's (start, end) in a read of n bases -> (s0, e), the inclusive segment as the selection measured it; an
+    empty segment has e = s0 - 1."""
+    s0 = min(max(start, 0), n)
+    return s0, min(max(end + 1, s0), n) - 1
+
+
+def _device_frame(dev, stream):
+    """(torch, dev, st) of a call on device tensors: dev = a torch device or an ordinal, st = the torch stream of `stream`
+    (_torch_stream)"""
+    import torch
+    if isinstance(dev, int):
+        dev = torch.device("cuda", dev)
+    return torch, dev, _torch_stream(torch, dev, stream)
+
+
+def _dptr(t):
+    """the device address of a tensor; NULL for None and for a tensor without elements"""
+    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+
+
+def _bench(fn, lead, ms_names, info_names, reps):
+    """fn(*lead, one float [reps] per name of ms_names, info) of a *_kernel_bench entry -> {name: [ms], ..., name: int, ...}"""
+    ms = [(C.c_float * reps)() for _ in ms_names]
+    info = (C.c_int64 * len(info_names))()
+    _check(fn(*lead, *ms, info), fn.__name__)
+    out = {k: [float(x) for x in v] for k, v in zip(ms_names, ms)}
+    out.update(zip(info_names, (int(x) for x in info)))
+    return out
+
+
+def _info(fn, names, slots=None):
+    """fn(info) of a sd_*_info entry -> {name: int}"""
+    info = (C.c_int64 * (slots or len(names)))()
+    fn(info)
+    return dict(zip(names, (int(x) for x in info)))
+
+
 FLAG_NO_F16, FLAG_FULL_FLOOR, FLAG_NO_EDTHR_COMPACT, FLAG_FILTER_GENERAL, FLAG_NO_STREAM_IDENT, FLAG_PROGRESS = 1, 2, 4, 8, 16, 32
 FLAG_TRACE_V1 = 64
 FLAG_NO_IDENT_PRUNE = 256   # --second-best: every homopolymer-compressed pair aligned in full (no distance-only pruning)
@@ -640,26 +766,14 @@ def profile_segments(seq, starts, ends, templates, pair_tmpl, threads=1, device=
     import numpy as np
     from . import formats
     L = load()
-    sb = _b(seq)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
-    n = int(st.shape[0])
-    if en.shape[0] != n or pt.shape[0] != n:
-        raise SdError(SD_ERR_PARAM, "profile_segments: starts, ends and pair_tmpl differ in length")
-    tb = [_b(t) for t in templates]
-    T = len(tb)
-    tl = (C.c_int32 * max(T, 1))(*[len(t) for t in tb])
-    counts = np.zeros(sum(len(t) + 1 for t in tb) * formats.PROFILE_NCOLS, dtype=np.uint64)
+    seg = _segments("profile_segments", seq, starts, ends, pair_tmpl=pair_tmpl, templates=templates)
+    counts = np.zeros(sum(len(t) + 1 for t in seg.tb) * formats.PROFILE_NCOLS, dtype=np.uint64)
     if device is None:
-        rc = L.sd_profile_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data,
-                                   int(threads), counts.ctypes.data)
+        rc = L.sd_profile_segments(*seg.lead, int(threads), counts.ctypes.data)
     else:
-        rc = L.sd_profile_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data,
-                                       int(device), int(threads), counts.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_profile_segments" + ("" if device is None else "_dev"))
-    return formats.split_counts([len(t) for t in tb], counts.astype(np.int64))
+        rc = L.sd_profile_segments_dev(*seg.lead, int(device), int(threads), counts.ctypes.data)
+    _check(rc, "sd_profile_segments" + ("" if device is None else "_dev"))
+    return formats.split_counts([len(t) for t in seg.tb], counts.astype(np.int64))
 
 
 def msa_row_offsets(tlen, pair_tmpl):
@@ -684,31 +798,20 @@ def msa_segments(seq, starts, ends, templates, pair_tmpl, threads=1, device=None
     import numpy as np
     from . import formats
     L = load()
-    sb = _b(seq)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
-    n = int(st.shape[0])
-    if en.shape[0] != n or pt.shape[0] != n:
-        raise SdError(SD_ERR_PARAM, "msa_segments: starts, ends and pair_tmpl differ in length")
-    tb = [_b(t) for t in templates]
-    T = len(tb)
+    seg = _segments("msa_segments", seq, starts, ends, pair_tmpl=pair_tmpl, templates=templates)
+    n, pt, T = seg.n, seg.pt, len(seg.tb)
     if n and (T < 1 or int(pt.min()) < 0 or int(pt.max()) >= 2 * T):
         raise SdError(SD_ERR_PARAM, "msa_segments: pair_tmpl outside the %d interleaved templates" % (2 * T))
-    tl = (C.c_int32 * max(T, 1))(*[len(t) for t in tb])
-    lens = [len(t) for t in tb]
+    lens = [len(t) for t in seg.tb]
     total = sum(formats.msa_pitch(lens[int(p) >> 1]) for p in pt.tolist())
     rows = np.zeros(max(total, 1), dtype=np.uint8)
     row_at = np.zeros(n + 1, dtype=np.int64)
     status = np.zeros(max(n, 1), dtype=np.uint8)
     if device is None:
-        rc = L.sd_msa_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data, int(threads),
-                               rows.ctypes.data, row_at.ctypes.data, status.ctypes.data)
+        rc = L.sd_msa_segments(*seg.lead, int(threads), rows.ctypes.data, row_at.ctypes.data, status.ctypes.data)
     else:
-        rc = L.sd_msa_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, _strs(tb), tl, T, pt.ctypes.data,
-                                   int(device), int(threads), rows.ctypes.data, row_at.ctypes.data, status.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_msa_segments" + ("" if device is None else "_dev"))
+        rc = L.sd_msa_segments_dev(*seg.lead, int(device), int(threads), rows.ctypes.data, row_at.ctypes.data, status.ctypes.data)
+    _check(rc, "sd_msa_segments" + ("" if device is None else "_dev"))
     return formats.Msa(rows[:total], row_at, status[:n], lens)
 
 
@@ -716,22 +819,9 @@ def msa_kernel_bench(seq, starts, ends, templates, pair_tmpl, device=0, warmup=2
     """sd_msa_kernel_bench: the row kernel and the profile kernel timed in turn on the same pairs (HIP events) ->
     {"msa_ms": [...], "profile_ms": [...], "K", "grid", "items", "pairs", "msa_lds_bytes", "staged", "profile_lds_bytes",
     "ck_slots"}."""
-    import numpy as np
-    L = load()
-    sb = _b(seq)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    pt = np.ascontiguousarray(pair_tmpl, dtype=np.int32)
-    tb = [_b(t) for t in templates]
-    tl = (C.c_int32 * max(len(tb), 1))(*[len(t) for t in tb])
-    a, b, info = (C.c_float * reps)(), (C.c_float * reps)(), (C.c_int64 * 8)()
-    rc = L.sd_msa_kernel_bench(sb, len(sb), st.ctypes.data, en.ctypes.data, len(st), _strs(tb), tl, len(tb), pt.ctypes.data,
-                               int(device), int(warmup), int(reps), a, b, info)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_msa_kernel_bench")
-    out = {"msa_ms": [float(x) for x in a], "profile_ms": [float(x) for x in b]}
-    out.update(zip(("K", "grid", "items", "pairs", "msa_lds_bytes", "staged", "profile_lds_bytes", "ck_slots"), [int(x) for x in info]))
-    return out
+    seg = _segments(None, seq, starts, ends, pair_tmpl=pair_tmpl, templates=templates)
+    return _bench(load().sd_msa_kernel_bench, seg.lead + (int(device), int(warmup), int(reps)), ("msa_ms", "profile_ms"),
+                  ("K", "grid", "items", "pairs", "msa_lds_bytes", "staged", "profile_lds_bytes", "ck_slots"), reps)
 
 
 def _msa_key_table(keys, mono_names):
@@ -757,20 +847,14 @@ def final_msa_host(final_rows, read_seqs, keys, mono_names, mono_seqs, threads=1
     import numpy as np
     kil = _msa_key_table(keys, mono_names)
     rows = final_rows[0]
-    rs = [_b(s) for s in read_seqs]
-    off, at = [], 0
-    for s in rs:
-        off.append(at)
-        at += len(s)
+    text, off, lens = _reads_text(read_seqs)
+    off, lens = off.tolist(), lens.tolist()
     st, en, pt = [], [], []
     for read, start, end, best in zip(rows["read"].tolist(), rows["start"].tolist(), rows["end"].tolist(), rows["best"].tolist()):
-        n = len(rs[read])
-        s0 = min(max(start, 0), n)
-        e1 = min(max(end + 1, s0), n)
+        s0, e = segment_clamp(start, end, lens[read])
         st.append(off[read] + s0)
-        en.append(off[read] + e1 - 1)   # (an empty segment: end = start - 1)
+        en.append(off[read] + e)
         pt.append(kil[best])
-    text = b"".join(rs)
     if not text:
         text, st, en = b"N", [0] * len(st), [-1] * len(en)
     return msa_segments(text, st, en, mono_seqs, pt, threads=threads), np.asarray(pt, dtype=np.int32)
@@ -801,11 +885,9 @@ class MsaTables:
         self.tlen = [len(s) for s in ms]
         self.n_keys = len(kil)
         self.h = C.c_void_p()
-        err = C.create_string_buffer(1024)
-        rc = self.L.sd_msa_tables_create(C.byref(self.h), kil.ctypes.data, len(kil), _strs(ms),
-                                         (C.c_int32 * max(len(ms), 1))(*self.tlen), len(ms), err, 1024)
-        if rc != SD_OK:
-            raise SdError(rc, err.value.decode(errors="replace"))
+        err = _err()
+        _text_check(self.L.sd_msa_tables_create(C.byref(self.h), kil.ctypes.data, len(kil), _strs(ms),
+                                                (C.c_int32 * max(len(ms), 1))(*self.tlen), len(ms), err, 1024), err)
 
     def close(self):
         if self.h:
@@ -868,9 +950,8 @@ def final_msa_classes(final_rows, read_lens, keys, mono_names, mono_seqs):
     rows = final_rows[0]
     out = []
     for read, start, end, best in zip(rows["read"].tolist(), rows["start"].tolist(), rows["end"].tolist(), rows["best"].tolist()):
-        n = int(read_lens[read])
-        s0 = min(max(start, 0), n)
-        q = min(max(end + 1, s0), n) - s0
+        s0, e = segment_clamp(start, end, int(read_lens[read]))
+        q = e + 1 - s0
         t = tl[kil[best] >> 1]
         if q <= 0 or t <= 0:
             out.append(0)
@@ -886,9 +967,7 @@ LAG_DMAX = 255
 
 def _lag_d(D, who):
     """1 <= D <= 255, refused here before any array is made or any device is touched"""
-    if not isinstance(D, int) or isinstance(D, bool) or not 1 <= D <= LAG_DMAX:
-        raise SdError(SD_ERR_PARAM, "%s: D = %r, must be an integer 1 .. %d" % (who, D, LAG_DMAX))
-    return D
+    return _int_arg(who, "D", D, 1, LAG_DMAX)
 
 
 def lag_segments(text, starts, ends, group_off, D, device=None, threads=1):
@@ -902,25 +981,15 @@ def lag_segments(text, starts, ends, group_off, D, device=None, threads=1):
     from . import formats
     D = _lag_d(D, "lag_segments")
     L = load()
-    sb = _b(text)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    go = np.ascontiguousarray(group_off, dtype=np.int64)
-    n = int(st.shape[0])
-    if en.shape[0] != n or go.ndim != 1 or go.shape[0] < 1:
-        raise SdError(SD_ERR_PARAM, "lag_segments: starts and ends differ in length, or group_off is empty")
-    G = int(go.shape[0]) - 1
-    dist = np.zeros((n, D), dtype=np.int32)
-    matches = np.zeros((n, D), dtype=np.int32)
-    sums = np.zeros((G, D, 3), dtype=np.int64)
+    seg = _segments("lag_segments", text, starts, ends, group_off=group_off)
+    dist = np.zeros((seg.n, D), dtype=np.int32)
+    matches = np.zeros((seg.n, D), dtype=np.int32)
+    sums = np.zeros((seg.G, D, 3), dtype=np.int64)
     if device is None:
-        rc = L.sd_lag_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, D, int(threads),
-                               dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
+        rc = L.sd_lag_segments(*seg.lead, D, int(threads), dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
     else:
-        rc = L.sd_lag_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, D, int(device), int(threads),
-                                   dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_lag_segments" + ("" if device is None else "_dev"))
+        rc = L.sd_lag_segments_dev(*seg.lead, D, int(device), int(threads), dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
+    _check(rc, "sd_lag_segments" + ("" if device is None else "_dev"))
     return formats.Lags(dist, matches, sums)
 
 
@@ -950,23 +1019,11 @@ def lag_periods(sums):
 def lag_kernel_bench(text, starts, ends, group_off, D, device=0, warmup=2, reps=5):
     """sd_lag_kernel_bench -> {"group_ms", "pairs_ms", "walk_ms", "ident_ms": [...], "pairs", "host_pairs", "K", "K_pairs",
     "ident_ck_slots", "ident_grid", "grid", "ck_slots"}."""
-    import numpy as np
     D = _lag_d(D, "lag_kernel_bench")
-    L = load()
-    sb = _b(text)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    go = np.ascontiguousarray(group_off, dtype=np.int64)
-    a, b, c, d = ((C.c_float * reps)() for _ in range(4))
-    info = (C.c_int64 * 8)()
-    rc = L.sd_lag_kernel_bench(sb, len(sb), st.ctypes.data, en.ctypes.data, len(st), go.ctypes.data, len(go) - 1, D, int(device),
-                               int(warmup), int(reps), a, b, c, d, info)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_lag_kernel_bench")
-    out = {"group_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b], "walk_ms": [float(x) for x in c],
-           "ident_ms": [float(x) for x in d]}
-    out.update(zip(("pairs", "host_pairs", "K", "K_pairs", "ident_ck_slots", "ident_grid", "grid", "ck_slots"), [int(x) for x in info]))
-    return out
+    seg = _segments(None, text, starts, ends, group_off=group_off)
+    return _bench(load().sd_lag_kernel_bench, seg.lead + (D, int(device), int(warmup), int(reps)),
+                  ("group_ms", "pairs_ms", "walk_ms", "ident_ms"),
+                  ("pairs", "host_pairs", "K", "K_pairs", "ident_ck_slots", "ident_grid", "grid", "ck_slots"), reps)
 
 
 class DeviceLags(namedtuple("DeviceLags", "dist matches sums classes")):
@@ -1018,21 +1075,13 @@ def final_lags_host(final_rows, read_seqs, D, threads=1):
     D = _lag_d(D, "final_lags_host")
     L = load()
     rows = np.ascontiguousarray(final_rows[0])
-    rs = [_b(s) for s in read_seqs]
-    off, at = [], 0
-    for s in rs:
-        off.append(at)
-        at += len(s)
-    n, R = int(rows.shape[0]), len(rs)
-    ro = np.ascontiguousarray(off, dtype=np.int64)
-    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64)
+    text, ro, rl = _reads_text(read_seqs)
+    n, R = int(rows.shape[0]), len(rl)
     dist = np.zeros((n, D), dtype=np.int32)
     matches = np.zeros((n, D), dtype=np.int32)
     sums = np.zeros((R, D, 3), dtype=np.int64)
-    rc = L.sd_lag_final_host(rows.ctypes.data, n, b"".join(rs) or b"N", ro.ctypes.data, rl.ctypes.data, R, D, int(threads),
-                             dist.ctypes.data, matches.ctypes.data, sums.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_lag_final_host")
+    _check(L.sd_lag_final_host(rows.ctypes.data, n, text or b"N", ro.ctypes.data, rl.ctypes.data, R, D, int(threads),
+                               dist.ctypes.data, matches.ctypes.data, sums.ctypes.data), "sd_lag_final_host")
     return formats.Lags(dist, matches, sums)
 
 
@@ -1042,15 +1091,8 @@ HEAT_BMAX = 1 << 20
 
 def _heat_args(B, W, max_pairs, who):
     """1 <= B <= 2^20, W >= 0, max_pairs >= 0, refused here before any array is made or any device is touched"""
-    def is_int(x):
-        return isinstance(x, int) and not isinstance(x, bool)
-    if not is_int(B) or not 1 <= B <= HEAT_BMAX:
-        raise SdError(SD_ERR_PARAM, "%s: B = %r, must be an integer 1 .. %d" % (who, B, HEAT_BMAX))
-    if not is_int(W) or not 0 <= W < (1 << 62):
-        raise SdError(SD_ERR_PARAM, "%s: W = %r, must be an integer, 0 (no limit) or more" % (who, W))
-    if not is_int(max_pairs) or not 0 <= max_pairs < (1 << 62):
-        raise SdError(SD_ERR_PARAM, "%s: max_pairs = %r, must be an integer, 0 (no limit) or more" % (who, max_pairs))
-    return B, W, max_pairs
+    return (_int_arg(who, "B", B, 1, HEAT_BMAX), _int_arg(who, "W", W, 0, (1 << 62) - 1, ", 0 (no limit) or more"),
+            _int_arg(who, "max_pairs", max_pairs, 0, (1 << 62) - 1, ", 0 (no limit) or more"))
 
 
 def heat_layout(group_off, B, W=0):
@@ -1065,9 +1107,7 @@ def heat_layout(group_off, B, W=0):
     G = int(go.shape[0]) - 1
     cell_off = np.zeros(G + 1, dtype=np.int64)
     cells, pairs = C.c_int64(0), C.c_int64(0)
-    rc = load().sd_heat_layout(go.ctypes.data, G, B, W, cell_off.ctypes.data, C.byref(cells), C.byref(pairs))
-    if rc != SD_OK:
-        raise SdError(rc, "sd_heat_layout")
+    _check(load().sd_heat_layout(go.ctypes.data, G, B, W, cell_off.ctypes.data, C.byref(cells), C.byref(pairs)), "sd_heat_layout")
     nb = (np.diff(go) + B - 1) // B
     return cell_off, nb.astype(np.int64), int(cells.value), int(pairs.value)
 
@@ -1084,15 +1124,9 @@ def heat_segments(text, starts, ends, group_off, B, W=0, device=None, threads=1,
     from . import formats
     B, W, max_pairs = _heat_args(B, W, max_pairs, "heat_segments")
     L = load()
-    sb = _b(text)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    go = np.ascontiguousarray(group_off, dtype=np.int64)
-    n = int(st.shape[0])
-    if en.shape[0] != n or go.ndim != 1 or go.shape[0] < 1:
-        raise SdError(SD_ERR_PARAM, "heat_segments: starts and ends differ in length, or group_off is empty")
-    G = int(go.shape[0]) - 1
-    err = C.create_string_buffer(1024)
+    seg = _segments("heat_segments", text, starts, ends, group_off=group_off)
+    go, G = seg.go, seg.G
+    err = _err()
     # the sums are sized by the closed forms; a layout the library would refuse gets one cell, and the library's refusal
     cell_off = np.zeros(G + 1, dtype=np.int64)
     cells, pairs = C.c_int64(0), C.c_int64(0)
@@ -1101,11 +1135,9 @@ def heat_segments(text, starts, ends, group_off, B, W=0, device=None, threads=1,
     sums = np.zeros((max(n_cells, 1), 3), dtype=np.int64)
     cls = (C.c_int64 * 3)()
     if device is None:
-        rc = L.sd_heat_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, B, W, max_pairs, int(which),
-                                int(threads), sums.ctypes.data, err, 1024)
+        rc = L.sd_heat_segments(*seg.lead, B, W, max_pairs, int(which), int(threads), sums.ctypes.data, err, 1024)
     else:
-        rc = L.sd_heat_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, go.ctypes.data, G, B, W, max_pairs, int(device),
-                                    int(threads), sums.ctypes.data, cls, err, 1024)
+        rc = L.sd_heat_segments_dev(*seg.lead, B, W, max_pairs, int(device), int(threads), sums.ctypes.data, cls, err, 1024)
     _text_check(rc, err)
     heat = formats.Heat(sums[:n_cells], cell_off, (np.diff(go) + B - 1) // B, B, W)
     heat.classes = tuple(int(x) for x in cls) if device is not None else None
@@ -1124,22 +1156,10 @@ def heat_identities(sums):
 def heat_kernel_bench(text, starts, ends, group_off, B, W=0, device=0, warmup=2, reps=5):
     """sd_heat_kernel_bench -> {"group_ms", "pairs_ms", "walk_ms": [...], "pairs", "host_pairs", "K", "items", "cells", "K_items",
     "grid", "ck_slots"}."""
-    import numpy as np
     B, W, _ = _heat_args(B, W, 0, "heat_kernel_bench")
-    L = load()
-    sb = _b(text)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    go = np.ascontiguousarray(group_off, dtype=np.int64)
-    a, b, c = ((C.c_float * reps)() for _ in range(3))
-    info = (C.c_int64 * 8)()
-    rc = L.sd_heat_kernel_bench(sb, len(sb), st.ctypes.data, en.ctypes.data, len(st), go.ctypes.data, len(go) - 1, B, W, int(device),
-                                int(warmup), int(reps), a, b, c, info)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_heat_kernel_bench")
-    out = {"group_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b], "walk_ms": [float(x) for x in c]}
-    out.update(zip(("pairs", "host_pairs", "K", "items", "cells", "K_items", "grid", "ck_slots"), [int(x) for x in info]))
-    return out
+    seg = _segments(None, text, starts, ends, group_off=group_off)
+    return _bench(load().sd_heat_kernel_bench, seg.lead + (B, W, int(device), int(warmup), int(reps)), ("group_ms", "pairs_ms", "walk_ms"),
+                  ("pairs", "host_pairs", "K", "items", "cells", "K_items", "grid", "ck_slots"), reps)
 
 
 class DeviceHeat(namedtuple("DeviceHeat", "sums cell_off nb classes")):
@@ -1197,14 +1217,8 @@ def final_heat_host(final_rows, read_seqs, B, W=0, threads=1, max_pairs=0, which
     B, W, max_pairs = _heat_args(B, W, max_pairs, "final_heat_host")
     L = load()
     rows = np.ascontiguousarray(final_rows[0])
-    rs = [_b(s) for s in read_seqs]
-    off, at = [], 0
-    for s in rs:
-        off.append(at)
-        at += len(s)
-    n, R = int(rows.shape[0]), len(rs)
-    ro = np.ascontiguousarray(off, dtype=np.int64)
-    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64)
+    text, ro, rl = _reads_text(read_seqs)
+    n, R = int(rows.shape[0]), len(rl)
     counts = np.bincount(rows["read"], minlength=R) if n else np.zeros(R, dtype=np.int64)
     if counts.shape[0] != R:
         raise SdError(SD_ERR_PARAM, "final_heat_host: a row's read index lies outside the %d reads" % R)
@@ -1213,8 +1227,8 @@ def final_heat_host(final_rows, read_seqs, B, W=0, threads=1, max_pairs=0, which
     n_cells = cells if cells <= HEAT_CELLS_MAX else 0   # (over the cap: the library refuses before it writes)
     sums = np.zeros((max(n_cells, 1), 3), dtype=np.int64)
     cls = (C.c_int64 * 3)()
-    err = C.create_string_buffer(1024)
-    _text_check(L.sd_heat_final_host(rows.ctypes.data, n, b"".join(rs) or b"N", ro.ctypes.data, rl.ctypes.data, R, B, W, max_pairs,
+    err = _err()
+    _text_check(L.sd_heat_final_host(rows.ctypes.data, n, text or b"N", ro.ctypes.data, rl.ctypes.data, R, B, W, max_pairs,
                                      int(which), int(threads), sums.ctypes.data, n_cells, cls, err, 1024), err)
     heat = formats.Heat(sums[:n_cells], cell_off, nb, B, W)
     heat.classes = tuple(int(x) for x in cls)
@@ -1228,23 +1242,14 @@ AUTOCORR_CELLS_MAX = 1 << 27
 
 def _autocorr_args(k, D, W, who):
     """1 <= k <= 32, 1 <= D <= 2^20, W >= 0, refused here before any array is made or any device is touched"""
-    def is_int(x):
-        return isinstance(x, int) and not isinstance(x, bool)
-    if not is_int(k) or not 1 <= k <= AUTOCORR_KMAX:
-        raise SdError(SD_ERR_PARAM, "%s: k = %r, must be an integer 1 .. %d" % (who, k, AUTOCORR_KMAX))
-    if not is_int(D) or not 1 <= D <= AUTOCORR_DMAX:
-        raise SdError(SD_ERR_PARAM, "%s: D = %r, must be an integer 1 .. %d" % (who, D, AUTOCORR_DMAX))
-    if not is_int(W) or not 0 <= W < (1 << 62):
-        raise SdError(SD_ERR_PARAM, "%s: window = %r, must be an integer, 0 (one window) or more" % (who, W))
-    return k, D, W
+    return (_int_arg(who, "k", k, 1, AUTOCORR_KMAX), _int_arg(who, "D", D, 1, AUTOCORR_DMAX),
+            _int_arg(who, "window", W, 0, (1 << 62) - 1, ", 0 (one window) or more"))
 
 
 def autocorr_info():
     """sd_autocorr_info -> {"tile": bases of a workgroup's tile, "lags": lags of a workgroup, "launch_work": the most
     base-lag products of one launch of the pair kernel, "launches": its launches in this process so far}"""
-    info = (C.c_int64 * 4)()
-    load().sd_autocorr_info(info)
-    return dict(zip(("tile", "lags", "launch_work", "launches"), (int(x) for x in info)))
+    return _info(load().sd_autocorr_info, ("tile", "lags", "launch_work", "launches"))
 
 
 def autocorr_layout(read_lens, window=0):
@@ -1255,26 +1260,14 @@ def autocorr_layout(read_lens, window=0):
     rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
     win_off = np.zeros(len(rl) + 1, dtype=np.int64)
     total = C.c_int64(0)
-    rc = load().sd_autocorr_layout(rl.ctypes.data, len(rl), W, win_off.ctypes.data, C.byref(total))
-    if rc != SD_OK:
-        raise SdError(rc, "sd_autocorr_layout: a negative read length, or 2^62 windows or more")
+    _check(load().sd_autocorr_layout(rl.ctypes.data, len(rl), W, win_off.ctypes.data, C.byref(total)),
+           "sd_autocorr_layout: a negative read length, or 2^62 windows or more")
     nw = np.diff(win_off)
     w = np.arange(int(total.value), dtype=np.int64) - np.repeat(win_off[:-1], nw)
     n = np.repeat(rl, nw)
     start = w * W
     end = np.minimum(n, start + W) if W > 0 else n
     return win_off, start, end, int(total.value)
-
-
-def _autocorr_reads(reads):
-    """a list of bytes / str -> (text, offsets, lengths): the reads back to back"""
-    import numpy as np
-    rs = [_b(s) for s in reads]
-    rl = np.ascontiguousarray([len(s) for s in rs], dtype=np.int64).reshape(-1)
-    ro = np.zeros(len(rs), dtype=np.int64)
-    if len(rs) > 1:
-        np.cumsum(rl[:-1], out=ro[1:])
-    return b"".join(rs), ro, rl
 
 
 def autocorr_text(text, read_off, read_lens, k, D=4096, window=0, device=None, threads=1):
@@ -1284,15 +1277,11 @@ def autocorr_text(text, read_off, read_lens, k, D=4096, window=0, device=None, t
     from . import formats
     k, D, W = _autocorr_args(k, D, window, "autocorr")
     L = load()
-    tb = _b(text)
-    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
-    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
-    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
-        raise SdError(SD_ERR_PARAM, "autocorr: offsets and lengths differ in number, or a read lies outside the text")
+    tb, ro, rl = _text_reads("autocorr", text, read_off, read_lens)
     win_off, start, end, windows = autocorr_layout(rl, W)
     cells = windows * D if windows * D <= AUTOCORR_CELLS_MAX else 0   # (over the cap: the library refuses before it writes)
     counts = np.zeros(max(cells, 1), dtype=np.int64)
-    err = C.create_string_buffer(1024)
+    err = _err()
     if device is None:
         rc = L.sd_autocorr_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, D, W, int(threads), counts.ctypes.data, err, 1024)
     else:
@@ -1310,7 +1299,7 @@ def autocorr(reads, k, D=4096, window=0, device=None, threads=1):
     csrc/sd_autocorr.hip on that device.  Both give the same integers.  -> formats.Autocorr"""
     if isinstance(reads, DeviceReads):
         return autocorr_device(reads, k, D, window).to_host(k, reads.read_lens, window)
-    text, ro, rl = _autocorr_reads(reads)
+    text, ro, rl = _reads_text(reads)
     return autocorr_text(text, ro, rl, k, D, window, device, threads)
 
 
@@ -1365,9 +1354,7 @@ def autocorr_positions(read_lens, k, D, window=0):
     if windows * D > AUTOCORR_CELLS_MAX:
         raise SdError(SD_ERR_PARAM, "autocorr_positions: %d windows x %d lags, the cap is %d cells" % (windows, D, AUTOCORR_CELLS_MAX))
     out = np.zeros((windows, D), dtype=np.int64)
-    rc = load().sd_autocorr_positions(rl.ctypes.data, len(rl), k, D, W, out.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_autocorr_positions")
+    _check(load().sd_autocorr_positions(rl.ctypes.data, len(rl), k, D, W, out.ctypes.data), "sd_autocorr_positions")
     return out
 
 
@@ -1381,15 +1368,13 @@ def autocorr_peaks(counts, lo=1, radius=8, peaks=8):
     if c.ndim == 1:
         c = c.reshape(1, -1)
     for name, v, low in (("lo", lo, 1), ("radius", radius, 0), ("peaks", peaks, 0)):
-        if not isinstance(v, int) or isinstance(v, bool) or v < low or v >= (1 << 31):
-            raise SdError(SD_ERR_PARAM, "autocorr_peaks: %s = %r, must be an integer, %d or more" % (name, v, low))
+        _int_arg("autocorr_peaks", name, v, low, (1 << 31) - 1, ", %d or more" % low)
     if c.ndim != 2 or not 1 <= c.shape[1] <= AUTOCORR_DMAX:
         raise SdError(SD_ERR_PARAM, "autocorr_peaks: counts must be [windows, D] with 1 <= D <= %d" % AUTOCORR_DMAX)
     lag = np.zeros((c.shape[0], peaks), dtype=np.int64)
     cnt = np.zeros((c.shape[0], peaks), dtype=np.int64)
-    rc = load().sd_autocorr_peaks(c.ctypes.data, c.shape[0], c.shape[1], lo, radius, peaks, lag.ctypes.data, cnt.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_autocorr_peaks")
+    _check(load().sd_autocorr_peaks(c.ctypes.data, c.shape[0], c.shape[1], lo, radius, peaks, lag.ctypes.data, cnt.ctypes.data),
+           "sd_autocorr_peaks")
     return lag, cnt
 
 
@@ -1397,13 +1382,10 @@ def autocorr_seed(seq, k, p):
     """(s, run): the longest run of consecutive hits at lag p in seq starts at s and has run positions, the first of equal
     runs; (-1, 0) when there is no hit (sd_autocorr_seed)"""
     k, _, _ = _autocorr_args(k, 1, 0, "autocorr_seed")
-    if not isinstance(p, int) or p < 1:
-        raise SdError(SD_ERR_PARAM, "autocorr_seed: p = %r, must be an integer, 1 or more" % (p,))
+    p = _int_arg("autocorr_seed", "p", p, 1, None, ", 1 or more", bools=True)   # (True has always been lag 1 here)
     sb = _b(seq)
     s, run = C.c_int64(0), C.c_int64(0)
-    rc = load().sd_autocorr_seed(sb or b"N", len(sb), k, p, C.byref(s), C.byref(run))
-    if rc != SD_OK:
-        raise SdError(rc, "sd_autocorr_seed")
+    _check(load().sd_autocorr_seed(sb or b"N", len(sb), k, p, C.byref(s), C.byref(run)), "sd_autocorr_seed")
     return int(s.value), int(run.value)
 
 
@@ -1463,16 +1445,9 @@ def autocorr_spectrum_rows(ac, names, read_lens):
 def autocorr_kernel_bench(reads, k, D=4096, window=0, device=0, warmup=2, reps=5):
     """sd_autocorr_kernel_bench -> {"prep_ms", "pairs_ms": [...], "launches", "workgroups", "cells", "words"}."""
     k, D, W = _autocorr_args(k, D, window, "autocorr_kernel_bench")
-    text, ro, rl = _autocorr_reads(reads)
-    a, b = ((C.c_float * reps)() for _ in range(2))
-    info = (C.c_int64 * 4)()
-    rc = load().sd_autocorr_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, D, W, int(device), int(warmup),
-                                         int(reps), a, b, info)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_autocorr_kernel_bench")
-    out = {"prep_ms": [float(x) for x in a], "pairs_ms": [float(x) for x in b]}
-    out.update(zip(("launches", "workgroups", "cells", "words"), [int(x) for x in info]))
-    return out
+    text, ro, rl = _reads_text(reads)
+    return _bench(load().sd_autocorr_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, D, W, int(device), int(warmup),
+                                                    int(reps)), ("prep_ms", "pairs_ms"), ("launches", "workgroups", "cells", "words"), reps)
 
 
 MOTIF_BUILTIN = {"cenpb": "NTTCGNNNNANNCGGGN"}   # the CENP-B box of alpha-satellite monomers
@@ -1516,9 +1491,8 @@ def motif_request(motifs):
 
 
 def _motif_mismatches(E, who):
-    if not isinstance(E, int) or isinstance(E, bool) or not -(1 << 31) <= E < (1 << 31):
-        raise SdError(SD_ERR_PARAM, "%s: mismatches = %r, must be an integer 0 .. %d" % (who, E, MOTIF_EMAX))
-    return E
+    """an integer that fits the C type; the range 0 .. 7 is the library's to refuse, with its text"""
+    return _int_arg(who, "mismatches", E, -(1 << 31), (1 << 31) - 1, " 0 .. %d" % MOTIF_EMAX)
 
 
 MotifStrand = namedtuple("MotifStrand", "motif strand length constrained palindrome")
@@ -1533,7 +1507,7 @@ def motif_compile(motifs, E=0):
     n = len(names)
     table = np.zeros((2 * max(n, 1), 5), dtype=np.int32)
     ns = C.c_int32(0)
-    err = C.create_string_buffer(1024)
+    err = _err()
     _text_check(load().sd_motif_compile(_strs(names), _strs(patterns), n, E, C.byref(ns), table.ctypes.data, err, 1024), err)
     return names, patterns, [MotifStrand(*(int(x) for x in row)) for row in table[:ns.value]]
 
@@ -1542,9 +1516,7 @@ def motif_info():
     """sd_motif_info -> {"tile": words of a workgroup's tile (64 starts each), "pattern_block": pattern-strands a workgroup
     takes, "launch_work": the most start x pattern-strand products of one launch, "launches": launches of the size and
     write kernels in this process so far}"""
-    info = (C.c_int64 * 4)()
-    load().sd_motif_info(info)
-    return dict(zip(("tile", "pattern_block", "launch_work", "launches"), (int(x) for x in info)))
+    return _info(load().sd_motif_info, ("tile", "pattern_block", "launch_work", "launches"))
 
 
 def motif_text(text, read_off, read_lens, motifs, E=0, device=None, threads=1):
@@ -1554,14 +1526,10 @@ def motif_text(text, read_off, read_lens, motifs, E=0, device=None, threads=1):
     from . import formats
     names, patterns, _ = motif_compile(motifs, E)
     L = load()
-    tb = _b(text)
-    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
-    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
-    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
-        raise SdError(SD_ERR_PARAM, "motif: offsets and lengths differ in number, or a read lies outside the text")
+    tb, ro, rl = _text_reads("motif", text, read_off, read_lens)
     per = np.zeros((len(rl), len(names), 2), dtype=np.int64)
     out, n = C.c_void_p(0), C.c_int64(0)
-    err = C.create_string_buffer(1024)
+    err = _err()
     if device is None:
         rc = L.sd_motif_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(threads),
                              C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
@@ -1583,7 +1551,7 @@ def motif(reads, motifs, E=0, device=None, threads=1):
     else the kernels of csrc/sd_motif.hip on that device.  Both give the same arrays.  -> formats.Motifs"""
     if isinstance(reads, DeviceReads):
         return motif_device(reads, motifs, E).to_host()
-    text, ro, rl = _autocorr_reads(reads)
+    text, ro, rl = _reads_text(reads)
     return motif_text(text, ro, rl, motifs, E, device, threads)
 
 
@@ -1641,16 +1609,10 @@ def motif_device(reads, motifs, E=0, stream=None, hits=None, per=None):
 def motif_kernel_bench(reads, motifs, E=0, device=0, warmup=2, reps=5):
     """sd_motif_kernel_bench -> {"prep_ms", "size_ms", "write_ms": [...], "launches", "items", "hits", "words"}."""
     names, patterns, _ = motif_compile(motifs, E)
-    text, ro, rl = _autocorr_reads(reads)
-    a, b, c = ((C.c_float * reps)() for _ in range(3))
-    info = (C.c_int64 * 4)()
-    rc = load().sd_motif_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(device),
-                                      int(warmup), int(reps), a, b, c, info)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_motif_kernel_bench")
-    out = {"prep_ms": [float(x) for x in a], "size_ms": [float(x) for x in b], "write_ms": [float(x) for x in c]}
-    out.update(zip(("launches", "items", "hits", "words"), [int(x) for x in info]))
-    return out
+    text, ro, rl = _reads_text(reads)
+    return _bench(load().sd_motif_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E,
+                                                 int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
+                  ("launches", "items", "hits", "words"), reps)
 
 
 DOTPLOT_KMAX = 32
@@ -1664,19 +1626,15 @@ DOTPLOT_SET_MAX = 4096
 def _dotplot_args(k, W, B, M, who):
     """1 <= k <= 32, 1 <= W <= 2^30, 0 <= B <= 2^30, 1 <= M <= 2^20, refused here before any array is made or any device
     is touched"""
-    for name, v, lo, hi in (("k", k, 1, DOTPLOT_KMAX), ("W", W, 1, DOTPLOT_WMAX), ("B", B, 0, DOTPLOT_BMAX), ("M", M, 1, DOTPLOT_MMAX)):
-        if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
-            raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer %d .. %d" % (who, name, v, lo, hi))
-    return k, W, B, M
+    return (_int_arg(who, "k", k, 1, DOTPLOT_KMAX), _int_arg(who, "W", W, 1, DOTPLOT_WMAX), _int_arg(who, "B", B, 0, DOTPLOT_BMAX),
+            _int_arg(who, "M", M, 1, DOTPLOT_MMAX))
 
 
 def dotplot_info():
     """sd_dotplot_info -> {"tile": positions of a tile of the counting pass, "jseg": cells of a row a workgroup of the pair
     kernel takes, "set_max", "launch_work": the most pair-elements of one launch of the pair kernel, "cells_max",
     "launches": its launches in this process so far}"""
-    info = (C.c_int64 * 6)()
-    load().sd_dotplot_info(info)
-    return dict(zip(("tile", "jseg", "set_max", "launch_work", "cells_max", "launches"), (int(x) for x in info)))
+    return _info(load().sd_dotplot_info, ("tile", "jseg", "set_max", "launch_work", "cells_max", "launches"))
 
 
 def dotplot_hash(x):
@@ -1693,9 +1651,8 @@ def dotplot_layout(read_lens, W, B=0):
     win_off = np.zeros(len(rl) + 1, dtype=np.int64)
     cell_off = np.zeros(len(rl) + 1, dtype=np.int64)
     nw, nc = C.c_int64(0), C.c_int64(0)
-    rc = load().sd_dotplot_layout(rl.ctypes.data, len(rl), W, B, win_off.ctypes.data, cell_off.ctypes.data, C.byref(nw), C.byref(nc))
-    if rc != SD_OK:
-        raise SdError(rc, "sd_dotplot_layout: a negative read length, or 2^62 windows or cells, or more")
+    _check(load().sd_dotplot_layout(rl.ctypes.data, len(rl), W, B, win_off.ctypes.data, cell_off.ctypes.data, C.byref(nw), C.byref(nc)),
+           "sd_dotplot_layout: a negative read length, or 2^62 windows or cells, or more")
     return win_off, cell_off, int(nw.value), int(nc.value)
 
 
@@ -1712,17 +1669,13 @@ def dotplot_text(text, read_off, read_lens, k, W, B=0, M=1, rc=False, device=Non
     from . import formats
     k, W, B, M = _dotplot_args(k, W, B, M, "dotplot")
     L = load()
-    tb = _b(text)
-    ro = np.ascontiguousarray(read_off, dtype=np.int64).reshape(-1)
-    rl = np.ascontiguousarray(read_lens, dtype=np.int64).reshape(-1)
-    if len(ro) != len(rl) or (len(rl) and (int(ro.min()) < 0 or int(rl.min()) < 0 or int((ro + rl).max()) > len(tb))):
-        raise SdError(SD_ERR_PARAM, "dotplot: offsets and lengths differ in number, or a read lies outside the text")
+    tb, ro, rl = _text_reads("dotplot", text, read_off, read_lens)
     win_off, cell_off, windows, cells = dotplot_layout(rl, W, B)
     _dotplot_cells_check("dotplot", windows, cells)
     kmers, shared = np.zeros(max(windows, 1), dtype=np.int32), np.zeros(max(cells, 1), dtype=np.int32)
     kmers_rc, shared_rc = (np.zeros_like(kmers), np.zeros_like(shared)) if rc else (None, None)
     ptr = lambda a: a.ctypes.data if a is not None else None
-    err = C.create_string_buffer(1024)
+    err = _err()
     if device is None:
         e = L.sd_dotplot_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, W, B, M, int(bool(rc)), int(threads), ptr(kmers),
                               ptr(kmers_rc), ptr(shared), ptr(shared_rc), err, 1024)
@@ -1743,7 +1696,7 @@ def dotplot(reads, k, W, B=0, M=1, rc=False, device=None, threads=1):
     -> formats.Dotplot"""
     if isinstance(reads, DeviceReads):
         return dotplot_device(reads, k, W, B, M, rc).to_host(reads.read_lens, k, W, B, M)
-    text, ro, rl = _autocorr_reads(reads)
+    text, ro, rl = _reads_text(reads)
     return dotplot_text(text, ro, rl, k, W, B, M, rc, device, threads)
 
 
@@ -1800,16 +1753,10 @@ def dotplot_kernel_bench(reads, k, W, B=0, M=1, rc=False, device=0, warmup=2, re
     """sd_dotplot_kernel_bench -> {"count_ms", "sets_ms", "pairs_ms": [...], "launches", "workgroups", "cells", "windows",
     "selected", "largest"}."""
     k, W, B, M = _dotplot_args(k, W, B, M, "dotplot_kernel_bench")
-    text, ro, rl = _autocorr_reads(reads)
-    a, b, c = ((C.c_float * reps)() for _ in range(3))
-    info = (C.c_int64 * 6)()
-    e = load().sd_dotplot_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, W, B, M, int(bool(rc)), int(device),
-                                       int(warmup), int(reps), a, b, c, info)
-    if e != SD_OK:
-        raise SdError(e, "sd_dotplot_kernel_bench")
-    out = {"count_ms": [float(x) for x in a], "sets_ms": [float(x) for x in b], "pairs_ms": [float(x) for x in c]}
-    out.update(zip(("launches", "workgroups", "cells", "windows", "selected", "largest"), [int(x) for x in info]))
-    return out
+    text, ro, rl = _reads_text(reads)
+    return _bench(load().sd_dotplot_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), k, W, B, M, int(bool(rc)),
+                                                   int(device), int(warmup), int(reps)), ("count_ms", "sets_ms", "pairs_ms"),
+                  ("launches", "workgroups", "cells", "windows", "selected", "largest"), reps)
 
 
 SPLIT_KMAX = 64
@@ -1819,14 +1766,13 @@ SPLIT_NMAX = 1 << 26
 
 def _split_args(R, K, min_size, max_iter, who):
     """R, min_size, max_iter >= 1 and 1 <= K <= 64, refused here before any array is made or any device is touched"""
-    def is_int(x):
-        return isinstance(x, int) and not isinstance(x, bool)
     for name, v in (("R", R), ("min_size", min_size), ("max_iter", max_iter)):
-        if not is_int(v) or not 1 <= v < (1 << 31):
-            raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer, 1 or more" % (who, name, v))
-    if not is_int(K) or not 1 <= K <= SPLIT_KMAX:
-        raise SdError(SD_ERR_PARAM, "%s: K = %r, must be an integer 1 .. %d" % (who, K, SPLIT_KMAX))
-    return R, K, min_size, max_iter
+        _int_arg(who, name, v, 1, (1 << 31) - 1, ", 1 or more")
+    return R, _int_arg(who, "K", K, 1, SPLIT_KMAX), min_size, max_iter
+
+
+def _split_percent(P, who):
+    return _int_arg(who, "P", P, 1, 100, " 1 .. 100 (a percentage of the monomer's length)")
 
 
 def split_radius(P, L):
@@ -1837,9 +1783,7 @@ def split_radius(P, L):
 def split_info():
     """sd_split_info -> {"kmax", "lmax": the longest monomer of the kernels, "nmax": the most member rows of a monomer,
     "launches": launches of the assign kernel in this process so far}"""
-    info = (C.c_int64 * 4)()
-    load().sd_split_info(info)
-    return dict(zip(("kmax", "lmax", "nmax", "launches"), (int(x) for x in info)))
+    return _info(load().sd_split_info, ("kmax", "lmax", "nmax", "launches"))
 
 
 def split_rows(sym, R, K=64, min_size=8, max_iter=16, device=None, threads=1):
@@ -1864,7 +1808,7 @@ def split_rows(sym, R, K=64, min_size=8, max_iter=16, device=None, threads=1):
     asg, d1, d2 = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
     sizes = np.zeros(K, dtype=np.int32)
     info = (C.c_int64 * 4)()
-    err = C.create_string_buffer(1024)
+    err = _err()
     L_ = load()
     base = a.ctypes.data if n else cen.ctypes.data
     if device is None:
@@ -1873,8 +1817,7 @@ def split_rows(sym, R, K=64, min_size=8, max_iter=16, device=None, threads=1):
     else:
         rc = L_.sd_split_dev(base, n, L, L, R, K, S, I, int(device), int(threads), cen.ctypes.data, asg.ctypes.data, d1.ctypes.data,
                              d2.ctypes.data, sizes.ctypes.data, info, err, 1024)
-    if rc != SD_OK:
-        raise SdError(rc, err.value.decode(errors="replace") or "sd_split" + ("_host" if device is None else "_dev"))
+    _text_check(rc, err, "sd_split" + ("_host" if device is None else "_dev"))
     k = int(info[0])
     return formats.Split(cen[:k].copy(), asg[:n], d1[:n], d2[:n], sizes[:k].copy(), int(info[1]), int(info[2]))
 
@@ -1885,8 +1828,7 @@ def split_msa(msa, pair_tmpl, mono_lens, P, K=64, min_size=8, max_iter=16, devic
     monomer (k = 0 for a monomer without instances)."""
     import numpy as np
     from . import formats
-    if not isinstance(P, int) or isinstance(P, bool) or not 1 <= P <= 100:
-        raise SdError(SD_ERR_PARAM, "split_msa: P = %r, must be an integer 1 .. 100 (a percentage of the monomer's length)" % (P,))
+    _split_percent(P, "split_msa")
     _split_args(1, K, min_size, max_iter, "split_msa")
     groups = [[] for _ in mono_lens]
     for i, il in enumerate(pair_tmpl):
@@ -1912,8 +1854,7 @@ class JobSplit(namedtuple("JobSplit", "sub d1 d2 centres cen_off sizes info")):
 
 def _split_job_args(mono_lens, P, K, min_size, max_iter, who):
     import numpy as np
-    if not isinstance(P, int) or isinstance(P, bool) or not 1 <= P <= 100:
-        raise SdError(SD_ERR_PARAM, "%s: P = %r, must be an integer 1 .. 100 (a percentage of the monomer's length)" % (who, P))
+    _split_percent(P, who)
     _, K, S, I = _split_args(1, K, min_size, max_iter, who)
     ml = np.ascontiguousarray(mono_lens, dtype=np.int32)
     if len(ml) and int(ml.min()) < 1:
@@ -1939,12 +1880,11 @@ def final_split_host(msa, pair_tmpl, mono_lens, P, K=64, min_size=8, max_iter=16
     cen_off = np.zeros(M + 1, dtype=np.int64)
     sizes = np.zeros((M, K), dtype=np.int32)
     info = np.zeros((M, 4), dtype=np.int64)
-    err = C.create_string_buffer(1024)
+    err = _err()
     rc = load().sd_split_final_host(rows.ctypes.data, row_at.ctypes.data, status.ctypes.data, fmono.ctypes.data, n, ml.ctypes.data,
                                     rad.ctypes.data, M, K, S, I, int(threads), sub.ctypes.data, d1.ctypes.data, d2.ctypes.data,
                                     centres.ctypes.data, cap, cen_off.ctypes.data, sizes.ctypes.data, info.ctypes.data, err, 1024)
-    if rc != SD_OK:
-        raise SdError(rc, err.value.decode(errors="replace") or "sd_split_final_host")
+    _text_check(rc, err, "sd_split_final_host")
     return JobSplit(sub[:n], d1[:n], d2[:n], centres[:int(cen_off[-1])], cen_off, sizes, info)
 
 
@@ -1956,15 +1896,8 @@ def split_kernel_bench(sym, R, K=64, min_size=8, max_iter=16, device=0, warmup=2
     a = np.ascontiguousarray(sym, dtype=np.uint8)
     if a.ndim != 2 or a.shape[0] < 1 or not 1 <= a.shape[1] <= SPLIT_LMAX:
         raise SdError(SD_ERR_PARAM, "split_kernel_bench: sym must be [n, L] with n >= 1 and 1 <= L <= %d" % SPLIT_LMAX)
-    x, y, z = ((C.c_float * reps)() for _ in range(3))
-    info = (C.c_int64 * 4)()
-    rc = load().sd_split_kernel_bench(a.ctypes.data, a.shape[0], a.shape[1], a.shape[1], R, K, S, I, int(device), int(warmup), int(reps),
-                                      x, y, z, info)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_split_kernel_bench")
-    out = {"prep_ms": [float(v) for v in x], "assign_ms": [float(v) for v in y], "modes_ms": [float(v) for v in z]}
-    out.update(zip(("k", "rounds", "iters", "launches"), [int(v) for v in info]))
-    return out
+    return _bench(load().sd_split_kernel_bench, (a.ctypes.data, a.shape[0], a.shape[1], a.shape[1], R, K, S, I, int(device), int(warmup),
+                                                 int(reps)), ("prep_ms", "assign_ms", "modes_ms"), ("k", "rounds", "iters", "launches"), reps)
 
 
 HOR_MMAX = 2048
@@ -1985,9 +1918,7 @@ def hor_unit_dtype():
 def hor_info():
     """sd_hor_info -> {"mmax": the most monomers, "pmax": the most monomers of an order and rows of a unit, "name_max": the
     bytes a name needs}"""
-    info = (C.c_int64 * 4)()
-    load().sd_hor_info(info)
-    return dict(zip(("mmax", "pmax", "name_max"), (int(x) for x in info)))
+    return _info(load().sd_hor_info, ("mmax", "pmax", "name_max"), slots=4)
 
 
 def hor_name(mask):
@@ -1999,11 +1930,8 @@ def hor_name(mask):
 
 def _hor_args(n_mono, G, C_, who):
     """integers that fit the C types; the ranges are the library's to refuse, with its texts"""
-    def is_int(x):
-        return isinstance(x, int) and not isinstance(x, bool)
     for name, v, bits in (("n_mono", n_mono, 31), ("G", G, 63), ("C", C_, 63)):
-        if not is_int(v) or not -(1 << bits) <= v < (1 << bits):
-            raise SdError(SD_ERR_PARAM, "%s: %s = %r, must be an integer" % (who, name, v))
+        _int_arg(who, name, v, -(1 << bits), (1 << bits) - 1, "")
     return n_mono, G, C_
 
 
@@ -2018,7 +1946,7 @@ class _HorOut:
         self.rows = np.zeros(M1, dtype=np.int64)
         self.hor, self.pos, self.kind, self.len, self.lfirst, self.llen = (np.zeros(M1, dtype=np.int32) for _ in range(6))
         self.info = (C.c_int64 * 4)()
-        self.err = C.create_string_buffer(1024)
+        self.err = _err()
         self.row_unit = np.zeros(max(n, 1), dtype=np.int32)
         self.units = np.zeros(max(n, 1), dtype=hor_unit_dtype())   # (n_rows always suffices)
 
@@ -2055,9 +1983,7 @@ def hor_rows(read, start, end, key, usable, n_mono, G=0, C_=2, threads=1, cap_un
     tail = o.tail()
     if cap_units is not None:
         tail[10] = min(int(cap_units), max(n, 1))
-    rc = load().sd_hor_rows(*ptrs, n, M, G, C_, int(threads), *tail)
-    if rc != SD_OK:
-        raise SdError(rc, o.err.value.decode(errors="replace") or "sd_hor_rows")
+    _text_check(load().sd_hor_rows(*ptrs, n, M, G, C_, int(threads), *tail), o.err, "sd_hor_rows")
     return o.result()
 
 
@@ -2069,9 +1995,8 @@ def final_hor_host(final_rows, n_mono, G=0, C_=2, threads=1):
     rows = np.ascontiguousarray(final_rows[0])
     n = int(rows.shape[0])
     o = _HorOut(n, M)
-    rc = load().sd_hor_final_host(rows.ctypes.data if n else o.T.ctypes.data, n, M, G, C_, int(threads), *o.tail())
-    if rc != SD_OK:
-        raise SdError(rc, o.err.value.decode(errors="replace") or "sd_hor_final_host")
+    _text_check(load().sd_hor_final_host(rows.ctypes.data if n else o.T.ctypes.data, n, M, G, C_, int(threads), *o.tail()), o.err,
+                "sd_hor_final_host")
     return o.result()
 
 
@@ -2483,11 +2408,9 @@ class TextTables:
         self.L = load()
         self.n_reads, self.n_cols = len(read_names), len(col_names)
         self.h = C.c_void_p()
-        err = C.create_string_buffer(1024)
-        rc = self.L.sd_text_tables_create(C.byref(self.h), _strs(read_names), self.n_reads, _strs(col_names), self.n_cols,
-                                          err, 1024)
-        if rc != SD_OK:
-            raise SdError(rc, err.value.decode(errors="replace"))
+        err = _err()
+        _text_check(self.L.sd_text_tables_create(C.byref(self.h), _strs(read_names), self.n_reads, _strs(col_names), self.n_cols,
+                                                 err, 1024), err)
 
     def close(self):
         if self.h:
@@ -2499,11 +2422,6 @@ class TextTables:
             self.close()
         except Exception:
             pass
-
-
-def _text_check(rc, err):
-    if rc != SD_OK:
-        raise SdError(rc, err.value.decode(errors="replace"))
 
 
 def _text_tables(tables, read_names, col_names):
@@ -2522,17 +2440,14 @@ def format_final_device(dfr, read_names, keys, stream=None, tables=None):
     reads in submit order; keys: Stream.keys(); tables: a TextTables over the same names, to upload them once for many
     jobs.  torch allocates the tensors on `stream` (Stream.collect_final_device's convention) and the library fills them
     there: the host waits for the text's size only, and work enqueued on the stream afterwards sees the text."""
-    import torch
     L = load()
-    dev = dfr.row_off.device
-    st = _torch_stream(torch, dev, stream)
+    torch, dev, st = _device_frame(dfr.row_off.device, stream)
     n, nr, nk = int(dfr.n_rows), len(read_names), len(keys)
     if dfr.row_off.shape[0] != nr + 1:
         raise SdError(SD_ERR_PARAM, "format_final_device: %d read names for %d reads" % (nr, dfr.row_off.shape[0] - 1))
     has_alt = dfr.alt is not None
     t, own = _text_tables(tables, read_names, keys)
-    err = C.create_string_buffer(1024)
-    ptr = lambda x: C.c_void_p(x.data_ptr() if x is not None and x.numel() else 0)   # noqa: E731
+    err = _err()
     try:
         with torch.cuda.stream(st):
             row_pos = torch.empty(n + 1, dtype=torch.int64, device=dev)
@@ -2542,14 +2457,14 @@ def format_final_device(dfr, read_names, keys, stream=None, tables=None):
         # (an empty alt still means "with _alt text": a pointer that is not NULL)
         alt_ptr = C.c_void_p((dfr.alt.data_ptr() if n and nk else alt_pos.data_ptr()) if has_alt else 0)
         fb, ab = C.c_int64(), C.c_int64()
-        _text_check(L.sd_text_final_size_dev(t.h, ptr(dfr.rows), n, ptr(dfr.row_off), alt_ptr, nk, dev.index or 0,
-                                             C.c_void_p(st.cuda_stream), ptr(row_pos), ptr(alt_pos), ptr(read_pos),
-                                             ptr(alt_read_pos), C.byref(fb), C.byref(ab), err, 1024), err)
+        _text_check(L.sd_text_final_size_dev(t.h, _dptr(dfr.rows), n, _dptr(dfr.row_off), alt_ptr, nk, dev.index or 0,
+                                             C.c_void_p(st.cuda_stream), _dptr(row_pos), _dptr(alt_pos), _dptr(read_pos),
+                                             _dptr(alt_read_pos), C.byref(fb), C.byref(ab), err, 1024), err)
         with torch.cuda.stream(st):
             ftext = torch.empty(fb.value, dtype=torch.uint8, device=dev)
             atext = torch.empty(ab.value, dtype=torch.uint8, device=dev) if has_alt else None
-        _text_check(L.sd_text_final_write_dev(t.h, ptr(dfr.rows), n, alt_ptr, nk, dev.index or 0, C.c_void_p(st.cuda_stream),
-                                              ptr(row_pos), ptr(alt_pos), ptr(ftext), fb.value, ptr(atext), ab.value, err, 1024),
+        _text_check(L.sd_text_final_write_dev(t.h, _dptr(dfr.rows), n, alt_ptr, nk, dev.index or 0, C.c_void_p(st.cuda_stream),
+                                              _dptr(row_pos), _dptr(alt_pos), _dptr(ftext), fb.value, _dptr(atext), ab.value, err, 1024),
                     err)
     finally:
         if own:
@@ -2560,28 +2475,25 @@ def format_final_device(dfr, read_names, keys, stream=None, tables=None):
 def format_raw_device(drows, read_names, tmpl_names, stream=None, tables=None):
     """The text of _raw.tsv of a DeviceRows, formatted on its device (sd_text_raw_size_dev / sd_text_raw_write_dev) ->
     DeviceText.  tmpl_names: the DP's templates (monomers, then monomers + "'"); the rest as format_final_device."""
-    import torch
     L = load()
-    dev = drows.row_off.device
-    st = _torch_stream(torch, dev, stream)
+    torch, dev, st = _device_frame(drows.row_off.device, stream)
     n, nr = int(drows.n_rows), len(read_names)
     if drows.row_off.shape[0] != nr + 1:
         raise SdError(SD_ERR_PARAM, "format_raw_device: %d read names for %d reads" % (nr, drows.row_off.shape[0] - 1))
     t, own = _text_tables(tables, read_names, tmpl_names)
-    err = C.create_string_buffer(1024)
-    ptr = lambda x: C.c_void_p(x.data_ptr() if x.numel() else 0)   # noqa: E731
+    err = _err()
     try:
         with torch.cuda.stream(st):
             row_pos = torch.empty(n + 1, dtype=torch.int64, device=dev)
             read_pos = torch.empty(nr + 1, dtype=torch.int64, device=dev)
             row_read = torch.empty(n, dtype=torch.int32, device=dev)
         nb = C.c_int64()
-        _text_check(L.sd_text_raw_size_dev(t.h, ptr(drows.rows), n, ptr(drows.row_off), dev.index or 0, C.c_void_p(st.cuda_stream),
-                                           ptr(row_read), ptr(row_pos), ptr(read_pos), C.byref(nb), err, 1024), err)
+        _text_check(L.sd_text_raw_size_dev(t.h, _dptr(drows.rows), n, _dptr(drows.row_off), dev.index or 0, C.c_void_p(st.cuda_stream),
+                                           _dptr(row_read), _dptr(row_pos), _dptr(read_pos), C.byref(nb), err, 1024), err)
         with torch.cuda.stream(st):
             text = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-        _text_check(L.sd_text_raw_write_dev(t.h, ptr(drows.rows), n, ptr(drows.row_off), dev.index or 0, C.c_void_p(st.cuda_stream),
-                                            ptr(row_read), ptr(row_pos), ptr(text), nb.value, err, 1024), err)
+        _text_check(L.sd_text_raw_write_dev(t.h, _dptr(drows.rows), n, _dptr(drows.row_off), dev.index or 0, C.c_void_p(st.cuda_stream),
+                                            _dptr(row_read), _dptr(row_pos), _dptr(text), nb.value, err, 1024), err)
     finally:
         if own:
             t.close()
@@ -3325,11 +3237,9 @@ def final_select_device(mono_names, mono_seqs, rows, row_off, widx, words, hword
     `device` through torch and the results come back as numpy.  Every output buffer carries guard bytes behind it: the
     result is (FinalRows, n_undecided, intact)."""
     import numpy as np
-    import torch
     r, o, wi, w, h, rl, per = _final_select_arrays(rows, row_off, widx, words, hwords, read_len, second_best, len(mono_seqs))
     nk = len(dict.fromkeys(x for n in mono_names for x in (n, n + "'")))
-    dev = torch.device("cuda", int(device))
-    st = _torch_stream(torch, dev, stream)
+    torch, dev, st = _device_frame(int(device), stream)
     G = 0x5a
     with torch.cuda.stream(st):
         up = lambda a: None if a is None else torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev)   # noqa: E731
@@ -3337,14 +3247,12 @@ def final_select_device(mono_names, mono_seqs, rows, row_off, widx, words, hword
         d_out = torch.full(((len(r) + 1) * 80,), G, dtype=torch.uint8, device=dev)
         d_off = torch.full(((len(o) + 1) * 8,), G, dtype=torch.uint8, device=dev)
         d_alt = torch.full(((len(r) * nk + 1) * 8,), G, dtype=torch.uint8, device=dev) if second_best else None
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)   # noqa: E731
         n, und = C.c_int64(), C.c_int64()
         rc = load().sd_final_select_dev(*_final_select_args(mono_names, mono_seqs, min_identity, second_best, lr_coef),
-                                        ptr(d_r), ptr(d_o), len(o) - 1, ptr(d_wi), ptr(d_w), ptr(d_h), len(w), per,
-                                        ptr(d_rl), int(device), C.c_void_p(st.cuda_stream), ptr(d_out), ptr(d_off),
-                                        ptr(d_alt), C.byref(n), C.byref(und))
-        if rc != SD_OK:
-            raise SdError(rc, "sd_final_select_dev")
+                                        _dptr(d_r), _dptr(d_o), len(o) - 1, _dptr(d_wi), _dptr(d_w), _dptr(d_h), len(w), per,
+                                        _dptr(d_rl), int(device), C.c_void_p(st.cuda_stream), _dptr(d_out), _dptr(d_off),
+                                        _dptr(d_alt), C.byref(n), C.byref(und))
+        _check(rc, "sd_final_select_dev")
         h_out, h_off = d_out.cpu().numpy(), d_off.cpu().numpy()
         h_alt = d_alt.cpu().numpy() if d_alt is not None else None
     k = n.value
@@ -3436,32 +3344,19 @@ def identity_segments(seq, starts, ends, templates, homo=False, threads=1, pair_
     (sd_identity_segments_dev), with the host implementation for input the kernel does not take."""
     import numpy as np
     L = load()
-    sb = _b(seq)
-    st = np.ascontiguousarray(starts, dtype=np.int64)
-    en = np.ascontiguousarray(ends, dtype=np.int64)
-    n = int(st.shape[0])
-    tb = [_b(t) for t in templates]
-    T = len(tb)
-    tl = (C.c_int32 * max(T, 1))(*[len(t) for t in tb])
-    pt = None if pair_tmpl is None else np.ascontiguousarray(pair_tmpl, dtype=np.int32)
-    shape = (n, T) if pt is None else (n,)
+    seg = _segments(None, seq, starts, ends, pair_tmpl=pair_tmpl, templates=templates)
+    shape = (seg.n, len(seg.tb)) if seg.pt is None else (seg.n,)
     d = np.zeros(shape, dtype=np.int32)
     m = np.zeros(shape, dtype=np.int32)
     c = np.zeros(shape, dtype=np.int32)
-    tarr = _strs(tb)
     rc = SD_ERR_UNSUPPORTED
     if device is not None:
-        rc = L.sd_identity_segments_dev(sb, len(sb), st.ctypes.data, en.ctypes.data, n, tarr, tl, T,
-                                        None if pt is None else pt.ctypes.data, 1 if homo else 0, int(device),
-                                        threads, d.ctypes.data, m.ctypes.data, c.ctypes.data)
-        if rc not in (SD_OK, SD_ERR_UNSUPPORTED):
-            raise SdError(rc, "sd_identity_segments_dev")
+        rc = L.sd_identity_segments_dev(*seg.lead, 1 if homo else 0, int(device), threads, d.ctypes.data, m.ctypes.data, c.ctypes.data)
+        if rc != SD_ERR_UNSUPPORTED:
+            _check(rc, "sd_identity_segments_dev")
     if rc == SD_ERR_UNSUPPORTED:
-        rc = L.sd_identity_segments(sb, len(sb), st.ctypes.data, en.ctypes.data, n, tarr, tl, T,
-                                    None if pt is None else pt.ctypes.data, 1 if homo else 0, threads,
-                                    d.ctypes.data, m.ctypes.data, c.ctypes.data)
-    if rc != SD_OK:
-        raise SdError(rc, "sd_identity_segments")
+        rc = L.sd_identity_segments(*seg.lead, 1 if homo else 0, threads, d.ctypes.data, m.ctypes.data, c.ctypes.data)
+    _check(rc, "sd_identity_segments")
     return d, m, c
 
 

@@ -457,41 +457,44 @@ def _log_input_stats(logger):
 MAX_DEVICE_ENTRIES = 16   # sd_run_files_devices
 
 
+def _refuse(msg, code=2):
+    """A request this process cannot serve ends it here: one line on stderr, before any work on a GPU."""
+    sys.stderr.write("stringdecomposer: %s\n" % msg)
+    sys.exit(code)
+
+
 def _device_list(args):
     """--gpus / --devices -> None (the single-device path of --device) or the list of ordinals for sd_run_files_devices.
     A request this process cannot serve ends it here, with one line on stderr, before any work on a GPU."""
-    def refuse(msg):
-        sys.stderr.write("stringdecomposer: %s\n" % msg)
-        sys.exit(2)
     if args.gpus is None and args.devices is None:
         return None
     if args.devices is not None:
         items = args.devices.split(",")
         if not all(x.strip().isdigit() for x in items):
-            refuse("--devices %s: expected a comma-separated list of device ordinals, e.g. 0,2,5" % args.devices)
+            _refuse("--devices %s: expected a comma-separated list of device ordinals, e.g. 0,2,5" % args.devices)
         devs = [int(x) for x in items]
         what = "--devices %s" % args.devices
     else:
         if args.gpus < 1:
-            refuse("--gpus %d: at least one device" % args.gpus)
+            _refuse("--gpus %d: at least one device" % args.gpus)
         if args.gpus == 1:
             return None   # today's single-device path, exactly
         devs = list(range(args.gpus))
         what = "--gpus %d" % args.gpus
     if len(devs) > MAX_DEVICE_ENTRIES:
-        refuse("%s: at most %d device entries in one process" % (what, MAX_DEVICE_ENTRIES))
+        _refuse("%s: at most %d device entries in one process" % (what, MAX_DEVICE_ENTRIES))
     if len(devs) > 1 and shard.world()[2] > 1:
-        refuse("%s: several devices per process cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)"
-               % (what, shard.world()[2]))
+        _refuse("%s: several devices per process cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)"
+                % (what, shard.world()[2]))
     try:
         count = lib.device_count()
     except lib.SdError as e:
-        refuse("%s: the HIP library is not available (%s)" % (what, e.msg))
+        _refuse("%s: the HIP library is not available (%s)" % (what, e.msg))
     bad = [d for d in devs if d >= count]
     if bad and args.devices is None:
-        refuse("%s: %d devices asked for, %d HIP device%s visible" % (what, len(devs), count, "" if count == 1 else "s"))
+        _refuse("%s: %d devices asked for, %d HIP device%s visible" % (what, len(devs), count, "" if count == 1 else "s"))
     if bad:
-        refuse("%s: device %d does not exist (%d HIP device%s visible)" % (what, bad[0], count, "" if count == 1 else "s"))
+        _refuse("%s: device %d does not exist (%d HIP device%s visible)" % (what, bad[0], count, "" if count == 1 else "s"))
     return devs
 
 
@@ -516,30 +519,24 @@ def _check_profile(args, flag="--profile", why="a profile needs one template per
 
 def _check_screen(args):
     """--screen requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
-    def refuse(msg):
-        sys.stderr.write("stringdecomposer: %s\n" % msg)
-        sys.exit(2)
     if shard.world()[2] > 1:
-        refuse("--screen cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
+        _refuse("--screen cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
     if args.screen < 0:
-        refuse("--screen %d: the threshold is an edit distance, at least 0" % args.screen)
+        _refuse("--screen %d: the threshold is an edit distance, at least 0" % args.screen)
     if args.records:
-        refuse("--screen cannot be combined with --records: the record stream holds whole reads")
+        _refuse("--screen cannot be combined with --records: the record stream holds whole reads")
     if args.overlap.isdigit() and args.batch_size.isdigit() and int(args.overlap) >= int(args.batch_size):
-        refuse("--screen needs -v/--overlap smaller than -b/--batch-size (the regions of a read must not overlap)")
+        _refuse("--screen needs -v/--overlap smaller than -b/--batch-size (the regions of a read must not overlap)")
 
 
 def _check_lags(args):
     """--lags requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
-    def refuse(msg):
-        sys.stderr.write("stringdecomposer: %s\n" % msg)
-        sys.exit(2)
     if shard.world()[2] > 1:
-        refuse("--lags cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
+        _refuse("--lags cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
     if not 1 <= args.lags <= lib.LAG_DMAX:
-        refuse("--lags %d: the number of neighbours is 1 .. %d" % (args.lags, lib.LAG_DMAX))
+        _refuse("--lags %d: the number of neighbours is 1 .. %d" % (args.lags, lib.LAG_DMAX))
     if args.records:
-        refuse("--lags cannot be combined with --records: it is a post-pass over the rows of the final TSV")
+        _refuse("--lags cannot be combined with --records: it is a post-pass over the rows of the final TSV")
 
 
 def _heatmap_arg(text):
@@ -552,45 +549,47 @@ def _heatmap_arg(text):
 
 def _check_heatmap(args):
     """--heatmap requests this process cannot serve end it here, with one line on stderr, before any work on a GPU."""
-    def refuse(msg):
-        sys.stderr.write("stringdecomposer: %s\n" % msg)
-        sys.exit(2)
     if shard.world()[2] > 1:
-        refuse("--heatmap cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
+        _refuse("--heatmap cannot be combined with a torch.distributed launch (WORLD_SIZE=%d)" % shard.world()[2])
     bw = _heatmap_arg(args.heatmap)
     if bw is None or not 1 <= bw[0] <= lib.HEAT_BMAX or bw[1] >= (1 << 62):
-        refuse("--heatmap %s: expected B or B,W with 1 <= B <= %d rows per bin and W >= 0 (0: no limit) the largest row "
-               "distance of a pair" % (args.heatmap, lib.HEAT_BMAX))
+        _refuse("--heatmap %s: expected B or B,W with 1 <= B <= %d rows per bin and W >= 0 (0: no limit) the largest row "
+                "distance of a pair" % (args.heatmap, lib.HEAT_BMAX))
     if args.heatmap_max_pairs < 0:
-        refuse("--heatmap-max-pairs %d: the cap is 0 (no limit) or more" % args.heatmap_max_pairs)
+        _refuse("--heatmap-max-pairs %d: the cap is 0 (no limit) or more" % args.heatmap_max_pairs)
     if args.records:
-        refuse("--heatmap cannot be combined with --records: it is a post-pass over the rows of the final TSV")
+        _refuse("--heatmap cannot be combined with --records: it is a post-pass over the rows of the final TSV")
 
 
 def _check_lenient(args):
     """--lenient requests this process cannot serve end it here, with one line on stderr, before any work."""
-    def refuse(msg):
-        sys.stderr.write("stringdecomposer: %s\n" % msg)
-        sys.exit(lib.SD_ERR_PARAM)
     if args.ref_compat:
-        refuse("--lenient cannot be combined with --ref-compat, whose purpose is the reference's behaviour (its error for "
-               "lower case, IUPAC codes and CRLF included): drop one of the two, or convert the input to upper-case ACGTN first")
+        _refuse("--lenient cannot be combined with --ref-compat, whose purpose is the reference's behaviour (its error for "
+                "lower case, IUPAC codes and CRLF included): drop one of the two, or convert the input to upper-case ACGTN first",
+                lib.SD_ERR_PARAM)
     if shard.world()[2] > 1:
-        refuse("--lenient cannot be combined with a torch.distributed launch (WORLD_SIZE=%d): the ranks' convert step reads "
-               "the files strictly; use --gpus N / --devices LIST, several GPUs in one process" % shard.world()[2])
+        _refuse("--lenient cannot be combined with a torch.distributed launch (WORLD_SIZE=%d): the ranks' convert step reads "
+                "the files strictly; use --gpus N / --devices LIST, several GPUs in one process" % shard.world()[2], lib.SD_ERR_PARAM)
+
+
+def _reads_by_name(args):
+    """The reads of the job, upper case, by header and by the header's first token (what the TSV names a read by); the
+    first of equal names holds."""
+    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
+    reads = {}
+    for n, s in zip(rn, rs):
+        reads.setdefault(n, s.upper())
+        reads.setdefault(n.split()[0], s.upper())
+    return reads
 
 
 def _write_msa(args, final_fn, msa_fn, device):
     """--msa: one line per row of the final TSV just written (formats.MSA_HEADER), the rows computed read by read on
     `device` (lib.msa_segments: the row kernel, the host form for the pairs it does not take)."""
     from . import formats
-    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
+    reads = _reads_by_name(args)
     mn, ms, _ = lib.fasta_load(args.monomers, lenient=args.lenient)
-    reads, il = {}, {}
-    for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
-        reads.setdefault(n, s.upper())
-        reads.setdefault(n.split()[0], s.upper())
-    ms = [s.upper() for s in ms]
+    ms, il = [s.upper() for s in ms], {}
     for m, n in enumerate(mn):
         for x in (n, n.split()[0]):
             il.setdefault(x, 2 * m)
@@ -599,8 +598,8 @@ def _write_msa(args, final_fn, msa_fn, device):
         f.write(formats.MSA_HEADER)
         for read, rows in formats.by_read(formats.read_final(final_fn)):
             seq = reads[read]
-            st = [min(max(r.start, 0), len(seq)) for r in rows]
-            en = [min(max(r.end + 1, s), len(seq)) - 1 for r, s in zip(rows, st)]   # (an empty segment: end = start - 1)
+            seg = [lib.segment_clamp(r.start, r.end, len(seq)) for r in rows]
+            st, en = [x[0] for x in seg], [x[1] for x in seg]
             pt = [il[r.monomer] for r in rows]
             msa = lib.msa_segments(seq or b"N", st, en, ms, pt, threads=max(1, int(args.threads)), device=device)
             f.write(formats.format_msa(formats.msa_rows(msa, pt, [(r.read, r.start, r.end, r.monomer) for r in rows]),
@@ -613,11 +612,7 @@ def _write_lags(args, final_fn, lags_fn, period_fn, device):
     line per row, and <out>_period.tsv, one line per read."""
     from . import formats
     D = int(args.lags)
-    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
-    reads = {}
-    for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
-        reads.setdefault(n, s.upper())
-        reads.setdefault(n.split()[0], s.upper())
+    reads = _reads_by_name(args)
     groups = formats.by_read(formats.read_final(final_fn))
     with open(lags_fn, "w", newline="") as fl, open(period_fn, "w", newline="") as fp:
         at = 0
@@ -627,9 +622,9 @@ def _write_lags(args, final_fn, lags_fn, period_fn, device):
                 seq = reads[groups[e][0]]
                 seq = seq if isinstance(seq, bytes) else seq.encode()
                 for r in groups[e][1]:
-                    s0 = min(max(r.start, 0), len(seq))
+                    s0, e0 = lib.segment_clamp(r.start, r.end, len(seq))
                     st.append(base + s0)
-                    en.append(base + min(max(r.end + 1, s0), len(seq)) - 1)   # (an empty segment: end = start - 1)
+                    en.append(base + e0)
                     rows.append((r.read, r.start, r.end))
                 text.append(seq)
                 base += len(seq)
@@ -651,11 +646,7 @@ def _write_heatmap(args, final_fn, heat_fn, device):
     from . import formats
     B, W = _heatmap_arg(args.heatmap)
     cap = int(args.heatmap_max_pairs)
-    rn, rs, _ = lib.fasta_load(args.sequences, lenient=args.lenient)
-    reads = {}
-    for n, s in zip(rn, rs):   # (the TSV names a read by its header's first token)
-        reads.setdefault(n, s.upper())
-        reads.setdefault(n.split()[0], s.upper())
+    reads = _reads_by_name(args)
     groups = formats.by_read(formats.read_final(final_fn))
     for read, rows in groups:   # every read's size first: a refusal leaves no half-written file
         _, _, cells, pairs = lib.heat_layout([0, len(rows)], B, W)
@@ -669,8 +660,8 @@ def _write_heatmap(args, final_fn, heat_fn, device):
         for read, rows in groups:
             seq = reads[read]
             seq = seq if isinstance(seq, bytes) else seq.encode()
-            st = [min(max(r.start, 0), len(seq)) for r in rows]
-            en = [min(max(r.end + 1, s), len(seq)) - 1 for r, s in zip(rows, st)]   # (an empty segment: end = start - 1)
+            seg = [lib.segment_clamp(r.start, r.end, len(seq)) for r in rows]
+            st, en = [x[0] for x in seg], [x[1] for x in seg]
             heat = lib.heat_segments(seq or b"N", st, en, [0, len(rows)], B, W, device=device, threads=max(1, int(args.threads)),
                                      max_pairs=cap)
             f.write(formats.format_heatmap(formats.heat_rows(heat, 0, read, [(r.start, r.end) for r in rows])))
