@@ -1364,6 +1364,51 @@ int sd_motif_kernel_bench(const char* text, const int64_t* read_off, const int64
                           int32_t n_motifs, int32_t E, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_size,
                           float* ms_write, int64_t info[4]);
 
+/* ---- IUPAC motif hits with insertions and deletions (--motif-edits; csrc/sd_motif_edit.hpp holds the rule) ------------
+ * Patterns, strands, the byte rule, the reads, per and the buffer rules are those of sd_motif_* above.  With K edits allowed
+ * (0 <= K <= SD_MOTIF_KMAX): a text byte the code does not match costs 1, an inserted text byte costs 1, a deleted
+ * pattern code costs 1 (an N too).  d(j), 1 <= j <= n, is the smallest edit distance of the pattern to any substring of
+ * the read that ends just before position j; d(0) = L, d(n + 1) is infinite.  End j is a hit when d(j) <= K and
+ * d(j) <= d(j + 1) and (d(j) < d(j - 1) or d(j) = 0): the first end of every valley and every exact occurrence.  The start
+ * of a hit is the largest s with ed(pattern, read[s .. j)) = d(j); its length is L - d .. L + d.
+ * hits: sd_motif_edit_hit records in canonical order -- read, then motif in request order, then + before -, then end.
+ * Limits, each refused (SD_ERR_PARAM) with its numbers in errbuf: at most SD_MOTIF_MAX motifs; every motif needs more than
+ * K constrained positions; at most SD_MOTIF_ITEMS_MAX (tile of SD_MOTIF_EDIT_TILE_WORDS words of a read, pattern-strand)
+ * items per call, refused before any device work; at most SD_MOTIF_HITS_MAX hits per call, refused when the size pass has
+ * counted them and before a record is written.
+ * sd_motif_edit_host / sd_motif_edit_dev: as sd_motif_host / sd_motif_dev; both give the same arrays byte for byte.
+ * sd_motif_edit_reads_size_dev / sd_motif_edit_reads_write_dev: as sd_motif_reads_size_dev / sd_motif_reads_write_dev,
+ *   with a work area of their own: the write call follows the last edit size call on that device.
+ * sd_motif_edit_info: info = {bases of a lane's stretch, SD_MOTIF_EDIT_TILE_WORDS, pattern-strands a workgroup takes, the
+ *   most end x pattern-strand products of one launch, launches of the size and write kernels in this process so far,
+ *   workgroups of one launch at most}.
+ * sd_motif_edit_kernel_bench: as sd_motif_kernel_bench. */
+#define SD_MOTIF_KMAX 7
+#define SD_MOTIF_EDIT_TILE_WORDS 256
+typedef struct {
+    int64_t start;        /* leftmost base, 0-based; the hit ends at start + length - 1 (inclusive) */
+    int32_t read;
+    uint16_t motif;       /* index in the request */
+    uint8_t length;       /* matched bases: L - edits .. L + edits */
+    uint8_t strand_edits; /* strand << 7 | edits; strand 0: '+', 1: '-' */
+} sd_motif_edit_hit;
+int sd_motif_edit_host(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                       int32_t n_motifs, int32_t K, int32_t threads, sd_motif_edit_hit** hits, int64_t* n_hits, int64_t* per, char* errbuf,
+                       size_t errlen);
+int sd_motif_edit_dev(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                      int32_t n_motifs, int32_t K, int32_t device, sd_motif_edit_hit** hits, int64_t* n_hits, int64_t* per, char* errbuf,
+                      size_t errlen);
+int sd_motif_edit_reads_size_dev(const void* d_text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads,
+                                 const char* const* patterns, int32_t n_motifs, int32_t K, int32_t device, void* hip_stream, int64_t* d_per,
+                                 int64_t* n_hits, char* errbuf, size_t errlen);
+int sd_motif_edit_reads_write_dev(const void* d_text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads,
+                                  const char* const* patterns, int32_t n_motifs, int32_t K, int32_t device, void* hip_stream,
+                                  sd_motif_edit_hit* d_hits, int64_t cap, char* errbuf, size_t errlen);
+void sd_motif_edit_info(int64_t info[6]);
+int sd_motif_edit_kernel_bench(const char* text, const int64_t* read_off, const int64_t* read_lens, int32_t n_reads, const char* const* patterns,
+                               int32_t n_motifs, int32_t K, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_size,
+                               float* ms_write, int64_t info[4]);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

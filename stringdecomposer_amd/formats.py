@@ -1302,6 +1302,28 @@ class Motifs:
         return [len(p) for p in self.patterns]
 
 
+class MotifEdits:
+    """lib.motif_edits / DeviceMotifEdits.to_host(): hits = a numpy record array (start, read, motif, length, strand_edits:
+    sd_motif_edit_hit of include/sd_hip.h) in canonical order -- read, motif in request order, + before -, end; per = int64
+    [reads, motifs, 2]; names, patterns: the request; K: the edits allowed."""
+
+    def __init__(self, hits, per, names, patterns, K):
+        self.hits, self.per, self.names, self.patterns, self.K = hits, per, list(names), list(patterns), int(K)
+
+    @property
+    def strand(self):
+        return self.hits["strand_edits"] >> 7
+
+    @property
+    def edits(self):
+        return self.hits["strand_edits"] & 127
+
+    @property
+    def end(self):
+        """one past the last base of every hit"""
+        return self.hits["start"] + self.hits["length"]
+
+
 MotifRow = namedtuple("MotifRow", "read start end strand motif mismatches sequence")   # a line of <out>_motif.tsv
 MotifRowsRow = namedtuple("MotifRowsRow", "read start end monomer counts")              # ... of <out>_motif_rows.tsv; counts: ((motif, n), ...)
 MotifMonomerRow = namedtuple("MotifMonomerRow", "monomer motif rows rows_hit hits")     # ... of <out>_motif_monomers.tsv
@@ -1333,6 +1355,22 @@ def motif_rows(motifs, read_names, reads):
     return out
 
 
+def motif_edit_rows(motifs, read_names, reads):
+    """The lines of <out>_motif.tsv for a MotifEdits -> [MotifRow] with end = start + length - 1 and the edits in the sixth
+    column, in the order read, start, end, motif, strand"""
+    import numpy as np
+    h = motifs.hits
+    strand, end = motifs.strand, h["start"] + h["length"].astype(np.int64) - 1
+    order = np.lexsort((strand, h["motif"], end, h["start"], h["read"]))
+    out = []
+    for start, r, m, length, se in h[order].tolist():
+        seq = reads[r]
+        seq = seq.encode() if isinstance(seq, str) else seq
+        out.append(MotifRow(read_names[r], start, start + length - 1, "-" if se >> 7 else "+", motifs.names[m], se & 127,
+                            motif_sequence(seq[start:start + length], se >> 7)))
+    return out
+
+
 def format_motif(rows):
     return "".join("%s\t%d\t%d\t%s\t%s\t%d\t%s\n" % tuple(r) for r in rows)
 
@@ -1360,12 +1398,24 @@ def motif_row_counts(hits, final_rows, lengths, read_names=None):
     lists: the rows by (read, start), and for every hit the last row that starts at or before it."""
     import numpy as np
     lengths = np.asarray(lengths, dtype=np.int64)
+    return _motif_row_join(hits, lengths[hits["motif"].astype(np.int64)] if len(hits) else lengths[:0], len(lengths), final_rows, read_names)
+
+
+def motif_edit_row_counts(hits, final_rows, n_motifs, read_names=None):
+    """motif_row_counts for sd_motif_edit_hit records: every hit has its own length, end = start + hit.length - 1."""
+    import numpy as np
+    return _motif_row_join(hits, hits["length"].astype(np.int64), n_motifs, final_rows, read_names)
+
+
+def _motif_row_join(hits, hit_len, n_motifs, final_rows, read_names):
+    """the join of motif_row_counts; hit_len: the bases of every hit"""
+    import numpy as np
     index = {n: i for i, n in enumerate(read_names)} if read_names is not None else None
     n = len(final_rows)
     rr = np.fromiter(((index[r[0]] if index is not None else r[0]) for r in final_rows), dtype=np.int64, count=n)
     rs = np.fromiter((r[2] for r in final_rows), dtype=np.int64, count=n)
     re_ = np.fromiter((r[3] for r in final_rows), dtype=np.int64, count=n)
-    out = np.zeros((n, len(lengths)), dtype=np.int64)
+    out = np.zeros((n, n_motifs), dtype=np.int64)
     if n == 0 or len(hits) == 0:
         return out
     order = np.lexsort((rs, rr))
@@ -1374,7 +1424,7 @@ def motif_row_counts(hits, final_rows, lengths, read_names=None):
     hm = hits["motif"].astype(np.int64)
     at = np.searchsorted(key, (hits["read"].astype(np.int64) << 42) + hs, side="right") - 1
     row = order[np.maximum(at, 0)]
-    inside = (at >= 0) & (rr[row] == hits["read"]) & (rs[row] <= hs) & (hs + lengths[hm] - 1 <= re_[row])
+    inside = (at >= 0) & (rr[row] == hits["read"]) & (rs[row] <= hs) & (hs + hit_len - 1 <= re_[row])
     np.add.at(out, (row[inside], hm[inside]), 1)
     return out
 

@@ -65,6 +65,8 @@ EXPORTS = [
     "sd_autocorr_seed", "sd_autocorr_info", "sd_autocorr_kernel_bench",
     "sd_motif_compile", "sd_motif_host", "sd_motif_dev", "sd_motif_reads_size_dev", "sd_motif_reads_write_dev", "sd_motif_info",
     "sd_motif_kernel_bench",
+    "sd_motif_edit_host", "sd_motif_edit_dev", "sd_motif_edit_reads_size_dev", "sd_motif_edit_reads_write_dev", "sd_motif_edit_info",
+    "sd_motif_edit_kernel_bench",
     "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
     "sd_hor_rows", "sd_hor_final_host", "sd_hor_name", "sd_hor_info",
     "sd_dotplot_layout", "sd_dotplot_host", "sd_dotplot_dev", "sd_dotplot_reads_dev", "sd_dotplot_info", "sd_dotplot_hash", "sd_dotplot_kernel_bench",
@@ -309,6 +311,13 @@ def load():
     L.sd_motif_info.restype = None
     L.sd_motif_kernel_bench.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, P(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int64)]
+    L.sd_motif_edit_host.argtypes = L.sd_motif_host.argtypes
+    L.sd_motif_edit_dev.argtypes = L.sd_motif_dev.argtypes
+    L.sd_motif_edit_reads_size_dev.argtypes = L.sd_motif_reads_size_dev.argtypes
+    L.sd_motif_edit_reads_write_dev.argtypes = L.sd_motif_reads_write_dev.argtypes
+    L.sd_motif_edit_info.argtypes = [P(C.c_int64)]
+    L.sd_motif_edit_info.restype = None
+    L.sd_motif_edit_kernel_bench.argtypes = L.sd_motif_kernel_bench.argtypes
     L.sd_dotplot_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
     L.sd_dotplot_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -1612,6 +1621,132 @@ def motif_kernel_bench(reads, motifs, E=0, device=0, warmup=2, reps=5):
     text, ro, rl = _reads_text(reads)
     return _bench(load().sd_motif_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E,
                                                  int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
+                  ("launches", "items", "hits", "words"), reps)
+
+
+MOTIF_KMAX = 7
+MOTIF_EDIT_TILE_WORDS = 256
+
+
+def motif_edit_hit_dtype():
+    """sd_motif_edit_hit (include/sd_hip.h) as a numpy dtype: 16 bytes; strand_edits = strand << 7 | edits"""
+    import numpy as np
+    return np.dtype([("start", "<i8"), ("read", "<i4"), ("motif", "<u2"), ("length", "u1"), ("strand_edits", "u1")])
+
+
+def motif_edits_request(motifs, K, who):
+    """The request of an edit call checked on the host -- names and patterns as motif_compile checks them, K an integer
+    0 .. MOTIF_KMAX, every motif with more than K constrained positions -> (names, patterns)"""
+    names, patterns, strands = motif_compile(motifs, 0)
+    _int_arg(who, "edits", K, 0, MOTIF_KMAX)
+    for s in strands:
+        if s.constrained <= K:
+            raise SdError(SD_ERR_PARAM, "%s: motif '%s': %d constrained positions with %d edits allowed: it would hit everywhere"
+                          % (who, names[s.motif], s.constrained, K))
+    return names, patterns
+
+
+def _motif_edit_hits(buf, n):
+    import numpy as np
+    return np.frombuffer(buf, dtype=motif_edit_hit_dtype()).copy() if n else np.zeros(0, dtype=motif_edit_hit_dtype())
+
+
+def motif_edits_info():
+    """sd_motif_edit_info -> {"stretch": consecutive ends a lane owns, "tile": words of a workgroup's tile (256 stretches),
+    "pattern_block": pattern-strands a workgroup takes, "launch_work": the most end x pattern-strand products of one launch,
+    "launches": launches of the size and write kernels in this process so far, "launch_wg": work items of one launch}"""
+    return _info(load().sd_motif_edit_info, ("stretch", "tile", "pattern_block", "launch_work", "launches", "launch_wg"))
+
+
+def motif_edits_text(text, read_off, read_lens, motifs, K, device=None, threads=1):
+    """motif_edits on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any
+    order of offsets are allowed) -> formats.MotifEdits"""
+    import numpy as np
+    from . import formats
+    names, patterns = motif_edits_request(motifs, K, "motif_edits")
+    L = load()
+    tb, ro, rl = _text_reads("motif_edits", text, read_off, read_lens)
+    per = np.zeros((len(rl), len(names), 2), dtype=np.int64)
+    out, n = C.c_void_p(0), C.c_int64(0)
+    err = _err()
+    if device is None:
+        rc = L.sd_motif_edit_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K, int(threads),
+                                  C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
+    else:
+        rc = L.sd_motif_edit_dev(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K, int(device),
+                                 C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
+    _text_check(rc, err)
+    try:
+        hits = _motif_edit_hits(C.string_at(out.value, 16 * n.value), n.value)
+    finally:
+        L.sd_free(out)
+    return formats.MotifEdits(hits, per, names, patterns, K)
+
+
+def motif_edits(reads, motifs, K, device=None, threads=1):
+    """The hits of IUPAC motifs on both strands of every read with up to K edits -- substitutions at the constrained
+    positions, inserted text bytes, deleted pattern codes (include/sd_hip.h: sd_motif_edit_*; csrc/sd_motif_edit.hpp holds
+    the rule).  reads: a list of bytes / str, or a DeviceReads (then the kernels read the device text where it lies).
+    motifs: see motif_request.  device=None: host threads (sd_motif_edit_host); else the kernels of csrc/sd_motif_edit.hip on
+    that device.  Both give the same arrays.  -> formats.MotifEdits"""
+    if isinstance(reads, DeviceReads):
+        return motif_edits_device(reads, motifs, K).to_host()
+    text, ro, rl = _reads_text(reads)
+    return motif_edits_text(text, ro, rl, motifs, K, device, threads)
+
+
+class DeviceMotifEdits(namedtuple("DeviceMotifEdits", "hits per n_hits names patterns K")):
+    """The edit hits of a DeviceReads in device memory (motif_edits_device): hits = uint8 [n_hits, 16], the
+    sd_motif_edit_hit records in canonical order; per = int64 [reads, motifs, 2]; torch tensors on the reads' device."""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> formats.MotifEdits (waits for the device)"""
+        from . import formats
+        return formats.MotifEdits(_motif_edit_hits(self.hits.cpu().numpy().tobytes(), self.n_hits), self.per.cpu().numpy(), self.names,
+                                  self.patterns, self.K)
+
+
+def motif_edits_device(reads, motifs, K, stream=None, hits=None, per=None):
+    """motif_edits on a DeviceReads, everything on the reads' device (sd_motif_edit_reads_size_dev / _write_dev) ->
+    DeviceMotifEdits(hits, per, n_hits, ...).  torch allocates the results on `stream` (None: the device's current stream)
+    -- or hits (uint8, at least 16 bytes per hit) and per (int64, reads x motifs x 2) are used, whatever they hold -- and
+    the library fills them there.  The host waits once, for the number of hits; the call returns with the write kernels in
+    flight."""
+    names, patterns = motif_edits_request(motifs, K, "motif_edits_device")
+    L = load()
+    torch, dev, st = _device_frame(reads.device, stream)
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    nm = len(names)
+    if per is None:
+        with torch.cuda.stream(st):
+            per = torch.empty((reads.n, nm, 2), dtype=torch.int64, device=dev)
+    elif per.dtype != torch.int64 or per.numel() != reads.n * nm * 2 or per.device != dev or not per.is_contiguous():
+        raise SdError(SD_ERR_PARAM, "motif_edits_device: per must be a contiguous int64 tensor of %d x %d x 2 elements on %s" % (reads.n, nm, dev))
+    pats = _strs(patterns)
+    n = C.c_int64(0)
+    err = _err()
+    _text_check(L.sd_motif_edit_reads_size_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, K, dev.index or 0,
+                                               C.c_void_p(st.cuda_stream), _dptr(per), C.byref(n), err, 1024), err)
+    if hits is None:
+        with torch.cuda.stream(st):
+            hits = torch.empty((n.value, 16), dtype=torch.uint8, device=dev)
+    elif hits.dtype != torch.uint8 or hits.device != dev or not hits.is_contiguous():
+        raise SdError(SD_ERR_PARAM, "motif_edits_device: hits must be a contiguous uint8 tensor on %s" % (dev,))
+    _text_check(L.sd_motif_edit_reads_write_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, K, dev.index or 0,
+                                                C.c_void_p(st.cuda_stream), _dptr(hits), hits.numel() // 16, err, 1024), err)
+    return DeviceMotifEdits(hits.view(-1)[:16 * n.value].view(n.value, 16), per.view(reads.n, nm, 2), int(n.value), names, patterns, K)
+
+
+def motif_edits_kernel_bench(reads, motifs, K, device=0, warmup=2, reps=5):
+    """sd_motif_edit_kernel_bench -> {"prep_ms", "size_ms", "write_ms": [...], "launches", "items", "hits", "words"}."""
+    names, patterns = motif_edits_request(motifs, K, "motif_edits_kernel_bench")
+    text, ro, rl = _reads_text(reads)
+    return _bench(load().sd_motif_edit_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K,
+                                                      int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
                   ("launches", "items", "hits", "words"), reps)
 
 

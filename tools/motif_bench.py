@@ -4,11 +4,14 @@ item counted, scanned; sd_motif_write: the records) on synthetic reads -- noisy 
 CENP-B box -- each stage between two HIP events (sd_motif_kernel_bench), `rounds` calls of warmup + reps repetitions each;
 medians, minima and maxima over all repetitions, base x pattern-strand products per second, the wall time of the whole call
 on host memory (sd_motif_dev) and of the device-resident call (sd_motif_reads_size_dev + _write_dev), one JSON line.  With
---host T: also the wall time of sd_motif_host on T threads, `rounds` times.
+--host T: also the wall time of sd_motif_host on T threads, `rounds` times.  With --edits K: the same figures for the kernels
+of --motif-edits (sd_motif_edit_size, sd_motif_edit_write) at a budget of K edits, -E ignored; a product is then one step of
+the bit-vector column, warm-up not counted.
 
 usage: python tools/motif_bench.py [--reads 1000] [--length 50000] [--motifs 0] [-E 1] [--rounds 3] [--reps 5]
        python tools/motif_bench.py --reads 1 --length 50000000
-       python tools/motif_bench.py --reads 100 --motifs 512 -E 0"""
+       python tools/motif_bench.py --reads 100 --motifs 512 -E 0
+       python tools/motif_bench.py --edits 1 --host 16"""
 import argparse
 import json
 import os
@@ -63,20 +66,25 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--edits", type=int, default=None, metavar="K", help="time the kernels of --motif-edits at K edits instead")
     ap.add_argument("--host", type=int, default=0, metavar="T", help="also time sd_motif_host on T threads")
     a = ap.parse_args()
     reads = make_reads(a.reads, a.length, seed=5)
     motifs = make_motifs(a.motifs, seed=6)
-    strands = len(lib.motif_compile(motifs, a.E)[2])
+    edits = a.edits is not None
+    budget = a.edits if edits else a.E
+    kernel_bench, whole, resident = ((lib.motif_edits_kernel_bench, lib.motif_edits, lib.motif_edits_device) if edits else
+                                     (lib.motif_kernel_bench, lib.motif, lib.motif_device))
+    strands = len(lib.motif_compile(motifs, 0 if edits else a.E)[2])
     ms = {"prep_ms": [], "size_ms": [], "write_ms": []}
     info = None
     for _ in range(a.rounds):
-        info = lib.motif_kernel_bench(reads, motifs, a.E, device=a.device, warmup=a.warmup, reps=a.reps)
+        info = kernel_bench(reads, motifs, budget, device=a.device, warmup=a.warmup, reps=a.reps)
         for key in ms:
             ms[key] += info[key]
     products = sum(len(s) for s in reads) * strands
     med = {key: statistics.median(v) for key, v in ms.items()}
-    out = {"reads": a.reads, "length": a.length, "motifs": len(motifs), "pattern_strands": strands, "E": a.E, "write_launches": info["launches"],
+    out = {"reads": a.reads, "length": a.length, "motifs": len(motifs), "pattern_strands": strands, "edits" if edits else "E": budget, "write_launches": info["launches"],
            "items": info["items"], "hits": info["hits"], "plane_words": info["words"], "base_strand_products": products}
     for key in ms:
         out[key] = med[key]
@@ -86,7 +94,7 @@ def main():
     call = []
     for _ in range(a.rounds + 1):   # the whole call on host memory: upload, the three stages, hits and per back (the first is a warm-up)
         t0 = time.perf_counter()
-        lib.motif(reads, motifs, a.E, device=a.device)
+        whole(reads, motifs, budget, device=a.device)
         call.append((time.perf_counter() - t0) * 1e3)
     out["call_ms"] = statistics.median(call[1:])
     out["call_ms_min_max"] = [min(call[1:]), max(call[1:])]
@@ -96,7 +104,7 @@ def main():
     res = []
     for _ in range(a.rounds + 1):   # the device-resident call: reads in HBM, hits left in HBM
         t0 = time.perf_counter()
-        lib.motif_device(dr, motifs, a.E)
+        resident(dr, motifs, budget)
         torch.cuda.synchronize()
         res.append((time.perf_counter() - t0) * 1e3)
     out["resident_ms"] = statistics.median(res[1:])
@@ -106,7 +114,7 @@ def main():
         host = []
         for _ in range(a.rounds):
             t0 = time.perf_counter()
-            lib.motif(reads, motifs, a.E, threads=a.host)
+            whole(reads, motifs, budget, threads=a.host)
             host.append((time.perf_counter() - t0) * 1e3)
         out["host_threads"] = a.host
         out["host_ms"] = statistics.median(host)
