@@ -1409,6 +1409,59 @@ int sd_motif_edit_kernel_bench(const char* text, const int64_t* read_off, const 
                                int32_t n_motifs, int32_t K, int32_t device, int32_t warmup, int32_t reps, float* ms_prep, float* ms_size,
                                float* ms_write, int64_t info[4]);
 
+/* ---- cyclic pairs and the merge of seed monomers (--autocorr-merge, bin/sd-merge; csrc/sd_cyclic.hpp holds the rule) --
+ * n sequences, sequence i = text[off[i] .. off[i] + lens[i]): upper-case A C G T only, length >= 1; anything else is
+ * SD_ERR_PARAM with the sequence's index, before any device work.
+ * The pair of a query q and a target t: on strand s (0 = +: t, 1 = -: its reverse complement) the text is U = t^s t^s
+ * without its last base; D(j) = the smallest unit-cost edit distance of q to a substring of U that ends at j inclusive
+ * (the empty substring allowed); dist_s = min D, end_s = the smallest j that attains it; the result is that of +, unless
+ * dist_- is strictly smaller.  phase = (end + 1) mod |t|.
+ * sd_cyclic_pairs_host / sd_cyclic_pairs_dev: queries qi[m] x targets ti[k] (indices of sequences, repeats allowed),
+ * m * k <= 2^24 -> dist / end / strand [m * k], pair (a, b) at a * k + b.  Both give the same arrays byte for byte.  The
+ * device form runs queries of <= SD_CYCLIC_QMAX bp against targets of <= SD_CYCLIC_TMAX bp on the device and every other
+ * pair of the call on `threads` host threads.
+ * sd_cyclic_merge_host / sd_cyclic_merge_dev: n <= 2^20 sequences, weight[n], 1 <= P <= 100.  R(q) = (100 - P) |q| / 100
+ * rounded down; q is close to a centre c when abs(|q| - |c|) <= R(q) and dist(q in c) <= R(q).  The sequences are visited
+ * by weight descending, then index ascending: one close to no centre so far becomes the next centre, any other joins the
+ * close centre of smallest dist, the earliest of equals.  block: sequences per step, 0 = the default; the result does not
+ * depend on it.  -> per sequence cluster (0-based, in order of creation), centre (the index of the cluster's centre),
+ * dist / end / strand of the sequence in its centre (a centre: 0, |c| - 1, 0), and *n_clusters.
+ * sd_cyclic_canon: out[len] = the lexicographically smallest among all rotations of seq and of its reverse complement,
+ * = s[*rotation ..] s[.. *rotation) with s = seq (*strand 0) or its reverse complement (*strand 1); the smallest such
+ * rotation, strand 0 where both give the same record.
+ * sd_cyclic_info: info = {SD_CYCLIC_QMAX, SD_CYCLIC_TMAX, the step bound of a launch, launches of the pair kernel in this
+ * process so far, pairs of a call at most, the default block (128)}.  The bound of a launch is compound: it takes at most
+ * info[2] = 2^31 word steps (columns x words x pairs) or SD_CYCLIC_LAUNCH_WG_MIN workgroups, whichever is more -- a
+ * workgroup of 32-word queries is 3e7 steps and more, and the step bound alone would leave most of the device idle.  So
+ * info[2] is the most only while workgroups are small; the most there can be is SD_CYCLIC_LAUNCH_WG_MIN times the largest
+ * workgroup (64 queries x 32 words x the 2 (2 x 65 535 - 1) columns of one target at the limit): 5.5e11 steps, seconds of
+ * kernel, with one of the workgroup's four waves at work on its one target.  That shape was not measured.
+ * sd_cyclic_kernel_bench: the launches of sd_cyclic_pairs_dev between two events, warmup untimed rounds, then reps timed
+ * ones into ms_pairs[reps]; info = {launches per round, pairs on the device, word steps, workgroups}.  variant: 0 = the
+ * kernels the library chooses, 1 = the column in 64-bit words for every class, 2 = in 32-bit halves for the classes of up
+ * to four words (the two give the same arrays).  dist / end / strand (all three, or NULL): the arrays of the timed call;
+ * a pair beyond the device's limits is not computed here and its three entries are unspecified (where any pair of the
+ * call ran on the device, the whole device arrays are copied back, those entries with what the work area held). */
+#define SD_CYCLIC_QMAX 2048
+#define SD_CYCLIC_TMAX 65535
+#define SD_CYCLIC_LAUNCH_WG_MIN 1024
+int sd_cyclic_pairs_host(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
+                         int32_t m, int32_t k, int32_t threads, int32_t* dist, int32_t* end, uint8_t* strand, char* errbuf, size_t errlen);
+int sd_cyclic_pairs_dev(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
+                        int32_t m, int32_t k, int32_t device, int32_t threads, int32_t* dist, int32_t* end, uint8_t* strand, char* errbuf,
+                        size_t errlen);
+int sd_cyclic_merge_host(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int64_t* weight, int32_t P,
+                         int32_t block, int32_t threads, int32_t* cluster, int32_t* centre, int32_t* dist, int32_t* end, uint8_t* strand,
+                         int32_t* n_clusters, char* errbuf, size_t errlen);
+int sd_cyclic_merge_dev(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int64_t* weight, int32_t P,
+                        int32_t block, int32_t device, int32_t threads, int32_t* cluster, int32_t* centre, int32_t* dist, int32_t* end,
+                        uint8_t* strand, int32_t* n_clusters, char* errbuf, size_t errlen);
+int sd_cyclic_canon(const char* seq, int64_t len, char* out, int64_t* rotation, int32_t* strand);
+void sd_cyclic_info(int64_t info[6]);
+int sd_cyclic_kernel_bench(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
+                           int32_t m, int32_t k, int32_t device, int32_t variant, int32_t warmup, int32_t reps, float* ms_pairs,
+                           int64_t info[4], int32_t* dist, int32_t* end, uint8_t* strand);
+
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the
  * reads' standard chunk plan (part_size, overlap; chunks numbered read by read).  dist is the distance of --ed_thr: the

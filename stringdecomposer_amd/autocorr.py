@@ -9,7 +9,7 @@ import argparse
 import os
 import sys
 
-from . import formats, lib, shard
+from . import cyclic, formats, lib, shard
 
 BATCH_BASES = 1 << 28
 BATCH_CELLS = 1 << 24
@@ -37,6 +37,13 @@ def add_arguments(parser):
                         help="also write <out-file>_autocorr_seeds.fa: for every read whose period counts at least MINCOUNT "
                              "positions, the period's worth of bases where the longest run of such positions starts -- a "
                              "monomer file for a second run with --profile, which polishes it")
+    parser.add_argument("--autocorr-merge", dest="autocorr_merge", type=int, default=None, metavar="P",
+                        help="with --autocorr-seeds, also write <out-file>_autocorr_merged.fa and <out-file>_autocorr_merge.tsv: "
+                             "the seeds of all reads clustered up to rotation and strand -- a seed within 100 - P percent of "
+                             "edits of a cluster's centre, and of its length, joins it; one record per cluster, and per seed "
+                             "its cluster, distance, strand and phase")
+    parser.add_argument("--autocorr-merge-min-size", dest="autocorr_merge_min_size", type=int, default=1, metavar="S",
+                        help="leave clusters of fewer than S seeds out of <out-file>_autocorr_merged.fa (by default 1)")
 
 
 def _ints(text, lo, hi):
@@ -64,6 +71,13 @@ def request(args):
             args.autocorr_peaks, PEAKS_MAX, lib.AUTOCORR_DMAX)
     if args.autocorr_seeds is not None and args.autocorr_seeds < 0:
         return "--autocorr-seeds %d: the smallest count of a seed's period is 0 or more" % args.autocorr_seeds
+    if getattr(args, "autocorr_merge", None) is not None:
+        if args.autocorr_seeds is None:
+            return "--autocorr-merge %d: the merge clusters the seeds, it needs --autocorr-seeds" % args.autocorr_merge
+        if cyclic.percent_error("--autocorr-merge", args.autocorr_merge):
+            return cyclic.percent_error("--autocorr-merge", args.autocorr_merge)
+        if args.autocorr_merge_min_size < 1:
+            return "--autocorr-merge-min-size %d: the smallest cluster written is 1 or more seeds" % args.autocorr_merge_min_size
     return K, D, args.autocorr_window, args.autocorr_min_lag, pr[0], pr[1] if len(pr) == 2 else 8
 
 
@@ -80,9 +94,22 @@ def check(args, prog="stringdecomposer"):
     return req
 
 
+def refuse_merge_alone(args, prog="stringdecomposer"):
+    """--autocorr-merge beside a decomposition without --autocorr: the pass that makes the seeds does not run (the other
+    --autocorr-* options are ignored without it, as they always were; this one asks for files and is refused)"""
+    sys.stderr.write("%s: --autocorr-merge %d: the merge clusters the seeds of --autocorr, it needs --autocorr and --autocorr-seeds\n" % (
+        prog, args.autocorr_merge))
+    sys.exit(2)
+
+
 def files(out_dir, out_file):
     base = os.path.join(out_dir, out_file)
     return base + "_autocorr.tsv", base + "_autocorr_spectrum.tsv", base + "_autocorr_seeds.fa"
+
+
+def merge_files(out_dir, out_file):
+    base = os.path.join(out_dir, out_file)
+    return base + "_autocorr_merged.fa", base + "_autocorr_merge.tsv"
 
 
 def write(args, out_dir, out_file, device):
@@ -94,6 +121,8 @@ def write(args, out_dir, out_file, device):
     names = [n.split()[0] if n.split() else n for n in rn]   # (the TSVs name a read by its header's first token)
     threads = max(1, int(args.threads))
     sum_fn, spec_fn, seed_fn = files(out_dir, out_file)
+    merged_fn, merge_fn = merge_files(out_dir, out_file)
+    merge, seeds = getattr(args, "autocorr_merge", None), []
     fs = open(spec_fn, "w", newline="") if args.autocorr_spectrum else None
     fa = open(seed_fn, "w", newline="") if args.autocorr_seeds is not None else None
     try:
@@ -116,13 +145,22 @@ def write(args, out_dir, out_file, device):
                 if fa:
                     for name, seq in lib.autocorr_seeds(reads, names[at:e], ac, LO, args.autocorr_seeds, R):
                         fa.write(">%s\n%s\n" % (name, seq))
+                        seeds.append((name, seq))
                 at = e
     finally:
         if fs:
             fs.close()
         if fa:
             fa.close()
-    return [sum_fn] + ([spec_fn] if fs else []) + ([seed_fn] if fa else [])
+    saved = [sum_fn] + ([spec_fn] if fs else []) + ([seed_fn] if fa else [])
+    if merge is not None:   # the seeds of all reads, clustered; a failure here leaves every other file
+        try:
+            cyclic.merge_files([n for n, _ in seeds], [s for _, s in seeds], merge, merged_fn, merge_fn, args.autocorr_merge_min_size,
+                               device, threads)
+            saved += [merged_fn, merge_fn]
+        except lib.SdError as e:
+            sys.stderr.write("--autocorr-merge failed: " + e.msg + "\n")
+    return saved
 
 
 def main(argv=None):

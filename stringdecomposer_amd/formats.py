@@ -57,6 +57,11 @@ Two more text files are this package's own (opt-in, `--profile`):
                       <out>_hor_variants.tsv, one line per (order, name): order, name, units, rows, bases.
                       read_hor / read_hor_orders / read_hor_variants below.
 
+  <out>_autocorr_merge.tsv  (`--autocorr-merge P`; `<out>_merge.tsv` of bin/sd-merge) one line per seed, no header: seed,
+                      length, cluster (M1, M2, ...), centre (the seed that is the cluster's centre), distance, identity
+                      ("%.2f" of 100 (length - distance) / length, printf's rounding), strand, phase.  <out>_autocorr_merged.fa / <out>_merged.fa: one record per cluster, its canonical
+                      record.  read_merge / write_merge / merged_records below.
+
 A fourth, binary, file is this package's own (the reference has no counterpart; opt-in, `--records`):
 
   <out>_raw.sdr   the rows of <out>_raw.tsv as 16-byte records per read (read_records / write_records below;
@@ -1492,3 +1497,76 @@ def write_motif_monomers(path, rows):
 def read_motif_monomers(path):
     """<out>_motif_monomers.tsv -> [MotifMonomerRow]."""
     return _parse(path, False, 5, (_ident, _ident, int, int, int), MotifMonomerRow)
+
+
+# ---- the merge of seed monomers (--autocorr-merge, bin/sd-merge) ---------------------------------------
+# <out>_autocorr_merge.tsv / <out>_merge.tsv, one line per sequence in input order, no header: seed (the header's first
+# token), length, cluster (M1, M2, ... in order of creation), centre (the seed that is the cluster's centre), distance (the
+# cyclic edit distance of the seed in its centre), identity = "%.2f" of 100 (length - distance) / length, strand and phase of the fit
+# (a centre: 0, 100.00, +, 0).  <out>_autocorr_merged.fa / <out>_merged.fa: one record per cluster, its canonical record.
+CyclicPairs = namedtuple("CyclicPairs", "dist end strand phase")   # [queries, targets] each; strand 0 = +, 1 = -
+CyclicMerge = namedtuple("CyclicMerge", "cluster centre dist end strand phase n_clusters")   # per sequence; cluster 0-based
+MergeRow = namedtuple("MergeRow", "seed length cluster centre distance identity strand phase")
+MergedRecord = namedtuple("MergedRecord", "name sequence cluster size count centre rotation strand")
+
+
+def _token(name):
+    return name.split()[0] if name.split() else name
+
+
+def merge_identity(length, distance):
+    """100 (length - distance) / length as "%.2f" prints it: the integer 100 (length - distance) divided by the integer
+    length in one correctly rounded double division, then printf's rounding of that double (an exact tie such as 90.625
+    goes to the even digit: 90.62)"""
+    return "%.2f" % (100 * (length - distance) / length)
+
+
+def merge_rows(merge, names, lens):
+    """The lines of the merge TSV for a CyclicMerge of the sequences `names` (headers) of lengths `lens` -> [MergeRow]"""
+    return [MergeRow(_token(names[i]), int(lens[i]), "M%d" % (int(merge.cluster[i]) + 1), _token(names[int(merge.centre[i])]), int(merge.dist[i]),
+                     merge_identity(int(lens[i]), int(merge.dist[i])), "-" if merge.strand[i] else "+", int(merge.phase[i]))
+            for i in range(len(names))]
+
+
+def format_merge(rows):
+    return "".join("%s\t%d\t%s\t%s\t%d\t%s\t%s\t%d\n" % tuple(r) for r in rows)
+
+
+def write_merge(path, rows):
+    _write_text(path, format_merge(rows))
+
+
+def _merge_identity(x):
+    float(x)
+    return x
+
+
+def read_merge(path):
+    """the merge TSV -> [MergeRow] (identity stays the text it was written as)"""
+    return _parse(path, False, 8, (_ident, int, _ident, _ident, int, _merge_identity, _strand, int), MergeRow)
+
+
+def merged_records(merge, names, seqs, weights, canon, min_size=1):
+    """One MergedRecord per cluster of at least min_size sequences, in cluster order: name = the FASTA header
+    "M{k} period={length of the centre} seeds={size} count={sum of weights} centre={seed} rotation={r} strand={+|-}",
+    sequence = the canonical record of the centre.  canon(seq) -> (record, rotation, strand): lib.cyclic_canon."""
+    out = []
+    size, count, centre = [0] * merge.n_clusters, [0] * merge.n_clusters, [0] * merge.n_clusters
+    for i in range(len(names)):
+        c = int(merge.cluster[i])
+        size[c] += 1
+        count[c] += int(weights[i])
+        centre[c] = int(merge.centre[i])
+    for c in range(merge.n_clusters):
+        if size[c] < min_size:
+            continue
+        rec, rot, strand = canon(seqs[centre[c]])
+        seed = _token(names[centre[c]])
+        sign = "-" if strand else "+"
+        out.append(MergedRecord("M%d period=%d seeds=%d count=%d centre=%s rotation=%d strand=%s" % (c + 1, len(rec), size[c], count[c], seed, rot, sign),
+                                rec, c, size[c], count[c], seed, rot, sign))
+    return out
+
+
+def format_merged(records):
+    return "".join(">%s\n%s\n" % (r.name, r.sequence) for r in records)

@@ -67,6 +67,8 @@ EXPORTS = [
     "sd_motif_kernel_bench",
     "sd_motif_edit_host", "sd_motif_edit_dev", "sd_motif_edit_reads_size_dev", "sd_motif_edit_reads_write_dev", "sd_motif_edit_info",
     "sd_motif_edit_kernel_bench",
+    "sd_cyclic_pairs_host", "sd_cyclic_pairs_dev", "sd_cyclic_merge_host", "sd_cyclic_merge_dev", "sd_cyclic_canon", "sd_cyclic_info",
+    "sd_cyclic_kernel_bench",
     "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
     "sd_hor_rows", "sd_hor_final_host", "sd_hor_name", "sd_hor_info",
     "sd_dotplot_layout", "sd_dotplot_host", "sd_dotplot_dev", "sd_dotplot_reads_dev", "sd_dotplot_info", "sd_dotplot_hash", "sd_dotplot_kernel_bench",
@@ -318,6 +320,17 @@ def load():
     L.sd_motif_edit_info.argtypes = [P(C.c_int64)]
     L.sd_motif_edit_info.restype = None
     L.sd_motif_edit_kernel_bench.argtypes = L.sd_motif_kernel_bench.argtypes
+    V = C.c_void_p
+    cyc = [C.c_char_p, V, V, C.c_int32]   # text, off, lens, n
+    L.sd_cyclic_pairs_host.argtypes = cyc + [V, V, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_char_p, C.c_size_t]
+    L.sd_cyclic_pairs_dev.argtypes = cyc + [V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_char_p, C.c_size_t]
+    L.sd_cyclic_merge_host.argtypes = cyc + [V, C.c_int32, C.c_int32, C.c_int32, V, V, V, V, V, P(C.c_int32), C.c_char_p, C.c_size_t]
+    L.sd_cyclic_merge_dev.argtypes = cyc + [V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, V, V, V, V, P(C.c_int32), C.c_char_p, C.c_size_t]
+    L.sd_cyclic_canon.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, P(C.c_int64), P(C.c_int32)]
+    L.sd_cyclic_info.argtypes = [P(C.c_int64)]
+    L.sd_cyclic_info.restype = None
+    L.sd_cyclic_kernel_bench.argtypes = cyc + [V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int64),
+                                               V, V, V]
     L.sd_dotplot_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
     L.sd_dotplot_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -1748,6 +1761,144 @@ def motif_edits_kernel_bench(reads, motifs, K, device=0, warmup=2, reps=5):
     return _bench(load().sd_motif_edit_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K,
                                                       int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
                   ("launches", "items", "hits", "words"), reps)
+
+
+# ---- cyclic pairs and the merge of seed monomers (csrc/sd_cyclic.hpp holds the rule) ---------------------------------------
+CYCLIC_QMAX = 2048        # SD_CYCLIC_QMAX: the longest query the device takes
+CYCLIC_TMAX = 65535       # SD_CYCLIC_TMAX: the longest target the device takes
+CYCLIC_PAIRS_MAX = 1 << 24
+CYCLIC_N_MAX = 1 << 20
+CYCLIC_LAUNCH_WG_MIN = 1024   # SD_CYCLIC_LAUNCH_WG_MIN: a launch is not closed by its step bound below this many workgroups
+
+
+def cyclic_info():
+    """sd_cyclic_info -> {"lmax_query", "lmax_target": the device's limits in bases, "launch_work": the step bound of a
+    launch of the pair kernel, "launches": of that kernel in this process so far, "pairs_max": pairs of a cyclic_pairs
+    call, "block": the default block of cyclic_merge}.  The bound of a launch is compound: at most launch_work word steps
+    (columns x words x pairs) or CYCLIC_LAUNCH_WG_MIN workgroups, whichever is more, so launch_work is the most only while
+    workgroups are small (include/sd_hip.h has the largest launch there can be)."""
+    return _info(load().sd_cyclic_info, ("lmax_query", "lmax_target", "launch_work", "launches", "pairs_max", "block"))
+
+
+def _cyclic_seqs(who, seqs, names=None):
+    """the sequences of a cyclic call as (text, offsets, lengths), each upper-case ACGT of length >= 1 -- refused here by
+    index, and by name where there is one, before the library is called"""
+    sb = [_b(s) for s in seqs]
+    for i, s in enumerate(sb):
+        tag = "sequence %d" % i + (" (%s)" % names[i] if names is not None else "")
+        if not s:
+            raise SdError(SD_ERR_PARAM, "%s: %s is empty" % (who, tag))
+        if s.strip(b"ACGT"):
+            raise SdError(SD_ERR_PARAM, "%s: %s holds a byte outside ACGT" % (who, tag))
+    return _reads_text(sb)
+
+
+def _cyclic_index(who, name, idx, n):
+    import numpy as np
+    a = np.arange(n, dtype=np.int32) if idx is None else np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+    if len(a) and (int(a.min()) < 0 or int(a.max()) >= n):
+        raise SdError(SD_ERR_PARAM, "%s: %s holds an index outside the %d sequences" % (who, name, n))
+    return a
+
+
+def _cyclic_call(who, seqs, queries, targets):
+    text, ro, rl = _cyclic_seqs(who, seqs)
+    qi, ti = _cyclic_index(who, "queries", queries, len(rl)), _cyclic_index(who, "targets", targets, len(rl))
+    if len(qi) * len(ti) > CYCLIC_PAIRS_MAX:
+        raise SdError(SD_ERR_PARAM, "%s: %d x %d pairs, the cap is %d per call" % (who, len(qi), len(ti), CYCLIC_PAIRS_MAX))
+    return text, ro, rl, qi, ti
+
+
+def cyclic_pairs(seqs, queries=None, targets=None, device=None, threads=1):
+    """Cyclic pairs: for every query q and target t of `seqs` (indices; None = all), the smallest edit distance of q to a
+    substring of t written twice, on either strand, and where that fit ends (include/sd_hip.h: sd_cyclic_pairs_*) ->
+    formats.CyclicPairs(dist, end, strand, phase), int32 / int32 / uint8 / int32 arrays [queries, targets]; phase =
+    (end + 1) mod |t|, where in t (on that strand) a query that is a whole period begins.
+    device=None: host threads (sd_cyclic_pairs_host); else the kernel of csrc/sd_cyclic.hip on that device, with the pairs
+    beyond its limits (query > 2 048 bp, target > 65 535 bp) on `threads` host threads.  Both give the same arrays."""
+    import numpy as np
+    from . import formats
+    text, ro, rl, qi, ti = _cyclic_call("cyclic_pairs", seqs, queries, targets)
+    m, k = len(qi), len(ti)
+    dist, end, strand = np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.uint8)
+    L, err = load(), _err()
+    lead = (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), qi.ctypes.data, ti.ctypes.data, m, k)
+    out = (dist.ctypes.data, end.ctypes.data, strand.ctypes.data, err, len(err))
+    if device is None:
+        rc = L.sd_cyclic_pairs_host(*lead, int(threads), *out)
+    else:
+        rc = L.sd_cyclic_pairs_dev(*lead, int(device), int(threads), *out)
+    _text_check(rc, err, "cyclic_pairs")
+    tl = rl[ti].astype(np.int32) if k else np.zeros(0, dtype=np.int32)
+    phase = (end + 1) % tl[None, :] if m and k else np.zeros((m, k), dtype=np.int32)
+    return formats.CyclicPairs(dist, end, strand, phase.astype(np.int32))
+
+
+def cyclic_merge(seqs, weights=None, P=85, block=None, device=None, threads=1, names=None):
+    """The merge of sequences that are the same monomer up to rotation, strand and (100 - P) percent of edits
+    (csrc/sd_cyclic.hpp has the rule; sd_cyclic_merge_*): visited by weight descending (None: all 0), then index ascending,
+    a sequence joins the closest centre it is close to, or becomes the next centre -> formats.CyclicMerge(cluster, centre,
+    dist, end, strand, phase, n_clusters), arrays per sequence: cluster 0-based in order of creation, centre the index of
+    the cluster's centre, the rest the sequence's pair in its centre.  block: sequences per step (None: the default); the
+    result does not depend on it.  device as in cyclic_pairs.  names: used in refusals only."""
+    import numpy as np
+    from . import formats
+    who = "cyclic_merge"
+    P = _int_arg(who, "P", P, 1, 100)
+    block = 0 if block is None else _int_arg(who, "block", block, 1, None, ", 1 or more")
+    text, ro, rl = _cyclic_seqs(who, seqs, names)
+    n = len(rl)
+    if n > CYCLIC_N_MAX:
+        raise SdError(SD_ERR_PARAM, "%s: %d sequences, the cap is %d" % (who, n, CYCLIC_N_MAX))
+    w = np.zeros(n, dtype=np.int64) if weights is None else np.ascontiguousarray(weights, dtype=np.int64).reshape(-1)
+    if len(w) != n:
+        raise SdError(SD_ERR_PARAM, "%s: %d weights for %d sequences" % (who, len(w), n))
+    cluster, centre, dist, end = (np.zeros(n, dtype=np.int32) for _ in range(4))
+    strand = np.zeros(n, dtype=np.uint8)
+    nc = C.c_int32(0)
+    L, err = load(), _err()
+    lead = (text or b"N", ro.ctypes.data, rl.ctypes.data, n, w.ctypes.data, P, min(block, 1 << 30))
+    out = (cluster.ctypes.data, centre.ctypes.data, dist.ctypes.data, end.ctypes.data, strand.ctypes.data, C.byref(nc), err, len(err))
+    if device is None:
+        rc = L.sd_cyclic_merge_host(*lead, int(threads), *out)
+    else:
+        rc = L.sd_cyclic_merge_dev(*lead, int(device), int(threads), *out)
+    _text_check(rc, err, who)
+    phase = ((end + 1) % rl[centre].astype(np.int32)).astype(np.int32) if n else np.zeros(0, dtype=np.int32)
+    return formats.CyclicMerge(cluster, centre, dist, end, strand, phase, int(nc.value))
+
+
+def cyclic_canon(seq):
+    """(record, rotation, strand): the lexicographically smallest among all rotations of seq and of its reverse complement
+    = s[rotation:] + s[:rotation] with s = seq (strand 0) or its reverse complement (strand 1) (sd_cyclic_canon)"""
+    sb = _b(seq)
+    if not sb or sb.strip(b"ACGT"):
+        raise SdError(SD_ERR_PARAM, "cyclic_canon: the sequence is empty or holds a byte outside ACGT")
+    out = C.create_string_buffer(len(sb))
+    rot, strand = C.c_int64(0), C.c_int32(0)
+    _check(load().sd_cyclic_canon(sb, len(sb), out, C.byref(rot), C.byref(strand)), "sd_cyclic_canon")
+    return out.raw.decode(), int(rot.value), int(strand.value)
+
+
+def cyclic_kernel_bench(seqs, queries=None, targets=None, device=0, warmup=2, reps=5, variant=0, arrays=False):
+    """sd_cyclic_kernel_bench -> {"pairs_ms": [...], "launches", "pairs", "steps", "workgroups"}: the pair kernel's launches
+    of cyclic_pairs(seqs, queries, targets, device) between two events; pairs and steps (columns x words x pairs) on the
+    device.  variant: 0 = the kernels the library chooses, 1 = 64-bit words throughout, 2 = 32-bit halves up to four words.
+    arrays=True: also "dist", "end", "strand" of the timed variant, as cyclic_pairs gives them."""
+    import numpy as np
+    text, ro, rl, qi, ti = _cyclic_call("cyclic_kernel_bench", seqs, queries, targets)
+    variant = _int_arg("cyclic_kernel_bench", "variant", variant, 0, 2)
+    m, k = len(qi), len(ti)
+    ms, info = (C.c_float * reps)(), (C.c_int64 * 4)()
+    dist, end, strand = np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.uint8)
+    _check(load().sd_cyclic_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), qi.ctypes.data, ti.ctypes.data, m, k, int(device),
+                                         variant, int(warmup), int(reps), ms, info, dist.ctypes.data, end.ctypes.data, strand.ctypes.data),
+           "sd_cyclic_kernel_bench")
+    out = {"pairs_ms": [float(x) for x in ms]}
+    out.update(zip(("launches", "pairs", "steps", "workgroups"), (int(x) for x in info)))
+    if arrays:
+        out.update(dist=dist, end=end, strand=strand)
+    return out
 
 
 DOTPLOT_KMAX = 32

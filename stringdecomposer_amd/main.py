@@ -753,6 +753,8 @@ def main(argv=None):
         _check_heatmap(args)
     if args.autocorr is not None:
         autocorr.check(args)
+    elif args.autocorr_merge is not None:
+        autocorr.refuse_merge_alone(args)
     if args.dotplot is not None:
         dotplot.check(args)
     if args.split is not None:
