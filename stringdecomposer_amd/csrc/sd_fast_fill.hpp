@@ -199,8 +199,8 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     using lds_u4 = __attribute__((address_space(3))) const u32x4_t;
     const uint32_t lds_lane = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint32_t*)lds + lane * 16;
-    auto load_table = [&](int r, uint32_t& after) {
-        uint32_t addr = lds_lane + (uint32_t)(r * (P4 * 256));
+    auto load_table_at = [&](uint32_t off, uint32_t& after) {   // off: byte offset of the symbol's table, r * (P4 * 256)
+        uint32_t addr = lds_lane + off;
         asm volatile("" : "+v"(addr), "+v"(after));
         lds_u4* t = (lds_u4*)(uintptr_t)addr;
 #pragma unroll
@@ -208,6 +208,15 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
             const u32x4_t q = t[c4 * 64];
             tb[4 * c4 + 0] = q.x; tb[4 * c4 + 1] = q.y; tb[4 * c4 + 2] = q.z; tb[4 * c4 + 3] = q.w;
         }
+    };
+    auto load_table = [&](int r, uint32_t& after) { load_table_at((uint32_t)(r * (P4 * 256)), after); };
+    // SLOT_RUNS: the sums of the slots behind the largest floor group read cells the in-place floors never touch, so they
+    // are made as soon as a row's cells and the next row's table are there (the row tail, between two crossbar trips of
+    // the carry scan) and the run in front of the chain holds the other slots' only
+    constexpr int PRE_FROM = SLOT_RUNS ? (FL < P - 1 ? FL : P - 1) + 1 : P;   // first slot whose sum is made ahead
+    auto pre_add = [&]() {
+#pragma unroll
+        for (int q = P - 1; q >= PRE_FROM; --q) asm volatile("v_add_u32 %0, %0, %1" : "+v"(tb[q]) : "v"(L[q - 1]));
     };
     // exclusive, template-segmented prefix maximum over the virtual lanes (both planes at once):
     // H = Vmax-1 carry hops of one lane each (DPP wave_shr:1)
@@ -236,13 +245,22 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
         return bfi(contMask, lane_up(inc, 1), NEGC);
     };
     // B_{row} (relative to base) = max over template ends; arg = smallest virtual lane attaining it
-    auto reduce_ends = [&](uint32_t Eend, int row) {
-        if constexpr (HRED) {
-            uint32_t val = CO::add(Eend, endOff);
-            if constexpr (U16 && RANKED) val &= endMask;   // (unranked: an idle plane's total and end offset are both 0)
+    // HRED: the reduction in three parts, so that the row loop can put LDS traffic between them (see the row tail):
+    // the lane's end value, its wave maximum (DPP), and the arg-max with the B word of the row
+    auto ends_val = [&](uint32_t Eend) {
+        uint32_t val = CO::add(Eend, endOff);
+        if constexpr (U16 && RANKED) val &= endMask;   // (unranked: an idle plane's total and end offset are both 0)
+        return val;
+    };
+    // (the join of the two planes is an instruction of its own: issued before the table reads, its result lives across
+    // them and so cannot share a register with a table word -- the DPP chain then needs no LDS wait in front of it)
+    auto ends_join = [&](uint32_t val) {
             uint32_t m;
-            asm("v_max_f16_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1\n\t"
-                "s_nop 1\n\t"
+            asm("v_max_f16_sdwa %0, %1, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1" : "=v"(m) : "v"(val));
+            return m;
+    };
+    auto ends_max = [&](uint32_t m) {
+            asm("s_nop 1\n\t"
                 "v_max_f16_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
                 "s_nop 1\n\t"
                 "v_max_f16_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
@@ -254,8 +272,10 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 "v_max_f16_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
                 "s_nop 1\n\t"
                 "v_max_f16_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
-                : "=&v"(m) : "v"(val));
-            const uint32_t b16 = (uint32_t)__builtin_amdgcn_readlane((int)m, 63) & 0xffffu;
+                : "+v"(m));
+            return (uint32_t)__builtin_amdgcn_readlane((int)m, 63) & 0xffffu;
+    };
+    auto ends_put = [&](uint32_t val, uint32_t b16, int row) {
             unsigned long long mlo, mhi;
             asm("v_cmp_eq_f16_e64 %0, %1, %2" : "=s"(mlo) : "v"(val), "s"(b16));
             asm("v_cmp_eq_f16_sdwa %0, %1, %2 src0_sel:WORD_1 src1_sel:WORD_0" : "=s"(mhi) : "v"(val), "s"(b16));
@@ -284,6 +304,11 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 const int Bv = base + bi - sc.del + tpl * sc.ins;
                 if (lane <= slot) Bc[row - slot + lane] = (int)(((uint32_t)Bv << 7) | (w & 127u));
             }
+    };
+    auto reduce_ends = [&](uint32_t Eend, int row) {
+        if constexpr (HRED) {
+            const uint32_t val = ends_val(Eend);
+            ends_put(val, ends_max(ends_join(val)), row);
             return;
         }
         const uint32_t val = CO::add(Eend, endOff);
@@ -352,6 +377,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
     K = excl_scan(a0);
     uint32_t Eend = CO::mx(a0, K);
     if constexpr (!HRED) reduce_ends(Eend, 1);
+    pre_add();   // row 1's sums behind the floor groups, as every row's tail makes them for the next
 
     // rows in groups of FAST_R: the per-group work (fairness, scan form, rebase, checkpoint) sits between two inner loops
     // instead of behind a test in every row
@@ -382,6 +408,9 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                     K = shift(K, d2m & notStart);
 #pragma unroll
                     for (int s = 0; s < P; ++s) L[s] = shift(L[s], d2m);
+                    // the sums made ahead for row i hold cells of before the shift: they move with them
+#pragma unroll
+                    for (int q = PRE_FROM; q < P; ++q) tb[q] = shift(tb[q], d2m);
                     guard.check_low(L, planeMask);
                 } else if constexpr (F16) {
                     guard.check_high(L);
@@ -404,7 +433,32 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
             if (lane == 0) ckb[q] = base + tp * sc.ins;
         }
         const int iend = min(n, (i | (FAST_R - 1)) + 1);
+        // SLOT_RUNS: the scan form of the group as a scalar word, compared anew at each of the tail's three tests (s_cmp +
+        // scalar branch).  One bool shared by the three was carried across the blocks as a lane mask, whose negation the
+        // compiler rebuilt through a VGPR in every row (v_cndmask + v_cmp: two vector instructions)
+        const int trips_word = bperm_scan;
+        auto trips_on = [&]() {
+            int t = trips_word;
+            asm volatile("" : "+s"(t));
+            return t != 0;
+        };
+        (void)trips_on;
         for (; i < iend; ++i) {
+        // the floor level of this row (FLS > 0), scalar, by the read symbols of rows i-1 and i
+        int lv = 0;
+        uint32_t toff = 0;
+        (void)lv; (void)toff;
+        if constexpr (FLS > 0) lv = (int)(levels >> (2 * (5 * rprev + rcur))) & 3;
+        if constexpr (SLOT_RUNS) {
+            // ... and then the symbol and the table offset of row i+1: nothing here depends on the row's cells, so the
+            // scalar unit does it under the slot loop instead of between the chain and the table reads, and the stream's
+            // refill loads (scalar memory, which lgkmcnt counts out of order) stay away from the LDS operations of the tail
+            rprev = rcur;
+            rcur = rs.code(i + 1);
+            rs.advance(i + 1);
+            toff = (uint32_t)(rcur * (P4 * 256));
+            asm volatile("" : "+s"(lv), "+s"(toff));
+        }
         uint32_t KB;
         if constexpr (HRED) {
             // max(K, {b+del, b+del}): the scalar's low half feeds both lanes of the packed op
@@ -433,7 +487,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 constexpr int FL3 = FL - 3 * FLS > 1 ? FL - 3 * FLS : 1;
                 constexpr int FL2 = FL - 2 * FLS > FL3 ? FL - 2 * FLS : FL3;
                 constexpr int FL1 = FL - FLS > FL2 ? FL - FLS : FL2;
-                const int lv = (int)(levels >> (2 * (5 * rprev + rcur))) & 3;   // scalar: the level of this row by the previous and its own read symbol
+                // (lv, scalar: the level of this row by the previous and its own read symbol)
 #pragma unroll
                 for (int q = 1; q <= FL3 && q < P; ++q) L[q - 1] = CO::mx(L[q - 1], KB);
                 if (lv <= 2) {
@@ -457,7 +511,7 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
                 // through any sched_barrier.  Each maximum consumes the one before it; the compiler puts the wait state
                 // (s_nop 0, no VALU slot) in front.
 #pragma unroll
-                for (int q = P - 1; q >= 1; --q) asm volatile("v_add_u32 %0, %0, %1" : "+v"(tb[q]) : "v"(L[q - 1]));
+                for (int q = PRE_FROM - 1; q >= 1; --q) asm volatile("v_add_u32 %0, %0, %1" : "+v"(tb[q]) : "v"(L[q - 1]));
                 asm volatile("v_add_u32 %0, %0, %1" : "+v"(tb[0]) : "v"(KB));
                 // slot 0: the old carry K joins the chain here (see the skewed loop below)
                 asm volatile("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(L[0]) : "v"(tb[0]), "v"(w0f), "v"(K));
@@ -514,6 +568,53 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
             __builtin_amdgcn_sched_barrier(0);
         }
         }
+        if constexpr (SLOT_RUNS) {
+            // Row tail of the SLOT_RUNS kernels (the other kernels keep the order below this block: table reads, first
+            // trip, one LDS wait, the whole reduction, the two other trips back to back).  Everything here needs only the
+            // lane total `a`, final when the chain ends.  The order, as compiled:
+            //   1. the first crossbar trip of the carry scan is issued;
+            //   2. the end value a + endOff and the join of its two planes go into registers of their own -- in a table
+            //      register (the unused last word of the last quad is free all row long, and the compiler took it) the
+            //      pending table reads have to be drained before the reduction may write it;
+            //   3. the nine table reads of the next row (its symbol was decoded ahead of the slot loop);
+            //   4. the six DPP steps of the wave maximum and v_readlane run while LDS works: no wait in front of them;
+            //   5. ONE wait for the first trip and the table, then the second trip goes out;
+            //   6. under it: the arg-max compares, their scalar work, the B word of the row, and the sums of the slots
+            //      behind the floor groups for the next row;
+            //   7. second trip back, third trip out; the next row's KB waits for it.
+            // The reduction is ONE piece of code for both scan forms (its accumulator stays in one register); in the DPP
+            // form (no trips) steps 1 and 7 and the trip of step 5 fall away and the scan follows the sums.
+            uint32_t a = L[P - 1];   // K already joined the chain
+            // a 1-bp template ends in slot 0: the pads behind a k = 0 cell keep their old value when the cell's falls
+            if constexpr (ONE) a = bfi(oneMask, L[0], a);   // (the lane is a start lane: no carry to join)
+            ++tp;
+            uint32_t t1, i1;   // (trips: set and read under trips_on() only)
+            if (trips_on()) t1 = (uint32_t)__builtin_amdgcn_ds_bpermute(bp1, (int)a);
+            __builtin_amdgcn_sched_barrier(0);
+            const uint32_t val = ends_val(a);
+            uint32_t m = ends_join(val);
+            load_table_at(toff, m);   // unconditional (clamped): keeps tb[] out of phi copies
+            __builtin_amdgcn_sched_barrier(0);
+            uint32_t b16 = ends_max(m);
+            asm volatile("" : "+s"(b16));   // (pins the chain, which is no volatile asm, in front of the wait below)
+            // (SLOT_RUNS: the wait for the table stands here, in front of the branch, and takes the first trip's with it:
+            // behind the join the compiler would wait for the second trip as well before the sums may read the table)
+            asm volatile("" : : "v"(tb[P4 - 1]));
+            if (trips_on()) {
+                i1 = CO::mx(a, t1);
+                t1 = (uint32_t)__builtin_amdgcn_ds_bpermute(bp2, (int)i1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            ends_put(val, b16, i + 1);
+            pre_add();   // (ONE copy for both scan forms: a copy in each gives the table two register sets, 18 moves per row)
+            if (trips_on()) {
+                const uint32_t i2 = CO::mx(i1, t1);
+                K = (uint32_t)__builtin_amdgcn_ds_bpermute(bp1, (int)i2);
+            } else {
+                K = excl_scan(a);
+            }
+            continue;
+        }
         rprev = rcur;
         rcur = rs.code(i + 1);
         load_table(rcur, L[P - 1]);  // unconditional (clamped): keeps tb[] out of phi copies
@@ -523,8 +624,11 @@ __global__ __launch_bounds__(SD_FILL_NW_MAX * 64, 4) void sd_fast_fill(
         if constexpr (ONE) a = bfi(oneMask, L[0], a);   // (the lane is a start lane: no carry to join)
         ++tp;
         if constexpr (HRED) {
-            // the scan's three crossbar trips run under the DPP chain of the B reduction (both need only `a`); the
-            // reduction is ONE piece of code for both scan forms (its accumulator stays in one register)
+            // fp16 cells, u16 cells with one floor level or a 1-bp template.  The scan's first trip is issued ahead of the
+            // B reduction (both need only `a`), but as compiled the reduction does NOT run under it: its accumulator sits
+            // in the free last word of the last table quad, so the table reads and the trip are drained first; the two
+            // other trips follow the arg-max, one after the other.  The reduction is ONE piece of code for both scan
+            // forms (its accumulator stays in one register)
             uint32_t t1 = 0;
             if (bperm_scan) t1 = (uint32_t)__builtin_amdgcn_ds_bpermute(bp1, (int)a);
             reduce_ends(a, i + 1);
