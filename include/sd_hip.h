@@ -1418,8 +1418,9 @@ int sd_motif_edit_kernel_bench(const char* text, const int64_t* read_off, const 
  * dist_- is strictly smaller.  phase = (end + 1) mod |t|.
  * sd_cyclic_pairs_host / sd_cyclic_pairs_dev: queries qi[m] x targets ti[k] (indices of sequences, repeats allowed),
  * m * k <= 2^24 -> dist / end / strand [m * k], pair (a, b) at a * k + b.  Both give the same arrays byte for byte.  The
- * device form runs queries of <= SD_CYCLIC_QMAX bp against targets of <= SD_CYCLIC_TMAX bp on the device and every other
- * pair of the call on `threads` host threads.
+ * device form runs queries of <= SD_CYCLIC_QMAX_LONG bp against targets of <= SD_CYCLIC_TMAX bp on the device -- those of
+ * <= SD_CYCLIC_QMAX bp one pair to a lane (sd_cyclic_pairs), the longer ones one query across a team of 16, 32 or 64 lanes
+ * with 1 to 4 words in each (sd_cyclic_pairs_long) -- and every other pair of the call on `threads` host threads.
  * sd_cyclic_merge_host / sd_cyclic_merge_dev: n <= 2^20 sequences, weight[n], 1 <= P <= 100.  R(q) = (100 - P) |q| / 100
  * rounded down; q is close to a centre c when abs(|q| - |c|) <= R(q) and dist(q in c) <= R(q).  The sequences are visited
  * by weight descending, then index ascending: one close to no centre so far becomes the next centre, any other joins the
@@ -1441,8 +1442,23 @@ int sd_motif_edit_kernel_bench(const char* text, const int64_t* read_off, const 
  * kernels the library chooses, 1 = the column in 64-bit words for every class, 2 = in 32-bit halves for the classes of up
  * to four words (the two give the same arrays).  dist / end / strand (all three, or NULL): the arrays of the timed call;
  * a pair beyond the device's limits is not computed here and its three entries are unspecified (where any pair of the
- * call ran on the device, the whole device arrays are copied back, those entries with what the work area held). */
+ * call ran on the device, the whole device arrays are copied back, those entries with what the work area held).  It
+ * times and runs the lane kernel only: a query of more than SD_CYCLIC_QMAX bp counts as beyond the limit here.
+ * The team kernel.  SD_CYCLIC_QMAX stays the lane kernel's limit, and sd_cyclic_info's launches stay those of the lane
+ * kernel.  A class of the team kernel is (K, L): K = 1 .. 4 words in each of L = 16, 32 or 64 lanes, 64 K L rows; a
+ * query's class is the one of smallest K L that holds it, the larger K where two are equal.
+ * sd_cyclic_pairs_team_host: the pairs as sd_cyclic_pairs_host gives them, computed by the team kernel's schedule of class
+ * (K, L) on the host -- L lanes in lock step, the carry and the column's symbol handed down one lane per step.  Needs no
+ * device.  SD_ERR_PARAM with one line where (K, L) is no class or a query has more than 64 K L bases.
+ * sd_cyclic_long_info: info = {SD_CYCLIC_QMAX_LONG, launches of the team kernel in this process so far, the number of
+ * instantiated classes (12), teams per wave at L = 16 (4)}.
+ * sd_cyclic_long_kernel_bench: as sd_cyclic_kernel_bench for the team kernel; info = {launches per round, pairs on the
+ * device, word steps with pad words and ramp steps counted, workgroups}.  K = L = 0: the queries of SD_CYCLIC_QMAX + 1 ..
+ * SD_CYCLIC_QMAX_LONG bp in the library's classes; else every query of the call runs in class (K, L), short ones
+ * included, and SD_ERR_PARAM where (K, L) is no class or a query has more than 64 K L bases.  Pairs of other queries, and
+ * of targets beyond SD_CYCLIC_TMAX, are not computed here. */
 #define SD_CYCLIC_QMAX 2048
+#define SD_CYCLIC_QMAX_LONG 16384
 #define SD_CYCLIC_TMAX 65535
 #define SD_CYCLIC_LAUNCH_WG_MIN 1024
 int sd_cyclic_pairs_host(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
@@ -1461,6 +1477,13 @@ void sd_cyclic_info(int64_t info[6]);
 int sd_cyclic_kernel_bench(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
                            int32_t m, int32_t k, int32_t device, int32_t variant, int32_t warmup, int32_t reps, float* ms_pairs,
                            int64_t info[4], int32_t* dist, int32_t* end, uint8_t* strand);
+int sd_cyclic_pairs_team_host(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
+                              int32_t m, int32_t k, int32_t K, int32_t L, int32_t threads, int32_t* dist, int32_t* end, uint8_t* strand,
+                              char* errbuf, size_t errlen);
+void sd_cyclic_long_info(int64_t info[4]);
+int sd_cyclic_long_kernel_bench(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti,
+                                int32_t m, int32_t k, int32_t device, int32_t K, int32_t L, int32_t warmup, int32_t reps, float* ms_pairs,
+                                int64_t info[4], int32_t* dist, int32_t* end, uint8_t* strand);
 
 /* ---- the screen: which chunks of a read can hold a monomer at all (csrc/sd_screen.hip) ------------------------------
  * key[c] = (min over templates j of dist(j, c)) << 16 | the smallest j that attains the minimum, for every chunk c of the

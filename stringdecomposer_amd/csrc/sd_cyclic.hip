@@ -12,8 +12,19 @@
 //                       lane, so it comes through a scalar load, once per 16 columns.  The text is not doubled: the column
 //                       counter wraps at |t|.  Per column, after the last word: cyclic_take.  The strand is chosen in the
 //                       lane; a pair's result is three plain vector stores.  No atomics; nothing depends on the geometry.
-// The host builds everything the kernel reads (masks, packed targets, groups, units); the inputs are kilobytes.  Pairs beyond
-// the device's limits (query > 2 048 bp, target > 65 535 bp) are computed by the host form inside the same call.
+//   sd_cyclic_pairs_long<K, L>  queries of 2 049 .. 16 384 bp: a query lies over a team of L lanes, K words of Pv / Mv per
+//                       lane in 32-bit halves; the columns run down the team as a systolic pipeline (sd_cyclic.hpp, "the team
+//                       form"), lane l at step s on column s - l.  What a lane hands down -- the carry's two bits and the
+//                       column's symbol -- is one register, moved by one DPP wave_shr:1; a team's lane 0 ignores what it
+//                       gets from the team before it and decodes the target through the scalar path of the lane kernel.  A
+//                       wave holds 64 / L teams, different queries against the same target, so the steps are uniform; a
+//                       workgroup's four waves take the targets of a run in turn.  The group's masks sit in LDS as
+//                       [word of the lane][symbol][lane of the wave], 2 KB x K: the symbol moves a lane's address by 512 B,
+//                       twice round the 64 banks, so a read's bank is (2 x lane) mod 64 whatever symbols the lanes
+//                       hold, and each half wave of a ds_read_b64 covers the banks once.  The team's last lane applies the
+//                       end rule and writes the pair with three vector stores.
+// The host builds everything the kernels read (masks, packed targets, groups, units); the inputs are kilobytes.  Pairs beyond
+// the device's limits (query > 16 384 bp, target > 65 535 bp) are computed by the host form inside the same call.
 #include <atomic>
 #include <cstring>
 
@@ -24,6 +35,8 @@
 static_assert(SD_CYCLIC_QMAX == sd::CYCLIC_QMAX && SD_CYCLIC_TMAX == sd::CYCLIC_TMAX && SD_CYCLIC_LAUNCH_WG_MIN == sd::CYCLIC_LAUNCH_WG_MIN,
               "include/sd_hip.h states the limits");
 static_assert(sd::CYCLIC_LANES * 4 * sd::CYCLIC_WMAX * 8 <= 65536, "a group's masks fit the LDS of a workgroup");
+static_assert(SD_CYCLIC_QMAX_LONG == sd::CYCLIC_QMAX_LONG && sd::CYCLIC_QMAX_LONG == 64 * sd::CYCLIC_TEAM_KMAX * sd::CYCLIC_LANES,
+              "include/sd_hip.h states the team kernel's limit: four words in each of a wave's lanes");
 
 namespace sd {
 
@@ -49,43 +62,6 @@ struct CyArgs {
     int32_t* end;
     uint8_t* strand;
 };
-
-// cyclic_step in 32-bit halves, as sd_hw_dist_u (sd_filter.hip) has it: the three-input boolean steps are single
-// v_bitop3_b32 instructions (truth table over a = 0xF0, b = 0xCC, c = 0xAA), the carries between words are plain 0 / 1
-// values.  The same column, bit for bit.
-template <int W, class Eq>
-__device__ inline int cyclic_step_u(uint32_t* PvL, uint32_t* PvH, uint32_t* MvL, uint32_t* MvH, Eq&& eq) {
-    constexpr uint32_t TT_XH = (0xF0 ^ 0xCC) | 0xAA;               // (a ^ b) | c
-    constexpr uint32_t TT_ORN = 0xF0 | (~(0xCC | 0xAA) & 0xFF);    // a | ~(b | c)
-    uint32_t cP = 0, cM = 0;
-#pragma unroll
-    for (int b = 0; b < W; ++b) {
-        const uint64_t E = eq(b);
-        uint32_t EqL = (uint32_t)E;
-        const uint32_t EqH = (uint32_t)(E >> 32);
-        const uint32_t pvL = PvL[b], pvH = PvH[b], mvL = MvL[b], mvH = MvH[b];
-        const uint32_t XvL = EqL | mvL, XvH = EqH | mvH;
-        EqL |= cM;
-        const uint64_t sum = (((uint64_t)(EqH & pvH) << 32) | (EqL & pvL)) + (((uint64_t)pvH << 32) | pvL);
-        const uint32_t XhL = __builtin_amdgcn_bitop3_b32((uint32_t)sum, pvL, EqL, TT_XH);
-        const uint32_t XhH = __builtin_amdgcn_bitop3_b32((uint32_t)(sum >> 32), pvH, EqH, TT_XH);
-        uint32_t PhL = __builtin_amdgcn_bitop3_b32(mvL, XhL, pvL, TT_ORN);
-        uint32_t PhH = __builtin_amdgcn_bitop3_b32(mvH, XhH, pvH, TT_ORN);
-        uint32_t MhL = pvL & XhL, MhH = pvH & XhH;
-        const uint32_t oP = PhH >> 31, oM = MhH >> 31;
-        PhH = __builtin_amdgcn_alignbit(PhH, PhL, 31);
-        MhH = __builtin_amdgcn_alignbit(MhH, MhL, 31);
-        PhL = (PhL << 1) | cP;
-        MhL = (MhL << 1) | cM;
-        PvL[b] = __builtin_amdgcn_bitop3_b32(MhL, XvL, PhL, TT_ORN);
-        PvH[b] = __builtin_amdgcn_bitop3_b32(MhH, XvH, PhH, TT_ORN);
-        MvL[b] = PhL & XvL;
-        MvH[b] = PhH & XvH;
-        cP = oP;
-        cM = oM;
-    }
-    return (int)cP - (int)cM;
-}
 
 // The columns of one strand of a target of n bases (tw: its codes) for the lane's query of m bases, masks at e[(c * W + b) *
 // 64].  U: the column in 32-bit halves (cyclic_step_u) instead of 64-bit words (cyclic_step).
@@ -155,12 +131,91 @@ __global__ __launch_bounds__(CY_T) void sd_cyclic_pairs(CyArgs a) {
     }
 }
 
+// The team form.  One strand of a target of n bases for the team this lane belongs to: l = the lane's place in its team,
+// e = the masks at this lane ([b][symbol][64]), m = the team's query.  Every lane of the wave runs every step (the DPP move
+// needs them all); a lane whose column is outside the strand leaves its words and what it hands down as they are.  The
+// result is the last lane's.
+template <int K, int L>
+__device__ inline CyclicBest cy_team_strand(const uint64_t* e, int m, int l, const uint32_t* tw, int n, int st) {
+    const int pad = cyclic_pad(m, K * L);
+    uint32_t PvL[K], PvH[K], MvL[K], MvH[K];
+#pragma unroll
+    for (int b = 0; b < K; ++b) {
+        const uint64_t pv = cyclic_fresh_pv(pad, l * K + b);
+        PvL[b] = (uint32_t)pv; PvH[b] = (uint32_t)(pv >> 32); MvL[b] = MvH[b] = 0u;
+    }
+    CyclicBest best = cyclic_fresh(m);
+    const int cols = 2 * n - 1, steps = cyclic_team_steps(cols, L);
+    uint32_t hand = 0u;
+    int p = 0, cur = -1, c0 = 0;
+    uint32_t word = 0;
+#pragma unroll 1
+    for (int s = 0; s < steps; ++s) {
+        // what the lane above handed down at its previous step: one DPP move (wave lane 0 gets 0)
+        uint32_t in = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hand, 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
+        if (s < cols) {   // column s enters at lane 0 (s, p, the word: the same in every lane)
+            const int x = cyclic_index(p, n, st);
+            if ((x >> 4) != cur) { cur = x >> 4; word = tw[cur]; }
+            c0 = (word >> (2 * (x & 15))) & 3;
+            if (st) c0 = 3 - c0;
+            if (++p == n) p = 0;
+        }
+        if (l == 0) in = cyclic_team_pack(0u, 0u, c0);   // (a team's first lane: not the last lane of the team before)
+        const int j = cyclic_team_column(s, l);
+        if ((unsigned)j < (unsigned)cols) {
+            hand = cyclic_team_lane<K>(PvL, PvH, MvL, MvH, in, [&](int c, int b) { return e[(b * 4 + c) * CYCLIC_LANES]; });
+            cyclic_take(best, cyclic_team_delta(hand), j);   // (means something in the last lane only, where j = s - (L - 1))
+        }
+    }
+    return best;
+}
+
+template <int K, int L>
+__global__ __launch_bounds__(CY_T) void sd_cyclic_pairs_long(CyArgs a) {
+    extern __shared__ uint64_t speq[];   // [K][4][64]
+    const CyUnit u = a.units[a.unit0 + blockIdx.x];
+    const CyGroup g = a.groups[u.group];   // nq <= 64 / L teams
+    const uint64_t* src = a.peq + (int64_t)g.peq64 * 64;
+    for (int i = threadIdx.x; i < 4 * K * CYCLIC_LANES; i += CY_T) speq[i] = src[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int team = lane / L, l = lane % L;
+    const bool live = team < g.nq;          // (the lanes of a missing team run along on masks of 0 and write nothing)
+    const bool writes = live && l == L - 1;
+    const int qs = g.q0 + (live ? team : 0);
+    const int m = a.qlen[qs], rad = a.qrad[qs];
+    const int64_t row = (int64_t)a.qrow[qs] * a.k;
+    for (int t = u.t0 + wave; t < u.t0 + u.nt; t += CYCLIC_WAVES) {
+        const int n = a.tlen[t];
+        const int64_t at = row + a.tcol[t];
+        const bool close = abs(m - n) <= rad;
+        if (__ballot(close && live) == 0) {   // the length condition fails in every team
+            if (writes) { a.dist[at] = -1; a.end[at] = -1; a.strand[at] = 0; }
+            continue;
+        }
+        const uint32_t* tw = a.tw + a.toff[t];
+        CyclicBest plus = cyclic_fresh(m), minus = plus;
+#pragma unroll 1
+        for (int st = 0; st < 2; ++st) {
+            const CyclicBest best = cy_team_strand<K, L>(speq + lane, m, l, tw, n, st);
+            if (st) minus = best; else plus = best;
+        }
+        if (writes) {
+            const int st = cyclic_strand(plus.best, minus.best);
+            a.dist[at] = close ? (st ? minus.best : plus.best) : -1;
+            a.end[at] = close ? (st ? minus.end : plus.end) : -1;
+            a.strand[at] = close ? (uint8_t)st : (uint8_t)0;
+        }
+    }
+}
+
 }  // namespace sd
 
 namespace sdi {
 namespace {
 
-std::atomic<int64_t> g_cy_launches{0};   // launches of the pair kernel in this process (sd_cyclic_info)
+std::atomic<int64_t> g_cy_launches{0};        // launches of the lane kernel sd_cyclic_pairs in this process (sd_cyclic_info)
+std::atomic<int64_t> g_cy_long_launches{0};   // ... of the team kernel sd_cyclic_pairs_long (sd_cyclic_long_info)
 
 // the sequences of a call, checked: codes 0 .. 3 back to back
 struct CySeqs {
@@ -211,6 +266,21 @@ int cy_pair_args(const char* who, const CySeqs& S, const int32_t* qi, const int3
     return SD_OK;
 }
 
+// a forced class of the team kernel: one of the twelve, and no query of the call longer than it holds
+int cy_team_args(const char* who, const CySeqs& S, const int32_t* qi, int32_t m, int32_t K, int32_t L, char* errbuf, size_t errlen) {
+    if (!sd::cyclic_team_is_class(K, L)) {
+        set_err(errbuf, errlen, std::string(who) + ": K = " + std::to_string(K) + ", L = " + std::to_string(L) + " is no class of the team kernel (K 1 .. 4 words, L 16, 32 or 64 lanes)");
+        return SD_ERR_PARAM;
+    }
+    for (int32_t a = 0; a < m; ++a)
+        if (S.len[(size_t)qi[a]] > 64 * K * L) {
+            set_err(errbuf, errlen, std::string(who) + ": query " + std::to_string(a) + " has " + std::to_string(S.len[(size_t)qi[a]]) + " bases, the class of " +
+                                        std::to_string(K) + " words x " + std::to_string(L) + " lanes holds " + std::to_string(64 * K * L));
+            return SD_ERR_PARAM;
+        }
+    return SD_OK;
+}
+
 // ---- the host form ------------------------------------------------------------------------------------------------------
 // the pairs (a, b) with want(a, b); radius (may be null): the length condition per query, a pair that fails it gets dist -1
 template <class Want>
@@ -238,15 +308,34 @@ struct CyCtx : DevWork {
 };
 
 struct CyLaunch {
-    int W;
+    int W, L;   // L = 0: the lane kernel at W words; else the team kernel <K = W, L>
     int64_t unit0;
     unsigned n_units;
 };
+// A bench call times one of the two kernels and plans only that kernel's queries.  team, K = L = 0: the queries of the team
+// kernel in the classes the library chooses; K, L > 0: every query of at most 64 K L bp in that class.
 struct CyBench {
     int warmup, reps, variant;
     float* ms;
     int64_t* info;
+    bool team;
+    int K, L;
 };
+// the class of a query of m bp: {W, 0} the lane kernel, {K, L} the team kernel, {0, 0} the host
+struct CyClass {
+    int W, L;
+    int key() const { return L == 0 ? W : 1024 + W * L * 8 + W; }   // classes in launch order: lanes by words, teams by capacity
+    int per_group() const { return L == 0 ? sd::CYCLIC_LANES : sd::CYCLIC_LANES / L; }
+};
+CyClass cy_class(int m, const CyBench* bench) {
+    if (bench && bench->team && bench->K > 0) return m <= 64 * bench->K * bench->L ? CyClass{bench->K, bench->L} : CyClass{0, 0};
+    if (m <= sd::CYCLIC_QMAX) return bench && bench->team ? CyClass{0, 0} : CyClass{sd::cyclic_class(m), 0};
+    if (m <= sd::CYCLIC_QMAX_LONG && !(bench && !bench->team)) {
+        const sd::CyclicTeam c = sd::cyclic_team_class(m);
+        return CyClass{c.K, c.L};
+    }
+    return CyClass{0, 0};
+}
 
 // The classes of up to this many words run the column in 32-bit halves (sd_cyclic_pairs<W, true>), the others in 64-bit
 // words.  Both are instantiated up to four words, where they were measured against each other
@@ -265,8 +354,27 @@ void cy_launch_w(hipStream_t st, unsigned grid, const sd::CyArgs& a, int variant
     }
     hipLaunchKernelGGL((sd::sd_cyclic_pairs<W, false>), dim3(grid), dim3(sd::CY_T), lds, st, a);
 }
+template <int K>
+void cy_launch_long(hipStream_t st, unsigned grid, const sd::CyArgs& a, int L) {
+    const size_t lds = (size_t)K * 4 * sd::CYCLIC_LANES * sizeof(uint64_t);
+    switch (L) {
+        case 16: hipLaunchKernelGGL((sd::sd_cyclic_pairs_long<K, 16>), dim3(grid), dim3(sd::CY_T), lds, st, a); break;
+        case 32: hipLaunchKernelGGL((sd::sd_cyclic_pairs_long<K, 32>), dim3(grid), dim3(sd::CY_T), lds, st, a); break;
+        default: hipLaunchKernelGGL((sd::sd_cyclic_pairs_long<K, 64>), dim3(grid), dim3(sd::CY_T), lds, st, a); break;
+    }
+}
 void cy_launch(hipStream_t st, const CyLaunch& l, sd::CyArgs a, int variant) {
     a.unit0 = l.unit0;
+    if (l.L > 0) {
+        switch (l.W) {
+            case 1: cy_launch_long<1>(st, l.n_units, a, l.L); break;
+            case 2: cy_launch_long<2>(st, l.n_units, a, l.L); break;
+            case 3: cy_launch_long<3>(st, l.n_units, a, l.L); break;
+            default: cy_launch_long<4>(st, l.n_units, a, l.L); break;
+        }
+        SD_HIP(hipGetLastError());
+        return;
+    }
     switch (l.W) {
         case 1: cy_launch_w<1>(st, l.n_units, a, variant); break;
         case 2: cy_launch_w<2>(st, l.n_units, a, variant); break;
@@ -282,44 +390,56 @@ void cy_launch(hipStream_t st, const CyLaunch& l, sd::CyArgs a, int variant) {
     SD_HIP(hipGetLastError());
 }
 
-// The pairs of a checked call on `device`: the in-limit rows x in-limit columns through the kernel, the rest on host
-// threads.  Throws HipFail.
+// The pairs of a checked call on `device`: the in-limit rows x in-limit columns through the kernels -- a row's class
+// (cy_class) says which, the lane kernel's groups and launches first, then the team kernel's, on one stream into one set of
+// arrays -- the rest on host threads.  Throws HipFail.
 void cy_dev(CyCtx& c, hipStream_t st, const CySeqs& S, const int32_t* qi, const int32_t* ti, int32_t m, int32_t k, const int32_t* radius,
             int threads, int32_t* dist, int32_t* end, uint8_t* strand, const CyBench* bench) {
     const int64_t pairs = (int64_t)m * k;
     if (pairs == 0) return;
     std::vector<uint8_t> row_in((size_t)m), col_in((size_t)k);
     std::vector<int32_t> rows, cols;
+    auto cls = [&](int32_t a) { return cy_class(S.len[(size_t)qi[a]], bench); };
     for (int32_t a = 0; a < m; ++a)
-        if ((row_in[(size_t)a] = S.len[(size_t)qi[a]] <= sd::CYCLIC_QMAX)) rows.push_back(a);
+        if ((row_in[(size_t)a] = cls(a).W > 0)) rows.push_back(a);
     for (int32_t b = 0; b < k; ++b)
         if ((col_in[(size_t)b] = S.len[(size_t)ti[b]] <= sd::CYCLIC_TMAX)) cols.push_back(b);
     const bool on_device = !rows.empty() && !cols.empty();
     if (on_device) {
-        // the queries by class, groups of 64, their masks as [symbol][word][lane]
-        std::stable_sort(rows.begin(), rows.end(), [&](int32_t x, int32_t y) { return sd::cyclic_class(S.len[(size_t)qi[x]]) < sd::cyclic_class(S.len[(size_t)qi[y]]); });
+        // the queries by class; groups of 64 queries with masks as [symbol][word][lane] for the lane kernel, of 64 / L
+        // queries with masks as [word of the lane][symbol][lane of the wave] for the team kernel
+        std::stable_sort(rows.begin(), rows.end(), [&](int32_t x, int32_t y) { return cls(x).key() < cls(y).key(); });
         const size_t nq = rows.size(), nt = cols.size();
         std::vector<int32_t> q3(3 * nq), t2(2 * nt);
         std::vector<sd::CyGroup> groups;
-        std::vector<int> group_w;
+        std::vector<CyClass> group_w;
         int64_t peq64 = 0;
         for (size_t x = 0; x < nq;) {
-            const int W = sd::cyclic_class(S.len[(size_t)qi[rows[x]]]);
+            const CyClass W = cls(rows[x]);
             size_t e = x;
-            while (e < nq && e - x < (size_t)sd::CYCLIC_LANES && sd::cyclic_class(S.len[(size_t)qi[rows[e]]]) == W) ++e;
+            while (e < nq && e - x < (size_t)W.per_group() && cls(rows[e]).key() == W.key()) ++e;
             groups.push_back(sd::CyGroup{(int32_t)peq64, (int32_t)x, (int32_t)(e - x), 0});
             group_w.push_back(W);
-            peq64 += 4 * W;
+            peq64 += 4 * W.W;
             x = e;
         }
         std::vector<uint64_t> peq((size_t)peq64 * 64, 0);
         sd::parallel_for((int64_t)groups.size(), threads, 1, [&](int64_t gi) {
             const sd::CyGroup& g = groups[(size_t)gi];
-            const int W = group_w[(size_t)gi];
+            const CyClass W = group_w[(size_t)gi];
             uint64_t* base = peq.data() + (size_t)g.peq64 * 64;
+            std::vector<uint64_t> team;
             for (int l = 0; l < g.nq; ++l) {
                 const int32_t s = qi[rows[(size_t)(g.q0 + l)]];
-                sd::cyclic_masks(S.seq(s), S.len[(size_t)s], W, base + l, sd::CYCLIC_LANES);
+                if (W.L == 0) {
+                    sd::cyclic_masks(S.seq(s), S.len[(size_t)s], W.W, base + l, sd::CYCLIC_LANES);
+                    continue;
+                }
+                const int K = W.W, nw = K * W.L;   // team l of the wave: word w = lane K + b of symbol c at [b][c][l L + lane]
+                team.assign(4 * (size_t)nw, 0);
+                sd::cyclic_masks(S.seq(s), S.len[(size_t)s], nw, team.data());
+                for (int c = 0; c < 4; ++c)
+                    for (int w = 0; w < nw; ++w) base[((size_t)(w % K) * 4 + c) * sd::CYCLIC_LANES + (size_t)l * W.L + w / K] = team[(size_t)c * nw + w];
             }
         });
         for (size_t x = 0; x < nq; ++x) {
@@ -342,28 +462,36 @@ void cy_dev(CyCtx& c, hipStream_t st, const CySeqs& S, const int32_t* qi, const 
             uint32_t* w = tw.data() + toff[(size_t)y];
             for (int i = 0; i < S.len[(size_t)s]; ++i) w[i >> 4] |= (uint32_t)t[i] << (2 * (i & 15));
         });
+        // (the team kernel: a run has a target for each of the workgroup's waves before its columns close it -- a wave there
+        // holds 1 to 4 queries, not 64, and two targets of 2 054 bases would leave half the workgroup without work)
         struct Run { int32_t t0, nt; int64_t cols; };
-        std::vector<Run> runs;
-        for (size_t y = 0; y < nt;) {
-            Run r{(int32_t)y, 0, 0};
-            while (y < nt && r.nt < sd::CYCLIC_TB && (r.nt == 0 || r.cols < sd::CYCLIC_TB_COLS)) {
-                r.cols += 2 * (2 * (int64_t)t2[y] - 1);
-                ++r.nt;
-                ++y;
+        auto make_runs = [&](int nt_min) {
+            std::vector<Run> runs;
+            for (size_t y = 0; y < nt;) {
+                Run r{(int32_t)y, 0, 0};
+                while (y < nt && r.nt < sd::CYCLIC_TB && (r.nt < nt_min || r.cols < sd::CYCLIC_TB_COLS)) {
+                    r.cols += 2 * (2 * (int64_t)t2[y] - 1);
+                    ++r.nt;
+                    ++y;
+                }
+                runs.push_back(r);
             }
-            runs.push_back(r);
-        }
-        // units by class (the groups are in class order), launches closed at CYCLIC_LAUNCH_WORK word steps
+            return runs;
+        };
+        const std::vector<Run> lane_runs = make_runs(1), team_runs = make_runs(sd::CYCLIC_WAVES);
+        // units by class (the groups are in class order), launches closed at CYCLIC_LAUNCH_WORK word steps; a team's steps
+        // count its pad words and the L - 1 ramp steps of each strand
         std::vector<sd::CyUnit> units;
         std::vector<CyLaunch> launches;
-        int64_t work = 0, steps = 0;
+        int64_t work = 0, steps = 0, n_lane = 0, n_long = 0;
         for (size_t gi = 0; gi < groups.size(); ++gi) {
-            const int W = group_w[gi];
-            for (const Run& r : runs) {
-                const int64_t w = r.cols * W * groups[gi].nq;
-                if (launches.empty() || launches.back().W != W ||
+            const CyClass W = group_w[gi];
+            for (const Run& r : W.L ? team_runs : lane_runs) {
+                const int64_t w = W.L ? (r.cols + 2 * (int64_t)(W.L - 1) * r.nt) * W.W * W.L * groups[gi].nq : r.cols * W.W * groups[gi].nq;
+                if (launches.empty() || launches.back().W != W.W || launches.back().L != W.L ||
                     (work + w > sd::CYCLIC_LAUNCH_WORK && launches.back().n_units >= (unsigned)sd::CYCLIC_LAUNCH_WG_MIN)) {
-                    launches.push_back(CyLaunch{W, (int64_t)units.size(), 0});
+                    launches.push_back(CyLaunch{W.W, W.L, (int64_t)units.size(), 0});
+                    ++(W.L ? n_long : n_lane);
                     work = 0;
                 }
                 units.push_back(sd::CyUnit{(int32_t)gi, r.t0, r.nt, 0});
@@ -397,7 +525,8 @@ void cy_dev(CyCtx& c, hipStream_t st, const CySeqs& S, const int32_t* qi, const 
         a.dist = c.dist.p; a.end = c.end.p; a.strand = c.strand.p;
         auto run = [&]() {
             for (const CyLaunch& l : launches) cy_launch(st, l, a, bench ? bench->variant : CY_DEFAULT);
-            g_cy_launches.fetch_add((int64_t)launches.size());
+            g_cy_launches.fetch_add(n_lane);
+            g_cy_long_launches.fetch_add(n_long);
         };
         if (bench) {
             StageClock clock;
@@ -556,7 +685,7 @@ int sd_cyclic_kernel_bench(const char* text, const int64_t* off, const int64_t* 
     if (warmup < 0 || reps < 1 || !ms_pairs || !info || m <= 0 || k <= 0 || variant < CY_DEFAULT || variant > CY_HALVES) return SD_ERR_PARAM;
     for (int i = 0; i < 4; ++i) info[i] = 0;
     for (int i = 0; i < reps; ++i) ms_pairs[i] = 0;
-    const CyBench b{warmup, reps, variant, ms_pairs, info};
+    const CyBench b{warmup, reps, variant, ms_pairs, info, false, 0, 0};
     std::vector<int32_t> d, e;
     std::vector<uint8_t> s;
     if (!dist || !end || !strand) {   // (the arrays of the timed variant, for a caller that wants to compare them)
@@ -566,6 +695,61 @@ int sd_cyclic_kernel_bench(const char* text, const int64_t* off, const int64_t* 
         dist = d.data(); end = e.data(); strand = s.data();
     }
     return cy_pairs_dev("sd_cyclic_kernel_bench", text, off, lens, n, qi, ti, m, k, device, 16, dist, end, strand, nullptr, 0, &b);
+} catch (const std::bad_alloc&) {
+    return SD_ERR_INTERNAL;
+}
+
+int sd_cyclic_pairs_team_host(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti, int32_t m,
+                              int32_t k, int32_t K, int32_t L, int32_t threads, int32_t* dist, int32_t* end, uint8_t* strand, char* errbuf,
+                              size_t errlen) try {
+    static const char* who = "sd_cyclic_pairs_team_host";
+    CySeqs S;
+    int rc = cy_seqs(who, text, off, lens, n, INT32_MAX, S, errbuf, errlen);
+    if (rc) return rc;
+    if ((rc = cy_pair_args(who, S, qi, ti, m, k, !dist || !end || !strand, errbuf, errlen))) return rc;
+    if ((rc = cy_team_args(who, S, qi, m, K, L, errbuf, errlen))) return rc;
+    sd::parallel_for((int64_t)m * k, std::max(1, threads), 1, [&](int64_t x) {
+        const int32_t a = (int32_t)(x / k), b = (int32_t)(x - (int64_t)a * k);
+        const int32_t q = qi[a], t = ti[b];
+        thread_local sd::CyclicTeamScratch sc;
+        sd::cyclic_pair_team(S.seq(q), S.len[(size_t)q], S.seq(t), S.len[(size_t)t], K, L, sc, dist + x, end + x, strand + x);
+    });
+    return SD_OK;
+} catch (const std::bad_alloc&) {
+    return SD_ERR_INTERNAL;
+}
+
+void sd_cyclic_long_info(int64_t info[4]) {
+    info[0] = sd::CYCLIC_QMAX_LONG;
+    info[1] = g_cy_long_launches.load();
+    info[2] = sd::CYCLIC_TEAM_N_CLASSES;
+    info[3] = sd::CYCLIC_LANES / sd::CYCLIC_TEAM_LS[0];
+}
+
+int sd_cyclic_long_kernel_bench(const char* text, const int64_t* off, const int64_t* lens, int32_t n, const int32_t* qi, const int32_t* ti, int32_t m,
+                                int32_t k, int32_t device, int32_t K, int32_t L, int32_t warmup, int32_t reps, float* ms_pairs, int64_t info[4],
+                                int32_t* dist, int32_t* end, uint8_t* strand) try {
+    static const char* who = "sd_cyclic_long_kernel_bench";
+    if (warmup < 0 || reps < 1 || !ms_pairs || !info || m <= 0 || k <= 0) return SD_ERR_PARAM;
+    for (int i = 0; i < 4; ++i) info[i] = 0;
+    for (int i = 0; i < reps; ++i) ms_pairs[i] = 0;
+    if (K != 0 || L != 0) {   // a forced class: checked before any device work
+        CySeqs S;
+        int rc = cy_seqs(who, text, off, lens, n, INT32_MAX, S, nullptr, 0);
+        if (rc) return rc;
+        if ((rc = cy_pair_args(who, S, qi, ti, m, k, false, nullptr, 0))) return rc;
+        if ((rc = cy_team_args(who, S, qi, m, K, L, nullptr, 0))) return rc;
+    }
+    const CyBench b{warmup, reps, CY_DEFAULT, ms_pairs, info, true, K, L};
+    std::vector<int32_t> d, e;
+    std::vector<uint8_t> s;
+    if (!dist || !end || !strand) {
+        d.resize((size_t)m * (size_t)k);
+        e.resize(d.size());
+        s.resize(d.size());
+        dist = d.data(); end = e.data(); strand = s.data();
+    }
+    return cy_pairs_dev(who, text, off, lens, n, qi, ti, m, k, device, 16, dist, end, strand, nullptr, 0, &b);
 } catch (const std::bad_alloc&) {
     return SD_ERR_INTERNAL;
 }

@@ -1,7 +1,7 @@
 // sd_cyclic.hpp -- "cyclic pairs" and the merge rule on top of them (--autocorr-merge, bin/sd-merge): which seed monomers
 // are the same monomer up to rotation and strand.  One text for host and device, as plain C++ that compiles for both (in
-// the manner of sd_motif_edit.hpp): the pair, the limits, the bit-vector column; and, host only, the merge walk and the
-// canonical record.  sd_cyclic.hip holds the kernels, the host form and the C-ABI (sd_cyclic_*, include/sd_hip.h).
+// the manner of sd_motif_edit.hpp): the pair, the limits, the bit-vector column, the team form of the column for queries
+// beyond one lane's registers; and, host only, that team schedule run lane by lane, the merge walk and the canonical record.  sd_cyclic.hip holds the kernels, the host form and the C-ABI (sd_cyclic_*, include/sd_hip.h).
 //
 // The pair.  Sequences are upper-case A C G T only, of length >= 1.  For a query q, a target t and a strand s: t^+ is t,
 // t^- its reverse complement; the text is U = t^s t^s without its last base, |U| = 2|t| - 1 -- every rotation of t^s is a
@@ -46,7 +46,7 @@
 
 namespace sd {
 
-constexpr int CYCLIC_QMAX = 2048;                       // device: the longest query (32 words)
+constexpr int CYCLIC_QMAX = 2048;                       // device: the longest query of the lane kernel (32 words)
 constexpr int CYCLIC_TMAX = 65535;                      // device: the longest target
 constexpr int CYCLIC_WMAX = CYCLIC_QMAX / 64;
 constexpr int64_t CYCLIC_PAIRS_MAX = (int64_t)1 << 24;  // pairs of one sd_cyclic_pairs_* call
@@ -148,6 +148,112 @@ SD_HD inline void cyclic_take(CyclicBest& b, int hout, int j) {
 // the strand rule: + unless - is strictly smaller
 SD_HD inline int cyclic_strand(int dist_plus, int dist_minus) { return dist_minus < dist_plus ? 1 : 0; }
 
+// ---- the team form: a query across the lanes of a wave (queries of CYCLIC_QMAX + 1 .. CYCLIC_QMAX_LONG bp) ----------------
+// A query lies over a team of L consecutive lanes, lane l holding words l K .. l K + K - 1 of its K L words, padded as
+// above with nw = K L: the bottom row is bit 63 of the last word of the team's last lane, and a lane that is all pad passes a
+// carry of 0 (its rows are copies of the free row).  The columns run as a systolic pipeline: at step s lane l computes
+// column cyclic_team_column(s, l) = s - l if that is one of the strand's 2 |t| - 1 columns, else it leaves its words as they
+// are; a strand takes cyclic_team_steps = 2 |t| - 1 + L - 1 steps.  What lane l hands to lane l + 1 for the next step is one
+// register (cyclic_team_pack): the horizontal delta out of its last word as the two bits the halves form has (+1: bit 0,
+// -1: bit 1) and the column's symbol above them, so only lane 0 reads the target.  Lane 0 takes a carry of 0 (the search
+// variant).  The last lane applies cyclic_take with j = s - (L - 1): the same (score, column) sequence as cyclic_pair sees.
+constexpr int CYCLIC_QMAX_LONG = 16384;                 // device: the longest query of the team kernel (256 words)
+constexpr int CYCLIC_TEAM_KMAX = 4;                     // words per lane: 1 .. 4
+constexpr int CYCLIC_TEAM_LS[] = {16, 32, 64};          // lanes per team
+constexpr int CYCLIC_TEAM_N_L = 3;
+constexpr int CYCLIC_TEAM_N_CLASSES = CYCLIC_TEAM_KMAX * CYCLIC_TEAM_N_L;
+struct CyclicTeam {
+    int K, L;   // K = 0: no class (beyond the limit)
+};
+SD_HD inline bool cyclic_team_is_class(int K, int L) { return K >= 1 && K <= CYCLIC_TEAM_KMAX && (L == 16 || L == 32 || L == 64); }
+// A length's class: the (K, L) of smallest K L that holds its words.  Of equal capacities the larger K (the shorter team)
+// wins: fewer ramp steps per strand and more queries to a wave (profiles/cyclic_timing.md has 4 x 16 beside 2 x 32).
+SD_HD inline CyclicTeam cyclic_team_class(int m) {
+    const int w = cyclic_words(m);
+    CyclicTeam best{0, 0};
+    for (int li = 0; li < CYCLIC_TEAM_N_L; ++li)
+        for (int K = 1; K <= CYCLIC_TEAM_KMAX; ++K) {
+            const int L = li == 0 ? 16 : li == 1 ? 32 : 64;
+            if (K * L >= w && (best.K == 0 || K * L < best.K * best.L || (K * L == best.K * best.L && K > best.K))) best = CyclicTeam{K, L};
+        }
+    return best;
+}
+SD_HD inline int cyclic_team_column(int s, int l) { return s - l; }
+SD_HD inline int cyclic_team_steps(int cols, int L) { return cols + L - 1; }
+SD_HD inline uint32_t cyclic_team_pack(uint32_t cP, uint32_t cM, int sym) { return cP | (cM << 1) | ((uint32_t)sym << 2); }
+
+// cyclic_step in 32-bit halves, as sd_hw_dist_u (sd_filter.hip) has it: on the device the three-input boolean steps are
+// single v_bitop3_b32 instructions (truth table over a = 0xF0, b = 0xCC, c = 0xAA), on the host the same functions written
+// out; the carries between words are plain 0 / 1 values.  The same column, bit for bit.  cP / cM: the carry into the first
+// word (+1 / -1) and, on return, out of the last one.
+SD_HD inline uint32_t cyclic_u_xh(uint32_t a, uint32_t b, uint32_t c) {    // (a ^ b) | c
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, (0xF0 ^ 0xCC) | 0xAA);
+#else
+    return (a ^ b) | c;
+#endif
+}
+SD_HD inline uint32_t cyclic_u_orn(uint32_t a, uint32_t b, uint32_t c) {   // a | ~(b | c)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0xF0 | (~(0xCC | 0xAA) & 0xFF));
+#else
+    return a | ~(b | c);
+#endif
+}
+SD_HD inline uint32_t cyclic_u_shl1(uint32_t hi, uint32_t lo) {            // the high half of (hi : lo) << 1
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, 31);
+#else
+    return (hi << 1) | (lo >> 31);
+#endif
+}
+template <int W, class Eq>
+SD_HD inline void cyclic_step_uc(uint32_t* PvL, uint32_t* PvH, uint32_t* MvL, uint32_t* MvH, Eq&& eq, uint32_t& cP, uint32_t& cM) {
+#pragma unroll
+    for (int b = 0; b < W; ++b) {
+        const uint64_t E = eq(b);
+        uint32_t EqL = (uint32_t)E;
+        const uint32_t EqH = (uint32_t)(E >> 32);
+        const uint32_t pvL = PvL[b], pvH = PvH[b], mvL = MvL[b], mvH = MvH[b];
+        const uint32_t XvL = EqL | mvL, XvH = EqH | mvH;
+        EqL |= cM;
+        const uint64_t sum = (((uint64_t)(EqH & pvH) << 32) | (EqL & pvL)) + (((uint64_t)pvH << 32) | pvL);
+        const uint32_t XhL = cyclic_u_xh((uint32_t)sum, pvL, EqL);
+        const uint32_t XhH = cyclic_u_xh((uint32_t)(sum >> 32), pvH, EqH);
+        uint32_t PhL = cyclic_u_orn(mvL, XhL, pvL);
+        uint32_t PhH = cyclic_u_orn(mvH, XhH, pvH);
+        uint32_t MhL = pvL & XhL, MhH = pvH & XhH;
+        const uint32_t oP = PhH >> 31, oM = MhH >> 31;
+        PhH = cyclic_u_shl1(PhH, PhL);
+        MhH = cyclic_u_shl1(MhH, MhL);
+        PhL = (PhL << 1) | cP;
+        MhL = (MhL << 1) | cM;
+        PvL[b] = cyclic_u_orn(MhL, XvL, PhL);
+        PvH[b] = cyclic_u_orn(MhH, XvH, PhH);
+        MvL[b] = PhL & XvL;
+        MvH[b] = PhH & XvH;
+        cP = oP;
+        cM = oM;
+    }
+}
+// ... a whole column: the carry into the first word is 0; returns the delta of the bottom row
+template <int W, class Eq>
+SD_HD inline int cyclic_step_u(uint32_t* PvL, uint32_t* PvH, uint32_t* MvL, uint32_t* MvH, Eq&& eq) {
+    uint32_t cP = 0, cM = 0;
+    cyclic_step_uc<W>(PvL, PvH, MvL, MvH, eq, cP, cM);
+    return (int)cP - (int)cM;
+}
+// One lane of a team at one step: `in` = what the lane above handed down (cyclic_team_pack; lane 0: carry 0 and the column's
+// symbol), eq(c, b) = word b of this lane's match mask for symbol c.  Returns what goes to the lane below.
+template <int K, class Eq>
+SD_HD inline uint32_t cyclic_team_lane(uint32_t* PvL, uint32_t* PvH, uint32_t* MvL, uint32_t* MvH, uint32_t in, Eq&& eq) {
+    uint32_t cP = in & 1u, cM = (in >> 1) & 1u;
+    const int c = (int)(in >> 2);
+    cyclic_step_uc<K>(PvL, PvH, MvL, MvH, [&](int b) { return eq(c, b); }, cP, cM);
+    return cyclic_team_pack(cP, cM, c);
+}
+SD_HD inline int cyclic_team_delta(uint32_t out) { return (int)(out & 1u) - (int)((out >> 1) & 1u); }
+
 // ---- host only ----------------------------------------------------------------------------------------------------------
 
 // The match masks of a query given as codes, on nw >= cyclic_words(m) words: word b of symbol c at peq[(c * nw + b) * pitch].
@@ -193,6 +299,62 @@ inline void cyclic_pair(const uint8_t* q, int m, const uint8_t* t, int n, Cyclic
             case 3: r[st] = cyclic_strand_run<3>(s.peq.data(), m, 3, t, n, st, Pv, Mv); break;
             case 4: r[st] = cyclic_strand_run<4>(s.peq.data(), m, 4, t, n, st, Pv, Mv); break;
             default: r[st] = cyclic_strand_run<0>(s.peq.data(), m, nw, t, n, st, s.pv.data(), s.mv.data()); break;
+        }
+    }
+    const int st = cyclic_strand(r[0].best, r[1].best);
+    *dist = r[st].best;
+    *end = r[st].end;
+    *strand = (uint8_t)st;
+}
+
+// The team schedule on the host: L "lanes" in lock step, lane l's words l K .. l K + K - 1 in 32-bit halves, what a lane
+// hands down read by the lane below one step later -- the kernel sd_cyclic_pairs_long<K, L> without a device, for tests and
+// sanitizer builds.  m <= 64 K L.
+template <int K>
+inline CyclicBest cyclic_team_strand(const uint64_t* peq, int m, const uint8_t* t, int n, int st, int L, uint32_t* v, uint32_t* hand) {
+    const int nw = K * L, pad = cyclic_pad(m, nw), cols = 2 * n - 1;
+    uint32_t *PvL = v, *PvH = v + nw, *MvL = v + 2 * nw, *MvH = v + 3 * nw;
+    for (int w = 0; w < nw; ++w) {
+        const uint64_t pv = cyclic_fresh_pv(pad, w);
+        PvL[w] = (uint32_t)pv; PvH[w] = (uint32_t)(pv >> 32); MvL[w] = MvH[w] = 0u;
+    }
+    for (int l = 0; l < L; ++l) hand[l] = 0u;
+    CyclicBest best = cyclic_fresh(m);
+    for (int s = 0; s < cyclic_team_steps(cols, L); ++s)
+        for (int l = L - 1; l >= 0; --l) {   // (downwards: hand[l - 1] is still the step before)
+            const int j = cyclic_team_column(s, l);
+            if (j < 0 || j >= cols) continue;
+            uint32_t in;
+            if (l == 0) {
+                const int x = t[cyclic_index(j % n, n, st)];
+                in = cyclic_team_pack(0u, 0u, st ? 3 - x : x);
+            } else {
+                in = hand[l - 1];
+            }
+            const int w0 = l * K;
+            hand[l] = cyclic_team_lane<K>(PvL + w0, PvH + w0, MvL + w0, MvH + w0, in, [&](int c, int b) { return peq[(size_t)c * nw + w0 + b]; });
+            if (l == L - 1) cyclic_take(best, cyclic_team_delta(hand[l]), j);
+        }
+    return best;
+}
+struct CyclicTeamScratch {
+    std::vector<uint64_t> peq;
+    std::vector<uint32_t> v, hand;
+};
+inline void cyclic_pair_team(const uint8_t* q, int m, const uint8_t* t, int n, int K, int L, CyclicTeamScratch& s, int32_t* dist, int32_t* end,
+                             uint8_t* strand) {
+    const int nw = K * L;
+    s.peq.resize(4 * (size_t)nw);
+    s.v.resize(4 * (size_t)nw);
+    s.hand.resize((size_t)L);
+    cyclic_masks(q, m, nw, s.peq.data());
+    CyclicBest r[2];
+    for (int st = 0; st < 2; ++st) {
+        switch (K) {
+            case 1: r[st] = cyclic_team_strand<1>(s.peq.data(), m, t, n, st, L, s.v.data(), s.hand.data()); break;
+            case 2: r[st] = cyclic_team_strand<2>(s.peq.data(), m, t, n, st, L, s.v.data(), s.hand.data()); break;
+            case 3: r[st] = cyclic_team_strand<3>(s.peq.data(), m, t, n, st, L, s.v.data(), s.hand.data()); break;
+            default: r[st] = cyclic_team_strand<4>(s.peq.data(), m, t, n, st, L, s.v.data(), s.hand.data()); break;
         }
     }
     const int st = cyclic_strand(r[0].best, r[1].best);

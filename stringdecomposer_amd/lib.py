@@ -68,7 +68,7 @@ EXPORTS = [
     "sd_motif_edit_host", "sd_motif_edit_dev", "sd_motif_edit_reads_size_dev", "sd_motif_edit_reads_write_dev", "sd_motif_edit_info",
     "sd_motif_edit_kernel_bench",
     "sd_cyclic_pairs_host", "sd_cyclic_pairs_dev", "sd_cyclic_merge_host", "sd_cyclic_merge_dev", "sd_cyclic_canon", "sd_cyclic_info",
-    "sd_cyclic_kernel_bench",
+    "sd_cyclic_kernel_bench", "sd_cyclic_pairs_team_host", "sd_cyclic_long_info", "sd_cyclic_long_kernel_bench",
     "sd_split_host", "sd_split_dev", "sd_split_final_host", "sd_split_info", "sd_split_kernel_bench",
     "sd_hor_rows", "sd_hor_final_host", "sd_hor_name", "sd_hor_info",
     "sd_dotplot_layout", "sd_dotplot_host", "sd_dotplot_dev", "sd_dotplot_reads_dev", "sd_dotplot_info", "sd_dotplot_hash", "sd_dotplot_kernel_bench",
@@ -331,6 +331,11 @@ def load():
     L.sd_cyclic_info.restype = None
     L.sd_cyclic_kernel_bench.argtypes = cyc + [V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_int64),
                                                V, V, V]
+    L.sd_cyclic_pairs_team_host.argtypes = cyc + [V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, V, V, V, C.c_char_p, C.c_size_t]
+    L.sd_cyclic_long_info.argtypes = [P(C.c_int64)]
+    L.sd_cyclic_long_info.restype = None
+    L.sd_cyclic_long_kernel_bench.argtypes = cyc + [V, V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_float),
+                                                    P(C.c_int64), V, V, V]
     L.sd_dotplot_layout.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, P(C.c_int64), P(C.c_int64)]
     L.sd_dotplot_host.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -1764,7 +1769,9 @@ def motif_edits_kernel_bench(reads, motifs, K, device=0, warmup=2, reps=5):
 
 
 # ---- cyclic pairs and the merge of seed monomers (csrc/sd_cyclic.hpp holds the rule) ---------------------------------------
-CYCLIC_QMAX = 2048        # SD_CYCLIC_QMAX: the longest query the device takes
+CYCLIC_QMAX = 2048        # SD_CYCLIC_QMAX: the longest query of the lane kernel (one pair to a lane)
+CYCLIC_QMAX_LONG = 16384  # SD_CYCLIC_QMAX_LONG: the longest query the device takes (the team kernel: a query across 16 .. 64 lanes)
+CYCLIC_TEAM_CLASSES = tuple((K, L) for L in (16, 32, 64) for K in (1, 2, 3, 4))   # words per lane x lanes: 64 K L rows
 CYCLIC_TMAX = 65535       # SD_CYCLIC_TMAX: the longest target the device takes
 CYCLIC_PAIRS_MAX = 1 << 24
 CYCLIC_N_MAX = 1 << 20
@@ -1772,8 +1779,9 @@ CYCLIC_LAUNCH_WG_MIN = 1024   # SD_CYCLIC_LAUNCH_WG_MIN: a launch is not closed 
 
 
 def cyclic_info():
-    """sd_cyclic_info -> {"lmax_query", "lmax_target": the device's limits in bases, "launch_work": the step bound of a
-    launch of the pair kernel, "launches": of that kernel in this process so far, "pairs_max": pairs of a cyclic_pairs
+    """sd_cyclic_info -> {"lmax_query": the lane kernel's limit in bases (cyclic_long_info has the team kernel's),
+    "lmax_target": the device's limit, "launch_work": the step bound of a launch of either pair kernel, "launches": of the
+    lane kernel in this process so far, "pairs_max": pairs of a cyclic_pairs
     call, "block": the default block of cyclic_merge}.  The bound of a launch is compound: at most launch_work word steps
     (columns x words x pairs) or CYCLIC_LAUNCH_WG_MIN workgroups, whichever is more, so launch_work is the most only while
     workgroups are small (include/sd_hip.h has the largest launch there can be)."""
@@ -1814,8 +1822,9 @@ def cyclic_pairs(seqs, queries=None, targets=None, device=None, threads=1):
     substring of t written twice, on either strand, and where that fit ends (include/sd_hip.h: sd_cyclic_pairs_*) ->
     formats.CyclicPairs(dist, end, strand, phase), int32 / int32 / uint8 / int32 arrays [queries, targets]; phase =
     (end + 1) mod |t|, where in t (on that strand) a query that is a whole period begins.
-    device=None: host threads (sd_cyclic_pairs_host); else the kernel of csrc/sd_cyclic.hip on that device, with the pairs
-    beyond its limits (query > 2 048 bp, target > 65 535 bp) on `threads` host threads.  Both give the same arrays."""
+    device=None: host threads (sd_cyclic_pairs_host); else the kernels of csrc/sd_cyclic.hip on that device -- queries of up
+    to 2 048 bp one pair to a lane, of up to 16 384 bp one query across a team of lanes -- with the pairs beyond its limits
+    (query > 16 384 bp, target > 65 535 bp) on `threads` host threads.  Both give the same arrays."""
     import numpy as np
     from . import formats
     text, ro, rl, qi, ti = _cyclic_call("cyclic_pairs", seqs, queries, targets)
@@ -1881,9 +1890,9 @@ def cyclic_canon(seq):
 
 
 def cyclic_kernel_bench(seqs, queries=None, targets=None, device=0, warmup=2, reps=5, variant=0, arrays=False):
-    """sd_cyclic_kernel_bench -> {"pairs_ms": [...], "launches", "pairs", "steps", "workgroups"}: the pair kernel's launches
+    """sd_cyclic_kernel_bench -> {"pairs_ms": [...], "launches", "pairs", "steps", "workgroups"}: the lane kernel's launches
     of cyclic_pairs(seqs, queries, targets, device) between two events; pairs and steps (columns x words x pairs) on the
-    device.  variant: 0 = the kernels the library chooses, 1 = 64-bit words throughout, 2 = 32-bit halves up to four words.
+    device.  Queries of more than CYCLIC_QMAX bp are not computed here: cyclic_long_kernel_bench times the team kernel.  variant: 0 = the kernels the library chooses, 1 = 64-bit words throughout, 2 = 32-bit halves up to four words.
     arrays=True: also "dist", "end", "strand" of the timed variant, as cyclic_pairs gives them."""
     import numpy as np
     text, ro, rl, qi, ti = _cyclic_call("cyclic_kernel_bench", seqs, queries, targets)
@@ -1894,6 +1903,75 @@ def cyclic_kernel_bench(seqs, queries=None, targets=None, device=0, warmup=2, re
     _check(load().sd_cyclic_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), qi.ctypes.data, ti.ctypes.data, m, k, int(device),
                                          variant, int(warmup), int(reps), ms, info, dist.ctypes.data, end.ctypes.data, strand.ctypes.data),
            "sd_cyclic_kernel_bench")
+    out = {"pairs_ms": [float(x) for x in ms]}
+    out.update(zip(("launches", "pairs", "steps", "workgroups"), (int(x) for x in info)))
+    if arrays:
+        out.update(dist=dist, end=end, strand=strand)
+    return out
+
+
+def cyclic_long_info():
+    """sd_cyclic_long_info -> {"lmax_query": the team kernel's limit in bases (CYCLIC_QMAX_LONG), "launches": of the team
+    kernel in this process so far, "classes": the instantiated (K, L), "teams_per_wave": queries of a wave at L = 16}"""
+    return _info(load().sd_cyclic_long_info, ("lmax_query", "launches", "classes", "teams_per_wave"))
+
+
+def cyclic_team_class(length):
+    """(K, L) of the team kernel for a query of `length` bases: the class of smallest K * L that holds it, the larger K of
+    equal ones (csrc/sd_cyclic.hpp: cyclic_team_class); None beyond CYCLIC_QMAX_LONG"""
+    words = (int(length) + 63) // 64
+    fit = [(K * L, -K, K, L) for K, L in CYCLIC_TEAM_CLASSES if K * L >= words]
+    return min(fit)[2:] if fit else None
+
+
+def _cyclic_team_args(who, K, L, rl, qi):
+    """a forced class, refused as the library refuses it"""
+    if (K, L) not in CYCLIC_TEAM_CLASSES:
+        raise SdError(SD_ERR_PARAM, "%s: K = %r, L = %r is no class of the team kernel (K 1 .. 4 words, L 16, 32 or 64 lanes)" % (who, K, L))
+    for a, q in enumerate(qi):
+        if rl[q] > 64 * K * L:
+            raise SdError(SD_ERR_PARAM, "%s: query %d has %d bases, the class of %d words x %d lanes holds %d" % (who, a, rl[q], K, L, 64 * K * L))
+
+
+def cyclic_pairs_team_host(seqs, queries=None, targets=None, K=4, L=64, threads=1):
+    """sd_cyclic_pairs_team_host: cyclic_pairs by the team kernel's schedule of class (K, L) run on the host -- L lanes in
+    lock step, K words each, the carry and the column's symbol handed down one lane per step -> formats.CyclicPairs, the
+    arrays of cyclic_pairs.  Needs no device.  Refuses a (K, L) outside CYCLIC_TEAM_CLASSES and a query of more than
+    64 * K * L bases (the library's line, SD_ERR_PARAM)."""
+    import numpy as np
+    from . import formats
+    who = "cyclic_pairs_team_host"
+    text, ro, rl, qi, ti = _cyclic_call(who, seqs, queries, targets)
+    m, k = len(qi), len(ti)
+    dist, end, strand = np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.uint8)
+    err = _err()
+    rc = load().sd_cyclic_pairs_team_host(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), qi.ctypes.data, ti.ctypes.data, m, k,
+                                          _int_arg(who, "K", K, 0, 1 << 30), _int_arg(who, "L", L, 0, 1 << 30), int(threads),
+                                          dist.ctypes.data, end.ctypes.data, strand.ctypes.data, err, len(err))
+    _text_check(rc, err, who)
+    tl = rl[ti].astype(np.int32) if k else np.zeros(0, dtype=np.int32)
+    phase = (end + 1) % tl[None, :] if m and k else np.zeros((m, k), dtype=np.int32)
+    return formats.CyclicPairs(dist, end, strand, phase.astype(np.int32))
+
+
+def cyclic_long_kernel_bench(seqs, queries=None, targets=None, device=0, K=0, L=0, warmup=2, reps=5, arrays=False):
+    """sd_cyclic_long_kernel_bench -> {"pairs_ms": [...], "launches", "pairs", "steps", "workgroups"}: the team kernel's
+    launches between two events; steps = columns x words x pairs with pad words and ramp steps counted.  K = L = 0: the
+    queries of CYCLIC_QMAX + 1 .. CYCLIC_QMAX_LONG bp in the library's classes; else every query of the call in class
+    (K, L), short ones included -- a (K, L) outside CYCLIC_TEAM_CLASSES or a query of more than 64 * K * L bases is refused
+    before the device is touched.  arrays=True: also "dist", "end", "strand" (pairs of other queries are not computed)."""
+    import numpy as np
+    who = "cyclic_long_kernel_bench"
+    text, ro, rl, qi, ti = _cyclic_call(who, seqs, queries, targets)
+    K, L = _int_arg(who, "K", K, 0, 1 << 30), _int_arg(who, "L", L, 0, 1 << 30)
+    if (K, L) != (0, 0):
+        _cyclic_team_args(who, K, L, rl, qi)
+    m, k = len(qi), len(ti)
+    ms, info = (C.c_float * reps)(), (C.c_int64 * 4)()
+    dist, end, strand = np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.int32), np.zeros((m, k), dtype=np.uint8)
+    _check(load().sd_cyclic_long_kernel_bench(text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), qi.ctypes.data, ti.ctypes.data, m, k, int(device),
+                                              K, L, int(warmup), int(reps), ms, info, dist.ctypes.data, end.ctypes.data, strand.ctypes.data),
+           "sd_cyclic_long_kernel_bench")
     out = {"pairs_ms": [float(x) for x in ms]}
     out.update(zip(("launches", "pairs", "steps", "workgroups"), (int(x) for x in info)))
     if arrays:
