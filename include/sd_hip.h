@@ -765,6 +765,11 @@ int sd_seam_merge_dev(const sd_rec* d_recs, const int64_t* d_read_off, int32_t n
  * rows must equal sd_seam_merge's.  Arguments as above, in host memory. */
 int sd_seam_pieces_selftest(const sd_rec* recs, const int64_t* read_off, int32_t n_reads, int32_t piece, sd_rec* rows,
                             int64_t* row_off, int64_t* n_rows);
+/* The device prefix scan of the post-pass units alone (for tests; csrc/sd_scan_dev.hpp): out[i] = values[0] + .. +
+ * values[i - 1] for i = 0 .. n, so out holds n + 1 entries and out[n] is the total; values and out in host memory,
+ * 0 <= n < 2^31.  tile_sums_32 != 0: the sums per tile of 256 values are kept as int32 (the form of the units that
+ * count flags), else as int64.  Returns when it is done.  SD_ERR_NO_DEVICE without a device. */
+int sd_scan_selftest(const int64_t* values, int64_t n, int32_t tile_sums_32, int32_t device, int64_t* out);
 /* The selection kernels alone (for tests): the rows of n_reads reads (read r = d_rows[d_row_off[r] .. d_row_off[r + 1]),
  * read-global, already merged), row b's identity words at d_words / d_hwords + d_widx[b] * per (plain / homopolymer-
  * compressed; per = 1, the word of the row's own monomer, or with second_best 2 * n_mono, one per interleaved template

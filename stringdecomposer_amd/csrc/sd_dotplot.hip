@@ -7,10 +7,10 @@
 //                            The tile's bases and the k - 1 behind it go to LDS as codes (dotplot_base); a lane takes four
 //                            positions, builds both codes from k LDS bytes (dotplot_kmer) and tests h(code) % M; ballots
 //                            and population counts give the tile's selected positions per strand.
-//   sd_dotplot_scan          one workgroup: the exclusive scan of the tile counts (the forward tiles of the call, then the
-//                            reverse ones) = where every tile's codes go; then per (window, strand) the offset and the
-//                            count of its set, and the summary the host reads: total, largest count, the first set over
-//                            DOTPLOT_SET_MAX.
+//   exclusive_scan_dev       (sd_scan_dev.hpp) the exclusive scan of the tile counts (the forward tiles of the call, then
+//                            the reverse ones) = where every tile's codes go
+//   sd_dotplot_windows       one workgroup: per (window, strand) the offset and the count of its set, and the summary the
+//                            host reads: total, largest count, the first set over DOTPLOT_SET_MAX.
 //   sd_dotplot_tiles<true>   the gather: the same arithmetic, the selected codes written at the tile's offset in position
 //                            order (ballot prefix), so the codes of a window and strand lie together.
 //   sd_dotplot_sets          a workgroup per (window, strand): its codes to LDS, a sorting network whose comparators all
@@ -33,11 +33,12 @@
 #include "sd_dotplot.hpp"
 #include "sd_host.hpp"
 #include "sd_job_dev.hpp"
+#include "sd_scan_dev.hpp"
 
 namespace sd {
 
 constexpr int DP_T = 256;        // threads of a workgroup of the tile, set and pair kernels
-constexpr int DP_SCAN_T = 1024;  // ... of the scan
+constexpr int DP_WIN_T = 1024;   // ... of the window kernel
 #ifndef SD_DOTPLOT_ILP
 #define SD_DOTPLOT_ILP 8
 #endif
@@ -125,36 +126,12 @@ __global__ __launch_bounds__(DP_T) void sd_dotplot_tiles(DpArgs a, int64_t tile0
     }
 }
 
-__global__ __launch_bounds__(DP_SCAN_T) void sd_dotplot_scan(DpArgs a) {
-    __shared__ int64_t part[DP_SCAN_T];
-    __shared__ int64_t red[3][DP_SCAN_T];
+__global__ __launch_bounds__(DP_WIN_T) void sd_dotplot_windows(DpArgs a) {
+    __shared__ int64_t red[3][DP_WIN_T];
     const int tid = threadIdx.x, strands = a.rc ? 2 : 1;
-    const int64_t N = strands * a.tiles, per = (N + DP_SCAN_T - 1) / DP_SCAN_T;
-    const int64_t lo = per * tid < N ? per * tid : N, hi = lo + per < N ? lo + per : N;
-    int64_t s = 0;
-    for (int64_t x = lo; x < hi; ++x) s += a.tcnt[x];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < DP_SCAN_T; ++i) {
-            const int64_t v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        a.toff[N] = run;
-        a.summary[0] = run;
-    }
-    __syncthreads();
-    s = part[tid];
-    for (int64_t x = lo; x < hi; ++x) {
-        a.toff[x] = s;
-        s += a.tcnt[x];
-    }
-    __syncthreads();   // (one workgroup: its own stores to global memory are visible to it behind the barrier)
     const int64_t tpw = dotplot_tiles_per_window(a.W);
     int64_t best = 0, bad = -1, badn = 0;
-    for (int64_t x = tid; x < strands * a.windows; x += DP_SCAN_T) {
+    for (int64_t x = tid; x < strands * a.windows; x += DP_WIN_T) {
         const int64_t st = x / a.windows, w = x - st * a.windows;
         const int r = dotplot_find(a.win_off, a.n_reads, w);
         const int64_t wl = w - a.win_off[r], last = a.win_off[r + 1] - a.win_off[r] - 1;
@@ -170,10 +147,11 @@ __global__ __launch_bounds__(DP_SCAN_T) void sd_dotplot_scan(DpArgs a) {
     red[2][tid] = badn;
     __syncthreads();
     if (tid == 0) {
-        for (int i = 1; i < DP_SCAN_T; ++i) {
+        for (int i = 1; i < DP_WIN_T; ++i) {
             if (red[0][i] > best) best = red[0][i];
             if (red[1][i] >= 0 && (bad < 0 || red[1][i] < bad)) { bad = red[1][i]; badn = red[2][i]; }
         }
+        a.summary[0] = a.toff[strands * a.tiles];
         a.summary[1] = best;
         a.summary[2] = bad;
         a.summary[3] = badn;
@@ -319,7 +297,7 @@ std::atomic<int64_t> g_dp_launches{0};   // launches of sd_dotplot_pairs in this
 // [roff | rlen | win_off | tile_off | cell_off].
 struct DpCtx : DevWork, ReadTable {
     DevBuf<int32_t> tcnt, wraw;
-    DevBuf<int64_t> toff, woff, summary;
+    DevBuf<int64_t> toff, woff, summary, tsum, tbase;   // tsum, tbase: the tiles of the scan of tcnt
     DevBuf<uint64_t> sets;
     DevBuf<uint8_t> text;       // sd_dotplot_dev: the reads, back to back
     DevBuf<int32_t> out;        // sd_dotplot_dev: kmers | kmers_rc | shared | shared_rc
@@ -454,6 +432,7 @@ struct DpBench {
 struct DpJob {
     sd::DpArgs a;
     std::vector<int64_t> win_off, cell_off;
+    int64_t *tsum = nullptr, *tbase = nullptr;   // the tiles of the scan of tcnt
     int64_t cells = 0, selected = 0, largest = 0, launches = 0, workgroups = 0;
 };
 
@@ -476,12 +455,16 @@ void dp_tables(DpCtx& c, hipStream_t st, DpJob& j, const uint8_t* d_text, const 
     const size_t strands = rc ? 2 : 1;
     c.tcnt.alloc(strands * (size_t)tiles);
     c.toff.alloc(strands * (size_t)tiles + 1);
+    c.tsum.alloc((size_t)sd::scan_tiles_of((int64_t)strands * tiles));
+    c.tbase.alloc((size_t)sd::scan_tiles_of((int64_t)strands * tiles) + 1);
     c.woff.alloc(strands * (size_t)windows);
     c.wraw.alloc(strands * (size_t)windows);
     c.summary.alloc(4);
     c.h_summary.alloc(4);
     j.a = sd::DpArgs{d_text, c.d(0), c.d(1), c.d(2), c.d(3), c.d(4), (int)n_reads, k, rc, M, W, B, windows, tiles,
                      c.tcnt.p, c.toff.p, c.woff.p, c.wraw.p, c.summary.p, nullptr, nullptr, nullptr, nullptr, nullptr};
+    j.tsum = c.tsum.p;
+    j.tbase = c.tbase.p;
 }
 
 template <bool GATHER>
@@ -495,7 +478,8 @@ void dp_tiles(const DpJob& j, hipStream_t st) {
 
 void dp_count(const DpJob& j, hipStream_t st) {
     dp_tiles<false>(j, st);
-    hipLaunchKernelGGL(sd::sd_dotplot_scan, dim3(1), dim3(sd::DP_SCAN_T), 0, st, j.a);
+    sd::exclusive_scan_dev(st, sd::ScanArray<int32_t>{j.a.tcnt}, (j.a.rc ? 2 : 1) * j.a.tiles, j.a.toff, j.tsum, j.tbase);
+    hipLaunchKernelGGL(sd::sd_dotplot_windows, dim3(1), dim3(sd::DP_WIN_T), 0, st, j.a);
     SD_HIP(hipGetLastError());
 }
 

@@ -7,19 +7,19 @@
 //   sd_final_best      second_best: a group of 8 .. 64 lanes per row strides the T plain and T homopolymer words, each
 //                      word read ONCE;
 //                      (value, index) reductions that prefer the smaller index on equal values
-//   sd_rows_count, sd_rows_scan (sd_rows_scan_dev.hpp)   kept rows per tile, before each tile, the kept-row count
+//   sd_rows_count (sd_rows_flags_dev.hpp), scan_bases (sd_scan_dev.hpp)   kept rows per tile, before each tile, their count
 //   sd_final_scatter, sd_final_alt           kept rows -> the caller's rows, row offsets, key identities
 // A row the words do not decide (a missing word, a segment edlib aligns by Hirschberg's split) is counted, not guessed.
 #include "sd_convert.hpp"
 #include "sd_final_ws.hpp"
 #include "sd_job_dev.hpp"
-#include "sd_rows_scan_dev.hpp"
+#include "sd_rows_flags_dev.hpp"
 
 namespace sd {
 
 // workgroups [0, n_tiles): the kept records of a tile of the STORE -> src of their merged rows; the workgroups behind
 // them: the merged row offsets of the reads.  (sd_rows_scatter, writing indices instead of records; the store's tiles are
-// the ROWS_TILE of sd_rows_scan_dev.hpp, which both units include.)
+// the ROWS_TILE of sd_rows_flags_dev.hpp, which both units include.)
 __global__ __launch_bounds__(ROWS_T) void sd_final_sources(const uint8_t* __restrict__ keep, int64_t n, int64_t n_tiles,
                                                           const int64_t* __restrict__ bbase, const int64_t* __restrict__ read_off,
                                                           int n_reads, int64_t* __restrict__ src, int64_t cap,
@@ -28,7 +28,7 @@ __global__ __launch_bounds__(ROWS_T) void sd_final_sources(const uint8_t* __rest
         const int64_t i0 = (int64_t)blockIdx.x * ROWS_TILE + threadIdx.x * 4;
         const uint32_t f = rows_flags(keep, n, i0);
         int total;
-        int64_t at = bbase[blockIdx.x] + rows_block_scan(rows_flag_count(f), &total);
+        int64_t at = bbase[blockIdx.x] + block_scan<int>(rows_flag_count(f), &total);
         for (int k = 0; k < 4; ++k)
             if ((f >> (8 * k)) & 1u) {
                 if (at < cap) src[at] = i0 + k;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(ROWS_T) void sd_final_scatter(const sd_final_row* _
         const int64_t i0 = (int64_t)blockIdx.x * ROWS_TILE + threadIdx.x * 4;
         const uint32_t f = rows_flags(keep, n, i0);
         int total;
-        int64_t at = bbase[blockIdx.x] + rows_block_scan(rows_flag_count(f), &total);
+        int64_t at = bbase[blockIdx.x] + block_scan<int>(rows_flag_count(f), &total);
         for (int k = 0; k < 4; ++k) {
             if (i0 + k >= n) break;
             if ((f >> (8 * k)) & 1u) {
@@ -253,7 +253,7 @@ void final_select(FinalWS& f, hipStream_t st, const sd::FinalTables& dtb, const 
     }
     if (f.n_tiles > 0)
         hipLaunchKernelGGL(sd::sd_rows_count, dim3((unsigned)f.n_tiles), dim3(sd::ROWS_T), 0, st, f.keep.p, cap, f.bsum.p);
-    hipLaunchKernelGGL(sd::sd_rows_scan, dim3(1), dim3(sd::ROWS_T), 0, st, f.bsum.p, f.n_tiles, f.bbase.p);
+    hipLaunchKernelGGL(sd::scan_bases<int32_t>, dim3(1), dim3(sd::SCAN_T), 0, st, f.bsum.p, f.n_tiles, f.bbase.p);
     SD_HIP(hipGetLastError());
     SD_HIP(hipMemcpyAsync(f.h_counts.p, f.bbase.p + f.n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     SD_HIP(hipMemcpyAsync(f.h_counts.p + 1, f.und.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));

@@ -12,8 +12,8 @@
 //   sd_heat_plan     one lane per row as a TARGET: its word class and its number of strips (position in the group, W);
 //                    targets per class and the longest query of the job (workgroup histogram in LDS, then global adds)
 //   group_scan / sd_heat_scatter   the targets the kernel takes -> order[], grouped by word class (sd_group_dev.hpp)
-//   sd_heat_scan_*   exclusive prefix of the strip counts in that order (64-bit): work item i of a class is strip
-//                    i - scan[t] of the target t found by a binary search in the scan
+//   exclusive_scan_dev   (sd_scan_dev.hpp) exclusive prefix of the strip counts in that order (64-bit): work item i of a
+//                    class is strip i - scan[t] of the target t found by a binary search in the scan
 //   sd_heat_pairs<K> one-wave workgroups, grid-stride over the work items of class K.  No per-pair store: in a wave the
 //                    target's bin J is fixed and the query's bin I = x / B is monotone over the lanes, so {1, m, d + m}
 //                    are summed over the lanes of a cell by a segmented shuffle reduction (6 steps, two packed dwords)
@@ -36,10 +36,11 @@
 #include "sd_host.hpp"
 #include "sd_job_dev.hpp"
 #include "sd_nw_kernel.hpp"
+#include "sd_scan_dev.hpp"
 
 namespace sd {
 
-constexpr int HEAT_T = 256;   // threads per workgroup of the row / plan / scan kernels
+constexpr int HEAT_T = 256;   // threads per workgroup of the row / plan kernels
 // sum[]: [0, 6) targets per word class, [6] (the scan's end), then
 enum { HEAT_SUM_QMAX = 7, HEAT_SUM_BAD = 8, HEAT_SUM_ORDER = 9, HEAT_SUM_FAIL = 10, HEAT_SUM_N = 11 };
 enum { HEAT_MODE_KEEP_MASKS = 1, HEAT_MODE_NO_SINK = 2 };   // bench: the walk alone
@@ -116,54 +117,11 @@ __global__ __launch_bounds__(GROUP_T) void sd_heat_scatter(const uint8_t* __rest
     group_scatter(HeatSrc{cls}, n_seg, n_seg, LAG_CLASSES, cursor, order);
 }
 
-// ---- exclusive prefix of strips[order[i]], i < base[LAG_CLASSES] targets; scan[] has n_seg + 1 entries (0 strips behind the targets)
-__global__ __launch_bounds__(HEAT_T) void sd_heat_scan_local(const int32_t* __restrict__ strips, const int32_t* __restrict__ order,
-                                                             const int32_t* __restrict__ base, int64_t n_seg, int64_t* __restrict__ scan,
-                                                             int64_t* __restrict__ bsum) {
-    __shared__ int64_t v[HEAT_T];
-    const int64_t i = (int64_t)blockIdx.x * HEAT_T + threadIdx.x;
-    const int64_t mine = i < n_seg && i < base[LAG_CLASSES] ? strips[order[i]] : 0;
-    v[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < HEAT_T; off <<= 1) {
-        const int64_t add = (int)threadIdx.x >= off ? v[threadIdx.x - off] : 0;
-        __syncthreads();
-        v[threadIdx.x] += add;
-        __syncthreads();
-    }
-    if (i < n_seg) scan[i] = v[threadIdx.x] - mine;
-    if (threadIdx.x == HEAT_T - 1) bsum[blockIdx.x] = v[threadIdx.x];
-}
-
-// one workgroup: bsum[0 .. nblk) -> its exclusive prefix in place, the total at bsum[nblk]
-__global__ __launch_bounds__(HEAT_T) void sd_heat_scan_blocks(int64_t* __restrict__ bsum, int64_t nblk) {
-    __shared__ int64_t v[HEAT_T];
-    const int64_t per = (nblk + HEAT_T - 1) / HEAT_T, first = (int64_t)threadIdx.x * per, end = first + per < nblk ? first + per : nblk;
-    int64_t mine = 0;
-    for (int64_t j = first; j < end; ++j) mine += bsum[j];
-    v[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < HEAT_T; off <<= 1) {
-        const int64_t add = (int)threadIdx.x >= off ? v[threadIdx.x - off] : 0;
-        __syncthreads();
-        v[threadIdx.x] += add;
-        __syncthreads();
-    }
-    int64_t at = v[threadIdx.x] - mine;
-    for (int64_t j = first; j < end; ++j) {
-        const int64_t x = bsum[j];
-        bsum[j] = at;
-        at += x;
-    }
-    if (threadIdx.x == HEAT_T - 1) bsum[nblk] = v[threadIdx.x];
-}
-
-__global__ __launch_bounds__(HEAT_T) void sd_heat_scan_add(int64_t* __restrict__ scan, const int64_t* __restrict__ bsum, int64_t n_seg,
-                                                           int64_t nblk) {
-    const int64_t i = (int64_t)blockIdx.x * HEAT_T + threadIdx.x;
-    if (i < n_seg) scan[i] += bsum[blockIdx.x];
-    if (i == 0) scan[n_seg] = bsum[nblk];
-}
+// the strips of the i-th target in the order of the grouping, 0 behind the targets: what scan[] (n_seg + 1 entries) sums
+struct HeatStrips {
+    const int32_t *strips, *order, *base;
+    __device__ int64_t operator()(int64_t i) const { return i < base[LAG_CLASSES] ? strips[order[i]] : 0; }
+};
 
 // bound[k] = the first work item of class k, bound[LAG_CLASSES] = all of them
 __global__ void sd_heat_bounds(const int64_t* __restrict__ scan, const int32_t* __restrict__ base, int64_t* __restrict__ bound) {
@@ -276,7 +234,7 @@ namespace {
 // Per device, kept between calls (sd_job_dev.hpp: DevWork): text, segments, plan, grouping, scan and checkpoints.
 struct HeatCtx : DevWork, FinalText {
     DevBuf<uint8_t> cls, ck;
-    DevBuf<int64_t> seg_start, grp, scan, bsum, bound;   // grp: [group_off | cell_off]
+    DevBuf<int64_t> seg_start, grp, scan, tsum, tbase, bound;   // grp: [group_off | cell_off]; tsum, tbase: the scan's tiles
     DevBuf<int32_t> seg_len, seg_grp, strips, order, sum, base, cursor, per_read;
     PinBuf<int64_t> h_grp, h_bound;
     PinBuf<int32_t> h_sum, h_len, h_per_read;
@@ -425,12 +383,13 @@ int heat_host(const HeatJob& j, int which, int threads, int64_t* sums) {
 // plan + grouping + scan on st over the segments in c (seg_len, seg_grp, grp); the summary and the classes' item bounds on
 // their way to c.h_sum / c.h_bound, ev_plan recorded
 void heat_plan(HeatCtx& c, hipStream_t st, int64_t n_seg, int32_t n_groups, int64_t W, bool clear_sum) {
-    const int64_t nblk = (n_seg + sd::HEAT_T - 1) / sd::HEAT_T;
+    const int64_t n_tiles = sd::scan_tiles_of(n_seg);
     c.cls.alloc((size_t)n_seg);
     c.strips.alloc((size_t)n_seg);
     c.order.alloc((size_t)n_seg);
     c.scan.alloc((size_t)n_seg + 1);
-    c.bsum.alloc((size_t)nblk + 1);
+    c.tsum.alloc((size_t)n_tiles);
+    c.tbase.alloc((size_t)n_tiles + 1);
     c.bound.alloc(sd::LAG_CLASSES + 1);
     c.base.alloc(sd::LAG_CLASSES + 1);
     c.cursor.alloc(sd::LAG_CLASSES + 1);
@@ -442,9 +401,7 @@ void heat_plan(HeatCtx& c, hipStream_t st, int64_t n_seg, int32_t n_groups, int6
                        c.sum.p);
     group_scan(st, c.sum.p, sd::LAG_CLASSES, c.base.p, c.cursor.p);
     hipLaunchKernelGGL(sd::sd_heat_scatter, dim3(grid), dim3(sd::GROUP_T), 0, st, c.cls.p, n_seg, c.cursor.p, c.order.p);
-    hipLaunchKernelGGL(sd::sd_heat_scan_local, dim3(grid), dim3(sd::HEAT_T), 0, st, c.strips.p, c.order.p, c.base.p, n_seg, c.scan.p, c.bsum.p);
-    hipLaunchKernelGGL(sd::sd_heat_scan_blocks, dim3(1), dim3(sd::HEAT_T), 0, st, c.bsum.p, nblk);
-    hipLaunchKernelGGL(sd::sd_heat_scan_add, dim3(grid), dim3(sd::HEAT_T), 0, st, c.scan.p, c.bsum.p, n_seg, nblk);
+    sd::exclusive_scan_dev(st, sd::HeatStrips{c.strips.p, c.order.p, c.base.p}, n_seg, c.scan.p, c.tsum.p, c.tbase.p);
     hipLaunchKernelGGL(sd::sd_heat_bounds, dim3(1), dim3(64), 0, st, c.scan.p, c.base.p, c.bound.p);
     SD_HIP(hipGetLastError());
     SD_HIP(hipMemcpyAsync(c.h_sum.p, c.sum.p, sd::HEAT_SUM_N * sizeof(int32_t), hipMemcpyDeviceToHost, st));

@@ -9,7 +9,7 @@
 //                     32-bit halves), the set's match word is formed and added to the bit-sliced mismatch counter
 //                     (motif_word).  The hit word is masked to i + L <= n, counted, and the workgroup's sum is the int32
 //                     count of the item (read, pattern-strand, tile), laid out in canonical order.
-//   sd_rows_scan      (sd_rows_scan_dev.hpp) one workgroup: the items' bases and the total
+//   scan_bases        (sd_scan_dev.hpp) one workgroup: the items' bases and the total
 //   sd_motif_per      per[read][motif][strand] from the bases
 //   sd_motif_write    the work item of sd_motif_size again, for the items with a count: the hit words are recomputed, the
 //                     lanes' counts scanned within the workgroup, and every lane writes its own hits as 16-byte records
@@ -24,17 +24,14 @@
 #include "sd_motif.hpp"
 #include "sd_host.hpp"
 #include "sd_job_dev.hpp"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"   // (sd_rows_count counts byte flags; the size kernel counts here)
-#include "sd_rows_scan_dev.hpp"
-#pragma clang diagnostic pop
+#include "sd_scan_dev.hpp"
 
 static_assert(sizeof(sd_motif_hit) == 16, "a hit is one 16-byte store");
 
 namespace sd {
 
 constexpr int MT_T = MOTIF_TILE_WORDS;   // threads per workgroup: one word per lane
-static_assert(MT_T == ROWS_T, "rows_block_scan scans a workgroup of ROWS_T lanes");
+static_assert(MT_T == SCAN_T, "block_scan scans a workgroup of SCAN_T lanes");
 
 struct MtArgs {
     const uint64_t *lo, *hi, *v;                 // the planes of the job
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(MT_T) void sd_motif_write(MtArgs a, uint4* __restri
         uint64_t h = motif_word<E1>(a.pos + P.off, P.np, l.lo0, l.hi0, l.v0, l.lo1, l.hi1, l.v1, cp) & autocorr_word_mask(l.t, 0, l.n - P.L + 1);
         if (!l.active) h = 0;
         int total;
-        int64_t o = motif_request_word(a.base + item) + rows_block_scan(__popcll(h), &total);
+        int64_t o = motif_request_word(a.base + item) + block_scan<int>(__popcll(h), &total);
         const uint32_t tag = (uint32_t)P.tag;   // motif | strand << 16
         while (h) {
             const int bit = __ffsll((unsigned long long)h) - 1;
@@ -351,7 +348,7 @@ void mt_size(MtCtx& c, hipStream_t st, const MtJob& j, int32_t n_reads, int64_t*
     sd::motif_with_budget(j.set.E, [&](auto e1) {
         mt_units(c, [&](unsigned grid) { hipLaunchKernelGGL(sd::sd_motif_size<decltype(e1)::value>, dim3(grid), dim3(sd::MT_T), 0, st, c.a); });
     });
-    hipLaunchKernelGGL(sd::sd_rows_scan, dim3(1), dim3(sd::ROWS_T), 0, st, c.cnt.p, j.items, c.base.p);
+    hipLaunchKernelGGL(sd::scan_bases<int32_t>, dim3(1), dim3(sd::SCAN_T), 0, st, c.cnt.p, j.items, c.base.p);
     SD_HIP(hipGetLastError());
     const int64_t cells = (int64_t)n_reads * j.set.n_motifs * 2, rp = (int64_t)n_reads * c.a.n_ps;
     if (cells) {

@@ -10,7 +10,7 @@
 //                        on one 32-bit word for L <= 32 and one 64-bit word above (motif_edit_scan), and counts the ends
 //                        the rule takes.  The workgroup's sum is the int32 count of the item (read, pattern-strand,
 //                        tile), laid out in canonical order.
-//   sd_rows_scan         (sd_rows_scan_dev.hpp) one workgroup: the items' bases and the total
+//   scan_bases           (sd_scan_dev.hpp) one workgroup: the items' bases and the total
 //   sd_motif_edit_per    per[read][motif][strand] from the bases
 //   sd_motif_edit_write  the work item of the size kernel again, for the items with a count: the lane recomputes its hits
 //                        as a bit mask over its stretch, the lanes' counts are scanned within the workgroup, and for each
@@ -25,10 +25,7 @@
 #include "sd_motif_edit.hpp"
 #include "sd_host.hpp"
 #include "sd_job_dev.hpp"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"   // (sd_rows_count counts byte flags; the size kernel counts here)
-#include "sd_rows_scan_dev.hpp"
-#pragma clang diagnostic pop
+#include "sd_scan_dev.hpp"
 
 static_assert(sizeof(sd_motif_edit_hit) == 16, "a hit is one 16-byte store");
 static_assert(SD_MOTIF_KMAX == sd::MOTIF_EDIT_KMAX && SD_MOTIF_EDIT_TILE_WORDS == sd::MOTIF_EDIT_TILE_WORDS, "include/sd_hip.h states the limits");
@@ -38,7 +35,7 @@ namespace sd {
 
 constexpr int ME_T = MOTIF_EDIT_LANES;
 constexpr int ME_SW = MOTIF_EDIT_STRETCH_WORDS;
-static_assert(ME_T == ROWS_T, "rows_block_scan scans a workgroup of ROWS_T lanes");
+static_assert(ME_T == SCAN_T, "block_scan scans a workgroup of SCAN_T lanes");
 
 struct MeArgs {
     const uint64_t *lo, *hi, *v;                 // the planes of the job
@@ -166,7 +163,7 @@ __global__ __launch_bounds__(ME_T) void sd_motif_edit_write(MeArgs a, uint4* __r
         if (P.L <= 32) me_mask<uint32_t>(a, l, l.ps0 + q, P.L, hm); else me_mask<uint64_t>(a, l, l.ps0 + q, P.L, hm);
         int c = 0, total;
         for (int k = 0; k < ME_SW; ++k) c += __popcll(hm[k]);
-        const int64_t o = motif_request_word(a.base + item) + rows_block_scan(c, &total);
+        const int64_t o = motif_request_word(a.base + item) + block_scan<int>(c, &total);
         if (P.L <= 32) me_records<uint32_t>(a, l, l.ps0 + q, P, hm, o, hits); else me_records<uint64_t>(a, l, l.ps0 + q, P, hm, o, hits);
     }
 }
@@ -377,7 +374,7 @@ void me_units(MeCtx& c, Launch&& launch) {
 // counts, scan, per (d_per: n_reads x n_motifs x 2) and the total on its way to c.h_total; nothing waits
 void me_size(MeCtx& c, hipStream_t st, const MeJob& j, int32_t n_reads, int64_t* d_per) {
     me_units(c, [&](unsigned grid) { hipLaunchKernelGGL(sd::sd_motif_edit_size, dim3(grid), dim3(sd::ME_T), 0, st, c.a); });
-    hipLaunchKernelGGL(sd::sd_rows_scan, dim3(1), dim3(sd::ROWS_T), 0, st, c.cnt.p, j.items, c.base.p);
+    hipLaunchKernelGGL(sd::scan_bases<int32_t>, dim3(1), dim3(sd::SCAN_T), 0, st, c.cnt.p, j.items, c.base.p);
     SD_HIP(hipGetLastError());
     const int64_t cells = (int64_t)n_reads * j.set.set.n_motifs * 2, rp = (int64_t)n_reads * c.a.n_ps;
     if (cells) {

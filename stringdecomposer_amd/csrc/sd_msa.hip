@@ -15,6 +15,7 @@
 #include "sd_job_dev.hpp"
 #include "sd_msa.hpp"
 #include "sd_nw_kernel.hpp"
+#include "sd_scan_dev.hpp"
 
 namespace sd {
 
@@ -342,8 +343,8 @@ int nw_msa_device(const char* seq, int64_t seqlen, const int64_t* seg_start, con
 //                   (the walk reads aligned dwords up to the next multiple of 4 past a segment's end)
 //   sd_msa_plan     one lane per final row: its pair (final_prof_pair: the segment the selection measured, the row's own
 //                   interleaved template), its class, its pitch; per forward monomer the number of kernel pairs, the
-//                   longest such segment, the class counts
-//   sd_msa_scan     exclusive prefix of the pitches: the rows' places
+//                   longest such segment, the class counts; its first lane writes the row count the grouping reads
+//   exclusive_scan_dev   (sd_scan_dev.hpp) exclusive prefix of the pitches, in place: the rows' places
 //   sd_msa_fill     status of every row; the rows of pairs the kernel does not take, cleared
 // Grouping and work items are those of the device profile (prof_group / prof_items), the walk is sd_nw_msa.
 namespace sd {
@@ -386,11 +387,13 @@ struct MsaPlanArgs {
     uint8_t* cls;
     int32_t* sum;              // M + 4
     int64_t* row_at;           // the row's pitch, scanned afterwards
+    int64_t* n_ptr;            // = n (prof_group's n_ptr)
 };
 
 __global__ __launch_bounds__(MSA_T) void sd_msa_plan(MsaPlanArgs a) {
     const int64_t i = (int64_t)blockIdx.x * MSA_T + threadIdx.x;
     if (i >= a.n) return;
+    if (i == 0) *a.n_ptr = a.n;
     const sd_final_row x = a.rows[i];
     uint8_t c = FPROF_NONE;
     int32_t il = -1, len = 0;
@@ -418,27 +421,6 @@ __global__ __launch_bounds__(MSA_T) void sd_msa_plan(MsaPlanArgs a) {
     a.row_at[i] = pitch;
 }
 
-// one workgroup: lane t owns rows [t * per, (t + 1) * per); at[n] = tot[0] = all bytes, tot[1] = n (the grouping's n_ptr)
-__global__ __launch_bounds__(MSA_T) void sd_msa_scan(int64_t* __restrict__ at, int64_t n, int64_t* __restrict__ tot) {
-    __shared__ int64_t part[MSA_T];
-    const int64_t per = (n + MSA_T - 1) / MSA_T;
-    const int64_t a = min(n, (int64_t)threadIdx.x * per), e = min(n, a + per);
-    int64_t s = 0;
-    for (int64_t i = a; i < e; ++i) s += at[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int t = 0; t < MSA_T; ++t) { const int64_t v = part[t]; part[t] = run; run += v; }
-        at[n] = run;
-        tot[0] = run;
-        tot[1] = n;
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t i = a; i < e; ++i) { const int64_t v = at[i]; at[i] = run; run += v; }
-}
-
 __global__ __launch_bounds__(MSA_T) void sd_msa_fill(const uint8_t* __restrict__ cls, const int32_t* __restrict__ pair_il,
                                                      const int32_t* __restrict__ tlen, const int64_t* __restrict__ row_at, int64_t n,
                                                      uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
@@ -463,7 +445,8 @@ struct sd_msa_tables {
     ProfDev d;
     ProfWS w;
     DevBuf<uint8_t> text;
-    DevBuf<int64_t> reads, tot;              // [roff | rlen | text_off] (n_reads + 1 each); {bytes, rows}
+    DevBuf<int64_t> reads, n_ptr;            // [roff | rlen | text_off] (n_reads + 1 each); the rows of the last size pass
+    DevBuf<int64_t> tsum, tbase;             // the tiles of the scan of row_at
     PinBuf<int64_t> h_reads, h_tot;
     PinBuf<int32_t> h_sum;                   // qmax, host pairs, no instance, bad rows, failed walks
     hipEvent_t ev_size = nullptr, ev_use = nullptr;
@@ -565,8 +548,10 @@ int sd_msa_final_size_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t 
         t->h_reads.alloc(3 * nr);
         t->reads.alloc(3 * nr);
         t->text.alloc((size_t)text + 8);
-        t->tot.alloc(2);
-        t->h_tot.alloc(2);
+        t->n_ptr.alloc(1);
+        t->tsum.alloc((size_t)sd::scan_tiles_of(n_rows));
+        t->tbase.alloc((size_t)sd::scan_tiles_of(n_rows) + 1);
+        t->h_tot.alloc(1);
         t->h_sum.alloc(8);
         w.seg_start.alloc(cap);
         w.seg_len.alloc(cap);
@@ -586,12 +571,12 @@ int sd_msa_final_size_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t 
         sd::launch_text_gather(st, static_cast<const uint8_t*>(d_text), t->reads.p, t->reads.p + 2 * nr, (int)n_reads, text, t->text.p);
         if (n_rows > 0) {
             sd::MsaPlanArgs a{d_rows, n_rows, t->d.own_il.p, (int)t->key_il.size(), t->d.tlen.p, t->d.tmax, M, t->reads.p + nr,
-                              t->reads.p + 2 * nr, (int)n_reads, w.seg_start.p, w.seg_len.p, w.pair_il.p, w.cls.p, w.sum.p, d_row_at};
+                              t->reads.p + 2 * nr, (int)n_reads, w.seg_start.p, w.seg_len.p, w.pair_il.p, w.cls.p, w.sum.p, d_row_at, t->n_ptr.p};
             hipLaunchKernelGGL(sd::sd_msa_plan, dim3(msa_grid(n_rows)), dim3(sd::MSA_T), 0, st, a);
         }
-        hipLaunchKernelGGL(sd::sd_msa_scan, dim3(1), dim3(sd::MSA_T), 0, st, d_row_at, n_rows, t->tot.p);
+        sd::exclusive_scan_dev(st, sd::ScanArray<int64_t>{d_row_at}, n_rows, d_row_at, t->tsum.p, t->tbase.p);
         SD_HIP(hipGetLastError());
-        SD_HIP(hipMemcpyAsync(t->h_tot.p, t->tot.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        SD_HIP(hipMemcpyAsync(t->h_tot.p, d_row_at + n_rows, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         SD_HIP(hipMemcpyAsync(t->h_sum.p, w.sum.p + M, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         SD_HIP(hipMemcpyAsync(t->h_sum.p + 4, t->d.fails(), sizeof(int32_t), hipMemcpyDeviceToHost, st));
         SD_HIP(hipEventRecord(t->ev_size, st));
@@ -654,7 +639,7 @@ int sd_msa_final_write_dev(sd_msa_tables* t, const sd_final_row* d_rows, int64_t
                            d_out, d_status);
         SD_HIP(hipGetLastError());
         if (t->nd > 0) {
-            prof_group(w, M, st, n_rows, t->tot.p + 1);
+            prof_group(w, M, st, n_rows, t->n_ptr.p);
             // (the sizes of nw_profile_device; the items from the pair count alone: at most nd / per + M of them)
             const int K = d.K, S = sd::nw_block_cols(K);
             const int ckcap = std::max(1, (t->qmax + S - 1) / S);

@@ -6,11 +6,11 @@
 // and a read of a million records take the same path; nothing is sequential over records.
 //   sd_rows_append   a batch's chunk-local records -> the job's store, chunk offsets added, scores scaled
 //   sd_seam_exits, sd_seam_chain, sd_seam_keep      the piece algebra
-//   sd_rows_count, sd_rows_scan                     kept records per tile, rows before each tile, the row count
+//   sd_rows_count, scan_bases (sd_scan_dev.hpp)     kept records per tile, rows before each tile, the row count
 //   sd_rows_scatter                                 kept records -> rows, row offsets per read
 // No look-back and no spinning: a launch per stage, seven for a job (~5 MB of records in the benchmark's step).
 #include "sd_job_dev.hpp"
-#include "sd_rows_scan_dev.hpp"
+#include "sd_rows_flags_dev.hpp"
 #include "sd_seam_dev.hpp"
 
 namespace sd {
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(ROWS_T) void sd_rows_scatter(const DevRec* __restri
         const int64_t i0 = (int64_t)blockIdx.x * ROWS_TILE + threadIdx.x * 4;
         const uint32_t f = rows_flags(keep, n, i0);
         int total;
-        int64_t at = bbase[blockIdx.x] + rows_block_scan(rows_flag_count(f), &total);
+        int64_t at = bbase[blockIdx.x] + block_scan<int>(rows_flag_count(f), &total);
         for (int k = 0; k < 4; ++k)
             if ((f >> (8 * k)) & 1u) {
                 if (at < cap) rows[at] = recs[i0 + k];
@@ -163,7 +163,7 @@ void rows_assemble(RowsWS& ws, hipStream_t st, const sd::DevRec* recs, const int
     }
     if (ws.n_tiles > 0)
         hipLaunchKernelGGL(sd::sd_rows_count, dim3((unsigned)ws.n_tiles), dim3(sd::ROWS_T), 0, st, ws.keep.p, ws.n_recs, ws.bsum.p);
-    hipLaunchKernelGGL(sd::sd_rows_scan, dim3(1), dim3(sd::ROWS_T), 0, st, ws.bsum.p, ws.n_tiles, ws.bbase.p);
+    hipLaunchKernelGGL(sd::scan_bases<int32_t>, dim3(1), dim3(sd::SCAN_T), 0, st, ws.bsum.p, ws.n_tiles, ws.bbase.p);
     SD_HIP(hipGetLastError());
     SD_HIP(hipMemcpyAsync(ws.h_total.p, ws.bbase.p + ws.n_tiles, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     SD_HIP(hipEventRecord(ws.ev_asm, st));
@@ -186,6 +186,18 @@ static bool rows_offsets_ok(const int64_t* read_off, int32_t n_reads) {
     for (int32_t r = 0; r < n_reads; ++r)
         if (read_off[r + 1] < read_off[r]) return false;
     return read_off[n_reads] < ((int64_t)1 << 40);
+}
+
+// sd_scan_selftest: the scan of sd_scan_dev.hpp over d_values with tile sums of type T, finished when it returns
+template <class T>
+static void scan_selftest(hipStream_t st, const int64_t* d_values, int64_t n, int64_t* d_out) {
+    DevBuf<T> tsum;
+    DevBuf<int64_t> tbase;
+    tsum.alloc((size_t)sd::scan_tiles_of(n));
+    tbase.alloc((size_t)sd::scan_tiles_of(n) + 1);
+    sd::exclusive_scan_dev(st, sd::ScanArray<int64_t>{d_values}, n, d_out, tsum.p, tbase.p);
+    SD_HIP(hipGetLastError());
+    SD_HIP(hipStreamSynchronize(st));   // (the buffers go back with nothing in flight on them)
 }
 
 }  // namespace sdi
@@ -218,6 +230,27 @@ int sd_seam_pieces_selftest(const sd_rec* recs, const int64_t* read_off, int32_t
         row_off[r + 1] = w;
     }
     if (n_rows) *n_rows = w;
+    return SD_OK;
+} catch (const std::bad_alloc&) {
+    return SD_ERR_INTERNAL;
+}
+
+int sd_scan_selftest(const int64_t* values, int64_t n, int32_t tile_sums_32, int32_t device, int64_t* out) try {
+    if (n < 0 || n >= ((int64_t)1 << 31) || !out || (n > 0 && !values)) return SD_ERR_PARAM;
+    if (const int rc = device_check(device, nullptr, 0)) return rc;
+    try {
+        DeviceScope on(device);
+        OwnedStream st;
+        DevBuf<int64_t> d_values, d_out;
+        d_values.alloc((size_t)n);
+        d_out.alloc((size_t)n + 1);
+        if (n > 0) SD_HIP(hipMemcpyAsync(d_values.p, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        if (tile_sums_32) scan_selftest<int32_t>(st, d_values.p, n, d_out.p);
+        else scan_selftest<int64_t>(st, d_values.p, n, d_out.p);
+        SD_HIP(hipMemcpy(out, d_out.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    } catch (const HipFail&) {
+        return SD_ERR_HIP;
+    }
     return SD_OK;
 } catch (const std::bad_alloc&) {
     return SD_ERR_INTERNAL;

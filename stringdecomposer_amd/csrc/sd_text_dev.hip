@@ -1,11 +1,12 @@
 // sd_text_dev.hip -- the text of device rows, formatted on the device: the last link of the chain DeviceReads -> device
 // rows -> device final rows.  The bytes of a row are sd_text_dev.hpp, one text with the host twin at the end of this file.
 //   sd_text_raw_len / sd_text_final_len   one lane per row: the row is checked against its tables (a bad index is counted,
-//                      never followed), its bytes go to row_pos[row] and their sum per tile of 256 rows to tsum; the raw
+//                      never followed), the bytes of the tile's rows before it go to row_pos[row] and the tile's sum (256
+//                      rows) to tsum; the raw
 //                      kernel also finds the row's read (row_read).  With alt, the lanes of the final kernel then stride
 //                      the tile's n_keys identities per row, coalesced, and add each line's digits into the row's LDS slot.
-//   sd_text_scan       one workgroup: the tile sums -> the bytes before each tile (int64)
-//   sd_text_place      per tile: row_pos[row] = bytes before the row; row_pos[n_rows] = the total
+//   scan_bases         (sd_scan_dev.hpp) one workgroup: the tile sums -> the bytes before each tile (int64)
+//   scan_place         (sd_scan_dev.hpp) row_pos[row] = bytes before the row; row_pos[n_rows] = the total
 //   sd_text_read_pos   the row offsets are checked; read_pos[r] = row_pos[row_off[r]]; totals and counts -> 32 bytes
 //   sd_text_write      a workgroup takes 256 consecutive rows (_alt: whole final rows of about 256 lines together, their
 //                      line positions from a scan inside the workgroup), whose text is one byte range.  The range is cut
@@ -17,36 +18,16 @@
 // Nothing is allocated per call: scratch that scales with the job is the caller's, tile sums and counters are grow-only
 // buffers of the sd_text_tables object.
 #include "sd_pipeline.hpp"
+#include "sd_scan_dev.hpp"
 #include "sd_text_dev.hpp"
 
 namespace sd {
 
-constexpr int TEXT_T = 256;             // lanes per workgroup = rows per tile (ROWS_T of sd_rows_scan_dev.hpp)
+constexpr int TEXT_T = SCAN_T;          // lanes per workgroup = rows per tile
 constexpr int TEXT_TILE = 32768;        // bytes of text staged in LDS at a time
 enum { TEXT_RAW = 0, TEXT_FINAL = 1, TEXT_ALT = 2 };
 enum { CNT_BYTES = 0, CNT_ALT_BYTES = 1, CNT_ODD = 2, CNT_BAD = 3 };
 typedef unsigned long long text_u64;
-
-// rows_block_scan (sd_rows_scan_dev.hpp) on int64
-__device__ inline int64_t text_block_scan(int64_t v, int64_t* total) {
-    __shared__ int64_t wsum[TEXT_T / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int64_t sc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t s2 = __shfl_up(sc, off);
-        if (lane >= off) sc += s2;
-    }
-    __syncthreads();   // (the last call's readers are through)
-    if (lane == 63) wsum[w] = sc;
-    __syncthreads();
-    int64_t pre = 0, all = 0;
-    for (int x = 0; x < TEXT_T / 64; ++x) {
-        if (x < w) pre += wsum[x];
-        all += wsum[x];
-    }
-    *total = all;
-    return pre + sc - v;
-}
 
 // the read r with row_off[r] <= i < row_off[r + 1] where the offsets rise; in [0, n_reads) whatever they hold
 __device__ inline int32_t text_read_of(const int64_t* __restrict__ row_off, int32_t n_reads, int64_t i) {
@@ -76,10 +57,10 @@ __global__ __launch_bounds__(TEXT_T) void sd_text_raw_len(TextNames R, TextNames
         if (ok) len = text_raw_len(R, T, rd, r, i > row_off[rd] ? rows[i - 1].end : 0);
         else atomicAdd(cnt + CNT_BAD, 1ull);
         row_read[i] = rd;
-        row_pos[i] = len;
     }
     int64_t total;
-    (void)text_block_scan(len, &total);
+    const int64_t ex = block_scan<int64_t>(len, &total);
+    if (i < n) row_pos[i] = ex;
     if (threadIdx.x == 0) tsum[blockIdx.x] = total;
 }
 
@@ -103,10 +84,10 @@ __global__ __launch_bounds__(TEXT_T) void sd_text_final_len(TextNames R, TextNam
         } else {
             atomicAdd(cnt + CNT_BAD, 1ull);
         }
-        row_pos[i] = len;
     }
     int64_t total;
-    (void)text_block_scan(len, &total);
+    const int64_t ex = block_scan<int64_t>(len, &total);
+    if (i < n) row_pos[i] = ex;
     if (threadIdx.x == 0) tsum[blockIdx.x] = total;
     if (!alt) {
         if (odd) atomicAdd(cnt + CNT_ODD, (text_u64)odd);
@@ -119,32 +100,10 @@ __global__ __launch_bounds__(TEXT_T) void sd_text_final_len(TextNames R, TextNam
     for (uint32_t j = threadIdx.x; j < nl; j += TEXT_T) atomicAdd(&acc[j / (uint32_t)n_keys], text_fixed2_len(a[j], &odd));
     __syncthreads();
     const int64_t alen = ok ? (int64_t)n_keys * common + (K.off[n_keys] - K.off[0]) + acc[threadIdx.x] : 0;
-    if (i < n) alt_pos[i] = alen;
     if (odd) atomicAdd(cnt + CNT_ODD, (text_u64)odd);
-    (void)text_block_scan(alen, &total);
+    const int64_t aex = block_scan<int64_t>(alen, &total);
+    if (i < n) alt_pos[i] = aex;
     if (threadIdx.x == 0) atsum[blockIdx.x] = total;
-}
-
-// one workgroup: tbase[b] = bytes before tile b, tbase[n_tiles] = all bytes
-__global__ __launch_bounds__(TEXT_T) void sd_text_scan(const int64_t* __restrict__ tsum, int64_t n_tiles, int64_t* __restrict__ tbase) {
-    int64_t run = 0;
-    for (int64_t b0 = 0; b0 < n_tiles; b0 += TEXT_T) {
-        const int64_t b = b0 + threadIdx.x;
-        int64_t total;
-        const int64_t ex = text_block_scan(b < n_tiles ? tsum[b] : 0, &total);
-        if (b < n_tiles) tbase[b] = run + ex;
-        run += total;
-    }
-    if (threadIdx.x == 0) tbase[n_tiles] = run;
-}
-
-__global__ __launch_bounds__(TEXT_T) void sd_text_place(int64_t* __restrict__ pos, int64_t n, const int64_t* __restrict__ tbase,
-                                                       int64_t n_tiles) {
-    const int64_t i = (int64_t)blockIdx.x * TEXT_T + threadIdx.x;
-    int64_t total;
-    const int64_t ex = text_block_scan(i < n ? pos[i] : 0, &total);
-    if (i < n) pos[i] = tbase[blockIdx.x] + ex;
-    if (blockIdx.x == 0 && threadIdx.x == 0) pos[n] = tbase[n_tiles];
 }
 
 __global__ __launch_bounds__(TEXT_T) void sd_text_read_pos(const int64_t* __restrict__ row_off, int32_t n_reads, int64_t n,
@@ -218,7 +177,7 @@ __global__ __launch_bounds__(TEXT_T) void sd_text_write(TextWriteArgs a) {
                 if (have) len = text_alt_line_len(text_alt_common(a.R, f), a.K, k, v, &odd);
             }
             int64_t total;
-            pos = base + text_block_scan(len, &total);
+            pos = base + block_scan<int64_t>(len, &total);
             end = pos + len;
             lo = base;
             hi = base + total;
@@ -342,12 +301,13 @@ static void text_used(sd_text_tables* t, hipStream_t st) {
 
 static inline unsigned text_grid(int64_t items, int per) { return (unsigned)std::max<int64_t>(1, (items + per - 1) / per); }
 
-// scan + place of one position array, then (last) the read positions and the counts; waits for the 32 bytes
+// the tile bases of one position array and their place in it, then (last) the read positions and the counts; waits for
+// the 32 bytes
 static void text_scan_place(sd_text_tables* t, hipStream_t st, int64_t* pos, int64_t n, int64_t n_tiles, int which) {
     int64_t* tsum = t->tsum.p + which * std::max<int64_t>(1, n_tiles);
     int64_t* tbase = t->tbase.p + which * (n_tiles + 1);
-    hipLaunchKernelGGL(sd::sd_text_scan, dim3(1), dim3(sd::TEXT_T), 0, st, tsum, n_tiles, tbase);
-    hipLaunchKernelGGL(sd::sd_text_place, dim3(text_grid(n, sd::TEXT_T)), dim3(sd::TEXT_T), 0, st, pos, n, tbase, n_tiles);
+    hipLaunchKernelGGL(sd::scan_bases<int64_t>, dim3(1), dim3(sd::TEXT_T), 0, st, tsum, n_tiles, tbase);
+    hipLaunchKernelGGL(sd::scan_place<int64_t>, dim3(text_grid(n, sd::TEXT_T)), dim3(sd::TEXT_T), 0, st, pos, n, tbase, n_tiles);
 }
 static int text_size_end(sd_text_tables* t, hipStream_t st, const int64_t* row_off, int64_t n, const int64_t* row_pos,
                          const int64_t* alt_pos, int64_t* read_pos, int64_t* alt_read_pos, int64_t* bytes, int64_t* alt_bytes,

@@ -50,6 +50,7 @@ EXPORTS = [
     "sd_stream_submit_dev", "sd_engine_load_reads_dev", "sd_pack_bases_dev", "sd_engine_filter_result",
     "sd_fasta_load_ex", "sd_normalize_host", "sd_normalize_dev", "sd_last_run_input_stats",
     "sd_stream_peek_dev", "sd_stream_collect_dev", "sd_engine_rows_dev", "sd_seam_merge_dev", "sd_seam_pieces_selftest",
+    "sd_scan_selftest",
     "sd_stream_peek_final_dev", "sd_stream_collect_final_dev", "sd_final_select_dev", "sd_final_select_host",
     "sd_stream_profile_dev", "sd_stream_profile_stats", "sd_final_profile_dev", "sd_final_profile_host",
     "sd_plan_floor_levels",
@@ -3517,6 +3518,20 @@ def seam_pieces_host(recs, read_off, piece=0):
     if rc != SD_OK:
         raise SdError(rc, "sd_seam_pieces_selftest")
     return rows[:n.value], row_off
+
+
+def scan_selftest(values, tile_sums_32=False, device=0):
+    """The device prefix scan of the post-pass units alone (sd_scan_selftest): values: n int64 counts ->
+    n + 1 int64, out[i] = the sum of values[:i].  tile_sums_32: keep the sums per tile as int32."""
+    import numpy as np
+    v = np.ascontiguousarray(values, dtype=np.int64)
+    out = np.empty(len(v) + 1, dtype=np.int64)
+    L = load()
+    L.sd_scan_selftest.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    rc = L.sd_scan_selftest(v.ctypes.data, len(v), 1 if tile_sums_32 else 0, int(device), out.ctypes.data)
+    if rc != SD_OK:
+        raise SdError(rc, "sd_scan_selftest")
+    return out
 
 
 def seam_merge_device(recs, read_off, piece=0, device=0, stream=None, pad=0):

@@ -105,6 +105,21 @@ def test_reduction_on_identical_rows():
     assert (one.sums == want).all()
 
 
+def test_scan_of_more_than_a_tile_of_targets_in_two_classes():
+    """one group of 300 rows of 60 and of 200 bp: the strip counts of 299 targets are scanned over two tiles of 256, in the
+    order of two word classes with a bound between them; every cell against the host form of the same call"""
+    r = random.Random(31)
+    short, long_ = lag_cases.rand_seq(r, 60), lag_cases.rand_seq(r, 200)
+    rows = [lag_cases.fit(r, lag_cases.mutate(r, b), len(b)) for b in (long_ if r.random() < 0.4 else short for _ in range(300))]
+    assert {lag_cases.words(len(s)) for s in rows} == {1, 4}
+    text, st, en, off = lag_cases.layout([rows], seed=31)
+    dev = lib.heat_segments(text, st, en, off, 16, 0, device=0, threads=THREADS)
+    host = lib.heat_segments(text, st, en, off, 16, 0, threads=THREADS, which=0)
+    assert dev.classes == (300 * 299 // 2, 0, 0)
+    assert dev.sums.shape == host.sums.shape and (dev.sums == host.sums).all()
+    assert int(dev.sums[:, 0].sum()) == 300 * 299 // 2
+
+
 # ---- the device-resident form ------------------------------------------------------------------------------------------
 
 def _device_reads(rs):

@@ -167,6 +167,26 @@ def test_final_msa_device_equals_host_on_the_rows_of_the_job(synth_job, kw):
         assert (c[:, :7] == p[:, :7]).all()
 
 
+def test_row_offsets_of_more_than_a_tile_of_rows():
+    """300 final rows of one read, made by hand from the segments of msa_cases, against monomers of three pitches: the
+    scan of the pitches runs over two tiles of 256 rows; row_at is sd_msa_row_offsets' on the host"""
+    import torch
+    monos = [msa_cases.random_monomer(n, 90 + n) for n in (64, 130, 171)]
+    names = ["m%d" % i for i in range(len(monos))]
+    keys = [n + s for n in names for s in ("", "'")]   # key k = interleaved template k
+    seq, st, en, pt = msa_cases.segments(monos, 300, seed=17)
+    rows = np.zeros(len(st), dtype=lib.final_dtype())
+    rows["start"], rows["end"], rows["best"] = st, en, pt
+    dfr = lib.DeviceFinalRows(torch.from_numpy(rows.view(np.uint8).reshape(len(st), -1)).to("cuda:0"),
+                              torch.tensor([0, len(st)], dtype=torch.int64, device="cuda:0"), None, len(st))
+    dm = lib.final_msa_device(dfr, _device_reads([seq.encode()]), keys, names, monos)
+    want = lib.msa_row_offsets([len(m) for m in monos], pt)
+    assert len({int(b - a) for a, b in zip(want[:-1], want[1:])}) == 3
+    assert (dm.row_at.cpu().numpy() == want).all() and dm.rows.numel() == int(want[-1])
+    assert dm.classes == (0, len(st), 0)
+    _same(dm.to_host(), lib.msa_segments(seq, st, en, monos, pt, threads=THREADS))
+
+
 def test_a_long_block_is_left_out_and_counted():
     """A run of 929 N inside one monomer instance (the construction of the long_block golden): the decomposition covers
     it with one block of 1 100 bases, which the row kernel does not take (segments up to 1024 bp).  Exactly that row has
