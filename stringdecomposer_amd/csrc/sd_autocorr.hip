@@ -175,23 +175,7 @@ int ac_limits(const char* who, const int64_t* read_lens, int32_t n_reads, int64_
 }
 
 // ---- the host form ------------------------------------------------------------------------------------------------------
-struct AcPlanes {
-    std::vector<uint64_t> lo, hi, v;   // autocorr_plane_words(n) + 1 words: the shifted partner reads one word further
-    int64_t rw = 0;
-    void build(const uint8_t* t, int64_t n) {
-        rw = sd::autocorr_words(n);
-        lo.assign((size_t)rw + 2, 0);
-        hi.assign((size_t)rw + 2, 0);
-        v.assign((size_t)rw + 2, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const int c = sd::autocorr_code(t[i]);
-            if (c < 0) continue;
-            const uint64_t bit = (uint64_t)1 << (i & 63);
-            v[(size_t)(i >> 6)] |= bit;
-            if (c & 1) lo[(size_t)(i >> 6)] |= bit;
-            if (c & 2) hi[(size_t)(i >> 6)] |= bit;
-        }
-    }
+struct AcPlanes : sd::AutocorrPlanes {
     static uint64_t at(const std::vector<uint64_t>& p, int64_t rw, int64_t idx) { return idx < rw ? p[(size_t)idx] : 0; }
     // the equality word of word t at lag d
     uint64_t eq(int64_t t, int64_t d) const {
@@ -334,9 +318,6 @@ int ac_dev(const char* who, const char* text, const int64_t* read_off, const int
     const int64_t cells = windows * D;
     if ((rc = reads_text_args(who, text, read_off, read_lens, n_reads, cells > 0 && !counts, errbuf, errlen))) return rc;
     if ((rc = device_check(device, errbuf, errlen))) return rc;
-    std::vector<int64_t> off((size_t)n_reads + 1, 0);
-    for (int32_t r = 0; r < n_reads; ++r) off[(size_t)r + 1] = off[(size_t)r] + read_lens[r];
-    const int64_t bases = off[(size_t)n_reads];
     try {
         DeviceScope on(device);
         AcCtx& c = device_ctx<AcCtx>(device);
@@ -345,10 +326,7 @@ int ac_dev(const char* who, const char* text, const int64_t* read_off, const int
         OwnedStream st;
         DevBuf<int64_t> d_counts;
         d_counts.alloc((size_t)cells);
-        c.text.alloc((size_t)bases);
-        for (int32_t r = 0; r < n_reads; ++r)   // the reads back to back, whatever their order and gaps in the caller's buffer
-            if (read_lens[r] > 0)
-                SD_HIP(hipMemcpyAsync(c.text.p + off[(size_t)r], text + read_off[r], (size_t)read_lens[r], hipMemcpyHostToDevice, st));
+        const std::vector<int64_t> off = reads_upload(c.text, st, text, read_off, read_lens, n_reads);
         ac_enqueue(c, st, c.text.p, off.data(), read_lens, n_reads, k, D, W, win_off.data(), windows, d_counts.p, bench);
         c.in_flight(st);
         if (cells) SD_HIP(hipMemcpyAsync(counts, d_counts.p, sizeof(int64_t) * (size_t)cells, hipMemcpyDeviceToHost, st));

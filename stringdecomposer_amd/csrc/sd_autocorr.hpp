@@ -16,6 +16,7 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>   // hipStream_t of launch_autocorr_prep
@@ -147,6 +148,28 @@ SD_HD inline bool autocorr_is_peak(const int64_t* a, int64_t D, int64_t LO, int6
 SD_HD inline bool autocorr_peak_before(int64_t count_a, int64_t lag_a, int64_t count_b, int64_t lag_b) {
     return count_a != count_b ? count_a > count_b : lag_a < lag_b;
 }
+
+// ---- host only: the planes of one read as sd_autocorr_prep lays them out, for the host forms of the passes that read
+// them (sd_autocorr.hip, sd_motif.hip, sd_motif_edit.hip).  Two words of zeros follow the read's own, one more than on the
+// device: a shifted partner or the pair (t, t + 1) of the last word of the planes reads inside them.
+struct AutocorrPlanes {
+    std::vector<uint64_t> lo, hi, v;   // autocorr_words(n) + 2 words
+    int64_t rw = 0;                    // autocorr_words(n)
+    void build(const uint8_t* t, int64_t n) {
+        rw = autocorr_words(n);
+        lo.assign((size_t)rw + 2, 0);
+        hi.assign((size_t)rw + 2, 0);
+        v.assign((size_t)rw + 2, 0);
+        for (int64_t i = 0; i < n; ++i) {
+            const int c = autocorr_code(t[i]);
+            if (c < 0) continue;
+            const uint64_t bit = (uint64_t)1 << (i & 63);
+            v[(size_t)(i >> 6)] |= bit;
+            if (c & 1) lo[(size_t)(i >> 6)] |= bit;
+            if (c & 2) hi[(size_t)(i >> 6)] |= bit;
+        }
+    }
+};
 
 #if defined(__HIPCC__)
 // sd_autocorr_prep (sd_autocorr.hip) for the other passes that read the planes (sd_motif.hip): the text of n_reads reads

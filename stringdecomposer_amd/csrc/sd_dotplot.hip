@@ -564,19 +564,13 @@ int dp_dev(const char* who, const char* text, const int64_t* read_off, const int
     rc = rc ? 1 : 0;
     if ((e = dp_text_args(who, text, read_off, read_lens, n_reads, rc, windows, j.cells, kmers, kmers_rc, shared, shared_rc, errbuf, errlen))) return e;
     if ((e = device_check(device, errbuf, errlen))) return e;
-    std::vector<int64_t> off((size_t)n_reads + 1, 0);
-    for (int32_t r = 0; r < n_reads; ++r) off[(size_t)r + 1] = off[(size_t)r] + read_lens[r];
-    const int64_t bases = off[(size_t)n_reads];
     try {
         DeviceScope on(device);
         DpCtx& c = device_ctx<DpCtx>(device);
         std::lock_guard<std::mutex> g(c.m);
         c.settle();
         OwnedStream st;
-        c.text.alloc((size_t)bases);
-        for (int32_t r = 0; r < n_reads; ++r)   // the reads back to back, whatever their order and gaps in the caller's buffer
-            if (read_lens[r] > 0)
-                SD_HIP(hipMemcpyAsync(c.text.p + off[(size_t)r], text + read_off[r], (size_t)read_lens[r], hipMemcpyHostToDevice, st));
+        const std::vector<int64_t> off = reads_upload(c.text, st, text, read_off, read_lens, n_reads);
         dp_tables(c, st, j, c.text.p, off.data(), read_lens, n_reads, k, W, B, (uint32_t)M, rc, windows);
         const size_t nw = (size_t)windows, nc = (size_t)j.cells;
         c.out.alloc(2 * nw + 2 * nc);

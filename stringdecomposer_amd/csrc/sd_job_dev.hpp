@@ -1,7 +1,8 @@
 // sd_job_dev.hpp -- internal to libsd_hip.so: the host-side frame that the analyses on final rows, segments and reads share
-// (sd_lags.hip, sd_heat.hip, sd_autocorr.hip, sd_split.hip, sd_dotplot.hip).  Header-only, no kernel: per-device work areas
-// kept between calls, the argument checks and their texts, the read tables, the stream of a host-memory call and the timed
-// repetitions of a bench entry.  DESIGN.md, "The frame of an analysis", says who owns what.
+// (sd_lags.hip, sd_heat.hip, sd_autocorr.hip, sd_split.hip, sd_dotplot.hip; sd_hits_job.hpp for the two motif searches).
+// Header-only, no kernel: per-device work areas kept between calls, the argument checks and their texts, the read tables,
+// the upload of a host-memory call's reads, the stream of such a call and the timed repetitions of a bench entry.
+// DESIGN.md, "The frame of an analysis", says who owns what.
 #pragma once
 
 #include <map>
@@ -123,6 +124,19 @@ inline int reads_text_args(const char* who, const void* text, const int64_t* rea
     }
     if ((bases > 0 && !text) || no_output) { set_err(errbuf, errlen, std::string(who) + ": missing argument"); return SD_ERR_PARAM; }
     return SD_OK;
+}
+
+// The reads of a host-memory call up into dst on st, back to back, whatever their order and gaps in the caller's buffer
+// -> where each lies in dst (n_reads + 1: the last entry is the bases of all)
+inline std::vector<int64_t> reads_upload(DevBuf<uint8_t>& dst, hipStream_t st, const char* text, const int64_t* read_off, const int64_t* read_lens,
+                                         int32_t n_reads) {
+    std::vector<int64_t> off((size_t)n_reads + 1, 0);
+    for (int32_t r = 0; r < n_reads; ++r) off[(size_t)r + 1] = off[(size_t)r] + read_lens[r];
+    dst.alloc((size_t)off[(size_t)n_reads]);
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_lens[r] > 0)
+            SD_HIP(hipMemcpyAsync(dst.p + off[(size_t)r], text + read_off[r], (size_t)read_lens[r], hipMemcpyHostToDevice, st));
+    return off;
 }
 
 // ---- a call on final rows in device memory: the reads as [roff | rlen | toff] and their text back to back ----------------

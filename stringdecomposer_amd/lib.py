@@ -1547,29 +1547,88 @@ def motif_info():
     return _info(load().sd_motif_info, ("tile", "pattern_block", "launch_work", "launches"))
 
 
-def motif_text(text, read_off, read_lens, motifs, E=0, device=None, threads=1):
-    """motif on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any order
-    of offsets are allowed) -> formats.Motifs"""
+# ---- the two hit searches, motif and motif_edits: one implementation of each call, parameterised by a _HitSearch
+# (csrc/sd_hits_job.hpp is the same frame on the other side of the C-ABI).  c: the prefix of the C functions; dtype: the hit
+# record; result / device_result: the classes of formats and of this module the calls return; request(who, motifs, budget)
+# -> (names, patterns), the request checked as the search checks it
+_HitSearch = namedtuple("_HitSearch", "c dtype result device_result request")
+
+
+def _hits_array(s, buf, n):
+    import numpy as np
+    return np.frombuffer(buf, dtype=s.dtype()).copy() if n else np.zeros(0, dtype=s.dtype())
+
+
+def _hits_text(s, who, text, read_off, read_lens, motifs, budget, device, threads):
     import numpy as np
     from . import formats
-    names, patterns, _ = motif_compile(motifs, E)
+    names, patterns = s.request(who, motifs, budget)
     L = load()
-    tb, ro, rl = _text_reads("motif", text, read_off, read_lens)
+    tb, ro, rl = _text_reads(who, text, read_off, read_lens)
     per = np.zeros((len(rl), len(names), 2), dtype=np.int64)
     out, n = C.c_void_p(0), C.c_int64(0)
     err = _err()
-    if device is None:
-        rc = L.sd_motif_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(threads),
-                             C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
-    else:
-        rc = L.sd_motif_dev(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E, int(device),
-                            C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
-    _text_check(rc, err)
+    fn, where = (getattr(L, s.c + "_host"), int(threads)) if device is None else (getattr(L, s.c + "_dev"), int(device))
+    _text_check(fn(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), budget, where,
+                   C.byref(out), C.byref(n), per.ctypes.data, err, 1024), err)
     try:
-        hits = np.frombuffer(C.string_at(out.value, 16 * n.value), dtype=motif_hit_dtype()).copy() if n.value else np.zeros(0, dtype=motif_hit_dtype())
+        hits = _hits_array(s, C.string_at(out.value, 16 * n.value), n.value)
     finally:
         L.sd_free(out)
-    return formats.Motifs(hits, per, names, patterns, E)
+    return getattr(formats, s.result)(hits, per, names, patterns, budget)
+
+
+class _DeviceHits:
+    """what DeviceMotifs and DeviceMotifEdits share: (hits, per, n_hits, names, patterns, budget) and the way to the host"""
+    __slots__ = ()
+
+    def to_host(self):
+        """-> formats.Motifs / formats.MotifEdits (waits for the device)"""
+        from . import formats
+        s = _HIT_SEARCH[self._search]
+        return getattr(formats, s.result)(_hits_array(s, self.hits.cpu().numpy().tobytes(), self.n_hits), self.per.cpu().numpy(),
+                                          self.names, self.patterns, self[5])
+
+
+def _hits_device(s, who, reads, motifs, budget, stream, hits, per):
+    names, patterns = s.request(who, motifs, budget)
+    L = load()
+    torch, dev, st = _device_frame(reads.device, stream)
+    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
+        ev = torch.cuda.Event()
+        ev.record(_torch_stream(torch, dev, reads.stream))
+        st.wait_event(ev)
+    nm = len(names)
+    if per is None:
+        with torch.cuda.stream(st):
+            per = torch.empty((reads.n, nm, 2), dtype=torch.int64, device=dev)
+    elif per.dtype != torch.int64 or per.numel() != reads.n * nm * 2 or per.device != dev or not per.is_contiguous():
+        raise SdError(SD_ERR_PARAM, "%s: per must be a contiguous int64 tensor of %d x %d x 2 elements on %s" % (who, reads.n, nm, dev))
+    lead = (C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, _strs(patterns), nm, budget, dev.index or 0, C.c_void_p(st.cuda_stream))
+    n = C.c_int64(0)
+    err = _err()
+    _text_check(getattr(L, s.c + "_reads_size_dev")(*lead, _dptr(per), C.byref(n), err, 1024), err)
+    if hits is None:
+        with torch.cuda.stream(st):
+            hits = torch.empty((n.value, 16), dtype=torch.uint8, device=dev)
+    elif hits.dtype != torch.uint8 or hits.device != dev or not hits.is_contiguous():
+        raise SdError(SD_ERR_PARAM, "%s: hits must be a contiguous uint8 tensor on %s" % (who, dev))
+    _text_check(getattr(L, s.c + "_reads_write_dev")(*lead, _dptr(hits), hits.numel() // 16, err, 1024), err)
+    return s.device_result(hits.view(-1)[:16 * n.value].view(n.value, 16), per.view(reads.n, nm, 2), int(n.value), names, patterns, budget)
+
+
+def _hits_kernel_bench(s, who, reads, motifs, budget, device, warmup, reps):
+    names, patterns = s.request(who, motifs, budget)
+    text, ro, rl = _reads_text(reads)
+    return _bench(getattr(load(), s.c + "_kernel_bench"), (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), budget,
+                                                           int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
+                  ("launches", "items", "hits", "words"), reps)
+
+
+def motif_text(text, read_off, read_lens, motifs, E=0, device=None, threads=1):
+    """motif on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any order
+    of offsets are allowed) -> formats.Motifs"""
+    return _hits_text(_HIT_SEARCH["motif"], "motif", text, read_off, read_lens, motifs, E, device, threads)
 
 
 def motif(reads, motifs, E=0, device=None, threads=1):
@@ -1583,19 +1642,12 @@ def motif(reads, motifs, E=0, device=None, threads=1):
     return motif_text(text, ro, rl, motifs, E, device, threads)
 
 
-class DeviceMotifs(namedtuple("DeviceMotifs", "hits per n_hits names patterns E")):
+class DeviceMotifs(_DeviceHits, namedtuple("DeviceMotifs", "hits per n_hits names patterns E")):
     """The motif hits of a DeviceReads in device memory (motif_device): hits = uint8 [n_hits, 16], the sd_motif_hit records
     in canonical order; per = int64 [reads, motifs, 2]; torch tensors on the reads' device.  names, patterns, E: the request
     they answer."""
     __slots__ = ()
-
-    def to_host(self):
-        """-> formats.Motifs (waits for the device)"""
-        import numpy as np
-        from . import formats
-        raw = self.hits.cpu().numpy()
-        hits = np.frombuffer(raw.tobytes(), dtype=motif_hit_dtype()).copy() if self.n_hits else np.zeros(0, dtype=motif_hit_dtype())
-        return formats.Motifs(hits, self.per.cpu().numpy(), self.names, self.patterns, self.E)
+    _search = "motif"
 
 
 def motif_device(reads, motifs, E=0, stream=None, hits=None, per=None):
@@ -1603,44 +1655,12 @@ def motif_device(reads, motifs, E=0, stream=None, hits=None, per=None):
     DeviceMotifs(hits, per, n_hits, ...).  torch allocates the results on `stream` (None: the device's current stream) -- or hits (uint8, at least
     16 bytes per hit) and per (int64, reads x motifs x 2) are used, whatever they hold -- and the library fills them there.
     The host waits once, for the number of hits; the call returns with the write kernels in flight."""
-    names, patterns, _ = motif_compile(motifs, E)
-    import torch
-    L = load()
-    dev = torch.device("cuda", reads.device)
-    st = _torch_stream(torch, dev, stream)
-    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
-        ev = torch.cuda.Event()
-        ev.record(_torch_stream(torch, dev, reads.stream))
-        st.wait_event(ev)
-    nm = len(names)
-    with torch.cuda.stream(st):
-        if per is None:
-            per = torch.empty((reads.n, nm, 2), dtype=torch.int64, device=dev)
-        elif per.dtype != torch.int64 or per.numel() != reads.n * nm * 2 or per.device != dev or not per.is_contiguous():
-            raise SdError(SD_ERR_PARAM, "motif_device: per must be a contiguous int64 tensor of %d x %d x 2 elements on %s" % (reads.n, nm, dev))
-    pats = _strs(patterns)
-    n = C.c_int64(0)
-    err = C.create_string_buffer(1024)
-    dptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else 0)
-    _text_check(L.sd_motif_reads_size_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, E, dev.index or 0,
-                                          C.c_void_p(st.cuda_stream), dptr(per), C.byref(n), err, 1024), err)
-    if hits is None:
-        with torch.cuda.stream(st):
-            hits = torch.empty((n.value, 16), dtype=torch.uint8, device=dev)
-    elif hits.dtype != torch.uint8 or hits.device != dev or not hits.is_contiguous():
-        raise SdError(SD_ERR_PARAM, "motif_device: hits must be a contiguous uint8 tensor on %s" % (dev,))
-    _text_check(L.sd_motif_reads_write_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, E, dev.index or 0,
-                                           C.c_void_p(st.cuda_stream), dptr(hits), hits.numel() // 16, err, 1024), err)
-    return DeviceMotifs(hits.view(-1)[:16 * n.value].view(n.value, 16), per.view(reads.n, nm, 2), int(n.value), names, patterns, E)
+    return _hits_device(_HIT_SEARCH["motif"], "motif_device", reads, motifs, E, stream, hits, per)
 
 
 def motif_kernel_bench(reads, motifs, E=0, device=0, warmup=2, reps=5):
     """sd_motif_kernel_bench -> {"prep_ms", "size_ms", "write_ms": [...], "launches", "items", "hits", "words"}."""
-    names, patterns, _ = motif_compile(motifs, E)
-    text, ro, rl = _reads_text(reads)
-    return _bench(load().sd_motif_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), E,
-                                                 int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
-                  ("launches", "items", "hits", "words"), reps)
+    return _hits_kernel_bench(_HIT_SEARCH["motif"], "motif_kernel_bench", reads, motifs, E, device, warmup, reps)
 
 
 MOTIF_KMAX = 7
@@ -1665,11 +1685,6 @@ def motif_edits_request(motifs, K, who):
     return names, patterns
 
 
-def _motif_edit_hits(buf, n):
-    import numpy as np
-    return np.frombuffer(buf, dtype=motif_edit_hit_dtype()).copy() if n else np.zeros(0, dtype=motif_edit_hit_dtype())
-
-
 def motif_edits_info():
     """sd_motif_edit_info -> {"stretch": consecutive ends a lane owns, "tile": words of a workgroup's tile (256 stretches),
     "pattern_block": pattern-strands a workgroup takes, "launch_work": the most end x pattern-strand products of one launch,
@@ -1680,26 +1695,7 @@ def motif_edits_info():
 def motif_edits_text(text, read_off, read_lens, motifs, K, device=None, threads=1):
     """motif_edits on reads given as one buffer with offsets and lengths, as the C-ABI takes them (gaps, padding and any
     order of offsets are allowed) -> formats.MotifEdits"""
-    import numpy as np
-    from . import formats
-    names, patterns = motif_edits_request(motifs, K, "motif_edits")
-    L = load()
-    tb, ro, rl = _text_reads("motif_edits", text, read_off, read_lens)
-    per = np.zeros((len(rl), len(names), 2), dtype=np.int64)
-    out, n = C.c_void_p(0), C.c_int64(0)
-    err = _err()
-    if device is None:
-        rc = L.sd_motif_edit_host(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K, int(threads),
-                                  C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
-    else:
-        rc = L.sd_motif_edit_dev(tb or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K, int(device),
-                                 C.byref(out), C.byref(n), per.ctypes.data, err, 1024)
-    _text_check(rc, err)
-    try:
-        hits = _motif_edit_hits(C.string_at(out.value, 16 * n.value), n.value)
-    finally:
-        L.sd_free(out)
-    return formats.MotifEdits(hits, per, names, patterns, K)
+    return _hits_text(_HIT_SEARCH["motif_edits"], "motif_edits", text, read_off, read_lens, motifs, K, device, threads)
 
 
 def motif_edits(reads, motifs, K, device=None, threads=1):
@@ -1714,16 +1710,11 @@ def motif_edits(reads, motifs, K, device=None, threads=1):
     return motif_edits_text(text, ro, rl, motifs, K, device, threads)
 
 
-class DeviceMotifEdits(namedtuple("DeviceMotifEdits", "hits per n_hits names patterns K")):
+class DeviceMotifEdits(_DeviceHits, namedtuple("DeviceMotifEdits", "hits per n_hits names patterns K")):
     """The edit hits of a DeviceReads in device memory (motif_edits_device): hits = uint8 [n_hits, 16], the
     sd_motif_edit_hit records in canonical order; per = int64 [reads, motifs, 2]; torch tensors on the reads' device."""
     __slots__ = ()
-
-    def to_host(self):
-        """-> formats.MotifEdits (waits for the device)"""
-        from . import formats
-        return formats.MotifEdits(_motif_edit_hits(self.hits.cpu().numpy().tobytes(), self.n_hits), self.per.cpu().numpy(), self.names,
-                                  self.patterns, self.K)
+    _search = "motif_edits"
 
 
 def motif_edits_device(reads, motifs, K, stream=None, hits=None, per=None):
@@ -1732,41 +1723,18 @@ def motif_edits_device(reads, motifs, K, stream=None, hits=None, per=None):
     -- or hits (uint8, at least 16 bytes per hit) and per (int64, reads x motifs x 2) are used, whatever they hold -- and
     the library fills them there.  The host waits once, for the number of hits; the call returns with the write kernels in
     flight."""
-    names, patterns = motif_edits_request(motifs, K, "motif_edits_device")
-    L = load()
-    torch, dev, st = _device_frame(reads.device, stream)
-    if reads.stream != st.cuda_stream:   # the reads' bytes were produced on another stream: st waits for it
-        ev = torch.cuda.Event()
-        ev.record(_torch_stream(torch, dev, reads.stream))
-        st.wait_event(ev)
-    nm = len(names)
-    if per is None:
-        with torch.cuda.stream(st):
-            per = torch.empty((reads.n, nm, 2), dtype=torch.int64, device=dev)
-    elif per.dtype != torch.int64 or per.numel() != reads.n * nm * 2 or per.device != dev or not per.is_contiguous():
-        raise SdError(SD_ERR_PARAM, "motif_edits_device: per must be a contiguous int64 tensor of %d x %d x 2 elements on %s" % (reads.n, nm, dev))
-    pats = _strs(patterns)
-    n = C.c_int64(0)
-    err = _err()
-    _text_check(L.sd_motif_edit_reads_size_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, K, dev.index or 0,
-                                               C.c_void_p(st.cuda_stream), _dptr(per), C.byref(n), err, 1024), err)
-    if hits is None:
-        with torch.cuda.stream(st):
-            hits = torch.empty((n.value, 16), dtype=torch.uint8, device=dev)
-    elif hits.dtype != torch.uint8 or hits.device != dev or not hits.is_contiguous():
-        raise SdError(SD_ERR_PARAM, "motif_edits_device: hits must be a contiguous uint8 tensor on %s" % (dev,))
-    _text_check(L.sd_motif_edit_reads_write_dev(C.c_void_p(reads.ptr), reads.c_off, reads.c_lens, reads.n, pats, nm, K, dev.index or 0,
-                                                C.c_void_p(st.cuda_stream), _dptr(hits), hits.numel() // 16, err, 1024), err)
-    return DeviceMotifEdits(hits.view(-1)[:16 * n.value].view(n.value, 16), per.view(reads.n, nm, 2), int(n.value), names, patterns, K)
+    return _hits_device(_HIT_SEARCH["motif_edits"], "motif_edits_device", reads, motifs, K, stream, hits, per)
 
 
 def motif_edits_kernel_bench(reads, motifs, K, device=0, warmup=2, reps=5):
     """sd_motif_edit_kernel_bench -> {"prep_ms", "size_ms", "write_ms": [...], "launches", "items", "hits", "words"}."""
-    names, patterns = motif_edits_request(motifs, K, "motif_edits_kernel_bench")
-    text, ro, rl = _reads_text(reads)
-    return _bench(load().sd_motif_edit_kernel_bench, (text or b"N", ro.ctypes.data, rl.ctypes.data, len(rl), _strs(patterns), len(names), K,
-                                                      int(device), int(warmup), int(reps)), ("prep_ms", "size_ms", "write_ms"),
-                  ("launches", "items", "hits", "words"), reps)
+    return _hits_kernel_bench(_HIT_SEARCH["motif_edits"], "motif_edits_kernel_bench", reads, motifs, K, device, warmup, reps)
+
+
+_HIT_SEARCH = {
+    "motif": _HitSearch("sd_motif", motif_hit_dtype, "Motifs", DeviceMotifs, lambda who, motifs, E: motif_compile(motifs, E)[:2]),
+    "motif_edits": _HitSearch("sd_motif_edit", motif_edit_hit_dtype, "MotifEdits", DeviceMotifEdits, lambda who, motifs, K: motif_edits_request(motifs, K, who)),
+}
 
 
 # ---- cyclic pairs and the merge of seed monomers (csrc/sd_cyclic.hpp holds the rule) ---------------------------------------

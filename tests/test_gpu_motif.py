@@ -246,6 +246,13 @@ def test_the_device_resident_form():
     hostper = np.zeros(hosts[0].per.size, dtype=np.int64)
     rc = L.sd_motif_reads_size_dev(*args, C.c_void_p(hostper.ctypes.data), C.byref(n), err, 512)
     assert rc == lib.SD_ERR_PARAM and b"not in device memory" in err.value
+    # a write call for another budget than the size call's is refused, and writes nothing
+    assert L.sd_motif_reads_size_dev(*args, C.c_void_p(per.data_ptr()), C.byref(n), err, 512) == lib.SD_OK and n.value == len(hosts[0].hits)
+    other = (C.c_void_p(dr.ptr), dr.c_off, dr.c_lens, dr.n, pats, len(names), 2, 0, None)
+    rc = L.sd_motif_reads_write_dev(*other, C.c_void_p(hits.data_ptr()), n.value, err, 512)
+    assert rc == lib.SD_ERR_PARAM and b"was not for these reads and motifs" in err.value
+    torch.cuda.synchronize()
+    assert (hits == 0x55).all()
 
 
 # ---- the command line --------------------------------------------------------------------------------------------------

@@ -290,6 +290,58 @@ def test_the_device_resident_form():
     assert rc == lib.SD_ERR_PARAM and b"was not for these reads and motifs" in err.value
 
 
+def test_the_two_searches_keep_separate_work_areas():
+    """The Hamming search (sd_motif_*) and the edit search each have a work area of their own on a device: a size call of
+    the one neither disturbs what the other's size call left nor answers for the other's write call."""
+    rng = random.Random(21)
+    motifs, budget = ["cenpb", "tel=TTAGGG"], 1
+    names, patterns = lib.motif_request(motifs)
+    pats = lib._strs(patterns)
+    L = lib.load()
+    err = C.create_string_buffer(512)
+
+    def device_reads(seed_offset):
+        reads = [text_of(rng, n) for n in (300, 0, 64 * lib.MOTIF_TILE_WORDS + 65, 64)]
+        for r in (0, 2):
+            inst = one_edit(rng, CENPB.replace("N", "C"), (r + seed_offset) % 3)[0]
+            reads[r] = plant(reads[r], len(reads[r]) - len(inst), inst)
+        width = max(len(s) for s in reads) + 13
+        rows = np.frombuffer(("".join(s + "A" * (width - len(s)) for s in reads)).encode(), dtype=np.uint8).reshape(len(reads), width)
+        dr = lib.DeviceReads(torch.from_numpy(rows.copy()).to("cuda:0"), [len(s) for s in reads])
+        return reads, dr, (C.c_void_p(dr.ptr), dr.c_off, dr.c_lens, dr.n, pats, len(names), budget, 0, None)
+
+    reads_a, dr_a, args_a = device_reads(0)
+    reads_b, dr_b, args_b = device_reads(1)
+    host_h = lib.motif(reads_a, motifs, budget, threads=THREADS)
+    host_e = lib.motif_edits(reads_a, motifs, budget, threads=THREADS)
+    assert len(host_h.hits) > 0 and len(host_e.hits) > 0
+    per_h = torch.full(host_h.per.shape, 77, dtype=torch.int64, device="cuda:0")
+    per_e = torch.full(host_e.per.shape, 77, dtype=torch.int64, device="cuda:0")
+    n_h, n_e = C.c_int64(0), C.c_int64(0)
+    torch.cuda.synchronize()
+    # both size calls on A, then both write calls: the edit size call left the Hamming work area as it was
+    assert L.sd_motif_reads_size_dev(*args_a, C.c_void_p(per_h.data_ptr()), C.byref(n_h), err, 512) == lib.SD_OK, err.value
+    assert L.sd_motif_edit_reads_size_dev(*args_a, C.c_void_p(per_e.data_ptr()), C.byref(n_e), err, 512) == lib.SD_OK, err.value
+    assert n_h.value == len(host_h.hits) and n_e.value == len(host_e.hits)
+    hits_h = torch.full((n_h.value, 16), 0x55, dtype=torch.uint8, device="cuda:0")
+    hits_e = torch.full((n_e.value, 16), 0x55, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    assert L.sd_motif_reads_write_dev(*args_a, C.c_void_p(hits_h.data_ptr()), n_h.value, err, 512) == lib.SD_OK, err.value
+    assert L.sd_motif_edit_reads_write_dev(*args_a, C.c_void_p(hits_e.data_ptr()), n_e.value, err, 512) == lib.SD_OK, err.value
+    torch.cuda.synchronize()
+    assert hits_h.cpu().numpy().tobytes() == host_h.hits.tobytes() and (per_h.cpu().numpy() == host_h.per).all()
+    assert hits_e.cpu().numpy().tobytes() == host_e.hits.tobytes() and (per_e.cpu().numpy() == host_e.per).all()
+    # the edit search sized on A, the Hamming search on B: the Hamming size call does not answer for an edit write call on B
+    assert L.sd_motif_edit_reads_size_dev(*args_a, C.c_void_p(per_e.data_ptr()), C.byref(n_e), err, 512) == lib.SD_OK, err.value
+    assert L.sd_motif_reads_size_dev(*args_b, C.c_void_p(per_h.data_ptr()), C.byref(n_h), err, 512) == lib.SD_OK, err.value
+    blank = torch.full((max(n_e.value, n_h.value) + 64, 16), 0x55, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    rc = L.sd_motif_edit_reads_write_dev(*args_b, C.c_void_p(blank.data_ptr()), blank.shape[0], err, 512)
+    assert rc == lib.SD_ERR_PARAM and b"was not for these reads and motifs" in err.value
+    torch.cuda.synchronize()
+    assert (blank == 0x55).all()   # nothing written
+
+
 # ---- the command line --------------------------------------------------------------------------------------------------
 OPTS = ["--motif", "cenpb", "--motif-edits", "1"]
 OURS = ("final_decomposition_motif.tsv", "final_decomposition_motif_rows.tsv", "final_decomposition_motif_monomers.tsv")

@@ -1,9 +1,12 @@
-// motif_edit_host_check.cpp -- a stand-alone run of the host form of --motif-edits (sd_motif_edit_host) on the
+// motif_edit_host_check.cpp -- a stand-alone run of the host forms of --motif-edits and --motif (sd_motif_edit_host,
+// sd_motif_host: both through the host frame of csrc/sd_hits_job.hpp and the plane build of csrc/sd_autocorr.hpp) on the
 // boundary-length cases, for a sanitizer build of the host code: reads of 0, 1, L - K - 1, L - K, L, 63, 64, 65 bases and a
-// lane's stretch +- 1, patterns of 6, 17, 32, 33 and 64 codes, K = 0, 1, 3, 7, a hit at the first and at the last base.
-// Build (no GPU needed; only sd_motif_edit.hip is instrumented, the other objects come from the normal build):
-//   hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -c sd_motif_edit.hip -o /tmp/me_san.o
-//   clang++ -fsanitize=address,undefined -I../include tools/motif_edit_host_check.cpp /tmp/me_san.o <the other _obj/*.o> -L$ROCM/lib -lamdhip64 -lpthread
+// lane's stretch +- 1, patterns of 6, 17, 32, 33 and 64 codes, K = E = 0, 1, 3, 7, a hit at the first and at the last base.
+// Build (no GPU needed; the two motif units and sd_autocorr.hip, whose host form builds its planes the same way, are
+// instrumented, the other objects come from the normal build):
+//   for u in sd_motif sd_motif_edit sd_autocorr; do
+//     hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -c $u.hip -o /tmp/${u}_san.o; done
+//   clang++ -fsanitize=address,undefined -I../include tools/motif_edit_host_check.cpp /tmp/sd_*_san.o <the other _obj/*.o> -L$ROCM/lib -lamdhip64 -lpthread
 // Prints the hits per case and "ok"; the sanitizers report on stderr and fail the run.
 #include <cstdio>
 #include <cstdlib>
@@ -32,10 +35,11 @@ int main() {
             for (char c : p) inst += c == 'R' ? 'G' : c == 'Y' ? 'C' : c == 'S' ? 'G' : c == 'W' ? 'T' : c == 'N' ? "ACGTn"[rnd(5)] : c;
             std::string text;
             std::vector<int64_t> off, len;
-            int r = 0;
+            int r = 0, with_instance = 0;
             for (int n : {0, 1, L - K - 1, L - K, L, 63, 64, 65, stretch - 1, stretch, stretch + 1}) {
                 std::string s;
                 for (int i = 0; i < n; ++i) s += "ACGTNa"[rnd(6)];
+                with_instance += n >= L;
                 if (n >= L) s.replace(r % 2 ? (size_t)(n - L) : 0, (size_t)L, inst);   // at the last base, or at the first
                 text += "TTCGAAAA";   // a gap of bases that would match if they were read
                 off.push_back((int64_t)text.size());
@@ -55,6 +59,18 @@ int main() {
             std::printf("L %2d K %d: %lld hits\n", L, K, (long long)n_hits);
             all += n_hits;
             sd_free(hits);
+            sd_motif_hit* mh = nullptr;   // the Hamming search on the same reads, E = K
+            const int rm = sd_motif_host(text.c_str(), off.data(), len.data(), (int32_t)len.size(), pats, K < 7 ? 2 : 1, K, 3, &mh, &n_hits, per.data(), err, sizeof err);
+            if (rm != SD_OK) { std::fprintf(stderr, "L %d E %d: rc %d %s\n", L, K, rm, err); return 1; }
+            int64_t planted = 0;
+            for (int64_t i = 0; i < n_hits; ++i) {
+                if (mh[i].start < 0 || mh[i].start + (mh[i].motif ? 12 : L) > len[(size_t)mh[i].read]) { std::fprintf(stderr, "a hit outside its read\n"); return 1; }
+                planted += mh[i].motif == 0 && mh[i].strand == 0 && mh[i].mismatches == 0;
+            }
+            if (planted < with_instance) { std::fprintf(stderr, "L %d E %d: %lld of the planted instances found\n", L, K, (long long)planted); return 1; }
+            std::printf("L %2d E %d: %lld hits\n", L, K, (long long)n_hits);
+            all += n_hits;
+            sd_free(mh);
         }
     std::printf("ok, %lld hits\n", (long long)all);
     return all > 0 ? 0 : 1;
